@@ -2,12 +2,14 @@
 """Audit of compiled kernels for SERIALISED vector-memory loads: a load followed (within a few instructions, no other
 load in between) by `s_waitcnt vmcnt(0)` is one exposed memory latency; a kernel with dozens of them in a row has a
 loop that hipcc could not batch (typically `cond ? ptr[i] : 0` or `if (cond) v += ptr[i]` inside an unrolled loop).
-usage: asm_serial_loads.py file.hip [kernel-name-regex]     (device-only compile to assembly, like kernel_regs.sh)"""
+usage: asm_serial_loads.py file.hip [kernel-name-regex]     (device-only compile to assembly, like kernel_regs.sh;
+$MBV_ASM_DIR, default /tmp/asm, receives it)"""
 import re, subprocess, sys, os
 src = sys.argv[1]
 pat = re.compile(sys.argv[2] if len(sys.argv) > 2 else ".")
-out = "/tmp/asm/%s.s" % os.path.basename(src).replace(".hip", "")
-os.makedirs("/tmp/asm", exist_ok=True)
+out_dir = os.environ.get("MBV_ASM_DIR", "/tmp/asm")         # where the assembly is written
+out = os.path.join(out_dir, os.path.basename(src).replace(".hip", "") + ".s")
+os.makedirs(out_dir, exist_ok=True)
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--offload-device-only", "-S", src, "-o", out],
                check=True, stderr=subprocess.DEVNULL)
 name, lines, kernels = None, [], {}

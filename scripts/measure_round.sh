@@ -13,14 +13,14 @@ if [ -z "$2" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/tests_gpu.log 2>&1 || { tail -5 $O/tests_gpu.log; exit 1; }
   tail -1 $O/tests_gpu.log
 fi
-timeout -k 10 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
-MBV_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_n1_force_dist.json 2>> $O/bench_n1.err || exit 1
+timeout -k 10 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
+MBV_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_n1_force_dist.json 2>> $O/bench_n1.err || exit 1
 : > $O/other_configs.jsonl
 for cb in "ljs_ms_istft_vits 64" "uudb_ms_istft_vits_ms 32" "ljs_mini_mb_istft_vits 64" "ljs_istft_vits 64" "ljs_mini_istft_vits 64" "ljs_mb_istft_vits 256"; do
   set -- $cb
-  timeout -k 10 400 python bench.py --config $1 --batch $2 --steps 5 --warmup 2 --no-cpu-baseline >> $O/other_configs.jsonl 2>> $O/bench_n1.err || exit 1
+  timeout -k 10 400 python bench.py --config $1 --batch $2 --steps 5 --warmup 2 --full --no-cpu-baseline >> $O/other_configs.jsonl 2>> $O/bench_n1.err || exit 1
 done
-timeout -k 10 300 python bench.py --ragged --steps 5 --warmup 2 --no-cpu-baseline >> $O/other_configs.jsonl 2>> $O/bench_n1.err || exit 1
+timeout -k 10 300 python bench.py --ragged --steps 5 --warmup 2 --full --no-cpu-baseline >> $O/other_configs.jsonl 2>> $O/bench_n1.err || exit 1
 { echo "== MBV_CONV_SPLITK=0"; MBV_CONV_SPLITK=0 timeout -k 10 200 python scripts/latency_b1.py; echo "== MBV_CONV_SPLITK=1"; MBV_CONV_SPLITK=1 timeout -k 10 200 python scripts/latency_b1.py; } 2>&1 | grep -v amdgpu.ids > $O/latency_b1.txt || exit 1
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python3 $R/scripts/run_infer.py ljs_mb_istft_vits 64 5 > $O/ks.log 2>&1 || exit 1

@@ -10,7 +10,7 @@ for cb in "${CF[@]}"; do
   set -- $cb; cfg=$1; b=$2
   for rep in 1 2; do
     for v in "${VARS[@]}"; do
-      env $v timeout -k 10 300 python bench.py --config $cfg --batch $b --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$cfg B=$b [$v]: %.3f ms/step  conv %.4f' % (d['ms_per_step'], d['roofline_conv']['frac']))" | tee -a $O/cfg_ab.txt
+      env $v timeout -k 10 300 python bench.py --config $cfg --batch $b --steps 5 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$cfg B=$b [$v]: %.3f ms/step  conv %.4f' % (d['ms_per_step'], d['roofline_conv']['frac']))" | tee -a $O/cfg_ab.txt
     done
   done
 done

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-dispatch view of the fused iSTFT+PQMF launch in a rocprofv3 --kernel-trace CSV of `bench.py`:
+"""Per-dispatch view of the fused iSTFT+PQMF launch in a rocprofv3 --kernel-trace CSV of `bench.py --full`:
 the dispatches come in the order [per-step all-outputs launches][1000 untimed warm-up launches]
 [7 x 50 timed waveform-only launches]; prints the averages of each group.
 usage: trace_istft_summary.py <..._kernel_trace.csv>"""

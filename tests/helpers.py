@@ -53,3 +53,49 @@ def thin(name, a):
 def rms(a):
     a = np.asarray(a, np.float64)
     return float(np.sqrt(np.mean(a * a))) if a.size else 0.0
+
+
+class EagerPathReached(AssertionError):
+    pass
+
+
+def ref_stand_in():
+    """What `from models import SynthesizerTrn` gives `reference_binding.bind`, without the reference's source:
+    the ctor attributes it keeps (models.py:602-624), every state-dict entry of the project's key table
+    (`spec.param_shapes`) as a parameter (a buffer for `dec.updown_filter`), a `dec` module, and eager
+    inference methods that raise `EagerPathReached`: a bound class must never fall through to them."""
+    import torch
+    from torch import nn
+
+    class SynthesizerTrn(nn.Module):
+        def __init__(self, cfg, hps_model, n_speakers):
+            super().__init__()
+            self.n_vocab, self.spec_channels = cfg.n_vocab, cfg.spec_channels
+            self.inter_channels, self.hidden_channels = cfg.inter_channels, cfg.hidden_channels
+            self.filter_channels, self.n_heads, self.n_layers = cfg.filter_channels, cfg.n_heads, cfg.n_layers
+            self.kernel_size, self.upsample_initial_channel = cfg.kernel_size, cfg.upsample_initial_channel
+            self.resblock, self.resblock_kernel_sizes = hps_model["resblock"], hps_model["resblock_kernel_sizes"]
+            self.resblock_dilation_sizes = hps_model["resblock_dilation_sizes"]
+            self.n_speakers, self.gin_channels = n_speakers, hps_model.get("gin_channels", 0)
+            self.use_sdp = hps_model.get("use_sdp", False)
+            self.ms_istft_vits = hps_model.get("ms_istft_vits", False)
+            self.mb_istft_vits = hps_model.get("mb_istft_vits", False)
+            for name, shape in mspec.param_shapes(cfg).items():
+                node, parts = self, name.split(".")
+                for part in parts[:-1]:
+                    if part not in node._modules:
+                        node.add_module(part, nn.Module())
+                    node = node._modules[part]
+                t = torch.zeros(*shape)
+                if name == "dec.updown_filter":
+                    node.register_buffer(parts[-1], t)
+                else:
+                    node.register_parameter(parts[-1], nn.Parameter(t, requires_grad=False))
+            self.dec.forward = self._eager
+
+        def _eager(self, *a, **k):
+            raise EagerPathReached("the reference's eager modules were called")
+
+        infer = infer_z_only = voice_conversion = _eager
+
+    return SynthesizerTrn

@@ -26,9 +26,10 @@ BUDGET = {
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 @pytest.mark.parametrize("src", sorted(BUDGET))
-def test_no_serialised_loads(src):
+def test_no_serialised_loads(src, tmp_path):
     pat, budget = BUDGET[src]
-    r = subprocess.run([sys.executable, TOOL, os.path.join(CSRC, src), pat], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, TOOL, os.path.join(CSRC, src), pat], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, MBV_ASM_DIR=str(tmp_path)))
     assert r.returncode == 0, r.stderr[-2000:]
     rows = re.findall(r"^(\S+)\s+loads\s+(\d+)\s+single load -> vmcnt\(0\):\s+(\d+)", r.stdout, re.M)
     assert rows, "the audit printed no kernel for %s:\n%s" % (src, r.stdout[-2000:])

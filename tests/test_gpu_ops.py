@@ -329,37 +329,11 @@ def test_reference_side_binding_runs_against_golden():
     has the REFERENCE's constructor attributes and state-dict keys (here a parameter-only stand-in
     built from the key table — the reference's own models.py does not travel to the GPU box) and
     must reproduce the reference's `mini_b1` / `uudb_b2` goldens."""
-    from torch import nn
-    from helpers import load_fixture, config_for, rms, FIXTURES
-    from mb_istft_vits_amd import synth, spec as mspec
+    from helpers import load_fixture, config_for, rms, FIXTURES, ref_stand_in
+    from mb_istft_vits_amd import synth
     from mb_istft_vits_amd.reference_binding import bind
 
-    class RefStandIn(nn.Module):                    # what `from models import SynthesizerTrn` gives: ctor attrs + parameters
-        def __init__(self, cfg, hps_model, n_speakers):
-            super().__init__()
-            self.n_vocab, self.spec_channels = cfg.n_vocab, cfg.spec_channels
-            self.inter_channels, self.hidden_channels = cfg.inter_channels, cfg.hidden_channels
-            self.filter_channels, self.n_heads, self.n_layers = cfg.filter_channels, cfg.n_heads, cfg.n_layers
-            self.kernel_size, self.upsample_initial_channel = cfg.kernel_size, cfg.upsample_initial_channel
-            self.resblock, self.resblock_kernel_sizes = hps_model["resblock"], hps_model["resblock_kernel_sizes"]
-            self.resblock_dilation_sizes = hps_model["resblock_dilation_sizes"]
-            self.n_speakers, self.gin_channels = n_speakers, hps_model.get("gin_channels", 0)
-            self.use_sdp = hps_model.get("use_sdp", False)
-            self.ms_istft_vits = hps_model.get("ms_istft_vits", False)
-            self.mb_istft_vits = hps_model.get("mb_istft_vits", False)
-            for name, shape in mspec.param_shapes(cfg).items():
-                node, parts = self, name.split(".")
-                for part in parts[:-1]:
-                    if part not in node._modules:
-                        node.add_module(part, nn.Module())
-                    node = node._modules[part]
-                t = torch.zeros(*shape)
-                if name == "dec.updown_filter":
-                    node.register_buffer(parts[-1], t)
-                else:
-                    node.register_parameter(parts[-1], nn.Parameter(t, requires_grad=False))
-
-    Bound = bind(RefStandIn)
+    Bound = bind(ref_stand_in())
     for fx in ("mini_b1", "uudb_b2"):
         gold = load_fixture(fx)
         hps, cfg = config_for(FIXTURES[fx], int(gold["n_vocab"]))

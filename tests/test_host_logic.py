@@ -149,6 +149,32 @@ def test_bench_flop_model_matches_survey():
     assert bench.ISTFT_BYTES_PER_FRAME == 5632
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """`--full` is off by default, `--steps` must be at least 1, and `--dump-outputs` writes float arrays:
+    small ones whole, large ones as the same seeded sample every time, under 64 MB for a whole batch-64 dump."""
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 0, False, None)
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    big = torch.arange(5 * (bench.DUMP_MAX_VALUES // 4), dtype=torch.float32).reshape(5, -1)
+    small = torch.randn(3, 4)
+    ylen = torch.tensor([3, 1], dtype=torch.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "y_lengths": ylen, "absent": None})
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("big", "small", "y_lengths")}
+    assert not (tmp_path / "a" / "absent.npy").exists()
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], small.numpy())
+    assert got["y_lengths"].dtype == np.float64 and got["y_lengths"].tolist() == [3.0, 1.0]
+    s = got["big"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_MAX_VALUES,)
+    assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < big.numel()       # distinct, sorted flat positions
+    assert np.array_equal(s, np.load(str(tmp_path / "b" / "big.npy")))        # the same sample every time
+    assert (len(bench.OUTPUT_NAMES) + 1) * bench.DUMP_MAX_VALUES * 4 <= 64e6   # float32 (y_lengths: a value per utterance)
+
+
 def test_graft_entry_build_runs_without_gpu():
     """`__graft_entry__.build()` is the driver's does-it-build check on the CPU container."""
     import __graft_entry__ as g
@@ -243,53 +269,37 @@ def test_wire_framing_matches_the_service_wrapper():
 
 
 def test_reference_binding_binds_the_real_reference_class():
-    """`reference_binding.bind` over the REAL `/root/reference/models.SynthesizerTrn` (build container only —
-    the reference does not travel to the GPU box, where this test skips): construct through the reference's
-    own ctor and hparams, strict `load_state_dict` of the synthetic checkpoint, every inference entry point of
-    the class is the binding's, `model.dec` is routed, and with no GPU the calls raise instead of falling
-    back to the reference's eager CPU modules.  Runs in a child process: importing the reference needs
-    `sys.modules` stubs and a `.cuda()` no-op (tests/golden/make_golden.py) that must not leak into this one."""
-    import subprocess
-    import sys
-    ref = os.environ.get("MBV_REFERENCE", "/root/reference")
-    if not os.path.isfile(os.path.join(ref, "models.py")):
-        pytest.skip("reference checkout not present (GPU box)")
-    code = r"""
-import os, sys
-sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests", "golden"))
-import torch
-import make_golden
-models, utils, stft, pqmf = make_golden.import_reference()
-from mb_istft_vits_amd import synth, spec
-from mb_istft_vits_amd.reference_binding import bind
-Bound = bind(models.SynthesizerTrn)
-assert Bound.__name__ == "SynthesizerTrn" and issubclass(Bound, models.SynthesizerTrn)
-for name in ("infer", "infer_z_only", "voice_conversion", "decode"):
-    assert name in Bound.__dict__, name
-for cfg_name in ("ljs_mini_mb_istft_vits", "uudb_ms_istft_vits_ms"):
-    hps = utils.get_hparams_from_file(os.path.join(make_golden.REF, "configs", cfg_name + ".json"))
-    net = Bound(59, hps.data.filter_length // 2 + 1, hps.train.segment_size // hps.data.hop_length,
-                n_speakers=hps.data.n_speakers, **hps.model).eval()
-    cfg = spec.config_from_ctor(59, hps.data.filter_length // 2 + 1, hps.train.segment_size // hps.data.hop_length,
-                                n_speakers=hps.data.n_speakers, **hps.model)
-    sd = synth.make_state_dict(cfg, 1234)
-    missing, unexpected = net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    assert not missing and not unexpected
-    x, xl = torch.randint(1, 59, (2, 9)), torch.tensor([9, 7])
-    sid = torch.tensor([0, 1]) if hps.data.n_speakers else None
-    for call in (lambda: net.infer(x, xl, sid=sid, noise_scale=0), lambda: net.infer_z_only(x, xl, sid=sid),
-                 lambda: net.dec(torch.zeros(1, hps.model["inter_channels"], 8)),
-                 lambda: net.decode(torch.zeros(1, hps.model["inter_channels"], 8))):
-        try:
-            call()
-        except RuntimeError as e:
-            assert "no CPU path" in str(e), e
-        else:
-            raise AssertionError("a CPU call went through: the binding fell back to the reference's modules")
-print("BOUND-OK")
-""" % (ROOT, ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "BOUND-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    """`reference_binding.bind` over the reference class as the binding sees it (`helpers.ref_stand_in`: the
+    ctor attributes of models.py:602-624 and every state-dict entry, from the project's key table; the reference's
+    source is not part of this repository): strict `load_state_dict` of the synthetic checkpoint, every inference
+    entry point of the class is the binding's, `model.dec` is routed, and with no GPU the calls raise instead of
+    falling back to the class's eager modules."""
+    from helpers import EagerPathReached, ref_stand_in
+    from mb_istft_vits_amd.reference_binding import bind
+    Ref = ref_stand_in()
+    Bound = bind(Ref)
+    assert Bound.__name__ == "SynthesizerTrn" and issubclass(Bound, Ref)
+    for name in ("infer", "infer_z_only", "voice_conversion", "decode"):
+        assert name in Bound.__dict__, name
+    for cfg_name in ("ljs_mini_mb_istft_vits", "uudb_ms_istft_vits_ms"):
+        hps, cfg = config_for(cfg_name)
+        net = Bound(cfg, dict(hps.model), hps.data.n_speakers).eval()
+        sd = synth.make_state_dict(cfg, 1234)
+        missing, unexpected = net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        assert not missing and not unexpected
+        x, xl = torch.randint(1, 59, (2, 9)), torch.tensor([9, 7])
+        sid = torch.tensor([0, 1]) if hps.data.n_speakers else None
+        for call in (lambda: net.infer(x, xl, sid=sid, noise_scale=0), lambda: net.infer_z_only(x, xl, sid=sid),
+                     lambda: net.dec(torch.zeros(1, hps.model["inter_channels"], 8)),
+                     lambda: net.decode(torch.zeros(1, hps.model["inter_channels"], 8))):
+            try:
+                call()
+            except EagerPathReached:
+                raise AssertionError("a CPU call went through: the binding fell back to the reference's modules")
+            except RuntimeError as e:
+                assert "no CPU path" in str(e), e
+            else:
+                raise AssertionError("a CPU call returned without a GPU")
 
 
 def test_integration_md_quotes_the_shipped_binding_verbatim():

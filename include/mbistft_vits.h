@@ -256,6 +256,46 @@ int mbv_istft_finalize(mbv_model *m, const float *spec, const float *phase, int 
 int mbv_pcm16(mbv_model *m, const float *wave, const int64_t *y_lengths, int B, int64_t stride,
               int auto_normalize, int16_t *pcm, void *stream);
 
+/* The same with the valid length of every row given in samples rather than frames, for rows that are no
+ * longer 256 samples per frame (the output of mbv_resample):
+ *   valid_samples  int64 [B] device (clamped to [0, stride]; the out_samples of mbv_resample), or NULL */
+int mbv_pcm16_samples(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t stride,
+                      int auto_normalize, int16_t *pcm, void *stream);
+
+/* ---- resampling -----------------------------------------------------------------
+ * replaces librosa.resample(audio, orig_sr=model_sr, target_sr=rate) of the service wrapper
+ * (tts_vits.py:199-200), librosa 0.9.2 (requirements_py39.txt:2): res_type "kaiser_best" (its default) or
+ * "kaiser_fast", i.e. resampy's windowed-sinc interpolator followed by fix_length to ceil(n * target / orig)
+ * samples.  Computed as a polyphase FIR (target / orig = L / M in lowest terms, L phases of K fp32 taps)
+ * whose bank restates resampy's float64 table arithmetic and is rounded to fp32 once; parity is pinned to
+ * that restatement (tests/resample_ref.py), not to the library.  Every row is resampled as if alone
+ * (zeros outside [0, valid)).  Refused: L > 4096 phases, K > 4096 taps, or an input window per 256 outputs
+ * beyond 64 KiB of LDS (downsampling by more than about 60x).
+ *   wave           fp32 [B, 1, in_stride] device
+ *   valid_samples  int64 [B] device, clamped to [0, in_stride]; NULL = every row is in_stride samples
+ *   filter         MBV_RESAMPLE_KAISER_BEST / MBV_RESAMPLE_KAISER_FAST
+ *   out            fp32 [B, 1, out_stride] device; row b holds int(n_b * ratio) resampled samples
+ *                  (ratio = (double)target_sr / orig_sr, n_b its valid input samples), zeros after them
+ *   out_samples    int64 [B] device, optional: min(ceil(n_b * ratio), out_stride) computed in fp64 as
+ *                  librosa does, the length of the row after fix_length.  out_stride =
+ *                  ceil(in_stride * ratio) holds every row.
+ * The first call for a rate pair and filter builds the bank on the host and uploads it with a synchronous
+ * copy (cached in the handle); later calls only enqueue one kernel.  Needs no weights. */
+#define MBV_RESAMPLE_KAISER_BEST 0   /* num_zeros 64, precision 9, Kaiser beta 14.769656459379492, rolloff 0.9475937167399596 */
+#define MBV_RESAMPLE_KAISER_FAST 1   /* num_zeros 16, precision 9, Kaiser beta 8.555504641634386, rolloff 0.85 */
+int mbv_resample(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t in_stride,
+                 int orig_sr, int target_sr, int filter, float *out, int64_t out_stride, int64_t *out_samples,
+                 void *stream);
+/* Host only (no handle, no GPU): the fp32 bank mbv_resample uses for a rate pair, [phases + 1][taps]
+ * row-major, phases = L = target / gcd(orig, target), M = orig / gcd.  Row r < L weighs x[floor(t * M / L)
+ * - left + k] (tap k) for every output t with (t * M) mod L == r; row L (fraction 1) weighs
+ * x[t * M / L - 1 - left + k] instead of row 0 for the outputs t > 0 whose fp64 time t / ratio rounds
+ * below the integer t * M / L (resampy then interpolates from the sample before).
+ * dst == NULL only queries phases / taps / left (any of them may be NULL).  On failure the message is
+ * available from mbv_last_error(NULL). */
+int mbv_resample_bank(int orig_sr, int target_sr, int filter, float *dst, int64_t capacity, int32_t *phases,
+                      int32_t *taps, int32_t *left);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"

@@ -19,6 +19,7 @@ SYMBOLS = [
     "mbv_speaker_embedding", "mbv_stage_times_ms", "mbv_istft_pqmf", "mbv_read_stage",
     "mbv_op_conv1d", "mbv_kernel_times_ms", "mbv_istft_finalize", "mbv_pcm16", "mbv_voice_conversion",
     "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
+    "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank",
 ]
 
 
@@ -91,6 +92,10 @@ def lib():
     L.mbv_istft_finalize.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.mbv_voice_conversion.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(MbvOutputs), vp, vp]
     L.mbv_pcm16.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp]
+    L.mbv_pcm16_samples.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp]
+    L.mbv_resample.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
+    L.mbv_resample_bank.argtypes = [i32, i32, i32, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32)]
     L.mbv_set_option.argtypes = [vp, C.c_char_p, i32]
     L.mbv_ticket.argtypes = [vp]
     L.mbv_ticket.restype = C.c_int64

@@ -4,6 +4,7 @@
 #include "../../include/mbistft_vits.h"
 #include "kernels.h"
 
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -96,6 +97,8 @@ struct mbv_model {
   char* scrB = nullptr; size_t scrB_bytes = 0;
   float* user_tab = nullptr;   // polyphase table of the stand-alone mbv_istft_pqmf entry
   unsigned* peak_buf = nullptr; int peak_cap = 0;   // per-utterance peaks of mbv_pcm16
+  struct ResampleBank { float* d = nullptr; ResampleGeom g{}; };
+  std::map<std::array<int, 3>, ResampleBank> resample_banks;   // (L, M, filter) -> fp32 bank on the device (mbv_resample)
   bool user_tab_is_pqmf = false;
   int xpost_F = 1;             // frames per row of the last x_post stage tensor
   int xpost_rows = 72;         // 72 (4 bands x 18) or 18 (single band)
@@ -1432,6 +1435,7 @@ void mbv_destroy(mbv_model* m) {
   if (m->scrB) (void)hipFree(m->scrB);
   if (m->user_tab) (void)hipFree(m->user_tab);
   if (m->peak_buf) (void)hipFree(m->peak_buf);
+  for (auto& kv : m->resample_banks) (void)hipFree(kv.second.d);
   if (m->ev_ok) { for (auto& set : m->evr) for (auto& e : set) if (e) (void)hipEventDestroy(e); for (auto& e : m->evk) (void)hipEventDestroy(e); }
   if (m->aux_ok) {
     for (auto& st : m->aux) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -1975,6 +1979,73 @@ int mbv_pcm16(mbv_model* m, const float* wave, const int64_t* y_lengths, int B, 
   }
   launch_pcm16(wave, y_lengths, B, stride, 256, auto_normalize, m->peak_buf, reinterpret_cast<short*>(pcm),
                (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_pcm16_samples(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t stride,
+                      int auto_normalize, int16_t* pcm, void* stream) {
+  if (!m) return 1;
+  if (!wave || !pcm || B <= 0 || stride <= 0) return m->fail("mbv_pcm16_samples: bad arguments");
+  if (B > 65535) return m->fail("mbv_pcm16_samples: more than 65535 rows");
+  DEVICE_GUARD(m);
+  if (m->peak_cap < B) {
+    if (m->peak_buf) HIPCHK(m, hipFree(m->peak_buf));
+    HIPCHK(m, hipMalloc((void**)&m->peak_buf, (size_t)B * sizeof(unsigned)));
+    m->peak_cap = B;
+  }
+  launch_pcm16(wave, valid_samples, B, stride, 1, auto_normalize, m->peak_buf, reinterpret_cast<short*>(pcm),
+               (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_resample_bank(int orig_sr, int target_sr, int filter, float* dst, int64_t capacity, int32_t* phases,
+                      int32_t* taps, int32_t* left) {
+  ResampleGeom g{};
+  std::vector<float> bank;
+  const char* why = resample_bank(orig_sr, target_sr, filter, dst ? &bank : nullptr, &g);
+  if (why) { g_create_error = std::string("mbv_resample_bank: ") + why; return 1; }
+  if (phases) *phases = g.L;
+  if (taps) *taps = g.K;
+  if (left) *left = g.left;
+  if (dst) {
+    if (capacity < (int64_t)bank.size()) { g_create_error = "mbv_resample_bank: capacity too small"; return 1; }
+    std::memcpy(dst, bank.data(), bank.size() * sizeof(float));
+  }
+  return 0;
+}
+
+int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
+                 int orig_sr, int target_sr, int filter, float* out, int64_t out_stride, int64_t* out_samples,
+                 void* stream) {
+  if (!m) return 1;
+  if (!wave || !out || B <= 0 || in_stride <= 0 || out_stride <= 0) return m->fail("mbv_resample: bad arguments");
+  if (B > 65535) return m->fail("mbv_resample: more than 65535 rows");
+  if ((out_stride + kResampleTile - 1) / kResampleTile > 0x7fffffff) return m->fail("mbv_resample: out_stride too large");
+  int L = 0, M = 0;
+  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("mbv_resample: sample rates must be positive");
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
+    return m->fail("mbv_resample: unknown filter %d", filter);
+  if ((double)out_stride * M >= 0x1p62) return m->fail("mbv_resample: out_stride * M overflows the 64-bit time index");
+  DEVICE_GUARD(m);
+  const std::array<int, 3> key{L, M, filter};
+  auto it = m->resample_banks.find(key);
+  if (it == m->resample_banks.end()) {
+    // first call for this pair: build on the host, upload once (synchronous copy)
+    mbv_model::ResampleBank rb;
+    std::vector<float> bank;
+    const char* why = resample_bank(orig_sr, target_sr, filter, &bank, &rb.g);
+    if (why) return m->fail("mbv_resample(%d -> %d): %s", orig_sr, target_sr, why);
+    HIPCHK(m, hipMalloc((void**)&rb.d, bank.size() * sizeof(float)));
+    if (hipMemcpy(rb.d, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(rb.d);
+      return m->fail("mbv_resample: uploading the filter bank failed");
+    }
+    it = m->resample_banks.emplace(key, rb).first;
+  }
+  launch_resample(wave, valid_samples, B, in_stride, it->second.d, it->second.g, out, out_stride, out_samples,
+                  (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace mbv {
 
 // ---------------------------------------------------------------- conv1d (MFMA)
@@ -248,6 +250,31 @@ void launch_unscale_xpost(const float* src, float* dst, int B, int rows, int F, 
 // float waveform -> int16 PCM (normalise / clip / scale), tts_vits.py:204-217
 void launch_pcm16(const float* x, const int64_t* lens, int B, int64_t stride, int spf, int auto_normalize,
                   unsigned* peak_scratch, short* out, hipStream_t s);
+
+// ---------------------------------------------------------------- resampling (resample.hip)
+// librosa.resample(kaiser_best | kaiser_fast) as a polyphase FIR: target / orig = L / M in lowest terms,
+// output t reads x[floor(t M / L) - left + k], k < K, with the fp32 weights bank[(t M) mod L][k]; bank row L
+// (fraction 1, read from floor(t M / L) - 1) serves the r = 0 outputs whose float64 time t / ratio rounds below
+// the integer (resample.hip).
+constexpr int kResampleTile = 256;             // outputs per workgroup (one per thread)
+constexpr int kResampleMaxPhases = 4096;       // cap on L
+constexpr int kResampleMaxTaps = 4096;         // cap on K
+constexpr int kResampleMaxLdsFloats = 16384;   // cap on the staged input window (64 KiB)
+struct ResampleGeom {
+  int L, M;          // target / orig in lowest terms
+  int K;             // taps per phase (a multiple of 4; trailing taps zero)
+  int left;          // taps left of n_t: tap k reads x[n_t - left + k]
+  double ratio;      // float(target) / orig, as resampy and librosa compute it
+};
+inline int64_t resample_lds_floats(const ResampleGeom& g) {
+  return (int64_t)(kResampleTile - 1) * g.M / g.L + 2 + g.K;
+}
+int resample_reduce(int orig_sr, int target_sr, int* L, int* M);
+// host: the float64 bank rounded to fp32, [L + 1][K] (bank may be null to get the geometry alone).
+// Returns null on success, else the reason the pair is refused.
+const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<float>* bank, ResampleGeom* geom);
+void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
+                     const ResampleGeom& g, float* out, int64_t out_stride, int64_t* out_samples, hipStream_t s);
 
 // z = (m + noise * exp(logs)) * mask   (PosteriorEncoder, models.py:245); stats = [B, 2I, T]
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,

@@ -1,0 +1,205 @@
+// Band-limited resampling of waveform rows: librosa 0.9.2 `resample(res_type="kaiser_best" | "kaiser_fast")`,
+// i.e. resampy's windowed-sinc interpolator followed by librosa's fix_length (tts_vits.py:199-200).
+//
+// resampy places output t at the float64 input time t / ratio and evaluates its interpolation table
+// there.  With target / orig = L / M in lowest terms that time is t M / L: output t reads around
+// n_t = floor(t M / L) with fractional phase r = (t M) mod L, so only L distinct weight vectors exist.
+// The host builds them once (float64, resampy's arithmetic: table lookup with linear interpolation, the
+// truncated index step int(scale * 2^precision)), rounds them to fp32 and the kernel is a plain
+// polyphase FIR: out[t] = sum_k bank[r][k] * x[n_t - left + k], K taps per phase.
+// One case does not follow from t M / L: at r = 0 the float64 quotient t / ratio can round to just
+// below the integer n_t, and resampy then interpolates from n_t - 1 at fraction ~1.  When downsampling
+// that is not the same filter (the index step is truncated), so the bank has a row L for it: phase
+// fraction 1, read around n_t - 1.  The kernel evaluates t / ratio in fp64 for r = 0 to pick the row.
+//
+// Parity is with a restatement of resampy's algorithm (tests/resample_ref.py), not with the library:
+// its filter tables are rebuilt from the documented specs here.
+#include "kernels.h"
+
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+namespace mbv {
+
+namespace {
+
+struct FilterSpec { int num_zeros, precision; double beta, rolloff; };
+// resampy's filter specs (kaiser_best / kaiser_fast)
+const FilterSpec kSpecs[2] = {
+    {64, 9, 14.769656459379492, 0.9475937167399596},
+    {16, 9, 8.555504641634386, 0.85},
+};
+
+// modified Bessel function of the first kind, order 0: the power series (all terms positive, no cancellation)
+double bessel_i0(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < sum * 1e-17) break;
+  }
+  return sum;
+}
+
+double sinc(double x) {
+  if (x == 0.0) return 1.0;
+  const double px = M_PI * x;
+  return std::sin(px) / px;
+}
+
+int64_t gcd64(int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; }
+
+}  // namespace
+
+int resample_reduce(int orig_sr, int target_sr, int* L, int* M) {
+  if (orig_sr <= 0 || target_sr <= 0) return 1;
+  const int64_t g = gcd64(orig_sr, target_sr);
+  *L = (int)(target_sr / g);
+  *M = (int)(orig_sr / g);
+  return 0;
+}
+
+const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<float>* bank, ResampleGeom* geom) {
+  if (orig_sr <= 0 || target_sr <= 0) return "sample rates must be positive";
+  if (filter != 0 && filter != 1) return "unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
+  ResampleGeom g{};
+  resample_reduce(orig_sr, target_sr, &g.L, &g.M);
+  if (g.L > kResampleMaxPhases)
+    return "rate pair needs more than 4096 polyphase phases (target / gcd(orig, target) > 4096)";
+  const FilterSpec& f = kSpecs[filter];
+  const int nb = 1 << f.precision;
+  const int n = nb * f.num_zeros;
+  const int nwin = n + 1;
+  // win = kaiser(2n + 1, beta)[n:] * rolloff * sinc(rolloff * linspace(0, num_zeros, n + 1))
+  std::vector<double> win(nwin), delta(nwin);
+  const double alpha = (double)n;            // (2n + 1 - 1) / 2
+  const double i0b = bessel_i0(f.beta);
+  for (int i = 0; i < nwin; ++i) {
+    const double u = (double)i / alpha;      // (j - alpha) / alpha for j = n + i
+    const double kw = bessel_i0(f.beta * std::sqrt(1.0 - u * u)) / i0b;
+    const double x = (double)i * ((double)f.num_zeros / (double)n);
+    win[i] = kw * (f.rolloff * sinc(f.rolloff * x));
+  }
+  const double ratio = (double)target_sr / (double)orig_sr;
+  if (ratio < 1.0)
+    for (auto& w : win) w *= ratio;
+  for (int i = 0; i + 1 < nwin; ++i) delta[i] = win[i + 1] - win[i];
+  delta[nwin - 1] = 0.0;
+  const double scale = ratio < 1.0 ? ratio : 1.0;
+  const int step = (int)(scale * nb);        // truncation as resampy's int(scale * num_table)
+  if (step < 1) return "downsampling ratio too small for the filter table";
+
+  // one wing of resampy's loop at fractional position `frac`: count and (offset, eta) into the table
+  struct Wing { int off, count; double eta; };
+  auto wing = [&](double frac) {
+    const double idx = frac * nb;
+    Wing w;
+    w.off = (int)idx;
+    w.eta = idx - w.off;
+    w.count = (nwin - w.off) / step;
+    return w;
+  };
+  // row r < L: fraction r / L;  row L: fraction 1 (the r = 0 output reached from below, read around n_t - 1)
+  int lmax = 0, rmax = 0;
+  for (int r = 0; r <= g.L; ++r) {
+    const double frac = scale * ((double)r / (double)g.L);
+    const Wing a = wing(frac), b = wing(scale - frac);
+    if (a.count > lmax) lmax = a.count;
+    if (b.count > rmax) rmax = b.count;
+  }
+  g.left = lmax - 1;                         // left wing: x[n - i], i < lmax
+  g.K = (g.left + 1 + rmax + 3) / 4 * 4;     // right wing: x[n + 1 + k], k < rmax; padded to whole float4 rows
+  if (g.K > kResampleMaxTaps) return "rate pair needs more than 4096 taps per phase (downsampling ratio too small)";
+  if (resample_lds_floats(g) > kResampleMaxLdsFloats) return "rate pair needs an input window larger than the LDS stage";
+  g.ratio = ratio;
+  if (bank) {
+    bank->assign((size_t)(g.L + 1) * g.K, 0.f);
+    std::vector<double> row(g.K);
+    for (int r = 0; r <= g.L; ++r) {
+      std::fill(row.begin(), row.end(), 0.0);
+      const double frac = scale * ((double)r / (double)g.L);
+      const Wing a = wing(frac), b = wing(scale - frac);
+      for (int i = 0; i < a.count; ++i) {
+        const int j = a.off + i * step;
+        row[g.left - i] = win[j] + a.eta * delta[j];
+      }
+      for (int k = 0; k < b.count; ++k) {
+        const int j = b.off + k * step;
+        row[g.left + 1 + k] = win[j] + b.eta * delta[j];
+      }
+      for (int k = 0; k < g.K; ++k) (*bank)[(size_t)r * g.K + k] = (float)row[k];
+    }
+  }
+  *geom = g;
+  return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Kernel: one workgroup = kResampleTile consecutive outputs of one row, one output per thread.  The input
+// window they read (with the K-tap halo) is staged in LDS, zero outside [0, valid): resampy's
+// min(n + 1, ...) / min(n_in - n - 1, ...) edge rule, every row resampled as if it were alone.
+// Outputs in [int(n ratio), out_stride) are written as zeros (librosa's fix_length pad and the row padding).
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kResampleTile)
+resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
+                const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                float* __restrict__ out, int64_t out_stride, int64_t* __restrict__ out_samples) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  int64_t n = in_stride;
+  if (valid) {
+    n = valid[b];
+    n = n < 0 ? 0 : (n > in_stride ? in_stride : n);
+  }
+  int64_t n_out = (int64_t)((double)n * ratio);          // resampy: int(n_in * sample_ratio)
+  if (n_out > out_stride) n_out = out_stride;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && out_samples) {
+    int64_t keep = (int64_t)ceil((double)n * ratio);     // librosa fix_length: int(np.ceil(n * ratio))
+    out_samples[b] = keep > out_stride ? out_stride : keep;
+  }
+  const int64_t t0 = (int64_t)blockIdx.x * kResampleTile;
+  const int64_t t = t0 + threadIdx.x;
+  float* ob = out + (int64_t)b * out_stride;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: tail only
+    if (t < out_stride) ob[t] = 0.f;
+    return;
+  }
+  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
+  const int64_t j0 = (t0 * M) / L - left - 1;              // - 1: room for row L (reads around n_t - 1)
+  const int W = (int)((t_last * M) / L - left + K - j0);  // <= resample_lds_floats(geom), checked on the host
+  const float* xb = x + (int64_t)b * in_stride;
+  for (int i = threadIdx.x; i < W; i += kResampleTile) {
+    const int64_t j = j0 + i;
+    xs[i] = (j >= 0 && j < n) ? xb[j] : 0.f;
+  }
+  __syncthreads();
+  if (t >= out_stride) return;
+  if (t >= n_out) { ob[t] = 0.f; return; }
+  const int64_t q = t * M;
+  int64_t nt = q / L;
+  int r = (int)(q - nt * L);
+  if (r == 0 && t > 0 && (double)t / ratio < (double)nt) { r = L; --nt; }   // resampy: int(t / ratio) = n_t - 1
+  const float4* w4 = reinterpret_cast<const float4*>(bank + (size_t)r * K);
+  const float* xw = xs + (nt - left - j0);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int k = 0; k < K / 4; ++k) {
+    const float4 w = w4[k];
+    a0 = fmaf(w.x, xw[4 * k + 0], a0);
+    a1 = fmaf(w.y, xw[4 * k + 1], a1);
+    a2 = fmaf(w.z, xw[4 * k + 2], a2);
+    a3 = fmaf(w.w, xw[4 * k + 3], a3);
+  }
+  ob[t] = (a0 + a1) + (a2 + a3);
+}
+
+void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
+                     const ResampleGeom& g, float* out, int64_t out_stride, int64_t* out_samples, hipStream_t s) {
+  const int64_t bx = (out_stride + kResampleTile - 1) / kResampleTile;
+  const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)bx, B), dim3(kResampleTile), lds, s, x, valid, in_stride,
+                     bank, g.L, g.M, g.K, g.left, g.ratio, out, out_stride, out_samples);
+}
+
+}  // namespace mbv

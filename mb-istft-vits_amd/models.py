@@ -8,6 +8,7 @@ but every forward computation happens in the gfx950 kernels behind
 stream and the RNG only.  The training-side `forward` is out of scope and raises.
 """
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -16,6 +17,9 @@ from torch import nn
 
 from . import _capi
 from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
+
+# librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
+RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
 
 _STAGES = ("text_encoder", "duration_predictor", "alignment_and_projection", "flow",
            "waveform_decoder")
@@ -537,22 +541,86 @@ class SynthesizerTrn(nn.Module):
         return o
 
     @torch.no_grad()
-    def to_pcm16(self, wave, y_lengths=None, auto_normalize=True):
+    def to_pcm16(self, wave, y_lengths=None, auto_normalize=True, valid_samples=None):
         """Waveform [B, 1, n] -> int16 PCM [B, n] on the GPU: the normalise / clip / *32767 /
         astype(int16) sequence of the service wrapper (tts_vits.py:204-217), per utterance over
-        its valid 256 * y_lengths samples (rest zero).  Bit-exact with the NumPy code."""
+        its valid 256 * y_lengths samples (rest zero).  Bit-exact with the NumPy code.
+        `valid_samples` (int64 [B], e.g. the lengths `resample` returns) gives the valid length in
+        samples instead; it excludes `y_lengths`."""
         h = self._ensure_handle()
         dev = self._device()
         wave = wave.to(device=dev, dtype=torch.float32).contiguous()
         B, n = wave.shape[0], wave.shape[-1]
+        pcm = torch.empty(B, n, device=dev, dtype=torch.int16)
+        if valid_samples is not None:
+            if y_lengths is not None:
+                raise ValueError("to_pcm16: give y_lengths (frames) or valid_samples (samples), not both")
+            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).contiguous()
+            if valid_samples.shape != (B,):
+                raise ValueError("valid_samples must be [B]")
+            with torch.cuda.device(dev):
+                _capi.check(h, _capi.lib().mbv_pcm16_samples(h, self._ptr(wave), self._ptr(valid_samples), B, n,
+                                                             int(bool(auto_normalize)), self._ptr(pcm),
+                                                             self._stream()),
+                            "mbv_pcm16_samples")
+            return pcm
         if y_lengths is not None:
             y_lengths = y_lengths.to(device=dev, dtype=torch.int64).contiguous()
-        pcm = torch.empty(B, n, device=dev, dtype=torch.int16)
         with torch.cuda.device(dev):
             _capi.check(h, _capi.lib().mbv_pcm16(h, self._ptr(wave), self._ptr(y_lengths), B, n,
                                                  int(bool(auto_normalize)), self._ptr(pcm), self._stream()),
                         "mbv_pcm16")
         return pcm
+
+    @torch.no_grad()
+    def resample(self, wave, orig_sr, target_sr, y_lengths=None, valid_samples=None, res_type="kaiser_best"):
+        """Waveform [B, 1, n] at `orig_sr` -> (out [B, 1, ceil(n * target_sr / orig_sr)], out_samples int64 [B])
+        on the GPU: `librosa.resample(row, orig_sr=orig_sr, target_sr=target_sr)` of librosa 0.9.2 for every
+        row over its valid samples (tts_vits.py:199-200; res_type "kaiser_best", its default, or
+        "kaiser_fast": resampy's interpolator + fix_length).  out_samples[b] = ceil(n_b * target / orig) is the
+        length librosa returns for row b; the rest of the row is zero.  Valid input samples come from
+        `y_lengths` (frames, x256, clamped to the row, negative -> 0, as in `to_pcm16`) or `valid_samples`
+        (samples); neither = whole rows.  Equal rates return `wave` and the lengths unchanged.  No host
+        synchronisation, except on the first call for a rate pair (the filter bank is built and uploaded).
+        Parity is pinned to a float64 restatement of resampy's algorithm, not to the library itself."""
+        filt = RESAMPLE_TYPES.get(res_type)
+        if filt is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        orig_sr, target_sr = int(orig_sr), int(target_sr)
+        if orig_sr <= 0 or target_sr <= 0:
+            raise ValueError("sample rates must be positive")
+        if y_lengths is not None and valid_samples is not None:
+            raise ValueError("resample: give y_lengths (frames) or valid_samples (samples), not both")
+        h = self._ensure_handle()
+        dev = self._device()
+        if wave.dim() != 3 or wave.shape[1] != 1:
+            raise ValueError("wave must be [B, 1, samples]")
+        B, n = wave.shape[0], wave.shape[-1]
+        if y_lengths is not None:
+            valid_samples = (y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
+        elif valid_samples is not None:
+            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).clamp(0, n).contiguous()
+        if valid_samples is not None and valid_samples.shape != (B,):
+            raise ValueError("y_lengths / valid_samples must be [B]")
+        if orig_sr == target_sr:
+            if valid_samples is None:
+                valid_samples = torch.full((B,), n, device=dev, dtype=torch.int64)
+            return wave, valid_samples
+        wave = wave.to(device=dev, dtype=torch.float32).contiguous()
+        n_out = int(math.ceil(n * (float(target_sr) / orig_sr)))
+        out = torch.empty(B, 1, max(n_out, 1), device=dev, dtype=torch.float32)
+        out_samples = torch.empty(B, device=dev, dtype=torch.int64)
+        if n == 0 or B == 0:
+            out.zero_()
+            out_samples.zero_()
+            return out[..., :n_out], out_samples
+        with torch.cuda.device(dev):
+            _capi.check(h, _capi.lib().mbv_resample(h, self._ptr(wave), self._ptr(valid_samples), B, n, orig_sr,
+                                                    target_sr, filt, self._ptr(out), out.shape[-1],
+                                                    self._ptr(out_samples), self._stream()),
+                        "mbv_resample")
+        return out, out_samples
 
     @torch.no_grad()
     def _speaker_embedding(self, sid):

@@ -3,10 +3,13 @@ utterance is cut into frames of `round(frame_length * rate)` samples (20 ms by d
 tts_vits.py:36-38) and every frame travels as the base64 text of its little-endian bytes
 (tts_vits.py:219-226; the last frame is simply shorter).  Host-side by nature: the payload is text.
 
-Resampling to a target rate (`librosa.resample`, tts_vits.py:199-200) is NOT provided: librosa /
-resampy / soxr are not part of this build, and a resampler of our own could not be pinned to the
-reference's output (parity unpinned) — a caller that needs another rate resamples `o` before
-`to_pcm16`, as the reference does.
+The steps before it run on the GPU: `service_pcm16` chains `SynthesizerTrn.resample` (the
+`librosa.resample` of tts_vits.py:199-200, librosa 0.9.2's default res_type "kaiser_best", i.e.
+resampy's windowed-sinc interpolator and fix_length) with the peak normalise / clip / int16 epilogue
+(tts_vits.py:204-217).  The resampler's parity is pinned to a float64 restatement of resampy's
+algorithm (tests/resample_ref.py), not to librosa / resampy themselves, which are not part of this
+build: its filter tables are rebuilt from resampy's documented filter specs.  librosa >= 0.10
+(the unpinned requirements.txt) defaults to soxr_hq, a different algorithm that is not provided.
 """
 import base64
 
@@ -34,3 +37,16 @@ def frame_pcm16(pcm, rate, frame_length=0.02, valid_samples=None):
         raise ValueError("frame_length * rate must be at least one sample")
     pcm = pcm.astype("<i2", copy=False)                    # ndarray.tobytes() of the reference runs on little-endian hosts
     return [base64.b64encode(pcm[t:t + n].tobytes()).decode("utf-8") for t in range(0, len(pcm), n)]
+
+
+def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best"):
+    """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
+    `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
+      o          fp32 [B, 1, n] waveforms of `net.infer` (device)
+      y_lengths  int64 [B] frames per utterance (valid samples = 256 * y_lengths, clamped to the row),
+                 or None = whole rows
+    -> (pcm int16 [B, n'], valid_samples int64 [B]); row b of `pcm` holds the int16 stream of utterance b
+    in its first valid_samples[b] samples, ready for `frame_pcm16(pcm[b], rate, valid_samples=...)`.
+    No host synchronisation (beyond the first call for a rate pair, see `SynthesizerTrn.resample`)."""
+    wave, valid = net.resample(o, model_sr, rate, y_lengths=y_lengths, res_type=res_type)
+    return net.to_pcm16(wave, auto_normalize=auto_normalize, valid_samples=valid), valid

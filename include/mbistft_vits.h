@@ -319,6 +319,64 @@ int mbv_op_conv1d(mbv_model *m, const float *x, const float *w_host, const float
                   float *y, int B, int Cin, int Cout, int T, int K, int dilation,
                   float in_slope, void *stream);
 
+/* One conv of the decoder's kinds through the launcher the decoder uses (tests): any route, any of the
+ * epilogues below.  Semantics, per utterance b (act = leaky-relu with in_slope, applied after chan_add;
+ * positions outside [0, Tin) and at or past in_lens[b] read as 0):
+ *   kind CONV:   y[co, t] = bias[co] + sum_ci,k w[co, ci, k] act(xp[ci, t + k dil - (K - 1) dil / 2])
+ *                with xp = x, or ReflectionPad1d((1, 0))(x) (Tin + 1 frames) when reflect1;
+ *                STORE: y = relu?(.) * (t < out_lens[b]);  RESID: y = . + res + res_chan_add[b, co];
+ *                RESID_ACC: y = (. + res + res_chan_add[b, co] + accum_in) * out_scale  (accum_in may be y);
+ *   kind CONVT4 / CONVT8: ConvTranspose1d(k 16, stride U, padding (16 - U) / 2) of act(x), T == Tin input
+ *                frames, y [B, Cout, U Tin]; epilogue STORE only.
+ * x DEVICE [B, Cin, x_rstride] (first Tin frames valid), y DEVICE [B, Cout, T] (conv) / [B, Cout, U T] (ConvTranspose).
+ * w HOST in the reference layout: conv [Cout, Cin, K], ConvTranspose [Cin, Cout, 16]; bias HOST [Cout] or NULL.
+ * Weights are packed by the weight loader's own packers.  Allocates, launches on `stream`, synchronises, frees. */
+#define MBV_CONV_KIND_CONV 0
+#define MBV_CONV_KIND_CONVT4 4
+#define MBV_CONV_KIND_CONVT8 8
+#define MBV_CONV_EPI_STORE 0
+#define MBV_CONV_EPI_RESID 1
+#define MBV_CONV_EPI_RESID_ACC 2
+typedef struct mbv_conv_desc {
+  int32_t B, Cin, Cout, Tin, T, K, dil;
+  int32_t x_rstride;              /* elements between channel rows of x (0: Tin) */
+  int32_t kind;                   /* MBV_CONV_KIND_* (ConvTranspose: K and dil are implied) */
+  int32_t epi;                    /* MBV_CONV_EPI_* */
+  float in_slope;                 /* 1: no activation */
+  int32_t relu, reflect1;
+  const int32_t *in_lens;         /* DEVICE [B] or NULL */
+  const int32_t *out_lens;        /* DEVICE [B] or NULL (STORE) */
+  const float *chan_add;          /* DEVICE [B, Cin] or NULL: added to x before the activation */
+  const float *res;               /* DEVICE [B, Cout, T] (RESID, RESID_ACC) */
+  const float *res_chan_add;      /* DEVICE [B, Cout] or NULL */
+  const float *accum_in;          /* DEVICE [B, Cout, T] or NULL (RESID_ACC) */
+  float out_scale;                /* RESID_ACC */
+  const int64_t *trim_lens;       /* HOST [B] or NULL: trimmed launch, column tiles below min(T, trim_lens[b] * trim_num + trim_add) */
+  int32_t trim_num, trim_add;
+  int32_t splitk;                 /* 1: split-K allowed (mbv_op_conv: also when the handle's option "splitk" is on, unless trimmed) */
+  int32_t prec;                   /* 0 exact fp32, 3 split-bf16 (as mbv_set_option "conv_bf16") */
+  int32_t legacy_convt;           /* 1: a ConvTranspose on the stand-alone ConvTranspose kernel (no epilogue options) */
+  int64_t ws_floats;              /* mbv_conv_plan only: the handle's split-K workspace (mbv_op_conv uses its own) */
+  int32_t n_counters;             /* ... and ticket counters */
+} mbv_conv_desc;
+/* plan[8] = route, tile rows, tile columns, threads, input-channel chunk, nb_big, vs_tv, split-K factor
+ * (tile fields 0 on the narrow kernel; see conv1d_plan in csrc/kernels.h) */
+#define MBV_ROUTE_NARROW_M 1
+#define MBV_ROUTE_NARROW_LAUNCH 2
+#define MBV_ROUTE_M64 3
+#define MBV_ROUTE_HALF 4
+#define MBV_ROUTE_SMALL 5
+#define MBV_ROUTE_BIG 6
+#define MBV_ROUTE_SPLIT_BATCH 7
+#define MBV_ROUTE_VS 8
+#define MBV_ROUTE_LEGACY_CONVT 9
+/* plan_out may be NULL. */
+int mbv_op_conv(mbv_model *m, const mbv_conv_desc *d, const float *x, const float *w_host, const float *bias_host,
+                float *y, int32_t *plan_out, void *stream);
+/* Host only (no handle, no GPU): the plan mbv_op_conv would execute for `d` (device pointers are only tested
+ * against NULL).  On failure the message is available from mbv_last_error(NULL). */
+int mbv_conv_plan(const mbv_conv_desc *d, int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

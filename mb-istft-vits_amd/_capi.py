@@ -19,7 +19,7 @@ SYMBOLS = [
     "mbv_speaker_embedding", "mbv_stage_times_ms", "mbv_istft_pqmf", "mbv_read_stage",
     "mbv_op_conv1d", "mbv_kernel_times_ms", "mbv_istft_finalize", "mbv_pcm16", "mbv_voice_conversion",
     "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
-    "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank",
+    "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
 ]
 
 
@@ -42,6 +42,26 @@ class MbvConfig(C.Structure):
 class MbvOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("o", "o_mb", "spec", "phase", "attn", "y_mask", "z", "z_p", "m_p", "logs_p")]
+
+
+class MbvConvDesc(C.Structure):
+    """mbv_conv_desc of include/mbistft_vits.h (mbv_op_conv / mbv_conv_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "Cin", "Cout", "Tin", "T", "K", "dil", "x_rstride", "kind", "epi")] + [
+        ("in_slope", C.c_float), ("relu", C.c_int32), ("reflect1", C.c_int32),
+        ("in_lens", C.c_void_p), ("out_lens", C.c_void_p), ("chan_add", C.c_void_p), ("res", C.c_void_p),
+        ("res_chan_add", C.c_void_p), ("accum_in", C.c_void_p), ("out_scale", C.c_float),
+        ("trim_lens", C.c_void_p), ("trim_num", C.c_int32), ("trim_add", C.c_int32),
+        ("splitk", C.c_int32), ("prec", C.c_int32), ("legacy_convt", C.c_int32),
+        ("ws_floats", C.c_int64), ("n_counters", C.c_int32),
+    ]
+
+
+# MBV_CONV_KIND_* / MBV_CONV_EPI_* / MBV_ROUTE_* of include/mbistft_vits.h
+CONV_KIND_CONV, CONV_KIND_CONVT4, CONV_KIND_CONVT8 = 0, 4, 8
+CONV_EPI_STORE, CONV_EPI_RESID, CONV_EPI_RESID_ACC = 0, 1, 2
+ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS",
+          9: "LEGACY_CONVT"}
+PLAN_FIELDS = ("route", "bm", "bn", "threads", "ck", "nb_big", "vs_tv", "S")
 
 
 def build(force=False, verbose=False):
@@ -108,6 +128,8 @@ def lib():
     L.mbv_read_stage.restype = C.c_int64
     L.mbv_op_rel_attention.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mbv_op_conv1d.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp]
+    L.mbv_op_conv.argtypes = [vp, C.POINTER(MbvConvDesc), vp, vp, vp, vp, C.POINTER(C.c_int32 * 8), vp]
+    L.mbv_conv_plan.argtypes = [C.POINTER(MbvConvDesc), C.POINTER(C.c_int32 * 8)]
     for s in SYMBOLS:
         getattr(L, s)          # AttributeError if the header and the library ever drift
     if L.mbv_abi_version() != ABI_VERSION:

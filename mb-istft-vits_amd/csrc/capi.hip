@@ -369,6 +369,59 @@ inline size_t conv_pack_index(int tap, int ci, int m, int Cin, int Mpad) {
   return ((((size_t)tap * (Cin / 8) + ci / 8) * 2 + (ci & 1)) * Mpad + m) * 4 + ((ci & 7) >> 1);
 }
 
+// w [Cout][Cin][K] (reference layout) -> dst [K * Cin * Mpad] packed; rows[mrow] -> source output channel (or -1 =
+// zero row), cin_map[ci] -> source ci (nullptr: identity)
+void pack_conv_rows(const float* w, int Cin, int K, const int* rows, int M, const int* cin_map, int Mpad, float* dst) {
+  for (int k = 0; k < K; ++k)
+    for (int ci = 0; ci < Cin; ++ci) {
+      const int sci = cin_map ? cin_map[ci] : ci;
+      for (int mrow = 0; mrow < M; ++mrow) {
+        const int co = rows[mrow];
+        dst[conv_pack_index(k, ci, mrow, Cin, Mpad)] = co < 0 ? 0.f : w[((size_t)co * Cin + sci) * K + k];
+      }
+    }
+}
+
+// ConvTranspose1d(k = 16, stride us, padding (16 - us) / 2), w [Cin][Cout][16] (reference layout), for the stand-alone
+// ConvTranspose kernel: dst = Wt[r][j][Cin][Mpad] (kernels.h ConvTArgs), columns >= Cout left as they are
+void pack_convt_phases(const float* w, int Cin, int Cout, int us, int Mpad, float* dst) {
+  const int tpp = 16 / us, pad = (16 - us) / 2;
+  for (int r = 0; r < us; ++r)
+    for (int j = 0; j < tpp; ++j) {
+      const int k = (r + pad) % us + us * j;
+      for (int ci = 0; ci < Cin; ++ci) {
+        float* d = dst + ((size_t)(r * tpp + j) * Cin + ci) * Mpad;
+        for (int co = 0; co < Cout; ++co) d[co] = w[((size_t)ci * Cout + co) * 16 + k];
+      }
+    }
+}
+
+// The same ConvTranspose1d as ONE (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT):
+//   y[co, us m + r] = sum_ci sum_j W[ci][co][kr + us j] x[ci, m + sh_r - j],  kr = (r + pad) % us,
+//   sh_r = (r + pad - kr) / us;  tap tau reads x[m - pl + tau]  ->  j = sh_r + pl - tau, with
+//   pl = tpp - 1 - pad / us  (us 4: 5 taps, pl 2;  us 8: 3 taps, pl 1).
+// Packed rows: groups of 64 = 64/us channels x [first us/2 phases (32 rows) | last us/2 phases
+// (32 rows)], row k of a half = channel k / (us/2), phase k % (us/2).  The last tap is zero for
+// the first half, tap 0 for the second; the kernel skips those MFMAs.
+// dst_w [(16/us + 1) * Cin * Mpad] packed (Mpad >= us * Cout), dst_bias [us * Cout] in row order.
+void pack_convt_rows(const float* w, const float* bias, int Cin, int Cout, int us, int Mpad, float* dst_w,
+                     float* dst_bias) {
+  const int tpp = 16 / us, pad = (16 - us) / 2;
+  const int Mp = us * Cout, PH = us / 2, CG = 32 / PH, Kc = tpp + 1, pl = tpp - 1 - pad / us;
+  for (int row = 0; row < Mp; ++row) {
+    const int grp = row / 64, half = (row % 64) / 32, k = row % 32;
+    const int co = grp * CG + k / PH, r = half * PH + k % PH;
+    const int kr = (r + pad) % us, sh = (r + pad - kr) / us;
+    dst_bias[row] = bias[co];
+    for (int tau = 0; tau < Kc; ++tau) {
+      const int j = sh + pl - tau;
+      for (int ci = 0; ci < Cin; ++ci)
+        dst_w[conv_pack_index(tau, ci, row, Cin, Mpad)] =
+            (j >= 0 && j < tpp) ? w[((size_t)ci * Cout + co) * 16 + kr + us * j] : 0.f;
+    }
+  }
+}
+
 struct Packer {
   mbv_model* m;
   std::vector<float>& a;
@@ -419,15 +472,7 @@ struct Packer {
     PConv p;
     p.M = (int)rows.size(); p.Mpad = (int)align_up(p.M, 128); p.Cin = Cin; p.K = K;
     p.w = alloc((size_t)K * Cin * p.Mpad);
-    for (int k = 0; k < K; ++k)
-      for (int ci = 0; ci < Cin; ++ci) {
-        const int sci = cin_map.empty() ? ci : cin_map[ci];
-        for (int mrow = 0; mrow < p.M; ++mrow) {
-          const int co = rows[mrow];
-          a[p.w + conv_pack_index(k, ci, mrow, Cin, p.Mpad)] =
-              co < 0 ? 0.f : w[((size_t)co * Cin + sci) * K + k];
-        }
-      }
+    pack_conv_rows(w.data(), Cin, K, rows.data(), p.M, cin_map.empty() ? nullptr : cin_map.data(), p.Mpad, &a[p.w]);
     if (bias) {
       const std::vector<int>& br = bias_rows ? *bias_rows : rows;
       p.bias = alloc(br.size());
@@ -791,43 +836,17 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
     U.Cin = (int)sh[0]; U.Cout = (int)sh[1]; U.Mpad = (int)align_up(U.Cout, 64);
     U.w = P.alloc((size_t)16 * U.Cin * U.Mpad);
     const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4;        // stride; k = 16, pad = (16-us)/2
-    const int tpp = 16 / us, pad = (16 - us) / 2;
-    for (int r = 0; r < us; ++r)
-      for (int j = 0; j < tpp; ++j) {
-        const int k = (r + pad) % us + us * j;
-        for (int ci = 0; ci < U.Cin; ++ci) {
-          float* dst = &arena[U.w + ((size_t)(r * tpp + j) * U.Cin + ci) * U.Mpad];
-          for (int co = 0; co < U.Cout; ++co) dst[co] = w[((size_t)ci * U.Cout + co) * 16 + k];
-        }
-      }
+    pack_convt_phases(w.data(), U.Cin, U.Cout, us, U.Mpad, &arena[U.w]);
     U.bias = P.vec(std::string(p) + ".bias").off;
     if ((us == 4 || us == 8) && U.Cout % 32 == 0 && U.Cin % 16 == 0) {
-      // The same ConvTranspose1d as ONE (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT):
-      //   y[co, us m + r] = sum_ci sum_j W[ci][co][kr + us j] x[ci, m + sh_r - j],  kr = (r + pad) % us,
-      //   sh_r = (r + pad - kr) / us;  tap tau reads x[m - pl + tau]  ->  j = sh_r + pl - tau, with
-      //   pl = tpp - 1 - pad / us  (us 4: 5 taps, pl 2;  us 8: 3 taps, pl 1).
-      // Packed rows: groups of 64 = 64/us channels x [first us/2 phases (32 rows) | last us/2 phases
-      // (32 rows)], row k of a half = channel k / (us/2), phase k % (us/2).  The last tap is zero for
-      // the first half, tap 0 for the second; the kernel skips those MFMAs.
-      const int Mp = us * U.Cout, PH = us / 2, CG = 32 / PH, Kc = tpp + 1, pl = tpp - 1 - pad / us;
+      // the same ConvTranspose1d as one (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT, pack_convt_rows)
       PConv pc;
-      pc.M = Mp; pc.Mpad = (int)align_up(Mp, 128); pc.Cin = U.Cin; pc.K = Kc;
-      pc.w = P.alloc((size_t)Kc * U.Cin * pc.Mpad);
-      pc.bias = P.alloc(Mp);
+      pc.M = us * U.Cout; pc.Mpad = (int)align_up(pc.M, 128); pc.Cin = U.Cin; pc.K = 16 / us + 1;
+      pc.w = P.alloc((size_t)pc.K * U.Cin * pc.Mpad);
+      pc.bias = P.alloc(pc.M);
       pc.has_bias = true;
-      const HostTensor& bt = P.t(std::string(p) + ".bias");
-      for (int row = 0; row < Mp; ++row) {
-        const int grp = row / 64, half = (row % 64) / 32, k = row % 32;
-        const int co = grp * CG + k / PH, r = half * PH + k % PH;
-        const int kr = (r + pad) % us, sh = (r + pad - kr) / us;
-        arena[pc.bias + row] = bt.data[co];
-        for (int tau = 0; tau < Kc; ++tau) {
-          const int j = sh + pl - tau;
-          for (int ci = 0; ci < U.Cin; ++ci)
-            arena[pc.w + conv_pack_index(tau, ci, row, U.Cin, pc.Mpad)] =
-                (j >= 0 && j < tpp) ? w[((size_t)ci * U.Cout + co) * 16 + kr + us * j] : 0.f;
-        }
-      }
+      pack_convt_rows(w.data(), P.t(std::string(p) + ".bias").data.data(), U.Cin, U.Cout, us, pc.Mpad, &arena[pc.w],
+                      &arena[pc.bias]);
       m->upc[i] = pc;
     } else {
       m->upc[i] = PConv{};
@@ -2145,6 +2164,192 @@ int mbv_op_conv1d(mbv_model* m, const float* x, const float* w_host, const float
   HIPCHK(m, hipFree(dw));
   if (dws) HIPCHK(m, hipFree(dws));
   if (db) HIPCHK(m, hipFree(db));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- mbv_op_conv / mbv_conv_plan: a descriptor as ConvArgs (shape and options; no weights)
+namespace {
+static_assert(MBV_ROUTE_NARROW_M == CONV_NARROW_M && MBV_ROUTE_NARROW_LAUNCH == CONV_NARROW_LAUNCH &&
+              MBV_ROUTE_M64 == CONV_M64 && MBV_ROUTE_HALF == CONV_HALF && MBV_ROUTE_SMALL == CONV_SMALL &&
+              MBV_ROUTE_BIG == CONV_BIG && MBV_ROUTE_SPLIT_BATCH == CONV_SPLIT_BATCH && MBV_ROUTE_VS == CONV_VS,
+              "route numbers of the C-ABI and the launcher");
+
+// null on success, else why the descriptor is refused
+const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
+  const bool convt = d.kind == MBV_CONV_KIND_CONVT4 || d.kind == MBV_CONV_KIND_CONVT8;
+  if (d.kind != MBV_CONV_KIND_CONV && !convt) return "kind must be MBV_CONV_KIND_CONV, _CONVT4 or _CONVT8";
+  if (d.B <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.Tin <= 0 || d.T <= 0) return "B, Cin, Cout, Tin and T must be > 0";
+  if (d.x_rstride != 0 && d.x_rstride < d.Tin) return "x_rstride must be 0 or >= Tin";
+  if (d.epi < MBV_CONV_EPI_STORE || d.epi > MBV_CONV_EPI_RESID_ACC) return "epi must be STORE, RESID or RESID_ACC";
+  if (d.prec != 0 && d.prec != 3) return "prec must be 0 or 3";
+  if (d.epi == MBV_CONV_EPI_STORE && (d.res || d.res_chan_add)) return "res / res_chan_add need a RESID epilogue";
+  if (d.epi != MBV_CONV_EPI_STORE && !d.res) return "RESID and RESID_ACC need res";
+  if (d.epi != MBV_CONV_EPI_STORE && (d.out_lens || d.relu)) return "out_lens / relu belong to STORE";
+  if (d.epi != MBV_CONV_EPI_RESID_ACC && d.accum_in) return "accum_in belongs to RESID_ACC";
+  if (d.trim_lens && (d.splitk || d.legacy_convt)) return "a trimmed launch takes neither split-K nor the legacy ConvTranspose";
+  const int U = d.kind;
+  if (convt) {
+    if (d.T != d.Tin) return "ConvTranspose: T must equal Tin (input frames)";
+    if (d.epi != MBV_CONV_EPI_STORE || d.out_lens || d.relu || d.reflect1) return "ConvTranspose: plain STORE only";
+    if (d.legacy_convt) {
+      if (d.Cin % 8 || d.x_rstride > d.Tin || d.in_lens || d.chan_add || d.splitk || d.prec)
+        return "legacy ConvTranspose: Cin % 8 == 0, contiguous x, no in_lens / chan_add / splitk / prec";
+    } else if (d.Cin % 16 || d.Cout % 32) {
+      return "ConvTranspose: Cin % 16 == 0 and Cout % 32 == 0";
+    }
+  } else {
+    if (d.legacy_convt) return "legacy_convt is a ConvTranspose option";
+    if (d.Cin % 32) return "conv: Cin must be a multiple of 32";
+    if (!conv1d_supported(d.K, d.dil)) return "conv: K <= 11 and (K - 1) * dil <= 72 required";
+  }
+  ConvArgs a{};
+  a.Tin = d.Tin; a.x_rstride = d.x_rstride ? d.x_rstride : d.Tin; a.Cin = d.Cin;
+  a.x_bstride = (int64_t)d.Cin * a.x_rstride;
+  a.M = convt ? U * d.Cout : d.Cout;
+  a.Mpad = (int)align_up(a.M, 128);
+  a.K = convt ? 16 / U + 1 : d.K;
+  a.dil = convt ? 1 : d.dil;
+  a.pad_left = convt ? (U == 4 ? 2 : 1) : (a.K - 1) * a.dil / 2;        // (run_decoder)
+  a.in_slope = d.in_slope;
+  a.in_lens = d.in_lens; a.chan_add = d.chan_add; a.reflect1 = d.reflect1;
+  a.T = d.T;
+  a.y_bstride = (int64_t)d.Cout * d.T * (convt ? U : 1);
+  a.epi = convt ? EPI_CONVT : d.epi;
+  a.convt_u = convt ? U : 0;
+  a.relu = d.relu; a.out_lens = d.out_lens;
+  a.res = d.res; a.res_bstride = (int64_t)d.Cout * d.T; a.res_chan_add = d.res_chan_add;
+  a.accum_in = d.accum_in; a.out_scale = d.epi == MBV_CONV_EPI_RESID_ACC ? d.out_scale : 1.f;
+  a.B = d.B;
+  a.splitk = d.splitk != 0;
+  a.prec = d.prec;
+  if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32))
+    return "one utterance's output exceeds 4 GiB";
+  *out = a;
+  return nullptr;
+}
+
+void plan_ints(const ConvPlan& p, int32_t* out) {
+  const int32_t v[8] = {p.route, p.bm, p.bn, p.threads, p.ck, p.nb_big, p.vs_tv, p.S};
+  std::memcpy(out, v, sizeof v);
+}
+
+// the plan of a (validated) descriptor; trimmed launches take the tile width conv1d_trim_bn names (0: refused)
+const char* conv_desc_plan(const mbv_conv_desc& d, const ConvArgs& a, ConvPlan* p) {
+  if (d.legacy_convt) {
+    *p = ConvPlan{};
+    p->route = MBV_ROUTE_LEGACY_CONVT; p->bm = 64; p->bn = 64; p->threads = 256; p->ck = 8; p->S = 1;
+    return nullptr;
+  }
+  if (d.trim_lens) {
+    const int bn = conv1d_trim_bn(a);
+    if (!bn) return "this conv runs on a kernel without trimmed launches (conv1d_trim_bn 0)";
+    *p = conv1d_plan(a, true);
+    if (p->bn != bn) return "internal error: conv1d_trim_bn and the trimmed plan disagree";
+    return nullptr;
+  }
+  *p = conv1d_plan(a, false);
+  return nullptr;
+}
+
+struct DevAllocs {                 // frees on every exit path (after the launch: the caller synchronised)
+  std::vector<void*> p;
+  ~DevAllocs() { for (void* q : p) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" {
+
+int mbv_conv_plan(const mbv_conv_desc* d, int32_t out[8]) {
+  if (!d || !out) { g_create_error = "mbv_conv_plan: NULL argument"; return 1; }
+  ConvArgs a{};
+  const char* why = conv_desc_args(*d, &a);
+  ConvPlan p{};
+  if (!why) {
+    a.ws_floats = d->ws_floats > 0 ? (size_t)d->ws_floats : 0;
+    a.n_counters = d->n_counters > 0 ? d->n_counters : 0;
+    why = conv_desc_plan(*d, a, &p);
+  }
+  if (why) { g_create_error = std::string("mbv_conv_plan: ") + why; return 1; }
+  plan_ints(p, out);
+  return 0;
+}
+
+int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const float* w_host, const float* bias_host,
+                float* y, int32_t* plan_out, void* stream) {
+  if (!m) return 1;
+  if (!d || !x || !w_host || !y) return m->fail("mbv_op_conv: NULL argument");
+  ConvArgs a{};
+  const char* why = conv_desc_args(*d, &a);
+  if (why) return m->fail("mbv_op_conv: %s", why);
+  a.ws = m->conv_ws; a.ws_floats = m->conv_ws_floats; a.counters = m->conv_cnt; a.n_counters = m->conv_ncnt;
+  if (m->splitk && !d->trim_lens && !d->legacy_convt) a.splitk = 1;      // the handle's low-latency mode (an explicit trim wins)
+  ConvPlan p{};
+  if ((why = conv_desc_plan(*d, a, &p))) return m->fail("mbv_op_conv: %s", why);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  DevAllocs mem;
+  auto upload = [&](const void* src, size_t bytes, void** dst) -> int {
+    HIPCHK(m, hipMalloc(dst, bytes));
+    mem.p.push_back(*dst);
+    HIPCHK(m, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  const bool convt = a.epi == EPI_CONVT;
+  const int U = a.convt_u;
+  std::vector<float> zero_bias;
+  if (!bias_host) { zero_bias.assign(d->Cout, 0.f); bias_host = zero_bias.data(); }
+  if (d->legacy_convt) {
+    ConvTArgs t{};
+    t.B = d->B; t.Cin = d->Cin; t.Cout = d->Cout; t.Mpad = (int)align_up(d->Cout, 64); t.Tin = d->Tin;
+    t.in_slope = d->in_slope; t.stride = U; t.x = x; t.y = y;
+    std::vector<float> wt((size_t)16 * t.Cin * t.Mpad, 0.f);
+    pack_convt_phases(w_host, t.Cin, t.Cout, U, t.Mpad, wt.data());
+    void *dw = nullptr, *db = nullptr;
+    if (upload(wt.data(), wt.size() * 4, &dw) || upload(bias_host, (size_t)d->Cout * 4, &db)) return 1;
+    t.w = (const float*)dw; t.bias = (const float*)db;
+    launch_convt(t, s);
+  } else {
+    std::vector<float> wp((size_t)a.K * a.Cin * a.Mpad, 0.f), bp(a.M);
+    if (convt) {
+      pack_convt_rows(w_host, bias_host, a.Cin, d->Cout, U, a.Mpad, wp.data(), bp.data());
+    } else {
+      std::vector<int> rows(a.M);
+      for (int i = 0; i < a.M; ++i) rows[i] = i;
+      pack_conv_rows(w_host, a.Cin, a.K, rows.data(), a.M, nullptr, a.Mpad, wp.data());
+      std::memcpy(bp.data(), bias_host, (size_t)a.M * 4);
+    }
+    void *dw = nullptr, *db = nullptr;
+    if (upload(wp.data(), wp.size() * 4, &dw) || upload(bp.data(), bp.size() * 4, &db)) return 1;
+    a.w = (const float*)dw; a.bias = (const float*)db;
+    if (a.prec == 3) {                               // the split copy of this call's weights
+      void* dws = nullptr;
+      HIPCHK(m, hipMalloc(&dws, wp.size() * 4));
+      mem.p.push_back(dws);
+      launch_split_planes(a.w, (float*)dws, wp.size(), s);
+      a.w_split = (const float*)dws;
+    }
+    a.x = x; a.y = y;
+    if (d->trim_lens) {
+      std::vector<int> l32(d->B);
+      for (int b = 0; b < d->B; ++b) {
+        const int64_t v = d->trim_lens[b];
+        l32[b] = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
+      }
+      void* dl = nullptr;
+      if (upload(l32.data(), l32.size() * 4, &dl)) return 1;
+      void* map = nullptr;
+      HIPCHK(m, hipMalloc(&map, launch_trim_map_ints(d->B, a.T, p.bn) * sizeof(int)));
+      mem.p.push_back(map);
+      launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
+      a.trim_map = (const int*)map; a.trim_bn = p.bn;
+    }
+    launch_conv1d(a, s);
+  }
+  HIPCHK(m, hipGetLastError());
+  HIPCHK(m, hipStreamSynchronize(s));
+  if (plan_out) plan_ints(p, plan_out);
   return 0;
 }
 

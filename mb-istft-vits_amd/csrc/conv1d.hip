@@ -963,6 +963,32 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
 #undef MBV_GLDS_DRAIN
 }
 
+// Split-K for launches that fill less than a quarter of the chip (single utterances: 34 tiles of a
+// 128-channel decoder conv at batch 1): at least two chunks per split, workspace and ticket
+// counters permitting.  OPT-IN (mbv_set_option("splitk", 1) or MBV_CONV_SPLITK=1: the low-latency service setting): the order of
+// summation then depends on the launch size, so a row computed inside a large batch is no longer
+// bitwise equal to the same row computed alone (it is within fp32 rounding); the default keeps
+// that property.  Every parity test passes in either mode.
+static int conv_splitk_factor(const ConvArgs& a, int BM, int BN, int CK, int NWN, int NT, long total, bool trimmed) {
+  const long slots = 256L * (NT == 512 ? 1 : 2);      // resident workgroups (launch_epi)
+  int S = 1;
+  const int nck = a.Cin / CK;
+  // an almost empty chip (<= 32 tiles: one utterance) repays splits of two chunks; up to a quarter
+  // full, K loops of >= 16 chunks cut into >= 4-chunk pieces (measured at batch 1 and 8)
+  static const int tiny_div = [] { const char* e = getenv("MBV_SPLITK_TINY"); return e ? atoi(e) : 16; }();
+  const bool tiny = total * (long)tiny_div <= slots;
+  const int min_chunks = tiny ? 2 : 4;
+  if (NWN == 2 && a.splitk && a.ws_floats && a.n_counters && total * 4 <= slots && nck >= (tiny ? 4 : 16) &&
+      total <= a.n_counters && !trimmed) {
+    S = (int)(slots / total);
+    if (S > nck / min_chunks) S = nck / min_chunks;
+    if (S > 16) S = 16;
+    while (S > 1 && (size_t)total * S * BM * BN > a.ws_floats) --S;
+    if (S < 1) S = 1;
+  }
+  return S;
+}
+
 template <int WM, int WN, int CK, int NWN, int EPI, int PREC = 0, int NWM = 2, int VS = 0>
 static void launch_epi(const ConvArgs& a, hipStream_t s) {
   constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, G = CK / 8, NT = 64 * NWM * NWN;
@@ -979,31 +1005,10 @@ static void launch_epi(const ConvArgs& a, hipStream_t s) {
   // 512-thread shape, 2 for the 256-thread one: both are register-limited to 2 waves / SIMD)
   static const int persist = [] { const char* e = getenv("MBV_CONV_PERSIST"); return e ? atoi(e) : 1; }();
   const long slots = 256L * (NT == 512 ? 1 : 2);
-  // Split-K for launches that fill less than a quarter of the chip (single utterances: 34 tiles of a
-  // 128-channel decoder conv at batch 1): at least two chunks per split, workspace and ticket
-  // counters permitting.  OPT-IN (mbv_set_option("splitk", 1) or MBV_CONV_SPLITK=1: the low-latency service setting): the order of
-  // summation then depends on the launch size, so a row computed inside a large batch is no longer
-  // bitwise equal to the same row computed alone (it is within fp32 rounding); the default keeps
-  // that property.  Every parity test passes in either mode.
-  const int splitk = a.splitk;
-  int S = 1;
-  const int nck = a.Cin / CK;
-  // an almost empty chip (<= 32 tiles: one utterance) repays splits of two chunks; up to a quarter
-  // full, K loops of >= 16 chunks cut into >= 4-chunk pieces (measured at batch 1 and 8)
-  static const int tiny_div = [] { const char* e = getenv("MBV_SPLITK_TINY"); return e ? atoi(e) : 16; }();
-  const bool tiny = total * (long)tiny_div <= slots;
-  const int min_chunks = tiny ? 2 : 4;
+  const int S = conv_splitk_factor(a, BM, BN, CK, NWN, NT, total, a.trim_map != nullptr);
   if (a.trim_map && a.trim_bn != BN) {
     fprintf(stderr, "mbv: trimmed decode: tile map built for %d-column tiles, the launch uses %d\n", a.trim_bn, BN);
     abort();
-  }
-  if (NWN == 2 && splitk && a.ws && a.counters && total * 4 <= slots && nck >= (tiny ? 4 : 16) &&
-      total <= a.n_counters && !a.trim_map) {
-    S = (int)(slots / total);
-    if (S > nck / min_chunks) S = nck / min_chunks;
-    if (S > 16) S = 16;
-    while (S > 1 && (size_t)total * S * BM * BN > a.ws_floats) --S;
-    if (S < 1) S = 1;
   }
   const long units = total * S;
   const int grid = (int)((persist && units > slots) ? slots : units);
@@ -1089,31 +1094,10 @@ static void launch_ck(const ConvArgs& a, hipStream_t s) {
   else launch_one<WM, WN, 8, NWN>(a, s);
 }
 
-// trimmed decode: the column-tile width launch_conv1d will pick for this conv (the tile map is built for it)
-int conv1d_trim_bn(const ConvArgs& a) {
-  if (a.epi == EPI_LN || a.splitk) return 0;
-  {   // a conv that launch_conv1d sends to the narrow kernel (<= 256 frames) keeps that route: trimming must never
-      // change which kernel — i.e. which summation order — computes a sample
-    static const int narrow = [] { const char* e = getenv("MBV_CONV_NARROW"); return e ? atoi(e) : 1; }();
-    if (narrow && conv1d_narrow_supported(a) && (a.T <= 256 || narrow == 2)) return 0;
-  }
-  const bool wide_m = a.M > 64 || a.epi == EPI_GATE || a.epi == EPI_CONVT;
-  static const int mode = [] { const char* e = getenv("MBV_CONV_WIDE"); return e ? atoi(e) : 3; }();
-  if (wide_m && mode >= 3 && a.T >= 384) {
-    const double eff2 = 0.90 * a.T / (double)(((a.T + 127) / 128) * 128);
-    const double eff3 = a.T / (double)(((a.T + 383) / 384) * 384);
-    const long blocks3 = (long)((a.T + 383) / 384) * ((a.M + 127) / 128) * a.B;
-    if (eff3 >= eff2 && blocks3 >= 512) return 384;
-  }
-  return 128;
-}
-
-void launch_conv1d(const ConvArgs& a, hipStream_t s) {
-  // (the residual / running-sum start values are read through a 32-bit buffer view of one utterance, conv_acc_init)
-  if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32)) {
-    fprintf(stderr, "mbv: conv1d: one utterance's [%d x %d] output exceeds 4 GiB\n", a.M, a.T);
-    abort();
-  }
+// The route of a launch (launch_conv1d executes it; conv1d_trim_bn and the tests read it).
+ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed) {
+  ConvPlan p{};
+  p.S = 1;
   // conv1d_narrow.hip (32-column units, rows split over waves, weights from L2) takes over where the
   // 128-column tiles below fit badly:
   //   (a) every sequence of <= 256 frames (the text encoder, the duration predictor): T = 200 fills
@@ -1124,12 +1108,8 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s) {
   // MBV_CONV_NARROW: 0 = never, 1 = these rules, 2 = whenever supported (experiments).
   {
     static const int narrow = [] { const char* e = getenv("MBV_CONV_NARROW"); return e ? atoi(e) : 1; }();
-    if (a.epi == EPI_LN) {
-      if (!conv1d_narrow_supported(a)) { fprintf(stderr, "mbv: EPI_LN outside the narrow kernel's range\n"); abort(); }
-      launch_conv1d_narrow(a, false, s);
-      return;
-    }
-    if (narrow && !a.trim_map && conv1d_narrow_supported(a)) {
+    if (a.epi == EPI_LN) { p.route = CONV_NARROW_M; return p; }
+    if (narrow && !trimmed && conv1d_narrow_supported(a)) {
       const long tiles128 = (long)((a.T + 127) / 128) * ((a.M + 127) / 128) * a.B;
       // (fewer than 16 units — conv_o / conv_2 of the text encoder of one short utterance: 8 — are better
       // served by split-K over the long Cin loop than by 8 workgroups walking it alone; measured on ljs_mb,
@@ -1137,13 +1117,15 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s) {
       const long units32 = (((long)a.B * ((a.T + 15) / 16) + 1) / 2) * ((a.M + 127) / 128);
       if (a.splitk && tiles128 <= 128) {
         static const int min_units = [] { const char* e = getenv("MBV_NARROW_MIN_UNITS"); return e ? atoi(e) : 16; }();
-        if (units32 >= min_units || narrow == 2) { launch_conv1d_narrow(a, true, s); return; }
+        if (units32 >= min_units || narrow == 2) { p.route = CONV_NARROW_LAUNCH; return p; }
       } else if (a.T <= 256 || narrow == 2) {
-        launch_conv1d_narrow(a, false, s);
-        return;
+        p.route = CONV_NARROW_M;
+        return p;
       }
     }
   }
+  const int halo = (a.K - 1) * a.dil;
+  const int ck = a.K == 1 ? 32 : (a.K <= 5 && halo <= 24) ? 16 : 8;        // launch_ck
   const bool wide_m = a.M > 64 || a.epi == EPI_GATE || a.epi == EPI_CONVT;
   // Long sequences with enough blocks to fill the chip: 512-thread workgroups, 128 x 384 tile
   // (6 accumulators per wave), double-buffered LDS.  Otherwise 256-thread, 128 x 128 tile.
@@ -1164,7 +1146,7 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s) {
     // first utterances, the rest as 128 x 128 tiles on the 512 half-CU slots.  In units of one big tile's time
     // (a small tile on half a CU: 1/3 of the work on 1/2 of the waves, measured 0.63 - 0.65):
     static const int split_on = [] { const char* e = getenv("MBV_CONV_BATCH_SPLIT"); return e ? atoi(e) : 1; }();
-    if (split_on && !a.splitk && !a.trim_map && eff3 >= eff2 && blocks3 > 256 && a.B > 1) {
+    if (split_on && !a.splitk && !trimmed && eff3 >= eff2 && blocks3 > 256 && a.B > 1) {
       const double c2 = 0.65;
       auto rounds = [](long n, long slots) { return (double)((n + slots - 1) / slots); };
       double best = big ? rounds(blocks3, 256) : rounds(tpb2 * a.B, 512) * c2;
@@ -1176,13 +1158,15 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s) {
       }
     }
   }
+  auto shape = [&](int route, int bm, int bn, int threads, int ck_) {
+    p.route = route; p.bm = bm; p.bn = bn; p.threads = threads; p.ck = ck_;
+  };
   // r03: the stride-4 upsampling conv on few, long-ish sequences (T' = 566 input frames: 1.47 tiles of 384 columns, 4.4 of
   // 128) tiled over the VIRTUAL sequence of the whole batch — utterance b at column b (T + halo), the gaps reading as
   // zero padding — so that only the last tile of the launch is ragged.  Same chain of operations per output element.
   {
     static const int vs_on = [] { const char* e = getenv("MBV_CONV_VS"); return e ? atoi(e) : 1; }();
-    const int halo = (a.K - 1) * a.dil;
-    if (vs_on && a.epi == EPI_CONVT && a.convt_u == 4 && a.prec != 3 && !a.splitk && !a.trim_map && !a.chan_add &&
+    if (vs_on && a.epi == EPI_CONVT && a.convt_u == 4 && a.prec != 3 && !a.splitk && !trimmed && !a.chan_add &&
         !a.reflect1 && a.B > 1 && a.K > 1 && a.K <= 5 && halo <= 24 && a.T >= 128 &&
         (int64_t)a.B * a.x_bstride < (1ll << 31)) {
       auto rounds = [](long n, long slots) { return (double)((n + slots - 1) / slots); };
@@ -1199,61 +1183,99 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s) {
         cur = rounds((long)((a.T + 127) / 128) * tiles_y * a.B, 512) * 0.65;
       }
       if (cost_vs >= 2.0 && cost_vs < 0.95 * cur) {
-        ConvArgs av = a;
-        av.vs_tv = (int)tv;
-        launch_epi<2, 3, 16, 4, EPI_CONVT, 0, 2, 1>(av, s);
-        return;
+        shape(CONV_VS, 128, 384, 512, 16);
+        p.vs_tv = (int)tv;
+        return p;                          // (S = 1: split-K is built for the 256-thread shapes only)
       }
     }
   }
   if (nb_big > 0) {
-    ConvArgs a1 = a, a2 = a;
-    const int nb = nb_big;
-    a1.B = nb;
-    a2.B = a.B - nb;
-    a2.x += (int64_t)nb * a.x_bstride;
-    a2.y += (int64_t)nb * a.y_bstride;
-    if (a.in_lens) a2.in_lens += nb;
-    if (a.out_lens) a2.out_lens += nb;
-    if (a.chan_add) a2.chan_add += (int64_t)nb * a.Cin;
-    if (a.res) a2.res += (int64_t)nb * a.res_bstride;
-    if (a.res_chan_add) a2.res_chan_add += (int64_t)nb * a.M;
-    if (a.accum_in) a2.accum_in += (int64_t)nb * a.y_bstride;
-    if (a.gate_cond) a2.gate_cond += (int64_t)nb * a.gate_cond_bstride;
-    if (a.skip) a2.skip += (int64_t)nb * (a.M - a.split) * a.T;
-    launch_ck<2, 3, 4>(a1, s);
-    launch_ck<2, 2, 2>(a2, s);
-    return;
+    shape(CONV_SPLIT_BATCH, 128, 384, 512, ck);
+    p.nb_big = nb_big;
+    return p;
   }
   if (wide_m) {
-    if (big) launch_ck<2, 3, 4>(a, s);
-    else launch_ck<2, 2, 2>(a, s);
+    if (big) shape(CONV_BIG, 128, 384, 512, ck);
+    else shape(CONV_SMALL, 128, 128, 256, ck);
   } else {
     // <= 64 output rows: the 64 x 384 shape when the launch fills its 512 half-CU slots (exact fp32, K > 1, the
     // decoder's epilogues); else 64 x 128.  Same chain of operations per output element either way.
     static const int half_on = [] { const char* e = getenv("MBV_CONV_HALF"); return e ? atoi(e) : 1; }();
-    if (half_on && mode >= 3 && a.T >= 384 && a.K > 1 && a.prec != 3 && !a.splitk && !a.trim_map &&
+    if (half_on && mode >= 3 && a.T >= 384 && a.K > 1 && a.prec != 3 && !a.splitk && !trimmed &&
+        (a.epi == EPI_STORE || a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) &&
         (long)((a.T + 383) / 384) * a.B >= 512 && a.T / (double)(((a.T + 383) / 384) * 384) >= 0.90 * a.T / (double)(((a.T + 127) / 128) * 128)) {
-      const bool ck16 = a.K <= 5 && (a.K - 1) * a.dil <= 24;
-      bool done = true;
-      if (ck16) {
+      shape(CONV_HALF, 64, 384, 256, a.K <= 5 && halo <= 24 ? 16 : 8);
+      return p;                            // (S = 1: NWN = 4)
+    }
+    shape(CONV_M64, 64, 128, 256, ck);
+  }
+  const long total = (long)((a.T + p.bn - 1) / p.bn) * ((a.M + p.bm - 1) / p.bm) * a.B;
+  p.S = conv_splitk_factor(a, p.bm, p.bn, p.ck, p.bn == 384 ? 4 : 2, p.threads, total, trimmed);   // (NWN 4: never split)
+  return p;
+}
+
+// trimmed decode: the column-tile width launch_conv1d will pick for this conv (the tile map is built for it)
+int conv1d_trim_bn(const ConvArgs& a) {
+  if (a.epi == EPI_LN || a.splitk) return 0;
+  // a conv that launch_conv1d sends to the narrow kernel (<= 256 frames) keeps that route: trimming must never
+  // change which kernel — i.e. which summation order — computes a sample
+  const int r = conv1d_plan(a, false).route;
+  if (r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH) return 0;
+  return conv1d_plan(a, true).bn;
+}
+
+void launch_conv1d(const ConvArgs& a, hipStream_t s) {
+  // (the residual / running-sum start values are read through a 32-bit buffer view of one utterance, conv_acc_init)
+  if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32)) {
+    fprintf(stderr, "mbv: conv1d: one utterance's [%d x %d] output exceeds 4 GiB\n", a.M, a.T);
+    abort();
+  }
+  if (a.epi == EPI_LN && !conv1d_narrow_supported(a)) { fprintf(stderr, "mbv: EPI_LN outside the narrow kernel's range\n"); abort(); }
+  const ConvPlan p = conv1d_plan(a);
+  switch (p.route) {
+    case CONV_NARROW_M: launch_conv1d_narrow(a, false, s); return;
+    case CONV_NARROW_LAUNCH: launch_conv1d_narrow(a, true, s); return;
+    case CONV_VS: {
+      ConvArgs av = a;
+      av.vs_tv = p.vs_tv;
+      launch_epi<2, 3, 16, 4, EPI_CONVT, 0, 2, 1>(av, s);
+      return;
+    }
+    case CONV_SPLIT_BATCH: {
+      ConvArgs a1 = a, a2 = a;
+      const int nb = p.nb_big;
+      a1.B = nb;
+      a2.B = a.B - nb;
+      a2.x += (int64_t)nb * a.x_bstride;
+      a2.y += (int64_t)nb * a.y_bstride;
+      if (a.in_lens) a2.in_lens += nb;
+      if (a.out_lens) a2.out_lens += nb;
+      if (a.chan_add) a2.chan_add += (int64_t)nb * a.Cin;
+      if (a.res) a2.res += (int64_t)nb * a.res_bstride;
+      if (a.res_chan_add) a2.res_chan_add += (int64_t)nb * a.M;
+      if (a.accum_in) a2.accum_in += (int64_t)nb * a.y_bstride;
+      if (a.gate_cond) a2.gate_cond += (int64_t)nb * a.gate_cond_bstride;
+      if (a.skip) a2.skip += (int64_t)nb * (a.M - a.split) * a.T;
+      launch_ck<2, 3, 4>(a1, s);
+      launch_ck<2, 2, 2>(a2, s);
+      return;
+    }
+    case CONV_BIG: launch_ck<2, 3, 4>(a, s); return;
+    case CONV_SMALL: launch_ck<2, 2, 2>(a, s); return;
+    case CONV_HALF:
+      if (p.ck == 16) {
         switch (a.epi) {
-          case EPI_STORE: launch_epi<2, 3, 16, 4, EPI_STORE, 0, 1>(a, s); break;
-          case EPI_RESID: launch_epi<2, 3, 16, 4, EPI_RESID, 0, 1>(a, s); break;
-          case EPI_RESID_ACC: launch_epi<2, 3, 16, 4, EPI_RESID_ACC, 0, 1>(a, s); break;
-          default: done = false;
-        }
-      } else {
-        switch (a.epi) {
-          case EPI_STORE: launch_epi<2, 3, 8, 4, EPI_STORE, 0, 1>(a, s); break;
-          case EPI_RESID: launch_epi<2, 3, 8, 4, EPI_RESID, 0, 1>(a, s); break;
-          case EPI_RESID_ACC: launch_epi<2, 3, 8, 4, EPI_RESID_ACC, 0, 1>(a, s); break;
-          default: done = false;
+          case EPI_STORE: launch_epi<2, 3, 16, 4, EPI_STORE, 0, 1>(a, s); return;
+          case EPI_RESID: launch_epi<2, 3, 16, 4, EPI_RESID, 0, 1>(a, s); return;
+          default: launch_epi<2, 3, 16, 4, EPI_RESID_ACC, 0, 1>(a, s); return;
         }
       }
-      if (done) return;
-    }
-    launch_ck<1, 2, 2>(a, s);
+      switch (a.epi) {
+        case EPI_STORE: launch_epi<2, 3, 8, 4, EPI_STORE, 0, 1>(a, s); return;
+        case EPI_RESID: launch_epi<2, 3, 8, 4, EPI_RESID, 0, 1>(a, s); return;
+        default: launch_epi<2, 3, 8, 4, EPI_RESID_ACC, 0, 1>(a, s); return;
+      }
+    default: launch_ck<1, 2, 2>(a, s); return;            // CONV_M64
   }
 }
 

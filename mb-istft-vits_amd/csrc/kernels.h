@@ -78,6 +78,7 @@ struct ConvArgs {
   // utterance b at virtual column b * vs_tv (vs_tv = T + halo); set by the launcher only
   int vs_tv;
   // split-K scratch (small launches): partial accumulators + one self-resetting ticket per tile
+  // (conv1d_plan decides from the sizes alone: ws_floats / n_counters are 0 whenever ws / counters are null)
   float* ws;
   size_t ws_floats;
   unsigned* counters;
@@ -91,7 +92,29 @@ struct ConvArgs {
   const float* ln_beta;    // [M]
   const int* ln_out_lens;  // mask behind the LayerNorm (the encoder's last layer), or nullptr
 };
-void launch_conv1d(const ConvArgs& a, hipStream_t s);
+// Which kernel launch_conv1d runs for a ConvArgs, as data (pure host logic: no launch, no device access; pointers
+// are only tested against null).  Values match MBV_ROUTE_* of include/mbistft_vits.h.
+enum ConvRoute : int {
+  CONV_NARROW_M = 1,        // conv1d_narrow.hip, row blocks by M (T <= 256, EPI_LN)
+  CONV_NARROW_LAUNCH = 2,   // conv1d_narrow.hip, row blocks by launch size (split-K mode, few tiles)
+  CONV_M64 = 3,             // 64 x 128 tiles, 256 threads (<= 64 rows)
+  CONV_HALF = 4,            // 64 x 384 tiles, 256 threads (<= 64 rows, long and many)
+  CONV_SMALL = 5,           // 128 x 128 tiles, 256 threads (split-K when S > 1)
+  CONV_BIG = 6,             // 128 x 384 tiles, 512 threads
+  CONV_SPLIT_BATCH = 7,     // the first nb_big utterances on 128 x 384 tiles, the rest on 128 x 128
+  CONV_VS = 8,              // 128 x 384 tiles over the virtual sequence of the batch (stride-4 EPI_CONVT)
+};
+struct ConvPlan {
+  int route;
+  int bm, bn, threads, ck;  // tile shape of the launch (of its first part for CONV_SPLIT_BATCH); 0 for the narrow kernel
+  int nb_big;               // CONV_SPLIT_BATCH: utterances on the 128 x 384 shape
+  int vs_tv;                // CONV_VS: virtual columns per utterance (T + halo)
+  int S;                    // split-K factor (1: none)
+};
+// trimmed: plan for a launch with a trim map (default: a.trim_map != nullptr)
+ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed);
+inline ConvPlan conv1d_plan(const ConvArgs& a) { return conv1d_plan(a, a.trim_map != nullptr); }
+void launch_conv1d(const ConvArgs& a, hipStream_t s);     // executes conv1d_plan(a)
 bool conv1d_supported(int K, int dil);   // kernel sizes / dilations the MFMA kernel is built for
 // conv1d_narrow.hip: the same contraction in 32-column x row-block units (launches with few columns)
 bool conv1d_narrow_supported(const ConvArgs& a);

@@ -465,6 +465,30 @@ def test_resblock_streams_are_bitwise_the_one_stream_schedule():
             net.set_option("splitk", 0)
 
 
+def test_infer_on_a_caller_stream_is_bitwise_the_default_stream():
+    """Everything is enqueued on the caller's stream: under `torch.cuda.stream(s)` with a fresh non-default stream
+    `infer` gives the default stream's bits — at B = 1, where the decoder forks its ResBlocks from the caller's stream
+    onto its internal streams (decoder_stage_concurrent), and at B = 8."""
+    from gpu_util import make_net
+    from mb_istft_vits_amd import synth
+    net, _ = make_net("ljs_mb_istft_vits")
+    for B in (1, 8):
+        x, xl, _ = synth.synthetic_batch(net.cfg, B, 40, seed=11 + B, ragged=True)
+        x, xl = torch.from_numpy(x).cuda(), torch.from_numpy(xl).cuda()
+        ref = net.infer(x, xl, noise_scale=0, length_scale=1)
+        torch.cuda.synchronize()
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            got = net.infer(x, xl, noise_scale=0, length_scale=1)
+        s.synchronize()
+        n = 0
+        for a, b in zip(list(ref[:6]) + list(ref[6]), list(got[:6]) + list(got[6])):
+            if isinstance(a, torch.Tensor):
+                assert torch.equal(a, b), (B, n)
+                n += 1
+        assert n >= 10
+
+
 def test_voice_conversion_matches_reference_golden():
     """`voice_conversion` (models.py:790-798) against the vector captured from the reference; the
     posterior encoder's noise draw is pinned by seeding torch and recovering it is not possible, so

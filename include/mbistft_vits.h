@@ -296,6 +296,32 @@ int mbv_resample(mbv_model *m, const float *wave, const int64_t *valid_samples, 
 int mbv_resample_bank(int orig_sr, int target_sr, int filter, float *dst, int64_t capacity, int32_t *phases,
                       int32_t *taps, int32_t *left);
 
+/* ---- linear spectrogram ------------------------------------------------------
+ * replaces spectrogram_torch(y, n_fft, sr, hop, win, center=False) (mel_processing.py:51-70), the input of
+ * mbv_voice_conversion: |STFT| with (n_fft - hop) / 2 zeros on each side of the row, no centring, the
+ * periodic Hann window of length win centred in n_fft as torch.stft centres it, onesided, and abs() with no
+ * epsilon.  Every row is transformed as if alone (zeros at and past its valid length; samples there are never
+ * read) and padded with zero frames, as the collate function pads a ragged batch (data_utils.py:125-147).
+ * Computed as a real FFT (complex FFT of n_fft / 2 points + split post-pass) on fp32 twiddle and window tables
+ * built in float64.  Refused: n_fft not a power of two in [256, 4096], hop or win outside [1, n_fft].
+ *   wave           [B, in_stride] device: fp32 (MBV_WAVE_F32) or int16 (MBV_WAVE_PCM16, scaled by exactly
+ *                  1 / 32768 as data_utils.py:75 does, so it equals the fp32 path on pcm / 32768 bitwise)
+ *   valid_samples  int64 [B] device, clamped to [0, in_stride]; NULL = every row is in_stride samples
+ *   spec           fp32 [B, n_fft / 2 + 1, frames] device, frames = mbv_spectrogram_frames(in_stride, ...)
+ *                  (any other value is refused); row b holds frames(valid_b) frames, zeros after them
+ *   spec_lengths   int64 [B] device, optional: frames(valid_b), computed on the device
+ * The first call for an (n_fft, win) pair builds the tables on the host and uploads them with a synchronous
+ * copy (cached in the handle); later calls only enqueue one kernel.  Needs no weights. */
+#define MBV_WAVE_F32   0
+#define MBV_WAVE_PCM16 1          /* int16, scaled by 1/32768 (data_utils.py:75) */
+int mbv_spectrogram(mbv_model *m, const void *wave, int wave_dtype, const int64_t *valid_samples, int B,
+                    int64_t in_stride, int n_fft, int hop, int win, float *spec, int64_t frames,
+                    int64_t *spec_lengths, void *stream);
+/* Host only (no handle, no GPU): frames of an n-sample row, 0 if n + 2 ((n_fft - hop) / 2) < n_fft (where
+ * torch.stft raises), else 1 + (n + 2 ((n_fft - hop) / 2) - n_fft) / hop.  -1 on bad arguments (n < 0, or
+ * n_fft / hop refused as above). */
+int64_t mbv_spectrogram_frames(int64_t n_samples, int n_fft, int hop);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"

@@ -20,6 +20,7 @@ SYMBOLS = [
     "mbv_op_conv1d", "mbv_kernel_times_ms", "mbv_istft_finalize", "mbv_pcm16", "mbv_voice_conversion",
     "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
     "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
+    "mbv_spectrogram", "mbv_spectrogram_frames",
 ]
 
 
@@ -116,6 +117,9 @@ def lib():
     L.mbv_resample.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
     L.mbv_resample_bank.argtypes = [i32, i32, i32, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32)]
+    L.mbv_spectrogram.argtypes = [vp, vp, i32, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
+    L.mbv_spectrogram_frames.argtypes = [C.c_int64, i32, i32]
+    L.mbv_spectrogram_frames.restype = C.c_int64
     L.mbv_set_option.argtypes = [vp, C.c_char_p, i32]
     L.mbv_ticket.argtypes = [vp]
     L.mbv_ticket.restype = C.c_int64

@@ -99,6 +99,8 @@ struct mbv_model {
   unsigned* peak_buf = nullptr; int peak_cap = 0;   // per-utterance peaks of mbv_pcm16
   struct ResampleBank { float* d = nullptr; ResampleGeom g{}; };
   std::map<std::array<int, 3>, ResampleBank> resample_banks;   // (L, M, filter) -> fp32 bank on the device (mbv_resample)
+  struct SpectrogramTables { float* tw = nullptr; float* win = nullptr; };
+  std::map<std::array<int, 2>, SpectrogramTables> spec_tables;   // (n_fft, win) -> twiddles + window (mbv_spectrogram)
   bool user_tab_is_pqmf = false;
   int xpost_F = 1;             // frames per row of the last x_post stage tensor
   int xpost_rows = 72;         // 72 (4 bands x 18) or 18 (single band)
@@ -1455,6 +1457,7 @@ void mbv_destroy(mbv_model* m) {
   if (m->user_tab) (void)hipFree(m->user_tab);
   if (m->peak_buf) (void)hipFree(m->peak_buf);
   for (auto& kv : m->resample_banks) (void)hipFree(kv.second.d);
+  for (auto& kv : m->spec_tables) { (void)hipFree(kv.second.tw); (void)hipFree(kv.second.win); }
   if (m->ev_ok) { for (auto& set : m->evr) for (auto& e : set) if (e) (void)hipEventDestroy(e); for (auto& e : m->evk) (void)hipEventDestroy(e); }
   if (m->aux_ok) {
     for (auto& st : m->aux) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -2065,6 +2068,60 @@ int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, 
   }
   launch_resample(wave, valid_samples, B, in_stride, it->second.d, it->second.g, out, out_stride, out_samples,
                   (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+namespace {
+const char* spectrogram_args_error(int n_fft, int hop, int win) {
+  if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1))) return "n_fft must be a power of two in [256, 4096]";
+  if (hop < 1 || hop > n_fft) return "hop must be in [1, n_fft]";
+  if (win < 1 || win > n_fft) return "win must be in [1, n_fft]";
+  return nullptr;
+}
+}  // namespace
+
+int64_t mbv_spectrogram_frames(int64_t n_samples, int n_fft, int hop) {
+  if (n_samples < 0 || spectrogram_args_error(n_fft, hop, 1)) return -1;
+  return spectrogram_frames(n_samples, n_fft, hop);
+}
+
+int mbv_spectrogram(mbv_model* m, const void* wave, int wave_dtype, const int64_t* valid_samples, int B,
+                    int64_t in_stride, int n_fft, int hop, int win, float* spec, int64_t frames,
+                    int64_t* spec_lengths, void* stream) {
+  if (!m) return 1;
+  if (const char* why = spectrogram_args_error(n_fft, hop, win)) return m->fail("mbv_spectrogram: %s", why);
+  if (wave_dtype != MBV_WAVE_F32 && wave_dtype != MBV_WAVE_PCM16)
+    return m->fail("mbv_spectrogram: unknown wave_dtype %d", wave_dtype);
+  if (!wave || B <= 0 || in_stride <= 0) return m->fail("mbv_spectrogram: bad arguments");
+  if (B > 65535) return m->fail("mbv_spectrogram: more than 65535 rows");
+  if (in_stride > ((int64_t)1 << 60)) return m->fail("mbv_spectrogram: in_stride too large");
+  const int64_t F = spectrogram_frames(in_stride, n_fft, hop);
+  if (frames != F)
+    return m->fail("mbv_spectrogram: frames is %lld, mbv_spectrogram_frames(in_stride) gives %lld", (long long)frames,
+                   (long long)F);
+  if (F > 0 && !spec) return m->fail("mbv_spectrogram: spec is NULL");
+  if (F / spectrogram_block_frames(n_fft, hop) >= 0x7fffffff) return m->fail("mbv_spectrogram: too many frames per row");
+  DEVICE_GUARD(m);
+  const std::array<int, 2> key{n_fft, win};
+  auto it = m->spec_tables.find(key);
+  if (it == m->spec_tables.end()) {
+    // first call for this (n_fft, win): build in float64 on the host, upload once (synchronous copy)
+    std::vector<float> tw, window;
+    spectrogram_tables(n_fft, win, &tw, &window);
+    mbv_model::SpectrogramTables t;
+    HIPCHK(m, hipMalloc((void**)&t.tw, tw.size() * sizeof(float)));
+    if (hipMalloc((void**)&t.win, window.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(t.win, window.data(), window.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(t.tw);
+      if (t.win) (void)hipFree(t.win);
+      return m->fail("mbv_spectrogram: uploading the twiddle / window tables failed");
+    }
+    it = m->spec_tables.emplace(key, t).first;
+  }
+  launch_spectrogram(wave, wave_dtype, valid_samples, B, in_stride, n_fft, hop, it->second.tw, it->second.win, spec, F,
+                     spec_lengths, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }

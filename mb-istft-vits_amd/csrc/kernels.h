@@ -299,6 +299,21 @@ const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<fl
 void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
                      const ResampleGeom& g, float* out, int64_t out_stride, int64_t* out_samples, hipStream_t s);
 
+// ---------------------------------------------------------------- linear spectrogram (spectrogram.hip)
+// |STFT| of spectrogram_torch(center=False) per row as if alone: (n_fft - hop) / 2 zeros each side, periodic
+// Hann of length win centred in n_fft, [B, n_fft / 2 + 1, F] with frames past a row's length zero.
+constexpr size_t kSpectrogramMaxLds = 80 * 1024;   // two workgroups per CU
+int64_t spectrogram_frames(int64_t n, int n_fft, int hop);     // 0 if n + 2 pad < n_fft
+size_t spectrogram_lds_bytes(int n_fft, int hop, int FB);
+int spectrogram_block_frames(int n_fft, int hop);              // FB: frames per workgroup (a power of two)
+// host, float64 rounded once: tw = e^{-2 pi i m / n_fft} as (re, im), m < n_fft; window [n_fft], zeros outside
+// the centred span of win
+void spectrogram_tables(int n_fft, int win, std::vector<float>* tw, std::vector<float>* window);
+// x: fp32 (dtype 0) or int16 scaled by 1 / 32768 (dtype 1), [B, in_stride]; n_fft a power of two in [256, 4096]
+void launch_spectrogram(const void* x, int dtype, const int64_t* valid, int B, int64_t in_stride, int n_fft, int hop,
+                        const float* tw, const float* win, float* spec, int64_t F, int64_t* spec_lengths,
+                        hipStream_t s);
+
 // z = (m + noise * exp(logs)) * mask   (PosteriorEncoder, models.py:245); stats = [B, 2I, T]
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,
                              int I, int T, hipStream_t s);

@@ -623,6 +623,56 @@ class SynthesizerTrn(nn.Module):
         return out, out_samples
 
     @torch.no_grad()
+    def spectrogram(self, wave, n_fft, hop_size, win_size, valid_samples=None, center=False):
+        """Waveform [B, n] or [B, 1, n] (fp32, or int16 PCM scaled by 1 / 32768 as data_utils.py:75 does) ->
+        (spec fp32 [B, n_fft // 2 + 1, F], spec_lengths int64 [B]) on the GPU: spectrogram_torch(y, n_fft, sr,
+        hop_size, win_size, center=False) (mel_processing.py:51-70) of every row over its valid samples
+        (`valid_samples` int64 [B], clamped to the row; None = whole rows), as if alone, then padded with zero
+        frames as the collate function pads a batch (data_utils.py:125-147).  spec_lengths[b] is the frame count
+        of row b (0 where torch.stft would refuse a row that short); F = the frame count of a whole row.  The
+        result is the `y, y_lengths` of `voice_conversion`.  No host synchronisation, except on the first call
+        for an (n_fft, win_size) pair (the twiddle and window tables are built and uploaded)."""
+        if center:
+            raise ValueError("spectrogram: center=True is not supported (the reference calls it with center=False)")
+        if wave.dtype == torch.int16:
+            dtype = 1                                            # MBV_WAVE_PCM16
+        elif wave.dtype == torch.float32:
+            dtype = 0                                            # MBV_WAVE_F32
+        else:
+            raise ValueError("spectrogram: wave must be float32 or int16, got %s" % wave.dtype)
+        if wave.dim() == 3 and wave.shape[1] == 1:
+            wave = wave[:, 0]
+        if wave.dim() != 2:
+            raise ValueError("spectrogram: wave must be [B, n] or [B, 1, n]")
+        n_fft, hop_size, win_size = int(n_fft), int(hop_size), int(win_size)
+        L = _capi.lib()
+        B, n = wave.shape
+        F = L.mbv_spectrogram_frames(n, n_fft, hop_size)
+        if F < 0:
+            raise ValueError("spectrogram: n_fft must be a power of two in [256, 4096] and hop_size in [1, n_fft] "
+                             "(n_fft %d, hop_size %d)" % (n_fft, hop_size))
+        if not 1 <= win_size <= n_fft:
+            raise ValueError("spectrogram: win_size must be in [1, n_fft] (win_size %d, n_fft %d)" % (win_size, n_fft))
+        h = self._ensure_handle()
+        dev = self._device()
+        wave = wave.to(device=dev).contiguous()
+        if valid_samples is not None:
+            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).contiguous()
+            if valid_samples.shape != (B,):
+                raise ValueError("valid_samples must be [B]")
+        spec = torch.empty(B, n_fft // 2 + 1, F, device=dev, dtype=torch.float32)
+        spec_lengths = torch.empty(B, device=dev, dtype=torch.int64)
+        if B == 0 or n == 0:
+            spec_lengths.zero_()
+            return spec, spec_lengths
+        with torch.cuda.device(dev):
+            _capi.check(h, L.mbv_spectrogram(h, self._ptr(wave), dtype, self._ptr(valid_samples), B, n, n_fft,
+                                             hop_size, win_size, self._ptr(spec), F, self._ptr(spec_lengths),
+                                             self._stream()),
+                        "mbv_spectrogram")
+        return spec, spec_lengths
+
+    @torch.no_grad()
     def _speaker_embedding(self, sid):
         h = self._ensure_handle()
         dev = self._device()

@@ -10,10 +10,15 @@ resampy's windowed-sinc interpolator and fix_length) with the peak normalise / c
 algorithm (tests/resample_ref.py), not to librosa / resampy themselves, which are not part of this
 build: its filter tables are rebuilt from resampy's documented filter specs.  librosa >= 0.10
 (the unpinned requirements.txt) defaults to soxr_hq, a different algorithm that is not provided.
+
+`convert_pcm16` is the audio-in, audio-out form of `voice_conversion`: resample to the model's rate,
+the linear spectrogram of the data path (`SynthesizerTrn.spectrogram`, mel_processing.py:51-70),
+voice conversion, then `service_pcm16`.
 """
 import base64
 
 import numpy as np
+import torch
 
 
 def chunk_size(rate, frame_length=0.02):
@@ -50,3 +55,32 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
     No host synchronisation (beyond the first call for a rate pair, see `SynthesizerTrn.resample`)."""
     wave, valid = net.resample(o, model_sr, rate, y_lengths=y_lengths, res_type=res_type)
     return net.to_pcm16(wave, auto_normalize=auto_normalize, valid_samples=valid), valid
+
+
+def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
+                  auto_normalize=True, res_type="kaiser_best"):
+    """Voice conversion from audio to audio as one GPU chain:
+      1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
+         `valid_samples` int64 [B] samples per utterance or None = whole rows;
+      2. `net.resample` to `model_sr` when the rates differ;
+      3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
+      4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt)`;
+      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`.
+    -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
+    anything is launched when win_size > n_fft or the model has no speakers.  The one host synchronisation is
+    the status check `voice_conversion` already has (besides the first-call table uploads of `resample` and
+    `spectrogram`)."""
+    n_fft = 2 * (net.cfg.spec_channels - 1)
+    if not net.n_speakers > 0:
+        raise ValueError("convert_pcm16: voice conversion needs a multi-speaker model (n_speakers > 0)")
+    if not 1 <= int(win_size) <= n_fft:
+        raise ValueError("convert_pcm16: win_size %d must be in [1, n_fft = 2 * (spec_channels - 1) = %d]"
+                         % (int(win_size), n_fft))
+    if wave.dim() == 2:
+        wave = wave.unsqueeze(1)
+    if wave.dtype == torch.int16 and int(in_sr) != int(model_sr):
+        wave = wave.float() / 32768.0                          # the resampler takes fp32; exact scaling
+    wave, valid = net.resample(wave, in_sr, model_sr, valid_samples=valid_samples, res_type=res_type)
+    spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
+    o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt)[0]
+    return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type)

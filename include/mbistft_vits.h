@@ -150,6 +150,22 @@ int mbv_synthesize(mbv_model *m, int t_frames, const float *noise, float noise_s
 int mbv_decode(mbv_model *m, const float *z, const float *g, int B, int t_frames,
                const mbv_outputs *outs, void *stream);
 
+/* ---- streaming decode (no reference counterpart; replaces the notebooks' chunk stitching) ----------------
+ * mbv_decoder_context (host only, like mbv_conv_plan): out = (L, R), the whole z-frames of left and right
+ * context any output sample of z-frame t can depend on, [t - L, t + R], derived from the decoder of cfg
+ * (conv_pre, the two ConvTranspose1d, the ResBlocks' kernels and dilations, ReflectionPad1d((1,0)) + conv_post,
+ * the iSTFT, the 63-tap synthesis filter).  ljs / uudb MB and MS: (25, 24); single band: (13, 13).
+ *
+ * mbv_decode_range: `net.dec(z, g)[0]` for z-frames [first, first + count) only.  z is the caller's whole
+ * [B, 192, t_frames] tensor; only frames [max(0, first - L), min(t_frames, first + count + R)) are read.  Writes
+ * samples [256 first, 256 (first + count)) of every row, at o + b o_row_stride, and nothing else (o 16-byte
+ * aligned, o_row_stride >= 256 t_frames and a multiple of 4).  In the default mode the samples are bitwise those of
+ * mbv_decode on the whole z; with "splitk" within fp32 rounding of it.  Honours "splitk", "dec_streams" and the
+ * batch split of x_post; never uses a trim map.  Errors leave the handle usable. */
+int mbv_decoder_context(const mbv_config *cfg, int32_t out[2]);
+int mbv_decode_range(mbv_model *m, const float *z, const float *g, int B, int t_frames, int first, int count,
+                     float *o, int64_t o_row_stride, void *stream);
+
 /* speaker embedding lookup: replaces `net.emb_g(sid)` (models.py:705).
  * out fp32 [B, gin] */
 int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, void *stream);

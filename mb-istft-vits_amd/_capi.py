@@ -20,7 +20,7 @@ SYMBOLS = [
     "mbv_op_conv1d", "mbv_kernel_times_ms", "mbv_istft_finalize", "mbv_pcm16", "mbv_voice_conversion",
     "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
     "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
-    "mbv_spectrogram", "mbv_spectrogram_frames",
+    "mbv_spectrogram", "mbv_spectrogram_frames", "mbv_decoder_context", "mbv_decode_range",
 ]
 
 
@@ -106,6 +106,8 @@ def lib():
     L.mbv_encode.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp, C.c_float, vp, vp]
     L.mbv_synthesize.argtypes = [vp, i32, vp, C.c_float, i32, C.POINTER(MbvOutputs), vp]
     L.mbv_decode.argtypes = [vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
+    L.mbv_decoder_context.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32 * 2)]
+    L.mbv_decode_range.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.c_int64, vp]
     L.mbv_speaker_embedding.argtypes = [vp, vp, i32, vp, vp]
     L.mbv_stage_times_ms.argtypes = [vp, C.POINTER(C.c_float * 5)]
     L.mbv_kernel_times_ms.argtypes = [vp, C.POINTER(C.c_float * 2)]

@@ -969,9 +969,67 @@ bool decoder_stage_concurrent(const mbv_model* m, int B, int ch, int Lo) {
   return m->dec_streams && m->aux_ok && m->cfg.resblock_type != 2 && conv_tiles <= 192 && !m->trim;   // (trim: its tile maps are built on the caller's stream)
 }
 
+// The streaming decode (mbv_decode_range): run_decoder on a z-window of Td frames whose first frame is z-frame
+// `first - keep_first` of an utterance of t_full frames.  The tail stores only window frames [keep_first,
+// keep_first + keep_count), at o + b o_row_stride (o already offset to the chunk's first sample).
+struct DecodeRange {
+  int t_full;
+  int keep_first, keep_count;
+  float* o;
+  int64_t o_row_stride;
+};
+
+// Receptive field of the decoder in whole z-frames (mbv_decoder_context): the interval of z-frames any sample of
+// frame t can depend on is [t - L, t + R].  Walked backwards, layer by layer, from the samples of one frame far
+// from both edges; every index interval is at the rate of the layer it belongs to.
+struct Span { int64_t lo, hi; };
+static Span span_conv(Span y, int K, int dil, int pad_left) { return {y.lo - pad_left, y.hi + (int64_t)(K - 1) * dil - pad_left}; }
+static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+static int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+// ConvTranspose1d(k, stride u, padding p): y[j] = sum_i x[i] w[j + p - u i], 0 <= j + p - u i < k
+static Span span_convt(Span y, int k, int u, int p) { return {ceil_div(y.lo + p - k + 1, u), floor_div(y.hi + p, u)}; }
+static Span span_union(Span a, Span b) { return {a.lo < b.lo ? a.lo : b.lo, a.hi > b.hi ? a.hi : b.hi}; }
+
+int decoder_context(const mbv_config& c, int* Lc, int* Rc) {
+  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
+  const int us = sb ? 8 : 4, kUp = 16;                  // ups: ConvTranspose1d(k 16, stride us, padding (16 - us) / 2)
+  const int kPre = 7, kPost = 7;                        // conv_pre, conv_post / subband_conv_post (models.py)
+  const int n_fft = 16, hop = 4;                        // TorchSTFT (center = True)
+  const int bands = sb ? 1 : 4, taps = 63;              // PQMF synthesis / multistream_conv_post: 63 taps, pad 31
+  const int64_t spf = (int64_t)us * us * hop * bands;   // waveform samples per z-frame
+  const int64_t t = 1 << 20;                            // a frame far from both edges
+  Span x{spf * t, spf * t + spf - 1};                   // the waveform samples of frame t
+  if (!sb) x = {ceil_div(x.lo - taps / 2, bands), floor_div(x.hi + taps / 2, bands)};   // sub-band samples (zero-stuffed x bands)
+  // iSTFT, center: output sample m is position m + n_fft / 2 of the overlap-add; frame f covers [hop f, hop f + n_fft)
+  x = {ceil_div(x.lo + n_fft / 2 - (n_fft - 1), hop), floor_div(x.hi + n_fft / 2, hop)};
+  // conv_post over ReflectionPad1d((1, 0)): frame f reads padded[f - 3 .. f + 3] = x[f - 4 .. f + 2]
+  x = span_conv(x, kPost, 1, (kPost - 1) / 2 + 1);
+  for (int i = 1; i >= 0; --i) {
+    Span need = x;                                      // xs / 3 of the three ResBlocks (and each one's skip path)
+    for (int j = 0; j < 3; ++j) {
+      Span r = x;
+      const int k = c.resblock_kernel_sizes[j];
+      const int nconv = c.resblock_type == 2 ? 2 : 3;
+      for (int q = nconv - 1; q >= 0; --q) {          // each step: x = conv(...)(x) + x
+        const int d = c.resblock_dilations[j][q];
+        if (c.resblock_type != 2) r = span_conv(r, k, 1, (k - 1) / 2);
+        r = span_conv(r, k, d, (k - 1) * d / 2);
+      }
+      need = span_union(need, r);
+    }
+    x = span_convt(need, kUp, us, (kUp - us) / 2);
+  }
+  x = span_conv(x, kPre, 1, (kPre - 1) / 2);
+  *Lc = (int)(t - x.lo);
+  *Rc = (int)(x.hi - t);
+  return 0;
+}
+
 int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, const float* gvec,
-                int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc) {
+                int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc, const DecodeRange* rg = nullptr) {
   const mbv_config& c = m->cfg;
+  // ranged decode, default mode: the length rules of the conv planner see the one-shot lengths (conv1d_plan)
+  const int rt_num = rg && !m->splitk ? rg->t_full : 0;
   const int I = c.inter_channels, C0 = c.upsample_initial_channel, gin = c.gin_channels;
   hipStream_t const s_main = s;
   if (sc.off + decoder_scratch_bytes(c, B, Td) > sc.cap) return m->fail("internal error: decoder scratch arena undersized");
@@ -1003,7 +1061,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     a.x_rstride = zstride;
     a.in_lens = zlens;
     with_trim(a, 1, 0);
-    launch_conv1d(a, s);
+    launch_conv1d(a, s, rt_num);
   }
   m->stages["dec_conv_pre"] = {x0, (int64_t)B * C0 * Td};
   const float* cur = x0;
@@ -1092,7 +1150,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
             a.out_scale = j == 2 ? (1.f / 3.f) : 1.f;
           }
           with_trim(a, Lo / Td, 0);
-          launch_conv1d(a, s);
+          launch_conv1d(a, s, rt_num * (Lo / Td));
           state = r;
         }
         continue;
@@ -1105,7 +1163,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           if (q == 0) a.chan_add = cadd;
           own_ws(a);
           with_trim(a, Lo / Td, 0);
-          launch_conv1d(a, s);
+          launch_conv1d(a, s, rt_num * (Lo / Td));
         }
         {
           ConvArgs a = conv_args(m, R.c2[q], t1, (int64_t)ch * Lo, Lo, r, (int64_t)ch * Lo, Lo, B, 1);
@@ -1123,7 +1181,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           }
           own_ws(a);
           with_trim(a, Lo / Td, 0);
-          launch_conv1d(a, s);
+          launch_conv1d(a, s, rt_num * (Lo / Td));
           if (conc && q == 2) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
         }
         state = r;
@@ -1155,9 +1213,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   if (Bc < 1) Bc = 1;
   if (Bc > B) Bc = B;
   float* xpost = sc.take<float>((size_t)Bc * prow * Fr);
-  float* o = outs ? outs->o : nullptr;
+  float* o = rg ? rg->o : outs ? outs->o : nullptr;
   float* otmp = nullptr;
   if (!o) { otmp = sc.take<float>((size_t)B * 256 * Td); o = otmp; }
+  // ranged: window sub-band samples (MB / MS) or output quads (SB) of the kept frames, 64 per z-frame either way
+  const IstftRange keep{rg ? 64 * rg->keep_first : 0, rg ? 64 * (rg->keep_first + rg->keep_count) : 0,
+                        rg ? rg->o_row_stride : 0};
   const int64_t M4 = (int64_t)(sb ? 4 : 256) * (sb ? (Fr - 1) : Td);          // waveform samples per utterance
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int nb = B - b0 < Bc ? B - b0 : Bc;
@@ -1176,7 +1237,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.spec = outs && outs->spec ? outs->spec + (size_t)b0 * 9 * Fr : nullptr;
       ia.phase = outs && outs->phase ? outs->phase + (size_t)b0 * 9 * Fr : nullptr;
       ia.B = nb; ia.F = Fr; ia.exact_math = m->exact_math; ia.prescaled = 1;
-      launch_istft_single(ia, s);
+      if (rg) {
+        ia.o = o + (size_t)b0 * rg->o_row_stride; ia.spec = ia.phase = nullptr;
+        launch_istft_single_range(ia, keep, s);
+      } else {
+        launch_istft_single(ia, s);
+      }
     } else {
       IstftArgs ia{};
       const bool ms = c.decoder == MBV_DEC_MULTISTREAM;
@@ -1187,7 +1253,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.B = nb; ia.Tp = Td; ia.multistream = ms;
       ia.fixed_bank = !ia.multistream; ia.exact_math = m->exact_math; ia.prescaled = 1;
       if (trim && nb == B && !ia.o_mb && !ia.spec && !ia.phase) ia.trim_lens = zlens;
-      launch_istft_pqmf(ia, s);
+      if (rg) {
+        ia.o = o + (size_t)b0 * rg->o_row_stride; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
+        launch_istft_pqmf_range(ia, keep, s);
+      } else {
+        launch_istft_pqmf(ia, s);
+      }
     }
   }
   if (Bc == B) m->stages["x_post"] = {xpost, (int64_t)B * prow * Fr};     // (a split run keeps only its last chunk)
@@ -1811,6 +1882,50 @@ int mbv_decode(mbv_model* m, const float* z, const float* g, int B, int t_frames
   m->stages.clear();
   if (run_decoder(m, z, t_frames, nullptr, (g && c.gin_channels) ? g : nullptr, B, t_frames, outs,
                   (hipStream_t)stream, sc))
+    return 1;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_decoder_context(const mbv_config* cfg, int32_t out[2]) {
+  if (!cfg || !out) return 1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return 1;
+  int L = 0, R = 0;
+  if (decoder_context(*cfg, &L, &R)) return 1;
+  out[0] = L;
+  out[1] = R;
+  return 0;
+}
+
+int mbv_decode_range(mbv_model* m, const float* z, const float* g, int B, int t_frames, int first, int count,
+                     float* o, int64_t o_row_stride, void* stream) {
+  if (!m) return 1;
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!z || !o || B <= 0 || t_frames <= 0) return m->fail("mbv_decode_range: bad arguments");
+  if (first < 0 || count <= 0 || first >= t_frames || count > t_frames - first)
+    return m->fail("mbv_decode_range: frames [%d, %d + %d) outside [0, %d)", first, first, count, t_frames);
+  const mbv_config& c = m->cfg;
+  const int64_t spf = 256;
+  if (o_row_stride < spf * t_frames)
+    return m->fail("mbv_decode_range: o_row_stride %lld < %lld samples per row", (long long)o_row_stride,
+                   (long long)(spf * t_frames));
+  if ((o_row_stride & 3) || ((uintptr_t)o & 15))
+    return m->fail("mbv_decode_range: o must be 16-byte aligned and o_row_stride a multiple of 4");
+  int Lc = 0, Rc = 0;
+  decoder_context(c, &Lc, &Rc);
+  const int wa = first - Lc > 0 ? first - Lc : 0;
+  const int wb = (int64_t)first + count + Rc < t_frames ? first + count + Rc : t_frames;
+  const int Tw = wb - wa;
+  DEVICE_GUARD(m);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, decoder_scratch_bytes(c, B, Tw))) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  m->stages.clear();
+  // the window [wa, wb) of the caller's z: conv_pre reads Tw frames at row stride t_frames, zeros beyond (a window
+  // edge is padded exactly as a stand-alone decode pads its edges); the samples of frames within L / R of a window
+  // edge that is not an utterance edge are not stored
+  const DecodeRange rg{t_frames, first - wa, count, o + spf * first, o_row_stride};
+  if (run_decoder(m, z + wa, t_frames, nullptr, (g && c.gin_channels) ? g : nullptr, B, Tw, nullptr,
+                  (hipStream_t)stream, sc, &rg))
     return 1;
   HIPCHK(m, hipGetLastError());
   return 0;

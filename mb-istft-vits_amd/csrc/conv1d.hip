@@ -1095,7 +1095,7 @@ static void launch_ck(const ConvArgs& a, hipStream_t s) {
 }
 
 // The route of a launch (launch_conv1d executes it; conv1d_trim_bn and the tests read it).
-ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed) {
+ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   ConvPlan p{};
   p.S = 1;
   // conv1d_narrow.hip (32-column units, rows split over waves, weights from L2) takes over where the
@@ -1118,7 +1118,7 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed) {
       if (a.splitk && tiles128 <= 128) {
         static const int min_units = [] { const char* e = getenv("MBV_NARROW_MIN_UNITS"); return e ? atoi(e) : 16; }();
         if (units32 >= min_units || narrow == 2) { p.route = CONV_NARROW_LAUNCH; return p; }
-      } else if (a.T <= 256 || narrow == 2) {
+      } else if ((route_T > 0 ? route_T : a.T) <= 256 || narrow == 2) {
         p.route = CONV_NARROW_M;
         return p;
       }
@@ -1224,14 +1224,14 @@ int conv1d_trim_bn(const ConvArgs& a) {
   return conv1d_plan(a, true).bn;
 }
 
-void launch_conv1d(const ConvArgs& a, hipStream_t s) {
+void launch_conv1d(const ConvArgs& a, hipStream_t s, int route_T) {
   // (the residual / running-sum start values are read through a 32-bit buffer view of one utterance, conv_acc_init)
   if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32)) {
     fprintf(stderr, "mbv: conv1d: one utterance's [%d x %d] output exceeds 4 GiB\n", a.M, a.T);
     abort();
   }
   if (a.epi == EPI_LN && !conv1d_narrow_supported(a)) { fprintf(stderr, "mbv: EPI_LN outside the narrow kernel's range\n"); abort(); }
-  const ConvPlan p = conv1d_plan(a);
+  const ConvPlan p = conv1d_plan(a, a.trim_map != nullptr, route_T);
   switch (p.route) {
     case CONV_NARROW_M: launch_conv1d_narrow(a, false, s); return;
     case CONV_NARROW_LAUNCH: launch_conv1d_narrow(a, true, s); return;

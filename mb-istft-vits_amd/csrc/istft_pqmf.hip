@@ -182,9 +182,12 @@ __device__ __forceinline__ void irfft16_hann(const float* re, const float* im, f
 
 // `taps` (device, 256 floats, only read by the trainable-bank variant):
 //   t[band][p][i] = 4 h[band][3 - p + 4 i]   (x4 up-sampling gain folded in; 0 where the tap is > 62)
-template <int TM, int NTHREADS, bool FIXED, bool FAST, bool PRE, bool POLAR>
+// RANGED (launch_istft_pqmf_range): the grid holds only the tiles that cover sub-band samples [rg.keep_lo,
+// rg.keep_hi) of every row, phase C stores only those (at a.o + b rg.o_row_stride + 4 (m - keep_lo)), and nothing
+// else is written.  (rg is the last argument, so that the one-shot instantiations keep their code.)
+template <int TM, int NTHREADS, bool FIXED, bool FAST, bool PRE, bool POLAR, bool RANGED = false>
 __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) void istft_pqmf_kernel(const IstftArgs a, const float* __restrict__ taps,
-                                                              int tiles_per_utt, int total_tiles) {
+                                                              int tiles_per_utt, int total_tiles, const IstftRange rg) {
   constexpr int NF = TM / 4 + 7;          // frames a tile touches per band
   constexpr int NFS = ((NF + 31) / 32) * 32 + 8;   // LDS frame stride, == 8 (mod 32): conflict-free phase B
   constexpr int YL = TM + 16;             // sub-band samples incl. PQMF halo
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
     tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
   }
   const int b = tile / tiles_per_utt;
-  const int m0 = (tile % tiles_per_utt) * TM;
+  const int m0 = ((tile % tiles_per_utt) + (RANGED ? rg.keep_lo / TM : 0)) * TM;
   // opt-in trimmed decode: sub-band samples at and beyond 64 * trim_lens[b] belong to no valid frame; a tile
   // wholly beyond is not computed (the caller zero-filled o), the tile across the boundary stores zeros there
   const int m_valid = a.trim_lens ? 64 * a.trim_lens[b] : 0x7fffffff;
@@ -246,6 +249,8 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
         for (int k = 0; k < 18; ++k)
           xin[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, voff, k * F * 4, 0));
         // frame f is owned (for the spec/phase outputs) by the tile holding sample 4f
+        // (RANGED: a.spec / a.phase are null at run time.  The stores stay in the code, so that the values they would
+        // store keep the uses, and with them the fused multiply-adds, of the one-shot kernel: bitwise the same samples.)
         const bool own = (4 * f >= m0 && 4 * f < m0 + TM) || (f == F - 1 && m0 + TM >= M);
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
@@ -302,7 +307,7 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
           s += fr[(band * 16 + 12 - 4 * g + r) * NFS + q + g];
         y[band] = s * renv;
       }
-      if (a.o_mb && u >= 8 && u < TM + 8) {          // owned samples m0 .. m0+TM-1
+      if (a.o_mb && u >= 8 && u < TM + 8) {          // (RANGED: null at run time, kept in the code as above)          // owned samples m0 .. m0+TM-1
         if (!a.multistream) {
           if (a.nt_stores) {
 #pragma unroll
@@ -374,8 +379,14 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
           }
         }
       }
-      *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * M + 4 * (int64_t)m) =
-          m < m_valid ? make_float4(acc[0], acc[1], acc[2], acc[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (RANGED) {
+        if (m >= rg.keep_lo && m < rg.keep_hi)
+          *reinterpret_cast<float4*>(a.o + (int64_t)b * rg.o_row_stride + 4 * (int64_t)(m - rg.keep_lo)) =
+              make_float4(acc[0], acc[1], acc[2], acc[3]);
+      } else {
+        *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * M + 4 * (int64_t)m) =
+            m < m_valid ? make_float4(acc[0], acc[1], acc[2], acc[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   }
 }
@@ -387,7 +398,7 @@ static void launch_istft_pqmf_t(const IstftArgs& a, hipStream_t s) {
   const int total = tiles_per_utt * a.B;
   const dim3 grid(total), block(NT);
 #define MBV_ISTFT_LAUNCH(FIXED, FAST, PRE, POLAR) \
-  hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, FIXED, FAST, PRE, POLAR>), grid, block, 0, s, a, a.filt, tiles_per_utt, total)
+  hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, FIXED, FAST, PRE, POLAR>), grid, block, 0, s, a, a.filt, tiles_per_utt, total, IstftRange{})
   if (a.polar_in) {          // (spec, phase) input: a.spec / a.phase are read, not written
     const int v = (a.fixed_bank ? 2 : 0) | (a.exact_math ? 0 : 1);
     switch (v) {
@@ -434,20 +445,39 @@ void launch_istft_pqmf(const IstftArgs& a_in, hipStream_t s) {
   else launch_istft_pqmf_t<480, 512>(a, s);
 }
 
+// The streaming decode's tail (mbv_decode_range): x_post of a z-window, only the chunk's samples stored.  Every
+// kept sample is computed by the same operations as in the one-shot launch (a tile's position changes no sample's
+// arithmetic), so it is bitwise the one-shot sample whenever x_post is.
+void launch_istft_pqmf_range(const IstftArgs& a, const IstftRange& r, hipStream_t s) {
+  constexpr int TM = 480, NT = 512;
+  const int tiles_per_utt = (r.keep_hi + TM - 1) / TM - r.keep_lo / TM;
+  const int total = tiles_per_utt * a.B;
+  const dim3 grid(total), block(NT);
+  const int v = (a.fixed_bank ? 2 : 0) | (a.exact_math ? 0 : 1);      // (x_post is always prescaled here)
+  switch (v) {
+    case 0: hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, false, false, true, false, true>), grid, block, 0, s, a, a.filt, tiles_per_utt, total, r); break;
+    case 1: hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, false, true, true, false, true>), grid, block, 0, s, a, a.filt, tiles_per_utt, total, r); break;
+    case 2: hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, true, false, true, false, true>), grid, block, 0, s, a, a.filt, tiles_per_utt, total, r); break;
+    default: hipLaunchKernelGGL((istft_pqmf_kernel<TM, NT, true, true, true, false, true>), grid, block, 0, s, a, a.filt, tiles_per_utt, total, r); break;
+  }
+}
+
 // ============================================================================
 // Single-band tail of iSTFT_Generator (models.py:296-300): exp / pi*sin, TorchSTFT.inverse
 // (n_fft 16, hop 4), no filter bank.  Phase A: one lane per frame (255 frames per workgroup);
 // phase B: one lane per quad of output samples (252 quads): overlap-add of the 4 covering
 // frames, edge-aware envelope, one 16-byte store.
 // ============================================================================
-template <bool FAST, bool PRE, bool POLAR>
-__global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, int tiles_per_utt) {
+// RANGED (launch_istft_single_range): only the tiles that cover quads [rg.keep_lo, rg.keep_hi), only those stored,
+// at a.o + b rg.o_row_stride + 4 (q - keep_lo)
+template <bool FAST, bool PRE, bool POLAR, bool RANGED = false>
+__global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, int tiles_per_utt, const IstftRange rg) {
   constexpr int QPB = 252;                 // output quads per workgroup
   constexpr int NFS = 256;
   __shared__ float fr[16 * NFS];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / tiles_per_utt;
-  const int q0 = (blockIdx.x % tiles_per_utt) * QPB;
+  const int q0 = ((blockIdx.x % tiles_per_utt) + (RANGED ? rg.keep_lo / QPB : 0)) * QPB;
   const int F = a.F;
   const int nquads = F - 1;                // 4 (F-1) output samples
 
@@ -466,7 +496,7 @@ __global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, 
         float xin[18];
 #pragma unroll
         for (int k = 0; k < 18; ++k) xin[k] = xp[(int64_t)k * F];
-        const bool own = f >= q0 && (f < q0 + QPB || f == F - 1);
+        const bool own = f >= q0 && (f < q0 + QPB || f == F - 1);     // (RANGED: spec / phase null, see istft_pqmf_kernel)
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
           float mag, ph;
@@ -500,8 +530,14 @@ __global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, 
       }
       y[r] = sacc / env;
     }
-    *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * nquads + 4 * (int64_t)fp) =
-        make_float4(y[0], y[1], y[2], y[3]);
+    if constexpr (RANGED) {
+      if (fp >= rg.keep_lo && fp < rg.keep_hi)
+        *reinterpret_cast<float4*>(a.o + (int64_t)b * rg.o_row_stride + 4 * (int64_t)(fp - rg.keep_lo)) =
+            make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+      *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * nquads + 4 * (int64_t)fp) =
+          make_float4(y[0], y[1], y[2], y[3]);
+    }
   }
 }
 
@@ -509,17 +545,24 @@ void launch_istft_single(const IstftSbArgs& a, hipStream_t s) {
   const int tiles = (a.F - 1 + 251) / 252;
   const dim3 grid(tiles * a.B), block(256);
   if (a.polar_in) {
-    if (a.exact_math) hipLaunchKernelGGL((istft_single_kernel<false, false, true>), grid, block, 0, s, a, tiles);
-    else hipLaunchKernelGGL((istft_single_kernel<true, false, true>), grid, block, 0, s, a, tiles);
+    if (a.exact_math) hipLaunchKernelGGL((istft_single_kernel<false, false, true>), grid, block, 0, s, a, tiles, IstftRange{});
+    else hipLaunchKernelGGL((istft_single_kernel<true, false, true>), grid, block, 0, s, a, tiles, IstftRange{});
     return;
   }
   const int variant = (a.exact_math ? 0 : 2) | (a.prescaled ? 1 : 0);
   switch (variant) {
-    case 0: hipLaunchKernelGGL((istft_single_kernel<false, false, false>), grid, block, 0, s, a, tiles); break;
-    case 1: hipLaunchKernelGGL((istft_single_kernel<false, true, false>), grid, block, 0, s, a, tiles); break;
-    case 2: hipLaunchKernelGGL((istft_single_kernel<true, false, false>), grid, block, 0, s, a, tiles); break;
-    default: hipLaunchKernelGGL((istft_single_kernel<true, true, false>), grid, block, 0, s, a, tiles); break;
+    case 0: hipLaunchKernelGGL((istft_single_kernel<false, false, false>), grid, block, 0, s, a, tiles, IstftRange{}); break;
+    case 1: hipLaunchKernelGGL((istft_single_kernel<false, true, false>), grid, block, 0, s, a, tiles, IstftRange{}); break;
+    case 2: hipLaunchKernelGGL((istft_single_kernel<true, false, false>), grid, block, 0, s, a, tiles, IstftRange{}); break;
+    default: hipLaunchKernelGGL((istft_single_kernel<true, true, false>), grid, block, 0, s, a, tiles, IstftRange{}); break;
   }
+}
+
+void launch_istft_single_range(const IstftSbArgs& a, const IstftRange& r, hipStream_t s) {
+  const int tiles = (r.keep_hi + 251) / 252 - r.keep_lo / 252;
+  const dim3 grid(tiles * a.B), block(256);
+  if (a.exact_math) hipLaunchKernelGGL((istft_single_kernel<false, true, false, true>), grid, block, 0, s, a, tiles, r);
+  else hipLaunchKernelGGL((istft_single_kernel<true, true, false, true>), grid, block, 0, s, a, tiles, r);
 }
 
 }  // namespace mbv

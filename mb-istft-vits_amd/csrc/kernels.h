@@ -112,9 +112,13 @@ struct ConvPlan {
   int S;                    // split-K factor (1: none)
 };
 // trimmed: plan for a launch with a trim map (default: a.trim_map != nullptr)
-ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed);
+// route_T > 0: the length the rule "T <= 256 -> narrow kernel" sees instead of a.T.  The ranged decode
+// (mbv_decode_range) passes the one-shot decode's length, so that a conv over a z-window runs the same chain of
+// operations as the conv over the whole utterance (the narrow kernel starts its sums from the bias, the tiled
+// kernels add it last).
+ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T = 0);
 inline ConvPlan conv1d_plan(const ConvArgs& a) { return conv1d_plan(a, a.trim_map != nullptr); }
-void launch_conv1d(const ConvArgs& a, hipStream_t s);     // executes conv1d_plan(a)
+void launch_conv1d(const ConvArgs& a, hipStream_t s, int route_T = 0);     // executes conv1d_plan(a, ., route_T)
 bool conv1d_supported(int K, int dil);   // kernel sizes / dilations the MFMA kernel is built for
 // conv1d_narrow.hip: the same contraction in 32-column x row-block units (launches with few columns)
 bool conv1d_narrow_supported(const ConvArgs& a);
@@ -254,6 +258,17 @@ struct IstftArgs {
                          // (the caller zero-fills o; o_mb / spec / phase must be null)
 };
 void launch_istft_pqmf(const IstftArgs& a, hipStream_t s);
+// Ranged output of the waveform tails (the streaming decode, mbv_decode_range): only the tiles that cover the kept
+// samples exist, only those are stored, nothing else is written (IstftArgs: o_mb / spec / phase / trim_lens null,
+// x_post prescaled; IstftSbArgs: spec / phase null).  MB / MS: sub-band samples [keep_lo, keep_hi), sample 4 m + p
+// of row b at o[b * o_row_stride + 4 (m - keep_lo) + p]; SB: output quads [keep_lo, keep_hi), quad q at
+// o[b * o_row_stride + 4 (q - keep_lo)].  o is already offset to the chunk's first sample.  (A separate
+// argument, so that the one-shot kernels keep their argument layout and code.)
+struct IstftRange {
+  int keep_lo, keep_hi;
+  int64_t o_row_stride;
+};
+void launch_istft_pqmf_range(const IstftArgs& a, const IstftRange& r, hipStream_t s);
 
 // single-band iSTFT (iSTFT_Generator, models.py:296-300): x_post [B, 18, F] -> o [B, 4 (F-1)]
 struct IstftSbArgs {
@@ -266,6 +281,7 @@ struct IstftSbArgs {
   int polar_in;          // 1: spec / phase [B,9,F] are the input
 };
 void launch_istft_single(const IstftSbArgs& a, hipStream_t s);
+void launch_istft_single_range(const IstftSbArgs& a, const IstftRange& r, hipStream_t s);
 
 // x_post rows back to the reference's units (stage introspection): inverse of the pre-scaling
 void launch_unscale_xpost(const float* src, float* dst, int B, int rows, int F, hipStream_t s);

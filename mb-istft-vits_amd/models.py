@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _capi
+from . import _capi, stream
 from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
 
 # librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
@@ -190,22 +190,7 @@ class SynthesizerTrn(nn.Module):
             L.mbv_destroy(self._handle)
             self._handle, self._synced_sig = None, None
         if self._handle is None:
-            c = _capi.MbvConfig()
-            c.struct_bytes = C.sizeof(_capi.MbvConfig)
-            cfg = self.cfg
-            c.n_vocab, c.inter_channels, c.hidden_channels = cfg.n_vocab, cfg.inter_channels, cfg.hidden_channels
-            c.filter_channels, c.n_heads, c.n_layers = cfg.filter_channels, cfg.n_heads, cfg.n_layers
-            c.kernel_size, c.upsample_initial_channel = cfg.kernel_size, cfg.upsample_initial_channel
-            c.spec_channels = cfg.spec_channels
-            for j in range(3):
-                c.resblock_kernel_sizes[j] = cfg.resblock_kernel_sizes[j]
-                for q, d in enumerate(cfg.resblock_dilation_sizes[j]):
-                    c.resblock_dilations[j][q] = d
-            c.resblock_type = int(cfg.resblock)
-            c.n_speakers, c.gin_channels = cfg.n_speakers, cfg.gin_channels
-            c.decoder = int(cfg.decoder)
-            c.device = idx
-            c.use_sdp = int(bool(cfg.use_sdp))
+            c = self._config_struct(idx)
             h = C.c_void_p()
             rc = L.mbv_create(C.byref(c), C.byref(h))
             if rc:
@@ -216,6 +201,25 @@ class SynthesizerTrn(nn.Module):
             self._upload_weights()
             self._synced_sig = sig
         return self._handle
+
+    def _config_struct(self, device_index=0):
+        c = _capi.MbvConfig()
+        c.struct_bytes = C.sizeof(_capi.MbvConfig)
+        cfg = self.cfg
+        c.n_vocab, c.inter_channels, c.hidden_channels = cfg.n_vocab, cfg.inter_channels, cfg.hidden_channels
+        c.filter_channels, c.n_heads, c.n_layers = cfg.filter_channels, cfg.n_heads, cfg.n_layers
+        c.kernel_size, c.upsample_initial_channel = cfg.kernel_size, cfg.upsample_initial_channel
+        c.spec_channels = cfg.spec_channels
+        for j in range(3):
+            c.resblock_kernel_sizes[j] = cfg.resblock_kernel_sizes[j]
+            for q, d in enumerate(cfg.resblock_dilation_sizes[j]):
+                c.resblock_dilations[j][q] = d
+        c.resblock_type = int(cfg.resblock)
+        c.n_speakers, c.gin_channels = cfg.n_speakers, cfg.gin_channels
+        c.decoder = int(cfg.decoder)
+        c.device = device_index
+        c.use_sdp = int(bool(cfg.use_sdp))
+        return c
 
     def _upload_weights(self):
         L = _capi.lib()
@@ -511,6 +515,50 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.device(dev):
             _capi.check(h, _capi.lib().mbv_decode(h, self._ptr(z), self._ptr(g), B, Tp, C.byref(out),
                                                   self._stream()), "mbv_decode")
+
+    # ------------------------------------------------------------------ streaming decode (stream.py)
+    def decoder_context(self):
+        """(L, R): the z-frames of left / right context any output sample of frame t depends on, [t - L, t + R]
+        (`mbv_decoder_context`, host only: no GPU needed)."""
+        return stream.decoder_context(self._config_struct())
+
+    def dec_stream(self, z, g=None, chunk_frames=32, max_chunk_frames=256):
+        """`dec(z, g)[0]` chunk by chunk: a `stream.DecodeStream` whose iteration yields (first_sample, o[:, :, a:b])
+        views of one full-length `o`, one `mbv_decode_range` call per chunk.  Chunks start at `chunk_frames` and
+        double up to `max_chunk_frames`.  The concatenation is bitwise `dec(z, g)[0]` (default mode)."""
+        h = self._ensure_handle()
+        dev = self._device()
+        if z.dim() != 3 or z.shape[1] != self.cfg.inter_channels:
+            raise ValueError("z must be [B, %d, T']" % self.cfg.inter_channels)
+        z = z.to(device=dev, dtype=torch.float32).contiguous()
+        B = z.shape[0]
+        if g is not None:
+            if self.cfg.gin_channels == 0:
+                g = None
+            else:
+                g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
+        return stream.DecodeStream(self, h, z, g, chunk_frames, max_chunk_frames)
+
+    @torch.no_grad()
+    def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
+                     chunk_frames=32, max_chunk_frames=256):
+        """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
+        flows exactly as `infer` does (same random draws), then returns `dec_stream` of z * y_mask (truncated to
+        max_len) with `y_lengths` set on the stream.  The concatenation is bitwise `infer(...)[0]` (default mode)."""
+        r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
+                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"))
+        y_mask, z, y_lengths = r[5], r[6][0], r[8]
+        Tp = z.shape[2]
+        Td = Tp if max_len is None else max(0, min(Tp, int(max_len)))
+        if Td <= 0:
+            raise ValueError("max_len leaves no frames to decode")
+        zd = (z * y_mask)[:, :, :Td].contiguous()
+        g = None
+        if self.n_speakers > 0:
+            g = self._speaker_embedding(sid.to(self._device()))
+        st = self.dec_stream(zd, g, chunk_frames, max_chunk_frames)
+        st.y_lengths = y_lengths
+        return st
 
     @torch.no_grad()
     def istft_finalize(self, spec, phase):

@@ -397,7 +397,7 @@ typedef struct mbv_conv_desc {
   int32_t trim_num, trim_add;
   int32_t splitk;                 /* 1: split-K allowed (mbv_op_conv: also when the handle's option "splitk" is on, unless trimmed) */
   int32_t prec;                   /* 0 exact fp32, 3 split-bf16 (as mbv_set_option "conv_bf16") */
-  int32_t legacy_convt;           /* 1: a ConvTranspose on the stand-alone ConvTranspose kernel (no epilogue options) */
+  int32_t legacy_convt;           /* must be 0 (a kernel that is gone; the slot keeps the layout) */
   int64_t ws_floats;              /* mbv_conv_plan only: the handle's split-K workspace (mbv_op_conv uses its own) */
   int32_t n_counters;             /* ... and ticket counters */
 } mbv_conv_desc;
@@ -411,7 +411,6 @@ typedef struct mbv_conv_desc {
 #define MBV_ROUTE_BIG 6
 #define MBV_ROUTE_SPLIT_BATCH 7
 #define MBV_ROUTE_VS 8
-#define MBV_ROUTE_LEGACY_CONVT 9
 /* plan_out may be NULL. */
 int mbv_op_conv(mbv_model *m, const mbv_conv_desc *d, const float *x, const float *w_host, const float *bias_host,
                 float *y, int32_t *plan_out, void *stream);

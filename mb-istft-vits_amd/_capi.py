@@ -60,8 +60,7 @@ class MbvConvDesc(C.Structure):
 # MBV_CONV_KIND_* / MBV_CONV_EPI_* / MBV_ROUTE_* of include/mbistft_vits.h
 CONV_KIND_CONV, CONV_KIND_CONVT4, CONV_KIND_CONVT8 = 0, 4, 8
 CONV_EPI_STORE, CONV_EPI_RESID, CONV_EPI_RESID_ACC = 0, 1, 2
-ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS",
-          9: "LEGACY_CONVT"}
+ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS"}
 PLAN_FIELDS = ("route", "bm", "bn", "threads", "ck", "nb_big", "vs_tv", "S")
 
 

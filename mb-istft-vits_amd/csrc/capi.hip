@@ -82,8 +82,7 @@ struct mbv_model {
   PConv conv_pre, conv_post;
   static constexpr int kEncQLayers = 16;     // models.py:646
   struct EncQ { PConv pre, proj, in[kEncQLayers], rs[kEncQLayers], in16[kEncQLayers], rsp[kEncQLayers]; PVec cw, cb; int cin_pad = 0; } encq;
-  struct Up { size_t w = 0, bias = 0; int Cin = 0, Cout = 0, Mpad = 0; } ups[2];
-  PConv upc[2];              // stride-4 ups as 5-tap convs over the output phases (EPI_CONVT)
+  PConv upc[2];              // ups (ConvTranspose1d k 16, stride us) as (16/us + 1)-tap convs over the output phases (EPI_CONVT)
   struct RB { PConv c1[3], c2[3]; PVec cw, cb; } rb[6];
   PVec emb_g;
   PVec filt;                 // synthesis-bank table of the fused iSTFT+PQMF kernel (352 floats)
@@ -384,21 +383,8 @@ void pack_conv_rows(const float* w, int Cin, int K, const int* rows, int M, cons
     }
 }
 
-// ConvTranspose1d(k = 16, stride us, padding (16 - us) / 2), w [Cin][Cout][16] (reference layout), for the stand-alone
-// ConvTranspose kernel: dst = Wt[r][j][Cin][Mpad] (kernels.h ConvTArgs), columns >= Cout left as they are
-void pack_convt_phases(const float* w, int Cin, int Cout, int us, int Mpad, float* dst) {
-  const int tpp = 16 / us, pad = (16 - us) / 2;
-  for (int r = 0; r < us; ++r)
-    for (int j = 0; j < tpp; ++j) {
-      const int k = (r + pad) % us + us * j;
-      for (int ci = 0; ci < Cin; ++ci) {
-        float* d = dst + ((size_t)(r * tpp + j) * Cin + ci) * Mpad;
-        for (int co = 0; co < Cout; ++co) d[co] = w[((size_t)ci * Cout + co) * 16 + k];
-      }
-    }
-}
-
-// The same ConvTranspose1d as ONE (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT):
+// ConvTranspose1d(k = 16, stride us, padding (16 - us) / 2), w [Cin][Cout][16] (reference layout), as ONE
+// (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT):
 //   y[co, us m + r] = sum_ci sum_j W[ci][co][kr + us j] x[ci, m + sh_r - j],  kr = (r + pad) % us,
 //   sh_r = (r + pad - kr) / us;  tap tau reads x[m - pl + tau]  ->  j = sh_r + pl - tau, with
 //   pl = tpp - 1 - pad / us  (us 4: 5 taps, pl 2;  us 8: 3 taps, pl 1).
@@ -834,25 +820,18 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
     snprintf(p, sizeof p, "dec.ups.%d", i);
     const std::vector<float> w = P.dense(p);            // [Cin][Cout][16], norm per Cin
     const auto& sh = P.t(std::string(p) + ".weight_v").shape;
-    auto& U = m->ups[i];
-    U.Cin = (int)sh[0]; U.Cout = (int)sh[1]; U.Mpad = (int)align_up(U.Cout, 64);
-    U.w = P.alloc((size_t)16 * U.Cin * U.Mpad);
+    const int Cin = (int)sh[0], Cout = (int)sh[1];
     const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4;        // stride; k = 16, pad = (16-us)/2
-    pack_convt_phases(w.data(), U.Cin, U.Cout, us, U.Mpad, &arena[U.w]);
-    U.bias = P.vec(std::string(p) + ".bias").off;
-    if ((us == 4 || us == 8) && U.Cout % 32 == 0 && U.Cin % 16 == 0) {
-      // the same ConvTranspose1d as one (16/us + 1)-tap conv on the conv1d kernel (EPI_CONVT, pack_convt_rows)
-      PConv pc;
-      pc.M = us * U.Cout; pc.Mpad = (int)align_up(pc.M, 128); pc.Cin = U.Cin; pc.K = 16 / us + 1;
-      pc.w = P.alloc((size_t)pc.K * U.Cin * pc.Mpad);
-      pc.bias = P.alloc(pc.M);
-      pc.has_bias = true;
-      pack_convt_rows(w.data(), P.t(std::string(p) + ".bias").data.data(), U.Cin, U.Cout, us, pc.Mpad, &arena[pc.w],
-                      &arena[pc.bias]);
-      m->upc[i] = pc;
-    } else {
-      m->upc[i] = PConv{};
-    }
+    if (Cout % 32 || Cin % 16)
+      return m->fail("%s: ConvTranspose1d %d -> %d channels: the EPI_CONVT conv needs Cout %% 32 == 0 and Cin %% 16 == 0",
+                     p, Cin, Cout);
+    PConv& pc = m->upc[i];
+    pc.M = us * Cout; pc.Mpad = (int)align_up(pc.M, 128); pc.Cin = Cin; pc.K = 16 / us + 1;
+    pc.w = P.alloc((size_t)pc.K * Cin * pc.Mpad);
+    pc.bias = P.alloc(pc.M);
+    pc.has_bias = true;
+    pack_convt_rows(w.data(), P.t(std::string(p) + ".bias").data.data(), Cin, Cout, us, pc.Mpad, &arena[pc.w],
+                    &arena[pc.bias]);
   }
   for (int n = 0; n < 6; ++n) {
     if (c.resblock_type == 1) {
@@ -1087,22 +1066,14 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       rs[j] = conc ? sc.take<float>(n) : rs[0];
     }
     xs = sc.take<float>(n);
-    static const int convt_as_conv = [] { const char* e = getenv("MBV_CONVT_AS_CONV"); return e ? atoi(e) : 1; }();
-    if (m->upc[i].M && convt_as_conv) {
-      ConvArgs a = conv_args(m, m->upc[i], cur, (int64_t)m->ups[i].Cin * L, L, u, (int64_t)ch * Lo, L, B);
+    {
+      ConvArgs a = conv_args(m, m->upc[i], cur, (int64_t)m->upc[i].Cin * L, L, u, (int64_t)ch * Lo, L, B);
       a.pad_left = us == 4 ? 2 : 1;
       a.in_slope = kLrelu;
       a.epi = EPI_CONVT;
       a.convt_u = us;
       with_trim(a, L / Td, 0);                      // tiles run over INPUT frames (rate of the stage below)
       launch_conv1d(a, s);
-    } else {
-      ConvTArgs a{};
-      a.x = cur; a.w = m->W(m->ups[i].w); a.bias = m->W(m->ups[i].bias); a.y = u;
-      a.B = B; a.Cin = m->ups[i].Cin; a.Cout = ch; a.Mpad = m->ups[i].Mpad; a.Tin = L;
-      a.in_slope = kLrelu;
-      a.stride = us;
-      launch_convt(a, s);
     }
     m->stages[i == 0 ? "dec_up_0" : "dec_up_1"] = {u, (int64_t)n};
     if (conc) {
@@ -1275,18 +1246,20 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
 // Fused path (default): one launch per layer over the units that hold valid frames, h ping-pongs
 // between hbuf and acts (the old path's gated-activation buffer); afterwards only `skip` is meaningful,
 // and only where the frame mask is 1 (every reader masks on load).
-// Two-launch path (MBV_WN_FUSED=0; experiments: MBV_WN_SMALL=<tiles> in the low-latency mode): gate conv,
+// Two-launch path (MBV_WN_FUSED=0, and large launches in the split-bf16 mode, see wn_takes_fused): gate conv,
 // then res/skip conv.
 struct WnFold { const PConv* rspf; int Cs; float* x1; int64_t x1_bstride; float sign;
                 const PConv* in16f0; const PConv* pref; int Gi; const float* x0; int in_cb; };   // in16f0 != nullptr: `pre` folded as well
-// can this WN stack take the fused one-launch-per-layer kernel (run_wn's own test; run_coupling asks before it folds `post`)
+// can this WN stack take the fused one-launch-per-layer kernel (run_wn's test; run_coupling asks before it folds `post`)
+// (r02f: the fused layer wins or ties at every size measured, down to one utterance = 9 workgroups —
+// ljs_mini B=1 3.55 -> 3.11 ms, B=8 4.33 -> 3.68, ljs_mb B=8 9.69 -> 9.04, B=1 5.10 -> 5.14.
+// Split-bf16 mode: the two-launch layer on the conv kernel, which has the mode — from ~12 k frames up the
+// gate conv + res/skip conv in split-bf16 beat the fused exact layer: ljs_mb B=64 23.6 -> 22.3 ms per infer,
+// uudb B=32 15.7 -> 14.9; B=16: 8.9 -> 9.0, so smaller launches keep the fused layer.)
 bool wn_takes_fused(const mbv_model* m, const PConv* in_l, const PConv* in16_l, int B, int T) {
   const int H = m->cfg.hidden_channels;
-  static const int small_units = [] { const char* e = getenv("MBV_WN_SMALL"); return e ? atoi(e) : 0; }();
-  const bool small = (long)B * ((T + 31) / 32) < small_units;
-  static const int wn_bf16 = [] { const char* e = getenv("MBV_WN_BF16"); return e ? atoi(e) : 1; }();
-  const bool two_launch_bf16 = wn_bf16 && m->Wsplit(0) != nullptr && (long)B * T >= 12288;
-  return !two_launch_bf16 && m->wn_fused && in16_l[0].M && wn_fused_supported(H, in_l[0].K) && wn_fused_fits(B, H, T) && !(m->splitk && small);
+  const bool two_launch_bf16 = m->Wsplit(0) != nullptr && (long)B * T >= 12288;
+  return !two_launch_bf16 && m->wn_fused && in16_l[0].M && wn_fused_supported(H, in_l[0].K) && wn_fused_fits(B, H, T);
 }
 int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16_l, const PConv* rsp_l, int nl,
            const PVec& cw, const PVec& cb, const float* gvec, float* hbuf, float* acts, float* skip, float* gc,
@@ -1296,17 +1269,7 @@ int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16
   const int64_t bsH = (int64_t)H * T;
   const bool cond = gvec && gin && cw.present;
   if (cond) launch_cond_gemv(gvec, nullptr, nullptr, m->W(cw.off), m->W(cb.off), gc, B, gin, 2 * H * nl, s);
-  // (r02f: the fused layer wins or ties at every size measured, down to one utterance = 9 workgroups —
-  // ljs_mini B=1 3.55 -> 3.11 ms, B=8 4.33 -> 3.68, ljs_mb B=8 9.69 -> 9.04, B=1 5.10 -> 5.14 — so the
-  // two-launch path is only taken when MBV_WN_SMALL asks for it: launches below that many 32-frame tiles)
-  static const int small_units = [] { const char* e = getenv("MBV_WN_SMALL"); return e ? atoi(e) : 0; }();
-  const bool small = (long)B * ((T + 31) / 32) < small_units;
-  // (split-bf16 mode: the two-launch layer on the conv kernel, which has the mode — from ~12 k frames up the
-  // gate conv + res/skip conv in split-bf16 beat the fused exact layer: ljs_mb B=64 23.6 -> 22.3 ms per infer,
-  // uudb B=32 15.7 -> 14.9; B=16: 8.9 -> 9.0, so smaller launches keep the fused layer.  MBV_WN_BF16=0: never)
-  static const int wn_bf16 = [] { const char* e = getenv("MBV_WN_BF16"); return e ? atoi(e) : 1; }();
-  const bool two_launch_bf16 = wn_bf16 && m->Wsplit(0) != nullptr && (long)B * T >= 12288;
-  if (!two_launch_bf16 && m->wn_fused && in16_l[0].M && wn_fused_supported(H, in_l[0].K) && wn_fused_fits(B, H, T) && !(m->splitk && small)) {
+  if (wn_takes_fused(m, in_l, in16_l, B, T)) {
     int* hmap = ustart + B + 1;
     launch_wn_units(lens, B, T, ustart, hmap, s);
     float* hin = hbuf;
@@ -1366,9 +1329,8 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
   const bool flipped = (f % 2) == 1;
   float* x0 = flipped ? z + (size_t)half * T : z;
   float* x1 = flipped ? z : z + (size_t)half * T;
-  static const int fold_env = [] { const char* e = getenv("MBV_FLOW_FOLD"); return e ? atoi(e) : 3; }();   // bit 0: post, bit 1: pre
-  const bool fold_post = (fold_env & 1) && F.rspf[0].M && wn_takes_fused(m, F.in, F.in16, B, T);
-  const bool fold_pre = fold_post && (fold_env & 2) && F.in16f0.M && F.pref.M && wn_fused_fits(B, I, T);   // (x0 is addressed through a whole-tensor view of z)
+  const bool fold_post = F.rspf[0].M && wn_takes_fused(m, F.in, F.in16, B, T);
+  const bool fold_pre = fold_post && F.in16f0.M && F.pref.M && wn_fused_fits(B, I, T);   // (x0 is addressed through a whole-tensor view of z)
   if (!fold_pre) {
     ConvArgs a = conv_args(m, F.pre, x0, bsI, T, hbuf, bsH, T, B);
     a.out_lens = lens;
@@ -1684,10 +1646,9 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
   HIPCHK(m, hipEventRecord(m->ev[0], s));
   launch_embed(ids, lengths, m->W(m->emb.off), x, m->lens32, bad, B, T, H, c.n_vocab, s);
   const int64_t bsH = (int64_t)H * T;
-  static const int fuse_ln_env = [] { const char* e = getenv("MBV_FUSE_LN"); return e ? atoi(e) : 1; }();
   // (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
   // size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
-  const bool fuse_ln = fuse_ln_env && T <= 256 && !(m->splitk && (long)B * ((T + 15) / 16) < 128);
+  const bool fuse_ln = T <= 256 && !(m->splitk && (long)B * ((T + 15) / 16) < 128);
   for (int i = 0; i < c.n_layers; ++i) {
     const auto& L = m->enc[i];
     launch_conv1d(conv_args(m, L.qkv, x, bsH, T, qkv, 3 * bsH, T, B), s);
@@ -2360,19 +2321,14 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   if (d.epi != MBV_CONV_EPI_STORE && !d.res) return "RESID and RESID_ACC need res";
   if (d.epi != MBV_CONV_EPI_STORE && (d.out_lens || d.relu)) return "out_lens / relu belong to STORE";
   if (d.epi != MBV_CONV_EPI_RESID_ACC && d.accum_in) return "accum_in belongs to RESID_ACC";
-  if (d.trim_lens && (d.splitk || d.legacy_convt)) return "a trimmed launch takes neither split-K nor the legacy ConvTranspose";
+  if (d.legacy_convt) return "legacy_convt must be 0 (the stand-alone ConvTranspose kernel was removed)";
+  if (d.trim_lens && d.splitk) return "a trimmed launch takes no split-K";
   const int U = d.kind;
   if (convt) {
     if (d.T != d.Tin) return "ConvTranspose: T must equal Tin (input frames)";
     if (d.epi != MBV_CONV_EPI_STORE || d.out_lens || d.relu || d.reflect1) return "ConvTranspose: plain STORE only";
-    if (d.legacy_convt) {
-      if (d.Cin % 8 || d.x_rstride > d.Tin || d.in_lens || d.chan_add || d.splitk || d.prec)
-        return "legacy ConvTranspose: Cin % 8 == 0, contiguous x, no in_lens / chan_add / splitk / prec";
-    } else if (d.Cin % 16 || d.Cout % 32) {
-      return "ConvTranspose: Cin % 16 == 0 and Cout % 32 == 0";
-    }
+    if (d.Cin % 16 || d.Cout % 32) return "ConvTranspose: Cin % 16 == 0 and Cout % 32 == 0";
   } else {
-    if (d.legacy_convt) return "legacy_convt is a ConvTranspose option";
     if (d.Cin % 32) return "conv: Cin must be a multiple of 32";
     if (!conv1d_supported(d.K, d.dil)) return "conv: K <= 11 and (K - 1) * dil <= 72 required";
   }
@@ -2409,11 +2365,6 @@ void plan_ints(const ConvPlan& p, int32_t* out) {
 
 // the plan of a (validated) descriptor; trimmed launches take the tile width conv1d_trim_bn names (0: refused)
 const char* conv_desc_plan(const mbv_conv_desc& d, const ConvArgs& a, ConvPlan* p) {
-  if (d.legacy_convt) {
-    *p = ConvPlan{};
-    p->route = MBV_ROUTE_LEGACY_CONVT; p->bm = 64; p->bn = 64; p->threads = 256; p->ck = 8; p->S = 1;
-    return nullptr;
-  }
   if (d.trim_lens) {
     const int bn = conv1d_trim_bn(a);
     if (!bn) return "this conv runs on a kernel without trimmed launches (conv1d_trim_bn 0)";
@@ -2456,7 +2407,7 @@ int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const floa
   const char* why = conv_desc_args(*d, &a);
   if (why) return m->fail("mbv_op_conv: %s", why);
   a.ws = m->conv_ws; a.ws_floats = m->conv_ws_floats; a.counters = m->conv_cnt; a.n_counters = m->conv_ncnt;
-  if (m->splitk && !d->trim_lens && !d->legacy_convt) a.splitk = 1;      // the handle's low-latency mode (an explicit trim wins)
+  if (m->splitk && !d->trim_lens) a.splitk = 1;      // the handle's low-latency mode (an explicit trim wins)
   ConvPlan p{};
   if ((why = conv_desc_plan(*d, a, &p))) return m->fail("mbv_op_conv: %s", why);
   DEVICE_GUARD(m);
@@ -2472,53 +2423,41 @@ int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const floa
   const int U = a.convt_u;
   std::vector<float> zero_bias;
   if (!bias_host) { zero_bias.assign(d->Cout, 0.f); bias_host = zero_bias.data(); }
-  if (d->legacy_convt) {
-    ConvTArgs t{};
-    t.B = d->B; t.Cin = d->Cin; t.Cout = d->Cout; t.Mpad = (int)align_up(d->Cout, 64); t.Tin = d->Tin;
-    t.in_slope = d->in_slope; t.stride = U; t.x = x; t.y = y;
-    std::vector<float> wt((size_t)16 * t.Cin * t.Mpad, 0.f);
-    pack_convt_phases(w_host, t.Cin, t.Cout, U, t.Mpad, wt.data());
-    void *dw = nullptr, *db = nullptr;
-    if (upload(wt.data(), wt.size() * 4, &dw) || upload(bias_host, (size_t)d->Cout * 4, &db)) return 1;
-    t.w = (const float*)dw; t.bias = (const float*)db;
-    launch_convt(t, s);
+  std::vector<float> wp((size_t)a.K * a.Cin * a.Mpad, 0.f), bp(a.M);
+  if (convt) {
+    pack_convt_rows(w_host, bias_host, a.Cin, d->Cout, U, a.Mpad, wp.data(), bp.data());
   } else {
-    std::vector<float> wp((size_t)a.K * a.Cin * a.Mpad, 0.f), bp(a.M);
-    if (convt) {
-      pack_convt_rows(w_host, bias_host, a.Cin, d->Cout, U, a.Mpad, wp.data(), bp.data());
-    } else {
-      std::vector<int> rows(a.M);
-      for (int i = 0; i < a.M; ++i) rows[i] = i;
-      pack_conv_rows(w_host, a.Cin, a.K, rows.data(), a.M, nullptr, a.Mpad, wp.data());
-      std::memcpy(bp.data(), bias_host, (size_t)a.M * 4);
-    }
-    void *dw = nullptr, *db = nullptr;
-    if (upload(wp.data(), wp.size() * 4, &dw) || upload(bp.data(), bp.size() * 4, &db)) return 1;
-    a.w = (const float*)dw; a.bias = (const float*)db;
-    if (a.prec == 3) {                               // the split copy of this call's weights
-      void* dws = nullptr;
-      HIPCHK(m, hipMalloc(&dws, wp.size() * 4));
-      mem.p.push_back(dws);
-      launch_split_planes(a.w, (float*)dws, wp.size(), s);
-      a.w_split = (const float*)dws;
-    }
-    a.x = x; a.y = y;
-    if (d->trim_lens) {
-      std::vector<int> l32(d->B);
-      for (int b = 0; b < d->B; ++b) {
-        const int64_t v = d->trim_lens[b];
-        l32[b] = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
-      }
-      void* dl = nullptr;
-      if (upload(l32.data(), l32.size() * 4, &dl)) return 1;
-      void* map = nullptr;
-      HIPCHK(m, hipMalloc(&map, launch_trim_map_ints(d->B, a.T, p.bn) * sizeof(int)));
-      mem.p.push_back(map);
-      launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
-      a.trim_map = (const int*)map; a.trim_bn = p.bn;
-    }
-    launch_conv1d(a, s);
+    std::vector<int> rows(a.M);
+    for (int i = 0; i < a.M; ++i) rows[i] = i;
+    pack_conv_rows(w_host, a.Cin, a.K, rows.data(), a.M, nullptr, a.Mpad, wp.data());
+    std::memcpy(bp.data(), bias_host, (size_t)a.M * 4);
   }
+  void *dw = nullptr, *db = nullptr;
+  if (upload(wp.data(), wp.size() * 4, &dw) || upload(bp.data(), bp.size() * 4, &db)) return 1;
+  a.w = (const float*)dw; a.bias = (const float*)db;
+  if (a.prec == 3) {                               // the split copy of this call's weights
+    void* dws = nullptr;
+    HIPCHK(m, hipMalloc(&dws, wp.size() * 4));
+    mem.p.push_back(dws);
+    launch_split_planes(a.w, (float*)dws, wp.size(), s);
+    a.w_split = (const float*)dws;
+  }
+  a.x = x; a.y = y;
+  if (d->trim_lens) {
+    std::vector<int> l32(d->B);
+    for (int b = 0; b < d->B; ++b) {
+      const int64_t v = d->trim_lens[b];
+      l32[b] = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
+    }
+    void* dl = nullptr;
+    if (upload(l32.data(), l32.size() * 4, &dl)) return 1;
+    void* map = nullptr;
+    HIPCHK(m, hipMalloc(&map, launch_trim_map_ints(d->B, a.T, p.bn) * sizeof(int)));
+    mem.p.push_back(map);
+    launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
+    a.trim_map = (const int*)map; a.trim_bn = p.bn;
+  }
+  launch_conv1d(a, s);
   HIPCHK(m, hipGetLastError());
   HIPCHK(m, hipStreamSynchronize(s));
   if (plan_out) plan_ints(p, plan_out);

@@ -291,7 +291,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
   const int wtap0 = RPI >= ROWS_PER_TAP ? wR0 / ROWS_PER_TAP : 0;
   const int wrem0 = RPI >= ROWS_PER_TAP ? wR0 % ROWS_PER_TAP : wR0;
   const int64_t tap_stride = (int64_t)(a.Cin / 8) * 2 * a.Mpad * 4;       // floats per tap
-  const int nchunks = (a.debug == 1 || a.debug == 4) ? 1 : a.Cin / CK;   // debug: stage chunk 0 only (timing)
 
   // per-tile load descriptors (of the tile whose chunks are being staged)
   int lb = 0, lm0 = 0, lt0 = 0;
@@ -343,7 +342,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     const int cn_ = (CN);                                                                    \
     const float* wchunk = wlane + (int64_t)(cn_ / 8) * 2 * a.Mpad * 4;                       \
     if constexpr (!GLDS) {                                                                   \
-    if (a.debug != 5 || cn_ == 0)     /* (ablation 5: weights staged for a tile's first chunk only; timing) */ \
     _Pragma("unroll") for (int u = 0; u < NW; ++u) {                                         \
       int64_t off;                                                                           \
       if constexpr (RPI >= ROWS_PER_TAP) {                                                   \
@@ -374,7 +372,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
   {                                                                                          \
     const int cn_ = (CN);                                                                    \
     if constexpr (!GLDS) {                                                                   \
-    if (a.debug != 5 || cn_ == 0)                                                            \
     _Pragma("unroll") for (int u = 0; u < NW; ++u) {                                         \
       const int e = tid + NT * u;                                                            \
       if (e < totalW) (WS)[e] = wreg[u];           /* LDS order == copy order */             \
@@ -435,7 +432,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
 
   // staging cursor: the next chunk to load (runs ahead of the tile being multiplied)
   const int nck = a.Cin / CK;
-  const bool stage0_only = a.debug == 1 || a.debug == 4;      // timing experiments: stage chunk 0 of a tile only
   // Split-K (small launches only, S = ksplit > 1): a work unit is (tile, split); split sp owns chunks
   // [sp nck / S, (sp + 1) nck / S).  Units of a tile leave their partial accumulators in a
   // workspace; the last one to arrive (ticket counter) sums them in split order on top of the
@@ -451,10 +447,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
   if (s_unit < total_units) {                                                                \
     const bool first_ = s_c == (s_unit % S) * nck / S;                                       \
     if (first_) MBV_SETUP_TILE(s_unit / S);                                                  \
-    if (first_ || !stage0_only) {                                                            \
-      MBV_ISSUE(s_c * CK);                                                                   \
-      pend_cn = s_c * CK;                                                                    \
-    }                                                                                        \
+    MBV_ISSUE(s_c * CK);                                                                     \
+    pend_cn = s_c * CK;                                                                      \
     if (++s_c == s_end) {                                                                    \
       s_unit += gridDim.x;                                                                   \
       s_c = (s_unit % S) * nck / S;                                                          \
@@ -462,12 +456,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     }                                                                                        \
   }
 
-  // (experiment, MBV_CONV_START_STAGGER via a.debug >> 8: workgroups start (blockIdx & 7) x that many s_sleep(127)s apart,
-  // so that their tile rounds — the start-value load bursts and the epilogue store bursts — stop coinciding)
-  if constexpr (DB) {
-    const int stg = (a.debug >> 8) & 0xff;
-    for (int i = (int)(blockIdx.x & 7) * stg; i > 0; --i) __builtin_amdgcn_s_sleep(127);
-  }
   // ---- prime: chunk 0 of the first tile -> LDS buffer 0 -------------------------
   MBV_ISSUE_NEXT();
   {
@@ -567,148 +555,146 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
       }
 
       MBV_CSTAMP(3)                      // chunk: MFMA loop starts
-      if (a.debug != 3) {
-        // ---- MFMA over (tap, group) steps; each step = 4 K-steps from one b128 per operand tile
-        const int nsteps = a.K * G;
-        const f32x4* wbase = Ws + hl * BM + wm * 32 * WM + l31;       // + step * 2 * BM
-        const f32x4* xbase = Xs + hl * XL + wn * 32 * WN + l31;       // + g * 2 * XL + tap * dil
-        // (split-bf16: a wave with one real row tile takes the same loop — its second tile's weights are the
-        // zero rows of the padded slab — because the half-height loop below reads the slots as fp32)
-        if (nact == WM || (PREC == 3 && nact > 0)) {
-          f32x4 a0[WM], b0[WN], a1[WM], b1[WN];
+      // ---- MFMA over (tap, group) steps; each step = 4 K-steps from one b128 per operand tile
+      const int nsteps = a.K * G;
+      const f32x4* wbase = Ws + hl * BM + wm * 32 * WM + l31;       // + step * 2 * BM
+      const f32x4* xbase = Xs + hl * XL + wn * 32 * WN + l31;       // + g * 2 * XL + tap * dil
+      // (split-bf16: a wave with one real row tile takes the same loop — its second tile's weights are the
+      // zero rows of the padded slab — because the half-height loop below reads the slots as fp32)
+      if (nact == WM || (PREC == 3 && nact > 0)) {
+        f32x4 a0[WM], b0[WN], a1[WM], b1[WN];
 #define MBV_LOAD_AB(ST, AV, BV)                                                   \
-          {                                                                        \
-            const int st_ = (ST);                                                  \
-            const int tap_ = st_ / G, g_ = st_ % G;                                \
-            const f32x4* wp_ = wbase + st_ * (2 * BM);                             \
-            const f32x4* xp_ = xbase + g_ * (2 * XL) + tap_ * a.dil;               \
-            _Pragma("unroll") for (int i = 0; i < WM; ++i) AV[i] = wp_[i * 32];    \
-            _Pragma("unroll") for (int j = 0; j < WN; ++j) BV[j] = xp_[j * 32];    \
-          }
-          /* EPI_CONVT: the i-tile whose weights are structurally zero at this tap (none: -1) */ \
+        {                                                                          \
+          const int st_ = (ST);                                                    \
+          const int tap_ = st_ / G, g_ = st_ % G;                                  \
+          const f32x4* wp_ = wbase + st_ * (2 * BM);                               \
+          const f32x4* xp_ = xbase + g_ * (2 * XL) + tap_ * a.dil;                 \
+          _Pragma("unroll") for (int i = 0; i < WM; ++i) AV[i] = wp_[i * 32];      \
+          _Pragma("unroll") for (int j = 0; j < WN; ++j) BV[j] = xp_[j * 32];      \
+        }
+        /* EPI_CONVT: the i-tile whose weights are structurally zero at this tap (none: -1) */   \
 #define MBV_SKIP(ST) (EPI == EPI_CONVT ? ((ST) / G == 0 ? 1 : ((ST) / G == a.K - 1 ? 0 : -1)) : -1)
 #define MBV_MMA(AV, BV, SK, ALLJ)                                                  \
-          {                                                                        \
-            const int sk_ = (SK);                                                  \
-            _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4)                       \
-              _Pragma("unroll") for (int i = 0; i < WM; ++i)                       \
-                _Pragma("unroll") for (int j = 0; j < WN; ++j)                     \
-                  if (((ALLJ) || j < nj) && (EPI != EPI_CONVT || i != sk_))        \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(AV[i][s4], BV[j][s4], acc[i][j], 0, 0, 0); \
-          }
-          // operands double-buffered one step ahead; sched_barrier keeps hipcc from sinking the
-          // prefetch back behind the MFMAs
-          // interior patches (every column tile inside the sequence) run a loop without any test
-          // between the MFMAs; edge patches the predicated one
+        {                                                                          \
+          const int sk_ = (SK);                                                    \
+          _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4)                         \
+            _Pragma("unroll") for (int i = 0; i < WM; ++i)                         \
+              _Pragma("unroll") for (int j = 0; j < WN; ++j)                       \
+                if (((ALLJ) || j < nj) && (EPI != EPI_CONVT || i != sk_))          \
+                  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(AV[i][s4], BV[j][s4], acc[i][j], 0, 0, 0);   \
+        }
+        // operands double-buffered one step ahead; sched_barrier keeps hipcc from sinking the
+        // prefetch back behind the MFMAs
+        // interior patches (every column tile inside the sequence) run a loop without any test
+        // between the MFMAs; edge patches the predicated one
 #define MBV_STEP_LOOP(ALLJ)                                                        \
-          {                                                                        \
-            MBV_LOAD_AB(0, a0, b0);                                                \
-            int st = 0;                                                            \
-            for (; st + 1 < nsteps; st += 2) {                                     \
-              MBV_LOAD_AB(st + 1, a1, b1);                                         \
-              __builtin_amdgcn_sched_barrier(0);                                   \
-              MBV_MMA(a0, b0, MBV_SKIP(st), ALLJ);                                 \
-              __builtin_amdgcn_sched_barrier(0);                                   \
-              MBV_LOAD_AB(st + 2, a0, b0); /* last pass: one step past the slab (padded, unused) */ \
-              __builtin_amdgcn_sched_barrier(0);                                   \
-              MBV_MMA(a1, b1, MBV_SKIP(st + 1), ALLJ);                             \
-              __builtin_amdgcn_sched_barrier(0);                                   \
-            }                                                                      \
-            if (st < nsteps) { MBV_MMA(a0, b0, MBV_SKIP(st), ALLJ); } /* odd step count */ \
-          }
-          // (256-thread shapes only: in the 512-thread shape the second loop body costs ~100 registers
-          // of live ranges and the kernel spills)
-          // split-bf16: two steps (16 K-values per lane half) per MFMA; the slots are already
-          // [hi x 4 | mid x 4] (see split_slot): an operand is two slots' halves, nothing to compute.
-          // No column test in either shape: columns past the sequence end are staged as zeros.
+        {                                                                          \
+          MBV_LOAD_AB(0, a0, b0);                                                  \
+          int st = 0;                                                              \
+          for (; st + 1 < nsteps; st += 2) {                                       \
+            MBV_LOAD_AB(st + 1, a1, b1);                                           \
+            __builtin_amdgcn_sched_barrier(0);                                     \
+            MBV_MMA(a0, b0, MBV_SKIP(st), ALLJ);                                   \
+            __builtin_amdgcn_sched_barrier(0);                                     \
+            MBV_LOAD_AB(st + 2, a0, b0); /* last pass: one step past the slab (padded, unused) */   \
+            __builtin_amdgcn_sched_barrier(0);                                     \
+            MBV_MMA(a1, b1, MBV_SKIP(st + 1), ALLJ);                               \
+            __builtin_amdgcn_sched_barrier(0);                                     \
+          }                                                                        \
+          if (st < nsteps) { MBV_MMA(a0, b0, MBV_SKIP(st), ALLJ); } /* odd step count */   \
+        }
+        // (256-thread shapes only: in the 512-thread shape the second loop body costs ~100 registers
+        // of live ranges and the kernel spills)
+        // split-bf16: two steps (16 K-values per lane half) per MFMA; the slots are already
+        // [hi x 4 | mid x 4] (see split_slot): an operand is two slots' halves, nothing to compute.
+        // No column test in either shape: columns past the sequence end are staged as zeros.
 #define MBV_BF16_LOOP()                                                                                   \
-          for (int st = 0; st < nsteps; st += 2) {                                                         \
-            f32x4 ra0[WM], rb0[WN], ra1[WM], rb1[WN];                                                      \
-            MBV_LOAD_AB(st, ra0, rb0);                                                                     \
-            if (st + 1 < nsteps) {                                                                         \
-              MBV_LOAD_AB(st + 1, ra1, rb1);                                                               \
-            } else {                                   /* odd step count: the second half of the K-values is absent */ \
-              _Pragma("unroll") for (int i = 0; i < WM; ++i) ra1[i] = f32x4{0.f, 0.f, 0.f, 0.f};           \
-              _Pragma("unroll") for (int j = 0; j < WN; ++j) rb1[j] = f32x4{0.f, 0.f, 0.f, 0.f};           \
-            }                                                                                              \
-            bf16x8 ah[WM], am[WM], bh[WN], bm[WN];                                                         \
-            _Pragma("unroll") for (int i = 0; i < WM; ++i) { ah[i] = plane_of<0>(ra0[i], ra1[i]); am[i] = plane_of<1>(ra0[i], ra1[i]); } \
-            _Pragma("unroll") for (int j = 0; j < WN; ++j) { bh[j] = plane_of<0>(rb0[j], rb1[j]); bm[j] = plane_of<1>(rb0[j], rb1[j]); } \
-            /* three rounds over the accumulators: consecutive MFMAs never share one */                   \
-            _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                 \
-              _Pragma("unroll") for (int j = 0; j < WN; ++j)                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], acc[i][j], 0, 0, 0);     \
-            _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                 \
-              _Pragma("unroll") for (int j = 0; j < WN; ++j)                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], acc[i][j], 0, 0, 0);     \
-            _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                 \
-              _Pragma("unroll") for (int j = 0; j < WN; ++j)                                               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);     \
-          }
-          if constexpr (EPI == EPI_CONVT && G == 2 && PREC == 0 && NWN == 4) {   // (256-thread shape: 31 registers spilled)
-            // The polyphase ConvTranspose skips the row tile whose weights are structurally zero at the first / last
-            // tap.  With the skip decided per MFMA at run time (`i != sk_` inside MBV_MMA, sk_ a function of the
-            // step) hipcc put a scalar branch around EVERY MFMA of the loop (r03 assembly audit: 24 branches per
-            // step; the two upsampling convs ran at 0.77 of peak against 0.85 for the k = 7 convs).  The stride-4
-            // form has exactly ten steps (5 taps x 2 groups): written out, every skip is a compile-time fact.
-            if (nj > 0 && a.K == 5) {
-              MBV_LOAD_AB(0, a0, b0);
+        for (int st = 0; st < nsteps; st += 2) {                                                           \
+          f32x4 ra0[WM], rb0[WN], ra1[WM], rb1[WN];                                                        \
+          MBV_LOAD_AB(st, ra0, rb0);                                                                       \
+          if (st + 1 < nsteps) {                                                                           \
+            MBV_LOAD_AB(st + 1, ra1, rb1);                                                                 \
+          } else {                                   /* odd step count: the second half of the K-values is absent */   \
+            _Pragma("unroll") for (int i = 0; i < WM; ++i) ra1[i] = f32x4{0.f, 0.f, 0.f, 0.f};             \
+            _Pragma("unroll") for (int j = 0; j < WN; ++j) rb1[j] = f32x4{0.f, 0.f, 0.f, 0.f};             \
+          }                                                                                                \
+          bf16x8 ah[WM], am[WM], bh[WN], bm[WN];                                                           \
+          _Pragma("unroll") for (int i = 0; i < WM; ++i) { ah[i] = plane_of<0>(ra0[i], ra1[i]); am[i] = plane_of<1>(ra0[i], ra1[i]); }   \
+          _Pragma("unroll") for (int j = 0; j < WN; ++j) { bh[j] = plane_of<0>(rb0[j], rb1[j]); bm[j] = plane_of<1>(rb0[j], rb1[j]); }   \
+          /* three rounds over the accumulators: consecutive MFMAs never share one */                     \
+          _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                   \
+            _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                 \
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], acc[i][j], 0, 0, 0);       \
+          _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                   \
+            _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                 \
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], acc[i][j], 0, 0, 0);       \
+          _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                   \
+            _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                 \
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);       \
+        }
+        if constexpr (EPI == EPI_CONVT && G == 2 && PREC == 0 && NWN == 4) {   // (256-thread shape: 31 registers spilled)
+          // The polyphase ConvTranspose skips the row tile whose weights are structurally zero at the first / last
+          // tap.  With the skip decided per MFMA at run time (`i != sk_` inside MBV_MMA, sk_ a function of the
+          // step) hipcc put a scalar branch around EVERY MFMA of the loop (r03 assembly audit: 24 branches per
+          // step; the two upsampling convs ran at 0.77 of peak against 0.85 for the k = 7 convs).  The stride-4
+          // form has exactly ten steps (5 taps x 2 groups): written out, every skip is a compile-time fact.
+          if (nj > 0 && a.K == 5) {
+            MBV_LOAD_AB(0, a0, b0);
 #pragma unroll
-              for (int st = 0; st < 10; st += 2) {
-                MBV_LOAD_AB(st + 1, a1, b1);
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_MMA(a0, b0, (st / 2 == 0 ? 1 : (st / 2 == 4 ? 0 : -1)), true);
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_LOAD_AB(st + 2, a0, b0); /* last pass: one step past the slab (padded, unused) */
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_MMA(a1, b1, (st / 2 == 0 ? 1 : (st / 2 == 4 ? 0 : -1)), true);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-            } else if (nj > 0 && a.K == 3) {     // stride 8 (single-band decoder): six steps
-              MBV_LOAD_AB(0, a0, b0);
+            for (int st = 0; st < 10; st += 2) {
+              MBV_LOAD_AB(st + 1, a1, b1);
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_MMA(a0, b0, (st / 2 == 0 ? 1 : (st / 2 == 4 ? 0 : -1)), true);
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_LOAD_AB(st + 2, a0, b0); /* last pass: one step past the slab (padded, unused) */
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_MMA(a1, b1, (st / 2 == 0 ? 1 : (st / 2 == 4 ? 0 : -1)), true);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else if (nj > 0 && a.K == 3) {     // stride 8 (single-band decoder): six steps
+            MBV_LOAD_AB(0, a0, b0);
 #pragma unroll
-              for (int st = 0; st < 6; st += 2) {
-                MBV_LOAD_AB(st + 1, a1, b1);
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_MMA(a0, b0, (st / 2 == 0 ? 1 : (st / 2 == 2 ? 0 : -1)), true);
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_LOAD_AB(st + 2, a0, b0);
-                __builtin_amdgcn_sched_barrier(0);
-                MBV_MMA(a1, b1, (st / 2 == 0 ? 1 : (st / 2 == 2 ? 0 : -1)), true);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-            } else if (nj > 0) MBV_STEP_LOOP(true)
-          } else if constexpr (PREC == 3) {
-            if (nj > 0) { MBV_BF16_LOOP() }
-          } else if constexpr (NWN == 2) {
-            // (r03: one loop for every wave that holds a real column, as in the 512-thread shape — columns past the end of
-            // the sequence are staged as zeros and never stored.  The per-MFMA `j < nj` form that edge patches used to
-            // take compiled to a scalar branch around every MFMA, and carrying a second loop body cost registers.)
-            if (nj > 0) MBV_STEP_LOOP(true)
-          } else {
-            // 512-thread shape: no column test at all — columns past the end of the sequence are
-            // staged as zeros and never stored, so the few MFMAs they cost on the last tile of a row
-            // buy a loop without exec-mask juggling around every MFMA
-            static_assert(NWN == 4, "");
-            if (nj > 0) MBV_STEP_LOOP(true)
-          }
+            for (int st = 0; st < 6; st += 2) {
+              MBV_LOAD_AB(st + 1, a1, b1);
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_MMA(a0, b0, (st / 2 == 0 ? 1 : (st / 2 == 2 ? 0 : -1)), true);
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_LOAD_AB(st + 2, a0, b0);
+              __builtin_amdgcn_sched_barrier(0);
+              MBV_MMA(a1, b1, (st / 2 == 0 ? 1 : (st / 2 == 2 ? 0 : -1)), true);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else if (nj > 0) MBV_STEP_LOOP(true)
+        } else if constexpr (PREC == 3) {
+          if (nj > 0) { MBV_BF16_LOOP() }
+        } else if constexpr (NWN == 2) {
+          // (r03: one loop for every wave that holds a real column, as in the 512-thread shape — columns past the end of
+          // the sequence are staged as zeros and never stored.  The per-MFMA `j < nj` form that edge patches used to
+          // take compiled to a scalar branch around every MFMA, and carrying a second loop body cost registers.)
+          if (nj > 0) MBV_STEP_LOOP(true)
+        } else {
+          // 512-thread shape: no column test at all — columns past the end of the sequence are
+          // staged as zeros and never stored, so the few MFMAs they cost on the last tile of a row
+          // buy a loop without exec-mask juggling around every MFMA
+          static_assert(NWN == 4, "");
+          if (nj > 0) MBV_STEP_LOOP(true)
+        }
 #undef MBV_BF16_LOOP
 #undef MBV_STEP_LOOP
 #undef MBV_LOAD_AB
 #undef MBV_MMA
 #undef MBV_SKIP
-        } else if (nact == 1) {                                // only reachable with WM == 2
-          for (int st = 0; st < nsteps; ++st) {
-            const int tap = st / G, g = st % G;
-            const f32x4 av = wbase[st * (2 * BM)];
-            const f32x4* xp = xbase + g * (2 * XL) + tap * a.dil;
+      } else if (nact == 1) {                                // only reachable with WM == 2
+        for (int st = 0; st < nsteps; ++st) {
+          const int tap = st / G, g = st % G;
+          const f32x4 av = wbase[st * (2 * BM)];
+          const f32x4* xp = xbase + g * (2 * XL) + tap * a.dil;
 #pragma unroll
-            for (int j = 0; j < WN; ++j) {
-              const f32x4 bv = xp[j * 32];
+          for (int j = 0; j < WN; ++j) {
+            const f32x4 bv = xp[j * 32];
 #pragma unroll
-              for (int s4 = 0; s4 < 4; ++s4)
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s4], bv[s4], acc[0][j], 0, 0, 0);
-            }
+            for (int s4 = 0; s4 < 4; ++s4)
+              acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s4], bv[s4], acc[0][j], 0, 0, 0);
           }
         }
       }
@@ -739,7 +725,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     // accumulator layout (32x32 tile): column = lane & 31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
     // stores only (see the accumulator initialisation above)
     MBV_CSTAMP(7)                        // epilogue starts
-    bool skip_epi = a.debug == 4 && acc[0][0][0] != 12345.678f;         // timing experiment: no epilogue traffic
+    bool skip_epi = false;                                           // split-K: only a tile's last unit stores
     if (S > 1) {
       const size_t tile_floats = (size_t)BM * BN;                      // == 16 WM WN NT
       float* wsu = a.ws + ((size_t)tile * S + sp) * tile_floats + tid;
@@ -969,14 +955,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
 // summation then depends on the launch size, so a row computed inside a large batch is no longer
 // bitwise equal to the same row computed alone (it is within fp32 rounding); the default keeps
 // that property.  Every parity test passes in either mode.
+constexpr int kSplitkTinyDiv = 16;         // "almost empty": tiles * kSplitkTinyDiv <= resident slots
 static int conv_splitk_factor(const ConvArgs& a, int BM, int BN, int CK, int NWN, int NT, long total, bool trimmed) {
   const long slots = 256L * (NT == 512 ? 1 : 2);      // resident workgroups (launch_epi)
   int S = 1;
   const int nck = a.Cin / CK;
   // an almost empty chip (<= 32 tiles: one utterance) repays splits of two chunks; up to a quarter
   // full, K loops of >= 16 chunks cut into >= 4-chunk pieces (measured at batch 1 and 8)
-  static const int tiny_div = [] { const char* e = getenv("MBV_SPLITK_TINY"); return e ? atoi(e) : 16; }();
-  const bool tiny = total * (long)tiny_div <= slots;
+  const bool tiny = total * (long)kSplitkTinyDiv <= slots;
   const int min_chunks = tiny ? 2 : 4;
   if (NWN == 2 && a.splitk && a.ws_floats && a.n_counters && total * 4 <= slots && nck >= (tiny ? 4 : 16) &&
       total <= a.n_counters && !trimmed) {
@@ -1003,7 +989,6 @@ static void launch_epi(const ConvArgs& a, hipStream_t s) {
   const long total = VS ? (long)tiles_x * tiles_y : (long)tiles_x * tiles_y * a.B;
   // persistent tiles: at most the workgroups that are resident at once (1 per CU for the
   // 512-thread shape, 2 for the 256-thread one: both are register-limited to 2 waves / SIMD)
-  static const int persist = [] { const char* e = getenv("MBV_CONV_PERSIST"); return e ? atoi(e) : 1; }();
   const long slots = 256L * (NT == 512 ? 1 : 2);
   const int S = conv_splitk_factor(a, BM, BN, CK, NWN, NT, total, a.trim_map != nullptr);
   if (a.trim_map && a.trim_bn != BN) {
@@ -1011,11 +996,7 @@ static void launch_epi(const ConvArgs& a, hipStream_t s) {
     abort();
   }
   const long units = total * S;
-  const int grid = (int)((persist && units > slots) ? slots : units);
-  ConvArgs a2 = a;
-  static const int dbg = [] { const char* e = getenv("MBV_CONV_DEBUG"); return e ? atoi(e) : 0; }();
-  static const int stg = [] { const char* e = getenv("MBV_CONV_START_STAGGER"); return e ? atoi(e) : 0; }();
-  a2.debug = dbg | ((stg & 0xff) << 8);
+  const int grid = (int)(units > slots ? slots : units);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_mfma_kernel<WM, WN, CK, NWN, EPI, PREC, NWM, VS>),
@@ -1027,7 +1008,7 @@ static void launch_epi(const ConvArgs& a, hipStream_t s) {
 #endif
     attr = true;
   }
-  hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN, CK, NWN, EPI, PREC, NWM, VS>), dim3(grid), dim3(NT), lds_bytes, s, a2,
+  hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN, CK, NWN, EPI, PREC, NWM, VS>), dim3(grid), dim3(NT), lds_bytes, s, a,
                      tiles_x, tiles_y, (int)total, S);
 }
 
@@ -1094,6 +1075,8 @@ static void launch_ck(const ConvArgs& a, hipStream_t s) {
   else launch_one<WM, WN, 8, NWN>(a, s);
 }
 
+constexpr int kNarrowMinUnits = 16;     // split-K mode: fewer 32-column units than this stay on the tiled kernels
+
 // The route of a launch (launch_conv1d executes it; conv1d_trim_bn and the tests read it).
 ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   ConvPlan p{};
@@ -1105,23 +1088,18 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   //   (b) in the opt-in low-latency mode, launches that would leave most of the chip idle (single
   //       utterances) instead of 128-column tiles + split-K: like split-K this makes the summation
   //       order a function of the launch size.
-  // MBV_CONV_NARROW: 0 = never, 1 = these rules, 2 = whenever supported (experiments).
-  {
-    static const int narrow = [] { const char* e = getenv("MBV_CONV_NARROW"); return e ? atoi(e) : 1; }();
-    if (a.epi == EPI_LN) { p.route = CONV_NARROW_M; return p; }
-    if (narrow && !trimmed && conv1d_narrow_supported(a)) {
-      const long tiles128 = (long)((a.T + 127) / 128) * ((a.M + 127) / 128) * a.B;
-      // (fewer than 16 units — conv_o / conv_2 of the text encoder of one short utterance: 8 — are better
-      // served by split-K over the long Cin loop than by 8 workgroups walking it alone; measured on ljs_mb,
-      // one utterance: threshold 48 / 16 / 4 -> 4.43 / 4.15 / 4.34 ms per infer)
-      const long units32 = (((long)a.B * ((a.T + 15) / 16) + 1) / 2) * ((a.M + 127) / 128);
-      if (a.splitk && tiles128 <= 128) {
-        static const int min_units = [] { const char* e = getenv("MBV_NARROW_MIN_UNITS"); return e ? atoi(e) : 16; }();
-        if (units32 >= min_units || narrow == 2) { p.route = CONV_NARROW_LAUNCH; return p; }
-      } else if ((route_T > 0 ? route_T : a.T) <= 256 || narrow == 2) {
-        p.route = CONV_NARROW_M;
-        return p;
-      }
+  if (a.epi == EPI_LN) { p.route = CONV_NARROW_M; return p; }
+  if (!trimmed && conv1d_narrow_supported(a)) {
+    const long tiles128 = (long)((a.T + 127) / 128) * ((a.M + 127) / 128) * a.B;
+    // (fewer than 16 units — conv_o / conv_2 of the text encoder of one short utterance: 8 — are better
+    // served by split-K over the long Cin loop than by 8 workgroups walking it alone; measured on ljs_mb,
+    // one utterance: threshold 48 / 16 / 4 -> 4.43 / 4.15 / 4.34 ms per infer)
+    const long units32 = (((long)a.B * ((a.T + 15) / 16) + 1) / 2) * ((a.M + 127) / 128);
+    if (a.splitk && tiles128 <= 128) {
+      if (units32 >= kNarrowMinUnits) { p.route = CONV_NARROW_LAUNCH; return p; }
+    } else if ((route_T > 0 ? route_T : a.T) <= 256) {
+      p.route = CONV_NARROW_M;
+      return p;
     }
   }
   const int halo = (a.K - 1) * a.dil;
@@ -1129,10 +1107,9 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   const bool wide_m = a.M > 64 || a.epi == EPI_GATE || a.epi == EPI_CONVT;
   // Long sequences with enough blocks to fill the chip: 512-thread workgroups, 128 x 384 tile
   // (6 accumulators per wave), double-buffered LDS.  Otherwise 256-thread, 128 x 128 tile.
-  static const int mode = [] { const char* e = getenv("MBV_CONV_WIDE"); return e ? atoi(e) : 3; }();
   bool big = false;
   int nb_big = 0;                          // r03: > 0: the first nb_big utterances on the 512-thread shape, the rest on the 256-thread one
-  if (wide_m && mode >= 3 && a.T >= 384) {
+  if (wide_m && a.T >= 384) {
     const double eff2 = 0.90 * a.T / (double)(((a.T + 127) / 128) * 128);
     const double eff3 = a.T / (double)(((a.T + 383) / 384) * 384);
     const long tpb3 = (long)((a.T + 383) / 384) * ((a.M + 127) / 128);          // tiles per utterance, 128 x 384
@@ -1145,8 +1122,7 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
     // chain of operations, so the batch can be cut between them: whole rounds of big tiles (one per CU) for the
     // first utterances, the rest as 128 x 128 tiles on the 512 half-CU slots.  In units of one big tile's time
     // (a small tile on half a CU: 1/3 of the work on 1/2 of the waves, measured 0.63 - 0.65):
-    static const int split_on = [] { const char* e = getenv("MBV_CONV_BATCH_SPLIT"); return e ? atoi(e) : 1; }();
-    if (split_on && !a.splitk && !trimmed && eff3 >= eff2 && blocks3 > 256 && a.B > 1) {
+    if (!a.splitk && !trimmed && eff3 >= eff2 && blocks3 > 256 && a.B > 1) {
       const double c2 = 0.65;
       auto rounds = [](long n, long slots) { return (double)((n + slots - 1) / slots); };
       double best = big ? rounds(blocks3, 256) : rounds(tpb2 * a.B, 512) * c2;
@@ -1164,29 +1140,26 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   // r03: the stride-4 upsampling conv on few, long-ish sequences (T' = 566 input frames: 1.47 tiles of 384 columns, 4.4 of
   // 128) tiled over the VIRTUAL sequence of the whole batch — utterance b at column b (T + halo), the gaps reading as
   // zero padding — so that only the last tile of the launch is ragged.  Same chain of operations per output element.
-  {
-    static const int vs_on = [] { const char* e = getenv("MBV_CONV_VS"); return e ? atoi(e) : 1; }();
-    if (vs_on && a.epi == EPI_CONVT && a.convt_u == 4 && a.prec != 3 && !a.splitk && !trimmed && !a.chan_add &&
-        !a.reflect1 && a.B > 1 && a.K > 1 && a.K <= 5 && halo <= 24 && a.T >= 128 &&
-        (int64_t)a.B * a.x_bstride < (1ll << 31)) {
-      auto rounds = [](long n, long slots) { return (double)((n + slots - 1) / slots); };
-      const long tiles_y = (a.M + 127) / 128;
-      const long tv = a.T + halo;
-      const double cost_vs = rounds(((long)a.B * tv + 383) / 384 * tiles_y, 256);
-      double cur;
-      if (nb_big > 0) {
-        const long tpb3 = (long)((a.T + 383) / 384) * tiles_y, tpb2 = (long)((a.T + 127) / 128) * tiles_y;
-        cur = rounds(nb_big * tpb3, 256) + rounds((a.B - nb_big) * tpb2, 512) * 0.65;
-      } else if (big) {
-        cur = rounds((long)((a.T + 383) / 384) * tiles_y * a.B, 256);
-      } else {
-        cur = rounds((long)((a.T + 127) / 128) * tiles_y * a.B, 512) * 0.65;
-      }
-      if (cost_vs >= 2.0 && cost_vs < 0.95 * cur) {
-        shape(CONV_VS, 128, 384, 512, 16);
-        p.vs_tv = (int)tv;
-        return p;                          // (S = 1: split-K is built for the 256-thread shapes only)
-      }
+  if (a.epi == EPI_CONVT && a.convt_u == 4 && a.prec != 3 && !a.splitk && !trimmed && !a.chan_add &&
+      !a.reflect1 && a.B > 1 && a.K > 1 && a.K <= 5 && halo <= 24 && a.T >= 128 &&
+      (int64_t)a.B * a.x_bstride < (1ll << 31)) {
+    auto rounds = [](long n, long slots) { return (double)((n + slots - 1) / slots); };
+    const long tiles_y = (a.M + 127) / 128;
+    const long tv = a.T + halo;
+    const double cost_vs = rounds(((long)a.B * tv + 383) / 384 * tiles_y, 256);
+    double cur;
+    if (nb_big > 0) {
+      const long tpb3 = (long)((a.T + 383) / 384) * tiles_y, tpb2 = (long)((a.T + 127) / 128) * tiles_y;
+      cur = rounds(nb_big * tpb3, 256) + rounds((a.B - nb_big) * tpb2, 512) * 0.65;
+    } else if (big) {
+      cur = rounds((long)((a.T + 383) / 384) * tiles_y * a.B, 256);
+    } else {
+      cur = rounds((long)((a.T + 127) / 128) * tiles_y * a.B, 512) * 0.65;
+    }
+    if (cost_vs >= 2.0 && cost_vs < 0.95 * cur) {
+      shape(CONV_VS, 128, 384, 512, 16);
+      p.vs_tv = (int)tv;
+      return p;                          // (S = 1: split-K is built for the 256-thread shapes only)
     }
   }
   if (nb_big > 0) {
@@ -1200,8 +1173,7 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   } else {
     // <= 64 output rows: the 64 x 384 shape when the launch fills its 512 half-CU slots (exact fp32, K > 1, the
     // decoder's epilogues); else 64 x 128.  Same chain of operations per output element either way.
-    static const int half_on = [] { const char* e = getenv("MBV_CONV_HALF"); return e ? atoi(e) : 1; }();
-    if (half_on && mode >= 3 && a.T >= 384 && a.K > 1 && a.prec != 3 && !a.splitk && !trimmed &&
+    if (a.T >= 384 && a.K > 1 && a.prec != 3 && !a.splitk && !trimmed &&
         (a.epi == EPI_STORE || a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) &&
         (long)((a.T + 383) / 384) * a.B >= 512 && a.T / (double)(((a.T + 383) / 384) * 384) >= 0.90 * a.T / (double)(((a.T + 127) / 128) * 128)) {
       shape(CONV_HALF, 64, 384, 256, a.K <= 5 && halo <= 24 ? 16 : 8);
@@ -1277,105 +1249,6 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s, int route_T) {
       }
     default: launch_ck<1, 2, 2>(a, s); return;            // CONV_M64
   }
-}
-
-// ============================================================================
-// ConvTranspose1d(k=16, stride=U, padding=(16-U)/2), U in {4, 8} — models.py:321-323 (mb/ms: 4),
-// models.py:264-267 (single-band iSTFT_Generator: 8).
-// Polyphase form: output phase r = t mod U of frame m = t / U is a (16/U)-tap conv
-//   y[co, U m + r] = bias + sum_ci sum_j W[ci][co][kr + U j] * act(x[ci, m + sh_r - j])
-//   kr = (r + p) % U, sh_r = (r + p - kr) / U   (p = padding)
-// All phases share the input window x[m + sh_0 - (TPP-1) .. m + sh_0 + 1]; one wave accumulates
-// the U phase tiles of a (32 co x 32 m) patch, so each lane ends up owning U consecutive output
-// samples -> 16-byte stores.
-// ============================================================================
-template <int U, int CK>
-__global__ __launch_bounds__(256) void convt_mfma_kernel(const ConvTArgs a) {
-  constexpr int TPP = 16 / U;                 // taps per phase
-  constexpr int PAD = (16 - U) / 2;
-  constexpr int SH0 = PAD / U;                // sh_r of phase 0 (phases with kr wrapped get SH0 + 1)
-  constexpr int BMc = 64;                     // output channels per block
-  constexpr int BNm = 64;                     // input frames per block
-  constexpr int XS = BNm + TPP;
-  __shared__ __attribute__((aligned(16))) float Xs[CK * XS];
-  __shared__ __attribute__((aligned(16))) float Ws[16 * CK * BMc];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, hl = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.z, co0 = blockIdx.y * BMc, mb0 = blockIdx.x * BNm;
-
-  f32x16 acc[U];
-#pragma unroll
-  for (int p = 0; p < U; ++p)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-
-  const float* xb = a.x + (int64_t)b * a.Cin * a.Tin;
-  for (int ci0 = 0; ci0 < a.Cin; ci0 += CK) {
-    __syncthreads();
-    for (int e = tid; e < CK * XS; e += 256) {
-      const int r = e / XS, c = e % XS;
-      const int n = mb0 + SH0 - (TPP - 1) + c;
-      float v = 0.f;
-      if (n >= 0 && n < a.Tin) v = lrelu(xb[(int64_t)(ci0 + r) * a.Tin + n], a.in_slope);
-      Xs[e] = v;
-    }
-    {
-      constexpr int Q = BMc / 4;
-      for (int e = tid; e < 16 * CK * Q; e += 256) {
-        const int row = e / Q, q = e % Q;      // row = (r*TPP + j)*CK + c
-        const int rj = row / CK, c = row % CK;
-        const float4* src = reinterpret_cast<const float4*>(
-            a.w + ((int64_t)rj * a.Cin + ci0 + c) * a.Mpad + co0) + q;
-        reinterpret_cast<float4*>(Ws + row * BMc)[q] = *src;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c2 = 0; c2 < CK / 2; ++c2) {
-      const float* xrow = Xs + (2 * c2 + hl) * XS + wn * 32 + l31;
-      const float* wbase = Ws + (2 * c2 + hl) * BMc + wm * 32 + l31;
-#pragma unroll
-      for (int tau = 0; tau <= TPP; ++tau) {
-        const float bv = xrow[tau];
-#pragma unroll
-        for (int r = 0; r < U; ++r) {
-          constexpr int dummy = 0; (void)dummy;
-          const int sh = ((r + PAD) - ((r + PAD) % U)) / U - SH0;   // 0 or 1 (compile-time after unroll)
-          const int j = sh + TPP - 1 - tau;
-          if (j >= 0 && j < TPP) {
-            const float av = wbase[((r * TPP + j) * CK) * BMc];
-            acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[r], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  const int m = mb0 + wn * 32 + l31;
-  if (m < a.Tin) {
-    const int Tout = U * a.Tin;
-    float* yb = a.y + (int64_t)b * a.Cout * Tout;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-      if (co < a.Cout) {
-        const float bias = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-        for (int q = 0; q < U / 4; ++q) {
-          float4 o;
-          o.x = acc[4 * q + 0][r] + bias; o.y = acc[4 * q + 1][r] + bias;
-          o.z = acc[4 * q + 2][r] + bias; o.w = acc[4 * q + 3][r] + bias;
-          *reinterpret_cast<float4*>(yb + (int64_t)co * Tout + U * m + 4 * q) = o;
-        }
-      }
-    }
-  }
-}
-
-void launch_convt(const ConvTArgs& a, hipStream_t s) {
-  dim3 grid((a.Tin + 63) / 64, (a.Cout + 63) / 64, a.B);
-  if (a.stride == 8) hipLaunchKernelGGL((convt_mfma_kernel<8, 8>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((convt_mfma_kernel<4, 8>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace mbv

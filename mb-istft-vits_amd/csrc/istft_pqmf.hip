@@ -26,7 +26,6 @@
 // Frames / samples in the halos are recomputed, not exchanged; consecutive
 // tiles are mapped to the same XCD so halo rows hit in its L2.
 #include "kernels.h"
-#include <cstdlib>
 
 namespace mbv {
 
@@ -258,13 +257,8 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
           polar<FAST, PRE>(xin[k], xin[9 + k], mag, ph, re[k], im[k], k != 0 && k != 8);
           if (own) {
             const int so = ((b * 4 + band) * 9 * F + f) * 4;
-            if (a.nt_stores) {                         // (experiment, off by default: see the launcher)
-              if (a.spec) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, mag), srsrc, so, k * F * 4, 2);
-              if (a.phase) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ph), prsrc, so, k * F * 4, 2);
-            } else {
-              if (a.spec) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, mag), srsrc, so, k * F * 4, 0);
-              if (a.phase) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ph), prsrc, so, k * F * 4, 0);
-            }
+            if (a.spec) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, mag), srsrc, so, k * F * 4, 0);
+            if (a.phase) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ph), prsrc, so, k * F * 4, 0);
           }
         }
       }
@@ -309,21 +303,15 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
       }
       if (a.o_mb && u >= 8 && u < TM + 8) {          // (RANGED: null at run time, kept in the code as above)          // owned samples m0 .. m0+TM-1
         if (!a.multistream) {
-          if (a.nt_stores) {
 #pragma unroll
-            for (int band = 0; band < 4; ++band)
-              __builtin_nontemporal_store(y[band], &a.o_mb[((int64_t)b * 4 + band) * M + m]);
-          } else {
-#pragma unroll
-            for (int band = 0; band < 4; ++band) a.o_mb[((int64_t)b * 4 + band) * M + m] = y[band];
-          }
+          for (int band = 0; band < 4; ++band) a.o_mb[((int64_t)b * 4 + band) * M + m] = y[band];
         } else {                                       // zero-stuffed x4, gain 4 (models.py:463)
           typedef float f4v __attribute__((ext_vector_type(4)));
 #pragma unroll
           for (int band = 0; band < 4; ++band) {
             f4v v = {4.f * y[band], 0.f, 0.f, 0.f};
             f4v* dst = reinterpret_cast<f4v*>(a.o_mb + ((int64_t)b * 4 + band) * 4 * M + 4 * (int64_t)m);
-            if (a.nt_stores) __builtin_nontemporal_store(v, dst); else *dst = v;
+            *dst = v;
           }
         }
       }
@@ -391,8 +379,18 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
   }
 }
 
-template <int TM, int NT>
-static void launch_istft_pqmf_t(const IstftArgs& a, hipStream_t s) {
+// 480 sub-band samples x 512 threads (4 workgroups / CU).  Measured and rejected (r02): (a) non-temporal stores for
+// spec / phase / o_mb — 91 vs 84 us for the all-outputs launch; (b) a persistent grid with the next tile's 18
+// inputs prefetched into registers: needs 80 registers per lane = 3 instead of 4 workgroups per CU,
+// and loses more to the lower occupancy than the prefetch gains (35.9 / 39.3 vs 32.2 us);
+// (c) 16-byte accesses through in-register 4 x 4 transposes across lane quads (DPP): x_post loads
+// 36.6 vs 31.6 us, spec / phase stores 84.8 vs 80.0 us in the same run (an apparent 84 -> 75 us gain
+// was box-to-box variation).  All three are in the history of this file (r02).  What the launch is
+// bound by: bytes in flight per CU at full occupancy (4 x 512 threads, 18 loads per lane) against
+// the latency of the level that serves them — 0.81 of the HBM peak from the Infinity Cache, 0.63
+// from HBM itself (bench.py roofline.past_cache), 0.61-0.65 with all outputs written.
+void launch_istft_pqmf(const IstftArgs& a, hipStream_t s) {
+  constexpr int TM = 480, NT = 512;
   const int M = 64 * a.Tp;
   const int tiles_per_utt = (M + TM - 1) / TM;
   const int total = tiles_per_utt * a.B;
@@ -421,28 +419,6 @@ static void launch_istft_pqmf_t(const IstftArgs& a, hipStream_t s) {
     default: MBV_ISTFT_LAUNCH(true, true, true, false); break;
   }
 #undef MBV_ISTFT_LAUNCH
-}
-
-void launch_istft_pqmf(const IstftArgs& a_in, hipStream_t s) {
-  IstftArgs a = a_in;
-  // Measured and rejected (r02): (a) non-temporal stores for spec / phase / o_mb — 91 vs 84 us for the
-  // all-outputs launch (MBV_ISTFT_NT=1 keeps the A/B); (b) a persistent grid with the next tile's 18
-  // inputs prefetched into registers: needs 80 registers per lane = 3 instead of 4 workgroups per CU,
-  // and loses more to the lower occupancy than the prefetch gains (35.9 / 39.3 vs 32.2 us);
-  // (c) 16-byte accesses through in-register 4 x 4 transposes across lane quads (DPP): x_post loads
-  // 36.6 vs 31.6 us, spec / phase stores 84.8 vs 80.0 us in the same run (an apparent 84 -> 75 us gain
-  // was box-to-box variation).  All three are in the history of this file (r02).  What the launch is
-  // bound by: bytes in flight per CU at full occupancy (4 x 512 threads, 18 loads per lane) against
-  // the latency of the level that serves them — 0.81 of the HBM peak from the Infinity Cache, 0.63
-  // from HBM itself (bench.py roofline.past_cache), 0.61-0.65 with all outputs written.
-  static const int nt = [] { const char* e = getenv("MBV_ISTFT_NT"); return e ? atoi(e) : 0; }();
-  a.nt_stores = nt;
-  // 480 sub-band samples x 512 threads (4 workgroups / CU) by default; MBV_ISTFT_TILE=224 selects
-  // the 224 x 256-thread shape (8 workgroups / CU) for A/B runs
-  static const int tile = [] { const char* e = getenv("MBV_ISTFT_TILE"); return e ? atoi(e) : 480; }();
-  if (tile == 224) launch_istft_pqmf_t<224, 256>(a, s);
-  else if (tile == 960) launch_istft_pqmf_t<960, 1024>(a, s);
-  else launch_istft_pqmf_t<480, 512>(a, s);
 }
 
 // The streaming decode's tail (mbv_decode_range): x_post of a z-window, only the chunk's samples stored.  Every

@@ -67,7 +67,6 @@ struct ConvArgs {
   int skip_accum;          // RES_SKIP: skip += v instead of skip = v
   float couple_sign;       // COUPLE: -1 reverse (x1 - m), +1 forward (x1 + m)
   int B;
-  int debug;               // timing experiments only (MBV_CONV_DEBUG): 1 = no restaging, 3 = no MFMA
   // r03, opt-in trimmed decode (mbv_set_option "trim"): only the column tiles that hold frames below a per-utterance
   // limit exist as work.  trim_map (device, launch_trim_map): [0 .. B] prefix sums of ceil(limit_b / BN), then the
   // utterance of every column tile; trim_bn = the BN it was built for (checked by the launcher).  The kernel walks
@@ -149,7 +148,6 @@ struct WnLayerArgs {
   int Mr, Mr_pad;          // rows of the res/skip conv (2H, or H for the last layer)
   int last;                // Mr == H: every row goes to skip
   int skip_accum;          // skip += (layers > 0) instead of skip =
-  int debug;               // set by the launcher (MBV_WN_DEBUG_A): timing experiments, results wrong by design
   // r03: the coupling layer's 1x1 `post` conv (modules.py:346-350) folded into the res/skip convs: their skip rows are
   // W_post . W_rs[skip rows] (Cs = I/2 rows instead of H), so `skip` accumulates m = post(sum of skips) directly and
   // the LAST layer applies the coupling x1 = (x1 + couple_sign * m) on its valid frames instead of storing skip.
@@ -173,20 +171,6 @@ bool wn_fused_fits(int B, int H, int T);      // h / skip small enough for the k
 size_t wn_units_ints(int B, int T);
 void launch_wn_units(const int* lens, int B, int T, int* ustart, int* hmap, hipStream_t s);
 void launch_wn_layer(const WnLayerArgs& a, hipStream_t s);
-
-// ---------------------------------------------------------------- ConvTranspose1d k=16, stride 4 / 8 (MFMA)
-// Packed: Wt[r][j][Cin][Mpad] with Wt[r][j][ci][co] = W[ci][co][(r + pad) % stride + stride * j],
-// r < stride, j < 16 / stride, pad = (16 - stride) / 2
-struct ConvTArgs {
-  const float* x;     // [B, Cin, Tin]
-  const float* w;     // packed
-  const float* bias;  // [Cout]
-  float* y;           // [B, Cout, stride*Tin]
-  int B, Cin, Cout, Mpad, Tin;
-  float in_slope;
-  int stride;         // 4 or 8
-};
-void launch_convt(const ConvTArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- text encoder pieces
 // bad[b] is set when an utterance has a token id / length outside the valid range
@@ -253,7 +237,6 @@ struct IstftArgs {
   int exact_math;        // 1: libm expf/sinf/sincosf instead of the hardware transcendentals
   int prescaled;         // 1: x_post rows already carry log2(e) (magnitude) / 1/(2 pi) (phase)
   int polar_in;          // 1: x_post unused; spec / phase [B,4,9,F] are the INPUT (istft_finalize)
-  int nt_stores;         // set by the launcher (MBV_ISTFT_NT, default 1): non-temporal stores for spec / phase / o_mb
   const int* trim_lens;  // opt-in trimmed decode: [B] valid z-frames; samples at and beyond 256 * trim_lens[b] are not computed
                          // (the caller zero-fills o; o_mb / spec / phase must be null)
 };

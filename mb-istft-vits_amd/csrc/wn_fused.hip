@@ -30,7 +30,6 @@
 // other's prologue / gating / epilogue.
 #include "kernels.h"
 #include <cstdio>
-#include <cstdlib>
 
 namespace mbv {
 
@@ -46,6 +45,7 @@ constexpr int kXS = 32;               // its column stride in the LDS image: the
                                       // 16 slots of 16 B behind the first half's, i.e. the same banks a
                                       // contiguous wave would (a stride of 20 is a 2-way ds_read_b128 conflict)
 constexpr int kXL = 2 * kXS;          // columns per (group, parity) row of the LDS image
+constexpr int kWnGrid = 512;          // workgroups of a launch: two resident per CU
 // tanh(x) * sigmoid(y) on the hardware transcendentals (v_exp_f32 / v_rcp_f32, 1 ulp each):
 //   sigmoid(y) = 1 / (1 + 2^(-y log2 e)),  tanh(x) = 1 - 2 / (1 + 2^(2 x log2 e))
 // absolute error ~1e-7 (the libm forms cost ~100 instructions per gated value; 24 values per lane and tile)
@@ -55,7 +55,6 @@ __device__ __forceinline__ float gate_fast(float x, float y) {
   const float th = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + e2x);
   return th * __builtin_amdgcn_rcpf(1.f + emy);
 }
-__device__ __forceinline__ float sigmoid_(float v) { return 1.f / (1.f + expf(-v)); }
 }  // namespace
 
 // ustart[b] = sum_{b' < b} ceil(len[b'] / 16), ustart[B] = number of half-units;
@@ -125,7 +124,7 @@ struct WnCtx {
   float couple_sign;
   int couple;                    // last layer applies x1 += sign * (skip + rs) instead of storing skip
   int xoff;                      // lane's column in the input-window image: half * kXS + (l31 & 15)
-  int G, H, Mr, wave, hl, l31, last, skip_accum, exact_gate;
+  int G, H, Mr, wave, hl, l31, last, skip_accum;
   int Gi;                        // input groups of the gate conv (== G unless `pre` is folded in)
   int prefold;                   // the window holds x0' = [x0 ; mask], not h: residual rows start from the wpre K-block
   __amdgpu_buffer_rsrc_t wp_rs; unsigned wp_voff, wp_step;
@@ -207,7 +206,7 @@ __device__ __forceinline__ void gate_act(const f32x16 (&acc)[NRT], f32x4* As, co
       f32x4 v;
 #pragma unroll
       for (int s = 0; s < 4; ++s)
-        v[s] = c.exact_gate ? tanhf(acc[j][8 * q + s]) * sigmoid_(acc[j][8 * q + s + 4]) : gate_fast(acc[j][8 * q + s], acc[j][8 * q + s + 4]);
+        v[s] = gate_fast(acc[j][8 * q + s], acc[j][8 * q + s + 4]);
       if (2 * tile + q < c.G) As[((2 * tile + q) * 2 + c.hl) * 32 + c.l31] = v;   // channels 16 tile + 8 q + 4 hl + s
     }
   }
@@ -376,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void wn_layer_kernel(const WnLayerArgs a) {
   c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.hl = lane >> 5; c.l31 = lane & 31;
   const int H = a.H, T = a.T;
-  c.H = H; c.G = H / 8; c.Mr = a.Mr; c.last = a.last; c.skip_accum = a.skip_accum; c.exact_gate = a.debug == 2;
+  c.H = H; c.G = H / 8; c.Mr = a.Mr; c.last = a.last; c.skip_accum = a.skip_accum;
   const int G = c.G;                           // 8-channel groups (4 K-steps each) of the gated tile
   c.Gi = a.Gi ? a.Gi : G;
   c.prefold = a.wpre != nullptr;
@@ -399,8 +398,8 @@ __global__ __launch_bounds__(256, 2) void wn_layer_kernel(const WnLayerArgs a) {
   c.br_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.br), 0, a.Mr * 4, kRsrcFlags);
   c.wg_voff = (unsigned)((c.hl * a.Mg_pad + c.wave * 32 + c.l31) * 16);
   c.wr_voff = (unsigned)((c.hl * a.Mr_pad + c.wave * 32 + c.l31) * 16);
-  c.wg_step = a.debug == 1 ? 0u : (unsigned)(2 * a.Mg_pad * 16);
-  c.wr_step = a.debug == 1 ? 0u : (unsigned)(2 * a.Mr_pad * 16);
+  c.wg_step = (unsigned)(2 * a.Mg_pad * 16);
+  c.wr_step = (unsigned)(2 * a.Mr_pad * 16);
   c.rowT = (unsigned)T * 4u;                   // bytes between channel rows of h / skip
   // whole-tensor views (the launcher checks B H T 4 < 2^32): the two halves of a tile may belong to
   // different utterances, so the utterance goes into the lane offset
@@ -498,15 +497,10 @@ void launch_wn_layer(const WnLayerArgs& a, hipStream_t s) {
   const int G = a.H / 8, Gi = a.Gi ? a.Gi : G;
   const int nrt = (2 * a.H / 32 + 3) / 4;
   const size_t lds_bytes = (size_t)(Gi * 2 * kXL + G * 2 * 32) * 16 + (size_t)128 * (nrt <= 2 ? 2 : 3) * 4;   // + the res / skip bias
-  WnLayerArgs a2 = a;
-  static const int dbg = [] { const char* e = getenv("MBV_WN_DEBUG_A"); return e ? atoi(e) : 0; }();
-  a2.debug = dbg;                    // experiments: 1 = every step reads the weights of step 0 (timing only, results wrong);
-                                     // 2 = libm tanhf / expf in the gating instead of the hardware transcendentals
   // at most two resident workgroups per CU (register / LDS budget); a workgroup walks units
   // blockIdx.x, blockIdx.x + grid, ...; the unit count itself lives on the device
   long max_units = ((long)a.B * ((a.T + kHalf - 1) / kHalf) + 1) / 2;
-  static const int grid_cap = [] { const char* e = getenv("MBV_WN_GRID"); return e ? atoi(e) : 512; }();
-  const int grid = (int)(max_units < grid_cap ? (max_units < 1 ? 1 : max_units) : grid_cap);
+  const int grid = (int)(max_units < kWnGrid ? (max_units < 1 ? 1 : max_units) : kWnGrid);
 #define MBV_WN_LAUNCH(N)                                                                          \
   {                                                                                               \
     static bool attr = false;                                                                     \
@@ -515,7 +509,7 @@ void launch_wn_layer(const WnLayerArgs& a, hipStream_t s) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);          \
       attr = true;                                                                                \
     }                                                                                             \
-    hipLaunchKernelGGL((wn_layer_kernel<N>), dim3(grid), dim3(256), lds_bytes, s, a2);            \
+    hipLaunchKernelGGL((wn_layer_kernel<N>), dim3(grid), dim3(256), lds_bytes, s, a);             \
   }
   if (nrt <= 2) MBV_WN_LAUNCH(2)
   else MBV_WN_LAUNCH(3)

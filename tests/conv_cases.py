@@ -30,7 +30,7 @@ def case(name, route, B, Cin, Cout, T, kind="conv", epi="STORE", K=3, dil=1, Tin
     c = dict(name=name, route=route, B=B, Cin=Cin, Cout=Cout, T=T, Tin=T if Tin is None else Tin, kind=kind,
              epi=epi, K=K, dil=dil, slope=slope, relu=0, reflect1=0, rstride=0, in_lens=None, out_lens=None,
              chan_add=False, res_chan_add=False, accum=False, out_scale=1.0, trim=None, splitk=0, prec=0,
-             legacy=0, pair=False, pair_route=None, S_gt1=False, check=None, seed=len(name))
+             pair=False, pair_route=None, S_gt1=False, check=None, seed=len(name))
     for k, v in kw.items():
         assert k in c, k
         c[k] = v
@@ -61,8 +61,6 @@ def features(c):
 def cell_route(c):
     """The matrix row a case belongs to."""
     r = c["route"]
-    if c["legacy"]:
-        return "LEGACY_CONVT"
     if c["trim"]:
         return "TRIM_%d" % (384 if r == "BIG" else 128)
     if c["prec"] == 3:
@@ -90,9 +88,7 @@ MATRIX = [
     ("VS", {"CONVT4"}),
 ] + [(r, f) for r in ("TRIM_128", "TRIM_384") for f in (
     {"STORE"}, {"RESID"}, {"RESID_ACC"}, {"CONVT"}, {"zero_len"}, {"tile_len"})] + [
-    ("PREC3_" + r, {f}) for r in ("SMALL", "BIG", "SPLIT_BATCH") for f in ("RESID", "RESID_ACC", "CONVT")] + [
-    ("LEGACY_CONVT", {"CONVT4"}), ("LEGACY_CONVT", {"CONVT8"}),
-]
+    ("PREC3_" + r, {f}) for r in ("SMALL", "BIG", "SPLIT_BATCH") for f in ("RESID", "RESID_ACC", "CONVT")]
 
 THIRD = 1.0 / 3.0
 CASES = [
@@ -169,9 +165,6 @@ CASES = [
     case("prec3_split_resacc", "SPLIT_BATCH", 32, 256, 256, 2264, epi="RESID_ACC", K=7, accum=True,
          out_scale=THIRD, prec=3),
     case("prec3_split_convt", "SPLIT_BATCH", 32, 128, 64, 2264, kind=4, chan_add=True, prec=3),
-    # -- the stand-alone ConvTranspose kernel (fallback of shapes EPI_CONVT is not packed for)
-    case("legacy_convt4", "LEGACY_CONVT", 3, 64, 32, 100, kind=4, legacy=1),
-    case("legacy_convt8", "LEGACY_CONVT", 2, 32, 32, 77, kind=8, legacy=1),
 ]
 BY_NAME = {c["name"]: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
@@ -222,7 +215,6 @@ def desc(c, B=None, ptrs=None, splitk=None, prec=None, trim=True, ws=True):
         d.trim_num, d.trim_add = num, add
     d.splitk = c["splitk"] if splitk is None else splitk
     d.prec = c["prec"] if prec is None else prec
-    d.legacy_convt = c["legacy"]
     if ws:
         d.ws_floats, d.n_counters = WS_FLOATS, N_COUNTERS
     d._keep = keep                       # the trim lengths live as long as the descriptor

@@ -57,7 +57,7 @@ def test_trim_width_is_the_plans():
     routes that do not depend on trimming, 128 or 384 otherwise; never split-K, the narrow kernel, HALF or VS."""
     n = 0
     for c in cc.CASES:
-        if c["legacy"] or c["prec"]:
+        if c["prec"]:
             continue
         lens = [c["T"]] * c["B"]
         cu = dict(c, trim=None)
@@ -80,15 +80,19 @@ def test_trim_width_is_the_plans():
 
 def test_prec3_never_plans_vs_or_half():
     for c in cc.CASES + [p[1] for p in cc.PRODUCTION]:
-        if c["legacy"]:
-            continue
         p = cc.plan(cc.desc(c, prec=3))
         assert p["route"] not in ("VS", "HALF"), (c["name"], p)
 
 
 def test_bad_descriptors_are_refused_not_fatal():
     base = cc.BY_NAME["small_resid"]
-    for bad in (dict(base, K=13), dict(base, Cin=100), dict(base, kind=5), dict(cc.BY_NAME["small_convt4"], T=10),
-                dict(base, epi="STORE", res_chan_add=True), dict(base, accum=True), dict(base, prec=2)):
+    bad = [cc.desc(c) for c in (
+        dict(base, K=13), dict(base, Cin=100), dict(base, kind=5), dict(cc.BY_NAME["small_convt4"], T=10),
+        dict(base, epi="STORE", res_chan_add=True), dict(base, accum=True), dict(base, prec=2))]
+    for c in (base, cc.BY_NAME["small_convt4"], cc.BY_NAME["small_convt8"]):
+        d = cc.desc(c)
+        d.legacy_convt = 1                   # the slot stays in the ABI; its kernel is gone
+        bad.append(d)
+    for d in bad:
         with pytest.raises(Exception):
-            cc.plan(cc.desc(bad))
+            cc.plan(d)

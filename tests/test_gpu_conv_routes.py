@@ -204,7 +204,7 @@ def _same(a, b):
 def test_conv_route(net, c):
     t = _inputs(c)
     y, plan = _launch(net, c, t, trim=False)
-    if not SPLITK or c["splitk"] or c["legacy"]:          # (MBV_CONV_SPLITK moves the other cases off their route)
+    if not SPLITK or c["splitk"]:                          # (MBV_CONV_SPLITK moves the other cases off their route)
         assert plan["route"] == c["route"], (c["name"], plan)
         if c["S_gt1"]:
             assert plan["S"] > 1, plan

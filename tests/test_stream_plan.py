@@ -123,7 +123,7 @@ def test_one_shot_istft_kernels_unchanged():
     with open(os.path.join(ROOT, "tests", "golden", "istft_disasm_fingerprints.json")) as f:
         golden = json.load(f)
     now = tool.compile_fingerprints()
-    assert len(golden) == 42
+    assert len(golden) == 18
     changed = sorted(k for k in golden if now.get(k) != golden[k])
     assert not changed, changed
     assert sum(k.endswith("+ranged") for k in now) == 6

@@ -312,6 +312,45 @@ int mbv_resample(mbv_model *m, const float *wave, const int64_t *valid_samples, 
 int mbv_resample_bank(int orig_sr, int target_sr, int filter, float *dst, int64_t capacity, int32_t *phases,
                       int32_t *taps, int32_t *left);
 
+/* ---- streamed wire output -------------------------------------------------------
+ * replaces the resample / normalise / int16 steps of the service wrapper (tts_vits.py:196-217) for a waveform
+ * that is still being decoded (mbv_decode_range): one step turns the samples that have become final into int16,
+ * and the concatenation of all steps is bitwise mbv_resample + mbv_pcm16_samples on the finished waveform.
+ *
+ * mbv_resample_ready (host only: no handle, no GPU): how many outputs of a row of in_total input samples are
+ * final once its samples [0, in_avail) exist.  With target / orig = L / M in lowest terms and the (taps K, left)
+ * of mbv_resample_bank, output t reads x[floor(t M / L) - left - (row L ? 1 : 0) + k], k < K, hence
+ *   in_avail <  in_total:  max(0, ceil((in_avail - K + left + 1) L / M))
+ *   in_avail >= in_total:  ceil(in_total * ratio) in fp64, the out_stride that holds every row of mbv_resample
+ * so no counted output has a tap (a padded zero tap included) at or past in_avail.  The stream lags the decoder
+ * by K - left - 1 input samples: 64 (kaiser_best, upsampling), 88 (22050 -> 16000), 16 / 22 (kaiser_fast).
+ * Equal rates: min(in_avail, in_total), no lag.  < 0 (message from mbv_last_error(NULL)) for a rate pair
+ * mbv_resample refuses, an unknown filter or in_total < 0.
+ *
+ * mbv_resample_pcm16_range: one launch for outputs [out_first, out_first + out_count) of every row.
+ *   wave, valid_samples, B, in_stride, orig_sr, target_sr, filter   as mbv_resample; in_stride is in_total
+ *   in_avail       input samples [0, in_avail) of every row exist; nothing at or past it is read
+ *   out_first, out_count   must end at or below min(mbv_resample_ready(.., in_avail, in_stride), pcm_stride)
+ *   peak           fp32 [B] device or NULL.  NULL: no normalisation (auto_normalize = 0 of mbv_pcm16).  Else
+ *                  v = (v / peak[b]) * 0.9 where peak[b] > 0.01, the operations of mbv_pcm16 in its order: fed
+ *                  the peak of the whole resampled row the stream is bitwise auto_normalize = 1
+ *   pcm            int16 [B, pcm_stride] device; only the range is written.  Samples at or past
+ *                  int(n_b * ratio) are 0, as mbv_resample + mbv_pcm16_samples leave them
+ *   running_peak   fp32 [B] device or NULL, owned and zeroed by the caller before the first step: raised to the
+ *                  largest |sample| of the row's resampled outputs in the range (an atomic max on the bits of the
+ *                  non-negative floats).  After the last step it is bitwise the peak mbv_pcm16_samples would have
+ *                  normalised by
+ *   out_samples    int64 [B] device or NULL: min(ceil(n_b * ratio), pcm_stride), as mbv_resample writes it
+ * Equal rates skip the FIR (a ranged mbv_pcm16_samples with a given peak).  All per-stream state is in the
+ * caller's buffers; the handle only caches the filter bank (first call for a rate pair: synchronous upload, as
+ * mbv_resample).  Argument errors, a range beyond what in_avail makes final included, return non-zero with a
+ * message, launch nothing and leave the handle usable. */
+int64_t mbv_resample_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total);
+int mbv_resample_pcm16_range(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t in_stride,
+                             int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
+                             int64_t out_count, const float *peak, int16_t *pcm, int64_t pcm_stride,
+                             float *running_peak, int64_t *out_samples, void *stream);
+
 /* ---- linear spectrogram ------------------------------------------------------
  * replaces spectrogram_torch(y, n_fft, sr, hop, win, center=False) (mel_processing.py:51-70), the input of
  * mbv_voice_conversion: |STFT| with (n_fft - hop) / 2 zeros on each side of the row, no centring, the

@@ -21,6 +21,7 @@ SYMBOLS = [
     "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
     "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
     "mbv_spectrogram", "mbv_spectrogram_frames", "mbv_decoder_context", "mbv_decode_range",
+    "mbv_resample_ready", "mbv_resample_pcm16_range",
 ]
 
 
@@ -118,6 +119,10 @@ def lib():
     L.mbv_resample.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
     L.mbv_resample_bank.argtypes = [i32, i32, i32, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32)]
+    L.mbv_resample_ready.argtypes = [i32, i32, i32, C.c_int64, C.c_int64]
+    L.mbv_resample_ready.restype = C.c_int64
+    L.mbv_resample_pcm16_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64,
+                                           vp, vp, C.c_int64, vp, vp, vp]
     L.mbv_spectrogram.argtypes = [vp, vp, i32, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
     L.mbv_spectrogram_frames.argtypes = [C.c_int64, i32, i32]
     L.mbv_spectrogram_frames.restype = C.c_int64

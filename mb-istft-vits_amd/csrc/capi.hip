@@ -2114,6 +2114,30 @@ int mbv_resample_bank(int orig_sr, int target_sr, int filter, float* dst, int64_
   return 0;
 }
 
+namespace {
+// the handle's device bank of a rate pair and filter; the first call builds it on the host and uploads it once
+// (synchronous copy).  0 on success, else m->fail(...) has been called.
+int resample_bank_of(mbv_model* m, const char* who, int orig_sr, int target_sr, int filter, int L, int M,
+                     const mbv_model::ResampleBank** out) {
+  const std::array<int, 3> key{L, M, filter};
+  auto it = m->resample_banks.find(key);
+  if (it == m->resample_banks.end()) {
+    mbv_model::ResampleBank rb;
+    std::vector<float> bank;
+    const char* why = resample_bank(orig_sr, target_sr, filter, &bank, &rb.g);
+    if (why) return m->fail("%s(%d -> %d): %s", who, orig_sr, target_sr, why);
+    HIPCHK(m, hipMalloc((void**)&rb.d, bank.size() * sizeof(float)));
+    if (hipMemcpy(rb.d, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(rb.d);
+      return m->fail("%s: uploading the filter bank failed", who);
+    }
+    it = m->resample_banks.emplace(key, rb).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+}  // namespace
+
 int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
                  int orig_sr, int target_sr, int filter, float* out, int64_t out_stride, int64_t* out_samples,
                  void* stream) {
@@ -2127,23 +2151,59 @@ int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, 
     return m->fail("mbv_resample: unknown filter %d", filter);
   if ((double)out_stride * M >= 0x1p62) return m->fail("mbv_resample: out_stride * M overflows the 64-bit time index");
   DEVICE_GUARD(m);
-  const std::array<int, 3> key{L, M, filter};
-  auto it = m->resample_banks.find(key);
-  if (it == m->resample_banks.end()) {
-    // first call for this pair: build on the host, upload once (synchronous copy)
-    mbv_model::ResampleBank rb;
-    std::vector<float> bank;
-    const char* why = resample_bank(orig_sr, target_sr, filter, &bank, &rb.g);
-    if (why) return m->fail("mbv_resample(%d -> %d): %s", orig_sr, target_sr, why);
-    HIPCHK(m, hipMalloc((void**)&rb.d, bank.size() * sizeof(float)));
-    if (hipMemcpy(rb.d, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(rb.d);
-      return m->fail("mbv_resample: uploading the filter bank failed");
-    }
-    it = m->resample_banks.emplace(key, rb).first;
+  const mbv_model::ResampleBank* rb = nullptr;
+  if (resample_bank_of(m, "mbv_resample", orig_sr, target_sr, filter, L, M, &rb)) return 1;
+  launch_resample(wave, valid_samples, B, in_stride, rb->d, rb->g, out, out_stride, out_samples, (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_resample_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total) {
+  if (in_total < 0) { g_create_error = "mbv_resample_ready: in_total must be >= 0"; return -1; }
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
+    g_create_error = "mbv_resample_ready: unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
+    return -1;
   }
-  launch_resample(wave, valid_samples, B, in_stride, it->second.d, it->second.g, out, out_stride, out_samples,
-                  (hipStream_t)stream);
+  if (orig_sr > 0 && orig_sr == target_sr) return in_avail < 0 ? 0 : (in_avail < in_total ? in_avail : in_total);
+  ResampleGeom g{};
+  const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
+  if (why) { g_create_error = std::string("mbv_resample_ready: ") + why; return -1; }
+  return resample_ready(g, in_avail, in_total);
+}
+
+int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
+                             int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
+                             int64_t out_count, const float* peak, int16_t* pcm, int64_t pcm_stride,
+                             float* running_peak, int64_t* out_samples, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_resample_pcm16_range";
+  if (!wave || !pcm || B <= 0 || in_stride <= 0 || pcm_stride <= 0) return m->fail("%s: bad arguments", who);
+  if (B > 65535) return m->fail("%s: more than 65535 rows", who);
+  if (in_avail < 0 || out_first < 0 || out_count < 0)
+    return m->fail("%s: in_avail, out_first and out_count must be >= 0", who);
+  int L = 0, M = 0;
+  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
+    return m->fail("%s: unknown filter %d", who, filter);
+  if (out_first > pcm_stride || out_count > pcm_stride - out_first)
+    return m->fail("%s: outputs [%lld, %lld) lie outside the row of pcm_stride %lld", who, (long long)out_first,
+                   (long long)(out_first + out_count), (long long)pcm_stride);
+  if ((double)pcm_stride * M >= 0x1p62) return m->fail("%s: pcm_stride * M overflows the 64-bit time index", who);
+  DEVICE_GUARD(m);
+  const bool fir = orig_sr != target_sr;
+  const mbv_model::ResampleBank* rb = nullptr;
+  int64_t ready = in_avail < in_stride ? in_avail : in_stride;
+  if (fir) {
+    if (resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
+    ready = resample_ready(rb->g, in_avail, in_stride);
+  }
+  if (out_first + out_count > ready)
+    return m->fail("%s: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final", who,
+                   (long long)(out_first + out_count), (long long)in_avail, (long long)in_stride, (long long)ready);
+  if (out_count == 0 && !out_samples) return 0;           // nothing to write
+  launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, fir ? rb->d : nullptr,
+                              fir ? rb->g : ResampleGeom{}, out_first, out_count, peak, reinterpret_cast<short*>(pcm),
+                              pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }

@@ -297,6 +297,16 @@ int resample_reduce(int orig_sr, int target_sr, int* L, int* M);
 const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<float>* bank, ResampleGeom* geom);
 void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
                      const ResampleGeom& g, float* out, int64_t out_stride, int64_t* out_samples, hipStream_t s);
+// streamed wire path: how many outputs of a row of in_total samples are final once its inputs [0, in_avail) exist
+// (no tap of theirs, padded zeros included, at or past in_avail); ceil(in_total ratio) once in_avail >= in_total
+int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total);
+// outputs [out_first, out_first + out_count) of every row from x[.., 0 : in_avail) -> int16 (pcm16_kernel's
+// epilogue with the given peaks, null = no normalisation) and the running peak; bank null = equal rates (no FIR).
+// The caller guarantees out_first + out_count <= min(resample_ready(g, in_avail, in_stride), pcm_stride).
+void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
+                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
+                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, hipStream_t s);
 
 // ---------------------------------------------------------------- linear spectrogram (spectrogram.hip)
 // |STFT| of spectrogram_torch(center=False) per row as if alone: (n_fft - hop) / 2 zeros each side, periodic

@@ -72,24 +72,29 @@ const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<fl
   const int nb = 1 << f.precision;
   const int n = nb * f.num_zeros;
   const int nwin = n + 1;
-  // win = kaiser(2n + 1, beta)[n:] * rolloff * sinc(rolloff * linspace(0, num_zeros, n + 1))
-  std::vector<double> win(nwin), delta(nwin);
-  const double alpha = (double)n;            // (2n + 1 - 1) / 2
-  const double i0b = bessel_i0(f.beta);
-  for (int i = 0; i < nwin; ++i) {
-    const double u = (double)i / alpha;      // (j - alpha) / alpha for j = n + i
-    const double kw = bessel_i0(f.beta * std::sqrt(1.0 - u * u)) / i0b;
-    const double x = (double)i * ((double)f.num_zeros / (double)n);
-    win[i] = kw * (f.rolloff * sinc(f.rolloff * x));
-  }
   const double ratio = (double)target_sr / (double)orig_sr;
-  if (ratio < 1.0)
-    for (auto& w : win) w *= ratio;
-  for (int i = 0; i + 1 < nwin; ++i) delta[i] = win[i + 1] - win[i];
-  delta[nwin - 1] = 0.0;
   const double scale = ratio < 1.0 ? ratio : 1.0;
   const int step = (int)(scale * nb);        // truncation as resampy's int(scale * num_table)
   if (step < 1) return "downsampling ratio too small for the filter table";
+  // win = kaiser(2n + 1, beta)[n:] * rolloff * sinc(rolloff * linspace(0, num_zeros, n + 1)); the geometry alone
+  // (bank == null: mbv_resample_ready, once per streamed chunk) needs only the wing counts, not the table
+  std::vector<double> win, delta;
+  if (bank) {
+    win.resize(nwin);
+    delta.resize(nwin);
+    const double alpha = (double)n;            // (2n + 1 - 1) / 2
+    const double i0b = bessel_i0(f.beta);
+    for (int i = 0; i < nwin; ++i) {
+      const double u = (double)i / alpha;      // (j - alpha) / alpha for j = n + i
+      const double kw = bessel_i0(f.beta * std::sqrt(1.0 - u * u)) / i0b;
+      const double x = (double)i * ((double)f.num_zeros / (double)n);
+      win[i] = kw * (f.rolloff * sinc(f.rolloff * x));
+    }
+    if (ratio < 1.0)
+      for (auto& w : win) w *= ratio;
+    for (int i = 0; i + 1 < nwin; ++i) delta[i] = win[i + 1] - win[i];
+    delta[nwin - 1] = 0.0;
+  }
 
   // one wing of resampy's loop at fractional position `frac`: count and (offset, eta) into the table
   struct Wing { int off, count; double eta; };
@@ -136,47 +141,42 @@ const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<fl
   return nullptr;
 }
 
+int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total) {
+  if (in_avail < 0) in_avail = 0;
+  const int64_t all = (int64_t)std::ceil((double)in_total * g.ratio);   // fix_length of the whole row, as mbv_resample
+  if (in_avail >= in_total) return all;
+  // output t reads up to x[floor(t M / L) - left + K - 1]: final once floor(t M / L) < in_avail - K + left + 1
+  const int64_t a = in_avail - g.K + g.left + 1;
+  if (a <= 0) return 0;
+  const int64_t r = (a * g.L + g.M - 1) / g.M;
+  return r < all ? r : all;
+}
+
 // ---------------------------------------------------------------------------------------------------
-// Kernel: one workgroup = kResampleTile consecutive outputs of one row, one output per thread.  The input
-// window they read (with the K-tap halo) is staged in LDS, zero outside [0, valid): resampy's
-// min(n + 1, ...) / min(n_in - n - 1, ...) edge rule, every row resampled as if it were alone.
-// Outputs in [int(n ratio), out_stride) are written as zeros (librosa's fix_length pad and the row padding).
+// Device code shared by the one-shot kernel and the ranged one: the staged input window of a tile and the
+// polyphase sum of one output.  One workgroup = up to kResampleTile consecutive outputs of one row, one output
+// per thread.  The input window they read (with the K-tap halo) is staged in LDS, zero outside [0, limit):
+// resampy's min(n + 1, ...) / min(n_in - n - 1, ...) edge rule, every row resampled as if it were alone.
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kResampleTile)
-resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
-                const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                float* __restrict__ out, int64_t out_stride, int64_t* __restrict__ out_samples) {
-  extern __shared__ float xs[];
-  const int b = blockIdx.y;
-  int64_t n = in_stride;
-  if (valid) {
-    n = valid[b];
-    n = n < 0 ? 0 : (n > in_stride ? in_stride : n);
-  }
-  int64_t n_out = (int64_t)((double)n * ratio);          // resampy: int(n_in * sample_ratio)
-  if (n_out > out_stride) n_out = out_stride;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && out_samples) {
-    int64_t keep = (int64_t)ceil((double)n * ratio);     // librosa fix_length: int(np.ceil(n * ratio))
-    out_samples[b] = keep > out_stride ? out_stride : keep;
-  }
-  const int64_t t0 = (int64_t)blockIdx.x * kResampleTile;
-  const int64_t t = t0 + threadIdx.x;
-  float* ob = out + (int64_t)b * out_stride;
-  if (t0 >= n_out) {                                      // uniform over the workgroup: tail only
-    if (t < out_stride) ob[t] = 0.f;
-    return;
-  }
-  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
-  const int64_t j0 = (t0 * M) / L - left - 1;              // - 1: room for row L (reads around n_t - 1)
-  const int W = (int)((t_last * M) / L - left + K - j0);  // <= resample_lds_floats(geom), checked on the host
-  const float* xb = x + (int64_t)b * in_stride;
+// first staged input index of the tile that starts at output t0 (- 1: room for row L, which reads around n_t - 1)
+__device__ __forceinline__ int64_t resample_window_first(int64_t t0, int L, int M, int left) {
+  return (t0 * M) / L - left - 1;
+}
+
+// stage x[j0, j0 + W) of one row, W = window of outputs [t0, t_last]; indices outside [0, limit) are not
+// loaded (zeros).  W <= resample_lds_floats(geom), checked on the host.
+__device__ __forceinline__ void resample_stage(float* xs, const float* __restrict__ xb, int64_t j0, int64_t t_last,
+                                               int L, int M, int K, int left, int64_t limit) {
+  const int W = (int)((t_last * M) / L - left + K - j0);
   for (int i = threadIdx.x; i < W; i += kResampleTile) {
     const int64_t j = j0 + i;
-    xs[i] = (j >= 0 && j < n) ? xb[j] : 0.f;
+    xs[i] = (j >= 0 && j < limit) ? xb[j] : 0.f;
   }
-  __syncthreads();
-  if (t >= out_stride) return;
-  if (t >= n_out) { ob[t] = 0.f; return; }
+}
+
+// output t from the staged window
+__device__ __forceinline__ float resample_output(const float* xs, int64_t j0, int64_t t, const float* __restrict__ bank,
+                                                 int L, int M, int K, int left, double ratio) {
   const int64_t q = t * M;
   int64_t nt = q / L;
   int r = (int)(q - nt * L);
@@ -191,7 +191,47 @@ resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, 
     a2 = fmaf(w.z, xw[4 * k + 2], a2);
     a3 = fmaf(w.w, xw[4 * k + 3], a3);
   }
-  ob[t] = (a0 + a1) + (a2 + a3);
+  return (a0 + a1) + (a2 + a3);
+}
+
+// valid input samples of row b (clamped to the row) and the outputs resampy computes from them
+__device__ __forceinline__ int64_t resample_row_valid(const int64_t* __restrict__ valid, int b, int64_t in_stride) {
+  if (!valid) return in_stride;
+  const int64_t n = valid[b];
+  return n < 0 ? 0 : (n > in_stride ? in_stride : n);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// One-shot kernel: whole rows.  Outputs in [int(n ratio), out_stride) are written as zeros (librosa's
+// fix_length pad and the row padding).
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kResampleTile)
+resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
+                const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                float* __restrict__ out, int64_t out_stride, int64_t* __restrict__ out_samples) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const int64_t n = resample_row_valid(valid, b, in_stride);
+  int64_t n_out = (int64_t)((double)n * ratio);          // resampy: int(n_in * sample_ratio)
+  if (n_out > out_stride) n_out = out_stride;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && out_samples) {
+    int64_t keep = (int64_t)ceil((double)n * ratio);     // librosa fix_length: int(np.ceil(n * ratio))
+    out_samples[b] = keep > out_stride ? out_stride : keep;
+  }
+  const int64_t t0 = (int64_t)blockIdx.x * kResampleTile;
+  const int64_t t = t0 + threadIdx.x;
+  float* ob = out + (int64_t)b * out_stride;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: tail only
+    if (t < out_stride) ob[t] = 0.f;
+    return;
+  }
+  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
+  const int64_t j0 = resample_window_first(t0, L, M, left);
+  resample_stage(xs, x + (int64_t)b * in_stride, j0, t_last, L, M, K, left, n);
+  __syncthreads();
+  if (t >= out_stride) return;
+  if (t >= n_out) { ob[t] = 0.f; return; }
+  ob[t] = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
 }
 
 void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
@@ -200,6 +240,95 @@ void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_str
   const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
   hipLaunchKernelGGL(resample_kernel, dim3((unsigned)bx, B), dim3(kResampleTile), lds, s, x, valid, in_stride,
                      bank, g.L, g.M, g.K, g.left, g.ratio, out, out_stride, out_samples);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Ranged kernel of the streamed wire path: outputs [out_first, out_end) of every row only, from the input
+// samples [0, in_avail) only, fused with the int16 epilogue of pcm16_kernel (ops.hip) and a running peak.
+//   - the caller (mbv_resample_pcm16_range) has checked out_end <= resample_ready(in_avail), so no stored
+//     output has a tap at or past in_avail; the staging still refuses to load those indices (the row beyond the
+//     decoded frontier is uninitialised memory, and a zero tap times a NaN is a NaN)
+//   - FIR = false: equal rates, the sample itself (a ranged pcm16 with a given peak)
+//   - epilogue in the order of pcm16_kernel: (v / peak) * 0.9 where peak > 0.01, clip, * 32767, truncate
+//   - running[b] = max(running[b], |v|) over the row's computed outputs (t < int(n ratio); the samples between
+//     that and ceil(n ratio) are zeros), by atomicMax on the bits as absmax_kernel does: one per wave
+// ---------------------------------------------------------------------------------------------------
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
+                            int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
+                            double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
+                            short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
+                            int64_t* __restrict__ out_samples) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const int64_t n = resample_row_valid(valid, b, in_stride);
+  int64_t n_out = FIR ? (int64_t)((double)n * ratio) : n;
+  if (n_out > pcm_stride) n_out = pcm_stride;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && out_samples) {
+    int64_t keep = FIR ? (int64_t)ceil((double)n * ratio) : n;
+    out_samples[b] = keep > pcm_stride ? pcm_stride : keep;
+  }
+  const int64_t t0 = out_first + (int64_t)blockIdx.x * kResampleTile;
+  const int64_t t = t0 + threadIdx.x;
+  short* ob = pcm + (int64_t)b * pcm_stride;
+  if (t0 >= out_end) return;                              // the empty range (only out_samples to write)
+  if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
+    if (t < out_end) ob[t] = 0;
+    return;
+  }
+  const int64_t limit = n < in_avail ? n : in_avail;
+  const float* xb = x + (int64_t)b * in_stride;
+  int64_t j0 = 0;
+  if (FIR) {
+    int64_t t_last = t0 + kResampleTile - 1;
+    if (t_last > n_out - 1) t_last = n_out - 1;
+    if (t_last > out_end - 1) t_last = out_end - 1;
+    j0 = resample_window_first(t0, L, M, left);
+    resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
+    __syncthreads();
+  }
+  float v = 0.f;
+  const bool live = t < out_end && t < n_out;
+  if (live) v = FIR ? resample_output(xs, j0, t, bank, L, M, K, left, ratio) : (t < limit ? xb[t] : 0.f);
+  if (running) {
+    float m = fabsf(v);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    // m >= 0: bit order == value order.  The peak only grows, so a wave that reads a value at least its own has
+    // nothing to add: most waves skip the atomic (hundreds of them on one address serialise in L2)
+    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(&running[b], __ATOMIC_RELAXED))
+      atomicMax(&running[b], __float_as_uint(m));
+  }
+  if (t >= out_end) return;
+  if (live) {
+    if (peak) {
+      const float p = peak[b];
+      if (p > 0.01f) v = (v / p) * 0.9f;
+    }
+    v = fminf(fmaxf(v, -1.f), 1.f);
+    v = v * 32767.f;
+  }
+  ob[t] = (short)(int)v;
+}
+
+void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
+                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
+                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, hipStream_t s) {
+  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
+  const dim3 grid((unsigned)bx, B), block(kResampleTile);
+  if (bank) {
+    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+    hipLaunchKernelGGL(resample_pcm16_range_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail, bank,
+                       g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
+                       running, out_samples);
+  } else {
+    hipLaunchKernelGGL(resample_pcm16_range_kernel<false>, grid, block, 0, s, x, valid, in_stride, in_avail, bank,
+                       1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
+                       out_samples);
+  }
 }
 
 }  // namespace mbv

@@ -671,6 +671,51 @@ class SynthesizerTrn(nn.Module):
         return out, out_samples
 
     @torch.no_grad()
+    def resample_pcm16_range(self, wave, orig_sr, target_sr, in_avail, out_first, out_count, pcm, valid_samples=None,
+                             peak=None, running_peak=None, out_samples=None, res_type="kaiser_best"):
+        """One step of the streamed wire output (`mbv_resample_pcm16_range`; `wire.stream_pcm16` drives it for a
+        decode stream): int16 samples [out_first, out_first + out_count) of every row of `pcm` [B, n'] from the
+        first `in_avail` samples of `wave` (fp32 [B, 1, n] or [B, n], contiguous, on the device; nothing at or
+        past `in_avail` is read), bitwise what `resample` + `to_pcm16(valid_samples=...)` give there for the
+        finished rows.  The range must end at or below `wire.resample_ready(orig_sr, target_sr, in_avail, n)`.
+          valid_samples  int64 [B] device valid input samples per row, or None = whole rows
+          peak           fp32 [B] device: divide by it (x 0.9) where it exceeds 0.01; None = no normalisation
+          running_peak   fp32 [B] device, zeroed by the caller before the first step: raised to the peak of the
+                         resampled samples of the range
+          out_samples    int64 [B] device: receives the row lengths `resample` returns
+        Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
+        filt = RESAMPLE_TYPES.get(res_type)
+        if filt is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        h = self._ensure_handle()
+        dev = self._device()
+        if wave.dim() == 3 and wave.shape[1] == 1:
+            wave = wave[:, 0]
+        if wave.dim() != 2 or pcm.dim() != 2 or pcm.shape[0] != wave.shape[0]:
+            raise ValueError("wave must be [B, 1, n] or [B, n] and pcm [B, n']")
+        B, n = wave.shape
+        for name, t, dt in (("wave", wave, torch.float32), ("pcm", pcm, torch.int16), ("peak", peak, torch.float32),
+                            ("running_peak", running_peak, torch.float32), ("out_samples", out_samples, torch.int64),
+                            ("valid_samples", valid_samples, torch.int64)):
+            if t is None:
+                continue
+            if t.device != dev or t.dtype != dt or t.stride(-1) != 1 or (t.dim() == 1 and t.shape != (B,)):
+                raise ValueError("resample_pcm16_range: %s must be a %s tensor on %s with unit stride%s"
+                                 % (name, dt, dev, "" if t.dim() == 2 else ", shape [B]"))
+        if B > 1 and wave.stride(0) != n:
+            raise ValueError("resample_pcm16_range: wave rows must be contiguous")
+        if int(out_first) + int(out_count) > pcm.shape[1]:
+            raise ValueError("resample_pcm16_range: outputs [%d, %d) lie outside pcm [B, %d]"
+                             % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
+        with torch.cuda.device(dev):
+            _capi.check(h, _capi.lib().mbv_resample_pcm16_range(
+                h, self._ptr(wave), self._ptr(valid_samples), B, n, int(orig_sr), int(target_sr), filt, int(in_avail),
+                int(out_first), int(out_count), self._ptr(peak), self._ptr(pcm), pcm.stride(0), self._ptr(running_peak),
+                self._ptr(out_samples), self._stream()),
+                "mbv_resample_pcm16_range")
+
+    @torch.no_grad()
     def spectrogram(self, wave, n_fft, hop_size, win_size, valid_samples=None, center=False):
         """Waveform [B, n] or [B, 1, n] (fp32, or int16 PCM scaled by 1 / 32768 as data_utils.py:75 does) ->
         (spec fp32 [B, n_fft // 2 + 1, F], spec_lengths int64 [B]) on the GPU: spectrogram_torch(y, n_fft, sr,

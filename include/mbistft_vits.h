@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define MBV_ABI_VERSION 3   /* 3 (r03): + arena export / import, call tickets, option "trim", mbv_op_rel_attention; structs unchanged */
+#define MBV_ABI_VERSION 3   /* 3 (r03): + arena export / import, call tickets, option "trim", mbv_op_rel_attention; structs unchanged
+                             * (later additions are new entry points; the test-only mbv_conv_desc grew at its end) */
 
 #define MBV_DEC_MULTIBAND   0   /* models.py:309 Multiband_iSTFT_Generator (fixed PQMF)        */
 #define MBV_DEC_MULTISTREAM 1   /* models.py:387 Multistream_iSTFT_Generator (trainable filter)*/
@@ -123,7 +124,9 @@ int mbv_missing_weights(mbv_model *m, char *buf, size_t cap);
  *   sid      int64 [B]      device     speaker ids, NULL iff n_speakers == 0
  *   y_lengths_out int64 [B] device     frames per utterance (clamped >= 1); -1 marks an utterance
  *                                      with a token id, length or speaker id out of range (the
- *                                      reference's nn.Embedding raises IndexError there)
+ *                                      reference's nn.Embedding raises IndexError there), or with
+ *                                      a duration outside the supported range: a token of 2^20
+ *                                      frames or more (inf and NaN included) or more than 2^30 in all
  *   noise_w  fp32 [B, 2, T]  device     use_sdp only: the standard-normal draws of models.py:94
  *                                      (NULL == zeros); scaled by noise_scale_w inside.  Ignored
  *                                      by the deterministic DurationPredictor.
@@ -418,6 +421,8 @@ int mbv_op_conv1d(mbv_model *m, const float *x, const float *w_host, const float
 #define MBV_CONV_EPI_STORE 0
 #define MBV_CONV_EPI_RESID 1
 #define MBV_CONV_EPI_RESID_ACC 2
+#define MBV_CONV_EPI_LN 7         /* conv + channel LayerNorm in one launch (narrow kernel only: T <= 256, Cout % 32 == 0, Cout <= 768):
+                                   * y = (LN_c(relu?(conv) * (t < out_lens[b]) + res) * ln_gamma + ln_beta) * (t < ln_out_lens[b]); res optional */
 typedef struct mbv_conv_desc {
   int32_t B, Cin, Cout, Tin, T, K, dil;
   int32_t x_rstride;              /* elements between channel rows of x (0: Tin) */
@@ -426,9 +431,9 @@ typedef struct mbv_conv_desc {
   float in_slope;                 /* 1: no activation */
   int32_t relu, reflect1;
   const int32_t *in_lens;         /* DEVICE [B] or NULL */
-  const int32_t *out_lens;        /* DEVICE [B] or NULL (STORE) */
+  const int32_t *out_lens;        /* DEVICE [B] or NULL (STORE, LN) */
   const float *chan_add;          /* DEVICE [B, Cin] or NULL: added to x before the activation */
-  const float *res;               /* DEVICE [B, Cout, T] (RESID, RESID_ACC) */
+  const float *res;               /* DEVICE [B, Cout, T] (RESID, RESID_ACC; LN: or NULL) */
   const float *res_chan_add;      /* DEVICE [B, Cout] or NULL */
   const float *accum_in;          /* DEVICE [B, Cout, T] or NULL (RESID_ACC) */
   float out_scale;                /* RESID_ACC */
@@ -439,6 +444,9 @@ typedef struct mbv_conv_desc {
   int32_t legacy_convt;           /* must be 0 (a kernel that is gone; the slot keeps the layout) */
   int64_t ws_floats;              /* mbv_conv_plan only: the handle's split-K workspace (mbv_op_conv uses its own) */
   int32_t n_counters;             /* ... and ticket counters */
+  const float *ln_gamma;          /* LN: DEVICE [Cout] */
+  const float *ln_beta;           /* LN: DEVICE [Cout] */
+  const int32_t *ln_out_lens;     /* LN: DEVICE [B] or NULL, the mask behind the LayerNorm */
 } mbv_conv_desc;
 /* plan[8] = route, tile rows, tile columns, threads, input-channel chunk, nb_big, vs_tv, split-K factor
  * (tile fields 0 on the narrow kernel; see conv1d_plan in csrc/kernels.h) */
@@ -456,6 +464,64 @@ int mbv_op_conv(mbv_model *m, const mbv_conv_desc *d, const float *x, const floa
 /* Host only (no handle, no GPU): the plan mbv_op_conv would execute for `d` (device pointers are only tested
  * against NULL).  On failure the message is available from mbv_last_error(NULL). */
 int mbv_conv_plan(const mbv_conv_desc *d, int32_t out[8]);
+
+/* ---- the small kernels between the convs, each by itself (tests) ---------------
+ * One entry per launcher of csrc/ops.hip and csrc/sdp.hip that mbv_encode / mbv_synthesize / mbv_voice_conversion
+ * call, with the argument patterns those use (the in-place forms are the caller's choice of pointers).  Every
+ * pointer is a DEVICE pointer; "or NULL" marks the optional ones.  Each call checks its arguments (a refusal
+ * returns non-zero with a message, launches nothing and leaves the handle usable), launches on `stream`,
+ * synchronises it and reports a launch error.  None needs weights.
+ *   mbv_op_embed            x [B, H, T] = emb[ids] * sqrt(H) * mask; lens32 [B] = lengths clamped to [0, T]; bad [B]
+ *                           = 1 for an id outside [0, n_vocab) or a length outside [0, T] (zeroed first)
+ *   mbv_op_layernorm        y = (LN_c(relu?(a + r)) * gamma + beta) * (t < out_lens[b]); r, out_lens or NULL; C <= 256
+ *   mbv_op_durations        w [C] given: logw = (w . h[:, :, t] + bias[0]) for t < lens[b], else 0; w NULL: h is
+ *                           logw [B, T].  w_ceil = ceil(exp(logw) * length_scale), cum = inclusive sums (int32),
+ *                           ylen32 = max(total, 1), ylen64 (or NULL) = that, or -1 where bad[b] (bad or NULL)
+ *                           Supported range: a token below 2^20 frames, an utterance at most 2^30; beyond it (or a
+ *                           duration that is inf / NaN) the token counts 0, ylen32 = 1 and ylen64 = -1
+ *   mbv_op_expand           length regulation from cum / ylen32 [B]: stats [B, 2 I, T] holds m_text | logs_text;
+ *                           noise [B, I, Tp] or NULL; m_p, logs_p, z_p, attn [B, Tp, T], y_mask [B, Tp] or NULL; z required
+ *   mbv_op_cond_gemv        out [B, Cout] = W [Cout, Cin] g[b] + bias (bias or NULL)
+ *   mbv_op_gather_rows      out [B, C] = table[sid[b]]; bad [B] or NULL is set (never cleared) for sid outside [0, n_rows)
+ *   mbv_op_posterior_sample z [B, I, T] = (m + noise * exp(logs)) * mask, stats [B, 2 I, T] = m | logs; noise or NULL
+ *   mbv_op_lens             lens32 [B], bad [B] from int64 lengths (as mbv_op_embed), then mask [B, T] (or NULL) from lens32
+ *   mbv_op_dds_sep          y = gelu(LN_c(depth-wise conv_K,dil(x * mask) + bias)); w [C, K]; K = 3, C <= 256
+ *   mbv_op_dds_res          y = (xres + gelu(LN_c(a))) * (t < out_lens[b]); out_lens or NULL; y may be xres
+ *   mbv_op_sdp_pre          h [B, C, T] = pre_w[c] * z[b, zc, t] + pre_b[c] + cond; z [B, 2, T], zc 0 or 1
+ *   mbv_op_sdp_spline       Flip + inverse rational-quadratic spline + mask in place on z [B, 2, T]; h [B, 29, T]
+ *   mbv_op_sdp_logw         logw [B, T] = (z[:, 1] - m[0]) * exp(-logs[0]) * mask
+ *   mbv_op_sdp_noise        z [n] = noise * scale, or zeros when noise is NULL
+ *   mbv_op_chan_add         x [B, C, T] += v [B, C] */
+int mbv_op_embed(mbv_model *m, const int64_t *ids, const int64_t *lengths, const float *emb, float *x, int32_t *lens32,
+                 int32_t *bad, int B, int T, int H, int n_vocab, void *stream);
+int mbv_op_layernorm(mbv_model *m, const float *a, const float *r, const float *gamma, const float *beta, float *y,
+                     int B, int C, int T, int pre_relu, const int32_t *out_lens, void *stream);
+int mbv_op_durations(mbv_model *m, const float *h, const float *w, const float *bias, const int32_t *lens,
+                     float length_scale, float *logw, float *w_ceil, int32_t *cum, int32_t *ylen32, int64_t *ylen64,
+                     const int32_t *bad, int B, int C, int T, void *stream);
+int mbv_op_expand(mbv_model *m, const float *stats, const int32_t *cum, const int32_t *ylen32, const float *noise,
+                  float noise_scale, float *m_p, float *logs_p, float *z_p, float *z, float *attn, float *y_mask,
+                  int B, int I, int T, int Tp, void *stream);
+int mbv_op_cond_gemv(mbv_model *m, const float *g, const float *W, const float *bias, float *out, int B, int Cin,
+                     int Cout, void *stream);
+int mbv_op_gather_rows(mbv_model *m, const float *table, const int64_t *sid, float *out, int B, int C, int n_rows,
+                       int32_t *bad, void *stream);
+int mbv_op_posterior_sample(mbv_model *m, const float *stats, const float *noise, const int32_t *lens, float *z,
+                            int B, int I, int T, void *stream);
+int mbv_op_lens(mbv_model *m, const int64_t *lengths, int32_t *lens32, int32_t *bad, float *mask, int B, int T,
+                void *stream);
+int mbv_op_dds_sep(mbv_model *m, const float *x, const int32_t *lens, const float *w, const float *bias,
+                   const float *gamma, const float *beta, float *y, int B, int C, int T, int K, int dil, void *stream);
+int mbv_op_dds_res(mbv_model *m, const float *a, const float *xres, const float *gamma, const float *beta, float *y,
+                   int B, int C, int T, const int32_t *out_lens, void *stream);
+int mbv_op_sdp_pre(mbv_model *m, const float *z, int zc, const float *pre_w, const float *pre_b, const float *cond,
+                   float *h, int B, int C, int T, void *stream);
+int mbv_op_sdp_spline(mbv_model *m, const float *h, float *z, const int32_t *lens, int B, int C, int T,
+                      float edge_const, void *stream);
+int mbv_op_sdp_logw(mbv_model *m, const float *z, const float *mean, const float *logs, const int32_t *lens,
+                    float *logw, int B, int T, void *stream);
+int mbv_op_sdp_noise(mbv_model *m, const float *noise, float scale, float *z, int64_t n, void *stream);
+int mbv_op_chan_add(mbv_model *m, float *x, const float *v, int B, int C, int T, void *stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,9 @@ SYMBOLS = [
     "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
     "mbv_spectrogram", "mbv_spectrogram_frames", "mbv_decoder_context", "mbv_decode_range",
     "mbv_resample_ready", "mbv_resample_pcm16_range",
+    "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
+    "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
+    "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
 ]
 
 
@@ -55,12 +58,13 @@ class MbvConvDesc(C.Structure):
         ("trim_lens", C.c_void_p), ("trim_num", C.c_int32), ("trim_add", C.c_int32),
         ("splitk", C.c_int32), ("prec", C.c_int32), ("legacy_convt", C.c_int32),
         ("ws_floats", C.c_int64), ("n_counters", C.c_int32),
+        ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_out_lens", C.c_void_p),
     ]
 
 
 # MBV_CONV_KIND_* / MBV_CONV_EPI_* / MBV_ROUTE_* of include/mbistft_vits.h
 CONV_KIND_CONV, CONV_KIND_CONVT4, CONV_KIND_CONVT8 = 0, 4, 8
-CONV_EPI_STORE, CONV_EPI_RESID, CONV_EPI_RESID_ACC = 0, 1, 2
+CONV_EPI_STORE, CONV_EPI_RESID, CONV_EPI_RESID_ACC, CONV_EPI_LN = 0, 1, 2, 7
 ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS"}
 PLAN_FIELDS = ("route", "bm", "bn", "threads", "ck", "nb_big", "vs_tv", "S")
 
@@ -140,6 +144,22 @@ def lib():
     L.mbv_op_conv1d.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp]
     L.mbv_op_conv.argtypes = [vp, C.POINTER(MbvConvDesc), vp, vp, vp, vp, C.POINTER(C.c_int32 * 8), vp]
     L.mbv_conv_plan.argtypes = [C.POINTER(MbvConvDesc), C.POINTER(C.c_int32 * 8)]
+    f32 = C.c_float
+    L.mbv_op_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.mbv_op_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.mbv_op_durations.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_op_expand.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.mbv_op_cond_gemv.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_op_gather_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.mbv_op_posterior_sample.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_op_lens.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    L.mbv_op_dds_sep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    L.mbv_op_dds_res.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.mbv_op_sdp_pre.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_op_sdp_spline.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp]
+    L.mbv_op_sdp_logw.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.mbv_op_sdp_noise.argtypes = [vp, vp, f32, vp, C.c_int64, vp]
+    L.mbv_op_chan_add.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     for s in SYMBOLS:
         getattr(L, s)          # AttributeError if the header and the library ever drift
     if L.mbv_abi_version() != ABI_VERSION:

@@ -2318,6 +2318,189 @@ int mbv_op_rel_attention(mbv_model* m, const float* qkv, const float* emb_k, con
   return 0;
 }
 
+// ---- the small kernels by themselves (tests): the launchers of ops.hip / sdp.hip with the argument patterns of
+// mbv_encode / mbv_synthesize / mbv_voice_conversion.  Arguments are checked before anything is launched.
+#define OP_REFUSE(cond, msg) \
+  do { if (cond) return m->fail("%s: %s", __func__, msg); } while (0)
+#define OP_BEGIN()       \
+  DEVICE_GUARD(m);       \
+  hipStream_t s = (hipStream_t)stream
+#define OP_END()                       \
+  HIPCHK(m, hipGetLastError());        \
+  HIPCHK(m, hipStreamSynchronize(s));  \
+  return 0
+namespace {
+constexpr int kGridYZ = 65535;     // a grid's y / z extent (the batch, and a channel count in some kernels)
+constexpr int kLnMaxC = 256;       // the channel LayerNorm tiles of ops.hip / sdp.hip: 8 groups x 32 values per thread
+}  // namespace
+
+int mbv_op_embed(mbv_model* m, const int64_t* ids, const int64_t* lengths, const float* emb, float* x, int32_t* lens32,
+                 int32_t* bad, int B, int T, int H, int n_vocab, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!ids || !lengths || !emb || !x || !lens32 || !bad, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0 || H <= 0 || n_vocab <= 0, "B, T, H and n_vocab must be > 0");
+  OP_REFUSE(B > kGridYZ || H > kGridYZ, "B and H must be <= 65535");
+  OP_BEGIN();
+  launch_embed(ids, lengths, emb, x, lens32, bad, B, T, H, n_vocab, s);
+  OP_END();
+}
+
+int mbv_op_layernorm(mbv_model* m, const float* a, const float* r, const float* gamma, const float* beta, float* y,
+                     int B, int C, int T, int pre_relu, const int32_t* out_lens, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!a || !gamma || !beta || !y, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535] and T > 0 required");
+  OP_REFUSE(C <= 0 || C > kLnMaxC, "C must be in [1, 256]");
+  OP_BEGIN();
+  launch_layernorm(a, r, gamma, beta, y, B, C, T, pre_relu, out_lens, s);
+  OP_END();
+}
+
+int mbv_op_durations(mbv_model* m, const float* h, const float* w, const float* bias, const int32_t* lens,
+                     float length_scale, float* logw, float* w_ceil, int32_t* cum, int32_t* ylen32, int64_t* ylen64,
+                     const int32_t* bad, int B, int C, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!h || !lens || !logw || !w_ceil || !cum || !ylen32, "NULL argument");
+  OP_REFUSE((w != nullptr) != (bias != nullptr), "w and bias come together (both NULL: h is logw)");
+  OP_REFUSE(B <= 0 || T <= 0, "B and T must be > 0");
+  OP_REFUSE(w ? C <= 0 : C != 1, "C must be > 0 with w, 1 without");
+  OP_REFUSE(!(length_scale > 0.f) || !(length_scale < INFINITY), "length_scale must be positive and finite");
+  OP_BEGIN();
+  launch_durations(h, w, bias, lens, length_scale, logw, w_ceil, cum, ylen32, ylen64, bad, B, C, T, s);
+  OP_END();
+}
+
+int mbv_op_expand(mbv_model* m, const float* stats, const int32_t* cum, const int32_t* ylen32, const float* noise,
+                  float noise_scale, float* m_p, float* logs_p, float* z_p, float* z, float* attn, float* y_mask,
+                  int B, int I, int T, int Tp, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!stats || !cum || !ylen32 || !z, "NULL argument");
+  OP_REFUSE(B <= 0 || I <= 0 || T <= 0 || Tp <= 0, "B, I, T and Tp must be > 0");
+  OP_REFUSE(B > kGridYZ || Tp > kGridYZ || (I + 15) / 16 > kGridYZ, "B, Tp <= 65535 required");
+  OP_BEGIN();
+  // m_text / logs_text: the two halves of the [B, 2I, T] buffer, as mbv_synthesize passes them
+  launch_expand(stats, stats + (size_t)I * T, (int64_t)2 * I * T, cum, ylen32, noise_scale != 0.f ? noise : nullptr,
+                noise_scale, m_p, logs_p, z_p, z, attn, y_mask, B, I, T, Tp, s);
+  OP_END();
+}
+
+int mbv_op_cond_gemv(mbv_model* m, const float* g, const float* W, const float* bias, float* out, int B, int Cin,
+                     int Cout, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!g || !W || !out, "NULL argument");
+  OP_REFUSE(B <= 0 || Cin <= 0 || Cout <= 0 || B > kGridYZ, "B in [1, 65535], Cin and Cout > 0 required");
+  OP_BEGIN();
+  launch_cond_gemv(g, nullptr, nullptr, W, bias, out, B, Cin, Cout, s);
+  OP_END();
+}
+
+int mbv_op_gather_rows(mbv_model* m, const float* table, const int64_t* sid, float* out, int B, int C, int n_rows,
+                       int32_t* bad, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!table || !sid || !out, "NULL argument");
+  OP_REFUSE(B <= 0 || C <= 0 || n_rows <= 0 || B > kGridYZ, "B in [1, 65535], C and n_rows > 0 required");
+  OP_BEGIN();
+  launch_gather_rows(table, sid, out, B, C, n_rows, bad, s);
+  OP_END();
+}
+
+int mbv_op_posterior_sample(mbv_model* m, const float* stats, const float* noise, const int32_t* lens, float* z,
+                            int B, int I, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!stats || !lens || !z, "NULL argument");
+  OP_REFUSE(B <= 0 || I <= 0 || T <= 0 || B > kGridYZ || I > kGridYZ, "B, I in [1, 65535] and T > 0 required");
+  OP_BEGIN();
+  launch_posterior_sample(stats, noise, lens, z, B, I, T, s);
+  OP_END();
+}
+
+int mbv_op_lens(mbv_model* m, const int64_t* lengths, int32_t* lens32, int32_t* bad, float* mask, int B, int T,
+                void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!lengths || !lens32 || !bad, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535] and T > 0 required");
+  OP_BEGIN();
+  launch_lens_to_i32(lengths, lens32, B, T, bad, s);
+  if (mask) launch_sequence_mask(lens32, mask, B, T, s);
+  OP_END();
+}
+
+int mbv_op_dds_sep(mbv_model* m, const float* x, const int32_t* lens, const float* w, const float* bias,
+                   const float* gamma, const float* beta, float* y, int B, int C, int T, int K, int dil, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!x || !lens || !w || !bias || !gamma || !beta || !y, "NULL argument");
+  OP_REFUSE(x == y, "y must not be x (columns read their neighbours)");
+  OP_REFUSE(B <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535] and T > 0 required");
+  OP_REFUSE(C <= 0 || C > kLnMaxC, "C must be in [1, 256]");
+  OP_REFUSE(K != 3 || (dil != 1 && dil != 3 && dil != 9), "K = 3 and dil in {1, 3, 9} (the DDSConv of the model)");
+  OP_BEGIN();
+  launch_dds_sep(x, lens, w, bias, gamma, beta, y, B, C, T, K, dil, s);
+  OP_END();
+}
+
+int mbv_op_dds_res(mbv_model* m, const float* a, const float* xres, const float* gamma, const float* beta, float* y,
+                   int B, int C, int T, const int32_t* out_lens, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!a || !xres || !gamma || !beta || !y, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535] and T > 0 required");
+  OP_REFUSE(C <= 0 || C > kLnMaxC, "C must be in [1, 256]");
+  OP_BEGIN();
+  launch_dds_res(a, xres, gamma, beta, y, B, C, T, out_lens, s);
+  OP_END();
+}
+
+int mbv_op_sdp_pre(mbv_model* m, const float* z, int zc, const float* pre_w, const float* pre_b, const float* cond,
+                   float* h, int B, int C, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!z || !pre_w || !pre_b || !cond || !h, "NULL argument");
+  OP_REFUSE(zc != 0 && zc != 1, "zc must be 0 or 1");
+  OP_REFUSE(B <= 0 || C <= 0 || T <= 0 || B > kGridYZ || C > kGridYZ, "B, C in [1, 65535] and T > 0 required");
+  OP_BEGIN();
+  launch_sdp_pre(z, zc, pre_w, pre_b, cond, h, B, C, T, s);
+  OP_END();
+}
+
+int mbv_op_sdp_spline(mbv_model* m, const float* h, float* z, const int32_t* lens, int B, int C, int T,
+                      float edge_const, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!h || !z || !lens, "NULL argument");
+  OP_REFUSE(B <= 0 || C <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535], C and T > 0 required");
+  OP_BEGIN();
+  launch_sdp_spline(h, z, lens, B, C, T, edge_const, s);
+  OP_END();
+}
+
+int mbv_op_sdp_logw(mbv_model* m, const float* z, const float* mean, const float* logs, const int32_t* lens,
+                    float* logw, int B, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!z || !mean || !logs || !lens || !logw, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0 || B > kGridYZ, "B in [1, 65535] and T > 0 required");
+  OP_BEGIN();
+  launch_sdp_logw(z, mean, logs, lens, logw, B, T, s);
+  OP_END();
+}
+
+int mbv_op_sdp_noise(mbv_model* m, const float* noise, float scale, float* z, int64_t n, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!z, "NULL argument");
+  OP_REFUSE(n <= 0 || n > ((int64_t)1 << 31), "n must be in [1, 2^31]");
+  OP_BEGIN();
+  launch_sdp_noise(noise, scale, z, n, s);
+  OP_END();
+}
+
+int mbv_op_chan_add(mbv_model* m, float* x, const float* v, int B, int C, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!x || !v, "NULL argument");
+  OP_REFUSE(B <= 0 || C <= 0 || T <= 0 || B > kGridYZ || C > kGridYZ, "B, C in [1, 65535] and T > 0 required");
+  OP_BEGIN();
+  launch_chan_add(x, v, B, C, T, s);
+  OP_END();
+}
+#undef OP_REFUSE
+#undef OP_BEGIN
+#undef OP_END
+
 int mbv_op_conv1d(mbv_model* m, const float* x, const float* w_host, const float* bias_host, float* y,
                   int B, int Cin, int Cout, int T, int K, int dilation, float in_slope, void* stream) {
   if (!m) return 1;
@@ -2368,6 +2551,7 @@ static_assert(MBV_ROUTE_NARROW_M == CONV_NARROW_M && MBV_ROUTE_NARROW_LAUNCH == 
               MBV_ROUTE_M64 == CONV_M64 && MBV_ROUTE_HALF == CONV_HALF && MBV_ROUTE_SMALL == CONV_SMALL &&
               MBV_ROUTE_BIG == CONV_BIG && MBV_ROUTE_SPLIT_BATCH == CONV_SPLIT_BATCH && MBV_ROUTE_VS == CONV_VS,
               "route numbers of the C-ABI and the launcher");
+static_assert(MBV_CONV_EPI_LN == EPI_LN, "epilogue numbers of the C-ABI and the launcher");
 
 // null on success, else why the descriptor is refused
 const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
@@ -2375,11 +2559,19 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   if (d.kind != MBV_CONV_KIND_CONV && !convt) return "kind must be MBV_CONV_KIND_CONV, _CONVT4 or _CONVT8";
   if (d.B <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.Tin <= 0 || d.T <= 0) return "B, Cin, Cout, Tin and T must be > 0";
   if (d.x_rstride != 0 && d.x_rstride < d.Tin) return "x_rstride must be 0 or >= Tin";
-  if (d.epi < MBV_CONV_EPI_STORE || d.epi > MBV_CONV_EPI_RESID_ACC) return "epi must be STORE, RESID or RESID_ACC";
+  const bool ln = d.epi == MBV_CONV_EPI_LN;
+  if ((d.epi < MBV_CONV_EPI_STORE || d.epi > MBV_CONV_EPI_RESID_ACC) && !ln) return "epi must be STORE, RESID, RESID_ACC or LN";
   if (d.prec != 0 && d.prec != 3) return "prec must be 0 or 3";
   if (d.epi == MBV_CONV_EPI_STORE && (d.res || d.res_chan_add)) return "res / res_chan_add need a RESID epilogue";
-  if (d.epi != MBV_CONV_EPI_STORE && !d.res) return "RESID and RESID_ACC need res";
-  if (d.epi != MBV_CONV_EPI_STORE && (d.out_lens || d.relu)) return "out_lens / relu belong to STORE";
+  if (d.epi != MBV_CONV_EPI_STORE && !ln && !d.res) return "RESID and RESID_ACC need res";
+  if (d.epi != MBV_CONV_EPI_STORE && !ln && (d.out_lens || d.relu)) return "out_lens / relu belong to STORE and LN";
+  if (!ln && (d.ln_gamma || d.ln_beta || d.ln_out_lens)) return "ln_gamma / ln_beta / ln_out_lens belong to LN";
+  if (ln) {
+    if (convt) return "LN: a conv only";
+    if (!d.ln_gamma || !d.ln_beta) return "LN needs ln_gamma and ln_beta";
+    if (d.res_chan_add || d.trim_lens || d.prec) return "LN takes no res_chan_add, no trimmed launch and no prec 3";
+    if (d.T > 256) return "LN: T <= 256 (the narrow kernel's rule in mbv_encode)";
+  }
   if (d.epi != MBV_CONV_EPI_RESID_ACC && d.accum_in) return "accum_in belongs to RESID_ACC";
   if (d.legacy_convt) return "legacy_convt must be 0 (the stand-alone ConvTranspose kernel was removed)";
   if (d.trim_lens && d.splitk) return "a trimmed launch takes no split-K";
@@ -2414,6 +2606,10 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   a.prec = d.prec;
   if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32))
     return "one utterance's output exceeds 4 GiB";
+  if (ln) {
+    a.ln_gamma = d.ln_gamma; a.ln_beta = d.ln_beta; a.ln_out_lens = d.ln_out_lens;
+    if (!conv1d_narrow_supported(a)) return "LN outside the narrow kernel's range (conv1d_narrow_supported)";
+  }
   *out = a;
   return nullptr;
 }

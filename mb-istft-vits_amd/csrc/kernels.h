@@ -192,6 +192,7 @@ void launch_durations(const float* h, const float* w, const float* b, const int*
                       float length_scale, float* logw, float* w_ceil, int* cum, int* ylen32,
                       int64_t* ylen64, const int* bad, int B, int C, int T, hipStream_t s);
 // (w == nullptr: h is logw itself, [B, T] — the SDP path)
+// a token of >= 2^20 frames (or inf / NaN) or an utterance of > 2^30: ylen32 = 1, ylen64 = -1 (ops.hip)
 
 // ---------------------------------------------------------------- StochasticDurationPredictor (sdp.hip)
 // DDSConv halves (modules.py:98-111), C <= 256

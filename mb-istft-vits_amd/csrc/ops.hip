@@ -139,17 +139,22 @@ void launch_layernorm(const float* a, const float* r, const float* gamma, const 
 //   logw = (w . (h * mask) + b) * mask ; w = exp(logw) * mask * length_scale
 //   w_ceil = ceil(w) ; cum = inclusive cumsum ; y_len = max(sum, 1)
 // One block per utterance; T is scanned in chunks of 256.
+// Supported range: every token below 2^20 frames, every utterance at most 2^30 (the int32 sums cannot wrap:
+// a chunk adds < 2^28 to a carry that stops at 2^30).  A duration at or beyond that, or not a number, counts 0
+// frames and flags the utterance like an invalid token id: y_len = 1, y_lengths = -1; w_ceil keeps its value.
 // ---------------------------------------------------------------------------
+constexpr float kMaxTokenFrames = 1048576.f;     // 2^20
+constexpr int kMaxTotalFrames = 1 << 30;
 __global__ __launch_bounds__(256) void durations_kernel(const float* h, const float* w,
                                                         const float* bias, const int* lens,
                                                         float length_scale, float* logw,
                                                         float* w_ceil, int* cum, int* ylen32,
                                                         int64_t* ylen64, const int* bad, int C, int T) {
   __shared__ int scan[256];
-  __shared__ int carry_s;
+  __shared__ int carry_s, over_s;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int len = lens[b];
-  if (tid == 0) carry_s = 0;
+  if (tid == 0) { carry_s = 0; over_s = 0; }
   __syncthreads();
   for (int t0 = 0; t0 < T; t0 += 256) {
     const int t = t0 + tid;
@@ -179,7 +184,8 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* h, const fl
       }
       logw[(int64_t)b * T + t] = lw;
       w_ceil[(int64_t)b * T + t] = wc;
-      d = (int)wc;
+      if (wc < kMaxTokenFrames) d = (int)wc;
+      else over_s = 1;                                  // too long, inf or NaN (every writer stores the same 1)
     }
     scan[tid] = d;
     __syncthreads();
@@ -192,13 +198,17 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* h, const fl
     const int carry = carry_s;
     if (t < T) cum[(int64_t)b * T + t] = carry + scan[tid];
     __syncthreads();
-    if (tid == 255) carry_s = carry + scan[255];
+    if (tid == 255) {
+      int c = carry + scan[255];
+      if (c > kMaxTotalFrames) { over_s = 1; c = kMaxTotalFrames; }
+      carry_s = c;
+    }
     __syncthreads();
   }
   if (tid == 0) {
-    const int total = carry_s < 1 ? 1 : carry_s;
+    const int total = (carry_s < 1 || over_s) ? 1 : carry_s;
     ylen32[b] = total;
-    if (ylen64) ylen64[b] = (bad && bad[b]) ? -1 : total;     // -1: invalid token id / length / sid
+    if (ylen64) ylen64[b] = ((bad && bad[b]) || over_s) ? -1 : total;     // -1: invalid token id / length / sid / duration
   }
 }
 

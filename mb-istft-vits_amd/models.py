@@ -365,7 +365,8 @@ class SynthesizerTrn(nn.Module):
             Tp, flag = (int(v) for v in stat.tolist())      # the one host sync (commons.py:123)
             if flag > 0:                            # flagged by the kernels, no extra sync
                 raise IndexError("index out of range in self (token id, x_lengths or sid outside the "
-                                 "model's tables)")
+                                 "model's tables, or a duration outside the supported range: 2^20 frames a token, "
+                                 "2^30 an utterance)")
             if frames_hook is not None:
                 Tp = int(frames_hook(Tp))
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729)

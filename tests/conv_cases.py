@@ -12,7 +12,8 @@ from mb_istft_vits_amd import _capi
 WS_FLOATS = 16 << 20      # the handle's split-K workspace and ticket counters (capi.hip, mbv_create)
 N_COUNTERS = 8192
 
-EPI = {"STORE": _capi.CONV_EPI_STORE, "RESID": _capi.CONV_EPI_RESID, "RESID_ACC": _capi.CONV_EPI_RESID_ACC}
+EPI = {"STORE": _capi.CONV_EPI_STORE, "RESID": _capi.CONV_EPI_RESID, "RESID_ACC": _capi.CONV_EPI_RESID_ACC,
+       "LN": _capi.CONV_EPI_LN}
 
 
 def ragged(B, T, seed=0):
@@ -30,7 +31,7 @@ def case(name, route, B, Cin, Cout, T, kind="conv", epi="STORE", K=3, dil=1, Tin
     c = dict(name=name, route=route, B=B, Cin=Cin, Cout=Cout, T=T, Tin=T if Tin is None else Tin, kind=kind,
              epi=epi, K=K, dil=dil, slope=slope, relu=0, reflect1=0, rstride=0, in_lens=None, out_lens=None,
              chan_add=False, res_chan_add=False, accum=False, out_scale=1.0, trim=None, splitk=0, prec=0,
-             pair=False, pair_route=None, S_gt1=False, check=None, seed=len(name))
+             pair=False, pair_route=None, S_gt1=False, check=None, seed=len(name), ln_res=False, ln_out_lens=None)
     for k, v in kw.items():
         assert k in c, k
         c[k] = v
@@ -169,6 +170,37 @@ CASES = [
 BY_NAME = {c["name"]: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 
+
+def _ln_site(site, H, T, B=3, Fc=768, rot=0):
+    """The conv + LayerNorm launches of mbv_encode (EPI_LN, conv1d_narrow.hip) as it sets them: `conv_o` (K 1, residual),
+    `ffn2` (K 3, in_lens, out_lens, residual, the mask behind the LayerNorm in the last layer only), `dp1` / `dp2` (K 3, relu, in_lens, dp1 with
+    the speaker's chan_add).  No activation on the input (slope 1)."""
+    pool = [T, 0, 1, max(1, min(T - 1, T // 2 // 32 * 32 + 13))]
+    lens = [pool[(i + rot) % 4] for i in range(B)]
+    kw = {"conv_o": dict(Cin=H, Cout=H, K=1, ln_res=True),
+          "ffn2": dict(Cin=Fc, Cout=H, K=3, in_lens=lens, out_lens=lens, ln_res=True, ln_out_lens=lens),   # the last layer
+          "ffn2i": dict(Cin=Fc, Cout=H, K=3, in_lens=lens, out_lens=lens, ln_res=True),                    # the layers before it
+          "dp1": dict(Cin=H, Cout=256, K=3, relu=1, chan_add=True, in_lens=lens),
+          "dp2": dict(Cin=256, Cout=256, K=3, relu=1, in_lens=lens)}[site]
+    return case("ln_%s_h%d_t%d" % (site, H, T), "NARROW_M", B, kw.pop("Cin"), kw.pop("Cout"), T, epi="LN", slope=1.0,
+                **kw)
+
+
+# conv + channel LayerNorm in one launch: not part of CASES / MATRIX (the decoder's matrix); test_conv_plan.py pins their
+# route, test_gpu_small_ops.py runs them against the float64 reference of small_op_cases.py
+LN_CASES = [
+    _ln_site("conv_o", 192, 1), _ln_site("conv_o", 192, 33, rot=1), _ln_site("conv_o", 192, 200), _ln_site("conv_o", 192, 256, rot=2),
+    _ln_site("ffn2", 192, 1, rot=2), _ln_site("ffn2", 192, 33), _ln_site("ffn2", 192, 200, rot=1), _ln_site("ffn2", 192, 256, rot=3),
+    _ln_site("dp1", 192, 1), _ln_site("dp1", 192, 33, rot=3), _ln_site("dp1", 192, 200, rot=2), _ln_site("dp1", 192, 256),
+    _ln_site("dp2", 192, 1, rot=3), _ln_site("dp2", 192, 33, rot=2), _ln_site("dp2", 192, 200), _ln_site("dp2", 192, 256, rot=1),
+    # the mini configuration: 96 hidden channels
+    _ln_site("conv_o", 96, 33), _ln_site("conv_o", 96, 256, rot=1), _ln_site("ffn2", 96, 1, rot=1), _ln_site("ffn2", 96, 200, rot=2),
+    _ln_site("dp1", 96, 33, rot=1), _ln_site("dp1", 96, 256, rot=3),
+    _ln_site("ffn2i", 192, 33, rot=1), _ln_site("ffn2i", 192, 200), _ln_site("ffn2i", 96, 256, rot=2),
+]
+LN_BY_NAME = {c["name"]: c for c in LN_CASES}
+assert len(LN_BY_NAME) == len(LN_CASES)
+
 # ljs_mb B = 64, T' = 566 (bench shape) and uudb B = 32 (the per-GPU share of the sharded configuration): DESIGN §3
 PRODUCTION = [
     # (what, case, expected routes)
@@ -202,7 +234,8 @@ def desc(c, B=None, ptrs=None, splitk=None, prec=None, trim=True, ws=True):
     d.in_slope, d.relu, d.reflect1 = c["slope"], c["relu"], c["reflect1"]
     d.out_scale = c["out_scale"]
     want = {"in_lens": c["in_lens"] is not None, "out_lens": c["out_lens"] is not None, "chan_add": c["chan_add"],
-            "res": c["epi"] != "STORE", "res_chan_add": c["res_chan_add"], "accum_in": c["accum"]}
+            "res": c["epi"] in ("RESID", "RESID_ACC") or c["ln_res"], "ln_out_lens": c["ln_out_lens"] is not None,
+            "ln_gamma": c["epi"] == "LN", "ln_beta": c["epi"] == "LN", "res_chan_add": c["res_chan_add"], "accum_in": c["accum"]}
     for k, on in want.items():
         if on:
             setattr(d, k, (ptrs or {}).get(k, 1 << 20))

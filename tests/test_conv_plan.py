@@ -23,6 +23,33 @@ def test_case_plans_its_route(c):
         assert q["route"] == c["pair_route"], (c["name"], q)
 
 
+@pytest.mark.parametrize("c", cc.LN_CASES, ids=lambda c: c["name"])
+def test_ln_case_plans_the_narrow_kernel(c):
+    """conv + LayerNorm in one launch exists on the narrow kernel only, whatever the mode."""
+    for splitk in (0, 1):
+        p = cc.plan(cc.desc(c, splitk=splitk))
+        assert p["route"] == "NARROW_M" and p["S"] == 1, (c["name"], p)
+    assert c["T"] <= 256 and c["Cout"] % 32 == 0 and c["Cout"] <= 768
+
+
+def test_ln_descriptors_outside_the_narrow_kernel_are_refused():
+    base = cc.LN_BY_NAME["ln_ffn2_h192_t200"]
+    bad = [dict(base, T=257, Tin=257), dict(base, Cout=800), dict(base, Cout=100), dict(base, reflect1=1),
+           dict(base, K=13), dict(base, prec=3), dict(base, res_chan_add=True), dict(base, kind=4),
+           dict(base, trim=(1, 0, [1, 2, 3]))]
+    for c in bad:
+        with pytest.raises(Exception):
+            cc.plan(cc.desc(c))
+    d = cc.desc(base)
+    d.ln_gamma = None
+    with pytest.raises(Exception, match="ln_gamma"):
+        cc.plan(d)
+    d = cc.desc(cc.BY_NAME["narrow_resid"])
+    d.ln_out_lens = 1 << 20                 # LayerNorm fields on another epilogue
+    with pytest.raises(Exception, match="belong to LN"):
+        cc.plan(d)
+
+
 def test_matrix_is_covered():
     missing = [(r, sorted(f)) for r, f in cc.MATRIX
                if not any(cc.cell_route(c) == r and f <= cc.features(c) for c in cc.CASES)]

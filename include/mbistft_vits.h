@@ -169,6 +169,43 @@ int mbv_decoder_context(const mbv_config *cfg, int32_t out[2]);
 int mbv_decode_range(mbv_model *m, const float *z, const float *g, int B, int t_frames, int first, int count,
                      float *o, int64_t o_row_stride, void *stream);
 
+/* ---- row-exact ragged decode (no reference counterpart: the reference service, tts_vits.py:122-139, decodes one
+ * utterance per request; this is what lets a service batch requests and still emit that audio) ----------------
+ * OPT-IN, never the default.  Row b of a batch is an utterance of lengths[b] z-frames and is decoded as if alone:
+ * its samples [0, 256 lengths[b]) are BITWISE what mbv_decode returns for z[b, :, :lengths[b]] (g[b]) by itself
+ * in the default mode, the samples at and past 256 lengths[b] are zeros, and nothing of z at or behind a row's end
+ * is read.  (The default decoder is unmasked, as the reference's is — models.py:344-377 / 430-467 / 286-300 —
+ * so in a batch the last ~25 z-frames of every row but the longest depend on its batch-mates' lengths.)
+ * Every conv masks its input at the row's own length at its rate, only the column tiles below it run, the
+ * waveform tail takes the row's own frame count.  The narrow conv kernel (<= 256 columns) and the tiled kernels
+ * sum in different orders, so the rows are decoded in one run per CLASS of lengths:
+ *
+ * mbv_ragged_classes (host only, like mbv_conv_plan): the classes of z-lengths 1 .. t_max for cfg — two lengths
+ * share a class iff every conv of the decoder, planned for one utterance of that length, takes the narrow kernel
+ * or not alike.  Classes are intervals; first[i] = the first length of class i (first[0] = 1), at most `capacity`
+ * are written.  Returns the number of classes, -1 on a bad argument.  splitk != 0: one class (no bitwise claim).
+ *
+ * mbv_ragged_plan (host only): the decoder runs a ragged call makes for B rows of the given HOST lengths — one per
+ * non-empty class, cut further only where a run's largest tensor would reach 2 GiB (as a stand-alone decode's
+ * may not either) or 65535 rows.  run_of_row [B] (or NULL) receives the run of every row, -1 for a row of length 0.
+ * Returns the number of runs, -1 on a bad argument (a length outside [0, t_frames] included).
+ *
+ * mbv_decode_ragged: z DEVICE [B, 192, t_frames], g DEVICE [B, gin] or NULL, lengths_host HOST int64 [B] (the
+ * class of a row decides its launches, so the lengths are needed on the host; nothing is copied or synchronised),
+ * o DEVICE [B, 256 t_frames], written whole.  A row of length 0 is all zeros.  With "splitk": within fp32 rounding
+ * of the stand-alone decode (the split factor depends on the launch size), bitwise run to run.  Refused with a
+ * message, launching nothing: a length outside [0, t_frames], the options "trim" or "conv_bf16" set.
+ *
+ * mbv_synthesize_ragged: mbv_synthesize with the decoder in this mode; y_lengths_host HOST int64 [B] = the
+ * y_lengths mbv_encode wrote, read back by the caller in its one host sync (lengths above max_len are cut to it).
+ * outs->o_mb / spec / phase must be NULL (refused otherwise). */
+int mbv_ragged_classes(const mbv_config *cfg, int splitk, int t_max, int32_t *first, int capacity);
+int mbv_ragged_plan(const mbv_config *cfg, int splitk, int B, int t_frames, const int64_t *lengths, int32_t *run_of_row);
+int mbv_decode_ragged(mbv_model *m, const float *z, const float *g, int B, int t_frames, const int64_t *lengths_host,
+                      float *o, void *stream);
+int mbv_synthesize_ragged(mbv_model *m, int t_frames, const float *noise, float noise_scale, int max_len,
+                          const mbv_outputs *outs, const int64_t *y_lengths_host, void *stream);
+
 /* speaker embedding lookup: replaces `net.emb_g(sid)` (models.py:705).
  * out fp32 [B, gin] */
 int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, void *stream);

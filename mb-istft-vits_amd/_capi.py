@@ -22,6 +22,7 @@ SYMBOLS = [
     "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
     "mbv_spectrogram", "mbv_spectrogram_frames", "mbv_decoder_context", "mbv_decode_range",
     "mbv_resample_ready", "mbv_resample_pcm16_range",
+    "mbv_ragged_classes", "mbv_decode_ragged", "mbv_synthesize_ragged", "mbv_ragged_plan",
     "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
     "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
@@ -160,8 +161,18 @@ def lib():
     L.mbv_op_sdp_logw.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.mbv_op_sdp_noise.argtypes = [vp, vp, f32, vp, C.c_int64, vp]
     L.mbv_op_chan_add.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
+    # those four entries may be absent there, and calling one then raises AttributeError.  Everything else, and the
+    # in-tree library always, must match the header.
+    optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged") if os.environ.get("MBV_LIB") else ()
+    if hasattr(L, "mbv_ragged_classes") or not optional:
+        L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
+        L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
+        L.mbv_decode_ragged.argtypes = [vp, vp, vp, i32, i32, i64p, vp, vp]
+        L.mbv_synthesize_ragged.argtypes = [vp, i32, vp, C.c_float, i32, C.POINTER(MbvOutputs), i64p, vp]
     for s in SYMBOLS:
-        getattr(L, s)          # AttributeError if the header and the library ever drift
+        if s not in optional or hasattr(L, s):
+            getattr(L, s)      # AttributeError if the header and the library ever drift
     if L.mbv_abi_version() != ABI_VERSION:
         raise RuntimeError("libmbistft_vits.so ABI version mismatch")
     _lib = L

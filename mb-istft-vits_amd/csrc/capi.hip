@@ -4,6 +4,7 @@
 #include "../../include/mbistft_vits.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdarg>
@@ -105,6 +106,8 @@ struct mbv_model {
   int xpost_rows = 72;         // 72 (4 bands x 18) or 18 (single band)
   int exact_math = 0;          // MBV_ISTFT_EXACT=1: libm transcendentals in the iSTFT kernel
   int trim = 0;                    // option "trim": opt-in trimmed decode (run_decoder)
+  std::vector<int> ragged_first;   // row-exact ragged decode: first length of every class up to ragged_scanned (ragged_classes)
+  int ragged_scanned = 0, ragged_splitk = -1;
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
   // state of the last encode
@@ -1004,9 +1007,27 @@ int decoder_context(const mbv_config& c, int* Lc, int* Rc) {
   return 0;
 }
 
+// The row-exact ragged decode (mbv_decode_ragged): run_decoder on the rows of one class (run_decoder_ragged below).
+// Row b is an utterance of len[b] <= Td frames and is decoded as if alone: every conv masks its input at the
+// row's own length at that conv's rate (true zeros: the padding a stand-alone decode applies), only the column
+// tiles that hold columns below it exist as work, the waveform tail takes the row's own frame count, and the row
+// is stored at row row_map[b] of o.  Whatever a conv stores at columns past a row's end (its bias, the residual it
+// read there) is never loaded by a consumer.
+struct RaggedRows {
+  const int* len;          // device [B]: len_b
+  const int* len_u;        // us len_b
+  const int* len_uu;       // us^2 len_b
+  const int* row_map;      // device [B]: the row of o
+  float* o;
+  int64_t o_row_stride;
+  int t_min;               // host: the shortest row of the run (run_decoder checks that it plans like the longest)
+};
+
 int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, const float* gvec,
-                int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc, const DecodeRange* rg = nullptr) {
+                int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc, const DecodeRange* rg = nullptr,
+                const RaggedRows* rr = nullptr) {
   const mbv_config& c = m->cfg;
+  if (rr) zlens = rr->len;
   // ranged decode, default mode: the length rules of the conv planner see the one-shot lengths (conv1d_plan)
   const int rt_num = rg && !m->splitk ? rg->t_full : 0;
   const int I = c.inter_channels, C0 = c.upsample_initial_channel, gin = c.gin_channels;
@@ -1021,17 +1042,36 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   // 6 frames away from its valid samples: those are bitwise the default's.  Column-tile maps are built on the device
   // from ylen32 (no extra host sync), one per (rate, tile width) geometry.
   constexpr int kTrimMargin = 32;
-  const bool trim = m->trim && zlens != nullptr && !m->splitk && c.decoder != MBV_DEC_SINGLEBAND;
+  // (the ragged mode uses the same tile maps with a margin of zero: nothing behind a row's end is computed)
+  const bool trim = rr ? !m->splitk : (m->trim && zlens != nullptr && !m->splitk && c.decoder != MBV_DEC_SINGLEBAND);
+  const int trim_margin = rr ? 0 : kTrimMargin;
   struct TrimKey { int num, add, T, bn; const int* map; };
   std::vector<TrimKey> trim_maps;
+  // Ragged mode: the classes come from decoder_conv_args' restatement of the convs below.  Tie them to what is
+  // really launched: every conv, planned for one utterance of the run's shortest row and of its longest, must fall
+  // on the same side of the narrow / tiled divide — else rows of this run would sum in an order their stand-alone
+  // decode does not use.  (num, add: the conv's columns per z-frame, as for the tile maps.)
+  bool route_drift = false;
+  auto narrow_alone = [&](const ConvArgs& a, int num, int add, int len) {
+    ConvArgs s1 = a;
+    s1.B = 1; s1.trim_map = nullptr;
+    s1.T = num * len + add;
+    s1.Tin = a.Tin - a.T + s1.T;
+    s1.x_rstride = s1.Tin; s1.x_bstride = (int64_t)a.Cin * s1.Tin;
+    s1.y_bstride = a.y_bstride / a.T * s1.T;
+    s1.res_bstride = a.res ? (int64_t)a.M * s1.T : 0;
+    const int r = conv1d_plan(s1, false).route;
+    return r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH;
+  };
   auto with_trim = [&](ConvArgs& a, int num, int add) {
+    if (rr && !m->splitk && narrow_alone(a, num, add, rr->t_min) != narrow_alone(a, num, add, Td)) route_drift = true;
     if (!trim) return;
     const int bn = conv1d_trim_bn(a);
     if (!bn) return;
     for (const auto& k : trim_maps)
       if (k.num == num && k.add == add && k.T == a.T && k.bn == bn) { a.trim_map = k.map; a.trim_bn = bn; return; }
     int* map = sc.take<int>(launch_trim_map_ints(B, a.T, bn));
-    launch_trim_map(zlens, B, num, num * kTrimMargin + add, a.T, bn, map, s_main);
+    launch_trim_map(zlens, B, num, num * trim_margin + add, a.T, bn, map, s_main);
     trim_maps.push_back({num, add, a.T, bn, map});
     a.trim_map = map; a.trim_bn = bn;
   };
@@ -1057,7 +1097,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     // of their convs cannot fill the chip (single utterances, small batches: decoder_stage_concurrent)
     // they run on three streams — own temporaries each, the three xs updates chained by events in the
     // order of the one-stream schedule, so the result is bitwise the same.
-    const bool conc = decoder_stage_concurrent(m, B, ch, Lo);
+    const bool conc = decoder_stage_concurrent(m, B, ch, Lo) && !trim;
     float *t1s[3], *rs[3];
     t1s[0] = sc.take<float>(n);
     rs[0] = sc.take<float>(n);
@@ -1072,6 +1112,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       a.in_slope = kLrelu;
       a.epi = EPI_CONVT;
       a.convt_u = us;
+      if (rr) a.in_lens = i == 0 ? rr->len : rr->len_u;
       with_trim(a, L / Td, 0);                      // tiles run over INPUT frames (rate of the stage below)
       launch_conv1d(a, s);
     }
@@ -1120,6 +1161,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
             a.accum_in = j == 0 ? nullptr : xs;
             a.out_scale = j == 2 ? (1.f / 3.f) : 1.f;
           }
+          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
           launch_conv1d(a, s, rt_num * (Lo / Td));
           state = r;
@@ -1133,6 +1175,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           a.in_slope = kLrelu;
           if (q == 0) a.chan_add = cadd;
           own_ws(a);
+          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
           launch_conv1d(a, s, rt_num * (Lo / Td));
         }
@@ -1151,6 +1194,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
             if (conc && j > 0) HIPCHK(m, hipStreamWaitEvent(s, m->ev_rb[j - 1], 0));   // xs of the ResBlock before
           }
           own_ws(a);
+          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
           launch_conv1d(a, s, rt_num * (Lo / Td));
           if (conc && q == 2) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
@@ -1184,12 +1228,13 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   if (Bc < 1) Bc = 1;
   if (Bc > B) Bc = B;
   float* xpost = sc.take<float>((size_t)Bc * prow * Fr);
-  float* o = rg ? rg->o : outs ? outs->o : nullptr;
+  float* o = rg ? rg->o : rr ? rr->o : outs ? outs->o : nullptr;
   float* otmp = nullptr;
   if (!o) { otmp = sc.take<float>((size_t)B * 256 * Td); o = otmp; }
   // ranged: window sub-band samples (MB / MS) or output quads (SB) of the kept frames, 64 per z-frame either way
-  const IstftRange keep{rg ? 64 * rg->keep_first : 0, rg ? 64 * (rg->keep_first + rg->keep_count) : 0,
-                        rg ? rg->o_row_stride : 0};
+  IstftRange keep{rg ? 64 * rg->keep_first : 0, rg ? 64 * (rg->keep_first + rg->keep_count) : 0,
+                  rg ? rg->o_row_stride : 0, nullptr, nullptr};
+  if (rr) keep = IstftRange{0, 64 * Td, rr->o_row_stride, rr->len, rr->row_map};      // every tile of the class, cut per row in the kernel
   const int64_t M4 = (int64_t)(sb ? 4 : 256) * (sb ? (Fr - 1) : Td);          // waveform samples per utterance
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int nb = B - b0 < Bc ? B - b0 : Bc;
@@ -1198,6 +1243,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
                              (int64_t)prow * Fr, Fr, nb);
       a.in_slope = 0.01f;                              // F.leaky_relu default slope (models.py:363)
       a.reflect1 = 1;                                  // ReflectionPad1d((1,0)) (models.py:364)
+      if (rr) a.in_lens = rr->len_uu + b0;             // (in frames of the unpadded input: us^2 len_b + 1 padded ones)
       if (nb == B) with_trim(a, L / Td, 1);            // (a split run keeps every tile: the maps are per full batch)
       launch_conv1d(a, s);
     }
@@ -1208,7 +1254,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.spec = outs && outs->spec ? outs->spec + (size_t)b0 * 9 * Fr : nullptr;
       ia.phase = outs && outs->phase ? outs->phase + (size_t)b0 * 9 * Fr : nullptr;
       ia.B = nb; ia.F = Fr; ia.exact_math = m->exact_math; ia.prescaled = 1;
-      if (rg) {
+      if (rr) {
+        IstftRange kb = keep;
+        kb.row_lens += b0; kb.row_map += b0;
+        ia.o = o; ia.spec = ia.phase = nullptr;
+        launch_istft_single_range(ia, kb, s);
+      } else if (rg) {
         ia.o = o + (size_t)b0 * rg->o_row_stride; ia.spec = ia.phase = nullptr;
         launch_istft_single_range(ia, keep, s);
       } else {
@@ -1224,7 +1275,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.B = nb; ia.Tp = Td; ia.multistream = ms;
       ia.fixed_bank = !ia.multistream; ia.exact_math = m->exact_math; ia.prescaled = 1;
       if (trim && nb == B && !ia.o_mb && !ia.spec && !ia.phase) ia.trim_lens = zlens;
-      if (rg) {
+      if (rr) {
+        IstftRange kb = keep;
+        kb.row_lens += b0; kb.row_map += b0;
+        ia.o = o; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
+        launch_istft_pqmf_range(ia, kb, s);
+      } else if (rg) {
         ia.o = o + (size_t)b0 * rg->o_row_stride; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
         launch_istft_pqmf_range(ia, keep, s);
       } else {
@@ -1238,6 +1294,177 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   HIPCHK(m, hipEventRecord(m->evk[2], s));
   m->evk_set = true;
   m->evk_split = Bc < B;
+  if (route_drift) return m->fail("internal error: a ragged run holds rows whose convs plan differently (ragged_classes out of step with run_decoder)");
+  return 0;
+}
+
+// ------------------------------------------------------------------ row-exact ragged decode
+// Every conv of the decoder as the planner sees it when ONE utterance of `len` z-frames is decoded alone (the
+// shapes run_decoder builds; data pointers are only ever tested against null).
+void decoder_conv_args(const mbv_config& c, int len, int splitk, std::vector<ConvArgs>* out) {
+  static const float kSome = 0.f;                   // "a tensor is given"
+  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
+  const int us = sb ? 8 : 4, I = c.inter_channels, C0 = c.upsample_initial_channel;
+  auto conv = [&](int Cin, int M, int K, int dil, int T, int epi) {
+    ConvArgs a{};
+    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = K; a.dil = dil; a.pad_left = (K - 1) * dil / 2;
+    a.Tin = T; a.x_rstride = T; a.x_bstride = (int64_t)Cin * T;
+    a.T = T; a.y_bstride = (int64_t)M * T; a.epi = epi; a.in_slope = 1.f; a.out_scale = 1.f; a.B = 1;
+    a.splitk = splitk;
+    if (epi == EPI_RESID || epi == EPI_RESID_ACC) { a.res = &kSome; a.res_bstride = (int64_t)M * T; }
+    return a;
+  };
+  out->clear();
+  out->push_back(conv(I, C0, 7, 1, len, EPI_STORE));                          // conv_pre
+  int L = len;
+  for (int i = 0; i < 2; ++i) {
+    const int ch = C0 >> (i + 1), Lo = us * L;
+    ConvArgs u = conv(C0 >> i, us * ch, 16 / us + 1, 1, L, EPI_CONVT);          // ups[i] as a phase conv over input frames
+    u.pad_left = us == 4 ? 2 : 1; u.convt_u = us; u.y_bstride = (int64_t)ch * Lo;
+    out->push_back(u);
+    for (int j = 0; j < 3; ++j) {
+      const int k = c.resblock_kernel_sizes[j];
+      const int nq = c.resblock_type == 2 ? 2 : 3;
+      for (int q = 0; q < nq; ++q) {
+        const int d = c.resblock_dilations[j][q];
+        const int last = q == nq - 1 ? EPI_RESID_ACC : EPI_RESID;
+        if (c.resblock_type == 2) {
+          out->push_back(conv(ch, ch, k, d, Lo, last));
+        } else {
+          out->push_back(conv(ch, ch, k, d, Lo, EPI_STORE));
+          out->push_back(conv(ch, ch, k, 1, Lo, last));
+        }
+      }
+    }
+    L = Lo;
+  }
+  ConvArgs p = conv(C0 >> 2, sb ? 18 : 72, 7, 1, L + 1, EPI_STORE);             // conv_post behind ReflectionPad1d((1, 0))
+  p.Tin = L; p.x_rstride = L; p.x_bstride = (int64_t)(C0 >> 2) * L; p.reflect1 = 1;
+  out->push_back(p);
+}
+
+// Classes of z-lengths 1 .. t_max: two lengths share a class iff every conv of the decoder, planned for an
+// utterance of that length alone, lands on the same side of the one divide that changes a sample's chain of
+// operations — the narrow kernel (sums start from the bias) or a tiled kernel (bias added last; BIG / SMALL / M64 /
+// HALF / VS / SPLIT_BATCH compute an element with the same chain).  first[i] = the first length of class i.  In the
+// split-K mode nothing is bitwise across launch sizes anyway: one class.
+void ragged_classes(const mbv_config& c, int splitk, int t_max, std::vector<int>* first) {
+  first->assign(1, 1);
+  if (splitk) return;
+  std::vector<ConvArgs> convs;
+  std::vector<char> prev, cur;
+  for (int len = 1; len <= t_max; ++len) {
+    decoder_conv_args(c, len, 0, &convs);
+    cur.clear();
+    for (const auto& a : convs) {
+      const int r = conv1d_plan(a, false).route;
+      cur.push_back(r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH);
+    }
+    if (len > 1 && cur != prev) first->push_back(len);
+    prev.swap(cur);
+  }
+}
+
+// null, or why the lengths are refused
+const char* ragged_lens_error(const int64_t* lens, int B, int Tp) {
+  if (!lens) return "the per-row lengths are missing";
+  for (int b = 0; b < B; ++b)
+    if (lens[b] < 0 || lens[b] > Tp) return "a row length lies outside [0, t_frames]";
+  return nullptr;
+}
+
+// One decoder run of the ragged decode: rows of one class, T = the longest of them
+struct RaggedRun { std::vector<int> rows, lens; int Tc; };
+
+// Host: the runs of a ragged decode of B rows with HOST lengths (already checked; clamped to Td here).  Rows of
+// length 0 belong to no run.  A run's tensors stay below 2 GiB each, as a stand-alone decode's do
+// (conv1d_narrow_supported tests it, and the route of a conv must not depend on the batch).
+void ragged_plan(const mbv_config& c, const std::vector<int>& first, int B, int Td, const int64_t* lens,
+                 std::vector<RaggedRun>* runs) {
+  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, C0 = c.upsample_initial_channel;
+  std::vector<std::vector<int>> rows(first.size());
+  auto len_of = [&](int b) { return (int)(lens[b] < Td ? lens[b] : Td); };
+  for (int b = 0; b < B; ++b) {
+    const int len = len_of(b);
+    if (len <= 0) continue;
+    size_t k = 0;
+    while (k + 1 < first.size() && first[k + 1] <= len) ++k;
+    rows[k].push_back(b);
+  }
+  runs->clear();
+  for (const auto& cls : rows) {
+    for (size_t at = 0; at < cls.size();) {
+      RaggedRun r;
+      r.Tc = 0;
+      while (at < cls.size() && r.rows.size() < 65535) {
+        const int len = len_of(cls[at]);
+        const int64_t Tn = len > r.Tc ? len : r.Tc;
+        int64_t per_row = (int64_t)I * Tn;
+        if ((int64_t)(C0 >> 2) * us * us * Tn > per_row) per_row = (int64_t)(C0 >> 2) * us * us * Tn;
+        if (72 * ((int64_t)us * us * Tn + 1) > per_row) per_row = 72 * ((int64_t)us * us * Tn + 1);
+        if (!r.rows.empty() && (int64_t)(r.rows.size() + 1) * per_row * 4 >= (1ll << 31)) break;
+        r.Tc = (int)Tn;
+        r.rows.push_back(cls[at]); r.lens.push_back(len);
+        ++at;
+      }
+      runs->push_back(std::move(r));
+    }
+  }
+}
+
+// ... with the classes of the handle's mode, scanned once up to the longest T' seen
+void ragged_plan(mbv_model* m, int B, int Td, const int64_t* lens, std::vector<RaggedRun>* runs) {
+  if (m->ragged_scanned < Td || m->ragged_splitk != m->splitk) {
+    ragged_classes(m->cfg, m->splitk, Td, &m->ragged_first);
+    m->ragged_scanned = Td; m->ragged_splitk = m->splitk;
+  }
+  ragged_plan(m->cfg, m->ragged_first, B, Td, lens, runs);
+}
+
+size_t ragged_scratch_bytes(const mbv_config& c, const std::vector<RaggedRun>& runs) {
+  size_t need = 0;
+  for (const auto& r : runs) {
+    const size_t n = r.rows.size();
+    const size_t v = (n * c.inter_channels * r.Tc + n * c.gin_channels) * sizeof(float) + 4 * n * sizeof(int) + 8 * 256 +
+                     decoder_scratch_bytes(c, (int)n, r.Tc);
+    if (v > need) need = v;
+  }
+  return need;
+}
+
+// The ragged decode of z [B, I, zstride]: o row b = the stand-alone decode of z[b, :, :len_b] over [0, spf len_b),
+// zeros behind.  One decoder run per RaggedRun, on its rows gathered into scratch.  The runs are ordered on the
+// stream, so they share the arena.
+int run_decoder_ragged(mbv_model* m, const float* z, int zstride, const float* gvec, int B, int Td,
+                       const std::vector<RaggedRun>& runs, float* o, int64_t o_row_stride, hipStream_t s, Bump& sc) {
+  const mbv_config& c = m->cfg;
+  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, gin = c.gin_channels;
+  const int64_t spf = 256;
+  HIPCHK(m, hipMemset2DAsync(o, (size_t)o_row_stride * sizeof(float), 0, (size_t)(spf * Td) * sizeof(float), B, s));
+  const size_t base = sc.off;
+  for (const auto& run : runs) {
+    const size_t n = run.rows.size();
+    const int Tc = run.Tc;
+    sc.off = base;
+    int* ints = sc.take<int>(4 * n);
+    for (size_t f = 0; f < n; f += kRaggedChunk) {
+      RaggedRowsArg r{};
+      const int nn = (int)(n - f < (size_t)kRaggedChunk ? n - f : (size_t)kRaggedChunk);
+      for (int i = 0; i < nn; ++i) { r.row[i] = run.rows[f + i]; r.len[i] = run.lens[f + i]; }
+      launch_ragged_rows(r, nn, (int)f, us, ints, (int)n, s);
+    }
+    float* zc = sc.take<float>(n * I * Tc);
+    launch_gather_frames(z, (int64_t)I * zstride, zstride, ints, ints + n, (int)n, I, Tc, zc, s);
+    float* gc = nullptr;
+    if (gvec && gin) {
+      gc = sc.take<float>(n * gin);
+      launch_gather_frames(gvec, gin, 1, ints, nullptr, (int)n, gin, 1, gc, s);
+    }
+    const RaggedRows rr{ints + n, ints + 2 * n, ints + 3 * n, ints, o, o_row_stride,
+                        *std::min_element(run.lens.begin(), run.lens.end())};
+    if (run_decoder(m, zc, Tc, nullptr, gc, (int)n, Tc, nullptr, s, sc, nullptr, &rr)) return 1;
+  }
+  sc.off = base;
   return 0;
 }
 
@@ -1782,12 +2009,30 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
   return 0;
 }
 
-int mbv_synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
-                   const mbv_outputs* outs, void* stream) {
-  if (!m) return 1;
-  if (!m->encoded) return m->fail("mbv_synthesize without a preceding mbv_encode");
+}  // extern "C"
+
+namespace {
+// what the ragged mode refuses, before anything is launched (null: nothing)
+const char* ragged_mode_error(const mbv_model* m, const mbv_outputs* outs) {
+  if (outs && (outs->o_mb || outs->spec || outs->phase)) return "the ragged decode writes the waveform only: o_mb / spec / phase must be NULL";
+  if (m->trim) return "the options \"trim\" and the ragged decode exclude each other";
+  if (m->conv_bf16) return "the ragged decode is not built for the \"conv_bf16\" mode";
+  return nullptr;
+}
+
+// mbv_synthesize; y_lens_host != nullptr: the decoder in the row-exact ragged mode (mbv_synthesize_ragged)
+int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
+               const mbv_outputs* outs, const int64_t* y_lens_host, void* stream) {
+  const char* const who = y_lens_host ? "mbv_synthesize_ragged" : "mbv_synthesize";
+  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
   if (t_frames <= 0) return m->fail("t_frames must be > 0");
   const mbv_config& c = m->cfg;
+  std::vector<RaggedRun> runs;
+  if (y_lens_host) {
+    const char* why = ragged_mode_error(m, outs);
+    if (!why) why = ragged_lens_error(y_lens_host, m->B, t_frames);
+    if (why) return m->fail("%s: %s", who, why);
+  }
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
   const int B = m->B, T = m->T, Tp = t_frames, H = c.hidden_channels, I = c.inter_channels;
@@ -1795,8 +2040,9 @@ int mbv_synthesize(mbv_model* m, int t_frames, const float* noise, float noise_s
   const int Td = (max_len > 0 && max_len < Tp) ? max_len : Tp;
   const size_t BTp = (size_t)B * Tp;
   const bool run_dec = outs && (outs->o || outs->o_mb || outs->spec || outs->phase);
+  if (y_lens_host && run_dec) ragged_plan(m, B, Td, y_lens_host, &runs);
   size_t need = (BTp * (4 * I + 3 * H) + (size_t)B * (2 * H * kFlowLayers + 2)) * 4 + wn_units_ints(B, Tp) * 4 + 64 * 256 +
-                decoder_scratch_bytes(c, B, Td);
+                (y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td));
   if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
   Bump sc{m->scrB, m->scrB_bytes};
   for (const char* k : {"dec_conv_pre", "dec_up_0", "dec_up_1", "dec_res_0", "dec_res_1", "x_post"})
@@ -1821,13 +2067,77 @@ int mbv_synthesize(mbv_model* m, int t_frames, const float* noise, float noise_s
   for (int f = kNFlows - 1; f >= 0; --f)
     run_coupling(m, f, true, z, m->has_g ? m->gvec : nullptr, hbuf, acts, skip, gc, ustart, m->ylen32, B, Tp, s);
   HIPCHK(m, hipEventRecord(m->ev[5], s));
-  if (run_dec) {
+  if (run_dec && y_lens_host) {
+    if (run_decoder_ragged(m, z, Tp, m->has_g ? m->gvec : nullptr, B, Td, runs, outs->o, (int64_t)256 * Td, s, sc)) return 1;
+  } else if (run_dec) {
     if (run_decoder(m, z, Tp, m->ylen32, m->has_g ? m->gvec : nullptr, B, Td, outs, s, sc)) return 1;
   }
   HIPCHK(m, hipEventRecord(m->ev[6], s));
   HIPCHK(m, hipGetLastError());
   m->ev_b = true;
   m->evr_b[m->ticket % mbv_model::kEvRing] = true;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mbv_synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
+                   const mbv_outputs* outs, void* stream) {
+  if (!m) return 1;
+  return synthesize(m, t_frames, noise, noise_scale, max_len, outs, nullptr, stream);
+}
+
+int mbv_synthesize_ragged(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
+                          const mbv_outputs* outs, const int64_t* y_lengths_host, void* stream) {
+  if (!m) return 1;
+  if (!y_lengths_host) return m->fail("mbv_synthesize_ragged: y_lengths_host is NULL");
+  return synthesize(m, t_frames, noise, noise_scale, max_len, outs, y_lengths_host, stream);
+}
+
+int mbv_ragged_classes(const mbv_config* cfg, int splitk, int t_max, int32_t* first, int capacity) {
+  if (!cfg || t_max < 1 || capacity < 0 || (capacity > 0 && !first)) return -1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+  std::vector<int> f;
+  ragged_classes(*cfg, splitk != 0, t_max, &f);
+  for (size_t i = 0; i < f.size() && i < (size_t)capacity; ++i) first[i] = f[i];
+  return (int)f.size();
+}
+
+int mbv_ragged_plan(const mbv_config* cfg, int splitk, int B, int t_frames, const int64_t* lengths, int32_t* run_of_row) {
+  if (!cfg || B <= 0 || t_frames < 1 || ragged_lens_error(lengths, B, t_frames)) return -1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+  std::vector<int> first;
+  ragged_classes(*cfg, splitk != 0, t_frames, &first);
+  std::vector<RaggedRun> runs;
+  ragged_plan(*cfg, first, B, t_frames, lengths, &runs);
+  if (run_of_row) {
+    for (int b = 0; b < B; ++b) run_of_row[b] = -1;
+    for (size_t r = 0; r < runs.size(); ++r)
+      for (int b : runs[r].rows) run_of_row[b] = (int32_t)r;
+  }
+  return (int)runs.size();
+}
+
+int mbv_decode_ragged(mbv_model* m, const float* z, const float* g, int B, int t_frames, const int64_t* lengths_host,
+                      float* o, void* stream) {
+  if (!m) return 1;
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!z || !o || B <= 0 || t_frames <= 0) return m->fail("mbv_decode_ragged: bad arguments");
+  const char* why = ragged_mode_error(m, nullptr);
+  if (!why) why = ragged_lens_error(lengths_host, B, t_frames);
+  if (why) return m->fail("mbv_decode_ragged: %s", why);
+  const mbv_config& c = m->cfg;
+  DEVICE_GUARD(m);
+  std::vector<RaggedRun> runs;
+  ragged_plan(m, B, t_frames, lengths_host, &runs);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, ragged_scratch_bytes(c, runs))) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  m->stages.clear();
+  if (run_decoder_ragged(m, z, t_frames, (g && c.gin_channels) ? g : nullptr, B, t_frames, runs, o,
+                         (int64_t)256 * t_frames, (hipStream_t)stream, sc))
+    return 1;
+  HIPCHK(m, hipGetLastError());
   return 0;
 }
 

@@ -184,6 +184,10 @@ __device__ __forceinline__ void irfft16_hann(const float* re, const float* im, f
 // RANGED (launch_istft_pqmf_range): the grid holds only the tiles that cover sub-band samples [rg.keep_lo,
 // rg.keep_hi) of every row, phase C stores only those (at a.o + b rg.o_row_stride + 4 (m - keep_lo)), and nothing
 // else is written.  (rg is the last argument, so that the one-shot instantiations keep their code.)
+// RANGED with rg.row_lens (the row-exact ragged decode, mbv_decode_ragged): row b is an utterance of row_lens[b]
+// z-frames inside a launch laid out for a.Tp — its frame count, envelope edges and the synthesis filter's zero
+// padding are those of its stand-alone launch (F_b = 16 len_b + 1, M_b = 64 len_b), only the strides are a.Tp's;
+// tiles at and past M_b do nothing, and row b is stored at row rg.row_map[b] of o.
 template <int TM, int NTHREADS, bool FIXED, bool FAST, bool PRE, bool POLAR, bool RANGED = false>
 __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) void istft_pqmf_kernel(const IstftArgs a, const float* __restrict__ taps,
                                                               int tiles_per_utt, int total_tiles, const IstftRange rg) {
@@ -213,6 +217,16 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
   const int Tp = a.Tp;
   const int F = 16 * Tp + 1;
   const int M = 64 * Tp;                  // sub-band samples per band
+  // frames / samples that exist for this row (RANGED + row_lens: the row's own; F and M stay the strides)
+  int Fe = F, Me = M, orow = b;
+  if constexpr (RANGED) {
+    if (rg.row_lens) {
+      const int len = rg.row_lens[b];
+      Fe = 16 * len + 1; Me = 64 * len;
+      if (m0 >= Me) return;
+    }
+    if (rg.row_map) orow = rg.row_map[b];
+  }
   const int tid = threadIdx.x;
   const int f_lo = m0 / 4 - 3;
   // raw buffer descriptors (stride 0, byte range of the whole tensor; launcher checks < 4 GiB)
@@ -229,7 +243,7 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
     const int band = tid / NF, fl = tid % NF;
     const int f = f_lo + fl;
     float out[16];
-    if (f >= 0 && f < F) {
+    if (f >= 0 && f < Fe) {
       float re[9], im[9];
       if constexpr (POLAR) {
         // input = (spec, phase) tensors [B, 4, 9, F] (chunked decode: cross-faded spectrograms)
@@ -280,16 +294,16 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
     const int m = m0 - 8 + u;
     const int fp = m0 / 4 - 2 + q;
     float y[4] = {0.f, 0.f, 0.f, 0.f};
-    if (u < YL && m >= 0 && m < M) {
+    if (u < YL && m >= 0 && m < Me) {
       float env;
-      if (fp - 1 >= 0 && fp + 2 < F) {
+      if (fp - 1 >= 0 && fp + 2 < Fe) {
         env = 1.5f;                        // sum of squared hann over 4 overlapping frames
       } else {
         env = 0.f;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int f = fp - 1 + g;
-          env += (f >= 0 && f < F) ? WSQ16[12 - 4 * g + r] : 0.f;
+          env += (f >= 0 && f < Fe) ? WSQ16[12 - 4 * g + r] : 0.f;
         }
       }
       const float renv = 1.f / env;          // one division per lane (torch.istft divides per sample)
@@ -339,7 +353,7 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
   // ---------------- phase C: polyphase synthesis filter --------------------
   if (tid < TM) {
     const int m = m0 + tid;
-    if (m < M) {
+    if (m < Me) {
       float acc[4] = {0.f, 0.f, 0.f, 0.f};
       if constexpr (FIXED) {
 #pragma unroll
@@ -369,7 +383,7 @@ __global__ __launch_bounds__(NTHREADS, (2048 / NTHREADS) * (NTHREADS / 256)) voi
       }
       if constexpr (RANGED) {
         if (m >= rg.keep_lo && m < rg.keep_hi)
-          *reinterpret_cast<float4*>(a.o + (int64_t)b * rg.o_row_stride + 4 * (int64_t)(m - rg.keep_lo)) =
+          *reinterpret_cast<float4*>(a.o + (int64_t)orow * rg.o_row_stride + 4 * (int64_t)(m - rg.keep_lo)) =
               make_float4(acc[0], acc[1], acc[2], acc[3]);
       } else {
         *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * M + 4 * (int64_t)m) =
@@ -455,12 +469,21 @@ __global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, 
   const int b = blockIdx.x / tiles_per_utt;
   const int q0 = ((blockIdx.x % tiles_per_utt) + (RANGED ? rg.keep_lo / QPB : 0)) * QPB;
   const int F = a.F;
-  const int nquads = F - 1;                // 4 (F-1) output samples
+  // frames that exist for this row (RANGED + row_lens: 64 len_b + 1, see istft_pqmf_kernel; F stays the stride)
+  int Fe = F, orow = b;
+  if constexpr (RANGED) {
+    if (rg.row_lens) {
+      Fe = 64 * rg.row_lens[b] + 1;
+      if (q0 >= Fe - 1) return;
+    }
+    if (rg.row_map) orow = rg.row_map[b];
+  }
+  const int nquads = Fe - 1;               // 4 (F-1) output samples
 
   {
     const int f = q0 - 1 + tid;
     float out[16];
-    if (tid < QPB + 3 && f >= 0 && f < F) {
+    if (tid < QPB + 3 && f >= 0 && f < Fe) {
       float re[9], im[9];
       if constexpr (POLAR) {
 #pragma unroll
@@ -502,13 +525,13 @@ __global__ __launch_bounds__(256) void istft_single_kernel(const IstftSbArgs a, 
       for (int g = 0; g < 4; ++g) {
         const int f = fp - 1 + g;
         sacc += fr[(12 - 4 * g + r) * NFS + tid + g];
-        env += (f >= 0 && f < F) ? HANN16[12 - 4 * g + r] * HANN16[12 - 4 * g + r] : 0.f;
+        env += (f >= 0 && f < Fe) ? HANN16[12 - 4 * g + r] * HANN16[12 - 4 * g + r] : 0.f;
       }
       y[r] = sacc / env;
     }
     if constexpr (RANGED) {
       if (fp >= rg.keep_lo && fp < rg.keep_hi)
-        *reinterpret_cast<float4*>(a.o + (int64_t)b * rg.o_row_stride + 4 * (int64_t)(fp - rg.keep_lo)) =
+        *reinterpret_cast<float4*>(a.o + (int64_t)orow * rg.o_row_stride + 4 * (int64_t)(fp - rg.keep_lo)) =
             make_float4(y[0], y[1], y[2], y[3]);
     } else {
       *reinterpret_cast<float4*>(a.o + (int64_t)b * 4 * nquads + 4 * (int64_t)fp) =

@@ -248,9 +248,15 @@ void launch_istft_pqmf(const IstftArgs& a, hipStream_t s);
 // of row b at o[b * o_row_stride + 4 (m - keep_lo) + p]; SB: output quads [keep_lo, keep_hi), quad q at
 // o[b * o_row_stride + 4 (q - keep_lo)].  o is already offset to the chunk's first sample.  (A separate
 // argument, so that the one-shot kernels keep their argument layout and code.)
+// row_lens / row_map (device [B], or null): the row-exact ragged decode.  Row b is an utterance of row_lens[b]
+// z-frames (<= a.Tp): its frame count, envelope edges and filter padding are those of its stand-alone launch, only
+// the tensor strides are the launch's; nothing at or past 64 row_lens[b] is computed or stored; row b goes to row
+// row_map[b] of o.
 struct IstftRange {
   int keep_lo, keep_hi;
   int64_t o_row_stride;
+  const int* row_lens;
+  const int* row_map;
 };
 void launch_istft_pqmf_range(const IstftArgs& a, const IstftRange& r, hipStream_t s);
 
@@ -336,6 +342,15 @@ void launch_fill(float* p, float v, int64_t n, hipStream_t s);
 // out: (B + 1) + B * ceil(T / BN) ints (launch_trim_map_ints)
 size_t launch_trim_map_ints(int B, int T, int BN);
 void launch_trim_map(const int* lens, int B, int num, int add, int T, int BN, int* out, hipStream_t s);
+// row-exact ragged decode: n rows of a class, given by value from the host (rows / lens hold up to kRaggedChunk
+// entries per launch) -> out[0 .. 4 stride): the source row of every class row, then its length at the three
+// rates of the decoder (len, us len, us^2 len), entry first + i
+constexpr int kRaggedChunk = 256;
+struct RaggedRowsArg { int row[kRaggedChunk]; int len[kRaggedChunk]; };
+void launch_ragged_rows(const RaggedRowsArg& r, int n, int first, int us, int* out, int stride, hipStream_t s);
+// dst[i, c, t] = src[rows[i], c, t] for t < lens[i] (lens null: t < T): dst [n, C, T], src rows of C x src_rstride
+void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride, const int* rows, const int* lens,
+                          int n, int C, int T, float* dst, hipStream_t s);
 // which column-tile width launch_conv1d will use for this conv (128 or 384; 0: a kernel without trim support)
 int conv1d_trim_bn(const ConvArgs& a);
 

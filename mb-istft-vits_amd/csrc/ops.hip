@@ -481,6 +481,39 @@ void launch_trim_map(const int* lens, int B, int num, int add, int T, int BN, in
   hipLaunchKernelGGL(trim_map_kernel, dim3(1), dim3(256), 0, s, lens, B, num, add, T, BN, out);
 }
 
+// row-exact ragged decode: the rows of a class and their lengths at the decoder's three rates, from host values
+// carried in the kernel arguments (no copy, no synchronisation)
+__global__ void ragged_rows_kernel(const RaggedRowsArg r, int n, int first, int us, int* __restrict__ out, int stride) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  const int len = r.len[i];
+  out[first + i] = r.row[i];
+  out[stride + first + i] = len;
+  out[2 * stride + first + i] = us * len;
+  out[3 * stride + first + i] = us * us * len;
+}
+
+void launch_ragged_rows(const RaggedRowsArg& r, int n, int first, int us, int* out, int stride, hipStream_t s) {
+  hipLaunchKernelGGL(ragged_rows_kernel, dim3(1), dim3(kRaggedChunk), 0, s, r, n, first, us, out, stride);
+}
+
+__global__ void gather_frames_kernel(const float* __restrict__ src, int64_t src_bstride, int src_rstride,
+                                     const int* __restrict__ rows, const int* __restrict__ lens, int C, int T,
+                                     float* __restrict__ dst) {
+  const int i = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int len = lens ? lens[i] : T;
+  if (t < T && t < len)
+    dst[((int64_t)i * C + c) * T + t] = src[rows[i] * src_bstride + (int64_t)c * src_rstride + t];
+}
+
+void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride, const int* rows, const int* lens,
+                          int n, int C, int T, float* dst, hipStream_t s) {
+  const int nt = T >= 256 ? 256 : 64;
+  hipLaunchKernelGGL(gather_frames_kernel, dim3((T + nt - 1) / nt, C, n), dim3(nt), 0, s, src, src_bstride,
+                     src_rstride, rows, lens, C, T, dst);
+}
+
 void launch_fill(float* p, float v, int64_t n, hipStream_t s) {
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;

@@ -35,9 +35,13 @@ class _Node(nn.Module):
 
 
 class _Decoder(_Node):
-    """`net.dec(z, g=None)` -> (y_g_hat, y_mb_hat, spec, phase)  (models.py:344-377 / 430-467)."""
+    """`net.dec(z, g=None)` -> (y_g_hat, y_mb_hat, spec, phase)  (models.py:344-377 / 430-467).
+    `net.dec(z, g=g, lengths=lens)` (extension) -> (o, None, None, None): the row-exact ragged decode, every row
+    bitwise its stand-alone decode (`SynthesizerTrn._decode_ragged`)."""
 
-    def forward(self, x, g=None):
+    def forward(self, x, g=None, lengths=None):
+        if lengths is not None:
+            return self._owner()._decode_ragged(x, g, lengths), None, None, None
         return self._owner()._decode(x, g)
 
 
@@ -317,7 +321,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
-             prior_rows=None, trim=False):
+             prior_rows=None, trim=False, ragged=False):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -328,7 +332,8 @@ class SynthesizerTrn(nn.Module):
           frames_hook  host-side override of T' (tests: pad a sub-batch like its parent batch)
           prior_rows   (lo, hi, B_global): draw the prior noise for the whole global batch and use
                        rows lo:hi (ranks seeded alike then reproduce the single-process draw)
-          trim         opt-in trimmed decode (see `infer`)"""
+          trim         opt-in trimmed decode (see `infer`)
+          ragged       opt-in row-exact ragged decode (see `infer`)"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
@@ -362,7 +367,11 @@ class SynthesizerTrn(nn.Module):
             stat = torch.stack((hi, -lo))           # [T'max, > 0 iff an utterance was flagged -1]
             if stat_reduce is not None:
                 stat_reduce(stat)
-            Tp, flag = (int(v) for v in stat.tolist())      # the one host sync (commons.py:123)
+            if ragged:                              # the B lengths ride in the same read-back
+                host = torch.cat((stat, y_lengths)).tolist()
+                Tp, flag, y_host = int(host[0]), int(host[1]), host[2:]
+            else:
+                Tp, flag = (int(v) for v in stat.tolist())      # the one host sync (commons.py:123)
             if flag > 0:                            # flagged by the kernels, no extra sync
                 raise IndexError("index out of range in self (token id, x_lengths or sid outside the "
                                  "model's tables, or a duration outside the supported range: 2^20 frames a token, "
@@ -398,6 +407,11 @@ class SynthesizerTrn(nn.Module):
                     raise ValueError("trim=True materialises the waveform only: pass outputs=('o',) (+ attn / y_mask / z ...)")
                 if self.cfg.decoder == DEC_SB:
                     raise ValueError("trim=True is built for the multiband / multistream decoders")
+            if ragged:
+                if trim:
+                    raise ValueError("trim=True and ragged=True exclude each other")
+                if want & {"o_mb", "spec", "phase"}:
+                    raise ValueError("ragged=True materialises the waveform only: pass outputs=('o',) (+ attn / y_mask / z ...)")
             if decode and want & {"o", "o_mb", "spec", "phase"}:
                 if Td <= 0:
                     raise ValueError("max_len leaves no frames to decode")
@@ -412,9 +426,15 @@ class SynthesizerTrn(nn.Module):
             if trim:
                 _capi.check(h, L.mbv_set_option(h, b"trim", 1), "mbv_set_option")
             try:
-                _capi.check(h, L.mbv_synthesize(h, Tp, self._ptr(noise), float(noise_scale),
-                                                int(Td if max_len is not None else 0), C.byref(out), stream),
-                            "mbv_synthesize")
+                if ragged:
+                    _capi.check(h, L.mbv_synthesize_ragged(h, Tp, self._ptr(noise), float(noise_scale),
+                                                           int(Td if max_len is not None else 0), C.byref(out),
+                                                           (C.c_int64 * B)(*y_host), stream),
+                                "mbv_synthesize_ragged")
+                else:
+                    _capi.check(h, L.mbv_synthesize(h, Tp, self._ptr(noise), float(noise_scale),
+                                                    int(Td if max_len is not None else 0), C.byref(out), stream),
+                                "mbv_synthesize")
             finally:
                 if trim:
                     _capi.check(h, L.mbv_set_option(h, b"trim", 0), "mbv_set_option")
@@ -444,7 +464,7 @@ class SynthesizerTrn(nn.Module):
         return o, o_mb, spec, phase
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-              max_len=None, outputs=None, trim=False):
+              max_len=None, outputs=None, trim=False, ragged=False):
         """-> (o, o_mb, spec, phase, attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:737)
 
         `outputs` (extension, default None = the reference's full tuple): names of the tensors to
@@ -455,9 +475,16 @@ class SynthesizerTrn(nn.Module):
         `trim` (extension, default False; needs `outputs` without o_mb / spec / phase): opt-in trimmed decode for
         ragged batches — per utterance the decoder only computes what its valid 256 * y_lengths[b] samples depend
         on (frames below y_lengths[b] + 32).  Those samples are bitwise the default's; the padded region of `o`,
-        which the reference's unmasked decoder fills with defined values, comes back as zeros."""
+        which the reference's unmasked decoder fills with defined values, comes back as zeros.
+
+        `ragged` (extension, default False; same condition on `outputs`; excludes `trim`): opt-in row-exact ragged
+        decode — the valid 256 * y_lengths[b] samples of row b are bitwise `net.dec(z[b:b+1, :, :y_lengths[b]], g)`
+        alone, i.e. what a one-utterance-per-call service (tts_vits.py:122-139) emits, whatever else is in the
+        batch; the rest of the row is zeros.  The default (and `trim`) keep the reference's batched values, where
+        the last ~25 frames of a row depend on what the unmasked decoder computes behind its end.  The B lengths
+        are read back in the call's one host synchronisation."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged)
         return r[:8]
 
     def infer_z_only(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
@@ -468,11 +495,11 @@ class SynthesizerTrn(nn.Module):
         return r[4], r[5], r[6], r[7]
 
     def infer_with_lengths(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1,
-                           max_len=None, noise_scale_w=1., outputs=None, trim=False):
+                           max_len=None, noise_scale_w=1., outputs=None, trim=False, ragged=False):
         """`infer` plus the per-utterance frame counts y_lengths [B] (int64) — what a batched
         caller needs to trim the padded waveforms (valid samples = 256 * y_lengths)."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged)
         return r[:8], r[8]
 
     @torch.no_grad()
@@ -496,6 +523,57 @@ class SynthesizerTrn(nn.Module):
             _capi.check(h, _capi.lib().mbv_decode(h, self._ptr(z), self._ptr(g), B, Tp, C.byref(out),
                                                   self._stream()), "mbv_decode")
         return o, o_mb, spec, phase
+
+    @torch.no_grad()
+    def _decode_ragged(self, z, g, lengths):
+        """`net.dec(z, g, lengths=lens)[0]`: o [B, 1, 256 T'] whose row b is, over its first 256 * lens[b] samples,
+        bitwise `net.dec(z[b:b+1, :, :lens[b]], g[b:b+1])[0]` (default mode; with "splitk" within fp32 rounding)
+        and zero behind; z at and past a row's length is never read.  `lengths`: a sequence of ints or an integer
+        tensor on either device (a device tensor is read back: one synchronisation)."""
+        h = self._ensure_handle()
+        dev = self._device()
+        if z.dim() != 3 or z.shape[1] != self.cfg.inter_channels:
+            raise ValueError("z must be [B, %d, T']" % self.cfg.inter_channels)
+        z = z.to(device=dev, dtype=torch.float32).contiguous()
+        B, _, Tp = z.shape
+        lens = lengths.tolist() if torch.is_tensor(lengths) else list(lengths)
+        if len(lens) != B:
+            raise ValueError("lengths must hold one length per row of z")
+        lens = [int(v) for v in lens]
+        if g is not None:
+            if self.cfg.gin_channels == 0:
+                g = None
+            else:
+                g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
+        with torch.cuda.device(dev):
+            o = torch.empty(B, 1, self.cfg.samples_per_frame * Tp, device=dev, dtype=torch.float32)
+            _capi.check(h, _capi.lib().mbv_decode_ragged(h, self._ptr(z), self._ptr(g), B, Tp, (C.c_int64 * B)(*lens),
+                                                         self._ptr(o), self._stream()), "mbv_decode_ragged")
+        return o
+
+    def ragged_classes(self, t_max, splitk=False):
+        """The first z-length of every class of the row-exact ragged decode for lengths 1 .. t_max
+        (`mbv_ragged_classes`, host only: no GPU needed): rows of one class share their decoder launches."""
+        cfg = self._config_struct()
+        n = _capi.lib().mbv_ragged_classes(C.byref(cfg), int(bool(splitk)), int(t_max), None, 0)
+        if n < 1:
+            raise ValueError("mbv_ragged_classes refused t_max=%r" % (t_max,))
+        buf = (C.c_int32 * n)()
+        _capi.lib().mbv_ragged_classes(C.byref(cfg), int(bool(splitk)), int(t_max), buf, n)
+        return list(buf)
+
+    def ragged_plan(self, lengths, t_frames=None, splitk=False):
+        """(runs, run_of_row): the decoder runs a ragged call makes for rows of these z-lengths (`mbv_ragged_plan`,
+        host only) — one per non-empty class, cut further only at 2 GiB tensors; run_of_row[b] = -1 for an empty row."""
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        B = len(lens)
+        t_frames = max(max(lens), 1) if t_frames is None else int(t_frames)
+        cfg = self._config_struct()
+        rows = (C.c_int32 * B)()
+        n = _capi.lib().mbv_ragged_plan(C.byref(cfg), int(bool(splitk)), B, t_frames, (C.c_int64 * B)(*lens), rows)
+        if n < 0:
+            raise ValueError("mbv_ragged_plan refused the lengths (outside [0, %d]?)" % t_frames)
+        return n, list(rows)
 
     @torch.no_grad()
     def _decode_into(self, z, g, outs):

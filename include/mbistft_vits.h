@@ -288,6 +288,43 @@ int mbv_voice_conversion(mbv_model *m, const float *y, const int64_t *y_lengths,
                          const int64_t *sid_src, const int64_t *sid_tgt, int B, int T,
                          const float *noise, const mbv_outputs *outs, int32_t *status, void *stream);
 
+/* ---- forced alignment ---------------------------------------------------------------
+ * The alignment of SynthesizerTrn.forward (models.py:659-680, :690-691) for utterances whose audio and text both
+ * exist: enc_p, enc_q, the forward flow, the negative cross-entropy matrix, Monotonic Alignment Search
+ * (monotonic_align/core.pyx) and the expanded prior.  The text encoder runs exact, as in mbv_encode.  No host
+ * synchronisation.  The call uses the scratch of mbv_encode: an mbv_synthesize needs a fresh mbv_encode after it.
+ *   ids, lengths   int64 [B, T_text] / [B]                  y, y_lengths  fp32 [B, spec_channels, T_spec] / int64 [B]
+ *   sid            int64 [B]; NULL iff n_speakers == 0
+ *   noise          fp32 [B, inter, T_spec] draws of PosteriorEncoder (models.py:245); z = m_q + noise * noise_scale *
+ *                  exp(logs_q); NULL or noise_scale == 0: z = m_q
+ *   outs           every member optional (NULL: not wanted, its stores never happen)
+ *   status         int32 [B] device, optional: bit 0 a token id / length / sid outside its table or tensor,
+ *                  bit 1 more tokens than frames (t_x > t_y: no monotone path), bit 2 an empty text or recording.
+ *                  A flagged row has w = 0; nothing faults. */
+typedef struct mbv_align_outputs {
+  int32_t *w;        /* [B, T_text]            frames per token (attn.sum(2), models.py:680); 0 behind the text */
+  float *attn;       /* [B, 1, T_spec, T_text] the path */
+  float *x_mask;     /* [B, 1, T_text] */
+  float *y_mask;     /* [B, 1, T_spec] */
+  float *z;          /* [B, inter, T_spec]     posterior sample */
+  float *z_p;        /* [B, inter, T_spec]     flow(z) */
+  float *m_p;        /* [B, inter, T_spec]     text statistics expanded by the path (models.py:690-691) */
+  float *logs_p;     /* [B, inter, T_spec] */
+  float *neg_cent;   /* [B, T_spec, T_text]    cells [y < y_lengths[b], x < lengths[b]) only; the rest is not written */
+} mbv_align_outputs;
+int mbv_align(mbv_model *m, const int64_t *ids, const int64_t *lengths, const float *y, const int64_t *y_lengths,
+              const int64_t *sid, int B, int T_text, int T_spec, const float *noise, float noise_scale,
+              const mbv_align_outputs *outs, int32_t *status, void *stream);
+
+/* Synthesis with given durations: valid after mbv_encode, before mbv_synthesize.  Replaces the predicted durations
+ * (w_ceil, their cumulated sums, the frame counts) by those of w, masked by the text lengths, with
+ * y_lengths = max(sum w, 1) (models.py:717-719); mbv_synthesize then proceeds unchanged.  Without the call nothing
+ * changes.
+ *   w              [B, T] non-negative integers: dtype 0 int32, 1 int64, 2 fp32
+ *   y_lengths_out  int64 [B] device; -1 under the rules of mbv_encode (whose flags are kept), and for a negative or
+ *                  non-integer duration */
+int mbv_set_durations(mbv_model *m, const void *w, int dtype, int B, int T, int64_t *y_lengths_out, void *stream);
+
 /* ---- spectrogram -> waveform ("istft_finalize") -------------------------------
  * The last step of the reference's chunked decoding (inferz_test.ipynb cells 6-7,
  * `istft_finalize`; intent of synthesis_module.py:306-353): chunks of z go through
@@ -559,6 +596,16 @@ int mbv_op_sdp_logw(mbv_model *m, const float *z, const float *mean, const float
                     float *logw, int B, int T, void *stream);
 int mbv_op_sdp_noise(mbv_model *m, const float *noise, float scale, float *z, int64_t n, void *stream);
 int mbv_op_chan_add(mbv_model *m, float *x, const float *v, int B, int C, int T, void *stream);
+/* the two kernels of mbv_align by themselves (align.hip).
+ *   neg_cent: z_p [B, I, T_t], m_p / logs_p [B, I, T_s] (dense), t_y32 / t_x32 int32 [B] -> value [B, T_t, T_s]
+ *             (cells outside [t_y, t_x) are not written; lengths are clamped to the tensors)
+ *   max_path: value is left untouched and not read outside [t_y, t_x); w_out int32 [B, T_s]; path_out int32
+ *             [B, T_t, T_s] or NULL; status int32 [B] or NULL: 0 ok, 1 t_x > t_y, 2 t_x < 1 or t_y < 1,
+ *             3 a length outside the tensors (such rows: w = 0, path = 0).  T_s <= 1024. */
+int mbv_op_neg_cent(mbv_model *m, const float *z_p, const float *m_p, const float *logs_p, const int32_t *t_y32,
+                    const int32_t *t_x32, float *value, int B, int I, int T_t, int T_s, void *stream);
+int mbv_op_max_path(mbv_model *m, const float *value, const int32_t *t_y32, const int32_t *t_x32, int32_t *w_out,
+                    int32_t *path_out, int32_t *status, int B, int T_t, int T_s, void *stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ SYMBOLS = [
     "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
     "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
+    "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
 ]
 
 
@@ -48,6 +49,12 @@ class MbvConfig(C.Structure):
 class MbvOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("o", "o_mb", "spec", "phase", "attn", "y_mask", "z", "z_p", "m_p", "logs_p")]
+
+
+class MbvAlignOutputs(C.Structure):
+    """mbv_align_outputs of include/mbistft_vits.h: NULL = not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in
+                ("w", "attn", "x_mask", "y_mask", "z", "z_p", "m_p", "logs_p", "neg_cent")]
 
 
 class MbvConvDesc(C.Structure):
@@ -161,6 +168,10 @@ def lib():
     L.mbv_op_sdp_logw.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.mbv_op_sdp_noise.argtypes = [vp, vp, f32, vp, C.c_int64, vp]
     L.mbv_op_chan_add.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_align.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, C.POINTER(MbvAlignOutputs), vp, vp]
+    L.mbv_set_durations.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries may be absent there, and calling one then raises AttributeError.  Everything else, and the
     # in-tree library always, must match the header.

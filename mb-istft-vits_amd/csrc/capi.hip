@@ -115,6 +115,7 @@ struct mbv_model {
   bool encoded = false, has_g = false;
   float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
   int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr;
+  int* bad32 = nullptr;         // per-utterance flags of the last encode (invalid id / length / sid)
   std::map<std::string, StageRef> stages;
 
   static constexpr int kEvRing = 8;
@@ -1821,61 +1822,25 @@ void run_dds(mbv_model* m, const mbv_model::Dds& d, float* x, float* t1, float* 
                    i == 2 ? m->lens32 : nullptr, s);
   }
 }
-}  // namespace
-
-int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
-               int T, float length_scale, const float* noise_w, float noise_scale_w,
-               int64_t* y_lengths_out, void* stream) {
-  if (!m) return 1;
-  if (!m->finalized) return m->fail("weights not finalized (call mbv_finalize_weights)");
-  if (!ids || !lengths || B <= 0 || T <= 0) return m->fail("mbv_encode: bad arguments");
+struct ExactScope {
+  mbv_model* m; int saved;
+  explicit ExactScope(mbv_model* mm) : m(mm), saved(mm->conv_bf16) { m->conv_bf16 = 0; }
+  ~ExactScope() { m->conv_bf16 = saved; }
+};
+// Phase A of mbv_encode: embedding, the attention layers and enc_p.proj (models.py:183-195) -> x [B, H, T] and
+// m->stats = [m_text | logs_text]; shared with mbv_align.  Runs in the caller's ExactScope.
+struct TextEncBufs { float *x, *x1, *qkv, *att, *y, *ffn; };
+// (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
+// size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
+bool text_fuse_ln(const mbv_model* m, int B, int T) { return T <= 256 && !(m->splitk && (long)B * ((T + 15) / 16) < 128); }
+void run_text_encoder(mbv_model* m, const int64_t* ids, const int64_t* lengths, const TextEncBufs& e, int* bad, int B,
+                      int T, hipStream_t s) {
   const mbv_config& c = m->cfg;
-  if (c.n_speakers > 0 && !sid) return m->fail("sid is required when n_speakers > 0 (models.py:704-705)");
-  if (c.n_speakers > 0 && !m->emb_g.present) return m->fail("n_speakers == 1: the reference has no emb_g either");
-  DEVICE_GUARD(m);
-  // The text encoder and the duration predictor ALWAYS run exact: the durations (ceil of an exponential) must
-  // not depend on the opt-in split-bf16 mode, which is for the waveform path only.  (Long texts, T > 256,
-  // use the conv kernels that have the mode; short ones the narrow kernel, which does not.)
-  struct ExactScope {
-    mbv_model* m; int saved;
-    explicit ExactScope(mbv_model* mm) : m(mm), saved(mm->conv_bf16) { m->conv_bf16 = 0; }
-    ~ExactScope() { m->conv_bf16 = saved; }
-  } exact_scope(m);
-  hipStream_t s = (hipStream_t)stream;
-  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
-  const size_t BT = (size_t)B * T;
-  size_t need = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2 * kDpFilter + 4 + 5 * H + 32 + 2) + (size_t)B * (gin + H + 12)) * 4 + 96 * 256;
-  if (ensure(m, &m->scrA, &m->scrA_bytes, need)) return 1;
-  Bump sc{m->scrA, m->scrA_bytes};
-  float* x = sc.take<float>(BT * H);
-  float* x1 = sc.take<float>(BT * H);
-  float* qkv = sc.take<float>(BT * 3 * H);
-  float* att = sc.take<float>(BT * H);
-  float* y = sc.take<float>(BT * H);
-  float* ffn = sc.take<float>(BT * Fc);
-  m->stats = sc.take<float>(BT * 2 * I);
-  float* h1 = sc.take<float>(BT * kDpFilter);
-  float* h2 = sc.take<float>(BT * kDpFilter);
-  m->logw = sc.take<float>(BT);
-  m->w_ceil = sc.take<float>(BT);
-  m->cum = sc.take<int>(BT);
-  m->lens32 = sc.take<int>(B);
-  m->ylen32 = sc.take<int>(B);
-  int* bad = sc.take<int>(B);
-  m->gvec = sc.take<float>((size_t)B * (gin ? gin : 1));
-  float* dpc = sc.take<float>((size_t)B * H);
-  m->stages.clear();
-
-  ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
-  m->ev = m->evr[m->ticket % mbv_model::kEvRing];
-  m->evr_a[m->ticket % mbv_model::kEvRing] = false;
-  m->evr_b[m->ticket % mbv_model::kEvRing] = false;
-  HIPCHK(m, hipEventRecord(m->ev[0], s));
+  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels;
+  float *x = e.x, *x1 = e.x1, *qkv = e.qkv, *att = e.att, *y = e.y, *ffn = e.ffn;
   launch_embed(ids, lengths, m->W(m->emb.off), x, m->lens32, bad, B, T, H, c.n_vocab, s);
   const int64_t bsH = (int64_t)H * T;
-  // (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
-  // size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
-  const bool fuse_ln = T <= 256 && !(m->splitk && (long)B * ((T + 15) / 16) < 128);
+  const bool fuse_ln = text_fuse_ln(m, B, T);
   for (int i = 0; i < c.n_layers; ++i) {
     const auto& L = m->enc[i];
     launch_conv1d(conv_args(m, L.qkv, x, bsH, T, qkv, 3 * bsH, T, B), s);
@@ -1916,12 +1881,62 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
       }
     }
   }
-  m->x_enc = x;
   {
     ConvArgs a = conv_args(m, m->enc_proj, x, bsH, T, m->stats, (int64_t)2 * I * T, T, B);
     a.out_lens = m->lens32;
     launch_conv1d(a, s);
   }
+}
+}  // namespace
+
+int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
+               int T, float length_scale, const float* noise_w, float noise_scale_w,
+               int64_t* y_lengths_out, void* stream) {
+  if (!m) return 1;
+  if (!m->finalized) return m->fail("weights not finalized (call mbv_finalize_weights)");
+  if (!ids || !lengths || B <= 0 || T <= 0) return m->fail("mbv_encode: bad arguments");
+  const mbv_config& c = m->cfg;
+  if (c.n_speakers > 0 && !sid) return m->fail("sid is required when n_speakers > 0 (models.py:704-705)");
+  if (c.n_speakers > 0 && !m->emb_g.present) return m->fail("n_speakers == 1: the reference has no emb_g either");
+  DEVICE_GUARD(m);
+  // The text encoder and the duration predictor ALWAYS run exact: the durations (ceil of an exponential) must
+  // not depend on the opt-in split-bf16 mode, which is for the waveform path only.  (Long texts, T > 256,
+  // use the conv kernels that have the mode; short ones the narrow kernel, which does not.)
+  ExactScope exact_scope(m);
+  hipStream_t s = (hipStream_t)stream;
+  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
+  const size_t BT = (size_t)B * T;
+  size_t need = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2 * kDpFilter + 4 + 5 * H + 32 + 2) + (size_t)B * (gin + H + 12)) * 4 + 96 * 256;
+  if (ensure(m, &m->scrA, &m->scrA_bytes, need)) return 1;
+  Bump sc{m->scrA, m->scrA_bytes};
+  float* x = sc.take<float>(BT * H);
+  float* x1 = sc.take<float>(BT * H);
+  float* qkv = sc.take<float>(BT * 3 * H);
+  float* att = sc.take<float>(BT * H);
+  float* y = sc.take<float>(BT * H);
+  float* ffn = sc.take<float>(BT * Fc);
+  m->stats = sc.take<float>(BT * 2 * I);
+  float* h1 = sc.take<float>(BT * kDpFilter);
+  float* h2 = sc.take<float>(BT * kDpFilter);
+  m->logw = sc.take<float>(BT);
+  m->w_ceil = sc.take<float>(BT);
+  m->cum = sc.take<int>(BT);
+  m->lens32 = sc.take<int>(B);
+  m->ylen32 = sc.take<int>(B);
+  int* bad = m->bad32 = sc.take<int>(B);
+  m->gvec = sc.take<float>((size_t)B * (gin ? gin : 1));
+  float* dpc = sc.take<float>((size_t)B * H);
+  m->stages.clear();
+
+  ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
+  m->ev = m->evr[m->ticket % mbv_model::kEvRing];
+  m->evr_a[m->ticket % mbv_model::kEvRing] = false;
+  m->evr_b[m->ticket % mbv_model::kEvRing] = false;
+  HIPCHK(m, hipEventRecord(m->ev[0], s));
+  run_text_encoder(m, ids, lengths, TextEncBufs{x, x1, qkv, att, y, ffn}, bad, B, T, s);
+  const int64_t bsH = (int64_t)H * T;
+  const bool fuse_ln = text_fuse_ln(m, B, T);
+  m->x_enc = x;
   HIPCHK(m, hipEventRecord(m->ev[1], s));
 
   // ---- speaker embedding + duration predictor (models.py:704-713)
@@ -2280,6 +2295,49 @@ int mbv_istft_pqmf(mbv_model* m, const float* x_post, int B, int t_frames, const
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+// scratch of the posterior side (mbv_voice_conversion, mbv_align): ypad [B, cin_pad, T], hbuf / acts / skip [B, H, T],
+// stats [B, 2I, T], gc [B, 2 H kEncQLayers], ustart wn_units_ints(B, T)
+struct PosteriorBufs { float *ypad, *hbuf, *acts, *skip, *stats, *gc; int* ustart; };
+// enc_q (models.py:239-246): pre * mask -> WN(g) -> proj * mask -> z = (m_q + noise * noise_scale * exp(logs_q)) * mask.
+// g == nullptr: the unconditioned WN of a single-speaker model.
+int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, const float* noise, float noise_scale,
+              const PosteriorBufs& p, float* z, int B, int T, hipStream_t s) {
+  const mbv_config& c = m->cfg;
+  const int H = c.hidden_channels, I = c.inter_channels, SC = c.spec_channels;
+  const auto& Q = m->encq;
+  const size_t BT = (size_t)B * T;
+  // the 1x1 `pre` conv reads channel groups of 32: zero-pad spec_channels (513) to a multiple of 32
+  launch_fill(p.ypad, 0.f, (int64_t)BT * Q.cin_pad, s);
+  HIPCHK(m, hipMemcpy2DAsync(p.ypad, (size_t)Q.cin_pad * T * 4, y, (size_t)SC * T * 4, (size_t)SC * T * 4, B,
+                             hipMemcpyDeviceToDevice, s));
+  const int64_t bsH = (int64_t)H * T;
+  {
+    ConvArgs a = conv_args(m, Q.pre, p.ypad, (int64_t)Q.cin_pad * T, T, p.hbuf, bsH, T, B);
+    a.out_lens = lens;
+    launch_conv1d(a, s);
+  }
+  run_wn(m, Q.in, Q.rs, Q.in16, Q.rsp, mbv_model::kEncQLayers, Q.cw, Q.cb, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s);
+  {
+    ConvArgs a = conv_args(m, Q.proj, p.skip, bsH, T, p.stats, (int64_t)2 * I * T, T, B);
+    a.in_lens = lens; a.out_lens = lens;
+    launch_conv1d(a, s);
+  }
+  launch_posterior_sample(p.stats, noise, lens, z, B, I, T, s, noise_scale);
+  return 0;
+}
+// the forward flow (models.py:207-211), in place on z
+void run_flow_forward(mbv_model* m, float* z, const float* g, const PosteriorBufs& p, const int* lens, int B, int T,
+                      hipStream_t s) {
+  for (int f = 0; f < kNFlows; ++f)
+    run_coupling(m, f, false, z, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s);
+}
+}  // namespace
+
+extern "C" {
+
 int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths, const int64_t* sid_src,
                          const int64_t* sid_tgt, int B, int T, const float* noise, const mbv_outputs* outs,
                          int32_t* status, void* stream) {
@@ -2292,7 +2350,7 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
     return m->fail("mbv_voice_conversion: bad arguments");
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
-  const int H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels, SC = c.spec_channels;
+  const int H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
   const auto& Q = m->encq;
   const size_t BT = (size_t)B * T;
   size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 4 * I) + (size_t)B * (2 * gin + 2 * H * mbv_model::kEncQLayers + 18)) * 4 + wn_units_ints(B, T) * 4 +
@@ -2318,32 +2376,118 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, bad, s);
   launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, bad, s);
   if (status) HIPCHK(m, hipMemcpyAsync(status, bad, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
-  // the 1x1 `pre` conv reads channel groups of 32: zero-pad spec_channels (513) to a multiple of 32
-  launch_fill(ypad, 0.f, (int64_t)BT * Q.cin_pad, s);
-  HIPCHK(m, hipMemcpy2DAsync(ypad, (size_t)Q.cin_pad * T * 4, y, (size_t)SC * T * 4, (size_t)SC * T * 4, B,
-                             hipMemcpyDeviceToDevice, s));
-  const int64_t bsH = (int64_t)H * T;
-  {   // enc_q (models.py:239-246): pre * mask -> WN(g_src) -> proj * mask -> sample
-    ConvArgs a = conv_args(m, Q.pre, ypad, (int64_t)Q.cin_pad * T, T, hbuf, bsH, T, B);
-    a.out_lens = lens;
-    launch_conv1d(a, s);
-  }
-  run_wn(m, Q.in, Q.rs, Q.in16, Q.rsp, mbv_model::kEncQLayers, Q.cw, Q.cb, g_src, hbuf, acts, skip, gc, ustart, lens, B, T, s);
-  {
-    ConvArgs a = conv_args(m, Q.proj, skip, bsH, T, stats, (int64_t)2 * I * T, T, B);
-    a.in_lens = lens; a.out_lens = lens;
-    launch_conv1d(a, s);
-  }
-  launch_posterior_sample(stats, noise, lens, zbuf, B, I, T, s);
+  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
+  if (run_enc_q(m, y, lens, g_src, noise, 1.f, pb, zbuf, B, T, s)) return 1;
   // forward flow with the source speaker (models.py:795), then reverse with the target (:796)
   HIPCHK(m, hipMemcpyAsync(zhat, zbuf, BT * I * 4, hipMemcpyDeviceToDevice, s));
-  for (int f = 0; f < kNFlows; ++f)
-    run_coupling(m, f, false, zhat, g_src, hbuf, acts, skip, gc, ustart, lens, B, T, s);
+  run_flow_forward(m, zhat, g_src, pb, lens, B, T, s);
   if (outs->z_p) HIPCHK(m, hipMemcpyAsync(outs->z_p, zhat, BT * I * 4, hipMemcpyDeviceToDevice, s));
   for (int f = kNFlows - 1; f >= 0; --f)
     run_coupling(m, f, true, zhat, g_tgt, hbuf, acts, skip, gc, ustart, lens, B, T, s);
   if (outs->y_mask) launch_sequence_mask(lens, outs->y_mask, B, T, s);
   if (run_decoder(m, zhat, T, lens, g_tgt, B, T, outs, s, sc)) return 1;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const float* y, const int64_t* y_lengths,
+              const int64_t* sid, int B, int T_text, int T_spec, const float* noise, float noise_scale,
+              const mbv_align_outputs* outs, int32_t* status, void* stream) {
+  if (!m) return 1;
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!ids || !lengths || !y || !y_lengths || !outs || B <= 0 || T_text <= 0 || T_spec <= 0)
+    return m->fail("mbv_align: bad arguments");
+  const mbv_config& c = m->cfg;
+  if ((c.n_speakers > 0) != (sid != nullptr))
+    return m->fail("mbv_align: sid is required when n_speakers > 0 and must be NULL otherwise (models.py:661-664)");
+  if (c.n_speakers > 0 && !m->emb_g.present) return m->fail("n_speakers == 1: the reference has no emb_g either");
+  if (B > 65535 || T_spec > 65535) return m->fail("mbv_align: B and T_spec must be <= 65535");
+  if (!max_path_supported(T_text)) return m->fail("mbv_align: T_text must be <= %d", kMaxPathMaxTs);
+  DEVICE_GUARD(m);
+  ExactScope exact_scope(m);                 // the text statistics as mbv_encode computes them; the path must not depend on the mode
+  hipStream_t s = (hipStream_t)stream;
+  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
+  const int T = T_text, Tp = T_spec;
+  const auto& Q = m->encq;
+  const size_t BT = (size_t)B * T, BTp = (size_t)B * Tp;
+  // ---- text side, in the scratch of mbv_encode (whose state it therefore ends)
+  m->encoded = false;
+  m->stages.clear();
+  size_t needA = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2) + (size_t)B * (gin + 12)) * 4 + 32 * 256;
+  if (ensure(m, &m->scrA, &m->scrA_bytes, needA)) return 1;
+  Bump sa{m->scrA, m->scrA_bytes};
+  TextEncBufs te{};
+  te.x = sa.take<float>(BT * H);
+  te.x1 = sa.take<float>(BT * H);
+  te.qkv = sa.take<float>(BT * 3 * H);
+  te.att = sa.take<float>(BT * H);
+  te.y = sa.take<float>(BT * H);
+  te.ffn = sa.take<float>(BT * Fc);
+  m->stats = sa.take<float>(BT * 2 * I);
+  m->cum = sa.take<int>(BT);
+  int* w32 = sa.take<int>(BT);
+  m->lens32 = sa.take<int>(B);
+  m->ylen32 = sa.take<int>(B);
+  int* bad_x = m->bad32 = sa.take<int>(B);
+  int* bad_y = sa.take<int>(B);
+  int* ylens = sa.take<int>(B);
+  int* mas = sa.take<int>(B);
+  m->gvec = sa.take<float>((size_t)B * (gin ? gin : 1));
+  // ---- posterior side
+  const size_t bits_bytes = max_path_scratch_bytes(B, Tp, T);
+  size_t needB = (BTp * ((size_t)Q.cin_pad + 3 * H + 4 * I + (size_t)T) + (size_t)B * (2 * H * mbv_model::kEncQLayers + 8)) * 4 +
+                 wn_units_ints(B, Tp) * 4 + bits_bytes + 64 * 256;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, needB)) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  PosteriorBufs pb{};
+  pb.ypad = sc.take<float>(BTp * Q.cin_pad);
+  pb.hbuf = sc.take<float>(BTp * H);
+  pb.acts = sc.take<float>(BTp * H);
+  pb.skip = sc.take<float>(BTp * H);
+  pb.stats = sc.take<float>(BTp * 2 * I);
+  pb.gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
+  pb.ustart = sc.take<int>(wn_units_ints(B, Tp));
+  float* zbuf = outs->z ? outs->z : sc.take<float>(BTp * I);
+  float* zp = outs->z_p ? outs->z_p : sc.take<float>(BTp * I);
+  float* value = outs->neg_cent ? outs->neg_cent : sc.take<float>(BTp * T);
+  void* bits = bits_bytes ? (void*)sc.take<char>(bits_bytes) : nullptr;
+  int* w_out = outs->w ? outs->w : w32;
+
+  run_text_encoder(m, ids, lengths, te, bad_x, B, T, s);
+  const float* g = nullptr;
+  if (c.n_speakers > 0) {
+    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad_x, s);
+    g = m->gvec;
+  }
+  launch_lens_to_i32(y_lengths, ylens, B, Tp, bad_y, s);
+  if (run_enc_q(m, y, ylens, g, noise_scale != 0.f ? noise : nullptr, noise_scale, pb, zbuf, B, Tp, s)) return 1;
+  HIPCHK(m, hipMemcpyAsync(zp, zbuf, BTp * I * 4, hipMemcpyDeviceToDevice, s));
+  run_flow_forward(m, zp, g, pb, ylens, B, Tp, s);
+  // ---- neg_cent, the search, the durations (models.py:668-680)
+  launch_neg_cent(zp, m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, ylens, m->lens32, value, B, I, Tp, T, s);
+  launch_max_path(value, ylens, m->lens32, w_out, nullptr, mas, bits, B, Tp, T, s);
+  launch_align_status(bad_x, bad_y, mas, status, nullptr, nullptr, B, T, s);
+  // ---- the path as length regulation takes it, and the expanded prior (:690-691)
+  if (outs->attn || outs->m_p || outs->logs_p) {
+    launch_set_durations(w_out, 0, m->lens32, nullptr, m->cum, m->ylen32, nullptr, nullptr, B, T, s);
+    // (a refused row has w = 0: y_len 1 and no token for its frame; pb.stats is free again and takes the copy `z`)
+    launch_expand(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, nullptr, 0.f, outs->m_p,
+                  outs->logs_p, nullptr, pb.stats, outs->attn, nullptr, B, I, T, Tp, s);
+  }
+  if (outs->x_mask) launch_sequence_mask(m->lens32, outs->x_mask, B, T, s);
+  if (outs->y_mask) launch_sequence_mask(ylens, outs->y_mask, B, Tp, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_set_durations(mbv_model* m, const void* w, int dtype, int B, int T, int64_t* y_lengths_out, void* stream) {
+  if (!m) return 1;
+  if (!m->encoded) return m->fail("mbv_set_durations without a preceding mbv_encode");
+  if (!w || !y_lengths_out) return m->fail("mbv_set_durations: NULL argument");
+  if (dtype < 0 || dtype > 2) return m->fail("mbv_set_durations: dtype must be 0 (int32), 1 (int64) or 2 (fp32)");
+  if (B != m->B || T != m->T) return m->fail("mbv_set_durations: w must be [%d, %d] as the encoded batch, got [%d, %d]", m->B, m->T, B, T);
+  DEVICE_GUARD(m);
+  launch_set_durations(w, dtype, m->lens32, m->w_ceil, m->cum, m->ylen32, y_lengths_out, m->bad32, B, T, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -2805,6 +2949,30 @@ int mbv_op_chan_add(mbv_model* m, float* x, const float* v, int B, int C, int T,
   OP_REFUSE(B <= 0 || C <= 0 || T <= 0 || B > kGridYZ || C > kGridYZ, "B, C in [1, 65535] and T > 0 required");
   OP_BEGIN();
   launch_chan_add(x, v, B, C, T, s);
+  OP_END();
+}
+
+int mbv_op_neg_cent(mbv_model* m, const float* z_p, const float* m_p, const float* logs_p, const int32_t* t_y32,
+                    const int32_t* t_x32, float* value, int B, int I, int T_t, int T_s, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!z_p || !m_p || !logs_p || !t_y32 || !t_x32 || !value, "NULL argument");
+  OP_REFUSE(B <= 0 || I <= 0 || T_t <= 0 || T_s <= 0, "B, I, T_t and T_s must be > 0");
+  OP_REFUSE(B > kGridYZ || (T_t + 63) / 64 > kGridYZ, "B <= 65535 and T_t <= 64 * 65535 required");
+  OP_BEGIN();
+  launch_neg_cent(z_p, m_p, logs_p, (int64_t)I * T_s, t_y32, t_x32, value, B, I, T_t, T_s, s);
+  OP_END();
+}
+
+int mbv_op_max_path(mbv_model* m, const float* value, const int32_t* t_y32, const int32_t* t_x32, int32_t* w_out,
+                    int32_t* path_out, int32_t* status, int B, int T_t, int T_s, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!value || !t_y32 || !t_x32 || !w_out, "NULL argument");
+  OP_REFUSE(B <= 0 || T_t <= 0 || T_s <= 0, "B, T_t and T_s must be > 0");
+  OP_REFUSE(!max_path_supported(T_s), "T_s must be <= 1024");
+  OP_BEGIN();
+  const size_t bits_bytes = max_path_scratch_bytes(B, T_t, T_s);
+  if (bits_bytes && ensure(m, &m->scrB, &m->scrB_bytes, bits_bytes)) return 1;
+  launch_max_path(value, t_y32, t_x32, w_out, path_out, status, bits_bytes ? m->scrB : nullptr, B, T_t, T_s, s);
   OP_END();
 }
 #undef OP_REFUSE

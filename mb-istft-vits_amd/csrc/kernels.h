@@ -330,9 +330,36 @@ void launch_spectrogram(const void* x, int dtype, const int64_t* valid, int B, i
                         const float* tw, const float* win, float* spec, int64_t F, int64_t* spec_lengths,
                         hipStream_t s);
 
-// z = (m + noise * exp(logs)) * mask   (PosteriorEncoder, models.py:245); stats = [B, 2I, T]
+// ---------------------------------------------------------------- forced alignment (align.hip)
+// value[b, y, x] = neg_cent of models.py:670-675 for y < t_ys[b], x < t_xs[b] (other cells are not written):
+// z_p [B, I, Tt]; m_p / logs_p [B, I, Ts] views with batch stride p_bstride (halves of the enc_p.proj output);
+// value [B, Tt, Ts], Ts fastest.  Lengths are clamped to the tensors.
+void launch_neg_cent(const float* z_p, const float* m_p, const float* logs_p, int64_t p_bstride, const int* t_ys,
+                     const int* t_xs, float* value, int B, int I, int Tt, int Ts, hipStream_t s);
+// maximum_path_each of monotonic_align/core.pyx on value [B, Tt, Ts] (left untouched; cells outside
+// [t_ys[b], t_xs[b]) are not read): w [B, Ts] int32 frames per token (0 for x >= t_x), path [B, Tt, Ts] int32 or
+// null, status [B] or null (0 ok, 1 t_x > t_y, 2 an empty side, 3 a length outside the tensors; such rows get
+// w = 0, path = 0).  The decision bits of an utterance live in LDS when max_path_lds_bytes(Tt, Ts) != 0, else in
+// bits_scratch (max_path_scratch_bytes(B, Tt, Ts) bytes).
+constexpr int kMaxPathMaxTs = 1024;            // columns (tokens) the search kernel is built for
+constexpr size_t kMaxPathLdsBytes = 64 * 1024;
+bool max_path_supported(int Ts);
+size_t max_path_lds_bytes(int Tt, int Ts);
+size_t max_path_scratch_bytes(int B, int Tt, int Ts);
+void launch_max_path(const float* value, const int* t_ys, const int* t_xs, int* w, int* path, int* status,
+                     void* bits_scratch, int B, int Tt, int Ts, hipStream_t s);
+// given non-negative integer durations w [B, T] (dtype 0 int32, 1 int64, 2 float32), masked by lens:
+// w_ceil (or null), cum, ylen32 = max(sum, 1), ylen64 (or null; -1 under the rules of launch_durations, and for a
+// negative or non-integer entry)
+void launch_set_durations(const void* w, int dtype, const int* lens, float* w_ceil, int* cum, int* ylen32,
+                          int64_t* ylen64, const int* bad, int B, int T, hipStream_t s);
+// status[b] = bit 0: bad_x | bad_y | mas == 3, bit 1: mas == 1, bit 2: mas == 2 ; w_f = float(w_i) (either may be null)
+void launch_align_status(const int* bad_x, const int* bad_y, const int* mas, int* status, float* w_f, const int* w_i,
+                         int B, int T, hipStream_t s);
+
+// z = (m + noise * noise_scale * exp(logs)) * mask   (PosteriorEncoder, models.py:245); stats = [B, 2I, T]
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,
-                             int I, int T, hipStream_t s);
+                             int I, int T, hipStream_t s, float noise_scale = 1.f);
 void launch_sequence_mask(const int* lens, float* mask, int B, int T, hipStream_t s);   // commons.py:121
 void launch_lens_to_i32(const int64_t* lens, int* out, int B, int T, int* bad, hipStream_t s);
 

@@ -403,21 +403,21 @@ void launch_pcm16(const float* x, const int64_t* lens, int B, int64_t stride, in
 }
 
 __global__ void posterior_sample_kernel(const float* stats, const float* noise, const int* lens,
-                                        float* z, int I, int T) {
+                                        float* z, int I, int T, float noise_scale) {
   const int b = blockIdx.z, c = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   const float m = stats[((int64_t)b * 2 * I + c) * T + t];
   const float lg = stats[((int64_t)b * 2 * I + I + c) * T + t];
   const int64_t o = ((int64_t)b * I + c) * T + t;
-  const float v = noise ? m + noise[o] * expf(lg) : m;
+  const float v = noise ? m + (noise[o] * noise_scale) * expf(lg) : m;   // (noise_scale 1: exact)
   z[o] = t < lens[b] ? v : 0.f;
 }
 
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,
-                             int I, int T, hipStream_t s) {
+                             int I, int T, hipStream_t s, float noise_scale) {
   dim3 grid((T + 127) / 128, I, B);
-  hipLaunchKernelGGL(posterior_sample_kernel, grid, dim3(128), 0, s, stats, noise, lens, z, I, T);
+  hipLaunchKernelGGL(posterior_sample_kernel, grid, dim3(128), 0, s, stats, noise, lens, z, I, T, noise_scale);
 }
 
 __global__ void sequence_mask_kernel(const int* lens, float* mask, int T) {

@@ -306,6 +306,27 @@ class SynthesizerTrn(nn.Module):
             sid = None
         return x, x_lengths, sid
 
+    def _check_durations(self, durations, B, T, length_scale):
+        """Given durations -> (contiguous device tensor [B, T], dtype code of mbv_set_durations)."""
+        if float(length_scale) != 1.0:
+            raise ValueError("durations= are used as given: length_scale must be 1 (scale the durations instead)")
+        if not torch.is_tensor(durations):
+            raise ValueError("durations must be a tensor [B, T_text] or [B, 1, T_text]")
+        if durations.dim() == 3 and durations.shape[1] == 1:
+            durations = durations[:, 0]
+        if tuple(durations.shape) != (B, T):
+            raise ValueError("durations must be [B, T_text] or [B, 1, T_text] = [%d, %d], got %s"
+                             % (B, T, tuple(durations.shape)))
+        if durations.dtype == torch.int32:
+            code = 0
+        elif durations.dtype == torch.int64:
+            code = 1
+        elif durations.dtype.is_floating_point:
+            durations, code = durations.to(torch.float32), 2
+        else:
+            durations, code = durations.to(torch.int64), 1
+        return durations.to(device=self._device()).contiguous(), code
+
     def _stage_times(self, ticket):
         if self._handle is None or ticket[0] is not self._handle:
             return [float("nan")] * 5               # the handle was re-created (device move)
@@ -321,7 +342,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
-             prior_rows=None, trim=False, ragged=False):
+             prior_rows=None, trim=False, ragged=False, durations=None):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -333,11 +354,14 @@ class SynthesizerTrn(nn.Module):
           prior_rows   (lo, hi, B_global): draw the prior noise for the whole global batch and use
                        rows lo:hi (ranks seeded alike then reproduce the single-process draw)
           trim         opt-in trimmed decode (see `infer`)
-          ragged       opt-in row-exact ragged decode (see `infer`)"""
+          ragged       opt-in row-exact ragged decode (see `infer`)
+          durations    frames per token to use instead of the predicted ones (see `infer`)"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
         dev, B, T = x.device, x.shape[0], x.shape[1]
+        if durations is not None:
+            durations, dur_dtype = self._check_durations(durations, B, T, length_scale)
         I = self.cfg.inter_channels
         if outputs is None:
             want = set(self._OUTPUT_NAMES)
@@ -363,6 +387,9 @@ class SynthesizerTrn(nn.Module):
                                         float(length_scale), self._ptr(noise_w), float(noise_scale_w),
                                         self._ptr(y_lengths), stream),
                         "mbv_encode")
+            if durations is not None:
+                _capi.check(h, L.mbv_set_durations(h, self._ptr(durations), dur_dtype, B, T, self._ptr(y_lengths), stream),
+                            "mbv_set_durations")
             lo, hi = torch.aminmax(y_lengths)
             stat = torch.stack((hi, -lo))           # [T'max, > 0 iff an utterance was flagged -1]
             if stat_reduce is not None:
@@ -375,7 +402,7 @@ class SynthesizerTrn(nn.Module):
             if flag > 0:                            # flagged by the kernels, no extra sync
                 raise IndexError("index out of range in self (token id, x_lengths or sid outside the "
                                  "model's tables, or a duration outside the supported range: 2^20 frames a token, "
-                                 "2^30 an utterance)")
+                                 "2^30 an utterance%s)" % ("" if durations is None else "; given durations must be non-negative integers"))
             if frames_hook is not None:
                 Tp = int(frames_hook(Tp))
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729)
@@ -464,8 +491,14 @@ class SynthesizerTrn(nn.Module):
         return o, o_mb, spec, phase
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-              max_len=None, outputs=None, trim=False, ragged=False):
+              max_len=None, outputs=None, trim=False, ragged=False, durations=None):
         """-> (o, o_mb, spec, phase, attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:737)
+
+        `durations` (extension, default None = the predicted durations, launch for launch as before): frames per
+        token, [B, T_text] or [B, 1, T_text] (e.g. the `w` of `align`), non-negative integers of any dtype.  They
+        are used as given, masked by x_lengths, with y_lengths = max(sum, 1): `length_scale` must stay 1 and
+        `noise_scale_w` is without effect (the duration predictor still runs; its result is replaced).  A negative
+        or non-integer entry raises IndexError after the call's one read-back, like an invalid token id.
 
         `outputs` (extension, default None = the reference's full tuple): names of the tensors to
         materialise; the rest of the tuple is None.  A caller that only takes `[0]`
@@ -484,14 +517,14 @@ class SynthesizerTrn(nn.Module):
         the last ~25 frames of a row depend on what the unmasked decoder computes behind its end.  The B lengths
         are read back in the call's one host synchronisation."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, durations=durations)
         return r[:8]
 
     def infer_z_only(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-                     max_len=None):
-        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788)"""
+                     max_len=None, durations=None):
+        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788); `durations` as in `infer`"""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w)
+                      noise_scale_w=noise_scale_w, durations=durations)
         return r[4], r[5], r[6], r[7]
 
     def infer_with_lengths(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1,
@@ -890,7 +923,88 @@ class SynthesizerTrn(nn.Module):
     # ------------------------------------------------------------------ out of scope
     def forward(self, *a, **k):
         raise NotImplementedError("training forward (models.py:657-695) is outside the inference "
-                                  "hot path this package implements")
+                                  "hot path this package implements; its alignment (enc_q, flow, neg_cent, "
+                                  "monotonic alignment search: models.py:659-680) is `align`")
+
+    _ALIGN_OUTPUT_NAMES = ("w", "attn", "x_mask", "y_mask", "z", "z_p", "m_p", "logs_p", "neg_cent")
+
+    @torch.no_grad()
+    def align(self, x, x_lengths, y, y_lengths, sid=None, noise_scale=1.0, outputs=None, noise=None):
+        """Forced alignment of recordings to their texts: the alignment half of the reference's `forward`
+        (models.py:659-680, :690-691) -> (attn, w, x_mask, y_mask, (z, z_p, m_p, logs_p)).
+
+          x, x_lengths   token ids [B, T_text], lengths [B]
+          y, y_lengths   linear spectrogram [B, spec_channels, T_spec] (`spectrogram`), frame counts [B]
+          sid            [B] for a multi-speaker model, else None
+          attn           [B, 1, T_spec, T_text] the monotone path: one token per valid frame, at least one frame a token
+          w              [B, 1, T_text] float frames per token = attn.sum(2); feed it to `infer(..., durations=w)`
+          m_p, logs_p    the text statistics expanded by the path
+          noise_scale    0: the deterministic z = m_q; else z = m_q + noise * noise_scale * exp(logs_q) with
+                         noise = torch.randn(B, inter, T_spec) drawn as `voice_conversion` draws it (or `noise`)
+          outputs        None = all of the above; or names from _ALIGN_OUTPUT_NAMES: only those are materialised,
+                         the rest come back as None (`outputs=("w",)` skips attn and the prior).  "neg_cent"
+                         ([B, T_spec, T_text], defined for [y < y_lengths[b], x < x_lengths[b]) only) is returned as
+                         a last, extra element of the tuple when named.
+        Every row needs 1 <= x_lengths[b] <= y_lengths[b] (more tokens than frames have no monotone path): ValueError;
+        ids / lengths / sid outside their tables: IndexError — both after the call's one host synchronisation."""
+        h = self._ensure_handle()
+        L = _capi.lib()
+        x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
+        dev, B, T = x.device, x.shape[0], x.shape[1]
+        cfg = self.cfg
+        I = cfg.inter_channels
+        if y.dim() != 3 or y.shape[0] != B or y.shape[1] != cfg.spec_channels:
+            raise ValueError("y must be [B, %d, T_spec] (linear spectrogram), B = %d" % (cfg.spec_channels, B))
+        if y_lengths.dim() != 1 or y_lengths.shape[0] != B:
+            raise ValueError("y_lengths must be [B]")
+        Tp = y.shape[2]
+        if T < 1 or Tp < 1:
+            raise ValueError("empty text or spectrogram")
+        if outputs is None:
+            want = set(self._ALIGN_OUTPUT_NAMES) - {"neg_cent"}
+        else:
+            want = set(outputs)
+            unknown = want - set(self._ALIGN_OUTPUT_NAMES)
+            if unknown:
+                raise ValueError("unknown output name(s) %s (known: %s)" % (sorted(unknown), ", ".join(self._ALIGN_OUTPUT_NAMES)))
+        y = y.to(device=dev, dtype=torch.float32).contiguous()
+        y_lengths = y_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        f32 = dict(device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            if float(noise_scale) != 0.0:
+                if noise is None:
+                    noise = torch.randn(B, I, Tp, **f32)             # randn_like(m) of models.py:245
+                elif tuple(noise.shape) != (B, I, Tp):
+                    raise ValueError("noise must be [B, %d, T_spec]" % I)
+                noise = noise.to(**f32).contiguous()
+            else:
+                noise = None
+            shapes = {"attn": (B, 1, Tp, T), "x_mask": (B, 1, T), "y_mask": (B, 1, Tp), "z": (B, I, Tp),
+                      "z_p": (B, I, Tp), "m_p": (B, I, Tp), "logs_p": (B, I, Tp)}
+            t = {k: torch.empty(*shapes[k], **f32) for k in shapes if k in want}
+            if "neg_cent" in want:
+                t["neg_cent"] = torch.zeros(B, Tp, T, **f32)
+            w32 = torch.empty(B, T, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            out = _capi.MbvAlignOutputs()
+            out.w = w32.data_ptr()
+            for k, v in t.items():
+                setattr(out, k, v.data_ptr())
+            _capi.check(h, L.mbv_align(h, self._ptr(x), self._ptr(x_lengths), self._ptr(y), self._ptr(y_lengths),
+                                       self._ptr(sid), B, T, Tp, self._ptr(noise), float(noise_scale), C.byref(out),
+                                       self._ptr(status), self._stream()), "mbv_align")
+            w = w32.to(torch.float32).unsqueeze(1) if "w" in want else None
+            flags = int(status.max())                               # the one host sync
+            if flags & 1:
+                raise IndexError("index out of range in self (token id, x_lengths, y_lengths or sid outside the "
+                                 "model's tables or the tensors)")
+            if flags & 2:
+                raise ValueError("align: an utterance has more tokens than frames (x_lengths > y_lengths): no monotone path")
+            if flags & 4:
+                raise ValueError("align: an utterance with x_lengths < 1 or y_lengths < 1")
+        g = t.get
+        r = (g("attn"), w, g("x_mask"), g("y_mask"), (g("z"), g("z_p"), g("m_p"), g("logs_p")))
+        return r + (t["neg_cent"],) if "neg_cent" in want else r
 
     @torch.no_grad()
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt):

@@ -206,6 +206,44 @@ int mbv_decode_ragged(mbv_model *m, const float *z, const float *g, int B, int t
 int mbv_synthesize_ragged(mbv_model *m, int t_frames, const float *noise, float noise_scale, int max_len,
                           const mbv_outputs *outs, const int64_t *y_lengths_host, void *stream);
 
+/* ---- pooled streaming decode: the next chunk of many concurrent streams in shared launches (no reference
+ * counterpart: the reference service decodes one request at a time) ----------------
+ * One call takes n chunks, each the z-frames [first, first + count) of its OWN utterance (own z, g, length and
+ * waveform row), and makes one decoder run per class of the utterances' lengths (mbv_ragged_classes) instead of one
+ * mbv_decode_range per chunk.  A run's rows are the chunks' z-windows [max(0, first - L), min(t_frames, first +
+ * count + R)), gathered into scratch and decoded as rows of the ragged decode of their window lengths, while every
+ * conv is planned as for the whole utterances (of one class: alike).  Each stored sample is BITWISE what
+ * mbv_decode_range, and so mbv_decode on the whole z, gives for that utterance alone (default mode; with "splitk"
+ * within fp32 rounding, bitwise run to run).  Only samples [256 first, 256 (first + count)) of each o are written,
+ * and no z-frame outside a chunk's window is read.  Two chunks of one call may belong to one utterance when their
+ * sample ranges are disjoint.
+ *
+ * mbv_chunks_plan (host only): the decoder runs a call makes for chunks of utterances of t_frames[i] z-frames — one
+ * per non-empty class, cut further exactly where mbv_ragged_plan cuts rows of those lengths (a 2 GiB tensor, 65535
+ * rows).  run_of_chunk [n] (or NULL) receives the run of every chunk.  Returns the number of runs, -1 on a bad
+ * argument (a t_frames < 1 included).
+ *
+ * mbv_decode_chunks: chunks_host HOST [n]; its values travel to the device as kernel arguments, so the array may be
+ * freed when the call returns; nothing is copied from caller memory and nothing is synchronised.  Refused with a
+ * message, launching nothing and leaving the handle usable: a range outside its utterance, an o that is not
+ * 16-byte aligned, a z_stride < t_frames, g given for some chunks and not for others (a model with gin_channels),
+ * the options "trim" or "conv_bf16" set.
+ *
+ * mbv_decoder_runs: decoder runs (passes through the decoder's conv chain) made on this handle since mbv_create,
+ * by any entry; the difference across a call is what that call cost in launch chains. */
+typedef struct mbv_chunk {
+  const float *z;        /* DEVICE, one utterance: [192, t_frames] at row stride z_stride (in floats) */
+  int64_t z_stride;
+  const float *g;        /* DEVICE [gin] or NULL */
+  int32_t t_frames;      /* the utterance's whole length: decides the class */
+  int32_t first, count;  /* z-frames [first, first + count) */
+  float *o;              /* DEVICE, the utterance's waveform row (>= 256 t_frames floats, 16-byte aligned); only
+                            samples [256 first, 256 (first + count)) are written */
+} mbv_chunk;
+int mbv_chunks_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_frames, int32_t *run_of_chunk);
+int mbv_decode_chunks(mbv_model *m, const mbv_chunk *chunks_host, int n, void *stream);
+int64_t mbv_decoder_runs(mbv_model *m);
+
 /* speaker embedding lookup: replaces `net.emb_g(sid)` (models.py:705).
  * out fp32 [B, gin] */
 int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, void *stream);

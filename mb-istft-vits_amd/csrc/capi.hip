@@ -108,6 +108,7 @@ struct mbv_model {
   int trim = 0;                    // option "trim": opt-in trimmed decode (run_decoder)
   std::vector<int> ragged_first;   // row-exact ragged decode: first length of every class up to ragged_scanned (ragged_classes)
   int ragged_scanned = 0, ragged_splitk = -1;
+  int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
   // state of the last encode
@@ -955,11 +956,17 @@ bool decoder_stage_concurrent(const mbv_model* m, int B, int ch, int Lo) {
 // The streaming decode (mbv_decode_range): run_decoder on a z-window of Td frames whose first frame is z-frame
 // `first - keep_first` of an utterance of t_full frames.  The tail stores only window frames [keep_first,
 // keep_first + keep_count), at o + b o_row_stride (o already offset to the chunk's first sample).
+// Pooled (mbv_decode_chunks; together with RaggedRows): every row is the window of its own chunk of its own
+// utterance.  `rows` (device [B]) then holds each row's kept range and destination, max_keep >= the longest kept
+// range in tail units (64 per z-frame), t_full = the longest utterance of the run — all of one class, so it plans
+// every conv as each of them does — and keep_first / keep_count / o / o_row_stride are not read.
 struct DecodeRange {
   int t_full;
   int keep_first, keep_count;
   float* o;
   int64_t o_row_stride;
+  const PoolRow* rows = nullptr;
+  int max_keep = 0;
 };
 
 // Receptive field of the decoder in whole z-frames (mbv_decoder_context): the interval of z-frames any sample of
@@ -1021,13 +1028,15 @@ struct RaggedRows {
   const int* row_map;      // device [B]: the row of o
   float* o;
   int64_t o_row_stride;
-  int t_min;               // host: the shortest row of the run (run_decoder checks that it plans like the longest)
+  int t_min;               // host: the shortest row of the run (run_decoder checks that it plans like the longest);
+                           // pooled: the shortest UTTERANCE a row of the run is cut from
 };
 
 int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, const float* gvec,
                 int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc, const DecodeRange* rg = nullptr,
                 const RaggedRows* rr = nullptr) {
   const mbv_config& c = m->cfg;
+  ++m->decoder_runs;
   if (rr) zlens = rr->len;
   // ranged decode, default mode: the length rules of the conv planner see the one-shot lengths (conv1d_plan)
   const int rt_num = rg && !m->splitk ? rg->t_full : 0;
@@ -1052,6 +1061,9 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   // really launched: every conv, planned for one utterance of the run's shortest row and of its longest, must fall
   // on the same side of the narrow / tiled divide — else rows of this run would sum in an order their stand-alone
   // decode does not use.  (num, add: the conv's columns per z-frame, as for the tile maps.)
+  // Pooled (rg and rr): the rows are windows, and what must agree is the plan of the UTTERANCES they are cut from:
+  // the shortest (rr->t_min) against the longest (rg->t_full), and the launch itself, which plans with the longest
+  // in place of its own columns (route_T), against both.
   bool route_drift = false;
   auto narrow_alone = [&](const ConvArgs& a, int num, int add, int len) {
     ConvArgs s1 = a;
@@ -1065,7 +1077,14 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     return r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH;
   };
   auto with_trim = [&](ConvArgs& a, int num, int add) {
-    if (rr && !m->splitk && narrow_alone(a, num, add, rr->t_min) != narrow_alone(a, num, add, Td)) route_drift = true;
+    if (rr && !m->splitk) {
+      const bool narrow_long = narrow_alone(a, num, add, rg ? rg->t_full : Td);
+      if (narrow_alone(a, num, add, rr->t_min) != narrow_long) route_drift = true;
+      if (rg) {
+        const int r = conv1d_plan(a, false, rt_num * num + add).route;
+        if ((r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH) != narrow_long) route_drift = true;
+      }
+    }
     if (!trim) return;
     const int bn = conv1d_trim_bn(a);
     if (!bn) return;
@@ -1231,7 +1250,8 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   float* xpost = sc.take<float>((size_t)Bc * prow * Fr);
   float* o = rg ? rg->o : rr ? rr->o : outs ? outs->o : nullptr;
   float* otmp = nullptr;
-  if (!o) { otmp = sc.take<float>((size_t)B * 256 * Td); o = otmp; }
+  const bool pooled = rg && rg->rows;      // (every row stores through its own table entry)
+  if (!o && !pooled) { otmp = sc.take<float>((size_t)B * 256 * Td); o = otmp; }
   // ranged: window sub-band samples (MB / MS) or output quads (SB) of the kept frames, 64 per z-frame either way
   IstftRange keep{rg ? 64 * rg->keep_first : 0, rg ? 64 * (rg->keep_first + rg->keep_count) : 0,
                   rg ? rg->o_row_stride : 0, nullptr, nullptr};
@@ -1255,7 +1275,10 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.spec = outs && outs->spec ? outs->spec + (size_t)b0 * 9 * Fr : nullptr;
       ia.phase = outs && outs->phase ? outs->phase + (size_t)b0 * 9 * Fr : nullptr;
       ia.B = nb; ia.F = Fr; ia.exact_math = m->exact_math; ia.prescaled = 1;
-      if (rr) {
+      if (pooled) {
+        ia.o = nullptr; ia.spec = ia.phase = nullptr;
+        launch_istft_single_pool(ia, rg->rows + b0, rg->max_keep, s);
+      } else if (rr) {
         IstftRange kb = keep;
         kb.row_lens += b0; kb.row_map += b0;
         ia.o = o; ia.spec = ia.phase = nullptr;
@@ -1276,7 +1299,10 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       ia.B = nb; ia.Tp = Td; ia.multistream = ms;
       ia.fixed_bank = !ia.multistream; ia.exact_math = m->exact_math; ia.prescaled = 1;
       if (trim && nb == B && !ia.o_mb && !ia.spec && !ia.phase) ia.trim_lens = zlens;
-      if (rr) {
+      if (pooled) {
+        ia.o = nullptr; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
+        launch_istft_pqmf_pool(ia, rg->rows + b0, rg->max_keep, s);
+      } else if (rr) {
         IstftRange kb = keep;
         kb.row_lens += b0; kb.row_map += b0;
         ia.o = o; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
@@ -1295,7 +1321,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   HIPCHK(m, hipEventRecord(m->evk[2], s));
   m->evk_set = true;
   m->evk_split = Bc < B;
-  if (route_drift) return m->fail("internal error: a ragged run holds rows whose convs plan differently (ragged_classes out of step with run_decoder)");
+  if (route_drift) return m->fail("internal error: a %s run holds rows whose convs plan differently (ragged_classes out of step with run_decoder)", pooled ? "pooled" : "ragged");
   return 0;
 }
 
@@ -1464,6 +1490,78 @@ int run_decoder_ragged(mbv_model* m, const float* z, int zstride, const float* g
     const RaggedRows rr{ints + n, ints + 2 * n, ints + 3 * n, ints, o, o_row_stride,
                         *std::min_element(run.lens.begin(), run.lens.end())};
     if (run_decoder(m, zc, Tc, nullptr, gc, (int)n, Tc, nullptr, s, sc, nullptr, &rr)) return 1;
+  }
+  sc.off = base;
+  return 0;
+}
+
+// ------------------------------------------------------------------ pooled ranged decode (mbv_decode_chunks)
+// One chunk of one utterance as a row of a run: the z-window [wa, wa + len) that mbv_decode_range would decode for
+// it, and the frames of the window that are kept.
+struct ChunkWindow { int wa, len, keep_first; };
+ChunkWindow chunk_window(const mbv_chunk& k, int Lc, int Rc) {
+  const int wa = k.first - Lc > 0 ? k.first - Lc : 0;
+  const int wb = (int64_t)k.first + k.count + Rc < k.t_frames ? k.first + k.count + Rc : k.t_frames;
+  return {wa, wb - wa, k.first - wa};
+}
+
+// A pooled run's widest window and longest chunk
+void pooled_run_extent(const mbv_chunk* chunks, const RaggedRun& run, int Lc, int Rc, int* Tw, int* max_count) {
+  *Tw = 0; *max_count = 0;
+  for (int i : run.rows) {
+    const int len = chunk_window(chunks[i], Lc, Rc).len;
+    if (len > *Tw) *Tw = len;
+    if (chunks[i].count > *max_count) *max_count = chunks[i].count;
+  }
+}
+
+size_t pooled_scratch_bytes(const mbv_config& c, const mbv_chunk* chunks, const std::vector<RaggedRun>& runs, int Lc, int Rc) {
+  size_t need = 0;
+  for (const auto& r : runs) {
+    int Tw, mc;
+    pooled_run_extent(chunks, r, Lc, Rc, &Tw, &mc);
+    const size_t n = r.rows.size();
+    const size_t v = n * sizeof(PoolRow) + 3 * n * sizeof(int) + (n * c.inter_channels * Tw + n * c.gin_channels) * sizeof(float) +
+                     8 * 256 + decoder_scratch_bytes(c, (int)n, Tw);
+    if (v > need) need = v;
+  }
+  return need;
+}
+
+// The chunks of one call, one decoder run per RaggedRun of their utterances' lengths (the classes of the ragged
+// decode): the run's rows are the chunks' windows gathered into scratch, decoded as ragged rows of their window
+// lengths, planned as their utterances plan.  The tables travel as kernel arguments (launch_pool_rows).
+int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const std::vector<RaggedRun>& runs, int Lc, int Rc,
+                       hipStream_t s, Bump& sc) {
+  const mbv_config& c = m->cfg;
+  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, gin = with_g ? c.gin_channels : 0;
+  const size_t base = sc.off;
+  for (const auto& run : runs) {
+    const size_t n = run.rows.size();
+    int Tw, max_count;
+    pooled_run_extent(chunks, run, Lc, Rc, &Tw, &max_count);
+    sc.off = base;
+    PoolRow* rows = sc.take<PoolRow>(n);
+    int* lens = sc.take<int>(3 * n);
+    for (size_t f = 0; f < n; f += kPoolChunk) {
+      PoolRowsArg r{};
+      const int nn = (int)(n - f < (size_t)kPoolChunk ? n - f : (size_t)kPoolChunk);
+      for (int i = 0; i < nn; ++i) {
+        const mbv_chunk& k = chunks[run.rows[f + i]];
+        const ChunkWindow w = chunk_window(k, Lc, Rc);
+        r.row[i] = PoolRow{k.z, k.z_stride, gin ? k.g : nullptr, k.o + (int64_t)256 * k.first, w.wa, w.len,
+                           64 * w.keep_first, 64 * (w.keep_first + k.count)};
+      }
+      launch_pool_rows(r, nn, (int)f, us, rows, lens, (int)n, s);
+    }
+    float* zc = sc.take<float>(n * I * Tw);
+    float* gc = gin ? sc.take<float>(n * gin) : nullptr;
+    launch_gather_windows(rows, (int)n, I, Tw, zc, gin, gc, s);
+    const RaggedRows rr{lens, lens + n, lens + 2 * n, nullptr, nullptr, 0,
+                        *std::min_element(run.lens.begin(), run.lens.end())};
+    DecodeRange rg{run.Tc, 0, max_count, nullptr, 0};
+    rg.rows = rows; rg.max_keep = 64 * max_count;
+    if (run_decoder(m, zc, Tw, nullptr, gc, (int)n, Tw, nullptr, s, sc, &rg, &rr)) return 1;
   }
   sc.off = base;
   return 0;
@@ -2216,6 +2314,62 @@ int mbv_decode_range(mbv_model* m, const float* z, const float* g, int B, int t_
   HIPCHK(m, hipGetLastError());
   return 0;
 }
+
+int mbv_chunks_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_frames, int32_t* run_of_chunk) {
+  if (!cfg || n <= 0 || !t_frames) return -1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+  std::vector<int64_t> lens(n);
+  int t_max = 0;
+  for (int i = 0; i < n; ++i) {
+    if (t_frames[i] < 1) return -1;
+    lens[i] = t_frames[i];
+    if (t_frames[i] > t_max) t_max = t_frames[i];
+  }
+  std::vector<int> first;
+  ragged_classes(*cfg, splitk != 0, t_max, &first);
+  std::vector<RaggedRun> runs;
+  ragged_plan(*cfg, first, n, t_max, lens.data(), &runs);
+  if (run_of_chunk)
+    for (size_t r = 0; r < runs.size(); ++r)
+      for (int i : runs[r].rows) run_of_chunk[i] = (int32_t)r;
+  return (int)runs.size();
+}
+
+int mbv_decode_chunks(mbv_model* m, const mbv_chunk* chunks_host, int n, void* stream) {
+  if (!m) return 1;
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!chunks_host || n <= 0) return m->fail("mbv_decode_chunks: bad arguments");
+  const char* why = ragged_mode_error(m, nullptr);
+  if (why) return m->fail("mbv_decode_chunks: %s", why);
+  const mbv_config& c = m->cfg;
+  std::vector<int64_t> lens(n);
+  int t_max = 0, with_g = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_chunk& k = chunks_host[i];
+    if (!k.z || !k.o || k.t_frames <= 0 || k.z_stride < k.t_frames)
+      return m->fail("mbv_decode_chunks: chunk %d: z / o missing, t_frames <= 0 or z_stride < t_frames", i);
+    if (k.first < 0 || k.count <= 0 || k.first >= k.t_frames || k.count > k.t_frames - k.first)
+      return m->fail("mbv_decode_chunks: chunk %d: frames [%d, %d + %d) outside [0, %d)", i, k.first, k.first, k.count, k.t_frames);
+    if ((uintptr_t)k.o & 15) return m->fail("mbv_decode_chunks: chunk %d: o must be 16-byte aligned", i);
+    if (c.gin_channels && k.g) ++with_g;
+    lens[i] = k.t_frames;
+    if (k.t_frames > t_max) t_max = k.t_frames;
+  }
+  if (with_g && with_g != n) return m->fail("mbv_decode_chunks: g is given for %d of %d chunks (all or none)", with_g, n);
+  int Lc = 0, Rc = 0;
+  decoder_context(c, &Lc, &Rc);
+  DEVICE_GUARD(m);
+  std::vector<RaggedRun> runs;
+  ragged_plan(m, n, t_max, lens.data(), &runs);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, pooled_scratch_bytes(c, chunks_host, runs, Lc, Rc))) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  m->stages.clear();
+  if (run_decoder_pooled(m, chunks_host, with_g != 0, runs, Lc, Rc, (hipStream_t)stream, sc)) return 1;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_decoder_runs(mbv_model* m) { return m ? m->decoder_runs : -1; }
 
 int mbv_stage_times_ms(mbv_model* m, float out[5]) {
   if (!m || !out) return 1;

@@ -260,6 +260,22 @@ struct IstftRange {
 };
 void launch_istft_pqmf_range(const IstftArgs& a, const IstftRange& r, hipStream_t s);
 
+// Pooled ranged decode (mbv_decode_chunks): row b of a run is the z-window of ONE chunk of some utterance.  Its
+// source, its window and what the tail keeps of it are its own; the table lives in the arena (launch_pool_rows).
+struct PoolRow {
+  const float* z;          // the utterance's z [192, .] at row stride z_stride
+  int64_t z_stride;
+  const float* g;          // [gin] or null
+  float* o;                // where sample 256 `first` of the utterance goes (the chunk's first sample)
+  int wa, len;             // the window: z-frames [wa, wa + len) of the utterance
+  int keep_lo, keep_hi;    // kept sub-band samples (MB / MS) or output quads (SB) of the window, 64 per z-frame
+};
+// The ranged tails with per-row ranges and destinations: row b is a window of rows[b].len z-frames inside a launch
+// laid out for a.Tp (a.F) exactly as a row of the ragged decode is; tiles [keep_lo / TM, ceil(keep_hi / TM)) of
+// every row do work (the grid holds span_tiles(max_keep) per row, the others return at once), and unit u in
+// [keep_lo, keep_hi) is stored at rows[b].o + 4 (u - keep_lo).  max_keep >= keep_hi - keep_lo of every row.
+void launch_istft_pqmf_pool(const IstftArgs& a, const PoolRow* rows, int max_keep, hipStream_t s);
+
 // single-band iSTFT (iSTFT_Generator, models.py:296-300): x_post [B, 18, F] -> o [B, 4 (F-1)]
 struct IstftSbArgs {
   const float* x_post;   // [B, 18, F]
@@ -272,6 +288,7 @@ struct IstftSbArgs {
 };
 void launch_istft_single(const IstftSbArgs& a, hipStream_t s);
 void launch_istft_single_range(const IstftSbArgs& a, const IstftRange& r, hipStream_t s);
+void launch_istft_single_pool(const IstftSbArgs& a, const PoolRow* rows, int max_keep, hipStream_t s);
 
 // x_post rows back to the reference's units (stage introspection): inverse of the pre-scaling
 void launch_unscale_xpost(const float* src, float* dst, int B, int rows, int F, hipStream_t s);
@@ -378,6 +395,14 @@ void launch_ragged_rows(const RaggedRowsArg& r, int n, int first, int us, int* o
 // dst[i, c, t] = src[rows[i], c, t] for t < lens[i] (lens null: t < T): dst [n, C, T], src rows of C x src_rstride
 void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride, const int* rows, const int* lens,
                           int n, int C, int T, float* dst, hipStream_t s);
+// pooled ranged decode: n rows given by value from the host (up to kPoolChunk per launch) -> rows[first + i], and
+// the window length of row first + i at the three rates of the decoder at lens[k stride + first + i], k < 3
+constexpr int kPoolChunk = 64;
+struct PoolRowsArg { PoolRow row[kPoolChunk]; };
+void launch_pool_rows(const PoolRowsArg& r, int n, int first, int us, PoolRow* rows, int* lens, int stride, hipStream_t s);
+// dst[i, c, t] = rows[i].z[c z_stride + wa + t] for t < rows[i].len (nothing outside a row's window is read; dst
+// [n, C, T] behind a row's length is left as it is: every reader masks at the length); gdst[i, :] = rows[i].g[0 .. gin)
+void launch_gather_windows(const PoolRow* rows, int n, int C, int T, float* dst, int gin, float* gdst, hipStream_t s);
 // which column-tile width launch_conv1d will use for this conv (128 or 384; 0: a kernel without trim support)
 int conv1d_trim_bn(const ConvArgs& a);
 

@@ -514,6 +514,40 @@ void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride
                      src_rstride, rows, lens, C, T, dst);
 }
 
+__global__ void pool_rows_kernel(const PoolRowsArg r, int n, int first, int us, PoolRow* __restrict__ rows,
+                                 int* __restrict__ lens, int stride) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  const int len = r.row[i].len;
+  rows[first + i] = r.row[i];
+  lens[first + i] = len;
+  lens[stride + first + i] = us * len;
+  lens[2 * stride + first + i] = us * us * len;
+}
+
+void launch_pool_rows(const PoolRowsArg& r, int n, int first, int us, PoolRow* rows, int* lens, int stride, hipStream_t s) {
+  hipLaunchKernelGGL(pool_rows_kernel, dim3(1), dim3(kPoolChunk), 0, s, r, n, first, us, rows, lens, stride);
+}
+
+// blockIdx.y < C: channel row c of window i; blockIdx.y == C (only when gin > 0): the row's speaker vector
+__global__ void gather_windows_kernel(const PoolRow* __restrict__ rows, int C, int T, float* __restrict__ dst, int gin,
+                                      float* __restrict__ gdst) {
+  const int i = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const PoolRow r = rows[i];
+  if (c == C) {
+    for (int k = t; k < gin; k += gridDim.x * blockDim.x) gdst[(int64_t)i * gin + k] = r.g[k];
+    return;
+  }
+  if (t < T && t < r.len) dst[((int64_t)i * C + c) * T + t] = r.z[(int64_t)c * r.z_stride + r.wa + t];
+}
+
+void launch_gather_windows(const PoolRow* rows, int n, int C, int T, float* dst, int gin, float* gdst, hipStream_t s) {
+  const int nt = T >= 256 ? 256 : 64;
+  hipLaunchKernelGGL(gather_windows_kernel, dim3((T + nt - 1) / nt, C + (gin > 0 ? 1 : 0), n), dim3(nt), 0, s, rows, C, T,
+                     dst, gin, gdst);
+}
+
 void launch_fill(float* p, float v, int64_t n, hipStream_t s) {
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;

@@ -651,6 +651,29 @@ class SynthesizerTrn(nn.Module):
                 g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
         return stream.DecodeStream(self, h, z, g, chunk_frames, max_chunk_frames)
 
+    def stream_pool(self):
+        """A `stream.StreamPool` of this model: `pool.add(st)` single-utterance streams of `dec_stream` /
+        `infer_stream`, then `pool.step()` decodes the next chunk of each in one `mbv_decode_chunks` call — one decoder
+        run per class of lengths (`chunks_plan`), every sample bitwise what the stream yields alone."""
+        return stream.StreamPool(self)
+
+    def chunks_plan(self, t_frames, splitk=False):
+        """(runs, run_of_chunk): the decoder runs one pooled step makes for chunks of utterances of these z-lengths
+        (`mbv_chunks_plan`, host only: no GPU needed)."""
+        t = [int(v) for v in (t_frames.tolist() if torch.is_tensor(t_frames) else t_frames)]
+        n = len(t)
+        cfg = self._config_struct()
+        runs = (C.c_int32 * max(n, 1))()
+        r = _capi.lib().mbv_chunks_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * max(n, 1))(*t), runs)
+        if r < 0:
+            raise ValueError("mbv_chunks_plan refused the lengths (every t_frames must be >= 1, and at least one chunk)")
+        return r, list(runs)[:n]
+
+    def decoder_runs(self):
+        """Decoder runs made on this model's handle so far (`mbv_decoder_runs`): the difference across a call is the
+        number of launch chains it cost."""
+        return int(_capi.lib().mbv_decoder_runs(self._ensure_handle()))
+
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
                      chunk_frames=32, max_chunk_frames=256):

@@ -466,6 +466,50 @@ int mbv_resample_pcm16_range(mbv_model *m, const float *wave, const int64_t *val
                              int64_t out_count, const float *peak, int16_t *pcm, int64_t pcm_stride,
                              float *running_peak, int64_t *out_samples, void *stream);
 
+/* ---- pooled wire output: the ranged step of many concurrent streams in ONE launch (no reference counterpart: the
+ * reference service handles one request at a time) ----------------
+ * One call takes n chunks, each the outputs [out_first, out_first + out_count) of its OWN stream (own wave row,
+ * length, frontier, peak and pcm row), and makes one resample / int16 launch for all of them instead of one
+ * mbv_resample_pcm16_range per stream.  Every stored int16, running peak and out_samples is BITWISE what
+ * mbv_resample_pcm16_range gives for that row alone: an output is computed by the same device code from the same
+ * staged input, whichever tile of whichever launch holds it, and a max does not depend on order.  The fields of a
+ * chunk are the arguments of mbv_resample_pcm16_range for one row (B = 1, in_stride = in_total, pcm_stride =
+ * pcm_capacity); peak may be given for some chunks and not for others.  Two chunks of one call may belong to one
+ * stream when their output ranges are disjoint (they may share running_peak and out_samples).
+ *
+ * mbv_pcm_chunks_plan (host only: no handle, no GPU; reads the integer fields only): checks every chunk as
+ * mbv_resample_pcm16_range checks its row — out_first >= 0, out_count >= 0 (in_avail >= 0, in_total > 0,
+ * pcm_capacity > 0) and out_first + out_count <= min(mbv_resample_ready(.., in_avail, in_total), pcm_capacity) —
+ * and fills packed_first[i] (or NULL) with the running sum of the out_count in chunk order: where chunk i starts
+ * in the packed buffer.  Returns the packed total (0 for n = 0), or -1 with a message that names the offending
+ * chunk ("chunk i: ...", mbv_last_error(NULL)); also -1 for an unknown filter or a rate pair mbv_resample refuses.
+ *
+ * mbv_resample_pcm16_chunks: chunks_host HOST [n]; its values travel to the device as kernel arguments (written
+ * to the handle's scratch by a one-workgroup kernel), so the array may be freed when the call returns; nothing is
+ * copied from caller memory and nothing is synchronised (beyond the first call for a rate pair, as mbv_resample).
+ *   packed, packed_capacity   int16 DEVICE or NULL: chunk i's samples are ALSO stored at packed[packed_first[i] ..),
+ *                             back to back in chunk order, so one copy takes the whole call to the host
+ * One rate pair and filter per call.  Refused with a message, launching nothing and leaving the handle usable:
+ * whatever the plan refuses, a missing wave or pcm, a packed_capacity below the packed total, two chunks that
+ * write overlapping ranges of one pcm.  A call whose chunks are all empty and carry no out_samples launches nothing.
+ *
+ * mbv_wire_runs: launches of the resample / int16 kernels made by mbv_resample_pcm16_range and
+ * mbv_resample_pcm16_chunks on this handle since mbv_create (table writers are not counted): the counterpart of
+ * mbv_decoder_runs for the wire step. */
+typedef struct mbv_pcm_chunk {
+  const float *wave; int64_t in_total;      /* DEVICE, one row */
+  const int64_t *valid_samples;             /* DEVICE, one int64, or NULL */
+  int64_t in_avail, out_first, out_count;
+  const float *peak;                        /* DEVICE, one float, or NULL (per chunk: mixed is allowed) */
+  int16_t *pcm; int64_t pcm_capacity;       /* the stream's own full-length row */
+  float *running_peak; int64_t *out_samples;/* DEVICE, one value each, or NULL */
+} mbv_pcm_chunk;
+int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pcm_chunk *chunks, int n,
+                            int64_t *packed_first);
+int mbv_resample_pcm16_chunks(mbv_model *m, const mbv_pcm_chunk *chunks_host, int n, int orig_sr, int target_sr,
+                              int filter, int16_t *packed, int64_t packed_capacity, void *stream);
+int64_t mbv_wire_runs(mbv_model *m);
+
 /* ---- linear spectrogram ------------------------------------------------------
  * replaces spectrogram_torch(y, n_fft, sr, hop, win, center=False) (mel_processing.py:51-70), the input of
  * mbv_voice_conversion: |STFT| with (n_fft - hop) / 2 zeros on each side of the row, no centring, the

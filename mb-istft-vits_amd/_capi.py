@@ -24,6 +24,7 @@ SYMBOLS = [
     "mbv_resample_ready", "mbv_resample_pcm16_range",
     "mbv_ragged_classes", "mbv_decode_ragged", "mbv_synthesize_ragged", "mbv_ragged_plan",
     "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
+    "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
     "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
     "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
@@ -56,6 +57,14 @@ class MbvChunk(C.Structure):
     """mbv_chunk of include/mbistft_vits.h (mbv_decode_chunks)."""
     _fields_ = [("z", C.c_void_p), ("z_stride", C.c_int64), ("g", C.c_void_p), ("t_frames", C.c_int32),
                 ("first", C.c_int32), ("count", C.c_int32), ("o", C.c_void_p)]
+
+
+class MbvPcmChunk(C.Structure):
+    """mbv_pcm_chunk of include/mbistft_vits.h (mbv_resample_pcm16_chunks)."""
+    _fields_ = [("wave", C.c_void_p), ("in_total", C.c_int64), ("valid_samples", C.c_void_p),
+                ("in_avail", C.c_int64), ("out_first", C.c_int64), ("out_count", C.c_int64), ("peak", C.c_void_p),
+                ("pcm", C.c_void_p), ("pcm_capacity", C.c_int64), ("running_peak", C.c_void_p),
+                ("out_samples", C.c_void_p)]
 
 
 class MbvAlignOutputs(C.Structure):
@@ -180,10 +189,11 @@ def lib():
     L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
-    # those four entries, and the pooled decode's three, may be absent there, and calling one then raises
-    # AttributeError.  Everything else, and the in-tree library always, must match the header.
+    # those four entries, the pooled decode's three and the pooled wire output's three may be absent there, and calling
+    # one then raises AttributeError.  Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
-                "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
+                "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -194,6 +204,12 @@ def lib():
         L.mbv_decode_chunks.argtypes = [vp, C.POINTER(MbvChunk), i32, vp]
         L.mbv_decoder_runs.argtypes = [vp]
         L.mbv_decoder_runs.restype = C.c_int64
+    if hasattr(L, "mbv_resample_pcm16_chunks") or not optional:
+        L.mbv_pcm_chunks_plan.argtypes = [i32, i32, i32, C.POINTER(MbvPcmChunk), i32, i64p]
+        L.mbv_pcm_chunks_plan.restype = C.c_int64
+        L.mbv_resample_pcm16_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), i32, i32, i32, i32, vp, C.c_int64, vp]
+        L.mbv_wire_runs.argtypes = [vp]
+        L.mbv_wire_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -109,6 +109,7 @@ struct mbv_model {
   std::vector<int> ragged_first;   // row-exact ragged decode: first length of every class up to ragged_scanned (ragged_classes)
   int ragged_scanned = 0, ragged_splitk = -1;
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
+  int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
   // state of the last encode
@@ -2809,12 +2810,141 @@ int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* val
     return m->fail("%s: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final", who,
                    (long long)(out_first + out_count), (long long)in_avail, (long long)in_stride, (long long)ready);
   if (out_count == 0 && !out_samples) return 0;           // nothing to write
+  ++m->wire_runs;
   launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, fir ? rb->d : nullptr,
                               fir ? rb->g : ResampleGeom{}, out_first, out_count, peak, reinterpret_cast<short*>(pcm),
                               pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
+
+namespace {
+// The checks mbv_resample_pcm16_range makes on its row, for every chunk of a pooled call (integer fields only);
+// g null = equal rates.  Fills packed_first (may be null) with the running sum of the out_count and returns the
+// packed total, or -1 with *err naming the offending chunk.
+int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const ResampleGeom* g, int M,
+                         int64_t* packed_first, std::string* err) {
+  char buf[512];
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_pcm_chunk& k = chunks[i];
+    const char* why = nullptr;
+    if (k.in_total <= 0 || k.pcm_capacity <= 0) why = "in_total and pcm_capacity must be > 0";
+    else if (k.in_avail < 0 || k.out_first < 0 || k.out_count < 0) why = "in_avail, out_first and out_count must be >= 0";
+    else if ((double)k.pcm_capacity * M >= 0x1p62) why = "pcm_capacity * M overflows the 64-bit time index";
+    if (why) {
+      snprintf(buf, sizeof buf, "%s: chunk %d: %s", who, i, why);
+      *err = buf;
+      return -1;
+    }
+    if (k.out_first > k.pcm_capacity || k.out_count > k.pcm_capacity - k.out_first) {
+      snprintf(buf, sizeof buf, "%s: chunk %d: outputs [%lld, %lld) lie outside the row of pcm_capacity %lld", who, i,
+               (long long)k.out_first, (long long)(k.out_first + k.out_count), (long long)k.pcm_capacity);
+      *err = buf;
+      return -1;
+    }
+    const int64_t ready = g ? resample_ready(*g, k.in_avail, k.in_total) : (k.in_avail < k.in_total ? k.in_avail : k.in_total);
+    if (k.out_first + k.out_count > ready) {
+      snprintf(buf, sizeof buf, "%s: chunk %d: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final",
+               who, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.in_total, (long long)ready);
+      *err = buf;
+      return -1;
+    }
+    if (packed_first) packed_first[i] = total;
+    total += k.out_count;
+  }
+  return total;
+}
+}  // namespace
+
+int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pcm_chunk* chunks, int n,
+                            int64_t* packed_first) {
+  const char* who = "mbv_pcm_chunks_plan";
+  if (n < 0 || (n > 0 && !chunks)) { g_create_error = std::string(who) + ": bad arguments"; return -1; }
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
+    g_create_error = std::string(who) + ": unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
+    return -1;
+  }
+  int L = 0, M = 0;
+  if (resample_reduce(orig_sr, target_sr, &L, &M)) { g_create_error = std::string(who) + ": sample rates must be positive"; return -1; }
+  ResampleGeom g{};
+  const bool fir = orig_sr != target_sr;
+  if (fir) {
+    const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
+    if (why) { g_create_error = std::string(who) + ": " + why; return -1; }
+  }
+  std::string err;
+  const int64_t total = pcm_chunks_check(who, chunks, n, fir ? &g : nullptr, M, packed_first, &err);
+  if (total < 0) g_create_error = err;
+  return total;
+}
+
+int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, int n, int orig_sr, int target_sr,
+                              int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_resample_pcm16_chunks";
+  if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
+  int L = 0, M = 0;
+  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
+    return m->fail("%s: unknown filter %d", who, filter);
+  for (int i = 0; i < n; ++i)
+    if (!chunks_host[i].wave || !chunks_host[i].pcm) return m->fail("%s: chunk %d: wave / pcm missing", who, i);
+  DEVICE_GUARD(m);
+  const bool fir = orig_sr != target_sr;
+  const mbv_model::ResampleBank* rb = nullptr;
+  if (fir && resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
+  std::string err;
+  std::vector<int64_t> off(n > 0 ? n : 1);
+  const int64_t total = pcm_chunks_check(who, chunks_host, n, fir ? &rb->g : nullptr, M, off.data(), &err);
+  if (total < 0) return m->fail("%s", err.c_str());
+  if (packed && packed_capacity < total)
+    return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
+  // two chunks must not write one sample: the non-empty ranges in address order
+  std::vector<int> order;
+  for (int i = 0; i < n; ++i)
+    if (chunks_host[i].out_count > 0) order.push_back(i);
+  auto lo = [&](int i) { return (uintptr_t)(chunks_host[i].pcm + chunks_host[i].out_first); };
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return lo(a) < lo(b); });
+  for (size_t j = 1; j < order.size(); ++j) {
+    if (lo(order[j - 1]) + sizeof(int16_t) * (uintptr_t)chunks_host[order[j - 1]].out_count > lo(order[j]))
+      return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, order[j - 1] < order[j] ? order[j - 1] : order[j],
+                     order[j - 1] < order[j] ? order[j] : order[j - 1]);
+  }
+  // rows with something to write (an empty range still carries out_samples)
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i)
+    if (chunks_host[i].out_count > 0 || chunks_host[i].out_samples) live.push_back(i);
+  if (live.empty()) return 0;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(PcmPoolRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
+  for (size_t f = 0; f < live.size(); f += kPcmPoolChunk) {
+    PcmPoolRowsArg r{};
+    const int nn = (int)(live.size() - f < (size_t)kPcmPoolChunk ? live.size() - f : (size_t)kPcmPoolChunk);
+    for (int i = 0; i < nn; ++i) {
+      const int c = live[f + i];
+      const mbv_pcm_chunk& k = chunks_host[c];
+      r.row[i] = PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count,
+                            k.peak, reinterpret_cast<short*>(k.pcm), k.pcm_capacity,
+                            reinterpret_cast<unsigned*>(k.running_peak), k.out_samples, packed ? off[c] : (int64_t)-1};
+    }
+    launch_pcm_pool_rows(r, nn, (int)f, rows, s);
+  }
+  for (size_t f = 0; f < live.size(); f += 65535) {         // the grid's y limit
+    const size_t nn = live.size() - f < 65535 ? live.size() - f : 65535;
+    int64_t max_count = 0;
+    for (size_t i = 0; i < nn; ++i)
+      if (chunks_host[live[f + i]].out_count > max_count) max_count = chunks_host[live[f + i]].out_count;
+    ++m->wire_runs;
+    launch_resample_pcm16_pool(rows + f, (int)nn, max_count, fir ? rb->d : nullptr, fir ? rb->g : ResampleGeom{},
+                               reinterpret_cast<short*>(packed), s);
+  }
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_wire_runs(mbv_model* m) { return m ? m->wire_runs : -1; }
 
 namespace {
 const char* spectrogram_args_error(int n_fft, int hop, int win) {

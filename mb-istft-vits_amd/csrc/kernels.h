@@ -331,6 +331,31 @@ void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, in
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
                                  int64_t* out_samples, hipStream_t s);
+// Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
+// what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
+// the arena (launch_pcm_pool_rows).
+struct PcmPoolRow {
+  const float* x;              // the stream's wave row
+  int64_t in_total;
+  const int64_t* valid;        // one int64, or null = in_total
+  int64_t in_avail, out_first, out_end;
+  const float* peak;           // one float, or null = no normalisation
+  short* pcm;                  // the stream's own full-length row
+  int64_t pcm_cap;
+  unsigned* running;           // one value, or null
+  int64_t* out_samples;        // one value, or null
+  int64_t packed_off;          // where out_first goes in the call's packed buffer, or -1
+};
+// n rows given by value from the host (up to kPcmPoolChunk per launch: 3 KiB of kernel arguments) -> rows[first + i]
+constexpr int kPcmPoolChunk = 32;
+struct PcmPoolRowsArg { PcmPoolRow row[kPcmPoolChunk]; };
+void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow* rows, hipStream_t s);
+// outputs [out_first, out_end) of every table row (n <= 65535), each bitwise what launch_resample_pcm16_range stores
+// for that row alone; also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
+// out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
+// in_total), pcm_cap) of every row.
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
+                                const ResampleGeom& g, short* packed, hipStream_t s);
 
 // ---------------------------------------------------------------- linear spectrogram (spectrogram.hip)
 // |STFT| of spectrogram_torch(center=False) per row as if alone: (n_fft - hop) / 2 zeros each side, periodic

@@ -331,4 +331,98 @@ void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, in
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Pooled ranged kernel (mbv_resample_pcm16_chunks): the ranged kernel with its per-row quantities read from a
+// table, blockIdx.y = table row, blockIdx.x = tile out_first + 256 x of that row's own range.  The grid holds the
+// tiles of the longest range; a tile at or past its row's out_end returns after the table load (the first tile
+// still writes out_samples, as the ranged kernel does for an empty range).  An output is computed by the same
+// device functions from the same staged values with the same limit min(n, in_avail), and its value does not depend
+// on which tile holds it; the running peak is a max, which does not depend on order: every stored value is bitwise
+// the ranged kernel's.  Each int16 goes to the row's own pcm[t] and, with a packed buffer, to packed[off + t - first].
+// ---------------------------------------------------------------------------------------------------
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
+                           int left, double ratio, short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmPoolRow r = rows[blockIdx.y];
+  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
+  if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
+  const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
+  int64_t n_out = FIR ? (int64_t)((double)n * ratio) : n;
+  if (n_out > r.pcm_cap) n_out = r.pcm_cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && r.out_samples) {
+    int64_t keep = FIR ? (int64_t)ceil((double)n * ratio) : n;
+    r.out_samples[0] = keep > r.pcm_cap ? r.pcm_cap : keep;
+  }
+  const int64_t t = t0 + threadIdx.x;
+  if (t0 >= r.out_end) return;                            // the empty range (only out_samples to write)
+  short* pk = (packed && r.packed_off >= 0) ? packed + (r.packed_off - r.out_first) : nullptr;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
+    if (t < r.out_end) {
+      r.pcm[t] = 0;
+      if (pk) pk[t] = 0;
+    }
+    return;
+  }
+  const int64_t limit = n < r.in_avail ? n : r.in_avail;
+  const float* xb = r.x;
+  int64_t j0 = 0;
+  if (FIR) {
+    int64_t t_last = t0 + kResampleTile - 1;
+    if (t_last > n_out - 1) t_last = n_out - 1;
+    if (t_last > r.out_end - 1) t_last = r.out_end - 1;
+    j0 = resample_window_first(t0, L, M, left);
+    resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
+    __syncthreads();
+  }
+  float v = 0.f;
+  const bool live = t < r.out_end && t < n_out;
+  if (live) v = FIR ? resample_output(xs, j0, t, bank, L, M, K, left, ratio) : (t < limit ? xb[t] : 0.f);
+  if (r.running) {
+    float m = fabsf(v);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    // m >= 0: bit order == value order; a wave that reads a value at least its own has nothing to add
+    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(r.running, __ATOMIC_RELAXED))
+      atomicMax(r.running, __float_as_uint(m));
+  }
+  if (t >= r.out_end) return;
+  if (live) {
+    if (r.peak) {
+      const float p = r.peak[0];
+      if (p > 0.01f) v = (v / p) * 0.9f;
+    }
+    v = fminf(fmaxf(v, -1.f), 1.f);
+    v = v * 32767.f;
+  }
+  const short q = (short)(int)v;
+  r.pcm[t] = q;
+  if (pk) pk[t] = q;
+}
+
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
+                                const ResampleGeom& g, short* packed, hipStream_t s) {
+  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
+  const dim3 grid((unsigned)bx, n), block(kResampleTile);
+  if (bank) {
+    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+    hipLaunchKernelGGL(resample_pcm16_pool_kernel<true>, grid, block, lds, s, rows, bank, g.L, g.M, g.K, g.left,
+                       g.ratio, packed);
+  } else {
+    hipLaunchKernelGGL(resample_pcm16_pool_kernel<false>, grid, block, 0, s, rows, bank, 1, 1, 0, 0, 1.0, packed);
+  }
+}
+
+// the table of a pooled call: by value from the host into the arena, one workgroup (as launch_pool_rows, ops.hip)
+__global__ void pcm_pool_rows_kernel(const PcmPoolRowsArg r, int n, int first, PcmPoolRow* __restrict__ rows) {
+  const int i = threadIdx.x;
+  if (i < n) rows[first + i] = r.row[i];
+}
+
+void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow* rows, hipStream_t s) {
+  hipLaunchKernelGGL(pcm_pool_rows_kernel, dim3(1), dim3(kPcmPoolChunk), 0, s, r, n, first, rows);
+}
+
 }  // namespace mbv

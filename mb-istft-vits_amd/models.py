@@ -851,6 +851,32 @@ class SynthesizerTrn(nn.Module):
                 "mbv_resample_pcm16_range")
 
     @torch.no_grad()
+    def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best"):
+        """The ranged wire step of many streams in ONE launch (`mbv_resample_pcm16_chunks`; `wire.pcm_pool` drives
+        it): `chunks` is a ctypes array (or a list) of `_capi.MbvPcmChunk`, each the arguments of
+        `resample_pcm16_range` for one row of its own stream, as device addresses.  Every stored value is bitwise
+        what `resample_pcm16_range` stores for that row alone.  `packed` (int16, 1-D, device) also receives the
+        chunks' samples back to back, in chunk order.  No host synchronisation (beyond the first call for a rate
+        pair)."""
+        filt = RESAMPLE_TYPES.get(res_type)
+        if filt is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        if not isinstance(chunks, C.Array):
+            chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
+        dev = self._device()
+        cap = 0
+        if packed is not None:
+            if packed.device != dev or packed.dtype != torch.int16 or packed.dim() != 1 or packed.stride(0) != 1:
+                raise ValueError("resample_pcm16_chunks: packed must be a 1-D int16 tensor on %s with unit stride" % dev)
+            cap = packed.shape[0]
+        h = self._ensure_handle()
+        with torch.cuda.device(dev):
+            _capi.check(h, _capi.lib().mbv_resample_pcm16_chunks(h, chunks, len(chunks), int(orig_sr), int(target_sr), filt,
+                                                                 self._ptr(packed), cap, self._stream()),
+                        "mbv_resample_pcm16_chunks")
+
+    @torch.no_grad()
     def spectrogram(self, wave, n_fft, hop_size, win_size, valid_samples=None, center=False):
         """Waveform [B, n] or [B, 1, n] (fp32, or int16 PCM scaled by 1 / 32768 as data_utils.py:75 does) ->
         (spec fp32 [B, n_fft // 2 + 1, F], spec_lengths int64 [B]) on the GPU: spectrogram_torch(y, n_fft, sr,

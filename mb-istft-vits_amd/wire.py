@@ -18,8 +18,13 @@ voice conversion, then `service_pcm16`.
 `stream_pcm16` is the streamed form of `service_pcm16`: it follows a `stream.DecodeStream` chunk by chunk and
 emits the int16 samples that have become final, bitwise those `service_pcm16` gives for the finished waveform
 (`mbv_resample_pcm16_range`); `FrameCutter` is `frame_pcm16` for such a stream of pieces.
+
+`pcm_pool` is `stream_pcm16` for many streams at once: a `PcmPool` steps a `stream.StreamPool` and wires the chunks
+that step (and earlier ones) made final for ALL its streams in one `mbv_resample_pcm16_chunks` launch, and can
+hand the pieces over in one pinned host buffer filled by one copy.
 """
 import base64
+import ctypes as C
 
 import numpy as np
 import torch
@@ -123,7 +128,10 @@ class PcmStream:
       peak           fp32 [B] device, the running peak of the resampled samples emitted so far; after the last
                      chunk bitwise the peak `service_pcm16(auto_normalize=True)` would have divided by
 
-    All state lives in tensors the stream owns, so paused and interleaved streams on one model do not mix."""
+    All state lives in tensors the stream owns, so paused and interleaved streams on one model do not mix.
+
+    A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
+    such a piece out without launching anything, and launches alone otherwise — the same bytes either way."""
 
     def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best"):
         self._net, self._st, self._h = net, st, st._h
@@ -149,6 +157,7 @@ class PcmStream:
                 raise ValueError("peak must be a float or an fp32 [B] tensor")
         self._peak_in = peak
         self._done = 0                            # outputs emitted so far
+        self._wired = 0                           # the first chunk whose final outputs are not emitted yet
 
     def __len__(self):
         return len(self._st)
@@ -163,11 +172,15 @@ class PcmStream:
         if net._handle is not self._h:
             raise RuntimeError("the model's handle was re-created (device move) since this stream started")
         first, count = st.schedule[i]
+        if i < self._wired:                       # a pool wired it already, on the stream current at its step
+            a, b = (self._ready[i - 1] if i else 0), self._ready[i]
+            return a, self.pcm[:, a:b]
         a, b = self._done, self._ready[i]
         net.resample_pcm16_range(st.o, self.model_sr, self.rate, st.spf * (first + count), a, b - a, self.pcm,
                                  valid_samples=self._valid_in, peak=self._peak_in, running_peak=self.peak,
-                                 out_samples=self.valid_samples if i == 0 else None, res_type=self.res_type)
-        self._done = b
+                                 out_samples=self.valid_samples if self._wired == 0 else None,
+                                 res_type=self.res_type)
+        self._done, self._wired = b, i + 1
         return a, self.pcm[:, a:b]
 
     def run(self):
@@ -188,6 +201,141 @@ def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best"):
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
     return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type)
+
+
+def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
+    """(total, packed_first) of `mbv_pcm_chunks_plan` for `_capi.MbvPcmChunk`s (host only: no GPU needed, only the
+    integer fields are read): the checks `resample_pcm16_chunks` makes, and where every chunk starts in the packed
+    buffer.  Raises `_capi.MbvError` naming the offending chunk."""
+    filt = RESAMPLE_TYPES.get(res_type)
+    if filt is None:
+        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    if not isinstance(chunks, C.Array):
+        chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
+    n = len(chunks)
+    first = (C.c_int64 * max(n, 1))()
+    L = _capi.lib()
+    total = L.mbv_pcm_chunks_plan(int(orig_sr), int(target_sr), filt, chunks, n, first)
+    if total < 0:
+        msg = L.mbv_last_error(None)
+        raise _capi.MbvError(msg.decode() if msg else "mbv_pcm_chunks_plan failed")
+    return int(total), list(first)[:n]
+
+
+def wire_runs(net):
+    """Resample / int16 launches of the streamed wire step made on the model's handle so far (`mbv_wire_runs`):
+    one per `resample_pcm16_range` call that had something to write, one per `resample_pcm16_chunks` call."""
+    return int(_capi.lib().mbv_wire_runs(net._ensure_handle()))
+
+
+class PcmPool:
+    """The wire output of many `DecodeStream`s of one model: `step()` steps the wrapped `stream.StreamPool` (one
+    `mbv_decode_chunks` call) and then turns what has become final on ALL pooled streams into int16 in ONE
+    `mbv_resample_pcm16_chunks` launch, instead of one `mbv_resample_pcm16_range` launch per stream.
+
+    `add(st, peak=None)` returns the stream's `PcmStream` follower, which holds the state it holds alone (`pcm`,
+    `valid_samples`, `peak`); the pieces count as wired ahead on it, so `next(follower)` afterwards hands them out
+    without a launch.  A stream may be driven through the pool, alone, or both in turn: the same bytes, those
+    `service_pcm16` gives for the finished waveform.  Finished streams drop out."""
+
+    def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best"):
+        if RESAMPLE_TYPES.get(res_type) is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        if pool._net is not net:
+            raise ValueError("the stream pool belongs to another model")
+        self._net, self.pool = net, pool
+        self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
+        self.followers = []
+        self._packed = None                       # int16 device, the call's pieces back to back (host=True)
+        self._host = self._host_np = None         # its pinned host copy, and that as a NumPy array
+        self._event = None
+
+    def __len__(self):
+        return len(self.followers)
+
+    def follower(self, st):
+        for f in self.followers:
+            if f._st is st:
+                return f
+        return None
+
+    def add(self, st, peak=None):
+        self.pool.add(st)                         # (refuses B > 1, another model, another device)
+        f = self.follower(st)
+        if f is None:
+            f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type)
+            self.followers.append(f)
+        return f
+
+    def step(self, streams=None, host=False):
+        """-> [(st, first_out_sample, piece), ...]: one entry per stream whose decoded frontier made outputs final
+        (an empty piece is possible, as for `PcmStream`).  `piece` is the 1-D view `follower.pcm[0, a:b]` on the
+        device, ordered on the current stream; with host=True it is a NumPy int16 view of ONE pinned buffer that
+        one copy and one event wait filled, valid until the next `step(host=True)`."""
+        net = self._net
+        if streams is None:
+            members = list(self.followers)
+        else:
+            members = []
+            for st in streams:
+                f = self.follower(st)
+                if f is None:
+                    raise ValueError("step(streams=...) names a stream that is not in the pool")
+                members.append(f)
+        named = None if streams is None else [f._st for f in members if f._st._decoded < len(f._st.schedule)]
+        if named is None or named:
+            self.pool.step(named)
+        todo = [f for f in members if f._st._decoded > f._wired]
+        out = []
+        if todo:
+            arr = (_capi.MbvPcmChunk * len(todo))()
+            for k, f in zip(arr, todo):
+                st = f._st
+                if net._handle is not f._h:
+                    raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
+                first, count = st.schedule[st._decoded - 1]
+                a, b = f._done, f._ready[st._decoded - 1]
+                k.wave, k.in_total = st.o.data_ptr(), st.o.shape[-1]
+                k.valid_samples = f._valid_in.data_ptr() if f._valid_in is not None else None
+                k.in_avail, k.out_first, k.out_count = st.spf * (first + count), a, b - a
+                k.peak = f._peak_in.data_ptr() if f._peak_in is not None else None
+                k.pcm, k.pcm_capacity = f.pcm.data_ptr(), f.out_stride
+                k.running_peak = f.peak.data_ptr()
+                k.out_samples = f.valid_samples.data_ptr() if f._wired == 0 else None
+                out.append((st, a, b))
+            dev = net._device()
+            packed = None
+            if host:
+                total, offs = pcm_chunks_plan(self.model_sr, self.rate, arr, self.res_type)
+                if self._packed is None or self._packed.shape[0] < total:
+                    cap = max(2 * total, 1 << 16)
+                    self._packed = torch.empty(cap, device=dev, dtype=torch.int16)
+                    self._host = torch.empty(cap, dtype=torch.int16, pin_memory=True)
+                    self._host_np = self._host.numpy()
+                    self._event = torch.cuda.Event()
+                packed = self._packed
+            net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type)
+            for f in todo:
+                f._done, f._wired = f._ready[f._st._decoded - 1], f._st._decoded
+            if host:
+                if total:
+                    with torch.cuda.device(dev):
+                        self._host[:total].copy_(packed[:total], non_blocking=True)
+                        self._event.record(torch.cuda.current_stream(dev))
+                        self._event.synchronize()
+                out = [(st, a, self._host_np[o:o + b - a]) for (st, a, b), o in zip(out, offs)]
+            else:
+                out = [(st, a, f.pcm[0, a:b]) for (st, a, b), f in zip(out, todo)]
+        self.followers = [f for f in self.followers if f._wired < len(f._st.schedule)]
+        return out
+
+
+def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best"):
+    """The pooled `stream_pcm16`: a `PcmPool` over a `stream.StreamPool` (`net.stream_pool()`) of the same model.
+    `add(st, peak=None)` takes `peak` as `stream_pcm16` does."""
+    return PcmPool(net, pool, model_sr, rate, res_type=res_type)
 
 
 class FrameCutter:

@@ -244,6 +244,61 @@ int mbv_chunks_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_f
 int mbv_decode_chunks(mbv_model *m, const mbv_chunk *chunks_host, int n, void *stream);
 int64_t mbv_decoder_runs(mbv_model *m);
 
+/* ---- pooled admission: the front half (text encoder, duration predictor, length regulation, flows) of many
+ * requests in one padded run (no reference counterpart: the reference service runs one request at a time,
+ * synthesis_module.py:141 taking the scales per request) ----------------
+ * What mbv_encode / mbv_synthesize take as one value per call — length_scale, noise_scale_w, noise_scale, given
+ * durations, max_len — comes per row, every row's noise is a block of the row's own shape, and each row's masked z,
+ * cut to the frames it keeps, lands in a tensor of its own.  In the default mode every such z is BITWISE the z of
+ * that utterance encoded and synthesised alone with the same noise (B = 1, T = its own length): the kernels in front
+ * of the decoder work below each row's length in units that do not depend on the padding, and the table-reading
+ * kernels run the scalar kernels' chains of operations.  With "splitk" (routes follow the launch size) the result is
+ * deterministic and within fp32 rounding of the stand-alone call; a predicted duration may then differ by one frame.
+ *
+ * mbv_admit_plan (host only): which requests may share a run.  Two text lengths share a class iff every conv in front
+ * of the flows, planned for either utterance alone, lands on the same side of the conv planner's one divide (today:
+ * T <= 256 the narrow kernel, beyond it the tiled ones); a class is cut into further runs only where B rows padded to
+ * the run's longest text would plan differently (2 GiB tensors) or exceed 65535 rows.  Runs are numbered in the order
+ * of their first request; run_of_request [n] (or NULL) receives each request's run.  "splitk": one class.  Returns
+ * the number of runs, -1 on a bad argument (n < 1, a length < 1).
+ *
+ * mbv_encode_rows: mbv_encode for the B rows of one run, ids [B, T] zero-padded, lengths[b] = rows[b].t_text.  The
+ * state the run leaves for its mbv_synthesize_rows is kept under `slot` (0 .. 63), so that several runs can be
+ * encoded, their lengths read back and their noise drawn before any is synthesised; slot 0 is the state a plain
+ * mbv_encode leaves, too.  rows_host is HOST memory and travels as kernel arguments (free it on return).  Rows with
+ * durations have them set as mbv_set_durations does (same range rules, same -1 marker); the others keep the predicted
+ * ones.  y_lengths_out as in mbv_encode: -1 flags a row (token id / sid / duration), read it before synthesising.
+ * Refused before any launch: t_text outside [1, T], noise_w missing on a model with the stochastic duration
+ * predictor, durations together with length_scale != 1, the option "conv_bf16" (there the flows' route follows the
+ * launch size), rows that mbv_admit_plan would not put into one run.
+ *
+ * mbv_synthesize_rows: length regulation + reverse flows of the run under `slot` (n = its B rows), t_frames >= every
+ * row's y_length, then ONE scatter launch: rows[b].z [inter, keep] = (z * y_mask)[b, :, :keep].  No decoder: the
+ * per-request z feed mbv_decode_chunks.  Refused before any launch: keep outside [1, t_frames], a noise_stride outside
+ * [1, t_frames] where noise_scale != 0, "conv_bf16", a run the fused WN layers do not take (option "wn_fused" off, or
+ * B * hidden * t_frames * 4 bytes >= 4 GiB).
+ *
+ * mbv_encoder_runs: passes through the text encoder made on this handle since mbv_create, by any entry. */
+typedef struct mbv_enc_row {
+  float length_scale, noise_scale_w;
+  const float *noise_w;          /* DEVICE [2, t_text], this row's own draw; NULL without the stochastic predictor */
+  const void *durations;         /* DEVICE [t_text] given frames per token, or NULL: the predicted ones */
+  int32_t durations_dtype;       /* 0 int32, 1 int64, 2 fp32 (as mbv_set_durations) */
+  int32_t t_text;                /* the row's text length = lengths[b] */
+} mbv_enc_row;
+typedef struct mbv_row {
+  const float *noise;            /* DEVICE [inter, noise_stride], this row's own prior draw (not read at noise_scale 0) */
+  int64_t noise_stride;          /* its row stride in floats: the row's y_length */
+  float noise_scale;
+  int32_t keep;                  /* frames of z kept: min(y_length, max_len) */
+  float *z;                      /* DEVICE [inter, keep], the request's own tensor */
+} mbv_row;
+int mbv_admit_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_text, int32_t *run_of_request);
+int mbv_encode_rows(mbv_model *m, int slot, const int64_t *ids, const int64_t *lengths, const int64_t *sid, int B, int T,
+                    const mbv_enc_row *rows_host, int64_t *y_lengths_out, void *stream);
+int mbv_synthesize_rows(mbv_model *m, int slot, int t_frames, const mbv_row *rows_host, int n, void *stream);
+int64_t mbv_encoder_runs(mbv_model *m);
+
 /* speaker embedding lookup: replaces `net.emb_g(sid)` (models.py:705).
  * out fp32 [B, gin] */
 int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, void *stream);
@@ -278,6 +333,8 @@ int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, v
  *                  (relative error of a product ~2^-16): ~1.9x faster decoder stage, waveform within 3e-6
  *                  RMS of the exact mode at batch 64 (bar 1e-4).  Any other value is refused. */
 int mbv_set_option(mbv_model *m, const char *name, int value);
+/* the current value of an integer option ("xpost_chunk_bytes" excepted), -1 for an unknown name */
+int mbv_get_option(mbv_model *m, const char *name);
 
 /* ---- stage timers -----------------------------------------------------------
  * replaces the `timings` dict (models.py:698-737): milliseconds of the five

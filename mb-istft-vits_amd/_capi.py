@@ -29,6 +29,7 @@ SYMBOLS = [
     "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
     "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
+    "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
 ]
 
 
@@ -65,6 +66,18 @@ class MbvPcmChunk(C.Structure):
                 ("in_avail", C.c_int64), ("out_first", C.c_int64), ("out_count", C.c_int64), ("peak", C.c_void_p),
                 ("pcm", C.c_void_p), ("pcm_capacity", C.c_int64), ("running_peak", C.c_void_p),
                 ("out_samples", C.c_void_p)]
+
+
+class MbvEncRow(C.Structure):
+    """mbv_enc_row of include/mbistft_vits.h (mbv_encode_rows)."""
+    _fields_ = [("length_scale", C.c_float), ("noise_scale_w", C.c_float), ("noise_w", C.c_void_p),
+                ("durations", C.c_void_p), ("durations_dtype", C.c_int32), ("t_text", C.c_int32)]
+
+
+class MbvRow(C.Structure):
+    """mbv_row of include/mbistft_vits.h (mbv_synthesize_rows)."""
+    _fields_ = [("noise", C.c_void_p), ("noise_stride", C.c_int64), ("noise_scale", C.c_float), ("keep", C.c_int32),
+                ("z", C.c_void_p)]
 
 
 class MbvAlignOutputs(C.Structure):
@@ -189,11 +202,13 @@ def lib():
     L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
-    # those four entries, the pooled decode's three and the pooled wire output's three may be absent there, and calling
-    # one then raises AttributeError.  Everything else, and the in-tree library always, must match the header.
+    # those four entries, the pooled decode's three, the pooled wire output's three and pooled admission's five may be
+    # absent there, and calling one then raises AttributeError.  Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
-                "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
+                "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs",
+                "mbv_get_option") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -210,6 +225,13 @@ def lib():
         L.mbv_resample_pcm16_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), i32, i32, i32, i32, vp, C.c_int64, vp]
         L.mbv_wire_runs.argtypes = [vp]
         L.mbv_wire_runs.restype = C.c_int64
+    if hasattr(L, "mbv_encode_rows") or not optional:
+        L.mbv_admit_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.mbv_encode_rows.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(MbvEncRow), vp, vp]
+        L.mbv_synthesize_rows.argtypes = [vp, i32, i32, C.POINTER(MbvRow), i32, vp]
+        L.mbv_encoder_runs.argtypes = [vp]
+        L.mbv_encoder_runs.restype = C.c_int64
+        L.mbv_get_option.argtypes = [vp, C.c_char_p]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

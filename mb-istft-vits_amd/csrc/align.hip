@@ -200,13 +200,22 @@ __global__ __launch_bounds__(64) void max_path_kernel(const float* __restrict__ 
 // count 0 frames and flag the utterance: y_len = 1, y_lengths = -1.
 //   dtype 0: int32, 1: int64, 2: float32
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void set_durations_kernel(const void* w, int dtype, const int* lens, float* w_ceil,
-                                                            int* cum, int* ylen32, int64_t* ylen64, const int* bad,
-                                                            int T) {
+// ROWS (pooled admission, kernels.h): row b reads its own tensor rows[b].dur [t_text] of rows[b].dur_dtype; a row
+// without one is left alone, predicted durations and all
+template <bool ROWS>
+__global__ __launch_bounds__(256) void set_durations_kernel(const void* w, int dtype, const AdmitEncRow* rows, const int* lens,
+                                                            float* w_ceil, int* cum, int* ylen32, int64_t* ylen64,
+                                                            const int* bad, int T) {
   __shared__ int scan[256];
   __shared__ int carry_s, over_s;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int len = lens[b];
+  int len = lens[b];
+  if (ROWS) {
+    w = rows[b].dur;
+    dtype = rows[b].dur_dtype;
+    if (!w) return;                                // uniform over the workgroup
+    if (len > rows[b].t_text) len = rows[b].t_text;    // never read past the row's own tensor
+  }
   if (tid == 0) { carry_s = 0; over_s = 0; }
   __syncthreads();
   for (int t0 = 0; t0 < T; t0 += 256) {
@@ -216,7 +225,7 @@ __global__ __launch_bounds__(256) void set_durations_kernel(const void* w, int d
       float wc = 0.f;
       bool ok = true;
       if (t < len) {
-        const int64_t i = (int64_t)b * T + t;
+        const int64_t i = ROWS ? (int64_t)t : (int64_t)b * T + t;
         if (dtype == 0) {
           const int v = ((const int*)w)[i];
           ok = v >= 0 && v < (1 << 20);
@@ -321,7 +330,12 @@ void launch_max_path(const float* value, const int* t_ys, const int* t_xs, int* 
 
 void launch_set_durations(const void* w, int dtype, const int* lens, float* w_ceil, int* cum, int* ylen32,
                           int64_t* ylen64, const int* bad, int B, int T, hipStream_t s) {
-  hipLaunchKernelGGL(set_durations_kernel, dim3(B), dim3(256), 0, s, w, dtype, lens, w_ceil, cum, ylen32, ylen64, bad, T);
+  hipLaunchKernelGGL(set_durations_kernel<false>, dim3(B), dim3(256), 0, s, w, dtype, nullptr, lens, w_ceil, cum, ylen32, ylen64, bad, T);
+}
+
+void launch_set_durations_rows(const AdmitEncRow* rows, const int* lens, float* w_ceil, int* cum, int* ylen32,
+                               int64_t* ylen64, const int* bad, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(set_durations_kernel<true>, dim3(B), dim3(256), 0, s, nullptr, 0, rows, lens, w_ceil, cum, ylen32, ylen64, bad, T);
 }
 
 void launch_align_status(const int* bad_x, const int* bad_y, const int* mas, int* status, float* w_f, const int* w_i,

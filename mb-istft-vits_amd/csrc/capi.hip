@@ -110,6 +110,7 @@ struct mbv_model {
   int ragged_scanned = 0, ragged_splitk = -1;
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
+  int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
   // state of the last encode
@@ -119,6 +120,12 @@ struct mbv_model {
   int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr;
   int* bad32 = nullptr;         // per-utterance flags of the last encode (invalid id / length / sid)
   std::map<std::string, StageRef> stages;
+  // pooled admission: the encode state of one padded run, kept until its mbv_synthesize_rows (mbv_encode_rows);
+  // slot 0 lives in scrA like a plain encode, every further slot in a buffer of its own
+  struct EncSlot { char* scr = nullptr; size_t bytes = 0; bool valid = false; int B = 0, T = 0; bool has_g = false;
+                   float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
+                   int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr, *bad32 = nullptr; };
+  std::vector<EncSlot> slots;
 
   static constexpr int kEvRing = 8;
   hipEvent_t evr[kEvRing][7]{};    // stage events of the last kEvRing encode (+ synthesize) calls
@@ -1805,6 +1812,18 @@ int mbv_set_option(mbv_model* m, const char* name, int value) {
   return m->fail("mbv_set_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, xpost_chunk_bytes, dec_streams, trim, conv_bf16)", name);
 }
 
+int mbv_get_option(mbv_model* m, const char* name) {
+  if (!m || !name) return -1;
+  if (!strcmp(name, "splitk")) return m->splitk;
+  if (!strcmp(name, "istft_exact")) return m->exact_math;
+  if (!strcmp(name, "wn_fused")) return m->wn_fused;
+  if (!strcmp(name, "dec_streams")) return m->dec_streams;
+  if (!strcmp(name, "trim")) return m->trim;
+  if (!strcmp(name, "conv_bf16")) return m->conv_bf16;
+  m->fail("mbv_get_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, dec_streams, trim, conv_bf16)", name);
+  return -1;
+}
+
 void mbv_destroy(mbv_model* m) {
   if (!m) return;
   DeviceGuard dev_guard_(m->cfg.device);
@@ -1814,6 +1833,8 @@ void mbv_destroy(mbv_model* m) {
   if (m->conv_cnt) (void)hipFree(m->conv_cnt);
   if (m->scrA) (void)hipFree(m->scrA);
   if (m->scrB) (void)hipFree(m->scrB);
+  for (auto& sl : m->slots)
+    if (sl.scr) (void)hipFree(sl.scr);
   if (m->user_tab) (void)hipFree(m->user_tab);
   if (m->peak_buf) (void)hipFree(m->peak_buf);
   for (auto& kv : m->resample_banks) (void)hipFree(kv.second.d);
@@ -1931,12 +1952,14 @@ struct ExactScope {
 struct TextEncBufs { float *x, *x1, *qkv, *att, *y, *ffn; };
 // (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
 // size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
-bool text_fuse_ln(const mbv_model* m, int B, int T) { return T <= 256 && !(m->splitk && (long)B * ((T + 15) / 16) < 128); }
+bool text_fuse_ln_at(int splitk, int B, int T) { return T <= 256 && !(splitk && (long)B * ((T + 15) / 16) < 128); }
+bool text_fuse_ln(const mbv_model* m, int B, int T) { return text_fuse_ln_at(m->splitk, B, T); }
 void run_text_encoder(mbv_model* m, const int64_t* ids, const int64_t* lengths, const TextEncBufs& e, int* bad, int B,
                       int T, hipStream_t s) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels;
   float *x = e.x, *x1 = e.x1, *qkv = e.qkv, *att = e.att, *y = e.y, *ffn = e.ffn;
+  ++m->encoder_runs;
   launch_embed(ids, lengths, m->W(m->emb.off), x, m->lens32, bad, B, T, H, c.n_vocab, s);
   const int64_t bsH = (int64_t)H * T;
   const bool fuse_ln = text_fuse_ln(m, B, T);
@@ -1986,14 +2009,14 @@ void run_text_encoder(mbv_model* m, const int64_t* ids, const int64_t* lengths, 
     launch_conv1d(a, s);
   }
 }
-}  // namespace
-
-int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
-               int T, float length_scale, const float* noise_w, float noise_scale_w,
-               int64_t* y_lengths_out, void* stream) {
-  if (!m) return 1;
+// mbv_encode; rows_host != nullptr: mbv_encode_rows — the per-call scalars and the SDP noise come from the table,
+// and rows with given durations have them set in the same call (the launches of mbv_set_durations)
+int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
+           int T, float length_scale, const float* noise_w, float noise_scale_w, const mbv_enc_row* rows_host,
+           int64_t* y_lengths_out, void* stream) {
+  const char* const who = rows_host ? "mbv_encode_rows" : "mbv_encode";
   if (!m->finalized) return m->fail("weights not finalized (call mbv_finalize_weights)");
-  if (!ids || !lengths || B <= 0 || T <= 0) return m->fail("mbv_encode: bad arguments");
+  if (!ids || !lengths || B <= 0 || T <= 0) return m->fail("%s: bad arguments", who);
   const mbv_config& c = m->cfg;
   if (c.n_speakers > 0 && !sid) return m->fail("sid is required when n_speakers > 0 (models.py:704-705)");
   if (c.n_speakers > 0 && !m->emb_g.present) return m->fail("n_speakers == 1: the reference has no emb_g either");
@@ -2006,6 +2029,7 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
   const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
   const size_t BT = (size_t)B * T;
   size_t need = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2 * kDpFilter + 4 + 5 * H + 32 + 2) + (size_t)B * (gin + H + 12)) * 4 + 96 * 256;
+  if (rows_host) need += (size_t)B * sizeof(AdmitEncRow);
   if (ensure(m, &m->scrA, &m->scrA_bytes, need)) return 1;
   Bump sc{m->scrA, m->scrA_bytes};
   float* x = sc.take<float>(BT * H);
@@ -2025,6 +2049,21 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
   int* bad = m->bad32 = sc.take<int>(B);
   m->gvec = sc.take<float>((size_t)B * (gin ? gin : 1));
   float* dpc = sc.take<float>((size_t)B * H);
+  AdmitEncRow* rows = nullptr;
+  bool any_given = false;
+  if (rows_host) {
+    rows = sc.take<AdmitEncRow>(B);
+    for (int f = 0; f < B; f += kAdmitChunk) {
+      AdmitEncRowsArg r{};
+      const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
+      for (int i = 0; i < nn; ++i) {
+        const mbv_enc_row& k = rows_host[f + i];
+        r.row[i] = AdmitEncRow{k.length_scale, k.noise_scale_w, k.noise_w, k.durations, k.durations_dtype, k.t_text};
+        any_given = any_given || k.durations;
+      }
+      launch_admit_enc_rows(r, nn, f, rows, (hipStream_t)stream);
+    }
+  }
   m->stages.clear();
 
   ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
@@ -2064,7 +2103,8 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
       a.out_lens = m->lens32;
       launch_conv1d(a, s);
     }
-    launch_sdp_noise(noise_w, noise_scale_w, zf, (int64_t)BT * 2, s);
+    if (rows) launch_sdp_noise_rows(rows, zf, B, T, s);
+    else launch_sdp_noise(noise_w, noise_scale_w, zf, (int64_t)BT * 2, s);
     for (int k = 0; k < 3; ++k) {
       const auto& f = m->sdp.flow[k];
       launch_sdp_pre(zf, 1, m->W(f.pre_w.off), m->W(f.pre_b.off), cond, hh, B, H, T, s);   // x0 = z[:, 1] after the Flip
@@ -2077,8 +2117,10 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
       launch_sdp_spline(h29, zf, m->lens32, B, H, T, m->sdp.edge_const, s);
     }
     launch_sdp_logw(zf, m->W(m->sdp.m.off), m->W(m->sdp.logs.off), m->lens32, h29, B, T, s);
-    launch_durations(h29, nullptr, nullptr, m->lens32, length_scale, m->logw, m->w_ceil, m->cum,
-                     m->ylen32, y_lengths_out, bad, B, 1, T, s);
+    if (rows) launch_durations_rows(h29, nullptr, nullptr, m->lens32, rows, m->logw, m->w_ceil, m->cum, m->ylen32,
+                                    y_lengths_out, bad, B, 1, T, s);
+    else launch_durations(h29, nullptr, nullptr, m->lens32, length_scale, m->logw, m->w_ceil, m->cum,
+                          m->ylen32, y_lengths_out, bad, B, 1, T, s);
     m->stages["sdp_cond"] = {cond, (int64_t)BT * H};
     m->stages["sdp_z"] = {zf, (int64_t)BT * 2};
   } else {
@@ -2109,9 +2151,12 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
       launch_layernorm(h1, nullptr, m->W(m->dp_g2.off), m->W(m->dp_b2.off), h2, B, kDpFilter, T, 1, nullptr, s);
     }
   }
-  launch_durations(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), m->lens32, length_scale, m->logw,
-                   m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
+  if (rows) launch_durations_rows(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), m->lens32, rows, m->logw,
+                                  m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
+  else launch_durations(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), m->lens32, length_scale, m->logw,
+                        m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
   }
+  if (any_given) launch_set_durations_rows(rows, m->lens32, m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, T, s);
   HIPCHK(m, hipEventRecord(m->ev[2], s));
   HIPCHK(m, hipGetLastError());
   m->B = B; m->T = T; m->encoded = true; m->ev_a = true; m->ev_b = false;
@@ -2121,6 +2166,14 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
   m->stages["logw"] = {m->logw, (int64_t)BT};
   m->stages["w_ceil"] = {m->w_ceil, (int64_t)BT};
   return 0;
+}
+}  // namespace
+
+int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
+               int T, float length_scale, const float* noise_w, float noise_scale_w,
+               int64_t* y_lengths_out, void* stream) {
+  if (!m) return 1;
+  return encode(m, ids, lengths, sid, B, T, length_scale, noise_w, noise_scale_w, nullptr, y_lengths_out, stream);
 }
 
 }  // extern "C"
@@ -2192,6 +2245,88 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   m->evr_b[m->ticket % mbv_model::kEvRing] = true;
   return 0;
 }
+
+// ------------------------------------------------------------------ pooled admission
+// Which side of the planner's one arithmetic divide — the narrow kernel or a tiled one — every conv in front of the
+// flows takes when B utterances padded to T tokens are encoded in one run (the shapes run_text_encoder and encode
+// build; data pointers are only ever tested against null), and whether the conv + LayerNorm pairs run fused.
+void front_signature(const mbv_config& c, int splitk, int B, int T, std::vector<char>* sig) {
+  static const float kSome = 0.f;                   // "a tensor is given"
+  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels;
+  auto conv = [&](int Cin, int M, int K) {
+    ConvArgs a{};
+    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = K; a.dil = 1; a.pad_left = (K - 1) / 2;
+    a.Tin = T; a.x_rstride = T; a.x_bstride = (int64_t)Cin * T;
+    a.T = T; a.y_bstride = (int64_t)M * T; a.epi = EPI_STORE; a.in_slope = 1.f; a.out_scale = 1.f; a.B = B;
+    a.splitk = splitk;
+    return a;
+  };
+  sig->clear();
+  const bool fuse = text_fuse_ln_at(splitk, B, T);
+  auto plain = [&](const ConvArgs& a) {
+    const int r = conv1d_plan(a, false).route;
+    sig->push_back(r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH);
+  };
+  auto with_ln = [&](ConvArgs a, bool res) {       // fused with its LayerNorm where encode fuses, else a plain conv
+    ConvArgs l = a;
+    l.epi = EPI_LN; l.ln_gamma = l.ln_beta = &kSome;
+    if (res) { l.res = &kSome; l.res_bstride = a.y_bstride; }
+    const bool fused = fuse && conv1d_narrow_supported(l);
+    sig->push_back(fused);
+    if (!fused) plain(a);
+  };
+  plain(conv(H, 3 * H, 1));                         // attention: qkv, conv_o + LayerNorm
+  with_ln(conv(H, H, 1), true);
+  plain(conv(H, Fc, c.kernel_size));                // FFN
+  with_ln(conv(Fc, H, c.kernel_size), true);
+  plain(conv(H, 2 * I, 1));                         // enc_p.proj
+  if (c.use_sdp) {
+    plain(conv(H, H, 1));                           // dp.pre / dp.proj / the DDSConv 1x1 convs
+    plain(conv(H, 29, 1));                          // ConvFlow.proj
+  } else {
+    with_ln(conv(H, kDpFilter, 3), false);
+    with_ln(conv(kDpFilter, kDpFilter, 3), false);
+  }
+}
+
+// Runs of one pooled admission for requests of t_text[i] tokens: requests share a front-half run iff their texts,
+// each encoded alone, put every conv on the same side of the divide (front_signature at B = 1) — and a run is cut
+// where its own launches, B rows padded to its longest text, would leave that side (tensors beyond the narrow
+// kernel's 32-bit offsets) or the grid's 65535 rows.  Split-K mode: nothing is bitwise across launch sizes anyway,
+// one class.  Returns the number of runs, -1 on a bad argument.
+int admit_plan(const mbv_config& c, int splitk, int n, const int32_t* t_text, int32_t* run_of_request) {
+  if (n <= 0 || !t_text) return -1;
+  for (int i = 0; i < n; ++i)
+    if (t_text[i] < 1) return -1;
+  struct Run { std::vector<char> sig; int B = 0, T = 0; bool open = true; };
+  std::vector<Run> runs;
+  std::map<int, std::vector<char>> sig_of;          // text length -> its stand-alone signature
+  std::vector<char> sig;
+  for (int i = 0; i < n; ++i) {
+    const int T = t_text[i];
+    auto it = sig_of.find(T);
+    if (it == sig_of.end()) {
+      if (splitk) sig.clear(); else front_signature(c, 0, 1, T, &sig);
+      it = sig_of.emplace(T, sig).first;
+    }
+    int r = -1;
+    for (size_t k = 0; k < runs.size() && r < 0; ++k) {
+      if (!runs[k].open || runs[k].sig != it->second) continue;
+      const int Tn = T > runs[k].T ? T : runs[k].T;
+      bool fits = runs[k].B + 1 <= 65535;
+      if (fits && !splitk) { front_signature(c, 0, runs[k].B + 1, Tn, &sig); fits = sig == runs[k].sig; }
+      if (fits) { r = (int)k; runs[k].T = Tn; ++runs[k].B; }
+      else runs[k].open = false;                    // full: later requests of the class start a new run
+    }
+    if (r < 0) {
+      Run nr; nr.sig = it->second; nr.B = 1; nr.T = T;
+      runs.push_back(nr);
+      r = (int)runs.size() - 1;
+    }
+    if (run_of_request) run_of_request[i] = r;
+  }
+  return (int)runs.size();
+}
 }  // namespace
 
 extern "C" {
@@ -2207,6 +2342,109 @@ int mbv_synthesize_ragged(mbv_model* m, int t_frames, const float* noise, float 
   if (!m) return 1;
   if (!y_lengths_host) return m->fail("mbv_synthesize_ragged: y_lengths_host is NULL");
   return synthesize(m, t_frames, noise, noise_scale, max_len, outs, y_lengths_host, stream);
+}
+
+int mbv_admit_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_text, int32_t* run_of_request) {
+  if (!cfg) return -1;
+  return admit_plan(*cfg, splitk != 0, n, t_text, run_of_request);
+}
+
+int64_t mbv_encoder_runs(mbv_model* m) { return m ? m->encoder_runs : -1; }
+
+int mbv_encode_rows(mbv_model* m, int slot, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B, int T,
+                    const mbv_enc_row* rows_host, int64_t* y_lengths_out, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_encode_rows";
+  if (!rows_host || !y_lengths_out || B <= 0 || T <= 0) return m->fail("%s: bad arguments", who);
+  if (slot < 0 || slot >= 64) return m->fail("%s: slot must be in [0, 64)", who);
+  if (B > 65535) return m->fail("%s: at most 65535 rows a run (mbv_admit_plan cuts there)", who);
+  if (m->conv_bf16) return m->fail("%s: pooled admission is not built for the \"conv_bf16\" mode", who);
+  for (int i = 0; i < B; ++i) {
+    const mbv_enc_row& k = rows_host[i];
+    if (k.t_text < 1 || k.t_text > T) return m->fail("%s: row %d: t_text %d outside [1, %d]", who, i, k.t_text, T);
+    if (m->cfg.use_sdp && !k.noise_w) return m->fail("%s: row %d: noise_w is required with the stochastic duration predictor", who, i);
+    if (k.durations && (k.durations_dtype < 0 || k.durations_dtype > 2))
+      return m->fail("%s: row %d: durations_dtype must be 0 (int32), 1 (int64) or 2 (fp32)", who, i);
+    if (k.durations && k.length_scale != 1.f)
+      return m->fail("%s: row %d: given durations are used as they are: length_scale must be 1", who, i);
+  }
+  {   // the rows must be ONE run of the plan: a second class in the launch would move some row to another route
+    std::vector<int32_t> tt(B);
+    for (int i = 0; i < B; ++i) tt[i] = rows_host[i].t_text;
+    if (admit_plan(m->cfg, m->splitk, B, tt.data(), nullptr) != 1)
+      return m->fail("%s: the rows belong to more than one run of mbv_admit_plan", who);
+  }
+  if ((size_t)slot >= m->slots.size()) m->slots.resize(slot + 1);
+  mbv_model::EncSlot& sl = m->slots[slot];
+  sl.valid = false;
+  if (slot > 0) { std::swap(m->scrA, sl.scr); std::swap(m->scrA_bytes, sl.bytes); }
+  const int rc = encode(m, ids, lengths, sid, B, T, 1.f, nullptr, 1.f, rows_host, y_lengths_out, stream);
+  if (slot > 0) { std::swap(m->scrA, sl.scr); std::swap(m->scrA_bytes, sl.bytes); }
+  if (rc) { m->encoded = false; return rc; }
+  sl.valid = true; sl.B = m->B; sl.T = m->T; sl.has_g = m->has_g;
+  sl.x_enc = m->x_enc; sl.stats = m->stats; sl.logw = m->logw; sl.w_ceil = m->w_ceil; sl.gvec = m->gvec;
+  sl.lens32 = m->lens32; sl.cum = m->cum; sl.ylen32 = m->ylen32; sl.bad32 = m->bad32;
+  return 0;
+}
+
+int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_synthesize_rows";
+  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
+    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
+  const mbv_model::EncSlot& sl = m->slots[slot];
+  if (!rows_host || n != sl.B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, sl.B, n);
+  if (t_frames <= 0) return m->fail("t_frames must be > 0");
+  if (m->conv_bf16) return m->fail("%s: pooled admission is not built for the \"conv_bf16\" mode", who);
+  const mbv_config& c = m->cfg;
+  const int B = sl.B, T = sl.T, Tp = t_frames, H = c.hidden_channels, I = c.inter_channels;
+  int max_keep = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_row& k = rows_host[i];
+    if (!k.z || k.keep < 1 || k.keep > Tp) return m->fail("%s: row %d: z missing or keep %d outside [1, %d]", who, i, k.keep, Tp);
+    if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < 1 || k.noise_stride > Tp))
+      return m->fail("%s: row %d: noise missing or noise_stride outside [1, %d]", who, i, Tp);
+    if (k.keep > max_keep) max_keep = k.keep;
+  }
+  // the flows must take, for the whole run, the route every utterance takes alone: the fused WN layers, which work
+  // on 16-frame half-units below each row's own length (the two-launch layers route on T')
+  for (int f = 0; f < kNFlows; ++f)
+    if (!wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, Tp) || !wn_fused_fits(B, I, Tp))
+      return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
+                     "do not cover, or tensors beyond their 32-bit offsets): admit fewer requests at a time", who, B, Tp);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t BTp = (size_t)B * Tp;
+  const size_t need = (BTp * (I + 3 * H) + (size_t)B * (2 * H * kFlowLayers + 2)) * 4 + wn_units_ints(B, Tp) * 4 +
+                      (size_t)B * sizeof(AdmitSynRow) + 64 * 256;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
+  // the run becomes the handle's "last encode", as if mbv_encode had just made it
+  m->B = sl.B; m->T = sl.T; m->has_g = sl.has_g; m->encoded = true;
+  m->x_enc = sl.x_enc; m->stats = sl.stats; m->logw = sl.logw; m->w_ceil = sl.w_ceil; m->gvec = sl.gvec;
+  m->lens32 = sl.lens32; m->cum = sl.cum; m->ylen32 = sl.ylen32; m->bad32 = sl.bad32;
+  Bump sc{m->scrB, m->scrB_bytes};
+  float* z = sc.take<float>(BTp * I);
+  float* hbuf = sc.take<float>(BTp * H);
+  float* acts = sc.take<float>(BTp * H);
+  float* skip = sc.take<float>(BTp * H);
+  float* gc = sc.take<float>((size_t)B * 2 * H * kFlowLayers);
+  int* ustart = sc.take<int>(wn_units_ints(B, Tp));
+  AdmitSynRow* rows = sc.take<AdmitSynRow>(B);
+  for (int f = 0; f < B; f += kAdmitChunk) {
+    AdmitSynRowsArg r{};
+    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
+    for (int i = 0; i < nn; ++i) {
+      const mbv_row& k = rows_host[f + i];
+      r.row[i] = AdmitSynRow{k.noise, k.noise_stride, k.noise_scale, k.keep, k.z};
+    }
+    launch_admit_syn_rows(r, nn, f, rows, s);
+  }
+  launch_expand_rows(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, rows, z, B, I, T, Tp, s);
+  for (int f = kNFlows - 1; f >= 0; --f)
+    run_coupling(m, f, true, z, m->has_g ? m->gvec : nullptr, hbuf, acts, skip, gc, ustart, m->ylen32, B, Tp, s);
+  launch_scatter_z_rows(z, m->ylen32, rows, B, I, Tp, max_keep, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
 }
 
 int mbv_ragged_classes(const mbv_config* cfg, int splitk, int t_max, int32_t* first, int capacity) {

@@ -218,6 +218,45 @@ void launch_expand(const float* m_t, const float* logs_t, int64_t src_bstride, c
                    float* logs_p, float* z_p, float* z, float* attn, float* y_mask, int B, int C,
                    int T, int Tp, hipStream_t s);
 
+// ---------------------------------------------------------------- pooled admission: table-reading variants
+// One padded front-half run for many requests (capi.hip mbv_encode_rows / mbv_synthesize_rows): what the scalar
+// launches above take as one value per call comes from a device table with one row per utterance.  Every variant
+// is the scalar kernel's own body (one template), so an element's chain of operations is the scalar launch's.
+struct AdmitEncRow {
+  float length_scale, noise_scale_w;
+  const float* noise_w;        // this row's SDP noise [2, t_text], packed; null without the SDP
+  const void* dur;             // given durations [t_text] of dtype dur_dtype, or null: keep the predicted ones
+  int dur_dtype, t_text;
+};
+struct AdmitSynRow {
+  const float* noise;          // this row's prior noise [C, noise_stride]
+  int64_t noise_stride;
+  float noise_scale;           // 0: zp = m, the noise is not read (the scalar path's null-noise branch)
+  int keep;                    // frames of z the request keeps (1 .. its y_len)
+  float* z;                    // the request's own [C, keep]
+};
+// n table rows by value from the host (kernel arguments) -> dst[first + i]
+constexpr int kAdmitChunk = 64;
+struct AdmitEncRowsArg { AdmitEncRow row[kAdmitChunk]; };
+struct AdmitSynRowsArg { AdmitSynRow row[kAdmitChunk]; };
+void launch_admit_enc_rows(const AdmitEncRowsArg& r, int n, int first, AdmitEncRow* dst, hipStream_t s);
+void launch_admit_syn_rows(const AdmitSynRowsArg& r, int n, int first, AdmitSynRow* dst, hipStream_t s);
+// launch_durations with length_scale = rows[b].length_scale
+void launch_durations_rows(const float* h, const float* w, const float* b, const int* lens, const AdmitEncRow* rows,
+                           float* logw, float* w_ceil, int* cum, int* ylen32, int64_t* ylen64, const int* bad, int B,
+                           int C, int T, hipStream_t s);
+// launch_sdp_noise on z [B, 2, T]: row b from its own packed [2, t_text] block, zeros behind t_text
+void launch_sdp_noise_rows(const AdmitEncRow* rows, float* z, int B, int T, hipStream_t s);
+// launch_set_durations for the rows that carry durations (their own [t_text] tensor); the others keep everything
+void launch_set_durations_rows(const AdmitEncRow* rows, const int* lens, float* w_ceil, int* cum, int* ylen32,
+                               int64_t* ylen64, const int* bad, int B, int T, hipStream_t s);
+// launch_expand writing z only: row b reads noise at row stride rows[b].noise_stride (frames below it only)
+void launch_expand_rows(const float* m_t, const float* logs_t, int64_t src_bstride, const int* cum, const int* ylen,
+                        const AdmitSynRow* rows, float* z, int B, int C, int T, int Tp, hipStream_t s);
+// rows[b].z[c, t] = z[b, c, t] * (t < ylen[b]) for t < rows[b].keep: every request's masked, truncated z in one launch
+void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* rows, int B, int C, int Tp, int max_keep,
+                           hipStream_t s);
+
 // ---------------------------------------------------------------- speaker conditioning
 // out[b][co] = bias[co] + sum_ci W[co][ci] * g[b][ci]   (g = table[sid[b]] if sid)
 void launch_cond_gemv(const float* g, const float* table, const int64_t* sid, const float* W,

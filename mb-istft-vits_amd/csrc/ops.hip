@@ -145,15 +145,18 @@ void launch_layernorm(const float* a, const float* r, const float* gamma, const 
 // ---------------------------------------------------------------------------
 constexpr float kMaxTokenFrames = 1048576.f;     // 2^20
 constexpr int kMaxTotalFrames = 1 << 30;
+// ROWS: length_scale = rows[b].length_scale (pooled admission, kernels.h); else the call's scalar
+template <bool ROWS>
 __global__ __launch_bounds__(256) void durations_kernel(const float* h, const float* w,
                                                         const float* bias, const int* lens,
-                                                        float length_scale, float* logw,
+                                                        float length_scale, const AdmitEncRow* rows, float* logw,
                                                         float* w_ceil, int* cum, int* ylen32,
                                                         int64_t* ylen64, const int* bad, int C, int T) {
   __shared__ int scan[256];
   __shared__ int carry_s, over_s;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int len = lens[b];
+  if (ROWS) length_scale = rows[b].length_scale;
   if (tid == 0) { carry_s = 0; over_s = 0; }
   __syncthreads();
   for (int t0 = 0; t0 < T; t0 += 256) {
@@ -215,8 +218,15 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* h, const fl
 void launch_durations(const float* h, const float* w, const float* b, const int* lens,
                       float length_scale, float* logw, float* w_ceil, int* cum, int* ylen32,
                       int64_t* ylen64, const int* bad, int B, int C, int T, hipStream_t s) {
-  hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, s, h, w, b, lens, length_scale, logw,
+  hipLaunchKernelGGL(durations_kernel<false>, dim3(B), dim3(256), 0, s, h, w, b, lens, length_scale, nullptr, logw,
                      w_ceil, cum, ylen32, ylen64, bad, C, T);
+}
+
+void launch_durations_rows(const float* h, const float* w, const float* b, const int* lens, const AdmitEncRow* rows,
+                           float* logw, float* w_ceil, int* cum, int* ylen32, int64_t* ylen64, const int* bad, int B,
+                           int C, int T, hipStream_t s) {
+  hipLaunchKernelGGL(durations_kernel<true>, dim3(B), dim3(256), 0, s, h, w, b, lens, 0.f, rows, logw, w_ceil, cum,
+                     ylen32, ylen64, bad, C, T);
 }
 
 // ---------------------------------------------------------------------------
@@ -226,16 +236,26 @@ void launch_durations(const float* h, const float* w, const float* b, const int*
 // noise * exp(logs_p) * noise_scale), z (copy of z_p: the flows run in place),
 // and optionally the dense attn path and y_mask.
 // ---------------------------------------------------------------------------
+// ROWS (pooled admission, kernels.h): row b takes noise_scale and its noise block [C, noise_stride] from rows[b];
+// frames at and past noise_stride (behind the row's own T') read no noise — they are masked to 0 in z
+template <bool ROWS>
 __global__ __launch_bounds__(256) void expand_kernel(const float* m_t, const float* logs_t,
                                                      int64_t src_bstride, const int* cum,
                                                      const int* ylen,
-                                                     const float* noise, float noise_scale,
+                                                     const float* noise, float noise_scale, const AdmitSynRow* rows,
                                                      float* m_p, float* logs_p, float* z_p, float* z,
                                                      float* y_mask, int C, int T, int Tp) {
   const int b = blockIdx.y;
   const int tp = blockIdx.x * blockDim.x + threadIdx.x;
   if (tp >= Tp) return;
   const int yl = ylen[b];
+  int64_t n_stride = Tp;
+  if (ROWS) {
+    const AdmitSynRow r = rows[b];
+    noise_scale = r.noise_scale;
+    n_stride = r.noise_stride;
+    noise = (noise_scale != 0.f && tp < n_stride) ? r.noise : nullptr;
+  }
   const int* cb = cum + (int64_t)b * T;
   int j = -1;
   if (tp < yl) {
@@ -256,7 +276,7 @@ __global__ __launch_bounds__(256) void expand_kernel(const float* m_t, const flo
       lg = logs_t[(int64_t)b * src_bstride + (int64_t)c * T + j];
     }
     float zp = m;
-    if (noise) zp = m + noise[o] * expf(lg) * noise_scale;
+    if (noise) zp = m + noise[ROWS ? (int64_t)c * n_stride + tp : o] * expf(lg) * noise_scale;
     if (m_p) m_p[o] = m;
     if (logs_p) logs_p[o] = lg;
     if (z_p) z_p[o] = zp;
@@ -280,12 +300,49 @@ void launch_expand(const float* m_t, const float* logs_t, int64_t src_bstride, c
                    float* logs_p, float* z_p, float* z, float* attn, float* y_mask, int B, int C,
                    int T, int Tp, hipStream_t s) {
   dim3 grid((Tp + 255) / 256, B, (C + 15) / 16);
-  hipLaunchKernelGGL(expand_kernel, grid, dim3(256), 0, s, m_t, logs_t, src_bstride, cum, ylen, noise,
-                     noise_scale, m_p, logs_p, z_p, z, y_mask, C, T, Tp);
+  hipLaunchKernelGGL(expand_kernel<false>, grid, dim3(256), 0, s, m_t, logs_t, src_bstride, cum, ylen, noise,
+                     noise_scale, nullptr, m_p, logs_p, z_p, z, y_mask, C, T, Tp);
   if (attn) {
     dim3 g2((T + 255) / 256, Tp, B);
     hipLaunchKernelGGL(attn_path_kernel, g2, dim3(256), 0, s, cum, ylen, attn, T, Tp);
   }
+}
+
+void launch_expand_rows(const float* m_t, const float* logs_t, int64_t src_bstride, const int* cum, const int* ylen,
+                        const AdmitSynRow* rows, float* z, int B, int C, int T, int Tp, hipStream_t s) {
+  dim3 grid((Tp + 255) / 256, B, (C + 15) / 16);
+  hipLaunchKernelGGL(expand_kernel<true>, grid, dim3(256), 0, s, m_t, logs_t, src_bstride, cum, ylen, nullptr, 0.f,
+                     rows, nullptr, nullptr, nullptr, z, nullptr, C, T, Tp);
+}
+
+// Pooled admission: what N `(z * y_mask)[:, :, :keep].contiguous()` chains of one-utterance calls do, for the rows of
+// one padded run, each into its request's own tensor.
+__global__ void scatter_z_rows_kernel(const float* z, const int* ylen, const AdmitSynRow* rows, int C, int Tp) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const AdmitSynRow r = rows[b];
+  if (t >= r.keep) return;
+  r.z[(int64_t)c * r.keep + t] = z[((int64_t)b * C + c) * Tp + t] * (t < ylen[b] ? 1.f : 0.f);
+}
+
+void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* rows, int B, int C, int Tp, int max_keep,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(scatter_z_rows_kernel, dim3((max_keep + 255) / 256, C, B), dim3(256), 0, s, z, ylen, rows, C, Tp);
+}
+
+__global__ void admit_enc_rows_kernel(const AdmitEncRowsArg r, int n, int first, AdmitEncRow* dst) {
+  const int i = threadIdx.x;
+  if (i < n) dst[first + i] = r.row[i];
+}
+__global__ void admit_syn_rows_kernel(const AdmitSynRowsArg r, int n, int first, AdmitSynRow* dst) {
+  const int i = threadIdx.x;
+  if (i < n) dst[first + i] = r.row[i];
+}
+void launch_admit_enc_rows(const AdmitEncRowsArg& r, int n, int first, AdmitEncRow* dst, hipStream_t s) {
+  hipLaunchKernelGGL(admit_enc_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst);
+}
+void launch_admit_syn_rows(const AdmitSynRowsArg& r, int n, int first, AdmitSynRow* dst, hipStream_t s) {
+  hipLaunchKernelGGL(admit_syn_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst);
 }
 
 // ---------------------------------------------------------------------------

@@ -203,6 +203,16 @@ __global__ void sdp_noise_kernel(const float* noise, float scale, float* z, int6
   if (i < n) z[i] = noise ? noise[i] * scale : 0.f;
 }
 
+// pooled admission: row b of z [B, 2, T] from its own packed [2, t_text] noise and its own scale (kernels.h)
+__global__ void sdp_noise_rows_kernel(const AdmitEncRow* rows, float* z, int T) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * T) return;
+  const AdmitEncRow r = rows[b];
+  const int ch = i / T, t = i - ch * T;
+  z[(int64_t)b * 2 * T + i] = (r.noise_w && t < r.t_text) ? r.noise_w[(int64_t)ch * r.t_text + t] * r.noise_scale_w : 0.f;
+}
+
 __global__ void chan_add_kernel(float* x, const float* v, int C, int T) {
   const int b = blockIdx.z, c = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < T) x[((int64_t)b * C + c) * T + t] += v[b * C + c];
@@ -246,6 +256,10 @@ void launch_sdp_logw(const float* z, const float* m, const float* logs, const in
 void launch_sdp_noise(const float* noise, float scale, float* z, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(sdp_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, noise,
                      scale, z, n);
+}
+
+void launch_sdp_noise_rows(const AdmitEncRow* rows, float* z, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(sdp_noise_rows_kernel, dim3((2 * T + 255) / 256, B), dim3(256), 0, s, rows, z, T);
 }
 
 }  // namespace mbv

@@ -21,6 +21,84 @@ from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
 # librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
 RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
 
+def _durations_code(durations):
+    """Given durations -> (tensor of a dtype mbv_set_durations reads, its dtype code): int32 0, int64 1, fp32 2."""
+    if durations.dtype == torch.int32:
+        return durations, 0
+    if durations.dtype == torch.int64:
+        return durations, 1
+    if durations.dtype.is_floating_point:
+        return durations.to(torch.float32), 2
+    return durations.to(torch.int64), 1
+
+
+class Request:
+    """One utterance of a pooled admission (`SynthesizerTrn.infer_streams`, `StreamPool.admit`, `PcmPool.admit`): the
+    arguments one `infer_stream` call takes, for one text.
+
+      x                  1-D token ids (tensor on either device, or a sequence of ints); at least one
+      sid                speaker id (an int; required by a multi-speaker model), or None
+      noise_scale, length_scale, noise_scale_w, max_len       as `infer`
+      chunk_frames, max_chunk_frames                          as `dec_stream`
+      durations          frames per token, [T_text] (or [1, T_text] / [1, 1, T_text]), as `infer(durations=)`:
+                         needs length_scale == 1
+    Everything that can be checked without the model is checked here (ValueError / TypeError)."""
+
+    __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
+                 "max_chunk_frames", "durations", "durations_dtype")
+
+    def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
+                 chunk_frames=32, max_chunk_frames=256, durations=None):
+        if not torch.is_tensor(x):
+            x = torch.as_tensor(x)
+        if x.dim() != 1:
+            raise ValueError("Request: x must be 1-D token ids (one utterance), got shape %s" % (tuple(x.shape),))
+        if x.numel() < 1:
+            raise ValueError("Request: empty text")
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise TypeError("Request: x must hold integer token ids, got %s" % x.dtype)
+        self.x = x.to(torch.int64)
+        if sid is not None:
+            if torch.is_tensor(sid):
+                if sid.numel() != 1:
+                    raise ValueError("Request: sid must be one speaker id")
+                sid = sid.reshape(()).item()
+            if isinstance(sid, bool) or int(sid) != sid:
+                raise TypeError("Request: sid must be an integer")
+            sid = int(sid)
+        self.sid = sid
+        self.noise_scale, self.length_scale = float(noise_scale), float(length_scale)
+        self.noise_scale_w = float(noise_scale_w)
+        for name in ("noise_scale", "length_scale", "noise_scale_w"):
+            if not math.isfinite(getattr(self, name)):
+                raise ValueError("Request: %s must be finite" % name)
+        if max_len is not None:
+            max_len = int(max_len)
+            if max_len < 1:
+                raise ValueError("Request: max_len leaves no frames to decode")
+        self.max_len = max_len
+        self.chunk_frames, self.max_chunk_frames = int(chunk_frames), int(max_chunk_frames)
+        if self.chunk_frames < 1 or self.max_chunk_frames < self.chunk_frames:
+            raise ValueError("Request: need 1 <= chunk_frames <= max_chunk_frames (got %d, %d)"
+                             % (self.chunk_frames, self.max_chunk_frames))
+        self.durations_dtype = None
+        if durations is not None:
+            if self.length_scale != 1.0:
+                raise ValueError("Request: durations= are used as given: length_scale must be 1 (scale the durations instead)")
+            if not torch.is_tensor(durations):
+                raise ValueError("Request: durations must be a tensor [T_text]")
+            T = self.x.numel()
+            if durations.numel() != T or tuple(durations.shape) not in ((T,), (1, T), (1, 1, T)):
+                raise ValueError("Request: durations must be [T_text] = [%d] (or [1, %d] / [1, 1, %d]), got %s"
+                                 % (T, T, T, tuple(durations.shape)))
+            durations, self.durations_dtype = _durations_code(durations.reshape(T))
+            durations = durations.contiguous()
+        self.durations = durations
+
+    def __repr__(self):
+        return "Request(%d tokens, sid=%r%s)" % (self.x.numel(), self.sid, "" if self.durations is None else ", durations")
+
+
 _STAGES = ("text_encoder", "duration_predictor", "alignment_and_projection", "flow",
            "waveform_decoder")
 
@@ -317,14 +395,7 @@ class SynthesizerTrn(nn.Module):
         if tuple(durations.shape) != (B, T):
             raise ValueError("durations must be [B, T_text] or [B, 1, T_text] = [%d, %d], got %s"
                              % (B, T, tuple(durations.shape)))
-        if durations.dtype == torch.int32:
-            code = 0
-        elif durations.dtype == torch.int64:
-            code = 1
-        elif durations.dtype.is_floating_point:
-            durations, code = durations.to(torch.float32), 2
-        else:
-            durations, code = durations.to(torch.int64), 1
+        durations, code = _durations_code(durations)
         return durations.to(device=self._device()).contiguous(), code
 
     def _stage_times(self, ticket):
@@ -676,12 +747,13 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                     chunk_frames=32, max_chunk_frames=256):
+                     chunk_frames=32, max_chunk_frames=256, durations=None):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
-        flows exactly as `infer` does (same random draws), then returns `dec_stream` of z * y_mask (truncated to
-        max_len) with `y_lengths` set on the stream.  The concatenation is bitwise `infer(...)[0]` (default mode)."""
+        flows exactly as `infer` does (same random draws; `durations` as in `infer`), then returns `dec_stream` of
+        z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
+        `infer(...)[0]` (default mode)."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"))
+                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations)
         y_mask, z, y_lengths = r[5], r[6][0], r[8]
         Tp = z.shape[2]
         Td = Tp if max_len is None else max(0, min(Tp, int(max_len)))
@@ -694,6 +766,161 @@ class SynthesizerTrn(nn.Module):
         st = self.dec_stream(zd, g, chunk_frames, max_chunk_frames)
         st.y_lengths = y_lengths
         return st
+
+    # ------------------------------------------------------------------ pooled admission
+    def admit_plan(self, t_text, splitk=False):
+        """(runs, run_of_request): the front-half runs `infer_streams` makes for requests of these text lengths
+        (`mbv_admit_plan`, host only: no GPU needed).  Requests share a padded run iff the conv planner sends every
+        conv in front of the flows to the same kernel family for either text alone — today two classes, T <= 256 and
+        beyond; with `splitk` one."""
+        t = [int(v) for v in (t_text.tolist() if torch.is_tensor(t_text) else t_text)]
+        n = len(t)
+        if n < 1:
+            raise ValueError("admit_plan: no requests")
+        if min(t) < 1:
+            raise ValueError("admit_plan: empty text (every length must be >= 1)")
+        cfg = self._config_struct()
+        runs = (C.c_int32 * n)()
+        r = _capi.lib().mbv_admit_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * n)(*t), runs)
+        if r < 0:
+            raise ValueError("mbv_admit_plan refused the lengths")
+        return r, list(runs)
+
+    def encoder_runs(self):
+        """Text-encoder runs made on this model's handle so far (`mbv_encoder_runs`): the difference across a call is
+        the number of front-half launch chains it cost."""
+        return int(_capi.lib().mbv_encoder_runs(self._ensure_handle()))
+
+    @torch.no_grad()
+    def infer_streams(self, requests):
+        """Pooled admission: one single-utterance `DecodeStream` per `Request`, in order — what `StreamPool.add` takes —
+        from ONE padded front-half run per class of `admit_plan` and ONE host read-back, instead of a launch chain and
+        a read-back per request.
+
+        Default mode: stream i is bitwise (z, g, y_lengths, schedule) what
+        `infer_stream(x_i[None], [len_i], sid_i, noise_scale_i, length_scale_i, noise_scale_w_i, max_len_i,
+        chunk_frames_i, max_chunk_frames_i, durations=d_i)` returns when those calls are made one after the other in
+        list order from the same RNG state, and both generators (CPU: the SDP draws, device: the prior draws) end in
+        the state those calls leave.  With the option "splitk" the result is deterministic and within fp32 rounding
+        of the stand-alone calls (a predicted duration may differ by a frame); "conv_bf16" is refused.
+
+        All or nothing: a request with a token id / sid outside the model's tables or an unusable duration raises
+        IndexError naming the request indices after the read-back, and no stream is created.  Refused before any
+        launch (ValueError): a missing sid on a multi-speaker model, "conv_bf16"; `Request` itself refuses an empty
+        text and durations with length_scale != 1."""
+        reqs = list(requests)
+        for i, r in enumerate(reqs):
+            if not isinstance(r, Request):
+                raise TypeError("infer_streams takes models.Request values (item %d is %s)" % (i, type(r).__name__))
+            if self.n_speakers > 0 and r.sid is None:
+                raise ValueError("request %d: sid is required for a multi-speaker model (models.py:704-705)" % i)
+        if not reqs:
+            return []
+        h = self._ensure_handle()
+        L = _capi.lib()
+        dev = self._device()
+        if L.mbv_get_option(h, b"conv_bf16") != 0:
+            raise ValueError("infer_streams is not built for the \"conv_bf16\" mode (the flows' route follows the launch "
+                             "size there): admit with infer_stream, one request at a time")
+        N, I = len(reqs), self.cfg.inter_channels
+        t_text = [r.x.numel() for r in reqs]
+        n_runs, run_of = self.admit_plan(t_text, splitk=L.mbv_get_option(h, b"splitk") != 0)
+        members = [[i for i in range(N) if run_of[i] == k] for k in range(n_runs)]
+        pos, first = [0] * N, []                   # request -> its row in y_all, run -> its first row
+        for m in members:
+            first.append(sum(len(q) for q in members[:len(first)]))
+            for b, i in enumerate(m):
+                pos[i] = first[-1] + b
+        with torch.cuda.device(dev):
+            hip_stream = self._stream()
+            keep = []                              # inputs of launches in flight
+            noise_w = [None] * N
+            if self.cfg.use_sdp:                   # the reference's draw, per request, on the default CPU generator
+                flat_w = torch.cat([torch.randn(1, 2, t).reshape(-1) for t in t_text]).to(dev)
+                keep.append(flat_w)
+                o = 0
+                for i, t in enumerate(t_text):
+                    noise_w[i] = flat_w.data_ptr() + 4 * o
+                    o += 2 * t
+            dur = [None] * N                       # device addresses of the given durations: host ones travel together
+            for code in (0, 1, 2):
+                host = [i for i in range(N) if reqs[i].durations_dtype == code and not reqs[i].durations.is_cuda]
+                if host:
+                    flat_d = torch.cat([reqs[i].durations for i in host]).to(dev)
+                    keep.append(flat_d)
+                    o = 0
+                    for i in host:
+                        dur[i] = flat_d.data_ptr() + flat_d.element_size() * o
+                        o += t_text[i]
+            for i, r in enumerate(reqs):
+                if r.durations is not None and dur[i] is None:
+                    d = r.durations.to(dev)
+                    keep.append(d)
+                    dur[i] = d.data_ptr()
+            y_all = torch.empty(N, dtype=torch.int64, device=dev)
+            # ids (zero-padded to the run's longest text), lengths and sids of every run: ONE host tensor, one copy
+            on_host = not any(r.x.is_cuda for r in reqs)
+            parts = []
+            for m in members:
+                xs = [reqs[i].x for i in m] if on_host else [reqs[i].x.to(dev) for i in m]
+                parts.append(torch.nn.utils.rnn.pad_sequence(xs, batch_first=True, padding_value=0).reshape(-1))
+                tail = [t_text[i] for i in m] + ([reqs[i].sid for i in m] if self.n_speakers > 0 else [])
+                parts.append(torch.tensor(tail, dtype=torch.int64) if on_host else torch.tensor(tail, dtype=torch.int64).to(dev))
+            packed = torch.cat(parts).to(dev)
+            keep.append(packed)
+            sids, o = [], 0
+            for k, m in enumerate(members):
+                B, T = len(m), max(t_text[i] for i in m)
+                ids, lens = packed.data_ptr() + 8 * o, packed.data_ptr() + 8 * (o + B * T)
+                sid = packed[o + B * T + B:o + B * T + 2 * B] if self.n_speakers > 0 else None
+                o += B * T + (2 * B if self.n_speakers > 0 else B)
+                sids.append(sid)
+                rows = (_capi.MbvEncRow * B)()
+                for row, i in zip(rows, m):
+                    r = reqs[i]
+                    row.length_scale, row.noise_scale_w, row.noise_w = r.length_scale, r.noise_scale_w, noise_w[i]
+                    row.durations, row.durations_dtype, row.t_text = dur[i], r.durations_dtype or 0, t_text[i]
+                _capi.check(h, L.mbv_encode_rows(h, k, C.c_void_p(ids), C.c_void_p(lens), self._ptr(sid), B, T, rows,
+                                                 C.c_void_p(y_all.data_ptr() + 8 * first[k]), hip_stream),
+                            "mbv_encode_rows")
+            y_host = y_all.tolist()                # the one host sync: every run's lengths, -1 = flagged
+            bad = [i for i in range(N) if y_host[pos[i]] < 0]
+            if bad:
+                raise IndexError("request%s %s: index out of range in self (token id or sid outside the model's tables, or "
+                                 "a duration outside the supported range: 2^20 frames a token, 2^30 an utterance; given "
+                                 "durations must be non-negative integers)"
+                                 % ("s" if len(bad) > 1 else "", ", ".join(str(i) for i in bad)))
+            Tp = [int(y_host[pos[i]]) for i in range(N)]
+            Td = [Tp[i] if r.max_len is None else min(Tp[i], r.max_len) for i, r in enumerate(reqs)]
+            # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729): per request, in list order,
+            # into one buffer — the values and the generator's progress of N stand-alone randn(1, I, T'_i) calls
+            flat = torch.empty(I * sum(Tp), device=dev, dtype=torch.float32)
+            noise, o = [0] * N, 0
+            for i in range(N):
+                flat[o:o + I * Tp[i]].view(1, I, Tp[i]).normal_()
+                noise[i] = flat.data_ptr() + 4 * o
+                o += I * Tp[i]
+            z = [torch.empty(1, I, Td[i], device=dev, dtype=torch.float32) for i in range(N)]
+            g = [None] * N
+            for k, m in enumerate(members):
+                B = len(m)
+                rows = (_capi.MbvRow * B)()
+                for row, i in zip(rows, m):
+                    row.noise, row.noise_stride, row.noise_scale = noise[i], Tp[i], reqs[i].noise_scale
+                    row.keep, row.z = Td[i], z[i].data_ptr()
+                _capi.check(h, L.mbv_synthesize_rows(h, k, max(Tp[i] for i in m), rows, B, hip_stream), "mbv_synthesize_rows")
+                if self.n_speakers > 0:            # (the sids passed the encode's range check)
+                    g_run = torch.empty(B, self.cfg.gin_channels, device=dev, dtype=torch.float32)
+                    _capi.check(h, L.mbv_speaker_embedding(h, self._ptr(sids[k]), B, self._ptr(g_run), hip_stream),
+                                "mbv_speaker_embedding")
+                    for b, i in enumerate(m):
+                        g[i] = g_run[b:b + 1]
+            out = []
+            for i, r in enumerate(reqs):
+                st = stream.DecodeStream(self, h, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
+                st.y_lengths = y_all[pos[i]:pos[i] + 1]
+                out.append(st)
+        return out
 
     @torch.no_grad()
     def istft_finalize(self, spec, phase):

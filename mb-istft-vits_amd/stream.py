@@ -110,7 +110,7 @@ class StreamPool:
     pooled stream that has one (or of those named) and returns `[(st, first_sample, view), ...]`; the chunks count as
     decoded ahead on their streams, so `next(st)` — and a `wire.PcmStream` over `st` — afterwards hands them out
     without a launch.  A stream may be advanced through the pool, alone, or both in turn.  Streams may be added at
-    any time; finished ones drop out."""
+    any time, one by one (`add`) or as the requests they come from (`admit`); finished ones drop out."""
 
     def __init__(self, net):
         self._net = net
@@ -133,6 +133,15 @@ class StreamPool:
         if not any(st is m for m in self.streams):
             self.streams.append(st)
         return st
+
+    def admit(self, requests):
+        """`net.infer_streams(requests)` + `add`: the front half of a tick's new requests in one padded run per class
+        of `net.admit_plan` and one host read-back; -> their streams, in order.  All or nothing: when a
+        request is refused or flagged, the exception passes through, no stream is created and the pool is unchanged."""
+        sts = self._net.infer_streams(requests)
+        for st in sts:
+            self.add(st)
+        return sts
 
     def step(self, streams=None):
         if streams is None:

@@ -269,6 +269,15 @@ class PcmPool:
             self.followers.append(f)
         return f
 
+    def admit(self, requests, peak=None):
+        """`StreamPool.admit(requests)` + a follower for each new stream (`peak`: None, one value for all, or one per
+        request, as `add` takes it); -> the followers, in order.  All or nothing, like `StreamPool.admit`."""
+        reqs = list(requests)
+        peaks = list(peak) if isinstance(peak, (list, tuple)) else [peak] * len(reqs)
+        if len(peaks) != len(reqs):
+            raise ValueError("admit: one peak per request expected (%d), got %d" % (len(reqs), len(peaks)))
+        return [self.add(st, peak=p) for st, p in zip(self.pool.admit(reqs), peaks)]
+
     def step(self, streams=None, host=False):
         """-> [(st, first_out_sample, piece), ...]: one entry per stream whose decoded frontier made outputs final
         (an empty piece is possible, as for `PcmStream`).  `piece` is the 1-D view `follower.pcm[0, a:b]` on the

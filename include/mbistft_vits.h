@@ -244,6 +244,28 @@ int mbv_chunks_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_f
 int mbv_decode_chunks(mbv_model *m, const mbv_chunk *chunks_host, int n, void *stream);
 int64_t mbv_decoder_runs(mbv_model *m);
 
+/* ---- "tail_once" (default 1; mbv_set_option("tail_once", 0) turns it off, 2 applies it at every size) -----------
+ * The decoder gets z * y_mask: behind the reach of row b's valid frames every activation is the zero-input response,
+ * the same in every row of a padded batch.  With the option on, the ResBlock convs of every row but the shortest
+ * (the donor) leave out the column tiles that lie wholly in that tail, and a copy kernel writes the donor's values
+ * there: every output and stage tensor is bitwise what it is with the option off.  Inert for B = 1, without
+ * y_lengths (mbv_decode), with "splitk", "trim", "conv_bf16", the ranged / ragged / pooled decodes and per-row
+ * speaker conditioning in the decoder (gin_channels > 0 with g given).
+ *
+ * mbv_tail_plan (host only, like mbv_conv_plan): one row of 6 ints per launch of the decoder, in launch order:
+ * kind (0 conv_pre, 1 ups[stage], 2 / 3 first / second conv of step q of ResBlock j, 4 conv_post, 5 the waveform
+ * tail), stage, j, q, rate (output columns per z-frame), reach (output columns past rate * len - 1 that a valid
+ * z-frame of a row of len frames can influence; for a launch that writes the running ResBlock sum, the maximum over
+ * the ResBlocks summed so far).  Row b's tail starts at column rate * len_b + reach.  At most `capacity` rows are
+ * written; returns the number of launches, -1 on a bad argument.
+ * mbv_tail_dropped: column tiles the tail maps left out on this handle since mbv_create (synchronises the device). */
+int mbv_tail_plan(const mbv_config *cfg, int32_t *out, int capacity);
+/* mbv_decode on z * sequence_mask(lengths): the decoder run mbv_synthesize makes, on a z of the caller's.
+ * lengths: DEVICE int32 [B], frames per row; z at and past a row's length is read as zero. */
+int mbv_decode_masked(mbv_model *m, const float *z, const float *g, const int32_t *lengths, int B, int t_frames,
+                      const mbv_outputs *outs, void *stream);
+int64_t mbv_tail_dropped(mbv_model *m);
+
 /* ---- pooled admission: the front half (text encoder, duration predictor, length regulation, flows) of many
  * requests in one padded run (no reference counterpart: the reference service runs one request at a time,
  * synthesis_module.py:141 taking the scales per request) ----------------
@@ -317,7 +339,11 @@ int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, v
  *   "dec_streams"  1 (default; MBV_DEC_STREAMS): when one ResBlock conv of a decoder stage cannot fill the
  *                  chip (single utterances, small batches) the stage's three ResBlocks (models.py:353-359)
  *                  run on three internal streams forked from / joined to `stream`; bitwise the result of
- *                  the one-stream schedule (0).
+ *                  the one-stream schedule (0).  With "tail_once" at work also at any batch size.
+ *   "tail_once"    1 (default): the zero-input tail of a padded batch is computed for the shortest row only and
+ *                  copied to the others (see mbv_tail_plan), in the decoder stages whose ResBlock convs exceed one
+ *                  round of the 256-workgroup grid (smaller launches have no round to save).  2: in every stage
+ *                  (tests).  0: off.  Every output and stage tensor is bitwise the same for all three values.
  *   "trim"         0 (default).  1: OPT-IN trimmed decode for ragged batches whose caller takes only the waveform
  *                  and cuts it by y_lengths (tts_vits.py:134-137 takes [0][0,0] of one utterance): in mbv_synthesize
  *                  the decoder computes, per utterance, only the tiles that hold frames below y_lengths[b] + 32
@@ -660,6 +686,8 @@ typedef struct mbv_conv_desc {
   const float *ln_gamma;          /* LN: DEVICE [Cout] */
   const float *ln_beta;           /* LN: DEVICE [Cout] */
   const int32_t *ln_out_lens;     /* LN: DEVICE [B] or NULL, the mask behind the LayerNorm */
+  int32_t tail_once;              /* 1 (with trim_lens; conv with STORE / RESID / RESID_ACC): the launch of "tail_once" — the row with the
+                                   * smallest trim_lens keeps every tile, the tiles the others drop are copied from it (trim_add = reach) */
 } mbv_conv_desc;
 /* plan[8] = route, tile rows, tile columns, threads, input-channel chunk, nb_big, vs_tv, split-K factor
  * (tile fields 0 on the narrow kernel; see conv1d_plan in csrc/kernels.h) */

@@ -30,6 +30,7 @@ SYMBOLS = [
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
     "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
     "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
+    "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
 ]
 
 
@@ -96,6 +97,7 @@ class MbvConvDesc(C.Structure):
         ("splitk", C.c_int32), ("prec", C.c_int32), ("legacy_convt", C.c_int32),
         ("ws_floats", C.c_int64), ("n_counters", C.c_int32),
         ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_out_lens", C.c_void_p),
+        ("tail_once", C.c_int32),
     ]
 
 
@@ -202,13 +204,14 @@ def lib():
     L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
-    # those four entries, the pooled decode's three, the pooled wire output's three and pooled admission's five may be
-    # absent there, and calling one then raises AttributeError.  Everything else, and the in-tree library always, must match the header.
+    # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five and
+    # the three that came with "tail_once" may be absent there, and calling one then raises AttributeError.
+    # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
                 "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
                 "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs",
-                "mbv_get_option") if os.environ.get("MBV_LIB") else ()
+                "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -232,6 +235,11 @@ def lib():
         L.mbv_encoder_runs.argtypes = [vp]
         L.mbv_encoder_runs.restype = C.c_int64
         L.mbv_get_option.argtypes = [vp, C.c_char_p]
+    if hasattr(L, "mbv_tail_plan") or not optional:
+        L.mbv_tail_plan.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32), i32]
+        L.mbv_tail_dropped.argtypes = [vp]
+        L.mbv_tail_dropped.restype = C.c_int64
+        L.mbv_decode_masked.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

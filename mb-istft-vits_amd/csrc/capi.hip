@@ -106,6 +106,8 @@ struct mbv_model {
   int xpost_rows = 72;         // 72 (4 bands x 18) or 18 (single band)
   int exact_math = 0;          // MBV_ISTFT_EXACT=1: libm transcendentals in the iSTFT kernel
   int trim = 0;                    // option "trim": opt-in trimmed decode (run_decoder)
+  int tail_once = 1;               // option "tail_once": the zero-input tail of a padded batch computed once (run_decoder)
+  unsigned long long* tail_cnt = nullptr;   // device: column tiles dropped by tail maps since mbv_create (mbv_tail_dropped)
   std::vector<int> ragged_first;   // row-exact ragged decode: first length of every class up to ragged_scanned (ragged_classes)
   int ragged_scanned = 0, ragged_splitk = -1;
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
@@ -952,13 +954,21 @@ ConvArgs conv_args(const mbv_model* m, const PConv& p, const float* x, int64_t x
 }
 
 // decoder + waveform tail on z [B, I, zstride] (first Td frames valid)
-size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td);
+size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td, int tail = 0);
+
+// "tail_once" as the handle's options leave it: 0 off (or excluded by split-K, "trim", "conv_bf16"), 1 the stages
+// whose ResBlock convs exceed one round of the 256-workgroup grid, 2 every stage (tests).  Below one round a
+// dropped tile saves no time and the map and fill launches would only add launch gaps (B = 8: + 0.1 ms).
+int tail_mode(const mbv_model* m) { return (!m->trim && !m->splitk && m->conv_bf16 != 3) ? m->tail_once : 0; }
+bool tail_stage(int mode, int B, long conv_tiles) { return B > 1 && (mode == 2 || (mode == 1 && conv_tiles > 256)); }
 
 // The three ResBlocks of a decoder stage on three streams?  Only when one of their convs (ch channels, Lo
 // frames) is at most 192 tiles of 128 x 384, i.e. cannot fill the chip by itself.
-bool decoder_stage_concurrent(const mbv_model* m, int B, int ch, int Lo) {
+// With tail maps (option "tail_once") at any size: a launch that lost its tail tiles ends in a partial round of the
+// persistent grid, which only a launch of another ResBlock can fill.
+bool decoder_stage_concurrent(const mbv_model* m, int B, int ch, int Lo, bool tail = false) {
   const long conv_tiles = (long)B * ((Lo + 383) / 384) * ((ch + 127) / 128);
-  return m->dec_streams && m->aux_ok && m->cfg.resblock_type != 2 && conv_tiles <= 192 && !m->trim;   // (trim: its tile maps are built on the caller's stream)
+  return m->dec_streams && m->aux_ok && m->cfg.resblock_type != 2 && (conv_tiles <= 192 || tail) && !m->trim;   // (trim: its tile maps are built on the caller's stream)
 }
 
 // The streaming decode (mbv_decode_range): run_decoder on a z-window of Td frames whose first frame is z-frame
@@ -1023,6 +1033,63 @@ int decoder_context(const mbv_config& c, int* Lc, int* Rc) {
   return 0;
 }
 
+// "tail_once": how far to the right a z-frame reaches at every launch of the decoder (mbv_tail_plan).  Walked
+// forwards with the same index rules as decoder_context walks backwards: `hi` is the last output column the input
+// columns up to x.hi can influence.
+static int64_t reach_conv(int64_t hi, int pad_left) { return hi + pad_left; }                  // y[t] reads x[t - pad_left + k dil]
+static int64_t reach_convt(int64_t hi, int k, int u, int p) { return (int64_t)u * hi - p + k - 1; }   // j = u i - p + [0, k)
+// One entry per launch, in launch order.  kind: 0 conv_pre, 1 ups[stage], 2 / 3 first / second conv of step q of
+// ResBlock j of `stage`, 4 conv_post, 5 the waveform tail (iSTFT + synthesis filter).  rate = output columns per
+// z-frame; reach = output columns past rate len - 1 that a valid z-frame of a row of len frames can still influence
+// (ResBlock launches that write the running sum xs: the maximum over the ResBlocks summed so far).  Row b's output
+// at and past column rate len_b + reach is the zero-input response: a function of the column alone.
+struct TailLaunch { int kind, stage, j, q, rate, reach; };
+void decoder_tail_plan(const mbv_config& c, std::vector<TailLaunch>* out) {
+  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
+  const int us = sb ? 8 : 4, kUp = 16, kPre = 7, kPost = 7, n_fft = 16, hop = 4, bands = sb ? 1 : 4, taps = 63;
+  (void)n_fft;
+  out->clear();
+  const int64_t len = 1 << 20;                        // a row far from both edges; every hi below is relative to it
+  int64_t rate = 1;
+  int64_t hi = len - 1;                               // the last valid z-frame
+  auto put = [&](int kind, int stage, int j, int q, int64_t h) {
+    out->push_back({kind, stage, j, q, (int)rate, (int)(h - (rate * len - 1))});
+  };
+  hi = reach_conv(hi, (kPre - 1) / 2);
+  put(0, -1, 0, 0, hi);
+  for (int i = 0; i < 2; ++i) {
+    hi = reach_convt(hi, kUp, us, (kUp - us) / 2);
+    rate *= us;
+    put(1, i, 0, 0, hi);
+    int64_t sum_hi = hi;                              // xs: the ResBlocks summed so far (each holds its skip path: >= hi)
+    for (int j = 0; j < 3; ++j) {
+      const int k = c.resblock_kernel_sizes[j];
+      const int nq = c.resblock_type == 2 ? 2 : 3;
+      int64_t r = hi;
+      for (int q = 0; q < nq; ++q) {
+        const int d = c.resblock_dilations[j][q];
+        const bool last = q == nq - 1;
+        if (c.resblock_type == 2) {
+          r = reach_conv(r, (k - 1) * d / 2);         // (+ the skip path: r only grows)
+          if (last) { sum_hi = sum_hi > r ? sum_hi : r; put(3, i, j, q, sum_hi); } else put(3, i, j, q, r);
+          continue;
+        }
+        r = reach_conv(r, (k - 1) * d / 2);
+        put(2, i, j, q, r);
+        r = reach_conv(r, (k - 1) / 2);
+        if (last) { sum_hi = sum_hi > r ? sum_hi : r; put(3, i, j, q, sum_hi); } else put(3, i, j, q, r);
+      }
+    }
+    hi = sum_hi;
+  }
+  hi = reach_conv(hi, (kPost - 1) / 2 + 1);           // frame f reads x[f - 4 .. f + 2] (ReflectionPad1d((1, 0)))
+  put(4, 2, 0, 0, hi);
+  hi = hop * hi + n_fft / 2 - 1;                      // frame f covers sub-band samples [hop f - n_fft / 2, hop f + n_fft / 2)
+  rate *= hop;
+  if (!sb) { hi = bands * hi + taps / 2; rate *= bands; }   // sample n reads sub-band samples [(n - 31) / bands, (n + 31) / bands]
+  put(5, 2, 0, 0, hi);
+}
+
 // The row-exact ragged decode (mbv_decode_ragged): run_decoder on the rows of one class (run_decoder_ragged below).
 // Row b is an utterance of len[b] <= Td frames and is decoded as if alone: every conv masks its input at the
 // row's own length at that conv's rate (true zeros: the padding a stand-alone decode applies), only the column
@@ -1050,7 +1117,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   const int rt_num = rg && !m->splitk ? rg->t_full : 0;
   const int I = c.inter_channels, C0 = c.upsample_initial_channel, gin = c.gin_channels;
   hipStream_t const s_main = s;
-  if (sc.off + decoder_scratch_bytes(c, B, Td) > sc.cap) return m->fail("internal error: decoder scratch arena undersized");
+  if (sc.off + decoder_scratch_bytes(c, B, Td, (rr || rg) ? 0 : tail_mode(m)) > sc.cap) return m->fail("internal error: decoder scratch arena undersized");
   float* x0 = sc.take<float>((size_t)B * C0 * Td);
   HIPCHK(m, hipEventRecord(m->evk[0], s));
   // Opt-in trimmed decode (option "trim"; the caller takes only `o` and trims by y_lengths): a conv computes the
@@ -1103,6 +1170,34 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     trim_maps.push_back({num, add, a.T, bn, map});
     a.trim_map = map; a.trim_bn = bn;
   };
+  // "tail_once" (default on): the decoder gets z * y_mask, so behind S_b = rate len_b + reach of a
+  // ResBlock launch (decoder_tail_plan) row b's output is the zero-input response, a function of the column alone
+  // and the same in every row.  Only the donor — the shortest row — computes it: the other rows drop the column
+  // tiles that lie wholly behind their S_b from the launch (the trim-map path of the conv kernel), and a copy kernel
+  // behind the launch writes the donor's values there.  An output element's chain of operations does not depend on
+  // its tile or row, so every tensor holds bitwise what it held.  A launch that lost tiles ends in a partial round
+  // of the persistent grid: the three ResBlocks then run on three streams at any batch size, so that another
+  // launch fills it.  Not with per-row conditioning in the ResBlocks (the tails differ), split-K, conv_bf16, one
+  // row, or the modes that bring their own maps.
+  const bool tail = tail_mode(m) && !trim && !rr && !rg && zlens && B > 1 && B <= 65535 && !(gvec && gin);
+  bool tail_drift = false;
+  std::vector<TailLaunch> tail_plan;
+  if (tail) decoder_tail_plan(c, &tail_plan);
+  struct TailMap { int kind, j, q, bn; const int* map; };
+  std::vector<TailMap> tail_maps;                      // of the current stage
+  auto with_tail = [&](ConvArgs& a, int kind, int j, int q) -> const TailMap* {
+    for (const auto& t : tail_maps)
+      if (t.kind == kind && t.j == j && t.q == q) {
+        // (the map was planned before the fork from the launch's shape alone: the launch itself must agree)
+        if (conv1d_trim_bn(a) != t.bn) { tail_drift = true; return nullptr; }
+        a.trim_map = t.map; a.trim_bn = t.bn;
+        return &t;
+      }
+    return nullptr;
+  };
+  auto fill_tail = [&](const ConvArgs& a, const TailMap* t, hipStream_t st) {
+    if (t) launch_tail_fill(a.y, a.y_bstride, B, a.M, a.T, t->bn, t->map, st);
+  };
   {
     ConvArgs a = conv_args(m, m->conv_pre, z, (int64_t)I * zstride, Td, x0, (int64_t)C0 * Td, Td, B);
     a.x_rstride = zstride;
@@ -1125,7 +1220,30 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     // of their convs cannot fill the chip (single utterances, small batches: decoder_stage_concurrent)
     // they run on three streams — own temporaries each, the three xs updates chained by events in the
     // order of the one-stream schedule, so the result is bitwise the same.
-    const bool conc = decoder_stage_concurrent(m, B, ch, Lo) && !trim;
+    // tail maps of this stage's ResBlock launches, all from one launch on the caller's stream (before the fork).
+    // A launch the planner sends to a route that takes no map (narrow, split-batch, half-height) keeps that route.
+    tail_maps.clear();
+    const long stage_tiles = (long)B * ((Lo + 383) / 384) * ((ch + 127) / 128);
+    if (tail && tail_stage(tail_mode(m), B, stage_tiles)) {
+      TailMapJobs jobs{};
+      int nj = 0;
+      for (const auto& tl : tail_plan) {
+        if (tl.stage != i || (tl.kind != 2 && tl.kind != 3) || nj == kTailMapJobs) continue;
+        const auto& R = m->rb[i * 3 + tl.j];
+        const bool second = tl.kind == 3 && c.resblock_type != 2;
+        ConvArgs a = conv_args(m, second ? R.c2[tl.q] : R.c1[tl.q], u, (int64_t)ch * Lo, Lo, u, (int64_t)ch * Lo, Lo, B,
+                               second ? 1 : c.resblock_dilations[tl.j][tl.q]);
+        a.in_slope = kLrelu;
+        if (tl.kind == 3) { a.epi = EPI_RESID; a.res = u; a.res_bstride = (int64_t)ch * Lo; }
+        const int bn = conv1d_trim_bn(a);
+        if (!bn || conv1d_plan(a, false).route != conv1d_plan(a, true).route) continue;
+        int* map = sc.take<int>(launch_tail_map_ints(B, Lo, bn));
+        jobs.job[nj++] = {Lo / Td, tl.reach, Lo, bn, map};
+        tail_maps.push_back({tl.kind, tl.j, tl.q, bn, map});
+      }
+      launch_tail_maps(zlens, B, jobs, nj, m->tail_cnt, s_main);
+    }
+    const bool conc = decoder_stage_concurrent(m, B, ch, Lo, !tail_maps.empty()) && !trim;
     float *t1s[3], *rs[3];
     t1s[0] = sc.take<float>(n);
     rs[0] = sc.take<float>(n);
@@ -1191,7 +1309,9 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           }
           if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
+          const TailMap* tm = with_tail(a, 3, j, q);
           launch_conv1d(a, s, rt_num * (Lo / Td));
+          fill_tail(a, tm, s);
           state = r;
         }
         continue;
@@ -1205,7 +1325,9 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           own_ws(a);
           if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
+          const TailMap* tm = with_tail(a, 2, j, q);
           launch_conv1d(a, s, rt_num * (Lo / Td));
+          fill_tail(a, tm, s);
         }
         {
           ConvArgs a = conv_args(m, R.c2[q], t1, (int64_t)ch * Lo, Lo, r, (int64_t)ch * Lo, Lo, B, 1);
@@ -1224,7 +1346,9 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
           own_ws(a);
           if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
           with_trim(a, Lo / Td, 0);
+          const TailMap* tm = with_tail(a, 3, j, q);
           launch_conv1d(a, s, rt_num * (Lo / Td));
+          fill_tail(a, tm, s);
           if (conc && q == 2) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
         }
         state = r;
@@ -1329,6 +1453,7 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   HIPCHK(m, hipEventRecord(m->evk[2], s));
   m->evk_set = true;
   m->evk_split = Bc < B;
+  if (tail_drift) return m->fail("internal error: a tail map was planned for another tile width than its launch uses");
   if (route_drift) return m->fail("internal error: a %s run holds rows whose convs plan differently (ragged_classes out of step with run_decoder)", pooled ? "pooled" : "ragged");
   return 0;
 }
@@ -1687,16 +1812,18 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
   return 0;
 }
 
-size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td) {
+size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td, int tail) {
   const size_t C0 = c.upsample_initial_channel;
   const size_t us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4;
   size_t n = (size_t)B * C0 * Td;                              // conv_pre
   // per stage: u, t1, r, xs — and t1, r twice more when the ResBlocks may run on three streams (small
-  // launches only; sized for it whenever the tile test can pass, whatever the option says)
+  // launches, sized for it whenever the tile test can pass, whatever "dec_streams" says; and the stages that
+  // "tail_once" runs concurrently at any size — `tail` = tail_mode of the handle, 0 for the runs the option
+  // never touches.  Headline batch, B = 64, T' = 566: 4 x (148 + 297) MB = 1.78 GB on top of 2.2 GB)
   for (int i = 0; i < 2; ++i) {
     const size_t ch = C0 >> (i + 1), Lo = (i == 0 ? us : us * us) * (size_t)Td;
     const long conv_tiles = (long)B * (long)((Lo + 383) / 384) * (long)((ch + 127) / 128);
-    n += (conv_tiles <= 192 ? 8 : 4) * (size_t)B * ch * Lo;
+    n += (conv_tiles <= 192 || tail_stage(tail, B, conv_tiles) ? 8 : 4) * (size_t)B * ch * Lo;
   }
   {   // x_post: run_decoder takes at most the sub-batch that stays below 2 GiB (its Bc; the option can only lower it)
     const size_t utt = 72 * (us * us * Td + 1);
@@ -1706,7 +1833,8 @@ size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td) {
   }
   n += 6 * (size_t)B * C0;                                     // cond vectors
   n += 12 * ((size_t)B + 2 + (size_t)B * ((us * us * Td + 1 + 127) / 128 + 1));   // trimmed decode: column-tile maps (ints)
-  return n * sizeof(float) + 64 * 256 + 32 * 256;              // + the 256-byte alignment of every take
+  n += 2 * kTailMapJobs * ((size_t)B + 3 + (size_t)B * ((us * us * Td + 127) / 128 + 1));   // "tail_once": a map per ResBlock launch (ints)
+  return n * sizeof(float) + 64 * 256 + 32 * 256 + 2 * kTailMapJobs * 256;   // + the 256-byte alignment of every take
 }
 
 }  // namespace
@@ -1789,6 +1917,12 @@ int mbv_create(const mbv_config* cfg, mbv_model** out) {
     m->conv_ws_floats = kWsFloats;
     m->conv_ncnt = kCounters;
   }
+  // (the counter of mbv_tail_dropped: eight bytes the tail-map kernel adds to; only tests read it)
+  if (hipMalloc((void**)&m->tail_cnt, sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(m->tail_cnt, 0, sizeof(unsigned long long)) != hipSuccess) {
+    mbv_destroy(m);
+    return bad("hipMalloc of the tail-map counter failed");
+  }
   *out = m;
   return 0;
 }
@@ -1803,13 +1937,18 @@ int mbv_set_option(mbv_model* m, const char* name, int value) {
   if (!strcmp(name, "xpost_chunk_bytes")) { m->xpost_chunk_bytes = value > 0 ? value : 0; return 0; }
   if (!strcmp(name, "dec_streams")) { m->dec_streams = value != 0; return 0; }
   if (!strcmp(name, "trim")) { m->trim = value != 0; return 0; }
+  if (!strcmp(name, "tail_once")) {
+    if (value < 0 || value > 2) return m->fail("mbv_set_option: tail_once takes 0 (off), 1 (launches beyond one round of the grid) or 2 (every size)");
+    m->tail_once = value;
+    return 0;
+  }
   if (!strcmp(name, "conv_bf16")) {
     if (value != 0 && value != 3) return m->fail("mbv_set_option: conv_bf16 takes 0 (exact fp32) or 3 (split-bf16, three products)");
     m->conv_bf16 = value;
     if (value == 3 && m->finalized && ensure_split_arena(m, nullptr)) return 1;
     return 0;
   }
-  return m->fail("mbv_set_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, xpost_chunk_bytes, dec_streams, trim, conv_bf16)", name);
+  return m->fail("mbv_set_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, xpost_chunk_bytes, dec_streams, trim, tail_once, conv_bf16)", name);
 }
 
 int mbv_get_option(mbv_model* m, const char* name) {
@@ -1819,8 +1958,9 @@ int mbv_get_option(mbv_model* m, const char* name) {
   if (!strcmp(name, "wn_fused")) return m->wn_fused;
   if (!strcmp(name, "dec_streams")) return m->dec_streams;
   if (!strcmp(name, "trim")) return m->trim;
+  if (!strcmp(name, "tail_once")) return m->tail_once;
   if (!strcmp(name, "conv_bf16")) return m->conv_bf16;
-  m->fail("mbv_get_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, dec_streams, trim, conv_bf16)", name);
+  m->fail("mbv_get_option: unknown option '%s' (known: splitk, istft_exact, wn_fused, dec_streams, trim, tail_once, conv_bf16)", name);
   return -1;
 }
 
@@ -1831,6 +1971,7 @@ void mbv_destroy(mbv_model* m) {
   if (m->darena_split) (void)hipFree(m->darena_split);
   if (m->conv_ws) (void)hipFree(m->conv_ws);
   if (m->conv_cnt) (void)hipFree(m->conv_cnt);
+  if (m->tail_cnt) (void)hipFree(m->tail_cnt);
   if (m->scrA) (void)hipFree(m->scrA);
   if (m->scrB) (void)hipFree(m->scrB);
   for (auto& sl : m->slots)
@@ -2209,7 +2350,7 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   const bool run_dec = outs && (outs->o || outs->o_mb || outs->spec || outs->phase);
   if (y_lens_host && run_dec) ragged_plan(m, B, Td, y_lens_host, &runs);
   size_t need = (BTp * (4 * I + 3 * H) + (size_t)B * (2 * H * kFlowLayers + 2)) * 4 + wn_units_ints(B, Tp) * 4 + 64 * 256 +
-                (y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td));
+                (y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td, tail_mode(m)));
   if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
   Bump sc{m->scrB, m->scrB_bytes};
   for (const char* k : {"dec_conv_pre", "dec_up_0", "dec_up_1", "dec_res_0", "dec_res_1", "x_post"})
@@ -2493,21 +2634,33 @@ int mbv_decode_ragged(mbv_model* m, const float* z, const float* g, int B, int t
   return 0;
 }
 
-int mbv_decode(mbv_model* m, const float* z, const float* g, int B, int t_frames,
-               const mbv_outputs* outs, void* stream) {
+// mbv_decode / mbv_decode_masked: one decoder run on the caller's z (lengths null: z as it is)
+static int decode_entry(mbv_model* m, const char* who, const float* z, const float* g, const int32_t* lengths, int B,
+                        int t_frames, const mbv_outputs* outs, void* stream) {
   if (!m) return 1;
   if (!m->finalized) return m->fail("weights not finalized");
-  if (!z || B <= 0 || t_frames <= 0 || !outs) return m->fail("mbv_decode: bad arguments");
+  if (!z || B <= 0 || t_frames <= 0 || !outs) return m->fail("%s: bad arguments", who);
   const mbv_config& c = m->cfg;
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, decoder_scratch_bytes(c, B, t_frames))) return 1;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, decoder_scratch_bytes(c, B, t_frames, tail_mode(m)))) return 1;
   Bump sc{m->scrB, m->scrB_bytes};
   m->stages.clear();
-  if (run_decoder(m, z, t_frames, nullptr, (g && c.gin_channels) ? g : nullptr, B, t_frames, outs,
+  if (run_decoder(m, z, t_frames, lengths, (g && c.gin_channels) ? g : nullptr, B, t_frames, outs,
                   (hipStream_t)stream, sc))
     return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
+}
+
+int mbv_decode(mbv_model* m, const float* z, const float* g, int B, int t_frames,
+               const mbv_outputs* outs, void* stream) {
+  return decode_entry(m, "mbv_decode", z, g, nullptr, B, t_frames, outs, stream);
+}
+
+int mbv_decode_masked(mbv_model* m, const float* z, const float* g, const int32_t* lengths, int B, int t_frames,
+                      const mbv_outputs* outs, void* stream) {
+  if (m && !lengths) return m->fail("mbv_decode_masked: bad arguments");
+  return decode_entry(m, "mbv_decode_masked", z, g, lengths, B, t_frames, outs, stream);
 }
 
 int mbv_decoder_context(const mbv_config* cfg, int32_t out[2]) {
@@ -2609,6 +2762,28 @@ int mbv_decode_chunks(mbv_model* m, const mbv_chunk* chunks_host, int n, void* s
 }
 
 int64_t mbv_decoder_runs(mbv_model* m) { return m ? m->decoder_runs : -1; }
+
+int mbv_tail_plan(const mbv_config* cfg, int32_t* out, int capacity) {
+  if (!cfg || (capacity > 0 && !out) || capacity < 0) return -1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+  if (cfg->resblock_type != 1 && cfg->resblock_type != 2) return -1;
+  std::vector<TailLaunch> plan;
+  decoder_tail_plan(*cfg, &plan);
+  for (size_t i = 0; i < plan.size() && (int)i < capacity; ++i) {
+    const int32_t v[6] = {plan[i].kind, plan[i].stage, plan[i].j, plan[i].q, plan[i].rate, plan[i].reach};
+    std::memcpy(out + 6 * i, v, sizeof v);
+  }
+  return (int)plan.size();
+}
+
+int64_t mbv_tail_dropped(mbv_model* m) {
+  if (!m) return -1;
+  DeviceGuard dev_guard_(m->cfg.device);
+  unsigned long long v = 0;
+  if (!dev_guard_.ok || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(&v, m->tail_cnt, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) { m->fail("mbv_tail_dropped: reading the counter failed"); return -1; }
+  return (int64_t)v;
+}
 
 int mbv_stage_times_ms(mbv_model* m, float out[5]) {
   if (!m || !out) return 1;
@@ -2747,7 +2922,7 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   const auto& Q = m->encq;
   const size_t BT = (size_t)B * T;
   size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 4 * I) + (size_t)B * (2 * gin + 2 * H * mbv_model::kEncQLayers + 18)) * 4 + wn_units_ints(B, T) * 4 +
-                64 * 256 + decoder_scratch_bytes(c, B, T);
+                64 * 256 + decoder_scratch_bytes(c, B, T, tail_mode(m));
   if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
   Bump sc{m->scrB, m->scrB_bytes};
   m->stages.clear();
@@ -3575,6 +3750,7 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   if (d.epi != MBV_CONV_EPI_RESID_ACC && d.accum_in) return "accum_in belongs to RESID_ACC";
   if (d.legacy_convt) return "legacy_convt must be 0 (the stand-alone ConvTranspose kernel was removed)";
   if (d.trim_lens && d.splitk) return "a trimmed launch takes no split-K";
+  if (d.tail_once && (!d.trim_lens || convt || ln)) return "tail_once needs trim_lens and a conv with a STORE / RESID / RESID_ACC epilogue";
   const int U = d.kind;
   if (convt) {
     if (d.T != d.Tin) return "ConvTranspose: T must equal Tin (input frames)";
@@ -3710,10 +3886,22 @@ int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const floa
     void* map = nullptr;
     HIPCHK(m, hipMalloc(&map, launch_trim_map_ints(d->B, a.T, p.bn) * sizeof(int)));
     mem.p.push_back(map);
-    launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
+    if (d->tail_once) {
+      if (d->B > 65535) return m->fail("mbv_op_conv: tail_once takes at most 65535 rows");
+      void* tmap = nullptr;
+      HIPCHK(m, hipMalloc(&tmap, launch_tail_map_ints(d->B, a.T, p.bn) * sizeof(int)));
+      mem.p.push_back(tmap);
+      TailMapJobs jobs{};
+      jobs.job[0] = {d->trim_num, d->trim_add, a.T, p.bn, (int*)tmap};
+      launch_tail_maps((const int*)dl, d->B, jobs, 1, m->tail_cnt, s);
+      map = tmap;
+    } else {
+      launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
+    }
     a.trim_map = (const int*)map; a.trim_bn = p.bn;
   }
   launch_conv1d(a, s);
+  if (d->tail_once) launch_tail_fill(a.y, a.y_bstride, a.B, a.M, a.T, a.trim_bn, a.trim_map, s);
   HIPCHK(m, hipGetLastError());
   HIPCHK(m, hipStreamSynchronize(s));
   if (plan_out) plan_ints(p, plan_out);

@@ -450,6 +450,19 @@ void launch_fill(float* p, float v, int64_t n, hipStream_t s);
 // out: (B + 1) + B * ceil(T / BN) ints (launch_trim_map_ints)
 size_t launch_trim_map_ints(int B, int T, int BN);
 void launch_trim_map(const int* lens, int B, int num, int add, int T, int BN, int* out, hipStream_t s);
+// "tail_once" (run_decoder): the same map for launches whose zero-input tail is computed once.  The donor — the row
+// with the smallest lens[b], lowest index on ties — keeps every tile; every other row keeps the tiles that hold a
+// column below S_b = min(T, lens[b] * num + reach), a prefix, and the tiles wholly inside [S_b, T) are dropped.  One
+// launch builds up to kTailMapJobs maps (one workgroup each).  out: launch_tail_map_ints ints = the trim map, then
+// the donor's index; *dropped (device, may be null) += the column tiles dropped by each map.
+constexpr int kTailMapJobs = 24;
+struct TailMapJob { int num, reach, T, BN; int* out; };
+struct TailMapJobs { TailMapJob job[kTailMapJobs]; };
+size_t launch_tail_map_ints(int B, int T, int BN);
+void launch_tail_maps(const int* lens, int B, const TailMapJobs& jobs, int n, unsigned long long* dropped, hipStream_t s);
+// y[b, m, c] = y[donor, m, c] for every column c of a tile that `map` (launch_tail_maps, tiles of BN columns) dropped
+// from row b; y [B, M, T] with batch stride y_bstride.  16-byte accesses when T, y_bstride and y allow them.
+void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s);
 // row-exact ragged decode: n rows of a class, given by value from the host (rows / lens hold up to kRaggedChunk
 // entries per launch) -> out[0 .. 4 stride): the source row of every class row, then its length at the three
 // rates of the decoder (len, us len, us^2 len), entry first + i

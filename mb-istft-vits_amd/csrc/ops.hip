@@ -538,6 +538,86 @@ void launch_trim_map(const int* lens, int B, int num, int add, int T, int BN, in
   hipLaunchKernelGGL(trim_map_kernel, dim3(1), dim3(256), 0, s, lens, B, num, add, T, BN, out);
 }
 
+// "tail_once" (kernels.h): the trim map of a launch whose zero-input tail only the donor row computes
+__global__ void tail_map_kernel(const int* __restrict__ lens, int B, const TailMapJobs jobs, unsigned long long* __restrict__ dropped) {
+  __shared__ int part[256];
+  __shared__ int part_b[256];
+  const TailMapJob jb = jobs.job[blockIdx.x];
+  const int num = jb.num, reach = jb.reach, T = jb.T, BN = jb.BN;
+  int* const out = jb.out;
+  const int tid = threadIdx.x;
+  const int per = (B + 255) / 256;
+  // donor: smallest length, lowest index on ties (a thread owns a run of rows in index order)
+  int best = 0x7fffffff, best_b = 0x7fffffff;
+  for (int i = 0; i < per; ++i) { const int b = tid * per + i; if (b < B && lens[b] < best) { best = lens[b]; best_b = b; } }
+  part[tid] = best; part_b[tid] = best_b;
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < 256; ++i) if (part[i] < best) { best = part[i]; best_b = part_b[i]; }
+    part_b[0] = best_b;
+  }
+  __syncthreads();
+  const int donor = part_b[0];
+  __syncthreads();
+  const int full = (T + BN - 1) / BN;
+  auto tiles_of = [&](int b) {
+    if (b == donor) return full;
+    long lim = (long)lens[b] * num + reach;
+    lim = lim < 0 ? 0 : (lim > T ? T : lim);
+    return (int)((lim + BN - 1) / BN);
+  };
+  int s = 0;
+  for (int i = 0; i < per; ++i) { const int b = tid * per + i; if (b < B) s += tiles_of(b); }
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) { int run = 0; for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; } }
+  __syncthreads();
+  int run = part[tid];
+  for (int i = 0; i < per; ++i) {
+    const int b = tid * per + i;
+    if (b < B) {
+      out[b] = run;
+      const int n = tiles_of(b);
+      for (int k = 0; k < n; ++k) out[B + 1 + run + k] = b;
+      run += n;
+      if (b == B - 1) {
+        out[B] = run;
+        out[B + 1 + (long)B * full] = donor;
+        if (dropped) atomicAdd(dropped, (unsigned long long)((long)B * full - run));
+      }
+    }
+  }
+}
+size_t launch_tail_map_ints(int B, int T, int BN) { return launch_trim_map_ints(B, T, BN) + 1; }
+void launch_tail_maps(const int* lens, int B, const TailMapJobs& jobs, int n, unsigned long long* dropped, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(tail_map_kernel, dim3(n), dim3(256), 0, s, lens, B, jobs, dropped);
+}
+
+// one workgroup per (row m, utterance b): the columns behind the tiles row b kept, from the donor's row m
+template <bool VEC>
+__global__ void tail_fill_kernel(float* __restrict__ y, int64_t y_bstride, int B, int T, int BN, const int* __restrict__ map) {
+  const int m = blockIdx.x, b = blockIdx.y;
+  const int full = (T + BN - 1) / BN;
+  const int donor = map[B + 1 + (long)B * full];
+  if (b == donor) return;
+  const long c0 = (long)(map[b + 1] - map[b]) * BN;
+  if (c0 >= T) return;
+  const float* src = y + (int64_t)donor * y_bstride + (int64_t)m * T;
+  float* dst = y + (int64_t)b * y_bstride + (int64_t)m * T;
+  if constexpr (VEC) {      // (c0 is a multiple of BN, BN of 4, and so is T)
+    for (long c = c0 + 4 * threadIdx.x; c < T; c += 4 * blockDim.x)
+      *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(src + c);
+  } else {
+    for (long c = c0 + threadIdx.x; c < T; c += blockDim.x) dst[c] = src[c];
+  }
+}
+void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s) {
+  const bool vec = T % 4 == 0 && y_bstride % 4 == 0 && BN % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(tail_fill_kernel<true>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map);
+  else hipLaunchKernelGGL(tail_fill_kernel<false>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map);
+}
+
 // row-exact ragged decode: the rows of a class and their lengths at the decoder's three rates, from host values
 // carried in the kernel arguments (no copy, no synchronisation)
 __global__ void ragged_rows_kernel(const RaggedRowsArg r, int n, int first, int us, int* __restrict__ out, int stride) {

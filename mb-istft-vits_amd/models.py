@@ -699,6 +699,41 @@ class SynthesizerTrn(nn.Module):
             _capi.check(h, _capi.lib().mbv_decode(h, self._ptr(z), self._ptr(g), B, Tp, C.byref(out),
                                                   self._stream()), "mbv_decode")
 
+    def _decode_masked_into(self, z, g, lengths, outs):
+        """`_decode_into` on z * sequence_mask(lengths) (`mbv_decode_masked`): the decoder run `infer` makes, on a z
+        of the caller's.  `lengths`: ints, one per row."""
+        h = self._ensure_handle()
+        dev = self._device()
+        z = z.to(device=dev, dtype=torch.float32).contiguous()
+        B, _, Tp = z.shape
+        lens = torch.as_tensor([int(v) for v in lengths], dtype=torch.int32).to(dev)
+        if lens.shape[0] != B:
+            raise ValueError("lengths must hold one length per row of z")
+        if g is not None:
+            g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
+        out = _capi.MbvOutputs()
+        for name, t in zip(("o", "o_mb", "spec", "phase"), outs):
+            if t is not None:
+                if not t.is_contiguous() or t.shape[0] != B:
+                    raise ValueError("%s: a contiguous block of %d rows expected" % (name, B))
+                setattr(out, name, t.data_ptr())
+        with torch.cuda.device(dev):
+            _capi.check(h, _capi.lib().mbv_decode_masked(h, self._ptr(z), self._ptr(g), self._ptr(lens), B, Tp,
+                                                         C.byref(out), self._stream()), "mbv_decode_masked")
+
+    def tail_plan(self):
+        """Rows (kind, stage, j, q, rate, reach) of `mbv_tail_plan` for this model's decoder (host only)."""
+        cs = self._config_struct()
+        buf = (C.c_int32 * (6 * 64))()
+        n = _capi.lib().mbv_tail_plan(C.byref(cs), buf, 64)
+        if n < 0 or n > 64:
+            raise ValueError("mbv_tail_plan refused the configuration")
+        return [tuple(buf[6 * i:6 * i + 6]) for i in range(n)]
+
+    def tail_dropped(self):
+        """Column tiles the "tail_once" maps left out on this handle so far (`mbv_tail_dropped`; synchronises)."""
+        return int(_capi.lib().mbv_tail_dropped(self._ensure_handle()))
+
     # ------------------------------------------------------------------ streaming decode (stream.py)
     def decoder_context(self):
         """(L, R): the z-frames of left / right context any output sample of frame t depends on, [t - L, t + R]
@@ -1177,7 +1212,7 @@ class SynthesizerTrn(nn.Module):
 
     def set_option(self, name, value):
         """Run-time options of the library (`mbv_set_option`): "splitk" (low-latency split-K for
-        small launches), "istft_exact", "xpost_chunk_bytes", "wn_fused", "dec_streams", "conv_bf16" (0 / 3: opt-in split-bf16
+        small launches), "istft_exact", "xpost_chunk_bytes", "wn_fused", "dec_streams", "tail_once", "conv_bf16" (0 / 3: opt-in split-bf16
         arithmetic in the large conv launches, see include/mbistft_vits.h).  Kept across weight refreshes; a
         handle re-created on another device starts from the defaults again."""
         h = self._ensure_handle()

@@ -619,11 +619,55 @@ int mbv_spectrogram(mbv_model *m, const void *wave, int wave_dtype, const int64_
  * n_fft / hop refused as above). */
 int64_t mbv_spectrogram_frames(int64_t n_samples, int n_fft, int hop);
 
+/* ---- pooled voice conversion: audio requests admitted as decode streams ---------
+ * The front half of mbv_voice_conversion — spectrogram, posterior encoder, forward flow with the source speaker,
+ * reverse flow with the target — for many audio requests as ONE padded run, stopping at z_hat: each row's
+ * (z_hat * y_mask)[:, :frames] lands in a tensor of the request's own, which feeds mbv_decode_chunks like the z of
+ * mbv_synthesize_rows.  In the default mode every such z is BITWISE the z of that request converted alone (n = 1,
+ * t_frames = its own frame count) with the same noise, and at noise_scale 1 bitwise the z_hat * y_mask of
+ * mbv_spectrogram + mbv_voice_conversion on that row: nothing on the posterior path looks behind a row's length, and
+ * the table-reading kernels run the scalar kernels' chains of operations.  With "splitk" the result is deterministic
+ * and within fp32 rounding of the stand-alone call.
+ *
+ * mbv_convert_plan (host only): which requests may share a run, by their frame counts (mbv_spectrogram_frames of the
+ * sample counts, n_fft = 2 (spec_channels - 1)).  Two requests share a class iff enc_q.pre, enc_q.proj and the
+ * coupling layers' pre / post convs, planned for either alone, land on the same side of the conv planner's narrow /
+ * tiled divide; a class is cut into further runs only where B rows padded to the run's longest request would plan
+ * differently, exceed 65535 rows, or exceed what the fused WN layers take (B * channels * t_frames * 4 bytes < 4 GiB).
+ * Runs are numbered in the order of their first request; run_of_request [n] (or NULL) receives each request's run.
+ * "splitk": one class.  Returns the number of runs, -1 on a bad argument (n < 1, a count < 1 or beyond that limit).
+ *
+ * mbv_convert_rows: one run.  rows_host is HOST memory and travels as kernel arguments (free it on return); the
+ * spectrogram kernel reads every row's samples in place through the table (no padded copy of the audio) and writes
+ * the posterior encoder's channel-padded input itself.  t_frames = the longest row's frame count (the run is planned
+ * at that width; any other value is refused); hop / win as
+ * mbv_spectrogram takes them.  g_out fp32 [n, gin] device receives emb_g(sid_tgt), the decoder's conditioning.
+ * Refused before any launch: a model without speakers (the reference's assertion text), "conv_bf16", a row without
+ * samples, with 0 frames or more than t_frames, a speaker id outside [0, n_speakers), noise_scale < 0, noise missing
+ * where noise_scale != 0, rows that mbv_convert_plan would not put into one run, a run the fused WN layers do not
+ * take (option "wn_fused" off).  No host synchronisation (beyond the first call's table upload for a win).
+ *
+ * mbv_converter_runs: posterior-encoder runs mbv_convert_rows made on this handle since mbv_create. */
+typedef struct mbv_convert_row {
+  const void *wave;              /* DEVICE [samples] at the model's rate, read in place */
+  int64_t samples;
+  int32_t wave_dtype;            /* MBV_WAVE_F32 or MBV_WAVE_PCM16 */
+  int32_t sid_src, sid_tgt;
+  const float *noise;            /* DEVICE [inter, frames], this row's own draw (not read at noise_scale 0) */
+  float noise_scale;
+  float *z;                      /* DEVICE [inter, frames], the request's own tensor */
+} mbv_convert_row;
+int mbv_convert_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_frames, int32_t *run_of_request);
+int mbv_convert_rows(mbv_model *m, const mbv_convert_row *rows_host, int n, int t_frames, int hop, int win,
+                     float *g_out, void *stream);
+int64_t mbv_converter_runs(mbv_model *m);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"
  * [B,1,T], "x_post" [B,72,F], "dec_conv_pre", "dec_up_0", "dec_res_0",
- * "dec_up_1", "dec_res_1".  Returns the element count, or < 0 on error;
+ * "dec_up_1", "dec_res_1"; after mbv_convert_rows "convert_ypad" [B, cin_pad, T], the posterior encoder's
+ * channel-padded input as the spectrogram kernel wrote it (cin_pad = spec_channels rounded up to 32).  Returns the element count, or < 0 on error;
  * dst == NULL only queries the count. */
 int64_t mbv_read_stage(mbv_model *m, const char *name, float *dst, int64_t capacity,
                        void *stream);

@@ -31,6 +31,7 @@ SYMBOLS = [
     "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
     "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
     "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
+    "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
 ]
 
 
@@ -79,6 +80,12 @@ class MbvRow(C.Structure):
     """mbv_row of include/mbistft_vits.h (mbv_synthesize_rows)."""
     _fields_ = [("noise", C.c_void_p), ("noise_stride", C.c_int64), ("noise_scale", C.c_float), ("keep", C.c_int32),
                 ("z", C.c_void_p)]
+
+
+class MbvConvertRow(C.Structure):
+    """mbv_convert_row of include/mbistft_vits.h (mbv_convert_rows)."""
+    _fields_ = [("wave", C.c_void_p), ("samples", C.c_int64), ("wave_dtype", C.c_int32), ("sid_src", C.c_int32),
+                ("sid_tgt", C.c_int32), ("noise", C.c_void_p), ("noise_scale", C.c_float), ("z", C.c_void_p)]
 
 
 class MbvAlignOutputs(C.Structure):
@@ -204,14 +211,16 @@ def lib():
     L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
-    # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five and
-    # the three that came with "tail_once" may be absent there, and calling one then raises AttributeError.
+    # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
+    # three that came with "tail_once" and pooled conversion's three may be absent there, and calling one then raises
+    # AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
                 "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
                 "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs",
-                "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked") if os.environ.get("MBV_LIB") else ()
+                "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
+                "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -240,6 +249,11 @@ def lib():
         L.mbv_tail_dropped.argtypes = [vp]
         L.mbv_tail_dropped.restype = C.c_int64
         L.mbv_decode_masked.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
+    if hasattr(L, "mbv_convert_rows") or not optional:
+        L.mbv_convert_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.mbv_convert_rows.argtypes = [vp, C.POINTER(MbvConvertRow), i32, i32, i32, i32, vp, vp]
+        L.mbv_converter_runs.argtypes = [vp]
+        L.mbv_converter_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -113,6 +113,7 @@ struct mbv_model {
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
+  int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
   // state of the last encode
@@ -2870,17 +2871,20 @@ namespace {
 // stats [B, 2I, T], gc [B, 2 H kEncQLayers], ustart wn_units_ints(B, T)
 struct PosteriorBufs { float *ypad, *hbuf, *acts, *skip, *stats, *gc; int* ustart; };
 // enc_q (models.py:239-246): pre * mask -> WN(g) -> proj * mask -> z = (m_q + noise * noise_scale * exp(logs_q)) * mask.
-// g == nullptr: the unconditioned WN of a single-speaker model.
+// g == nullptr: the unconditioned WN of a single-speaker model.  y == nullptr: p.ypad holds the channel-padded input
+// already (mbv_convert_rows: the spectrogram kernel wrote it); rows: per-row noise and noise_scale (the same entry).
 int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, const float* noise, float noise_scale,
-              const PosteriorBufs& p, float* z, int B, int T, hipStream_t s) {
+              const PosteriorBufs& p, float* z, int B, int T, hipStream_t s, const AdmitSynRow* rows = nullptr) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, SC = c.spec_channels;
   const auto& Q = m->encq;
   const size_t BT = (size_t)B * T;
   // the 1x1 `pre` conv reads channel groups of 32: zero-pad spec_channels (513) to a multiple of 32
-  launch_fill(p.ypad, 0.f, (int64_t)BT * Q.cin_pad, s);
-  HIPCHK(m, hipMemcpy2DAsync(p.ypad, (size_t)Q.cin_pad * T * 4, y, (size_t)SC * T * 4, (size_t)SC * T * 4, B,
-                             hipMemcpyDeviceToDevice, s));
+  if (y) {
+    launch_fill(p.ypad, 0.f, (int64_t)BT * Q.cin_pad, s);
+    HIPCHK(m, hipMemcpy2DAsync(p.ypad, (size_t)Q.cin_pad * T * 4, y, (size_t)SC * T * 4, (size_t)SC * T * 4, B,
+                               hipMemcpyDeviceToDevice, s));
+  }
   const int64_t bsH = (int64_t)H * T;
   {
     ConvArgs a = conv_args(m, Q.pre, p.ypad, (int64_t)Q.cin_pad * T, T, p.hbuf, bsH, T, B);
@@ -2893,7 +2897,8 @@ int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, con
     a.in_lens = lens; a.out_lens = lens;
     launch_conv1d(a, s);
   }
-  launch_posterior_sample(p.stats, noise, lens, z, B, I, T, s, noise_scale);
+  if (rows) launch_posterior_sample_rows(p.stats, rows, lens, z, B, I, T, s);
+  else launch_posterior_sample(p.stats, noise, lens, z, B, I, T, s, noise_scale);
   return 0;
 }
 // the forward flow (models.py:207-211), in place on z
@@ -3366,6 +3371,28 @@ const char* spectrogram_args_error(int n_fft, int hop, int win) {
   if (win < 1 || win > n_fft) return "win must be in [1, n_fft]";
   return nullptr;
 }
+// the handle's twiddle and window tables of an (n_fft, win) pair; the first call builds them in float64 on the host
+// and uploads them once (synchronous copy).  0 on success, else m->fail(...) has been called.
+int spectrogram_tables_of(mbv_model* m, const char* who, int n_fft, int win, const mbv_model::SpectrogramTables** out) {
+  const std::array<int, 2> key{n_fft, win};
+  auto it = m->spec_tables.find(key);
+  if (it == m->spec_tables.end()) {
+    std::vector<float> tw, window;
+    spectrogram_tables(n_fft, win, &tw, &window);
+    mbv_model::SpectrogramTables t;
+    HIPCHK(m, hipMalloc((void**)&t.tw, tw.size() * sizeof(float)));
+    if (hipMalloc((void**)&t.win, window.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(t.win, window.data(), window.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(t.tw);
+      if (t.win) (void)hipFree(t.win);
+      return m->fail("%s: uploading the twiddle / window tables failed", who);
+    }
+    it = m->spec_tables.emplace(key, t).first;
+  }
+  *out = &it->second;
+  return 0;
+}
 }  // namespace
 
 int64_t mbv_spectrogram_frames(int64_t n_samples, int n_fft, int hop) {
@@ -3390,28 +3417,190 @@ int mbv_spectrogram(mbv_model* m, const void* wave, int wave_dtype, const int64_
   if (F > 0 && !spec) return m->fail("mbv_spectrogram: spec is NULL");
   if (F / spectrogram_block_frames(n_fft, hop) >= 0x7fffffff) return m->fail("mbv_spectrogram: too many frames per row");
   DEVICE_GUARD(m);
-  const std::array<int, 2> key{n_fft, win};
-  auto it = m->spec_tables.find(key);
-  if (it == m->spec_tables.end()) {
-    // first call for this (n_fft, win): build in float64 on the host, upload once (synchronous copy)
-    std::vector<float> tw, window;
-    spectrogram_tables(n_fft, win, &tw, &window);
-    mbv_model::SpectrogramTables t;
-    HIPCHK(m, hipMalloc((void**)&t.tw, tw.size() * sizeof(float)));
-    if (hipMalloc((void**)&t.win, window.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(t.win, window.data(), window.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(t.tw);
-      if (t.win) (void)hipFree(t.win);
-      return m->fail("mbv_spectrogram: uploading the twiddle / window tables failed");
-    }
-    it = m->spec_tables.emplace(key, t).first;
-  }
-  launch_spectrogram(wave, wave_dtype, valid_samples, B, in_stride, n_fft, hop, it->second.tw, it->second.win, spec, F,
+  const mbv_model::SpectrogramTables* tab = nullptr;
+  if (spectrogram_tables_of(m, "mbv_spectrogram", n_fft, win, &tab)) return 1;
+  launch_spectrogram(wave, wave_dtype, valid_samples, B, in_stride, n_fft, hop, tab->tw, tab->win, spec, F,
                      spec_lengths, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
+
+// ------------------------------------------------------------------ pooled voice conversion
+namespace {
+// Which side of the planner's narrow / tiled divide the convs of the posterior path take when B utterances padded to
+// T frames run together: enc_q.pre (on the channel-padded spectrogram), enc_q.proj, and a coupling layer's pre / post
+// (the shapes run_enc_q and run_coupling build; the fused WN layers fold the latter two and are no conv launches).
+void posterior_signature(const mbv_config& c, int splitk, int B, int T, std::vector<char>* sig) {
+  static const int kSome = 0;                       // "a length table is given"
+  const int H = c.hidden_channels, I = c.inter_channels, cpad = (int)align_up(c.spec_channels, 32);
+  auto conv = [&](int Cin, int64_t x_bstride, int M, int64_t y_bstride, bool in_lens, int epi) {
+    ConvArgs a{};
+    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = 1; a.dil = 1; a.pad_left = 0;
+    a.Tin = T; a.x_rstride = T; a.x_bstride = x_bstride;
+    a.T = T; a.y_bstride = y_bstride; a.epi = epi; a.in_slope = 1.f; a.out_scale = 1.f; a.B = B;
+    a.out_lens = &kSome;
+    if (in_lens) a.in_lens = &kSome;
+    a.couple_sign = 1.f;
+    a.splitk = splitk;
+    const int r = conv1d_plan(a, false).route;
+    sig->push_back(r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH);
+  };
+  sig->clear();
+  conv(cpad, (int64_t)cpad * T, H, (int64_t)H * T, false, EPI_STORE);            // enc_q.pre
+  conv(H, (int64_t)H * T, 2 * I, (int64_t)2 * I * T, true, EPI_STORE);           // enc_q.proj
+  conv(I / 2, (int64_t)I * T, H, (int64_t)H * T, false, EPI_STORE);              // flow.pre
+  conv(H, (int64_t)H * T, I / 2, (int64_t)I * T, true, EPI_COUPLE);              // flow.post
+}
+
+// a run of B rows padded to T frames stays inside the grid and inside what the fused WN layers take
+bool convert_run_fits(const mbv_config& c, int B, int T) {
+  return B <= 65535 && wn_fused_fits(B, c.hidden_channels, T) && wn_fused_fits(B, c.inter_channels, T);
+}
+
+// Runs of one pooled conversion for requests of t_frames[i] frames, built as admit_plan builds its own: requests share
+// a run iff their posterior_signature at B = 1 agree, and a run is cut where the padded run would plan differently,
+// exceed 65535 rows or exceed the fused WN layers' 32-bit offsets.  Split-K: one class.  -1 on a bad argument (a
+// request that alone is beyond the fused WN layers included).
+int convert_plan(const mbv_config& c, int splitk, int n, const int32_t* t_frames, int32_t* run_of_request) {
+  if (n <= 0 || !t_frames) return -1;
+  for (int i = 0; i < n; ++i)
+    if (t_frames[i] < 1 || !convert_run_fits(c, 1, t_frames[i])) return -1;
+  struct Run { std::vector<char> sig; int B = 0, T = 0; bool open = true; };
+  std::vector<Run> runs;
+  std::map<int, std::vector<char>> sig_of;          // frame count -> its stand-alone signature
+  std::vector<char> sig;
+  for (int i = 0; i < n; ++i) {
+    const int T = t_frames[i];
+    auto it = sig_of.find(T);
+    if (it == sig_of.end()) {
+      if (splitk) sig.clear(); else posterior_signature(c, 0, 1, T, &sig);
+      it = sig_of.emplace(T, sig).first;
+    }
+    int r = -1;
+    for (size_t k = 0; k < runs.size() && r < 0; ++k) {
+      if (!runs[k].open || runs[k].sig != it->second) continue;
+      const int Tn = T > runs[k].T ? T : runs[k].T;
+      bool fits = convert_run_fits(c, runs[k].B + 1, Tn);
+      if (fits && !splitk) { posterior_signature(c, 0, runs[k].B + 1, Tn, &sig); fits = sig == runs[k].sig; }
+      if (fits) { r = (int)k; runs[k].T = Tn; ++runs[k].B; }
+      else runs[k].open = false;                    // full: later requests of the class start a new run
+    }
+    if (r < 0) {
+      Run nr; nr.sig = it->second; nr.B = 1; nr.T = T;
+      runs.push_back(nr);
+      r = (int)runs.size() - 1;
+    }
+    if (run_of_request) run_of_request[i] = r;
+  }
+  return (int)runs.size();
+}
+}  // namespace
+
+int mbv_convert_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_frames, int32_t* run_of_request) {
+  if (!cfg) return -1;
+  return convert_plan(*cfg, splitk != 0, n, t_frames, run_of_request);
+}
+
+int64_t mbv_converter_runs(mbv_model* m) { return m ? m->converter_runs : -1; }
+
+int mbv_convert_rows(mbv_model* m, const mbv_convert_row* rows_host, int n, int t_frames, int hop, int win, float* g_out,
+                     void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_convert_rows";
+  if (!m->finalized) return m->fail("weights not finalized");
+  const mbv_config& c = m->cfg;
+  if (c.n_speakers <= 0 || !m->emb_g.present)
+    return m->fail("n_speakers have to be larger than 0.");              // models.py:791 assert
+  if (!rows_host || !g_out || n <= 0 || t_frames <= 0) return m->fail("%s: bad arguments", who);
+  if (m->conv_bf16) return m->fail("%s: pooled conversion is not built for the \"conv_bf16\" mode", who);
+  const int n_fft = 2 * (c.spec_channels - 1);
+  if (const char* why = spectrogram_args_error(n_fft, hop, win))
+    return m->fail("%s: %s (n_fft = 2 (spec_channels - 1) = %d)", who, why, n_fft);
+  const int B = n, T = t_frames, H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
+  std::vector<int32_t> fr(B);
+  int longest = 0;
+  for (int i = 0; i < B; ++i) {
+    const mbv_convert_row& k = rows_host[i];
+    if (!k.wave || !k.z || k.samples < 1) return m->fail("%s: row %d: wave or z missing, or no samples", who, i);
+    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
+      return m->fail("%s: row %d: unknown wave_dtype %d", who, i, k.wave_dtype);
+    const int64_t f = spectrogram_frames(k.samples, n_fft, hop);
+    if (f < 1 || f > T) return m->fail("%s: row %d: %lld frames outside [1, %d]", who, i, (long long)f, T);
+    fr[i] = (int32_t)f;
+    if (fr[i] > longest) longest = fr[i];
+    if (k.sid_src < 0 || k.sid_src >= c.n_speakers || k.sid_tgt < 0 || k.sid_tgt >= c.n_speakers)
+      return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, c.n_speakers);
+    if (!(k.noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
+    if (k.noise_scale != 0.f && !k.noise) return m->fail("%s: row %d: noise missing", who, i);
+  }
+  // the run is planned at its longest row (mbv_convert_plan): a wider launch could take a route no row takes alone
+  if (T != longest)
+    return m->fail("%s: t_frames is %d, the longest row has %d frames: a run is padded to its longest row", who, T, longest);
+  // the rows must be ONE run of the plan: a second class in the launch would move some row to another route
+  if (convert_plan(c, m->splitk, B, fr.data(), nullptr) != 1)
+    return m->fail("%s: the rows belong to more than one run of mbv_convert_plan", who);
+  // the whole run must take the route every row takes alone: the fused WN layers, which work on 16-frame half-units
+  // below each row's own length (the two-launch layers route on T)
+  const auto& Q = m->encq;
+  bool fused = wn_takes_fused(m, Q.in, Q.in16, B, T) && wn_fused_fits(B, I, T);
+  for (int f = 0; f < kNFlows; ++f) fused = fused && wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T);
+  if (!fused)
+    return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
+                   "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  const mbv_model::SpectrogramTables* tab = nullptr;
+  if (spectrogram_tables_of(m, who, n_fft, win, &tab)) return 1;
+  const size_t BT = (size_t)B * T;
+  const size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 3 * I) + (size_t)B * (gin + 2 * H * mbv_model::kEncQLayers + 1)) * 4 +
+                      wn_units_ints(B, T) * 4 + (size_t)B * (sizeof(ConvertRow) + sizeof(AdmitSynRow) + 16) + 64 * 256;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  m->stages.clear();
+  float* ypad = sc.take<float>(BT * Q.cin_pad);
+  m->stages["convert_ypad"] = StageRef{ypad, (int64_t)(BT * Q.cin_pad)};
+  float* hbuf = sc.take<float>(BT * H);
+  float* acts = sc.take<float>(BT * H);
+  float* skip = sc.take<float>(BT * H);
+  float* stats = sc.take<float>(BT * 2 * I);
+  float* z = sc.take<float>(BT * I);
+  float* g_src = sc.take<float>((size_t)B * gin);
+  float* gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
+  int* lens = sc.take<int>(B);
+  int* ustart = sc.take<int>(wn_units_ints(B, T));
+  ConvertRow* crows = sc.take<ConvertRow>(B);
+  AdmitSynRow* srows = sc.take<AdmitSynRow>(B);
+  int64_t* sid_src = sc.take<int64_t>(B);
+  int64_t* sid_tgt = sc.take<int64_t>(B);
+  int max_keep = 0;
+  for (int f = 0; f < B; f += kAdmitChunk) {
+    ConvertRowsArg cr{};
+    AdmitSynRowsArg sr{};
+    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
+    for (int i = 0; i < nn; ++i) {
+      const mbv_convert_row& k = rows_host[f + i];
+      cr.row[i] = ConvertRow{k.wave, k.samples, k.wave_dtype, fr[f + i], k.sid_src, k.sid_tgt};
+      sr.row[i] = AdmitSynRow{k.noise, fr[f + i], k.noise_scale, fr[f + i], k.z};
+      if (fr[f + i] > max_keep) max_keep = fr[f + i];
+    }
+    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
+    launch_admit_syn_rows(sr, nn, f, srows, s);
+  }
+  ++m->converter_runs;
+  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
+  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_out, B, gin, c.n_speakers, nullptr, s);
+  launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, ypad, Q.cin_pad, T, s);
+  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
+  if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows)) return 1;
+  // forward flow with the source speaker (models.py:795), then reverse with the target (:796), in place
+  run_flow_forward(m, z, g_src, pb, lens, B, T, s);
+  for (int f = kNFlows - 1; f >= 0; --f)
+    run_coupling(m, f, true, z, g_out, hbuf, acts, skip, gc, ustart, lens, B, T, s);
+  launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
 
 int64_t mbv_read_stage(mbv_model* m, const char* name, float* dst, int64_t capacity, void* stream) {
   if (!m || !name) return -1;

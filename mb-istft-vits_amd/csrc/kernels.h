@@ -441,6 +441,29 @@ void launch_align_status(const int* bad_x, const int* bad_y, const int* mas, int
 // z = (m + noise * noise_scale * exp(logs)) * mask   (PosteriorEncoder, models.py:245); stats = [B, 2I, T]
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,
                              int I, int T, hipStream_t s, float noise_scale = 1.f);
+
+// ---------------------------------------------------------------- pooled voice conversion: table-reading variants
+// One padded posterior run for many audio requests (capi.hip mbv_convert_rows), in the style of pooled admission
+// above: each variant is the scalar kernel's own body behind a template flag.
+struct ConvertRow {
+  const void* wave;            // this row's samples, in place: fp32 (dtype 0) or int16 scaled by 1 / 32768 (dtype 1)
+  int64_t samples;
+  int dtype, frames;           // frames = spectrogram_frames(samples): the row's length in the run
+  int sid_src, sid_tgt;
+};
+struct ConvertRowsArg { ConvertRow row[kAdmitChunk]; };
+// n table rows by value -> dst[first + i], and the columns the existing launches read: lens (frames), the two sids
+void launch_convert_rows(const ConvertRowsArg& r, int n, int first, ConvertRow* dst, int* lens, int64_t* sid_src,
+                         int64_t* sid_tgt, hipStream_t s);
+// launch_spectrogram for row b = rows[b].wave over rows[b].samples, written into dst [B, cpad, F] (cpad >=
+// n_fft / 2 + 1: enc_q's channel-padded input): EXACT zeros in channels n_fft / 2 + 1 .. cpad and in frames at and
+// past the row's own count, so every element of dst is written
+void launch_spectrogram_rows(const ConvertRow* rows, int B, int n_fft, int hop, const float* tw, const float* win,
+                             float* dst, int cpad, int64_t F, hipStream_t s);
+// launch_posterior_sample with row b's noise block [I, rows[b].noise_stride] and rows[b].noise_scale; at scale 0
+// (and behind the block) the scalar kernel's null-noise branch
+void launch_posterior_sample_rows(const float* stats, const AdmitSynRow* rows, const int* lens, float* z, int B,
+                                  int I, int T, hipStream_t s);
 void launch_sequence_mask(const int* lens, float* mask, int B, int T, hipStream_t s);   // commons.py:121
 void launch_lens_to_i32(const int64_t* lens, int* out, int B, int T, int* bad, hipStream_t s);
 

@@ -459,22 +459,54 @@ void launch_pcm16(const float* x, const int64_t* lens, int B, int64_t stride, in
                      auto_normalize, out);
 }
 
+// ROWS (pooled voice conversion, kernels.h): row b takes noise_scale and its noise block [I, noise_stride] from
+// rows[b]; frames at and past noise_stride (behind the row's own length) read no noise — they are masked to 0
+template <bool ROWS>
 __global__ void posterior_sample_kernel(const float* stats, const float* noise, const int* lens,
-                                        float* z, int I, int T, float noise_scale) {
+                                        float* z, int I, int T, float noise_scale, const AdmitSynRow* rows) {
   const int b = blockIdx.z, c = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   const float m = stats[((int64_t)b * 2 * I + c) * T + t];
   const float lg = stats[((int64_t)b * 2 * I + I + c) * T + t];
   const int64_t o = ((int64_t)b * I + c) * T + t;
-  const float v = noise ? m + (noise[o] * noise_scale) * expf(lg) : m;   // (noise_scale 1: exact)
+  int64_t no = o;
+  if (ROWS) {
+    const AdmitSynRow r = rows[b];
+    noise_scale = r.noise_scale;
+    noise = (noise_scale != 0.f && t < r.noise_stride) ? r.noise : nullptr;
+    no = (int64_t)c * r.noise_stride + t;
+  }
+  const float v = noise ? m + (noise[no] * noise_scale) * expf(lg) : m;   // (noise_scale 1: exact)
   z[o] = t < lens[b] ? v : 0.f;
 }
 
 void launch_posterior_sample(const float* stats, const float* noise, const int* lens, float* z, int B,
                              int I, int T, hipStream_t s, float noise_scale) {
   dim3 grid((T + 127) / 128, I, B);
-  hipLaunchKernelGGL(posterior_sample_kernel, grid, dim3(128), 0, s, stats, noise, lens, z, I, T, noise_scale);
+  hipLaunchKernelGGL(posterior_sample_kernel<false>, grid, dim3(128), 0, s, stats, noise, lens, z, I, T, noise_scale,
+                     nullptr);
+}
+
+void launch_posterior_sample_rows(const float* stats, const AdmitSynRow* rows, const int* lens, float* z, int B,
+                                  int I, int T, hipStream_t s) {
+  dim3 grid((T + 127) / 128, I, B);
+  hipLaunchKernelGGL(posterior_sample_kernel<true>, grid, dim3(128), 0, s, stats, nullptr, lens, z, I, T, 0.f, rows);
+}
+
+__global__ void convert_rows_kernel(const ConvertRowsArg r, int n, int first, ConvertRow* dst, int* lens,
+                                    int64_t* sid_src, int64_t* sid_tgt) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  const ConvertRow k = r.row[i];
+  dst[first + i] = k;
+  lens[first + i] = k.frames;
+  sid_src[first + i] = k.sid_src;
+  sid_tgt[first + i] = k.sid_tgt;
+}
+void launch_convert_rows(const ConvertRowsArg& r, int n, int first, ConvertRow* dst, int* lens, int64_t* sid_src,
+                         int64_t* sid_tgt, hipStream_t s) {
+  hipLaunchKernelGGL(convert_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst, lens, sid_src, sid_tgt);
 }
 
 __global__ void sequence_mask_kernel(const int* lens, float* mask, int T) {

@@ -89,12 +89,16 @@ __device__ __forceinline__ void stockham_pass(float2* buf, int Ns, int t, const 
 // ((FB - 1) hop + n_fft samples, padding included) is staged in LDS once, zero outside [0, valid).
 // G = 256 / (N / 8) frames are transformed at a time, one per team; the magnitudes go to an LDS tile
 // [N + 1][FB + 1] that is then stored bin by bin as runs of FB consecutive frames.
+// ROWS (pooled voice conversion, kernels.h): row b's samples, their count and their dtype come from rows[b] (x, valid,
+// in_stride and scale are not used: the table travels in global memory, the LDS layout is the scalar kernel's), and
+// the destination row has KC = cpad >= N + 1 channels, those from N + 1 on written as zeros.
 // ---------------------------------------------------------------------------------------------------
-template <int LOGN, typename In>
+template <int LOGN, typename In, bool ROWS>
 __global__ void __launch_bounds__(kThreads)
 spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride, float scale,
                    int hop, int pad, const float2* __restrict__ tw, const float* __restrict__ win, int FB,
-                   float* __restrict__ spec, int64_t F, int64_t* __restrict__ spec_lengths) {
+                   float* __restrict__ spec, int64_t F, int64_t* __restrict__ spec_lengths,
+                   const ConvertRow* __restrict__ rows, int cpad) {
   constexpr int N = 1 << LOGN, NFFT = 2 * N, T = N / 8, G = kThreads / T;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float2* work = reinterpret_cast<float2*>(smem);                 // [G][N]
@@ -103,8 +107,17 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
   float* xs = tile + (N + 1) * FBp;                               // [(FB - 1) hop + n_fft]
 
   const int b = blockIdx.y;
+  const int KC = ROWS ? cpad : N + 1;                             // channels of a destination row
   int64_t v = in_stride;
-  if (valid) {
+  const void* xr = nullptr;
+  bool pcm = false;
+  if (ROWS) {
+    const ConvertRow r = rows[b];
+    v = r.samples < 0 ? 0 : r.samples;
+    xr = r.wave;
+    pcm = r.dtype == 1;
+    scale = pcm ? 1.f / 32768.f : 1.f;
+  } else if (valid) {
     v = valid[b];
     v = v < 0 ? 0 : (v > in_stride ? in_stride : v);
   }
@@ -114,11 +127,11 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
   const int64_t f0 = (int64_t)blockIdx.x * FB;
   if (f0 >= F) return;
   const int nf = (int)(F - f0 < FB ? F - f0 : FB);               // frames of this block inside the output
-  float* out = spec + (int64_t)b * (N + 1) * F + f0;
+  float* out = spec + (int64_t)b * KC * F + f0;
   const int lg_fb = __ffs(FB) - 1;                                // FB is a power of two
 
   if (f0 >= nfr) {                                                // past the row's length: zeros only
-    for (int e = threadIdx.x; e < (N + 1) * FB; e += kThreads) {
+    for (int e = threadIdx.x; e < KC * FB; e += kThreads) {
       const int k = e >> lg_fb, fl = e & (FB - 1);
       if (fl < nf) out[(int64_t)k * F + fl] = 0.f;
     }
@@ -135,7 +148,10 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
     for (int u = 0; u < 8; ++u) {
       const int i = i0 + u * kThreads + threadIdx.x;
       const int64_t j = j0 + i;
-      r[u] = (i < S && j >= 0 && j < v) ? (float)xb[j] * scale : 0.f;
+      if (ROWS)
+        r[u] = (i < S && j >= 0 && j < v) ? (pcm ? (float)((const short*)xr)[j] : ((const float*)xr)[j]) * scale : 0.f;
+      else
+        r[u] = (i < S && j >= 0 && j < v) ? (float)xb[j] * scale : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -175,9 +191,9 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
     __syncthreads();                     // buf is rewritten by the next group's first pass
   }
 
-  for (int e = threadIdx.x; e < (N + 1) * FB; e += kThreads) {
+  for (int e = threadIdx.x; e < KC * FB; e += kThreads) {
     const int k = e >> lg_fb, fl = e & (FB - 1);
-    if (fl < nf) out[(int64_t)k * F + fl] = tile[k * FBp + fl];
+    if (fl < nf) out[(int64_t)k * F + fl] = (!ROWS || k <= N) ? tile[k * FBp + fl] : 0.f;
   }
 }
 
@@ -189,19 +205,35 @@ void launch_logn(const void* x, int dtype, const int64_t* valid, int B, int64_t 
   const size_t lds = spectrogram_lds_bytes(1 << (LOGN + 1), hop, FB);
   const dim3 grid((unsigned)nbx, (unsigned)B), block(kThreads);
   static const bool attr = [] {                   // dynamic LDS past 64 KiB must be allowed per kernel
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spectrogram_kernel<LOGN, short>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spectrogram_kernel<LOGN, short, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSpectrogramMaxLds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spectrogram_kernel<LOGN, float>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spectrogram_kernel<LOGN, float, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSpectrogramMaxLds);
     return true;
   }();
   (void)attr;
   if (dtype == 1)
-    hipLaunchKernelGGL((spectrogram_kernel<LOGN, short>), grid, block, lds, s, (const short*)x, valid, in_stride,
-                       1.f / 32768.f, hop, pad, tw, win, FB, spec, F, spec_lengths);
+    hipLaunchKernelGGL((spectrogram_kernel<LOGN, short, false>), grid, block, lds, s, (const short*)x, valid, in_stride,
+                       1.f / 32768.f, hop, pad, tw, win, FB, spec, F, spec_lengths, nullptr, 0);
   else
-    hipLaunchKernelGGL((spectrogram_kernel<LOGN, float>), grid, block, lds, s, (const float*)x, valid, in_stride,
-                       1.f, hop, pad, tw, win, FB, spec, F, spec_lengths);
+    hipLaunchKernelGGL((spectrogram_kernel<LOGN, float, false>), grid, block, lds, s, (const float*)x, valid, in_stride,
+                       1.f, hop, pad, tw, win, FB, spec, F, spec_lengths, nullptr, 0);
+}
+
+template <int LOGN>
+void launch_rows_logn(const ConvertRow* rows, int B, int hop, int pad, const float2* tw, const float* win, int FB,
+                      float* dst, int cpad, int64_t F, hipStream_t s) {
+  const int64_t nbx = F > 0 ? (F + FB - 1) / FB : 1;
+  const size_t lds = spectrogram_lds_bytes(1 << (LOGN + 1), hop, FB);
+  const dim3 grid((unsigned)nbx, (unsigned)B), block(kThreads);
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spectrogram_kernel<LOGN, float, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSpectrogramMaxLds);
+    return true;
+  }();
+  (void)attr;
+  hipLaunchKernelGGL((spectrogram_kernel<LOGN, float, true>), grid, block, lds, s, (const float*)nullptr, nullptr,
+                     (int64_t)0, 1.f, hop, pad, tw, win, FB, dst, F, nullptr, rows, cpad);
 }
 
 }  // namespace
@@ -248,6 +280,20 @@ void launch_spectrogram(const void* x, int dtype, const int64_t* valid, int B, i
     case 1024: launch_logn<9>(x, dtype, valid, B, in_stride, hop, pad, t2, win, FB, spec, F, spec_lengths, s); break;
     case 2048: launch_logn<10>(x, dtype, valid, B, in_stride, hop, pad, t2, win, FB, spec, F, spec_lengths, s); break;
     default: launch_logn<11>(x, dtype, valid, B, in_stride, hop, pad, t2, win, FB, spec, F, spec_lengths, s); break;
+  }
+}
+
+void launch_spectrogram_rows(const ConvertRow* rows, int B, int n_fft, int hop, const float* tw, const float* win,
+                             float* dst, int cpad, int64_t F, hipStream_t s) {
+  const int pad = (n_fft - hop) / 2;
+  const int FB = spectrogram_block_frames(n_fft, hop);
+  const float2* t2 = reinterpret_cast<const float2*>(tw);
+  switch (n_fft) {
+    case 256: launch_rows_logn<7>(rows, B, hop, pad, t2, win, FB, dst, cpad, F, s); break;
+    case 512: launch_rows_logn<8>(rows, B, hop, pad, t2, win, FB, dst, cpad, F, s); break;
+    case 1024: launch_rows_logn<9>(rows, B, hop, pad, t2, win, FB, dst, cpad, F, s); break;
+    case 2048: launch_rows_logn<10>(rows, B, hop, pad, t2, win, FB, dst, cpad, F, s); break;
+    default: launch_rows_logn<11>(rows, B, hop, pad, t2, win, FB, dst, cpad, F, s); break;
   }
 }
 

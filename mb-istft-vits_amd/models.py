@@ -99,6 +99,84 @@ class Request:
         return "Request(%d tokens, sid=%r%s)" % (self.x.numel(), self.sid, "" if self.durations is None else ", durations")
 
 
+class ConvertRequest:
+    """One utterance of a pooled voice conversion (`SynthesizerTrn.convert_streams`, `StreamPool.admit`,
+    `PcmPool.admit`): the arguments one `convert_stream` call takes, for one recording.
+
+      wave               1-D int16 (scaled by 1 / 32768, as data_utils.py:75 does) or fp32 samples at `in_sr`, on either
+                         device; at least one
+      sid_src, sid_tgt   speaker ids (ints)
+      model_sr, hop_size, win_size      the model's data config (sampling_rate, hop_length, win_length)
+      in_sr              the rate of `wave`; None = model_sr
+      noise_scale        scale of the posterior draw (1 = `voice_conversion`), >= 0
+      chunk_frames, max_chunk_frames    as `dec_stream`
+    n_fft is not a field: it is 2 (spec_channels - 1) of the model the request is given to, which also checks
+    win_size <= n_fft.  Everything that can be checked without the model is checked here (ValueError / TypeError)."""
+
+    __slots__ = ("wave", "sid_src", "sid_tgt", "model_sr", "hop_size", "win_size", "in_sr", "noise_scale",
+                 "chunk_frames", "max_chunk_frames")
+
+    MAX_N_FFT = 4096                # the largest transform `spectrogram` is built for
+
+    def __init__(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
+                 chunk_frames=32, max_chunk_frames=256):
+        if not torch.is_tensor(wave):
+            wave = torch.as_tensor(wave)
+        if wave.dtype not in (torch.int16, torch.float32):
+            raise TypeError("ConvertRequest: wave must be int16 or float32, got %s" % wave.dtype)
+        if wave.dim() != 1:
+            raise ValueError("ConvertRequest: wave must be 1-D samples (one recording), got shape %s" % (tuple(wave.shape),))
+        if wave.numel() < 1:
+            raise ValueError("ConvertRequest: empty wave")
+        self.wave = wave.contiguous()
+        sids = []
+        for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
+            if torch.is_tensor(sid):
+                if sid.numel() != 1:
+                    raise ValueError("ConvertRequest: %s must be one speaker id" % name)
+                sid = sid.reshape(()).item()
+            if isinstance(sid, bool) or not isinstance(sid, (int, float, np.integer, np.floating)) or int(sid) != sid:
+                raise TypeError("ConvertRequest: %s must be an integer" % name)
+            sids.append(int(sid))
+        self.sid_src, self.sid_tgt = sids
+        self.model_sr, self.hop_size, self.win_size = int(model_sr), int(hop_size), int(win_size)
+        self.in_sr = self.model_sr if in_sr is None else int(in_sr)
+        if self.model_sr <= 0 or self.in_sr <= 0:
+            raise ValueError("ConvertRequest: sample rates must be positive")
+        if self.hop_size < 1:
+            raise ValueError("ConvertRequest: hop_size must be >= 1")
+        if not 1 <= self.win_size <= self.MAX_N_FFT:
+            raise ValueError("ConvertRequest: win_size %d outside [1, n_fft] (n_fft <= %d)" % (self.win_size, self.MAX_N_FFT))
+        self.noise_scale = float(noise_scale)
+        if not math.isfinite(self.noise_scale) or self.noise_scale < 0:
+            raise ValueError("ConvertRequest: noise_scale must be finite and >= 0")
+        self.chunk_frames, self.max_chunk_frames = int(chunk_frames), int(max_chunk_frames)
+        if self.chunk_frames < 1 or self.max_chunk_frames < self.chunk_frames:
+            raise ValueError("ConvertRequest: need 1 <= chunk_frames <= max_chunk_frames (got %d, %d)"
+                             % (self.chunk_frames, self.max_chunk_frames))
+
+    def model_samples(self):
+        """Samples at the model's rate: the length `resample` returns for the wave (librosa's fix_length)."""
+        n = self.wave.numel()
+        if self.in_sr == self.model_sr:
+            return n
+        return int(math.ceil(n * (float(self.model_sr) / self.in_sr)))
+
+    def frames(self, n_fft):
+        """Spectrogram frames of the request under an n_fft-point transform (DESIGN 7.2's formula, on the host)."""
+        return spectrogram_frames(self.model_samples(), n_fft, self.hop_size)
+
+    def __repr__(self):
+        return "ConvertRequest(%d samples at %d Hz, sid %d -> %d)" % (self.wave.numel(), self.in_sr, self.sid_src, self.sid_tgt)
+
+
+def spectrogram_frames(n_samples, n_fft, hop_size):
+    """Frames `spectrogram` gives an n-sample row (`mbv_spectrogram_frames`, restated for the host side of pooled
+    conversion): 0 where torch.stft would refuse a row that short."""
+    padded = int(n_samples) + 2 * ((int(n_fft) - int(hop_size)) // 2)
+    return 0 if padded < n_fft else 1 + (padded - int(n_fft)) // int(hop_size)
+
+
 _STAGES = ("text_encoder", "duration_predictor", "alignment_and_projection", "flow",
            "waveform_decoder")
 
@@ -954,6 +1032,176 @@ class SynthesizerTrn(nn.Module):
             for i, r in enumerate(reqs):
                 st = stream.DecodeStream(self, h, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
                 st.y_lengths = y_all[pos[i]:pos[i] + 1]
+                out.append(st)
+        return out
+
+    # ------------------------------------------------------------------ pooled voice conversion
+    def convert_plan(self, t_frames, splitk=False):
+        """(runs, run_of_request): the posterior runs `convert_streams` makes for requests of these frame counts
+        (`mbv_convert_plan`, host only: no GPU needed).  Requests share a padded run iff the conv planner sends
+        enc_q.pre, enc_q.proj and the flows' convs to the same kernel family for either alone; a class is cut at
+        65 535 rows and at what the fused WN layers take; with `splitk` one class."""
+        t = [int(v) for v in (t_frames.tolist() if torch.is_tensor(t_frames) else t_frames)]
+        n = len(t)
+        if n < 1:
+            raise ValueError("convert_plan: no requests")
+        if min(t) < 1:
+            raise ValueError("convert_plan: a request without frames (every count must be >= 1)")
+        cfg = self._config_struct()
+        runs = (C.c_int32 * n)()
+        r = _capi.lib().mbv_convert_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * n)(*t), runs)
+        if r < 0:
+            raise ValueError("mbv_convert_plan refused the frame counts (one request beyond the fused WN layers?)")
+        return r, list(runs)
+
+    def converter_runs(self):
+        """Posterior-encoder runs `convert_streams` / `convert_stream` made on this model's handle so far
+        (`mbv_converter_runs`): the difference across a call is the number of launch chains it cost."""
+        return int(_capi.lib().mbv_converter_runs(self._ensure_handle()))
+
+    def convert_stream(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
+                       chunk_frames=32, max_chunk_frames=256):
+        """Voice conversion of one recording up to z_hat, as a `DecodeStream`: resample to `model_sr` if `in_sr`
+        differs, spectrogram, posterior encoder, forward flow with emb_g(sid_src), reverse flow with emb_g(sid_tgt);
+        -> `dec_stream(z_hat * y_mask, g = emb_g(sid_tgt))` with `y_lengths` = the frame count.  Draws exactly one
+        `torch.randn(1, inter, T)` on the device generator, as `voice_conversion` does for that spectrogram alone: at
+        noise_scale 1 and in_sr == model_sr, `st.z` is bitwise that call's z_hat * y_mask and `st.run()` its o_hat
+        (default mode).  Arguments as `ConvertRequest`."""
+        req = ConvertRequest(wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=in_sr, noise_scale=noise_scale,
+                             chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames)
+        return self._convert([req], alone=True)[0]
+
+    def convert_streams(self, requests):
+        """Pooled voice conversion: one single-utterance `DecodeStream` per `ConvertRequest`, in order — what
+        `StreamPool.add` takes — from ONE padded posterior run per class of `convert_plan`, with no host read-back:
+        frame counts follow from the sample counts and speaker ids are ints, so every refusal happens before the
+        first launch.
+
+        Default mode: stream i is bitwise (z, g, y_lengths, schedule) what `convert_stream(...)` returns for request
+        i alone when those calls are made in list order from the same RNG state; the device generator ends where
+        those calls leave it and the CPU generator is not touched.  With the option "splitk" the result is
+        deterministic and within fp32 rounding of the stand-alone calls; "conv_bf16" is refused.
+
+        All requests must agree on (model_sr, hop_size, win_size): one model has one data config.  Refused before any
+        launch, naming the request: audio that gives 0 frames (ValueError), a speaker id outside [0, n_speakers)
+        (IndexError); a single-speaker model raises the reference's assertion.  No stream is created then."""
+        return self._convert(list(requests), alone=False)
+
+    @torch.no_grad()
+    def _convert(self, reqs, alone):
+        for i, r in enumerate(reqs):
+            if not isinstance(r, ConvertRequest):
+                raise TypeError("convert_streams takes models.ConvertRequest values (item %d is %s)" % (i, type(r).__name__))
+        if not reqs:
+            return []
+        r0 = reqs[0]
+        for i, r in enumerate(reqs):
+            if (r.model_sr, r.hop_size, r.win_size) != (r0.model_sr, r0.hop_size, r0.win_size):
+                raise ValueError("request %d: (model_sr, hop_size, win_size) = %s differs from request 0's %s: one model "
+                                 "has one data config" % (i, (r.model_sr, r.hop_size, r.win_size),
+                                                          (r0.model_sr, r0.hop_size, r0.win_size)))
+        if not self.n_speakers > 0:
+            raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
+        n_fft = 2 * (self.cfg.spec_channels - 1)
+        if _capi.lib().mbv_spectrogram_frames(1, n_fft, r0.hop_size) < 0:
+            raise ValueError("convert_streams: n_fft = 2 (spec_channels - 1) = %d must be a power of two in [256, 4096] "
+                             "and hop_size in [1, n_fft] (hop_size %d)" % (n_fft, r0.hop_size))
+        if r0.win_size > n_fft:
+            raise ValueError("convert_streams: win_size %d must be in [1, n_fft = 2 * (spec_channels - 1) = %d]"
+                             % (r0.win_size, n_fft))
+        N, I = len(reqs), self.cfg.inter_channels
+        samples = [r.model_samples() for r in reqs]
+        frames = [r.frames(n_fft) for r in reqs]
+        for i, r in enumerate(reqs):
+            if frames[i] < 1:
+                raise ValueError("request %d: %d samples at %d Hz give no spectrogram frame (n_fft %d, hop_size %d)"
+                                 % (i, r.wave.numel(), r.in_sr, n_fft, r.hop_size))
+            for name, sid in (("sid_src", r.sid_src), ("sid_tgt", r.sid_tgt)):
+                if not 0 <= sid < self.n_speakers:
+                    raise IndexError("request %d: index out of range in self (%s %d outside [0, %d))"
+                                     % (i, name, sid, self.n_speakers))
+        h = self._ensure_handle()
+        L = _capi.lib()
+        dev = self._device()
+        if L.mbv_get_option(h, b"conv_bf16") != 0:
+            raise ValueError("convert_streams is not built for the \"conv_bf16\" mode (the flows' route follows the launch "
+                             "size there): convert with voice_conversion")
+        try:
+            n_runs, run_of = self.convert_plan(frames, splitk=L.mbv_get_option(h, b"splitk") != 0)
+        except ValueError:
+            raise ValueError("convert_streams: a request of %d frames is beyond what the fused WN layers take" % max(frames))
+        members = [[i for i in range(N) if run_of[i] == k] for k in range(n_runs)]
+        with torch.cuda.device(dev):
+            hip_stream = self._stream()
+            keep = []                              # inputs of launches in flight
+            wave_ptr, wave_dtype = [None] * N, [0] * N
+            # rows at another rate: one `resample` call per distinct in_sr over their padded batch; the result is read
+            # in place, row by row
+            for sr in sorted({r.in_sr for r in reqs if r.in_sr != r.model_sr}):
+                idx = [i for i in range(N) if reqs[i].in_sr == sr]
+                on_host = not any(reqs[i].wave.is_cuda for i in idx)
+                ws = []
+                for i in idx:
+                    w = reqs[i].wave if on_host else reqs[i].wave.to(dev)
+                    ws.append(w.float() / 32768.0 if w.dtype == torch.int16 else w)     # exact scaling, as convert_pcm16
+                batch = torch.nn.utils.rnn.pad_sequence(ws, batch_first=True).unsqueeze(1)
+                valid = None
+                if len(idx) > 1:
+                    valid = torch.tensor([reqs[i].wave.numel() for i in idx], dtype=torch.int64)
+                out, _ = self.resample(batch.to(dev), sr, r0.model_sr, valid_samples=valid)
+                keep.append(out)
+                for b, i in enumerate(idx):
+                    wave_ptr[i] = out.data_ptr() + 4 * b * out.shape[-1]
+            # rows at the model's rate: host waves travel in one concatenated copy per dtype, device waves stay
+            for dt, code in ((torch.float32, 0), (torch.int16, 1)):
+                same = [i for i in range(N) if reqs[i].in_sr == reqs[i].model_sr and reqs[i].wave.dtype == dt]
+                host = [i for i in same if not reqs[i].wave.is_cuda]
+                if host:
+                    flat_w = torch.cat([reqs[i].wave for i in host]).to(dev)
+                    keep.append(flat_w)
+                    o = 0
+                    for i in host:
+                        wave_ptr[i] = flat_w.data_ptr() + flat_w.element_size() * o
+                        o += reqs[i].wave.numel()
+                for i in same:
+                    wave_dtype[i] = code
+                    if wave_ptr[i] is None:
+                        w = reqs[i].wave.to(dev)
+                        keep.append(w)
+                        wave_ptr[i] = w.data_ptr()
+            # the posterior draw, per request, in list order: the values and the generator's progress of N stand-alone
+            # randn(1, I, T_i) calls (drawn at noise_scale == 0 too, as convert_stream does)
+            if alone:
+                flat = torch.randn(1, I, frames[0], device=dev, dtype=torch.float32)
+                noise = [flat.data_ptr()]
+                y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
+            else:
+                flat = torch.empty(I * sum(frames), device=dev, dtype=torch.float32)
+                noise, o = [0] * N, 0
+                for i in range(N):
+                    flat[o:o + I * frames[i]].view(1, I, frames[i]).normal_()
+                    noise[i] = flat.data_ptr() + 4 * o
+                    o += I * frames[i]
+                y_all = torch.tensor(frames, dtype=torch.int64).to(dev)
+            z = [torch.empty(1, I, frames[i], device=dev, dtype=torch.float32) for i in range(N)]
+            g = [None] * N
+            for m in members:
+                B = len(m)
+                rows = (_capi.MbvConvertRow * B)()
+                for row, i in zip(rows, m):
+                    r = reqs[i]
+                    row.wave, row.samples, row.wave_dtype = wave_ptr[i], samples[i], wave_dtype[i]
+                    row.sid_src, row.sid_tgt = r.sid_src, r.sid_tgt
+                    row.noise, row.noise_scale, row.z = noise[i], r.noise_scale, z[i].data_ptr()
+                g_run = torch.empty(B, self.cfg.gin_channels, device=dev, dtype=torch.float32)
+                _capi.check(h, L.mbv_convert_rows(h, rows, B, max(frames[i] for i in m), r0.hop_size, r0.win_size,
+                                                  self._ptr(g_run), hip_stream), "mbv_convert_rows")
+                for b, i in enumerate(m):
+                    g[i] = g_run[b:b + 1]
+            out = []
+            for i, r in enumerate(reqs):
+                st = stream.DecodeStream(self, h, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
+                st.y_lengths = y_all[i:i + 1]
                 out.append(st)
         return out
 

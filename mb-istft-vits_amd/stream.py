@@ -136,9 +136,17 @@ class StreamPool:
 
     def admit(self, requests):
         """`net.infer_streams(requests)` + `add`: the front half of a tick's new requests in one padded run per class
-        of `net.admit_plan` and one host read-back; -> their streams, in order.  All or nothing: when a
-        request is refused or flagged, the exception passes through, no stream is created and the pool is unchanged."""
-        sts = self._net.infer_streams(requests)
+        of `net.admit_plan` and one host read-back; -> their streams, in order.  A list that is all
+        `models.ConvertRequest` goes through `net.convert_streams` instead (audio requests); a list that
+        mixes the two kinds is a TypeError.  All or nothing: when a request is refused or flagged, the exception
+        passes through, no stream is created and the pool is unchanged."""
+        from .models import ConvertRequest
+        reqs = list(requests)
+        n_audio = sum(isinstance(r, ConvertRequest) for r in reqs)
+        if n_audio and n_audio != len(reqs):
+            raise TypeError("admit takes a list that is all models.Request or all models.ConvertRequest "
+                            "(%d of %d items are ConvertRequest): admit the two kinds in two calls" % (n_audio, len(reqs)))
+        sts = self._net.convert_streams(reqs) if n_audio else self._net.infer_streams(reqs)
         for st in sts:
             self.add(st)
         return sts

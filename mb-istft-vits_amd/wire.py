@@ -271,7 +271,8 @@ class PcmPool:
 
     def admit(self, requests, peak=None):
         """`StreamPool.admit(requests)` + a follower for each new stream (`peak`: None, one value for all, or one per
-        request, as `add` takes it); -> the followers, in order.  All or nothing, like `StreamPool.admit`."""
+        request, as `add` takes it); -> the followers, in order.  `requests` is all `models.Request` or all
+        `models.ConvertRequest` (audio), as `StreamPool.admit` takes them.  All or nothing, like `StreamPool.admit`."""
         reqs = list(requests)
         peaks = list(peak) if isinstance(peak, (list, tuple)) else [peak] * len(reqs)
         if len(peaks) != len(reqs):

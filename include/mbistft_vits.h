@@ -242,6 +242,13 @@ typedef struct mbv_chunk {
 } mbv_chunk;
 int mbv_chunks_plan(const mbv_config *cfg, int splitk, int n, const int32_t *t_frames, int32_t *run_of_chunk);
 int mbv_decode_chunks(mbv_model *m, const mbv_chunk *chunks_host, int n, void *stream);
+/* mbv_decode_chunks with the length that decides a chunk's class given apart from t_frames: route_frames HOST [n] (or
+ * NULL = mbv_decode_chunks), entry i 0 = t_frames, else >= t_frames (a smaller value is refused).  For an utterance
+ * that is still growing (live conversion below): t_frames = the z-frames that are final now, which clips the window,
+ * and route_frames = a length of the class the finished utterance is to be decoded in.  Chunks share a run iff
+ * mbv_chunks_plan puts their route lengths into one run, so rows whose routes differ never share a launch. */
+int mbv_decode_chunks_routed(mbv_model *m, const mbv_chunk *chunks_host, const int32_t *route_frames, int n,
+                             void *stream);
 int64_t mbv_decoder_runs(mbv_model *m);
 
 /* ---- "tail_once" (default 1; mbv_set_option("tail_once", 0) turns it off, 2 applies it at every size) -----------
@@ -647,7 +654,8 @@ int64_t mbv_spectrogram_frames(int64_t n_samples, int n_fft, int hop);
  * where noise_scale != 0, rows that mbv_convert_plan would not put into one run, a run the fused WN layers do not
  * take (option "wn_fused" off).  No host synchronisation (beyond the first call's table upload for a win).
  *
- * mbv_converter_runs: posterior-encoder runs mbv_convert_rows made on this handle since mbv_create. */
+ * mbv_converter_runs: posterior-encoder runs mbv_convert_rows and mbv_convert_ranges made on this handle since
+ * mbv_create. */
 typedef struct mbv_convert_row {
   const void *wave;              /* DEVICE [samples] at the model's rate, read in place */
   int64_t samples;
@@ -662,11 +670,60 @@ int mbv_convert_rows(mbv_model *m, const mbv_convert_row *rows_host, int n, int 
                      float *g_out, void *stream);
 int64_t mbv_converter_runs(mbv_model *m);
 
+/* ---- live voice conversion: a recording that is still arriving -----------------
+ * Nothing on the way from audio to z_hat looks far: spectrogram frame f reads samples [f hop - pad, f hop - pad +
+ * n_fft) (pad = (n_fft - hop) / 2, zeros outside the recording), and z_hat frame t depends on spectrogram frames
+ * [t - L, t + R] only, (L, R) = mbv_converter_context.  So z_hat frames [first, first + count) of a recording are
+ * computed from the spectrogram window mbv_convert_window names, as one row of a padded run, and only those frames are
+ * stored, in place, into the recording's own z.  The convs of a window are planned as for a recording longer than 256
+ * frames (the conv planner's narrow-kernel rule cannot be known while the recording is open): in the default mode the
+ * stored frames do not depend on how the recording was cut into ranges, and for a recording of more than 256 frames
+ * they are BITWISE the z of mbv_convert_rows on the whole recording with the same noise.  For a shorter one they are
+ * within fp32 rounding of it (the other kernel family sums in another order).  "splitk": deterministic, within
+ * rounding.
+ *
+ * mbv_converter_context (host only): out = (L, R) in frames, the plain sum of the reaches of the posterior encoder's and
+ * both flow passes' k = 5 layers (96 for every supported model; the reach observed is 88).
+ * mbv_spectrogram_ready (host only): how many leading spectrogram frames are final once `arrived` samples exist:
+ * mbv_spectrogram_frames(arrived) when closed, else the frames all of whose samples exist, max(0, (arrived + pad -
+ * n_fft) / hop + 1).  -1 on bad arguments.
+ * mbv_convert_window (host only): out = [wa, wb), the spectrogram window for z_hat frames [first, first + count) when
+ * final_frames are final: [first - L, first + count + R) clipped to [0, final_frames), wa rounded down to a multiple
+ * of 32 (the fused WN layers' unit).  1 on bad arguments.
+ * mbv_convert_ranges_plan (host only): the runs for windows of window_frames[i] frames, in order; a run is cut where
+ * one more row would exceed 65535 rows or what the fused WN layers take.  Returns the number of runs, -1 on a bad
+ * argument (a window alone beyond that limit included).
+ *
+ * mbv_convert_ranges: one padded run, one row per recording.  rows_host is HOST memory and travels as kernel
+ * arguments; the samples are read in place; no host synchronisation (beyond the first call's table upload for a
+ * win).  Counted by mbv_converter_runs.  Refused before any launch, naming the row: frames that are not final yet
+ * (first + count + R beyond mbv_spectrogram_ready while open, or first + count beyond it), a speaker id outside
+ * [0, n_speakers), noise missing or its stride shorter than the window, z_stride < first + count, rows of more than
+ * one run of mbv_convert_ranges_plan, "conv_bf16", a model without speakers (the reference's assertion text). */
+typedef struct mbv_convert_range {
+  const void *wave;              /* DEVICE, the recording's buffer at the model's rate, read in place */
+  int64_t arrived;               /* samples that exist so far */
+  int32_t closed;                /* != 0: no more samples will come (the right padding of the spectrogram applies) */
+  int32_t wave_dtype;            /* MBV_WAVE_F32 or MBV_WAVE_PCM16 */
+  int32_t sid_src, sid_tgt;
+  int32_t first, count;          /* z_hat frames [first, first + count) */
+  const float *noise;            /* DEVICE [inter, noise_stride], the recording's block (not read at noise_scale 0) */
+  int64_t noise_stride;
+  float noise_scale;
+  float *z;                      /* DEVICE [inter, z_stride], the recording's own z; only the range is written */
+  int64_t z_stride;
+} mbv_convert_range;
+int mbv_converter_context(const mbv_config *cfg, int32_t out[2]);
+int64_t mbv_spectrogram_ready(int64_t arrived, int closed, int n_fft, int hop);
+int mbv_convert_window(const mbv_config *cfg, int first, int count, int64_t final_frames, int32_t out[2]);
+int mbv_convert_ranges_plan(const mbv_config *cfg, int n, const int32_t *window_frames, int32_t *run_of_range);
+int mbv_convert_ranges(mbv_model *m, const mbv_convert_range *rows_host, int n, int hop, int win, void *stream);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"
  * [B,1,T], "x_post" [B,72,F], "dec_conv_pre", "dec_up_0", "dec_res_0",
- * "dec_up_1", "dec_res_1"; after mbv_convert_rows "convert_ypad" [B, cin_pad, T], the posterior encoder's
+ * "dec_up_1", "dec_res_1"; after mbv_convert_rows / mbv_convert_ranges "convert_ypad" [B, cin_pad, T], the posterior encoder's
  * channel-padded input as the spectrogram kernel wrote it (cin_pad = spec_channels rounded up to 32).  Returns the element count, or < 0 on error;
  * dst == NULL only queries the count. */
 int64_t mbv_read_stage(mbv_model *m, const char *name, float *dst, int64_t capacity,

@@ -32,6 +32,8 @@ SYMBOLS = [
     "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
     "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
     "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
+    "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
+    "mbv_convert_ranges_plan", "mbv_convert_ranges",
 ]
 
 
@@ -86,6 +88,14 @@ class MbvConvertRow(C.Structure):
     """mbv_convert_row of include/mbistft_vits.h (mbv_convert_rows)."""
     _fields_ = [("wave", C.c_void_p), ("samples", C.c_int64), ("wave_dtype", C.c_int32), ("sid_src", C.c_int32),
                 ("sid_tgt", C.c_int32), ("noise", C.c_void_p), ("noise_scale", C.c_float), ("z", C.c_void_p)]
+
+
+class MbvConvertRange(C.Structure):
+    """mbv_convert_range of include/mbistft_vits.h (mbv_convert_ranges)."""
+    _fields_ = [("wave", C.c_void_p), ("arrived", C.c_int64), ("closed", C.c_int32), ("wave_dtype", C.c_int32),
+                ("sid_src", C.c_int32), ("sid_tgt", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+                ("noise", C.c_void_p), ("noise_stride", C.c_int64), ("noise_scale", C.c_float), ("z", C.c_void_p),
+                ("z_stride", C.c_int64)]
 
 
 class MbvAlignOutputs(C.Structure):
@@ -212,15 +222,17 @@ def lib():
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
-    # three that came with "tail_once" and pooled conversion's three may be absent there, and calling one then raises
-    # AttributeError.
+    # three that came with "tail_once", pooled conversion's three and live conversion's six may be absent there, and
+    # calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
                 "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
                 "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs",
                 "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
-                "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
+                "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
+                "mbv_convert_ranges_plan", "mbv_convert_ranges") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -254,6 +266,14 @@ def lib():
         L.mbv_convert_rows.argtypes = [vp, C.POINTER(MbvConvertRow), i32, i32, i32, i32, vp, vp]
         L.mbv_converter_runs.argtypes = [vp]
         L.mbv_converter_runs.restype = C.c_int64
+    if hasattr(L, "mbv_convert_ranges") or not optional:
+        L.mbv_decode_chunks_routed.argtypes = [vp, C.POINTER(MbvChunk), C.POINTER(C.c_int32), i32, vp]
+        L.mbv_converter_context.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32 * 2)]
+        L.mbv_spectrogram_ready.argtypes = [C.c_int64, i32, i32, i32]
+        L.mbv_spectrogram_ready.restype = C.c_int64
+        L.mbv_convert_window.argtypes = [C.POINTER(MbvConfig), i32, i32, C.c_int64, C.POINTER(C.c_int32 * 2)]
+        L.mbv_convert_ranges_plan.argtypes = [C.POINTER(MbvConfig), i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.mbv_convert_ranges.argtypes = [vp, C.POINTER(MbvConvertRange), i32, i32, i32, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -1781,7 +1781,7 @@ int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16
 // precedes (reverse) / follows (forward) it is folded into the packing, see do_finalize.
 //   reverse: x1 = (x1 - m) * mask          forward: x1 = m + x1 * mask = (x1 + m) * mask
 int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec, float* hbuf, float* acts,
-                 float* skip, float* gc, int* ustart, const int* lens, int B, int T, hipStream_t s) {
+                 float* skip, float* gc, int* ustart, const int* lens, int B, int T, hipStream_t s, int route_T = 0) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, half = I / 2;
   const int64_t bsI = (int64_t)I * T, bsH = (int64_t)H * T;
@@ -1794,7 +1794,7 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
   if (!fold_pre) {
     ConvArgs a = conv_args(m, F.pre, x0, bsI, T, hbuf, bsH, T, B);
     a.out_lens = lens;
-    launch_conv1d(a, s);
+    launch_conv1d(a, s, route_T);
   }
   if (fold_post) {
     // `post` lives in the res/skip convs (do_finalize): the last WN layer applies the coupling on the valid frames.
@@ -1808,7 +1808,7 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
     ConvArgs a = conv_args(m, F.post, skip, bsH, T, x1, bsI, T, B);
     a.in_lens = lens; a.epi = EPI_COUPLE; a.out_lens = lens;
     a.couple_sign = reverse ? -1.f : 1.f;
-    launch_conv1d(a, s);
+    launch_conv1d(a, s, route_T);
   }
   return 0;
 }
@@ -2729,6 +2729,10 @@ int mbv_chunks_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_f
 }
 
 int mbv_decode_chunks(mbv_model* m, const mbv_chunk* chunks_host, int n, void* stream) {
+  return mbv_decode_chunks_routed(m, chunks_host, nullptr, n, stream);
+}
+
+int mbv_decode_chunks_routed(mbv_model* m, const mbv_chunk* chunks_host, const int32_t* route_frames, int n, void* stream) {
   if (!m) return 1;
   if (!m->finalized) return m->fail("weights not finalized");
   if (!chunks_host || n <= 0) return m->fail("mbv_decode_chunks: bad arguments");
@@ -2745,8 +2749,13 @@ int mbv_decode_chunks(mbv_model* m, const mbv_chunk* chunks_host, int n, void* s
       return m->fail("mbv_decode_chunks: chunk %d: frames [%d, %d + %d) outside [0, %d)", i, k.first, k.first, k.count, k.t_frames);
     if ((uintptr_t)k.o & 15) return m->fail("mbv_decode_chunks: chunk %d: o must be 16-byte aligned", i);
     if (c.gin_channels && k.g) ++with_g;
-    lens[i] = k.t_frames;
-    if (k.t_frames > t_max) t_max = k.t_frames;
+    // the length that decides the class (and, through the run, the route of every conv): the utterance's own, or the
+    // one the caller names for an utterance that is still growing
+    const int route = route_frames && route_frames[i] ? route_frames[i] : k.t_frames;
+    if (route < k.t_frames)
+      return m->fail("mbv_decode_chunks: chunk %d: route_frames %d < t_frames %d", i, route, k.t_frames);
+    lens[i] = route;
+    if (route > t_max) t_max = route;
   }
   if (with_g && with_g != n) return m->fail("mbv_decode_chunks: g is given for %d of %d chunks (all or none)", with_g, n);
   int Lc = 0, Rc = 0;
@@ -2873,8 +2882,10 @@ struct PosteriorBufs { float *ypad, *hbuf, *acts, *skip, *stats, *gc; int* ustar
 // enc_q (models.py:239-246): pre * mask -> WN(g) -> proj * mask -> z = (m_q + noise * noise_scale * exp(logs_q)) * mask.
 // g == nullptr: the unconditioned WN of a single-speaker model.  y == nullptr: p.ypad holds the channel-padded input
 // already (mbv_convert_rows: the spectrogram kernel wrote it); rows: per-row noise and noise_scale (the same entry).
+// route_T > 0 (mbv_convert_ranges): the length the conv planner's narrow / tiled rule sees for pre and proj.
 int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, const float* noise, float noise_scale,
-              const PosteriorBufs& p, float* z, int B, int T, hipStream_t s, const AdmitSynRow* rows = nullptr) {
+              const PosteriorBufs& p, float* z, int B, int T, hipStream_t s, const AdmitSynRow* rows = nullptr,
+              int route_T = 0) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, SC = c.spec_channels;
   const auto& Q = m->encq;
@@ -2889,13 +2900,13 @@ int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, con
   {
     ConvArgs a = conv_args(m, Q.pre, p.ypad, (int64_t)Q.cin_pad * T, T, p.hbuf, bsH, T, B);
     a.out_lens = lens;
-    launch_conv1d(a, s);
+    launch_conv1d(a, s, route_T);
   }
   run_wn(m, Q.in, Q.rs, Q.in16, Q.rsp, mbv_model::kEncQLayers, Q.cw, Q.cb, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s);
   {
     ConvArgs a = conv_args(m, Q.proj, p.skip, bsH, T, p.stats, (int64_t)2 * I * T, T, B);
     a.in_lens = lens; a.out_lens = lens;
-    launch_conv1d(a, s);
+    launch_conv1d(a, s, route_T);
   }
   if (rows) launch_posterior_sample_rows(p.stats, rows, lens, z, B, I, T, s);
   else launch_posterior_sample(p.stats, noise, lens, z, B, I, T, s, noise_scale);
@@ -2903,9 +2914,9 @@ int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, con
 }
 // the forward flow (models.py:207-211), in place on z
 void run_flow_forward(mbv_model* m, float* z, const float* g, const PosteriorBufs& p, const int* lens, int B, int T,
-                      hipStream_t s) {
+                      hipStream_t s, int route_T = 0) {
   for (int f = 0; f < kNFlows; ++f)
-    run_coupling(m, f, false, z, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s);
+    run_coupling(m, f, false, z, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s, route_T);
 }
 }  // namespace
 
@@ -3596,6 +3607,189 @@ int mbv_convert_rows(mbv_model* m, const mbv_convert_row* rows_host, int n, int 
   run_flow_forward(m, z, g_src, pb, lens, B, T, s);
   for (int f = kNFlows - 1; f >= 0; --f)
     run_coupling(m, f, true, z, g_out, hbuf, acts, skip, gc, ustart, lens, B, T, s);
+  launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------ live voice conversion (audio that is still arriving)
+namespace {
+// Any length past the narrow kernel's 256: what the conv planner sees for a window of a recording whose final length is
+// not known yet (conv1d_plan's route_T).  The tiled kernels compute an element with one chain of operations whatever the
+// launch size, so every window of a recording, and its one-shot conversion once it is longer than 256 frames, agree.
+constexpr int kLiveRouteFrames = 257;
+
+// spectrogram frames [0, n) whose samples all exist: frame f reads [f hop - pad, f hop - pad + n_fft)
+int64_t spectrogram_ready(int64_t arrived, int closed, int n_fft, int hop) {
+  if (closed) return spectrogram_frames(arrived, n_fft, hop);
+  const int64_t pad = (n_fft - hop) / 2;
+  return arrived + pad < n_fft ? 0 : (arrived + pad - n_fft) / hop + 1;
+}
+
+// z_hat frame t depends on spectrogram frames [t - L, t + R] only: enc_q's WN and the couplings' WNs of both flow
+// passes are stacks of k = kFlowK, dilation-1 convs (every other conv of the path is 1x1), each reaching (k - 1) / 2
+// frames to either side.  The plain sum of the layers (the Flip between couplings lets half of the channels lag by a
+// layer stack, so the reach seen is a little smaller: DESIGN 7.11).
+void converter_context(int* L, int* R) {
+  const int reach = (mbv_model::kEncQLayers + 2 * kNFlows * kFlowLayers) * ((kFlowK - 1) / 2);
+  *L = reach; *R = reach;
+}
+
+// The spectrogram window from which z_hat frames [first, first + count) are computed when `final` frames are final: the
+// context to either side, clipped to the recording, its start aligned down to a whole 32-frame unit of the fused WN
+// layers (so that a frame sits in its unit where the whole-recording run has it).
+void convert_window(int first, int count, int64_t final_frames, int* wa, int* wb) {
+  int L, R;
+  converter_context(&L, &R);
+  const int a = first - L > 0 ? first - L : 0;
+  *wa = a & ~31;
+  const int64_t b = (int64_t)first + count + R;
+  *wb = (int)(b < final_frames ? b : final_frames);
+}
+}  // namespace
+
+int mbv_converter_context(const mbv_config* cfg, int32_t out[2]) {
+  if (!cfg || !out) return 1;
+  int L, R;
+  converter_context(&L, &R);
+  out[0] = L; out[1] = R;
+  return 0;
+}
+
+int64_t mbv_spectrogram_ready(int64_t arrived, int closed, int n_fft, int hop) {
+  if (arrived < 0 || spectrogram_args_error(n_fft, hop, 1)) return -1;
+  return spectrogram_ready(arrived, closed != 0, n_fft, hop);
+}
+
+int mbv_convert_window(const mbv_config* cfg, int first, int count, int64_t final_frames, int32_t out[2]) {
+  if (!cfg || !out || first < 0 || count < 1 || final_frames < (int64_t)first + count || final_frames > 0x7fffffff) return 1;
+  int wa, wb;
+  convert_window(first, count, final_frames, &wa, &wb);
+  out[0] = wa; out[1] = wb;
+  return 0;
+}
+
+int mbv_convert_ranges_plan(const mbv_config* cfg, int n, const int32_t* window_frames, int32_t* run_of_range) {
+  if (!cfg || n <= 0 || !window_frames) return -1;
+  int runs = 0, B = 0, T = 0;
+  for (int i = 0; i < n; ++i) {
+    const int w = window_frames[i];
+    if (w < 1 || !convert_run_fits(*cfg, 1, w)) return -1;
+    const int Tn = w > T ? w : T;
+    if (B == 0 || !convert_run_fits(*cfg, B + 1, Tn)) { ++runs; B = 1; T = w; }
+    else { ++B; T = Tn; }
+    if (run_of_range) run_of_range[i] = runs - 1;
+  }
+  return runs;
+}
+
+int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, int hop, int win, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_convert_ranges";
+  if (!m->finalized) return m->fail("weights not finalized");
+  const mbv_config& c = m->cfg;
+  if (c.n_speakers <= 0 || !m->emb_g.present)
+    return m->fail("n_speakers have to be larger than 0.");              // models.py:791 assert
+  if (!rows_host || n <= 0) return m->fail("%s: bad arguments", who);
+  if (m->conv_bf16) return m->fail("%s: live conversion is not built for the \"conv_bf16\" mode", who);
+  const int n_fft = 2 * (c.spec_channels - 1);
+  if (const char* why = spectrogram_args_error(n_fft, hop, win))
+    return m->fail("%s: %s (n_fft = 2 (spec_channels - 1) = %d)", who, why, n_fft);
+  const int B = n, H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
+  int Lv, Rv;
+  converter_context(&Lv, &Rv);
+  struct Win { int wa, len; };
+  std::vector<Win> wins(B);
+  std::vector<int32_t> wlen(B);
+  int T = 0, max_keep = 0;
+  for (int i = 0; i < B; ++i) {
+    const mbv_convert_range& k = rows_host[i];
+    if (!k.wave || !k.z || k.arrived < 1) return m->fail("%s: row %d: wave or z missing, or no samples", who, i);
+    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
+      return m->fail("%s: row %d: unknown wave_dtype %d", who, i, k.wave_dtype);
+    const int64_t fin = spectrogram_ready(k.arrived, k.closed != 0, n_fft, hop);
+    if (fin > 0x7fffffff) return m->fail("%s: row %d: too many frames", who, i);
+    if (k.first < 0 || k.count < 1 || (int64_t)k.first + k.count > fin)
+      return m->fail("%s: row %d: frames [%d, %d + %d) outside the %lld final spectrogram frames", who, i, k.first, k.first,
+                     k.count, (long long)fin);
+    if (!k.closed && (int64_t)k.first + k.count + Rv > fin)
+      return m->fail("%s: row %d: frames [%d, %d + %d) are not final yet: they need spectrogram frames up to %lld, and "
+                     "%lld are final (the recording is open)", who, i, k.first, k.first, k.count,
+                     (long long)k.first + k.count + Rv, (long long)fin);
+    if (k.sid_src < 0 || k.sid_src >= c.n_speakers || k.sid_tgt < 0 || k.sid_tgt >= c.n_speakers)
+      return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, c.n_speakers);
+    if (!(k.noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
+    int wa, wb;
+    convert_window(k.first, k.count, fin, &wa, &wb);
+    if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < wb))
+      return m->fail("%s: row %d: noise missing, or noise_stride %lld < the window's end %d", who, i, (long long)k.noise_stride, wb);
+    if (k.z_stride < (int64_t)k.first + k.count)
+      return m->fail("%s: row %d: z_stride %lld < first + count = %d", who, i, (long long)k.z_stride, k.first + k.count);
+    wins[i] = Win{wa, wb - wa};
+    wlen[i] = wb - wa;
+    if (wlen[i] > T) T = wlen[i];
+    if (k.count > max_keep) max_keep = k.count;
+  }
+  if (mbv_convert_ranges_plan(&c, B, wlen.data(), nullptr) != 1)
+    return m->fail("%s: the %d rows (widest window %d frames) belong to more than one run of mbv_convert_ranges_plan", who, B, T);
+  const auto& Q = m->encq;
+  bool fused = wn_takes_fused(m, Q.in, Q.in16, B, T) && wn_fused_fits(B, I, T);
+  for (int f = 0; f < kNFlows; ++f) fused = fused && wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T);
+  if (!fused)
+    return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
+                   "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  const mbv_model::SpectrogramTables* tab = nullptr;
+  if (spectrogram_tables_of(m, who, n_fft, win, &tab)) return 1;
+  const size_t BT = (size_t)B * T;
+  const size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 3 * I) + (size_t)B * (2 * gin + 2 * H * mbv_model::kEncQLayers + 1)) * 4 +
+                      wn_units_ints(B, T) * 4 + (size_t)B * (sizeof(ConvertRow) + sizeof(AdmitSynRow) + 16) + 64 * 256;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
+  Bump sc{m->scrB, m->scrB_bytes};
+  m->stages.clear();
+  float* ypad = sc.take<float>(BT * Q.cin_pad);
+  m->stages["convert_ypad"] = StageRef{ypad, (int64_t)(BT * Q.cin_pad)};
+  float* hbuf = sc.take<float>(BT * H);
+  float* acts = sc.take<float>(BT * H);
+  float* skip = sc.take<float>(BT * H);
+  float* stats = sc.take<float>(BT * 2 * I);
+  float* z = sc.take<float>(BT * I);
+  float* g_src = sc.take<float>((size_t)B * gin);
+  float* g_tgt = sc.take<float>((size_t)B * gin);
+  float* gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
+  int* lens = sc.take<int>(B);
+  int* ustart = sc.take<int>(wn_units_ints(B, T));
+  ConvertRow* crows = sc.take<ConvertRow>(B);
+  AdmitSynRow* srows = sc.take<AdmitSynRow>(B);
+  int64_t* sid_src = sc.take<int64_t>(B);
+  int64_t* sid_tgt = sc.take<int64_t>(B);
+  for (int f = 0; f < B; f += kAdmitChunk) {
+    ConvertRowsArg cr{};
+    AdmitSynRowsArg sr{};
+    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
+    for (int i = 0; i < nn; ++i) {
+      const mbv_convert_range& k = rows_host[f + i];
+      const Win& w = wins[f + i];
+      cr.row[i] = ConvertRow{k.wave, k.arrived, k.wave_dtype, w.len, k.sid_src, k.sid_tgt, w.wa, 0};
+      // the noise of the window's frames at the block's stride; the kept frames [first, first + count) of the window
+      // go to frame `first` of the stream's own z
+      sr.row[i] = AdmitSynRow{k.noise ? k.noise + w.wa : nullptr, k.noise_stride, k.noise_scale, k.count,
+                              k.z + k.first, w.len, k.first - w.wa, k.z_stride};
+    }
+    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
+    launch_admit_syn_rows(sr, nn, f, srows, s);
+  }
+  ++m->converter_runs;
+  const int rt = T > kLiveRouteFrames ? T : kLiveRouteFrames;
+  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
+  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s);
+  launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, ypad, Q.cin_pad, T, s);
+  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
+  if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows, rt)) return 1;
+  run_flow_forward(m, z, g_src, pb, lens, B, T, s, rt);
+  for (int f = kNFlows - 1; f >= 0; --f)
+    run_coupling(m, f, true, z, g_tgt, hbuf, acts, skip, gc, ustart, lens, B, T, s, rt);
   launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
   HIPCHK(m, hipGetLastError());
   return 0;

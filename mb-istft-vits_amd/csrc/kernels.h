@@ -234,6 +234,10 @@ struct AdmitSynRow {
   float noise_scale;           // 0: zp = m, the noise is not read (the scalar path's null-noise branch)
   int keep;                    // frames of z the request keeps (1 .. its y_len)
   float* z;                    // the request's own [C, keep]
+  // live conversion (mbv_convert_ranges): the row is a frame window of a longer recording.  All 0: the rules above.
+  int noise_len;               // frames of `noise` (already offset to the window) that may be read; 0: noise_stride
+  int src_off;                 // the kept frames start at frame src_off of the run's row
+  int64_t z_stride;            // row stride of `z` (already offset to the first kept frame); 0: keep
 };
 // n table rows by value from the host (kernel arguments) -> dst[first + i]
 constexpr int kAdmitChunk = 64;
@@ -254,6 +258,7 @@ void launch_set_durations_rows(const AdmitEncRow* rows, const int* lens, float* 
 void launch_expand_rows(const float* m_t, const float* logs_t, int64_t src_bstride, const int* cum, const int* ylen,
                         const AdmitSynRow* rows, float* z, int B, int C, int T, int Tp, hipStream_t s);
 // rows[b].z[c, t] = z[b, c, t] * (t < ylen[b]) for t < rows[b].keep: every request's masked, truncated z in one launch
+// (with src_off / z_stride: rows[b].z[c z_stride + t] = z[b, c, src_off + t] * (src_off + t < ylen[b]))
 void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* rows, int B, int C, int Tp, int max_keep,
                            hipStream_t s);
 
@@ -450,6 +455,9 @@ struct ConvertRow {
   int64_t samples;
   int dtype, frames;           // frames = spectrogram_frames(samples): the row's length in the run
   int sid_src, sid_tgt;
+  // live conversion (mbv_convert_ranges): the row is the frame window [first, first + frames) of a recording of which
+  // `samples` have arrived; the host guarantees that those frames are final.  0: the whole recording.
+  int first, reserved;
 };
 struct ConvertRowsArg { ConvertRow row[kAdmitChunk]; };
 // n table rows by value -> dst[first + i], and the columns the existing launches read: lens (frames), the two sids
@@ -457,11 +465,12 @@ void launch_convert_rows(const ConvertRowsArg& r, int n, int first, ConvertRow* 
                          int64_t* sid_tgt, hipStream_t s);
 // launch_spectrogram for row b = rows[b].wave over rows[b].samples, written into dst [B, cpad, F] (cpad >=
 // n_fft / 2 + 1: enc_q's channel-padded input): EXACT zeros in channels n_fft / 2 + 1 .. cpad and in frames at and
-// past the row's own count, so every element of dst is written
+// past the row's own count, so every element of dst is written.  rows[b].first > 0: frame f of the row is frame
+// first + f of the recording (samples [(first + f) hop - pad, .. + n_fft), zeros outside [0, samples))
 void launch_spectrogram_rows(const ConvertRow* rows, int B, int n_fft, int hop, const float* tw, const float* win,
                              float* dst, int cpad, int64_t F, hipStream_t s);
 // launch_posterior_sample with row b's noise block [I, rows[b].noise_stride] and rows[b].noise_scale; at scale 0
-// (and behind the block) the scalar kernel's null-noise branch
+// (and behind the block, or behind rows[b].noise_len where that is set) the scalar kernel's null-noise branch
 void launch_posterior_sample_rows(const float* stats, const AdmitSynRow* rows, const int* lens, float* z, int B,
                                   int I, int T, hipStream_t s);
 void launch_sequence_mask(const int* lens, float* mask, int B, int T, hipStream_t s);   // commons.py:121

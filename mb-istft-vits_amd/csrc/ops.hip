@@ -322,7 +322,9 @@ __global__ void scatter_z_rows_kernel(const float* z, const int* ylen, const Adm
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const AdmitSynRow r = rows[b];
   if (t >= r.keep) return;
-  r.z[(int64_t)c * r.keep + t] = z[((int64_t)b * C + c) * Tp + t] * (t < ylen[b] ? 1.f : 0.f);
+  const int64_t zs = r.z_stride ? r.z_stride : r.keep;
+  const int ts = r.src_off + t;                       // (src_off + keep <= Tp: the host checks it)
+  r.z[(int64_t)c * zs + t] = z[((int64_t)b * C + c) * Tp + ts] * (ts < ylen[b] ? 1.f : 0.f);
 }
 
 void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* rows, int B, int C, int Tp, int max_keep,
@@ -474,7 +476,8 @@ __global__ void posterior_sample_kernel(const float* stats, const float* noise, 
   if (ROWS) {
     const AdmitSynRow r = rows[b];
     noise_scale = r.noise_scale;
-    noise = (noise_scale != 0.f && t < r.noise_stride) ? r.noise : nullptr;
+    const int64_t nl = r.noise_len ? r.noise_len : r.noise_stride;
+    noise = (noise_scale != 0.f && t < nl) ? r.noise : nullptr;
     no = (int64_t)c * r.noise_stride + t;
   }
   const float v = noise ? m + (noise[no] * noise_scale) * expf(lg) : m;   // (noise_scale 1: exact)

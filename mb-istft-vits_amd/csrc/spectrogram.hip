@@ -91,7 +91,8 @@ __device__ __forceinline__ void stockham_pass(float2* buf, int Ns, int t, const 
 // [N + 1][FB + 1] that is then stored bin by bin as runs of FB consecutive frames.
 // ROWS (pooled voice conversion, kernels.h): row b's samples, their count and their dtype come from rows[b] (x, valid,
 // in_stride and scale are not used: the table travels in global memory, the LDS layout is the scalar kernel's), and
-// the destination row has KC = cpad >= N + 1 channels, those from N + 1 on written as zeros.
+// the destination row has KC = cpad >= N + 1 channels, those from N + 1 on written as zeros.  rows[b].first > 0: the row
+// is the frame window [first, first + frames) of its recording (live conversion); frame f reads from (first + f) hop - pad.
 // ---------------------------------------------------------------------------------------------------
 template <int LOGN, typename In, bool ROWS>
 __global__ void __launch_bounds__(kThreads)
@@ -111,18 +112,26 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
   int64_t v = in_stride;
   const void* xr = nullptr;
   bool pcm = false;
+  int64_t first = 0;                                              // ROWS: the row is a frame window starting here
+  int rframes = 0;
   if (ROWS) {
     const ConvertRow r = rows[b];
     v = r.samples < 0 ? 0 : r.samples;
     xr = r.wave;
     pcm = r.dtype == 1;
     scale = pcm ? 1.f / 32768.f : 1.f;
+    first = r.first;
+    rframes = r.frames;
   } else if (valid) {
     v = valid[b];
     v = v < 0 ? 0 : (v > in_stride ? in_stride : v);
   }
   const int64_t padded = v + 2 * (int64_t)pad;
-  const int64_t nfr = padded < NFFT ? 0 : 1 + (padded - NFFT) / hop;
+  int64_t nfr = padded < NFFT ? 0 : 1 + (padded - NFFT) / hop;
+  if (ROWS) {                       // the window's own frames (a whole recording: first = 0 and frames = nfr already)
+    nfr -= first;
+    if (nfr > rframes) nfr = rframes;
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0 && spec_lengths) spec_lengths[b] = nfr;
   const int64_t f0 = (int64_t)blockIdx.x * FB;
   if (f0 >= F) return;
@@ -140,7 +149,7 @@ spectrogram_kernel(const In* __restrict__ x, const int64_t* __restrict__ valid, 
 
   // stage padded samples [f0 hop, f0 hop + S) = x[f0 hop - pad + i]
   const int S = (FB - 1) * hop + NFFT;
-  const int64_t j0 = f0 * hop - pad;
+  const int64_t j0 = (first + f0) * hop - pad;
   const In* xb = x + (int64_t)b * in_stride;
   for (int i0 = 0; i0 < S; i0 += 8 * kThreads) {     // 8 loads in flight per lane before their LDS writes
     float r[8];

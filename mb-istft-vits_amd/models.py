@@ -1060,16 +1060,34 @@ class SynthesizerTrn(nn.Module):
         return int(_capi.lib().mbv_converter_runs(self._ensure_handle()))
 
     def convert_stream(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
-                       chunk_frames=32, max_chunk_frames=256):
+                       chunk_frames=32, max_chunk_frames=256, noise=None):
         """Voice conversion of one recording up to z_hat, as a `DecodeStream`: resample to `model_sr` if `in_sr`
         differs, spectrogram, posterior encoder, forward flow with emb_g(sid_src), reverse flow with emb_g(sid_tgt);
         -> `dec_stream(z_hat * y_mask, g = emb_g(sid_tgt))` with `y_lengths` = the frame count.  Draws exactly one
         `torch.randn(1, inter, T)` on the device generator, as `voice_conversion` does for that spectrogram alone: at
         noise_scale 1 and in_sr == model_sr, `st.z` is bitwise that call's z_hat * y_mask and `st.run()` its o_hat
-        (default mode).  Arguments as `ConvertRequest`."""
+        (default mode).  Arguments as `ConvertRequest`.  `noise` [1, inter, T] fp32 replaces the draw and leaves the
+        generator untouched (what `convert_live` is measured against); the default is the path as it was."""
         req = ConvertRequest(wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=in_sr, noise_scale=noise_scale,
                              chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames)
-        return self._convert([req], alone=True)[0]
+        return self._convert([req], alone=True, noise=noise)[0]
+
+    def converter_context(self):
+        """(L, R) of `mbv_converter_context` (host only): z_hat frame t depends on spectrogram frames [t - L, t + R]."""
+        return stream.converter_context(self._config_struct())
+
+    def convert_live(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
+                     noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None):
+        """Voice conversion of a recording that is still arriving: a `stream.LiveStream` that takes the samples in
+        `push` calls of any size and hands out decoded chunks from `poll` as soon as the audio they depend on exists
+        (DESIGN 7.11).  The result does not depend on how the samples were cut into pushes; for a recording of more
+        than 256 frames it is bitwise `convert_stream(whole, ..., noise=st.noise[:, :, :T])` chunk by chunk (default
+        mode), for a shorter one within fp32 rounding of it.  Draws one `torch.randn(1, inter, max_frames)` on the device
+        generator here, unless `noise` (that shape) is given.  Buffers are sized for `max_samples` once.  The audio
+        must be at the model's rate: a streaming input resampler is not built."""
+        return stream.LiveStream(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=dtype,
+                                 noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
+                                 max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr)
 
     def convert_streams(self, requests):
         """Pooled voice conversion: one single-utterance `DecodeStream` per `ConvertRequest`, in order — what
@@ -1088,7 +1106,7 @@ class SynthesizerTrn(nn.Module):
         return self._convert(list(requests), alone=False)
 
     @torch.no_grad()
-    def _convert(self, reqs, alone):
+    def _convert(self, reqs, alone, noise=None):
         for i, r in enumerate(reqs):
             if not isinstance(r, ConvertRequest):
                 raise TypeError("convert_streams takes models.ConvertRequest values (item %d is %s)" % (i, type(r).__name__))
@@ -1171,7 +1189,14 @@ class SynthesizerTrn(nn.Module):
                         wave_ptr[i] = w.data_ptr()
             # the posterior draw, per request, in list order: the values and the generator's progress of N stand-alone
             # randn(1, I, T_i) calls (drawn at noise_scale == 0 too, as convert_stream does)
-            if alone:
+            if alone and noise is not None:
+                if not torch.is_tensor(noise) or noise.dtype != torch.float32 or tuple(noise.shape) != (1, I, frames[0]):
+                    raise ValueError("convert_stream: noise must be a float32 tensor [1, %d, %d] (inter_channels, frames)"
+                                     % (I, frames[0]))
+                flat = noise.to(dev).contiguous()
+                noise = [flat.data_ptr()]
+                y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
+            elif alone:
                 flat = torch.randn(1, I, frames[0], device=dev, dtype=torch.float32)
                 noise = [flat.data_ptr()]
                 y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)

@@ -14,6 +14,10 @@ time to the first audio low, and the halo cost (L + R frames of decoder work per
 Many streams at once: a `StreamPool` decodes the next chunk of each of its streams in ONE call (`mbv_decode_chunks`),
 one decoder run per class of utterance lengths instead of one launch chain per stream, every sample bitwise what the
 stream yields alone.
+
+Audio that is still arriving: a `LiveStream` (`net.convert_live`) takes a recording in `push` calls, converts z_hat
+frames from spectrogram windows as soon as the samples they depend on exist (`LivePlan`, `mbv_convert_ranges`) and
+decodes every chunk whose z-window is final; a `StreamPool` serves live streams next to finished ones.
 """
 import ctypes as C
 
@@ -45,6 +49,327 @@ def decoder_context(config_struct):
     if _capi.lib().mbv_decoder_context(C.byref(config_struct), C.byref(out)):
         raise _capi.MbvError("mbv_decoder_context: unsupported decoder %d" % config_struct.decoder)
     return int(out[0]), int(out[1])
+
+
+def converter_context(config_struct):
+    """(L, R) of `mbv_converter_context` for an `_capi.MbvConfig` (host only): z_hat frame t depends on spectrogram
+    frames [t - L, t + R] only."""
+    out = (C.c_int32 * 2)()
+    if _capi.lib().mbv_converter_context(C.byref(config_struct), C.byref(out)):
+        raise _capi.MbvError("mbv_converter_context failed")
+    return int(out[0]), int(out[1])
+
+
+def spectrogram_ready(arrived, closed, n_fft, hop_size):
+    """Leading spectrogram frames that are final once `arrived` samples exist (`mbv_spectrogram_ready`, host only)."""
+    r = int(_capi.lib().mbv_spectrogram_ready(int(arrived), int(bool(closed)), int(n_fft), int(hop_size)))
+    if r < 0:
+        raise ValueError("mbv_spectrogram_ready refused (arrived %d, n_fft %d, hop_size %d)" % (arrived, n_fft, hop_size))
+    return r
+
+
+class LivePlan:
+    """What a recording that is still arriving may convert and decode, in pure integers (no tensor, no GPU).
+
+      spectrogram frame f   final iff closed, or all its samples exist               (`spectrogram_ready`)
+      z_hat frame t         may be converted iff spectrogram frames up to t + R_conv are final, or closed
+      conversion            launches when >= `convert_frames` new z_hat frames may be converted, or on close
+      chunk (first, count)  decodable iff z_hat frames up to first + count + R_dec are converted, or closed
+    Chunks are those of `chunk_schedule(T, chunk_frames, max_chunk_frames)`: only the cut of the last one depends on T,
+    and while the recording is open a decodable chunk lies R_dec frames before the end, so it is never the cut one."""
+
+    def __init__(self, n_fft, hop_size, r_conv, r_dec, chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+        self.n_fft, self.hop = int(n_fft), int(hop_size)
+        self.r_conv, self.r_dec = int(r_conv), int(r_dec)
+        c, cap, cf = int(chunk_frames), int(max_chunk_frames), int(convert_frames)
+        if c < 1 or cap < c:
+            raise ValueError("need 1 <= chunk_frames <= max_chunk_frames (got %d, %d)" % (c, cap))
+        if cf < 1:
+            raise ValueError("convert_frames must be >= 1")
+        self.convert_frames = cf
+        self.arrived, self.closed = 0, False
+        self.z_done = 0                        # z_hat frames [0, z_done) are converted
+        self._first, self._c, self._cap = 0, c, cap          # the next chunk to release
+
+    def push(self, n):
+        if self.closed:
+            raise ValueError("push after close()")
+        self.arrived += int(n)
+
+    def close(self):
+        self.closed = True
+
+    @property
+    def spec_final(self):
+        return spectrogram_ready(self.arrived, self.closed, self.n_fft, self.hop)
+
+    @property
+    def total(self):
+        """T, once closed."""
+        return self.spec_final if self.closed else None
+
+    def convert_due(self):
+        """The z_hat range [a, b) to convert now, or None."""
+        f = self.spec_final
+        b = f if self.closed else max(0, f - self.r_conv)
+        a = self.z_done
+        if b > a and (self.closed or b - a >= self.convert_frames):
+            return a, b
+        return None
+
+    def converted(self, a, b):
+        if a != self.z_done or b <= a:
+            raise ValueError("ranges are converted in order, once")
+        self.z_done = b
+
+    def decodable(self):
+        """[(first, count), ...]: the chunks not released yet that are decodable now, in order."""
+        first, c, out = self._first, self._c, []
+        T = self.spec_final if self.closed else None
+        while True:
+            if self.closed:
+                if self.z_done < T or first >= T:
+                    break
+                n = min(c, T - first)
+            else:
+                if self.z_done < first + c + self.r_dec:
+                    break
+                n = c
+            out.append((first, n))
+            first, c = first + n, min(2 * c, self._cap)
+        return out
+
+    def next_chunk(self):
+        """The next chunk (first, count) if it is decodable now, else None."""
+        d = self.decodable()
+        return d[0] if d else None
+
+    def released(self, first, count):
+        if first != self._first:
+            raise ValueError("chunks are released in order")
+        self._first += count
+        self._c = min(2 * self._c, self._cap)
+
+    @property
+    def all_released(self):
+        return self.closed and self._first >= self.spec_final
+
+
+class LiveStream:
+    """Voice conversion of a recording that is pushed piece by piece (`net.convert_live`).
+
+    `push(samples)` appends to a device buffer allocated once; `poll()` converts the z_hat frames whose audio exists
+    (one `mbv_convert_ranges` run over a spectrogram window, only the new frames stored into the stream's own `z`),
+    decodes every chunk that has become decodable and returns `[(first_sample, view), ...]`; `close()` ends the
+    recording.  z, o, g, the noise block and the sample buffer belong to the stream, so `infer`, `voice_conversion`
+    or other streams may run between any two calls.  Once `finished`, `y_lengths` is set and `result()` is
+    o[:, :, :256 T].  A `StreamPool` converts and decodes for many live streams in shared launches; chunks it decoded
+    ahead are handed out by the next `poll()` without a launch."""
+
+    def __init__(self, net, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
+                 noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None):
+        import math
+        self.model_sr, self.hop_size, self.win_size = int(model_sr), int(hop_size), int(win_size)
+        if in_sr is not None and int(in_sr) != self.model_sr:
+            raise ValueError("convert_live takes audio at the model's rate (in_sr %d, model_sr %d): a streaming input "
+                             "resampler is not built; resample before pushing" % (int(in_sr), self.model_sr))
+        if dtype not in (torch.float32, torch.int16):
+            raise TypeError("convert_live: dtype must be int16 or float32, got %s" % dtype)
+        sids = []
+        for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
+            if torch.is_tensor(sid):
+                if sid.numel() != 1:
+                    raise ValueError("convert_live: %s must be one speaker id" % name)
+                sid = sid.reshape(()).item()
+            if isinstance(sid, bool) or int(sid) != sid:
+                raise TypeError("convert_live: %s must be an integer" % name)
+            sids.append(int(sid))
+        self.sid_src, self.sid_tgt = sids
+        self.noise_scale = float(noise_scale)
+        if not math.isfinite(self.noise_scale) or self.noise_scale < 0:
+            raise ValueError("convert_live: noise_scale must be finite and >= 0")
+        if not net.n_speakers > 0:
+            raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
+        for name, sid in (("sid_src", self.sid_src), ("sid_tgt", self.sid_tgt)):
+            if not 0 <= sid < net.n_speakers:
+                raise IndexError("index out of range in self (%s %d outside [0, %d))" % (name, sid, net.n_speakers))
+        L = _capi.lib()
+        self.n_fft = 2 * (net.cfg.spec_channels - 1)
+        if L.mbv_spectrogram_frames(1, self.n_fft, self.hop_size) < 0:
+            raise ValueError("convert_live: n_fft = 2 (spec_channels - 1) = %d must be a power of two in [256, 4096] and "
+                             "hop_size in [1, n_fft] (hop_size %d)" % (self.n_fft, self.hop_size))
+        if not 1 <= self.win_size <= self.n_fft:
+            raise ValueError("convert_live: win_size %d must be in [1, n_fft = %d]" % (self.win_size, self.n_fft))
+        self.max_samples = int(max_samples)
+        self.max_frames = int(L.mbv_spectrogram_frames(max(self.max_samples, 0), self.n_fft, self.hop_size))
+        if self.max_samples < 1 or self.max_frames < 1:
+            raise ValueError("convert_live: max_samples %d gives no spectrogram frame (n_fft %d, hop_size %d)"
+                             % (self.max_samples, self.n_fft, self.hop_size))
+        h = net._ensure_handle()
+        if L.mbv_get_option(h, b"conv_bf16") != 0:
+            raise ValueError("convert_live is not built for the \"conv_bf16\" mode: convert with voice_conversion")
+        cfg = net._config_struct()
+        self._plan = LivePlan(self.n_fft, self.hop_size, converter_context(cfg)[1], decoder_context(cfg)[1],
+                              chunk_frames, max_chunk_frames, convert_frames)
+        self._cfg_struct = cfg
+        self.chunk_frames, self.max_chunk_frames = int(chunk_frames), int(max_chunk_frames)
+        self._net, self._h = net, h
+        dev = net._device()
+        I, F = net.cfg.inter_channels, self.max_frames
+        self.spf = net.cfg.samples_per_frame
+        self.dtype = dtype
+        with torch.cuda.device(dev), torch.no_grad():
+            if noise is None:
+                self.noise = torch.randn(1, I, F, device=dev, dtype=torch.float32)
+            else:
+                if not torch.is_tensor(noise) or noise.dtype != torch.float32 or tuple(noise.shape) != (1, I, F):
+                    raise ValueError("convert_live: noise must be a float32 tensor [1, %d, %d] (inter_channels, the frames "
+                                     "of max_samples)" % (I, F))
+                self.noise = noise.to(dev).contiguous()
+            self.samples = torch.zeros(self.max_samples, device=dev, dtype=dtype)
+            self.z = torch.zeros(1, I, F, device=dev, dtype=torch.float32)
+            self.o = torch.empty(1, 1, self.spf * F, device=dev, dtype=torch.float32)
+            self.g = net.emb_g(torch.tensor([self.sid_tgt], dtype=torch.int64, device=dev))
+        self.y_lengths = None
+        self._chunks = []             # (first, count) of every chunk decoded so far, in order
+        self._next = 0                # the chunk poll() hands out next
+        self._decoded = 0             # == len(_chunks)
+
+    # ---- the recording
+    @property
+    def arrived(self):
+        return self._plan.arrived
+
+    @property
+    def closed(self):
+        return self._plan.closed
+
+    @property
+    def frames(self):
+        """T, once closed (None before)."""
+        return self._plan.total
+
+    @property
+    def z_frames(self):
+        """z_hat frames converted so far: z[:, :, :z_frames] is final."""
+        return self._plan.z_done
+
+    def pending(self):
+        """The z_hat range (a, b) the next `poll()` / `StreamPool.step()` converts, or None."""
+        return self._plan.convert_due()
+
+    @property
+    def schedule(self):
+        """`chunk_schedule(T, ...)` once closed; before, the chunks decoded so far (a prefix of it)."""
+        if self._plan.closed:
+            return chunk_schedule(self._plan.total, self.chunk_frames, self.max_chunk_frames)
+        return list(self._chunks)
+
+    @property
+    def finished(self):
+        return self._plan.all_released and self._next >= self._decoded
+
+    def push(self, samples):
+        if not torch.is_tensor(samples):
+            raise TypeError("push takes a 1-D tensor of %s samples" % self.dtype)
+        if samples.dtype != self.dtype:
+            raise TypeError("push: the stream was opened for %s samples, got %s" % (self.dtype, samples.dtype))
+        if samples.dim() != 1:
+            raise ValueError("push takes 1-D samples, got shape %s" % (tuple(samples.shape),))
+        if self._plan.closed:
+            raise ValueError("push after close()")
+        n, a = samples.numel(), self._plan.arrived
+        if a + n > self.max_samples:
+            raise ValueError("push: %d + %d samples exceed the stream's capacity of %d (max_samples)" % (a, n, self.max_samples))
+        if n:
+            self.samples[a:a + n].copy_(samples)
+            self._plan.push(n)
+
+    def close(self):
+        if self._plan.closed:
+            return
+        a = self._plan.arrived
+        if a < 1 or spectrogram_ready(a, True, self.n_fft, self.hop_size) < 1:
+            raise ValueError("%d samples at %d Hz give no spectrogram frame (n_fft %d, hop_size %d)"
+                             % (a, self.model_sr, self.n_fft, self.hop_size))
+        self._plan.close()
+
+    # ---- what a pool shares (StreamPool.step); poll() is the stand-alone form of the same steps
+    def _check_handle(self):
+        if self._net._handle is not self._h:
+            raise RuntimeError("the model's handle was re-created (device move) since this stream started")
+
+    def _window_frames(self, a, b):
+        out = (C.c_int32 * 2)()
+        if _capi.lib().mbv_convert_window(C.byref(self._cfg_struct), a, b - a, self._plan.spec_final, C.byref(out)):
+            raise _capi.MbvError("mbv_convert_window refused [%d, %d)" % (a, b))
+        return int(out[1]) - int(out[0])
+
+    def _fill_range(self, row, a, b):
+        row.wave, row.arrived, row.closed = self.samples.data_ptr(), self._plan.arrived, int(self._plan.closed)
+        row.wave_dtype = 1 if self.dtype == torch.int16 else 0
+        row.sid_src, row.sid_tgt, row.first, row.count = self.sid_src, self.sid_tgt, a, b - a
+        row.noise, row.noise_stride, row.noise_scale = self.noise.data_ptr(), self.noise.stride(1), self.noise_scale
+        row.z, row.z_stride = self.z.data_ptr(), self.z.stride(1)
+
+    def _fill_chunk(self, k, first, count):
+        """-> the route length: the class a finished recording of more than 256 frames is decoded in."""
+        t = self._plan.z_done
+        k.z, k.z_stride, k.t_frames = self.z.data_ptr(), self.z.stride(1), t
+        k.g, k.first, k.count, k.o = self.g.data_ptr(), first, count, self.o.data_ptr()
+        return max(t, 257)
+
+    def _chunk_decoded(self, first, count):
+        self._plan.released(first, count)
+        self._chunks.append((first, count))
+        self._decoded += 1
+
+    def _convert(self):
+        due = self._plan.convert_due()
+        if due is None:
+            return False
+        self._check_handle()
+        net, L = self._net, _capi.lib()
+        rows = (_capi.MbvConvertRange * 1)()
+        self._fill_range(rows[0], *due)
+        with torch.cuda.device(self.z.device), torch.no_grad():
+            h = net._ensure_handle()
+            _capi.check(h, L.mbv_convert_ranges(h, rows, 1, self.hop_size, self.win_size, net._stream()), "mbv_convert_ranges")
+        self._plan.converted(*due)
+        return True
+
+    def poll(self):
+        """Convert what the rules allow, decode every chunk that has become decodable (all of them in one
+        `mbv_decode_chunks_routed` call) and hand out every chunk not handed out yet: [(first_sample, view), ...]."""
+        self._convert()
+        todo = self._plan.decodable()
+        if todo:
+            self._check_handle()
+            net = self._net
+            arr = (_capi.MbvChunk * len(todo))()
+            route = (C.c_int32 * len(todo))()
+            for i, (first, count) in enumerate(todo):
+                route[i] = self._fill_chunk(arr[i], first, count)
+            with torch.cuda.device(self.z.device), torch.no_grad():
+                h = net._ensure_handle()
+                _capi.check(h, _capi.lib().mbv_decode_chunks_routed(h, arr, route, len(todo), net._stream()),
+                            "mbv_decode_chunks_routed")
+            for first, count in todo:
+                self._chunk_decoded(first, count)
+        out = []
+        while self._next < self._decoded:
+            first, count = self._chunks[self._next]
+            out.append((self.spf * first, self.o[:, :, self.spf * first:self.spf * (first + count)]))
+            self._next += 1
+        if self._plan.all_released and self.y_lengths is None:
+            self.y_lengths = torch.full((1,), self._plan.total, dtype=torch.int64, device=self.z.device)
+        return out
+
+    def result(self):
+        """o[:, :, :256 T] of the finished stream."""
+        if not self.finished:
+            raise RuntimeError("result(): the stream is not finished (close() it and poll() until `finished`)")
+        return self.o[:, :, :self.spf * self._plan.total]
 
 
 class DecodeStream:
@@ -110,7 +435,11 @@ class StreamPool:
     pooled stream that has one (or of those named) and returns `[(st, first_sample, view), ...]`; the chunks count as
     decoded ahead on their streams, so `next(st)` — and a `wire.PcmStream` over `st` — afterwards hands them out
     without a launch.  A stream may be advanced through the pool, alone, or both in turn.  Streams may be added at
-    any time, one by one (`add`) or as the requests they come from (`admit`); finished ones drop out."""
+    any time, one by one (`add`) or as the requests they come from (`admit`); finished ones drop out.
+
+    A `LiveStream` is a member like any other: `step()` first converts the pending windows of all live members in one
+    `mbv_convert_ranges` run, then decodes at most one decodable chunk of each along with the others' chunks; a live
+    member with nothing decodable yet is skipped and stays, and its next `poll()` hands the pooled chunks out."""
 
     def __init__(self, net):
         self._net = net
@@ -120,8 +449,9 @@ class StreamPool:
         return len(self.streams)
 
     def add(self, st):
-        if not isinstance(st, DecodeStream):
-            raise TypeError("StreamPool.add takes a DecodeStream (net.dec_stream / net.infer_stream)")
+        if not isinstance(st, (DecodeStream, LiveStream)):
+            raise TypeError("StreamPool.add takes a DecodeStream (net.dec_stream / net.infer_stream) or a LiveStream "
+                            "(net.convert_live)")
         if st.z.shape[0] != 1:
             raise ValueError("StreamPool takes streams of ONE utterance (this one has %d rows): a pooled chunk is bitwise "
                              "its utterance's stand-alone decode, and a row of a batch is measured against the batch's "
@@ -151,7 +481,43 @@ class StreamPool:
             self.add(st)
         return sts
 
+    @staticmethod
+    def _done(st):
+        if isinstance(st, LiveStream):
+            return st._plan.all_released
+        return st._decoded >= len(st.schedule)
+
+    def _convert_live(self, members):
+        """The pending z_hat windows of every live member in one `mbv_convert_ranges` run per run of the planner."""
+        net, L = self._net, _capi.lib()
+        by_cfg = {}
+        for st in members:
+            if isinstance(st, LiveStream):
+                due = st._plan.convert_due()
+                if due is not None:
+                    st._check_handle()
+                    by_cfg.setdefault((st.hop_size, st.win_size), []).append((st, due))
+        for (hop, win), todo in by_cfg.items():
+            n = len(todo)
+            wl = (C.c_int32 * n)(*[st._window_frames(*due) for st, due in todo])
+            run_of = (C.c_int32 * n)()
+            n_runs = L.mbv_convert_ranges_plan(C.byref(todo[0][0]._cfg_struct), n, wl, run_of)
+            if n_runs < 1:
+                raise ValueError("mbv_convert_ranges_plan refused the windows (one beyond the fused WN layers?)")
+            for r in range(n_runs):
+                part = [t for t, k in zip(todo, run_of) if k == r]
+                rows = (_capi.MbvConvertRange * len(part))()
+                for row, (st, due) in zip(rows, part):
+                    st._fill_range(row, *due)
+                with torch.cuda.device(net._device()), torch.no_grad():
+                    h = net._ensure_handle()
+                    _capi.check(h, L.mbv_convert_ranges(h, rows, len(part), hop, win, net._stream()), "mbv_convert_ranges")
+                for st, due in part:
+                    st._plan.converted(*due)
+
     def step(self, streams=None):
+        """Live members first convert their pending windows together (`_convert_live`); then at most one chunk per
+        member is decoded in the one call.  A live member with nothing decodable is skipped and stays pooled."""
         if streams is None:
             members = list(self.streams)
         else:
@@ -159,26 +525,50 @@ class StreamPool:
             for st in members:
                 if not any(st is m for m in self.streams):
                     raise ValueError("step(streams=...) names a stream that is not in the pool")
-        self.streams = [st for st in self.streams if st._decoded < len(st.schedule)]
-        members = [st for st in members if st._decoded < len(st.schedule)]
+        self.streams = [st for st in self.streams if not self._done(st)]
+        members = [st for st in members if not self._done(st)]
         if not members:
             return []
         net = self._net
-        arr = (_capi.MbvChunk * len(members))()
-        out = []
-        for k, st in zip(arr, members):
+        any_live = any(isinstance(st, LiveStream) for st in members)
+        if any_live:
+            self._convert_live(members)
+        work = []                     # (stream, first, count)
+        for st in members:
             if net._handle is not st._h:
                 raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
-            first, count = st.schedule[st._decoded]
-            k.z, k.z_stride, k.t_frames = st.z.data_ptr(), st.z.stride(1), st.z.shape[2]
-            k.g = st.g.data_ptr() if st.g is not None else None
-            k.first, k.count, k.o = first, count, st.o.data_ptr()
+            if isinstance(st, LiveStream):
+                nxt = st._plan.next_chunk()
+                if nxt is not None:
+                    work.append((st,) + nxt)
+            else:
+                work.append((st,) + st.schedule[st._decoded])
+        if not work:
+            return []
+        arr = (_capi.MbvChunk * len(work))()
+        route = (C.c_int32 * len(work))()
+        out = []
+        for i, (st, first, count) in enumerate(work):
+            k = arr[i]
+            if isinstance(st, LiveStream):
+                route[i] = st._fill_chunk(k, first, count)
+            else:
+                k.z, k.z_stride, k.t_frames = st.z.data_ptr(), st.z.stride(1), st.z.shape[2]
+                k.g = st.g.data_ptr() if st.g is not None else None
+                k.first, k.count, k.o = first, count, st.o.data_ptr()
             out.append((st, st.spf * first, st.o[:, :, st.spf * first:st.spf * (first + count)]))
         dev = net._device()
         with torch.cuda.device(dev), torch.no_grad():
             h = net._ensure_handle()
-            _capi.check(h, _capi.lib().mbv_decode_chunks(h, arr, len(members), net._stream()), "mbv_decode_chunks")
-        for st in members:
-            st._decoded += 1
-        self.streams = [st for st in self.streams if st._decoded < len(st.schedule)]
+            if any_live:
+                _capi.check(h, _capi.lib().mbv_decode_chunks_routed(h, arr, route, len(work), net._stream()),
+                            "mbv_decode_chunks_routed")
+            else:
+                _capi.check(h, _capi.lib().mbv_decode_chunks(h, arr, len(work), net._stream()), "mbv_decode_chunks")
+        for st, first, count in work:
+            if isinstance(st, LiveStream):
+                st._chunk_decoded(first, count)
+            else:
+                st._decoded += 1
+        self.streams = [st for st in self.streams if not self._done(st)]
         return out

@@ -113,6 +113,14 @@ def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best
     return int(r)
 
 
+def _refuse_live(st):
+    from .stream import LiveStream
+    if isinstance(st, LiveStream):
+        raise TypeError("the wire output of a LiveStream (net.convert_live) is not built: the resampler's output length "
+                        "and valid_samples need the recording's total length, which an open stream does not have. "
+                        "Take the float chunks from poll(), or convert the finished recording with convert_stream")
+
+
 class PcmStream:
     """Iterator over (first_out_sample, pcm[:, a:b]) of one streamed decode: after every chunk of the wrapped
     `stream.DecodeStream` one `mbv_resample_pcm16_range` launch turns the resampled samples that chunk made final
@@ -134,6 +142,7 @@ class PcmStream:
     such a piece out without launching anything, and launches alone otherwise — the same bytes either way."""
 
     def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best"):
+        _refuse_live(st)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         o = st.o
@@ -262,6 +271,7 @@ class PcmPool:
         return None
 
     def add(self, st, peak=None):
+        _refuse_live(st)
         self.pool.add(st)                         # (refuses B > 1, another model, another device)
         f = self.follower(st)
         if f is None:

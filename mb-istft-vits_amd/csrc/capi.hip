@@ -45,9 +45,18 @@ struct StageRef { const float* ptr; int64_t numel; };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// state of an encode: its shape and the tensors it left in its scratch (mbv_model: of the last encode; EncSlot: of a kept run)
+struct EncState {
+  int B = 0, T = 0;
+  bool has_g = false;
+  float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
+  int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr;
+  int* bad32 = nullptr;         // per-utterance flags (invalid id / length / sid)
+};
+
 }  // namespace
 
-struct mbv_model {
+struct mbv_model : EncState {     // the base: the state of the last encode
   mbv_config cfg{};
   std::string err;
   std::map<std::string, HostTensor> raw;
@@ -116,18 +125,11 @@ struct mbv_model {
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
-  // state of the last encode
-  int B = 0, T = 0;
-  bool encoded = false, has_g = false;
-  float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
-  int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr;
-  int* bad32 = nullptr;         // per-utterance flags of the last encode (invalid id / length / sid)
+  bool encoded = false;           // the EncState base holds an encode
   std::map<std::string, StageRef> stages;
   // pooled admission: the encode state of one padded run, kept until its mbv_synthesize_rows (mbv_encode_rows);
   // slot 0 lives in scrA like a plain encode, every further slot in a buffer of its own
-  struct EncSlot { char* scr = nullptr; size_t bytes = 0; bool valid = false; int B = 0, T = 0; bool has_g = false;
-                   float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
-                   int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr, *bad32 = nullptr; };
+  struct EncSlot { char* scr = nullptr; size_t bytes = 0; bool valid = false; EncState enc; };
   std::vector<EncSlot> slots;
 
   static constexpr int kEvRing = 8;
@@ -920,13 +922,14 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
 
 // ------------------------------------------------------------------ scratch
 struct Bump {
-  char* base; size_t cap, off = 0;
+  char* base; size_t cap, off = 0;     // base == nullptr: a measuring pass, take advances `off` as ever and returns null
   template <typename Tp> Tp* take(size_t n) {
     off = align_up(off, 256);
-    Tp* p = reinterpret_cast<Tp*>(base + off);
+    Tp* p = base ? reinterpret_cast<Tp*>(base + off) : nullptr;
     off += n * sizeof(Tp);
     return p;
   }
+  bool fits() const { return off <= cap; }
 };
 
 int ensure(mbv_model* m, char** buf, size_t* cap, size_t need) {
@@ -936,6 +939,21 @@ int ensure(mbv_model* m, char** buf, size_t* cap, size_t need) {
   HIPCHK(m, hipMalloc((void**)buf, need));
   *cap = need;
   return 0;
+}
+
+// An entry's fixed scratch is written ONCE, as `carve(Bump&)`: run on a measuring Bump for the byte count, then, with
+// the buffer grown to that plus `extra` (the decoder's part, which carves on from *rest: decoder_scratch_bytes and its
+// like), on the buffer itself.  A tensor that may go to a caller's pointer instead is decided inside `carve`, so both
+// passes agree on it.  Nothing carved may be used before this returns 0.
+template <typename Carve>
+int lay_out(mbv_model* m, const char* who, char** buf, size_t* cap, Carve&& carve, size_t extra = 0, Bump* rest = nullptr) {
+  Bump measure{nullptr, 0};
+  carve(measure);
+  if (ensure(m, buf, cap, measure.off + extra)) return 1;
+  Bump sc{*buf, *cap};
+  carve(sc);
+  if (rest) *rest = sc;
+  return sc.fits() ? 0 : m->fail("%s: scratch layout exceeds its buffer", who);
 }
 
 ConvArgs conv_args(const mbv_model* m, const PConv& p, const float* x, int64_t x_bstride, int Tin,
@@ -1702,6 +1720,19 @@ int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const
 }
 
 
+// scratch of a WN stack: hbuf / acts / skip [B, H, T], gc [B, 2 H layers], ustart wn_units_ints(B, T)
+struct FlowBufs { float *hbuf, *acts, *skip, *gc; int* ustart; };
+FlowBufs carve_flow(Bump& sc, const mbv_config& c, int B, int T, int layers) {
+  const size_t BTH = (size_t)B * T * c.hidden_channels;
+  FlowBufs p{};
+  p.hbuf = sc.take<float>(BTH);
+  p.acts = sc.take<float>(BTH);
+  p.skip = sc.take<float>(BTH);
+  p.gc = sc.take<float>((size_t)B * 2 * c.hidden_channels * layers);
+  p.ustart = sc.take<int>(wn_units_ints(B, T));
+  return p;
+}
+
 // WN stack (modules.py:148-176): h -> skip; `nl` layers, gate conditioning from gvec.
 // Fused path (default): one launch per layer over the units that hold valid frames, h ping-pongs
 // between hbuf and acts (the old path's gated-activation buffer); afterwards only `skip` is meaningful,
@@ -1721,9 +1752,11 @@ bool wn_takes_fused(const mbv_model* m, const PConv* in_l, const PConv* in16_l, 
   const bool two_launch_bf16 = m->Wsplit(0) != nullptr && (long)B * T >= 12288;
   return !two_launch_bf16 && m->wn_fused && in16_l[0].M && wn_fused_supported(H, in_l[0].K) && wn_fused_fits(B, H, T);
 }
-int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16_l, const PConv* rsp_l, int nl,
-           const PVec& cw, const PVec& cb, const float* gvec, float* hbuf, float* acts, float* skip, float* gc,
-           int* ustart, const int* lens, int B, int T, hipStream_t s, const WnFold* fold = nullptr) {
+[[nodiscard]] int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16_l, const PConv* rsp_l,
+                         int nl, const PVec& cw, const PVec& cb, const float* gvec, const FlowBufs& p, const int* lens,
+                         int B, int T, hipStream_t s, const WnFold* fold = nullptr) {
+  float *const hbuf = p.hbuf, *const acts = p.acts, *const skip = p.skip, *const gc = p.gc;
+  int* const ustart = p.ustart;
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, gin = c.gin_channels;
   const int64_t bsH = (int64_t)H * T;
@@ -1780,8 +1813,8 @@ int run_wn(mbv_model* m, const PConv* in_l, const PConv* rs_l, const PConv* in16
 // One ResidualCouplingLayer (modules.py:334-353) in place on z [B, I, T]; the channel Flip that
 // precedes (reverse) / follows (forward) it is folded into the packing, see do_finalize.
 //   reverse: x1 = (x1 - m) * mask          forward: x1 = m + x1 * mask = (x1 + m) * mask
-int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec, float* hbuf, float* acts,
-                 float* skip, float* gc, int* ustart, const int* lens, int B, int T, hipStream_t s, int route_T = 0) {
+[[nodiscard]] int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec, const FlowBufs& p,
+                               const int* lens, int B, int T, hipStream_t s, int route_T = 0) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, half = I / 2;
   const int64_t bsI = (int64_t)I * T, bsH = (int64_t)H * T;
@@ -1792,7 +1825,7 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
   const bool fold_post = F.rspf[0].M && wn_takes_fused(m, F.in, F.in16, B, T);
   const bool fold_pre = fold_post && F.in16f0.M && F.pref.M && wn_fused_fits(B, I, T);   // (x0 is addressed through a whole-tensor view of z)
   if (!fold_pre) {
-    ConvArgs a = conv_args(m, F.pre, x0, bsI, T, hbuf, bsH, T, B);
+    ConvArgs a = conv_args(m, F.pre, x0, bsI, T, p.hbuf, bsH, T, B);
     a.out_lens = lens;
     launch_conv1d(a, s, route_T);
   }
@@ -1801,15 +1834,24 @@ int run_coupling(mbv_model* m, int f, bool reverse, float* z, const float* gvec,
     // Frames at and beyond lens[b] are not touched: z arrives masked (expand_kernel / posterior_sample) and stays so.
     const WnFold fold{F.rspf, half, x1, bsI, reverse ? -1.f : 1.f,
                       fold_pre ? &F.in16f0 : nullptr, fold_pre ? &F.pref : nullptr, F.Gi, x0, I};
-    return run_wn(m, F.in, F.rs, F.in16, F.rsp, kFlowLayers, F.cw, F.cb, gvec, hbuf, acts, skip, gc, ustart, lens, B, T, s, &fold);
+    return run_wn(m, F.in, F.rs, F.in16, F.rsp, kFlowLayers, F.cw, F.cb, gvec, p, lens, B, T, s, &fold);
   }
-  run_wn(m, F.in, F.rs, F.in16, F.rsp, kFlowLayers, F.cw, F.cb, gvec, hbuf, acts, skip, gc, ustart, lens, B, T, s);
+  if (int rc = run_wn(m, F.in, F.rs, F.in16, F.rsp, kFlowLayers, F.cw, F.cb, gvec, p, lens, B, T, s)) return rc;
   {
-    ConvArgs a = conv_args(m, F.post, skip, bsH, T, x1, bsI, T, B);
+    ConvArgs a = conv_args(m, F.post, p.skip, bsH, T, x1, bsI, T, B);
     a.in_lens = lens; a.epi = EPI_COUPLE; a.out_lens = lens;
     a.couple_sign = reverse ? -1.f : 1.f;
     launch_conv1d(a, s, route_T);
   }
+  return 0;
+}
+
+// The flow in place on z [B, I, T]: forward (models.py:207-211) the couplings 0 .. 3, reverse (:212-214) 3 .. 0.
+// Returns the first non-zero status.
+[[nodiscard]] int run_flows(mbv_model* m, bool reverse, float* z, const float* g, const FlowBufs& p, const int* lens,
+                            int B, int T, hipStream_t s, int route_T = 0) {
+  for (int i = 0; i < kNFlows; ++i)
+    if (int rc = run_coupling(m, reverse ? kNFlows - 1 - i : i, reverse, z, g, p, lens, B, T, s, route_T)) return rc;
   return 0;
 }
 
@@ -2092,6 +2134,18 @@ struct ExactScope {
 // Phase A of mbv_encode: embedding, the attention layers and enc_p.proj (models.py:183-195) -> x [B, H, T] and
 // m->stats = [m_text | logs_text]; shared with mbv_align.  Runs in the caller's ExactScope.
 struct TextEncBufs { float *x, *x1, *qkv, *att, *y, *ffn; };
+TextEncBufs carve_text(Bump& sc, mbv_model* m, int B, int T) {      // and m->stats [B, 2I, T]
+  const size_t BT = (size_t)B * T, H = m->cfg.hidden_channels;
+  TextEncBufs e{};
+  e.x = sc.take<float>(BT * H);
+  e.x1 = sc.take<float>(BT * H);
+  e.qkv = sc.take<float>(BT * 3 * H);
+  e.att = sc.take<float>(BT * H);
+  e.y = sc.take<float>(BT * H);
+  e.ffn = sc.take<float>(BT * m->cfg.filter_channels);
+  m->stats = sc.take<float>(BT * 2 * m->cfg.inter_channels);
+  return e;
+}
 // (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
 // size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
 bool text_fuse_ln_at(int splitk, int B, int T) { return T <= 256 && !(splitk && (long)B * ((T + 15) / 16) < 128); }
@@ -2168,33 +2222,38 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   // use the conv kernels that have the mode; short ones the narrow kernel, which does not.)
   ExactScope exact_scope(m);
   hipStream_t s = (hipStream_t)stream;
-  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
+  const int H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
   const size_t BT = (size_t)B * T;
-  size_t need = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2 * kDpFilter + 4 + 5 * H + 32 + 2) + (size_t)B * (gin + H + 12)) * 4 + 96 * 256;
-  if (rows_host) need += (size_t)B * sizeof(AdmitEncRow);
-  if (ensure(m, &m->scrA, &m->scrA_bytes, need)) return 1;
-  Bump sc{m->scrA, m->scrA_bytes};
-  float* x = sc.take<float>(BT * H);
-  float* x1 = sc.take<float>(BT * H);
-  float* qkv = sc.take<float>(BT * 3 * H);
-  float* att = sc.take<float>(BT * H);
-  float* y = sc.take<float>(BT * H);
-  float* ffn = sc.take<float>(BT * Fc);
-  m->stats = sc.take<float>(BT * 2 * I);
-  float* h1 = sc.take<float>(BT * kDpFilter);
-  float* h2 = sc.take<float>(BT * kDpFilter);
-  m->logw = sc.take<float>(BT);
-  m->w_ceil = sc.take<float>(BT);
-  m->cum = sc.take<int>(BT);
-  m->lens32 = sc.take<int>(B);
-  m->ylen32 = sc.take<int>(B);
-  int* bad = m->bad32 = sc.take<int>(B);
-  m->gvec = sc.take<float>((size_t)B * (gin ? gin : 1));
-  float* dpc = sc.take<float>((size_t)B * H);
+  TextEncBufs te{};
+  float *h1, *h2, *dpc;
+  float *cond = nullptr, *hh = nullptr, *t1 = nullptr, *t2 = nullptr, *h29 = nullptr, *zf = nullptr;   // the SDP's
   AdmitEncRow* rows = nullptr;
+  if (lay_out(m, who, &m->scrA, &m->scrA_bytes, [&](Bump& b) {
+        te = carve_text(b, m, B, T);
+        h1 = b.take<float>(BT * kDpFilter);
+        h2 = b.take<float>(BT * kDpFilter);
+        m->logw = b.take<float>(BT);
+        m->w_ceil = b.take<float>(BT);
+        m->cum = b.take<int>(BT);
+        m->lens32 = b.take<int>(B);
+        m->ylen32 = b.take<int>(B);
+        m->bad32 = b.take<int>(B);
+        m->gvec = b.take<float>((size_t)B * (gin ? gin : 1));
+        dpc = b.take<float>((size_t)B * H);
+        if (rows_host) rows = b.take<AdmitEncRow>(B);
+        if (c.use_sdp) {
+          cond = b.take<float>(BT * H);
+          hh = b.take<float>(BT * H);
+          t1 = b.take<float>(BT * H);
+          t2 = b.take<float>(BT * H);
+          h29 = b.take<float>(BT * 32);
+          zf = b.take<float>(BT * 2);
+        }
+      })) { m->encoded = false; return 1; }      // (the state of the encode before is gone: its scratch is this one)
+  int* const bad = m->bad32;
+  float* const x = te.x;
   bool any_given = false;
   if (rows_host) {
-    rows = sc.take<AdmitEncRow>(B);
     for (int f = 0; f < B; f += kAdmitChunk) {
       AdmitEncRowsArg r{};
       const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
@@ -2213,7 +2272,7 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   m->evr_a[m->ticket % mbv_model::kEvRing] = false;
   m->evr_b[m->ticket % mbv_model::kEvRing] = false;
   HIPCHK(m, hipEventRecord(m->ev[0], s));
-  run_text_encoder(m, ids, lengths, TextEncBufs{x, x1, qkv, att, y, ffn}, bad, B, T, s);
+  run_text_encoder(m, ids, lengths, te, bad, B, T, s);
   const int64_t bsH = (int64_t)H * T;
   const bool fuse_ln = text_fuse_ln(m, B, T);
   m->x_enc = x;
@@ -2231,12 +2290,6 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   }
   if (c.use_sdp) {
     // models.py:53-60: conditioning trunk; :89-100: z through [Flip, ConvFlow] x 3, Flip, affine
-    float* cond = sc.take<float>(BT * H);
-    float* hh = sc.take<float>(BT * H);
-    float* t1 = sc.take<float>(BT * H);
-    float* t2 = sc.take<float>(BT * H);
-    float* h29 = sc.take<float>(BT * 32);
-    float* zf = sc.take<float>(BT * 2);
     launch_conv1d(conv_args(m, m->sdp.pre, x, bsH, T, hh, bsH, T, B), s);
     if (cadd) launch_chan_add(hh, cadd, B, H, T, s);
     run_dds(m, m->sdp.dds, hh, t1, t2, B, H, T, s);
@@ -2344,25 +2397,20 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   }
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
-  const int B = m->B, T = m->T, Tp = t_frames, H = c.hidden_channels, I = c.inter_channels;
-  const int gin = c.gin_channels;
+  const int B = m->B, T = m->T, Tp = t_frames, I = c.inter_channels;
   const int Td = (max_len > 0 && max_len < Tp) ? max_len : Tp;
   const size_t BTp = (size_t)B * Tp;
   const bool run_dec = outs && (outs->o || outs->o_mb || outs->spec || outs->phase);
   if (y_lens_host && run_dec) ragged_plan(m, B, Td, y_lens_host, &runs);
-  size_t need = (BTp * (4 * I + 3 * H) + (size_t)B * (2 * H * kFlowLayers + 2)) * 4 + wn_units_ints(B, Tp) * 4 + 64 * 256 +
-                (y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td, tail_mode(m)));
-  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  float* z;
+  FlowBufs fb{};
+  Bump sc{};
+  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        z = outs && outs->z ? outs->z : b.take<float>(BTp * I);
+        fb = carve_flow(b, c, B, Tp, kFlowLayers);
+      }, y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td, tail_mode(m)), &sc)) return 1;
   for (const char* k : {"dec_conv_pre", "dec_up_0", "dec_up_1", "dec_res_0", "dec_res_1", "x_post"})
     m->stages.erase(k);
-  float* z = outs && outs->z ? outs->z : sc.take<float>(BTp * I);
-  float* hbuf = sc.take<float>(BTp * H);
-  float* acts = sc.take<float>(BTp * H);
-  float* skip = sc.take<float>(BTp * H);
-  float* gc = sc.take<float>((size_t)B * 2 * H * kFlowLayers);
-  int* ustart = sc.take<int>(wn_units_ints(B, Tp));
-  (void)gin;
 
   HIPCHK(m, hipEventRecord(m->ev[3], s));
   // m_text / logs_text are the two halves of enc_p.proj's output [B, 2I, T]
@@ -2373,8 +2421,7 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   HIPCHK(m, hipEventRecord(m->ev[4], s));
 
   // ---- reverse flows, in place on z (models.py:207-214, modules.py:334-353)
-  for (int f = kNFlows - 1; f >= 0; --f)
-    run_coupling(m, f, true, z, m->has_g ? m->gvec : nullptr, hbuf, acts, skip, gc, ustart, m->ylen32, B, Tp, s);
+  if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
   HIPCHK(m, hipEventRecord(m->ev[5], s));
   if (run_dec && y_lens_host) {
     if (run_decoder_ragged(m, z, Tp, m->has_g ? m->gvec : nullptr, B, Td, runs, outs->o, (int64_t)256 * Td, s, sc)) return 1;
@@ -2431,6 +2478,44 @@ void front_signature(const mbv_config& c, int splitk, int B, int T, std::vector<
   }
 }
 
+// The greedy planner of every pooled entry.  Each length's B = 1 signature is cached; a request joins the first open run
+// of its class (its signature) that still fits and still plans the same way at B + 1 rows padded to the new maximum,
+// else that run is closed — later requests of the class start a new one — and a new run is opened.  signature(B, T,
+// &sig) may leave sig empty: one class.  Per-request refusals are the caller's, in front of the call.  Returns the
+// number of runs.
+template <typename Signature, typename Fits>
+int plan_runs(int n, const int32_t* lengths, Signature signature, Fits fits, int32_t* run_of) {
+  struct Run { std::vector<char> sig; int B = 0, T = 0; bool open = true; };
+  std::vector<Run> runs;
+  std::map<int, std::vector<char>> sig_of;          // length -> its stand-alone signature
+  std::vector<char> sig;
+  for (int i = 0; i < n; ++i) {
+    const int T = lengths[i];
+    auto it = sig_of.find(T);
+    if (it == sig_of.end()) {
+      signature(1, T, &sig);
+      it = sig_of.emplace(T, sig).first;
+    }
+    int r = -1;
+    for (size_t k = 0; k < runs.size() && r < 0; ++k) {
+      if (!runs[k].open || runs[k].sig != it->second) continue;
+      const int Tn = T > runs[k].T ? T : runs[k].T;
+      bool ok = fits(runs[k].B + 1, Tn);
+      if (ok) { signature(runs[k].B + 1, Tn, &sig); ok = sig == runs[k].sig; }
+      if (ok) { r = (int)k; runs[k].T = Tn; ++runs[k].B; }
+      else runs[k].open = false;
+    }
+    if (r < 0) {
+      Run nr; nr.sig = it->second; nr.B = 1; nr.T = T;
+      runs.push_back(nr);
+      r = (int)runs.size() - 1;
+    }
+    if (run_of) run_of[i] = r;
+  }
+  return (int)runs.size();
+}
+inline void no_signature(int, int, std::vector<char>* sig) { sig->clear(); }   // split-K, live windows: one class
+
 // Runs of one pooled admission for requests of t_text[i] tokens: requests share a front-half run iff their texts,
 // each encoded alone, put every conv on the same side of the divide (front_signature at B = 1) — and a run is cut
 // where its own launches, B rows padded to its longest text, would leave that side (tensors beyond the narrow
@@ -2440,34 +2525,16 @@ int admit_plan(const mbv_config& c, int splitk, int n, const int32_t* t_text, in
   if (n <= 0 || !t_text) return -1;
   for (int i = 0; i < n; ++i)
     if (t_text[i] < 1) return -1;
-  struct Run { std::vector<char> sig; int B = 0, T = 0; bool open = true; };
-  std::vector<Run> runs;
-  std::map<int, std::vector<char>> sig_of;          // text length -> its stand-alone signature
-  std::vector<char> sig;
-  for (int i = 0; i < n; ++i) {
-    const int T = t_text[i];
-    auto it = sig_of.find(T);
-    if (it == sig_of.end()) {
-      if (splitk) sig.clear(); else front_signature(c, 0, 1, T, &sig);
-      it = sig_of.emplace(T, sig).first;
-    }
-    int r = -1;
-    for (size_t k = 0; k < runs.size() && r < 0; ++k) {
-      if (!runs[k].open || runs[k].sig != it->second) continue;
-      const int Tn = T > runs[k].T ? T : runs[k].T;
-      bool fits = runs[k].B + 1 <= 65535;
-      if (fits && !splitk) { front_signature(c, 0, runs[k].B + 1, Tn, &sig); fits = sig == runs[k].sig; }
-      if (fits) { r = (int)k; runs[k].T = Tn; ++runs[k].B; }
-      else runs[k].open = false;                    // full: later requests of the class start a new run
-    }
-    if (r < 0) {
-      Run nr; nr.sig = it->second; nr.B = 1; nr.T = T;
-      runs.push_back(nr);
-      r = (int)runs.size() - 1;
-    }
-    if (run_of_request) run_of_request[i] = r;
-  }
-  return (int)runs.size();
+  auto fits = [](int B, int) { return B <= 65535; };
+  if (splitk) return plan_runs(n, t_text, no_signature, fits, run_of_request);
+  return plan_runs(n, t_text, [&](int B, int T, std::vector<char>* sig) { front_signature(c, 0, B, T, sig); }, fits, run_of_request);
+}
+
+// rows [f, f + nn) of a host AdmitSynRow table, by value, into dst (nn <= kAdmitChunk)
+void upload_syn_rows(const std::vector<AdmitSynRow>& host, int f, int nn, AdmitSynRow* dst, hipStream_t s) {
+  AdmitSynRowsArg r{};
+  std::copy(host.begin() + f, host.begin() + f + nn, r.row);
+  launch_admit_syn_rows(r, nn, f, dst, s);
 }
 }  // namespace
 
@@ -2523,9 +2590,7 @@ int mbv_encode_rows(mbv_model* m, int slot, const int64_t* ids, const int64_t* l
   const int rc = encode(m, ids, lengths, sid, B, T, 1.f, nullptr, 1.f, rows_host, y_lengths_out, stream);
   if (slot > 0) { std::swap(m->scrA, sl.scr); std::swap(m->scrA_bytes, sl.bytes); }
   if (rc) { m->encoded = false; return rc; }
-  sl.valid = true; sl.B = m->B; sl.T = m->T; sl.has_g = m->has_g;
-  sl.x_enc = m->x_enc; sl.stats = m->stats; sl.logw = m->logw; sl.w_ceil = m->w_ceil; sl.gvec = m->gvec;
-  sl.lens32 = m->lens32; sl.cum = m->cum; sl.ylen32 = m->ylen32; sl.bad32 = m->bad32;
+  sl.valid = true; sl.enc = *m;
   return 0;
 }
 
@@ -2535,18 +2600,20 @@ int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* row
   if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
     return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
   const mbv_model::EncSlot& sl = m->slots[slot];
-  if (!rows_host || n != sl.B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, sl.B, n);
+  if (!rows_host || n != sl.enc.B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, sl.enc.B, n);
   if (t_frames <= 0) return m->fail("t_frames must be > 0");
   if (m->conv_bf16) return m->fail("%s: pooled admission is not built for the \"conv_bf16\" mode", who);
   const mbv_config& c = m->cfg;
-  const int B = sl.B, T = sl.T, Tp = t_frames, H = c.hidden_channels, I = c.inter_channels;
+  const int B = sl.enc.B, T = sl.enc.T, Tp = t_frames, I = c.inter_channels;
   int max_keep = 0;
+  std::vector<AdmitSynRow> rows_h(n);
   for (int i = 0; i < n; ++i) {
     const mbv_row& k = rows_host[i];
     if (!k.z || k.keep < 1 || k.keep > Tp) return m->fail("%s: row %d: z missing or keep %d outside [1, %d]", who, i, k.keep, Tp);
     if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < 1 || k.noise_stride > Tp))
       return m->fail("%s: row %d: noise missing or noise_stride outside [1, %d]", who, i, Tp);
     if (k.keep > max_keep) max_keep = k.keep;
+    rows_h[i] = AdmitSynRow{k.noise, k.noise_stride, k.noise_scale, k.keep, k.z};
   }
   // the flows must take, for the whole run, the route every utterance takes alone: the fused WN layers, which work
   // on 16-frame half-units below each row's own length (the two-launch layers route on T')
@@ -2557,33 +2624,20 @@ int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* row
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
   const size_t BTp = (size_t)B * Tp;
-  const size_t need = (BTp * (I + 3 * H) + (size_t)B * (2 * H * kFlowLayers + 2)) * 4 + wn_units_ints(B, Tp) * 4 +
-                      (size_t)B * sizeof(AdmitSynRow) + 64 * 256;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
+  float* z;
+  FlowBufs fb{};
+  AdmitSynRow* rows;
+  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        z = b.take<float>(BTp * I);
+        fb = carve_flow(b, c, B, Tp, kFlowLayers);
+        rows = b.take<AdmitSynRow>(B);
+      })) return 1;
   // the run becomes the handle's "last encode", as if mbv_encode had just made it
-  m->B = sl.B; m->T = sl.T; m->has_g = sl.has_g; m->encoded = true;
-  m->x_enc = sl.x_enc; m->stats = sl.stats; m->logw = sl.logw; m->w_ceil = sl.w_ceil; m->gvec = sl.gvec;
-  m->lens32 = sl.lens32; m->cum = sl.cum; m->ylen32 = sl.ylen32; m->bad32 = sl.bad32;
-  Bump sc{m->scrB, m->scrB_bytes};
-  float* z = sc.take<float>(BTp * I);
-  float* hbuf = sc.take<float>(BTp * H);
-  float* acts = sc.take<float>(BTp * H);
-  float* skip = sc.take<float>(BTp * H);
-  float* gc = sc.take<float>((size_t)B * 2 * H * kFlowLayers);
-  int* ustart = sc.take<int>(wn_units_ints(B, Tp));
-  AdmitSynRow* rows = sc.take<AdmitSynRow>(B);
-  for (int f = 0; f < B; f += kAdmitChunk) {
-    AdmitSynRowsArg r{};
-    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
-    for (int i = 0; i < nn; ++i) {
-      const mbv_row& k = rows_host[f + i];
-      r.row[i] = AdmitSynRow{k.noise, k.noise_stride, k.noise_scale, k.keep, k.z};
-    }
-    launch_admit_syn_rows(r, nn, f, rows, s);
-  }
+  static_cast<EncState&>(*m) = sl.enc;
+  m->encoded = true;
+  for (int f = 0; f < B; f += kAdmitChunk) upload_syn_rows(rows_h, f, std::min(B - f, kAdmitChunk), rows, s);
   launch_expand_rows(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, rows, z, B, I, T, Tp, s);
-  for (int f = kNFlows - 1; f >= 0; --f)
-    run_coupling(m, f, true, z, m->has_g ? m->gvec : nullptr, hbuf, acts, skip, gc, ustart, m->ylen32, B, Tp, s);
+  if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
   launch_scatter_z_rows(z, m->ylen32, rows, B, I, Tp, max_keep, s);
   HIPCHK(m, hipGetLastError());
   return 0;
@@ -2876,9 +2930,17 @@ int mbv_istft_pqmf(mbv_model* m, const float* x_post, int B, int t_frames, const
 }  // extern "C"
 
 namespace {
-// scratch of the posterior side (mbv_voice_conversion, mbv_align): ypad [B, cin_pad, T], hbuf / acts / skip [B, H, T],
-// stats [B, 2I, T], gc [B, 2 H kEncQLayers], ustart wn_units_ints(B, T)
-struct PosteriorBufs { float *ypad, *hbuf, *acts, *skip, *stats, *gc; int* ustart; };
+// scratch of the posterior side (every entry that runs enc_q): ypad [B, cin_pad, T], the WN stack's of kEncQLayers
+// layers (which the couplings' shorter stacks then use), stats [B, 2I, T]
+struct PosteriorBufs : FlowBufs { float *ypad, *stats; };
+PosteriorBufs carve_posterior(Bump& sc, const mbv_model* m, int B, int T) {
+  const size_t BT = (size_t)B * T;
+  PosteriorBufs p{};
+  p.ypad = sc.take<float>(BT * m->encq.cin_pad);
+  static_cast<FlowBufs&>(p) = carve_flow(sc, m->cfg, B, T, mbv_model::kEncQLayers);
+  p.stats = sc.take<float>(BT * 2 * m->cfg.inter_channels);
+  return p;
+}
 // enc_q (models.py:239-246): pre * mask -> WN(g) -> proj * mask -> z = (m_q + noise * noise_scale * exp(logs_q)) * mask.
 // g == nullptr: the unconditioned WN of a single-speaker model.  y == nullptr: p.ypad holds the channel-padded input
 // already (mbv_convert_rows: the spectrogram kernel wrote it); rows: per-row noise and noise_scale (the same entry).
@@ -2902,7 +2964,7 @@ int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, con
     a.out_lens = lens;
     launch_conv1d(a, s, route_T);
   }
-  run_wn(m, Q.in, Q.rs, Q.in16, Q.rsp, mbv_model::kEncQLayers, Q.cw, Q.cb, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s);
+  if (int rc = run_wn(m, Q.in, Q.rs, Q.in16, Q.rsp, mbv_model::kEncQLayers, Q.cw, Q.cb, g, p, lens, B, T, s)) return rc;
   {
     ConvArgs a = conv_args(m, Q.proj, p.skip, bsH, T, p.stats, (int64_t)2 * I * T, T, B);
     a.in_lens = lens; a.out_lens = lens;
@@ -2911,12 +2973,6 @@ int run_enc_q(mbv_model* m, const float* y, const int* lens, const float* g, con
   if (rows) launch_posterior_sample_rows(p.stats, rows, lens, z, B, I, T, s);
   else launch_posterior_sample(p.stats, noise, lens, z, B, I, T, s, noise_scale);
   return 0;
-}
-// the forward flow (models.py:207-211), in place on z
-void run_flow_forward(mbv_model* m, float* z, const float* g, const PosteriorBufs& p, const int* lens, int B, int T,
-                      hipStream_t s, int route_T = 0) {
-  for (int f = 0; f < kNFlows; ++f)
-    run_coupling(m, f, false, z, g, p.hbuf, p.acts, p.skip, p.gc, p.ustart, lens, B, T, s, route_T);
 }
 }  // namespace
 
@@ -2934,40 +2990,33 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
     return m->fail("mbv_voice_conversion: bad arguments");
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
-  const int H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
-  const auto& Q = m->encq;
+  const int I = c.inter_channels, gin = c.gin_channels;
   const size_t BT = (size_t)B * T;
-  size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 4 * I) + (size_t)B * (2 * gin + 2 * H * mbv_model::kEncQLayers + 18)) * 4 + wn_units_ints(B, T) * 4 +
-                64 * 256 + decoder_scratch_bytes(c, B, T, tail_mode(m));
-  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  PosteriorBufs pb{};
+  float *zbuf, *zhat, *g_src, *g_tgt;
+  int *lens, *bad;
+  Bump sc{};
+  if (lay_out(m, "mbv_voice_conversion", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        pb = carve_posterior(b, m, B, T);
+        zbuf = outs->z ? outs->z : b.take<float>(BT * I);
+        zhat = outs->m_p ? outs->m_p : b.take<float>(BT * I);
+        g_src = b.take<float>((size_t)B * gin);
+        g_tgt = b.take<float>((size_t)B * gin);
+        lens = b.take<int>(B);
+        bad = b.take<int>(B);
+      }, decoder_scratch_bytes(c, B, T, tail_mode(m)), &sc)) return 1;
   m->stages.clear();
-  float* ypad = sc.take<float>(BT * Q.cin_pad);
-  float* hbuf = sc.take<float>(BT * H);
-  float* acts = sc.take<float>(BT * H);
-  float* skip = sc.take<float>(BT * H);
-  float* stats = sc.take<float>(BT * 2 * I);
-  float* zbuf = outs->z ? outs->z : sc.take<float>(BT * I);
-  float* zhat = outs->m_p ? outs->m_p : sc.take<float>(BT * I);
-  float* g_src = sc.take<float>((size_t)B * gin);
-  float* g_tgt = sc.take<float>((size_t)B * gin);
-  float* gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
-  int* lens = sc.take<int>(B);
-  int* bad = sc.take<int>(B);
-  int* ustart = sc.take<int>(wn_units_ints(B, T));
 
   launch_lens_to_i32(y_lengths, lens, B, T, bad, s);
   launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, bad, s);
   launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, bad, s);
   if (status) HIPCHK(m, hipMemcpyAsync(status, bad, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
-  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
   if (run_enc_q(m, y, lens, g_src, noise, 1.f, pb, zbuf, B, T, s)) return 1;
   // forward flow with the source speaker (models.py:795), then reverse with the target (:796)
   HIPCHK(m, hipMemcpyAsync(zhat, zbuf, BT * I * 4, hipMemcpyDeviceToDevice, s));
-  run_flow_forward(m, zhat, g_src, pb, lens, B, T, s);
+  if (int rc = run_flows(m, false, zhat, g_src, pb, lens, B, T, s)) return rc;
   if (outs->z_p) HIPCHK(m, hipMemcpyAsync(outs->z_p, zhat, BT * I * 4, hipMemcpyDeviceToDevice, s));
-  for (int f = kNFlows - 1; f >= 0; --f)
-    run_coupling(m, f, true, zhat, g_tgt, hbuf, acts, skip, gc, ustart, lens, B, T, s);
+  if (int rc = run_flows(m, true, zhat, g_tgt, pb, lens, B, T, s)) return rc;
   if (outs->y_mask) launch_sequence_mask(lens, outs->y_mask, B, T, s);
   if (run_decoder(m, zhat, T, lens, g_tgt, B, T, outs, s, sc)) return 1;
   HIPCHK(m, hipGetLastError());
@@ -2990,51 +3039,39 @@ int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const fl
   DEVICE_GUARD(m);
   ExactScope exact_scope(m);                 // the text statistics as mbv_encode computes them; the path must not depend on the mode
   hipStream_t s = (hipStream_t)stream;
-  const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels, gin = c.gin_channels;
+  const int I = c.inter_channels, gin = c.gin_channels;
   const int T = T_text, Tp = T_spec;
-  const auto& Q = m->encq;
   const size_t BT = (size_t)B * T, BTp = (size_t)B * Tp;
   // ---- text side, in the scratch of mbv_encode (whose state it therefore ends)
   m->encoded = false;
   m->stages.clear();
-  size_t needA = (BT * (H * 5 + 3 * H + Fc + 2 * I + 2) + (size_t)B * (gin + 12)) * 4 + 32 * 256;
-  if (ensure(m, &m->scrA, &m->scrA_bytes, needA)) return 1;
-  Bump sa{m->scrA, m->scrA_bytes};
   TextEncBufs te{};
-  te.x = sa.take<float>(BT * H);
-  te.x1 = sa.take<float>(BT * H);
-  te.qkv = sa.take<float>(BT * 3 * H);
-  te.att = sa.take<float>(BT * H);
-  te.y = sa.take<float>(BT * H);
-  te.ffn = sa.take<float>(BT * Fc);
-  m->stats = sa.take<float>(BT * 2 * I);
-  m->cum = sa.take<int>(BT);
-  int* w32 = sa.take<int>(BT);
-  m->lens32 = sa.take<int>(B);
-  m->ylen32 = sa.take<int>(B);
-  int* bad_x = m->bad32 = sa.take<int>(B);
-  int* bad_y = sa.take<int>(B);
-  int* ylens = sa.take<int>(B);
-  int* mas = sa.take<int>(B);
-  m->gvec = sa.take<float>((size_t)B * (gin ? gin : 1));
+  int *w32, *bad_y, *ylens, *mas;
+  if (lay_out(m, "mbv_align", &m->scrA, &m->scrA_bytes, [&](Bump& b) {
+        te = carve_text(b, m, B, T);
+        m->cum = b.take<int>(BT);
+        w32 = b.take<int>(BT);
+        m->lens32 = b.take<int>(B);
+        m->ylen32 = b.take<int>(B);
+        m->bad32 = b.take<int>(B);
+        bad_y = b.take<int>(B);
+        ylens = b.take<int>(B);
+        mas = b.take<int>(B);
+        m->gvec = b.take<float>((size_t)B * (gin ? gin : 1));
+      })) return 1;
+  int* const bad_x = m->bad32;
   // ---- posterior side
   const size_t bits_bytes = max_path_scratch_bytes(B, Tp, T);
-  size_t needB = (BTp * ((size_t)Q.cin_pad + 3 * H + 4 * I + (size_t)T) + (size_t)B * (2 * H * mbv_model::kEncQLayers + 8)) * 4 +
-                 wn_units_ints(B, Tp) * 4 + bits_bytes + 64 * 256;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, needB)) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
   PosteriorBufs pb{};
-  pb.ypad = sc.take<float>(BTp * Q.cin_pad);
-  pb.hbuf = sc.take<float>(BTp * H);
-  pb.acts = sc.take<float>(BTp * H);
-  pb.skip = sc.take<float>(BTp * H);
-  pb.stats = sc.take<float>(BTp * 2 * I);
-  pb.gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
-  pb.ustart = sc.take<int>(wn_units_ints(B, Tp));
-  float* zbuf = outs->z ? outs->z : sc.take<float>(BTp * I);
-  float* zp = outs->z_p ? outs->z_p : sc.take<float>(BTp * I);
-  float* value = outs->neg_cent ? outs->neg_cent : sc.take<float>(BTp * T);
-  void* bits = bits_bytes ? (void*)sc.take<char>(bits_bytes) : nullptr;
+  float *zbuf, *zp, *value;
+  void* bits = nullptr;
+  if (lay_out(m, "mbv_align", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        pb = carve_posterior(b, m, B, Tp);
+        zbuf = outs->z ? outs->z : b.take<float>(BTp * I);
+        zp = outs->z_p ? outs->z_p : b.take<float>(BTp * I);
+        value = outs->neg_cent ? outs->neg_cent : b.take<float>(BTp * T);
+        if (bits_bytes) bits = b.take<char>(bits_bytes);
+      })) return 1;
   int* w_out = outs->w ? outs->w : w32;
 
   run_text_encoder(m, ids, lengths, te, bad_x, B, T, s);
@@ -3046,7 +3083,7 @@ int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const fl
   launch_lens_to_i32(y_lengths, ylens, B, Tp, bad_y, s);
   if (run_enc_q(m, y, ylens, g, noise_scale != 0.f ? noise : nullptr, noise_scale, pb, zbuf, B, Tp, s)) return 1;
   HIPCHK(m, hipMemcpyAsync(zp, zbuf, BTp * I * 4, hipMemcpyDeviceToDevice, s));
-  run_flow_forward(m, zp, g, pb, ylens, B, Tp, s);
+  if (int rc = run_flows(m, false, zp, g, pb, ylens, B, Tp, s)) return rc;
   // ---- neg_cent, the search, the durations (models.py:668-680)
   launch_neg_cent(zp, m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, ylens, m->lens32, value, B, I, Tp, T, s);
   launch_max_path(value, ylens, m->lens32, w_out, nullptr, mas, bits, B, Tp, T, s);
@@ -3468,42 +3505,99 @@ bool convert_run_fits(const mbv_config& c, int B, int T) {
   return B <= 65535 && wn_fused_fits(B, c.hidden_channels, T) && wn_fused_fits(B, c.inter_channels, T);
 }
 
-// Runs of one pooled conversion for requests of t_frames[i] frames, built as admit_plan builds its own: requests share
-// a run iff their posterior_signature at B = 1 agree, and a run is cut where the padded run would plan differently,
-// exceed 65535 rows or exceed the fused WN layers' 32-bit offsets.  Split-K: one class.  -1 on a bad argument (a
-// request that alone is beyond the fused WN layers included).
+// Runs of one pooled conversion for requests of t_frames[i] frames (plan_runs): requests share a run iff their
+// posterior_signature at B = 1 agree, and a run is cut where the padded run would plan differently, exceed 65535 rows
+// or exceed the fused WN layers' 32-bit offsets.  Split-K: one class.  -1 on a bad argument (a request that alone is
+// beyond the fused WN layers included).
 int convert_plan(const mbv_config& c, int splitk, int n, const int32_t* t_frames, int32_t* run_of_request) {
   if (n <= 0 || !t_frames) return -1;
   for (int i = 0; i < n; ++i)
     if (t_frames[i] < 1 || !convert_run_fits(c, 1, t_frames[i])) return -1;
-  struct Run { std::vector<char> sig; int B = 0, T = 0; bool open = true; };
-  std::vector<Run> runs;
-  std::map<int, std::vector<char>> sig_of;          // frame count -> its stand-alone signature
-  std::vector<char> sig;
-  for (int i = 0; i < n; ++i) {
-    const int T = t_frames[i];
-    auto it = sig_of.find(T);
-    if (it == sig_of.end()) {
-      if (splitk) sig.clear(); else posterior_signature(c, 0, 1, T, &sig);
-      it = sig_of.emplace(T, sig).first;
-    }
-    int r = -1;
-    for (size_t k = 0; k < runs.size() && r < 0; ++k) {
-      if (!runs[k].open || runs[k].sig != it->second) continue;
-      const int Tn = T > runs[k].T ? T : runs[k].T;
-      bool fits = convert_run_fits(c, runs[k].B + 1, Tn);
-      if (fits && !splitk) { posterior_signature(c, 0, runs[k].B + 1, Tn, &sig); fits = sig == runs[k].sig; }
-      if (fits) { r = (int)k; runs[k].T = Tn; ++runs[k].B; }
-      else runs[k].open = false;                    // full: later requests of the class start a new run
-    }
-    if (r < 0) {
-      Run nr; nr.sig = it->second; nr.B = 1; nr.T = T;
-      runs.push_back(nr);
-      r = (int)runs.size() - 1;
-    }
-    if (run_of_request) run_of_request[i] = r;
+  auto fits = [&](int B, int T) { return convert_run_fits(c, B, T); };
+  if (splitk) return plan_runs(n, t_frames, no_signature, fits, run_of_request);
+  return plan_runs(n, t_frames, [&](int B, int T, std::vector<char>* sig) { posterior_signature(c, 0, B, T, sig); }, fits, run_of_request);
+}
+
+// What mbv_convert_rows ("pooled") and mbv_convert_ranges ("live") both refuse: of the call (bad_args: the entry's own
+// argument test, in its place among the others) and of a row; of the planned run: run_posterior_rows.
+int convert_call_refusal(mbv_model* m, const char* who, const char* kind, bool bad_args, int hop, int win) {
+  if (!m->finalized) return m->fail("weights not finalized");
+  const mbv_config& c = m->cfg;
+  if (c.n_speakers <= 0 || !m->emb_g.present)
+    return m->fail("n_speakers have to be larger than 0.");              // models.py:791 assert
+  if (bad_args) return m->fail("%s: bad arguments", who);
+  if (m->conv_bf16) return m->fail("%s: %s conversion is not built for the \"conv_bf16\" mode", who, kind);
+  const int n_fft = 2 * (c.spec_channels - 1);
+  if (const char* why = spectrogram_args_error(n_fft, hop, win))
+    return m->fail("%s: %s (n_fft = 2 (spec_channels - 1) = %d)", who, why, n_fft);
+  return 0;
+}
+int convert_row_refusal(mbv_model* m, const char* who, int i, int wave_dtype, int sid_src, int sid_tgt, float noise_scale) {
+  const int ns = m->cfg.n_speakers;
+  if (wave_dtype != MBV_WAVE_F32 && wave_dtype != MBV_WAVE_PCM16)
+    return m->fail("%s: row %d: unknown wave_dtype %d", who, i, wave_dtype);
+  if (sid_src < 0 || sid_src >= ns || sid_tgt < 0 || sid_tgt >= ns)
+    return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, ns);
+  if (!(noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
+  return 0;
+}
+
+// One pooled posterior run over validated rows (crows[i].frames <= T): the two tables go up in kAdmitChunk pieces, then
+// the speaker vectors, the spectrograms into enc_q's padded input, enc_q, the forward flow with the source speaker
+// (models.py:795) and the reverse flow with the target (:796) in place, and every row's kept frames to its own z.
+// g_out: where the target speaker vectors [B, gin] go (null: scratch).  route_T: see run_enc_q.
+int run_posterior_rows(mbv_model* m, const char* who, const std::vector<ConvertRow>& crows_h,
+                       const std::vector<AdmitSynRow>& srows_h, int T, int max_keep, int route_T, float* g_out, int hop,
+                       int win, hipStream_t s) {
+  const mbv_config& c = m->cfg;
+  const int B = (int)crows_h.size(), I = c.inter_channels, gin = c.gin_channels, n_fft = 2 * (c.spec_channels - 1);
+  // the whole run must take the route every row takes alone: the fused WN layers, which work on 16-frame half-units
+  // below each row's own length (the two-launch layers route on T)
+  bool fused = wn_takes_fused(m, m->encq.in, m->encq.in16, B, T) && wn_fused_fits(B, I, T);
+  for (int f = 0; f < kNFlows; ++f) fused = fused && wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T);
+  if (!fused)
+    return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
+                   "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
+  DEVICE_GUARD(m);
+  const mbv_model::SpectrogramTables* tab = nullptr;
+  if (spectrogram_tables_of(m, who, n_fft, win, &tab)) return 1;
+  const size_t BT = (size_t)B * T;
+  PosteriorBufs pb{};
+  float *z, *g_src, *g_tgt;
+  int* lens;
+  ConvertRow* crows;
+  AdmitSynRow* srows;
+  int64_t *sid_src, *sid_tgt;
+  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        pb = carve_posterior(b, m, B, T);
+        z = b.take<float>(BT * I);
+        g_src = b.take<float>((size_t)B * gin);
+        g_tgt = g_out ? g_out : b.take<float>((size_t)B * gin);
+        lens = b.take<int>(B);
+        crows = b.take<ConvertRow>(B);
+        srows = b.take<AdmitSynRow>(B);
+        sid_src = b.take<int64_t>(B);
+        sid_tgt = b.take<int64_t>(B);
+      })) return 1;
+  m->stages.clear();
+  m->stages["convert_ypad"] = StageRef{pb.ypad, (int64_t)(BT * m->encq.cin_pad)};
+  for (int f = 0; f < B; f += kAdmitChunk) {
+    const int nn = std::min(B - f, kAdmitChunk);
+    ConvertRowsArg cr{};
+    std::copy(crows_h.begin() + f, crows_h.begin() + f + nn, cr.row);
+    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
+    upload_syn_rows(srows_h, f, nn, srows, s);
   }
-  return (int)runs.size();
+  ++m->converter_runs;
+  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
+  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s);
+  launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, pb.ypad, m->encq.cin_pad, T, s);
+  if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows, route_T)) return 1;
+  if (int rc = run_flows(m, false, z, g_src, pb, lens, B, T, s, route_T)) return rc;
+  if (int rc = run_flows(m, true, z, g_tgt, pb, lens, B, T, s, route_T)) return rc;
+  launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
 }
 }  // namespace
 
@@ -3518,31 +3612,24 @@ int mbv_convert_rows(mbv_model* m, const mbv_convert_row* rows_host, int n, int 
                      void* stream) {
   if (!m) return 1;
   const char* who = "mbv_convert_rows";
-  if (!m->finalized) return m->fail("weights not finalized");
+  if (convert_call_refusal(m, who, "pooled", !rows_host || !g_out || n <= 0 || t_frames <= 0, hop, win)) return 1;
   const mbv_config& c = m->cfg;
-  if (c.n_speakers <= 0 || !m->emb_g.present)
-    return m->fail("n_speakers have to be larger than 0.");              // models.py:791 assert
-  if (!rows_host || !g_out || n <= 0 || t_frames <= 0) return m->fail("%s: bad arguments", who);
-  if (m->conv_bf16) return m->fail("%s: pooled conversion is not built for the \"conv_bf16\" mode", who);
-  const int n_fft = 2 * (c.spec_channels - 1);
-  if (const char* why = spectrogram_args_error(n_fft, hop, win))
-    return m->fail("%s: %s (n_fft = 2 (spec_channels - 1) = %d)", who, why, n_fft);
-  const int B = n, T = t_frames, H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
+  const int n_fft = 2 * (c.spec_channels - 1), B = n, T = t_frames;
+  std::vector<ConvertRow> crows(B);
+  std::vector<AdmitSynRow> srows(B);
   std::vector<int32_t> fr(B);
   int longest = 0;
   for (int i = 0; i < B; ++i) {
     const mbv_convert_row& k = rows_host[i];
     if (!k.wave || !k.z || k.samples < 1) return m->fail("%s: row %d: wave or z missing, or no samples", who, i);
-    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
-      return m->fail("%s: row %d: unknown wave_dtype %d", who, i, k.wave_dtype);
+    if (convert_row_refusal(m, who, i, k.wave_dtype, k.sid_src, k.sid_tgt, k.noise_scale)) return 1;
     const int64_t f = spectrogram_frames(k.samples, n_fft, hop);
     if (f < 1 || f > T) return m->fail("%s: row %d: %lld frames outside [1, %d]", who, i, (long long)f, T);
     fr[i] = (int32_t)f;
     if (fr[i] > longest) longest = fr[i];
-    if (k.sid_src < 0 || k.sid_src >= c.n_speakers || k.sid_tgt < 0 || k.sid_tgt >= c.n_speakers)
-      return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, c.n_speakers);
-    if (!(k.noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
     if (k.noise_scale != 0.f && !k.noise) return m->fail("%s: row %d: noise missing", who, i);
+    crows[i] = ConvertRow{k.wave, k.samples, k.wave_dtype, fr[i], k.sid_src, k.sid_tgt};
+    srows[i] = AdmitSynRow{k.noise, fr[i], k.noise_scale, fr[i], k.z};
   }
   // the run is planned at its longest row (mbv_convert_plan): a wider launch could take a route no row takes alone
   if (T != longest)
@@ -3550,66 +3637,7 @@ int mbv_convert_rows(mbv_model* m, const mbv_convert_row* rows_host, int n, int 
   // the rows must be ONE run of the plan: a second class in the launch would move some row to another route
   if (convert_plan(c, m->splitk, B, fr.data(), nullptr) != 1)
     return m->fail("%s: the rows belong to more than one run of mbv_convert_plan", who);
-  // the whole run must take the route every row takes alone: the fused WN layers, which work on 16-frame half-units
-  // below each row's own length (the two-launch layers route on T)
-  const auto& Q = m->encq;
-  bool fused = wn_takes_fused(m, Q.in, Q.in16, B, T) && wn_fused_fits(B, I, T);
-  for (int f = 0; f < kNFlows; ++f) fused = fused && wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T);
-  if (!fused)
-    return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
-                   "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
-  DEVICE_GUARD(m);
-  hipStream_t s = (hipStream_t)stream;
-  const mbv_model::SpectrogramTables* tab = nullptr;
-  if (spectrogram_tables_of(m, who, n_fft, win, &tab)) return 1;
-  const size_t BT = (size_t)B * T;
-  const size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 3 * I) + (size_t)B * (gin + 2 * H * mbv_model::kEncQLayers + 1)) * 4 +
-                      wn_units_ints(B, T) * 4 + (size_t)B * (sizeof(ConvertRow) + sizeof(AdmitSynRow) + 16) + 64 * 256;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
-  m->stages.clear();
-  float* ypad = sc.take<float>(BT * Q.cin_pad);
-  m->stages["convert_ypad"] = StageRef{ypad, (int64_t)(BT * Q.cin_pad)};
-  float* hbuf = sc.take<float>(BT * H);
-  float* acts = sc.take<float>(BT * H);
-  float* skip = sc.take<float>(BT * H);
-  float* stats = sc.take<float>(BT * 2 * I);
-  float* z = sc.take<float>(BT * I);
-  float* g_src = sc.take<float>((size_t)B * gin);
-  float* gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
-  int* lens = sc.take<int>(B);
-  int* ustart = sc.take<int>(wn_units_ints(B, T));
-  ConvertRow* crows = sc.take<ConvertRow>(B);
-  AdmitSynRow* srows = sc.take<AdmitSynRow>(B);
-  int64_t* sid_src = sc.take<int64_t>(B);
-  int64_t* sid_tgt = sc.take<int64_t>(B);
-  int max_keep = 0;
-  for (int f = 0; f < B; f += kAdmitChunk) {
-    ConvertRowsArg cr{};
-    AdmitSynRowsArg sr{};
-    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
-    for (int i = 0; i < nn; ++i) {
-      const mbv_convert_row& k = rows_host[f + i];
-      cr.row[i] = ConvertRow{k.wave, k.samples, k.wave_dtype, fr[f + i], k.sid_src, k.sid_tgt};
-      sr.row[i] = AdmitSynRow{k.noise, fr[f + i], k.noise_scale, fr[f + i], k.z};
-      if (fr[f + i] > max_keep) max_keep = fr[f + i];
-    }
-    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
-    launch_admit_syn_rows(sr, nn, f, srows, s);
-  }
-  ++m->converter_runs;
-  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
-  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_out, B, gin, c.n_speakers, nullptr, s);
-  launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, ypad, Q.cin_pad, T, s);
-  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
-  if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows)) return 1;
-  // forward flow with the source speaker (models.py:795), then reverse with the target (:796), in place
-  run_flow_forward(m, z, g_src, pb, lens, B, T, s);
-  for (int f = kNFlows - 1; f >= 0; --f)
-    run_coupling(m, f, true, z, g_out, hbuf, acts, skip, gc, ustart, lens, B, T, s);
-  launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
-  HIPCHK(m, hipGetLastError());
-  return 0;
+  return run_posterior_rows(m, who, crows, srows, T, longest, 0, g_out, hop, win, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ live voice conversion (audio that is still arriving)
@@ -3671,42 +3699,28 @@ int mbv_convert_window(const mbv_config* cfg, int first, int count, int64_t fina
 
 int mbv_convert_ranges_plan(const mbv_config* cfg, int n, const int32_t* window_frames, int32_t* run_of_range) {
   if (!cfg || n <= 0 || !window_frames) return -1;
-  int runs = 0, B = 0, T = 0;
-  for (int i = 0; i < n; ++i) {
-    const int w = window_frames[i];
-    if (w < 1 || !convert_run_fits(*cfg, 1, w)) return -1;
-    const int Tn = w > T ? w : T;
-    if (B == 0 || !convert_run_fits(*cfg, B + 1, Tn)) { ++runs; B = 1; T = w; }
-    else { ++B; T = Tn; }
-    if (run_of_range) run_of_range[i] = runs - 1;
-  }
-  return runs;
+  for (int i = 0; i < n; ++i)
+    if (window_frames[i] < 1 || !convert_run_fits(*cfg, 1, window_frames[i])) return -1;
+  // With a single class, at most one run is ever open: the generic loop gives exactly the sequential cut.
+  return plan_runs(n, window_frames, no_signature, [&](int B, int T) { return convert_run_fits(*cfg, B, T); }, run_of_range);
 }
 
 int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, int hop, int win, void* stream) {
   if (!m) return 1;
   const char* who = "mbv_convert_ranges";
-  if (!m->finalized) return m->fail("weights not finalized");
+  if (convert_call_refusal(m, who, "live", !rows_host || n <= 0, hop, win)) return 1;
   const mbv_config& c = m->cfg;
-  if (c.n_speakers <= 0 || !m->emb_g.present)
-    return m->fail("n_speakers have to be larger than 0.");              // models.py:791 assert
-  if (!rows_host || n <= 0) return m->fail("%s: bad arguments", who);
-  if (m->conv_bf16) return m->fail("%s: live conversion is not built for the \"conv_bf16\" mode", who);
-  const int n_fft = 2 * (c.spec_channels - 1);
-  if (const char* why = spectrogram_args_error(n_fft, hop, win))
-    return m->fail("%s: %s (n_fft = 2 (spec_channels - 1) = %d)", who, why, n_fft);
-  const int B = n, H = c.hidden_channels, I = c.inter_channels, gin = c.gin_channels;
+  const int n_fft = 2 * (c.spec_channels - 1), B = n;
   int Lv, Rv;
   converter_context(&Lv, &Rv);
-  struct Win { int wa, len; };
-  std::vector<Win> wins(B);
+  std::vector<ConvertRow> crows(B);
+  std::vector<AdmitSynRow> srows(B);
   std::vector<int32_t> wlen(B);
   int T = 0, max_keep = 0;
   for (int i = 0; i < B; ++i) {
     const mbv_convert_range& k = rows_host[i];
     if (!k.wave || !k.z || k.arrived < 1) return m->fail("%s: row %d: wave or z missing, or no samples", who, i);
-    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
-      return m->fail("%s: row %d: unknown wave_dtype %d", who, i, k.wave_dtype);
+    if (convert_row_refusal(m, who, i, k.wave_dtype, k.sid_src, k.sid_tgt, k.noise_scale)) return 1;
     const int64_t fin = spectrogram_ready(k.arrived, k.closed != 0, n_fft, hop);
     if (fin > 0x7fffffff) return m->fail("%s: row %d: too many frames", who, i);
     if (k.first < 0 || k.count < 1 || (int64_t)k.first + k.count > fin)
@@ -3716,83 +3730,26 @@ int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, 
       return m->fail("%s: row %d: frames [%d, %d + %d) are not final yet: they need spectrogram frames up to %lld, and "
                      "%lld are final (the recording is open)", who, i, k.first, k.first, k.count,
                      (long long)k.first + k.count + Rv, (long long)fin);
-    if (k.sid_src < 0 || k.sid_src >= c.n_speakers || k.sid_tgt < 0 || k.sid_tgt >= c.n_speakers)
-      return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, c.n_speakers);
-    if (!(k.noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
     int wa, wb;
     convert_window(k.first, k.count, fin, &wa, &wb);
     if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < wb))
       return m->fail("%s: row %d: noise missing, or noise_stride %lld < the window's end %d", who, i, (long long)k.noise_stride, wb);
     if (k.z_stride < (int64_t)k.first + k.count)
       return m->fail("%s: row %d: z_stride %lld < first + count = %d", who, i, (long long)k.z_stride, k.first + k.count);
-    wins[i] = Win{wa, wb - wa};
     wlen[i] = wb - wa;
     if (wlen[i] > T) T = wlen[i];
     if (k.count > max_keep) max_keep = k.count;
+    crows[i] = ConvertRow{k.wave, k.arrived, k.wave_dtype, wlen[i], k.sid_src, k.sid_tgt, wa, 0};
+    // the noise of the window's frames at the block's stride; the kept frames [first, first + count) of the window
+    // go to frame `first` of the stream's own z
+    srows[i] = AdmitSynRow{k.noise ? k.noise + wa : nullptr, k.noise_stride, k.noise_scale, k.count,
+                           k.z + k.first, wlen[i], k.first - wa, k.z_stride};
   }
   if (mbv_convert_ranges_plan(&c, B, wlen.data(), nullptr) != 1)
     return m->fail("%s: the %d rows (widest window %d frames) belong to more than one run of mbv_convert_ranges_plan", who, B, T);
-  const auto& Q = m->encq;
-  bool fused = wn_takes_fused(m, Q.in, Q.in16, B, T) && wn_fused_fits(B, I, T);
-  for (int f = 0; f < kNFlows; ++f) fused = fused && wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T);
-  if (!fused)
-    return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
-                   "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
-  DEVICE_GUARD(m);
-  hipStream_t s = (hipStream_t)stream;
-  const mbv_model::SpectrogramTables* tab = nullptr;
-  if (spectrogram_tables_of(m, who, n_fft, win, &tab)) return 1;
-  const size_t BT = (size_t)B * T;
-  const size_t need = (BT * ((size_t)Q.cin_pad + 3 * H + 3 * I) + (size_t)B * (2 * gin + 2 * H * mbv_model::kEncQLayers + 1)) * 4 +
-                      wn_units_ints(B, T) * 4 + (size_t)B * (sizeof(ConvertRow) + sizeof(AdmitSynRow) + 16) + 64 * 256;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, need)) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
-  m->stages.clear();
-  float* ypad = sc.take<float>(BT * Q.cin_pad);
-  m->stages["convert_ypad"] = StageRef{ypad, (int64_t)(BT * Q.cin_pad)};
-  float* hbuf = sc.take<float>(BT * H);
-  float* acts = sc.take<float>(BT * H);
-  float* skip = sc.take<float>(BT * H);
-  float* stats = sc.take<float>(BT * 2 * I);
-  float* z = sc.take<float>(BT * I);
-  float* g_src = sc.take<float>((size_t)B * gin);
-  float* g_tgt = sc.take<float>((size_t)B * gin);
-  float* gc = sc.take<float>((size_t)B * 2 * H * mbv_model::kEncQLayers);
-  int* lens = sc.take<int>(B);
-  int* ustart = sc.take<int>(wn_units_ints(B, T));
-  ConvertRow* crows = sc.take<ConvertRow>(B);
-  AdmitSynRow* srows = sc.take<AdmitSynRow>(B);
-  int64_t* sid_src = sc.take<int64_t>(B);
-  int64_t* sid_tgt = sc.take<int64_t>(B);
-  for (int f = 0; f < B; f += kAdmitChunk) {
-    ConvertRowsArg cr{};
-    AdmitSynRowsArg sr{};
-    const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
-    for (int i = 0; i < nn; ++i) {
-      const mbv_convert_range& k = rows_host[f + i];
-      const Win& w = wins[f + i];
-      cr.row[i] = ConvertRow{k.wave, k.arrived, k.wave_dtype, w.len, k.sid_src, k.sid_tgt, w.wa, 0};
-      // the noise of the window's frames at the block's stride; the kept frames [first, first + count) of the window
-      // go to frame `first` of the stream's own z
-      sr.row[i] = AdmitSynRow{k.noise ? k.noise + w.wa : nullptr, k.noise_stride, k.noise_scale, k.count,
-                              k.z + k.first, w.len, k.first - w.wa, k.z_stride};
-    }
-    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
-    launch_admit_syn_rows(sr, nn, f, srows, s);
-  }
-  ++m->converter_runs;
-  const int rt = T > kLiveRouteFrames ? T : kLiveRouteFrames;
-  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
-  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s);
-  launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, ypad, Q.cin_pad, T, s);
-  const PosteriorBufs pb{ypad, hbuf, acts, skip, stats, gc, ustart};
-  if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows, rt)) return 1;
-  run_flow_forward(m, z, g_src, pb, lens, B, T, s, rt);
-  for (int f = kNFlows - 1; f >= 0; --f)
-    run_coupling(m, f, true, z, g_tgt, hbuf, acts, skip, gc, ustart, lens, B, T, s, rt);
-  launch_scatter_z_rows(z, lens, srows, B, I, T, max_keep, s);
-  HIPCHK(m, hipGetLastError());
-  return 0;
+  // the target speaker vectors stay in scratch; the planner sees a length past the narrow kernel's for every window
+  return run_posterior_rows(m, who, crows, srows, T, max_keep, T > kLiveRouteFrames ? T : kLiveRouteFrames, nullptr, hop,
+                            win, (hipStream_t)stream);
 }
 
 

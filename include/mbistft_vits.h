@@ -600,6 +600,44 @@ int mbv_resample_pcm16_chunks(mbv_model *m, const mbv_pcm_chunk *chunks_host, in
                               int filter, int16_t *packed, int64_t packed_capacity, void *stream);
 int64_t mbv_wire_runs(mbv_model *m);
 
+/* ---- live input: recordings that are still arriving, resampled to the model's rate range by range ----------
+ * The polyphase resampler puts zeros outside [0, n).  An output whose taps all lie below the samples that have
+ * arrived therefore has the value it will have in the finished row, whatever n turns out to be; the total matters
+ * only for the flush at close (the outputs whose taps reach past the end, and the zeros of fix_length) and for the
+ * row's length.  mbv_resample_ranges computes fp32 outputs [out_first, out_first + out_count) of n recordings in
+ * ONE launch, each from its own raw row (read in place, fp32 or int16 scaled by exactly 1 / 32768) into its own
+ * model-rate row; only the range is written.  Every stored value is BITWISE what mbv_resample stores there for the
+ * finished recording (int16: for pcm / 32768): same staged taps, same tap order, same four-accumulator sum.
+ *
+ * mbv_resample_ready_open (host only: no handle, no GPU): how many outputs are final once in_avail raw samples of an
+ * OPEN recording exist: the open branch of mbv_resample_ready, which does not depend on the total.  Equal rates:
+ * in_avail.  -1 with a message (mbv_last_error(NULL)) for an unknown filter or a rate pair mbv_resample refuses.
+ * A closed row (in_total >= 0) is ready up to min(ceil(in_total * target / orig), out_capacity); a closed row's
+ * outputs in [int(n ratio), ceil(n ratio)) are written as zeros, as mbv_resample writes them.
+ *
+ * rows_host is HOST memory [n]; its values travel to the device as kernel arguments (written to the handle's
+ * scratch by a one-workgroup kernel), so the array may be freed when the call returns; nothing is copied from
+ * caller memory and nothing is synchronised (beyond the first call for a rate pair, as mbv_resample).  Nothing at
+ * or past in_avail is read from wave.  Refused with a message that names the row, launching nothing and leaving
+ * the handle usable: a range that ends beyond what is ready, out_first + out_count > out_capacity, a negative field
+ * (in_total below -1), in_total >= 0 with in_avail != in_total, a missing pointer, an unknown dtype or filter, a
+ * rate pair mbv_resample refuses, equal rates (they take no kernel), two rows that write overlapping ranges of one
+ * out, n < 0.  n == 0, or a call whose ranges are all empty, launches nothing and counts nothing.
+ *
+ * mbv_input_runs: launches of the live-input resampler on this handle since mbv_create (table writers are not
+ * counted), the counterpart of mbv_wire_runs for the input side. */
+typedef struct mbv_resample_range {
+  const void *wave; int32_t wave_dtype;  /* DEVICE raw recording at orig_sr, MBV_WAVE_F32 / MBV_WAVE_PCM16, read in place */
+  int64_t in_avail;                      /* raw samples that exist */
+  int64_t in_total;                      /* -1: open; >= 0: closed at that many samples (then in_avail == in_total) */
+  int64_t out_first, out_count;          /* outputs [out_first, out_first + out_count) */
+  float *out; int64_t out_capacity;      /* DEVICE, the recording's own model-rate row; only the range is written */
+} mbv_resample_range;
+int64_t mbv_resample_ready_open(int orig_sr, int target_sr, int filter, int64_t in_avail);
+int mbv_resample_ranges(mbv_model *m, const mbv_resample_range *rows_host, int n, int orig_sr, int target_sr,
+                        int filter, void *stream);
+int64_t mbv_input_runs(mbv_model *m);
+
 /* ---- linear spectrogram ------------------------------------------------------
  * replaces spectrogram_torch(y, n_fft, sr, hop, win, center=False) (mel_processing.py:51-70), the input of
  * mbv_voice_conversion: |STFT| with (n_fft - hop) / 2 zeros on each side of the row, no centring, the

@@ -34,6 +34,7 @@ SYMBOLS = [
     "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
     "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
     "mbv_convert_ranges_plan", "mbv_convert_ranges",
+    "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
 ]
 
 
@@ -96,6 +97,12 @@ class MbvConvertRange(C.Structure):
                 ("sid_src", C.c_int32), ("sid_tgt", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
                 ("noise", C.c_void_p), ("noise_stride", C.c_int64), ("noise_scale", C.c_float), ("z", C.c_void_p),
                 ("z_stride", C.c_int64)]
+
+
+class MbvResampleRange(C.Structure):
+    """mbv_resample_range of include/mbistft_vits.h (mbv_resample_ranges)."""
+    _fields_ = [("wave", C.c_void_p), ("wave_dtype", C.c_int32), ("in_avail", C.c_int64), ("in_total", C.c_int64),
+                ("out_first", C.c_int64), ("out_count", C.c_int64), ("out", C.c_void_p), ("out_capacity", C.c_int64)]
 
 
 class MbvAlignOutputs(C.Structure):
@@ -222,8 +229,8 @@ def lib():
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
-    # three that came with "tail_once", pooled conversion's three and live conversion's six may be absent there, and
-    # calling one then raises AttributeError.
+    # three that came with "tail_once", pooled conversion's three, live conversion's six and the live wire's three may
+    # be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -232,7 +239,8 @@ def lib():
                 "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
                 "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
                 "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
-                "mbv_convert_ranges_plan", "mbv_convert_ranges") if os.environ.get("MBV_LIB") else ()
+                "mbv_convert_ranges_plan", "mbv_convert_ranges",
+                "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -274,6 +282,12 @@ def lib():
         L.mbv_convert_window.argtypes = [C.POINTER(MbvConfig), i32, i32, C.c_int64, C.POINTER(C.c_int32 * 2)]
         L.mbv_convert_ranges_plan.argtypes = [C.POINTER(MbvConfig), i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.mbv_convert_ranges.argtypes = [vp, C.POINTER(MbvConvertRange), i32, i32, i32, vp]
+    if hasattr(L, "mbv_resample_ranges") or not optional:
+        L.mbv_resample_ready_open.argtypes = [i32, i32, i32, C.c_int64]
+        L.mbv_resample_ready_open.restype = C.c_int64
+        L.mbv_resample_ranges.argtypes = [vp, C.POINTER(MbvResampleRange), i32, i32, i32, i32, vp]
+        L.mbv_input_runs.argtypes = [vp]
+        L.mbv_input_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -121,6 +121,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int ragged_scanned = 0, ragged_splitk = -1;
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
+  int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
@@ -3411,6 +3412,105 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
 }
 
 int64_t mbv_wire_runs(mbv_model* m) { return m ? m->wire_runs : -1; }
+
+int64_t mbv_resample_ready_open(int orig_sr, int target_sr, int filter, int64_t in_avail) {
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
+    g_create_error = "mbv_resample_ready_open: unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
+    return -1;
+  }
+  if (in_avail < 0) in_avail = 0;
+  if (orig_sr > 0 && orig_sr == target_sr) return in_avail;
+  ResampleGeom g{};
+  const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
+  if (why) { g_create_error = std::string("mbv_resample_ready_open: ") + why; return -1; }
+  return resample_ready_open(g, in_avail);
+}
+
+int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n, int orig_sr, int target_sr,
+                        int filter, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_resample_ranges";
+  if (n < 0 || (n > 0 && !rows_host)) return m->fail("%s: bad arguments", who);
+  int L = 0, M = 0;
+  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
+    return m->fail("%s: unknown filter %d", who, filter);
+  if (orig_sr == target_sr)
+    return m->fail("%s: equal rates (%d) take no kernel: the samples are the model's input as they are", who, orig_sr);
+  for (int i = 0; i < n; ++i) {
+    const mbv_resample_range& k = rows_host[i];
+    if (!k.wave || !k.out) return m->fail("%s: row %d: wave / out missing", who, i);
+    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
+      return m->fail("%s: row %d: unknown wave_dtype %d", who, i, (int)k.wave_dtype);
+    if (k.in_avail < 0 || k.in_total < -1 || k.out_first < 0 || k.out_count < 0 || k.out_capacity < 0)
+      return m->fail("%s: row %d: in_avail, out_first, out_count and out_capacity must be >= 0, in_total >= -1", who, i);
+    if (k.in_total >= 0 && k.in_avail != k.in_total)
+      return m->fail("%s: row %d: a closed recording has all its samples (in_avail %lld, in_total %lld)", who, i,
+                     (long long)k.in_avail, (long long)k.in_total);
+    if (k.out_first > k.out_capacity || k.out_count > k.out_capacity - k.out_first)
+      return m->fail("%s: row %d: outputs [%lld, %lld) lie outside the row of out_capacity %lld", who, i,
+                     (long long)k.out_first, (long long)(k.out_first + k.out_count), (long long)k.out_capacity);
+    if ((double)k.out_capacity * M >= 0x1p62 || (double)k.in_avail * L >= 0x1p62)
+      return m->fail("%s: row %d: out_capacity * M or in_avail * L overflows the 64-bit time index", who, i);
+  }
+  DEVICE_GUARD(m);
+  const mbv_model::ResampleBank* rb = nullptr;
+  if (resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i) {
+    const mbv_resample_range& k = rows_host[i];
+    int64_t ready;
+    if (k.in_total >= 0) {
+      ready = (int64_t)std::ceil((double)k.in_total * rb->g.ratio);        // fix_length of the whole row, as mbv_resample
+      if (ready > k.out_capacity) ready = k.out_capacity;
+    } else {
+      ready = resample_ready_open(rb->g, k.in_avail);
+    }
+    if (k.out_first + k.out_count > ready)
+      return m->fail("%s: row %d: outputs up to %lld asked for, but %lld input samples (%s) make only %lld final", who, i,
+                     (long long)(k.out_first + k.out_count), (long long)k.in_avail, k.in_total >= 0 ? "closed" : "open",
+                     (long long)ready);
+    if (k.out_count > 0) live.push_back(i);
+  }
+  if (live.empty()) return 0;
+  {
+    // two rows must not write one sample: the non-empty ranges in address order (as mbv_resample_pcm16_chunks)
+    std::vector<int> order(live);
+    auto lo = [&](int i) { return (uintptr_t)(rows_host[i].out + rows_host[i].out_first); };
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return lo(a) < lo(b); });
+    for (size_t j = 1; j < order.size(); ++j) {
+      const int a = order[j - 1], b = order[j];
+      if (lo(a) + sizeof(float) * (uintptr_t)rows_host[a].out_count > lo(b))
+        return m->fail("%s: rows %d and %d write overlapping ranges of one out", who, a < b ? a : b, a < b ? b : a);
+    }
+  }
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(ResampleRangeRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  ResampleRangeRow* rows = reinterpret_cast<ResampleRangeRow*>(m->scrB);
+  for (size_t f = 0; f < live.size(); f += kPcmPoolChunk) {
+    ResampleRangeRowsArg r{};
+    const int nn = (int)(live.size() - f < (size_t)kPcmPoolChunk ? live.size() - f : (size_t)kPcmPoolChunk);
+    for (int i = 0; i < nn; ++i) {
+      const mbv_resample_range& k = rows_host[live[f + i]];
+      r.row[i] = ResampleRangeRow{k.wave, k.wave_dtype, k.in_total >= 0 ? 1 : 0, k.in_avail, k.out_first,
+                                  k.out_first + k.out_count, k.out};
+    }
+    launch_resample_range_rows(r, nn, (int)f, rows, s);
+  }
+  for (size_t f = 0; f < live.size(); f += 65535) {         // the grid's y limit
+    const size_t nn = live.size() - f < 65535 ? live.size() - f : 65535;
+    int64_t max_count = 0;
+    for (size_t i = 0; i < nn; ++i)
+      if (rows_host[live[f + i]].out_count > max_count) max_count = rows_host[live[f + i]].out_count;
+    if ((max_count + kResampleTile - 1) / kResampleTile > 0x7fffffff) return m->fail("%s: a range too long for one grid", who);
+    ++m->input_runs;
+    launch_resample_ranges(rows + f, (int)nn, max_count, rb->d, rb->g, s);
+  }
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_input_runs(mbv_model* m) { return m ? m->input_runs : -1; }
 
 namespace {
 const char* spectrogram_args_error(int n_fft, int hop, int win) {

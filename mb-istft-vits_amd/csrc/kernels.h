@@ -400,6 +400,26 @@ void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow*
 // in_total), pcm_cap) of every row.
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
                                 const ResampleGeom& g, short* packed, hipStream_t s);
+// Live input (mbv_resample_ranges): fp32 outputs [out_first, out_end) of MANY recordings that are still arriving,
+// each from its own raw row (fp32, or int16 scaled by 1 / 32768) into its own model-rate row, in one launch.  A
+// table row is one recording; the table lives in the arena (launch_resample_range_rows).
+struct ResampleRangeRow {
+  const void* x;               // the raw recording, read in place
+  int32_t dtype;               // 0 = fp32, 1 = int16
+  int32_t closed;              // 1: n is the recording's length (outputs at or past int(n ratio) are zeros)
+  int64_t n;                   // raw samples that exist: nothing at or past it is loaded
+  int64_t out_first, out_end;
+  float* out;                  // the recording's own model-rate row
+};
+struct ResampleRangeRowsArg { ResampleRangeRow row[kPcmPoolChunk]; };
+void launch_resample_range_rows(const ResampleRangeRowsArg& r, int n, int first, ResampleRangeRow* rows, hipStream_t s);
+// open count of resample_ready without a total: outputs no tap of which lies at or past in_avail
+int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail);
+// outputs [out_first, out_end) of every table row (n <= 65535), each bitwise what launch_resample stores there for the
+// finished recording.  max_count >= out_end - out_first of every row.  The caller guarantees out_end <=
+// resample_ready_open(g, n) for an open row, <= ceil(n ratio) for a closed one, and the row's capacity.
+void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
+                            const ResampleGeom& g, hipStream_t s);
 
 // ---------------------------------------------------------------- linear spectrogram (spectrogram.hip)
 // |STFT| of spectrogram_torch(center=False) per row as if alone: (n_fft - hop) / 2 zeros each side, periodic

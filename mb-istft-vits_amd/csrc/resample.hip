@@ -152,6 +152,13 @@ int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total
   return r < all ? r : all;
 }
 
+int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail) {
+  // the open branch of resample_ready: floor(t M / L) - left + K - 1 < in_avail.  No total enters it.
+  const int64_t a = in_avail - g.K + g.left + 1;
+  if (a <= 0) return 0;
+  return (a * g.L + g.M - 1) / g.M;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Device code shared by the one-shot kernel and the ranged one: the staged input window of a tile and the
 // polyphase sum of one output.  One workgroup = up to kResampleTile consecutive outputs of one row, one output
@@ -171,6 +178,16 @@ __device__ __forceinline__ void resample_stage(float* xs, const float* __restric
   for (int i = threadIdx.x; i < W; i += kResampleTile) {
     const int64_t j = j0 + i;
     xs[i] = (j >= 0 && j < limit) ? xb[j] : 0.f;
+  }
+}
+
+// the same window of an int16 recording: (float)s * 2^-15 is exact, bitwise pcm.float() / 32768
+__device__ __forceinline__ void resample_stage(float* xs, const short* __restrict__ xb, int64_t j0, int64_t t_last,
+                                               int L, int M, int K, int left, int64_t limit) {
+  const int W = (int)((t_last * M) / L - left + K - j0);
+  for (int i = threadIdx.x; i < W; i += kResampleTile) {
+    const int64_t j = j0 + i;
+    xs[i] = (j >= 0 && j < limit) ? (float)xb[j] * (1.f / 32768.f) : 0.f;
   }
 }
 
@@ -423,6 +440,65 @@ __global__ void pcm_pool_rows_kernel(const PcmPoolRowsArg r, int n, int first, P
 
 void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow* rows, hipStream_t s) {
   hipLaunchKernelGGL(pcm_pool_rows_kernel, dim3(1), dim3(kPcmPoolChunk), 0, s, r, n, first, rows);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Live input (mbv_resample_ranges): the one-shot kernel's outputs [out_first, out_end) of many recordings that are
+// still arriving, blockIdx.y = table row, blockIdx.x = tile out_first + 256 x of that row's own range; the grid holds
+// the tiles of the longest range and a tile past its row's end returns after the table load.
+//   - the caller has checked out_end against the readiness of the row, so no stored output of an open row has a tap
+//     at or past n; the staging still refuses to load those indices (the raw buffer beyond the frontier is
+//     uninitialised memory)
+//   - taps below n see what the one-shot kernel's staging gives them and taps outside [0, n) are zeros in both, the
+//     sum runs in resample_output's order: every stored value is bitwise the one-shot kernel's for the finished row,
+//     whichever tile holds it
+//   - a closed row stores zeros in [int(n ratio), out_end), as the one-shot kernel does up to ceil(n ratio)
+// No atomics, no LDS beyond resample_lds_floats(g).
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kResampleTile)
+resample_ranges_kernel(const ResampleRangeRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
+                       int left, double ratio) {
+  extern __shared__ float xs[];
+  const ResampleRangeRow r = rows[blockIdx.y];
+  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
+  if (t0 >= r.out_end) return;                            // uniform over the workgroup: a shorter range than the grid's
+  int64_t n_out = r.out_end;                              // open: every output of the range is computed
+  if (r.closed) {
+    n_out = (int64_t)((double)r.n * ratio);               // resampy: int(n_in * sample_ratio)
+    if (n_out > r.out_end) n_out = r.out_end;
+  }
+  const int64_t t = t0 + threadIdx.x;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: the zeros of fix_length
+    if (t < r.out_end) r.out[t] = 0.f;
+    return;
+  }
+  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
+  const int64_t j0 = resample_window_first(t0, L, M, left);
+  if (r.dtype == 1) resample_stage(xs, static_cast<const short*>(r.x), j0, t_last, L, M, K, left, r.n);
+  else resample_stage(xs, static_cast<const float*>(r.x), j0, t_last, L, M, K, left, r.n);
+  __syncthreads();
+  if (t >= r.out_end) return;
+  if (t >= n_out) { r.out[t] = 0.f; return; }
+  r.out[t] = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
+}
+
+void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
+                            const ResampleGeom& g, hipStream_t s) {
+  const int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+  hipLaunchKernelGGL(resample_ranges_kernel, dim3((unsigned)bx, n), dim3(kResampleTile), lds, s, rows, bank, g.L, g.M,
+                     g.K, g.left, g.ratio);
+}
+
+// the table of a live-input call: by value from the host into the arena, one workgroup (as launch_pcm_pool_rows)
+__global__ void resample_range_rows_kernel(const ResampleRangeRowsArg r, int n, int first,
+                                           ResampleRangeRow* __restrict__ rows) {
+  const int i = threadIdx.x;
+  if (i < n) rows[first + i] = r.row[i];
+}
+
+void launch_resample_range_rows(const ResampleRangeRowsArg& r, int n, int first, ResampleRangeRow* rows, hipStream_t s) {
+  hipLaunchKernelGGL(resample_range_rows_kernel, dim3(1), dim3(kPcmPoolChunk), 0, s, r, n, first, rows);
 }
 
 }  // namespace mbv

@@ -1084,7 +1084,8 @@ class SynthesizerTrn(nn.Module):
         than 256 frames it is bitwise `convert_stream(whole, ..., noise=st.noise[:, :, :T])` chunk by chunk (default
         mode), for a shorter one within fp32 rounding of it.  Draws one `torch.randn(1, inter, max_frames)` on the device
         generator here, unless `noise` (that shape) is given.  Buffers are sized for `max_samples` once.  The audio
-        must be at the model's rate: a streaming input resampler is not built."""
+        must be at the model's rate; `wire.convert_live_pcm16` is the form that takes raw samples at any rate and
+        hands out int16 at the service's rate."""
         return stream.LiveStream(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=dtype,
                                  noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
                                  max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr)
@@ -1410,6 +1411,30 @@ class SynthesizerTrn(nn.Module):
             _capi.check(h, _capi.lib().mbv_resample_pcm16_chunks(h, chunks, len(chunks), int(orig_sr), int(target_sr), filt,
                                                                  self._ptr(packed), cap, self._stream()),
                         "mbv_resample_pcm16_chunks")
+
+    @torch.no_grad()
+    def resample_ranges(self, rows, orig_sr, target_sr, res_type="kaiser_best"):
+        """The input side of a live wire (`mbv_resample_ranges`; `wire.LiveWire` and `wire.PcmPool` drive it): `rows`
+        is a ctypes array (or a list) of `_capi.MbvResampleRange`, each the raw buffer of one recording that is still
+        arriving (fp32 or int16, device address), how much of it exists, and the range of its model-rate row to write.
+        ONE launch for all rows; every stored value is bitwise what `resample` gives there for the finished recording.
+        A range must end at or below `wire.resample_ready_open(orig_sr, target_sr, in_avail)` while the recording is
+        open.  No host synchronisation (beyond the first call for a rate pair)."""
+        filt = RESAMPLE_TYPES.get(res_type)
+        if filt is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        if not isinstance(rows, C.Array):
+            rows = (_capi.MbvResampleRange * len(rows))(*rows)
+        h = self._ensure_handle()
+        with torch.cuda.device(self._device()):
+            _capi.check(h, _capi.lib().mbv_resample_ranges(h, rows, len(rows), int(orig_sr), int(target_sr), filt,
+                                                           self._stream()),
+                        "mbv_resample_ranges")
+
+    def input_runs(self):
+        """Launches of the live-input resampler made on this model's handle so far (`mbv_input_runs`)."""
+        return int(_capi.lib().mbv_input_runs(self._ensure_handle()))
 
     @torch.no_grad()
     def spectrogram(self, wave, n_fft, hop_size, win_size, valid_samples=None, center=False):

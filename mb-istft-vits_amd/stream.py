@@ -68,6 +68,14 @@ def spectrogram_ready(arrived, closed, n_fft, hop_size):
     return r
 
 
+def check_closable(arrived, sr, n_fft, hop_size):
+    """A recording may be closed once it gives a spectrogram frame; ValueError otherwise (the one check of
+    `LiveStream.close` and `wire.LiveWirePlan.close`; `arrived` counts samples at the model's rate `sr`)."""
+    if arrived < 1 or spectrogram_ready(arrived, True, n_fft, hop_size) < 1:
+        raise ValueError("%d samples at %d Hz give no spectrogram frame (n_fft %d, hop_size %d)"
+                         % (arrived, sr, n_fft, hop_size))
+
+
 class LivePlan:
     """What a recording that is still arriving may convert and decode, in pure integers (no tensor, no GPU).
 
@@ -172,7 +180,8 @@ class LiveStream:
         self.model_sr, self.hop_size, self.win_size = int(model_sr), int(hop_size), int(win_size)
         if in_sr is not None and int(in_sr) != self.model_sr:
             raise ValueError("convert_live takes audio at the model's rate (in_sr %d, model_sr %d): a streaming input "
-                             "resampler is not built; resample before pushing" % (int(in_sr), self.model_sr))
+                             "resampler is not part of it; wire.convert_live_pcm16 takes raw samples at any rate"
+                             % (int(in_sr), self.model_sr))
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("convert_live: dtype must be int16 or float32, got %s" % dtype)
         sids = []
@@ -288,11 +297,35 @@ class LiveStream:
     def close(self):
         if self._plan.closed:
             return
-        a = self._plan.arrived
-        if a < 1 or spectrogram_ready(a, True, self.n_fft, self.hop_size) < 1:
-            raise ValueError("%d samples at %d Hz give no spectrogram frame (n_fft %d, hop_size %d)"
-                             % (a, self.model_sr, self.n_fft, self.hop_size))
+        check_closable(self._plan.arrived, self.model_sr, self.n_fft, self.hop_size)
         self._plan.close()
+
+    # ---- for an owner that fills `samples` itself (wire.LiveWire resamples into it)
+    @property
+    def plan(self):
+        """The stream's `LivePlan` (integers only)."""
+        return self._plan
+
+    @property
+    def chunks(self):
+        """(first, count) of every chunk decoded so far, in order (by `poll` or by a pool)."""
+        return tuple(self._chunks)
+
+    @property
+    def all_decoded(self):
+        """The recording is closed and its last chunk is decoded."""
+        return self._plan.all_released
+
+    def fed(self, count, last=False):
+        """The owner wrote `count` more samples behind `arrived` into `samples` (no copy here); `last` closes the
+        recording, through `close()` and its check."""
+        if count:
+            self._plan.push(count)
+        if last:
+            self.close()
+
+    def check_handle(self):
+        self._check_handle()
 
     # ---- what a pool shares (StreamPool.step); poll() is the stand-alone form of the same steps
     def _check_handle(self):

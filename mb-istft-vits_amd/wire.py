@@ -22,9 +22,15 @@ emits the int16 samples that have become final, bitwise those `service_pcm16` gi
 `pcm_pool` is `stream_pcm16` for many streams at once: a `PcmPool` steps a `stream.StreamPool` and wires the chunks
 that step (and earlier ones) made final for ALL its streams in one `mbv_resample_pcm16_chunks` launch, and can
 hand the pieces over in one pinned host buffer filled by one copy.
+
+`convert_live_pcm16` is the live form of `convert_pcm16`: a `LiveWire` takes raw samples at the caller's rate while
+they arrive, resamples what has become final into the model-rate buffer of the `stream.LiveStream` it owns
+(`mbv_resample_ranges`), and wires the decoded frontier to int16 at the service's rate; `PcmPool.add_live` serves many
+of them with one launch per stage and tick.
 """
 import base64
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -113,12 +119,29 @@ def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best
     return int(r)
 
 
+def resample_ready_open(orig_sr, target_sr, in_avail, res_type="kaiser_best"):
+    """How many resampled samples of a row that is still OPEN are final once its first `in_avail` samples exist
+    (`mbv_resample_ready_open`, host only: no GPU needed): those no tap of which lies at or past `in_avail`.  The
+    count does not depend on the length the row will have."""
+    filt = RESAMPLE_TYPES.get(res_type)
+    if filt is None:
+        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    L = _capi.lib()
+    r = L.mbv_resample_ready_open(int(orig_sr), int(target_sr), filt, int(in_avail))
+    if r < 0:
+        msg = L.mbv_last_error(None)
+        raise _capi.MbvError(msg.decode() if msg else "mbv_resample_ready_open failed")
+    return int(r)
+
+
 def _refuse_live(st):
     from .stream import LiveStream
     if isinstance(st, LiveStream):
-        raise TypeError("the wire output of a LiveStream (net.convert_live) is not built: the resampler's output length "
-                        "and valid_samples need the recording's total length, which an open stream does not have. "
-                        "Take the float chunks from poll(), or convert the finished recording with convert_stream")
+        raise TypeError("a PcmStream does not follow a LiveStream (net.convert_live): its schedule, output length and "
+                        "valid_samples need the recording's total length, which an open stream does not have. "
+                        "wire.convert_live_pcm16 / PcmPool.add_live wire a live stream; or take the float chunks "
+                        "from poll(), or convert the finished recording with convert_stream")
 
 
 class PcmStream:
@@ -238,6 +261,327 @@ def wire_runs(net):
     return int(_capi.lib().mbv_wire_runs(net._ensure_handle()))
 
 
+class LiveWirePlan:
+    """What a live wire may resample, and what it may hand out as int16, in pure integers (no tensor, no GPU); the
+    conversion and decoding in between are the `stream.LivePlan` it wraps.
+
+      input   model-rate sample t is final iff no tap of it lies at or past the raw samples that arrived
+              (`resample_ready_open`), or the recording is closed; then there are ceil(n_raw * model_sr / in_sr) of
+              them, the `out_samples` of `net.resample`.  `feed_due()` is the range to resample now; `fed(count)`
+              records it and says whether it was the last of a closed recording, and the caller advances (and then
+              closes) the `LivePlan` by it, as `LiveStream.fed(count, last)` does.  Equal rates: `push` and
+              `close` go straight to the `LivePlan`.
+      output  after decoded chunk (first, count), int16 sample u is final iff no tap of it lies at or past
+              spf * (first + count); after the LAST chunk all ceil(spf * T * rate / model_sr) are.  One piece per
+              decoded chunk, so the pieces do not depend on how the recording was cut into pushes."""
+
+    def __init__(self, in_sr, model_sr, rate, plan, spf, max_raw, res_type="kaiser_best"):
+        self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
+        if min(self.in_sr, self.model_sr, self.rate) <= 0:
+            raise ValueError("sample rates must be positive")
+        self.plan, self.spf, self.max_raw = plan, int(spf), int(max_raw)
+        if self.max_raw < 1:
+            raise ValueError("max_samples must be >= 1")
+        self.resamples = self.in_sr != self.model_sr
+        if self.resamples:
+            resample_ready_open(self.in_sr, self.model_sr, 0, res_type)      # refuses the rate pair / filter here
+        self.capacity = self.model_total(self.max_raw)                       # model-rate samples
+        frames = int(_capi.lib().mbv_spectrogram_frames(self.capacity, plan.n_fft, plan.hop))
+        if frames < 1:
+            raise ValueError("max_samples %d gives no spectrogram frame" % self.max_raw)
+        self.o_capacity = self.spf * frames
+        self.pcm_capacity = resample_ready(self.model_sr, self.rate, self.o_capacity, self.o_capacity, res_type)
+        self._raw, self._closed = 0, False
+        self.fed_samples = 0          # model-rate samples [0, fed_samples) are in the stream's buffer
+        self.wired_chunks = 0         # decoded chunks whose final outputs are int16 already
+        self.out_done = 0             # int16 samples [0, out_done) are final and written
+        self.wire_done = False        # the last chunk is wired: valid is set
+        self.valid = None
+
+    def model_total(self, n_raw):
+        """Model-rate samples of a finished recording of n_raw raw samples: `net.resample`'s out_samples."""
+        if not self.resamples:
+            return int(n_raw)
+        return int(math.ceil(n_raw * (float(self.model_sr) / self.in_sr)))
+
+    @property
+    def raw(self):
+        return self._raw if self.resamples else self.plan.arrived
+
+    @property
+    def closed(self):
+        return self._closed if self.resamples else self.plan.closed
+
+    def check_push(self, n):
+        if self.closed:
+            raise ValueError("push after close()")
+        if self.raw + int(n) > self.max_raw:
+            raise ValueError("push: %d + %d samples exceed the stream's capacity of %d (max_samples)"
+                             % (self.raw, int(n), self.max_raw))
+
+    def push(self, n):
+        self.check_push(n)
+        if self.resamples:
+            self._raw += int(n)
+        else:
+            self.plan.push(n)
+
+    def check_close(self):
+        from .stream import check_closable
+        check_closable(self.model_total(self.raw) if self.raw > 0 else 0, self.model_sr, self.plan.n_fft, self.plan.hop)
+
+    def close(self):
+        if self.closed:
+            return
+        self.check_close()
+        if self.resamples:
+            self._closed = True
+        else:
+            self.plan.close()
+
+    @property
+    def total(self):
+        """Model-rate samples of the recording, once closed (None before)."""
+        return self.model_total(self.raw) if self.closed else None
+
+    def feed_due(self):
+        """(first, count) of the model-rate samples to resample now (count 0: only the close is left to pass on), or
+        None."""
+        if not self.resamples or self.plan.closed:
+            return None
+        if self._closed:
+            return self.fed_samples, self.total - self.fed_samples
+        ready = min(resample_ready_open(self.in_sr, self.model_sr, self._raw, self.res_type), self.capacity)
+        return (self.fed_samples, ready - self.fed_samples) if ready > self.fed_samples else None
+
+    def fed(self, count):
+        """`count` more model-rate samples are in the stream's buffer; -> True when they were the last of a closed
+        recording: the caller then advances the `LivePlan` by `count` and closes it (`LiveStream.fed(count, last)`)."""
+        self.fed_samples += int(count)
+        if self._closed and self.fed_samples != self.total:
+            raise ValueError("a closed recording is fed to its end")
+        return self._closed
+
+    def wire_due(self, chunks):
+        """chunks: the (first, count) decoded so far, in order.  -> None, or (in_avail, in_total, out_first, out_count,
+        final, pieces): the arguments of the ranged wire step that takes in every decoded chunk not wired yet, and the
+        (a, b) of the piece each of them made final."""
+        if self.wire_done or len(chunks) <= self.wired_chunks:
+            return None
+        final = self.plan.all_released                     # then the last decoded chunk is the recording's last
+        in_avail = self.spf * (chunks[-1][0] + chunks[-1][1])  # the decoded frontier
+        in_total = self.spf * self.plan.total if final else self.o_capacity
+        pieces, a = [], self.out_done
+        for i in range(self.wired_chunks, len(chunks)):
+            first, count = chunks[i]
+            if final and i == len(chunks) - 1:
+                b = resample_ready(self.model_sr, self.rate, in_total, in_total, self.res_type)
+            else:
+                b = resample_ready(self.model_sr, self.rate, self.spf * (first + count), self.o_capacity, self.res_type)
+            pieces.append((a, b))
+            a = b
+        return in_avail, in_total, self.out_done, a - self.out_done, final, pieces
+
+    def wired(self, n_chunks, out_done, final):
+        self.wired_chunks, self.out_done = int(n_chunks), int(out_done)
+        if final:
+            self.wire_done, self.valid = True, int(out_done)
+
+
+class LiveWire:
+    """One live voice conversion from raw samples to int16 (`convert_live_pcm16`): the live form of
+    `convert_pcm16`.
+
+    `push(raw)` appends 1-D int16 / fp32 samples at `in_sr` to a device buffer allocated once (no kernel).  `poll()`
+    makes at most one `mbv_resample_ranges` launch, which writes the model-rate samples that have become final
+    straight into `live.samples`, lets the `stream.LiveStream` it owns convert and decode, then wires what the decoded
+    frontier made final in one ranged resample + int16 launch and returns `[(first_out_sample, view of pcm[0, a:b])]`.
+    `close()` ends the recording: the model-rate total is ceil(n_raw * model_sr / in_sr), `net.resample`'s.
+
+      pcm            int16 [1, ceil(capacity of live.o * rate / model_sr)]
+      valid_samples  int64 [1] device, written with the last piece
+      peak           fp32 [1] device, the running peak of the resampled output so far; the `peak=` given when the
+                     stream was opened is an input, as for `stream_pcm16`
+    With `in_sr == model_sr` the samples go to `LiveStream.push` as they are (int16 stays int16) and no input kernel
+    runs.  A `PcmPool` may feed, step and wire for many at once; pieces it wired are handed out by the next `poll()`
+    without a launch, the same bytes either way."""
+
+    def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
+                 dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
+                 chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+        from .stream import LiveStream
+        if RESAMPLE_TYPES.get(res_type) is None:
+            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        if dtype not in (torch.float32, torch.int16):
+            raise TypeError("convert_live_pcm16: dtype must be int16 or float32, got %s" % dtype)
+        self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
+        if min(self.in_sr, self.model_sr, self.rate) <= 0:
+            raise ValueError("sample rates must be positive")
+        self.max_samples, self.dtype = int(max_samples), dtype
+        if self.max_samples < 1:
+            raise ValueError("convert_live_pcm16: max_samples must be >= 1")
+        resamples = self.in_sr != self.model_sr
+        if resamples:
+            resample_ready_open(self.in_sr, self.model_sr, 0, res_type)      # refuses the rate pair before any buffer
+        if self.rate != self.model_sr:
+            resample_ready(self.model_sr, self.rate, 0, 1, res_type)
+        cap = int(math.ceil(self.max_samples * (float(self.model_sr) / self.in_sr))) if resamples else self.max_samples
+        self.live = LiveStream(net, sid_src, sid_tgt, model_sr, hop_size, win_size, cap,
+                               dtype=torch.float32 if resamples else dtype, noise_scale=noise_scale, noise=noise,
+                               chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames,
+                               convert_frames=convert_frames)
+        live = self.live
+        self._net = net
+        self._plan = LiveWirePlan(self.in_sr, self.model_sr, self.rate, live.plan, live.spf, self.max_samples, res_type)
+        assert self._plan.o_capacity == live.o.shape[-1] and self._plan.capacity == live.max_samples
+        dev = live.z.device
+        with torch.cuda.device(dev):
+            # raw samples beyond the frontier are never read, so the buffer is not cleared
+            self.raw = torch.empty(self.max_samples, device=dev, dtype=dtype) if resamples else None
+            self.pcm = torch.zeros(1, self._plan.pcm_capacity, device=dev, dtype=torch.int16)
+            self.valid_samples = torch.zeros(1, device=dev, dtype=torch.int64)
+            self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
+            # valid input samples of the wire step: the capacity of o while the total is unknown
+            self._valid_in = torch.full((1,), self._plan.o_capacity, device=dev, dtype=torch.int64)
+            if peak is not None:
+                if not torch.is_tensor(peak):
+                    peak = torch.full((1,), float(peak), device=dev, dtype=torch.float32)
+                peak = peak.to(device=dev, dtype=torch.float32).contiguous()
+                if peak.shape != (1,):
+                    raise ValueError("peak must be a float or an fp32 [1] tensor")
+            self._peak_in = peak
+        self._pieces = []             # (a, b) of every piece wired so far, in order
+        self._handed = 0              # the piece poll() hands out next
+
+    # ---- the recording
+    @property
+    def arrived(self):
+        """Raw samples pushed so far."""
+        return self._plan.raw
+
+    @property
+    def closed(self):
+        return self._plan.closed
+
+    @property
+    def finished(self):
+        return self._plan.wire_done and self._handed >= len(self._pieces)
+
+    def push(self, samples):
+        if self.raw is None:
+            self.live.push(samples)                # equal rates: the stream's own push, unchanged
+            return
+        if not torch.is_tensor(samples):
+            raise TypeError("push takes a 1-D tensor of %s samples" % self.dtype)
+        if samples.dtype != self.dtype:
+            raise TypeError("push: the stream was opened for %s samples, got %s" % (self.dtype, samples.dtype))
+        if samples.dim() != 1:
+            raise ValueError("push takes 1-D samples, got shape %s" % (tuple(samples.shape),))
+        n, a = samples.numel(), self._plan.raw
+        self._plan.check_push(n)
+        if n:
+            self.raw[a:a + n].copy_(samples)
+            self._plan.push(n)
+
+    def close(self):
+        if self.raw is None:
+            self.live.close()
+        else:
+            self._plan.close()
+
+    # ---- what a pool shares (PcmPool.step); poll() is the stand-alone form of the same steps
+    def _feed_row(self, row):
+        """Fills `row` with the input range due now; -> its count, or None when nothing is due (a count of 0: only the
+        close is left to pass on)."""
+        due = self._plan.feed_due()
+        if due is None:
+            return None
+        self.live.check_handle()
+        p = self._plan
+        row.wave, row.wave_dtype = self.raw.data_ptr(), 1 if self.dtype == torch.int16 else 0
+        row.in_avail, row.in_total = p.raw, p.raw if p.closed else -1
+        row.out_first, row.out_count = due
+        row.out, row.out_capacity = self.live.samples.data_ptr(), p.capacity
+        return due[1]
+
+    def _feed(self):
+        rows = (_capi.MbvResampleRange * 1)()
+        n = self._feed_row(rows[0])
+        if n is None:
+            return
+        if n:
+            self._net.resample_ranges(rows, self.in_sr, self.model_sr, self.res_type)
+        self._fed(n)
+
+    def _fed(self, n):
+        self.live.fed(n, last=self._plan.fed(n))
+
+    def _wire_due(self):
+        """-> `LiveWirePlan.wire_due` of the chunks decoded so far; with the last chunk the valid input samples become
+        256 T, as `service_pcm16` counts them (a device fill)."""
+        w = self._plan.wire_due(self.live.chunks)
+        if w is None:
+            return None
+        self.live.check_handle()
+        if w[4]:
+            with torch.cuda.device(self.pcm.device):
+                self._valid_in.fill_(min(256 * self.live.frames, w[1]))
+        return w
+
+    def _wire_chunk(self, k):
+        """Fills the `_capi.MbvPcmChunk` `k` with the wire step due now; -> (final, pieces), or None."""
+        w = self._wire_due()
+        if w is None:
+            return None
+        in_avail, in_total, out_first, out_count, final, pieces = w
+        k.wave, k.in_total, k.valid_samples = self.live.o.data_ptr(), in_total, self._valid_in.data_ptr()
+        k.in_avail, k.out_first, k.out_count = in_avail, out_first, out_count
+        k.peak = self._peak_in.data_ptr() if self._peak_in is not None else None
+        k.pcm, k.pcm_capacity = self.pcm.data_ptr(), self._plan.pcm_capacity
+        k.running_peak = self.peak.data_ptr()
+        k.out_samples = self.valid_samples.data_ptr() if final else None
+        return final, pieces
+
+    def _wired(self, final, pieces):
+        self._pieces.extend(pieces)
+        self._plan.wired(len(self.live.chunks), pieces[-1][1], final)
+
+    def _wire(self):
+        w = self._wire_due()
+        if w is None:
+            return
+        in_avail, in_total, out_first, out_count, final, pieces = w
+        self._net.resample_pcm16_range(self.live.o[:, 0, :in_total], self.model_sr, self.rate, in_avail, out_first,
+                                       out_count, self.pcm, valid_samples=self._valid_in, peak=self._peak_in,
+                                       running_peak=self.peak, out_samples=self.valid_samples if final else None,
+                                       res_type=self.res_type)
+        self._wired(final, pieces)
+
+    def poll(self):
+        """-> [(first_out_sample, int16 view of pcm[0, a:b]), ...]: every piece not handed out yet, one per decoded
+        chunk (an empty piece is possible while the chunk is shorter than the filter's lag)."""
+        self._feed()
+        self.live.poll()
+        self._wire()
+        out = [(a, self.pcm[0, a:b]) for a, b in self._pieces[self._handed:]]
+        self._handed = len(self._pieces)
+        return out
+
+
+def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
+                       dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
+                       chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+    """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32) while the recording arrives, int16
+    out at `rate`; -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
+    `LiveStream` it opens, [1, inter, frames of ceil(max_samples * model_sr / in_sr)].  `peak` as `stream_pcm16` takes
+    it.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
+    `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`."""
+    return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
+                    peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
+                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames)
+
+
 class PcmPool:
     """The wire output of many `DecodeStream`s of one model: `step()` steps the wrapped `stream.StreamPool` (one
     `mbv_decode_chunks` call) and then turns what has become final on ALL pooled streams into int16 in ONE
@@ -257,12 +601,13 @@ class PcmPool:
         self._net, self.pool = net, pool
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         self.followers = []
+        self.lives = []                           # the `LiveWire`s added with add_live
         self._packed = None                       # int16 device, the call's pieces back to back (host=True)
         self._host = self._host_np = None         # its pinned host copy, and that as a NumPy array
         self._event = None
 
     def __len__(self):
-        return len(self.followers)
+        return len(self.followers) + len(self.lives)
 
     def follower(self, st):
         for f in self.followers:
@@ -289,42 +634,92 @@ class PcmPool:
             raise ValueError("admit: one peak per request expected (%d), got %d" % (len(reqs), len(peaks)))
         return [self.add(st, peak=p) for st, p in zip(self.pool.admit(reqs), peaks)]
 
+    def add_live(self, lw):
+        """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
+        feeds, steps and wires it along with the others; -> `lw`."""
+        if not isinstance(lw, LiveWire):
+            raise TypeError("add_live takes a wire.LiveWire (wire.convert_live_pcm16)")
+        if (lw.model_sr, lw.rate) != (self.model_sr, self.rate):
+            raise ValueError("the live wire runs %d -> %d Hz, the pool %d -> %d Hz"
+                             % (lw.model_sr, lw.rate, self.model_sr, self.rate))
+        if lw.res_type != self.res_type:
+            raise ValueError("the live wire resamples with %r, the pool with %r" % (lw.res_type, self.res_type))
+        self.pool.add(lw.live)                    # (refuses another model, another device)
+        if not any(lw is m for m in self.lives):
+            self.lives.append(lw)
+        return lw
+
+    def _feed_lives(self, lives):
+        """The input ranges due on all live members in one `mbv_resample_ranges` launch (one per raw rate among them)."""
+        by_sr = {}
+        for lw in lives:
+            row = _capi.MbvResampleRange()
+            n = lw._feed_row(row)
+            if n is not None:
+                by_sr.setdefault(lw.in_sr, []).append((lw, row, n))
+        for in_sr, todo in by_sr.items():
+            rows = (_capi.MbvResampleRange * len(todo))(*[row for _, row, _ in todo])
+            if any(n for _, _, n in todo):
+                self._net.resample_ranges(rows, in_sr, self.model_sr, self.res_type)
+            for lw, _, n in todo:
+                lw._fed(n)
+
     def step(self, streams=None, host=False):
         """-> [(st, first_out_sample, piece), ...]: one entry per stream whose decoded frontier made outputs final
-        (an empty piece is possible, as for `PcmStream`).  `piece` is the 1-D view `follower.pcm[0, a:b]` on the
-        device, ordered on the current stream; with host=True it is a NumPy int16 view of ONE pinned buffer that
-        one copy and one event wait filled, valid until the next `step(host=True)`."""
+        (an empty piece is possible, as for `PcmStream`); for a live member `st` is its `LiveWire`, one entry per
+        decoded chunk.  `piece` is the 1-D view `follower.pcm[0, a:b]` on the device, ordered on the current stream;
+        with host=True it is a NumPy int16 view of ONE pinned buffer that one copy and one event wait filled, valid
+        until the next `step(host=True)`.  Live members first resample what has arrived in ONE `mbv_resample_ranges`
+        launch; `streams` may name them by their `LiveWire`."""
         net = self._net
         if streams is None:
-            members = list(self.followers)
+            members, lives = list(self.followers), list(self.lives)
         else:
-            members = []
+            members, lives = [], []
             for st in streams:
+                if isinstance(st, LiveWire):
+                    if not any(st is m for m in self.lives):
+                        raise ValueError("step(streams=...) names a live wire that is not in the pool")
+                    lives.append(st)
+                    continue
                 f = self.follower(st)
                 if f is None:
                     raise ValueError("step(streams=...) names a stream that is not in the pool")
                 members.append(f)
-        named = None if streams is None else [f._st for f in members if f._st._decoded < len(f._st.schedule)]
+        if lives:
+            self._feed_lives(lives)
+        named = None
+        if streams is not None:
+            named = [f._st for f in members if f._st._decoded < len(f._st.schedule)]
+            named += [lw.live for lw in lives if not lw.live.all_decoded]
         if named is None or named:
             self.pool.step(named)
         todo = [f for f in members if f._st._decoded > f._wired]
+        arr = (_capi.MbvPcmChunk * (len(todo) + len(lives)))()
+        rows = []                                 # (stream, its pcm, [(a, b), ...]) per table row
+        for k, f in zip(arr, todo):
+            st = f._st
+            if net._handle is not f._h:
+                raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
+            first, count = st.schedule[st._decoded - 1]
+            a, b = f._done, f._ready[st._decoded - 1]
+            k.wave, k.in_total = st.o.data_ptr(), st.o.shape[-1]
+            k.valid_samples = f._valid_in.data_ptr() if f._valid_in is not None else None
+            k.in_avail, k.out_first, k.out_count = st.spf * (first + count), a, b - a
+            k.peak = f._peak_in.data_ptr() if f._peak_in is not None else None
+            k.pcm, k.pcm_capacity = f.pcm.data_ptr(), f.out_stride
+            k.running_peak = f.peak.data_ptr()
+            k.out_samples = f.valid_samples.data_ptr() if f._wired == 0 else None
+            rows.append((st, f.pcm, [(a, b)]))
+        live_done = []
+        for lw in lives:
+            w = lw._wire_chunk(arr[len(rows)])
+            if w is not None:
+                rows.append((lw, lw.pcm, w[1]))
+                live_done.append((lw, w))
         out = []
-        if todo:
-            arr = (_capi.MbvPcmChunk * len(todo))()
-            for k, f in zip(arr, todo):
-                st = f._st
-                if net._handle is not f._h:
-                    raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
-                first, count = st.schedule[st._decoded - 1]
-                a, b = f._done, f._ready[st._decoded - 1]
-                k.wave, k.in_total = st.o.data_ptr(), st.o.shape[-1]
-                k.valid_samples = f._valid_in.data_ptr() if f._valid_in is not None else None
-                k.in_avail, k.out_first, k.out_count = st.spf * (first + count), a, b - a
-                k.peak = f._peak_in.data_ptr() if f._peak_in is not None else None
-                k.pcm, k.pcm_capacity = f.pcm.data_ptr(), f.out_stride
-                k.running_peak = f.peak.data_ptr()
-                k.out_samples = f.valid_samples.data_ptr() if f._wired == 0 else None
-                out.append((st, a, b))
+        if rows:
+            arr = (_capi.MbvPcmChunk * len(rows))(*arr[:len(rows)])
             dev = net._device()
             packed = None
             if host:
@@ -339,16 +734,22 @@ class PcmPool:
             net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type)
             for f in todo:
                 f._done, f._wired = f._ready[f._st._decoded - 1], f._st._decoded
+            for lw, w in live_done:
+                lw._wired(*w)
             if host:
                 if total:
                     with torch.cuda.device(dev):
                         self._host[:total].copy_(packed[:total], non_blocking=True)
                         self._event.record(torch.cuda.current_stream(dev))
                         self._event.synchronize()
-                out = [(st, a, self._host_np[o:o + b - a]) for (st, a, b), o in zip(out, offs)]
+                for (st, _, pieces), o in zip(rows, offs):
+                    first = pieces[0][0]
+                    out += [(st, a, self._host_np[o + a - first:o + b - first]) for a, b in pieces]
             else:
-                out = [(st, a, f.pcm[0, a:b]) for (st, a, b), f in zip(out, todo)]
+                for st, pcm, pieces in rows:
+                    out += [(st, a, pcm[0, a:b]) for a, b in pieces]
         self.followers = [f for f in self.followers if f._wired < len(f._st.schedule)]
+        self.lives = [lw for lw in self.lives if not lw._plan.wire_done]
         return out
 
 

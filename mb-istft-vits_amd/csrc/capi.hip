@@ -701,7 +701,9 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
       for (int ci = 0; ci < half; ++ci) cmap[ci] = flipped ? half - 1 - ci : ci;
       F.pre = P.conv(w, H, half, 1, rows, cmap, &P.t(s + "pre.bias").data, nullptr);
     }
-    if (wn_fused_supported(H, kFlowK)) {
+    // (only where the x0' window fits the kernel's staging loop and `post` is folded too, see run_coupling: otherwise
+    // in16f0.M stays 0 and run_coupling launches F.pre itself)
+    if (wn_prefold_fits(H, I) && wn_postfold_fits(H, I)) {
       // r03: `pre` folded into the first fused WN layer.  h = (W_pre x0 + b_pre) mask = W_pre' x0' with
       // x0' = [x0 ; mask ; 0 ..] (Cin' = half + 1 channels padded to a multiple of 8) and W_pre' = [W_pre | b_pre | 0 ..]
       // (input channels in the physical order of the half, the Flip folded as in F.pre).  The gate conv of layer 0
@@ -767,8 +769,9 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
       // layers' gated tiles: m = sum_l (W_post W_rs_l[skip rows]) acts_l + (W_post sum_l b_rs_l[skip] + b_post), so
       // layer l's res/skip conv gets `half` skip rows (W_post W_rs_l[skip rows], composed in fp64) instead of H,
       // `skip` accumulates m itself and the last layer applies the coupling (WnLayerArgs::x1).  Row r of m is the
-      // physical channel r of the half being updated (the Flip folded as in F.post above).
-      if (wn_fused_supported(H, kFlowK)) {
+      // physical channel r of the half being updated (the Flip folded as in F.post above).  Only where H + half rows
+      // fit the kernel's row tiles: otherwise rspf[0].M stays 0 and run_coupling launches F.post (EPI_COUPLE) itself.
+      if (wn_postfold_fits(H, I)) {
         const std::vector<float>& bpost = P.t(s + "post.bias").data;
         for (int l = 0; l < kFlowLayers; ++l) {
           const std::string q = s + "enc.res_skip_layers." + std::to_string(l);
@@ -1721,14 +1724,15 @@ int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const
 }
 
 
-// scratch of a WN stack: hbuf / acts / skip [B, H, T], gc [B, 2 H layers], ustart wn_units_ints(B, T)
+// scratch of a WN stack: hbuf / acts [B, H, T], skip [B, max(H, I / 2), T], gc [B, 2 H layers], ustart wn_units_ints(B, T)
 struct FlowBufs { float *hbuf, *acts, *skip, *gc; int* ustart; };
 FlowBufs carve_flow(Bump& sc, const mbv_config& c, int B, int T, int layers) {
   const size_t BTH = (size_t)B * T * c.hidden_channels;
   FlowBufs p{};
   p.hbuf = sc.take<float>(BTH);
   p.acts = sc.take<float>(BTH);
-  p.skip = sc.take<float>(BTH);
+  // (with `post` folded, `skip` holds m: I / 2 channel rows, which is more than H where inter_channels > 2 hidden_channels)
+  p.skip = sc.take<float>((size_t)B * T * std::max(c.hidden_channels, c.inter_channels / 2));
   p.gc = sc.take<float>((size_t)B * 2 * c.hidden_channels * layers);
   p.ustart = sc.take<int>(wn_units_ints(B, T));
   return p;
@@ -1823,8 +1827,9 @@ bool wn_takes_fused(const mbv_model* m, const PConv* in_l, const PConv* in16_l, 
   const bool flipped = (f % 2) == 1;
   float* x0 = flipped ? z + (size_t)half * T : z;
   float* x1 = flipped ? z : z + (size_t)half * T;
-  const bool fold_post = F.rspf[0].M && wn_takes_fused(m, F.in, F.in16, B, T);
-  const bool fold_pre = fold_post && F.in16f0.M && F.pref.M && wn_fused_fits(B, I, T);   // (x0 is addressed through a whole-tensor view of z)
+  // (the folded layers address x0 and x1 through whole-tensor views of z with 32-bit offsets, like h and skip)
+  const bool fold_post = F.rspf[0].M && wn_takes_fused(m, F.in, F.in16, B, T) && wn_fused_fits(B, I, T);
+  const bool fold_pre = fold_post && F.in16f0.M && F.pref.M;
   if (!fold_pre) {
     ConvArgs a = conv_args(m, F.pre, x0, bsI, T, p.hbuf, bsH, T, B);
     a.out_lens = lens;

@@ -167,6 +167,9 @@ struct WnLayerArgs {
 };
 bool wn_fused_supported(int H, int K);
 bool wn_fused_fits(int B, int H, int T);      // h / skip small enough for the kernel's 32-bit offsets
+// may a coupling layer's `pre` / `post` be folded into its fused WN layers (the kernel's input window / row tiles)
+bool wn_prefold_fits(int H, int I);
+bool wn_postfold_fits(int H, int I);
 // `ustart` points at wn_units_ints(B, T) ints: [B + 1] prefix sums, then the half-unit -> utterance map
 size_t wn_units_ints(int B, int T);
 void launch_wn_units(const int* lens, int B, int T, int* ustart, int* hmap, hipStream_t s);

@@ -30,6 +30,7 @@
 // other's prologue / gating / epilogue.
 #include "kernels.h"
 #include <cstdio>
+#include <cstdlib>
 
 namespace mbv {
 
@@ -46,6 +47,13 @@ constexpr int kXS = 32;               // its column stride in the LDS image: the
                                       // contiguous wave would (a stride of 20 is a 2-way ds_read_b128 conflict)
 constexpr int kXL = 2 * kXS;          // columns per (group, parity) row of the LDS image
 constexpr int kWnGrid = 512;          // workgroups of a launch: two resident per CU
+// NRT = row tiles per wave of wn_layer_kernel<NRT>: ceil(2H / 32 / 4), and the kernel is built for 2 and 3 only
+constexpr int wn_nrt(int H) { return (2 * H / 32 + 3) / 4 <= 2 ? 2 : 3; }
+// window items (16 bytes) a thread stages per tile: 256 threads x NXI items hold the [Gi][2][kXL] image, so a
+// launch takes at most 256 NXI / (2 kXL) = 2 NXI input channel groups (16 at NRT = 2, 24 at NRT = 3).  G = H / 8
+// <= 8 NRT always fits; the x0' window of a folded `pre` has Gi = ceil((I / 2 + 1) / 8) groups, whatever H is
+// (wn_prefold_fits)
+constexpr int wn_nxi(int nrt) { return nrt == 3 ? 12 : 8; }
 // tanh(x) * sigmoid(y) on the hardware transcendentals (v_exp_f32 / v_rcp_f32, 1 ulp each):
 //   sigmoid(y) = 1 / (1 + 2^(-y log2 e)),  tanh(x) = 1 - 2 / (1 + 2^(2 x log2 e))
 // absolute error ~1e-7 (the libm forms cost ~100 instructions per gated value; 24 values per lane and tile)
@@ -444,7 +452,7 @@ __global__ __launch_bounds__(256, 2) void wn_layer_kernel(const WnLayerArgs a) {
     // ---- input windows: all H channels x 2 x 20 frames, masked, k-interleaved.  Every load of the
     // tile's prologue (ring, windows, bias) is issued before the first wait: one memory latency
     // instead of one per staging pass.
-    constexpr int NXI = NRT == 3 ? 12 : 8;     // window items per thread (G * 2 * kXL / 256, G <= 8 NRT)
+    constexpr int NXI = wn_nxi(NRT);           // window items per thread: Gi * 2 * kXL <= 256 NXI (see wn_nxi)
     f32x4 xw[NXI];
 #pragma unroll
     for (int i = 0; i < NXI; ++i) {
@@ -493,9 +501,28 @@ bool wn_fused_supported(int H, int K) {
   return K == kK && H % 32 == 0 && H >= 32 && H <= 192;      // <= 3 row tiles per wave (4 spill)
 }
 
+// What do_finalize asks before it folds `pre` / `post` of a coupling layer into the fused WN layers (capi.hip).
+// `pre`: layer 0 stages x0' = [x0 ; mask] (I / 2 + 1 channels in groups of 8) where the other layers stage h, and
+// the staging loop holds 256 NXI items: the groups beyond that would never reach LDS — the last one is the mask /
+// bias channel — and the gate GEMM would read what an earlier tile left there.
+bool wn_prefold_fits(int H, int I) {
+  const int Gi = (I / 2 + 1 + 7) / 8;
+  return wn_fused_supported(H, kK) && Gi * 2 * kXL <= 256 * wn_nxi(wn_nrt(H));
+}
+// `post`: the res/skip GEMM gets H residual + I / 2 coupling rows (the last layer I / 2), and a workgroup runs
+// 4 NRT row tiles of 32: rows beyond 128 NRT would not be computed at all.
+bool wn_postfold_fits(int H, int I) {
+  return wn_fused_supported(H, kK) && H + I / 2 <= 128 * wn_nrt(H);
+}
+
 void launch_wn_layer(const WnLayerArgs& a, hipStream_t s) {
   const int G = a.H / 8, Gi = a.Gi ? a.Gi : G;
-  const int nrt = (2 * a.H / 32 + 3) / 4;
+  const int nrt = wn_nrt(a.H);
+  if (Gi * 2 * kXL > 256 * wn_nxi(nrt) || a.Mr > 128 * nrt) {     // (do_finalize never packs such a layer)
+    fprintf(stderr, "launch_wn_layer: H = %d with Gi = %d input groups / Mr = %d rows is beyond the kernel's window "
+                    "(%d groups) or its row tiles (%d rows)\n", a.H, Gi, a.Mr, 2 * wn_nxi(nrt), 128 * nrt);
+    abort();
+  }
   const size_t lds_bytes = (size_t)(Gi * 2 * kXL + G * 2 * 32) * 16 + (size_t)128 * (nrt <= 2 ? 2 : 3) * 4;   // + the res / skip bias
   // at most two resident workgroups per CU (register / LDS budget); a workgroup walks units
   // blockIdx.x, blockIdx.x + grid, ...; the unit count itself lives on the device

@@ -397,7 +397,13 @@ def test_fused_wn_layer_kernel_against_cpu_loop(tmp_path):
     """`wn_layer_kernel` (wn_fused.hip) on its own against a plain CPU loop in float64
     (`scripts/wn_layer_check.hip` includes the kernel source and is compiled here with hipcc):
     ragged lengths, tiles that span two utterances, the last layer's 6-tile res/skip GEMM (idle tile
-    slots must not store into the next utterance), 64 / 96 / 160 / 192 channels."""
+    slots must not store into the next utterance), 64 / 96 / 160 / 192 channels.
+
+    This is ONE plain layer: `gcond` is null, `skip_accum` is 1, `Cs` is H, and `wpre` / `Gi` / `in_cb` (the first
+    layer of a coupling reading x0' = [x0 ; mask] through the composed weights), `x1` / `x1_bstride` / `couple_sign`
+    (the last layer applying the coupling through the res/skip conv with `post` folded in, Cs = I / 2) are never set.
+    Those arguments of `WnLayerArgs`, the Flip folded into the packing, both signs and the two-launch layer are reached
+    by test_gpu_wn_stack.py through `align`, `infer_z_only` and `voice_conversion`."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

@@ -1686,7 +1686,7 @@ size_t pooled_scratch_bytes(const mbv_config& c, const mbv_chunk* chunks, const 
 
 // The chunks of one call, one decoder run per RaggedRun of their utterances' lengths (the classes of the ragged
 // decode): the run's rows are the chunks' windows gathered into scratch, decoded as ragged rows of their window
-// lengths, planned as their utterances plan.  The tables travel as kernel arguments (launch_pool_rows).
+// lengths, planned as their utterances plan.  The tables travel as kernel arguments (upload_rows).
 int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const std::vector<RaggedRun>& runs, int Lc, int Rc,
                        hipStream_t s, Bump& sc) {
   const mbv_config& c = m->cfg;
@@ -1699,17 +1699,12 @@ int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const
     sc.off = base;
     PoolRow* rows = sc.take<PoolRow>(n);
     int* lens = sc.take<int>(3 * n);
-    for (size_t f = 0; f < n; f += kPoolChunk) {
-      PoolRowsArg r{};
-      const int nn = (int)(n - f < (size_t)kPoolChunk ? n - f : (size_t)kPoolChunk);
-      for (int i = 0; i < nn; ++i) {
-        const mbv_chunk& k = chunks[run.rows[f + i]];
-        const ChunkWindow w = chunk_window(k, Lc, Rc);
-        r.row[i] = PoolRow{k.z, k.z_stride, gin ? k.g : nullptr, k.o + (int64_t)256 * k.first, w.wa, w.len,
-                           64 * w.keep_first, 64 * (w.keep_first + k.count)};
-      }
-      launch_pool_rows(r, nn, (int)f, us, rows, lens, (int)n, s);
-    }
+    upload_rows<kPoolChunk>(n, rows, s, [&](size_t i) {
+      const mbv_chunk& k = chunks[run.rows[i]];
+      const ChunkWindow w = chunk_window(k, Lc, Rc);
+      return PoolRow{k.z, k.z_stride, gin ? k.g : nullptr, k.o + (int64_t)256 * k.first, w.wa, w.len,
+                     64 * w.keep_first, 64 * (w.keep_first + k.count)};
+    }, PoolRowLens{lens, (int)n, us});
     float* zc = sc.take<float>(n * I * Tw);
     float* gc = gin ? sc.take<float>(n * gin) : nullptr;
     launch_gather_windows(rows, (int)n, I, Tw, zc, gin, gc, s);
@@ -2259,18 +2254,12 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   int* const bad = m->bad32;
   float* const x = te.x;
   bool any_given = false;
-  if (rows_host) {
-    for (int f = 0; f < B; f += kAdmitChunk) {
-      AdmitEncRowsArg r{};
-      const int nn = B - f < kAdmitChunk ? B - f : kAdmitChunk;
-      for (int i = 0; i < nn; ++i) {
-        const mbv_enc_row& k = rows_host[f + i];
-        r.row[i] = AdmitEncRow{k.length_scale, k.noise_scale_w, k.noise_w, k.durations, k.durations_dtype, k.t_text};
-        any_given = any_given || k.durations;
-      }
-      launch_admit_enc_rows(r, nn, f, rows, (hipStream_t)stream);
-    }
-  }
+  if (rows_host)
+    upload_rows<kAdmitChunk>(B, rows, (hipStream_t)stream, [&](size_t i) {
+      const mbv_enc_row& k = rows_host[i];
+      any_given = any_given || k.durations;
+      return AdmitEncRow{k.length_scale, k.noise_scale_w, k.noise_w, k.durations, k.durations_dtype, k.t_text};
+    });
   m->stages.clear();
 
   ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
@@ -2535,13 +2524,6 @@ int admit_plan(const mbv_config& c, int splitk, int n, const int32_t* t_text, in
   if (splitk) return plan_runs(n, t_text, no_signature, fits, run_of_request);
   return plan_runs(n, t_text, [&](int B, int T, std::vector<char>* sig) { front_signature(c, 0, B, T, sig); }, fits, run_of_request);
 }
-
-// rows [f, f + nn) of a host AdmitSynRow table, by value, into dst (nn <= kAdmitChunk)
-void upload_syn_rows(const std::vector<AdmitSynRow>& host, int f, int nn, AdmitSynRow* dst, hipStream_t s) {
-  AdmitSynRowsArg r{};
-  std::copy(host.begin() + f, host.begin() + f + nn, r.row);
-  launch_admit_syn_rows(r, nn, f, dst, s);
-}
 }  // namespace
 
 extern "C" {
@@ -2641,7 +2623,7 @@ int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* row
   // the run becomes the handle's "last encode", as if mbv_encode had just made it
   static_cast<EncState&>(*m) = sl.enc;
   m->encoded = true;
-  for (int f = 0; f < B; f += kAdmitChunk) upload_syn_rows(rows_h, f, std::min(B - f, kAdmitChunk), rows, s);
+  upload_rows<kAdmitChunk>(B, rows, s, [&](size_t i) { return rows_h[i]; });
   launch_expand_rows(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, rows, z, B, I, T, Tp, s);
   if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
   launch_scatter_z_rows(z, m->ylen32, rows, B, I, Tp, max_keep, s);
@@ -3146,37 +3128,33 @@ int mbv_istft_finalize(mbv_model* m, const float* spec, const float* phase, int 
   return 0;
 }
 
-int mbv_pcm16(mbv_model* m, const float* wave, const int64_t* y_lengths, int B, int64_t stride,
-              int auto_normalize, int16_t* pcm, void* stream) {
+namespace {
+// mbv_pcm16 (spf 256: lengths in z-frames) and mbv_pcm16_samples (spf 1: lengths in samples)
+int pcm16(mbv_model* m, const char* who, const float* wave, const int64_t* lens, int B, int64_t stride, int spf,
+          int auto_normalize, int16_t* pcm, void* stream) {
   if (!m) return 1;
-  if (!wave || !pcm || B <= 0 || stride <= 0) return m->fail("mbv_pcm16: bad arguments");
+  if (!wave || !pcm || B <= 0 || stride <= 0) return m->fail("%s: bad arguments", who);
+  if (spf == 1 && B > 65535) return m->fail("%s: more than 65535 rows", who);
   DEVICE_GUARD(m);
   if (m->peak_cap < B) {
     if (m->peak_buf) HIPCHK(m, hipFree(m->peak_buf));
     HIPCHK(m, hipMalloc((void**)&m->peak_buf, (size_t)B * sizeof(unsigned)));
     m->peak_cap = B;
   }
-  launch_pcm16(wave, y_lengths, B, stride, 256, auto_normalize, m->peak_buf, reinterpret_cast<short*>(pcm),
-               (hipStream_t)stream);
+  launch_pcm16(wave, lens, B, stride, spf, auto_normalize, m->peak_buf, reinterpret_cast<short*>(pcm), (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
+}
+}  // namespace
+
+int mbv_pcm16(mbv_model* m, const float* wave, const int64_t* y_lengths, int B, int64_t stride,
+              int auto_normalize, int16_t* pcm, void* stream) {
+  return pcm16(m, "mbv_pcm16", wave, y_lengths, B, stride, 256, auto_normalize, pcm, stream);
 }
 
 int mbv_pcm16_samples(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t stride,
                       int auto_normalize, int16_t* pcm, void* stream) {
-  if (!m) return 1;
-  if (!wave || !pcm || B <= 0 || stride <= 0) return m->fail("mbv_pcm16_samples: bad arguments");
-  if (B > 65535) return m->fail("mbv_pcm16_samples: more than 65535 rows");
-  DEVICE_GUARD(m);
-  if (m->peak_cap < B) {
-    if (m->peak_buf) HIPCHK(m, hipFree(m->peak_buf));
-    HIPCHK(m, hipMalloc((void**)&m->peak_buf, (size_t)B * sizeof(unsigned)));
-    m->peak_cap = B;
-  }
-  launch_pcm16(wave, valid_samples, B, stride, 1, auto_normalize, m->peak_buf, reinterpret_cast<short*>(pcm),
-               (hipStream_t)stream);
-  HIPCHK(m, hipGetLastError());
-  return 0;
+  return pcm16(m, "mbv_pcm16_samples", wave, valid_samples, B, stride, 1, auto_normalize, pcm, stream);
 }
 
 int mbv_resample_bank(int orig_sr, int target_sr, int filter, float* dst, int64_t capacity, int32_t* phases,
@@ -3195,12 +3173,31 @@ int mbv_resample_bank(int orig_sr, int target_sr, int filter, float* dst, int64_
   return 0;
 }
 
+}  // extern "C"
+
 namespace {
-// the handle's device bank of a rate pair and filter; the first call builds it on the host and uploads it once
-// (synchronous copy).  0 on success, else m->fail(...) has been called.
-int resample_bank_of(mbv_model* m, const char* who, int orig_sr, int target_sr, int filter, int L, int M,
-                     const mbv_model::ResampleBank** out) {
-  const std::array<int, 3> key{L, M, filter};
+// The rate pair and filter of a wire entry: validated and reduced to L / M.  Unequal rates (fir) also get the geometry
+// and, with a handle, its device bank of the pair: the first call builds it on the host and uploads it once
+// (synchronous copy).  Equal rates get neither (the sample itself), unless equal_is_fir asks for the L = M = 1 bank.
+// Returns 0, or 1 with the reason in m->err (g_create_error without a handle).
+struct RatePair {
+  int L = 0, M = 0;
+  bool fir = false;
+  ResampleGeom g{};
+  const float* bank = nullptr;
+};
+int rate_pair(mbv_model* m, const char* who, int orig_sr, int target_sr, int filter, RatePair* rp, bool equal_is_fir = false) {
+  auto fail = [&](const std::string& why) { (m ? m->err : g_create_error) = std::string(who) + ": " + why; return 1; };
+  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
+    return fail("unknown filter " + std::to_string(filter) + " (0 = kaiser_best, 1 = kaiser_fast)");
+  if (resample_reduce(orig_sr, target_sr, &rp->L, &rp->M)) return fail("sample rates must be positive");
+  rp->fir = equal_is_fir || orig_sr != target_sr;
+  if (!rp->fir) return 0;
+  if (!m) {
+    const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &rp->g);
+    return why ? fail(why) : 0;
+  }
+  const std::array<int, 3> key{rp->L, rp->M, filter};
   auto it = m->resample_banks.find(key);
   if (it == m->resample_banks.end()) {
     mbv_model::ResampleBank rb;
@@ -3214,10 +3211,41 @@ int resample_bank_of(mbv_model* m, const char* who, int orig_sr, int target_sr, 
     }
     it = m->resample_banks.emplace(key, rb).first;
   }
-  *out = &it->second;
+  rp->g = it->second.g;
+  rp->bank = it->second.d;
+  return 0;
+}
+
+// Two rows of a pooled call must not write one sample.  Row i writes bytes(i) bytes from address lo(i); empty rows
+// write nothing.  Returns the first pair that shares a byte, in address order, as (lower index, higher index), or
+// (-1, -1).
+template <typename Lo, typename Bytes>
+std::pair<int, int> ranges_overlap(int n, Lo lo, Bytes bytes) {
+  std::vector<int> order;
+  for (int i = 0; i < n; ++i)
+    if (bytes(i) > 0) order.push_back(i);
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return lo(a) < lo(b); });
+  for (size_t j = 1; j < order.size(); ++j) {
+    const int a = order[j - 1], b = order[j];
+    if (lo(a) + bytes(a) > lo(b)) return {std::min(a, b), std::max(a, b)};
+  }
+  return {-1, -1};
+}
+
+// The grid's y limit: the table rows of a pooled call in slices of 65535, launch(first, rows, longest count of the slice)
+template <typename Count, typename Launch>
+int grid_y_slices(const std::vector<int>& live, Count count, Launch launch) {
+  for (size_t f = 0; f < live.size(); f += 65535) {
+    const size_t nn = std::min<size_t>(live.size() - f, 65535);
+    int64_t max_count = 0;
+    for (size_t i = 0; i < nn; ++i) max_count = std::max<int64_t>(max_count, count(live[f + i]));
+    if (int rc = launch(f, (int)nn, max_count)) return rc;
+  }
   return 0;
 }
 }  // namespace
+
+extern "C" {
 
 int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
                  int orig_sr, int target_sr, int filter, float* out, int64_t out_stride, int64_t* out_samples,
@@ -3226,30 +3254,21 @@ int mbv_resample(mbv_model* m, const float* wave, const int64_t* valid_samples, 
   if (!wave || !out || B <= 0 || in_stride <= 0 || out_stride <= 0) return m->fail("mbv_resample: bad arguments");
   if (B > 65535) return m->fail("mbv_resample: more than 65535 rows");
   if ((out_stride + kResampleTile - 1) / kResampleTile > 0x7fffffff) return m->fail("mbv_resample: out_stride too large");
-  int L = 0, M = 0;
-  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("mbv_resample: sample rates must be positive");
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
-    return m->fail("mbv_resample: unknown filter %d", filter);
-  if ((double)out_stride * M >= 0x1p62) return m->fail("mbv_resample: out_stride * M overflows the 64-bit time index");
   DEVICE_GUARD(m);
-  const mbv_model::ResampleBank* rb = nullptr;
-  if (resample_bank_of(m, "mbv_resample", orig_sr, target_sr, filter, L, M, &rb)) return 1;
-  launch_resample(wave, valid_samples, B, in_stride, rb->d, rb->g, out, out_stride, out_samples, (hipStream_t)stream);
+  RatePair rp;
+  if (rate_pair(m, "mbv_resample", orig_sr, target_sr, filter, &rp, true)) return 1;
+  if ((double)out_stride * rp.M >= 0x1p62) return m->fail("mbv_resample: out_stride * M overflows the 64-bit time index");
+  launch_resample(wave, valid_samples, B, in_stride, rp.bank, rp.g, out, out_stride, out_samples, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 int64_t mbv_resample_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total) {
   if (in_total < 0) { g_create_error = "mbv_resample_ready: in_total must be >= 0"; return -1; }
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
-    g_create_error = "mbv_resample_ready: unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
-    return -1;
-  }
-  if (orig_sr > 0 && orig_sr == target_sr) return in_avail < 0 ? 0 : (in_avail < in_total ? in_avail : in_total);
-  ResampleGeom g{};
-  const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
-  if (why) { g_create_error = std::string("mbv_resample_ready: ") + why; return -1; }
-  return resample_ready(g, in_avail, in_total);
+  RatePair rp;
+  if (rate_pair(nullptr, "mbv_resample_ready", orig_sr, target_sr, filter, &rp)) return -1;
+  if (!rp.fir) return in_avail < 0 ? 0 : (in_avail < in_total ? in_avail : in_total);
+  return resample_ready(rp.g, in_avail, in_total);
 }
 
 int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
@@ -3262,40 +3281,32 @@ int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* val
   if (B > 65535) return m->fail("%s: more than 65535 rows", who);
   if (in_avail < 0 || out_first < 0 || out_count < 0)
     return m->fail("%s: in_avail, out_first and out_count must be >= 0", who);
-  int L = 0, M = 0;
-  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
-    return m->fail("%s: unknown filter %d", who, filter);
+  DEVICE_GUARD(m);
+  RatePair rp;
+  if (rate_pair(m, who, orig_sr, target_sr, filter, &rp)) return 1;
   if (out_first > pcm_stride || out_count > pcm_stride - out_first)
     return m->fail("%s: outputs [%lld, %lld) lie outside the row of pcm_stride %lld", who, (long long)out_first,
                    (long long)(out_first + out_count), (long long)pcm_stride);
-  if ((double)pcm_stride * M >= 0x1p62) return m->fail("%s: pcm_stride * M overflows the 64-bit time index", who);
-  DEVICE_GUARD(m);
-  const bool fir = orig_sr != target_sr;
-  const mbv_model::ResampleBank* rb = nullptr;
-  int64_t ready = in_avail < in_stride ? in_avail : in_stride;
-  if (fir) {
-    if (resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
-    ready = resample_ready(rb->g, in_avail, in_stride);
-  }
+  if ((double)pcm_stride * rp.M >= 0x1p62) return m->fail("%s: pcm_stride * M overflows the 64-bit time index", who);
+  const int64_t ready = rp.fir ? resample_ready(rp.g, in_avail, in_stride) : (in_avail < in_stride ? in_avail : in_stride);
   if (out_first + out_count > ready)
     return m->fail("%s: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final", who,
                    (long long)(out_first + out_count), (long long)in_avail, (long long)in_stride, (long long)ready);
   if (out_count == 0 && !out_samples) return 0;           // nothing to write
   ++m->wire_runs;
-  launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, fir ? rb->d : nullptr,
-                              fir ? rb->g : ResampleGeom{}, out_first, out_count, peak, reinterpret_cast<short*>(pcm),
-                              pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, (hipStream_t)stream);
+  launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
+                              reinterpret_cast<short*>(pcm), pcm_stride, reinterpret_cast<unsigned*>(running_peak),
+                              out_samples, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 namespace {
-// The checks mbv_resample_pcm16_range makes on its row, for every chunk of a pooled call (integer fields only);
-// g null = equal rates.  Fills packed_first (may be null) with the running sum of the out_count and returns the
-// packed total, or -1 with *err naming the offending chunk.
-int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const ResampleGeom* g, int M,
-                         int64_t* packed_first, std::string* err) {
+// The checks mbv_resample_pcm16_range makes on its row, for every chunk of a pooled call (integer fields only).
+// Fills packed_first (may be null) with the running sum of the out_count and returns the packed total, or -1 with
+// *err naming the offending chunk.
+int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const RatePair& rp, int64_t* packed_first,
+                         std::string* err) {
   char buf[512];
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
@@ -3303,7 +3314,7 @@ int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, co
     const char* why = nullptr;
     if (k.in_total <= 0 || k.pcm_capacity <= 0) why = "in_total and pcm_capacity must be > 0";
     else if (k.in_avail < 0 || k.out_first < 0 || k.out_count < 0) why = "in_avail, out_first and out_count must be >= 0";
-    else if ((double)k.pcm_capacity * M >= 0x1p62) why = "pcm_capacity * M overflows the 64-bit time index";
+    else if ((double)k.pcm_capacity * rp.M >= 0x1p62) why = "pcm_capacity * M overflows the 64-bit time index";
     if (why) {
       snprintf(buf, sizeof buf, "%s: chunk %d: %s", who, i, why);
       *err = buf;
@@ -3315,7 +3326,7 @@ int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, co
       *err = buf;
       return -1;
     }
-    const int64_t ready = g ? resample_ready(*g, k.in_avail, k.in_total) : (k.in_avail < k.in_total ? k.in_avail : k.in_total);
+    const int64_t ready = rp.fir ? resample_ready(rp.g, k.in_avail, k.in_total) : (k.in_avail < k.in_total ? k.in_avail : k.in_total);
     if (k.out_first + k.out_count > ready) {
       snprintf(buf, sizeof buf, "%s: chunk %d: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final",
                who, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.in_total, (long long)ready);
@@ -3333,20 +3344,10 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
                             int64_t* packed_first) {
   const char* who = "mbv_pcm_chunks_plan";
   if (n < 0 || (n > 0 && !chunks)) { g_create_error = std::string(who) + ": bad arguments"; return -1; }
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
-    g_create_error = std::string(who) + ": unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
-    return -1;
-  }
-  int L = 0, M = 0;
-  if (resample_reduce(orig_sr, target_sr, &L, &M)) { g_create_error = std::string(who) + ": sample rates must be positive"; return -1; }
-  ResampleGeom g{};
-  const bool fir = orig_sr != target_sr;
-  if (fir) {
-    const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
-    if (why) { g_create_error = std::string(who) + ": " + why; return -1; }
-  }
+  RatePair rp;
+  if (rate_pair(nullptr, who, orig_sr, target_sr, filter, &rp)) return -1;
   std::string err;
-  const int64_t total = pcm_chunks_check(who, chunks, n, fir ? &g : nullptr, M, packed_first, &err);
+  const int64_t total = pcm_chunks_check(who, chunks, n, rp, packed_first, &err);
   if (total < 0) g_create_error = err;
   return total;
 }
@@ -3356,33 +3357,21 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
   if (!m) return 1;
   const char* who = "mbv_resample_pcm16_chunks";
   if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
-  int L = 0, M = 0;
-  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
-    return m->fail("%s: unknown filter %d", who, filter);
   for (int i = 0; i < n; ++i)
     if (!chunks_host[i].wave || !chunks_host[i].pcm) return m->fail("%s: chunk %d: wave / pcm missing", who, i);
   DEVICE_GUARD(m);
-  const bool fir = orig_sr != target_sr;
-  const mbv_model::ResampleBank* rb = nullptr;
-  if (fir && resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
+  RatePair rp;
+  if (rate_pair(m, who, orig_sr, target_sr, filter, &rp)) return 1;
   std::string err;
   std::vector<int64_t> off(n > 0 ? n : 1);
-  const int64_t total = pcm_chunks_check(who, chunks_host, n, fir ? &rb->g : nullptr, M, off.data(), &err);
+  const int64_t total = pcm_chunks_check(who, chunks_host, n, rp, off.data(), &err);
   if (total < 0) return m->fail("%s", err.c_str());
   if (packed && packed_capacity < total)
     return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
-  // two chunks must not write one sample: the non-empty ranges in address order
-  std::vector<int> order;
-  for (int i = 0; i < n; ++i)
-    if (chunks_host[i].out_count > 0) order.push_back(i);
-  auto lo = [&](int i) { return (uintptr_t)(chunks_host[i].pcm + chunks_host[i].out_first); };
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return lo(a) < lo(b); });
-  for (size_t j = 1; j < order.size(); ++j) {
-    if (lo(order[j - 1]) + sizeof(int16_t) * (uintptr_t)chunks_host[order[j - 1]].out_count > lo(order[j]))
-      return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, order[j - 1] < order[j] ? order[j - 1] : order[j],
-                     order[j - 1] < order[j] ? order[j] : order[j - 1]);
-  }
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(chunks_host[i].pcm + chunks_host[i].out_first); },
+                                    [&](int i) { return sizeof(int16_t) * (uintptr_t)chunks_host[i].out_count; });
+  if (clash.first >= 0)
+    return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, clash.first, clash.second);
   // rows with something to write (an empty range still carries out_samples)
   std::vector<int> live;
   for (int i = 0; i < n; ++i)
@@ -3391,27 +3380,17 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
   if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(PcmPoolRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
   PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
-  for (size_t f = 0; f < live.size(); f += kPcmPoolChunk) {
-    PcmPoolRowsArg r{};
-    const int nn = (int)(live.size() - f < (size_t)kPcmPoolChunk ? live.size() - f : (size_t)kPcmPoolChunk);
-    for (int i = 0; i < nn; ++i) {
-      const int c = live[f + i];
-      const mbv_pcm_chunk& k = chunks_host[c];
-      r.row[i] = PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count,
-                            k.peak, reinterpret_cast<short*>(k.pcm), k.pcm_capacity,
-                            reinterpret_cast<unsigned*>(k.running_peak), k.out_samples, packed ? off[c] : (int64_t)-1};
-    }
-    launch_pcm_pool_rows(r, nn, (int)f, rows, s);
-  }
-  for (size_t f = 0; f < live.size(); f += 65535) {         // the grid's y limit
-    const size_t nn = live.size() - f < 65535 ? live.size() - f : 65535;
-    int64_t max_count = 0;
-    for (size_t i = 0; i < nn; ++i)
-      if (chunks_host[live[f + i]].out_count > max_count) max_count = chunks_host[live[f + i]].out_count;
+  upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_pcm_chunk& k = chunks_host[live[i]];
+    return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
+                      reinterpret_cast<short*>(k.pcm), k.pcm_capacity, reinterpret_cast<unsigned*>(k.running_peak),
+                      k.out_samples, packed ? off[live[i]] : (int64_t)-1};
+  });
+  grid_y_slices(live, [&](int i) { return chunks_host[i].out_count; }, [&](size_t f, int nn, int64_t max_count) {
     ++m->wire_runs;
-    launch_resample_pcm16_pool(rows + f, (int)nn, max_count, fir ? rb->d : nullptr, fir ? rb->g : ResampleGeom{},
-                               reinterpret_cast<short*>(packed), s);
-  }
+    launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, reinterpret_cast<short*>(packed), s);
+    return 0;
+  });
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3419,16 +3398,10 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
 int64_t mbv_wire_runs(mbv_model* m) { return m ? m->wire_runs : -1; }
 
 int64_t mbv_resample_ready_open(int orig_sr, int target_sr, int filter, int64_t in_avail) {
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST) {
-    g_create_error = "mbv_resample_ready_open: unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
-    return -1;
-  }
+  RatePair rp;
+  if (rate_pair(nullptr, "mbv_resample_ready_open", orig_sr, target_sr, filter, &rp)) return -1;
   if (in_avail < 0) in_avail = 0;
-  if (orig_sr > 0 && orig_sr == target_sr) return in_avail;
-  ResampleGeom g{};
-  const char* why = resample_bank(orig_sr, target_sr, filter, nullptr, &g);
-  if (why) { g_create_error = std::string("mbv_resample_ready_open: ") + why; return -1; }
-  return resample_ready_open(g, in_avail);
+  return rp.fir ? resample_ready_open(rp.g, in_avail) : in_avail;
 }
 
 int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n, int orig_sr, int target_sr,
@@ -3436,11 +3409,10 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
   if (!m) return 1;
   const char* who = "mbv_resample_ranges";
   if (n < 0 || (n > 0 && !rows_host)) return m->fail("%s: bad arguments", who);
-  int L = 0, M = 0;
-  if (resample_reduce(orig_sr, target_sr, &L, &M)) return m->fail("%s: sample rates must be positive", who);
-  if (filter != MBV_RESAMPLE_KAISER_BEST && filter != MBV_RESAMPLE_KAISER_FAST)
-    return m->fail("%s: unknown filter %d", who, filter);
-  if (orig_sr == target_sr)
+  DEVICE_GUARD(m);
+  RatePair rp;
+  if (rate_pair(m, who, orig_sr, target_sr, filter, &rp)) return 1;
+  if (!rp.fir)
     return m->fail("%s: equal rates (%d) take no kernel: the samples are the model's input as they are", who, orig_sr);
   for (int i = 0; i < n; ++i) {
     const mbv_resample_range& k = rows_host[i];
@@ -3455,21 +3427,18 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
     if (k.out_first > k.out_capacity || k.out_count > k.out_capacity - k.out_first)
       return m->fail("%s: row %d: outputs [%lld, %lld) lie outside the row of out_capacity %lld", who, i,
                      (long long)k.out_first, (long long)(k.out_first + k.out_count), (long long)k.out_capacity);
-    if ((double)k.out_capacity * M >= 0x1p62 || (double)k.in_avail * L >= 0x1p62)
+    if ((double)k.out_capacity * rp.M >= 0x1p62 || (double)k.in_avail * rp.L >= 0x1p62)
       return m->fail("%s: row %d: out_capacity * M or in_avail * L overflows the 64-bit time index", who, i);
   }
-  DEVICE_GUARD(m);
-  const mbv_model::ResampleBank* rb = nullptr;
-  if (resample_bank_of(m, who, orig_sr, target_sr, filter, L, M, &rb)) return 1;
   std::vector<int> live;
   for (int i = 0; i < n; ++i) {
     const mbv_resample_range& k = rows_host[i];
     int64_t ready;
     if (k.in_total >= 0) {
-      ready = (int64_t)std::ceil((double)k.in_total * rb->g.ratio);        // fix_length of the whole row, as mbv_resample
+      ready = (int64_t)std::ceil((double)k.in_total * rp.g.ratio);         // fix_length of the whole row, as mbv_resample
       if (ready > k.out_capacity) ready = k.out_capacity;
     } else {
-      ready = resample_ready_open(rb->g, k.in_avail);
+      ready = resample_ready_open(rp.g, k.in_avail);
     }
     if (k.out_first + k.out_count > ready)
       return m->fail("%s: row %d: outputs up to %lld asked for, but %lld input samples (%s) make only %lld final", who, i,
@@ -3478,39 +3447,24 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
     if (k.out_count > 0) live.push_back(i);
   }
   if (live.empty()) return 0;
-  {
-    // two rows must not write one sample: the non-empty ranges in address order (as mbv_resample_pcm16_chunks)
-    std::vector<int> order(live);
-    auto lo = [&](int i) { return (uintptr_t)(rows_host[i].out + rows_host[i].out_first); };
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return lo(a) < lo(b); });
-    for (size_t j = 1; j < order.size(); ++j) {
-      const int a = order[j - 1], b = order[j];
-      if (lo(a) + sizeof(float) * (uintptr_t)rows_host[a].out_count > lo(b))
-        return m->fail("%s: rows %d and %d write overlapping ranges of one out", who, a < b ? a : b, a < b ? b : a);
-    }
-  }
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(rows_host[i].out + rows_host[i].out_first); },
+                                    [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].out_count; });
+  if (clash.first >= 0)
+    return m->fail("%s: rows %d and %d write overlapping ranges of one out", who, clash.first, clash.second);
   if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(ResampleRangeRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
   ResampleRangeRow* rows = reinterpret_cast<ResampleRangeRow*>(m->scrB);
-  for (size_t f = 0; f < live.size(); f += kPcmPoolChunk) {
-    ResampleRangeRowsArg r{};
-    const int nn = (int)(live.size() - f < (size_t)kPcmPoolChunk ? live.size() - f : (size_t)kPcmPoolChunk);
-    for (int i = 0; i < nn; ++i) {
-      const mbv_resample_range& k = rows_host[live[f + i]];
-      r.row[i] = ResampleRangeRow{k.wave, k.wave_dtype, k.in_total >= 0 ? 1 : 0, k.in_avail, k.out_first,
-                                  k.out_first + k.out_count, k.out};
-    }
-    launch_resample_range_rows(r, nn, (int)f, rows, s);
-  }
-  for (size_t f = 0; f < live.size(); f += 65535) {         // the grid's y limit
-    const size_t nn = live.size() - f < 65535 ? live.size() - f : 65535;
-    int64_t max_count = 0;
-    for (size_t i = 0; i < nn; ++i)
-      if (rows_host[live[f + i]].out_count > max_count) max_count = rows_host[live[f + i]].out_count;
-    if ((max_count + kResampleTile - 1) / kResampleTile > 0x7fffffff) return m->fail("%s: a range too long for one grid", who);
-    ++m->input_runs;
-    launch_resample_ranges(rows + f, (int)nn, max_count, rb->d, rb->g, s);
-  }
+  upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_resample_range& k = rows_host[live[i]];
+    return ResampleRangeRow{k.wave, k.wave_dtype, k.in_total >= 0 ? 1 : 0, k.in_avail, k.out_first,
+                            k.out_first + k.out_count, k.out};
+  });
+  if (grid_y_slices(live, [&](int i) { return rows_host[i].out_count; }, [&](size_t f, int nn, int64_t max_count) {
+        if ((max_count + kResampleTile - 1) / kResampleTile > 0x7fffffff) return m->fail("%s: a range too long for one grid", who);
+        ++m->input_runs;
+        launch_resample_ranges(rows + f, nn, max_count, rp.bank, rp.g, s);
+        return 0;
+      })) return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3686,13 +3640,8 @@ int run_posterior_rows(mbv_model* m, const char* who, const std::vector<ConvertR
       })) return 1;
   m->stages.clear();
   m->stages["convert_ypad"] = StageRef{pb.ypad, (int64_t)(BT * m->encq.cin_pad)};
-  for (int f = 0; f < B; f += kAdmitChunk) {
-    const int nn = std::min(B - f, kAdmitChunk);
-    ConvertRowsArg cr{};
-    std::copy(crows_h.begin() + f, crows_h.begin() + f + nn, cr.row);
-    launch_convert_rows(cr, nn, f, crows, lens, sid_src, sid_tgt, s);
-    upload_syn_rows(srows_h, f, nn, srows, s);
-  }
+  upload_rows<kAdmitChunk>(B, crows, s, [&](size_t i) { return crows_h[i]; }, ConvertRowCols{lens, sid_src, sid_tgt});
+  upload_rows<kAdmitChunk>(B, srows, s, [&](size_t i) { return srows_h[i]; });
   ++m->converter_runs;
   launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
   launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s);

@@ -8,6 +8,34 @@
 
 namespace mbv {
 
+// ---------------------------------------------------------------- table upload
+// Every device table of the pooled entries (one Row per utterance, chunk or recording) goes up the same way: the rows
+// travel by value as kernel arguments, N per launch, no copy and no synchronisation.  upload_rows walks rows
+// [0, n): row i = fill(i) -> dst[i], then extra(i, row) for the columns a table derives from its rows.
+template <typename Row, int N>
+struct RowsArg { Row row[N]; };
+struct NoExtra {
+  template <typename Row>
+  __device__ void operator()(int, const Row&) const {}
+};
+template <typename Row, int N, typename Extra>
+__global__ void rows_kernel(const RowsArg<Row, N> r, int n, int first, Row* __restrict__ dst, const Extra extra) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  dst[first + i] = r.row[i];
+  extra(first + i, r.row[i]);
+}
+template <int N, typename Row, typename Fill, typename Extra = NoExtra>
+void upload_rows(size_t n, Row* dst, hipStream_t s, Fill fill, Extra extra = Extra{}) {
+  static_assert(sizeof(RowsArg<Row, N>) + 64 <= 4096, "kernel arguments stay under 4 KiB per launch");
+  for (size_t f = 0; f < n; f += N) {
+    RowsArg<Row, N> r{};
+    const int nn = (int)(n - f < (size_t)N ? n - f : (size_t)N);
+    for (int i = 0; i < nn; ++i) r.row[i] = fill(f + i);
+    hipLaunchKernelGGL((rows_kernel<Row, N, Extra>), dim3(1), dim3(N), 0, s, r, nn, (int)f, dst, extra);
+  }
+}
+
 // ---------------------------------------------------------------- conv1d (MFMA)
 // Packed weight layout of the implicit-GEMM conv kernel (k-interleaved, see conv1d.hip):
 //   Wp[K][Cin/8][ci & 1][Mpad][(ci % 8) / 2], Mpad a multiple of 128, rows >= M zero.
@@ -242,12 +270,7 @@ struct AdmitSynRow {
   int src_off;                 // the kept frames start at frame src_off of the run's row
   int64_t z_stride;            // row stride of `z` (already offset to the first kept frame); 0: keep
 };
-// n table rows by value from the host (kernel arguments) -> dst[first + i]
-constexpr int kAdmitChunk = 64;
-struct AdmitEncRowsArg { AdmitEncRow row[kAdmitChunk]; };
-struct AdmitSynRowsArg { AdmitSynRow row[kAdmitChunk]; };
-void launch_admit_enc_rows(const AdmitEncRowsArg& r, int n, int first, AdmitEncRow* dst, hipStream_t s);
-void launch_admit_syn_rows(const AdmitSynRowsArg& r, int n, int first, AdmitSynRow* dst, hipStream_t s);
+constexpr int kAdmitChunk = 64;   // rows per upload_rows launch
 // launch_durations with length_scale = rows[b].length_scale
 void launch_durations_rows(const float* h, const float* w, const float* b, const int* lens, const AdmitEncRow* rows,
                            float* logw, float* w_ceil, int* cum, int* ylen32, int64_t* ylen64, const int* bad, int B,
@@ -308,7 +331,7 @@ struct IstftRange {
 void launch_istft_pqmf_range(const IstftArgs& a, const IstftRange& r, hipStream_t s);
 
 // Pooled ranged decode (mbv_decode_chunks): row b of a run is the z-window of ONE chunk of some utterance.  Its
-// source, its window and what the tail keeps of it are its own; the table lives in the arena (launch_pool_rows).
+// source, its window and what the tail keeps of it are its own; the table lives in the arena (upload_rows).
 struct PoolRow {
   const float* z;          // the utterance's z [192, .] at row stride z_stride
   int64_t z_stride;
@@ -380,7 +403,7 @@ void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, in
                                  int64_t* out_samples, hipStream_t s);
 // Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
 // what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
-// the arena (launch_pcm_pool_rows).
+// the arena (upload_rows).
 struct PcmPoolRow {
   const float* x;              // the stream's wave row
   int64_t in_total;
@@ -393,19 +416,16 @@ struct PcmPoolRow {
   int64_t* out_samples;        // one value, or null
   int64_t packed_off;          // where out_first goes in the call's packed buffer, or -1
 };
-// n rows given by value from the host (up to kPcmPoolChunk per launch: 3 KiB of kernel arguments) -> rows[first + i]
-constexpr int kPcmPoolChunk = 32;
-struct PcmPoolRowsArg { PcmPoolRow row[kPcmPoolChunk]; };
-void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow* rows, hipStream_t s);
-// outputs [out_first, out_end) of every table row (n <= 65535), each bitwise what launch_resample_pcm16_range stores
-// for that row alone; also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
+constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of kernel arguments
+// outputs [out_first, out_end) of every table row (n <= 65535), each what launch_resample_pcm16_range stores for that
+// row alone (one tile function); also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
 // out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
 // in_total), pcm_cap) of every row.
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
                                 const ResampleGeom& g, short* packed, hipStream_t s);
 // Live input (mbv_resample_ranges): fp32 outputs [out_first, out_end) of MANY recordings that are still arriving,
 // each from its own raw row (fp32, or int16 scaled by 1 / 32768) into its own model-rate row, in one launch.  A
-// table row is one recording; the table lives in the arena (launch_resample_range_rows).
+// table row is one recording; the table lives in the arena (upload_rows, kPcmPoolChunk per launch).
 struct ResampleRangeRow {
   const void* x;               // the raw recording, read in place
   int32_t dtype;               // 0 = fp32, 1 = int16
@@ -414,12 +434,10 @@ struct ResampleRangeRow {
   int64_t out_first, out_end;
   float* out;                  // the recording's own model-rate row
 };
-struct ResampleRangeRowsArg { ResampleRangeRow row[kPcmPoolChunk]; };
-void launch_resample_range_rows(const ResampleRangeRowsArg& r, int n, int first, ResampleRangeRow* rows, hipStream_t s);
 // open count of resample_ready without a total: outputs no tap of which lies at or past in_avail
 int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail);
-// outputs [out_first, out_end) of every table row (n <= 65535), each bitwise what launch_resample stores there for the
-// finished recording.  max_count >= out_end - out_first of every row.  The caller guarantees out_end <=
+// outputs [out_first, out_end) of every table row (n <= 65535), each what launch_resample stores there for the
+// finished recording (one tile function).  max_count >= out_end - out_first of every row.  The caller guarantees out_end <=
 // resample_ready_open(g, n) for an open row, <= ceil(n ratio) for a closed one, and the row's capacity.
 void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
                             const ResampleGeom& g, hipStream_t s);
@@ -482,10 +500,11 @@ struct ConvertRow {
   // `samples` have arrived; the host guarantees that those frames are final.  0: the whole recording.
   int first, reserved;
 };
-struct ConvertRowsArg { ConvertRow row[kAdmitChunk]; };
-// n table rows by value -> dst[first + i], and the columns the existing launches read: lens (frames), the two sids
-void launch_convert_rows(const ConvertRowsArg& r, int n, int first, ConvertRow* dst, int* lens, int64_t* sid_src,
-                         int64_t* sid_tgt, hipStream_t s);
+// upload_rows' Extra of a ConvertRow table: the columns the existing launches read, lens (frames) and the two sids
+struct ConvertRowCols {
+  int* lens; int64_t* sid_src; int64_t* sid_tgt;
+  __device__ void operator()(int i, const ConvertRow& k) const { lens[i] = k.frames; sid_src[i] = k.sid_src; sid_tgt[i] = k.sid_tgt; }
+};
 // launch_spectrogram for row b = rows[b].wave over rows[b].samples, written into dst [B, cpad, F] (cpad >=
 // n_fft / 2 + 1: enc_q's channel-padded input): EXACT zeros in channels n_fft / 2 + 1 .. cpad and in frames at and
 // past the row's own count, so every element of dst is written.  rows[b].first > 0: frame f of the row is frame
@@ -527,11 +546,15 @@ void launch_ragged_rows(const RaggedRowsArg& r, int n, int first, int us, int* o
 // dst[i, c, t] = src[rows[i], c, t] for t < lens[i] (lens null: t < T): dst [n, C, T], src rows of C x src_rstride
 void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride, const int* rows, const int* lens,
                           int n, int C, int T, float* dst, hipStream_t s);
-// pooled ranged decode: n rows given by value from the host (up to kPoolChunk per launch) -> rows[first + i], and
-// the window length of row first + i at the three rates of the decoder at lens[k stride + first + i], k < 3
+// pooled ranged decode: upload_rows' Extra of a PoolRow table (kPoolChunk rows per launch), the window length of
+// row i at the three rates of the decoder at lens[k stride + i], k < 3
 constexpr int kPoolChunk = 64;
-struct PoolRowsArg { PoolRow row[kPoolChunk]; };
-void launch_pool_rows(const PoolRowsArg& r, int n, int first, int us, PoolRow* rows, int* lens, int stride, hipStream_t s);
+struct PoolRowLens {
+  int* lens; int stride, us;
+  __device__ void operator()(int i, const PoolRow& k) const {
+    lens[i] = k.len; lens[stride + i] = us * k.len; lens[2 * stride + i] = us * us * k.len;
+  }
+};
 // dst[i, c, t] = rows[i].z[c z_stride + wa + t] for t < rows[i].len (nothing outside a row's window is read; dst
 // [n, C, T] behind a row's length is left as it is: every reader masks at the length); gdst[i, :] = rows[i].g[0 .. gin)
 void launch_gather_windows(const PoolRow* rows, int n, int C, int T, float* dst, int gin, float* gdst, hipStream_t s);

@@ -332,21 +332,6 @@ void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* r
   hipLaunchKernelGGL(scatter_z_rows_kernel, dim3((max_keep + 255) / 256, C, B), dim3(256), 0, s, z, ylen, rows, C, Tp);
 }
 
-__global__ void admit_enc_rows_kernel(const AdmitEncRowsArg r, int n, int first, AdmitEncRow* dst) {
-  const int i = threadIdx.x;
-  if (i < n) dst[first + i] = r.row[i];
-}
-__global__ void admit_syn_rows_kernel(const AdmitSynRowsArg r, int n, int first, AdmitSynRow* dst) {
-  const int i = threadIdx.x;
-  if (i < n) dst[first + i] = r.row[i];
-}
-void launch_admit_enc_rows(const AdmitEncRowsArg& r, int n, int first, AdmitEncRow* dst, hipStream_t s) {
-  hipLaunchKernelGGL(admit_enc_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst);
-}
-void launch_admit_syn_rows(const AdmitSynRowsArg& r, int n, int first, AdmitSynRow* dst, hipStream_t s) {
-  hipLaunchKernelGGL(admit_syn_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst);
-}
-
 // ---------------------------------------------------------------------------
 // Speaker conditioning: 1x1 convs on g [B, gin, 1] are GEMVs
 // (models.py:127 dp.cond, modules.py:152 WN cond_layer, modules.py:215 ResBlock cond).
@@ -495,21 +480,6 @@ void launch_posterior_sample_rows(const float* stats, const AdmitSynRow* rows, c
                                   int I, int T, hipStream_t s) {
   dim3 grid((T + 127) / 128, I, B);
   hipLaunchKernelGGL(posterior_sample_kernel<true>, grid, dim3(128), 0, s, stats, nullptr, lens, z, I, T, 0.f, rows);
-}
-
-__global__ void convert_rows_kernel(const ConvertRowsArg r, int n, int first, ConvertRow* dst, int* lens,
-                                    int64_t* sid_src, int64_t* sid_tgt) {
-  const int i = threadIdx.x;
-  if (i >= n) return;
-  const ConvertRow k = r.row[i];
-  dst[first + i] = k;
-  lens[first + i] = k.frames;
-  sid_src[first + i] = k.sid_src;
-  sid_tgt[first + i] = k.sid_tgt;
-}
-void launch_convert_rows(const ConvertRowsArg& r, int n, int first, ConvertRow* dst, int* lens, int64_t* sid_src,
-                         int64_t* sid_tgt, hipStream_t s) {
-  hipLaunchKernelGGL(convert_rows_kernel, dim3(1), dim3(kAdmitChunk), 0, s, r, n, first, dst, lens, sid_src, sid_tgt);
 }
 
 __global__ void sequence_mask_kernel(const int* lens, float* mask, int T) {
@@ -684,21 +654,6 @@ void launch_gather_frames(const float* src, int64_t src_bstride, int src_rstride
   const int nt = T >= 256 ? 256 : 64;
   hipLaunchKernelGGL(gather_frames_kernel, dim3((T + nt - 1) / nt, C, n), dim3(nt), 0, s, src, src_bstride,
                      src_rstride, rows, lens, C, T, dst);
-}
-
-__global__ void pool_rows_kernel(const PoolRowsArg r, int n, int first, int us, PoolRow* __restrict__ rows,
-                                 int* __restrict__ lens, int stride) {
-  const int i = threadIdx.x;
-  if (i >= n) return;
-  const int len = r.row[i].len;
-  rows[first + i] = r.row[i];
-  lens[first + i] = len;
-  lens[stride + first + i] = us * len;
-  lens[2 * stride + first + i] = us * us * len;
-}
-
-void launch_pool_rows(const PoolRowsArg& r, int n, int first, int us, PoolRow* rows, int* lens, int stride, hipStream_t s) {
-  hipLaunchKernelGGL(pool_rows_kernel, dim3(1), dim3(kPoolChunk), 0, s, r, n, first, us, rows, lens, stride);
 }
 
 // blockIdx.y < C: channel row c of window i; blockIdx.y == C (only when gin > 0): the row's speaker vector

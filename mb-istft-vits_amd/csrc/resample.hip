@@ -160,8 +160,8 @@ int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Device code shared by the one-shot kernel and the ranged one: the staged input window of a tile and the
-// polyphase sum of one output.  One workgroup = up to kResampleTile consecutive outputs of one row, one output
+// Device code shared by every kernel below: the staged input window of a tile and the polyphase sum of one
+// output.  One workgroup = up to kResampleTile consecutive outputs of one row, one output
 // per thread.  The input window they read (with the K-tap halo) is staged in LDS, zero outside [0, limit):
 // resampy's min(n + 1, ...) / min(n_in - n - 1, ...) edge rule, every row resampled as if it were alone.
 // ---------------------------------------------------------------------------------------------------
@@ -219,9 +219,30 @@ __device__ __forceinline__ int64_t resample_row_valid(const int64_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// One-shot kernel: whole rows.  Outputs in [int(n ratio), out_stride) are written as zeros (librosa's
-// fix_length pad and the row padding).
+// fp32 tile: outputs [t0, t0 + kResampleTile) below out_end of one row, from its input samples [0, n); outputs in
+// [n_out, out_end) are written as zeros (librosa's fix_length pad and the row padding).  x is fp32 (dtype 0) or int16
+// (dtype 1).  The one-shot kernel and the live-input kernel both store through this function.
 // ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void resample_f32_tile(float* xs, const void* x, int dtype, int64_t n, int64_t n_out,
+                                                  int64_t t0, int64_t out_end, float* ob,
+                                                  const float* __restrict__ bank, int L, int M, int K, int left,
+                                                  double ratio) {
+  const int64_t t = t0 + threadIdx.x;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: tail only
+    if (t < out_end) ob[t] = 0.f;
+    return;
+  }
+  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
+  const int64_t j0 = resample_window_first(t0, L, M, left);
+  if (dtype == 1) resample_stage(xs, static_cast<const short*>(x), j0, t_last, L, M, K, left, n);
+  else resample_stage(xs, static_cast<const float*>(x), j0, t_last, L, M, K, left, n);
+  __syncthreads();
+  if (t >= out_end) return;
+  if (t >= n_out) { ob[t] = 0.f; return; }
+  ob[t] = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
+}
+
+// One-shot kernel: whole rows, the closed fp32 row with the range [0, out_stride) (dtype is a constant here: no branch)
 __global__ void __launch_bounds__(kResampleTile)
 resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
                 const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
@@ -235,20 +256,8 @@ resample_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, 
     int64_t keep = (int64_t)ceil((double)n * ratio);     // librosa fix_length: int(np.ceil(n * ratio))
     out_samples[b] = keep > out_stride ? out_stride : keep;
   }
-  const int64_t t0 = (int64_t)blockIdx.x * kResampleTile;
-  const int64_t t = t0 + threadIdx.x;
-  float* ob = out + (int64_t)b * out_stride;
-  if (t0 >= n_out) {                                      // uniform over the workgroup: tail only
-    if (t < out_stride) ob[t] = 0.f;
-    return;
-  }
-  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
-  const int64_t j0 = resample_window_first(t0, L, M, left);
-  resample_stage(xs, x + (int64_t)b * in_stride, j0, t_last, L, M, K, left, n);
-  __syncthreads();
-  if (t >= out_stride) return;
-  if (t >= n_out) { ob[t] = 0.f; return; }
-  ob[t] = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
+  resample_f32_tile(xs, x + (int64_t)b * in_stride, 0, n, n_out, (int64_t)blockIdx.x * kResampleTile, out_stride,
+                    out + (int64_t)b * out_stride, bank, L, M, K, left, ratio);
 }
 
 void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_stride, const float* bank,
@@ -259,110 +268,55 @@ void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_str
                      bank, g.L, g.M, g.K, g.left, g.ratio, out, out_stride, out_samples);
 }
 
+// Live input (mbv_resample_ranges): the one-shot tile over the outputs [out_first, out_end) of many recordings that
+// are still arriving, blockIdx.y = table row, blockIdx.x = tile out_first + 256 x of that row's own range; the grid
+// holds the tiles of the longest range and a tile past its row's end returns after the table load.
+//   - the caller has checked out_end against the readiness of the row, so no stored output of an open row has a tap
+//     at or past n; the staging still refuses to load those indices (the raw buffer beyond the frontier is
+//     uninitialised memory)
+//   - an open row computes every output of its range; a closed one stores zeros in [int(n ratio), out_end)
+// No atomics, no LDS beyond resample_lds_floats(g).
+__global__ void __launch_bounds__(kResampleTile)
+resample_ranges_kernel(const ResampleRangeRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
+                       int left, double ratio) {
+  extern __shared__ float xs[];
+  const ResampleRangeRow r = rows[blockIdx.y];
+  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
+  if (t0 >= r.out_end) return;                            // uniform over the workgroup: a shorter range than the grid's
+  int64_t n_out = r.out_end;
+  if (r.closed) {
+    n_out = (int64_t)((double)r.n * ratio);               // resampy: int(n_in * sample_ratio)
+    if (n_out > r.out_end) n_out = r.out_end;
+  }
+  resample_f32_tile(xs, r.x, r.dtype, r.n, n_out, t0, r.out_end, r.out, bank, L, M, K, left, ratio);
+}
+
+void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
+                            const ResampleGeom& g, hipStream_t s) {
+  const int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+  hipLaunchKernelGGL(resample_ranges_kernel, dim3((unsigned)bx, n), dim3(kResampleTile), lds, s, rows, bank, g.L, g.M,
+                     g.K, g.left, g.ratio);
+}
+
 // ---------------------------------------------------------------------------------------------------
-// Ranged kernel of the streamed wire path: outputs [out_first, out_end) of every row only, from the input
-// samples [0, in_avail) only, fused with the int16 epilogue of pcm16_kernel (ops.hip) and a running peak.
-//   - the caller (mbv_resample_pcm16_range) has checked out_end <= resample_ready(in_avail), so no stored
-//     output has a tap at or past in_avail; the staging still refuses to load those indices (the row beyond the
-//     decoded frontier is uninitialised memory, and a zero tap times a NaN is a NaN)
+// int16 tile of the streamed wire path: outputs [out_first + 256 blockIdx.x, ..) below out_end of one row (a
+// PcmPoolRow), from its input samples [0, in_avail) only, fused with the int16 epilogue of pcm16_kernel (ops.hip) and
+// a running peak.  The ranged kernel and the pooled one both store through this function.
+//   - the caller has checked out_end <= resample_ready(in_avail), so no stored output has a tap at or past in_avail;
+//     the staging still refuses to load those indices (the row beyond the decoded frontier is uninitialised memory,
+//     and a zero tap times a NaN is a NaN)
+//   - the first tile writes out_samples even for an empty range; any other tile at or past out_end returns at once
 //   - FIR = false: equal rates, the sample itself (a ranged pcm16 with a given peak)
 //   - epilogue in the order of pcm16_kernel: (v / peak) * 0.9 where peak > 0.01, clip, * 32767, truncate
-//   - running[b] = max(running[b], |v|) over the row's computed outputs (t < int(n ratio); the samples between
-//     that and ceil(n ratio) are zeros), by atomicMax on the bits as absmax_kernel does: one per wave
+//   - running = max(running, |v|) over the row's computed outputs (t < int(n ratio); the samples between that and
+//     ceil(n ratio) are zeros), by atomicMax on the bits as absmax_kernel does: one per wave
+//   - each int16 goes to the row's own pcm[t] and, with a packed buffer, to packed[packed_off + t - out_first]
 // ---------------------------------------------------------------------------------------------------
 template <bool FIR>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
-                            int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
-                            double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
-                            short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
-                            int64_t* __restrict__ out_samples) {
-  extern __shared__ float xs[];
-  const int b = blockIdx.y;
-  const int64_t n = resample_row_valid(valid, b, in_stride);
-  int64_t n_out = FIR ? (int64_t)((double)n * ratio) : n;
-  if (n_out > pcm_stride) n_out = pcm_stride;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && out_samples) {
-    int64_t keep = FIR ? (int64_t)ceil((double)n * ratio) : n;
-    out_samples[b] = keep > pcm_stride ? pcm_stride : keep;
-  }
-  const int64_t t0 = out_first + (int64_t)blockIdx.x * kResampleTile;
-  const int64_t t = t0 + threadIdx.x;
-  short* ob = pcm + (int64_t)b * pcm_stride;
-  if (t0 >= out_end) return;                              // the empty range (only out_samples to write)
-  if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
-    if (t < out_end) ob[t] = 0;
-    return;
-  }
-  const int64_t limit = n < in_avail ? n : in_avail;
-  const float* xb = x + (int64_t)b * in_stride;
-  int64_t j0 = 0;
-  if (FIR) {
-    int64_t t_last = t0 + kResampleTile - 1;
-    if (t_last > n_out - 1) t_last = n_out - 1;
-    if (t_last > out_end - 1) t_last = out_end - 1;
-    j0 = resample_window_first(t0, L, M, left);
-    resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
-    __syncthreads();
-  }
-  float v = 0.f;
-  const bool live = t < out_end && t < n_out;
-  if (live) v = FIR ? resample_output(xs, j0, t, bank, L, M, K, left, ratio) : (t < limit ? xb[t] : 0.f);
-  if (running) {
-    float m = fabsf(v);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    // m >= 0: bit order == value order.  The peak only grows, so a wave that reads a value at least its own has
-    // nothing to add: most waves skip the atomic (hundreds of them on one address serialise in L2)
-    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(&running[b], __ATOMIC_RELAXED))
-      atomicMax(&running[b], __float_as_uint(m));
-  }
-  if (t >= out_end) return;
-  if (live) {
-    if (peak) {
-      const float p = peak[b];
-      if (p > 0.01f) v = (v / p) * 0.9f;
-    }
-    v = fminf(fmaxf(v, -1.f), 1.f);
-    v = v * 32767.f;
-  }
-  ob[t] = (short)(int)v;
-}
-
-void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
-                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
-                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, hipStream_t s) {
-  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
-  const dim3 grid((unsigned)bx, B), block(kResampleTile);
-  if (bank) {
-    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
-    hipLaunchKernelGGL(resample_pcm16_range_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail, bank,
-                       g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
-                       running, out_samples);
-  } else {
-    hipLaunchKernelGGL(resample_pcm16_range_kernel<false>, grid, block, 0, s, x, valid, in_stride, in_avail, bank,
-                       1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
-                       out_samples);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Pooled ranged kernel (mbv_resample_pcm16_chunks): the ranged kernel with its per-row quantities read from a
-// table, blockIdx.y = table row, blockIdx.x = tile out_first + 256 x of that row's own range.  The grid holds the
-// tiles of the longest range; a tile at or past its row's out_end returns after the table load (the first tile
-// still writes out_samples, as the ranged kernel does for an empty range).  An output is computed by the same
-// device functions from the same staged values with the same limit min(n, in_avail), and its value does not depend
-// on which tile holds it; the running peak is a max, which does not depend on order: every stored value is bitwise
-// the ranged kernel's.  Each int16 goes to the row's own pcm[t] and, with a packed buffer, to packed[off + t - first].
-// ---------------------------------------------------------------------------------------------------
-template <bool FIR>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
-                           int left, double ratio, short* __restrict__ packed) {
-  extern __shared__ float xs[];
-  const PcmPoolRow r = rows[blockIdx.y];
+__device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
+                                                    int L, int M, int K, int left, double ratio,
+                                                    short* __restrict__ packed) {
   const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
   if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
   const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
@@ -400,7 +354,8 @@ resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __r
     float m = fabsf(v);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    // m >= 0: bit order == value order; a wave that reads a value at least its own has nothing to add
+    // m >= 0: bit order == value order.  The peak only grows, so a wave that reads a value at least its own has
+    // nothing to add: most waves skip the atomic (hundreds of them on one address serialise in L2)
     if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(r.running, __ATOMIC_RELAXED))
       atomicMax(r.running, __float_as_uint(m));
   }
@@ -418,6 +373,52 @@ resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __r
   if (pk) pk[t] = q;
 }
 
+// Ranged kernel (mbv_resample_pcm16_range): row blockIdx.y of [B] tensors, one range for all rows
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
+                            int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
+                            double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
+                            short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
+                            int64_t* __restrict__ out_samples) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
+                     peak ? peak + b : nullptr, pcm + (int64_t)b * pcm_stride, pcm_stride,
+                     running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
+  resample_pcm16_tile<FIR>(xs, r, bank, L, M, K, left, ratio, nullptr);
+}
+
+void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
+                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
+                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, hipStream_t s) {
+  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
+  const dim3 grid((unsigned)bx, B), block(kResampleTile);
+  if (bank) {
+    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
+    hipLaunchKernelGGL(resample_pcm16_range_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail, bank,
+                       g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
+                       running, out_samples);
+  } else {
+    hipLaunchKernelGGL(resample_pcm16_range_kernel<false>, grid, block, 0, s, x, valid, in_stride, in_avail, bank,
+                       1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
+                       out_samples);
+  }
+}
+
+// Pooled ranged kernel (mbv_resample_pcm16_chunks): row blockIdx.y of a table, each with its own range; the grid
+// holds the tiles of the longest one
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
+                           int left, double ratio, short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmPoolRow r = rows[blockIdx.y];
+  resample_pcm16_tile<FIR>(xs, r, bank, L, M, K, left, ratio, packed);
+}
+
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
                                 const ResampleGeom& g, short* packed, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
@@ -430,75 +431,6 @@ void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count
   } else {
     hipLaunchKernelGGL(resample_pcm16_pool_kernel<false>, grid, block, 0, s, rows, bank, 1, 1, 0, 0, 1.0, packed);
   }
-}
-
-// the table of a pooled call: by value from the host into the arena, one workgroup (as launch_pool_rows, ops.hip)
-__global__ void pcm_pool_rows_kernel(const PcmPoolRowsArg r, int n, int first, PcmPoolRow* __restrict__ rows) {
-  const int i = threadIdx.x;
-  if (i < n) rows[first + i] = r.row[i];
-}
-
-void launch_pcm_pool_rows(const PcmPoolRowsArg& r, int n, int first, PcmPoolRow* rows, hipStream_t s) {
-  hipLaunchKernelGGL(pcm_pool_rows_kernel, dim3(1), dim3(kPcmPoolChunk), 0, s, r, n, first, rows);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Live input (mbv_resample_ranges): the one-shot kernel's outputs [out_first, out_end) of many recordings that are
-// still arriving, blockIdx.y = table row, blockIdx.x = tile out_first + 256 x of that row's own range; the grid holds
-// the tiles of the longest range and a tile past its row's end returns after the table load.
-//   - the caller has checked out_end against the readiness of the row, so no stored output of an open row has a tap
-//     at or past n; the staging still refuses to load those indices (the raw buffer beyond the frontier is
-//     uninitialised memory)
-//   - taps below n see what the one-shot kernel's staging gives them and taps outside [0, n) are zeros in both, the
-//     sum runs in resample_output's order: every stored value is bitwise the one-shot kernel's for the finished row,
-//     whichever tile holds it
-//   - a closed row stores zeros in [int(n ratio), out_end), as the one-shot kernel does up to ceil(n ratio)
-// No atomics, no LDS beyond resample_lds_floats(g).
-// ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kResampleTile)
-resample_ranges_kernel(const ResampleRangeRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
-                       int left, double ratio) {
-  extern __shared__ float xs[];
-  const ResampleRangeRow r = rows[blockIdx.y];
-  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
-  if (t0 >= r.out_end) return;                            // uniform over the workgroup: a shorter range than the grid's
-  int64_t n_out = r.out_end;                              // open: every output of the range is computed
-  if (r.closed) {
-    n_out = (int64_t)((double)r.n * ratio);               // resampy: int(n_in * sample_ratio)
-    if (n_out > r.out_end) n_out = r.out_end;
-  }
-  const int64_t t = t0 + threadIdx.x;
-  if (t0 >= n_out) {                                      // uniform over the workgroup: the zeros of fix_length
-    if (t < r.out_end) r.out[t] = 0.f;
-    return;
-  }
-  const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
-  const int64_t j0 = resample_window_first(t0, L, M, left);
-  if (r.dtype == 1) resample_stage(xs, static_cast<const short*>(r.x), j0, t_last, L, M, K, left, r.n);
-  else resample_stage(xs, static_cast<const float*>(r.x), j0, t_last, L, M, K, left, r.n);
-  __syncthreads();
-  if (t >= r.out_end) return;
-  if (t >= n_out) { r.out[t] = 0.f; return; }
-  r.out[t] = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
-}
-
-void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
-                            const ResampleGeom& g, hipStream_t s) {
-  const int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
-  const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
-  hipLaunchKernelGGL(resample_ranges_kernel, dim3((unsigned)bx, n), dim3(kResampleTile), lds, s, rows, bank, g.L, g.M,
-                     g.K, g.left, g.ratio);
-}
-
-// the table of a live-input call: by value from the host into the arena, one workgroup (as launch_pcm_pool_rows)
-__global__ void resample_range_rows_kernel(const ResampleRangeRowsArg r, int n, int first,
-                                           ResampleRangeRow* __restrict__ rows) {
-  const int i = threadIdx.x;
-  if (i < n) rows[first + i] = r.row[i];
-}
-
-void launch_resample_range_rows(const ResampleRangeRowsArg& r, int n, int first, ResampleRangeRow* rows, hipStream_t s) {
-  hipLaunchKernelGGL(resample_range_rows_kernel, dim3(1), dim3(kPcmPoolChunk), 0, s, r, n, first, rows);
 }
 
 }  // namespace mbv

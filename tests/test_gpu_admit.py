@@ -362,3 +362,25 @@ def test_side_stream_and_interleaved_calls():
         assert torch.equal(net.dec(zr, g=gr, lengths=[120, 40, 9])[0], rag)
     for a, b, o in zip(sts, want, full):
         assert _same(a, b) and torch.equal(a.o, o)
+
+
+@pytest.mark.timeout(600)
+def test_a_table_longer_than_one_upload_launch():
+    """65 requests in one run: both admission tables go up in two launches, and an offset wrong in the second one shows
+    in table row 64.  Every stream bitwise its stand-alone call, one encoder run, both generators where they end."""
+    net = _net("mini")
+    reqs = [Request(_ids(4 + k % 6, 700 + k), noise_scale=(0.0, 0.5, 1.0)[k % 3], length_scale=(0.8, 1.0, 1.3)[(k // 2) % 3],
+                    noise_scale_w=(0.0, 0.8)[k % 2], chunk_frames=SCHEDULES[k % 7][0], max_chunk_frames=SCHEDULES[k % 7][1])
+            for k in range(65)]
+    _seed(13)
+    solo = [_solo(net, r) for r in reqs]
+    states = _rng_states()
+    _seed(13)
+    runs = net.encoder_runs()
+    sts = net.infer_streams(reqs)
+    assert net.encoder_runs() - runs == _plan_runs(net, reqs) == 1
+    assert len(sts) == 65
+    for k, (a, b, r) in enumerate(zip(sts, solo, reqs)):
+        assert _same(a, b), (k, r, tuple(a.z.shape), tuple(b.z.shape))
+    after = _rng_states()
+    assert torch.equal(after[0], states[0]) and torch.equal(after[1], states[1])

@@ -449,3 +449,24 @@ def test_side_stream_and_interleaved_calls():
         assert torch.equal(net.voice_conversion(spec, lens, sid[:1], sid[1:2])[0], vc)
     for s, b, o in zip(sts, want, full):
         assert _same(s, b) and torch.equal(s.o, o)
+
+
+@pytest.mark.timeout(600)
+def test_a_table_longer_than_one_upload_launch():
+    """65 recordings of 0.1 to 0.2 s in one run: both tables go up in two launches, and an offset wrong in the second
+    one shows in table row 64.  Every stream bitwise its stand-alone call, one converter run."""
+    net = _net()
+    reqs = [_request(7 + k % 5, k, seed=5, noise_scale=(0.0, 0.5, 1.0)[k % 3], chunk_frames=SCHEDULES[k % 7][0],
+                     max_chunk_frames=SCHEDULES[k % 7][1]) for k in range(65)]
+    assert all(0.1 <= r.model_samples() / MODEL_SR <= 0.2 for r in reqs)
+    _seed(17)
+    solo = [_solo(net, r) for r in reqs]
+    state = torch.cuda.get_rng_state().clone()
+    _seed(17)
+    runs = net.converter_runs()
+    sts = net.convert_streams(reqs)
+    assert net.converter_runs() - runs == _plan_runs(net, reqs) == 1
+    assert len(sts) == 65
+    for k, (a, b, r) in enumerate(zip(sts, solo, reqs)):
+        assert _same(a, b), (k, r, tuple(a.z.shape), tuple(b.z.shape))
+    assert torch.equal(torch.cuda.get_rng_state(), state), "the device generator ends elsewhere"

@@ -244,6 +244,45 @@ def test_rows_at_different_stages_share_one_launch():
     assert net.input_runs() == runs
 
 
+def test_a_table_longer_than_one_upload_launch():
+    """33 rows, int16 and fp32, open and closed: the table goes up in two launches, and an offset wrong in the second
+    one shows in table row 32.  Every row bitwise its own call and the one-shot resample, one input run."""
+    net = _net()
+    in_sr, n = 48000, 1500
+    raws = [_audio(n, 40 + k, in_sr, k % 2 == 0).cuda() for k in range(33)]
+    wants = [_whole_resampled(net, w, in_sr) for w in raws]
+    total = wants[0][1]
+    spans, avail = [], []
+    for k in range(33):
+        if k % 3 == 2:                                      # a closed row's flush
+            spans.append((200 + k, total - 200 - k))
+            avail.append(n)
+        else:                                               # an open row, from its start or inside
+            f = 0 if k % 3 == 0 else 100 + k
+            spans.append((f, 150 + 7 * k))
+            avail.append(_raw_min(in_sr, f + 150 + 7 * k))
+    assert max(avail[k] for k in range(33) if k % 3 != 2) < n
+    bufs = []
+    for w, a in zip(raws, avail):
+        b = _unarrived(n, w.dtype == torch.int16)
+        b[:a] = w[:a]
+        bufs.append(b)
+
+    def rows(outs):
+        return [_range(b, a, n if a == n else -1, f, c, o) for b, a, (f, c), o in zip(bufs, avail, spans, outs)]
+
+    alone = [torch.full((total + 50,), CANARY).cuda() for _ in raws]
+    for r in rows(alone):
+        net.resample_ranges([r], in_sr, MODEL_SR)
+    both = [torch.full((total + 50,), CANARY).cuda() for _ in raws]
+    runs = net.input_runs()
+    net.resample_ranges(rows(both), in_sr, MODEL_SR)
+    assert net.input_runs() - runs == 1
+    for a, b, (want, _), (f, c) in zip(alone, both, wants, spans):
+        assert torch.equal(a, b) and torch.equal(b[f:f + c], want[f:f + c])
+        assert bool((b[:f] == CANARY).all()) and bool((b[f + c:] == CANARY).all())
+
+
 # ------------------------------------------------------------------------------------------------ contract clause 3
 LONG = [(T, pcm, chain) for T in (257, 300) for pcm in (True, False) for chain in CHAINS]
 

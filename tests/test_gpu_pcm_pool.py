@@ -148,6 +148,36 @@ def test_raw_call_is_bitwise_the_ranged_step_row_by_row(orig, target, res_type):
     assert wire.wire_runs(net) == runs + 1 and torch.equal(r.state[1]["pcm"], before)
 
 
+@pytest.mark.timeout(600)
+def test_a_table_longer_than_one_upload_launch():
+    """33 chunks: the table goes up in two launches, and an offset wrong in the second one shows in table row 32.
+    Every row bitwise its ranged step alone, one wire run, the packed buffer in chunk order."""
+    net = _net()
+    orig, target, res_type = 22050, 24000, "kaiser_fast"
+    lag = _lag(orig, target, res_type)
+    rows = [Row(k, 257 + 31 * k, None if k % 3 else 200 + 30 * k, orig, target, res_type, lag) for k in range(33)]
+    chunks = []
+    for r in rows:
+        ref = r.state[0]
+        net.resample_pcm16_range(r.x.view(1, 1, -1), orig, target, r.n, 0, r.width, ref["pcm"], valid_samples=r.valid,
+                                 running_peak=ref["running"], out_samples=ref["ns"], res_type=res_type)
+        chunks.append(r.chunk(r.x, r.n, 0, r.width, True))
+    total, first = wire.pcm_chunks_plan(orig, target, chunks, res_type)
+    assert total == sum(r.width for r in rows) and first == [sum(r.width for r in rows[:i]) for i in range(33)]
+    packed = torch.full((total + 64,), SENTINEL, device="cuda", dtype=torch.int16)
+    runs = wire.wire_runs(net)
+    net.resample_pcm16_chunks(chunks, orig, target, packed=packed, res_type=res_type)
+    assert wire.wire_runs(net) - runs == 1
+    torch.cuda.synchronize()
+    for r in rows:
+        ref, got = r.state
+        assert torch.equal(got["pcm"], ref["pcm"]), (r.k, int((got["pcm"] != ref["pcm"]).sum()))
+        assert torch.equal(got["running"].view(torch.int32), ref["running"].view(torch.int32)), r.k
+        assert torch.equal(got["ns"], ref["ns"]) and int(got["ns"]) >= 0, r.k
+    assert torch.equal(packed[:total], torch.cat([r.state[0]["pcm"][0] for r in rows]))
+    assert bool((packed[total:] == SENTINEL).all())
+
+
 # ------------------------------------------------------------------------------------------------ end to end
 def _text(net, T, seed):
     x, xl, sid = synth.synthetic_batch(net.cfg, 1, T, seed=seed, ragged=False)

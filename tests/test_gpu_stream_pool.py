@@ -321,6 +321,27 @@ def _chunk(z, g, o, first, count, t_frames=None, o_off=0):
 
 
 @pytest.mark.timeout(600)
+def test_a_table_longer_than_one_upload_launch():
+    """65 chunks of 4 frames of one 260-frame z in one call: the run's table goes up in two launches, and an offset
+    wrong in the second one shows in table row 64.  Every chunk bitwise the stream's own, the runs as planned."""
+    net = _net("ljs_mini_mb_istft_vits")
+    z, g = _z(net, 260, 31), _g(net, 32)
+    full = net.dec(z, g)[0].clone()
+    solo = [(a, v.clone()) for a, v in net.dec_stream(z, g, 4, 4)]
+    assert len(solo) == 65
+    o = torch.full_like(full, SENTINEL)
+    chunks = [_chunk(z, g, o, 4 * k, 4) for k in range(65)]
+    runs = net.decoder_runs()
+    assert _capi.lib().mbv_decode_chunks(net._ensure_handle(), (_capi.MbvChunk * 65)(*chunks), 65, net._stream()) == 0
+    assert net.decoder_runs() - runs == net.chunks_plan([260] * 65)[0] == 1
+    torch.cuda.synchronize()
+    spf = net.cfg.samples_per_frame
+    for k, (a, v) in enumerate(solo):
+        assert a == spf * 4 * k and torch.equal(o[:, :, a:a + v.shape[2]], v), k
+    assert torch.equal(o, full)
+
+
+@pytest.mark.timeout(600)
 def test_error_paths_launch_nothing_and_the_pool_serves_on():
     net = _net("uudb_ms_istft_vits_ms")
     L = _capi.lib()

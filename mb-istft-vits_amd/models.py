@@ -21,6 +21,29 @@ from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
 # librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
 RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
 
+
+def _filter_code(res_type):
+    """res_type -> its MBV_RESAMPLE_* code; ValueError for a filter the GPU path does not have."""
+    filt = RESAMPLE_TYPES.get(res_type)
+    if filt is None:
+        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
+                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    return filt
+
+
+def _ints(values):
+    """A tensor (either device; a device tensor is read back) or a sequence -> a list of ints."""
+    return [int(v) for v in (values.tolist() if torch.is_tensor(values) else values)]
+
+
+def _valid_samples(valid, B, dev, what="valid_samples"):
+    """Per-row sample (or frame) counts -> contiguous int64 [B] on the device."""
+    valid = valid.to(device=dev, dtype=torch.int64).contiguous()
+    if valid.shape != (B,):
+        raise ValueError("%s must be [B]" % what)
+    return valid
+
+
 def _durations_code(durations):
     """Given durations -> (tensor of a dtype mbv_set_durations reads, its dtype code): int32 0, int64 1, fp32 2."""
     if durations.dtype == torch.int32:
@@ -389,8 +412,7 @@ class SynthesizerTrn(nn.Module):
             _capi.check(self._handle, L.mbv_load_weight(self._handle, name.encode(),
                                                         a.ctypes.data_as(C.c_void_p), shape, a.ndim),
                         "mbv_load_weight(%s)" % name)
-        _capi.check(self._handle, L.mbv_finalize_weights(self._handle, self._stream()),
-                    "mbv_finalize_weights")
+        self._launch(self._handle, "mbv_finalize_weights")
 
     def export_arena(self):
         """The folded, packed weight arena of this model as one flat fp32 device tensor (`mbv_export_arena`):
@@ -403,7 +425,7 @@ class SynthesizerTrn(nn.Module):
         dev = self._device()
         flat = torch.empty(n, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _capi.check(h, L.mbv_export_arena(h, self._ptr(flat), n, self._stream()), "mbv_export_arena")
+            self._launch(h, "mbv_export_arena", flat, n)
         return flat
 
     def import_arena(self, flat):
@@ -416,20 +438,18 @@ class SynthesizerTrn(nn.Module):
             raise RuntimeError("move the model to a ROCm device first (.to('cuda')): the arena lives on the GPU")
         flat = flat.to(device=dev, dtype=torch.float32).contiguous()
         self._synced_sig = self._weights_signature()      # _ensure_handle: nothing to upload
-        h = self._ensure_handle()
-        with torch.cuda.device(dev):
-            try:
-                _capi.check(h, _capi.lib().mbv_import_arena(h, self._ptr(flat), flat.numel(), self._stream()), "mbv_import_arena")
-            except Exception:
-                self._synced_sig = None
-                raise
+        try:
+            self._call("mbv_import_arena", flat, flat.numel())
+        except Exception:
+            self._synced_sig = None
+            raise
 
     def refresh_weights(self):
         """Force a re-fold/re-upload (only needed after in-place edits through `.data`)."""
         self._synced_sig = None
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._device()).cuda_stream)
+    def _stream(self, dev=None):
+        return C.c_void_p(torch.cuda.current_stream(self._device() if dev is None else dev).cuda_stream)
 
     def __del__(self):
         try:
@@ -443,6 +463,22 @@ class SynthesizerTrn(nn.Module):
     @staticmethod
     def _ptr(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _launch(self, h, name, *args, stream=None):
+        """The library entry `name` on handle `h`, inside a device scope the caller holds: tensors among `args` go as
+        their addresses and the HIP stream goes last — `stream` when a caller with several launches looked it up once,
+        else the current one; False: the entry takes none.  A failure raises MbvError."""
+        args = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+        if stream is not False:
+            args.append(self._stream() if stream is None else stream)     # (a null stream is falsy: test for None)
+        _capi.check(h, getattr(_capi.lib(), name)(h, *args), name)
+
+    def _call(self, name, *args, stream=None):
+        """The preamble of every entry: the handle (created, weights uploaded), the model's device, then `_launch`."""
+        h = self._ensure_handle()
+        dev = self._device()
+        with torch.cuda.device(dev):
+            self._launch(h, name, *args, stream=self._stream(dev) if stream is None else stream)
 
     def _check_inputs(self, x, x_lengths, sid):
         dev = self._device()
@@ -532,13 +568,10 @@ class SynthesizerTrn(nn.Module):
                 noise_w = noise_w.to(device=dev, dtype=torch.float32).contiguous()
             else:
                 noise_w = None
-            _capi.check(h, L.mbv_encode(h, self._ptr(x), self._ptr(x_lengths), self._ptr(sid), B, T,
-                                        float(length_scale), self._ptr(noise_w), float(noise_scale_w),
-                                        self._ptr(y_lengths), stream),
-                        "mbv_encode")
+            self._launch(h, "mbv_encode", x, x_lengths, sid, B, T, float(length_scale), noise_w, float(noise_scale_w),
+                         y_lengths, stream=stream)
             if durations is not None:
-                _capi.check(h, L.mbv_set_durations(h, self._ptr(durations), dur_dtype, B, T, self._ptr(y_lengths), stream),
-                            "mbv_set_durations")
+                self._launch(h, "mbv_set_durations", durations, dur_dtype, B, T, y_lengths, stream=stream)
             lo, hi = torch.aminmax(y_lengths)
             stat = torch.stack((hi, -lo))           # [T'max, > 0 iff an utterance was flagged -1]
             if stat_reduce is not None:
@@ -599,21 +632,18 @@ class SynthesizerTrn(nn.Module):
                 if v is not None:
                     setattr(out, k, v.data_ptr())
             self._ticket += 1
+            keep = int(Td if max_len is not None else 0)
             if trim:
-                _capi.check(h, L.mbv_set_option(h, b"trim", 1), "mbv_set_option")
+                self._launch(h, "mbv_set_option", b"trim", 1, stream=False)
             try:
                 if ragged:
-                    _capi.check(h, L.mbv_synthesize_ragged(h, Tp, self._ptr(noise), float(noise_scale),
-                                                           int(Td if max_len is not None else 0), C.byref(out),
-                                                           (C.c_int64 * B)(*y_host), stream),
-                                "mbv_synthesize_ragged")
+                    self._launch(h, "mbv_synthesize_ragged", Tp, noise, float(noise_scale), keep, C.byref(out),
+                                 (C.c_int64 * B)(*y_host), stream=stream)
                 else:
-                    _capi.check(h, L.mbv_synthesize(h, Tp, self._ptr(noise), float(noise_scale),
-                                                    int(Td if max_len is not None else 0), C.byref(out), stream),
-                                "mbv_synthesize")
+                    self._launch(h, "mbv_synthesize", Tp, noise, float(noise_scale), keep, C.byref(out), stream=stream)
             finally:
                 if trim:
-                    _capi.check(h, L.mbv_set_option(h, b"trim", 0), "mbv_set_option")
+                    self._launch(h, "mbv_set_option", b"trim", 0, stream=False)
         timings = Timings(self, (h, int(L.mbv_ticket(h))))
         g = t.get
         return (g("o"), g("o_mb"), g("spec"), g("phase"), g("attn"), g("y_mask"),
@@ -684,27 +714,43 @@ class SynthesizerTrn(nn.Module):
                       noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged)
         return r[:8], r[8]
 
-    @torch.no_grad()
-    def _decode(self, z, g=None):
-        h = self._ensure_handle()
+    def _z_g(self, z, g, checked=True):
+        """(z, g) as the decoder entries read them: fp32, contiguous, on the device, g as [B, gin].  `checked` (every
+        caller but `_decode_into`, whose z and g are the model's own): z must be [B, inter, T'], and a model
+        without speakers drops g."""
         dev = self._device()
-        if z.dim() != 3 or z.shape[1] != self.cfg.inter_channels:
+        if checked and (z.dim() != 3 or z.shape[1] != self.cfg.inter_channels):
             raise ValueError("z must be [B, %d, T']" % self.cfg.inter_channels)
         z = z.to(device=dev, dtype=torch.float32).contiguous()
-        B, _, Tp = z.shape
         if g is not None:
-            if self.cfg.gin_channels == 0:
+            if checked and self.cfg.gin_channels == 0:
                 g = None
             else:
-                g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
-        with torch.cuda.device(dev):
-            o, o_mb, spec, phase = self._alloc_decoder_outputs(B, Tp, dev)
-            out = _capi.MbvOutputs()
-            out.o, out.spec, out.phase = o.data_ptr(), spec.data_ptr(), phase.data_ptr()
-            out.o_mb = o_mb.data_ptr() if o_mb is not None else None
-            _capi.check(h, _capi.lib().mbv_decode(h, self._ptr(z), self._ptr(g), B, Tp, C.byref(out),
-                                                  self._stream()), "mbv_decode")
-        return o, o_mb, spec, phase
+                g = g.to(device=dev, dtype=torch.float32).reshape(z.shape[0], self.cfg.gin_channels).contiguous()
+        return z, g
+
+    @staticmethod
+    def _outputs_struct(outs, B):
+        """(o, o_mb, spec, phase), any of them None -> the `MbvOutputs` that names them."""
+        out = _capi.MbvOutputs()
+        for name, t in zip(("o", "o_mb", "spec", "phase"), outs):
+            if t is not None:
+                if not t.is_contiguous() or t.shape[0] != B:
+                    raise ValueError("%s: a contiguous block of %d rows expected" % (name, B))
+                setattr(out, name, t.data_ptr())
+        return out
+
+    def _decode_rows(self, entry, z, g, outs, *extra):
+        """The decoder entry `entry`(z, g, *extra, B, T', outputs) into (o, o_mb, spec, phase), any of them None."""
+        B, _, Tp = z.shape
+        self._call(entry, z, g, *extra, B, Tp, C.byref(self._outputs_struct(outs, B)))
+
+    @torch.no_grad()
+    def _decode(self, z, g=None):
+        z, g = self._z_g(z, g)
+        outs = self._alloc_decoder_outputs(z.shape[0], z.shape[2], z.device)
+        self._decode_rows("mbv_decode", z, g, outs)
+        return outs
 
     @torch.no_grad()
     def _decode_ragged(self, z, g, lengths):
@@ -712,25 +758,13 @@ class SynthesizerTrn(nn.Module):
         bitwise `net.dec(z[b:b+1, :, :lens[b]], g[b:b+1])[0]` (default mode; with "splitk" within fp32 rounding)
         and zero behind; z at and past a row's length is never read.  `lengths`: a sequence of ints or an integer
         tensor on either device (a device tensor is read back: one synchronisation)."""
-        h = self._ensure_handle()
-        dev = self._device()
-        if z.dim() != 3 or z.shape[1] != self.cfg.inter_channels:
-            raise ValueError("z must be [B, %d, T']" % self.cfg.inter_channels)
-        z = z.to(device=dev, dtype=torch.float32).contiguous()
+        z, g = self._z_g(z, g)
         B, _, Tp = z.shape
-        lens = lengths.tolist() if torch.is_tensor(lengths) else list(lengths)
+        lens = _ints(lengths)
         if len(lens) != B:
             raise ValueError("lengths must hold one length per row of z")
-        lens = [int(v) for v in lens]
-        if g is not None:
-            if self.cfg.gin_channels == 0:
-                g = None
-            else:
-                g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
-        with torch.cuda.device(dev):
-            o = torch.empty(B, 1, self.cfg.samples_per_frame * Tp, device=dev, dtype=torch.float32)
-            _capi.check(h, _capi.lib().mbv_decode_ragged(h, self._ptr(z), self._ptr(g), B, Tp, (C.c_int64 * B)(*lens),
-                                                         self._ptr(o), self._stream()), "mbv_decode_ragged")
+        o = torch.empty(B, 1, self.cfg.samples_per_frame * Tp, device=z.device, dtype=torch.float32)
+        self._call("mbv_decode_ragged", z, g, B, Tp, (C.c_int64 * B)(*lens), o)
         return o
 
     def ragged_classes(self, t_max, splitk=False):
@@ -747,7 +781,7 @@ class SynthesizerTrn(nn.Module):
     def ragged_plan(self, lengths, t_frames=None, splitk=False):
         """(runs, run_of_row): the decoder runs a ragged call makes for rows of these z-lengths (`mbv_ragged_plan`,
         host only) — one per non-empty class, cut further only at 2 GiB tensors; run_of_row[b] = -1 for an empty row."""
-        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        lens = _ints(lengths)
         B = len(lens)
         t_frames = max(max(lens), 1) if t_frames is None else int(t_frames)
         cfg = self._config_struct()
@@ -761,43 +795,17 @@ class SynthesizerTrn(nn.Module):
     def _decode_into(self, z, g, outs):
         """`net.dec` on a block of rows, writing into caller-owned (o, o_mb, spec, phase) — any may be None.
         dist.sharded_infer(overlap="halves") decodes a shard in two pieces with it."""
-        h = self._ensure_handle()
-        dev = self._device()
-        z = z.to(device=dev, dtype=torch.float32).contiguous()
-        B, _, Tp = z.shape
-        if g is not None:
-            g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
-        out = _capi.MbvOutputs()
-        for name, t in zip(("o", "o_mb", "spec", "phase"), outs):
-            if t is not None:
-                if not t.is_contiguous() or t.shape[0] != B:
-                    raise ValueError("%s: a contiguous block of %d rows expected" % (name, B))
-                setattr(out, name, t.data_ptr())
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_decode(h, self._ptr(z), self._ptr(g), B, Tp, C.byref(out),
-                                                  self._stream()), "mbv_decode")
+        self._decode_rows("mbv_decode", *self._z_g(z, g, checked=False), outs)
 
+    @torch.no_grad()
     def _decode_masked_into(self, z, g, lengths, outs):
         """`_decode_into` on z * sequence_mask(lengths) (`mbv_decode_masked`): the decoder run `infer` makes, on a z
         of the caller's.  `lengths`: ints, one per row."""
-        h = self._ensure_handle()
-        dev = self._device()
-        z = z.to(device=dev, dtype=torch.float32).contiguous()
-        B, _, Tp = z.shape
-        lens = torch.as_tensor([int(v) for v in lengths], dtype=torch.int32).to(dev)
-        if lens.shape[0] != B:
+        z, g = self._z_g(z, g, checked=False)
+        lens = torch.as_tensor([int(v) for v in lengths], dtype=torch.int32).to(z.device)
+        if lens.shape[0] != z.shape[0]:
             raise ValueError("lengths must hold one length per row of z")
-        if g is not None:
-            g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
-        out = _capi.MbvOutputs()
-        for name, t in zip(("o", "o_mb", "spec", "phase"), outs):
-            if t is not None:
-                if not t.is_contiguous() or t.shape[0] != B:
-                    raise ValueError("%s: a contiguous block of %d rows expected" % (name, B))
-                setattr(out, name, t.data_ptr())
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_decode_masked(h, self._ptr(z), self._ptr(g), self._ptr(lens), B, Tp,
-                                                         C.byref(out), self._stream()), "mbv_decode_masked")
+        self._decode_rows("mbv_decode_masked", z, g, outs, lens)
 
     def tail_plan(self):
         """Rows (kind, stage, j, q, rate, reach) of `mbv_tail_plan` for this model's decoder (host only)."""
@@ -823,16 +831,7 @@ class SynthesizerTrn(nn.Module):
         views of one full-length `o`, one `mbv_decode_range` call per chunk.  Chunks start at `chunk_frames` and
         double up to `max_chunk_frames`.  The concatenation is bitwise `dec(z, g)[0]` (default mode)."""
         h = self._ensure_handle()
-        dev = self._device()
-        if z.dim() != 3 or z.shape[1] != self.cfg.inter_channels:
-            raise ValueError("z must be [B, %d, T']" % self.cfg.inter_channels)
-        z = z.to(device=dev, dtype=torch.float32).contiguous()
-        B = z.shape[0]
-        if g is not None:
-            if self.cfg.gin_channels == 0:
-                g = None
-            else:
-                g = g.to(device=dev, dtype=torch.float32).reshape(B, self.cfg.gin_channels).contiguous()
+        z, g = self._z_g(z, g)
         return stream.DecodeStream(self, h, z, g, chunk_frames, max_chunk_frames)
 
     def stream_pool(self):
@@ -844,13 +843,19 @@ class SynthesizerTrn(nn.Module):
     def chunks_plan(self, t_frames, splitk=False):
         """(runs, run_of_chunk): the decoder runs one pooled step makes for chunks of utterances of these z-lengths
         (`mbv_chunks_plan`, host only: no GPU needed)."""
-        t = [int(v) for v in (t_frames.tolist() if torch.is_tensor(t_frames) else t_frames)]
+        return self._plan_runs("mbv_chunks_plan", t_frames, splitk,
+                               "mbv_chunks_plan refused the lengths (every t_frames must be >= 1, and at least one chunk)")
+
+    def _plan_runs(self, entry, lengths, splitk, refusal):
+        """(runs, run_of_item) of a host-only planner `entry`(config, splitk, n, int32 lengths, int32 run_of_item):
+        `lengths` is a sequence of ints or an integer tensor; a negative return raises ValueError(refusal)."""
+        t = _ints(lengths)
         n = len(t)
         cfg = self._config_struct()
         runs = (C.c_int32 * max(n, 1))()
-        r = _capi.lib().mbv_chunks_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * max(n, 1))(*t), runs)
+        r = getattr(_capi.lib(), entry)(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * max(n, 1))(*t), runs)
         if r < 0:
-            raise ValueError("mbv_chunks_plan refused the lengths (every t_frames must be >= 1, and at least one chunk)")
+            raise ValueError(refusal)
         return r, list(runs)[:n]
 
     def decoder_runs(self):
@@ -881,23 +886,60 @@ class SynthesizerTrn(nn.Module):
         return st
 
     # ------------------------------------------------------------------ pooled admission
+    @staticmethod
+    def _pack_host(tensors, dev):
+        """1-D tensors (or None), one per request -> (the device address of each, the tensors to keep alive while
+        launches read them): host tensors travel in one concatenated copy per dtype, device tensors stay."""
+        ptr, keep = [None] * len(tensors), []
+        for dt in (torch.int32, torch.int64, torch.float32, torch.int16):
+            host = [i for i, t in enumerate(tensors) if t is not None and not t.is_cuda and t.dtype == dt]
+            if host:
+                flat = torch.cat([tensors[i] for i in host]).to(dev)
+                keep.append(flat)
+                o = 0
+                for i in host:
+                    ptr[i] = flat.data_ptr() + flat.element_size() * o
+                    o += tensors[i].numel()
+        for i, t in enumerate(tensors):
+            if t is not None and ptr[i] is None:
+                t = t.to(dev)
+                keep.append(t)
+                ptr[i] = t.data_ptr()
+        return ptr, keep
+
+    @staticmethod
+    def _draw_rows(I, lengths, dev):
+        """One standard-normal block [1, I, T_i] per request, in list order, in one flat buffer -> (the buffer, the
+        address of each block): the values and the generator's progress of N stand-alone randn(1, I, T_i) calls."""
+        flat = torch.empty(I * sum(lengths), device=dev, dtype=torch.float32)
+        ptr, o = [], 0
+        for t in lengths:
+            flat[o:o + I * t].view(1, I, t).normal_()
+            ptr.append(flat.data_ptr() + 4 * o)
+            o += I * t
+        return flat, ptr
+
+    def _streams_of(self, reqs, z, g, y_all, pos):
+        """One single-utterance `DecodeStream` per request over its own z and g; `y_lengths` is the one-element slice
+        of `y_all` at the request's row."""
+        out = []
+        for i, r in enumerate(reqs):
+            st = stream.DecodeStream(self, self._handle, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
+            st.y_lengths = y_all[pos[i]:pos[i] + 1]
+            out.append(st)
+        return out
+
     def admit_plan(self, t_text, splitk=False):
         """(runs, run_of_request): the front-half runs `infer_streams` makes for requests of these text lengths
         (`mbv_admit_plan`, host only: no GPU needed).  Requests share a padded run iff the conv planner sends every
         conv in front of the flows to the same kernel family for either text alone — today two classes, T <= 256 and
         beyond; with `splitk` one."""
-        t = [int(v) for v in (t_text.tolist() if torch.is_tensor(t_text) else t_text)]
-        n = len(t)
-        if n < 1:
+        t = _ints(t_text)
+        if not t:
             raise ValueError("admit_plan: no requests")
         if min(t) < 1:
             raise ValueError("admit_plan: empty text (every length must be >= 1)")
-        cfg = self._config_struct()
-        runs = (C.c_int32 * n)()
-        r = _capi.lib().mbv_admit_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * n)(*t), runs)
-        if r < 0:
-            raise ValueError("mbv_admit_plan refused the lengths")
-        return r, list(runs)
+        return self._plan_runs("mbv_admit_plan", t, splitk, "mbv_admit_plan refused the lengths")
 
     def encoder_runs(self):
         """Text-encoder runs made on this model's handle so far (`mbv_encoder_runs`): the difference across a call is
@@ -929,12 +971,9 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError("request %d: sid is required for a multi-speaker model (models.py:704-705)" % i)
         if not reqs:
             return []
-        h = self._ensure_handle()
+        h = self._handle_not_bf16("infer_streams", "admit with infer_stream, one request at a time")
         L = _capi.lib()
         dev = self._device()
-        if L.mbv_get_option(h, b"conv_bf16") != 0:
-            raise ValueError("infer_streams is not built for the \"conv_bf16\" mode (the flows' route follows the launch "
-                             "size there): admit with infer_stream, one request at a time")
         N, I = len(reqs), self.cfg.inter_channels
         t_text = [r.x.numel() for r in reqs]
         n_runs, run_of = self.admit_plan(t_text, splitk=L.mbv_get_option(h, b"splitk") != 0)
@@ -945,7 +984,7 @@ class SynthesizerTrn(nn.Module):
             for b, i in enumerate(m):
                 pos[i] = first[-1] + b
         with torch.cuda.device(dev):
-            hip_stream = self._stream()
+            hip_stream = self._stream(dev)
             keep = []                              # inputs of launches in flight
             noise_w = [None] * N
             if self.cfg.use_sdp:                   # the reference's draw, per request, on the default CPU generator
@@ -955,21 +994,8 @@ class SynthesizerTrn(nn.Module):
                 for i, t in enumerate(t_text):
                     noise_w[i] = flat_w.data_ptr() + 4 * o
                     o += 2 * t
-            dur = [None] * N                       # device addresses of the given durations: host ones travel together
-            for code in (0, 1, 2):
-                host = [i for i in range(N) if reqs[i].durations_dtype == code and not reqs[i].durations.is_cuda]
-                if host:
-                    flat_d = torch.cat([reqs[i].durations for i in host]).to(dev)
-                    keep.append(flat_d)
-                    o = 0
-                    for i in host:
-                        dur[i] = flat_d.data_ptr() + flat_d.element_size() * o
-                        o += t_text[i]
-            for i, r in enumerate(reqs):
-                if r.durations is not None and dur[i] is None:
-                    d = r.durations.to(dev)
-                    keep.append(d)
-                    dur[i] = d.data_ptr()
+            dur, kept = self._pack_host([r.durations for r in reqs], dev)       # (None where none are given)
+            keep += kept
             y_all = torch.empty(N, dtype=torch.int64, device=dev)
             # ids (zero-padded to the run's longest text), lengths and sids of every run: ONE host tensor, one copy
             on_host = not any(r.x.is_cuda for r in reqs)
@@ -993,9 +1019,8 @@ class SynthesizerTrn(nn.Module):
                     r = reqs[i]
                     row.length_scale, row.noise_scale_w, row.noise_w = r.length_scale, r.noise_scale_w, noise_w[i]
                     row.durations, row.durations_dtype, row.t_text = dur[i], r.durations_dtype or 0, t_text[i]
-                _capi.check(h, L.mbv_encode_rows(h, k, C.c_void_p(ids), C.c_void_p(lens), self._ptr(sid), B, T, rows,
-                                                 C.c_void_p(y_all.data_ptr() + 8 * first[k]), hip_stream),
-                            "mbv_encode_rows")
+                self._launch(h, "mbv_encode_rows", k, C.c_void_p(ids), C.c_void_p(lens), sid, B, T, rows,
+                             C.c_void_p(y_all.data_ptr() + 8 * first[k]), stream=hip_stream)
             y_host = y_all.tolist()                # the one host sync: every run's lengths, -1 = flagged
             bad = [i for i in range(N) if y_host[pos[i]] < 0]
             if bad:
@@ -1007,12 +1032,8 @@ class SynthesizerTrn(nn.Module):
             Td = [Tp[i] if r.max_len is None else min(Tp[i], r.max_len) for i, r in enumerate(reqs)]
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729): per request, in list order,
             # into one buffer — the values and the generator's progress of N stand-alone randn(1, I, T'_i) calls
-            flat = torch.empty(I * sum(Tp), device=dev, dtype=torch.float32)
-            noise, o = [0] * N, 0
-            for i in range(N):
-                flat[o:o + I * Tp[i]].view(1, I, Tp[i]).normal_()
-                noise[i] = flat.data_ptr() + 4 * o
-                o += I * Tp[i]
+            flat, noise = self._draw_rows(I, Tp, dev)
+            keep.append(flat)
             z = [torch.empty(1, I, Td[i], device=dev, dtype=torch.float32) for i in range(N)]
             g = [None] * N
             for k, m in enumerate(members):
@@ -1021,19 +1042,13 @@ class SynthesizerTrn(nn.Module):
                 for row, i in zip(rows, m):
                     row.noise, row.noise_stride, row.noise_scale = noise[i], Tp[i], reqs[i].noise_scale
                     row.keep, row.z = Td[i], z[i].data_ptr()
-                _capi.check(h, L.mbv_synthesize_rows(h, k, max(Tp[i] for i in m), rows, B, hip_stream), "mbv_synthesize_rows")
+                self._launch(h, "mbv_synthesize_rows", k, max(Tp[i] for i in m), rows, B, stream=hip_stream)
                 if self.n_speakers > 0:            # (the sids passed the encode's range check)
                     g_run = torch.empty(B, self.cfg.gin_channels, device=dev, dtype=torch.float32)
-                    _capi.check(h, L.mbv_speaker_embedding(h, self._ptr(sids[k]), B, self._ptr(g_run), hip_stream),
-                                "mbv_speaker_embedding")
+                    self._launch(h, "mbv_speaker_embedding", sids[k], B, g_run, stream=hip_stream)
                     for b, i in enumerate(m):
                         g[i] = g_run[b:b + 1]
-            out = []
-            for i, r in enumerate(reqs):
-                st = stream.DecodeStream(self, h, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
-                st.y_lengths = y_all[pos[i]:pos[i] + 1]
-                out.append(st)
-        return out
+            return self._streams_of(reqs, z, g, y_all, pos)
 
     # ------------------------------------------------------------------ pooled voice conversion
     def convert_plan(self, t_frames, splitk=False):
@@ -1041,18 +1056,13 @@ class SynthesizerTrn(nn.Module):
         (`mbv_convert_plan`, host only: no GPU needed).  Requests share a padded run iff the conv planner sends
         enc_q.pre, enc_q.proj and the flows' convs to the same kernel family for either alone; a class is cut at
         65 535 rows and at what the fused WN layers take; with `splitk` one class."""
-        t = [int(v) for v in (t_frames.tolist() if torch.is_tensor(t_frames) else t_frames)]
-        n = len(t)
-        if n < 1:
+        t = _ints(t_frames)
+        if not t:
             raise ValueError("convert_plan: no requests")
         if min(t) < 1:
             raise ValueError("convert_plan: a request without frames (every count must be >= 1)")
-        cfg = self._config_struct()
-        runs = (C.c_int32 * n)()
-        r = _capi.lib().mbv_convert_plan(C.byref(cfg), int(bool(splitk)), n, (C.c_int32 * n)(*t), runs)
-        if r < 0:
-            raise ValueError("mbv_convert_plan refused the frame counts (one request beyond the fused WN layers?)")
-        return r, list(runs)
+        return self._plan_runs("mbv_convert_plan", t, splitk,
+                               "mbv_convert_plan refused the frame counts (one request beyond the fused WN layers?)")
 
     def converter_runs(self):
         """Posterior-encoder runs `convert_streams` / `convert_stream` made on this model's handle so far
@@ -1106,6 +1116,32 @@ class SynthesizerTrn(nn.Module):
         (IndexError); a single-speaker model raises the reference's assertion.  No stream is created then."""
         return self._convert(list(requests), alone=False)
 
+    def _check_conversion(self, who, hop_size, win_size, n_fft_is=""):
+        """What a conversion entry (`_convert`, `stream.LiveStream`) refuses about the model and the data config, on
+        the host; -> n_fft.  `who` names the caller in the messages, `n_fft_is` is what its win_size message adds."""
+        if not self.n_speakers > 0:
+            raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
+        n_fft = 2 * (self.cfg.spec_channels - 1)
+        if _capi.lib().mbv_spectrogram_frames(1, n_fft, hop_size) < 0:
+            raise ValueError("%s: n_fft = 2 (spec_channels - 1) = %d must be a power of two in [256, 4096] "
+                             "and hop_size in [1, n_fft] (hop_size %d)" % (who, n_fft, hop_size))
+        if not 1 <= win_size <= n_fft:
+            raise ValueError("%s: win_size %d must be in [1, n_fft =%s %d]" % (who, win_size, n_fft_is, n_fft))
+        return n_fft
+
+    def _check_speakers(self, sid_src, sid_tgt, prefix=""):
+        for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
+            if not 0 <= sid < self.n_speakers:
+                raise IndexError("%sindex out of range in self (%s %d outside [0, %d))"
+                                 % (prefix, name, sid, self.n_speakers))
+
+    def _handle_not_bf16(self, who, instead, why=" (the flows' route follows the launch size there)"):
+        """`_ensure_handle()` for the entries that are not built for the "conv_bf16" mode: ValueError there."""
+        h = self._ensure_handle()
+        if _capi.lib().mbv_get_option(h, b"conv_bf16") != 0:
+            raise ValueError("%s is not built for the \"conv_bf16\" mode%s: %s" % (who, why, instead))
+        return h
+
     @torch.no_grad()
     def _convert(self, reqs, alone, noise=None):
         for i, r in enumerate(reqs):
@@ -1119,15 +1155,7 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError("request %d: (model_sr, hop_size, win_size) = %s differs from request 0's %s: one model "
                                  "has one data config" % (i, (r.model_sr, r.hop_size, r.win_size),
                                                           (r0.model_sr, r0.hop_size, r0.win_size)))
-        if not self.n_speakers > 0:
-            raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
-        n_fft = 2 * (self.cfg.spec_channels - 1)
-        if _capi.lib().mbv_spectrogram_frames(1, n_fft, r0.hop_size) < 0:
-            raise ValueError("convert_streams: n_fft = 2 (spec_channels - 1) = %d must be a power of two in [256, 4096] "
-                             "and hop_size in [1, n_fft] (hop_size %d)" % (n_fft, r0.hop_size))
-        if r0.win_size > n_fft:
-            raise ValueError("convert_streams: win_size %d must be in [1, n_fft = 2 * (spec_channels - 1) = %d]"
-                             % (r0.win_size, n_fft))
+        n_fft = self._check_conversion("convert_streams", r0.hop_size, r0.win_size, " 2 * (spec_channels - 1) =")
         N, I = len(reqs), self.cfg.inter_channels
         samples = [r.model_samples() for r in reqs]
         frames = [r.frames(n_fft) for r in reqs]
@@ -1135,25 +1163,19 @@ class SynthesizerTrn(nn.Module):
             if frames[i] < 1:
                 raise ValueError("request %d: %d samples at %d Hz give no spectrogram frame (n_fft %d, hop_size %d)"
                                  % (i, r.wave.numel(), r.in_sr, n_fft, r.hop_size))
-            for name, sid in (("sid_src", r.sid_src), ("sid_tgt", r.sid_tgt)):
-                if not 0 <= sid < self.n_speakers:
-                    raise IndexError("request %d: index out of range in self (%s %d outside [0, %d))"
-                                     % (i, name, sid, self.n_speakers))
-        h = self._ensure_handle()
+            self._check_speakers(r.sid_src, r.sid_tgt, "request %d: " % i)
+        h = self._handle_not_bf16("convert_streams", "convert with voice_conversion")
         L = _capi.lib()
         dev = self._device()
-        if L.mbv_get_option(h, b"conv_bf16") != 0:
-            raise ValueError("convert_streams is not built for the \"conv_bf16\" mode (the flows' route follows the launch "
-                             "size there): convert with voice_conversion")
         try:
             n_runs, run_of = self.convert_plan(frames, splitk=L.mbv_get_option(h, b"splitk") != 0)
         except ValueError:
             raise ValueError("convert_streams: a request of %d frames is beyond what the fused WN layers take" % max(frames))
         members = [[i for i in range(N) if run_of[i] == k] for k in range(n_runs)]
         with torch.cuda.device(dev):
-            hip_stream = self._stream()
+            hip_stream = self._stream(dev)
             keep = []                              # inputs of launches in flight
-            wave_ptr, wave_dtype = [None] * N, [0] * N
+            wave_ptr = [None] * N
             # rows at another rate: one `resample` call per distinct in_sr over their padded batch; the result is read
             # in place, row by row
             for sr in sorted({r.in_sr for r in reqs if r.in_sr != r.model_sr}):
@@ -1171,23 +1193,12 @@ class SynthesizerTrn(nn.Module):
                 keep.append(out)
                 for b, i in enumerate(idx):
                     wave_ptr[i] = out.data_ptr() + 4 * b * out.shape[-1]
-            # rows at the model's rate: host waves travel in one concatenated copy per dtype, device waves stay
-            for dt, code in ((torch.float32, 0), (torch.int16, 1)):
-                same = [i for i in range(N) if reqs[i].in_sr == reqs[i].model_sr and reqs[i].wave.dtype == dt]
-                host = [i for i in same if not reqs[i].wave.is_cuda]
-                if host:
-                    flat_w = torch.cat([reqs[i].wave for i in host]).to(dev)
-                    keep.append(flat_w)
-                    o = 0
-                    for i in host:
-                        wave_ptr[i] = flat_w.data_ptr() + flat_w.element_size() * o
-                        o += reqs[i].wave.numel()
-                for i in same:
-                    wave_dtype[i] = code
-                    if wave_ptr[i] is None:
-                        w = reqs[i].wave.to(dev)
-                        keep.append(w)
-                        wave_ptr[i] = w.data_ptr()
+            # rows at the model's rate are read as they came (MBV_WAVE_F32 0 / MBV_WAVE_PCM16 1)
+            same = [r.in_sr == r.model_sr for r in reqs]
+            own_ptr, kept = self._pack_host([r.wave if same[i] else None for i, r in enumerate(reqs)], dev)
+            keep += kept
+            wave_ptr = [own_ptr[i] if same[i] else wave_ptr[i] for i in range(N)]
+            wave_dtype = [int(same[i] and r.wave.dtype == torch.int16) for i, r in enumerate(reqs)]
             # the posterior draw, per request, in list order: the values and the generator's progress of N stand-alone
             # randn(1, I, T_i) calls (drawn at noise_scale == 0 too, as convert_stream does)
             if alone and noise is not None:
@@ -1202,12 +1213,7 @@ class SynthesizerTrn(nn.Module):
                 noise = [flat.data_ptr()]
                 y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
             else:
-                flat = torch.empty(I * sum(frames), device=dev, dtype=torch.float32)
-                noise, o = [0] * N, 0
-                for i in range(N):
-                    flat[o:o + I * frames[i]].view(1, I, frames[i]).normal_()
-                    noise[i] = flat.data_ptr() + 4 * o
-                    o += I * frames[i]
+                flat, noise = self._draw_rows(I, frames, dev)
                 y_all = torch.tensor(frames, dtype=torch.int64).to(dev)
             z = [torch.empty(1, I, frames[i], device=dev, dtype=torch.float32) for i in range(N)]
             g = [None] * N
@@ -1220,16 +1226,11 @@ class SynthesizerTrn(nn.Module):
                     row.sid_src, row.sid_tgt = r.sid_src, r.sid_tgt
                     row.noise, row.noise_scale, row.z = noise[i], r.noise_scale, z[i].data_ptr()
                 g_run = torch.empty(B, self.cfg.gin_channels, device=dev, dtype=torch.float32)
-                _capi.check(h, L.mbv_convert_rows(h, rows, B, max(frames[i] for i in m), r0.hop_size, r0.win_size,
-                                                  self._ptr(g_run), hip_stream), "mbv_convert_rows")
+                self._launch(h, "mbv_convert_rows", rows, B, max(frames[i] for i in m), r0.hop_size, r0.win_size, g_run,
+                             stream=hip_stream)
                 for b, i in enumerate(m):
                     g[i] = g_run[b:b + 1]
-            out = []
-            for i, r in enumerate(reqs):
-                st = stream.DecodeStream(self, h, z[i], g[i], r.chunk_frames, r.max_chunk_frames)
-                st.y_lengths = y_all[i:i + 1]
-                out.append(st)
-        return out
+            return self._streams_of(reqs, z, g, y_all, range(N))
 
     @torch.no_grad()
     def istft_finalize(self, spec, phase):
@@ -1237,7 +1238,6 @@ class SynthesizerTrn(nn.Module):
         of the reference's chunked decoding (`istft_finalize` in inferz_test.ipynb cell 6; the
         cross-fade of the chunks' spectrograms stays in the caller).  Accepts the complex
         spectrogram too (`spec * exp(1j * phase)`), as the notebook passes it."""
-        h = self._ensure_handle()
         dev = self._device()
         if phase is None:
             if not torch.is_complex(spec):
@@ -1253,10 +1253,7 @@ class SynthesizerTrn(nn.Module):
         B, Fr = spec.shape[0], spec.shape[-1]
         n = (4 if sb else 16) * (Fr - 1)
         o = torch.empty(B, 1, n, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_istft_finalize(h, self._ptr(spec), self._ptr(phase), B, Fr,
-                                                          self._ptr(o), None, self._stream()),
-                        "mbv_istft_finalize")
+        self._call("mbv_istft_finalize", spec, phase, B, Fr, o, None)
         return o
 
     @torch.no_grad()
@@ -1266,7 +1263,6 @@ class SynthesizerTrn(nn.Module):
         its valid 256 * y_lengths samples (rest zero).  Bit-exact with the NumPy code.
         `valid_samples` (int64 [B], e.g. the lengths `resample` returns) gives the valid length in
         samples instead; it excludes `y_lengths`."""
-        h = self._ensure_handle()
         dev = self._device()
         wave = wave.to(device=dev, dtype=torch.float32).contiguous()
         B, n = wave.shape[0], wave.shape[-1]
@@ -1274,21 +1270,11 @@ class SynthesizerTrn(nn.Module):
         if valid_samples is not None:
             if y_lengths is not None:
                 raise ValueError("to_pcm16: give y_lengths (frames) or valid_samples (samples), not both")
-            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).contiguous()
-            if valid_samples.shape != (B,):
-                raise ValueError("valid_samples must be [B]")
-            with torch.cuda.device(dev):
-                _capi.check(h, _capi.lib().mbv_pcm16_samples(h, self._ptr(wave), self._ptr(valid_samples), B, n,
-                                                             int(bool(auto_normalize)), self._ptr(pcm),
-                                                             self._stream()),
-                            "mbv_pcm16_samples")
+            self._call("mbv_pcm16_samples", wave, _valid_samples(valid_samples, B, dev), B, n, int(bool(auto_normalize)), pcm)
             return pcm
         if y_lengths is not None:
             y_lengths = y_lengths.to(device=dev, dtype=torch.int64).contiguous()
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_pcm16(h, self._ptr(wave), self._ptr(y_lengths), B, n,
-                                                 int(bool(auto_normalize)), self._ptr(pcm), self._stream()),
-                        "mbv_pcm16")
+        self._call("mbv_pcm16", wave, y_lengths, B, n, int(bool(auto_normalize)), pcm)
         return pcm
 
     @torch.no_grad()
@@ -1302,10 +1288,7 @@ class SynthesizerTrn(nn.Module):
         (samples); neither = whole rows.  Equal rates return `wave` and the lengths unchanged.  No host
         synchronisation, except on the first call for a rate pair (the filter bank is built and uploaded).
         Parity is pinned to a float64 restatement of resampy's algorithm, not to the library itself."""
-        filt = RESAMPLE_TYPES.get(res_type)
-        if filt is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        filt = _filter_code(res_type)
         orig_sr, target_sr = int(orig_sr), int(target_sr)
         if orig_sr <= 0 or target_sr <= 0:
             raise ValueError("sample rates must be positive")
@@ -1317,11 +1300,9 @@ class SynthesizerTrn(nn.Module):
             raise ValueError("wave must be [B, 1, samples]")
         B, n = wave.shape[0], wave.shape[-1]
         if y_lengths is not None:
-            valid_samples = (y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
+            valid_samples = (_valid_samples(y_lengths, B, dev, "y_lengths / valid_samples") * 256).clamp(0, n)
         elif valid_samples is not None:
-            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).clamp(0, n).contiguous()
-        if valid_samples is not None and valid_samples.shape != (B,):
-            raise ValueError("y_lengths / valid_samples must be [B]")
+            valid_samples = _valid_samples(valid_samples, B, dev, "y_lengths / valid_samples").clamp(0, n)
         if orig_sr == target_sr:
             if valid_samples is None:
                 valid_samples = torch.full((B,), n, device=dev, dtype=torch.int64)
@@ -1335,10 +1316,8 @@ class SynthesizerTrn(nn.Module):
             out_samples.zero_()
             return out[..., :n_out], out_samples
         with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_resample(h, self._ptr(wave), self._ptr(valid_samples), B, n, orig_sr,
-                                                    target_sr, filt, self._ptr(out), out.shape[-1],
-                                                    self._ptr(out_samples), self._stream()),
-                        "mbv_resample")
+            self._launch(h, "mbv_resample", wave, valid_samples, B, n, orig_sr, target_sr, filt, out, out.shape[-1],
+                         out_samples)
         return out, out_samples
 
     @torch.no_grad()
@@ -1355,11 +1334,7 @@ class SynthesizerTrn(nn.Module):
                          resampled samples of the range
           out_samples    int64 [B] device: receives the row lengths `resample` returns
         Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
-        filt = RESAMPLE_TYPES.get(res_type)
-        if filt is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
-        h = self._ensure_handle()
+        filt = _filter_code(res_type)
         dev = self._device()
         if wave.dim() == 3 and wave.shape[1] == 1:
             wave = wave[:, 0]
@@ -1379,12 +1354,8 @@ class SynthesizerTrn(nn.Module):
         if int(out_first) + int(out_count) > pcm.shape[1]:
             raise ValueError("resample_pcm16_range: outputs [%d, %d) lie outside pcm [B, %d]"
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_resample_pcm16_range(
-                h, self._ptr(wave), self._ptr(valid_samples), B, n, int(orig_sr), int(target_sr), filt, int(in_avail),
-                int(out_first), int(out_count), self._ptr(peak), self._ptr(pcm), pcm.stride(0), self._ptr(running_peak),
-                self._ptr(out_samples), self._stream()),
-                "mbv_resample_pcm16_range")
+        self._call("mbv_resample_pcm16_range", wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail),
+                   int(out_first), int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
 
     @torch.no_grad()
     def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best"):
@@ -1394,10 +1365,7 @@ class SynthesizerTrn(nn.Module):
         what `resample_pcm16_range` stores for that row alone.  `packed` (int16, 1-D, device) also receives the
         chunks' samples back to back, in chunk order.  No host synchronisation (beyond the first call for a rate
         pair)."""
-        filt = RESAMPLE_TYPES.get(res_type)
-        if filt is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        filt = _filter_code(res_type)
         if not isinstance(chunks, C.Array):
             chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
         dev = self._device()
@@ -1406,11 +1374,7 @@ class SynthesizerTrn(nn.Module):
             if packed.device != dev or packed.dtype != torch.int16 or packed.dim() != 1 or packed.stride(0) != 1:
                 raise ValueError("resample_pcm16_chunks: packed must be a 1-D int16 tensor on %s with unit stride" % dev)
             cap = packed.shape[0]
-        h = self._ensure_handle()
-        with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_resample_pcm16_chunks(h, chunks, len(chunks), int(orig_sr), int(target_sr), filt,
-                                                                 self._ptr(packed), cap, self._stream()),
-                        "mbv_resample_pcm16_chunks")
+        self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
 
     @torch.no_grad()
     def resample_ranges(self, rows, orig_sr, target_sr, res_type="kaiser_best"):
@@ -1420,17 +1384,10 @@ class SynthesizerTrn(nn.Module):
         ONE launch for all rows; every stored value is bitwise what `resample` gives there for the finished recording.
         A range must end at or below `wire.resample_ready_open(orig_sr, target_sr, in_avail)` while the recording is
         open.  No host synchronisation (beyond the first call for a rate pair)."""
-        filt = RESAMPLE_TYPES.get(res_type)
-        if filt is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        filt = _filter_code(res_type)
         if not isinstance(rows, C.Array):
             rows = (_capi.MbvResampleRange * len(rows))(*rows)
-        h = self._ensure_handle()
-        with torch.cuda.device(self._device()):
-            _capi.check(h, _capi.lib().mbv_resample_ranges(h, rows, len(rows), int(orig_sr), int(target_sr), filt,
-                                                           self._stream()),
-                        "mbv_resample_ranges")
+        self._call("mbv_resample_ranges", rows, len(rows), int(orig_sr), int(target_sr), filt)
 
     def input_runs(self):
         """Launches of the live-input resampler made on this model's handle so far (`mbv_input_runs`)."""
@@ -1471,19 +1428,15 @@ class SynthesizerTrn(nn.Module):
         dev = self._device()
         wave = wave.to(device=dev).contiguous()
         if valid_samples is not None:
-            valid_samples = valid_samples.to(device=dev, dtype=torch.int64).contiguous()
-            if valid_samples.shape != (B,):
-                raise ValueError("valid_samples must be [B]")
+            valid_samples = _valid_samples(valid_samples, B, dev)
         spec = torch.empty(B, n_fft // 2 + 1, F, device=dev, dtype=torch.float32)
         spec_lengths = torch.empty(B, device=dev, dtype=torch.int64)
         if B == 0 or n == 0:
             spec_lengths.zero_()
             return spec, spec_lengths
         with torch.cuda.device(dev):
-            _capi.check(h, L.mbv_spectrogram(h, self._ptr(wave), dtype, self._ptr(valid_samples), B, n, n_fft,
-                                             hop_size, win_size, self._ptr(spec), F, self._ptr(spec_lengths),
-                                             self._stream()),
-                        "mbv_spectrogram")
+            self._launch(h, "mbv_spectrogram", wave, dtype, valid_samples, B, n, n_fft, hop_size, win_size, spec, F,
+                         spec_lengths)
         return spec, spec_lengths
 
     @torch.no_grad()
@@ -1496,16 +1449,13 @@ class SynthesizerTrn(nn.Module):
             raise IndexError("index out of range in self")       # nn.Embedding's message
         out = torch.empty(flat.numel(), self.cfg.gin_channels, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _capi.check(h, _capi.lib().mbv_speaker_embedding(h, self._ptr(flat), flat.numel(),
-                                                             self._ptr(out), self._stream()),
-                        "mbv_speaker_embedding")
+            self._launch(h, "mbv_speaker_embedding", flat, flat.numel(), out)
         return out.reshape(*sid.shape, self.cfg.gin_channels)
 
     def kernel_times_ms(self):
         """(decoder conv stack ms, fused iSTFT+PQMF launch ms) of the last infer / dec call."""
         buf = (C.c_float * 2)()
-        _capi.check(self._handle, _capi.lib().mbv_kernel_times_ms(self._handle, C.byref(buf)),
-                    "mbv_kernel_times_ms")
+        self._launch(self._handle, "mbv_kernel_times_ms", C.byref(buf), stream=False)
         return float(buf[0]), float(buf[1])
 
     def set_option(self, name, value):
@@ -1513,9 +1463,7 @@ class SynthesizerTrn(nn.Module):
         small launches), "istft_exact", "xpost_chunk_bytes", "wn_fused", "dec_streams", "tail_once", "conv_bf16" (0 / 3: opt-in split-bf16
         arithmetic in the large conv launches, see include/mbistft_vits.h).  Kept across weight refreshes; a
         handle re-created on another device starts from the defaults again."""
-        h = self._ensure_handle()
-        with torch.cuda.device(self._device()):
-            _capi.check(h, _capi.lib().mbv_set_option(h, name.encode(), int(value)), "mbv_set_option")
+        self._call("mbv_set_option", name.encode(), int(value), stream=False)
 
     def read_stage(self, name):
         """Internal stage tensor of the last call as a flat fp32 tensor (tests/debugging)."""
@@ -1557,7 +1505,6 @@ class SynthesizerTrn(nn.Module):
         Every row needs 1 <= x_lengths[b] <= y_lengths[b] (more tokens than frames have no monotone path): ValueError;
         ids / lengths / sid outside their tables: IndexError — both after the call's one host synchronisation."""
         h = self._ensure_handle()
-        L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
         dev, B, T = x.device, x.shape[0], x.shape[1]
         cfg = self.cfg
@@ -1599,9 +1546,8 @@ class SynthesizerTrn(nn.Module):
             out.w = w32.data_ptr()
             for k, v in t.items():
                 setattr(out, k, v.data_ptr())
-            _capi.check(h, L.mbv_align(h, self._ptr(x), self._ptr(x_lengths), self._ptr(y), self._ptr(y_lengths),
-                                       self._ptr(sid), B, T, Tp, self._ptr(noise), float(noise_scale), C.byref(out),
-                                       self._ptr(status), self._stream()), "mbv_align")
+            self._launch(h, "mbv_align", x, x_lengths, y, y_lengths, sid, B, T, Tp, noise, float(noise_scale), C.byref(out),
+                         status)
             w = w32.to(torch.float32).unsqueeze(1) if "w" in want else None
             flags = int(status.max())                               # the one host sync
             if flags & 1:
@@ -1638,13 +1584,9 @@ class SynthesizerTrn(nn.Module):
             y_mask = torch.empty(B, 1, T, **f32)
             z, z_p, z_hat = (torch.empty(B, I, T, **f32) for _ in range(3))
             status = torch.empty(B, dtype=torch.int32, device=dev)
-            out = _capi.MbvOutputs()
-            out.o, out.spec, out.phase = o.data_ptr(), spec.data_ptr(), phase.data_ptr()
-            out.o_mb = o_mb.data_ptr() if o_mb is not None else None
+            out = self._outputs_struct((o, o_mb, spec, phase), B)
             out.y_mask, out.z, out.z_p, out.m_p = y_mask.data_ptr(), z.data_ptr(), z_p.data_ptr(), z_hat.data_ptr()
-            _capi.check(h, _capi.lib().mbv_voice_conversion(
-                h, self._ptr(y), self._ptr(y_lengths), self._ptr(sid_src), self._ptr(sid_tgt), B, T,
-                self._ptr(noise), C.byref(out), self._ptr(status), self._stream()), "mbv_voice_conversion")
+            self._launch(h, "mbv_voice_conversion", y, y_lengths, sid_src, sid_tgt, B, T, noise, C.byref(out), status)
             if bool(status.any()):
                 raise IndexError("index out of range in self (y_lengths or speaker id)")
         return o, o_mb, y_mask, (z, z_p, z_hat)

@@ -76,6 +76,32 @@ def check_closable(arrived, sr, n_fft, hop_size):
                          % (arrived, sr, n_fft, hop_size))
 
 
+def _decode_chunks(net, work):
+    """One decoder call for `work` = [(stream, first, count), ...], each a chunk its stream is ready for: the streams
+    fill the `MbvChunk` table (`_fill_chunk`) and are told what was decoded (`_chunk_decoded`).  A member that names
+    a route length (a recording that is still growing) makes it `mbv_decode_chunks_routed`."""
+    arr = (_capi.MbvChunk * len(work))()
+    route = (C.c_int32 * len(work))()
+    for i, (st, first, count) in enumerate(work):
+        route[i] = st._fill_chunk(arr[i], first, count) or 0
+    if any(route):
+        net._call("mbv_decode_chunks_routed", arr, route, len(work))
+    else:
+        net._call("mbv_decode_chunks", arr, len(work))
+    for st, first, count in work:
+        st._chunk_decoded(first, count)
+
+
+def _convert_ranges(net, todo, hop_size, win_size):
+    """One `mbv_convert_ranges` run for `todo` = [(live stream, (a, b)), ...], the z_hat range due on each."""
+    rows = (_capi.MbvConvertRange * len(todo))()
+    for row, (st, due) in zip(rows, todo):
+        st._fill_range(row, *due)
+    net._call("mbv_convert_ranges", rows, len(todo), hop_size, win_size)
+    for st, due in todo:
+        st._plan.converted(*due)
+
+
 class LivePlan:
     """What a recording that is still arriving may convert and decode, in pure integers (no tensor, no GPU).
 
@@ -197,26 +223,14 @@ class LiveStream:
         self.noise_scale = float(noise_scale)
         if not math.isfinite(self.noise_scale) or self.noise_scale < 0:
             raise ValueError("convert_live: noise_scale must be finite and >= 0")
-        if not net.n_speakers > 0:
-            raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
-        for name, sid in (("sid_src", self.sid_src), ("sid_tgt", self.sid_tgt)):
-            if not 0 <= sid < net.n_speakers:
-                raise IndexError("index out of range in self (%s %d outside [0, %d))" % (name, sid, net.n_speakers))
-        L = _capi.lib()
-        self.n_fft = 2 * (net.cfg.spec_channels - 1)
-        if L.mbv_spectrogram_frames(1, self.n_fft, self.hop_size) < 0:
-            raise ValueError("convert_live: n_fft = 2 (spec_channels - 1) = %d must be a power of two in [256, 4096] and "
-                             "hop_size in [1, n_fft] (hop_size %d)" % (self.n_fft, self.hop_size))
-        if not 1 <= self.win_size <= self.n_fft:
-            raise ValueError("convert_live: win_size %d must be in [1, n_fft = %d]" % (self.win_size, self.n_fft))
+        self.n_fft = net._check_conversion("convert_live", self.hop_size, self.win_size)
+        net._check_speakers(self.sid_src, self.sid_tgt)
         self.max_samples = int(max_samples)
-        self.max_frames = int(L.mbv_spectrogram_frames(max(self.max_samples, 0), self.n_fft, self.hop_size))
+        self.max_frames = int(_capi.lib().mbv_spectrogram_frames(max(self.max_samples, 0), self.n_fft, self.hop_size))
         if self.max_samples < 1 or self.max_frames < 1:
             raise ValueError("convert_live: max_samples %d gives no spectrogram frame (n_fft %d, hop_size %d)"
                              % (self.max_samples, self.n_fft, self.hop_size))
-        h = net._ensure_handle()
-        if L.mbv_get_option(h, b"conv_bf16") != 0:
-            raise ValueError("convert_live is not built for the \"conv_bf16\" mode: convert with voice_conversion")
+        h = net._handle_not_bf16("convert_live", "convert with voice_conversion", why="")
         cfg = net._config_struct()
         self._plan = LivePlan(self.n_fft, self.hop_size, converter_context(cfg)[1], decoder_context(cfg)[1],
                               chunk_frames, max_chunk_frames, convert_frames)
@@ -352,23 +366,26 @@ class LiveStream:
         k.g, k.first, k.count, k.o = self.g.data_ptr(), first, count, self.o.data_ptr()
         return max(t, 257)
 
+    def _convert_due(self):
+        return self._plan.convert_due()
+
+    def _next_chunk(self):
+        return self._plan.next_chunk()
+
     def _chunk_decoded(self, first, count):
         self._plan.released(first, count)
         self._chunks.append((first, count))
         self._decoded += 1
 
+    def _drained(self):
+        return self._plan.all_released
+
     def _convert(self):
-        due = self._plan.convert_due()
+        due = self._convert_due()
         if due is None:
             return False
         self._check_handle()
-        net, L = self._net, _capi.lib()
-        rows = (_capi.MbvConvertRange * 1)()
-        self._fill_range(rows[0], *due)
-        with torch.cuda.device(self.z.device), torch.no_grad():
-            h = net._ensure_handle()
-            _capi.check(h, L.mbv_convert_ranges(h, rows, 1, self.hop_size, self.win_size, net._stream()), "mbv_convert_ranges")
-        self._plan.converted(*due)
+        _convert_ranges(self._net, [(self, due)], self.hop_size, self.win_size)
         return True
 
     def poll(self):
@@ -378,17 +395,7 @@ class LiveStream:
         todo = self._plan.decodable()
         if todo:
             self._check_handle()
-            net = self._net
-            arr = (_capi.MbvChunk * len(todo))()
-            route = (C.c_int32 * len(todo))()
-            for i, (first, count) in enumerate(todo):
-                route[i] = self._fill_chunk(arr[i], first, count)
-            with torch.cuda.device(self.z.device), torch.no_grad():
-                h = net._ensure_handle()
-                _capi.check(h, _capi.lib().mbv_decode_chunks_routed(h, arr, route, len(todo), net._stream()),
-                            "mbv_decode_chunks_routed")
-            for first, count in todo:
-                self._chunk_decoded(first, count)
+            _decode_chunks(self._net, [(self, first, count) for first, count in todo])
         out = []
         while self._next < self._decoded:
             first, count = self._chunks[self._next]
@@ -445,11 +452,9 @@ class DecodeStream:
         if net._handle is not h:
             raise RuntimeError("the model's handle was re-created (device move) since this stream started")
         B, _, Tp = self.z.shape
-        with torch.cuda.device(self.z.device), torch.no_grad():
+        with torch.cuda.device(self.z.device):
             net._ensure_handle()                  # (re-uploads weights edited in place, as every entry does)
-            _capi.check(h, _capi.lib().mbv_decode_range(h, net._ptr(self.z), net._ptr(self.g), B, Tp, first, count,
-                                                        net._ptr(self.o), self.o.stride(0), net._stream()),
-                        "mbv_decode_range")
+            net._launch(h, "mbv_decode_range", self.z, self.g, B, Tp, first, count, self.o, self.o.stride(0))
         self._next += 1
         self._decoded = self._next
         return a, self.o[:, :, a:b]
@@ -459,6 +464,25 @@ class DecodeStream:
         for _ in self:
             pass
         return self.o
+
+    # ---- what a pool shares (StreamPool.step), as `LiveStream` has it
+    def _convert_due(self):
+        return None                   # z is whole
+
+    def _next_chunk(self):
+        return self.schedule[self._decoded] if self._decoded < len(self.schedule) else None
+
+    def _fill_chunk(self, k, first, count):
+        """-> None: a finished utterance is decoded in the class of its own length."""
+        k.z, k.z_stride, k.t_frames = self.z.data_ptr(), self.z.stride(1), self.z.shape[2]
+        k.g = self.g.data_ptr() if self.g is not None else None
+        k.first, k.count, k.o = first, count, self.o.data_ptr()
+
+    def _chunk_decoded(self, first, count):
+        self._decoded += 1
+
+    def _drained(self):
+        return self._decoded >= len(self.schedule)
 
 
 class StreamPool:
@@ -514,22 +538,15 @@ class StreamPool:
             self.add(st)
         return sts
 
-    @staticmethod
-    def _done(st):
-        if isinstance(st, LiveStream):
-            return st._plan.all_released
-        return st._decoded >= len(st.schedule)
-
     def _convert_live(self, members):
         """The pending z_hat windows of every live member in one `mbv_convert_ranges` run per run of the planner."""
-        net, L = self._net, _capi.lib()
         by_cfg = {}
         for st in members:
-            if isinstance(st, LiveStream):
-                due = st._plan.convert_due()
-                if due is not None:
-                    st._check_handle()
-                    by_cfg.setdefault((st.hop_size, st.win_size), []).append((st, due))
+            due = st._convert_due()
+            if due is not None:
+                st._check_handle()
+                by_cfg.setdefault((st.hop_size, st.win_size), []).append((st, due))
+        net, L = self._net, _capi.lib()
         for (hop, win), todo in by_cfg.items():
             n = len(todo)
             wl = (C.c_int32 * n)(*[st._window_frames(*due) for st, due in todo])
@@ -538,15 +555,7 @@ class StreamPool:
             if n_runs < 1:
                 raise ValueError("mbv_convert_ranges_plan refused the windows (one beyond the fused WN layers?)")
             for r in range(n_runs):
-                part = [t for t, k in zip(todo, run_of) if k == r]
-                rows = (_capi.MbvConvertRange * len(part))()
-                for row, (st, due) in zip(rows, part):
-                    st._fill_range(row, *due)
-                with torch.cuda.device(net._device()), torch.no_grad():
-                    h = net._ensure_handle()
-                    _capi.check(h, L.mbv_convert_ranges(h, rows, len(part), hop, win, net._stream()), "mbv_convert_ranges")
-                for st, due in part:
-                    st._plan.converted(*due)
+                _convert_ranges(net, [t for t, k in zip(todo, run_of) if k == r], hop, win)
 
     def step(self, streams=None):
         """Live members first convert their pending windows together (`_convert_live`); then at most one chunk per
@@ -558,50 +567,21 @@ class StreamPool:
             for st in members:
                 if not any(st is m for m in self.streams):
                     raise ValueError("step(streams=...) names a stream that is not in the pool")
-        self.streams = [st for st in self.streams if not self._done(st)]
-        members = [st for st in members if not self._done(st)]
+        self.streams = [st for st in self.streams if not st._drained()]
+        members = [st for st in members if not st._drained()]
         if not members:
             return []
         net = self._net
-        any_live = any(isinstance(st, LiveStream) for st in members)
-        if any_live:
-            self._convert_live(members)
+        self._convert_live(members)
         work = []                     # (stream, first, count)
         for st in members:
             if net._handle is not st._h:
                 raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
-            if isinstance(st, LiveStream):
-                nxt = st._plan.next_chunk()
-                if nxt is not None:
-                    work.append((st,) + nxt)
-            else:
-                work.append((st,) + st.schedule[st._decoded])
+            nxt = st._next_chunk()
+            if nxt is not None:
+                work.append((st,) + nxt)
         if not work:
             return []
-        arr = (_capi.MbvChunk * len(work))()
-        route = (C.c_int32 * len(work))()
-        out = []
-        for i, (st, first, count) in enumerate(work):
-            k = arr[i]
-            if isinstance(st, LiveStream):
-                route[i] = st._fill_chunk(k, first, count)
-            else:
-                k.z, k.z_stride, k.t_frames = st.z.data_ptr(), st.z.stride(1), st.z.shape[2]
-                k.g = st.g.data_ptr() if st.g is not None else None
-                k.first, k.count, k.o = first, count, st.o.data_ptr()
-            out.append((st, st.spf * first, st.o[:, :, st.spf * first:st.spf * (first + count)]))
-        dev = net._device()
-        with torch.cuda.device(dev), torch.no_grad():
-            h = net._ensure_handle()
-            if any_live:
-                _capi.check(h, _capi.lib().mbv_decode_chunks_routed(h, arr, route, len(work), net._stream()),
-                            "mbv_decode_chunks_routed")
-            else:
-                _capi.check(h, _capi.lib().mbv_decode_chunks(h, arr, len(work), net._stream()), "mbv_decode_chunks")
-        for st, first, count in work:
-            if isinstance(st, LiveStream):
-                st._chunk_decoded(first, count)
-            else:
-                st._decoded += 1
-        self.streams = [st for st in self.streams if not self._done(st)]
-        return out
+        _decode_chunks(net, work)
+        self.streams = [st for st in self.streams if not st._drained()]
+        return [(st, st.spf * first, st.o[:, :, st.spf * first:st.spf * (first + count)]) for st, first, count in work]

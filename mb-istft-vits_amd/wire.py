@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .models import RESAMPLE_TYPES
+from .models import RESAMPLE_TYPES, _filter_code      # noqa: F401  (RESAMPLE_TYPES stays a name of this module)
 
 
 def chunk_size(rate, frame_length=0.02):
@@ -107,10 +107,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
     """How many resampled samples of a row of `in_total` input samples are final once its first `in_avail`
     exist (`mbv_resample_ready`, host only: no GPU needed); ceil(in_total * target / orig) once all do."""
-    filt = RESAMPLE_TYPES.get(res_type)
-    if filt is None:
-        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    filt = _filter_code(res_type)
     L = _capi.lib()
     r = L.mbv_resample_ready(int(orig_sr), int(target_sr), filt, int(in_avail), int(in_total))
     if r < 0:
@@ -123,10 +120,7 @@ def resample_ready_open(orig_sr, target_sr, in_avail, res_type="kaiser_best"):
     """How many resampled samples of a row that is still OPEN are final once its first `in_avail` samples exist
     (`mbv_resample_ready_open`, host only: no GPU needed): those no tap of which lies at or past `in_avail`.  The
     count does not depend on the length the row will have."""
-    filt = RESAMPLE_TYPES.get(res_type)
-    if filt is None:
-        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    filt = _filter_code(res_type)
     L = _capi.lib()
     r = L.mbv_resample_ready_open(int(orig_sr), int(target_sr), filt, int(in_avail))
     if r < 0:
@@ -142,6 +136,38 @@ def _refuse_live(st):
                         "valid_samples need the recording's total length, which an open stream does not have. "
                         "wire.convert_live_pcm16 / PcmPool.add_live wire a live stream; or take the float chunks "
                         "from poll(), or convert the finished recording with convert_stream")
+
+
+def _peak_arg(peak, B, dev, shape="B"):
+    """`peak=` of a wire stream -> None (no normalisation) or a contiguous fp32 [B] device tensor."""
+    if peak is None:
+        return None
+    if not torch.is_tensor(peak):
+        peak = torch.full((B,), float(peak), device=dev, dtype=torch.float32)   # a fill, not a host copy
+    peak = peak.to(device=dev, dtype=torch.float32).contiguous()
+    if peak.shape != (B,):
+        raise ValueError("peak must be a float or an fp32 [%s] tensor" % shape)
+    return peak
+
+
+# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in):
+# from the first `in_avail` samples of `wave` [B, n] to the int16 samples [out_first, out_first + out_count); `lengths`:
+# this step also writes `valid_samples`.  Alone it is one `mbv_resample_pcm16_range` launch, in a pool one row of the
+# `mbv_resample_pcm16_chunks` table.
+def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
+    w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
+                                valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
+                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type)
+
+
+def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
+    k.wave, k.in_total = wave.data_ptr(), wave.shape[1]
+    k.valid_samples = w._valid_in.data_ptr() if w._valid_in is not None else None
+    k.in_avail, k.out_first, k.out_count = in_avail, out_first, out_count
+    k.peak = w._peak_in.data_ptr() if w._peak_in is not None else None
+    k.pcm, k.pcm_capacity = w.pcm.data_ptr(), w.pcm.shape[1]
+    k.running_peak = w.peak.data_ptr()
+    k.out_samples = w.valid_samples.data_ptr() if lengths else None
 
 
 class PcmStream:
@@ -181,13 +207,7 @@ class PcmStream:
         self._valid_in = None                     # valid input samples, as service_pcm16 counts them
         if st.y_lengths is not None:
             self._valid_in = (st.y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
-        if peak is not None:
-            if not torch.is_tensor(peak):
-                peak = torch.full((B,), float(peak), device=dev, dtype=torch.float32)   # a fill, not a host copy
-            peak = peak.to(device=dev, dtype=torch.float32).contiguous()
-            if peak.shape != (B,):
-                raise ValueError("peak must be a float or an fp32 [B] tensor")
-        self._peak_in = peak
+        self._peak_in = _peak_arg(peak, B, dev)
         self._done = 0                            # outputs emitted so far
         self._wired = 0                           # the first chunk whose final outputs are not emitted yet
 
@@ -203,17 +223,32 @@ class PcmStream:
         next(st)                                  # decodes chunk i (StopIteration ends this stream too)
         if net._handle is not self._h:
             raise RuntimeError("the model's handle was re-created (device move) since this stream started")
-        first, count = st.schedule[i]
         if i < self._wired:                       # a pool wired it already, on the stream current at its step
             a, b = (self._ready[i - 1] if i else 0), self._ready[i]
             return a, self.pcm[:, a:b]
         a, b = self._done, self._ready[i]
-        net.resample_pcm16_range(st.o, self.model_sr, self.rate, st.spf * (first + count), a, b - a, self.pcm,
-                                 valid_samples=self._valid_in, peak=self._peak_in, running_peak=self.peak,
-                                 out_samples=self.valid_samples if self._wired == 0 else None,
-                                 res_type=self.res_type)
+        _wire_alone(self, *self._step_through(i))
         self._done, self._wired = b, i + 1
         return a, self.pcm[:, a:b]
+
+    def _step_through(self, i):
+        """The wire step that takes in the decoded chunks up to chunk i."""
+        first, count = self._st.schedule[i]
+        return self._st.o[:, 0], self._st.spf * (first + count), self._done, self._ready[i] - self._done, self._wired == 0
+
+    # ---- what a pool shares (PcmPool.step), as `LiveWire` has it
+    def _wire_chunk(self, k):
+        """Fills the `_capi.MbvPcmChunk` `k` with the wire step due now; -> (final, pieces), or None."""
+        i = self._st._decoded - 1
+        if i < self._wired:
+            return None
+        if self._net._handle is not self._h:
+            raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
+        _wire_row(self, k, *self._step_through(i))
+        return i + 1 == len(self._st.schedule), [(self._done, self._ready[i])]
+
+    def _chunk_wired(self, final, pieces):
+        self._done, self._wired = pieces[-1][1], self._st._decoded
 
     def run(self):
         """Every remaining chunk; -> (pcm, valid_samples)."""
@@ -239,10 +274,7 @@ def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
     """(total, packed_first) of `mbv_pcm_chunks_plan` for `_capi.MbvPcmChunk`s (host only: no GPU needed, only the
     integer fields are read): the checks `resample_pcm16_chunks` makes, and where every chunk starts in the packed
     buffer.  Raises `_capi.MbvError` naming the offending chunk."""
-    filt = RESAMPLE_TYPES.get(res_type)
-    if filt is None:
-        raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                         % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+    filt = _filter_code(res_type)
     if not isinstance(chunks, C.Array):
         chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
     n = len(chunks)
@@ -410,9 +442,7 @@ class LiveWire:
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                  chunk_frames=32, max_chunk_frames=256, convert_frames=32):
         from .stream import LiveStream
-        if RESAMPLE_TYPES.get(res_type) is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        _filter_code(res_type)
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("convert_live_pcm16: dtype must be int16 or float32, got %s" % dtype)
         self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
@@ -444,13 +474,7 @@ class LiveWire:
             self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
             # valid input samples of the wire step: the capacity of o while the total is unknown
             self._valid_in = torch.full((1,), self._plan.o_capacity, device=dev, dtype=torch.int64)
-            if peak is not None:
-                if not torch.is_tensor(peak):
-                    peak = torch.full((1,), float(peak), device=dev, dtype=torch.float32)
-                peak = peak.to(device=dev, dtype=torch.float32).contiguous()
-                if peak.shape != (1,):
-                    raise ValueError("peak must be a float or an fp32 [1] tensor")
-            self._peak_in = peak
+            self._peak_in = _peak_arg(peak, 1, dev, shape="1")
         self._pieces = []             # (a, b) of every piece wired so far, in order
         self._handed = 0              # the piece poll() hands out next
 
@@ -518,45 +542,36 @@ class LiveWire:
         self.live.fed(n, last=self._plan.fed(n))
 
     def _wire_due(self):
-        """-> `LiveWirePlan.wire_due` of the chunks decoded so far; with the last chunk the valid input samples become
-        256 T, as `service_pcm16` counts them (a device fill)."""
+        """-> None, or ((the arguments of the wire step due now), final, pieces) from `LiveWirePlan.wire_due` of the
+        chunks decoded so far; with the last chunk the valid input samples become 256 T, as `service_pcm16` counts them
+        (a device fill)."""
         w = self._plan.wire_due(self.live.chunks)
         if w is None:
             return None
         self.live.check_handle()
-        if w[4]:
+        in_avail, in_total, out_first, out_count, final, pieces = w
+        if final:
             with torch.cuda.device(self.pcm.device):
-                self._valid_in.fill_(min(256 * self.live.frames, w[1]))
-        return w
+                self._valid_in.fill_(min(256 * self.live.frames, in_total))
+        return (self.live.o[:, 0, :in_total], in_avail, out_first, out_count, final), final, pieces
 
     def _wire_chunk(self, k):
         """Fills the `_capi.MbvPcmChunk` `k` with the wire step due now; -> (final, pieces), or None."""
         w = self._wire_due()
         if w is None:
             return None
-        in_avail, in_total, out_first, out_count, final, pieces = w
-        k.wave, k.in_total, k.valid_samples = self.live.o.data_ptr(), in_total, self._valid_in.data_ptr()
-        k.in_avail, k.out_first, k.out_count = in_avail, out_first, out_count
-        k.peak = self._peak_in.data_ptr() if self._peak_in is not None else None
-        k.pcm, k.pcm_capacity = self.pcm.data_ptr(), self._plan.pcm_capacity
-        k.running_peak = self.peak.data_ptr()
-        k.out_samples = self.valid_samples.data_ptr() if final else None
-        return final, pieces
+        _wire_row(self, k, *w[0])
+        return w[1:]
 
-    def _wired(self, final, pieces):
+    def _chunk_wired(self, final, pieces):
         self._pieces.extend(pieces)
         self._plan.wired(len(self.live.chunks), pieces[-1][1], final)
 
     def _wire(self):
         w = self._wire_due()
-        if w is None:
-            return
-        in_avail, in_total, out_first, out_count, final, pieces = w
-        self._net.resample_pcm16_range(self.live.o[:, 0, :in_total], self.model_sr, self.rate, in_avail, out_first,
-                                       out_count, self.pcm, valid_samples=self._valid_in, peak=self._peak_in,
-                                       running_peak=self.peak, out_samples=self.valid_samples if final else None,
-                                       res_type=self.res_type)
-        self._wired(final, pieces)
+        if w is not None:
+            _wire_alone(self, *w[0])
+            self._chunk_wired(*w[1:])
 
     def poll(self):
         """-> [(first_out_sample, int16 view of pcm[0, a:b]), ...]: every piece not handed out yet, one per decoded
@@ -593,9 +608,7 @@ class PcmPool:
     `service_pcm16` gives for the finished waveform.  Finished streams drop out."""
 
     def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best"):
-        if RESAMPLE_TYPES.get(res_type) is None:
-            raise ValueError("res_type %r is not supported on the GPU path (supported: %s)"
-                             % (res_type, ", ".join(sorted(RESAMPLE_TYPES))))
+        _filter_code(res_type)
         if pool._net is not net:
             raise ValueError("the stream pool belongs to another model")
         self._net, self.pool = net, pool
@@ -690,36 +703,18 @@ class PcmPool:
             self._feed_lives(lives)
         named = None
         if streams is not None:
-            named = [f._st for f in members if f._st._decoded < len(f._st.schedule)]
-            named += [lw.live for lw in lives if not lw.live.all_decoded]
+            named = [st for st in [f._st for f in members] + [lw.live for lw in lives] if not st._drained()]
         if named is None or named:
             self.pool.step(named)
-        todo = [f for f in members if f._st._decoded > f._wired]
-        arr = (_capi.MbvPcmChunk * (len(todo) + len(lives)))()
-        rows = []                                 # (stream, its pcm, [(a, b), ...]) per table row
-        for k, f in zip(arr, todo):
-            st = f._st
-            if net._handle is not f._h:
-                raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
-            first, count = st.schedule[st._decoded - 1]
-            a, b = f._done, f._ready[st._decoded - 1]
-            k.wave, k.in_total = st.o.data_ptr(), st.o.shape[-1]
-            k.valid_samples = f._valid_in.data_ptr() if f._valid_in is not None else None
-            k.in_avail, k.out_first, k.out_count = st.spf * (first + count), a, b - a
-            k.peak = f._peak_in.data_ptr() if f._peak_in is not None else None
-            k.pcm, k.pcm_capacity = f.pcm.data_ptr(), f.out_stride
-            k.running_peak = f.peak.data_ptr()
-            k.out_samples = f.valid_samples.data_ptr() if f._wired == 0 else None
-            rows.append((st, f.pcm, [(a, b)]))
-        live_done = []
-        for lw in lives:
-            w = lw._wire_chunk(arr[len(rows)])
-            if w is not None:
-                rows.append((lw, lw.pcm, w[1]))
-                live_done.append((lw, w))
+        rows = []                                 # (stream, member, its table row, (final, [(a, b), ...])) per row
+        for w, st in [(f, f._st) for f in members] + [(lw, lw) for lw in lives]:
+            k = _capi.MbvPcmChunk()
+            due = w._wire_chunk(k)
+            if due is not None:
+                rows.append((st, w, k, due))
         out = []
         if rows:
-            arr = (_capi.MbvPcmChunk * len(rows))(*arr[:len(rows)])
+            arr = (_capi.MbvPcmChunk * len(rows))(*[k for _, _, k, _ in rows])
             dev = net._device()
             packed = None
             if host:
@@ -732,22 +727,20 @@ class PcmPool:
                     self._event = torch.cuda.Event()
                 packed = self._packed
             net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type)
-            for f in todo:
-                f._done, f._wired = f._ready[f._st._decoded - 1], f._st._decoded
-            for lw, w in live_done:
-                lw._wired(*w)
+            for _, w, _, due in rows:
+                w._chunk_wired(*due)
             if host:
                 if total:
                     with torch.cuda.device(dev):
                         self._host[:total].copy_(packed[:total], non_blocking=True)
                         self._event.record(torch.cuda.current_stream(dev))
                         self._event.synchronize()
-                for (st, _, pieces), o in zip(rows, offs):
+                for (st, _, _, (_, pieces)), o in zip(rows, offs):
                     first = pieces[0][0]
                     out += [(st, a, self._host_np[o + a - first:o + b - first]) for a, b in pieces]
             else:
-                for st, pcm, pieces in rows:
-                    out += [(st, a, pcm[0, a:b]) for a, b in pieces]
+                for st, w, _, (_, pieces) in rows:
+                    out += [(st, a, w.pcm[0, a:b]) for a, b in pieces]
         self.followers = [f for f in self.followers if f._wired < len(f._st.schedule)]
         self.lives = [lw for lw in self.lives if not lw._plan.wire_done]
         return out

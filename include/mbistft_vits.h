@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 #define MBV_ABI_VERSION 3   /* 3 (r03): + arena export / import, call tickets, option "trim", mbv_op_rel_attention; structs unchanged
-                             * (later additions are new entry points; the test-only mbv_conv_desc grew at its end) */
+                             * (later additions are new entry points, mbv_randn_blocks / mbv_randn_host / mbv_noise_runs
+                             * among them; the test-only mbv_conv_desc grew at its end) */
 
 #define MBV_DEC_MULTIBAND   0   /* models.py:309 Multiband_iSTFT_Generator (fixed PQMF)        */
 #define MBV_DEC_MULTISTREAM 1   /* models.py:387 Multistream_iSTFT_Generator (trainable filter)*/
@@ -637,6 +638,49 @@ int64_t mbv_resample_ready_open(int orig_sr, int target_sr, int filter, int64_t 
 int mbv_resample_ranges(mbv_model *m, const mbv_resample_range *rows_host, int n, int orig_sr, int target_sr,
                         int filter, void *stream);
 int64_t mbv_input_runs(mbv_model *m);
+
+/* ---- seeded noise: standard normals as a pure function of (seed, purpose, row, channel, frame) ---------------
+ * Every entry above that takes `noise` / `noise_w` reads a device buffer the caller fills.  These entries fill such
+ * buffers from a counter-based generator, so that a request's noise depends on its seed alone: not on a global
+ * generator, the requests before it, its place in a batch, padding, chunking or how a recording was pushed.  The
+ * consumers are unchanged and keep every bitwise relation they have.  The generator is part of the contract:
+ *   Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85
+ *   key      (seed & 0xffffffff, seed >> 32)
+ *   counter  (t >> 2, c, purpose, row): t the frame, c the channel, purpose MBV_NOISE_*, row a sub-stream index
+ *   the output words w0..w3 give the normals of frames 4 (t >> 2) + 0..3 of channel c: (w0, w1) -> (n0, n1) and
+ *   (w2, w3) -> (n2, n3) by Box-Muller in fp32, u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24,
+ *   r = sqrtf(-2 logf(u1)), n_even = r cos(2 pi u2), n_odd = r sin(2 pi u2) (sincospif(2 u2); accurate libm only)
+ * Element (c, t) is lane t & 3 of block t >> 2 ALWAYS, also when a fill starts or ends inside a block: a fill of
+ * [first, first + count) is bitwise the slice of a fill of [0, first + count).
+ * Known answer: counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ *
+ * mbv_randn_blocks fills the n blocks of a table in ONE launch: dst[c * stride + (t - first)] for c < channels and
+ * t in [first, first + count); nothing else is written.  blocks_host is HOST memory [n] and travels as kernel
+ * arguments like the other row tables (it may be freed when the call returns); no copy, no synchronisation.
+ * Refused before any launch, with a message that names the block: n < 1, a null dst with count > 0, stride < count,
+ * channels < 1, first < 0, count < 0, first + count > 2^30 (the frame limit of an utterance), purpose > 2.  A block
+ * with count 0 is legal and writes nothing; a call whose blocks are all empty launches and counts nothing.
+ *
+ * mbv_randn_host computes frames [first, first + count) of one channel on the host with the same Philox function and
+ * logf / sqrtf / sinf / cosf in fp32: no GPU, no handle.  Host and device libm differ in the last bits, so the two
+ * agree within 1e-5 absolute (measured: DESIGN 7.13), not bitwise.  Returns 1 for the arguments mbv_randn_blocks
+ * refuses.
+ *
+ * mbv_noise_runs: mbv_randn_blocks launches on this handle since mbv_create (table writers are not counted). */
+#define MBV_NOISE_PRIOR     0   /* models.py:729  z_p = m_p + noise * exp(logs_p) * noise_scale: [inter, T']      */
+#define MBV_NOISE_SDP       1   /* models.py:94   the duration predictor's draw: [2, T_text]                      */
+#define MBV_NOISE_POSTERIOR 2   /* models.py:245  z = m + noise * exp(logs): [inter, T_spec]                      */
+typedef struct mbv_randn_block {
+  float *dst;                 /* DEVICE; row c of the block starts at dst + c * stride */
+  int64_t stride;             /* floats between channel rows, >= count */
+  int32_t channels, reserved;
+  int64_t first, count;       /* frames [first, first + count) */
+  uint64_t seed;
+  uint32_t purpose, row;      /* MBV_NOISE_*, sub-stream index */
+} mbv_randn_block;
+int mbv_randn_blocks(mbv_model *m, const mbv_randn_block *blocks_host, int n, void *stream);
+int mbv_randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, int64_t first, int64_t count, float *dst);
+int64_t mbv_noise_runs(mbv_model *m);
 
 /* ---- linear spectrogram ------------------------------------------------------
  * replaces spectrogram_torch(y, n_fft, sr, hop, win, center=False) (mel_processing.py:51-70), the input of

@@ -35,6 +35,7 @@ SYMBOLS = [
     "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
     "mbv_convert_ranges_plan", "mbv_convert_ranges",
     "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
+    "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
 ]
 
 
@@ -103,6 +104,17 @@ class MbvResampleRange(C.Structure):
     """mbv_resample_range of include/mbistft_vits.h (mbv_resample_ranges)."""
     _fields_ = [("wave", C.c_void_p), ("wave_dtype", C.c_int32), ("in_avail", C.c_int64), ("in_total", C.c_int64),
                 ("out_first", C.c_int64), ("out_count", C.c_int64), ("out", C.c_void_p), ("out_capacity", C.c_int64)]
+
+
+class MbvRandnBlock(C.Structure):
+    """mbv_randn_block of include/mbistft_vits.h (mbv_randn_blocks)."""
+    _fields_ = [("dst", C.c_void_p), ("stride", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32),
+                ("first", C.c_int64), ("count", C.c_int64), ("seed", C.c_uint64), ("purpose", C.c_uint32),
+                ("row", C.c_uint32)]
+
+
+# MBV_NOISE_* of include/mbistft_vits.h: the `purpose` word of the generator's counter
+NOISE_PRIOR, NOISE_SDP, NOISE_POSTERIOR = 0, 1, 2
 
 
 class MbvAlignOutputs(C.Structure):
@@ -229,8 +241,8 @@ def lib():
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
-    # three that came with "tail_once", pooled conversion's three, live conversion's six and the live wire's three may
-    # be absent there, and calling one then raises AttributeError.
+    # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three and
+    # the seeded noise's three may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -240,7 +252,8 @@ def lib():
                 "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
                 "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
                 "mbv_convert_ranges_plan", "mbv_convert_ranges",
-                "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
+                "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -288,6 +301,11 @@ def lib():
         L.mbv_resample_ranges.argtypes = [vp, C.POINTER(MbvResampleRange), i32, i32, i32, i32, vp]
         L.mbv_input_runs.argtypes = [vp]
         L.mbv_input_runs.restype = C.c_int64
+    if hasattr(L, "mbv_randn_blocks") or not optional:
+        L.mbv_randn_blocks.argtypes = [vp, C.POINTER(MbvRandnBlock), i32, vp]
+        L.mbv_randn_host.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, vp]
+        L.mbv_noise_runs.argtypes = [vp]
+        L.mbv_noise_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -122,6 +122,9 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
+  int64_t noise_runs = 0;          // mbv_randn_blocks launches (mbv_noise_runs)
+  char* noise_tab = nullptr; size_t noise_tab_bytes = 0;   // mbv_randn_blocks' table: its own buffer, so that a fill
+                                                           // between an encode and its synthesize disturbs no scratch
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
@@ -2018,6 +2021,7 @@ void mbv_destroy(mbv_model* m) {
   if (m->tail_cnt) (void)hipFree(m->tail_cnt);
   if (m->scrA) (void)hipFree(m->scrA);
   if (m->scrB) (void)hipFree(m->scrB);
+  if (m->noise_tab) (void)hipFree(m->noise_tab);
   for (auto& sl : m->slots)
     if (sl.scr) (void)hipFree(sl.scr);
   if (m->user_tab) (void)hipFree(m->user_tab);
@@ -3470,6 +3474,62 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
 }
 
 int64_t mbv_input_runs(mbv_model* m) { return m ? m->input_runs : -1; }
+
+namespace {
+// what mbv_randn_blocks and mbv_randn_host refuse about one block's range and purpose, or null
+const char* randn_range_error(int64_t first, int64_t count, uint32_t purpose) {
+  if (first < 0 || count < 0) return "first and count must be >= 0";
+  if (first > (int64_t(1) << 30) || count > (int64_t(1) << 30) - first) return "first + count exceeds 2^30 frames";
+  if (purpose > MBV_NOISE_POSTERIOR) return "unknown purpose (MBV_NOISE_PRIOR 0, MBV_NOISE_SDP 1, MBV_NOISE_POSTERIOR 2)";
+  return nullptr;
+}
+}  // namespace
+
+int mbv_randn_blocks(mbv_model* m, const mbv_randn_block* blocks_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_randn_blocks";
+  if (n < 1 || !blocks_host) return m->fail("%s: bad arguments (n >= 1 blocks expected)", who);
+  DEVICE_GUARD(m);
+  std::vector<RandnRow> live;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_randn_block& k = blocks_host[i];
+    if (const char* e = randn_range_error(k.first, k.count, k.purpose)) return m->fail("%s: block %d: %s", who, i, e);
+    if (k.channels < 1) return m->fail("%s: block %d: channels must be >= 1", who, i);
+    if (k.stride < k.count) return m->fail("%s: block %d: stride %lld < count %lld", who, i, (long long)k.stride, (long long)k.count);
+    if (!k.dst && k.count > 0) return m->fail("%s: block %d: dst missing", who, i);
+    if (k.count == 0) continue;
+    const int64_t quads = ((k.first + k.count + 3) >> 2) - (k.first >> 2);
+    live.push_back(RandnRow{k.dst, k.stride, total, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.purpose, k.row,
+                            (int32_t)k.first, (int32_t)k.count, (int32_t)quads, 0});
+    total += quads * k.channels;             // < 2^28 * 2^31 a block
+    if ((total + 255) / 256 > 0x7fffffff) return m->fail("%s: more work than one grid holds (block %d)", who, i);
+  }
+  if (live.empty()) return 0;
+  if (ensure(m, &m->noise_tab, &m->noise_tab_bytes, live.size() * sizeof(RandnRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  RandnRow* rows = reinterpret_cast<RandnRow*>(m->noise_tab);
+  upload_rows<kRandnChunk>(live.size(), rows, s, [&](size_t i) { return live[i]; });
+  ++m->noise_runs;
+  launch_randn_blocks(rows, (int)live.size(), total, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, int64_t first, int64_t count, float* dst) {
+  if (const char* e = randn_range_error(first, count, purpose)) {
+    g_create_error = std::string("mbv_randn_host: ") + e;
+    return 1;
+  }
+  if (!dst && count > 0) {
+    g_create_error = "mbv_randn_host: dst missing";
+    return 1;
+  }
+  randn_host(seed, purpose, row, c, first, count, dst);
+  return 0;
+}
+
+int64_t mbv_noise_runs(mbv_model* m) { return m ? m->noise_runs : -1; }
 
 namespace {
 const char* spectrogram_args_error(int n_fft, int hop, int win) {

@@ -561,4 +561,20 @@ void launch_gather_windows(const PoolRow* rows, int n, int C, int T, float* dst,
 // which column-tile width launch_conv1d will use for this conv (128 or 384; 0: a kernel without trim support)
 int conv1d_trim_bn(const ConvArgs& a);
 
+// ---------------------------------------------------------------- seeded noise (rng.hip, philox.h)
+// One table row = one block of mbv_randn_blocks that has frames: dst[c stride + (t - first)] for c < channels,
+// t in [first, first + count).  `quads` = the Philox blocks (four frames each) that hold one of those frames,
+// `begin` = the prefix sum of channels * quads over the rows before it: the launch's grid runs over that sum.
+struct RandnRow {
+  float* dst;
+  int64_t stride, begin;
+  uint32_t seed_lo, seed_hi, purpose, row;
+  int32_t first, count, quads, reserved;
+};
+constexpr int kRandnChunk = 64;     // rows per upload_rows launch: 3.5 KiB of kernel arguments
+// every row of the table (in the arena: upload_rows) in one launch; total = the work items of all rows, > 0
+void launch_randn_blocks(const RandnRow* rows, int n, int64_t total, hipStream_t s);
+// the same values on the host (fp32 logf / sqrtf / sinf / cosf): frames [first, first + count) of channel c
+void randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, int64_t first, int64_t count, float* dst);
+
 }  // namespace mbv

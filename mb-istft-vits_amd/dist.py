@@ -168,7 +168,7 @@ def gather_waveforms(o_local, ylen_local, shard_sizes, timing=None):
 
 
 def sharded_infer(net, x, x_lengths, sid=None, noise_scale=1, length_scale=1, max_len=None,
-                  noise_scale_w=1., outputs=("o",), overlap=None, timing=None):
+                  noise_scale_w=1., outputs=("o",), overlap=None, timing=None, seed=None):
     """Every rank passes the SAME full batch; each synthesises its contiguous block and all ranks
     return the full-batch waveform [B, 1, 256 T'max] and y_lengths [B].
 
@@ -181,7 +181,9 @@ def sharded_infer(net, x, x_lengths, sid=None, noise_scale=1, length_scale=1, ma
     advances as in a single-process run), and with a StochasticDurationPredictor each
     rank draws the full-batch duration noise on the CPU generator (models.py:94) and uses its
     block — so ranks that are seeded alike (torch.manual_seed) reproduce the single-process draws;
-    ranks seeded differently produce valid but different samples.
+    ranks seeded differently produce valid but different samples.  With `seed=` (as `infer` takes it, for the
+    full batch) none of that is needed: a rank fills only its own rows from the seeded generator with
+    row = the global row index, which is what `infer(x, ..., seed=seed)` draws for them; no generator is touched.
 
     overlap (GPU, any backend):
       None     gathers on the caller's stream after the shard's last kernel; returns (o, y_lengths).
@@ -203,7 +205,10 @@ def sharded_infer(net, x, x_lengths, sid=None, noise_scale=1, length_scale=1, ma
     sizes = [shard_bounds(B, world, r)[1] - shard_bounds(B, world, r)[0] for r in range(world)]
     lo, hi = shard_bounds(B, world, rank)
     extra = {}
-    if getattr(net.cfg, "use_sdp", False):
+    if seed is not None:
+        from .models import RowSeeds, _row_seeds
+        extra = dict(noise_scale_w=noise_scale_w, seed=RowSeeds(_row_seeds(seed, B)[lo:hi]))
+    elif getattr(net.cfg, "use_sdp", False):
         extra = dict(noise_scale_w=noise_scale_w, noise_w=torch.randn(B, 2, x.shape[1])[lo:hi])
     if timing is not None:
         timing.world = world

@@ -55,6 +55,40 @@ def _durations_code(durations):
     return durations.to(torch.int64), 1
 
 
+def _seed_value(v, what="seed"):
+    """One seed of the device generator -> int in [0, 2^64).  TypeError for anything that is not an
+    integer (bool and floats included), ValueError outside the range."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s must be an integer in [0, 2^64), got %s" % (what, type(v).__name__))
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError("%s must be in [0, 2^64), got %d" % (what, v))
+    return v
+
+
+class RowSeeds(list):
+    """(seed, row) of every row of a batched call, checked: what `_row_seeds` returns."""
+
+
+def _row_seeds(seed, B, what="seed"):
+    """`seed=` of a batched entry -> RowSeeds [(seed_b, row_b)] * B, or None for None: an int s gives row b the
+    sub-stream (s, row=b); a length-B sequence or integer tensor gives row b (seed_b, row=0)."""
+    if seed is None or isinstance(seed, RowSeeds):
+        return seed
+    if torch.is_tensor(seed):
+        if seed.dtype.is_floating_point or seed.dtype.is_complex or seed.dtype == torch.bool:
+            raise TypeError("%s must hold integers, got %s" % (what, seed.dtype))
+        seed = seed.item() if seed.dim() == 0 else seed.reshape(-1).tolist()
+    elif isinstance(seed, np.ndarray):
+        seed = seed.reshape(-1).tolist() if seed.ndim else seed.item()
+    if isinstance(seed, (list, tuple)):
+        if len(seed) != B:
+            raise ValueError("%s: %d seeds for %d rows" % (what, len(seed), B))
+        return RowSeeds((_seed_value(v, what), 0) for v in seed)
+    s = _seed_value(seed, what)
+    return RowSeeds((s, b) for b in range(B))
+
+
 class Request:
     """One utterance of a pooled admission (`SynthesizerTrn.infer_streams`, `StreamPool.admit`, `PcmPool.admit`): the
     arguments one `infer_stream` call takes, for one text.
@@ -65,13 +99,16 @@ class Request:
       chunk_frames, max_chunk_frames                          as `dec_stream`
       durations          frames per token, [T_text] (or [1, T_text] / [1, 1, T_text]), as `infer(durations=)`:
                          needs length_scale == 1
+      seed               None = the noise comes from torch's generators, as `infer_stream` draws it; an int in
+                         [0, 2^64): the request's noise is a function of the seed alone, at row 0
     Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
-                 "max_chunk_frames", "durations", "durations_dtype")
+                 "max_chunk_frames", "durations", "durations_dtype", "seed")
 
     def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                 chunk_frames=32, max_chunk_frames=256, durations=None):
+                 chunk_frames=32, max_chunk_frames=256, durations=None, seed=None):
+        self.seed = None if seed is None else _seed_value(seed, "Request: seed")
         if not torch.is_tensor(x):
             x = torch.as_tensor(x)
         if x.dim() != 1:
@@ -133,16 +170,19 @@ class ConvertRequest:
       in_sr              the rate of `wave`; None = model_sr
       noise_scale        scale of the posterior draw (1 = `voice_conversion`), >= 0
       chunk_frames, max_chunk_frames    as `dec_stream`
+      seed               None = the posterior draw comes from torch's device generator; an int in [0, 2^64): it is a
+                         function of the seed alone, at row 0
     n_fft is not a field: it is 2 (spec_channels - 1) of the model the request is given to, which also checks
     win_size <= n_fft.  Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("wave", "sid_src", "sid_tgt", "model_sr", "hop_size", "win_size", "in_sr", "noise_scale",
-                 "chunk_frames", "max_chunk_frames")
+                 "chunk_frames", "max_chunk_frames", "seed")
 
     MAX_N_FFT = 4096                # the largest transform `spectrogram` is built for
 
     def __init__(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
-                 chunk_frames=32, max_chunk_frames=256):
+                 chunk_frames=32, max_chunk_frames=256, seed=None):
+        self.seed = None if seed is None else _seed_value(seed, "ConvertRequest: seed")
         if not torch.is_tensor(wave):
             wave = torch.as_tensor(wave)
         if wave.dtype not in (torch.int16, torch.float32):
@@ -480,6 +520,47 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.device(dev):
             self._launch(h, name, *args, stream=self._stream(dev) if stream is None else stream)
 
+    # ------------------------------------------------------------------ seeded noise
+    def _fill_noise(self, h, blocks, stream=None):
+        """ONE `mbv_randn_blocks` launch inside a device scope the caller holds: `blocks` is a list of
+        (address, stride, channels, first, count, seed, purpose, row)."""
+        arr = (_capi.MbvRandnBlock * len(blocks))()
+        for k, (dst, stride, channels, first, count, seed, purpose, row) in zip(arr, blocks):
+            k.dst, k.stride, k.channels, k.first, k.count = dst, stride, channels, first, count
+            k.seed, k.purpose, k.row = seed, purpose, row
+        self._launch(h, "mbv_randn_blocks", arr, len(blocks), stream=stream)
+
+    def _seeded_rows(self, h, seeds, channels, frames, purpose, stream=None):
+        """[B, channels, frames] fp32: row b from the sub-stream seeds[b] = (seed, row), in one launch."""
+        out = torch.empty(len(seeds), channels, frames, device=self._device(), dtype=torch.float32)
+        self._fill_noise(h, [(out.data_ptr() + 4 * b * channels * frames, frames, channels, 0, frames, s, purpose, row)
+                             for b, (s, row) in enumerate(seeds)], stream=stream)
+        return out
+
+    @torch.no_grad()
+    def randn(self, seed, channels, frames, purpose=0, row=0, first=0):
+        """[channels, frames] fp32 standard normals on the model's device from the seeded generator (DESIGN 7.13,
+        `mbv_randn_blocks`): element (c, t) is a function of (seed, purpose, row, c, first + t) alone.  purpose: 0 the
+        prior draw of `infer`, 1 the SDP draw, 2 the posterior draw; `row` the sub-stream a batched entry gives its
+        row b under an int seed.  Neither torch generator is touched."""
+        seed = _seed_value(seed)
+        channels, frames, purpose, row, first = int(channels), int(frames), int(purpose), int(row), int(first)
+        if channels < 1 or frames < 0 or first < 0 or first + frames > 1 << 30:
+            raise ValueError("randn: need channels >= 1 and 0 <= first <= first + frames <= 2^30")
+        if purpose not in (0, 1, 2) or not 0 <= row < 1 << 32:
+            raise ValueError("randn: purpose must be 0, 1 or 2 and row in [0, 2^32)")
+        h = self._ensure_handle()
+        dev = self._device()
+        with torch.cuda.device(dev):
+            out = torch.empty(channels, frames, device=dev, dtype=torch.float32)
+            self._fill_noise(h, [(out.data_ptr(), frames, channels, first, frames, seed, purpose, row)])
+        return out
+
+    def noise_runs(self):
+        """`mbv_randn_blocks` launches made on this model's handle so far (`mbv_noise_runs`): a seeded call costs one
+        per noise tensor it needs, however many rows or requests it serves."""
+        return int(_capi.lib().mbv_noise_runs(self._ensure_handle()))
+
     def _check_inputs(self, x, x_lengths, sid):
         dev = self._device()
         if x.dim() != 2:
@@ -527,7 +608,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
-             prior_rows=None, trim=False, ragged=False, durations=None):
+             prior_rows=None, trim=False, ragged=False, durations=None, seed=None):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -540,11 +621,17 @@ class SynthesizerTrn(nn.Module):
                        rows lo:hi (ranks seeded alike then reproduce the single-process draw)
           trim         opt-in trimmed decode (see `infer`)
           ragged       opt-in row-exact ragged decode (see `infer`)
-          durations    frames per token to use instead of the predicted ones (see `infer`)"""
+          durations    frames per token to use instead of the predicted ones (see `infer`)
+          seed         None = both draws come from torch's generators; else (see `infer`) the SDP draw and the prior
+                       draw are one `mbv_randn_blocks` launch each and no generator is touched.  A sharded caller
+                       passes the `RowSeeds` of its own rows (row = the global row index)"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
         dev, B, T = x.device, x.shape[0], x.shape[1]
+        seeds = _row_seeds(seed, B)
+        if seeds is not None and noise_w is not None:
+            raise ValueError("seed= and an explicit noise_w= exclude each other")
         if durations is not None:
             durations, dur_dtype = self._check_durations(durations, B, T, length_scale)
         I = self.cfg.inter_channels
@@ -561,7 +648,9 @@ class SynthesizerTrn(nn.Module):
             if self.cfg.use_sdp:
                 # the reference draws on the default CPU generator and moves it over (models.py:94);
                 # a sharded caller passes its block of the full-batch draw instead
-                if noise_w is None:
+                if seeds is not None:
+                    noise_w = self._seeded_rows(h, seeds, 2, T, _capi.NOISE_SDP, stream=stream)
+                elif noise_w is None:
                     noise_w = torch.randn(B, 2, T)
                 if tuple(noise_w.shape) != (B, 2, T):
                     raise ValueError("noise_w must be [B, 2, T_text]")
@@ -588,7 +677,13 @@ class SynthesizerTrn(nn.Module):
             if frames_hook is not None:
                 Tp = int(frames_hook(Tp))
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729)
-            if prior_rows is not None:
+            if seeds is not None:
+                # a function of (seed, row, channel, frame): no generator, no dependence on the batch or its padding;
+                # at noise_scale == 0 nothing reads it and no generator has to advance
+                noise = None
+                if float(noise_scale) != 0.0:
+                    noise = self._seeded_rows(h, seeds, I, Tp, _capi.NOISE_PRIOR, stream=stream)
+            elif prior_rows is not None:
                 # sharded run: the draw of the WHOLE batch, this shard's rows — also at noise_scale == 0, so that
                 # the device generator advances exactly as in a single-process run of the full batch (a later
                 # noisy call in the same process then still reproduces the single-process draws).  Large draws take
@@ -670,8 +765,16 @@ class SynthesizerTrn(nn.Module):
         return o, o_mb, spec, phase
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-              max_len=None, outputs=None, trim=False, ragged=False, durations=None):
+              max_len=None, outputs=None, trim=False, ragged=False, durations=None, seed=None):
         """-> (o, o_mb, spec, phase, attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:737)
+
+        `seed` (extension, default None = the noise comes from torch's two generators, launch for launch as before):
+        reproducible noise.  An int s gives row b the sub-stream (s, row=b); a length-B sequence or
+        integer tensor gives row b (seed_b, row=0), so `infer(x[b:b+1], ..., seed=[s_b])` draws what row b of
+        `infer(x, ..., seed=[s_0 .. s_{B-1}])` draws.  Seeds are integers in [0, 2^64) (TypeError for bool / float,
+        ValueError for a wrong count or range).  The prior draw, and the SDP draw of a `use_sdp` model, are one
+        `mbv_randn_blocks` launch each on the device (`net.randn` gives the same values); both torch generators stay
+        exactly where they were.
 
         `durations` (extension, default None = the predicted durations, launch for launch as before): frames per
         token, [B, T_text] or [B, 1, T_text] (e.g. the `w` of `align`), non-negative integers of any dtype.  They
@@ -696,22 +799,23 @@ class SynthesizerTrn(nn.Module):
         the last ~25 frames of a row depend on what the unmasked decoder computes behind its end.  The B lengths
         are read back in the call's one host synchronisation."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, durations=durations)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, durations=durations,
+                      seed=seed)
         return r[:8]
 
     def infer_z_only(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-                     max_len=None, durations=None):
-        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788); `durations` as in `infer`"""
+                     max_len=None, durations=None, seed=None):
+        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788); `durations`, `seed` as in `infer`"""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w, durations=durations)
+                      noise_scale_w=noise_scale_w, durations=durations, seed=seed)
         return r[4], r[5], r[6], r[7]
 
     def infer_with_lengths(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1,
-                           max_len=None, noise_scale_w=1., outputs=None, trim=False, ragged=False):
+                           max_len=None, noise_scale_w=1., outputs=None, trim=False, ragged=False, seed=None):
         """`infer` plus the per-utterance frame counts y_lengths [B] (int64) — what a batched
-        caller needs to trim the padded waveforms (valid samples = 256 * y_lengths)."""
+        caller needs to trim the padded waveforms (valid samples = 256 * y_lengths).  `seed` as in `infer`."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, seed=seed)
         return r[:8], r[8]
 
     def _z_g(self, z, g, checked=True):
@@ -865,13 +969,13 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                     chunk_frames=32, max_chunk_frames=256, durations=None):
+                     chunk_frames=32, max_chunk_frames=256, durations=None, seed=None):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
-        flows exactly as `infer` does (same random draws; `durations` as in `infer`), then returns `dec_stream` of
+        flows exactly as `infer` does (same random draws; `durations` and `seed` as in `infer`), then returns `dec_stream` of
         z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
         `infer(...)[0]` (default mode)."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations)
+                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed)
         y_mask, z, y_lengths = r[5], r[6][0], r[8]
         Tp = z.shape[2]
         Td = Tp if max_len is None else max(0, min(Tp, int(max_len)))
@@ -919,6 +1023,18 @@ class SynthesizerTrn(nn.Module):
             o += I * t
         return flat, ptr
 
+    def _seeded_blocks(self, h, items, seeds, channels, lengths, purpose, ptr, stream):
+        """The blocks [channels, lengths[j]] of the seeded requests `items` (sub-stream (seeds[j], row 0)), back to
+        back in one flat buffer, filled by ONE launch -> the buffer; ptr[items[j]] = the address of block j."""
+        flat = torch.empty(channels * sum(lengths), device=self._device(), dtype=torch.float32)
+        blocks, o = [], 0
+        for i, s, t in zip(items, seeds, lengths):
+            ptr[i] = flat.data_ptr() + 4 * o
+            blocks.append((ptr[i], t, channels, 0, t, s, purpose, 0))
+            o += channels * t
+        self._fill_noise(h, blocks, stream=stream)
+        return flat
+
     def _streams_of(self, reqs, z, g, y_all, pos):
         """One single-utterance `DecodeStream` per request over its own z and g; `y_lengths` is the one-element slice
         of `y_all` at the request's row."""
@@ -956,7 +1072,11 @@ class SynthesizerTrn(nn.Module):
         `infer_stream(x_i[None], [len_i], sid_i, noise_scale_i, length_scale_i, noise_scale_w_i, max_len_i,
         chunk_frames_i, max_chunk_frames_i, durations=d_i)` returns when those calls are made one after the other in
         list order from the same RNG state, and both generators (CPU: the SDP draws, device: the prior draws) end in
-        the state those calls leave.  With the option "splitk" the result is deterministic and within fp32 rounding
+        the state those calls leave.  A request with `seed=` takes no part in that order: its stream is bitwise
+        `infer_stream(x_i[None], ..., seed=[seed_i])` whatever else is in the list and wherever it stands, its draws touch
+        no generator, and ONE `mbv_randn_blocks` launch fills the prior blocks of all seeded requests of the call (a
+        second their SDP blocks); seeded and unseeded requests may be mixed, the unseeded ones drawing in list order
+        among themselves.  With the option "splitk" the result is deterministic and within fp32 rounding
         of the stand-alone calls (a predicted duration may differ by a frame); "conv_bf16" is refused.
 
         All or nothing: a request with a token id / sid outside the model's tables or an unusable duration raises
@@ -987,13 +1107,18 @@ class SynthesizerTrn(nn.Module):
             hip_stream = self._stream(dev)
             keep = []                              # inputs of launches in flight
             noise_w = [None] * N
-            if self.cfg.use_sdp:                   # the reference's draw, per request, on the default CPU generator
-                flat_w = torch.cat([torch.randn(1, 2, t).reshape(-1) for t in t_text]).to(dev)
+            seeded = [i for i in range(N) if reqs[i].seed is not None]
+            drawn = [i for i in range(N) if reqs[i].seed is None]
+            if self.cfg.use_sdp and drawn:         # the reference's draw, per request, on the default CPU generator
+                flat_w = torch.cat([torch.randn(1, 2, t_text[i]).reshape(-1) for i in drawn]).to(dev)
                 keep.append(flat_w)
                 o = 0
-                for i, t in enumerate(t_text):
+                for i in drawn:
                     noise_w[i] = flat_w.data_ptr() + 4 * o
-                    o += 2 * t
+                    o += 2 * t_text[i]
+            if self.cfg.use_sdp and seeded:        # every seeded request's [2, T_text], across classes: one launch
+                keep.append(self._seeded_blocks(h, seeded, [reqs[i].seed for i in seeded], 2,
+                                                [t_text[i] for i in seeded], _capi.NOISE_SDP, noise_w, hip_stream))
             dur, kept = self._pack_host([r.durations for r in reqs], dev)       # (None where none are given)
             keep += kept
             y_all = torch.empty(N, dtype=torch.int64, device=dev)
@@ -1031,9 +1156,17 @@ class SynthesizerTrn(nn.Module):
             Tp = [int(y_host[pos[i]]) for i in range(N)]
             Td = [Tp[i] if r.max_len is None else min(Tp[i], r.max_len) for i, r in enumerate(reqs)]
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729): per request, in list order,
-            # into one buffer — the values and the generator's progress of N stand-alone randn(1, I, T'_i) calls
-            flat, noise = self._draw_rows(I, Tp, dev)
-            keep.append(flat)
+            # into one buffer — the values and the generator's progress of N stand-alone randn(1, I, T'_i) calls.
+            # Seeded requests take no part in that: their blocks are one launch, across classes
+            noise = [None] * N
+            if drawn:
+                flat, ptr = self._draw_rows(I, [Tp[i] for i in drawn], dev)
+                keep.append(flat)
+                for i, a in zip(drawn, ptr):
+                    noise[i] = a
+            if seeded:
+                keep.append(self._seeded_blocks(h, seeded, [reqs[i].seed for i in seeded], I, [Tp[i] for i in seeded],
+                                                _capi.NOISE_PRIOR, noise, hip_stream))
             z = [torch.empty(1, I, Td[i], device=dev, dtype=torch.float32) for i in range(N)]
             g = [None] * N
             for k, m in enumerate(members):
@@ -1070,16 +1203,22 @@ class SynthesizerTrn(nn.Module):
         return int(_capi.lib().mbv_converter_runs(self._ensure_handle()))
 
     def convert_stream(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
-                       chunk_frames=32, max_chunk_frames=256, noise=None):
+                       chunk_frames=32, max_chunk_frames=256, noise=None, seed=None):
         """Voice conversion of one recording up to z_hat, as a `DecodeStream`: resample to `model_sr` if `in_sr`
         differs, spectrogram, posterior encoder, forward flow with emb_g(sid_src), reverse flow with emb_g(sid_tgt);
         -> `dec_stream(z_hat * y_mask, g = emb_g(sid_tgt))` with `y_lengths` = the frame count.  Draws exactly one
         `torch.randn(1, inter, T)` on the device generator, as `voice_conversion` does for that spectrogram alone: at
         noise_scale 1 and in_sr == model_sr, `st.z` is bitwise that call's z_hat * y_mask and `st.run()` its o_hat
         (default mode).  Arguments as `ConvertRequest`.  `noise` [1, inter, T] fp32 replaces the draw and leaves the
-        generator untouched (what `convert_live` is measured against); the default is the path as it was."""
+        generator untouched (what `convert_live` is measured against); the default is the path as it was.  `seed` (an int,
+        or a one-element sequence as the batched entries take it) makes the draw a function of the seed (DESIGN 7.13:
+        purpose 2, row 0; one `mbv_randn_blocks` launch, no generator touched); it excludes `noise`."""
+        if seed is not None:
+            if noise is not None:
+                raise ValueError("convert_stream: seed= and noise= exclude each other")
+            seed = _row_seeds(seed, 1, "convert_stream: seed")[0][0]
         req = ConvertRequest(wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=in_sr, noise_scale=noise_scale,
-                             chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames)
+                             chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames, seed=seed)
         return self._convert([req], alone=True, noise=noise)[0]
 
     def converter_context(self):
@@ -1087,18 +1226,21 @@ class SynthesizerTrn(nn.Module):
         return stream.converter_context(self._config_struct())
 
     def convert_live(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
-                     noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None):
+                     noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None,
+                     seed=None):
         """Voice conversion of a recording that is still arriving: a `stream.LiveStream` that takes the samples in
         `push` calls of any size and hands out decoded chunks from `poll` as soon as the audio they depend on exists
         (DESIGN 7.11).  The result does not depend on how the samples were cut into pushes; for a recording of more
         than 256 frames it is bitwise `convert_stream(whole, ..., noise=st.noise[:, :, :T])` chunk by chunk (default
         mode), for a shorter one within fp32 rounding of it.  Draws one `torch.randn(1, inter, max_frames)` on the device
-        generator here, unless `noise` (that shape) is given.  Buffers are sized for `max_samples` once.  The audio
-        must be at the model's rate; `wire.convert_live_pcm16` is the form that takes raw samples at any rate and
-        hands out int16 at the service's rate."""
+        generator here, unless `noise` (that shape) is given, or `seed` (as `convert_stream` takes it; excludes
+        `noise`): then the capacity buffer is filled once, as one `mbv_randn_blocks` block, and since element (c, t)
+        does not depend on the buffer's length the stream equals `convert_stream(whole, ..., seed=[s])`.  Buffers are
+        sized for `max_samples` once.  The audio must be at the model's rate; `wire.convert_live_pcm16` is the form that
+        takes raw samples at any rate and hands out int16 at the service's rate."""
         return stream.LiveStream(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=dtype,
                                  noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
-                                 max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr)
+                                 max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr, seed=seed)
 
     def convert_streams(self, requests):
         """Pooled voice conversion: one single-utterance `DecodeStream` per `ConvertRequest`, in order — what
@@ -1108,7 +1250,10 @@ class SynthesizerTrn(nn.Module):
 
         Default mode: stream i is bitwise (z, g, y_lengths, schedule) what `convert_stream(...)` returns for request
         i alone when those calls are made in list order from the same RNG state; the device generator ends where
-        those calls leave it and the CPU generator is not touched.  With the option "splitk" the result is
+        those calls leave it and the CPU generator is not touched.  Requests with `seed=` take no part in that order:
+        each is bitwise `convert_stream(..., seed=[seed_i])` whatever else is in the list, and ONE `mbv_randn_blocks`
+        launch fills the posterior blocks of all of them; the unseeded ones draw in list order among themselves.  With
+        the option "splitk" the result is
         deterministic and within fp32 rounding of the stand-alone calls; "conv_bf16" is refused.
 
         All requests must agree on (model_sr, hop_size, win_size): one model has one data config.  Refused before any
@@ -1208,13 +1353,26 @@ class SynthesizerTrn(nn.Module):
                 flat = noise.to(dev).contiguous()
                 noise = [flat.data_ptr()]
                 y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
-            elif alone:
+            elif alone and reqs[0].seed is None:
                 flat = torch.randn(1, I, frames[0], device=dev, dtype=torch.float32)
                 noise = [flat.data_ptr()]
                 y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
             else:
-                flat, noise = self._draw_rows(I, frames, dev)
-                y_all = torch.tensor(frames, dtype=torch.int64).to(dev)
+                # seeded requests take no part in the list-order draw: their blocks are one launch, across classes
+                seeded = [i for i in range(N) if reqs[i].seed is not None]
+                drawn = [i for i in range(N) if reqs[i].seed is None]
+                noise = [None] * N
+                if drawn:
+                    flat, ptr = self._draw_rows(I, [frames[i] for i in drawn], dev)
+                    for i, a in zip(drawn, ptr):
+                        noise[i] = a
+                if seeded:
+                    keep.append(self._seeded_blocks(h, seeded, [reqs[i].seed for i in seeded], I,
+                                                    [frames[i] for i in seeded], _capi.NOISE_POSTERIOR, noise, hip_stream))
+                if alone:
+                    y_all = torch.full((1,), frames[0], dtype=torch.int64, device=dev)
+                else:
+                    y_all = torch.tensor(frames, dtype=torch.int64).to(dev)
             z = [torch.empty(1, I, frames[i], device=dev, dtype=torch.float32) for i in range(N)]
             g = [None] * N
             for m in members:
@@ -1486,7 +1644,7 @@ class SynthesizerTrn(nn.Module):
     _ALIGN_OUTPUT_NAMES = ("w", "attn", "x_mask", "y_mask", "z", "z_p", "m_p", "logs_p", "neg_cent")
 
     @torch.no_grad()
-    def align(self, x, x_lengths, y, y_lengths, sid=None, noise_scale=1.0, outputs=None, noise=None):
+    def align(self, x, x_lengths, y, y_lengths, sid=None, noise_scale=1.0, outputs=None, noise=None, seed=None):
         """Forced alignment of recordings to their texts: the alignment half of the reference's `forward`
         (models.py:659-680, :690-691) -> (attn, w, x_mask, y_mask, (z, z_p, m_p, logs_p)).
 
@@ -1498,6 +1656,8 @@ class SynthesizerTrn(nn.Module):
           m_p, logs_p    the text statistics expanded by the path
           noise_scale    0: the deterministic z = m_q; else z = m_q + noise * noise_scale * exp(logs_q) with
                          noise = torch.randn(B, inter, T_spec) drawn as `voice_conversion` draws it (or `noise`)
+          seed           as `infer` takes it: the posterior draw from the seeded generator instead (purpose
+                         2; one launch, no torch generator touched); excludes `noise`
           outputs        None = all of the above; or names from _ALIGN_OUTPUT_NAMES: only those are materialised,
                          the rest come back as None (`outputs=("w",)` skips attn and the prior).  "neg_cent"
                          ([B, T_spec, T_text], defined for [y < y_lengths[b], x < x_lengths[b]) only) is returned as
@@ -1507,6 +1667,9 @@ class SynthesizerTrn(nn.Module):
         h = self._ensure_handle()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
         dev, B, T = x.device, x.shape[0], x.shape[1]
+        if seed is not None and noise is not None:
+            raise ValueError("align: seed= and noise= exclude each other")
+        seeds = _row_seeds(seed, B)
         cfg = self.cfg
         I = cfg.inter_channels
         if y.dim() != 3 or y.shape[0] != B or y.shape[1] != cfg.spec_channels:
@@ -1528,7 +1691,9 @@ class SynthesizerTrn(nn.Module):
         f32 = dict(device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             if float(noise_scale) != 0.0:
-                if noise is None:
+                if seeds is not None:
+                    noise = self._seeded_rows(h, seeds, I, Tp, _capi.NOISE_POSTERIOR)
+                elif noise is None:
                     noise = torch.randn(B, I, Tp, **f32)             # randn_like(m) of models.py:245
                 elif tuple(noise.shape) != (B, I, Tp):
                     raise ValueError("noise must be [B, %d, T_spec]" % I)
@@ -1562,8 +1727,10 @@ class SynthesizerTrn(nn.Module):
         return r + (t["neg_cent"],) if "neg_cent" in want else r
 
     @torch.no_grad()
-    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt):
-        """-> (o_hat, o_hat_mb, y_mask, (z, z_p, z_hat))  (models.py:790-798)."""
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, seed=None):
+        """-> (o_hat, o_hat_mb, y_mask, (z, z_p, z_hat))  (models.py:790-798).  `seed` (extension, as `infer` takes
+        it): the posterior draw from the seeded generator (purpose 2) in one launch, no torch generator
+        touched; the default draws torch.randn as before."""
         if not self.n_speakers > 0:
             raise AssertionError("n_speakers have to be larger than 0.")      # models.py:791
         h = self._ensure_handle()
@@ -1573,13 +1740,17 @@ class SynthesizerTrn(nn.Module):
             raise ValueError("y must be [B, %d, T] (linear spectrogram)" % cfg.spec_channels)
         y = y.to(device=dev, dtype=torch.float32).contiguous()
         B, _, T = y.shape
+        seeds = _row_seeds(seed, B)
         y_lengths = y_lengths.to(device=dev, dtype=torch.int64).contiguous()
         sid_src = sid_src.to(device=dev, dtype=torch.int64).contiguous()
         sid_tgt = sid_tgt.to(device=dev, dtype=torch.int64).contiguous()
         I = cfg.inter_channels
         f32 = dict(device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            noise = torch.randn(B, I, T, **f32)                  # randn_like(m) of models.py:245
+            if seeds is not None:
+                noise = self._seeded_rows(h, seeds, I, T, _capi.NOISE_POSTERIOR)
+            else:
+                noise = torch.randn(B, I, T, **f32)              # randn_like(m) of models.py:245
             o, o_mb, spec, phase = self._alloc_decoder_outputs(B, T, dev)
             y_mask = torch.empty(B, 1, T, **f32)
             z, z_p, z_hat = (torch.empty(B, I, T, **f32) for _ in range(3))

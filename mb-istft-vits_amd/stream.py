@@ -201,8 +201,14 @@ class LiveStream:
     ahead are handed out by the next `poll()` without a launch."""
 
     def __init__(self, net, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
-                 noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None):
+                 noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None,
+                 seed=None):
         import math
+        if seed is not None:
+            from .models import _row_seeds
+            if noise is not None:
+                raise ValueError("convert_live: seed= and noise= exclude each other")
+            seed = _row_seeds(seed, 1, "convert_live: seed")[0][0]
         self.model_sr, self.hop_size, self.win_size = int(model_sr), int(hop_size), int(win_size)
         if in_sr is not None and int(in_sr) != self.model_sr:
             raise ValueError("convert_live takes audio at the model's rate (in_sr %d, model_sr %d): a streaming input "
@@ -242,7 +248,10 @@ class LiveStream:
         self.spf = net.cfg.samples_per_frame
         self.dtype = dtype
         with torch.cuda.device(dev), torch.no_grad():
-            if noise is None:
+            if seed is not None:
+                # the capacity buffer, once, as one block: element (c, t) does not depend on F
+                self.noise = net.randn(seed, I, F, purpose=_capi.NOISE_POSTERIOR).unsqueeze(0)
+            elif noise is None:
                 self.noise = torch.randn(1, I, F, device=dev, dtype=torch.float32)
             else:
                 if not torch.is_tensor(noise) or noise.dtype != torch.float32 or tuple(noise.shape) != (1, I, F):

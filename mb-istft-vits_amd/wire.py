@@ -76,13 +76,14 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
 
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
-                  auto_normalize=True, res_type="kaiser_best"):
+                  auto_normalize=True, res_type="kaiser_best", seed=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
       2. `net.resample` to `model_sr` when the rates differ;
       3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
-      4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt)`;
+      4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)` (`seed` as `infer` takes it: None =
+         torch's generator, as before);
       5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`.
     -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
     anything is launched when win_size > n_fft or the model has no speakers.  The one host synchronisation is
@@ -100,7 +101,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
         wave = wave.float() / 32768.0                          # the resampler takes fp32; exact scaling
     wave, valid = net.resample(wave, in_sr, model_sr, valid_samples=valid_samples, res_type=res_type)
     spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
-    o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt)[0]
+    o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)[0]
     return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type)
 
 
@@ -440,7 +441,7 @@ class LiveWire:
 
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                 chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+                 chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None):
         from .stream import LiveStream
         _filter_code(res_type)
         if dtype not in (torch.float32, torch.int16):
@@ -460,7 +461,7 @@ class LiveWire:
         self.live = LiveStream(net, sid_src, sid_tgt, model_sr, hop_size, win_size, cap,
                                dtype=torch.float32 if resamples else dtype, noise_scale=noise_scale, noise=noise,
                                chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames,
-                               convert_frames=convert_frames)
+                               convert_frames=convert_frames, seed=seed)
         live = self.live
         self._net = net
         self._plan = LiveWirePlan(self.in_sr, self.model_sr, self.rate, live.plan, live.spf, self.max_samples, res_type)
@@ -586,15 +587,16 @@ class LiveWire:
 
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                       chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+                       chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32) while the recording arrives, int16
     out at `rate`; -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
     `LiveStream` it opens, [1, inter, frames of ceil(max_samples * model_sr / in_sr)].  `peak` as `stream_pcm16` takes
     it.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
-    `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`."""
+    `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
+    (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead."""
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
-                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames)
+                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed)
 
 
 class PcmPool:

@@ -54,6 +54,23 @@ struct EncState {
   int* bad32 = nullptr;         // per-utterance flags (invalid id / length / sid)
 };
 
+// one launch of the decoder, as integers (decoder_table)
+enum { DL_PRE = 0, DL_UP = 1, DL_C1 = 2, DL_C2 = 3, DL_POST = 4, DL_TAIL = 5 };
+struct DecLaunch {
+  int kind, stage, j, q;
+  int Cin, M, K, dil, pad_left;
+  int num, add, rate;
+  int epi, convt_u, reflect1;
+  int res, chan_add, res_chan_add, lens;
+  int tk, tp;                      // DL_UP: kernel size and padding of the ConvTranspose1d itself
+  int n_fft, hop, bands, taps;     // DL_TAIL: iSTFT (center = True) and the synthesis filter (taps, pad taps / 2)
+};
+inline int dec_us(const mbv_config& c) { return c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4; }   // upsample stride of both stages
+// ConvTranspose1d(k 16, stride u, padding (16 - u) / 2) as a phase conv over its input frames (EPI_CONVT)
+constexpr int kConvtK = 16;
+inline int convt_taps(int u) { return kConvtK / u + 1; }
+inline int convt_pad_left(int u) { return u == 4 ? 2 : 1; }
+
 }  // namespace
 
 struct mbv_model : EncState {     // the base: the state of the last encode
@@ -117,6 +134,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int trim = 0;                    // option "trim": opt-in trimmed decode (run_decoder)
   int tail_once = 1;               // option "tail_once": the zero-input tail of a padded batch computed once (run_decoder)
   unsigned long long* tail_cnt = nullptr;   // device: column tiles dropped by tail maps since mbv_create (mbv_tail_dropped)
+  std::vector<DecLaunch> dec_table;   // decoder_table(cfg), built once at mbv_create
   std::vector<int> ragged_first;   // row-exact ragged decode: first length of every class up to ragged_scanned (ragged_classes)
   int ragged_scanned = 0, ragged_splitk = -1;
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
@@ -416,8 +434,8 @@ void pack_conv_rows(const float* w, int Cin, int K, const int* rows, int M, cons
 // dst_w [(16/us + 1) * Cin * Mpad] packed (Mpad >= us * Cout), dst_bias [us * Cout] in row order.
 void pack_convt_rows(const float* w, const float* bias, int Cin, int Cout, int us, int Mpad, float* dst_w,
                      float* dst_bias) {
-  const int tpp = 16 / us, pad = (16 - us) / 2;
-  const int Mp = us * Cout, PH = us / 2, CG = 32 / PH, Kc = tpp + 1, pl = tpp - 1 - pad / us;
+  const int tpp = kConvtK / us, pad = (kConvtK - us) / 2;
+  const int Mp = us * Cout, PH = us / 2, CG = 32 / PH, Kc = convt_taps(us), pl = tpp - 1 - pad / us;   // (pl = convt_pad_left(us))
   for (int row = 0; row < Mp; ++row) {
     const int grp = row / 64, half = (row % 64) / 32, k = row % 32;
     const int co = grp * CG + k / PH, r = half * PH + k % PH;
@@ -846,12 +864,12 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
     const std::vector<float> w = P.dense(p);            // [Cin][Cout][16], norm per Cin
     const auto& sh = P.t(std::string(p) + ".weight_v").shape;
     const int Cin = (int)sh[0], Cout = (int)sh[1];
-    const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4;        // stride; k = 16, pad = (16-us)/2
+    const int us = dec_us(c);
     if (Cout % 32 || Cin % 16)
       return m->fail("%s: ConvTranspose1d %d -> %d channels: the EPI_CONVT conv needs Cout %% 32 == 0 and Cin %% 16 == 0",
                      p, Cin, Cout);
     PConv& pc = m->upc[i];
-    pc.M = us * Cout; pc.Mpad = (int)align_up(pc.M, 128); pc.Cin = Cin; pc.K = 16 / us + 1;
+    pc.M = us * Cout; pc.Mpad = (int)align_up(pc.M, 128); pc.Cin = Cin; pc.K = convt_taps(us);
     pc.w = P.alloc((size_t)pc.K * Cin * pc.Mpad);
     pc.bias = P.alloc(pc.M);
     pc.has_bias = true;
@@ -948,39 +966,55 @@ int ensure(mbv_model* m, char** buf, size_t* cap, size_t need) {
   return 0;
 }
 
-// An entry's fixed scratch is written ONCE, as `carve(Bump&)`: run on a measuring Bump for the byte count, then, with
-// the buffer grown to that plus `extra` (the decoder's part, which carves on from *rest: decoder_scratch_bytes and its
-// like), on the buffer itself.  A tensor that may go to a caller's pointer instead is decided inside `carve`, so both
-// passes agree on it.  Nothing carved may be used before this returns 0.
+// An entry's scratch is written ONCE, as `carve(Bump&)`: run on a measuring Bump for the byte count, then, with the
+// buffer grown to that, on the buffer itself.  A tensor that may go to a caller's pointer instead is decided inside
+// `carve`, so both passes agree on it; what a take depends on must be a host fact, never a pointer carved before it
+// (the measuring pass hands out null).  Nothing carved may be used before this returns 0.  An arena that already
+// holds the layout — every call but the first of a larger size — is carved at once: that one pass is all.  So a carve
+// may run up to three times per call and must do nothing but set its outputs; a pass that does not fit hands out
+// pointers past the arena, which nobody may read before lay_out has returned 0.
 template <typename Carve>
-int lay_out(mbv_model* m, const char* who, char** buf, size_t* cap, Carve&& carve, size_t extra = 0, Bump* rest = nullptr) {
+int lay_out(mbv_model* m, const char* who, char** buf, size_t* cap, Carve&& carve) {
+  Bump sc{*buf, *cap};
+  if (*buf) carve(sc);
+  if (*buf && sc.fits()) return 0;
   Bump measure{nullptr, 0};
   carve(measure);
-  if (ensure(m, buf, cap, measure.off + extra)) return 1;
-  Bump sc{*buf, *cap};
+  if (ensure(m, buf, cap, measure.off)) return 1;
+  sc = Bump{*buf, *cap};
   carve(sc);
-  if (rest) *rest = sc;
   return sc.fits() ? 0 : m->fail("%s: scratch layout exceeds its buffer", who);
 }
 
-ConvArgs conv_args(const mbv_model* m, const PConv& p, const float* x, int64_t x_bstride, int Tin,
-                   float* y, int64_t y_bstride, int T, int B, int dil = 1) {
+// The integer half of a ConvArgs, all that conv1d_plan, conv1d_trim_bn and conv1d_narrow_supported read besides which
+// optional tensors are given: B rows of Cin x Tin -> M x T, dense, "same" padding, plain store.
+ConvArgs conv_shape(int Cin, int M, int K, int dil, int Tin, int T, int B, int splitk) {
   ConvArgs a{};
-  a.x = x; a.x_bstride = x_bstride; a.Tin = Tin; a.x_rstride = Tin; a.Cin = p.Cin;
+  a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = K; a.dil = dil; a.pad_left = (K - 1) * dil / 2;
+  a.Tin = Tin; a.x_rstride = Tin; a.x_bstride = (int64_t)Cin * Tin;
+  a.T = T; a.y_bstride = (int64_t)M * T; a.epi = EPI_STORE; a.in_slope = 1.f; a.out_scale = 1.f; a.B = B;
+  a.splitk = splitk;
+  return a;
+}
+
+// ... of a packed conv of the handle, on real tensors
+ConvArgs conv_bind(const mbv_model* m, const PConv& p, ConvArgs a, const float* x, float* y) {
+  a.x = x; a.y = y;
   a.w = m->W(p.w); a.bias = p.has_bias ? m->W(p.bias) : nullptr;
   a.w_split = m->Wsplit(p.w);
-  a.M = p.M; a.Mpad = p.Mpad; a.K = p.K; a.dil = dil;
-  a.pad_left = (p.K - 1) * dil / 2;
-  a.in_slope = 1.f;
-  a.y = y; a.y_bstride = y_bstride; a.T = T; a.epi = EPI_STORE; a.out_scale = 1.f; a.B = B;
   a.ws = m->conv_ws; a.ws_floats = m->conv_ws_floats; a.counters = m->conv_cnt; a.n_counters = m->conv_ncnt;
-  a.splitk = m->splitk;
   a.prec = a.w_split ? 3 : 0;
   return a;
 }
 
+ConvArgs conv_args(const mbv_model* m, const PConv& p, const float* x, int64_t x_bstride, int Tin,
+                   float* y, int64_t y_bstride, int T, int B, int dil = 1) {
+  ConvArgs a = conv_shape(p.Cin, p.M, p.K, dil, Tin, T, B, m->splitk);
+  a.x_bstride = x_bstride; a.y_bstride = y_bstride;
+  return conv_bind(m, p, a, x, y);
+}
+
 // decoder + waveform tail on z [B, I, zstride] (first Td frames valid)
-size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td, int tail = 0);
 
 // "tail_once" as the handle's options leave it: 0 off (or excluded by split-K, "trim", "conv_bf16"), 1 the stages
 // whose ResBlock convs exceed one round of the 256-workgroup grid, 2 every stage (tests).  Below one round a
@@ -1013,9 +1047,84 @@ struct DecodeRange {
   int max_keep = 0;
 };
 
+// ------------------------------------------------------------------ the decoder, stated once
+// Every launch of the decoder in launch order, as integers.  kind: conv_pre, ups[stage], the first / second conv of
+// step q of ResBlock j of `stage` (ResBlock2: its one conv counts as the second), conv_post behind
+// ReflectionPad1d((1, 0)), the waveform tail.  A conv of a row of len z-frames runs over num len input columns and
+// T = num len + add launch columns; rate = output columns per z-frame (ups runs over INPUT frames: convt_u num).
+// res / chan_add / res_chan_add: the optional tensors of the launch (the latter two with speaker-conditioned
+// ResBlocks); lens: which of a ragged row's lengths (len, us len, us^2 len) masks the input.
+std::vector<DecLaunch> decoder_table(const mbv_config& c) {
+  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
+  const int us = dec_us(c), C0 = c.upsample_initial_channel;
+  const int kPre = 7, kPost = 7;                        // conv_pre, conv_post / subband_conv_post (models.py)
+  const int n_fft = 16, hop = 4;                        // TorchSTFT
+  const int bands = sb ? 1 : 4, taps = 63;              // PQMF synthesis / multistream_conv_post
+  const int nq = c.resblock_type == 2 ? 2 : 3;
+  std::vector<DecLaunch> t;
+  auto conv = [&](int kind, int stage, int j, int q, int Cin, int M, int K, int dil, int num, int epi) -> DecLaunch& {
+    DecLaunch e{};
+    e.kind = kind; e.stage = stage; e.j = j; e.q = q;
+    e.Cin = Cin; e.M = M; e.K = K; e.dil = dil; e.pad_left = (K - 1) * dil / 2;
+    e.num = e.rate = num; e.lens = stage + 1; e.epi = epi; e.res = epi == EPI_RESID || epi == EPI_RESID_ACC;
+    t.push_back(e);
+    return t.back();
+  };
+  conv(DL_PRE, -1, 0, 0, c.inter_channels, C0, kPre, 1, 1, EPI_STORE);
+  int num = 1;
+  for (int i = 0; i < 2; ++i) {
+    const int ch = C0 >> (i + 1);
+    DecLaunch& u = conv(DL_UP, i, 0, 0, C0 >> i, us * ch, convt_taps(us), 1, num, EPI_CONVT);
+    u.pad_left = convt_pad_left(us); u.convt_u = us; u.rate = us * num; u.lens = i;
+    u.tk = kConvtK; u.tp = (kConvtK - us) / 2;
+    num *= us;
+    for (int j = 0; j < 3; ++j) {
+      const int k = c.resblock_kernel_sizes[j];
+      for (int q = 0; q < nq; ++q) {                  // each step: x = conv(...)(x) + x; the last one adds into xs
+        const int d = c.resblock_dilations[j][q];
+        const int last = q == nq - 1 ? EPI_RESID_ACC : EPI_RESID;
+        if (c.resblock_type == 2) {
+          DecLaunch& e = conv(DL_C2, i, j, q, ch, ch, k, d, num, last);
+          e.chan_add = e.res_chan_add = q == 0;
+        } else {
+          conv(DL_C1, i, j, q, ch, ch, k, d, num, EPI_STORE).chan_add = q == 0;
+          conv(DL_C2, i, j, q, ch, ch, k, 1, num, last).res_chan_add = q == 0;
+        }
+      }
+    }
+  }
+  DecLaunch& p = conv(DL_POST, 2, 0, 0, C0 >> 2, 2 * (n_fft / 2 + 1) * bands, kPost, 1, num, EPI_STORE);
+  p.add = 1; p.reflect1 = 1; p.lens = 2;               // frame f reads padded[f - 3 .. f + 3] = x[f - 4 .. f + 2]
+  DecLaunch w{};
+  w.kind = DL_TAIL; w.stage = 2; w.num = num; w.add = 1; w.rate = num * hop * bands;
+  w.n_fft = n_fft; w.hop = hop; w.bands = bands; w.taps = taps;
+  t.push_back(w);
+  return t;
+}
+
+// The integer shape of entry e for B rows of len z-frames: what run_decoder launches (it adds tensors, the strides of
+// its real buffers and the per-call options) and what the planner-side readers plan.
+ConvArgs dec_shape(const DecLaunch& e, int len, int B, int splitk) {
+  ConvArgs a = conv_shape(e.Cin, e.M, e.K, e.dil, e.num * len, e.num * len + e.add, B, splitk);
+  a.pad_left = e.pad_left; a.epi = e.epi; a.convt_u = e.convt_u; a.reflect1 = e.reflect1;
+  if (e.res) a.res_bstride = a.y_bstride;
+  return a;
+}
+// ... for conv1d_plan / conv1d_trim_bn / conv1d_narrow_supported alone, which test data pointers against null: the
+// one place that hands out a placeholder.  Never launched.
+ConvArgs dec_planner_args(const DecLaunch& e, int len, int B, int splitk, int prec = 0, bool cond = false) {
+  static const float kSome = 0.f;                   // "a tensor is given"
+  ConvArgs a = dec_shape(e, len, B, splitk);
+  if (e.res) a.res = &kSome;
+  if (cond && e.chan_add) a.chan_add = &kSome;      // (cond: a speaker vector reaches conditioned ResBlocks)
+  if (cond && e.res_chan_add) a.res_chan_add = &kSome;
+  a.prec = prec;
+  return a;
+}
+
 // Receptive field of the decoder in whole z-frames (mbv_decoder_context): the interval of z-frames any sample of
-// frame t can depend on is [t - L, t + R].  Walked backwards, layer by layer, from the samples of one frame far
-// from both edges; every index interval is at the rate of the layer it belongs to.
+// frame t can depend on is [t - L, t + R].  Walked backwards over the table from the samples of one frame far from
+// both edges; every index interval is at the rate of the layer it belongs to.
 struct Span { int64_t lo, hi; };
 static Span span_conv(Span y, int K, int dil, int pad_left) { return {y.lo - pad_left, y.hi + (int64_t)(K - 1) * dil - pad_left}; }
 static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
@@ -1024,39 +1133,35 @@ static int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 static Span span_convt(Span y, int k, int u, int p) { return {ceil_div(y.lo + p - k + 1, u), floor_div(y.hi + p, u)}; }
 static Span span_union(Span a, Span b) { return {a.lo < b.lo ? a.lo : b.lo, a.hi > b.hi ? a.hi : b.hi}; }
 
-int decoder_context(const mbv_config& c, int* Lc, int* Rc) {
-  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
-  const int us = sb ? 8 : 4, kUp = 16;                  // ups: ConvTranspose1d(k 16, stride us, padding (16 - us) / 2)
-  const int kPre = 7, kPost = 7;                        // conv_pre, conv_post / subband_conv_post (models.py)
-  const int n_fft = 16, hop = 4;                        // TorchSTFT (center = True)
-  const int bands = sb ? 1 : 4, taps = 63;              // PQMF synthesis / multistream_conv_post: 63 taps, pad 31
-  const int64_t spf = (int64_t)us * us * hop * bands;   // waveform samples per z-frame
+void decoder_context(const std::vector<DecLaunch>& table, int* Lc, int* Rc) {
   const int64_t t = 1 << 20;                            // a frame far from both edges
-  Span x{spf * t, spf * t + spf - 1};                   // the waveform samples of frame t
-  if (!sb) x = {ceil_div(x.lo - taps / 2, bands), floor_div(x.hi + taps / 2, bands)};   // sub-band samples (zero-stuffed x bands)
-  // iSTFT, center: output sample m is position m + n_fft / 2 of the overlap-add; frame f covers [hop f, hop f + n_fft)
-  x = {ceil_div(x.lo + n_fft / 2 - (n_fft - 1), hop), floor_div(x.hi + n_fft / 2, hop)};
-  // conv_post over ReflectionPad1d((1, 0)): frame f reads padded[f - 3 .. f + 3] = x[f - 4 .. f + 2]
-  x = span_conv(x, kPost, 1, (kPost - 1) / 2 + 1);
-  for (int i = 1; i >= 0; --i) {
-    Span need = x;                                      // xs / 3 of the three ResBlocks (and each one's skip path)
-    for (int j = 0; j < 3; ++j) {
-      Span r = x;
-      const int k = c.resblock_kernel_sizes[j];
-      const int nconv = c.resblock_type == 2 ? 2 : 3;
-      for (int q = nconv - 1; q >= 0; --q) {          // each step: x = conv(...)(x) + x
-        const int d = c.resblock_dilations[j][q];
-        if (c.resblock_type != 2) r = span_conv(r, k, 1, (k - 1) / 2);
-        r = span_conv(r, k, d, (k - 1) * d / 2);
-      }
-      need = span_union(need, r);
+  Span x{}, need{}, r{};                                // of a stage: its output xs, its input u, the ResBlock in hand
+  for (size_t n = table.size(); n-- > 0;) {
+    const DecLaunch& e = table[n];
+    switch (e.kind) {
+      case DL_TAIL:
+        x = {e.rate * t, e.rate * t + e.rate - 1};      // the waveform samples of frame t
+        if (e.bands > 1) x = {ceil_div(x.lo - e.taps / 2, e.bands), floor_div(x.hi + e.taps / 2, e.bands)};   // sub-band samples (zero-stuffed x bands)
+        // iSTFT, center: output sample m is position m + n_fft / 2 of the overlap-add; frame f covers [hop f, hop f + n_fft)
+        x = {ceil_div(x.lo + e.n_fft / 2 - (e.n_fft - 1), e.hop), floor_div(x.hi + e.n_fft / 2, e.hop)};
+        break;
+      case DL_POST:
+        need = r = x = span_conv(x, e.K, e.dil, e.pad_left + e.reflect1);
+        break;
+      case DL_C1: case DL_C2:
+        if (e.epi == EPI_RESID_ACC) { need = span_union(need, r); r = x; }    // a ResBlock's last launch: xs / 3 needs x of it
+        r = span_conv(r, e.K, e.dil, e.pad_left);
+        break;
+      case DL_UP:
+        need = r = x = span_convt(span_union(need, r), e.tk, e.convt_u, e.tp);
+        break;
+      case DL_PRE:
+        x = span_conv(x, e.K, e.dil, e.pad_left);
+        break;
     }
-    x = span_convt(need, kUp, us, (kUp - us) / 2);
   }
-  x = span_conv(x, kPre, 1, (kPre - 1) / 2);
   *Lc = (int)(t - x.lo);
   *Rc = (int)(x.hi - t);
-  return 0;
 }
 
 // "tail_once": how far to the right a z-frame reaches at every launch of the decoder (mbv_tail_plan).  Walked
@@ -1064,56 +1169,39 @@ int decoder_context(const mbv_config& c, int* Lc, int* Rc) {
 // columns up to x.hi can influence.
 static int64_t reach_conv(int64_t hi, int pad_left) { return hi + pad_left; }                  // y[t] reads x[t - pad_left + k dil]
 static int64_t reach_convt(int64_t hi, int k, int u, int p) { return (int64_t)u * hi - p + k - 1; }   // j = u i - p + [0, k)
-// One entry per launch, in launch order.  kind: 0 conv_pre, 1 ups[stage], 2 / 3 first / second conv of step q of
-// ResBlock j of `stage`, 4 conv_post, 5 the waveform tail (iSTFT + synthesis filter).  rate = output columns per
-// z-frame; reach = output columns past rate len - 1 that a valid z-frame of a row of len frames can still influence
-// (ResBlock launches that write the running sum xs: the maximum over the ResBlocks summed so far).  Row b's output
-// at and past column rate len_b + reach is the zero-input response: a function of the column alone.
+// One entry per entry of the table, with its kind / stage / j / q.  rate = output columns per z-frame; reach = output
+// columns past rate len - 1 that a valid z-frame of a row of len frames can still influence (ResBlock launches that
+// write the running sum xs: the maximum over the ResBlocks summed so far).  Row b's output at and past column
+// rate len_b + reach is the zero-input response: a function of the column alone.
 struct TailLaunch { int kind, stage, j, q, rate, reach; };
-void decoder_tail_plan(const mbv_config& c, std::vector<TailLaunch>* out) {
-  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
-  const int us = sb ? 8 : 4, kUp = 16, kPre = 7, kPost = 7, n_fft = 16, hop = 4, bands = sb ? 1 : 4, taps = 63;
-  (void)n_fft;
+void decoder_tail_plan(const std::vector<DecLaunch>& table, std::vector<TailLaunch>* out) {
   out->clear();
   const int64_t len = 1 << 20;                        // a row far from both edges; every hi below is relative to it
-  int64_t rate = 1;
-  int64_t hi = len - 1;                               // the last valid z-frame
-  auto put = [&](int kind, int stage, int j, int q, int64_t h) {
-    out->push_back({kind, stage, j, q, (int)rate, (int)(h - (rate * len - 1))});
-  };
-  hi = reach_conv(hi, (kPre - 1) / 2);
-  put(0, -1, 0, 0, hi);
-  for (int i = 0; i < 2; ++i) {
-    hi = reach_convt(hi, kUp, us, (kUp - us) / 2);
-    rate *= us;
-    put(1, i, 0, 0, hi);
-    int64_t sum_hi = hi;                              // xs: the ResBlocks summed so far (each holds its skip path: >= hi)
-    for (int j = 0; j < 3; ++j) {
-      const int k = c.resblock_kernel_sizes[j];
-      const int nq = c.resblock_type == 2 ? 2 : 3;
-      int64_t r = hi;
-      for (int q = 0; q < nq; ++q) {
-        const int d = c.resblock_dilations[j][q];
-        const bool last = q == nq - 1;
-        if (c.resblock_type == 2) {
-          r = reach_conv(r, (k - 1) * d / 2);         // (+ the skip path: r only grows)
-          if (last) { sum_hi = sum_hi > r ? sum_hi : r; put(3, i, j, q, sum_hi); } else put(3, i, j, q, r);
-          continue;
-        }
-        r = reach_conv(r, (k - 1) * d / 2);
-        put(2, i, j, q, r);
-        r = reach_conv(r, (k - 1) / 2);
-        if (last) { sum_hi = sum_hi > r ? sum_hi : r; put(3, i, j, q, sum_hi); } else put(3, i, j, q, r);
-      }
+  int64_t sum_hi = len - 1;                           // the last valid z-frame; then xs: the ResBlocks summed so far
+  int64_t hi = sum_hi, r = sum_hi;                    // a stage's input u (each ResBlock holds its skip path: >= hi), the ResBlock in hand
+  for (const DecLaunch& e : table) {
+    int64_t h = 0;
+    switch (e.kind) {
+      case DL_PRE:
+        h = sum_hi = reach_conv(sum_hi, e.pad_left);
+        break;
+      case DL_UP:
+        h = hi = r = sum_hi = reach_convt(sum_hi, e.tk, e.convt_u, e.tp);
+        break;
+      case DL_C1: case DL_C2:
+        h = r = reach_conv(r, e.pad_left);            // (+ the skip path: r only grows)
+        if (e.epi == EPI_RESID_ACC) { h = sum_hi = sum_hi > r ? sum_hi : r; r = hi; }
+        break;
+      case DL_POST:
+        h = sum_hi = reach_conv(sum_hi, e.pad_left + e.reflect1);
+        break;
+      case DL_TAIL:
+        h = e.hop * sum_hi + e.n_fft / 2 - 1;         // frame f covers sub-band samples [hop f - n_fft / 2, hop f + n_fft / 2)
+        if (e.bands > 1) h = e.bands * h + e.taps / 2;   // sample n reads sub-band samples [(n - 31) / bands, (n + 31) / bands]
+        break;
     }
-    hi = sum_hi;
+    out->push_back({e.kind, e.stage, e.j, e.q, e.rate, (int)(h - ((int64_t)e.rate * len - 1))});
   }
-  hi = reach_conv(hi, (kPost - 1) / 2 + 1);           // frame f reads x[f - 4 .. f + 2] (ReflectionPad1d((1, 0)))
-  put(4, 2, 0, 0, hi);
-  hi = hop * hi + n_fft / 2 - 1;                      // frame f covers sub-band samples [hop f - n_fft / 2, hop f + n_fft / 2)
-  rate *= hop;
-  if (!sb) { hi = bands * hi + taps / 2; rate *= bands; }   // sample n reads sub-band samples [(n - 31) / bands, (n + 31) / bands]
-  put(5, 2, 0, 0, hi);
 }
 
 // The row-exact ragged decode (mbv_decode_ragged): run_decoder on the rows of one class (run_decoder_ragged below).
@@ -1133,39 +1221,153 @@ struct RaggedRows {
                            // pooled: the shortest UTTERANCE a row of the run is cut from
 };
 
-int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, const float* gvec,
-                int B, int Td, const mbv_outputs* outs, hipStream_t s, Bump& sc, const DecodeRange* rg = nullptr,
-                const RaggedRows* rr = nullptr) {
+// What the scratch of one decoder run depends on, host facts all: z [B, I, zstride], first Td frames valid; lens: frame
+// lengths are given; cond: a speaker vector reaches a conditioned model; own_o: no caller takes the waveform.
+struct DecCall { int B, Td, zstride; bool lens, cond, own_o, ranged, ragged; };
+
+// The scratch of one run (carve_decoder), and the two modes decided with it.
+// trim — the opt-in trimmed decode (option "trim"; the caller takes only `o` and trims by y_lengths): a conv computes
+// the column tiles that hold frames below (len_b + kTrimMargin) * rate of its utterance and nothing behind them.  The
+// decoder's one-sided receptive field is 25.2 z-frames (conv_pre 3 + ups 2 + 0.5, the k = 11 ResBlocks 15 + 3.75,
+// conv_post / iSTFT / PQMF < 1), so whatever sits behind an utterance's limit — stale scratch — stays more than
+// 6 frames away from its valid samples: those are bitwise the default's.  Column-tile maps are built on the device
+// from the lengths, one per (num, add, T, tile width) geometry; the ragged mode uses them with a margin of zero.
+// tail — "tail_once" (default on): the decoder gets z * y_mask, so behind S_b = rate len_b + reach of a
+// ResBlock launch (decoder_tail_plan) row b's output is the zero-input response, a function of the column alone
+// and the same in every row.  Only the donor — the shortest row — computes it: the other rows drop the column
+// tiles that lie wholly behind their S_b from the launch (the trim-map path of the conv kernel), and a copy kernel
+// behind the launch writes the donor's values there.  An output element's chain of operations does not depend on
+// its tile or row, so every tensor holds bitwise what it held.  A launch that lost tiles ends in a partial round
+// of the persistent grid: the three ResBlocks then run on three streams at any batch size, so that another launch
+// fills it.  Not with per-row conditioning (the tails differ), split-K, conv_bf16, one row, or modes with own maps.
+constexpr int kTrimMargin = 32;
+struct DecBufs {
+  DecCall call;
+  bool trim, tail;
+  float* x0;
+  struct TrimMap { int num, add, T, bn; int* map; bool built; };
+  TrimMap trim_maps[12]; int n_trim;   // one per geometry: at most two tile widths for each of four (num, add)
+  int trim_of[48];                 // per table entry (1 + 2 (1 + 18) + 2 at most): its trim map, -1 none
+  struct TailMap { int kind, j, q, bn; const int* map; };
+  // per stage: u, t1 / r of each ResBlock (its own when the three run concurrently), xs, cond vectors, tail maps
+  struct Stage { float *u, *t1s[3], *rs[3], *xs, *cb[3]; bool conc; int n_tail; TailMap tail_maps[kTailMapJobs]; TailMapJobs jobs; } st[2];
+  int Bc;                          // rows per conv_post + tail sub-batch; 0: one utterance's x_post reaches 2 GiB
+  float *xpost, *otmp;
+};
+
+void carve_decoder(const mbv_model* m, const DecCall& k, Bump& sc, DecBufs* out) {
   const mbv_config& c = m->cfg;
+  const std::vector<DecLaunch>& table = m->dec_table;
+  const int B = k.B, Td = k.Td;
+  DecBufs& d = *out;                                // (plain data, filled in place: a carve allocates nothing)
+  std::memset(&d, 0, sizeof d); d.call = k;
+  d.trim = k.ragged ? !m->splitk : (m->trim && k.lens && !m->splitk && c.decoder != MBV_DEC_SINGLEBAND);
+  d.tail = tail_mode(m) && !d.trim && !k.ragged && !k.ranged && k.lens && B > 1 && B <= 65535 && !k.cond;
+  auto planned = [&](const DecLaunch& e) {
+    ConvArgs a = dec_planner_args(e, Td, B, m->splitk, m->Wsplit(0) ? 3 : 0,
+                                  k.cond && e.stage >= 0 && e.stage < 2 && m->rb[e.stage * 3 + e.j].cw.present);
+    if (e.kind == DL_PRE) { a.x_rstride = k.zstride; a.x_bstride = (int64_t)e.Cin * k.zstride; }   // (z as the caller holds it)
+    return a;
+  };
+  std::vector<TailLaunch> tail_plan;
+  if (d.tail) decoder_tail_plan(table, &tail_plan);
+  d.x0 = sc.take<float>((size_t)B * table[0].M * Td);
+  for (const DecLaunch& up : table) {
+    if (up.kind != DL_UP) continue;
+    DecBufs::Stage& st = d.st[up.stage];
+    const int ch = up.M / up.convt_u, Lo = up.rate * Td;
+    const size_t n = (size_t)B * ch * Lo;
+    // tail maps of this stage's ResBlock launches; a route that takes no map (narrow, split-batch, half-height) is kept
+    const long stage_tiles = (long)B * ((Lo + 383) / 384) * ((ch + 127) / 128);
+    if (d.tail && tail_stage(tail_mode(m), B, stage_tiles))
+      for (size_t n_e = 0; n_e < table.size() && st.n_tail < kTailMapJobs; ++n_e) {
+        const DecLaunch& e = table[n_e];
+        if (e.stage != up.stage || (e.kind != DL_C1 && e.kind != DL_C2)) continue;
+        const ConvArgs a = planned(e);
+        const int bn = conv1d_trim_bn(a);
+        if (!bn || conv1d_plan(a, false).route != conv1d_plan(a, true).route) continue;
+        st.jobs.job[st.n_tail] = {e.rate, tail_plan[n_e].reach, Lo, bn, nullptr};
+        st.tail_maps[st.n_tail++] = {e.kind, e.j, e.q, bn, nullptr};
+      }
+    // The three ResBlocks of a stage read the same input and only meet in the running sum xs.  When one of their convs
+    // cannot fill the chip (decoder_stage_concurrent) they run on three streams — own temporaries each, the three xs
+    // updates chained by events in the order of the one-stream schedule, so the result is bitwise the same.
+    st.conc = decoder_stage_concurrent(m, B, ch, Lo, st.n_tail > 0) && !d.trim;
+    st.u = sc.take<float>(n);
+    for (int j = 0; j < 3; ++j) {
+      st.t1s[j] = j == 0 || st.conc ? sc.take<float>(n) : st.t1s[0];
+      st.rs[j] = j == 0 || st.conc ? sc.take<float>(n) : st.rs[0];
+    }
+    st.xs = sc.take<float>(n);
+  }
+  // ---- cond vectors: x = x + cond(g)   (modules.py:214-215)
+  for (const DecLaunch& up : table)
+    for (int j = 0; j < 3 && up.kind == DL_UP; ++j)
+      if (k.cond && m->rb[up.stage * 3 + j].cw.present) d.st[up.stage].cb[j] = sc.take<float>((size_t)B * (up.M / up.convt_u));
+  // ---- x_post.  The fused iSTFT kernels address it with 32-bit byte offsets: a batch whose x_post would reach 2 GiB
+  // runs conv_post + iSTFT in sub-batches (same T', same kernels: bitwise an unsplit launch).
+  const DecLaunch& post = table[table.size() - 2];
+  const int64_t utt_bytes = (int64_t)post.M * (post.num * (int64_t)Td + post.add) * 4;
+  int64_t cap_bytes = (1LL << 31) - 1;
+  if (m->xpost_chunk_bytes > 0 && m->xpost_chunk_bytes < cap_bytes) cap_bytes = m->xpost_chunk_bytes;
+  d.Bc = utt_bytes > (1LL << 31) - 1 ? 0 : (int)std::min<int64_t>(B, std::max<int64_t>(1, cap_bytes / utt_bytes));
+  // ---- trim maps, one per geometry among the launches (a split conv_post keeps every tile: the maps are per full batch)
+  // trim_of[entry]: its map, or -1 where the launch takes none (a route without trimmed launches: conv1d_trim_bn 0)
+  for (size_t n_e = 0; n_e < table.size(); ++n_e) {
+    const DecLaunch& e = table[n_e];
+    d.trim_of[n_e] = -1;
+    if (!d.trim || e.kind == DL_TAIL || (e.kind == DL_POST && d.Bc != B)) continue;
+    const ConvArgs a = planned(e);
+    const int bn = conv1d_trim_bn(a);
+    for (int t = 0; bn && t < d.n_trim && d.trim_of[n_e] < 0; ++t)
+      if (d.trim_maps[t].num == e.num && d.trim_maps[t].add == e.add && d.trim_maps[t].T == a.T && d.trim_maps[t].bn == bn) d.trim_of[n_e] = t;
+    if (bn && d.trim_of[n_e] < 0 && d.n_trim < 12) {
+      d.trim_of[n_e] = d.n_trim;
+      d.trim_maps[d.n_trim++] = {e.num, e.add, a.T, bn, sc.take<int>(launch_trim_map_ints(B, a.T, bn)), false};
+    }
+  }
+  for (auto& st : d.st)
+    for (int i = 0; i < st.n_tail; ++i)
+      st.tail_maps[i].map = st.jobs.job[i].out = sc.take<int>(launch_tail_map_ints(B, st.jobs.job[i].T, st.jobs.job[i].BN));
+  d.xpost = sc.take<float>((size_t)d.Bc * (utt_bytes / 4));
+  if (k.own_o) d.otmp = sc.take<float>((size_t)B * table.back().rate * Td);
+}
+
+// One decoder run on scratch laid out for it (lay_out with carve_decoder for the same call).
+int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gvec, const mbv_outputs* outs,
+                hipStream_t s, DecBufs& d, const DecodeRange* rg = nullptr, const RaggedRows* rr = nullptr) {
+  const mbv_config& c = m->cfg;
+  const std::vector<DecLaunch>& table = m->dec_table;
+  const int B = d.call.B, Td = d.call.Td, zstride = d.call.zstride, gin = c.gin_channels;
   ++m->decoder_runs;
   if (rr) zlens = rr->len;
+  float* o = rg ? rg->o : rr ? rr->o : outs ? outs->o : nullptr;
+  const bool pooled = rg && rg->rows;      // (every row stores through its own table entry)
+  if (d.call.lens != (zlens != nullptr) || d.call.cond != (gvec && gin) || d.call.ranged != (rg != nullptr) ||
+      d.call.ragged != (rr != nullptr) || d.call.own_o != (!o && !pooled))
+    return m->fail("internal error: the decoder's scratch was laid out for another call");
+  if (!d.Bc)
+    return m->fail("utterance too long for one launch: %d frames (x_post of ONE utterance must stay below 2 GiB)", Td);
+  if (!o) o = d.otmp;
   // ranged decode, default mode: the length rules of the conv planner see the one-shot lengths (conv1d_plan)
   const int rt_num = rg && !m->splitk ? rg->t_full : 0;
-  const int I = c.inter_channels, C0 = c.upsample_initial_channel, gin = c.gin_channels;
   hipStream_t const s_main = s;
-  if (sc.off + decoder_scratch_bytes(c, B, Td, (rr || rg) ? 0 : tail_mode(m)) > sc.cap) return m->fail("internal error: decoder scratch arena undersized");
-  float* x0 = sc.take<float>((size_t)B * C0 * Td);
+  const int* const rr_lens[3] = {rr ? rr->len : nullptr, rr ? rr->len_u : nullptr, rr ? rr->len_uu : nullptr};
+  // an entry's launch: its shape from the table, on real tensors (nb rows: the sub-batches of conv_post)
+  auto conv = [&](const DecLaunch& e, const PConv& p, const float* x, float* y, float in_slope, int nb) {
+    ConvArgs a = conv_bind(m, p, dec_shape(e, Td, nb, m->splitk), x, y);
+    a.in_slope = in_slope;
+    if (rr) a.in_lens = rr_lens[e.lens];
+    return a;
+  };
   HIPCHK(m, hipEventRecord(m->evk[0], s));
-  // Opt-in trimmed decode (option "trim"; the caller takes only `o` and trims by y_lengths): a conv computes the
-  // column tiles that hold frames below (len_b + kTrimMargin) * rate of its utterance and nothing behind them.  The
-  // decoder's one-sided receptive field is 25.2 z-frames (conv_pre 3 + ups 2 + 0.5, the k = 11 ResBlocks 15 + 3.75,
-  // conv_post / iSTFT / PQMF < 1), so whatever sits behind an utterance's limit — stale scratch — stays more than
-  // 6 frames away from its valid samples: those are bitwise the default's.  Column-tile maps are built on the device
-  // from ylen32 (no extra host sync), one per (rate, tile width) geometry.
-  constexpr int kTrimMargin = 32;
-  // (the ragged mode uses the same tile maps with a margin of zero: nothing behind a row's end is computed)
-  const bool trim = rr ? !m->splitk : (m->trim && zlens != nullptr && !m->splitk && c.decoder != MBV_DEC_SINGLEBAND);
-  const int trim_margin = rr ? 0 : kTrimMargin;
-  struct TrimKey { int num, add, T, bn; const int* map; };
-  std::vector<TrimKey> trim_maps;
-  // Ragged mode: the classes come from decoder_conv_args' restatement of the convs below.  Tie them to what is
-  // really launched: every conv, planned for one utterance of the run's shortest row and of its longest, must fall
-  // on the same side of the narrow / tiled divide — else rows of this run would sum in an order their stand-alone
-  // decode does not use.  (num, add: the conv's columns per z-frame, as for the tile maps.)
+  // Ragged mode: the classes come from ragged_classes' reading of the table.  Tie them to what is really launched:
+  // every conv, planned for one utterance of the run's shortest row and of its longest, must fall on the same side of
+  // the narrow / tiled divide — else rows of this run would sum in an order their stand-alone decode does not use.
   // Pooled (rg and rr): the rows are windows, and what must agree is the plan of the UTTERANCES they are cut from:
   // the shortest (rr->t_min) against the longest (rg->t_full), and the launch itself, which plans with the longest
   // in place of its own columns (route_T), against both.
-  bool route_drift = false;
+  bool route_drift = false, tail_drift = false;
   auto narrow_alone = [&](const ConvArgs& a, int num, int add, int len) {
     ConvArgs s1 = a;
     s1.B = 1; s1.trim_map = nullptr;
@@ -1177,115 +1379,62 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     const int r = conv1d_plan(s1, false).route;
     return r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH;
   };
-  auto with_trim = [&](ConvArgs& a, int num, int add) {
+  auto with_trim = [&](ConvArgs& a, const DecLaunch& e) {
     if (rr && !m->splitk) {
-      const bool narrow_long = narrow_alone(a, num, add, rg ? rg->t_full : Td);
-      if (narrow_alone(a, num, add, rr->t_min) != narrow_long) route_drift = true;
+      const bool narrow_long = narrow_alone(a, e.num, e.add, rg ? rg->t_full : Td);
+      if (narrow_alone(a, e.num, e.add, rr->t_min) != narrow_long) route_drift = true;
       if (rg) {
-        const int r = conv1d_plan(a, false, rt_num * num + add).route;
+        const int r = conv1d_plan(a, false, rt_num * e.num + e.add).route;
         if ((r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH) != narrow_long) route_drift = true;
       }
     }
-    if (!trim) return;
-    const int bn = conv1d_trim_bn(a);
-    if (!bn) return;
-    for (const auto& k : trim_maps)
-      if (k.num == num && k.add == add && k.T == a.T && k.bn == bn) { a.trim_map = k.map; a.trim_bn = bn; return; }
-    int* map = sc.take<int>(launch_trim_map_ints(B, a.T, bn));
-    launch_trim_map(zlens, B, num, num * trim_margin + add, a.T, bn, map, s_main);
-    trim_maps.push_back({num, add, a.T, bn, map});
-    a.trim_map = map; a.trim_bn = bn;
+    if (!d.trim) return;
+    // (the map was laid out from the entry's shape alone, like a tail map: the launch itself must agree)
+    const int at = d.trim_of[&e - table.data()], bn = conv1d_trim_bn(a);
+    if (bn != (at < 0 ? 0 : d.trim_maps[at].bn)) { tail_drift = true; return; }
+    if (at < 0) return;
+    DecBufs::TrimMap& k = d.trim_maps[at];
+    if (!k.built) launch_trim_map(zlens, B, e.num, e.num * (rr ? 0 : kTrimMargin) + e.add, a.T, bn, k.map, s_main);
+    k.built = true;
+    a.trim_map = k.map; a.trim_bn = bn;
   };
-  // "tail_once" (default on): the decoder gets z * y_mask, so behind S_b = rate len_b + reach of a
-  // ResBlock launch (decoder_tail_plan) row b's output is the zero-input response, a function of the column alone
-  // and the same in every row.  Only the donor — the shortest row — computes it: the other rows drop the column
-  // tiles that lie wholly behind their S_b from the launch (the trim-map path of the conv kernel), and a copy kernel
-  // behind the launch writes the donor's values there.  An output element's chain of operations does not depend on
-  // its tile or row, so every tensor holds bitwise what it held.  A launch that lost tiles ends in a partial round
-  // of the persistent grid: the three ResBlocks then run on three streams at any batch size, so that another
-  // launch fills it.  Not with per-row conditioning in the ResBlocks (the tails differ), split-K, conv_bf16, one
-  // row, or the modes that bring their own maps.
-  const bool tail = tail_mode(m) && !trim && !rr && !rg && zlens && B > 1 && B <= 65535 && !(gvec && gin);
-  bool tail_drift = false;
-  std::vector<TailLaunch> tail_plan;
-  if (tail) decoder_tail_plan(c, &tail_plan);
-  struct TailMap { int kind, j, q, bn; const int* map; };
-  std::vector<TailMap> tail_maps;                      // of the current stage
-  auto with_tail = [&](ConvArgs& a, int kind, int j, int q) -> const TailMap* {
-    for (const auto& t : tail_maps)
-      if (t.kind == kind && t.j == j && t.q == q) {
-        // (the map was planned before the fork from the launch's shape alone: the launch itself must agree)
-        if (conv1d_trim_bn(a) != t.bn) { tail_drift = true; return nullptr; }
-        a.trim_map = t.map; a.trim_bn = t.bn;
-        return &t;
-      }
+  const DecBufs::Stage* tail_stage_bufs = nullptr;  // the current stage, for its tail maps
+  auto with_tail = [&](ConvArgs& a, const DecLaunch& e) -> const DecBufs::TailMap* {
+    for (int n_t = 0; n_t < tail_stage_bufs->n_tail; ++n_t) {
+      const DecBufs::TailMap& t = tail_stage_bufs->tail_maps[n_t];
+      if (t.kind != e.kind || t.j != e.j || t.q != e.q) continue;
+      // (the map was planned before the fork from the launch's shape alone: the launch itself must agree)
+      if (conv1d_trim_bn(a) != t.bn) { tail_drift = true; return nullptr; }
+      a.trim_map = t.map; a.trim_bn = t.bn;
+      return &t;
+    }
     return nullptr;
   };
-  auto fill_tail = [&](const ConvArgs& a, const TailMap* t, hipStream_t st) {
-    if (t) launch_tail_fill(a.y, a.y_bstride, B, a.M, a.T, t->bn, t->map, st);
-  };
   {
-    ConvArgs a = conv_args(m, m->conv_pre, z, (int64_t)I * zstride, Td, x0, (int64_t)C0 * Td, Td, B);
+    const DecLaunch& e = table[0];
+    ConvArgs a = conv(e, m->conv_pre, z, d.x0, 1.f, B);
+    a.x_bstride = (int64_t)e.Cin * zstride;
     a.x_rstride = zstride;
     a.in_lens = zlens;
-    with_trim(a, 1, 0);
+    with_trim(a, e);
     launch_conv1d(a, s, rt_num);
   }
-  m->stages["dec_conv_pre"] = {x0, (int64_t)B * C0 * Td};
-  const float* cur = x0;
-  int L = Td;
-  float* xs = nullptr;
-  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
-  const int us = sb ? 8 : 4;                       // upsample stride of both stages
+  m->stages["dec_conv_pre"] = {d.x0, (int64_t)B * table[0].M * Td};
+  const float* cur = d.x0;
+  size_t next = 1;                                   // the table entry of the next launch
   for (int i = 0; i < 2; ++i) {
-    const int ch = C0 >> (i + 1);
-    const int Lo = us * L;
-    const size_t n = (size_t)B * ch * Lo;
-    float* u = sc.take<float>(n);
-    // The three ResBlocks of a stage read the same input and only meet in the running sum xs.  When one
-    // of their convs cannot fill the chip (single utterances, small batches: decoder_stage_concurrent)
-    // they run on three streams — own temporaries each, the three xs updates chained by events in the
-    // order of the one-stream schedule, so the result is bitwise the same.
-    // tail maps of this stage's ResBlock launches, all from one launch on the caller's stream (before the fork).
-    // A launch the planner sends to a route that takes no map (narrow, split-batch, half-height) keeps that route.
-    tail_maps.clear();
-    const long stage_tiles = (long)B * ((Lo + 383) / 384) * ((ch + 127) / 128);
-    if (tail && tail_stage(tail_mode(m), B, stage_tiles)) {
-      TailMapJobs jobs{};
-      int nj = 0;
-      for (const auto& tl : tail_plan) {
-        if (tl.stage != i || (tl.kind != 2 && tl.kind != 3) || nj == kTailMapJobs) continue;
-        const auto& R = m->rb[i * 3 + tl.j];
-        const bool second = tl.kind == 3 && c.resblock_type != 2;
-        ConvArgs a = conv_args(m, second ? R.c2[tl.q] : R.c1[tl.q], u, (int64_t)ch * Lo, Lo, u, (int64_t)ch * Lo, Lo, B,
-                               second ? 1 : c.resblock_dilations[tl.j][tl.q]);
-        a.in_slope = kLrelu;
-        if (tl.kind == 3) { a.epi = EPI_RESID; a.res = u; a.res_bstride = (int64_t)ch * Lo; }
-        const int bn = conv1d_trim_bn(a);
-        if (!bn || conv1d_plan(a, false).route != conv1d_plan(a, true).route) continue;
-        int* map = sc.take<int>(launch_tail_map_ints(B, Lo, bn));
-        jobs.job[nj++] = {Lo / Td, tl.reach, Lo, bn, map};
-        tail_maps.push_back({tl.kind, tl.j, tl.q, bn, map});
-      }
-      launch_tail_maps(zlens, B, jobs, nj, m->tail_cnt, s_main);
-    }
-    const bool conc = decoder_stage_concurrent(m, B, ch, Lo, !tail_maps.empty()) && !trim;
-    float *t1s[3], *rs[3];
-    t1s[0] = sc.take<float>(n);
-    rs[0] = sc.take<float>(n);
-    for (int j = 1; j < 3; ++j) {
-      t1s[j] = conc ? sc.take<float>(n) : t1s[0];
-      rs[j] = conc ? sc.take<float>(n) : rs[0];
-    }
-    xs = sc.take<float>(n);
+    DecBufs::Stage& bufs = d.st[i];
+    const DecLaunch& up = table[next++];
+    const int ch = up.M / up.convt_u;
+    const size_t n = (size_t)B * ch * up.rate * Td;
+    float *const u = bufs.u, *const xs = bufs.xs;
+    const bool conc = bufs.conc;
+    // tail maps of this stage's ResBlock launches, all from one launch on the caller's stream (before the fork)
+    tail_stage_bufs = &bufs;
+    launch_tail_maps(zlens, B, bufs.jobs, bufs.n_tail, m->tail_cnt, s_main);
     {
-      ConvArgs a = conv_args(m, m->upc[i], cur, (int64_t)m->upc[i].Cin * L, L, u, (int64_t)ch * Lo, L, B);
-      a.pad_left = us == 4 ? 2 : 1;
-      a.in_slope = kLrelu;
-      a.epi = EPI_CONVT;
-      a.convt_u = us;
-      if (rr) a.in_lens = i == 0 ? rr->len : rr->len_u;
-      with_trim(a, L / Td, 0);                      // tiles run over INPUT frames (rate of the stage below)
+      ConvArgs a = conv(up, m->upc[i], cur, u, kLrelu, B);
+      with_trim(a, up);                             // tiles run over INPUT frames (rate of the stage below)
       launch_conv1d(a, s);
     }
     m->stages[i == 0 ? "dec_up_0" : "dec_up_1"] = {u, (int64_t)n};
@@ -1300,8 +1449,8 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     for (int j = 0; j < 3; ++j) {
       const auto& R = m->rb[i * 3 + j];
       hipStream_t s = (conc && j > 0) ? m->aux[j - 1] : s_main;   // this ResBlock's stream
-      float* const t1 = t1s[j];
-      float* const r = rs[j];
+      float* const t1 = bufs.t1s[j];
+      float* const r = bufs.rs[j];
       // split-K scratch (low-latency mode): a third each, so that concurrent convs never share partials or tickets
       auto own_ws = [&](ConvArgs& a) {
         if (!conc) return;
@@ -1312,72 +1461,32 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
       };
       const float* cadd = nullptr;
       if (gvec && gin && R.cw.present) {           // x = x + cond(g)   (modules.py:214-215)
-        float* cb = sc.take<float>((size_t)B * ch);
-        launch_cond_gemv(gvec, nullptr, nullptr, m->W(R.cw.off), m->W(R.cb.off), cb, B, gin, ch, s);
-        cadd = cb;
+        launch_cond_gemv(gvec, nullptr, nullptr, m->W(R.cw.off), m->W(R.cb.off), bufs.cb[j], B, gin, ch, s);
+        cadd = bufs.cb[j];
       }
+      // ResBlock1: x = c2(lrelu(c1_d(lrelu(x)))) + x per dilation, c1 into t1; ResBlock2 (modules.py:251-262): x =
+      // conv_d(lrelu(x)) + x with the one conv of its steps in c1.  The step's result goes to r, the last one's into xs.
       const float* state = u;
-      if (c.resblock_type == 2) {
-        // ResBlock2 (modules.py:251-262): x = conv_d(lrelu(x)) + x for d in dilations
-        for (int q = 0; q < 2; ++q) {
-          const int d = c.resblock_dilations[j][q];
-          ConvArgs a = conv_args(m, R.c1[q], state, (int64_t)ch * Lo, Lo, r, (int64_t)ch * Lo, Lo, B, d);
-          a.in_slope = kLrelu;
-          a.res = state; a.res_bstride = (int64_t)ch * Lo;
-          if (q == 0) { a.chan_add = cadd; a.res_chan_add = cadd; }
-          if (q == 0) {
-            a.epi = EPI_RESID;
-          } else {
-            a.epi = EPI_RESID_ACC;
-            a.y = xs;
-            a.accum_in = j == 0 ? nullptr : xs;
-            a.out_scale = j == 2 ? (1.f / 3.f) : 1.f;
-          }
-          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
-          with_trim(a, Lo / Td, 0);
-          const TailMap* tm = with_tail(a, 3, j, q);
-          launch_conv1d(a, s, rt_num * (Lo / Td));
-          fill_tail(a, tm, s);
-          state = r;
+      for (; table[next].stage == i && table[next].j == j; ++next) {
+        const DecLaunch& e = table[next];
+        const bool first = e.kind == DL_C1, second = !first && c.resblock_type != 2;
+        ConvArgs a = conv(e, second ? R.c2[e.q] : R.c1[e.q], second ? t1 : state, first ? t1 : r, kLrelu, B);
+        if (e.res) a.res = state;
+        if (e.chan_add) a.chan_add = cadd;
+        if (e.res_chan_add) a.res_chan_add = cadd;
+        if (e.epi == EPI_RESID_ACC) {                // xs (+)= resblock output ; /3 on the last
+          a.y = xs;
+          a.accum_in = j == 0 ? nullptr : xs;
+          a.out_scale = j == 2 ? (1.f / 3.f) : 1.f;
+          if (conc && j > 0) HIPCHK(m, hipStreamWaitEvent(s, m->ev_rb[j - 1], 0));   // xs of the ResBlock before
         }
-        continue;
-      }
-      for (int q = 0; q < 3; ++q) {
-        const int d = c.resblock_dilations[j][q];
-        {
-          ConvArgs a = conv_args(m, R.c1[q], state, (int64_t)ch * Lo, Lo, t1, (int64_t)ch * Lo, Lo, B, d);
-          a.in_slope = kLrelu;
-          if (q == 0) a.chan_add = cadd;
-          own_ws(a);
-          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
-          with_trim(a, Lo / Td, 0);
-          const TailMap* tm = with_tail(a, 2, j, q);
-          launch_conv1d(a, s, rt_num * (Lo / Td));
-          fill_tail(a, tm, s);
-        }
-        {
-          ConvArgs a = conv_args(m, R.c2[q], t1, (int64_t)ch * Lo, Lo, r, (int64_t)ch * Lo, Lo, B, 1);
-          a.in_slope = kLrelu;
-          a.res = state; a.res_bstride = (int64_t)ch * Lo;
-          if (q == 0) a.res_chan_add = cadd;
-          if (q < 2) {
-            a.epi = EPI_RESID;
-          } else {                                   // xs (+)= resblock output ; /3 on the last
-            a.epi = EPI_RESID_ACC;
-            a.y = xs;
-            a.accum_in = j == 0 ? nullptr : xs;
-            a.out_scale = j == 2 ? (1.f / 3.f) : 1.f;
-            if (conc && j > 0) HIPCHK(m, hipStreamWaitEvent(s, m->ev_rb[j - 1], 0));   // xs of the ResBlock before
-          }
-          own_ws(a);
-          if (rr) a.in_lens = i == 0 ? rr->len_u : rr->len_uu;
-          with_trim(a, Lo / Td, 0);
-          const TailMap* tm = with_tail(a, 3, j, q);
-          launch_conv1d(a, s, rt_num * (Lo / Td));
-          fill_tail(a, tm, s);
-          if (conc && q == 2) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
-        }
-        state = r;
+        own_ws(a);
+        with_trim(a, e);
+        const DecBufs::TailMap* tm = with_tail(a, e);
+        launch_conv1d(a, s, rt_num * e.num);
+        if (tm) launch_tail_fill(a.y, a.y_bstride, B, a.M, a.T, tm->bn, tm->map, s);
+        if (conc && e.epi == EPI_RESID_ACC) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
+        if (!first) state = r;
       }
     }
     return 0;
@@ -1389,88 +1498,56 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
     if (conc) HIPCHK(m, hipStreamWaitEvent(s_main, m->ev_rb[2], 0));
     m->stages[i == 0 ? "dec_res_0" : "dec_res_1"] = {xs, (int64_t)n};
     cur = xs;
-    L = Lo;
   }
-  const int Fr = L + 1;
-  const int chl = C0 >> 2;
-  const int prow = sb ? 18 : 72;
-  // The fused iSTFT kernels address x_post with 32-bit byte offsets: a batch whose x_post would
-  // reach 2 GiB runs conv_post + iSTFT in sub-batches (same T', same kernels, per-utterance
-  // arithmetic unchanged: results are bitwise those of an unsplit launch).
-  const int64_t utt_bytes = (int64_t)prow * Fr * 4;
-  int64_t cap_bytes = (1LL << 31) - 1;
-  if (m->xpost_chunk_bytes > 0 && m->xpost_chunk_bytes < cap_bytes) cap_bytes = m->xpost_chunk_bytes;
-  if (utt_bytes > (1LL << 31) - 1)
-    return m->fail("utterance too long for one launch: %d frames (x_post of ONE utterance must stay below 2 GiB)", Td);
-  int Bc = (int)(cap_bytes / utt_bytes);
-  if (Bc < 1) Bc = 1;
-  if (Bc > B) Bc = B;
-  float* xpost = sc.take<float>((size_t)Bc * prow * Fr);
-  float* o = rg ? rg->o : rr ? rr->o : outs ? outs->o : nullptr;
-  float* otmp = nullptr;
-  const bool pooled = rg && rg->rows;      // (every row stores through its own table entry)
-  if (!o && !pooled) { otmp = sc.take<float>((size_t)B * 256 * Td); o = otmp; }
+  const DecLaunch &post = table[next], &wave = table[next + 1];
+  const bool sb = wave.bands == 1;
+  const int L = post.num * Td, Fr = L + post.add, prow = post.M, Bc = d.Bc;
+  const int bins = wave.n_fft / 2 + 1;             // rows of spec / phase per band
+  float* const xpost = d.xpost;
   // ranged: window sub-band samples (MB / MS) or output quads (SB) of the kept frames, 64 per z-frame either way
-  IstftRange keep{rg ? 64 * rg->keep_first : 0, rg ? 64 * (rg->keep_first + rg->keep_count) : 0,
+  const int upf = wave.rate / 4;                   // those units per z-frame
+  IstftRange keep{rg ? upf * rg->keep_first : 0, rg ? upf * (rg->keep_first + rg->keep_count) : 0,
                   rg ? rg->o_row_stride : 0, nullptr, nullptr};
-  if (rr) keep = IstftRange{0, 64 * Td, rr->o_row_stride, rr->len, rr->row_map};      // every tile of the class, cut per row in the kernel
-  const int64_t M4 = (int64_t)(sb ? 4 : 256) * (sb ? (Fr - 1) : Td);          // waveform samples per utterance
+  if (rr) keep = IstftRange{0, upf * Td, rr->o_row_stride, rr->len, rr->row_map};      // every tile of the class, cut per row in the kernel
+  const int64_t M4 = (int64_t)wave.rate * Td;      // waveform samples per utterance
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int nb = B - b0 < Bc ? B - b0 : Bc;
     {
-      ConvArgs a = conv_args(m, m->conv_post, cur + (size_t)b0 * chl * L, (int64_t)chl * L, L, xpost,
-                             (int64_t)prow * Fr, Fr, nb);
-      a.in_slope = 0.01f;                              // F.leaky_relu default slope (models.py:363)
-      a.reflect1 = 1;                                  // ReflectionPad1d((1,0)) (models.py:364)
-      if (rr) a.in_lens = rr->len_uu + b0;             // (in frames of the unpadded input: us^2 len_b + 1 padded ones)
-      if (nb == B) with_trim(a, L / Td, 1);            // (a split run keeps every tile: the maps are per full batch)
+      ConvArgs a = conv(post, m->conv_post, cur + (size_t)b0 * post.Cin * L, xpost, 0.01f, nb);   // F.leaky_relu default slope (models.py:363)
+      if (rr) a.in_lens += b0;                         // (in frames of the unpadded input: us^2 len_b + 1 padded ones)
+      if (nb == B) with_trim(a, post);                 // (a split run keeps every tile: the maps are per full batch)
       launch_conv1d(a, s);
     }
     if (b0 == 0) HIPCHK(m, hipEventRecord(m->evk[1], s));   // (a split run interleaves conv_post and iSTFT launches: evk_split below)
+    // Only the one-shot decode takes o_mb / spec / phase and "trim" in the tail.  Ranged: this sub-batch's rows of the
+    // caller's o; ragged: every row finds its own through row_map; pooled: through its PoolRow.
+    const bool plain = !rg && !rr;
+    float* const ob = pooled ? nullptr : rr ? o : o + (size_t)b0 * (rg ? rg->o_row_stride : M4);
+    auto extra = [&](float* p, int64_t per_row) { return plain && p ? p + (size_t)b0 * per_row : nullptr; };
+    IstftRange kb = keep;
+    if (rr) { kb.row_lens += b0; kb.row_map += b0; }
     if (sb) {
       IstftSbArgs ia{};
-      ia.x_post = xpost; ia.o = o + (size_t)b0 * M4;
-      ia.spec = outs && outs->spec ? outs->spec + (size_t)b0 * 9 * Fr : nullptr;
-      ia.phase = outs && outs->phase ? outs->phase + (size_t)b0 * 9 * Fr : nullptr;
+      ia.x_post = xpost; ia.o = ob;
+      ia.spec = extra(outs ? outs->spec : nullptr, bins * Fr);
+      ia.phase = extra(outs ? outs->phase : nullptr, bins * Fr);
       ia.B = nb; ia.F = Fr; ia.exact_math = m->exact_math; ia.prescaled = 1;
-      if (pooled) {
-        ia.o = nullptr; ia.spec = ia.phase = nullptr;
-        launch_istft_single_pool(ia, rg->rows + b0, rg->max_keep, s);
-      } else if (rr) {
-        IstftRange kb = keep;
-        kb.row_lens += b0; kb.row_map += b0;
-        ia.o = o; ia.spec = ia.phase = nullptr;
-        launch_istft_single_range(ia, kb, s);
-      } else if (rg) {
-        ia.o = o + (size_t)b0 * rg->o_row_stride; ia.spec = ia.phase = nullptr;
-        launch_istft_single_range(ia, keep, s);
-      } else {
-        launch_istft_single(ia, s);
-      }
+      if (pooled) launch_istft_single_pool(ia, rg->rows + b0, rg->max_keep, s);
+      else if (!plain) launch_istft_single_range(ia, kb, s);
+      else launch_istft_single(ia, s);
     } else {
       IstftArgs ia{};
       const bool ms = c.decoder == MBV_DEC_MULTISTREAM;
-      ia.x_post = xpost; ia.filt = m->W(m->filt.off); ia.o = o + (size_t)b0 * M4;
-      ia.o_mb = outs && outs->o_mb ? outs->o_mb + (size_t)b0 * (ms ? 1024 : 256) * Td : nullptr;
-      ia.spec = outs && outs->spec ? outs->spec + (size_t)b0 * 36 * Fr : nullptr;
-      ia.phase = outs && outs->phase ? outs->phase + (size_t)b0 * 36 * Fr : nullptr;
+      ia.x_post = xpost; ia.filt = m->W(m->filt.off); ia.o = ob;
+      ia.o_mb = extra(outs ? outs->o_mb : nullptr, (ms ? wave.bands : 1) * M4);
+      ia.spec = extra(outs ? outs->spec : nullptr, wave.bands * bins * Fr);
+      ia.phase = extra(outs ? outs->phase : nullptr, wave.bands * bins * Fr);
       ia.B = nb; ia.Tp = Td; ia.multistream = ms;
       ia.fixed_bank = !ia.multistream; ia.exact_math = m->exact_math; ia.prescaled = 1;
-      if (trim && nb == B && !ia.o_mb && !ia.spec && !ia.phase) ia.trim_lens = zlens;
-      if (pooled) {
-        ia.o = nullptr; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
-        launch_istft_pqmf_pool(ia, rg->rows + b0, rg->max_keep, s);
-      } else if (rr) {
-        IstftRange kb = keep;
-        kb.row_lens += b0; kb.row_map += b0;
-        ia.o = o; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
-        launch_istft_pqmf_range(ia, kb, s);
-      } else if (rg) {
-        ia.o = o + (size_t)b0 * rg->o_row_stride; ia.o_mb = ia.spec = ia.phase = nullptr; ia.trim_lens = nullptr;
-        launch_istft_pqmf_range(ia, keep, s);
-      } else {
-        launch_istft_pqmf(ia, s);
-      }
+      if (plain && d.trim && nb == B && !ia.o_mb && !ia.spec && !ia.phase) ia.trim_lens = zlens;
+      if (pooled) launch_istft_pqmf_pool(ia, rg->rows + b0, rg->max_keep, s);
+      else if (!plain) launch_istft_pqmf_range(ia, kb, s);
+      else launch_istft_pqmf(ia, s);
     }
   }
   if (Bc == B) m->stages["x_post"] = {xpost, (int64_t)B * prow * Fr};     // (a split run keeps only its last chunk)
@@ -1479,56 +1556,12 @@ int run_decoder(mbv_model* m, const float* z, int zstride, const int* zlens, con
   HIPCHK(m, hipEventRecord(m->evk[2], s));
   m->evk_set = true;
   m->evk_split = Bc < B;
-  if (tail_drift) return m->fail("internal error: a tail map was planned for another tile width than its launch uses");
+  if (tail_drift) return m->fail("internal error: a tile map was planned for another tile width than its launch uses");
   if (route_drift) return m->fail("internal error: a %s run holds rows whose convs plan differently (ragged_classes out of step with run_decoder)", pooled ? "pooled" : "ragged");
   return 0;
 }
 
 // ------------------------------------------------------------------ row-exact ragged decode
-// Every conv of the decoder as the planner sees it when ONE utterance of `len` z-frames is decoded alone (the
-// shapes run_decoder builds; data pointers are only ever tested against null).
-void decoder_conv_args(const mbv_config& c, int len, int splitk, std::vector<ConvArgs>* out) {
-  static const float kSome = 0.f;                   // "a tensor is given"
-  const bool sb = c.decoder == MBV_DEC_SINGLEBAND;
-  const int us = sb ? 8 : 4, I = c.inter_channels, C0 = c.upsample_initial_channel;
-  auto conv = [&](int Cin, int M, int K, int dil, int T, int epi) {
-    ConvArgs a{};
-    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = K; a.dil = dil; a.pad_left = (K - 1) * dil / 2;
-    a.Tin = T; a.x_rstride = T; a.x_bstride = (int64_t)Cin * T;
-    a.T = T; a.y_bstride = (int64_t)M * T; a.epi = epi; a.in_slope = 1.f; a.out_scale = 1.f; a.B = 1;
-    a.splitk = splitk;
-    if (epi == EPI_RESID || epi == EPI_RESID_ACC) { a.res = &kSome; a.res_bstride = (int64_t)M * T; }
-    return a;
-  };
-  out->clear();
-  out->push_back(conv(I, C0, 7, 1, len, EPI_STORE));                          // conv_pre
-  int L = len;
-  for (int i = 0; i < 2; ++i) {
-    const int ch = C0 >> (i + 1), Lo = us * L;
-    ConvArgs u = conv(C0 >> i, us * ch, 16 / us + 1, 1, L, EPI_CONVT);          // ups[i] as a phase conv over input frames
-    u.pad_left = us == 4 ? 2 : 1; u.convt_u = us; u.y_bstride = (int64_t)ch * Lo;
-    out->push_back(u);
-    for (int j = 0; j < 3; ++j) {
-      const int k = c.resblock_kernel_sizes[j];
-      const int nq = c.resblock_type == 2 ? 2 : 3;
-      for (int q = 0; q < nq; ++q) {
-        const int d = c.resblock_dilations[j][q];
-        const int last = q == nq - 1 ? EPI_RESID_ACC : EPI_RESID;
-        if (c.resblock_type == 2) {
-          out->push_back(conv(ch, ch, k, d, Lo, last));
-        } else {
-          out->push_back(conv(ch, ch, k, d, Lo, EPI_STORE));
-          out->push_back(conv(ch, ch, k, 1, Lo, last));
-        }
-      }
-    }
-    L = Lo;
-  }
-  ConvArgs p = conv(C0 >> 2, sb ? 18 : 72, 7, 1, L + 1, EPI_STORE);             // conv_post behind ReflectionPad1d((1, 0))
-  p.Tin = L; p.x_rstride = L; p.x_bstride = (int64_t)(C0 >> 2) * L; p.reflect1 = 1;
-  out->push_back(p);
-}
-
 // Classes of z-lengths 1 .. t_max: two lengths share a class iff every conv of the decoder, planned for an
 // utterance of that length alone, lands on the same side of the one divide that changes a sample's chain of
 // operations — the narrow kernel (sums start from the bias) or a tiled kernel (bias added last; BIG / SMALL / M64 /
@@ -1537,13 +1570,13 @@ void decoder_conv_args(const mbv_config& c, int len, int splitk, std::vector<Con
 void ragged_classes(const mbv_config& c, int splitk, int t_max, std::vector<int>* first) {
   first->assign(1, 1);
   if (splitk) return;
-  std::vector<ConvArgs> convs;
+  const std::vector<DecLaunch> table = decoder_table(c);
   std::vector<char> prev, cur;
   for (int len = 1; len <= t_max; ++len) {
-    decoder_conv_args(c, len, 0, &convs);
     cur.clear();
-    for (const auto& a : convs) {
-      const int r = conv1d_plan(a, false).route;
+    for (const DecLaunch& e : table) {
+      if (e.kind == DL_TAIL) continue;
+      const int r = conv1d_plan(dec_planner_args(e, len, 1, 0), false).route;
       cur.push_back(r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH);
     }
     if (len > 1 && cur != prev) first->push_back(len);
@@ -1567,7 +1600,7 @@ struct RaggedRun { std::vector<int> rows, lens; int Tc; };
 // (conv1d_narrow_supported tests it, and the route of a conv must not depend on the batch).
 void ragged_plan(const mbv_config& c, const std::vector<int>& first, int B, int Td, const int64_t* lens,
                  std::vector<RaggedRun>* runs) {
-  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, C0 = c.upsample_initial_channel;
+  const int us = dec_us(c), I = c.inter_channels, C0 = c.upsample_initial_channel;
   std::vector<std::vector<int>> rows(first.size());
   auto len_of = [&](int b) { return (int)(lens[b] < Td ? lens[b] : Td); };
   for (int b = 0; b < B; ++b) {
@@ -1607,50 +1640,58 @@ void ragged_plan(mbv_model* m, int B, int Td, const int64_t* lens, std::vector<R
   ragged_plan(m->cfg, m->ragged_first, B, Td, lens, runs);
 }
 
-size_t ragged_scratch_bytes(const mbv_config& c, const std::vector<RaggedRun>& runs) {
-  size_t need = 0;
-  for (const auto& r : runs) {
-    const size_t n = r.rows.size();
-    const size_t v = (n * c.inter_channels * r.Tc + n * c.gin_channels) * sizeof(float) + 4 * n * sizeof(int) + 8 * 256 +
-                     decoder_scratch_bytes(c, (int)n, r.Tc);
-    if (v > need) need = v;
+// Scratch of one run of a ragged or pooled decode: the rows' tables (ragged: source row, then the length at the three
+// rates; pooled: a PoolRow each, then the three lengths), their z of `width` frames and g gathered, the decoder's.
+// The runs of a call are ordered on the stream and share the arena: each is carved from the same offset.
+struct RunBufs { PoolRow* rows; int* ints; float *zc, *gc; DecBufs dec; };
+void carve_runs(const mbv_model* m, const std::vector<RaggedRun>& runs, const std::vector<int>* widths, bool with_g,
+                Bump& sc, std::vector<RunBufs>* out) {
+  const int I = m->cfg.inter_channels, gin = m->cfg.gin_channels;
+  out->resize(runs.size());
+  const size_t base = sc.off;
+  size_t end = base;
+  for (size_t r = 0; r < runs.size(); ++r) {
+    const size_t n = runs[r].rows.size();
+    const int T = widths ? (*widths)[r] : runs[r].Tc;
+    RunBufs& b = (*out)[r];
+    sc.off = base;
+    b.rows = widths ? sc.take<PoolRow>(n) : nullptr;
+    b.ints = sc.take<int>((widths ? 3 : 4) * n);
+    b.zc = sc.take<float>(n * I * T);
+    b.gc = with_g ? sc.take<float>(n * gin) : nullptr;
+    carve_decoder(m, DecCall{(int)n, T, T, true, with_g, false, widths != nullptr, true}, sc, &b.dec);
+    if (sc.off > end) end = sc.off;
   }
-  return need;
+  sc.off = end;
 }
 
 // The ragged decode of z [B, I, zstride]: o row b = the stand-alone decode of z[b, :, :len_b] over [0, spf len_b),
-// zeros behind.  One decoder run per RaggedRun, on its rows gathered into scratch.  The runs are ordered on the
-// stream, so they share the arena.
+// zeros behind.  One decoder run per RaggedRun, on its rows gathered into scratch (carve_runs, without widths).
 int run_decoder_ragged(mbv_model* m, const float* z, int zstride, const float* gvec, int B, int Td,
-                       const std::vector<RaggedRun>& runs, float* o, int64_t o_row_stride, hipStream_t s, Bump& sc) {
+                       const std::vector<RaggedRun>& runs, float* o, int64_t o_row_stride, hipStream_t s,
+                       std::vector<RunBufs>& bufs) {
   const mbv_config& c = m->cfg;
-  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, gin = c.gin_channels;
-  const int64_t spf = 256;
+  const int us = dec_us(c), I = c.inter_channels, gin = c.gin_channels;
+  const int64_t spf = m->dec_table.back().rate;
   HIPCHK(m, hipMemset2DAsync(o, (size_t)o_row_stride * sizeof(float), 0, (size_t)(spf * Td) * sizeof(float), B, s));
-  const size_t base = sc.off;
-  for (const auto& run : runs) {
+  for (size_t k = 0; k < runs.size(); ++k) {
+    const RaggedRun& run = runs[k];
+    RunBufs& b = bufs[k];
     const size_t n = run.rows.size();
     const int Tc = run.Tc;
-    sc.off = base;
-    int* ints = sc.take<int>(4 * n);
+    int* const ints = b.ints;
     for (size_t f = 0; f < n; f += kRaggedChunk) {
       RaggedRowsArg r{};
       const int nn = (int)(n - f < (size_t)kRaggedChunk ? n - f : (size_t)kRaggedChunk);
       for (int i = 0; i < nn; ++i) { r.row[i] = run.rows[f + i]; r.len[i] = run.lens[f + i]; }
       launch_ragged_rows(r, nn, (int)f, us, ints, (int)n, s);
     }
-    float* zc = sc.take<float>(n * I * Tc);
-    launch_gather_frames(z, (int64_t)I * zstride, zstride, ints, ints + n, (int)n, I, Tc, zc, s);
-    float* gc = nullptr;
-    if (gvec && gin) {
-      gc = sc.take<float>(n * gin);
-      launch_gather_frames(gvec, gin, 1, ints, nullptr, (int)n, gin, 1, gc, s);
-    }
+    launch_gather_frames(z, (int64_t)I * zstride, zstride, ints, ints + n, (int)n, I, Tc, b.zc, s);
+    if (b.gc) launch_gather_frames(gvec, gin, 1, ints, nullptr, (int)n, gin, 1, b.gc, s);
     const RaggedRows rr{ints + n, ints + 2 * n, ints + 3 * n, ints, o, o_row_stride,
                         *std::min_element(run.lens.begin(), run.lens.end())};
-    if (run_decoder(m, zc, Tc, nullptr, gc, (int)n, Tc, nullptr, s, sc, nullptr, &rr)) return 1;
+    if (run_decoder(m, b.zc, nullptr, b.gc, nullptr, s, b.dec, nullptr, &rr)) return 1;
   }
-  sc.off = base;
   return 0;
 }
 
@@ -1674,50 +1715,35 @@ void pooled_run_extent(const mbv_chunk* chunks, const RaggedRun& run, int Lc, in
   }
 }
 
-size_t pooled_scratch_bytes(const mbv_config& c, const mbv_chunk* chunks, const std::vector<RaggedRun>& runs, int Lc, int Rc) {
-  size_t need = 0;
-  for (const auto& r : runs) {
-    int Tw, mc;
-    pooled_run_extent(chunks, r, Lc, Rc, &Tw, &mc);
-    const size_t n = r.rows.size();
-    const size_t v = n * sizeof(PoolRow) + 3 * n * sizeof(int) + (n * c.inter_channels * Tw + n * c.gin_channels) * sizeof(float) +
-                     8 * 256 + decoder_scratch_bytes(c, (int)n, Tw);
-    if (v > need) need = v;
-  }
-  return need;
-}
-
 // The chunks of one call, one decoder run per RaggedRun of their utterances' lengths (the classes of the ragged
-// decode): the run's rows are the chunks' windows gathered into scratch, decoded as ragged rows of their window
-// lengths, planned as their utterances plan.  The tables travel as kernel arguments (upload_rows).
+// decode): the run's rows are the chunks' windows gathered into scratch (carve_runs, as wide as the run's widest
+// window), decoded as ragged rows of their window lengths, planned as their utterances plan.  The tables travel as
+// kernel arguments (upload_rows).
 int run_decoder_pooled(mbv_model* m, const mbv_chunk* chunks, bool with_g, const std::vector<RaggedRun>& runs, int Lc, int Rc,
-                       hipStream_t s, Bump& sc) {
+                       hipStream_t s, std::vector<RunBufs>& bufs) {
   const mbv_config& c = m->cfg;
-  const int us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4, I = c.inter_channels, gin = with_g ? c.gin_channels : 0;
-  const size_t base = sc.off;
-  for (const auto& run : runs) {
+  const int us = dec_us(c), I = c.inter_channels, gin = with_g ? c.gin_channels : 0;
+  const int spf = m->dec_table.back().rate, upf = spf / 4;      // samples, and units of a kept range, per z-frame
+  for (size_t r = 0; r < runs.size(); ++r) {
+    const RaggedRun& run = runs[r];
+    RunBufs& b = bufs[r];
     const size_t n = run.rows.size();
     int Tw, max_count;
     pooled_run_extent(chunks, run, Lc, Rc, &Tw, &max_count);
-    sc.off = base;
-    PoolRow* rows = sc.take<PoolRow>(n);
-    int* lens = sc.take<int>(3 * n);
-    upload_rows<kPoolChunk>(n, rows, s, [&](size_t i) {
+    int* const lens = b.ints;
+    upload_rows<kPoolChunk>(n, b.rows, s, [&](size_t i) {
       const mbv_chunk& k = chunks[run.rows[i]];
       const ChunkWindow w = chunk_window(k, Lc, Rc);
-      return PoolRow{k.z, k.z_stride, gin ? k.g : nullptr, k.o + (int64_t)256 * k.first, w.wa, w.len,
-                     64 * w.keep_first, 64 * (w.keep_first + k.count)};
+      return PoolRow{k.z, k.z_stride, gin ? k.g : nullptr, k.o + (int64_t)spf * k.first, w.wa, w.len,
+                     upf * w.keep_first, upf * (w.keep_first + k.count)};
     }, PoolRowLens{lens, (int)n, us});
-    float* zc = sc.take<float>(n * I * Tw);
-    float* gc = gin ? sc.take<float>(n * gin) : nullptr;
-    launch_gather_windows(rows, (int)n, I, Tw, zc, gin, gc, s);
+    launch_gather_windows(b.rows, (int)n, I, Tw, b.zc, gin, b.gc, s);
     const RaggedRows rr{lens, lens + n, lens + 2 * n, nullptr, nullptr, 0,
                         *std::min_element(run.lens.begin(), run.lens.end())};
     DecodeRange rg{run.Tc, 0, max_count, nullptr, 0};
-    rg.rows = rows; rg.max_keep = 64 * max_count;
-    if (run_decoder(m, zc, Tw, nullptr, gc, (int)n, Tw, nullptr, s, sc, &rg, &rr)) return 1;
+    rg.rows = b.rows; rg.max_keep = upf * max_count;
+    if (run_decoder(m, b.zc, nullptr, b.gc, nullptr, s, b.dec, &rg, &rr)) return 1;
   }
-  sc.off = base;
   return 0;
 }
 
@@ -1859,31 +1885,6 @@ bool wn_takes_fused(const mbv_model* m, const PConv* in_l, const PConv* in16_l, 
   return 0;
 }
 
-size_t decoder_scratch_bytes(const mbv_config& c, int B, int Td, int tail) {
-  const size_t C0 = c.upsample_initial_channel;
-  const size_t us = c.decoder == MBV_DEC_SINGLEBAND ? 8 : 4;
-  size_t n = (size_t)B * C0 * Td;                              // conv_pre
-  // per stage: u, t1, r, xs — and t1, r twice more when the ResBlocks may run on three streams (small
-  // launches, sized for it whenever the tile test can pass, whatever "dec_streams" says; and the stages that
-  // "tail_once" runs concurrently at any size — `tail` = tail_mode of the handle, 0 for the runs the option
-  // never touches.  Headline batch, B = 64, T' = 566: 4 x (148 + 297) MB = 1.78 GB on top of 2.2 GB)
-  for (int i = 0; i < 2; ++i) {
-    const size_t ch = C0 >> (i + 1), Lo = (i == 0 ? us : us * us) * (size_t)Td;
-    const long conv_tiles = (long)B * (long)((Lo + 383) / 384) * (long)((ch + 127) / 128);
-    n += (conv_tiles <= 192 || tail_stage(tail, B, conv_tiles) ? 8 : 4) * (size_t)B * ch * Lo;
-  }
-  {   // x_post: run_decoder takes at most the sub-batch that stays below 2 GiB (its Bc; the option can only lower it)
-    const size_t utt = 72 * (us * us * Td + 1);
-    size_t bc = utt ? ((size_t)(1ULL << 31) - 1) / (utt * sizeof(float)) : (size_t)B;
-    if (bc < 1) bc = 1;
-    n += (bc < (size_t)B ? bc : (size_t)B) * utt + (size_t)B * 256 * Td;
-  }
-  n += 6 * (size_t)B * C0;                                     // cond vectors
-  n += 12 * ((size_t)B + 2 + (size_t)B * ((us * us * Td + 1 + 127) / 128 + 1));   // trimmed decode: column-tile maps (ints)
-  n += 2 * kTailMapJobs * ((size_t)B + 3 + (size_t)B * ((us * us * Td + 127) / 128 + 1));   // "tail_once": a map per ResBlock launch (ints)
-  return n * sizeof(float) + 64 * 256 + 32 * 256 + 2 * kTailMapJobs * 256;   // + the 256-byte alignment of every take
-}
-
 }  // namespace
 
 // ======================================================================== C ABI
@@ -1932,6 +1933,7 @@ int mbv_create(const mbv_config* cfg, mbv_model** out) {
   mbv_model* m = new (std::nothrow) mbv_model();
   if (!m) return bad("out of host memory");
   m->cfg = *cfg;
+  m->dec_table = decoder_table(m->cfg);
   { const char* e = getenv("MBV_ISTFT_EXACT"); m->exact_math = (e && e[0] == '1') ? 1 : 0; }
   { const char* e = getenv("MBV_CONV_SPLITK"); m->splitk = (e && atoi(e) != 0) ? 1 : 0; }
   { const char* e = getenv("MBV_WN_FUSED"); m->wn_fused = e ? (atoi(e) != 0) : 1; }
@@ -2403,11 +2405,15 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   if (y_lens_host && run_dec) ragged_plan(m, B, Td, y_lens_host, &runs);
   float* z;
   FlowBufs fb{};
-  Bump sc{};
+  const bool with_g = m->has_g && c.gin_channels;
+  DecBufs dec;
+  std::vector<RunBufs> run_bufs;
   if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
         z = outs && outs->z ? outs->z : b.take<float>(BTp * I);
         fb = carve_flow(b, c, B, Tp, kFlowLayers);
-      }, y_lens_host ? ragged_scratch_bytes(c, runs) : decoder_scratch_bytes(c, B, Td, tail_mode(m)), &sc)) return 1;
+        if (run_dec && y_lens_host) carve_runs(m, runs, nullptr, with_g, b, &run_bufs);
+        else if (run_dec) carve_decoder(m, DecCall{B, Td, Tp, true, with_g, !outs->o, false, false}, b, &dec);
+      })) return 1;
   for (const char* k : {"dec_conv_pre", "dec_up_0", "dec_up_1", "dec_res_0", "dec_res_1", "x_post"})
     m->stages.erase(k);
 
@@ -2423,9 +2429,9 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
   if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
   HIPCHK(m, hipEventRecord(m->ev[5], s));
   if (run_dec && y_lens_host) {
-    if (run_decoder_ragged(m, z, Tp, m->has_g ? m->gvec : nullptr, B, Td, runs, outs->o, (int64_t)256 * Td, s, sc)) return 1;
+    if (run_decoder_ragged(m, z, Tp, m->has_g ? m->gvec : nullptr, B, Td, runs, outs->o, (int64_t)m->dec_table.back().rate * Td, s, run_bufs)) return 1;
   } else if (run_dec) {
-    if (run_decoder(m, z, Tp, m->ylen32, m->has_g ? m->gvec : nullptr, B, Td, outs, s, sc)) return 1;
+    if (run_decoder(m, z, m->ylen32, m->has_g ? m->gvec : nullptr, outs, s, dec)) return 1;
   }
   HIPCHK(m, hipEventRecord(m->ev[6], s));
   HIPCHK(m, hipGetLastError());
@@ -2441,14 +2447,7 @@ int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale
 void front_signature(const mbv_config& c, int splitk, int B, int T, std::vector<char>* sig) {
   static const float kSome = 0.f;                   // "a tensor is given"
   const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels;
-  auto conv = [&](int Cin, int M, int K) {
-    ConvArgs a{};
-    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = K; a.dil = 1; a.pad_left = (K - 1) / 2;
-    a.Tin = T; a.x_rstride = T; a.x_bstride = (int64_t)Cin * T;
-    a.T = T; a.y_bstride = (int64_t)M * T; a.epi = EPI_STORE; a.in_slope = 1.f; a.out_scale = 1.f; a.B = B;
-    a.splitk = splitk;
-    return a;
-  };
+  auto conv = [&](int Cin, int M, int K) { return conv_shape(Cin, M, K, 1, T, T, B, splitk); };
   sig->clear();
   const bool fuse = text_fuse_ln_at(splitk, B, T);
   auto plain = [&](const ConvArgs& a) {
@@ -2644,19 +2643,24 @@ int mbv_ragged_classes(const mbv_config* cfg, int splitk, int t_max, int32_t* fi
   return (int)f.size();
 }
 
-int mbv_ragged_plan(const mbv_config* cfg, int splitk, int B, int t_frames, const int64_t* lengths, int32_t* run_of_row) {
-  if (!cfg || B <= 0 || t_frames < 1 || ragged_lens_error(lengths, B, t_frames)) return -1;
-  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+// the runs of B rows of these lengths (classes scanned up to t_max); run_of_row[b] = -1 for an empty row
+static int plan_rows(const mbv_config& cfg, int splitk, int B, int t_max, const int64_t* lengths, int32_t* run_of_row) {
   std::vector<int> first;
-  ragged_classes(*cfg, splitk != 0, t_frames, &first);
+  ragged_classes(cfg, splitk != 0, t_max, &first);
   std::vector<RaggedRun> runs;
-  ragged_plan(*cfg, first, B, t_frames, lengths, &runs);
+  ragged_plan(cfg, first, B, t_max, lengths, &runs);
   if (run_of_row) {
     for (int b = 0; b < B; ++b) run_of_row[b] = -1;
     for (size_t r = 0; r < runs.size(); ++r)
       for (int b : runs[r].rows) run_of_row[b] = (int32_t)r;
   }
   return (int)runs.size();
+}
+
+int mbv_ragged_plan(const mbv_config* cfg, int splitk, int B, int t_frames, const int64_t* lengths, int32_t* run_of_row) {
+  if (!cfg || B <= 0 || t_frames < 1 || ragged_lens_error(lengths, B, t_frames)) return -1;
+  if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
+  return plan_rows(*cfg, splitk, B, t_frames, lengths, run_of_row);
 }
 
 int mbv_decode_ragged(mbv_model* m, const float* z, const float* g, int B, int t_frames, const int64_t* lengths_host,
@@ -2671,11 +2675,12 @@ int mbv_decode_ragged(mbv_model* m, const float* z, const float* g, int B, int t
   DEVICE_GUARD(m);
   std::vector<RaggedRun> runs;
   ragged_plan(m, B, t_frames, lengths_host, &runs);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, ragged_scratch_bytes(c, runs))) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  if (!c.gin_channels) g = nullptr;
+  std::vector<RunBufs> bufs;
+  if (lay_out(m, "mbv_decode_ragged", &m->scrB, &m->scrB_bytes, [&](Bump& b) { carve_runs(m, runs, nullptr, g != nullptr, b, &bufs); }))
+    return 1;
   m->stages.clear();
-  if (run_decoder_ragged(m, z, t_frames, (g && c.gin_channels) ? g : nullptr, B, t_frames, runs, o,
-                         (int64_t)256 * t_frames, (hipStream_t)stream, sc))
+  if (run_decoder_ragged(m, z, t_frames, g, B, t_frames, runs, o, (int64_t)m->dec_table.back().rate * t_frames, (hipStream_t)stream, bufs))
     return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
@@ -2689,12 +2694,13 @@ static int decode_entry(mbv_model* m, const char* who, const float* z, const flo
   if (!z || B <= 0 || t_frames <= 0 || !outs) return m->fail("%s: bad arguments", who);
   const mbv_config& c = m->cfg;
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, decoder_scratch_bytes(c, B, t_frames, tail_mode(m)))) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  if (!c.gin_channels) g = nullptr;
+  DecBufs dec;
+  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        carve_decoder(m, DecCall{B, t_frames, t_frames, lengths != nullptr, g != nullptr, !outs->o, false, false}, b, &dec);
+      })) return 1;
   m->stages.clear();
-  if (run_decoder(m, z, t_frames, lengths, (g && c.gin_channels) ? g : nullptr, B, t_frames, outs,
-                  (hipStream_t)stream, sc))
-    return 1;
+  if (run_decoder(m, z, lengths, g, outs, (hipStream_t)stream, dec)) return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -2713,10 +2719,7 @@ int mbv_decode_masked(mbv_model* m, const float* z, const float* g, const int32_
 int mbv_decoder_context(const mbv_config* cfg, int32_t out[2]) {
   if (!cfg || !out) return 1;
   if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return 1;
-  int L = 0, R = 0;
-  if (decoder_context(*cfg, &L, &R)) return 1;
-  out[0] = L;
-  out[1] = R;
+  decoder_context(decoder_table(*cfg), &out[0], &out[1]);
   return 0;
 }
 
@@ -2728,28 +2731,29 @@ int mbv_decode_range(mbv_model* m, const float* z, const float* g, int B, int t_
   if (first < 0 || count <= 0 || first >= t_frames || count > t_frames - first)
     return m->fail("mbv_decode_range: frames [%d, %d + %d) outside [0, %d)", first, first, count, t_frames);
   const mbv_config& c = m->cfg;
-  const int64_t spf = 256;
+  const int64_t spf = m->dec_table.back().rate;
   if (o_row_stride < spf * t_frames)
     return m->fail("mbv_decode_range: o_row_stride %lld < %lld samples per row", (long long)o_row_stride,
                    (long long)(spf * t_frames));
   if ((o_row_stride & 3) || ((uintptr_t)o & 15))
     return m->fail("mbv_decode_range: o must be 16-byte aligned and o_row_stride a multiple of 4");
   int Lc = 0, Rc = 0;
-  decoder_context(c, &Lc, &Rc);
+  decoder_context(m->dec_table, &Lc, &Rc);
   const int wa = first - Lc > 0 ? first - Lc : 0;
   const int wb = (int64_t)first + count + Rc < t_frames ? first + count + Rc : t_frames;
   const int Tw = wb - wa;
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, decoder_scratch_bytes(c, B, Tw))) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  if (!c.gin_channels) g = nullptr;
+  DecBufs dec;
+  if (lay_out(m, "mbv_decode_range", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+        carve_decoder(m, DecCall{B, Tw, t_frames, false, g != nullptr, false, true, false}, b, &dec);
+      })) return 1;
   m->stages.clear();
   // the window [wa, wb) of the caller's z: conv_pre reads Tw frames at row stride t_frames, zeros beyond (a window
   // edge is padded exactly as a stand-alone decode pads its edges); the samples of frames within L / R of a window
   // edge that is not an utterance edge are not stored
   const DecodeRange rg{t_frames, first - wa, count, o + spf * first, o_row_stride};
-  if (run_decoder(m, z + wa, t_frames, nullptr, (g && c.gin_channels) ? g : nullptr, B, Tw, nullptr,
-                  (hipStream_t)stream, sc, &rg))
-    return 1;
+  if (run_decoder(m, z + wa, nullptr, g, nullptr, (hipStream_t)stream, dec, &rg)) return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -2764,14 +2768,7 @@ int mbv_chunks_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_f
     lens[i] = t_frames[i];
     if (t_frames[i] > t_max) t_max = t_frames[i];
   }
-  std::vector<int> first;
-  ragged_classes(*cfg, splitk != 0, t_max, &first);
-  std::vector<RaggedRun> runs;
-  ragged_plan(*cfg, first, n, t_max, lens.data(), &runs);
-  if (run_of_chunk)
-    for (size_t r = 0; r < runs.size(); ++r)
-      for (int i : runs[r].rows) run_of_chunk[i] = (int32_t)r;
-  return (int)runs.size();
+  return plan_rows(*cfg, splitk, n, t_max, lens.data(), run_of_chunk);       // (no length is 0: every chunk is in a run)
 }
 
 int mbv_decode_chunks(mbv_model* m, const mbv_chunk* chunks_host, int n, void* stream) {
@@ -2805,14 +2802,17 @@ int mbv_decode_chunks_routed(mbv_model* m, const mbv_chunk* chunks_host, const i
   }
   if (with_g && with_g != n) return m->fail("mbv_decode_chunks: g is given for %d of %d chunks (all or none)", with_g, n);
   int Lc = 0, Rc = 0;
-  decoder_context(c, &Lc, &Rc);
+  decoder_context(m->dec_table, &Lc, &Rc);
   DEVICE_GUARD(m);
   std::vector<RaggedRun> runs;
   ragged_plan(m, n, t_max, lens.data(), &runs);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, pooled_scratch_bytes(c, chunks_host, runs, Lc, Rc))) return 1;
-  Bump sc{m->scrB, m->scrB_bytes};
+  std::vector<int> widths(runs.size());
+  for (size_t r = 0; r < runs.size(); ++r) { int mc; pooled_run_extent(chunks_host, runs[r], Lc, Rc, &widths[r], &mc); }
+  std::vector<RunBufs> bufs;
+  if (lay_out(m, "mbv_decode_chunks", &m->scrB, &m->scrB_bytes, [&](Bump& b) { carve_runs(m, runs, &widths, with_g != 0, b, &bufs); }))
+    return 1;
   m->stages.clear();
-  if (run_decoder_pooled(m, chunks_host, with_g != 0, runs, Lc, Rc, (hipStream_t)stream, sc)) return 1;
+  if (run_decoder_pooled(m, chunks_host, with_g != 0, runs, Lc, Rc, (hipStream_t)stream, bufs)) return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -2824,7 +2824,7 @@ int mbv_tail_plan(const mbv_config* cfg, int32_t* out, int capacity) {
   if (cfg->decoder != MBV_DEC_MULTIBAND && cfg->decoder != MBV_DEC_MULTISTREAM && cfg->decoder != MBV_DEC_SINGLEBAND) return -1;
   if (cfg->resblock_type != 1 && cfg->resblock_type != 2) return -1;
   std::vector<TailLaunch> plan;
-  decoder_tail_plan(*cfg, &plan);
+  decoder_tail_plan(decoder_table(*cfg), &plan);
   for (size_t i = 0; i < plan.size() && (int)i < capacity; ++i) {
     const int32_t v[6] = {plan[i].kind, plan[i].stage, plan[i].j, plan[i].q, plan[i].rate, plan[i].reach};
     std::memcpy(out + 6 * i, v, sizeof v);
@@ -2987,7 +2987,7 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   PosteriorBufs pb{};
   float *zbuf, *zhat, *g_src, *g_tgt;
   int *lens, *bad;
-  Bump sc{};
+  DecBufs dec;
   if (lay_out(m, "mbv_voice_conversion", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
         pb = carve_posterior(b, m, B, T);
         zbuf = outs->z ? outs->z : b.take<float>(BT * I);
@@ -2996,7 +2996,8 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
         g_tgt = b.take<float>((size_t)B * gin);
         lens = b.take<int>(B);
         bad = b.take<int>(B);
-      }, decoder_scratch_bytes(c, B, T, tail_mode(m)), &sc)) return 1;
+        carve_decoder(m, DecCall{B, T, T, true, gin > 0, !outs->o, false, false}, b, &dec);
+      })) return 1;
   m->stages.clear();
 
   launch_lens_to_i32(y_lengths, lens, B, T, bad, s);
@@ -3010,7 +3011,7 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   if (outs->z_p) HIPCHK(m, hipMemcpyAsync(outs->z_p, zhat, BT * I * 4, hipMemcpyDeviceToDevice, s));
   if (int rc = run_flows(m, true, zhat, g_tgt, pb, lens, B, T, s)) return rc;
   if (outs->y_mask) launch_sequence_mask(lens, outs->y_mask, B, T, s);
-  if (run_decoder(m, zhat, T, lens, g_tgt, B, T, outs, s, sc)) return 1;
+  if (run_decoder(m, zhat, lens, g_tgt, outs, s, dec)) return 1;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3600,23 +3601,21 @@ namespace {
 void posterior_signature(const mbv_config& c, int splitk, int B, int T, std::vector<char>* sig) {
   static const int kSome = 0;                       // "a length table is given"
   const int H = c.hidden_channels, I = c.inter_channels, cpad = (int)align_up(c.spec_channels, 32);
-  auto conv = [&](int Cin, int64_t x_bstride, int M, int64_t y_bstride, bool in_lens, int epi) {
-    ConvArgs a{};
-    a.Cin = Cin; a.M = M; a.Mpad = (int)align_up(M, 128); a.K = 1; a.dil = 1; a.pad_left = 0;
-    a.Tin = T; a.x_rstride = T; a.x_bstride = x_bstride;
-    a.T = T; a.y_bstride = y_bstride; a.epi = epi; a.in_slope = 1.f; a.out_scale = 1.f; a.B = B;
+  auto side = [&](ConvArgs a, bool in_lens) {
     a.out_lens = &kSome;
     if (in_lens) a.in_lens = &kSome;
-    a.couple_sign = 1.f;
-    a.splitk = splitk;
     const int r = conv1d_plan(a, false).route;
     sig->push_back(r == CONV_NARROW_M || r == CONV_NARROW_LAUNCH);
   };
   sig->clear();
-  conv(cpad, (int64_t)cpad * T, H, (int64_t)H * T, false, EPI_STORE);            // enc_q.pre
-  conv(H, (int64_t)H * T, 2 * I, (int64_t)2 * I * T, true, EPI_STORE);           // enc_q.proj
-  conv(I / 2, (int64_t)I * T, H, (int64_t)H * T, false, EPI_STORE);              // flow.pre
-  conv(H, (int64_t)H * T, I / 2, (int64_t)I * T, true, EPI_COUPLE);              // flow.post
+  side(conv_shape(cpad, H, 1, 1, T, T, B, splitk), false);                       // enc_q.pre
+  side(conv_shape(H, 2 * I, 1, 1, T, T, B, splitk), true);                       // enc_q.proj
+  ConvArgs pre = conv_shape(I / 2, H, 1, 1, T, T, B, splitk);                    // flow.pre, on a half of z
+  pre.x_bstride = (int64_t)I * T;
+  side(pre, false);
+  ConvArgs post = conv_shape(H, I / 2, 1, 1, T, T, B, splitk);                   // flow.post, onto the other half
+  post.y_bstride = (int64_t)I * T; post.epi = EPI_COUPLE; post.couple_sign = 1.f;
+  side(post, true);
 }
 
 // a run of B rows padded to T frames stays inside the grid and inside what the fused WN layers take
@@ -4219,9 +4218,9 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   a.x_bstride = (int64_t)d.Cin * a.x_rstride;
   a.M = convt ? U * d.Cout : d.Cout;
   a.Mpad = (int)align_up(a.M, 128);
-  a.K = convt ? 16 / U + 1 : d.K;
+  a.K = convt ? convt_taps(U) : d.K;
   a.dil = convt ? 1 : d.dil;
-  a.pad_left = convt ? (U == 4 ? 2 : 1) : (a.K - 1) * a.dil / 2;        // (run_decoder)
+  a.pad_left = convt ? convt_pad_left(U) : (a.K - 1) * a.dil / 2;        // (decoder_table)
   a.in_slope = d.in_slope;
   a.in_lens = d.in_lens; a.chan_add = d.chan_add; a.reflect1 = d.reflect1;
   a.T = d.T;

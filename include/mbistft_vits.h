@@ -601,6 +601,51 @@ int mbv_resample_pcm16_chunks(mbv_model *m, const mbv_pcm_chunk *chunks_host, in
                               int filter, int16_t *packed, int64_t packed_capacity, void *stream);
 int64_t mbv_wire_runs(mbv_model *m);
 
+/* ---- look-ahead limiter on the wire step (no reference counterpart: the service normalises a finished utterance
+ * by its own peak, tts_vits.py:204-213, which a stream does not have) -------------------------------------------
+ * A causal level control with a bounded lag, fused into the ranged and the pooled wire step between the static
+ * peak gain and the clip.  With v[t] the fp32 sample those steps clip ((v / peak) * 0.9 included where peak is
+ * given; zero for t < 0 and at or past the row's computed outputs int(n * ratio)), all in fp32:
+ *   r[t] = |v[t]| > c ? c / |v[t]| : 1
+ *   m[j] = min r[k], k in [j - hold, j + lookahead]
+ *   g[t] = (m[t - lookahead] + ... + m[t]) / (float)(lookahead + 1), added in ascending order from m[t - lookahead]
+ *   y[t] = v[t] * g[t], then clip to [-1, 1], * 32767, truncate, as before
+ * so |y| <= c up to rounding, the gain ramps down over `lookahead` outputs before a peak, holds for `hold` after it
+ * and ramps back over `lookahead`; where nothing in reach exceeds c, g is exactly 1 and the int16 is bitwise the
+ * unlimited one.  The step is stateless (every workgroup recomputes the v its outputs read), so an int16 is a pure
+ * function of the finished waveform: it does not depend on how the stream was cut, pooled or pushed.
+ *   ceiling in (0, 1], lookahead in [0, 255], hold in [0, 1024] (output samples); anything else is refused.
+ *
+ * mbv_limiter_ready (host only: no handle, no GPU): how many outputs are final under a limiter with that lookahead.
+ * Output t reads v up to t + lookahead, so with R = mbv_resample_ready(.., in_avail, in_total) it is
+ *   in_avail >= in_total >= 0:  R (everything: the last step flushes the lag)
+ *   otherwise:                  max(0, R - lookahead); in_total < 0 is an OPEN recording, R = mbv_resample_ready_open
+ * -1 with a message (mbv_last_error(NULL)) for whatever those two refuse or a lookahead outside [0, 255].
+ *
+ * mbv_resample_pcm16_range_limited: mbv_resample_pcm16_range with one limiter for all rows; the range must end at
+ * or below min(mbv_limiter_ready(.., in_avail, in_stride, lookahead), pcm_stride).  running_peak keeps its meaning:
+ * the largest |resampled sample| (before any gain) of the outputs emitted.
+ *
+ * mbv_resample_pcm16_chunks_limited: mbv_resample_pcm16_chunks with limits HOST [n] (or NULL = no row limited),
+ * one per chunk; ceiling == 0 marks a chunk without a limiter, which is then exactly a chunk of
+ * mbv_resample_pcm16_chunks.  The limited chunks of a call share ONE launch, whatever their parameters, and the
+ * others share one: a mixed call costs two launches (mbv_wire_runs), a call of one kind one.  Each chunk is bitwise
+ * its own ranged call.  Both entries refuse what their unlimited forms refuse, bad limiter parameters ("chunk i: ..."
+ * in the pooled form), and a rate pair whose halo window does not fit the 64 KiB LDS stage, launching nothing. */
+typedef struct mbv_pcm_limit {
+  float ceiling;               /* c; 0 in a pooled call: this chunk has no limiter */
+  int32_t lookahead, hold;     /* output samples */
+} mbv_pcm_limit;
+int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total, int lookahead);
+int mbv_resample_pcm16_range_limited(mbv_model *m, const float *wave, const int64_t *valid_samples, int B,
+                                     int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                     int64_t out_first, int64_t out_count, const float *peak, int16_t *pcm,
+                                     int64_t pcm_stride, float *running_peak, int64_t *out_samples,
+                                     const mbv_pcm_limit *limit, void *stream);
+int mbv_resample_pcm16_chunks_limited(mbv_model *m, const mbv_pcm_chunk *chunks_host, const mbv_pcm_limit *limits_host,
+                                      int n, int orig_sr, int target_sr, int filter, int16_t *packed,
+                                      int64_t packed_capacity, void *stream);
+
 /* ---- live input: recordings that are still arriving, resampled to the model's rate range by range ----------
  * The polyphase resampler puts zeros outside [0, n).  An output whose taps all lie below the samples that have
  * arrived therefore has the value it will have in the finished row, whatever n turns out to be; the total matters

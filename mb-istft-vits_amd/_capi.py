@@ -36,6 +36,7 @@ SYMBOLS = [
     "mbv_convert_ranges_plan", "mbv_convert_ranges",
     "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
     "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
+    "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
 ]
 
 
@@ -72,6 +73,11 @@ class MbvPcmChunk(C.Structure):
                 ("in_avail", C.c_int64), ("out_first", C.c_int64), ("out_count", C.c_int64), ("peak", C.c_void_p),
                 ("pcm", C.c_void_p), ("pcm_capacity", C.c_int64), ("running_peak", C.c_void_p),
                 ("out_samples", C.c_void_p)]
+
+
+class MbvPcmLimit(C.Structure):
+    """mbv_pcm_limit of include/mbistft_vits.h (the limited wire entries); ceiling 0 = this chunk has no limiter."""
+    _fields_ = [("ceiling", C.c_float), ("lookahead", C.c_int32), ("hold", C.c_int32)]
 
 
 class MbvEncRow(C.Structure):
@@ -241,8 +247,8 @@ def lib():
     L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
-    # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three and
-    # the seeded noise's three may be absent there, and calling one then raises AttributeError.
+    # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
+    # seeded noise's three and the limiter's three may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -253,7 +259,9 @@ def lib():
                 "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
                 "mbv_convert_ranges_plan", "mbv_convert_ranges",
                 "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
-                "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
+                "mbv_limiter_ready", "mbv_resample_pcm16_range_limited",
+                "mbv_resample_pcm16_chunks_limited") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -306,6 +314,13 @@ def lib():
         L.mbv_randn_host.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, vp]
         L.mbv_noise_runs.argtypes = [vp]
         L.mbv_noise_runs.restype = C.c_int64
+    if hasattr(L, "mbv_limiter_ready") or not optional:
+        L.mbv_limiter_ready.argtypes = [i32, i32, i32, C.c_int64, C.c_int64, i32]
+        L.mbv_limiter_ready.restype = C.c_int64
+        L.mbv_resample_pcm16_range_limited.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
+                                                       C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), vp]
+        L.mbv_resample_pcm16_chunks_limited.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32,
+                                                        i32, i32, vp, C.c_int64, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -3276,12 +3276,30 @@ int64_t mbv_resample_ready(int orig_sr, int target_sr, int filter, int64_t in_av
   return resample_ready(rp.g, in_avail, in_total);
 }
 
-int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
-                             int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
-                             int64_t out_count, const float* peak, int16_t* pcm, int64_t pcm_stride,
-                             float* running_peak, int64_t* out_samples, void* stream) {
+}  // extern "C"
+
+namespace {
+// final outputs of a row with its first in_avail of in_total samples, under a limiter of that lookahead (0: none)
+int64_t wire_ready(const RatePair& rp, int64_t in_avail, int64_t in_total, int lookahead) {
+  const int64_t ready = rp.fir ? resample_ready(rp.g, in_avail, in_total) : (in_avail < in_total ? in_avail : in_total);
+  return limiter_ready(ready, ready, in_avail >= in_total, lookahead);
+}
+
+// the limiter of a wire entry: refused, or too large for the LDS stage with this rate pair
+const char* limit_refusal(const RatePair& rp, const mbv_pcm_limit& l) {
+  const LimiterParams p{l.ceiling, l.lookahead, l.hold};
+  if (const char* why = limiter_refusal(p)) return why;
+  if (limiter_lds_floats(rp.g, rp.fir, p) > kResampleMaxLdsFloats)
+    return "rate pair and limiter need a halo window larger than the LDS stage";
+  return nullptr;
+}
+
+// mbv_resample_pcm16_range and its limited form: one body, lim null = no limiter
+int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
+                int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first, int64_t out_count,
+                const float* peak, int16_t* pcm, int64_t pcm_stride, float* running_peak, int64_t* out_samples,
+                const mbv_pcm_limit* lim, void* stream) {
   if (!m) return 1;
-  const char* who = "mbv_resample_pcm16_range";
   if (!wave || !pcm || B <= 0 || in_stride <= 0 || pcm_stride <= 0) return m->fail("%s: bad arguments", who);
   if (B > 65535) return m->fail("%s: more than 65535 rows", who);
   if (in_avail < 0 || out_first < 0 || out_count < 0)
@@ -3293,17 +3311,60 @@ int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* val
     return m->fail("%s: outputs [%lld, %lld) lie outside the row of pcm_stride %lld", who, (long long)out_first,
                    (long long)(out_first + out_count), (long long)pcm_stride);
   if ((double)pcm_stride * rp.M >= 0x1p62) return m->fail("%s: pcm_stride * M overflows the 64-bit time index", who);
-  const int64_t ready = rp.fir ? resample_ready(rp.g, in_avail, in_stride) : (in_avail < in_stride ? in_avail : in_stride);
+  if (lim)
+    if (const char* why = limit_refusal(rp, *lim)) return m->fail("%s: %s", who, why);
+  const int64_t ready = wire_ready(rp, in_avail, in_stride, lim ? lim->lookahead : 0);
   if (out_first + out_count > ready)
     return m->fail("%s: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final", who,
                    (long long)(out_first + out_count), (long long)in_avail, (long long)in_stride, (long long)ready);
   if (out_count == 0 && !out_samples) return 0;           // nothing to write
   ++m->wire_runs;
-  launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
-                              reinterpret_cast<short*>(pcm), pcm_stride, reinterpret_cast<unsigned*>(running_peak),
-                              out_samples, (hipStream_t)stream);
+  if (lim)
+    launch_resample_pcm16_range_limited(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count,
+                                        peak, reinterpret_cast<short*>(pcm), pcm_stride,
+                                        reinterpret_cast<unsigned*>(running_peak), out_samples,
+                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, (hipStream_t)stream);
+  else
+    launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
+                                reinterpret_cast<short*>(pcm), pcm_stride, reinterpret_cast<unsigned*>(running_peak),
+                                out_samples, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
+                             int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
+                             int64_t out_count, const float* peak, int16_t* pcm, int64_t pcm_stride,
+                             float* running_peak, int64_t* out_samples, void* stream) {
+  return pcm16_range(m, "mbv_resample_pcm16_range", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
+                     in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, nullptr, stream);
+}
+
+int mbv_resample_pcm16_range_limited(mbv_model* m, const float* wave, const int64_t* valid_samples, int B,
+                                     int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                     int64_t out_first, int64_t out_count, const float* peak, int16_t* pcm,
+                                     int64_t pcm_stride, float* running_peak, int64_t* out_samples,
+                                     const mbv_pcm_limit* limit, void* stream) {
+  if (m && !limit) return m->fail("mbv_resample_pcm16_range_limited: limit missing");
+  return pcm16_range(m, "mbv_resample_pcm16_range_limited", wave, valid_samples, B, in_stride, orig_sr, target_sr,
+                     filter, in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, limit,
+                     stream);
+}
+
+int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total, int lookahead) {
+  const char* who = "mbv_limiter_ready";
+  if (lookahead < 0 || lookahead > kLimiterMaxLookahead) {
+    g_create_error = std::string(who) + ": limiter lookahead must be in [0, 255] output samples";
+    return -1;
+  }
+  RatePair rp;
+  if (rate_pair(nullptr, who, orig_sr, target_sr, filter, &rp)) return -1;
+  if (in_avail < 0) in_avail = 0;
+  if (in_total < 0) return limiter_ready(rp.fir ? resample_ready_open(rp.g, in_avail) : in_avail, 0, false, lookahead);
+  return wire_ready(rp, in_avail, in_total, lookahead);
 }
 
 namespace {
@@ -3311,7 +3372,7 @@ namespace {
 // Fills packed_first (may be null) with the running sum of the out_count and returns the packed total, or -1 with
 // *err naming the offending chunk.
 int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const RatePair& rp, int64_t* packed_first,
-                         std::string* err) {
+                         std::string* err, const mbv_pcm_limit* limits = nullptr) {
   char buf[512];
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
@@ -3331,7 +3392,14 @@ int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, co
       *err = buf;
       return -1;
     }
-    const int64_t ready = rp.fir ? resample_ready(rp.g, k.in_avail, k.in_total) : (k.in_avail < k.in_total ? k.in_avail : k.in_total);
+    const bool limited = limits && limits[i].ceiling != 0.f;
+    if (limited)
+      if (const char* bad = limit_refusal(rp, limits[i])) {
+        snprintf(buf, sizeof buf, "%s: chunk %d: %s", who, i, bad);
+        *err = buf;
+        return -1;
+      }
+    const int64_t ready = wire_ready(rp, k.in_avail, k.in_total, limited ? limits[i].lookahead : 0);
     if (k.out_first + k.out_count > ready) {
       snprintf(buf, sizeof buf, "%s: chunk %d: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final",
                who, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.in_total, (long long)ready);
@@ -3357,10 +3425,14 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
   return total;
 }
 
-int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, int n, int orig_sr, int target_sr,
-                              int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
+}  // extern "C"
+
+namespace {
+// mbv_resample_pcm16_chunks and its limited form: one body, limits null = no row limited.  The rows without a
+// limiter go through the unlimited kernel and the limited ones through theirs: one table and one launch per kind
+int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits, int n,
+                 int orig_sr, int target_sr, int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
   if (!m) return 1;
-  const char* who = "mbv_resample_pcm16_chunks";
   if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
   for (int i = 0; i < n; ++i)
     if (!chunks_host[i].wave || !chunks_host[i].pcm) return m->fail("%s: chunk %d: wave / pcm missing", who, i);
@@ -3369,7 +3441,7 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
   if (rate_pair(m, who, orig_sr, target_sr, filter, &rp)) return 1;
   std::string err;
   std::vector<int64_t> off(n > 0 ? n : 1);
-  const int64_t total = pcm_chunks_check(who, chunks_host, n, rp, off.data(), &err);
+  const int64_t total = pcm_chunks_check(who, chunks_host, n, rp, off.data(), &err, limits);
   if (total < 0) return m->fail("%s", err.c_str());
   if (packed && packed_capacity < total)
     return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
@@ -3377,27 +3449,69 @@ int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, in
                                     [&](int i) { return sizeof(int16_t) * (uintptr_t)chunks_host[i].out_count; });
   if (clash.first >= 0)
     return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, clash.first, clash.second);
-  // rows with something to write (an empty range still carries out_samples)
-  std::vector<int> live;
-  for (int i = 0; i < n; ++i)
-    if (chunks_host[i].out_count > 0 || chunks_host[i].out_samples) live.push_back(i);
-  if (live.empty()) return 0;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(PcmPoolRow))) return 1;
+  // rows with something to write (an empty range still carries out_samples), by kind
+  std::vector<int> live, live_lim;
+  int64_t lds_floats = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!(chunks_host[i].out_count > 0 || chunks_host[i].out_samples)) continue;
+    if (limits && limits[i].ceiling != 0.f) {
+      live_lim.push_back(i);
+      lds_floats = std::max(lds_floats, limiter_lds_floats(rp.g, rp.fir, LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold}));
+    } else {
+      live.push_back(i);
+    }
+  }
+  if (live.empty() && live_lim.empty()) return 0;
+  const size_t lim_at = align_up(live.size() * sizeof(PcmPoolRow), 256);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, lim_at + live_lim.size() * sizeof(PcmLimRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
-  upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
-    const mbv_pcm_chunk& k = chunks_host[live[i]];
+  auto row_of = [&](int i) {
+    const mbv_pcm_chunk& k = chunks_host[i];
     return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
                       reinterpret_cast<short*>(k.pcm), k.pcm_capacity, reinterpret_cast<unsigned*>(k.running_peak),
-                      k.out_samples, packed ? off[live[i]] : (int64_t)-1};
-  });
-  grid_y_slices(live, [&](int i) { return chunks_host[i].out_count; }, [&](size_t f, int nn, int64_t max_count) {
-    ++m->wire_runs;
-    launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, reinterpret_cast<short*>(packed), s);
-    return 0;
-  });
+                      k.out_samples, packed ? off[i] : (int64_t)-1};
+  };
+  auto count_of = [&](int i) { return chunks_host[i].out_count; };
+  if (!live.empty()) {
+    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
+    upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
+    grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
+      ++m->wire_runs;
+      launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, reinterpret_cast<short*>(packed), s);
+      return 0;
+    });
+  }
+  if (!live_lim.empty()) {
+    PcmLimRow* rows = reinterpret_cast<PcmLimRow*>(m->scrB + lim_at);
+    upload_rows<kPcmPoolChunk>(live_lim.size(), rows, s, [&](size_t i) {
+      const mbv_pcm_limit& l = limits[live_lim[i]];
+      return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
+    });
+    grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
+      ++m->wire_runs;
+      launch_resample_pcm16_pool_limited(rows + f, nn, max_count, rp.bank, rp.g, lds_floats,
+                                         reinterpret_cast<short*>(packed), s);
+      return 0;
+    });
+  }
   HIPCHK(m, hipGetLastError());
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, int n, int orig_sr, int target_sr,
+                              int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
+  return pcm16_chunks(m, "mbv_resample_pcm16_chunks", chunks_host, nullptr, n, orig_sr, target_sr, filter, packed,
+                      packed_capacity, stream);
+}
+
+int mbv_resample_pcm16_chunks_limited(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host,
+                                      int n, int orig_sr, int target_sr, int filter, int16_t* packed,
+                                      int64_t packed_capacity, void* stream) {
+  return pcm16_chunks(m, "mbv_resample_pcm16_chunks_limited", chunks_host, limits_host, n, orig_sr, target_sr, filter,
+                      packed, packed_capacity, stream);
 }
 
 int64_t mbv_wire_runs(mbv_model* m) { return m ? m->wire_runs : -1; }

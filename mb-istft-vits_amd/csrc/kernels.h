@@ -423,6 +423,50 @@ constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of ker
 // in_total), pcm_cap) of every row.
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
                                 const ResampleGeom& g, short* packed, hipStream_t s);
+// Look-ahead limiter of the wire step (mbv_resample_pcm16_range_limited / mbv_resample_pcm16_chunks_limited, DESIGN
+// §7.14).  With v the sample the unlimited kernels clip (static peak gain included; zero outside the row's computed
+// outputs), all in fp32:
+//   r[t] = |v[t]| > c ? c / |v[t]| : 1       m[j] = min r[j - H .. j + L]
+//   g[t] = (m[t-L] + ... + m[t]) / (float)(L + 1), added in ascending order from m[t-L]       y[t] = v[t] g[t]
+// Stateless: a workgroup recomputes v on [t0 - L - H, t_last + L] (every r that the g of its outputs reads), so an
+// int16 does not depend on where a range or a tile begins.
+constexpr int kLimiterMaxLookahead = 255;
+constexpr int kLimiterMaxHold = 1024;
+struct LimiterParams {
+  float ceiling;               // c, 0 < c <= 1
+  int32_t lookahead, hold;     // L, H in output samples
+};
+// null, or why the parameters are refused
+const char* limiter_refusal(const LimiterParams& p);
+// v values a workgroup holds: its tile and the halo
+inline int64_t limiter_span(const LimiterParams& p) { return kResampleTile + 2 * (int64_t)p.lookahead + p.hold; }
+// LDS floats of the limited tile: the staged input window of the span (none with equal rates), v, and two buffers
+// of the log-step minimum
+inline int64_t limiter_lds_floats(const ResampleGeom& g, bool fir, const LimiterParams& p) {
+  const int64_t S = limiter_span(p);
+  return (fir ? (S - 1) * g.M / g.L + 2 + g.K : 0) + 3 * S;
+}
+// outputs that are final under the limiter: t + L below what the resampler has made final, everything once the row
+// is complete.  ready / all: resample_ready of the frontier / of the whole row (in_avail for an open row, no `all`)
+inline int64_t limiter_ready(int64_t ready, int64_t all, bool complete, int lookahead) {
+  if (complete) return all;
+  return ready > lookahead ? ready - lookahead : 0;
+}
+struct PcmLimRow {
+  PcmPoolRow row;
+  LimiterParams lim;
+  int32_t pad_;
+};
+// launch_resample_pcm16_range / launch_resample_pcm16_pool through the limited tile; lds_floats >=
+// limiter_lds_floats of every row, at most kResampleMaxLdsFloats (checked by the caller).  The caller guarantees
+// out_end <= min(limiter_ready(..), pcm_cap) of every row.
+void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
+                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
+                                         int64_t out_count, const float* peak, short* pcm, int64_t pcm_stride,
+                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim,
+                                         hipStream_t s);
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
+                                        const ResampleGeom& g, int64_t lds_floats, short* packed, hipStream_t s);
 // Live input (mbv_resample_ranges): fp32 outputs [out_first, out_end) of MANY recordings that are still arriving,
 // each from its own raw row (fp32, or int16 scaled by 1 / 32768) into its own model-rate row, in one launch.  A
 // table row is one recording; the table lives in the arena (upload_rows, kPcmPoolChunk per launch).

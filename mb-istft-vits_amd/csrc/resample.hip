@@ -152,6 +152,13 @@ int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total
   return r < all ? r : all;
 }
 
+const char* limiter_refusal(const LimiterParams& p) {
+  if (!(p.ceiling > 0.f && p.ceiling <= 1.f)) return "limiter ceiling must be in (0, 1]";
+  if (p.lookahead < 0 || p.lookahead > kLimiterMaxLookahead) return "limiter lookahead must be in [0, 255] output samples";
+  if (p.hold < 0 || p.hold > kLimiterMaxHold) return "limiter hold must be in [0, 1024] output samples";
+  return nullptr;
+}
+
 int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail) {
   // the open branch of resample_ready: floor(t M / L) - left + K - 1 < in_avail.  No total enters it.
   const int64_t a = in_avail - g.K + g.left + 1;
@@ -312,11 +319,20 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - running = max(running, |v|) over the row's computed outputs (t < int(n ratio); the samples between that and
 //     ceil(n ratio) are zeros), by atomicMax on the bits as absmax_kernel does: one per wave
 //   - each int16 goes to the row's own pcm[t] and, with a packed buffer, to packed[packed_off + t - out_first]
+//   - LIM = true: the look-ahead limiter between the static gain and the clip (resample_pcm16_limited below); the
+//     caller has checked out_end + lookahead <= resample_ready(in_avail) unless the row is complete.  LIM = false
+//     never reads `lim`
 // ---------------------------------------------------------------------------------------------------
 template <bool FIR>
+__device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
+                                                       int64_t t0, int64_t n_out, int64_t limit, short* pk,
+                                                       const float* __restrict__ bank, int L, int M, int K, int left,
+                                                       double ratio);
+
+template <bool FIR, bool LIM>
 __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
                                                     int L, int M, int K, int left, double ratio,
-                                                    short* __restrict__ packed) {
+                                                    short* __restrict__ packed, const LimiterParams& lim) {
   const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
   if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
   const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
@@ -337,6 +353,10 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
     return;
   }
   const int64_t limit = n < r.in_avail ? n : r.in_avail;
+  if constexpr (LIM) {
+    resample_pcm16_limited<FIR>(xs, r, lim, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
+    return;
+  }
   const float* xb = r.x;
   int64_t j0 = 0;
   if (FIR) {
@@ -373,6 +393,93 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   if (pk) pk[t] = q;
 }
 
+// The limited tile of outputs [t0, t_end), t_end = min(t0 + 256, out_end, n_out) > t0:
+//   1. v[k], static gain included, for k in [t0 - La - H, t_end - 1 + La] (zero outside [0, n_out)) from ONE staged
+//      window by the FIR of the unlimited tile (FIR = false: the sample itself), a few per thread; r[k] beside it.
+//      Every k is below out_end + La, which the caller has checked against the readiness of the row
+//   2. the sliding minimum over Wn = H + La + 1 values by doubling: a_s[i] = min r[i .. i + 2^s) in two LDS buffers
+//      that swap, then m[j] = min(a_p[j], a_p[j + Wn - 2^p]), 2^p <= Wn < 2^(p+1).  min is exact: the bits do not
+//      depend on the scheme
+//   3. g[t]: La + 1 fp32 adds in ascending order from m[t - La], one division; y = v g; the epilogue of the
+//      unlimited tile.  Where every m is 1.0f the sum and the quotient are exact, g = 1.0f and y is bitwise v
+// LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
+// over the workgroup; no thread leaves before the last barrier.
+template <bool FIR>
+__device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
+                                                       int64_t t0, int64_t n_out, int64_t limit, short* pk,
+                                                       const float* __restrict__ bank, int L, int M, int K, int left,
+                                                       double ratio) {
+  const int La = lim.lookahead, H = lim.hold;
+  const float c = lim.ceiling;
+  int64_t t_end = t0 + kResampleTile;
+  if (t_end > r.out_end) t_end = r.out_end;
+  if (t_end > n_out) t_end = n_out;
+  const int cnt = (int)(t_end - t0);
+  const int S = cnt + 2 * La + H;                        // v values held
+  const int64_t lo = t0 - La - H;                        // output index of vs[0]
+  const int span = kResampleTile + 2 * La + H;           // limiter_span: the layout does not depend on the tile
+  float* vs = lds + (FIR ? (int64_t)(span - 1) * M / L + 2 + K : 0);
+  float* a = vs + span;
+  float* b = a + span;
+  const float* xb = r.x;
+  int64_t j0 = 0;
+  if (FIR) {
+    const int64_t k_lo = lo > 0 ? lo : 0;
+    int64_t k_hi = lo + S - 1;
+    if (k_hi > n_out - 1) k_hi = n_out - 1;
+    j0 = resample_window_first(k_lo, L, M, left);
+    resample_stage(lds, xb, j0, k_hi, L, M, K, left, limit);
+    __syncthreads();
+  }
+  float p = 0.f;
+  if (r.peak) p = r.peak[0];
+  float top = 0.f;                                       // |v| before the gain, over this tile's own outputs
+  for (int i = threadIdx.x; i < S; i += kResampleTile) {
+    const int64_t k = lo + i;
+    float v = 0.f;
+    if (k >= 0 && k < n_out) {
+      v = FIR ? resample_output(lds, j0, k, bank, L, M, K, left, ratio) : (k < limit ? xb[k] : 0.f);
+      if (k >= t0 && k < t_end) top = fmaxf(top, fabsf(v));
+      if (p > 0.01f) v = (v / p) * 0.9f;
+    }
+    vs[i] = v;
+    const float m = fabsf(v);
+    a[i] = m > c ? c / m : 1.f;
+  }
+  __syncthreads();
+  if (r.running) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) top = fmaxf(top, __shfl_xor(top, off));
+    if ((threadIdx.x & 63) == 0 && __float_as_uint(top) > __atomic_load_n(r.running, __ATOMIC_RELAXED))
+      atomicMax(r.running, __float_as_uint(top));
+  }
+  const int Wn = H + La + 1;
+  int w = 1;
+  while (2 * w <= Wn) {
+    for (int i = threadIdx.x; i < S; i += kResampleTile) b[i] = i + w < S ? fminf(a[i], a[i + w]) : a[i];
+    __syncthreads();
+    float* sw = a; a = b; b = sw;
+    w *= 2;
+  }
+  const int Sm = cnt + La;                               // m[t0 - La .. t_end): b[jj] = m[t0 - La + jj]
+  for (int jj = threadIdx.x; jj < Sm; jj += kResampleTile) b[jj] = fminf(a[jj], a[jj + Wn - w]);
+  __syncthreads();
+  const int64_t t = t0 + threadIdx.x;
+  if (t >= r.out_end) return;
+  float y = 0.f;
+  if (t < t_end) {
+    float sum = b[threadIdx.x];
+    for (int i = 1; i <= La; ++i) sum += b[threadIdx.x + i];
+    const float g = sum / (float)(La + 1);
+    y = vs[threadIdx.x + La + H] * g;
+    y = fminf(fmaxf(y, -1.f), 1.f);
+    y = y * 32767.f;
+  }
+  const short q = (short)(int)y;
+  r.pcm[t] = q;
+  if (pk) pk[t] = q;
+}
+
 // Ranged kernel (mbv_resample_pcm16_range): row blockIdx.y of [B] tensors, one range for all rows
 template <bool FIR>
 __global__ void __launch_bounds__(kResampleTile)
@@ -386,7 +493,43 @@ resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restri
   const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
                      peak ? peak + b : nullptr, pcm + (int64_t)b * pcm_stride, pcm_stride,
                      running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
-  resample_pcm16_tile<FIR>(xs, r, bank, L, M, K, left, ratio, nullptr);
+  resample_pcm16_tile<FIR, false>(xs, r, bank, L, M, K, left, ratio, nullptr, LimiterParams{});
+}
+
+// the same rows through the limited tile
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_range_limited_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
+                                    int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
+                                    double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
+                                    short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
+                                    int64_t* __restrict__ out_samples, LimiterParams lim) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
+                     peak ? peak + b : nullptr, pcm + (int64_t)b * pcm_stride, pcm_stride,
+                     running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
+  resample_pcm16_tile<FIR, true>(xs, r, bank, L, M, K, left, ratio, nullptr, lim);
+}
+
+void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
+                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
+                                         int64_t out_count, const float* peak, short* pcm, int64_t pcm_stride,
+                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim,
+                                         hipStream_t s) {
+  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
+  const dim3 grid((unsigned)bx, B), block(kResampleTile);
+  const size_t lds = (size_t)limiter_lds_floats(g, bank != nullptr, lim) * sizeof(float);
+  if (bank) {
+    hipLaunchKernelGGL(resample_pcm16_range_limited_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail,
+                       bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
+                       running, out_samples, lim);
+  } else {
+    hipLaunchKernelGGL(resample_pcm16_range_limited_kernel<false>, grid, block, lds, s, x, valid, in_stride, in_avail,
+                       bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
+                       out_samples, lim);
+  }
 }
 
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
@@ -416,7 +559,32 @@ resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __r
                            int left, double ratio, short* __restrict__ packed) {
   extern __shared__ float xs[];
   const PcmPoolRow r = rows[blockIdx.y];
-  resample_pcm16_tile<FIR>(xs, r, bank, L, M, K, left, ratio, packed);
+  resample_pcm16_tile<FIR, false>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{});
+}
+
+// the same table through the limited tile, each row with its own limiter
+template <bool FIR>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const float* __restrict__ bank, int L, int M,
+                                   int K, int left, double ratio, short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmLimRow r = rows[blockIdx.y];
+  resample_pcm16_tile<FIR, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim);
+}
+
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
+                                        const ResampleGeom& g, int64_t lds_floats, short* packed, hipStream_t s) {
+  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
+  const dim3 grid((unsigned)bx, n), block(kResampleTile);
+  const size_t lds = (size_t)lds_floats * sizeof(float);
+  if (bank) {
+    hipLaunchKernelGGL(resample_pcm16_pool_limited_kernel<true>, grid, block, lds, s, rows, bank, g.L, g.M, g.K,
+                       g.left, g.ratio, packed);
+  } else {
+    hipLaunchKernelGGL(resample_pcm16_pool_limited_kernel<false>, grid, block, lds, s, rows, bank, 1, 1, 0, 0, 1.0,
+                       packed);
+  }
 }
 
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,

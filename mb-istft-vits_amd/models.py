@@ -1480,7 +1480,7 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def resample_pcm16_range(self, wave, orig_sr, target_sr, in_avail, out_first, out_count, pcm, valid_samples=None,
-                             peak=None, running_peak=None, out_samples=None, res_type="kaiser_best"):
+                             peak=None, running_peak=None, out_samples=None, res_type="kaiser_best", limiter=None):
         """One step of the streamed wire output (`mbv_resample_pcm16_range`; `wire.stream_pcm16` drives it for a
         decode stream): int16 samples [out_first, out_first + out_count) of every row of `pcm` [B, n'] from the
         first `in_avail` samples of `wave` (fp32 [B, 1, n] or [B, n], contiguous, on the device; nothing at or
@@ -1491,6 +1491,10 @@ class SynthesizerTrn(nn.Module):
           running_peak   fp32 [B] device, zeroed by the caller before the first step: raised to the peak of the
                          resampled samples of the range
           out_samples    int64 [B] device: receives the row lengths `resample` returns
+          limiter        None, or (ceiling, lookahead, hold) in output samples (`wire.Limiter.resolve`): the
+                         look-ahead limiter of DESIGN §7.14 between the gain and the clip
+                         (`mbv_resample_pcm16_range_limited`); the range must then end at or below
+                         `wire.limiter_ready(orig_sr, target_sr, in_avail, n, lookahead)`
         Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
         dev = self._device()
@@ -1512,17 +1516,23 @@ class SynthesizerTrn(nn.Module):
         if int(out_first) + int(out_count) > pcm.shape[1]:
             raise ValueError("resample_pcm16_range: outputs [%d, %d) lie outside pcm [B, %d]"
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
-        self._call("mbv_resample_pcm16_range", wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail),
-                   int(out_first), int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
+        args = (wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail), int(out_first),
+                int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
+        if limiter is None:
+            self._call("mbv_resample_pcm16_range", *args)
+        else:
+            self._call("mbv_resample_pcm16_range_limited", *args, C.byref(_capi.MbvPcmLimit(*limiter)))
 
     @torch.no_grad()
-    def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best"):
+    def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None):
         """The ranged wire step of many streams in ONE launch (`mbv_resample_pcm16_chunks`; `wire.pcm_pool` drives
         it): `chunks` is a ctypes array (or a list) of `_capi.MbvPcmChunk`, each the arguments of
         `resample_pcm16_range` for one row of its own stream, as device addresses.  Every stored value is bitwise
         what `resample_pcm16_range` stores for that row alone.  `packed` (int16, 1-D, device) also receives the
-        chunks' samples back to back, in chunk order.  No host synchronisation (beyond the first call for a rate
-        pair)."""
+        chunks' samples back to back, in chunk order.  `limits`: None, or one entry per chunk, each None or the
+        (ceiling, lookahead, hold) `resample_pcm16_range` takes as `limiter` (`mbv_resample_pcm16_chunks_limited`:
+        one launch for the limited chunks, one for the others).  No host synchronisation (beyond the first call for a
+        rate pair)."""
         filt = _filter_code(res_type)
         if not isinstance(chunks, C.Array):
             chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
@@ -1532,7 +1542,14 @@ class SynthesizerTrn(nn.Module):
             if packed.device != dev or packed.dtype != torch.int16 or packed.dim() != 1 or packed.stride(0) != 1:
                 raise ValueError("resample_pcm16_chunks: packed must be a 1-D int16 tensor on %s with unit stride" % dev)
             cap = packed.shape[0]
-        self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
+        if limits is None or all(l is None for l in limits):
+            self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
+            return
+        if len(limits) != len(chunks):
+            raise ValueError("resample_pcm16_chunks: one limit per chunk expected (%d), got %d" % (len(chunks), len(limits)))
+        lim = (_capi.MbvPcmLimit * len(chunks))(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+        self._call("mbv_resample_pcm16_chunks_limited", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt,
+                   packed, cap)
 
     @torch.no_grad()
     def resample_ranges(self, rows, orig_sr, target_sr, res_type="kaiser_best"):

@@ -27,6 +27,10 @@ hand the pieces over in one pinned host buffer filled by one copy
 they arrive, resamples what has become final into the model-rate buffer of the `stream.LiveStream` it owns
 (`mbv_resample_ranges`), and wires the decoded frontier to int16 at the service's rate; `PcmPool.add_live` serves many
 of them with one launch per stage and tick.
+
+`Limiter` is the level control of all of these (`limiter=`): a look-ahead peak limiter fused into the wire step, so
+that a streamed or live int16 output never reaches the hard clip, with a lag of `lookahead` output samples and the
+same bytes however the stream was chunked, pooled or pushed.
 """
 import base64
 import ctypes as C
@@ -62,7 +66,85 @@ def frame_pcm16(pcm, rate, frame_length=0.02, valid_samples=None):
     return [base64.b64encode(pcm[t:t + n].tobytes()).decode("utf-8") for t in range(0, len(pcm), n)]
 
 
-def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best"):
+class Limiter:
+    """The look-ahead peak limiter of the wire step (`mbv_resample_pcm16_range_limited`):
+      ceiling       c in (0, 1]: no output exceeds it (0.9 is the margin the service leaves, tts_vits.py:208)
+      lookahead_ms  the gain ramps down over this long before a sample above c, and the stream lags by it
+      hold_ms       the gain stays down this long after it, then ramps back over `lookahead_ms`
+    The defaults (0.9, 5 ms, 20 ms) are conventions, not measurements.  `resolve(rate)` gives (c, L, H) in output
+    samples at `rate`, L = round(lookahead_ms * rate / 1000) <= 255 and H = round(hold_ms * rate / 1000) <= 1024."""
+
+    MAX_LOOKAHEAD, MAX_HOLD = 255, 1024
+
+    def __init__(self, ceiling=0.9, lookahead_ms=5.0, hold_ms=20.0):
+        self.ceiling, self.lookahead_ms, self.hold_ms = float(ceiling), float(lookahead_ms), float(hold_ms)
+        if not 0.0 < self.ceiling <= 1.0:
+            raise ValueError("Limiter: ceiling %r must be in (0, 1]" % (ceiling,))
+        if not self.lookahead_ms >= 0.0 or not self.hold_ms >= 0.0:
+            raise ValueError("Limiter: lookahead_ms and hold_ms must be >= 0")
+
+    def __eq__(self, other):
+        return isinstance(other, Limiter) and (self.ceiling, self.lookahead_ms, self.hold_ms) == (
+            other.ceiling, other.lookahead_ms, other.hold_ms)
+
+    def __hash__(self):
+        return hash((self.ceiling, self.lookahead_ms, self.hold_ms))
+
+    def __repr__(self):
+        return "Limiter(ceiling=%r, lookahead_ms=%r, hold_ms=%r)" % (self.ceiling, self.lookahead_ms, self.hold_ms)
+
+    def resolve(self, rate):
+        """(ceiling, lookahead, hold) in output samples at `rate`; ValueError beyond the kernel's caps."""
+        rate = int(rate)
+        if rate <= 0:
+            raise ValueError("sample rates must be positive")
+        L, H = int(round(self.lookahead_ms * 1e-3 * rate)), int(round(self.hold_ms * 1e-3 * rate))
+        if L > self.MAX_LOOKAHEAD:
+            raise ValueError("Limiter: lookahead_ms %g is %d samples at %d Hz, more than the %d the kernel holds"
+                             % (self.lookahead_ms, L, rate, self.MAX_LOOKAHEAD))
+        if H > self.MAX_HOLD:
+            raise ValueError("Limiter: hold_ms %g is %d samples at %d Hz, more than the %d the kernel holds"
+                             % (self.hold_ms, H, rate, self.MAX_HOLD))
+        return self.ceiling, L, H
+
+
+def _limit_arg(limiter, rate):
+    """`limiter=` of a wire entry -> None or (ceiling, lookahead, hold) at `rate`."""
+    if limiter is None:
+        return None
+    if not isinstance(limiter, Limiter):
+        raise TypeError("limiter must be a wire.Limiter or None, got %s" % type(limiter).__name__)
+    return limiter.resolve(rate)
+
+
+def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak):
+    """`service_pcm16` through the ranged wire kernel over the whole row, which is where the limiter lives: one launch
+    with a given peak (or none), two with auto_normalize (the first measures the peak the second divides by)."""
+    lim = _limit_arg(limiter, rate)
+    dev = net._device()
+    if o.dim() != 3 or o.shape[1] != 1:
+        raise ValueError("wave must be [B, 1, samples]")
+    wave = o.to(device=dev, dtype=torch.float32).contiguous()[:, 0]
+    B, n = wave.shape
+    stride = resample_ready(model_sr, rate, n, n, res_type)
+    valid_in = None
+    if y_lengths is not None:
+        valid_in = (y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
+    with torch.cuda.device(dev):
+        pcm = torch.empty(B, stride, device=dev, dtype=torch.int16)
+        valid = torch.zeros(B, device=dev, dtype=torch.int64)
+        peak_in = _peak_arg(peak, B, dev)
+        if peak_in is None and auto_normalize:
+            peak_in = torch.zeros(B, device=dev, dtype=torch.float32)
+            net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in,
+                                     running_peak=peak_in, res_type=res_type)
+    net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in, peak=peak_in,
+                             out_samples=valid, res_type=res_type, limiter=lim)
+    return pcm, valid
+
+
+def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best", limiter=None,
+                  peak=None):
     """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
     `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
       o          fp32 [B, 1, n] waveforms of `net.infer` (device)
@@ -70,13 +152,22 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
                  or None = whole rows
     -> (pcm int16 [B, n'], valid_samples int64 [B]); row b of `pcm` holds the int16 stream of utterance b
     in its first valid_samples[b] samples, ready for `frame_pcm16(pcm[b], rate, valid_samples=...)`.
-    No host synchronisation (beyond the first call for a rate pair, see `SynthesizerTrn.resample`)."""
+    No host synchronisation (beyond the first call for a rate pair, see `SynthesizerTrn.resample`).
+      limiter  a `Limiter`: the look-ahead limiter of DESIGN §7.14 between the gain and the clip; the bytes are then
+               those `stream_pcm16(..., limiter=limiter)` emits for the same waveform and peak.  None: as before
+      peak     with `limiter` only: a float or fp32 [B] tensor to divide by instead of the utterance's own peak, as
+               `stream_pcm16` takes it (it overrides auto_normalize)"""
+    if limiter is not None:
+        return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak)
+    if peak is not None:
+        raise ValueError("service_pcm16: peak= is the static gain of the limited path; without limiter= the "
+                         "utterance's own peak is used (auto_normalize)")
     wave, valid = net.resample(o, model_sr, rate, y_lengths=y_lengths, res_type=res_type)
     return net.to_pcm16(wave, auto_normalize=auto_normalize, valid_samples=valid), valid
 
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
-                  auto_normalize=True, res_type="kaiser_best", seed=None):
+                  auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -84,11 +175,12 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
       3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
       4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)` (`seed` as `infer` takes it: None =
          torch's generator, as before);
-      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`.
+      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter` as it takes it.
     -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
     anything is launched when win_size > n_fft or the model has no speakers.  The one host synchronisation is
     the status check `voice_conversion` already has (besides the first-call table uploads of `resample` and
     `spectrogram`)."""
+    _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
     n_fft = 2 * (net.cfg.spec_channels - 1)
     if not net.n_speakers > 0:
         raise ValueError("convert_pcm16: voice conversion needs a multi-speaker model (n_speakers > 0)")
@@ -102,7 +194,8 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     wave, valid = net.resample(wave, in_sr, model_sr, valid_samples=valid_samples, res_type=res_type)
     spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
     o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)[0]
-    return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type)
+    return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type,
+                         limiter=limiter)
 
 
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
@@ -130,6 +223,21 @@ def resample_ready_open(orig_sr, target_sr, in_avail, res_type="kaiser_best"):
     return int(r)
 
 
+def limiter_ready(orig_sr, target_sr, in_avail, in_total, lookahead, res_type="kaiser_best"):
+    """How many int16 samples are final under a limiter of `lookahead` output samples (the rule of
+    `mbv_limiter_ready`, restated on `resample_ready` / `resample_ready_open`; host only): output t reads the
+    resampled samples up to t + lookahead, so it is final once t + lookahead is below what the resampler has made
+    final, and everything is once the row is complete.  `in_total` None or negative: an open recording."""
+    lookahead = int(lookahead)
+    if not 0 <= lookahead <= Limiter.MAX_LOOKAHEAD:
+        raise ValueError("limiter lookahead must be in [0, %d] output samples" % Limiter.MAX_LOOKAHEAD)
+    in_avail = max(int(in_avail), 0)
+    if in_total is None or int(in_total) < 0:
+        return max(resample_ready_open(orig_sr, target_sr, in_avail, res_type) - lookahead, 0)
+    ready = resample_ready(orig_sr, target_sr, in_avail, in_total, res_type)
+    return ready if in_avail >= int(in_total) else max(ready - lookahead, 0)
+
+
 def _refuse_live(st):
     from .stream import LiveStream
     if isinstance(st, LiveStream):
@@ -151,14 +259,15 @@ def _peak_arg(peak, B, dev, shape="B"):
     return peak
 
 
-# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in):
-# from the first `in_avail` samples of `wave` [B, n] to the int16 samples [out_first, out_first + out_count); `lengths`:
-# this step also writes `valid_samples`.  Alone it is one `mbv_resample_pcm16_range` launch, in a pool one row of the
-# `mbv_resample_pcm16_chunks` table.
+# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in
+# and _lim, the resolved limiter or None): from the first `in_avail` samples of `wave` [B, n] to the int16 samples
+# [out_first, out_first + out_count); `lengths`: this step also writes `valid_samples`.  Alone it is one
+# `mbv_resample_pcm16_range` launch (`..._range_limited` with a limiter), in a pool one row of the
+# `mbv_resample_pcm16_chunks` table (`PcmPool.step` passes the rows' `_lim` along).
 def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
     w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
                                 valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
-                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type)
+                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim)
 
 
 def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
@@ -177,7 +286,8 @@ class PcmStream:
     into int16, on the caller's current stream, and the view is ordered on that stream like every other output.
     The filter needs input on both sides of an output, so the wire lags the decoder by the filter's half-width
     (64 input samples for kaiser_best upsampling); the last chunk flushes it.  A chunk shorter than that lag
-    yields an empty view.  No host synchronisation per chunk.
+    yields an empty view.  With a `limiter` the lag grows by its lookahead, in output samples (`limiter_ready`).  No
+    host synchronisation per chunk.
 
       pcm            int16 [B, out_stride], out_stride = ceil(spf T' * rate / model_sr); after the last chunk
                      bitwise the `service_pcm16` of the finished `st.o` (auto_normalize = `peak is not None`
@@ -191,15 +301,17 @@ class PcmStream:
     A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
     such a piece out without launching anything, and launches alone otherwise — the same bytes either way."""
 
-    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best"):
+    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None):
         _refuse_live(st)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
+        self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
+        lag = self._lim[1] if self._lim else 0
         o = st.o
         B, n = o.shape[0], o.shape[-1]
         dev = o.device
         # final outputs after each decoded chunk (pure integers of the schedule: nothing to ask the device)
-        self._ready = [resample_ready(model_sr, rate, st.spf * (first + count), n, res_type)
+        self._ready = [limiter_ready(model_sr, rate, st.spf * (first + count), n, lag, res_type)
                        for first, count in st.schedule]
         self.out_stride = resample_ready(model_sr, rate, n, n, res_type)
         self.pcm = torch.empty(B, self.out_stride, device=dev, dtype=torch.int16)
@@ -258,17 +370,22 @@ class PcmStream:
         return self.pcm, self.valid_samples
 
 
-def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best"):
+def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None):
     """The streamed `service_pcm16`: wraps a `stream.DecodeStream` (`net.dec_stream` / `net.infer_stream`, not yet
     iterated) in a `PcmStream`.
       peak  None: no normalisation (auto_normalize=False, exact).  A float or an fp32 [B] tensor: every sample is
             divided by it and scaled by 0.9 where it exceeds 0.01, as tts_vits.py:205-208 does with the peak of
             the whole resampled utterance.  That peak does not exist before the last chunk, so it is an input
-            here (e.g. `PcmStream.peak` of the speaker's previous utterance); the clip that follows bounds
-            what a peak chosen too small can do."""
+            here (e.g. `PcmStream.peak` of the speaker's previous utterance), a static gain and no more: one
+            chosen too small hard-clips (audible distortion), one chosen too large leaves the utterance quiet.
+            Give a `limiter` to take the level off the guess.
+      limiter  None, or a `Limiter`: the look-ahead limiter of DESIGN §7.14 after the static gain, so that no sample
+            reaches the clip; `peak` and the limiter combine.  The stream then lags by the limiter's lookahead as
+            well, and the bytes are those of `service_pcm16(..., limiter=limiter, peak=peak)` on the finished
+            waveform.  Where nothing exceeds the ceiling they are the bytes without a limiter."""
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
-    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type)
+    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter)
 
 
 def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
@@ -306,10 +423,14 @@ class LiveWirePlan:
               `close` go straight to the `LivePlan`.
       output  after decoded chunk (first, count), int16 sample u is final iff no tap of it lies at or past
               spf * (first + count); after the LAST chunk all ceil(spf * T * rate / model_sr) are.  One piece per
-              decoded chunk, so the pieces do not depend on how the recording was cut into pushes."""
+              decoded chunk, so the pieces do not depend on how the recording was cut into pushes.  Under a limiter
+              u + `lookahead` must be final in that sense (`limiter_ready`)."""
 
-    def __init__(self, in_sr, model_sr, rate, plan, spf, max_raw, res_type="kaiser_best"):
+    def __init__(self, in_sr, model_sr, rate, plan, spf, max_raw, res_type="kaiser_best", lookahead=0):
         self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
+        self.lookahead = int(lookahead)           # of the limiter on the output side: the pieces lag by it (0: none)
+        if not 0 <= self.lookahead <= Limiter.MAX_LOOKAHEAD:
+            raise ValueError("limiter lookahead must be in [0, %d] output samples" % Limiter.MAX_LOOKAHEAD)
         if min(self.in_sr, self.model_sr, self.rate) <= 0:
             raise ValueError("sample rates must be positive")
         self.plan, self.spf, self.max_raw = plan, int(spf), int(max_raw)
@@ -410,7 +531,8 @@ class LiveWirePlan:
             if final and i == len(chunks) - 1:
                 b = resample_ready(self.model_sr, self.rate, in_total, in_total, self.res_type)
             else:
-                b = resample_ready(self.model_sr, self.rate, self.spf * (first + count), self.o_capacity, self.res_type)
+                b = limiter_ready(self.model_sr, self.rate, self.spf * (first + count), self.o_capacity, self.lookahead,
+                                  self.res_type)
             pieces.append((a, b))
             a = b
         return in_avail, in_total, self.out_done, a - self.out_done, final, pieces
@@ -433,17 +555,18 @@ class LiveWire:
 
       pcm            int16 [1, ceil(capacity of live.o * rate / model_sr)]
       valid_samples  int64 [1] device, written with the last piece
-      peak           fp32 [1] device, the running peak of the resampled output so far; the `peak=` given when the
-                     stream was opened is an input, as for `stream_pcm16`
+      peak           fp32 [1] device, the running peak of the resampled output so far; the `peak=` and the `limiter=`
+                     given when the stream was opened are inputs, as for `stream_pcm16`
     With `in_sr == model_sr` the samples go to `LiveStream.push` as they are (int16 stays int16) and no input kernel
     runs.  A `PcmPool` may feed, step and wire for many at once; pieces it wired are handed out by the next `poll()`
     without a launch, the same bytes either way."""
 
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                 chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None):
+                 chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None):
         from .stream import LiveStream
         _filter_code(res_type)
+        self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("convert_live_pcm16: dtype must be int16 or float32, got %s" % dtype)
         self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
@@ -464,7 +587,8 @@ class LiveWire:
                                convert_frames=convert_frames, seed=seed)
         live = self.live
         self._net = net
-        self._plan = LiveWirePlan(self.in_sr, self.model_sr, self.rate, live.plan, live.spf, self.max_samples, res_type)
+        self._plan = LiveWirePlan(self.in_sr, self.model_sr, self.rate, live.plan, live.spf, self.max_samples, res_type,
+                                  lookahead=self._lim[1] if self._lim else 0)
         assert self._plan.o_capacity == live.o.shape[-1] and self._plan.capacity == live.max_samples
         dev = live.z.device
         with torch.cuda.device(dev):
@@ -587,16 +711,17 @@ class LiveWire:
 
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                       chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None):
+                       chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32) while the recording arrives, int16
     out at `rate`; -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
-    `LiveStream` it opens, [1, inter, frames of ceil(max_samples * model_sr / in_sr)].  `peak` as `stream_pcm16` takes
-    it.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
+    `LiveStream` it opens, [1, inter, frames of ceil(max_samples * model_sr / in_sr)].  `peak` and `limiter` as
+    `stream_pcm16` takes them: the level of a live recording is whatever the microphone delivers, so there is no
+    earlier utterance to take a peak from, and the limiter is the level control.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
     `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
     (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead."""
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
-                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed)
+                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter)
 
 
 class PcmPool:
@@ -604,10 +729,11 @@ class PcmPool:
     `mbv_decode_chunks` call) and then turns what has become final on ALL pooled streams into int16 in ONE
     `mbv_resample_pcm16_chunks` launch, instead of one `mbv_resample_pcm16_range` launch per stream.
 
-    `add(st, peak=None)` returns the stream's `PcmStream` follower, which holds the state it holds alone (`pcm`,
+    `add(st, peak=None, limiter=None)` returns the stream's `PcmStream` follower, which holds the state it holds alone (`pcm`,
     `valid_samples`, `peak`); the pieces count as wired ahead on it, so `next(follower)` afterwards hands them out
     without a launch.  A stream may be driven through the pool, alone, or both in turn: the same bytes, those
-    `service_pcm16` gives for the finished waveform.  Finished streams drop out."""
+    `service_pcm16` gives for the finished waveform.  Finished streams drop out.  Members with a `Limiter` (each its
+    own) share one launch of the limited kernel and the others one of the unlimited: two launches in a mixed tick."""
 
     def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best"):
         _filter_code(res_type)
@@ -630,30 +756,39 @@ class PcmPool:
                 return f
         return None
 
-    def add(self, st, peak=None):
+    def add(self, st, peak=None, limiter=None):
         _refuse_live(st)
+        _limit_arg(limiter, self.rate)            # refuses bad parameters before the stream joins the pool
         self.pool.add(st)                         # (refuses B > 1, another model, another device)
         f = self.follower(st)
         if f is None:
-            f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type)
+            f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter)
             self.followers.append(f)
         return f
 
-    def admit(self, requests, peak=None):
+    def admit(self, requests, peak=None, limiter=None):
         """`StreamPool.admit(requests)` + a follower for each new stream (`peak`: None, one value for all, or one per
-        request, as `add` takes it); -> the followers, in order.  `requests` is all `models.Request` or all
+        request, as `add` takes it; `limiter` likewise); -> the followers, in order.  `requests` is all `models.Request` or all
         `models.ConvertRequest` (audio), as `StreamPool.admit` takes them.  All or nothing, like `StreamPool.admit`."""
         reqs = list(requests)
         peaks = list(peak) if isinstance(peak, (list, tuple)) else [peak] * len(reqs)
         if len(peaks) != len(reqs):
             raise ValueError("admit: one peak per request expected (%d), got %d" % (len(reqs), len(peaks)))
-        return [self.add(st, peak=p) for st, p in zip(self.pool.admit(reqs), peaks)]
+        limiters = list(limiter) if isinstance(limiter, (list, tuple)) else [limiter] * len(reqs)
+        if len(limiters) != len(reqs):
+            raise ValueError("admit: one limiter per request expected (%d), got %d" % (len(reqs), len(limiters)))
+        for lim in limiters:
+            _limit_arg(lim, self.rate)
+        return [self.add(st, peak=p, limiter=lim) for st, p, lim in zip(self.pool.admit(reqs), peaks, limiters)]
 
-    def add_live(self, lw):
+    def add_live(self, lw, limiter=None):
         """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
-        feeds, steps and wires it along with the others; -> `lw`."""
+        feeds, steps and wires it along with the others; -> `lw`.  The wire keeps the limiter it was opened with;
+        `limiter`, when given, must be that one (the lag is part of the pieces it has planned)."""
         if not isinstance(lw, LiveWire):
             raise TypeError("add_live takes a wire.LiveWire (wire.convert_live_pcm16)")
+        if limiter is not None and limiter != lw.limiter:
+            raise ValueError("add_live: the live wire was opened with %r, not %r" % (lw.limiter, limiter))
         if (lw.model_sr, lw.rate) != (self.model_sr, self.rate):
             raise ValueError("the live wire runs %d -> %d Hz, the pool %d -> %d Hz"
                              % (lw.model_sr, lw.rate, self.model_sr, self.rate))
@@ -728,7 +863,8 @@ class PcmPool:
                     self._host_np = self._host.numpy()
                     self._event = torch.cuda.Event()
                 packed = self._packed
-            net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type)
+            net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
+                                      limits=[w._lim for _, w, _, _ in rows])
             for _, w, _, due in rows:
                 w._chunk_wired(*due)
             if host:
@@ -750,7 +886,7 @@ class PcmPool:
 
 def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best"):
     """The pooled `stream_pcm16`: a `PcmPool` over a `stream.StreamPool` (`net.stream_pool()`) of the same model.
-    `add(st, peak=None)` takes `peak` as `stream_pcm16` does."""
+    `add(st, peak=None, limiter=None)` takes `peak` and `limiter` as `stream_pcm16` does."""
     return PcmPool(net, pool, model_sr, rate, res_type=res_type)
 
 

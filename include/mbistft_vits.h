@@ -592,7 +592,7 @@ typedef struct mbv_pcm_chunk {
   const int64_t *valid_samples;             /* DEVICE, one int64, or NULL */
   int64_t in_avail, out_first, out_count;
   const float *peak;                        /* DEVICE, one float, or NULL (per chunk: mixed is allowed) */
-  int16_t *pcm; int64_t pcm_capacity;       /* the stream's own full-length row */
+  int16_t *pcm; int64_t pcm_capacity;       /* the stream's own full-length row (mbv_resample_g711_chunks: bytes) */
   float *running_peak; int64_t *out_samples;/* DEVICE, one value each, or NULL */
 } mbv_pcm_chunk;
 int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pcm_chunk *chunks, int n,
@@ -673,7 +673,7 @@ int mbv_resample_pcm16_chunks_limited(mbv_model *m, const mbv_pcm_chunk *chunks_
  * mbv_input_runs: launches of the live-input resampler on this handle since mbv_create (table writers are not
  * counted), the counterpart of mbv_wire_runs for the input side. */
 typedef struct mbv_resample_range {
-  const void *wave; int32_t wave_dtype;  /* DEVICE raw recording at orig_sr, MBV_WAVE_F32 / MBV_WAVE_PCM16, read in place */
+  const void *wave; int32_t wave_dtype;  /* DEVICE raw recording at orig_sr, MBV_WAVE_F32 / _PCM16 / _ULAW / _ALAW, read in place */
   int64_t in_avail;                      /* raw samples that exist */
   int64_t in_total;                      /* -1: open; >= 0: closed at that many samples (then in_avail == in_total) */
   int64_t out_first, out_count;          /* outputs [out_first, out_first + out_count) */
@@ -683,6 +683,43 @@ int64_t mbv_resample_ready_open(int orig_sr, int target_sr, int filter, int64_t 
 int mbv_resample_ranges(mbv_model *m, const mbv_resample_range *rows_host, int n, int orig_sr, int target_sr,
                         int filter, void *stream);
 int64_t mbv_input_runs(mbv_model *m);
+
+/* ---- G.711 on the wire: mu-law / A-law bytes out of the wire step and into the live input (no reference
+ * counterpart: the reference service emits 16-bit linear PCM only) ------------------------------------------------
+ * The codec is BITWISE CPython 3.10's audioop.lin2ulaw / lin2alaw / ulaw2lin / alaw2lin at width 2 (the arithmetic
+ * of Sun's g711.c): mu-law works on s >> 2 clipped to 8159 with bias 33, A-law on s >> 3; encode(0) is 0xFF / 0xD5;
+ * encode(decode(b)) == b for every byte but mu-law 0x7F (negative zero), which re-encodes to 0xFF.
+ *
+ * mbv_g711_encode / mbv_g711_decode: n samples, DEVICE int16 <-> DEVICE bytes, one launch (n == 0: none).
+ *
+ * mbv_resample_g711_range: mbv_resample_pcm16_range (limit NULL) or mbv_resample_pcm16_range_limited (limit given)
+ * with the codec as the epilogue: out is uint8 [B, out_stride] and every byte written is encode(q) of the int16 q
+ * that entry stores at the same index, the zeros of the padding included (0xFF / 0xD5).  running_peak, out_samples,
+ * the readiness rules and every refusal are that entry's; out_stride counts bytes.
+ *
+ * mbv_resample_g711_chunks: mbv_resample_pcm16_chunks_limited (limits_host NULL: no chunk limited) likewise.  The
+ * chunk's `pcm` then points to BYTES (cast the uint8_t pointer) and pcm_capacity counts bytes; packed receives bytes
+ * and packed_capacity counts them; mbv_pcm_chunks_plan counts samples, which are the bytes.  One codec per call.  One
+ * launch per kind (limited / unlimited) as there, counted by mbv_wire_runs with the int16 launches.
+ *
+ * A law other than MBV_G711_ULAW / MBV_G711_ALAW is refused before anything is launched, the handle stays usable.
+ *
+ * Input: a row of mbv_resample_ranges may hold G.711 bytes (wave_dtype MBV_WAVE_ULAW / MBV_WAVE_ALAW); it is staged
+ * as (float)decode(byte) * (1 / 32768), exactly, so every output is bitwise that of the int16 row decode(bytes).
+ * Only mbv_resample_ranges takes these two: telephone audio arrives at 8 kHz, no model runs at that rate, so it
+ * always passes through the resampler; mbv_spectrogram, mbv_convert_rows and mbv_convert_ranges refuse them. */
+#define MBV_G711_ULAW 1
+#define MBV_G711_ALAW 2
+int mbv_g711_encode(mbv_model *m, const int16_t *pcm, int64_t n, int law, uint8_t *out, void *stream);
+int mbv_g711_decode(mbv_model *m, const uint8_t *in, int64_t n, int law, int16_t *pcm, void *stream);
+int mbv_resample_g711_range(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t in_stride,
+                            int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
+                            int64_t out_count, const float *peak, uint8_t *out, int64_t out_stride,
+                            float *running_peak, int64_t *out_samples, const mbv_pcm_limit *limit, int law,
+                            void *stream);
+int mbv_resample_g711_chunks(mbv_model *m, const mbv_pcm_chunk *chunks_host, const mbv_pcm_limit *limits_host, int n,
+                             int orig_sr, int target_sr, int filter, int law, uint8_t *packed,
+                             int64_t packed_capacity, void *stream);
 
 /* ---- seeded noise: standard normals as a pure function of (seed, purpose, row, channel, frame) ---------------
  * Every entry above that takes `noise` / `noise_w` reads a device buffer the caller fills.  These entries fill such
@@ -745,6 +782,8 @@ int64_t mbv_noise_runs(mbv_model *m);
  * copy (cached in the handle); later calls only enqueue one kernel.  Needs no weights. */
 #define MBV_WAVE_F32   0
 #define MBV_WAVE_PCM16 1          /* int16, scaled by 1/32768 (data_utils.py:75) */
+#define MBV_WAVE_ULAW  8          /* G.711 mu-law bytes: rows of mbv_resample_ranges ONLY (2..7 are no dtype) */
+#define MBV_WAVE_ALAW  9          /* G.711 A-law bytes, likewise */
 int mbv_spectrogram(mbv_model *m, const void *wave, int wave_dtype, const int64_t *valid_samples, int B,
                     int64_t in_stride, int n_fft, int hop, int win, float *spec, int64_t frames,
                     int64_t *spec_lengths, void *stream);

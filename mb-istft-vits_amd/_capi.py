@@ -37,6 +37,7 @@ SYMBOLS = [
     "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
     "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
     "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
+    "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range", "mbv_resample_g711_chunks",
 ]
 
 
@@ -117,6 +118,11 @@ class MbvRandnBlock(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("stride", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32),
                 ("first", C.c_int64), ("count", C.c_int64), ("seed", C.c_uint64), ("purpose", C.c_uint32),
                 ("row", C.c_uint32)]
+
+
+# MBV_G711_* / MBV_WAVE_* of include/mbistft_vits.h: the codec of a G.711 wire entry; the dtype of a raw recording
+G711_LAWS = {"ulaw": 1, "alaw": 2}
+WAVE_F32, WAVE_PCM16, WAVE_ULAW, WAVE_ALAW = 0, 1, 8, 9
 
 
 # MBV_NOISE_* of include/mbistft_vits.h: the `purpose` word of the generator's counter
@@ -248,7 +254,8 @@ def lib():
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three and the limiter's three may be absent there, and calling one then raises AttributeError.
+    # seeded noise's three, the limiter's three and G.711's four may be absent there, and calling one then raises
+    # AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -260,8 +267,9 @@ def lib():
                 "mbv_convert_ranges_plan", "mbv_convert_ranges",
                 "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
                 "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
-                "mbv_limiter_ready", "mbv_resample_pcm16_range_limited",
-                "mbv_resample_pcm16_chunks_limited") if os.environ.get("MBV_LIB") else ()
+                "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
+                "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range",
+                "mbv_resample_g711_chunks") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -321,6 +329,13 @@ def lib():
                                                        C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), vp]
         L.mbv_resample_pcm16_chunks_limited.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32,
                                                         i32, i32, vp, C.c_int64, vp]
+    if hasattr(L, "mbv_resample_g711_range") or not optional:
+        L.mbv_g711_encode.argtypes = [vp, vp, C.c_int64, i32, vp, vp]
+        L.mbv_g711_decode.argtypes = [vp, vp, C.c_int64, i32, vp, vp]
+        L.mbv_resample_g711_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64,
+                                              vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32, vp]
+        L.mbv_resample_g711_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32, i32, i32,
+                                               i32, vp, C.c_int64, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -3,6 +3,7 @@
 // the caller's stream.  Reference call stack being replaced: SURVEY §3.1.
 #include "../../include/mbistft_vits.h"
 #include "kernels.h"
+#include "g711.h"
 
 #include <algorithm>
 #include <array>
@@ -3294,11 +3295,20 @@ const char* limit_refusal(const RatePair& rp, const mbv_pcm_limit& l) {
   return nullptr;
 }
 
-// mbv_resample_pcm16_range and its limited form: one body, lim null = no limiter
+static_assert(MBV_G711_ULAW == kLawUlaw && MBV_G711_ALAW == kLawAlaw && MBV_WAVE_ULAW == kWaveUlaw &&
+              MBV_WAVE_ALAW == kWaveAlaw, "G.711 numbers of the C-ABI and the kernels");
+
+// the codec of a G.711 entry, or why it is refused
+const char* law_refusal(int law) {
+  return law == MBV_G711_ULAW || law == MBV_G711_ALAW ? nullptr : "unknown law (MBV_G711_ULAW 1, MBV_G711_ALAW 2)";
+}
+
+// mbv_resample_pcm16_range, its limited form and mbv_resample_g711_range: one body, lim null = no limiter, law
+// kLawNone = int16 (else pcm holds bytes and pcm_stride counts them; the entry has checked law)
 int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
                 int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first, int64_t out_count,
-                const float* peak, int16_t* pcm, int64_t pcm_stride, float* running_peak, int64_t* out_samples,
-                const mbv_pcm_limit* lim, void* stream) {
+                const float* peak, void* pcm, int64_t pcm_stride, float* running_peak, int64_t* out_samples,
+                const mbv_pcm_limit* lim, int law, void* stream) {
   if (!m) return 1;
   if (!wave || !pcm || B <= 0 || in_stride <= 0 || pcm_stride <= 0) return m->fail("%s: bad arguments", who);
   if (B > 65535) return m->fail("%s: more than 65535 rows", who);
@@ -3321,13 +3331,13 @@ int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t*
   ++m->wire_runs;
   if (lim)
     launch_resample_pcm16_range_limited(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count,
-                                        peak, reinterpret_cast<short*>(pcm), pcm_stride,
-                                        reinterpret_cast<unsigned*>(running_peak), out_samples,
-                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, (hipStream_t)stream);
+                                        peak, pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples,
+                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, law,
+                                        (hipStream_t)stream);
   else
     launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
-                                reinterpret_cast<short*>(pcm), pcm_stride, reinterpret_cast<unsigned*>(running_peak),
-                                out_samples, (hipStream_t)stream);
+                                pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, law,
+                                (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3340,7 +3350,8 @@ int mbv_resample_pcm16_range(mbv_model* m, const float* wave, const int64_t* val
                              int64_t out_count, const float* peak, int16_t* pcm, int64_t pcm_stride,
                              float* running_peak, int64_t* out_samples, void* stream) {
   return pcm16_range(m, "mbv_resample_pcm16_range", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
-                     in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, nullptr, stream);
+                     in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, nullptr, kLawNone,
+                     stream);
 }
 
 int mbv_resample_pcm16_range_limited(mbv_model* m, const float* wave, const int64_t* valid_samples, int B,
@@ -3351,7 +3362,17 @@ int mbv_resample_pcm16_range_limited(mbv_model* m, const float* wave, const int6
   if (m && !limit) return m->fail("mbv_resample_pcm16_range_limited: limit missing");
   return pcm16_range(m, "mbv_resample_pcm16_range_limited", wave, valid_samples, B, in_stride, orig_sr, target_sr,
                      filter, in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, limit,
-                     stream);
+                     kLawNone, stream);
+}
+
+int mbv_resample_g711_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
+                            int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first,
+                            int64_t out_count, const float* peak, uint8_t* out, int64_t out_stride, float* running_peak,
+                            int64_t* out_samples, const mbv_pcm_limit* limit, int law, void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_range: %s, got %d", why, law);
+  return pcm16_range(m, "mbv_resample_g711_range", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
+                     in_avail, out_first, out_count, peak, out, out_stride, running_peak, out_samples, limit, law, stream);
 }
 
 int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total, int lookahead) {
@@ -3428,10 +3449,11 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
 }  // extern "C"
 
 namespace {
-// mbv_resample_pcm16_chunks and its limited form: one body, limits null = no row limited.  The rows without a
+// mbv_resample_pcm16_chunks, its limited form and mbv_resample_g711_chunks: one body, limits null = no row limited,
+// law kLawNone = int16 (else every pcm and packed hold bytes; the entry has checked law).  The rows without a
 // limiter go through the unlimited kernel and the limited ones through theirs: one table and one launch per kind
 int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits, int n,
-                 int orig_sr, int target_sr, int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
+                 int orig_sr, int target_sr, int filter, void* packed, int64_t packed_capacity, int law, void* stream) {
   if (!m) return 1;
   if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
   for (int i = 0; i < n; ++i)
@@ -3445,8 +3467,9 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
   if (total < 0) return m->fail("%s", err.c_str());
   if (packed && packed_capacity < total)
     return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
-  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(chunks_host[i].pcm + chunks_host[i].out_first); },
-                                    [&](int i) { return sizeof(int16_t) * (uintptr_t)chunks_host[i].out_count; });
+  const uintptr_t sample_bytes = law == kLawNone ? sizeof(int16_t) : 1;
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)chunks_host[i].pcm + sample_bytes * (uintptr_t)chunks_host[i].out_first; },
+                                    [&](int i) { return sample_bytes * (uintptr_t)chunks_host[i].out_count; });
   if (clash.first >= 0)
     return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, clash.first, clash.second);
   // rows with something to write (an empty range still carries out_samples), by kind
@@ -3477,7 +3500,7 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
     upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
     grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, reinterpret_cast<short*>(packed), s);
+      launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, packed, law, s);
       return 0;
     });
   }
@@ -3489,8 +3512,7 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
     });
     grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      launch_resample_pcm16_pool_limited(rows + f, nn, max_count, rp.bank, rp.g, lds_floats,
-                                         reinterpret_cast<short*>(packed), s);
+      launch_resample_pcm16_pool_limited(rows + f, nn, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
       return 0;
     });
   }
@@ -3504,14 +3526,47 @@ extern "C" {
 int mbv_resample_pcm16_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, int n, int orig_sr, int target_sr,
                               int filter, int16_t* packed, int64_t packed_capacity, void* stream) {
   return pcm16_chunks(m, "mbv_resample_pcm16_chunks", chunks_host, nullptr, n, orig_sr, target_sr, filter, packed,
-                      packed_capacity, stream);
+                      packed_capacity, kLawNone, stream);
 }
 
 int mbv_resample_pcm16_chunks_limited(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host,
                                       int n, int orig_sr, int target_sr, int filter, int16_t* packed,
                                       int64_t packed_capacity, void* stream) {
   return pcm16_chunks(m, "mbv_resample_pcm16_chunks_limited", chunks_host, limits_host, n, orig_sr, target_sr, filter,
-                      packed, packed_capacity, stream);
+                      packed, packed_capacity, kLawNone, stream);
+}
+
+int mbv_resample_g711_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host, int n,
+                             int orig_sr, int target_sr, int filter, int law, uint8_t* packed, int64_t packed_capacity,
+                             void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_chunks: %s, got %d", why, law);
+  return pcm16_chunks(m, "mbv_resample_g711_chunks", chunks_host, limits_host, n, orig_sr, target_sr, filter, packed,
+                      packed_capacity, law, stream);
+}
+
+int mbv_g711_encode(mbv_model* m, const int16_t* pcm, int64_t n, int law, uint8_t* out, void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_g711_encode: %s, got %d", why, law);
+  if (n < 0 || (n > 0 && (!pcm || !out))) return m->fail("mbv_g711_encode: bad arguments");
+  if ((n + 255) / 256 > 0x7fffffff) return m->fail("mbv_g711_encode: too many samples for one grid");
+  if (n == 0) return 0;
+  DEVICE_GUARD(m);
+  launch_g711_encode(reinterpret_cast<const short*>(pcm), n, law, out, (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_g711_decode(mbv_model* m, const uint8_t* in, int64_t n, int law, int16_t* pcm, void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_g711_decode: %s, got %d", why, law);
+  if (n < 0 || (n > 0 && (!in || !pcm))) return m->fail("mbv_g711_decode: bad arguments");
+  if ((n + 255) / 256 > 0x7fffffff) return m->fail("mbv_g711_decode: too many samples for one grid");
+  if (n == 0) return 0;
+  DEVICE_GUARD(m);
+  launch_g711_decode(in, n, law, reinterpret_cast<short*>(pcm), (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
 }
 
 int64_t mbv_wire_runs(mbv_model* m) { return m ? m->wire_runs : -1; }
@@ -3536,7 +3591,8 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
   for (int i = 0; i < n; ++i) {
     const mbv_resample_range& k = rows_host[i];
     if (!k.wave || !k.out) return m->fail("%s: row %d: wave / out missing", who, i);
-    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16)
+    if (k.wave_dtype != MBV_WAVE_F32 && k.wave_dtype != MBV_WAVE_PCM16 && k.wave_dtype != MBV_WAVE_ULAW &&
+        k.wave_dtype != MBV_WAVE_ALAW)
       return m->fail("%s: row %d: unknown wave_dtype %d", who, i, (int)k.wave_dtype);
     if (k.in_avail < 0 || k.in_total < -1 || k.out_first < 0 || k.out_count < 0 || k.out_capacity < 0)
       return m->fail("%s: row %d: in_avail, out_first, out_count and out_capacity must be >= 0, in_total >= -1", who, i);

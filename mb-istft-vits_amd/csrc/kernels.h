@@ -397,10 +397,12 @@ int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total
 // outputs [out_first, out_first + out_count) of every row from x[.., 0 : in_avail) -> int16 (pcm16_kernel's
 // epilogue with the given peaks, null = no normalisation) and the running peak; bank null = equal rates (no FIR).
 // The caller guarantees out_first + out_count <= min(resample_ready(g, in_avail, in_stride), pcm_stride).
+// law (g711.h; the same for the three launchers below): kLawNone stores the int16 (pcm is short*), kLawUlaw / kLawAlaw
+// its G.711 byte at the same index (pcm, pcm_stride, pcm_cap, packed and packed_off then address bytes); DESIGN §7.15.
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
-                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, hipStream_t s);
+                                 const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, int law, hipStream_t s);
 // Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
 // what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
 // the arena (upload_rows).
@@ -410,8 +412,8 @@ struct PcmPoolRow {
   const int64_t* valid;        // one int64, or null = in_total
   int64_t in_avail, out_first, out_end;
   const float* peak;           // one float, or null = no normalisation
-  short* pcm;                  // the stream's own full-length row
-  int64_t pcm_cap;
+  short* pcm;                  // the stream's own full-length row (bytes under a G.711 launch)
+  int64_t pcm_cap;             // in stored samples
   unsigned* running;           // one value, or null
   int64_t* out_samples;        // one value, or null
   int64_t packed_off;          // where out_first goes in the call's packed buffer, or -1
@@ -422,7 +424,7 @@ constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of ker
 // out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
 // in_total), pcm_cap) of every row.
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
-                                const ResampleGeom& g, short* packed, hipStream_t s);
+                                const ResampleGeom& g, void* packed, int law, hipStream_t s);
 // Look-ahead limiter of the wire step (mbv_resample_pcm16_range_limited / mbv_resample_pcm16_chunks_limited, DESIGN
 // §7.14).  With v the sample the unlimited kernels clip (static peak gain included; zero outside the row's computed
 // outputs), all in fp32:
@@ -462,17 +464,24 @@ struct PcmLimRow {
 // out_end <= min(limiter_ready(..), pcm_cap) of every row.
 void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
                                          int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
-                                         int64_t out_count, const float* peak, short* pcm, int64_t pcm_stride,
-                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim,
+                                         int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
+                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
                                          hipStream_t s);
 void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
-                                        const ResampleGeom& g, int64_t lds_floats, short* packed, hipStream_t s);
+                                        const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
+                                        hipStream_t s);
+// the stand-alone codec: n samples, law kLawUlaw or kLawAlaw (checked by the caller)
+void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s);
+void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s);
 // Live input (mbv_resample_ranges): fp32 outputs [out_first, out_end) of MANY recordings that are still arriving,
-// each from its own raw row (fp32, or int16 scaled by 1 / 32768) into its own model-rate row, in one launch.  A
-// table row is one recording; the table lives in the arena (upload_rows, kPcmPoolChunk per launch).
+// each from its own raw row (fp32, int16 scaled by 1 / 32768, or G.711 bytes expanded to that int16) into its own
+// model-rate row, in one launch.  A table row is one recording; the table lives in the arena (upload_rows,
+// kPcmPoolChunk per launch).
+constexpr int kWaveUlaw = 8;   // MBV_WAVE_ULAW / MBV_WAVE_ALAW of the header: the live-input resampler alone takes them
+constexpr int kWaveAlaw = 9;
 struct ResampleRangeRow {
   const void* x;               // the raw recording, read in place
-  int32_t dtype;               // 0 = fp32, 1 = int16
+  int32_t dtype;               // 0 = fp32, 1 = int16, kWaveUlaw, kWaveAlaw
   int32_t closed;              // 1: n is the recording's length (outputs at or past int(n ratio) are zeros)
   int64_t n;                   // raw samples that exist: nothing at or past it is loaded
   int64_t out_first, out_end;

@@ -15,9 +15,11 @@
 // Parity is with a restatement of resampy's algorithm (tests/resample_ref.py), not with the library:
 // its filter tables are rebuilt from the documented specs here.
 #include "kernels.h"
+#include "g711.h"
 
 #include <cmath>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 namespace mbv {
@@ -198,6 +200,17 @@ __device__ __forceinline__ void resample_stage(float* xs, const short* __restric
   }
 }
 
+// the same window of a G.711 recording: the byte expands to its int16 (g711.h), then as above
+template <int LAW>
+__device__ __forceinline__ void resample_stage(float* xs, const uint8_t* __restrict__ xb, int64_t j0, int64_t t_last,
+                                               int L, int M, int K, int left, int64_t limit) {
+  const int W = (int)((t_last * M) / L - left + K - j0);
+  for (int i = threadIdx.x; i < W; i += kResampleTile) {
+    const int64_t j = j0 + i;
+    xs[i] = (j >= 0 && j < limit) ? (float)g711_decode<LAW>(xb[j]) * (1.f / 32768.f) : 0.f;
+  }
+}
+
 // output t from the staged window
 __device__ __forceinline__ float resample_output(const float* xs, int64_t j0, int64_t t, const float* __restrict__ bank,
                                                  int L, int M, int K, int left, double ratio) {
@@ -227,8 +240,9 @@ __device__ __forceinline__ int64_t resample_row_valid(const int64_t* __restrict_
 
 // ---------------------------------------------------------------------------------------------------
 // fp32 tile: outputs [t0, t0 + kResampleTile) below out_end of one row, from its input samples [0, n); outputs in
-// [n_out, out_end) are written as zeros (librosa's fix_length pad and the row padding).  x is fp32 (dtype 0) or int16
-// (dtype 1).  The one-shot kernel and the live-input kernel both store through this function.
+// [n_out, out_end) are written as zeros (librosa's fix_length pad and the row padding).  x is fp32 (dtype 0), int16
+// (dtype 1) or G.711 bytes (kWaveUlaw, kWaveAlaw).  The one-shot kernel and the live-input kernel both store through
+// this function.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void resample_f32_tile(float* xs, const void* x, int dtype, int64_t n, int64_t n_out,
                                                   int64_t t0, int64_t out_end, float* ob,
@@ -242,6 +256,8 @@ __device__ __forceinline__ void resample_f32_tile(float* xs, const void* x, int 
   const int64_t t_last = (t0 + kResampleTile - 1 < n_out - 1) ? t0 + kResampleTile - 1 : n_out - 1;
   const int64_t j0 = resample_window_first(t0, L, M, left);
   if (dtype == 1) resample_stage(xs, static_cast<const short*>(x), j0, t_last, L, M, K, left, n);
+  else if (dtype == kWaveUlaw) resample_stage<kLawUlaw>(xs, static_cast<const uint8_t*>(x), j0, t_last, L, M, K, left, n);
+  else if (dtype == kWaveAlaw) resample_stage<kLawAlaw>(xs, static_cast<const uint8_t*>(x), j0, t_last, L, M, K, left, n);
   else resample_stage(xs, static_cast<const float*>(x), j0, t_last, L, M, K, left, n);
   __syncthreads();
   if (t >= out_end) return;
@@ -322,17 +338,36 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - LIM = true: the look-ahead limiter between the static gain and the clip (resample_pcm16_limited below); the
 //     caller has checked out_end + lookahead <= resample_ready(in_avail) unless the row is complete.  LIM = false
 //     never reads `lim`
+//   - LAW = kLawUlaw / kLawAlaw: the G.711 byte of that int16 is stored where the int16 would be, so
+//     pcm, pcm_cap, packed and packed_off then count bytes; everything before the store is the same code.  Uniform
+//     over a launch, like FIR and LIM
 // ---------------------------------------------------------------------------------------------------
-template <bool FIR>
+// what a wire launch stores for the int16 q
+template <int LAW>
+struct WireSample {
+  using type = uint8_t;
+  static __device__ __forceinline__ uint8_t of(short q) { return g711_encode<LAW>(q); }
+};
+template <>
+struct WireSample<kLawNone> {
+  using type = short;
+  static __device__ __forceinline__ short of(short q) { return q; }
+};
+
+template <bool FIR, int LAW>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
-                                                       int64_t t0, int64_t n_out, int64_t limit, short* pk,
+                                                       int64_t t0, int64_t n_out, int64_t limit,
+                                                       typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
                                                        double ratio);
 
-template <bool FIR, bool LIM>
+template <bool FIR, bool LIM, int LAW>
 __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
                                                     int L, int M, int K, int left, double ratio,
                                                     short* __restrict__ packed, const LimiterParams& lim) {
+  using Sample = WireSample<LAW>;
+  using W = typename Sample::type;
+  W* pcm = reinterpret_cast<W*>(r.pcm);
   const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
   if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
   const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
@@ -344,17 +379,17 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   }
   const int64_t t = t0 + threadIdx.x;
   if (t0 >= r.out_end) return;                            // the empty range (only out_samples to write)
-  short* pk = (packed && r.packed_off >= 0) ? packed + (r.packed_off - r.out_first) : nullptr;
+  W* pk = (packed && r.packed_off >= 0) ? reinterpret_cast<W*>(packed) + (r.packed_off - r.out_first) : nullptr;
   if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
     if (t < r.out_end) {
-      r.pcm[t] = 0;
-      if (pk) pk[t] = 0;
+      pcm[t] = Sample::of(0);
+      if (pk) pk[t] = Sample::of(0);
     }
     return;
   }
   const int64_t limit = n < r.in_avail ? n : r.in_avail;
   if constexpr (LIM) {
-    resample_pcm16_limited<FIR>(xs, r, lim, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
+    resample_pcm16_limited<FIR, LAW>(xs, r, lim, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
     return;
   }
   const float* xb = r.x;
@@ -388,8 +423,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
     v = fminf(fmaxf(v, -1.f), 1.f);
     v = v * 32767.f;
   }
-  const short q = (short)(int)v;
-  r.pcm[t] = q;
+  const W q = Sample::of((short)(int)v);
+  pcm[t] = q;
   if (pk) pk[t] = q;
 }
 
@@ -404,9 +439,10 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
 //      unlimited tile.  Where every m is 1.0f the sum and the quotient are exact, g = 1.0f and y is bitwise v
 // LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
 // over the workgroup; no thread leaves before the last barrier.
-template <bool FIR>
+template <bool FIR, int LAW>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
-                                                       int64_t t0, int64_t n_out, int64_t limit, short* pk,
+                                                       int64_t t0, int64_t n_out, int64_t limit,
+                                                       typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
                                                        double ratio) {
   const int La = lim.lookahead, H = lim.hold;
@@ -475,130 +511,166 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     y = fminf(fmaxf(y, -1.f), 1.f);
     y = y * 32767.f;
   }
-  const short q = (short)(int)y;
-  r.pcm[t] = q;
+  using Sample = WireSample<LAW>;
+  const typename Sample::type q = Sample::of((short)(int)y);
+  reinterpret_cast<typename Sample::type*>(r.pcm)[t] = q;
   if (pk) pk[t] = q;
 }
 
-// Ranged kernel (mbv_resample_pcm16_range): row blockIdx.y of [B] tensors, one range for all rows
-template <bool FIR>
+// Ranged kernel (mbv_resample_pcm16_range, mbv_resample_g711_range): row blockIdx.y of [B] tensors, one range for all
+// rows; pcm_stride counts stored samples (int16, or bytes with a codec)
+template <bool FIR, bool LIM, int LAW>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
                             int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
                             double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
-                            short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
-                            int64_t* __restrict__ out_samples) {
+                            typename WireSample<LAW>::type* __restrict__ pcm, int64_t pcm_stride,
+                            unsigned* __restrict__ running, int64_t* __restrict__ out_samples, LimiterParams lim) {
   extern __shared__ float xs[];
   const int b = blockIdx.y;
   const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
-                     peak ? peak + b : nullptr, pcm + (int64_t)b * pcm_stride, pcm_stride,
+                     peak ? peak + b : nullptr, reinterpret_cast<short*>(pcm + (int64_t)b * pcm_stride), pcm_stride,
                      running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
-  resample_pcm16_tile<FIR, false>(xs, r, bank, L, M, K, left, ratio, nullptr, LimiterParams{});
+  resample_pcm16_tile<FIR, LIM, LAW>(xs, r, bank, L, M, K, left, ratio, nullptr, lim);
 }
 
-// the same rows through the limited tile
-template <bool FIR>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_range_limited_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
-                                    int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
-                                    double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
-                                    short* __restrict__ pcm, int64_t pcm_stride, unsigned* __restrict__ running,
-                                    int64_t* __restrict__ out_samples, LimiterParams lim) {
-  extern __shared__ float xs[];
-  const int b = blockIdx.y;
-  const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
-                     peak ? peak + b : nullptr, pcm + (int64_t)b * pcm_stride, pcm_stride,
-                     running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
-  resample_pcm16_tile<FIR, true>(xs, r, bank, L, M, K, left, ratio, nullptr, lim);
+namespace {
+// f(LAW as a std::integral_constant) for the codec of a launch (the caller has refused every other value)
+template <typename F>
+void with_law(int law, F f) {
+  if (law == kLawUlaw) f(std::integral_constant<int, kLawUlaw>{});
+  else if (law == kLawAlaw) f(std::integral_constant<int, kLawAlaw>{});
+  else f(std::integral_constant<int, kLawNone>{});
 }
 
-void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
-                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
-                                         int64_t out_count, const float* peak, short* pcm, int64_t pcm_stride,
-                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim,
-                                         hipStream_t s) {
+template <bool LIM>
+void launch_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail, const float* bank,
+                  const ResampleGeom& g, int64_t out_first, int64_t out_count, const float* peak, void* pcm,
+                  int64_t pcm_stride, unsigned* running, int64_t* out_samples, const LimiterParams& lim, size_t lds,
+                  int law, hipStream_t s) {
   int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
   const dim3 grid((unsigned)bx, B), block(kResampleTile);
+  with_law(law, [&](auto lc) {
+    constexpr int LAW = decltype(lc)::value;
+    auto* out = static_cast<typename WireSample<LAW>::type*>(pcm);
+    if (bank) {
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW>), grid, block, lds, s, x, valid, in_stride,
+                         in_avail, bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, out,
+                         pcm_stride, running, out_samples, lim);
+    } else {
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW>), grid, block, lds, s, x, valid, in_stride,
+                         in_avail, bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, out, pcm_stride,
+                         running, out_samples, lim);
+    }
+  });
+}
+}  // namespace
+
+void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
+                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
+                                         int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
+                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
+                                         hipStream_t s) {
   const size_t lds = (size_t)limiter_lds_floats(g, bank != nullptr, lim) * sizeof(float);
-  if (bank) {
-    hipLaunchKernelGGL(resample_pcm16_range_limited_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail,
-                       bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
-                       running, out_samples, lim);
-  } else {
-    hipLaunchKernelGGL(resample_pcm16_range_limited_kernel<false>, grid, block, lds, s, x, valid, in_stride, in_avail,
-                       bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
-                       out_samples, lim);
-  }
+  launch_range<true>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
+                     out_samples, lim, lds, law, s);
 }
 
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
-                                 const float* peak, short* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, hipStream_t s) {
-  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
-  const dim3 grid((unsigned)bx, B), block(kResampleTile);
-  if (bank) {
-    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
-    hipLaunchKernelGGL(resample_pcm16_range_kernel<true>, grid, block, lds, s, x, valid, in_stride, in_avail, bank,
-                       g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, pcm, pcm_stride,
-                       running, out_samples);
-  } else {
-    hipLaunchKernelGGL(resample_pcm16_range_kernel<false>, grid, block, 0, s, x, valid, in_stride, in_avail, bank,
-                       1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, pcm, pcm_stride, running,
-                       out_samples);
-  }
+                                 const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, int law, hipStream_t s) {
+  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
+  launch_range<false>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
+                      out_samples, LimiterParams{}, lds, law, s);
 }
 
-// Pooled ranged kernel (mbv_resample_pcm16_chunks): row blockIdx.y of a table, each with its own range; the grid
-// holds the tiles of the longest one
-template <bool FIR>
+// Pooled ranged kernel (mbv_resample_pcm16_chunks, mbv_resample_g711_chunks): row blockIdx.y of a table, each with its
+// own range; the grid holds the tiles of the longest one
+template <bool FIR, int LAW>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
                            int left, double ratio, short* __restrict__ packed) {
   extern __shared__ float xs[];
   const PcmPoolRow r = rows[blockIdx.y];
-  resample_pcm16_tile<FIR, false>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{});
+  resample_pcm16_tile<FIR, false, LAW>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{});
 }
 
 // the same table through the limited tile, each row with its own limiter
-template <bool FIR>
+template <bool FIR, int LAW>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const float* __restrict__ bank, int L, int M,
                                    int K, int left, double ratio, short* __restrict__ packed) {
   extern __shared__ float xs[];
   const PcmLimRow r = rows[blockIdx.y];
-  resample_pcm16_tile<FIR, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim);
+  resample_pcm16_tile<FIR, true, LAW>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim);
 }
 
 void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
-                                        const ResampleGeom& g, int64_t lds_floats, short* packed, hipStream_t s) {
+                                        const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
+                                        hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
   const size_t lds = (size_t)lds_floats * sizeof(float);
-  if (bank) {
-    hipLaunchKernelGGL(resample_pcm16_pool_limited_kernel<true>, grid, block, lds, s, rows, bank, g.L, g.M, g.K,
-                       g.left, g.ratio, packed);
-  } else {
-    hipLaunchKernelGGL(resample_pcm16_pool_limited_kernel<false>, grid, block, lds, s, rows, bank, 1, 1, 0, 0, 1.0,
-                       packed);
-  }
+  short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
+  with_law(law, [&](auto lc) {
+    constexpr int LAW = decltype(lc)::value;
+    if (bank) {
+      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW>), grid, block, lds, s, rows, bank, g.L, g.M,
+                         g.K, g.left, g.ratio, pk);
+    } else {
+      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW>), grid, block, lds, s, rows, bank, 1, 1, 0, 0,
+                         1.0, pk);
+    }
+  });
 }
 
 void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
-                                const ResampleGeom& g, short* packed, hipStream_t s) {
+                                const ResampleGeom& g, void* packed, int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
-  if (bank) {
-    const size_t lds = (size_t)resample_lds_floats(g) * sizeof(float);
-    hipLaunchKernelGGL(resample_pcm16_pool_kernel<true>, grid, block, lds, s, rows, bank, g.L, g.M, g.K, g.left,
-                       g.ratio, packed);
-  } else {
-    hipLaunchKernelGGL(resample_pcm16_pool_kernel<false>, grid, block, 0, s, rows, bank, 1, 1, 0, 0, 1.0, packed);
-  }
+  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
+  short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
+  with_law(law, [&](auto lc) {
+    constexpr int LAW = decltype(lc)::value;
+    if (bank) {
+      hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW>), grid, block, lds, s, rows, bank, g.L, g.M, g.K,
+                         g.left, g.ratio, pk);
+    } else {
+      hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW>), grid, block, lds, s, rows, bank, 1, 1, 0, 0, 1.0,
+                         pk);
+    }
+  });
+}
+
+// Stand-alone codec (mbv_g711_encode / mbv_g711_decode): one sample per thread
+template <int LAW>
+__global__ void __launch_bounds__(256) g711_encode_kernel(const short* __restrict__ pcm, int64_t n,
+                                                          uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = g711_encode<LAW>(pcm[i]);
+}
+
+template <int LAW>
+__global__ void __launch_bounds__(256) g711_decode_kernel(const uint8_t* __restrict__ in, int64_t n,
+                                                          short* __restrict__ pcm) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) pcm[i] = g711_decode<LAW>(in[i]);
+}
+
+void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (law == kLawUlaw) hipLaunchKernelGGL(g711_encode_kernel<kLawUlaw>, grid, block, 0, s, pcm, n, out);
+  else hipLaunchKernelGGL(g711_encode_kernel<kLawAlaw>, grid, block, 0, s, pcm, n, out);
+}
+
+void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (law == kLawUlaw) hipLaunchKernelGGL(g711_decode_kernel<kLawUlaw>, grid, block, 0, s, in, n, pcm);
+  else hipLaunchKernelGGL(g711_decode_kernel<kLawAlaw>, grid, block, 0, s, in, n, pcm);
 }
 
 }  // namespace mbv

@@ -22,6 +22,25 @@ from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
 RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
 
 
+ENCODINGS = ("pcm16", "ulaw", "alaw")     # what the wire step stores: 16-bit linear, or G.711 bytes
+
+
+def _law_code(encoding, what="encoding"):
+    """`encoding=` of a wire entry -> 0 (int16) or the MBV_G711_* code; ValueError for anything else."""
+    if encoding == "pcm16":
+        return 0
+    law = _capi.G711_LAWS.get(encoding) if isinstance(encoding, str) else None
+    if law is None:
+        raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(repr(e) for e in ENCODINGS), encoding))
+    return law
+
+
+def _g711_law(law):
+    if not isinstance(law, str) or law not in _capi.G711_LAWS:
+        raise ValueError("law must be 'ulaw' or 'alaw', got %r" % (law,))
+    return _capi.G711_LAWS[law]
+
+
 def _filter_code(res_type):
     """res_type -> its MBV_RESAMPLE_* code; ValueError for a filter the GPU path does not have."""
     filt = RESAMPLE_TYPES.get(res_type)
@@ -1480,7 +1499,8 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def resample_pcm16_range(self, wave, orig_sr, target_sr, in_avail, out_first, out_count, pcm, valid_samples=None,
-                             peak=None, running_peak=None, out_samples=None, res_type="kaiser_best", limiter=None):
+                             peak=None, running_peak=None, out_samples=None, res_type="kaiser_best", limiter=None,
+                             encoding="pcm16"):
         """One step of the streamed wire output (`mbv_resample_pcm16_range`; `wire.stream_pcm16` drives it for a
         decode stream): int16 samples [out_first, out_first + out_count) of every row of `pcm` [B, n'] from the
         first `in_avail` samples of `wave` (fp32 [B, 1, n] or [B, n], contiguous, on the device; nothing at or
@@ -1495,15 +1515,19 @@ class SynthesizerTrn(nn.Module):
                          look-ahead limiter of DESIGN §7.14 between the gain and the clip
                          (`mbv_resample_pcm16_range_limited`); the range must then end at or below
                          `wire.limiter_ready(orig_sr, target_sr, in_avail, n, lookahead)`
+          encoding       "pcm16", or "ulaw" / "alaw": `pcm` is then uint8 and receives the G.711 byte of the int16 the
+                         call would have stored at the same index (`mbv_resample_g711_range`)
         Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
+        law = _law_code(encoding)
         dev = self._device()
         if wave.dim() == 3 and wave.shape[1] == 1:
             wave = wave[:, 0]
         if wave.dim() != 2 or pcm.dim() != 2 or pcm.shape[0] != wave.shape[0]:
             raise ValueError("wave must be [B, 1, n] or [B, n] and pcm [B, n']")
         B, n = wave.shape
-        for name, t, dt in (("wave", wave, torch.float32), ("pcm", pcm, torch.int16), ("peak", peak, torch.float32),
+        for name, t, dt in (("wave", wave, torch.float32), ("pcm", pcm, torch.uint8 if law else torch.int16),
+                            ("peak", peak, torch.float32),
                             ("running_peak", running_peak, torch.float32), ("out_samples", out_samples, torch.int64),
                             ("valid_samples", valid_samples, torch.int64)):
             if t is None:
@@ -1518,36 +1542,52 @@ class SynthesizerTrn(nn.Module):
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
         args = (wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail), int(out_first),
                 int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
-        if limiter is None:
+        if law:
+            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
+            self._call("mbv_resample_g711_range", *args, lim, law)
+        elif limiter is None:
             self._call("mbv_resample_pcm16_range", *args)
         else:
             self._call("mbv_resample_pcm16_range_limited", *args, C.byref(_capi.MbvPcmLimit(*limiter)))
 
     @torch.no_grad()
-    def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None):
+    def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
+                              encoding="pcm16"):
         """The ranged wire step of many streams in ONE launch (`mbv_resample_pcm16_chunks`; `wire.pcm_pool` drives
         it): `chunks` is a ctypes array (or a list) of `_capi.MbvPcmChunk`, each the arguments of
         `resample_pcm16_range` for one row of its own stream, as device addresses.  Every stored value is bitwise
         what `resample_pcm16_range` stores for that row alone.  `packed` (int16, 1-D, device) also receives the
         chunks' samples back to back, in chunk order.  `limits`: None, or one entry per chunk, each None or the
         (ceiling, lookahead, hold) `resample_pcm16_range` takes as `limiter` (`mbv_resample_pcm16_chunks_limited`:
-        one launch for the limited chunks, one for the others).  No host synchronisation (beyond the first call for a
-        rate pair)."""
+        one launch for the limited chunks, one for the others).  `encoding` "ulaw" / "alaw": every chunk's `pcm` and
+        `packed` are uint8 and receive G.711 bytes (`mbv_resample_g711_chunks`; `pcm_capacity` counts bytes).  No host
+        synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
+        law = _law_code(encoding)
+        wire_dtype = torch.uint8 if law else torch.int16
         if not isinstance(chunks, C.Array):
             chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
         dev = self._device()
         cap = 0
         if packed is not None:
-            if packed.device != dev or packed.dtype != torch.int16 or packed.dim() != 1 or packed.stride(0) != 1:
-                raise ValueError("resample_pcm16_chunks: packed must be a 1-D int16 tensor on %s with unit stride" % dev)
+            if packed.device != dev or packed.dtype != wire_dtype or packed.dim() != 1 or packed.stride(0) != 1:
+                raise ValueError("resample_pcm16_chunks: packed must be a 1-D %s tensor on %s with unit stride"
+                                 % (str(wire_dtype).replace("torch.", ""), dev))
             cap = packed.shape[0]
-        if limits is None or all(l is None for l in limits):
+        unlimited = limits is None or all(l is None for l in limits)
+        if unlimited and not law:
             self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
             return
-        if len(limits) != len(chunks):
-            raise ValueError("resample_pcm16_chunks: one limit per chunk expected (%d), got %d" % (len(chunks), len(limits)))
-        lim = (_capi.MbvPcmLimit * len(chunks))(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+        lim = None
+        if not unlimited:
+            if len(limits) != len(chunks):
+                raise ValueError("resample_pcm16_chunks: one limit per chunk expected (%d), got %d"
+                                 % (len(chunks), len(limits)))
+            lim = (_capi.MbvPcmLimit * len(chunks))(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+        if law:
+            self._call("mbv_resample_g711_chunks", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt, law,
+                       packed, cap)
+            return
         self._call("mbv_resample_pcm16_chunks_limited", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt,
                    packed, cap)
 
@@ -1563,6 +1603,30 @@ class SynthesizerTrn(nn.Module):
         if not isinstance(rows, C.Array):
             rows = (_capi.MbvResampleRange * len(rows))(*rows)
         self._call("mbv_resample_ranges", rows, len(rows), int(orig_sr), int(target_sr), filt)
+
+    @torch.no_grad()
+    def g711_encode(self, pcm, law):
+        """int16 tensor (any shape) -> uint8 tensor of the same shape on the model's device: G.711 mu-law ("ulaw") or
+        A-law ("alaw"), bitwise CPython's `audioop.lin2ulaw` / `lin2alaw` at width 2 (`mbv_g711_encode`)."""
+        code = _g711_law(law)
+        if not torch.is_tensor(pcm) or pcm.dtype != torch.int16:
+            raise TypeError("g711_encode takes an int16 tensor")
+        pcm = pcm.to(self._device()).contiguous()
+        out = torch.empty(pcm.shape, device=pcm.device, dtype=torch.uint8)
+        self._call("mbv_g711_encode", pcm, pcm.numel(), code, out)
+        return out
+
+    @torch.no_grad()
+    def g711_decode(self, data, law):
+        """uint8 tensor (any shape) of G.711 bytes -> int16 tensor of the same shape on the model's device: bitwise
+        `audioop.ulaw2lin` / `alaw2lin` at width 2 (`mbv_g711_decode`)."""
+        code = _g711_law(law)
+        if not torch.is_tensor(data) or data.dtype != torch.uint8:
+            raise TypeError("g711_decode takes a uint8 tensor")
+        data = data.to(self._device()).contiguous()
+        out = torch.empty(data.shape, device=data.device, dtype=torch.int16)
+        self._call("mbv_g711_decode", data, data.numel(), code, out)
+        return out
 
     def input_runs(self):
         """Launches of the live-input resampler made on this model's handle so far (`mbv_input_runs`)."""

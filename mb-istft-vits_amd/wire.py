@@ -31,6 +31,12 @@ of them with one launch per stage and tick.
 `Limiter` is the level control of all of these (`limiter=`): a look-ahead peak limiter fused into the wire step, so
 that a streamed or live int16 output never reaches the hard clip, with a lag of `lookahead` output samples and the
 same bytes however the stream was chunked, pooled or pushed.
+
+`encoding="ulaw" | "alaw"` on all of these makes the wire step store G.711 bytes (8 bits per sample, what a telephony
+media gateway takes at 8 kHz) where it stores int16: the codec is the epilogue of the same kernels, each byte the
+`audioop.lin2ulaw` / `lin2alaw` of the int16 the call would have emitted, so every bitwise relation above carries
+over.  `in_encoding=` lets a live wire take the caller's G.711 bytes as they arrive; `frame_g711` and
+`FrameCutter(sample_bytes=1)` frame such a stream.
 """
 import base64
 import ctypes as C
@@ -40,7 +46,30 @@ import numpy as np
 import torch
 
 from . import _capi
-from .models import RESAMPLE_TYPES, _filter_code      # noqa: F401  (RESAMPLE_TYPES stays a name of this module)
+# (RESAMPLE_TYPES and ENCODINGS stay names of this module)
+from .models import ENCODINGS, RESAMPLE_TYPES, _filter_code, _g711_law, _law_code      # noqa: F401
+
+G711_ZERO = {"ulaw": 0xFF, "alaw": 0xD5}      # the code of the int16 zero: what the wire kernels store as padding
+# `wave_dtype` of a live wire's raw buffer (MBV_WAVE_*), by its dtype or, for uint8, its `in_encoding`
+_WAVE_DTYPE = {torch.float32: _capi.WAVE_F32, torch.int16: _capi.WAVE_PCM16, "ulaw": _capi.WAVE_ULAW,
+               "alaw": _capi.WAVE_ALAW}
+
+
+def _wire_dtype(encoding):
+    """The dtype of the samples a wire step stores: int16, or uint8 for the G.711 encodings (refuses any other)."""
+    return torch.uint8 if _law_code(encoding) else torch.int16
+
+
+def _in_law(in_encoding, in_sr, model_sr, who):
+    """`in_encoding=` of an audio-in entry: None, or "ulaw" / "alaw" with rates that differ (G.711 input always passes
+    through the resampler: telephone audio is at 8 kHz and no model runs at that rate)."""
+    if in_encoding is None:
+        return None
+    _g711_law(in_encoding)
+    if int(in_sr) == int(model_sr):
+        raise ValueError("%s: in_encoding=%r needs in_sr != model_sr (G.711 input goes through the resampler; %d Hz "
+                         "is the model's own rate)" % (who, in_encoding, int(in_sr)))
+    return in_encoding
 
 
 def chunk_size(rate, frame_length=0.02):
@@ -64,6 +93,23 @@ def frame_pcm16(pcm, rate, frame_length=0.02, valid_samples=None):
         raise ValueError("frame_length * rate must be at least one sample")
     pcm = pcm.astype("<i2", copy=False)                    # ndarray.tobytes() of the reference runs on little-endian hosts
     return [base64.b64encode(pcm[t:t + n].tobytes()).decode("utf-8") for t in range(0, len(pcm), n)]
+
+
+def frame_g711(data, rate, frame_length=0.02, valid_samples=None):
+    """`frame_pcm16` for G.711: data 1-D uint8 (numpy array or torch tensor, any device), one byte per sample, of ONE
+    utterance -> list of base64 strings, one per frame of `chunk_size(rate, frame_length)` bytes (160 for 20 ms at
+    8 kHz; the last frame is simply shorter)."""
+    if hasattr(data, "detach"):
+        data = data.detach().cpu().numpy()
+    data = np.ascontiguousarray(data)
+    if data.dtype != np.uint8 or data.ndim != 1:
+        raise ValueError("data must be a 1-D uint8 array (a row of service_pcm16(encoding='ulaw' | 'alaw'))")
+    if valid_samples is not None:
+        data = data[:int(valid_samples)]
+    n = chunk_size(rate, frame_length)
+    if n <= 0:
+        raise ValueError("frame_length * rate must be at least one sample")
+    return [base64.b64encode(data[t:t + n].tobytes()).decode("utf-8") for t in range(0, len(data), n)]
 
 
 class Limiter:
@@ -117,10 +163,12 @@ def _limit_arg(limiter, rate):
     return limiter.resolve(rate)
 
 
-def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak):
-    """`service_pcm16` through the ranged wire kernel over the whole row, which is where the limiter lives: one launch
-    with a given peak (or none), two with auto_normalize (the first measures the peak the second divides by)."""
+def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding="pcm16"):
+    """`service_pcm16` through the ranged wire kernel over the whole row, which is where the limiter and the G.711
+    epilogue live: one launch with a given peak (or none), two with auto_normalize (the first measures the peak the
+    second divides by)."""
     lim = _limit_arg(limiter, rate)
+    dtype = _wire_dtype(encoding)
     dev = net._device()
     if o.dim() != 3 or o.shape[1] != 1:
         raise ValueError("wave must be [B, 1, samples]")
@@ -131,20 +179,20 @@ def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type
     if y_lengths is not None:
         valid_in = (y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
     with torch.cuda.device(dev):
-        pcm = torch.empty(B, stride, device=dev, dtype=torch.int16)
+        pcm = torch.empty(B, stride, device=dev, dtype=dtype)
         valid = torch.zeros(B, device=dev, dtype=torch.int64)
         peak_in = _peak_arg(peak, B, dev)
         if peak_in is None and auto_normalize:
             peak_in = torch.zeros(B, device=dev, dtype=torch.float32)
             net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in,
-                                     running_peak=peak_in, res_type=res_type)
+                                     running_peak=peak_in, res_type=res_type, encoding=encoding)
     net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in, peak=peak_in,
-                             out_samples=valid, res_type=res_type, limiter=lim)
+                             out_samples=valid, res_type=res_type, limiter=lim, encoding=encoding)
     return pcm, valid
 
 
 def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best", limiter=None,
-                  peak=None):
+                  peak=None, encoding="pcm16"):
     """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
     `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
       o          fp32 [B, 1, n] waveforms of `net.infer` (device)
@@ -156,18 +204,25 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
       limiter  a `Limiter`: the look-ahead limiter of DESIGN §7.14 between the gain and the clip; the bytes are then
                those `stream_pcm16(..., limiter=limiter)` emits for the same waveform and peak.  None: as before
       peak     with `limiter` only: a float or fp32 [B] tensor to divide by instead of the utterance's own peak, as
-               `stream_pcm16` takes it (it overrides auto_normalize)"""
+               `stream_pcm16` takes it (it overrides auto_normalize)
+      encoding "ulaw" / "alaw": `pcm` is uint8, the G.711 byte of every int16 the call would have returned (the zero
+               padding becomes 0xFF / 0xD5), fused into the ranged kernel as the limiter is: with auto_normalize one
+               launch for the peak and one that encodes"""
+    law = _law_code(encoding)
     if limiter is not None:
-        return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak)
+        return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding)
     if peak is not None:
         raise ValueError("service_pcm16: peak= is the static gain of the limited path; without limiter= the "
                          "utterance's own peak is used (auto_normalize)")
+    if law:
+        return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, None, None, encoding)
     wave, valid = net.resample(o, model_sr, rate, y_lengths=y_lengths, res_type=res_type)
     return net.to_pcm16(wave, auto_normalize=auto_normalize, valid_samples=valid), valid
 
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
-                  auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None):
+                  auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None, encoding="pcm16",
+                  in_encoding=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -175,18 +230,27 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
       3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
       4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)` (`seed` as `infer` takes it: None =
          torch's generator, as before);
-      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter` as it takes it.
+      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter` and `encoding` as it takes them.
+    `in_encoding` "ulaw" / "alaw": `wave` is uint8 G.711 at `in_sr` != `model_sr`; it is expanded by `net.g711_decode`
+    and goes on as int16.
     -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
     anything is launched when win_size > n_fft or the model has no speakers.  The one host synchronisation is
     the status check `voice_conversion` already has (besides the first-call table uploads of `resample` and
     `spectrogram`)."""
     _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
+    _law_code(encoding)
+    in_law = _in_law(in_encoding, in_sr, model_sr, "convert_pcm16")
+    if (wave.dtype == torch.uint8) != (in_law is not None):
+        raise TypeError("convert_pcm16: uint8 samples need in_encoding='ulaw' | 'alaw', and in_encoding takes uint8 "
+                        "samples (got %s, in_encoding=%r)" % (wave.dtype, in_encoding))
     n_fft = 2 * (net.cfg.spec_channels - 1)
     if not net.n_speakers > 0:
         raise ValueError("convert_pcm16: voice conversion needs a multi-speaker model (n_speakers > 0)")
     if not 1 <= int(win_size) <= n_fft:
         raise ValueError("convert_pcm16: win_size %d must be in [1, n_fft = 2 * (spec_channels - 1) = %d]"
                          % (int(win_size), n_fft))
+    if in_law:
+        wave = net.g711_decode(wave, in_law)
     if wave.dim() == 2:
         wave = wave.unsqueeze(1)
     if wave.dtype == torch.int16 and int(in_sr) != int(model_sr):
@@ -195,7 +259,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
     o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)[0]
     return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type,
-                         limiter=limiter)
+                         limiter=limiter, encoding=encoding)
 
 
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
@@ -259,15 +323,16 @@ def _peak_arg(peak, B, dev, shape="B"):
     return peak
 
 
-# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in
-# and _lim, the resolved limiter or None): from the first `in_avail` samples of `wave` [B, n] to the int16 samples
+# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in,
+# encoding and _lim, the resolved limiter or None): from the first `in_avail` samples of `wave` [B, n] to the int16 samples
 # [out_first, out_first + out_count); `lengths`: this step also writes `valid_samples`.  Alone it is one
 # `mbv_resample_pcm16_range` launch (`..._range_limited` with a limiter), in a pool one row of the
 # `mbv_resample_pcm16_chunks` table (`PcmPool.step` passes the rows' `_lim` along).
 def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
     w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
                                 valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
-                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim)
+                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim,
+                                encoding=w.encoding)
 
 
 def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
@@ -291,7 +356,8 @@ class PcmStream:
 
       pcm            int16 [B, out_stride], out_stride = ceil(spf T' * rate / model_sr); after the last chunk
                      bitwise the `service_pcm16` of the finished `st.o` (auto_normalize = `peak is not None`
-                     when `peak` is the utterance's true peak)
+                     when `peak` is the utterance's true peak).  uint8 G.711 bytes with `encoding` "ulaw" / "alaw",
+                     then bitwise `service_pcm16(..., encoding=encoding)`
       valid_samples  int64 [B] device, the lengths `service_pcm16` returns (written by the first chunk)
       peak           fp32 [B] device, the running peak of the resampled samples emitted so far; after the last
                      chunk bitwise the peak `service_pcm16(auto_normalize=True)` would have divided by
@@ -301,8 +367,9 @@ class PcmStream:
     A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
     such a piece out without launching anything, and launches alone otherwise — the same bytes either way."""
 
-    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None):
+    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16"):
         _refuse_live(st)
+        self.encoding, dtype = encoding, _wire_dtype(encoding)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
@@ -314,7 +381,7 @@ class PcmStream:
         self._ready = [limiter_ready(model_sr, rate, st.spf * (first + count), n, lag, res_type)
                        for first, count in st.schedule]
         self.out_stride = resample_ready(model_sr, rate, n, n, res_type)
-        self.pcm = torch.empty(B, self.out_stride, device=dev, dtype=torch.int16)
+        self.pcm = torch.empty(B, self.out_stride, device=dev, dtype=dtype)
         self.valid_samples = torch.zeros(B, device=dev, dtype=torch.int64)
         self.peak = torch.zeros(B, device=dev, dtype=torch.float32)
         self._valid_in = None                     # valid input samples, as service_pcm16 counts them
@@ -370,7 +437,7 @@ class PcmStream:
         return self.pcm, self.valid_samples
 
 
-def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None):
+def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16"):
     """The streamed `service_pcm16`: wraps a `stream.DecodeStream` (`net.dec_stream` / `net.infer_stream`, not yet
     iterated) in a `PcmStream`.
       peak  None: no normalisation (auto_normalize=False, exact).  A float or an fp32 [B] tensor: every sample is
@@ -382,10 +449,12 @@ def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", lim
       limiter  None, or a `Limiter`: the look-ahead limiter of DESIGN §7.14 after the static gain, so that no sample
             reaches the clip; `peak` and the limiter combine.  The stream then lags by the limiter's lookahead as
             well, and the bytes are those of `service_pcm16(..., limiter=limiter, peak=peak)` on the finished
-            waveform.  Where nothing exceeds the ceiling they are the bytes without a limiter."""
+            waveform.  Where nothing exceeds the ceiling they are the bytes without a limiter.
+      encoding  "pcm16", or "ulaw" / "alaw": the pieces are uint8 G.711 bytes, those of
+            `service_pcm16(..., encoding=encoding)` on the finished waveform."""
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
-    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter)
+    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter, encoding=encoding)
 
 
 def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
@@ -558,16 +627,24 @@ class LiveWire:
       peak           fp32 [1] device, the running peak of the resampled output so far; the `peak=` and the `limiter=`
                      given when the stream was opened are inputs, as for `stream_pcm16`
     With `in_sr == model_sr` the samples go to `LiveStream.push` as they are (int16 stays int16) and no input kernel
-    runs.  A `PcmPool` may feed, step and wire for many at once; pieces it wired are handed out by the next `poll()`
+    runs.  `encoding` "ulaw" / "alaw": `pcm` is uint8 G.711 bytes (unwritten samples hold the code of zero).
+    `in_encoding` "ulaw" / "alaw" with `dtype=torch.uint8`: `push` takes the caller's G.711 bytes, which the input
+    kernel expands while it stages them (`in_sr` must differ from `model_sr`); DESIGN §7.15.  A `PcmPool` may feed, step and wire for many at once; pieces it wired are handed out by the next `poll()`
     without a launch, the same bytes either way."""
 
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                 chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None):
+                 chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
+                 encoding="pcm16", in_encoding=None):
         from .stream import LiveStream
         _filter_code(res_type)
         self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
-        if dtype not in (torch.float32, torch.int16):
+        self.encoding, out_law = encoding, _law_code(encoding)
+        self.in_encoding = _in_law(in_encoding, in_sr, model_sr, "convert_live_pcm16")
+        if (dtype == torch.uint8) != (self.in_encoding is not None):
+            raise TypeError("convert_live_pcm16: dtype=torch.uint8 and in_encoding='ulaw' | 'alaw' go together "
+                            "(got dtype %s, in_encoding=%r)" % (dtype, in_encoding))
+        if dtype not in (torch.float32, torch.int16, torch.uint8):
             raise TypeError("convert_live_pcm16: dtype must be int16 or float32, got %s" % dtype)
         self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
         if min(self.in_sr, self.model_sr, self.rate) <= 0:
@@ -594,7 +671,10 @@ class LiveWire:
         with torch.cuda.device(dev):
             # raw samples beyond the frontier are never read, so the buffer is not cleared
             self.raw = torch.empty(self.max_samples, device=dev, dtype=dtype) if resamples else None
-            self.pcm = torch.zeros(1, self._plan.pcm_capacity, device=dev, dtype=torch.int16)
+            if out_law:                           # silence in G.711 is not the zero byte
+                self.pcm = torch.full((1, self._plan.pcm_capacity), G711_ZERO[encoding], device=dev, dtype=torch.uint8)
+            else:
+                self.pcm = torch.zeros(1, self._plan.pcm_capacity, device=dev, dtype=torch.int16)
             self.valid_samples = torch.zeros(1, device=dev, dtype=torch.int64)
             self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
             # valid input samples of the wire step: the capacity of o while the total is unknown
@@ -648,7 +728,7 @@ class LiveWire:
             return None
         self.live.check_handle()
         p = self._plan
-        row.wave, row.wave_dtype = self.raw.data_ptr(), 1 if self.dtype == torch.int16 else 0
+        row.wave, row.wave_dtype = self.raw.data_ptr(), _WAVE_DTYPE[self.in_encoding or self.dtype]
         row.in_avail, row.in_total = p.raw, p.raw if p.closed else -1
         row.out_first, row.out_count = due
         row.out, row.out_capacity = self.live.samples.data_ptr(), p.capacity
@@ -711,9 +791,11 @@ class LiveWire:
 
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
-                       chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None):
-    """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32) while the recording arrives, int16
-    out at `rate`; -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
+                       chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
+                       encoding="pcm16", in_encoding=None):
+    """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32; G.711 bytes with `dtype=torch.uint8,
+    in_encoding="ulaw" | "alaw"`, which needs `in_sr != model_sr`) while the recording arrives, int16 out at `rate`
+    (G.711 bytes with `encoding="ulaw" | "alaw"`); -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
     `LiveStream` it opens, [1, inter, frames of ceil(max_samples * model_sr / in_sr)].  `peak` and `limiter` as
     `stream_pcm16` takes them: the level of a live recording is whatever the microphone delivers, so there is no
     earlier utterance to take a peak from, and the limiter is the level control.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
@@ -721,7 +803,8 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
     (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead."""
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
-                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter)
+                    max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter,
+                    encoding=encoding, in_encoding=in_encoding)
 
 
 class PcmPool:
@@ -733,17 +816,20 @@ class PcmPool:
     `valid_samples`, `peak`); the pieces count as wired ahead on it, so `next(follower)` afterwards hands them out
     without a launch.  A stream may be driven through the pool, alone, or both in turn: the same bytes, those
     `service_pcm16` gives for the finished waveform.  Finished streams drop out.  Members with a `Limiter` (each its
-    own) share one launch of the limited kernel and the others one of the unlimited: two launches in a mixed tick."""
+    own) share one launch of the limited kernel and the others one of the unlimited: two launches in a mixed tick.
+    One `encoding` per pool, like `rate` and `res_type`: with "ulaw" / "alaw" the followers' `pcm`, the packed buffer
+    and the pinned host buffer are uint8 (`mbv_resample_g711_chunks`), at the same launch counts."""
 
-    def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best"):
+    def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
         _filter_code(res_type)
+        self.encoding, self._dtype = encoding, _wire_dtype(encoding)
         if pool._net is not net:
             raise ValueError("the stream pool belongs to another model")
         self._net, self.pool = net, pool
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         self.followers = []
         self.lives = []                           # the `LiveWire`s added with add_live
-        self._packed = None                       # int16 device, the call's pieces back to back (host=True)
+        self._packed = None                       # device, the call's pieces back to back (host=True)
         self._host = self._host_np = None         # its pinned host copy, and that as a NumPy array
         self._event = None
 
@@ -762,7 +848,8 @@ class PcmPool:
         self.pool.add(st)                         # (refuses B > 1, another model, another device)
         f = self.follower(st)
         if f is None:
-            f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter)
+            f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter,
+                          encoding=self.encoding)
             self.followers.append(f)
         return f
 
@@ -794,6 +881,8 @@ class PcmPool:
                              % (lw.model_sr, lw.rate, self.model_sr, self.rate))
         if lw.res_type != self.res_type:
             raise ValueError("the live wire resamples with %r, the pool with %r" % (lw.res_type, self.res_type))
+        if lw.encoding != self.encoding:
+            raise ValueError("the live wire was opened with encoding %r, the pool with %r" % (lw.encoding, self.encoding))
         self.pool.add(lw.live)                    # (refuses another model, another device)
         if not any(lw is m for m in self.lives):
             self.lives.append(lw)
@@ -818,7 +907,7 @@ class PcmPool:
         """-> [(st, first_out_sample, piece), ...]: one entry per stream whose decoded frontier made outputs final
         (an empty piece is possible, as for `PcmStream`); for a live member `st` is its `LiveWire`, one entry per
         decoded chunk.  `piece` is the 1-D view `follower.pcm[0, a:b]` on the device, ordered on the current stream;
-        with host=True it is a NumPy int16 view of ONE pinned buffer that one copy and one event wait filled, valid
+        with host=True it is a NumPy int16 (uint8 in a G.711 pool) view of ONE pinned buffer that one copy and one event wait filled, valid
         until the next `step(host=True)`.  Live members first resample what has arrived in ONE `mbv_resample_ranges`
         launch; `streams` may name them by their `LiveWire`."""
         net = self._net
@@ -858,13 +947,13 @@ class PcmPool:
                 total, offs = pcm_chunks_plan(self.model_sr, self.rate, arr, self.res_type)
                 if self._packed is None or self._packed.shape[0] < total:
                     cap = max(2 * total, 1 << 16)
-                    self._packed = torch.empty(cap, device=dev, dtype=torch.int16)
-                    self._host = torch.empty(cap, dtype=torch.int16, pin_memory=True)
+                    self._packed = torch.empty(cap, device=dev, dtype=self._dtype)
+                    self._host = torch.empty(cap, dtype=self._dtype, pin_memory=True)
                     self._host_np = self._host.numpy()
                     self._event = torch.cuda.Event()
                 packed = self._packed
             net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
-                                      limits=[w._lim for _, w, _, _ in rows])
+                                      limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding)
             for _, w, _, due in rows:
                 w._chunk_wired(*due)
             if host:
@@ -884,36 +973,41 @@ class PcmPool:
         return out
 
 
-def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best"):
+def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
     """The pooled `stream_pcm16`: a `PcmPool` over a `stream.StreamPool` (`net.stream_pool()`) of the same model.
-    `add(st, peak=None, limiter=None)` takes `peak` and `limiter` as `stream_pcm16` does."""
-    return PcmPool(net, pool, model_sr, rate, res_type=res_type)
+    `add(st, peak=None, limiter=None)` takes `peak` and `limiter` as `stream_pcm16` does; `encoding` is the pool's."""
+    return PcmPool(net, pool, model_sr, rate, res_type=res_type, encoding=encoding)
 
 
 class FrameCutter:
     """`frame_pcm16` for an int16 stream that arrives in pieces: `push` returns the whole frames of
     `chunk_size(rate, frame_length)` samples that are complete, as base64 text, and carries the remainder;
     `close` returns the short last frame, if any.  The frames of all calls are those of `frame_pcm16` on the
-    concatenation."""
+    concatenation.  `sample_bytes=1`: a G.711 stream, uint8 pieces, frames of that many BYTES (`frame_g711`)."""
 
-    def __init__(self, rate, frame_length=0.02):
+    def __init__(self, rate, frame_length=0.02, sample_bytes=2):
+        if sample_bytes not in (1, 2):
+            raise ValueError("sample_bytes must be 2 (int16) or 1 (G.711 bytes), got %r" % (sample_bytes,))
         self.n = chunk_size(rate, frame_length)
         if self.n <= 0:
             raise ValueError("frame_length * rate must be at least one sample")
-        self._rest = np.zeros(0, "<i2")
+        self.sample_bytes = sample_bytes
+        self._wire = np.dtype("<i2" if sample_bytes == 2 else "u1")
+        self._rest = np.zeros(0, self._wire)
 
     def push(self, pcm):
-        """pcm: 1-D int16 (numpy array or torch tensor, any device; may be empty) -> [base64, ...]"""
+        """pcm: 1-D int16 (uint8 with sample_bytes=1; numpy array or torch tensor, any device; may be empty) ->
+        [base64, ...]"""
         if hasattr(pcm, "detach"):
             pcm = pcm.detach().cpu().numpy()
         pcm = np.asarray(pcm)
-        if pcm.dtype != np.int16 or pcm.ndim != 1:
-            raise ValueError("pcm must be a 1-D int16 array")
-        buf = np.concatenate([self._rest, pcm.astype("<i2", copy=False)])
+        if pcm.dtype != (np.int16 if self.sample_bytes == 2 else np.uint8) or pcm.ndim != 1:
+            raise ValueError("pcm must be a 1-D %s array" % ("int16" if self.sample_bytes == 2 else "uint8"))
+        buf = np.concatenate([self._rest, pcm.astype(self._wire, copy=False)])
         whole = len(buf) // self.n * self.n
         self._rest = buf[whole:]
         return [base64.b64encode(buf[t:t + self.n].tobytes()).decode("utf-8") for t in range(0, whole, self.n)]
 
     def close(self):
-        rest, self._rest = self._rest, np.zeros(0, "<i2")
+        rest, self._rest = self._rest, np.zeros(0, self._wire)
         return [base64.b64encode(rest.tobytes()).decode("utf-8")] if len(rest) else []

@@ -721,6 +721,63 @@ int mbv_resample_g711_chunks(mbv_model *m, const mbv_pcm_chunk *chunks_host, con
                              int orig_sr, int target_sr, int filter, int law, uint8_t *packed,
                              int64_t packed_capacity, void *stream);
 
+/* ---- fade-out on the wire: a stream that is revoked ends without a click --------
+ * A fade is (first, count) in output samples of the wire stream.  With k = t - first, the fp32 value of output t that
+ * the entries above clip and quantise (after the static gain, and after the limiter's gain where there is one) is
+ * first multiplied by
+ *   1                            k < 0: the sample is bitwise what the unfaded entry stores
+ *   (float)(count - k) * inv     0 <= k < count;  inv = 1.0f / (float)(count + 1), computed once on the host
+ *   0                            k >= count: a range that overshoots the fade stores silence (int16 0, encode(0))
+ * The ramp is a pure function of t, so every chunk-invariance of the unfaded entries holds for the faded ones, and it
+ * is below 1, so a limited stream still never clips.  count == 0 is a hard cut at `first`; count < 0 means "no fade"
+ * (a row of a pooled call that plays on).  A caller that shortens a stream to first + count simply never asks for
+ * the outputs beyond.
+ *
+ * mbv_pcm_fade_make (host only): fills *out, inv included; -1 when first < 0, count < 0 or out is NULL.
+ *
+ * The four *_faded entries are mbv_resample_pcm16_range_limited, mbv_resample_pcm16_chunks_limited,
+ * mbv_resample_g711_range and mbv_resample_g711_chunks with a fade (range: one for all rows, NULL = none; chunks:
+ * fades_host [n] beside chunks_host, NULL = none) and with limit / limits_host optional (NULL = no limiter).  A row
+ * without a fade is bitwise its row in the unfaded entry.  The launches are those of the unfaded call (one per kind,
+ * mbv_wire_runs); fading rows only add a table upload beside the row table.  Refused before anything is launched,
+ * the handle stays usable: first < 0, and an inv that is not bitwise the one mbv_pcm_fade_make gives for count. */
+typedef struct mbv_pcm_fade { int64_t first; int64_t count; float inv; } mbv_pcm_fade;  /* count < 0: no fade on this row */
+int mbv_pcm_fade_make(int64_t first, int64_t count, mbv_pcm_fade *out);
+int mbv_resample_pcm16_range_faded(mbv_model *m, const float *wave, const int64_t *valid_samples, int B,
+                                   int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                   int64_t out_first, int64_t out_count, const float *peak, int16_t *pcm,
+                                   int64_t pcm_stride, float *running_peak, int64_t *out_samples,
+                                   const mbv_pcm_limit *limit, const mbv_pcm_fade *fade, void *stream);
+int mbv_resample_pcm16_chunks_faded(mbv_model *m, const mbv_pcm_chunk *chunks_host, const mbv_pcm_limit *limits_host,
+                                    const mbv_pcm_fade *fades_host, int n, int orig_sr, int target_sr, int filter,
+                                    int16_t *packed, int64_t packed_capacity, void *stream);
+int mbv_resample_g711_range_faded(mbv_model *m, const float *wave, const int64_t *valid_samples, int B,
+                                  int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                  int64_t out_first, int64_t out_count, const float *peak, uint8_t *out,
+                                  int64_t out_stride, float *running_peak, int64_t *out_samples,
+                                  const mbv_pcm_limit *limit, int law, const mbv_pcm_fade *fade, void *stream);
+int mbv_resample_g711_chunks_faded(mbv_model *m, const mbv_pcm_chunk *chunks_host, const mbv_pcm_limit *limits_host,
+                                   const mbv_pcm_fade *fades_host, int n, int orig_sr, int target_sr, int filter,
+                                   int law, uint8_t *packed, int64_t packed_capacity, void *stream);
+
+/* ---- token marks: where every token starts, in z-frames ------------------------
+ * The exclusive prefix sums of the per-token durations the length regulator uses (predicted, or given with
+ * mbv_set_durations / mbv_enc_row.durations): marks[0] = 0, marks[j] = d_0 + .. + d_{j-1}; entry t_text is the sum, and
+ * entries behind a row's own text repeat it.  They are what a dialogue manager needs to tell which tokens a listener
+ * heard before a stream was revoked.  The scan is the one the duration kernels already ran on the device; these
+ * entries store it as int64 so that the caller can place it next to y_lengths and read both back in ONE copy.  One
+ * launch each, no synchronisation, and no part in mbv_encoder_runs.
+ *
+ * mbv_token_marks: after mbv_encode (and mbv_set_durations): row b of the encoded batch -> marks[b * marks_stride + j],
+ * j in [0, T]; marks_stride >= T + 1 (DEVICE int64).
+ *
+ * mbv_token_marks_rows: after mbv_encode_rows on `slot`, one table row per encoded row, in ONE launch for the run:
+ * `count` entries (1 .. t_text + 1 <= T + 1) to `marks` (DEVICE), nothing where marks is NULL.  rows_host is HOST memory
+ * and travels as kernel arguments.  A call whose rows are all NULL launches nothing. */
+typedef struct mbv_mark_row { int64_t *marks; int32_t count; int32_t reserved; } mbv_mark_row;
+int mbv_token_marks(mbv_model *m, int64_t *marks, int64_t marks_stride, void *stream);
+int mbv_token_marks_rows(mbv_model *m, int slot, const mbv_mark_row *rows_host, int n, void *stream);
+
 /* ---- seeded noise: standard normals as a pure function of (seed, purpose, row, channel, frame) ---------------
  * Every entry above that takes `noise` / `noise_w` reads a device buffer the caller fills.  These entries fill such
  * buffers from a counter-based generator, so that a request's noise depends on its seed alone: not on a global

@@ -38,6 +38,9 @@ SYMBOLS = [
     "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
     "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
     "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range", "mbv_resample_g711_chunks",
+    "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
+    "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
+    "mbv_token_marks", "mbv_token_marks_rows",
 ]
 
 
@@ -79,6 +82,27 @@ class MbvPcmChunk(C.Structure):
 class MbvPcmLimit(C.Structure):
     """mbv_pcm_limit of include/mbistft_vits.h (the limited wire entries); ceiling 0 = this chunk has no limiter."""
     _fields_ = [("ceiling", C.c_float), ("lookahead", C.c_int32), ("hold", C.c_int32)]
+
+
+class MbvPcmFade(C.Structure):
+    """mbv_pcm_fade of include/mbistft_vits.h (the faded wire entries); count < 0 = this chunk has no fade."""
+    _fields_ = [("first", C.c_int64), ("count", C.c_int64), ("inv", C.c_float)]
+
+
+def pcm_fade(first, count):
+    """`mbv_pcm_fade_make` (host only): the `MbvPcmFade` of (first, count), `inv` included; ValueError when refused."""
+    f = MbvPcmFade()
+    if lib().mbv_pcm_fade_make(int(first), int(count), C.byref(f)):
+        raise ValueError("a fade is (first, count) with first >= 0 and count >= 0, got (%r, %r)" % (first, count))
+    return f
+
+
+NO_FADE = (0, -1, 0.0)          # the fields of a table row that does not fade
+
+
+class MbvMarkRow(C.Structure):
+    """mbv_mark_row of include/mbistft_vits.h (mbv_token_marks_rows); marks None = this row has none."""
+    _fields_ = [("marks", C.c_void_p), ("count", C.c_int32), ("reserved", C.c_int32)]
 
 
 class MbvEncRow(C.Structure):
@@ -254,8 +278,8 @@ def lib():
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three, the limiter's three and G.711's four may be absent there, and calling one then raises
-    # AttributeError.
+    # seeded noise's three, the limiter's three, G.711's four, the fade's five and the marks' two may be absent there, and calling one
+    # then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -269,7 +293,10 @@ def lib():
                 "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
                 "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
                 "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range",
-                "mbv_resample_g711_chunks") if os.environ.get("MBV_LIB") else ()
+                "mbv_resample_g711_chunks",
+                "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
+                "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
+                "mbv_token_marks", "mbv_token_marks_rows") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -336,6 +363,22 @@ def lib():
                                               vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32, vp]
         L.mbv_resample_g711_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32, i32, i32,
                                                i32, vp, C.c_int64, vp]
+    if hasattr(L, "mbv_pcm_fade_make") or not optional:
+        fadep = C.POINTER(MbvPcmFade)
+        L.mbv_pcm_fade_make.argtypes = [C.c_int64, C.c_int64, fadep]
+        L.mbv_resample_pcm16_range_faded.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
+                                                     C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit),
+                                                     fadep, vp]
+        L.mbv_resample_pcm16_chunks_faded.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), fadep, i32,
+                                                      i32, i32, i32, vp, C.c_int64, vp]
+        L.mbv_resample_g711_range_faded.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
+                                                    C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32,
+                                                    fadep, vp]
+        L.mbv_resample_g711_chunks_faded.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), fadep, i32,
+                                                     i32, i32, i32, i32, vp, C.c_int64, vp]
+    if hasattr(L, "mbv_token_marks") or not optional:
+        L.mbv_token_marks.argtypes = [vp, vp, C.c_int64, vp]
+        L.mbv_token_marks_rows.argtypes = [vp, i32, C.POINTER(MbvMarkRow), i32, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -3107,6 +3107,44 @@ int mbv_set_durations(mbv_model* m, const void* w, int dtype, int B, int T, int6
   return 0;
 }
 
+int mbv_token_marks(mbv_model* m, int64_t* marks, int64_t marks_stride, void* stream) {
+  if (!m) return 1;
+  if (!m->encoded) return m->fail("mbv_token_marks without a preceding mbv_encode");
+  if (!marks || marks_stride < (int64_t)m->T + 1)
+    return m->fail("mbv_token_marks: marks must be [%d, marks_stride >= %d]", m->B, m->T + 1);
+  if (m->B > 65535) return m->fail("mbv_token_marks: more than 65535 rows");
+  DEVICE_GUARD(m);
+  launch_token_marks(m->cum, m->B, m->T, marks, marks_stride, m->T + 1, nullptr, (hipStream_t)stream);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_token_marks_rows(mbv_model* m, int slot, const mbv_mark_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_token_marks_rows";
+  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
+    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
+  const mbv_model::EncSlot& sl = m->slots[slot];
+  const int B = sl.enc.B, T = sl.enc.T;
+  if (!rows_host || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const mbv_mark_row& k = rows_host[i];
+    if (k.marks && (k.count < 1 || k.count > T + 1))
+      return m->fail("%s: row %d: count %d outside [1, t_text + 1 <= %d]", who, i, k.count, T + 1);
+    any = any || k.marks;
+  }
+  if (!any) return 0;                                      // nothing to write
+  DEVICE_GUARD(m);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, (size_t)n * sizeof(MarkRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  MarkRow* rows = reinterpret_cast<MarkRow*>(m->scrB);
+  upload_rows<kAdmitChunk>(n, rows, s, [&](size_t i) { return MarkRow{rows_host[i].marks, rows_host[i].marks ? rows_host[i].count : 0, 0}; });
+  launch_token_marks(sl.enc.cum, B, T, nullptr, 0, 0, rows, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
 int mbv_istft_finalize(mbv_model* m, const float* spec, const float* phase, int B, int frames,
                        float* o, float* o_mb, void* stream) {
   if (!m) return 1;
@@ -3298,18 +3336,35 @@ const char* limit_refusal(const RatePair& rp, const mbv_pcm_limit& l) {
 static_assert(MBV_G711_ULAW == kLawUlaw && MBV_G711_ALAW == kLawAlaw && MBV_WAVE_ULAW == kWaveUlaw &&
               MBV_WAVE_ALAW == kWaveAlaw, "G.711 numbers of the C-ABI and the kernels");
 
+// the ramp factor of a fade of `count` samples, as mbv_pcm_fade_make computes it
+float fade_inv(int64_t count) { return 1.0f / (float)(count + 1); }
+
+// the fade of a *_faded entry (count < 0: none), or why it is refused
+const char* fade_refusal(const mbv_pcm_fade& f) {
+  if (f.count < 0) return nullptr;
+  if (f.first < 0) return "fade first must be >= 0";
+  const float want = fade_inv(f.count);
+  if (memcmp(&f.inv, &want, sizeof want) != 0) return "fade inv is not the value mbv_pcm_fade_make gives for this count";
+  return nullptr;
+}
+
+PcmFade fade_of(const mbv_pcm_fade* f) { return f && f->count >= 0 ? PcmFade{f->first, f->count, f->inv, 0} : kNoFade; }
+
 // the codec of a G.711 entry, or why it is refused
 const char* law_refusal(int law) {
   return law == MBV_G711_ULAW || law == MBV_G711_ALAW ? nullptr : "unknown law (MBV_G711_ULAW 1, MBV_G711_ALAW 2)";
 }
 
-// mbv_resample_pcm16_range, its limited form and mbv_resample_g711_range: one body, lim null = no limiter, law
-// kLawNone = int16 (else pcm holds bytes and pcm_stride counts them; the entry has checked law)
+// mbv_resample_pcm16_range, its limited form, mbv_resample_g711_range and their faded forms: one body, lim null = no
+// limiter, law kLawNone = int16 (else pcm holds bytes and pcm_stride counts them; the entry has checked law), fade null
+// (or count < 0) = no fade
 int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
                 int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first, int64_t out_count,
                 const float* peak, void* pcm, int64_t pcm_stride, float* running_peak, int64_t* out_samples,
-                const mbv_pcm_limit* lim, int law, void* stream) {
+                const mbv_pcm_limit* lim, int law, void* stream, const mbv_pcm_fade* fade = nullptr) {
   if (!m) return 1;
+  if (fade)
+    if (const char* why = fade_refusal(*fade)) return m->fail("%s: %s", who, why);
   if (!wave || !pcm || B <= 0 || in_stride <= 0 || pcm_stride <= 0) return m->fail("%s: bad arguments", who);
   if (B > 65535) return m->fail("%s: more than 65535 rows", who);
   if (in_avail < 0 || out_first < 0 || out_count < 0)
@@ -3332,12 +3387,12 @@ int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t*
   if (lim)
     launch_resample_pcm16_range_limited(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count,
                                         peak, pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples,
-                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, law,
+                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, law, fade_of(fade),
                                         (hipStream_t)stream);
   else
     launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
                                 pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, law,
-                                (hipStream_t)stream);
+                                fade_of(fade), (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3373,6 +3428,37 @@ int mbv_resample_g711_range(mbv_model* m, const float* wave, const int64_t* vali
   if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_range: %s, got %d", why, law);
   return pcm16_range(m, "mbv_resample_g711_range", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
                      in_avail, out_first, out_count, peak, out, out_stride, running_peak, out_samples, limit, law, stream);
+}
+
+int mbv_pcm_fade_make(int64_t first, int64_t count, mbv_pcm_fade* out) {
+  if (!out || first < 0 || count < 0) {
+    g_create_error = "mbv_pcm_fade_make: first and count must be >= 0, out given";
+    return -1;
+  }
+  *out = mbv_pcm_fade{first, count, fade_inv(count)};
+  return 0;
+}
+
+int mbv_resample_pcm16_range_faded(mbv_model* m, const float* wave, const int64_t* valid_samples, int B,
+                                   int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                   int64_t out_first, int64_t out_count, const float* peak, int16_t* pcm,
+                                   int64_t pcm_stride, float* running_peak, int64_t* out_samples,
+                                   const mbv_pcm_limit* limit, const mbv_pcm_fade* fade, void* stream) {
+  return pcm16_range(m, "mbv_resample_pcm16_range_faded", wave, valid_samples, B, in_stride, orig_sr, target_sr,
+                     filter, in_avail, out_first, out_count, peak, pcm, pcm_stride, running_peak, out_samples, limit,
+                     kLawNone, stream, fade);
+}
+
+int mbv_resample_g711_range_faded(mbv_model* m, const float* wave, const int64_t* valid_samples, int B,
+                                  int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                  int64_t out_first, int64_t out_count, const float* peak, uint8_t* out,
+                                  int64_t out_stride, float* running_peak, int64_t* out_samples,
+                                  const mbv_pcm_limit* limit, int law, const mbv_pcm_fade* fade, void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_range_faded: %s, got %d", why, law);
+  return pcm16_range(m, "mbv_resample_g711_range_faded", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
+                     in_avail, out_first, out_count, peak, out, out_stride, running_peak, out_samples, limit, law, stream,
+                     fade);
 }
 
 int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total, int lookahead) {
@@ -3451,11 +3537,17 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
 namespace {
 // mbv_resample_pcm16_chunks, its limited form and mbv_resample_g711_chunks: one body, limits null = no row limited,
 // law kLawNone = int16 (else every pcm and packed hold bytes; the entry has checked law).  The rows without a
-// limiter go through the unlimited kernel and the limited ones through theirs: one table and one launch per kind
+// limiter go through the unlimited kernel and the limited ones through theirs: one table and one launch per kind.
+// fades null (or every count < 0) = no row fades; else a kind with a fading row gets a second table beside its rows,
+// read by the same launch
 int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits, int n,
-                 int orig_sr, int target_sr, int filter, void* packed, int64_t packed_capacity, int law, void* stream) {
+                 int orig_sr, int target_sr, int filter, void* packed, int64_t packed_capacity, int law, void* stream,
+                 const mbv_pcm_fade* fades = nullptr) {
   if (!m) return 1;
   if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
+  if (fades)
+    for (int i = 0; i < n; ++i)
+      if (const char* why = fade_refusal(fades[i])) return m->fail("%s: chunk %d: %s", who, i, why);
   for (int i = 0; i < n; ++i)
     if (!chunks_host[i].wave || !chunks_host[i].pcm) return m->fail("%s: chunk %d: wave / pcm missing", who, i);
   DEVICE_GUARD(m);
@@ -3485,9 +3577,25 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
     }
   }
   if (live.empty() && live_lim.empty()) return 0;
+  auto fading = [&](const std::vector<int>& kind) {
+    if (fades)
+      for (int i : kind)
+        if (fades[i].count >= 0) return true;
+    return false;
+  };
+  const bool fade_live = fading(live), fade_lim = fading(live_lim);
   const size_t lim_at = align_up(live.size() * sizeof(PcmPoolRow), 256);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, lim_at + live_lim.size() * sizeof(PcmLimRow))) return 1;
+  const size_t fade_at = align_up(lim_at + live_lim.size() * sizeof(PcmLimRow), 256);
+  const size_t fade_lim_at = fade_at + (fade_live ? align_up(live.size() * sizeof(PcmFade), 256) : 0);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, fade_lim_at + (fade_lim ? live_lim.size() * sizeof(PcmFade) : 0))) return 1;
   hipStream_t s = (hipStream_t)stream;
+  // the fade table of a kind with a fading row, in the order of its row table; null for a kind without one
+  auto fade_table = [&](const std::vector<int>& kind, bool any, size_t at) -> PcmFade* {
+    if (!any) return nullptr;
+    PcmFade* t = reinterpret_cast<PcmFade*>(m->scrB + at);
+    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return fade_of(&fades[kind[i]]); });
+    return t;
+  };
   auto row_of = [&](int i) {
     const mbv_pcm_chunk& k = chunks_host[i];
     return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
@@ -3498,9 +3606,10 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
   if (!live.empty()) {
     PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
     upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
+    const PcmFade* ft = fade_table(live, fade_live, fade_at);
     grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      launch_resample_pcm16_pool(rows + f, nn, max_count, rp.bank, rp.g, packed, law, s);
+      launch_resample_pcm16_pool(rows + f, ft ? ft + f : nullptr, nn, max_count, rp.bank, rp.g, packed, law, s);
       return 0;
     });
   }
@@ -3510,9 +3619,11 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
       const mbv_pcm_limit& l = limits[live_lim[i]];
       return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
     });
+    const PcmFade* ft = fade_table(live_lim, fade_lim, fade_lim_at);
     grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      launch_resample_pcm16_pool_limited(rows + f, nn, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
+      launch_resample_pcm16_pool_limited(rows + f, ft ? ft + f : nullptr, nn, max_count, rp.bank, rp.g, lds_floats,
+                                         packed, law, s);
       return 0;
     });
   }
@@ -3543,6 +3654,22 @@ int mbv_resample_g711_chunks(mbv_model* m, const mbv_pcm_chunk* chunks_host, con
   if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_chunks: %s, got %d", why, law);
   return pcm16_chunks(m, "mbv_resample_g711_chunks", chunks_host, limits_host, n, orig_sr, target_sr, filter, packed,
                       packed_capacity, law, stream);
+}
+
+int mbv_resample_pcm16_chunks_faded(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host,
+                                    const mbv_pcm_fade* fades_host, int n, int orig_sr, int target_sr, int filter,
+                                    int16_t* packed, int64_t packed_capacity, void* stream) {
+  return pcm16_chunks(m, "mbv_resample_pcm16_chunks_faded", chunks_host, limits_host, n, orig_sr, target_sr, filter,
+                      packed, packed_capacity, kLawNone, stream, fades_host);
+}
+
+int mbv_resample_g711_chunks_faded(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host,
+                                   const mbv_pcm_fade* fades_host, int n, int orig_sr, int target_sr, int filter,
+                                   int law, uint8_t* packed, int64_t packed_capacity, void* stream) {
+  if (!m) return 1;
+  if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_chunks_faded: %s, got %d", why, law);
+  return pcm16_chunks(m, "mbv_resample_g711_chunks_faded", chunks_host, limits_host, n, orig_sr, target_sr, filter,
+                      packed, packed_capacity, law, stream, fades_host);
 }
 
 int mbv_g711_encode(mbv_model* m, const int16_t* pcm, int64_t n, int law, uint8_t* out, void* stream) {

@@ -224,6 +224,14 @@ void launch_durations(const float* h, const float* w, const float* b, const int*
                       int64_t* ylen64, const int* bad, int B, int C, int T, hipStream_t s);
 // (w == nullptr: h is logw itself, [B, T] — the SDP path)
 // a token of >= 2^20 frames (or inf / NaN) or an utterance of > 2^30: ylen32 = 1, ylen64 = -1 (ops.hip)
+// token marks: dst[b stride + j] = j ? cum[b, j - 1] : 0 for j < count (<= T + 1); with a table (in the arena,
+// upload_rows) row b writes rows[b].count entries to rows[b].dst instead, none where that is null.  One launch.
+struct MarkRow {
+  int64_t* dst;
+  int32_t count, pad_;
+};
+void launch_token_marks(const int* cum, int B, int T, int64_t* dst, int64_t stride, int count, const MarkRow* rows,
+                        hipStream_t s);
 
 // ---------------------------------------------------------------- StochasticDurationPredictor (sdp.hip)
 // DDSConv halves (modules.py:98-111), C <= 256
@@ -399,10 +407,22 @@ int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total
 // The caller guarantees out_first + out_count <= min(resample_ready(g, in_avail, in_stride), pcm_stride).
 // law (g711.h; the same for the three launchers below): kLawNone stores the int16 (pcm is short*), kLawUlaw / kLawAlaw
 // its G.711 byte at the same index (pcm, pcm_stride, pcm_cap, packed and packed_off then address bytes); DESIGN §7.15.
+// Fade-out of the wire step (the *_faded entries): with k = t - first, the fp32 value of output t that
+// the clip and the quantisation take is first multiplied by
+//   1 for k < 0,   (float)(count - k) * inv for 0 <= k < count,   0 for k >= count;      inv = 1.0f / (float)(count + 1)
+// (after the limiter's gain where there is one).  A pure function of t: no state, no halo.  count < 0: no fade, and
+// the value is not touched.  The four launchers take it: one for all rows of a ranged launch, a table beside the row
+// table (null = no row fades) for a pooled one.
+struct PcmFade {
+  int64_t first, count;
+  float inv;
+  int32_t pad_;
+};
+constexpr PcmFade kNoFade{0, -1, 0.f, 0};
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, hipStream_t s);
+                                 int64_t* out_samples, int law, const PcmFade& fade, hipStream_t s);
 // Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
 // what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
 // the arena (upload_rows).
@@ -423,8 +443,9 @@ constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of ker
 // row alone (one tile function); also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
 // out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
 // in_total), pcm_cap) of every row.
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
-                                const ResampleGeom& g, void* packed, int law, hipStream_t s);
+// fades: null, or fades[i] beside rows[i].
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, int n, int64_t max_count,
+                                const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s);
 // Look-ahead limiter of the wire step (mbv_resample_pcm16_range_limited / mbv_resample_pcm16_chunks_limited, DESIGN
 // §7.14).  With v the sample the unlimited kernels clip (static peak gain included; zero outside the row's computed
 // outputs), all in fp32:
@@ -466,10 +487,10 @@ void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, i
                                          int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
                                          int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
                                          unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         hipStream_t s);
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
-                                        const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
-                                        hipStream_t s);
+                                         const PcmFade& fade, hipStream_t s);
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, int n, int64_t max_count,
+                                        const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
+                                        int law, hipStream_t s);
 // the stand-alone codec: n samples, law kLawUlaw or kLawAlaw (checked by the caller)
 void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s);
 void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s);

@@ -229,6 +229,26 @@ void launch_durations_rows(const float* h, const float* w, const float* b, const
                      ylen32, ylen64, bad, C, T);
 }
 
+// Token marks (mbv_token_marks / mbv_token_marks_rows): the EXCLUSIVE prefix sums of the durations the length regulator
+// uses, as int64 next to y_lengths in the caller's read-back buffer.  `cum` is the inclusive scan the kernels above
+// (or launch_set_durations) left, so this is a shifted copy: dst[0] = 0, dst[j] = cum[b, j - 1].  Row b of the grid
+// writes `count` entries to dst + b stride, or, with a table, rows[b].count entries to rows[b].dst (null: none).
+__global__ __launch_bounds__(256) void token_marks_kernel(const int* __restrict__ cum, int T, int64_t* dst,
+                                                          int64_t stride, int count, const MarkRow* __restrict__ rows) {
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  int64_t* d = rows ? rows[b].dst : dst + (int64_t)b * stride;
+  const int n = rows ? rows[b].count : count;
+  if (!d || j >= n || j > T) return;
+  d[j] = j ? (int64_t)cum[(int64_t)b * T + j - 1] : 0;
+}
+
+void launch_token_marks(const int* cum, int B, int T, int64_t* dst, int64_t stride, int count, const MarkRow* rows,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(token_marks_kernel, dim3((unsigned)(T / 256 + 1), B), dim3(256), 0, s, cum, T, dst, stride, count,
+                     rows);
+}
+
 // ---------------------------------------------------------------------------
 // Length regulation (models.py:720-729, commons.py:128-143).  The reference
 // builds a one-hot path [B,1,T',T] and matmuls; it is a gather: frame t' takes

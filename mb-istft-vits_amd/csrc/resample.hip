@@ -341,6 +341,9 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - LAW = kLawUlaw / kLawAlaw: the G.711 byte of that int16 is stored where the int16 would be, so
 //     pcm, pcm_cap, packed and packed_off then count bytes; everything before the store is the same code.  Uniform
 //     over a launch, like FIR and LIM
+//   - fade (kernels.h): the value the clip takes is first scaled by the ramp of its own index t; a row
+//     without one (count < 0) skips the multiply, so its bits are those of a launch that knows no fade.  FADE = false
+//     (a ranged launch without a fade) compiles the test away: that instantiation is the kernel of before
 // ---------------------------------------------------------------------------------------------------
 // what a wire launch stores for the int16 q
 template <int LAW>
@@ -354,17 +357,25 @@ struct WireSample<kLawNone> {
   static __device__ __forceinline__ short of(short q) { return q; }
 };
 
-template <bool FIR, int LAW>
+// the ramp of output t: 1 in front of the fade, (count - k) inv inside it, 0 behind it (a range that overshoots)
+__device__ __forceinline__ float fade_gain(const PcmFade& f, int64_t t) {
+  const int64_t k = t - f.first;
+  if (k < 0) return 1.f;
+  return k < f.count ? (float)(f.count - k) * f.inv : 0.f;
+}
+
+template <bool FIR, int LAW, bool FADE>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
-                                                       int64_t t0, int64_t n_out, int64_t limit,
+                                                       const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
                                                        double ratio);
 
-template <bool FIR, bool LIM, int LAW>
+template <bool FIR, bool LIM, int LAW, bool FADE>
 __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
                                                     int L, int M, int K, int left, double ratio,
-                                                    short* __restrict__ packed, const LimiterParams& lim) {
+                                                    short* __restrict__ packed, const LimiterParams& lim,
+                                                    const PcmFade& fade) {
   using Sample = WireSample<LAW>;
   using W = typename Sample::type;
   W* pcm = reinterpret_cast<W*>(r.pcm);
@@ -389,7 +400,7 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   }
   const int64_t limit = n < r.in_avail ? n : r.in_avail;
   if constexpr (LIM) {
-    resample_pcm16_limited<FIR, LAW>(xs, r, lim, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
+    resample_pcm16_limited<FIR, LAW, FADE>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
     return;
   }
   const float* xb = r.x;
@@ -420,6 +431,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
       const float p = r.peak[0];
       if (p > 0.01f) v = (v / p) * 0.9f;
     }
+    if constexpr (FADE)
+      if (fade.count >= 0) v *= fade_gain(fade, t);
     v = fminf(fmaxf(v, -1.f), 1.f);
     v = v * 32767.f;
   }
@@ -436,12 +449,13 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
 //      that swap, then m[j] = min(a_p[j], a_p[j + Wn - 2^p]), 2^p <= Wn < 2^(p+1).  min is exact: the bits do not
 //      depend on the scheme
 //   3. g[t]: La + 1 fp32 adds in ascending order from m[t - La], one division; y = v g; the epilogue of the
-//      unlimited tile.  Where every m is 1.0f the sum and the quotient are exact, g = 1.0f and y is bitwise v
+//      unlimited tile.  Where every m is 1.0f the sum and the quotient are exact, g = 1.0f and y is bitwise v.
+//      A fade scales y, not v: the limiter sees the unfaded signal, and |y| only shrinks (the ramp is below 1)
 // LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
 // over the workgroup; no thread leaves before the last barrier.
-template <bool FIR, int LAW>
+template <bool FIR, int LAW, bool FADE>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
-                                                       int64_t t0, int64_t n_out, int64_t limit,
+                                                       const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
                                                        double ratio) {
@@ -508,6 +522,8 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     for (int i = 1; i <= La; ++i) sum += b[threadIdx.x + i];
     const float g = sum / (float)(La + 1);
     y = vs[threadIdx.x + La + H] * g;
+    if constexpr (FADE)
+      if (fade.count >= 0) y *= fade_gain(fade, t);
     y = fminf(fmaxf(y, -1.f), 1.f);
     y = y * 32767.f;
   }
@@ -518,20 +534,21 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
 }
 
 // Ranged kernel (mbv_resample_pcm16_range, mbv_resample_g711_range): row blockIdx.y of [B] tensors, one range for all
-// rows; pcm_stride counts stored samples (int16, or bytes with a codec)
-template <bool FIR, bool LIM, int LAW>
+// rows; pcm_stride counts stored samples (int16, or bytes with a codec).  FADE = false never reads `fade`
+template <bool FIR, bool LIM, int LAW, bool FADE>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
                             int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
                             double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
                             typename WireSample<LAW>::type* __restrict__ pcm, int64_t pcm_stride,
-                            unsigned* __restrict__ running, int64_t* __restrict__ out_samples, LimiterParams lim) {
+                            unsigned* __restrict__ running, int64_t* __restrict__ out_samples, LimiterParams lim,
+                            PcmFade fade) {
   extern __shared__ float xs[];
   const int b = blockIdx.y;
   const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
                      peak ? peak + b : nullptr, reinterpret_cast<short*>(pcm + (int64_t)b * pcm_stride), pcm_stride,
                      running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
-  resample_pcm16_tile<FIR, LIM, LAW>(xs, r, bank, L, M, K, left, ratio, nullptr, lim);
+  resample_pcm16_tile<FIR, LIM, LAW, FADE>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade);
 }
 
 namespace {
@@ -547,22 +564,27 @@ template <bool LIM>
 void launch_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail, const float* bank,
                   const ResampleGeom& g, int64_t out_first, int64_t out_count, const float* peak, void* pcm,
                   int64_t pcm_stride, unsigned* running, int64_t* out_samples, const LimiterParams& lim, size_t lds,
-                  int law, hipStream_t s) {
+                  int law, const PcmFade& fade, hipStream_t s) {
   int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
   const dim3 grid((unsigned)bx, B), block(kResampleTile);
-  with_law(law, [&](auto lc) {
+  auto launch = [&](auto lc, auto fc) {
     constexpr int LAW = decltype(lc)::value;
+    constexpr bool FADE = decltype(fc)::value;
     auto* out = static_cast<typename WireSample<LAW>::type*>(pcm);
     if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW>), grid, block, lds, s, x, valid, in_stride,
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW, FADE>), grid, block, lds, s, x, valid, in_stride,
                          in_avail, bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, out,
-                         pcm_stride, running, out_samples, lim);
+                         pcm_stride, running, out_samples, lim, fade);
     } else {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW>), grid, block, lds, s, x, valid, in_stride,
-                         in_avail, bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, out, pcm_stride,
-                         running, out_samples, lim);
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW, FADE>), grid, block, lds, s, x, valid,
+                         in_stride, in_avail, bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, out,
+                         pcm_stride, running, out_samples, lim, fade);
     }
+  };
+  with_law(law, [&](auto lc) {
+    if (fade.count >= 0) launch(lc, std::true_type{});
+    else launch(lc, std::false_type{});
   });
 }
 }  // namespace
@@ -571,45 +593,49 @@ void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, i
                                          int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
                                          int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
                                          unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         hipStream_t s) {
+                                         const PcmFade& fade, hipStream_t s) {
   const size_t lds = (size_t)limiter_lds_floats(g, bank != nullptr, lim) * sizeof(float);
   launch_range<true>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                     out_samples, lim, lds, law, s);
+                     out_samples, lim, lds, law, fade, s);
 }
 
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, hipStream_t s) {
+                                 int64_t* out_samples, int law, const PcmFade& fade, hipStream_t s) {
   const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
   launch_range<false>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                      out_samples, LimiterParams{}, lds, law, s);
+                      out_samples, LimiterParams{}, lds, law, fade, s);
 }
 
 // Pooled ranged kernel (mbv_resample_pcm16_chunks, mbv_resample_g711_chunks): row blockIdx.y of a table, each with its
 // own range; the grid holds the tiles of the longest one
 template <bool FIR, int LAW>
 __global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const float* __restrict__ bank, int L, int M, int K,
-                           int left, double ratio, short* __restrict__ packed) {
+resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const PcmFade* __restrict__ fades,
+                           const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                           short* __restrict__ packed) {
   extern __shared__ float xs[];
   const PcmPoolRow r = rows[blockIdx.y];
-  resample_pcm16_tile<FIR, false, LAW>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{});
+  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
+  resample_pcm16_tile<FIR, false, LAW, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade);
 }
 
 // the same table through the limited tile, each row with its own limiter
 template <bool FIR, int LAW>
 __global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const float* __restrict__ bank, int L, int M,
-                                   int K, int left, double ratio, short* __restrict__ packed) {
+resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const PcmFade* __restrict__ fades,
+                                   const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                                   short* __restrict__ packed) {
   extern __shared__ float xs[];
   const PcmLimRow r = rows[blockIdx.y];
-  resample_pcm16_tile<FIR, true, LAW>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim);
+  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
+  resample_pcm16_tile<FIR, true, LAW, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade);
 }
 
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t max_count, const float* bank,
-                                        const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
-                                        hipStream_t s) {
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, int n, int64_t max_count,
+                                        const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
+                                        int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
@@ -618,17 +644,17 @@ void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, int n, int64_t ma
   with_law(law, [&](auto lc) {
     constexpr int LAW = decltype(lc)::value;
     if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW>), grid, block, lds, s, rows, bank, g.L, g.M,
-                         g.K, g.left, g.ratio, pk);
+      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW>), grid, block, lds, s, rows, fades, bank, g.L,
+                         g.M, g.K, g.left, g.ratio, pk);
     } else {
-      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW>), grid, block, lds, s, rows, bank, 1, 1, 0, 0,
-                         1.0, pk);
+      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW>), grid, block, lds, s, rows, fades, bank, 1, 1,
+                         0, 0, 1.0, pk);
     }
   });
 }
 
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count, const float* bank,
-                                const ResampleGeom& g, void* packed, int law, hipStream_t s) {
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, int n, int64_t max_count,
+                                const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
@@ -637,11 +663,11 @@ void launch_resample_pcm16_pool(const PcmPoolRow* rows, int n, int64_t max_count
   with_law(law, [&](auto lc) {
     constexpr int LAW = decltype(lc)::value;
     if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW>), grid, block, lds, s, rows, bank, g.L, g.M, g.K,
-                         g.left, g.ratio, pk);
+      hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW>), grid, block, lds, s, rows, fades, bank, g.L, g.M,
+                         g.K, g.left, g.ratio, pk);
     } else {
-      hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW>), grid, block, lds, s, rows, bank, 1, 1, 0, 0, 1.0,
-                         pk);
+      hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW>), grid, block, lds, s, rows, fades, bank, 1, 1, 0, 0,
+                         1.0, pk);
     }
   });
 }

@@ -120,14 +120,17 @@ class Request:
                          needs length_scale == 1
       seed               None = the noise comes from torch's generators, as `infer_stream` draws it; an int in
                          [0, 2^64): the request's noise is a function of the seed alone, at row 0
+      marks              True: the stream gets `marks`, the z-frame at which every token starts, as
+                         `infer_stream(marks=True)` gives them
     Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
-                 "max_chunk_frames", "durations", "durations_dtype", "seed")
+                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks")
 
     def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                 chunk_frames=32, max_chunk_frames=256, durations=None, seed=None):
+                 chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False):
         self.seed = None if seed is None else _seed_value(seed, "Request: seed")
+        self.marks = bool(marks)
         if not torch.is_tensor(x):
             x = torch.as_tensor(x)
         if x.dim() != 1:
@@ -627,7 +630,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
-             prior_rows=None, trim=False, ragged=False, durations=None, seed=None):
+             prior_rows=None, trim=False, ragged=False, durations=None, seed=None, marks_out=None):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -643,7 +646,9 @@ class SynthesizerTrn(nn.Module):
           durations    frames per token to use instead of the predicted ones (see `infer`)
           seed         None = both draws come from torch's generators; else (see `infer`) the SDP draw and the prior
                        draw are one `mbv_randn_blocks` launch each and no generator is touched.  A sharded caller
-                       passes the `RowSeeds` of its own rows (row = the global row index)"""
+                       passes the `RowSeeds` of its own rows (row = the global row index)
+          marks_out    a list: receives one host list per row, the token marks of `infer_stream(marks=True)` (one
+                       `mbv_token_marks` launch; they ride in the read-back of T'max, with the rows' x_lengths)"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
@@ -684,7 +689,15 @@ class SynthesizerTrn(nn.Module):
             stat = torch.stack((hi, -lo))           # [T'max, > 0 iff an utterance was flagged -1]
             if stat_reduce is not None:
                 stat_reduce(stat)
-            if ragged:                              # the B lengths ride in the same read-back
+            if marks_out is not None:               # [B, T + 1] exclusive prefix sums, in the same read-back
+                marks_dev = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
+                self._launch(h, "mbv_token_marks", marks_dev, T + 1, stream=stream)
+                host = torch.cat((stat, y_lengths, x_lengths.to(torch.int64), marks_dev.reshape(-1))).tolist()
+                Tp, flag, y_host = int(host[0]), int(host[1]), host[2:2 + B]
+                for b in range(B):
+                    n = max(0, min(int(host[2 + B + b]), T))
+                    marks_out.append([int(v) for v in host[2 + 2 * B + b * (T + 1):2 + 2 * B + b * (T + 1) + n + 1]])
+            elif ragged:                            # the B lengths ride in the same read-back
                 host = torch.cat((stat, y_lengths)).tolist()
                 Tp, flag, y_host = int(host[0]), int(host[1]), host[2:]
             else:
@@ -988,13 +1001,21 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                     chunk_frames=32, max_chunk_frames=256, durations=None, seed=None):
+                     chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
         flows exactly as `infer` does (same random draws; `durations` and `seed` as in `infer`), then returns `dec_stream` of
         z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
-        `infer(...)[0]` (default mode)."""
+        `infer(...)[0]` (default mode).
+          marks  True: `st.marks` is one host list per row (the list itself for a single utterance) of x_lengths + 1
+                 integers, the z-frame at which every token starts: the exclusive prefix sums of the durations the
+                 length regulator used (predicted or given), the last entry their sum, all clipped to the frames the
+                 stream keeps (`max_len`).  One `mbv_token_marks` launch; the integers ride in the read-back the call
+                 already makes, so there is no second host synchronisation.  False (default): `st.marks` is None and
+                 nothing is added."""
+        marks_out = [] if marks else None
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed)
+                      noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed,
+                      marks_out=marks_out)
         y_mask, z, y_lengths = r[5], r[6][0], r[8]
         Tp = z.shape[2]
         Td = Tp if max_len is None else max(0, min(Tp, int(max_len)))
@@ -1006,6 +1027,9 @@ class SynthesizerTrn(nn.Module):
             g = self._speaker_embedding(sid.to(self._device()))
         st = self.dec_stream(zd, g, chunk_frames, max_chunk_frames)
         st.y_lengths = y_lengths
+        if marks:
+            rows = [[min(v, Td) for v in row] for row in marks_out]
+            st.marks = rows[0] if len(rows) == 1 else rows
         return st
 
     # ------------------------------------------------------------------ pooled admission
@@ -1140,7 +1164,14 @@ class SynthesizerTrn(nn.Module):
                                                 [t_text[i] for i in seeded], _capi.NOISE_SDP, noise_w, hip_stream))
             dur, kept = self._pack_host([r.durations for r in reqs], dev)       # (None where none are given)
             keep += kept
-            y_all = torch.empty(N, dtype=torch.int64, device=dev)
+            # [the N lengths | the marks of the requests that want them, t_text + 1 each]: one buffer, one read-back
+            marked = [i for i in range(N) if reqs[i].marks]
+            mark_at, o = {}, N
+            for i in marked:
+                mark_at[i] = o
+                o += t_text[i] + 1
+            y_buf = torch.empty(o, dtype=torch.int64, device=dev)
+            y_all = y_buf[:N]
             # ids (zero-padded to the run's longest text), lengths and sids of every run: ONE host tensor, one copy
             on_host = not any(r.x.is_cuda for r in reqs)
             parts = []
@@ -1165,7 +1196,13 @@ class SynthesizerTrn(nn.Module):
                     row.durations, row.durations_dtype, row.t_text = dur[i], r.durations_dtype or 0, t_text[i]
                 self._launch(h, "mbv_encode_rows", k, C.c_void_p(ids), C.c_void_p(lens), sid, B, T, rows,
                              C.c_void_p(y_all.data_ptr() + 8 * first[k]), stream=hip_stream)
-            y_host = y_all.tolist()                # the one host sync: every run's lengths, -1 = flagged
+                if any(i in mark_at for i in m):   # the run's marks: one table-reading launch
+                    mrows = (_capi.MbvMarkRow * B)()
+                    for row, i in zip(mrows, m):
+                        if i in mark_at:
+                            row.marks, row.count = y_buf.data_ptr() + 8 * mark_at[i], t_text[i] + 1
+                    self._launch(h, "mbv_token_marks_rows", k, mrows, B, stream=hip_stream)
+            y_host = y_buf.tolist()                # the one host sync: every run's lengths, -1 = flagged
             bad = [i for i in range(N) if y_host[pos[i]] < 0]
             if bad:
                 raise IndexError("request%s %s: index out of range in self (token id or sid outside the model's tables, or "
@@ -1200,7 +1237,10 @@ class SynthesizerTrn(nn.Module):
                     self._launch(h, "mbv_speaker_embedding", sids[k], B, g_run, stream=hip_stream)
                     for b, i in enumerate(m):
                         g[i] = g_run[b:b + 1]
-            return self._streams_of(reqs, z, g, y_all, pos)
+            sts = self._streams_of(reqs, z, g, y_all, pos)
+            for i in marked:
+                sts[i].marks = [min(int(v), Td[i]) for v in y_host[mark_at[i]:mark_at[i] + t_text[i] + 1]]
+            return sts
 
     # ------------------------------------------------------------------ pooled voice conversion
     def convert_plan(self, t_frames, splitk=False):
@@ -1500,7 +1540,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def resample_pcm16_range(self, wave, orig_sr, target_sr, in_avail, out_first, out_count, pcm, valid_samples=None,
                              peak=None, running_peak=None, out_samples=None, res_type="kaiser_best", limiter=None,
-                             encoding="pcm16"):
+                             encoding="pcm16", fade=None):
         """One step of the streamed wire output (`mbv_resample_pcm16_range`; `wire.stream_pcm16` drives it for a
         decode stream): int16 samples [out_first, out_first + out_count) of every row of `pcm` [B, n'] from the
         first `in_avail` samples of `wave` (fp32 [B, 1, n] or [B, n], contiguous, on the device; nothing at or
@@ -1517,6 +1557,9 @@ class SynthesizerTrn(nn.Module):
                          `wire.limiter_ready(orig_sr, target_sr, in_avail, n, lookahead)`
           encoding       "pcm16", or "ulaw" / "alaw": `pcm` is then uint8 and receives the G.711 byte of the int16 the
                          call would have stored at the same index (`mbv_resample_g711_range`)
+          fade           None, or (first, count) in output samples: the fade-out of DESIGN §7.16 on every row, through
+                         `mbv_resample_pcm16_range_faded` / `mbv_resample_g711_range_faded`; a `_capi.MbvPcmFade` is
+                         passed as it is (the entry checks it)
         Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
         law = _law_code(encoding)
@@ -1542,7 +1585,15 @@ class SynthesizerTrn(nn.Module):
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
         args = (wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail), int(out_first),
                 int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
-        if law:
+        if fade is not None:
+            if not isinstance(fade, _capi.MbvPcmFade):
+                fade = _capi.pcm_fade(*fade)
+            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
+            if law:
+                self._call("mbv_resample_g711_range_faded", *args, lim, law, C.byref(fade))
+            else:
+                self._call("mbv_resample_pcm16_range_faded", *args, lim, C.byref(fade))
+        elif law:
             lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
             self._call("mbv_resample_g711_range", *args, lim, law)
         elif limiter is None:
@@ -1552,7 +1603,7 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
-                              encoding="pcm16"):
+                              encoding="pcm16", fades=None):
         """The ranged wire step of many streams in ONE launch (`mbv_resample_pcm16_chunks`; `wire.pcm_pool` drives
         it): `chunks` is a ctypes array (or a list) of `_capi.MbvPcmChunk`, each the arguments of
         `resample_pcm16_range` for one row of its own stream, as device addresses.  Every stored value is bitwise
@@ -1560,8 +1611,11 @@ class SynthesizerTrn(nn.Module):
         chunks' samples back to back, in chunk order.  `limits`: None, or one entry per chunk, each None or the
         (ceiling, lookahead, hold) `resample_pcm16_range` takes as `limiter` (`mbv_resample_pcm16_chunks_limited`:
         one launch for the limited chunks, one for the others).  `encoding` "ulaw" / "alaw": every chunk's `pcm` and
-        `packed` are uint8 and receive G.711 bytes (`mbv_resample_g711_chunks`; `pcm_capacity` counts bytes).  No host
-        synchronisation (beyond the first call for a rate pair)."""
+        `packed` are uint8 and receive G.711 bytes (`mbv_resample_g711_chunks`; `pcm_capacity` counts bytes).  `fades`:
+        None, or one entry per chunk, each None, a (first, count) or a `_capi.MbvPcmFade`: the fade-out of DESIGN §7.16
+        on those chunks (`mbv_resample_pcm16_chunks_faded` / `mbv_resample_g711_chunks_faded`), in the launches the call
+        makes without it; all None is the call without `fades`.  No host synchronisation (beyond the first call for a
+        rate pair)."""
         filt = _filter_code(res_type)
         law = _law_code(encoding)
         wire_dtype = torch.uint8 if law else torch.int16
@@ -1575,7 +1629,8 @@ class SynthesizerTrn(nn.Module):
                                  % (str(wire_dtype).replace("torch.", ""), dev))
             cap = packed.shape[0]
         unlimited = limits is None or all(l is None for l in limits)
-        if unlimited and not law:
+        unfaded = fades is None or all(f is None for f in fades)
+        if unlimited and unfaded and not law:
             self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
             return
         lim = None
@@ -1584,6 +1639,20 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError("resample_pcm16_chunks: one limit per chunk expected (%d), got %d"
                                  % (len(chunks), len(limits)))
             lim = (_capi.MbvPcmLimit * len(chunks))(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+        if not unfaded:
+            if len(fades) != len(chunks):
+                raise ValueError("resample_pcm16_chunks: one fade per chunk expected (%d), got %d"
+                                 % (len(chunks), len(fades)))
+            fd = (_capi.MbvPcmFade * len(chunks))(*[
+                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
+                else _capi.pcm_fade(*f) for f in fades])
+            if law:
+                self._call("mbv_resample_g711_chunks_faded", chunks, lim, fd, len(chunks), int(orig_sr),
+                           int(target_sr), filt, law, packed, cap)
+            else:
+                self._call("mbv_resample_pcm16_chunks_faded", chunks, lim, fd, len(chunks), int(orig_sr),
+                           int(target_sr), filt, packed, cap)
+            return
         if law:
             self._call("mbv_resample_g711_chunks", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt, law,
                        packed, cap)

@@ -440,6 +440,7 @@ class DecodeStream:
         self.schedule = chunk_schedule(Tp, chunk_frames, max_chunk_frames)
         self.o = torch.empty(B, 1, self.spf * Tp, device=z.device, dtype=torch.float32)
         self.y_lengths = None
+        self.marks = None             # token marks in z-frames (`infer_stream(marks=True)`); a converted stream has none
         self._next = 0                # the chunk next() hands out
         self._decoded = 0             # the first chunk not decoded yet (>= _next; ahead of it only through a pool)
 
@@ -493,6 +494,11 @@ class DecodeStream:
     def _drained(self):
         return self._decoded >= len(self.schedule)
 
+    def _truncate(self, n_chunks):
+        """A revoked stream (`wire.PcmStream.revoke`) decodes its first `n_chunks` chunks only: the later ones are
+        never issued (n_chunks >= the chunks decoded so far)."""
+        self.schedule = self.schedule[:max(int(n_chunks), self._decoded)]
+
 
 class StreamPool:
     """The next chunk of many `DecodeStream`s of one model in one `mbv_decode_chunks` call per `step()`.
@@ -501,7 +507,8 @@ class StreamPool:
     pooled stream that has one (or of those named) and returns `[(st, first_sample, view), ...]`; the chunks count as
     decoded ahead on their streams, so `next(st)` — and a `wire.PcmStream` over `st` — afterwards hands them out
     without a launch.  A stream may be advanced through the pool, alone, or both in turn.  Streams may be added at
-    any time, one by one (`add`) or as the requests they come from (`admit`); finished ones drop out.
+    any time, one by one (`add`) or as the requests they come from (`admit`); finished ones drop out, and `remove`
+    drops one that is not (a revoked request).
 
     A `LiveStream` is a member like any other: `step()` first converts the pending windows of all live members in one
     `mbv_convert_ranges` run, then decodes at most one decodable chunk of each along with the others' chunks; a live
@@ -529,6 +536,13 @@ class StreamPool:
         if not any(st is m for m in self.streams):
             self.streams.append(st)
         return st
+
+    def remove(self, st):
+        """Drops a member (a revoked request, in a pool without a wire): none of its later chunks is decoded by this
+        pool.  ValueError for a stream that is not a member."""
+        if not any(st is m for m in self.streams):
+            raise ValueError("StreamPool.remove names a stream that is not in the pool")
+        self.streams = [m for m in self.streams if m is not st]
 
     def admit(self, requests):
         """`net.infer_streams(requests)` + `add`: the front half of a tick's new requests in one padded run per class

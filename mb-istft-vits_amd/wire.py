@@ -37,6 +37,13 @@ media gateway takes at 8 kHz) where it stores int16: the codec is the epilogue o
 `audioop.lin2ulaw` / `lin2alaw` of the int16 the call would have emitted, so every bitwise relation above carries
 over.  `in_encoding=` lets a live wire take the caller's G.711 bytes as they arrive; `frame_g711` and
 `FrameCutter(sample_bytes=1)` frame such a stream.
+
+Barge-in: `PcmStream.revoke` / `PcmPool.revoke` take a stream back while it plays: the samples not yet
+handed out fade to silence over a few milliseconds (a ramp inside the same wire kernels, a pure function of the output
+index, so streamed = pooled = one-shot stays bitwise), the stream's length shrinks to the end of the fade, and decoding
+stops with the first chunk that makes that many outputs final (`revoke_plan`).  `service_pcm16(fade=)` is the one-shot
+counterpart.  `mark_samples` maps the token marks of `infer_stream(marks=True)` to wire samples, so that a caller can
+fade at a token boundary (`at="token"`) and learn how many tokens the listener heard begin.
 """
 import base64
 import ctypes as C
@@ -163,7 +170,63 @@ def _limit_arg(limiter, rate):
     return limiter.resolve(rate)
 
 
-def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding="pcm16"):
+def _fade_arg(fade):
+    """`fade=` of a one-shot wire entry -> None or (first, count), both >= 0."""
+    if fade is None:
+        return None
+    first, count = (int(v) for v in fade)
+    if first < 0 or count < 0:
+        raise ValueError("fade is (first, count) in output samples, both >= 0, got %r" % (fade,))
+    return first, count
+
+
+def mark_samples(marks, samples_per_frame, model_sr, rate, lookahead=0):
+    """Token marks in z-frames (`infer_stream(marks=True)`) -> wire sample indices, in pure integers: a mark at frame f
+    maps to ceil(f * samples_per_frame * rate / model_sr) + lookahead, the first wire sample at or after the token's
+    first model sample, moved by the limiter's lag (a limited stream is the unlimited one `lookahead` samples later)."""
+    spf, model_sr, rate, lookahead = int(samples_per_frame), int(model_sr), int(rate), int(lookahead)
+    if spf < 1 or model_sr < 1 or rate < 1 or lookahead < 0:
+        raise ValueError("mark_samples: samples_per_frame and the rates must be positive, lookahead >= 0")
+    return [-((-int(f) * spf * rate) // model_sr) + lookahead for f in marks]
+
+
+def revoke_plan(ready, total, emitted, first, count):
+    """The plan of a revoke in pure integers (no tensor, no GPU).
+      ready    final outputs after each chunk of the schedule, non-decreasing (`resample_ready`, or `limiter_ready`
+               with a limiter); the last is the whole row
+      total    the stream's length in wire samples; emitted: those already handed out (E)
+      first, count   the fade (F, N); F >= E
+    -> (cut, last, ready'): the new length cut = min(total, F + N); the index of the last chunk to decode, the first
+    whose end makes `ready` reach cut; and ready' = min(ready[i], cut) for i <= last: no step asks for an output at or
+    beyond cut."""
+    total, emitted, first, count = int(total), int(emitted), int(first), int(count)
+    if count < 0:
+        raise ValueError("revoke: the fade cannot be shorter than 0 samples")
+    if first < emitted:
+        raise ValueError("revoke: the fade cannot start at sample %d: %d samples have been handed out already"
+                         % (first, emitted))
+    cut = min(total, first + count)
+    last = next(i for i, r in enumerate(ready) if r >= cut or i == len(ready) - 1)
+    return cut, last, [min(r, cut) for r in ready[:last + 1]]
+
+
+class Revoked:
+    """What `revoke` reports: the fade starts at wire sample `first` and lasts `count` samples, the stream now ends at
+    `valid_samples`, and (streams with marks; else None) `tokens_started` tokens begin in front of `first`: those the
+    listener heard begin."""
+
+    __slots__ = ("first", "count", "valid_samples", "tokens_started")
+
+    def __init__(self, first, count, valid_samples, tokens_started):
+        self.first, self.count, self.valid_samples, self.tokens_started = first, count, valid_samples, tokens_started
+
+    def __repr__(self):
+        return "Revoked(first=%d, count=%d, valid_samples=%d, tokens_started=%r)" % (
+            self.first, self.count, self.valid_samples, self.tokens_started)
+
+
+def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding="pcm16",
+                     fade=None):
     """`service_pcm16` through the ranged wire kernel over the whole row, which is where the limiter and the G.711
     epilogue live: one launch with a given peak (or none), two with auto_normalize (the first measures the peak the
     second divides by)."""
@@ -187,12 +250,15 @@ def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type
             net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in,
                                      running_peak=peak_in, res_type=res_type, encoding=encoding)
     net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in, peak=peak_in,
-                             out_samples=valid, res_type=res_type, limiter=lim, encoding=encoding)
+                             out_samples=valid, res_type=res_type, limiter=lim, encoding=encoding, fade=fade)
+    if fade is not None:
+        with torch.cuda.device(dev):
+            valid.clamp_(max=fade[0] + fade[1])
     return pcm, valid
 
 
 def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best", limiter=None,
-                  peak=None, encoding="pcm16"):
+                  peak=None, encoding="pcm16", fade=None):
     """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
     `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
       o          fp32 [B, 1, n] waveforms of `net.infer` (device)
@@ -207,8 +273,19 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
                `stream_pcm16` takes it (it overrides auto_normalize)
       encoding "ulaw" / "alaw": `pcm` is uint8, the G.711 byte of every int16 the call would have returned (the zero
                padding becomes 0xFF / 0xD5), fused into the ranged kernel as the limiter is: with auto_normalize one
-               launch for the peak and one that encodes"""
+               launch for the peak and one that encodes
+      fade     (first, count) in output samples: the fade-out of a revoked stream on the finished waveform (DESIGN
+               §7.16): sample t >= first is scaled by (count - (t - first)) / (count + 1) before the clip, silence from
+               first + count on, and valid_samples becomes min(valid_samples, first + count).  The bytes are those a
+               stream revoked with that fade emitted.  Through the ranged kernel, as `limiter` and `encoding` go"""
     law = _law_code(encoding)
+    fade = _fade_arg(fade)
+    if fade is not None:
+        if limiter is None and peak is not None:
+            raise ValueError("service_pcm16: peak= is the static gain of the limited path; without limiter= the "
+                             "utterance's own peak is used (auto_normalize)")
+        return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding,
+                                fade=fade)
     if limiter is not None:
         return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding)
     if peak is not None:
@@ -222,7 +299,7 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
                   auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None, encoding="pcm16",
-                  in_encoding=None):
+                  in_encoding=None, fade=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -230,7 +307,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
       3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
       4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)` (`seed` as `infer` takes it: None =
          torch's generator, as before);
-      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter` and `encoding` as it takes them.
+      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter`, `encoding` and `fade` as it takes them.
     `in_encoding` "ulaw" / "alaw": `wave` is uint8 G.711 at `in_sr` != `model_sr`; it is expanded by `net.g711_decode`
     and goes on as int16.
     -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
@@ -239,6 +316,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     `spectrogram`)."""
     _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
     _law_code(encoding)
+    _fade_arg(fade)
     in_law = _in_law(in_encoding, in_sr, model_sr, "convert_pcm16")
     if (wave.dtype == torch.uint8) != (in_law is not None):
         raise TypeError("convert_pcm16: uint8 samples need in_encoding='ulaw' | 'alaw', and in_encoding takes uint8 "
@@ -259,7 +337,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
     o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)[0]
     return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type,
-                         limiter=limiter, encoding=encoding)
+                         limiter=limiter, encoding=encoding, fade=fade)
 
 
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
@@ -324,15 +402,16 @@ def _peak_arg(peak, B, dev, shape="B"):
 
 
 # The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in,
-# encoding and _lim, the resolved limiter or None): from the first `in_avail` samples of `wave` [B, n] to the int16 samples
-# [out_first, out_first + out_count); `lengths`: this step also writes `valid_samples`.  Alone it is one
-# `mbv_resample_pcm16_range` launch (`..._range_limited` with a limiter), in a pool one row of the
-# `mbv_resample_pcm16_chunks` table (`PcmPool.step` passes the rows' `_lim` along).
+# encoding, _lim, the resolved limiter or None, and _fade, the (first, count) of a revoke or None): from the first
+# `in_avail` samples of `wave` [B, n] to the int16 samples [out_first, out_first + out_count); `lengths`: this step also
+# writes `valid_samples`.  Alone it is one `mbv_resample_pcm16_range` launch (`..._range_limited` with a limiter,
+# `..._range_faded` once revoked), in a pool one row of the `mbv_resample_pcm16_chunks` table (`PcmPool.step` passes
+# the rows' `_lim` and `_fade` along).
 def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
     w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
                                 valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
                                 out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim,
-                                encoding=w.encoding)
+                                encoding=w.encoding, fade=w._fade)
 
 
 def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
@@ -365,7 +444,11 @@ class PcmStream:
     All state lives in tensors the stream owns, so paused and interleaved streams on one model do not mix.
 
     A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
-    such a piece out without launching anything, and launches alone otherwise — the same bytes either way."""
+    such a piece out without launching anything, and launches alone otherwise — the same bytes either way.
+
+    `marks` (a stream made with `marks=True`; else None) lists the wire sample at which every token starts
+    (`mark_samples`, the limiter's lag included).  `revoke()` takes the stream back with a fade-out; `finished` and
+    `revoked` say where it stands."""
 
     def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16"):
         _refuse_live(st)
@@ -390,9 +473,90 @@ class PcmStream:
         self._peak_in = _peak_arg(peak, B, dev)
         self._done = 0                            # outputs emitted so far
         self._wired = 0                           # the first chunk whose final outputs are not emitted yet
+        self._fade = None                         # (first, count) once revoked with a fade inside the stream
+        self._revoked = None                      # the `Revoked` report of the revoke that stands
+        self._cut = None                          # the length a revoke left: valid_samples is clamped to it
+        # token marks in wire samples (None: the stream carries none, e.g. a converted recording)
+        self.marks = None
+        marks = getattr(st, "marks", None)
+        if marks is not None:
+            each = [mark_samples(m, st.spf, model_sr, rate, lag) for m in (marks if B > 1 else [marks])]
+            self.marks = each if B > 1 else each[0]
 
     def __len__(self):
         return len(self._st)
+
+    @property
+    def finished(self):
+        """Every chunk the stream will decode is wired (after a revoke: every chunk up to the end of the fade)."""
+        return self._wired >= len(self._st.schedule)
+
+    @property
+    def revoked(self):
+        return self._revoked is not None
+
+    def _total(self):
+        """The stream's length in wire samples, on the host: what `valid_samples` holds for a single utterance, whose
+        `y_lengths` covers at least the frames the stream keeps."""
+        n = self._st.o.shape[-1]
+        v = n if self._st.y_lengths is None else min(256 * self._st.z.shape[2], n)
+        return resample_ready(self.model_sr, self.rate, v, v, self.res_type)
+
+    def _clamp_valid(self):
+        # (the first wire step writes valid_samples; a revoke before it is applied right after that step)
+        if self._cut is not None and self._wired > 0:
+            with torch.cuda.device(self.valid_samples.device):
+                self.valid_samples.clamp_(max=self._cut)
+            self._cut = None
+
+    def revoke(self, fade_ms=5.0, at="now"):
+        """Takes the stream back (barge-in): what has been handed out stays, the rest fades to silence
+        and the stream ends there.  With E the samples handed out so far and N = round(fade_ms * rate / 1000):
+          at="now"    the fade starts at F = E
+          at="token"  at the first token mark >= E (`marks`; ValueError on a stream without marks)
+          at=int      at that wire sample (ValueError below E)
+        The stream's length becomes min(old length, F + N) (`valid_samples`); sample t in [F, F + N) is scaled by
+        (N - (t - F)) / (N + 1) before the clip, N = 0 is a hard cut.  Decoding stops with the first chunk whose end
+        makes F + N outputs final (`revoke_plan`): the later chunks are never issued, and `finished` turns true after
+        it.  The whole stream is bitwise `service_pcm16(..., fade=(F, N))` of the finished waveform over the new
+        length.  -> a `Revoked` report.  Revoking a finished or already revoked stream changes nothing and returns
+        the report of what stands.  The 5 ms default is a convention, like the limiter's, not a measurement.  Single
+        utterances only (B = 1), as a pool takes them."""
+        if self._revoked is not None:
+            return self._revoked
+        if self.pcm.shape[0] != 1:
+            raise ValueError("revoke: a stream of ONE utterance is taken back (this one has %d rows)" % self.pcm.shape[0])
+        if not float(fade_ms) >= 0.0:
+            raise ValueError("revoke: fade_ms must be >= 0")
+        total, E = self._total(), self._done
+        if self.finished:
+            return Revoked(total, 0, total, self._started(total))
+        N = int(round(float(fade_ms) * 1e-3 * self.rate))
+        if at == "now":
+            F = E
+        elif at == "token":
+            if self.marks is None:
+                raise ValueError("revoke(at='token'): the stream has no token marks (infer_stream(marks=True); a "
+                                 "converted recording has no tokens)")
+            F = next((m for m in self.marks if m >= E), total)
+        elif isinstance(at, (int, np.integer)) and not isinstance(at, bool):
+            F = int(at)
+        else:
+            raise ValueError("revoke: at must be 'now', 'token' or a wire sample index, got %r" % (at,))
+        cut, last, ready = revoke_plan(self._ready, total, E, F, N)      # (refuses F < E before anything changes)
+        st = self._st
+        keep = max(last + 1, st._decoded, self._wired)
+        st._truncate(keep)
+        self._ready = ready + [cut] * (keep - len(ready))
+        if F < total:
+            self._fade = (F, N)
+        self._cut = cut
+        self._clamp_valid()
+        self._revoked = Revoked(F, N, cut, self._started(F))
+        return self._revoked
+
+    def _started(self, first):
+        return None if self.marks is None else sum(1 for m in self.marks[:-1] if m < first)
 
     def __iter__(self):
         return self
@@ -409,6 +573,7 @@ class PcmStream:
         a, b = self._done, self._ready[i]
         _wire_alone(self, *self._step_through(i))
         self._done, self._wired = b, i + 1
+        self._clamp_valid()
         return a, self.pcm[:, a:b]
 
     def _step_through(self, i):
@@ -429,6 +594,7 @@ class PcmStream:
 
     def _chunk_wired(self, final, pieces):
         self._done, self._wired = pieces[-1][1], self._st._decoded
+        self._clamp_valid()
 
     def run(self):
         """Every remaining chunk; -> (pcm, valid_samples)."""
@@ -680,6 +846,7 @@ class LiveWire:
             # valid input samples of the wire step: the capacity of o while the total is unknown
             self._valid_in = torch.full((1,), self._plan.o_capacity, device=dev, dtype=torch.int64)
             self._peak_in = _peak_arg(peak, 1, dev, shape="1")
+        self._fade = None             # (a live wire is not revoked: the caller stops pushing and drops it)
         self._pieces = []             # (a, b) of every piece wired so far, in order
         self._handed = 0              # the piece poll() hands out next
 
@@ -818,7 +985,8 @@ class PcmPool:
     `service_pcm16` gives for the finished waveform.  Finished streams drop out.  Members with a `Limiter` (each its
     own) share one launch of the limited kernel and the others one of the unlimited: two launches in a mixed tick.
     One `encoding` per pool, like `rate` and `res_type`: with "ulaw" / "alaw" the followers' `pcm`, the packed buffer
-    and the pinned host buffer are uint8 (`mbv_resample_g711_chunks`), at the same launch counts."""
+    and the pinned host buffer are uint8 (`mbv_resample_g711_chunks`), at the same launch counts.
+    `revoke(st)` takes a member back: its fade rides in the tick's launch and it leaves when the fade is out."""
 
     def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
         _filter_code(res_type)
@@ -867,6 +1035,25 @@ class PcmPool:
         for lim in limiters:
             _limit_arg(lim, self.rate)
         return [self.add(st, peak=p, limiter=lim) for st, p, lim in zip(self.pool.admit(reqs), peaks, limiters)]
+
+    def revoke(self, st, fade_ms=5.0, at="now"):
+        """`PcmStream.revoke` for a member added with `add` or `admit` (a text request or a converted recording; `st`
+        is the decode stream or its follower): the fade rides in the pool's one wire launch per tick, the member's
+        later chunks are never decoded, and it leaves this pool and the wrapped `StreamPool` when the fade is out
+        (at once, when nothing is left to wire).  -> the `Revoked` report.  A live member is not revoked (ValueError,
+        nothing launched): a caller who hangs up stops pushing and drops the wire.  The 5 ms default is a convention,
+        not a measurement."""
+        if isinstance(st, LiveWire) or any(st is lw.live for lw in self.lives):
+            raise ValueError("PcmPool.revoke: a live member is not revoked (stop pushing and drop the LiveWire)")
+        f = st if isinstance(st, PcmStream) else self.follower(st)
+        if f is None or not any(f is m for m in self.followers):
+            raise ValueError("PcmPool.revoke names a stream that is not in the pool")
+        report = f.revoke(fade_ms=fade_ms, at=at)
+        if f.finished:
+            self.followers = [m for m in self.followers if m is not f]
+            if any(f._st is m for m in self.pool.streams):
+                self.pool.remove(f._st)
+        return report
 
     def add_live(self, lw, limiter=None):
         """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
@@ -953,7 +1140,8 @@ class PcmPool:
                     self._event = torch.cuda.Event()
                 packed = self._packed
             net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
-                                      limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding)
+                                      limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
+                                      fades=[w._fade for _, w, _, _ in rows])
             for _, w, _, due in rows:
                 w._chunk_wired(*due)
             if host:

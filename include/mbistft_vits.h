@@ -778,6 +778,54 @@ typedef struct mbv_mark_row { int64_t *marks; int32_t count; int32_t reserved; }
 int mbv_token_marks(mbv_model *m, int64_t *marks, int64_t marks_stride, void *stream);
 int mbv_token_marks_rows(mbv_model *m, int slot, const mbv_mark_row *rows_host, int n, void *stream);
 
+/* ---- loudness: ITU-R BS.1770 integrated loudness of a mono waveform, on the device ------------------------------
+ * K-weighting (two cascaded biquads, zero state at sample 0), segments of H = (rate + 5) / 10 samples (100 ms; a half
+ * rounds up), blocks of four segments (400 ms, 75 % overlap), the absolute gate at -70 LKFS and the relative gate 10 LU
+ * below the loudness of the absolute-gated blocks; L = -0.691 + 10 log10(mean z of the blocks that pass both), -inf
+ * when there are fewer than four complete segments or no block passes.  An incomplete last segment is dropped.
+ *
+ * The cascade runs in transposed direct form II in fp64, state s = (shelf s1, s2, high-pass s1, s2):
+ *   y = b0 x + s1;  s1 = b1 x - a1 y + s2;  s2 = b2 x - a2 y     per stage, the shelf's y being the high-pass's x
+ * The kernel is parallel over segments: the zero-state end state r_k of every segment, the chain s_{k+1} = M s_k + r_k
+ * in segment order (M the H-step zero-input transition of s), then every energy e_k = sum y^2 from its true start
+ * state.  Inside a segment the arithmetic is a fixed function of the samples and s_k, so e_k, the state and L do not
+ * depend on how the segments were cut into calls.  One launch a call, one workgroup a row; no synchronisation.
+ *
+ * mbv_kweighting (host only): coeffs = shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2} for `rate` by the
+ * bilinear re-derivation of the standard's 48 kHz table (which it reproduces to 1e-14); M row-major 4 x 4.
+ * mbv_loudness_segments (host only): -> samples / H, and H to *hop (may be NULL); -1 when refused.
+ *
+ * mbv_loudness: row b of wave [B, in_stride] (DEVICE fp32) over its first valid_samples[b] samples (DEVICE int64,
+ * clamped to the row; NULL = whole rows) -> loudness[b] (DEVICE fp32).  energies: NULL, or DEVICE fp64
+ * [B, in_stride / H]: e_k of every complete segment, 0 behind the row's valid length.
+ *
+ * mbv_loudness_range: segments [seg_first, seg_first + seg_count) of every row, of which the first in_avail samples
+ * exist.  state (DEVICE fp64 [B, 4]) carries s between calls; a call with seg_first == 0 starts from zero whatever it
+ * holds.  energies (DEVICE fp64 [B, energy_stride]) receives the range and is read below it; loudness[b] becomes the
+ * integrated loudness of segments [0, seg_first + seg_count).  A row whose valid_samples ends inside the range
+ * measures up to there.
+ *
+ * mbv_loudness_chunks: the same with every per-row quantity from a table row, ONE launch for all rows that have
+ * segments (a call in which none has launches nothing).  chunks_host is HOST memory and travels as kernel arguments.
+ *
+ * Refused before anything is launched, the handle stays usable: a rate below 1000 Hz; a range that does not start at
+ * the row's next segment (the handle remembers, by state buffer, where the last call on it ended; 0 always starts
+ * over); a range that ends beyond in_avail / H or beyond the energies; a NULL state, energies or loudness.
+ * mbv_loudness_runs counts the launches. */
+typedef struct mbv_loudness_chunk {
+  const float *wave; int64_t in_total; const int64_t *valid_samples; int64_t in_avail;
+  int64_t seg_first; int64_t seg_count; double *state; double *energies; int64_t energy_capacity; float *loudness;
+} mbv_loudness_chunk;
+int mbv_kweighting(int rate, double *coeffs /* [10] */, double *M /* [16] */);
+int64_t mbv_loudness_segments(int rate, int64_t samples, int32_t *hop);
+int mbv_loudness(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t in_stride, int rate,
+                 float *loudness, double *energies, void *stream);
+int mbv_loudness_range(mbv_model *m, const float *wave, const int64_t *valid_samples, int B, int64_t in_stride, int rate,
+                       int64_t in_avail, int64_t seg_first, int64_t seg_count, double *state, double *energies,
+                       int64_t energy_stride, float *loudness, void *stream);
+int mbv_loudness_chunks(mbv_model *m, const mbv_loudness_chunk *chunks_host, int n, int rate, void *stream);
+int64_t mbv_loudness_runs(mbv_model *m);
+
 /* ---- seeded noise: standard normals as a pure function of (seed, purpose, row, channel, frame) ---------------
  * Every entry above that takes `noise` / `noise_w` reads a device buffer the caller fills.  These entries fill such
  * buffers from a counter-based generator, so that a request's noise depends on its seed alone: not on a global

@@ -41,6 +41,8 @@ SYMBOLS = [
     "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
     "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
     "mbv_token_marks", "mbv_token_marks_rows",
+    "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
+    "mbv_loudness_runs",
 ]
 
 
@@ -103,6 +105,32 @@ NO_FADE = (0, -1, 0.0)          # the fields of a table row that does not fade
 class MbvMarkRow(C.Structure):
     """mbv_mark_row of include/mbistft_vits.h (mbv_token_marks_rows); marks None = this row has none."""
     _fields_ = [("marks", C.c_void_p), ("count", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MbvLoudnessChunk(C.Structure):
+    """mbv_loudness_chunk of include/mbistft_vits.h (mbv_loudness_chunks)."""
+    _fields_ = [("wave", C.c_void_p), ("in_total", C.c_int64), ("valid_samples", C.c_void_p), ("in_avail", C.c_int64),
+                ("seg_first", C.c_int64), ("seg_count", C.c_int64), ("state", C.c_void_p), ("energies", C.c_void_p),
+                ("energy_capacity", C.c_int64), ("loudness", C.c_void_p)]
+
+
+def kweighting(rate):
+    """`mbv_kweighting` (host only) -> (coeffs, M): the ten K-weighting coefficients of `rate` (shelf b0 b1 b2 a1 a2,
+    high-pass b0 b1 b2 a1 a2) and the 4 x 4 H-step transition matrix, row-major, as float64 lists; ValueError when
+    the rate is refused."""
+    c, m = (C.c_double * 10)(), (C.c_double * 16)()
+    if lib().mbv_kweighting(int(rate), c, m):
+        raise ValueError((lib().mbv_last_error(None) or b"mbv_kweighting failed").decode())
+    return list(c), list(m)
+
+
+def loudness_segments(rate, samples):
+    """`mbv_loudness_segments` (host only, pure integers) -> (H, samples // H); ValueError when refused."""
+    hop = C.c_int32()
+    n = lib().mbv_loudness_segments(int(rate), int(samples), C.byref(hop))
+    if n < 0:
+        raise ValueError((lib().mbv_last_error(None) or b"mbv_loudness_segments failed").decode())
+    return int(hop.value), int(n)
 
 
 class MbvEncRow(C.Structure):
@@ -278,7 +306,7 @@ def lib():
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three, the limiter's three, G.711's four, the fade's five and the marks' two may be absent there, and calling one
+    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two and loudness's six may be absent there, and calling one
     # then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
@@ -296,7 +324,9 @@ def lib():
                 "mbv_resample_g711_chunks",
                 "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
                 "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
-                "mbv_token_marks", "mbv_token_marks_rows") if os.environ.get("MBV_LIB") else ()
+                "mbv_token_marks", "mbv_token_marks_rows",
+                "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
+                "mbv_loudness_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -379,6 +409,17 @@ def lib():
     if hasattr(L, "mbv_token_marks") or not optional:
         L.mbv_token_marks.argtypes = [vp, vp, C.c_int64, vp]
         L.mbv_token_marks_rows.argtypes = [vp, i32, C.POINTER(MbvMarkRow), i32, vp]
+    if hasattr(L, "mbv_loudness") or not optional:
+        dp = C.POINTER(C.c_double)
+        L.mbv_kweighting.argtypes = [i32, dp, dp]
+        L.mbv_loudness_segments.argtypes = [i32, C.c_int64, C.POINTER(C.c_int32)]
+        L.mbv_loudness_segments.restype = C.c_int64
+        L.mbv_loudness.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp]
+        L.mbv_loudness_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, C.c_int64, C.c_int64, C.c_int64, vp, vp,
+                                         C.c_int64, vp, vp]
+        L.mbv_loudness_chunks.argtypes = [vp, C.POINTER(MbvLoudnessChunk), i32, i32, vp]
+        L.mbv_loudness_runs.argtypes = [vp]
+        L.mbv_loudness_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -142,6 +143,9 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
   int64_t noise_runs = 0;          // mbv_randn_blocks launches (mbv_noise_runs)
+  int64_t loudness_runs = 0;       // launches of the loudness kernel (mbv_loudness_runs)
+  std::map<int, LoudnessParams> loudness_params;    // rate -> K-weighting tables (built once a rate, host only)
+  std::map<const void*, int64_t> loudness_next;     // state buffer of a measured row -> its next segment
   char* noise_tab = nullptr; size_t noise_tab_bytes = 0;   // mbv_randn_blocks' table: its own buffer, so that a fill
                                                            // between an encode and its synthesize disturbs no scratch
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
@@ -3828,6 +3832,159 @@ int mbv_randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, in
 }
 
 int64_t mbv_noise_runs(mbv_model* m) { return m ? m->noise_runs : -1; }
+
+}  // extern "C"
+
+namespace {
+// the rate of a loudness entry, or why it is refused (the upper end bounds the host's H-step matrix product)
+const char* loudness_rate_refusal(int rate) {
+  if (rate < 1000) return "rate must be at least 1000 Hz";
+  if (rate > 768000) return "rate must be at most 768000 Hz";
+  return nullptr;
+}
+
+const LoudnessParams& loudness_params(mbv_model* m, int rate) {
+  auto it = m->loudness_params.find(rate);
+  if (it == m->loudness_params.end()) {
+    LoudnessParams p{};
+    kweighting_host(rate, &p);
+    it = m->loudness_params.emplace(rate, p).first;
+  }
+  return it->second;
+}
+
+// mbv_loudness_range and mbv_loudness_chunks: the checks on every row, then ONE launch for the rows with segments
+int loudness_chunks(mbv_model* m, const char* who, const mbv_loudness_chunk* chunks, int n, int rate, void* stream) {
+  if (const char* why = loudness_rate_refusal(rate)) return m->fail("%s: %s, got %d", who, why, rate);
+  const LoudnessParams& p = loudness_params(m, rate);
+  std::vector<int> live;
+  std::set<const void*> states;
+  for (int i = 0; i < n; ++i) {
+    const mbv_loudness_chunk& k = chunks[i];
+    if (!k.wave) return m->fail("%s: chunk %d: wave missing", who, i);
+    if (!k.state || !k.energies || !k.loudness) return m->fail("%s: chunk %d: state / energies / loudness missing", who, i);
+    if (k.in_total <= 0 || k.in_avail < 0 || k.in_avail > k.in_total || k.seg_first < 0 || k.seg_count < 0 || k.energy_capacity < 0)
+      return m->fail("%s: chunk %d: need in_total > 0, 0 <= in_avail <= in_total, seg_first, seg_count and energy_capacity >= 0", who, i);
+    const int64_t have = k.in_avail / p.H, end = k.seg_first + k.seg_count;
+    if (end > have)
+      return m->fail("%s: chunk %d: segments up to %lld asked for, but %lld samples hold only %lld complete segments of %d",
+                     who, i, (long long)end, (long long)k.in_avail, (long long)have, (int)p.H);
+    if (end > k.energy_capacity)
+      return m->fail("%s: chunk %d: segments up to %lld lie outside the energies of capacity %lld", who, i, (long long)end,
+                     (long long)k.energy_capacity);
+    if (k.seg_first != 0) {
+      const auto it = m->loudness_next.find(k.state);
+      const int64_t next = it == m->loudness_next.end() ? 0 : it->second;
+      if (next != k.seg_first)
+        return m->fail("%s: chunk %d: the range starts at segment %lld, but the row's next segment is %lld", who, i,
+                       (long long)k.seg_first, (long long)next);
+    }
+    if (!states.insert(k.state).second) return m->fail("%s: chunk %d: a state buffer appears twice in one call", who, i);
+    if (k.seg_count > 0) live.push_back(i);
+  }
+  // (a row that starts over is remembered even when it brings no segment: its buffer's earlier use is forgotten)
+  for (int i = 0; i < n; ++i)
+    if (chunks[i].seg_count == 0) m->loudness_next[chunks[i].state] = chunks[i].seg_first;
+  if (live.empty()) return 0;
+  DEVICE_GUARD(m);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(LoudnessRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB);
+  upload_rows<kLoudnessChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_loudness_chunk& k = chunks[live[i]];
+    return LoudnessRow{k.wave, k.valid_samples, k.in_avail, k.seg_first, k.seg_first + k.seg_count, k.state, k.energies,
+                       k.loudness};
+  });
+  ++m->loudness_runs;
+  launch_loudness(rows, (int)live.size(), p, s);
+  HIPCHK(m, hipGetLastError());
+  for (int i : live) m->loudness_next[chunks[i].state] = chunks[i].seg_first + chunks[i].seg_count;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mbv_kweighting(int rate, double* coeffs, double* M) {
+  if (const char* why = loudness_rate_refusal(rate)) {
+    g_create_error = std::string("mbv_kweighting: ") + why;
+    return 1;
+  }
+  if (!coeffs || !M) {
+    g_create_error = "mbv_kweighting: coeffs / M missing";
+    return 1;
+  }
+  LoudnessParams p{};
+  kweighting_host(rate, &p);
+  memcpy(coeffs, p.coef, sizeof p.coef);
+  memcpy(M, p.M, sizeof p.M);
+  return 0;
+}
+
+int64_t mbv_loudness_segments(int rate, int64_t samples, int32_t* hop) {
+  if (const char* why = loudness_rate_refusal(rate)) {
+    g_create_error = std::string("mbv_loudness_segments: ") + why;
+    return -1;
+  }
+  if (samples < 0) {
+    g_create_error = "mbv_loudness_segments: samples must be >= 0";
+    return -1;
+  }
+  const int32_t H = (rate + 5) / 10;
+  if (hop) *hop = H;
+  return samples / H;
+}
+
+int mbv_loudness(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride, int rate,
+                 float* loudness, double* energies, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_loudness";
+  if (const char* why = loudness_rate_refusal(rate)) return m->fail("%s: %s, got %d", who, why, rate);
+  if (!wave || !loudness || B <= 0 || in_stride <= 0) return m->fail("%s: bad arguments", who);
+  const LoudnessParams& p = loudness_params(m, rate);
+  const int64_t segs = in_stride / p.H;
+  DEVICE_GUARD(m);
+  // scratch: the rows' states, their energies where the caller wants none, then the table
+  const size_t energy_at = align_up((size_t)B * 4 * sizeof(double), 256);
+  const size_t table_at = energy_at + (energies ? 0 : align_up((size_t)B * (size_t)segs * sizeof(double), 256));
+  if (ensure(m, &m->scrB, &m->scrB_bytes, table_at + (size_t)B * sizeof(LoudnessRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  double* state = reinterpret_cast<double*>(m->scrB);
+  double* e = energies ? energies : reinterpret_cast<double*>(m->scrB + energy_at);
+  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB + table_at);
+  upload_rows<kLoudnessChunk>((size_t)B, rows, s, [&](size_t b) {
+    return LoudnessRow{wave + b * in_stride, valid_samples ? valid_samples + b : nullptr, in_stride, 0, segs,
+                       state + 4 * b, e + b * segs, loudness + b};
+  });
+  ++m->loudness_runs;
+  launch_loudness(rows, B, p, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_loudness_range(mbv_model* m, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride, int rate,
+                       int64_t in_avail, int64_t seg_first, int64_t seg_count, double* state, double* energies,
+                       int64_t energy_stride, float* loudness, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_loudness_range";
+  if (B <= 0 || in_stride <= 0 || energy_stride < 0) return m->fail("%s: bad arguments", who);
+  if (!state || !energies) return m->fail("%s: state / energies missing", who);
+  if (!wave || !loudness) return m->fail("%s: wave / loudness missing", who);
+  std::vector<mbv_loudness_chunk> rows((size_t)B);
+  for (int b = 0; b < B; ++b)
+    rows[b] = mbv_loudness_chunk{wave + (int64_t)b * in_stride, in_stride, valid_samples ? valid_samples + b : nullptr,
+                                 in_avail, seg_first, seg_count, state + 4 * b, energies + (int64_t)b * energy_stride,
+                                 energy_stride, loudness + b};
+  return loudness_chunks(m, who, rows.data(), B, rate, stream);
+}
+
+int mbv_loudness_chunks(mbv_model* m, const mbv_loudness_chunk* chunks_host, int n, int rate, void* stream) {
+  if (!m) return 1;
+  if (n < 0 || (n > 0 && !chunks_host)) return m->fail("mbv_loudness_chunks: bad arguments");
+  return loudness_chunks(m, "mbv_loudness_chunks", chunks_host, n, rate, stream);
+}
+
+int64_t mbv_loudness_runs(mbv_model* m) { return m ? m->loudness_runs : -1; }
 
 namespace {
 const char* spectrogram_args_error(int n_fft, int hop, int win) {

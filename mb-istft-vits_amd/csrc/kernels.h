@@ -651,4 +651,32 @@ void launch_randn_blocks(const RandnRow* rows, int n, int64_t total, hipStream_t
 // the same values on the host (fp32 logf / sqrtf / sinf / cosf): frames [first, first + count) of channel c
 void randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, int64_t first, int64_t count, float* dst);
 
+// ---------------------------------------------------------------- loudness (loudness.hip)
+// ITU-R BS.1770 integrated loudness of mono fp32 rows, measured in 100 ms segments of H samples.  The K-weighting
+// cascade runs in transposed direct form II, state (s1, s2) of the shelf then (s1, s2) of the high-pass, in fp64:
+//   y = b0 x + s1;  s1 = b1 x - a1 y + s2;  s2 = b2 x - a2 y          (per stage; the shelf's y is the high-pass's x)
+// coef = shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2}; M = the H-step zero-input transition of that
+// state, row-major; both built by kweighting_host in float64 and carried as kernel arguments.
+struct LoudnessParams {
+  double coef[10];
+  double M[16];
+  double z_abs;                // 10^((-70 + 0.691) / 10): the absolute gate on a block's mean square
+  int32_t H, pad_;
+};
+// rate >= 1000 (checked by the caller): H = (rate + 5) / 10 and the tables above
+void kweighting_host(int rate, LoudnessParams* p);
+// One table row = segments [k0, k1) of one waveform row; the table lives in the arena (upload_rows).
+struct LoudnessRow {
+  const float* x;              // the row's samples
+  const int64_t* valid;        // one int64 (clamped to [0, avail]), or null = avail
+  int64_t avail;               // samples of x that exist: nothing at or past it is read
+  int64_t k0, k1;              // k1 * H <= avail; segments at or past valid / H count as absent (their energy is 0)
+  double* state;               // 4 doubles: s_{k0} in (ignored, zero, when k0 == 0), s_{min(k1, valid / H)} out
+  double* energy;              // e_k for k in [k0, k1); entries [0, k0) are read by the gate pass
+  float* L;                    // one float: the integrated loudness over segments [0, min(k1, valid / H))
+};
+constexpr int kLoudnessChunk = 32;   // rows per upload_rows launch: 2 KiB of kernel arguments
+// every row of the table in ONE launch (one workgroup a row); n >= 1
+void launch_loudness(const LoudnessRow* rows, int n, const LoudnessParams& p, hipStream_t s);
+
 }  // namespace mbv

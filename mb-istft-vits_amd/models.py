@@ -1697,6 +1697,72 @@ class SynthesizerTrn(nn.Module):
         self._call("mbv_g711_decode", data, data.numel(), code, out)
         return out
 
+    # ------------------------------------------------------------------ loudness
+    @torch.no_grad()
+    def loudness(self, wave, rate, y_lengths=None, valid_samples=None, return_energies=False):
+        """Waveform [B, 1, n] (fp32, mono, at `rate` Hz) -> fp32 [B] on the device: the ITU-R BS.1770 integrated
+        loudness (LUFS) of every row over its valid samples (`mbv_loudness`): K-weighting, 400 ms blocks
+        of four 100 ms segments, the -70 LKFS and the relative gate; -inf for a row with fewer than four complete
+        segments or none that passes.  Valid samples come from `y_lengths` (frames, x256, clamped to the row) or
+        `valid_samples` (samples); neither = whole rows.  One launch, no host synchronisation, nothing copied to the
+        host.  `return_energies=True`: -> (L, energies fp64 [B, n // H]), the K-weighted energy of every 100 ms
+        segment (0 behind a row's valid length)."""
+        rate = int(rate)
+        H, segs = _capi.loudness_segments(rate, wave.shape[-1])          # (refuses the rate before anything else)
+        if y_lengths is not None and valid_samples is not None:
+            raise ValueError("loudness: give y_lengths (frames) or valid_samples (samples), not both")
+        if wave.dim() != 3 or wave.shape[1] != 1 or wave.shape[0] < 1 or wave.shape[-1] < 1:
+            raise ValueError("wave must be [B, 1, samples]")
+        dev = self._device()
+        wave = wave.to(device=dev, dtype=torch.float32).contiguous()
+        B, n = wave.shape[0], wave.shape[-1]
+        if y_lengths is not None:
+            valid_samples = (_valid_samples(y_lengths, B, dev, "y_lengths / valid_samples") * 256).clamp(0, n)
+        elif valid_samples is not None:
+            valid_samples = _valid_samples(valid_samples, B, dev, "y_lengths / valid_samples").clamp(0, n)
+        out = torch.empty(B, device=dev, dtype=torch.float32)
+        energies = torch.empty(B, segs, device=dev, dtype=torch.float64) if return_energies else None
+        self._call("mbv_loudness", wave, valid_samples, B, n, rate, out, energies)
+        return (out, energies) if return_energies else out
+
+    @torch.no_grad()
+    def loudness_range(self, wave, rate, in_avail, seg_first, seg_count, state, energies, loudness, valid_samples=None):
+        """Segments [seg_first, seg_first + seg_count) of every row of `wave` (fp32 [B, n] or [B, 1, n], contiguous,
+        device), of which the first `in_avail` samples exist (`mbv_loudness_range`; `wire.stream_pcm16(loudness=)`
+        drives it): `state` fp64 [B, 4] carries the filter between calls (seg_first == 0 starts from zero),
+        `energies` fp64 [B, >= segments] receives the range, `loudness` fp32 [B] the integrated loudness of segments
+        [0, seg_first + seg_count).  Bitwise `loudness` of the finished rows however the segments were cut."""
+        if wave.dim() == 3 and wave.shape[1] == 1:
+            wave = wave[:, 0]
+        dev = self._device()
+        B, n = wave.shape
+        for name, t, dt, shape in (("wave", wave, torch.float32, None), ("state", state, torch.float64, (B, 4)),
+                                   ("energies", energies, torch.float64, None), ("loudness", loudness, torch.float32, (B,)),
+                                   ("valid_samples", valid_samples, torch.int64, (B,))):
+            if t is None and name == "valid_samples":
+                continue
+            if t is None:
+                raise ValueError("loudness_range: %s is missing" % name)
+            if t.device != dev or t.dtype != dt or not t.is_contiguous() or (shape and tuple(t.shape) != shape):
+                raise ValueError("loudness_range: %s must be a contiguous %s tensor on %s%s"
+                                 % (name, dt, dev, " of shape %s" % (shape,) if shape else ""))
+        if energies.dim() != 2 or energies.shape[0] != B:
+            raise ValueError("loudness_range: energies must be [B, segments]")
+        self._call("mbv_loudness_range", wave, valid_samples, B, n, int(rate), int(in_avail), int(seg_first),
+                   int(seg_count), state, energies, energies.shape[1], loudness)
+
+    @torch.no_grad()
+    def loudness_chunks(self, chunks, rate):
+        """`loudness_range` for many rows, each of its own stream, in ONE launch (`mbv_loudness_chunks`; `wire.PcmPool`
+        drives it): `chunks` is a ctypes array (or a list) of `_capi.MbvLoudnessChunk`, device addresses."""
+        if not isinstance(chunks, C.Array):
+            chunks = (_capi.MbvLoudnessChunk * len(chunks))(*chunks)
+        self._call("mbv_loudness_chunks", chunks, len(chunks), int(rate))
+
+    def loudness_runs(self):
+        """Launches of the loudness kernel made on this model's handle so far (`mbv_loudness_runs`)."""
+        return int(_capi.lib().mbv_loudness_runs(self._ensure_handle()))
+
     def input_runs(self):
         """Launches of the live-input resampler made on this model's handle so far (`mbv_input_runs`)."""
         return int(_capi.lib().mbv_input_runs(self._ensure_handle()))

@@ -44,6 +44,12 @@ index, so streamed = pooled = one-shot stays bitwise), the stream's length shrin
 stops with the first chunk that makes that many outputs final (`revoke_plan`).  `service_pcm16(fade=)` is the one-shot
 counterpart.  `mark_samples` maps the token marks of `infer_stream(marks=True)` to wire samples, so that a caller can
 fade at a token boundary (`at="token"`) and learn how many tokens the listener heard begin.
+
+`Loudness` (`loudness=`) delivers at a programme-loudness target instead of by the peak rule: the one-shot
+entries measure the ITU-R BS.1770 integrated loudness of the model-rate waveform on the device (`net.loudness`) and
+choose the static gain from it; the streamed entries take the measured value as an input, as they take `peak=`, and
+keep `.loudness`, the running value of what they have decoded (`mbv_loudness_range`; one `mbv_loudness_chunks` launch
+per tick in a `PcmPool`).  The gain enters the wire kernels as their `peak`, so every bitwise relation above holds.
 """
 import base64
 import ctypes as C
@@ -170,6 +176,142 @@ def _limit_arg(limiter, rate):
     return limiter.resolve(rate)
 
 
+class Loudness:
+    """Delivery at a programme-loudness target: the static gain of the wire step is chosen so that an
+    utterance of integrated loudness L (ITU-R BS.1770, `net.loudness`) leaves at `target` LUFS, instead of as loud as
+    its largest sample allows (the peak rule of tts_vits.py:205-208).
+      target       LUFS; -23.0 is EBU R128's.  None: measure only, the gain stays what `peak=` makes it
+      measured     None: the call measures the waveform itself (one-shot entries only).  A float, an fp32 [B] tensor or
+                   another stream's `.loudness`: the L to aim from, e.g. the speaker's previous utterance; required on
+                   a stream, whose own L does not exist before its last chunk (the convention of `peak=` there)
+      max_gain_db  the gain never exceeds it, so that near-silence is not blown up; at most 39 dB, which keeps the
+                   kernels' divisor 0.9 / g above their 0.01 threshold
+    The gain is g = min(10^((target - L) / 20), 10^(max_gain_db / 20)), 1 where L is -inf, in fp32 on the device; it
+    enters the wire kernels as `peak = 0.9 / g`, which they turn into the factor 0.9 / peak = g.  No kernel changes, so
+    every bitwise relation of the wire path holds with that `peak`.  -23 LUFS and 20 dB are conventions, not
+    measurements.  Without a `limiter` a positive gain can reach the hard clip.  The loudness is that of the model-rate
+    waveform: what a lower wire rate (8 kHz G.711) removes is not accounted for."""
+
+    MAX_GAIN_DB = 39.0
+
+    def __init__(self, target=-23.0, measured=None, max_gain_db=20.0):
+        self.target = None if target is None else float(target)
+        self.max_gain_db = float(max_gain_db)
+        if self.target is not None and not math.isfinite(self.target):
+            raise ValueError("Loudness: target %r must be a finite LUFS value, or None to measure only" % (target,))
+        if not 0.0 <= self.max_gain_db <= self.MAX_GAIN_DB:
+            raise ValueError("Loudness: max_gain_db %r must be in [0, %g] (beyond it 0.9 / g falls below the wire "
+                             "kernels' 0.01 threshold)" % (max_gain_db, self.MAX_GAIN_DB))
+        if measured is not None and not torch.is_tensor(measured):
+            measured = float(measured)
+            if math.isnan(measured) or measured == math.inf:
+                raise ValueError("Loudness: measured %r must be a LUFS value or -inf" % (measured,))
+        self.measured = measured
+
+    def __repr__(self):
+        return "Loudness(target=%r, measured=%r, max_gain_db=%r)" % (self.target, self.measured, self.max_gain_db)
+
+    def gain(self, L):
+        """fp32 tensor of LUFS values -> the fp32 gain of each, on L's device (no read-back)."""
+        if self.target is None:
+            raise ValueError("Loudness(target=None) only measures: it has no gain")
+        L = L.to(torch.float32)
+        g = torch.pow(torch.full_like(L, 10.0), (self.target - L) / 20.0)
+        g = torch.clamp(g, max=10.0 ** (self.max_gain_db / 20.0))
+        return torch.where(torch.isneginf(L), torch.ones_like(g), g)
+
+    def peak(self, L):
+        """The `peak` that gives the wire kernels this gain: 0.9 / gain(L), fp32 on L's device."""
+        return 0.9 / self.gain(L)
+
+    def measured_rows(self, B, dev):
+        """`measured` as an fp32 [B] tensor on `dev` (a float is a fill, not a host copy)."""
+        m = self.measured
+        if not torch.is_tensor(m):
+            return torch.full((B,), m, device=dev, dtype=torch.float32)
+        m = m.to(device=dev, dtype=torch.float32).contiguous()
+        if m.shape != (B,):
+            raise ValueError("Loudness: measured must be a float or an fp32 [%d] tensor, got shape %s" % (B, tuple(m.shape)))
+        return m
+
+
+def _loudness_arg(loudness, peak, who, stream):
+    """`loudness=` of a wire entry -> None or the `Loudness`; refuses `peak=` beside it and, on a stream, a target
+    without `measured`."""
+    if loudness is None:
+        return None
+    if not isinstance(loudness, Loudness):
+        raise TypeError("loudness must be a wire.Loudness or None, got %s" % type(loudness).__name__)
+    if peak is not None:
+        raise ValueError("%s: loudness= replaces the peak rule; give peak= or loudness=, not both" % who)
+    if stream and loudness.target is not None and loudness.measured is None:
+        raise ValueError("%s: a stream's own loudness does not exist before its last chunk: give "
+                         "Loudness(measured=...) (a float, an fp32 tensor, another stream's .loudness), or "
+                         "Loudness(target=None) to measure only" % who)
+    if not stream and loudness.target is None:
+        raise ValueError("%s: Loudness(target=None) only measures; net.loudness is the one-shot measurement" % who)
+    return loudness
+
+
+def _segments_due(done, in_avail, hop):
+    """The segment count after a step that sees `in_avail` samples, `done` segments having been measured."""
+    return max(int(in_avail) // hop, done)
+
+
+def loudness_plan(avail, hop):
+    """The segments a stream measures with each chunk, in pure integers (no tensor, no GPU): `avail` lists the
+    model-rate samples that exist after each chunk (non-decreasing), `hop` the segment length H -> [(k0, k1), ...],
+    chunk i measures segments [k0, k1): those its samples completed.  The ranges tile [0, avail[-1] // hop)."""
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("loudness_plan: hop must be >= 1")
+    out, done = [], 0
+    for a in avail:
+        k1 = _segments_due(done, a, hop)
+        out.append((done, k1))
+        done = k1
+    return out
+
+
+# The measuring half of a wire step of `w`, a `PcmStream` or a `LiveWire` opened with `loudness=` (both then hold
+# loudness, fp32 [B], the running integrated loudness; _lstate, fp64 [B, 4]; _lenergy, fp64 [B, capacity // H]; _lseg,
+# the segments measured so far; _valid_in): the segments that the first `in_avail` samples completed.  Alone it is one
+# `mbv_loudness_range` launch, in a pool one row of the tick's `mbv_loudness_chunks` table.
+def _loudness_open(w, loud, B, capacity, dev):
+    w._loud, w.loudness = loud, None
+    if loud is None:
+        return
+    w._lhop, segs = _capi.loudness_segments(w.model_sr, capacity)
+    with torch.cuda.device(dev):
+        w.loudness = torch.full((B,), -math.inf, device=dev, dtype=torch.float32)
+        w._lstate = torch.zeros(B, 4, device=dev, dtype=torch.float64)
+        w._lenergy = torch.zeros(B, max(segs, 1), device=dev, dtype=torch.float64)
+    w._lseg = 0
+
+
+def _loudness_alone(w, wave, in_avail):
+    if w.loudness is None:
+        return
+    k1 = _segments_due(w._lseg, in_avail, w._lhop)
+    if k1 > w._lseg:
+        w._net.loudness_range(wave, w.model_sr, in_avail, w._lseg, k1 - w._lseg, w._lstate, w._lenergy, w.loudness,
+                              valid_samples=w._valid_in)
+        w._lseg = k1
+
+
+def _loudness_row(w, k, wave_ptr, in_total, in_avail):
+    """Fills the `_capi.MbvLoudnessChunk` `k` with the segments due now; -> the new segment count, or None."""
+    k1 = _segments_due(w._lseg, in_avail, w._lhop)
+    if k1 <= w._lseg:
+        return None
+    k.wave, k.in_total, k.in_avail = wave_ptr, in_total, in_avail
+    k.valid_samples = w._valid_in.data_ptr() if w._valid_in is not None else None
+    k.seg_first, k.seg_count = w._lseg, k1 - w._lseg
+    k.state, k.energies, k.energy_capacity = w._lstate.data_ptr(), w._lenergy.data_ptr(), w._lenergy.shape[1]
+    k.loudness = w.loudness.data_ptr()
+    return k1
+
+
 def _fade_arg(fade):
     """`fade=` of a one-shot wire entry -> None or (first, count), both >= 0."""
     if fade is None:
@@ -258,7 +400,7 @@ def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type
 
 
 def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best", limiter=None,
-                  peak=None, encoding="pcm16", fade=None):
+                  peak=None, encoding="pcm16", fade=None, loudness=None):
     """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
     `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
       o          fp32 [B, 1, n] waveforms of `net.infer` (device)
@@ -277,9 +419,28 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
       fade     (first, count) in output samples: the fade-out of a revoked stream on the finished waveform (DESIGN
                §7.16): sample t >= first is scaled by (count - (t - first)) / (count + 1) before the clip, silence from
                first + count on, and valid_samples becomes min(valid_samples, first + count).  The bytes are those a
-               stream revoked with that fade emitted.  Through the ranged kernel, as `limiter` and `encoding` go"""
+               stream revoked with that fade emitted.  Through the ranged kernel, as `limiter` and `encoding` go
+      loudness a `Loudness`: deliver at its target LUFS instead of by the peak rule.  With
+               `measured=None` the call first measures the model-rate waveform (`net.loudness`, one launch more), then
+               wires with the static gain that takes it to the target: the bytes are those of
+               `service_pcm16(..., peak=loudness.peak(L))` on the limited path.  `auto_normalize` is ignored then (not
+               refused: it is the default), `peak=` beside it is a ValueError.  Combines with `limiter`, `encoding`
+               and `fade`; without a limiter a positive gain can reach the hard clip"""
     law = _law_code(encoding)
     fade = _fade_arg(fade)
+    loud = _loudness_arg(loudness, peak, "service_pcm16", stream=False)
+    if loud is not None:
+        _limit_arg(limiter, rate)                               # refuses bad parameters before the measuring launch
+        dev = net._device()
+        if o.dim() != 3 or o.shape[1] != 1:
+            raise ValueError("wave must be [B, 1, samples]")
+        if loud.measured is None:
+            L = net.loudness(o, model_sr, y_lengths=y_lengths)
+        else:
+            L = loud.measured_rows(o.shape[0], dev)
+        with torch.cuda.device(dev):
+            peak = loud.peak(L)
+        return _service_limited(net, o, y_lengths, model_sr, rate, False, res_type, limiter, peak, encoding, fade=fade)
     if fade is not None:
         if limiter is None and peak is not None:
             raise ValueError("service_pcm16: peak= is the static gain of the limited path; without limiter= the "
@@ -299,7 +460,7 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
                   auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None, encoding="pcm16",
-                  in_encoding=None, fade=None):
+                  in_encoding=None, fade=None, loudness=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -307,7 +468,8 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
       3. `net.spectrogram` with n_fft = 2 (spec_channels - 1), the posterior encoder's input width;
       4. `net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)` (`seed` as `infer` takes it: None =
          torch's generator, as before);
-      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter`, `encoding` and `fade` as it takes them.
+      5. `service_pcm16(net, o, y_lengths, model_sr, rate, ...)`, with `limiter`, `encoding`, `fade` and `loudness` as
+         it takes them (the loudness measured is that of the converted waveform).
     `in_encoding` "ulaw" / "alaw": `wave` is uint8 G.711 at `in_sr` != `model_sr`; it is expanded by `net.g711_decode`
     and goes on as int16.
     -> (pcm int16 [B, n'], valid_samples int64 [B]) as `service_pcm16` returns them.  Raises ValueError before
@@ -317,6 +479,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
     _law_code(encoding)
     _fade_arg(fade)
+    _loudness_arg(loudness, None, "convert_pcm16", stream=False)
     in_law = _in_law(in_encoding, in_sr, model_sr, "convert_pcm16")
     if (wave.dtype == torch.uint8) != (in_law is not None):
         raise TypeError("convert_pcm16: uint8 samples need in_encoding='ulaw' | 'alaw', and in_encoding takes uint8 "
@@ -337,7 +500,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     spec, spec_lengths = net.spectrogram(wave, n_fft, hop_size, win_size, valid_samples=valid)
     o = net.voice_conversion(spec, spec_lengths, sid_src, sid_tgt, seed=seed)[0]
     return service_pcm16(net, o, spec_lengths, model_sr, rate, auto_normalize=auto_normalize, res_type=res_type,
-                         limiter=limiter, encoding=encoding, fade=fade)
+                         limiter=limiter, encoding=encoding, fade=fade, loudness=loudness)
 
 
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
@@ -440,6 +603,10 @@ class PcmStream:
       valid_samples  int64 [B] device, the lengths `service_pcm16` returns (written by the first chunk)
       peak           fp32 [B] device, the running peak of the resampled samples emitted so far; after the last
                      chunk bitwise the peak `service_pcm16(auto_normalize=True)` would have divided by
+      loudness       (streams opened with `loudness=`; else None) fp32 [B] device, the running BS.1770 integrated
+                     loudness of the decoded model-rate samples so far, updated by the step that wires a chunk over the
+                     100 ms segments that chunk completed (one `mbv_loudness_range` launch, none when it completed
+                     none); after the last chunk bitwise `net.loudness(st.o, model_sr, y_lengths)`
 
     All state lives in tensors the stream owns, so paused and interleaved streams on one model do not mix.
 
@@ -450,8 +617,10 @@ class PcmStream:
     (`mark_samples`, the limiter's lag included).  `revoke()` takes the stream back with a fade-out; `finished` and
     `revoked` say where it stands."""
 
-    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16"):
+    def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16",
+                 loudness=None):
         _refuse_live(st)
+        loud = _loudness_arg(loudness, peak, "stream_pcm16", stream=True)
         self.encoding, dtype = encoding, _wire_dtype(encoding)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
@@ -471,6 +640,10 @@ class PcmStream:
         if st.y_lengths is not None:
             self._valid_in = (st.y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
         self._peak_in = _peak_arg(peak, B, dev)
+        _loudness_open(self, loud, B, n, dev)     # .loudness: the running integrated loudness, or None
+        if loud is not None and loud.target is not None:
+            with torch.cuda.device(dev):
+                self._peak_in = loud.peak(loud.measured_rows(B, dev)).contiguous()
         self._done = 0                            # outputs emitted so far
         self._wired = 0                           # the first chunk whose final outputs are not emitted yet
         self._fade = None                         # (first, count) once revoked with a fade inside the stream
@@ -571,7 +744,9 @@ class PcmStream:
             a, b = (self._ready[i - 1] if i else 0), self._ready[i]
             return a, self.pcm[:, a:b]
         a, b = self._done, self._ready[i]
-        _wire_alone(self, *self._step_through(i))
+        step = self._step_through(i)
+        _wire_alone(self, *step)
+        _loudness_alone(self, step[0], step[1])
         self._done, self._wired = b, i + 1
         self._clamp_valid()
         return a, self.pcm[:, a:b]
@@ -603,7 +778,8 @@ class PcmStream:
         return self.pcm, self.valid_samples
 
 
-def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16"):
+def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16",
+                 loudness=None):
     """The streamed `service_pcm16`: wraps a `stream.DecodeStream` (`net.dec_stream` / `net.infer_stream`, not yet
     iterated) in a `PcmStream`.
       peak  None: no normalisation (auto_normalize=False, exact).  A float or an fp32 [B] tensor: every sample is
@@ -617,10 +793,15 @@ def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", lim
             well, and the bytes are those of `service_pcm16(..., limiter=limiter, peak=peak)` on the finished
             waveform.  Where nothing exceeds the ceiling they are the bytes without a limiter.
       encoding  "pcm16", or "ulaw" / "alaw": the pieces are uint8 G.711 bytes, those of
-            `service_pcm16(..., encoding=encoding)` on the finished waveform."""
+            `service_pcm16(..., encoding=encoding)` on the finished waveform.
+      loudness  None, or a `Loudness`: the static gain comes from its `measured` LUFS (required with a
+            target, as `peak` is an input here; `peak=` beside it is a ValueError) and the stream keeps `.loudness`,
+            the running integrated loudness of what it has decoded, e.g. the `measured` of the speaker's next
+            utterance.  `Loudness(target=None)` measures only: the bytes are those without `loudness=`."""
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
-    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter, encoding=encoding)
+    return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter, encoding=encoding,
+                     loudness=loudness)
 
 
 def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
@@ -792,6 +973,9 @@ class LiveWire:
       valid_samples  int64 [1] device, written with the last piece
       peak           fp32 [1] device, the running peak of the resampled output so far; the `peak=` and the `limiter=`
                      given when the stream was opened are inputs, as for `stream_pcm16`
+      loudness       (opened with `loudness=`; else None) fp32 [1] device, the running integrated loudness of the
+                     converted model-rate samples decoded so far, as on a `PcmStream`; after the last piece bitwise
+                     `net.loudness` of the finished `live.o` over its 256 * frames samples
     With `in_sr == model_sr` the samples go to `LiveStream.push` as they are (int16 stays int16) and no input kernel
     runs.  `encoding` "ulaw" / "alaw": `pcm` is uint8 G.711 bytes (unwritten samples hold the code of zero).
     `in_encoding` "ulaw" / "alaw" with `dtype=torch.uint8`: `push` takes the caller's G.711 bytes, which the input
@@ -801,9 +985,10 @@ class LiveWire:
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                  chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                 encoding="pcm16", in_encoding=None):
+                 encoding="pcm16", in_encoding=None, loudness=None):
         from .stream import LiveStream
         _filter_code(res_type)
+        loud = _loudness_arg(loudness, peak, "convert_live_pcm16", stream=True)
         self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
         self.encoding, out_law = encoding, _law_code(encoding)
         self.in_encoding = _in_law(in_encoding, in_sr, model_sr, "convert_live_pcm16")
@@ -846,6 +1031,9 @@ class LiveWire:
             # valid input samples of the wire step: the capacity of o while the total is unknown
             self._valid_in = torch.full((1,), self._plan.o_capacity, device=dev, dtype=torch.int64)
             self._peak_in = _peak_arg(peak, 1, dev, shape="1")
+            if loud is not None and loud.target is not None:
+                self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
+        _loudness_open(self, loud, 1, self._plan.o_capacity, dev)     # .loudness, as on a `PcmStream`
         self._fade = None             # (a live wire is not revoked: the caller stops pushing and drops it)
         self._pieces = []             # (a, b) of every piece wired so far, in order
         self._handed = 0              # the piece poll() hands out next
@@ -943,6 +1131,7 @@ class LiveWire:
         w = self._wire_due()
         if w is not None:
             _wire_alone(self, *w[0])
+            _loudness_alone(self, w[0][0], w[0][1])
             self._chunk_wired(*w[1:])
 
     def poll(self):
@@ -959,7 +1148,7 @@ class LiveWire:
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                        chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                       encoding="pcm16", in_encoding=None):
+                       encoding="pcm16", in_encoding=None, loudness=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32; G.711 bytes with `dtype=torch.uint8,
     in_encoding="ulaw" | "alaw"`, which needs `in_sr != model_sr`) while the recording arrives, int16 out at `rate`
     (G.711 bytes with `encoding="ulaw" | "alaw"`); -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
@@ -967,11 +1156,12 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
     `stream_pcm16` takes them: the level of a live recording is whatever the microphone delivers, so there is no
     earlier utterance to take a peak from, and the limiter is the level control.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
     `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
-    (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead."""
+    (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead.  `loudness` as
+    `stream_pcm16` takes it: `measured` is required with a target, and the wire keeps `.loudness`."""
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
                     max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter,
-                    encoding=encoding, in_encoding=in_encoding)
+                    encoding=encoding, in_encoding=in_encoding, loudness=loudness)
 
 
 class PcmPool:
@@ -986,7 +1176,10 @@ class PcmPool:
     own) share one launch of the limited kernel and the others one of the unlimited: two launches in a mixed tick.
     One `encoding` per pool, like `rate` and `res_type`: with "ulaw" / "alaw" the followers' `pcm`, the packed buffer
     and the pinned host buffer are uint8 (`mbv_resample_g711_chunks`), at the same launch counts.
-    `revoke(st)` takes a member back: its fade rides in the tick's launch and it leaves when the fade is out."""
+    `revoke(st)` takes a member back: its fade rides in the tick's launch and it leaves when the fade is out.
+    Members added with `loudness=` keep their running `.loudness`: ONE `mbv_loudness_chunks` launch per tick measures
+    the segments completed on all of them; a tick in which none completed one, and a pool without such members,
+    launches nothing for it."""
 
     def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
         _filter_code(res_type)
@@ -1010,20 +1203,21 @@ class PcmPool:
                 return f
         return None
 
-    def add(self, st, peak=None, limiter=None):
+    def add(self, st, peak=None, limiter=None, loudness=None):
         _refuse_live(st)
         _limit_arg(limiter, self.rate)            # refuses bad parameters before the stream joins the pool
+        _loudness_arg(loudness, peak, "PcmPool.add", stream=True)
         self.pool.add(st)                         # (refuses B > 1, another model, another device)
         f = self.follower(st)
         if f is None:
             f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter,
-                          encoding=self.encoding)
+                          encoding=self.encoding, loudness=loudness)
             self.followers.append(f)
         return f
 
-    def admit(self, requests, peak=None, limiter=None):
+    def admit(self, requests, peak=None, limiter=None, loudness=None):
         """`StreamPool.admit(requests)` + a follower for each new stream (`peak`: None, one value for all, or one per
-        request, as `add` takes it; `limiter` likewise); -> the followers, in order.  `requests` is all `models.Request` or all
+        request, as `add` takes it; `limiter` and `loudness` likewise); -> the followers, in order.  `requests` is all `models.Request` or all
         `models.ConvertRequest` (audio), as `StreamPool.admit` takes them.  All or nothing, like `StreamPool.admit`."""
         reqs = list(requests)
         peaks = list(peak) if isinstance(peak, (list, tuple)) else [peak] * len(reqs)
@@ -1034,7 +1228,13 @@ class PcmPool:
             raise ValueError("admit: one limiter per request expected (%d), got %d" % (len(reqs), len(limiters)))
         for lim in limiters:
             _limit_arg(lim, self.rate)
-        return [self.add(st, peak=p, limiter=lim) for st, p, lim in zip(self.pool.admit(reqs), peaks, limiters)]
+        louds = list(loudness) if isinstance(loudness, (list, tuple)) else [loudness] * len(reqs)
+        if len(louds) != len(reqs):
+            raise ValueError("admit: one loudness per request expected (%d), got %d" % (len(reqs), len(louds)))
+        for p, loud in zip(peaks, louds):
+            _loudness_arg(loud, p, "PcmPool.admit", stream=True)
+        return [self.add(st, peak=p, limiter=lim, loudness=loud)
+                for st, p, lim, loud in zip(self.pool.admit(reqs), peaks, limiters, louds)]
 
     def revoke(self, st, fade_ms=5.0, at="now"):
         """`PcmStream.revoke` for a member added with `add` or `admit` (a text request or a converted recording; `st`
@@ -1055,14 +1255,17 @@ class PcmPool:
                 self.pool.remove(f._st)
         return report
 
-    def add_live(self, lw, limiter=None):
+    def add_live(self, lw, limiter=None, loudness=None):
         """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
         feeds, steps and wires it along with the others; -> `lw`.  The wire keeps the limiter it was opened with;
-        `limiter`, when given, must be that one (the lag is part of the pieces it has planned)."""
+        `limiter`, when given, must be that one (the lag is part of the pieces it has planned); `loudness` likewise
+        (its state is the wire's)."""
         if not isinstance(lw, LiveWire):
             raise TypeError("add_live takes a wire.LiveWire (wire.convert_live_pcm16)")
         if limiter is not None and limiter != lw.limiter:
             raise ValueError("add_live: the live wire was opened with %r, not %r" % (lw.limiter, limiter))
+        if loudness is not None and loudness is not lw._loud:
+            raise ValueError("add_live: the live wire was opened with %r, not %r" % (lw._loud, loudness))
         if (lw.model_sr, lw.rate) != (self.model_sr, self.rate):
             raise ValueError("the live wire runs %d -> %d Hz, the pool %d -> %d Hz"
                              % (lw.model_sr, lw.rate, self.model_sr, self.rate))
@@ -1142,6 +1345,17 @@ class PcmPool:
             net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
                                       limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
                                       fades=[w._fade for _, w, _, _ in rows])
+            # the measuring members of the tick: the segments their frontier completed, in ONE launch
+            measuring = []
+            for _, w, k, _ in rows:
+                lk = _capi.MbvLoudnessChunk()
+                k1 = _loudness_row(w, lk, k.wave, k.in_total, k.in_avail) if w.loudness is not None else None
+                if k1 is not None:
+                    measuring.append((w, lk, k1))
+            if measuring:
+                net.loudness_chunks([lk for _, lk, _ in measuring], self.model_sr)
+                for w, _, k1 in measuring:
+                    w._lseg = k1
             for _, w, _, due in rows:
                 w._chunk_wired(*due)
             if host:
@@ -1163,7 +1377,8 @@ class PcmPool:
 
 def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
     """The pooled `stream_pcm16`: a `PcmPool` over a `stream.StreamPool` (`net.stream_pool()`) of the same model.
-    `add(st, peak=None, limiter=None)` takes `peak` and `limiter` as `stream_pcm16` does; `encoding` is the pool's."""
+    `add(st, peak=None, limiter=None, loudness=None)` takes `peak`, `limiter` and `loudness` as `stream_pcm16` does;
+    `encoding` is the pool's."""
     return PcmPool(net, pool, model_sr, rate, res_type=res_type, encoding=encoding)
 
 

@@ -760,6 +760,57 @@ int mbv_resample_g711_chunks_faded(mbv_model *m, const mbv_pcm_chunk *chunks_hos
                                    const mbv_pcm_fade *fades_host, int n, int orig_sr, int target_sr, int filter,
                                    int law, uint8_t *packed, int64_t packed_capacity, void *stream);
 
+/* ---- turns on the wire: several utterances as ONE gapless wire stream (no reference counterpart: the reference
+ * synthesises every unit of a turn alone and butt-joins their int16, tts_vits.py) ---------------------------------
+ * The input of a turn row is a TIMELINE at the model's rate, never materialised: segment s, the waveform of one
+ * utterance of `length` valid samples, sits at `start`; segments are ascending and disjoint, and what lies between
+ * them is silence (0.f).  Each segment is multiplied at its two ends by a de-click ramp of `ramp` samples, in fp32
+ * with one rounding, i the index inside the segment:
+ *   i < ramp:             wave[i] * ((float)(i + 1) * inv)
+ *   i >= length - ramp:   wave[i] * ((float)(ramp - (i - (length - ramp))) * inv)
+ * with inv the value mbv_pcm_fade_make gives for count = ramp (the fade's ramp, mirrored for the rise), and is not
+ * touched anywhere else; ramp <= length / 2, so the two never overlap, ramp = 0 is none.  The wire step over that
+ * timeline is the one of the chunk entries: every stored int16 / G.711 byte, running peak and out_samples is BITWISE
+ * what mbv_resample_pcm16_chunks_faded / mbv_resample_g711_chunks_faded store for a chunk whose `wave` is the
+ * timeline written out as one fp32 row (the same device code behind the staging of the input window).
+ *
+ * mbv_turn_chunk: `chunk` as in those entries with chunk.wave NULL; in_total is the timeline's total (or, while the
+ * turn is open, a capacity that stands in for it: an open row's final outputs do not depend on it) and in_avail its
+ * frontier: every timeline sample below it exists (decoded, or silence), and nothing at or past it is read.  segs is
+ * HOST memory [n_segs]: the segments that intersect the input window of the chunk's outputs (more may be given).
+ *
+ * mbv_turn_plan (host only: no handle, no GPU; reads the integer fields only): the checks of mbv_pcm_chunks_plan on
+ * every `chunk` — with limits (HOST [n] or NULL, ceiling == 0 = not limited) the range must end at or below
+ * min(mbv_limiter_ready(.., in_avail, in_total, lookahead), pcm_capacity), the open branch being
+ * mbv_resample_ready_open(in_avail) — and on its segments: start >= 0, length > 0, 0 <= ramp <= length / 2, ascending
+ * and disjoint, at most MBV_TURN_MAX_SEGS segments in one call.  Fills packed_first (or NULL) and returns the packed
+ * total as mbv_pcm_chunks_plan does, or -1 with a message that names the turn ("turn i: ...").
+ *
+ * mbv_resample_turns: turns_host, limits_host (or NULL), fades_host (or NULL) are HOST [n] and travel as kernel
+ * arguments like the chunk tables, the segments in one table for the call; nothing is synchronised and the arrays may
+ * be freed on return.  law 0 stores int16, MBV_G711_ULAW / MBV_G711_ALAW bytes (pcm, pcm_capacity, packed and
+ * packed_capacity then count bytes).  ONE launch for the unlimited turns of a call and one for the limited ones
+ * (mbv_wire_runs).  Refused before anything is launched, the handle stays usable: whatever the plan refuses, a
+ * non-NULL chunk.wave, a missing pcm or segment wave, a law other than those three, a bad fade, a packed_capacity
+ * below the total, two turns that write overlapping ranges of one pcm, and a limited turn whose halo window does not
+ * fit the LDS stage. */
+#define MBV_TURN_MAX_SEGS 4096
+typedef struct mbv_turn_seg {
+  const float *wave;           /* DEVICE, the utterance's wave row */
+  int64_t start, length;       /* its place on the timeline and its valid samples */
+  int32_t ramp;                /* de-click samples at either end */
+} mbv_turn_seg;
+typedef struct mbv_turn_chunk {
+  mbv_pcm_chunk chunk;         /* chunk.wave NULL */
+  const mbv_turn_seg *segs;    /* HOST [n_segs] */
+  int32_t n_segs;
+} mbv_turn_chunk;
+int64_t mbv_turn_plan(int orig_sr, int target_sr, int filter, const mbv_turn_chunk *turns,
+                      const mbv_pcm_limit *limits, int n, int64_t *packed_first);
+int mbv_resample_turns(mbv_model *m, const mbv_turn_chunk *turns_host, const mbv_pcm_limit *limits_host,
+                       const mbv_pcm_fade *fades_host, int n, int orig_sr, int target_sr, int filter, int law,
+                       void *packed, int64_t packed_capacity, void *stream);
+
 /* ---- token marks: where every token starts, in z-frames ------------------------
  * The exclusive prefix sums of the per-token durations the length regulator uses (predicted, or given with
  * mbv_set_durations / mbv_enc_row.durations): marks[0] = 0, marks[j] = d_0 + .. + d_{j-1}; entry t_text is the sum, and

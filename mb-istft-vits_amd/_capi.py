@@ -43,6 +43,7 @@ SYMBOLS = [
     "mbv_token_marks", "mbv_token_marks_rows",
     "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
     "mbv_loudness_runs",
+    "mbv_turn_plan", "mbv_resample_turns",
 ]
 
 
@@ -100,6 +101,19 @@ def pcm_fade(first, count):
 
 
 NO_FADE = (0, -1, 0.0)          # the fields of a table row that does not fade
+
+
+class MbvTurnSeg(C.Structure):
+    """mbv_turn_seg of include/mbistft_vits.h (mbv_resample_turns): one utterance on a turn's timeline."""
+    _fields_ = [("wave", C.c_void_p), ("start", C.c_int64), ("length", C.c_int64), ("ramp", C.c_int32)]
+
+
+class MbvTurnChunk(C.Structure):
+    """mbv_turn_chunk of include/mbistft_vits.h (mbv_resample_turns); chunk.wave stays None."""
+    _fields_ = [("chunk", MbvPcmChunk), ("segs", C.POINTER(MbvTurnSeg)), ("n_segs", C.c_int32)]
+
+
+TURN_MAX_SEGS = 4096            # MBV_TURN_MAX_SEGS
 
 
 class MbvMarkRow(C.Structure):
@@ -306,8 +320,8 @@ def lib():
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two and loudness's six may be absent there, and calling one
-    # then raises AttributeError.
+    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six and the
+    # turns' two may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -326,7 +340,7 @@ def lib():
                 "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
                 "mbv_token_marks", "mbv_token_marks_rows",
                 "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
-                "mbv_loudness_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_loudness_runs", "mbv_turn_plan", "mbv_resample_turns") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -420,6 +434,11 @@ def lib():
         L.mbv_loudness_chunks.argtypes = [vp, C.POINTER(MbvLoudnessChunk), i32, i32, vp]
         L.mbv_loudness_runs.argtypes = [vp]
         L.mbv_loudness_runs.restype = C.c_int64
+    if hasattr(L, "mbv_resample_turns") or not optional:
+        L.mbv_turn_plan.argtypes = [i32, i32, i32, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit), i32, i64p]
+        L.mbv_turn_plan.restype = C.c_int64
+        L.mbv_resample_turns.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit), C.POINTER(MbvPcmFade), i32,
+                                         i32, i32, i32, i32, vp, C.c_int64, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

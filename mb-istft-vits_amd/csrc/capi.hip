@@ -3478,27 +3478,31 @@ int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_ava
   return wire_ready(rp, in_avail, in_total, lookahead);
 }
 
+}  // extern "C"
+
 namespace {
 // The checks mbv_resample_pcm16_range makes on its row, for every chunk of a pooled call (integer fields only).
 // Fills packed_first (may be null) with the running sum of the out_count and returns the packed total, or -1 with
 // *err naming the offending chunk.
-int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const RatePair& rp, int64_t* packed_first,
-                         std::string* err, const mbv_pcm_limit* limits = nullptr) {
+// `at(i)` is row i's mbv_pcm_chunk and `noun` what the messages call a row ("chunk", or "turn": mbv_turn_plan).
+template <typename At>
+int64_t pcm_rows_check(const char* who, const char* noun, At at, int n, const RatePair& rp, int64_t* packed_first,
+                       std::string* err, const mbv_pcm_limit* limits) {
   char buf[512];
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
-    const mbv_pcm_chunk& k = chunks[i];
+    const mbv_pcm_chunk& k = at(i);
     const char* why = nullptr;
     if (k.in_total <= 0 || k.pcm_capacity <= 0) why = "in_total and pcm_capacity must be > 0";
     else if (k.in_avail < 0 || k.out_first < 0 || k.out_count < 0) why = "in_avail, out_first and out_count must be >= 0";
     else if ((double)k.pcm_capacity * rp.M >= 0x1p62) why = "pcm_capacity * M overflows the 64-bit time index";
     if (why) {
-      snprintf(buf, sizeof buf, "%s: chunk %d: %s", who, i, why);
+      snprintf(buf, sizeof buf, "%s: %s %d: %s", who, noun, i, why);
       *err = buf;
       return -1;
     }
     if (k.out_first > k.pcm_capacity || k.out_count > k.pcm_capacity - k.out_first) {
-      snprintf(buf, sizeof buf, "%s: chunk %d: outputs [%lld, %lld) lie outside the row of pcm_capacity %lld", who, i,
+      snprintf(buf, sizeof buf, "%s: %s %d: outputs [%lld, %lld) lie outside the row of pcm_capacity %lld", who, noun, i,
                (long long)k.out_first, (long long)(k.out_first + k.out_count), (long long)k.pcm_capacity);
       *err = buf;
       return -1;
@@ -3506,14 +3510,14 @@ int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, co
     const bool limited = limits && limits[i].ceiling != 0.f;
     if (limited)
       if (const char* bad = limit_refusal(rp, limits[i])) {
-        snprintf(buf, sizeof buf, "%s: chunk %d: %s", who, i, bad);
+        snprintf(buf, sizeof buf, "%s: %s %d: %s", who, noun, i, bad);
         *err = buf;
         return -1;
       }
     const int64_t ready = wire_ready(rp, k.in_avail, k.in_total, limited ? limits[i].lookahead : 0);
     if (k.out_first + k.out_count > ready) {
-      snprintf(buf, sizeof buf, "%s: chunk %d: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final",
-               who, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.in_total, (long long)ready);
+      snprintf(buf, sizeof buf, "%s: %s %d: outputs up to %lld asked for, but %lld input samples of %lld make only %lld final",
+               who, noun, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.in_total, (long long)ready);
       *err = buf;
       return -1;
     }
@@ -3522,7 +3526,15 @@ int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, co
   }
   return total;
 }
+
+int64_t pcm_chunks_check(const char* who, const mbv_pcm_chunk* chunks, int n, const RatePair& rp, int64_t* packed_first,
+                         std::string* err, const mbv_pcm_limit* limits = nullptr) {
+  return pcm_rows_check(who, "chunk", [&](int i) -> const mbv_pcm_chunk& { return chunks[i]; }, n, rp, packed_first, err,
+                        limits);
+}
 }  // namespace
+
+extern "C" {
 
 int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pcm_chunk* chunks, int n,
                             int64_t* packed_first) {
@@ -3539,11 +3551,120 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
 }  // extern "C"
 
 namespace {
+// The body the pooled wire entries share (mbv_resample_pcm16_chunks and its forms, mbv_resample_turns), behind their own
+// checks: `at(i)` is row i's mbv_pcm_chunk, `noun` what the messages call a row, `off` / `total` what the plan returned.
+// The rows without a limiter go through the unlimited kernel and the limited ones through theirs: one row table and
+// one launch per kind, and a kind with a fading row gets a fade table beside its rows, read by the same launch.  `side`
+// is what an entry has beside its rows: nothing (ChunkSide), or a turn's tables (TurnSide): `head_bytes` in front of
+// everything, written by head(); `row_bytes` per row beside each kind's rows, written by rows(kind, ..); and the two
+// launches, which get the row table, the side rows, the head and the fade table (or null) of their slice.
+template <typename At, typename Side>
+int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mbv_pcm_limit* limits,
+                const mbv_pcm_fade* fades, int n, const RatePair& rp, const std::vector<int64_t>& off, int64_t total,
+                int law, void* packed, int64_t packed_capacity, void* stream, const Side& side) {
+  if (packed && packed_capacity < total)
+    return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
+  const uintptr_t sample_bytes = law == kLawNone ? sizeof(int16_t) : 1;
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)at(i).pcm + sample_bytes * (uintptr_t)at(i).out_first; },
+                                    [&](int i) { return sample_bytes * (uintptr_t)at(i).out_count; });
+  if (clash.first >= 0)
+    return m->fail("%s: %ss %d and %d write overlapping ranges of one pcm", who, noun, clash.first, clash.second);
+  // rows with something to write (an empty range still carries out_samples), by kind
+  std::vector<int> live, live_lim;
+  int64_t lds_floats = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!(at(i).out_count > 0 || at(i).out_samples)) continue;
+    if (limits && limits[i].ceiling != 0.f) {
+      live_lim.push_back(i);
+      lds_floats = std::max(lds_floats, limiter_lds_floats(rp.g, rp.fir, LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold}));
+    } else {
+      live.push_back(i);
+    }
+  }
+  if (live.empty() && live_lim.empty()) return 0;
+  auto fading = [&](const std::vector<int>& kind) {
+    if (fades)
+      for (int i : kind)
+        if (fades[i].count >= 0) return true;
+    return false;
+  };
+  // the scratch: the head, then per kind its rows, its side rows and (with a fading row) its fades
+  size_t end = 0;
+  auto take = [&](size_t bytes) { const size_t a = end; end = align_up(end + bytes, 256); return a; };
+  const size_t head_at = take(side.head_bytes);
+  struct Kind { size_t rows, side, fades; bool fade; };
+  auto kind_of = [&](const std::vector<int>& k, size_t row_bytes) {
+    Kind t{take(k.size() * row_bytes), take(k.size() * side.row_bytes), 0, fading(k)};
+    if (t.fade) t.fades = take(k.size() * sizeof(PcmFade));
+    return t;
+  };
+  const Kind ku = kind_of(live, sizeof(PcmPoolRow)), kl = kind_of(live_lim, sizeof(PcmLimRow));
+  if (ensure(m, &m->scrB, &m->scrB_bytes, end)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  const char* head = m->scrB + head_at;
+  side.head(m->scrB + head_at, s);
+  // the side rows and the fade table of a kind, in the order of its row table; the fades null for a kind without one
+  auto beside = [&](const std::vector<int>& kind, const Kind& k) -> const PcmFade* {
+    side.rows(kind, m->scrB + k.side, s);
+    if (!k.fade) return nullptr;
+    PcmFade* t = reinterpret_cast<PcmFade*>(m->scrB + k.fades);
+    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return fade_of(&fades[kind[i]]); });
+    return t;
+  };
+  auto row_of = [&](int i) {
+    const mbv_pcm_chunk& k = at(i);
+    return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
+                      reinterpret_cast<short*>(k.pcm), k.pcm_capacity, reinterpret_cast<unsigned*>(k.running_peak),
+                      k.out_samples, packed ? off[i] : (int64_t)-1};
+  };
+  auto count_of = [&](int i) { return at(i).out_count; };
+  if (!live.empty()) {
+    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB + ku.rows);
+    upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
+    const PcmFade* ft = beside(live, ku);
+    grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
+      ++m->wire_runs;
+      side.launch(rows + f, m->scrB + ku.side + f * side.row_bytes, head, ft ? ft + f : nullptr, nn, max_count, rp,
+                  packed, law, s);
+      return 0;
+    });
+  }
+  if (!live_lim.empty()) {
+    PcmLimRow* rows = reinterpret_cast<PcmLimRow*>(m->scrB + kl.rows);
+    upload_rows<kPcmPoolChunk>(live_lim.size(), rows, s, [&](size_t i) {
+      const mbv_pcm_limit& l = limits[live_lim[i]];
+      return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
+    });
+    const PcmFade* ft = beside(live_lim, kl);
+    grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
+      ++m->wire_runs;
+      side.launch_limited(rows + f, m->scrB + kl.side + f * side.row_bytes, head, ft ? ft + f : nullptr, nn, max_count,
+                          rp, lds_floats, packed, law, s);
+      return 0;
+    });
+  }
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+// the chunk entries have nothing beside their rows
+struct ChunkSide {
+  size_t head_bytes = 0, row_bytes = 0;
+  void head(char*, hipStream_t) const {}
+  void rows(const std::vector<int>&, char*, hipStream_t) const {}
+  void launch(const PcmPoolRow* rows, const char*, const char*, const PcmFade* ft, int n, int64_t max_count,
+              const RatePair& rp, void* packed, int law, hipStream_t s) const {
+    launch_resample_pcm16_pool(rows, ft, n, max_count, rp.bank, rp.g, packed, law, s);
+  }
+  void launch_limited(const PcmLimRow* rows, const char*, const char*, const PcmFade* ft, int n, int64_t max_count,
+                      const RatePair& rp, int64_t lds_floats, void* packed, int law, hipStream_t s) const {
+    launch_resample_pcm16_pool_limited(rows, ft, n, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
+  }
+};
+
 // mbv_resample_pcm16_chunks, its limited form and mbv_resample_g711_chunks: one body, limits null = no row limited,
-// law kLawNone = int16 (else every pcm and packed hold bytes; the entry has checked law).  The rows without a
-// limiter go through the unlimited kernel and the limited ones through theirs: one table and one launch per kind.
-// fades null (or every count < 0) = no row fades; else a kind with a fading row gets a second table beside its rows,
-// read by the same launch
+// law kLawNone = int16 (else every pcm and packed hold bytes; the entry has checked law), fades null (or every
+// count < 0) = no row fades
 int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits, int n,
                  int orig_sr, int target_sr, int filter, void* packed, int64_t packed_capacity, int law, void* stream,
                  const mbv_pcm_fade* fades = nullptr) {
@@ -3561,78 +3682,8 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
   std::vector<int64_t> off(n > 0 ? n : 1);
   const int64_t total = pcm_chunks_check(who, chunks_host, n, rp, off.data(), &err, limits);
   if (total < 0) return m->fail("%s", err.c_str());
-  if (packed && packed_capacity < total)
-    return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
-  const uintptr_t sample_bytes = law == kLawNone ? sizeof(int16_t) : 1;
-  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)chunks_host[i].pcm + sample_bytes * (uintptr_t)chunks_host[i].out_first; },
-                                    [&](int i) { return sample_bytes * (uintptr_t)chunks_host[i].out_count; });
-  if (clash.first >= 0)
-    return m->fail("%s: chunks %d and %d write overlapping ranges of one pcm", who, clash.first, clash.second);
-  // rows with something to write (an empty range still carries out_samples), by kind
-  std::vector<int> live, live_lim;
-  int64_t lds_floats = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!(chunks_host[i].out_count > 0 || chunks_host[i].out_samples)) continue;
-    if (limits && limits[i].ceiling != 0.f) {
-      live_lim.push_back(i);
-      lds_floats = std::max(lds_floats, limiter_lds_floats(rp.g, rp.fir, LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold}));
-    } else {
-      live.push_back(i);
-    }
-  }
-  if (live.empty() && live_lim.empty()) return 0;
-  auto fading = [&](const std::vector<int>& kind) {
-    if (fades)
-      for (int i : kind)
-        if (fades[i].count >= 0) return true;
-    return false;
-  };
-  const bool fade_live = fading(live), fade_lim = fading(live_lim);
-  const size_t lim_at = align_up(live.size() * sizeof(PcmPoolRow), 256);
-  const size_t fade_at = align_up(lim_at + live_lim.size() * sizeof(PcmLimRow), 256);
-  const size_t fade_lim_at = fade_at + (fade_live ? align_up(live.size() * sizeof(PcmFade), 256) : 0);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, fade_lim_at + (fade_lim ? live_lim.size() * sizeof(PcmFade) : 0))) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  // the fade table of a kind with a fading row, in the order of its row table; null for a kind without one
-  auto fade_table = [&](const std::vector<int>& kind, bool any, size_t at) -> PcmFade* {
-    if (!any) return nullptr;
-    PcmFade* t = reinterpret_cast<PcmFade*>(m->scrB + at);
-    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return fade_of(&fades[kind[i]]); });
-    return t;
-  };
-  auto row_of = [&](int i) {
-    const mbv_pcm_chunk& k = chunks_host[i];
-    return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
-                      reinterpret_cast<short*>(k.pcm), k.pcm_capacity, reinterpret_cast<unsigned*>(k.running_peak),
-                      k.out_samples, packed ? off[i] : (int64_t)-1};
-  };
-  auto count_of = [&](int i) { return chunks_host[i].out_count; };
-  if (!live.empty()) {
-    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB);
-    upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
-    const PcmFade* ft = fade_table(live, fade_live, fade_at);
-    grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
-      ++m->wire_runs;
-      launch_resample_pcm16_pool(rows + f, ft ? ft + f : nullptr, nn, max_count, rp.bank, rp.g, packed, law, s);
-      return 0;
-    });
-  }
-  if (!live_lim.empty()) {
-    PcmLimRow* rows = reinterpret_cast<PcmLimRow*>(m->scrB + lim_at);
-    upload_rows<kPcmPoolChunk>(live_lim.size(), rows, s, [&](size_t i) {
-      const mbv_pcm_limit& l = limits[live_lim[i]];
-      return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
-    });
-    const PcmFade* ft = fade_table(live_lim, fade_lim, fade_lim_at);
-    grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
-      ++m->wire_runs;
-      launch_resample_pcm16_pool_limited(rows + f, ft ? ft + f : nullptr, nn, max_count, rp.bank, rp.g, lds_floats,
-                                         packed, law, s);
-      return 0;
-    });
-  }
-  HIPCHK(m, hipGetLastError());
-  return 0;
+  return pooled_wire(m, who, "chunk", [&](int i) -> const mbv_pcm_chunk& { return chunks_host[i]; }, limits, fades, n, rp,
+                     off, total, law, packed, packed_capacity, stream, ChunkSide{});
 }
 }  // namespace
 
@@ -3674,6 +3725,141 @@ int mbv_resample_g711_chunks_faded(mbv_model* m, const mbv_pcm_chunk* chunks_hos
   if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_chunks_faded: %s, got %d", why, law);
   return pcm16_chunks(m, "mbv_resample_g711_chunks_faded", chunks_host, limits_host, n, orig_sr, target_sr, filter,
                       packed, packed_capacity, law, stream, fades_host);
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(MBV_TURN_MAX_SEGS == kTurnMaxSegs, "segment bound of the C-ABI and the kernels");
+constexpr int kTurnSegChunk = 96;   // segments per upload_rows launch: 3 KiB of kernel arguments
+
+// The checks of mbv_turn_plan: every turn's `chunk` as pcm_chunks_check checks a chunk, then its segments (integer
+// fields only).  Returns the packed total, or -1 with *err naming the offending turn.
+int64_t turns_check(const char* who, const mbv_turn_chunk* turns, int n, const RatePair& rp, int64_t* packed_first,
+                    std::string* err, const mbv_pcm_limit* limits) {
+  const int64_t total = pcm_rows_check(who, "turn", [&](int i) -> const mbv_pcm_chunk& { return turns[i].chunk; }, n, rp,
+                                       packed_first, err, limits);
+  if (total < 0) return -1;
+  char buf[512];
+  int64_t all_segs = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_turn_chunk& t = turns[i];
+    if (t.n_segs < 0 || (t.n_segs > 0 && !t.segs)) {
+      snprintf(buf, sizeof buf, "%s: turn %d: n_segs must be >= 0 and segs given", who, i);
+      *err = buf;
+      return -1;
+    }
+    all_segs += t.n_segs;
+    if (all_segs > MBV_TURN_MAX_SEGS) {
+      snprintf(buf, sizeof buf, "%s: turn %d: more than %d segments in one call (MBV_TURN_MAX_SEGS)", who, i, MBV_TURN_MAX_SEGS);
+      *err = buf;
+      return -1;
+    }
+    int64_t end = 0;
+    for (int s = 0; s < t.n_segs; ++s) {
+      const mbv_turn_seg& sg = t.segs[s];
+      buf[0] = 0;
+      if (sg.start < 0 || sg.length <= 0 || (double)sg.start + (double)sg.length >= 0x1p62)
+        snprintf(buf, sizeof buf, "%s: turn %d: segment %d: start must be >= 0 and length > 0", who, i, s);
+      else if (sg.ramp < 0 || sg.ramp > sg.length / 2)
+        snprintf(buf, sizeof buf, "%s: turn %d: segment %d: ramp %d must be in [0, length / 2 = %lld]", who, i, s, sg.ramp,
+                 (long long)(sg.length / 2));
+      else if (sg.start < end)
+        snprintf(buf, sizeof buf, "%s: turn %d: segment %d starts at %lld, below the end %lld of the one before: segments "
+                 "are ascending and disjoint", who, i, s, (long long)sg.start, (long long)end);
+      if (buf[0]) {
+        *err = buf;
+        return -1;
+      }
+      end = sg.start + sg.length;
+    }
+  }
+  return total;
+}
+
+// what mbv_resample_turns has beside its rows: the call's segment table in front, a slice of it per row
+struct TurnSide {
+  const std::vector<TurnSeg>& segs;
+  const std::vector<int>& seg_first;
+  const mbv_turn_chunk* turns;
+  size_t head_bytes, row_bytes = sizeof(TurnSlice);
+  void head(char* dst, hipStream_t s) const {
+    upload_rows<kTurnSegChunk>(segs.size(), reinterpret_cast<TurnSeg*>(dst), s, [&](size_t i) { return segs[i]; });
+  }
+  void rows(const std::vector<int>& kind, char* dst, hipStream_t s) const {
+    upload_rows<kPcmPoolChunk>(kind.size(), reinterpret_cast<TurnSlice*>(dst), s,
+                               [&](size_t i) { return TurnSlice{seg_first[kind[i]], turns[kind[i]].n_segs}; });
+  }
+  void launch(const PcmPoolRow* rows, const char* slices, const char* head, const PcmFade* ft, int n, int64_t max_count,
+              const RatePair& rp, void* packed, int law, hipStream_t s) const {
+    launch_resample_pcm16_turns(rows, reinterpret_cast<const TurnSlice*>(slices), reinterpret_cast<const TurnSeg*>(head),
+                                ft, n, max_count, rp.bank, rp.g, packed, law, s);
+  }
+  void launch_limited(const PcmLimRow* rows, const char* slices, const char* head, const PcmFade* ft, int n,
+                      int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law, hipStream_t s) const {
+    launch_resample_pcm16_turns_limited(rows, reinterpret_cast<const TurnSlice*>(slices),
+                                        reinterpret_cast<const TurnSeg*>(head), ft, n, max_count, rp.bank, rp.g,
+                                        lds_floats, packed, law, s);
+  }
+};
+
+// mbv_resample_turns: the chunk entries' body (pooled_wire) for rows whose input is a timeline
+int pcm16_turns(mbv_model* m, const char* who, const mbv_turn_chunk* turns, const mbv_pcm_limit* limits,
+                const mbv_pcm_fade* fades, int n, int orig_sr, int target_sr, int filter, int law, void* packed,
+                int64_t packed_capacity, void* stream) {
+  if (!m) return 1;
+  if (n < 0 || (n > 0 && !turns)) return m->fail("%s: bad arguments", who);
+  if (law != kLawNone)
+    if (const char* why = law_refusal(law)) return m->fail("%s: %s (0: int16), got %d", who, why, law);
+  if (fades)
+    for (int i = 0; i < n; ++i)
+      if (const char* why = fade_refusal(fades[i])) return m->fail("%s: turn %d: %s", who, i, why);
+  for (int i = 0; i < n; ++i) {
+    if (turns[i].chunk.wave) return m->fail("%s: turn %d: chunk.wave must be NULL (the input is the segments)", who, i);
+    if (!turns[i].chunk.pcm) return m->fail("%s: turn %d: pcm missing", who, i);
+  }
+  DEVICE_GUARD(m);
+  RatePair rp;
+  if (rate_pair(m, who, orig_sr, target_sr, filter, &rp)) return 1;
+  std::string err;
+  std::vector<int64_t> off(n > 0 ? n : 1);
+  const int64_t total = turns_check(who, turns, n, rp, off.data(), &err, limits);
+  if (total < 0) return m->fail("%s", err.c_str());
+  std::vector<int> seg_first(n > 0 ? n : 1);
+  std::vector<TurnSeg> segs;
+  for (int i = 0; i < n; ++i) {
+    seg_first[i] = (int)segs.size();
+    for (int k = 0; k < turns[i].n_segs; ++k) {
+      const mbv_turn_seg& sg = turns[i].segs[k];
+      if (!sg.wave) return m->fail("%s: turn %d: segment %d: wave missing", who, i, k);
+      segs.push_back(TurnSeg{sg.wave, sg.start, sg.length, sg.ramp, fade_inv(sg.ramp)});
+    }
+  }
+  return pooled_wire(m, who, "turn", [&](int i) -> const mbv_pcm_chunk& { return turns[i].chunk; }, limits, fades, n, rp,
+                     off, total, law, packed, packed_capacity, stream,
+                     TurnSide{segs, seg_first, turns, segs.size() * sizeof(TurnSeg)});
+}
+}  // namespace
+
+extern "C" {
+
+int64_t mbv_turn_plan(int orig_sr, int target_sr, int filter, const mbv_turn_chunk* turns, const mbv_pcm_limit* limits,
+                      int n, int64_t* packed_first) {
+  const char* who = "mbv_turn_plan";
+  if (n < 0 || (n > 0 && !turns)) { g_create_error = std::string(who) + ": bad arguments"; return -1; }
+  RatePair rp;
+  if (rate_pair(nullptr, who, orig_sr, target_sr, filter, &rp)) return -1;
+  std::string err;
+  const int64_t total = turns_check(who, turns, n, rp, packed_first, &err, limits);
+  if (total < 0) g_create_error = err;
+  return total;
+}
+
+int mbv_resample_turns(mbv_model* m, const mbv_turn_chunk* turns_host, const mbv_pcm_limit* limits_host,
+                       const mbv_pcm_fade* fades_host, int n, int orig_sr, int target_sr, int filter, int law,
+                       void* packed, int64_t packed_capacity, void* stream) {
+  return pcm16_turns(m, "mbv_resample_turns", turns_host, limits_host, fades_host, n, orig_sr, target_sr, filter, law,
+                     packed, packed_capacity, stream);
 }
 
 int mbv_g711_encode(mbv_model* m, const int16_t* pcm, int64_t n, int law, uint8_t* out, void* stream) {

@@ -491,6 +491,32 @@ void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, i
 void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, int n, int64_t max_count,
                                         const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
                                         int law, hipStream_t s);
+// Turns on the wire (mbv_resample_turns): the input of a row is not one wave row but a TIMELINE of
+// segments, each the waveform of one utterance, with silence between them; it is never materialised.  Timeline index j
+// holds x[j - start] g(j - start) of the segment with start <= j < start + n, and 0.f anywhere else.  g is the
+// de-click ramp of a segment's two ends, with i the local index, one fp32 multiply with one rounding:
+//   i < ramp:       (float)(i + 1) * inv              i >= n - ramp:   (float)(ramp - (i - (n - ramp))) * inv
+// (the fade's own ramp, mirrored for the rise; inv = 1.0f / (float)(ramp + 1), as mbv_pcm_fade_make computes it) and
+// no multiply anywhere else; ramp <= n / 2, so the two never overlap.  A table row of the pooled kernels
+// (PcmPoolRow / PcmLimRow with x = null) reads segs[first .. first + count) of the call's segment table: the segments
+// that intersect its input window, ascending.  Everything behind the staging is the code of the plain rows, so a turn
+// row is bitwise the plain row of the assembled timeline.
+struct TurnSeg {
+  const float* x;              // the utterance's wave row
+  int64_t start, n;            // its place on the timeline and its valid length
+  int32_t ramp;                // de-click samples at either end (0: none)
+  float inv;
+};
+struct TurnSlice { int32_t first, count; };
+constexpr int kTurnMaxSegs = 4096;   // segments of one call (MBV_TURN_MAX_SEGS)
+// launch_resample_pcm16_pool / _pool_limited over turn rows: slices[i] beside rows[i]
+void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
+                                 const PcmFade* fades, int n, int64_t max_count, const float* bank,
+                                 const ResampleGeom& g, void* packed, int law, hipStream_t s);
+void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
+                                         const PcmFade* fades, int n, int64_t max_count, const float* bank,
+                                         const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
+                                         hipStream_t s);
 // the stand-alone codec: n samples, law kLawUlaw or kLawAlaw (checked by the caller)
 void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s);
 void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s);

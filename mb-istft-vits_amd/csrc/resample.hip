@@ -211,6 +211,39 @@ __device__ __forceinline__ void resample_stage(float* xs, const uint8_t* __restr
   }
 }
 
+// The segmented source of a turn row (kernels.h).  The scan over the row's few segments has a uniform
+// trip count and reads the table through uniform addresses; per element it only selects an address and a ramp, and
+// the ONE load behind it is predicated exactly as the plain row's is (below the frontier, inside a segment).
+struct TurnSrc { const TurnSeg* __restrict__ segs; int n; };
+
+// timeline index j: zero in a pause, beyond the timeline and at or past `limit` (nothing there is loaded)
+__device__ __forceinline__ float turn_sample(const TurnSrc& src, int64_t j, int64_t limit) {
+  const float* p = nullptr;
+  float g = 1.f;
+  bool ramped = false;
+  for (int s = 0; s < src.n; ++s) {
+    const TurnSeg sg = src.segs[s];
+    const int64_t i = j - sg.start;
+    const bool in = i >= 0 && i < sg.n;
+    const int64_t fall = i - (sg.n - sg.ramp);             // >= 0: inside the falling ramp
+    const bool rise = i < sg.ramp;
+    const float gs = (float)(rise ? i + 1 : sg.ramp - fall) * sg.inv;
+    p = in ? sg.x + i : p;
+    g = in ? gs : g;
+    ramped = in ? (rise || fall >= 0) : ramped;
+  }
+  if (!p || j >= limit) return 0.f;
+  const float v = *p;
+  return ramped ? v * g : v;
+}
+
+// the window of the plain row's resample_stage, from the timeline
+__device__ __forceinline__ void resample_stage(float* xs, const TurnSrc& src, int64_t j0, int64_t t_last,
+                                               int L, int M, int K, int left, int64_t limit) {
+  const int W = (int)((t_last * M) / L - left + K - j0);
+  for (int i = threadIdx.x; i < W; i += kResampleTile) xs[i] = turn_sample(src, j0 + i, limit);
+}
+
 // output t from the staged window
 __device__ __forceinline__ float resample_output(const float* xs, int64_t j0, int64_t t, const float* __restrict__ bank,
                                                  int L, int M, int K, int left, double ratio) {
@@ -344,6 +377,9 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - fade (kernels.h): the value the clip takes is first scaled by the ramp of its own index t; a row
 //     without one (count < 0) skips the multiply, so its bits are those of a launch that knows no fade.  FADE = false
 //     (a ranged launch without a fade) compiles the test away: that instantiation is the kernel of before
+//   - TURN = true: the row's input is the timeline of `src` (r.x is null): the staging, and the direct
+//     read of FIR = false, go through turn_sample; in_total / in_avail count timeline samples.  TURN = false never
+//     reads `src`: those instantiations are the kernels of before
 // ---------------------------------------------------------------------------------------------------
 // what a wire launch stores for the int16 q
 template <int LAW>
@@ -364,18 +400,18 @@ __device__ __forceinline__ float fade_gain(const PcmFade& f, int64_t t) {
   return k < f.count ? (float)(f.count - k) * f.inv : 0.f;
 }
 
-template <bool FIR, int LAW, bool FADE>
+template <bool FIR, int LAW, bool FADE, bool TURN>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
                                                        const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio);
+                                                       double ratio, const TurnSrc& src);
 
-template <bool FIR, bool LIM, int LAW, bool FADE>
+template <bool FIR, bool LIM, int LAW, bool FADE, bool TURN = false>
 __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
                                                     int L, int M, int K, int left, double ratio,
                                                     short* __restrict__ packed, const LimiterParams& lim,
-                                                    const PcmFade& fade) {
+                                                    const PcmFade& fade, const TurnSrc& src = TurnSrc{nullptr, 0}) {
   using Sample = WireSample<LAW>;
   using W = typename Sample::type;
   W* pcm = reinterpret_cast<W*>(r.pcm);
@@ -400,7 +436,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   }
   const int64_t limit = n < r.in_avail ? n : r.in_avail;
   if constexpr (LIM) {
-    resample_pcm16_limited<FIR, LAW, FADE>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left, ratio);
+    resample_pcm16_limited<FIR, LAW, FADE, TURN>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left, ratio,
+                                                 src);
     return;
   }
   const float* xb = r.x;
@@ -410,12 +447,17 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
     if (t_last > n_out - 1) t_last = n_out - 1;
     if (t_last > r.out_end - 1) t_last = r.out_end - 1;
     j0 = resample_window_first(t0, L, M, left);
-    resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
+    if constexpr (TURN) resample_stage(xs, src, j0, t_last, L, M, K, left, limit);
+    else resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
     __syncthreads();
   }
   float v = 0.f;
   const bool live = t < r.out_end && t < n_out;
-  if (live) v = FIR ? resample_output(xs, j0, t, bank, L, M, K, left, ratio) : (t < limit ? xb[t] : 0.f);
+  if (live) {
+    if constexpr (FIR) v = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
+    else if constexpr (TURN) v = turn_sample(src, t, limit);
+    else v = t < limit ? xb[t] : 0.f;
+  }
   if (r.running) {
     float m = fabsf(v);
 #pragma unroll
@@ -453,12 +495,12 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
 //      A fade scales y, not v: the limiter sees the unfaded signal, and |y| only shrinks (the ramp is below 1)
 // LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
 // over the workgroup; no thread leaves before the last barrier.
-template <bool FIR, int LAW, bool FADE>
+template <bool FIR, int LAW, bool FADE, bool TURN>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
                                                        const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio) {
+                                                       double ratio, const TurnSrc& src) {
   const int La = lim.lookahead, H = lim.hold;
   const float c = lim.ceiling;
   int64_t t_end = t0 + kResampleTile;
@@ -478,7 +520,8 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     int64_t k_hi = lo + S - 1;
     if (k_hi > n_out - 1) k_hi = n_out - 1;
     j0 = resample_window_first(k_lo, L, M, left);
-    resample_stage(lds, xb, j0, k_hi, L, M, K, left, limit);
+    if constexpr (TURN) resample_stage(lds, src, j0, k_hi, L, M, K, left, limit);
+    else resample_stage(lds, xb, j0, k_hi, L, M, K, left, limit);
     __syncthreads();
   }
   float p = 0.f;
@@ -488,7 +531,9 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     const int64_t k = lo + i;
     float v = 0.f;
     if (k >= 0 && k < n_out) {
-      v = FIR ? resample_output(lds, j0, k, bank, L, M, K, left, ratio) : (k < limit ? xb[k] : 0.f);
+      if constexpr (FIR) v = resample_output(lds, j0, k, bank, L, M, K, left, ratio);
+      else if constexpr (TURN) v = turn_sample(src, k, limit);
+      else v = k < limit ? xb[k] : 0.f;
       if (k >= t0 && k < t_end) top = fmaxf(top, fabsf(v));
       if (p > 0.01f) v = (v / p) * 0.9f;
     }
@@ -668,6 +713,77 @@ void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, in
     } else {
       hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW>), grid, block, lds, s, rows, fades, bank, 1, 1, 0, 0,
                          1.0, pk);
+    }
+  });
+}
+
+// The pooled kernels over turn rows (mbv_resample_turns): the same tile, its input the row's slice of the call's
+// segment table
+template <bool FIR, int LAW>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_turn_kernel(const PcmPoolRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
+                           const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
+                           const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                           short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmPoolRow r = rows[blockIdx.y];
+  const TurnSlice sl = slices[blockIdx.y];
+  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
+  resample_pcm16_tile<FIR, false, LAW, true, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade,
+                                                   TurnSrc{segs + sl.first, sl.count});
+}
+
+template <bool FIR, int LAW>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_turn_limited_kernel(const PcmLimRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
+                                   const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
+                                   const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
+                                   short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmLimRow r = rows[blockIdx.y];
+  const TurnSlice sl = slices[blockIdx.y];
+  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
+  resample_pcm16_tile<FIR, true, LAW, true, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
+                                                  TurnSrc{segs + sl.first, sl.count});
+}
+
+void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
+                                         const PcmFade* fades, int n, int64_t max_count, const float* bank,
+                                         const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
+                                         hipStream_t s) {
+  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
+  const dim3 grid((unsigned)bx, n), block(kResampleTile);
+  const size_t lds = (size_t)lds_floats * sizeof(float);
+  short* pk = static_cast<short*>(packed);
+  with_law(law, [&](auto lc) {
+    constexpr int LAW = decltype(lc)::value;
+    if (bank) {
+      hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<true, LAW>), grid, block, lds, s, rows, slices, segs,
+                         fades, bank, g.L, g.M, g.K, g.left, g.ratio, pk);
+    } else {
+      hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<false, LAW>), grid, block, lds, s, rows, slices, segs,
+                         fades, bank, 1, 1, 0, 0, 1.0, pk);
+    }
+  });
+}
+
+void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
+                                 const PcmFade* fades, int n, int64_t max_count, const float* bank,
+                                 const ResampleGeom& g, void* packed, int law, hipStream_t s) {
+  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
+  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
+  const dim3 grid((unsigned)bx, n), block(kResampleTile);
+  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
+  short* pk = static_cast<short*>(packed);
+  with_law(law, [&](auto lc) {
+    constexpr int LAW = decltype(lc)::value;
+    if (bank) {
+      hipLaunchKernelGGL((resample_pcm16_turn_kernel<true, LAW>), grid, block, lds, s, rows, slices, segs, fades, bank,
+                         g.L, g.M, g.K, g.left, g.ratio, pk);
+    } else {
+      hipLaunchKernelGGL((resample_pcm16_turn_kernel<false, LAW>), grid, block, lds, s, rows, slices, segs, fades, bank,
+                         1, 1, 0, 0, 1.0, pk);
     }
   });
 }

@@ -1661,6 +1661,42 @@ class SynthesizerTrn(nn.Module):
                    packed, cap)
 
     @torch.no_grad()
+    def resample_turns(self, turns, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
+                       encoding="pcm16", fades=None):
+        """`resample_pcm16_chunks` for rows whose input is a TIMELINE of utterances (`mbv_resample_turns`, DESIGN §7.18;
+        `wire.PcmPool` drives it for its `wire.Turn`s): `turns` is a ctypes array (or a list) of `_capi.MbvTurnChunk`,
+        each a chunk with `wave` None, `in_total` / `in_avail` the timeline's total and frontier, and `segs` a ctypes
+        array of the `_capi.MbvTurnSeg` its input window touches.  Every stored value is bitwise what
+        `resample_pcm16_range` stores for the timeline written out as one row (`wire.assemble_turn`).  `packed`,
+        `limits`, `encoding` and `fades` as `resample_pcm16_chunks` takes them; one launch for the unlimited turns and
+        one for the limited ones.  No host synchronisation (beyond the first call for a rate pair)."""
+        filt = _filter_code(res_type)
+        law = _law_code(encoding)
+        wire_dtype = torch.uint8 if law else torch.int16
+        if not isinstance(turns, C.Array):
+            turns = (_capi.MbvTurnChunk * len(turns))(*turns)
+        n = len(turns)
+        dev = self._device()
+        cap = 0
+        if packed is not None:
+            if packed.device != dev or packed.dtype != wire_dtype or packed.dim() != 1 or packed.stride(0) != 1:
+                raise ValueError("resample_turns: packed must be a 1-D %s tensor on %s with unit stride"
+                                 % (str(wire_dtype).replace("torch.", ""), dev))
+            cap = packed.shape[0]
+        lim = fd = None
+        if limits is not None and any(l is not None for l in limits):
+            if len(limits) != n:
+                raise ValueError("resample_turns: one limit per turn expected (%d), got %d" % (n, len(limits)))
+            lim = (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+        if fades is not None and any(f is not None for f in fades):
+            if len(fades) != n:
+                raise ValueError("resample_turns: one fade per turn expected (%d), got %d" % (n, len(fades)))
+            fd = (_capi.MbvPcmFade * n)(*[
+                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
+                else _capi.pcm_fade(*f) for f in fades])
+        self._call("mbv_resample_turns", turns, lim, fd, n, int(orig_sr), int(target_sr), filt, law, packed, cap)
+
+    @torch.no_grad()
     def resample_ranges(self, rows, orig_sr, target_sr, res_type="kaiser_best"):
         """The input side of a live wire (`mbv_resample_ranges`; `wire.LiveWire` and `wire.PcmPool` drive it): `rows`
         is a ctypes array (or a list) of `_capi.MbvResampleRange`, each the raw buffer of one recording that is still

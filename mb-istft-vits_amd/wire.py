@@ -50,6 +50,12 @@ entries measure the ITU-R BS.1770 integrated loudness of the model-rate waveform
 choose the static gain from it; the streamed entries take the measured value as an input, as they take `peak=`, and
 keep `.loudness`, the running value of what they have decoded (`mbv_loudness_range`; one `mbv_loudness_chunks` launch
 per tick in a `PcmPool`).  The gain enters the wire kernels as their `peak`, so every bitwise relation above holds.
+
+Turns: `PcmPool.add_turn` opens a `Turn`, the phrases of a dialogue turn as ONE gapless wire stream.  Its
+segments are ordinary single-utterance decode streams of the pool; the wire kernels read their timeline in place
+(`mbv_resample_turns`: silence in the pauses, a de-click ramp at both ends of every segment), so one resampler, one
+limiter and one framing run over the joints.  `TurnPlan` is its integer planning, `assemble_turn` the timeline written
+out as one row: the turn's bytes are bitwise `service_pcm16` of that row, `revoke` with `fade=` included.
 """
 import base64
 import ctypes as C
@@ -1164,6 +1170,489 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
                     encoding=encoding, in_encoding=in_encoding, loudness=loudness)
 
 
+# ---- turns: several utterances as one gapless wire stream
+def turn_ramp(ramp, n):
+    """De-click samples at either end of a segment of `n` samples under a turn's ramp of `ramp`: min(ramp, n // 2), so
+    that the two ramps of a segment never overlap."""
+    return min(int(ramp), int(n) // 2)
+
+
+def assemble_turn(waves, lengths, pauses, ramp):
+    """The timeline of a turn written out as ONE fp32 row [1, 1, total], in torch and on the device of `waves[0]`: the
+    one-shot form of what a `Turn` streams, and the row its bytes are defined by (`service_pcm16` of it, with the
+    turn's `peak`, `limiter`, `encoding` and `fade`).
+      waves    the segments' waveforms (`st.o` of each finished stream; any shape, read flat)
+      lengths  valid samples n_s of each
+      pauses   model-rate samples of silence in front of segments 1 .. S-1
+      ramp     N, the de-click ramp in model-rate samples (round(ramp_ms * model_sr / 1000))
+    Segment s starts at p_0 = 0, p_{s+1} = p_s + n_s + pauses[s]; with N_s = min(N, n_s // 2) its sample i is multiplied
+    by (i + 1) * inv for i < N_s and by (N_s - (i - (n_s - N_s))) * inv for i >= n_s - N_s, inv = 1.0f / (N_s + 1) as
+    `mbv_pcm_fade_make` gives it, in fp32 with one rounding each, and is copied anywhere else.  Exact in fp32, so it is
+    bitwise the timeline `mbv_resample_turns` reads."""
+    waves, lengths, pauses = list(waves), [int(n) for n in lengths], [int(p) for p in pauses]
+    if not waves or len(lengths) != len(waves) or len(pauses) != len(waves) - 1:
+        raise ValueError("assemble_turn: S >= 1 waves, S lengths and S - 1 pauses expected")
+    if min(lengths) < 1 or (pauses and min(pauses) < 0) or int(ramp) < 0:
+        raise ValueError("assemble_turn: lengths must be >= 1, pauses and ramp >= 0")
+    dev = waves[0].device
+    out = torch.zeros(1, 1, sum(lengths) + sum(pauses), device=dev, dtype=torch.float32)
+    p = 0
+    for s, (w, n) in enumerate(zip(waves, lengths)):
+        if s:
+            p += pauses[s - 1]
+        seg = w.detach().reshape(-1)[:n].to(device=dev, dtype=torch.float32).clone()
+        if seg.numel() != n:
+            raise ValueError("assemble_turn: wave %d holds %d samples, fewer than its length %d" % (s, seg.numel(), n))
+        k = turn_ramp(ramp, n)
+        if k:
+            inv = torch.tensor(_capi.pcm_fade(0, k).inv, device=dev, dtype=torch.float32)
+            g = torch.arange(1, k + 1, device=dev, dtype=torch.float32) * inv
+            seg[:k] *= g
+            seg[n - k:] *= g.flip(0)
+        out[0, 0, p:p + n] = seg
+        p += n
+    return out
+
+
+def resample_geometry(orig_sr, target_sr, res_type="kaiser_best"):
+    """(L, M, K, left) of the polyphase bank of a rate pair (`mbv_resample_bank`, host only): output t reads the inputs
+    floor(t M / L) - left - 1 .. floor(t M / L) - left + K - 1.  Equal rates: (1, 1, 0, 0), the sample itself."""
+    filt = _filter_code(res_type)
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if min(orig_sr, target_sr) <= 0:
+        raise ValueError("sample rates must be positive")
+    if orig_sr == target_sr:
+        return 1, 1, 0, 0
+    lib = _capi.lib()
+    taps, left = C.c_int32(), C.c_int32()
+    if lib.mbv_resample_bank(orig_sr, target_sr, filt, None, 0, None, C.byref(taps), C.byref(left)):
+        msg = lib.mbv_last_error(None)
+        raise _capi.MbvError(msg.decode() if msg else "mbv_resample_bank failed")
+    g = math.gcd(orig_sr, target_sr)
+    return target_sr // g, orig_sr // g, int(taps.value), int(left.value)
+
+
+def turn_plan(orig_sr, target_sr, turns, res_type="kaiser_best", limits=None):
+    """(total, packed_first) of `mbv_turn_plan` for `_capi.MbvTurnChunk`s (host only: no GPU needed, only the integer
+    fields are read): the checks `resample_turns` makes on every turn and its segments, and where every turn starts in
+    the packed buffer.  Raises `_capi.MbvError` naming the offending turn."""
+    filt = _filter_code(res_type)
+    if not isinstance(turns, C.Array):
+        turns = (_capi.MbvTurnChunk * len(turns))(*turns)
+    n = len(turns)
+    lim = None
+    if limits is not None and any(l is not None for l in limits):
+        lim = (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+    first = (C.c_int64 * max(n, 1))()
+    L = _capi.lib()
+    total = L.mbv_turn_plan(int(orig_sr), int(target_sr), filt, turns, lim, n, first)
+    if total < 0:
+        msg = L.mbv_last_error(None)
+        raise _capi.MbvError(msg.decode() if msg else "mbv_turn_plan failed")
+    return int(total), list(first)[:n]
+
+
+class TurnPlan:
+    """What a turn may hand out as int16, in pure integers (no tensor, no GPU).
+
+    A turn is a timeline at the model's rate: `append(n, pause)` puts a segment of n samples `pause` samples behind the
+    end of the one before (the first at 0), `decoded(s, avail)` says how much of segment s exists, `close()` fixes the
+    total at the end of the last segment.  `frontier()` is the contiguous decoded prefix: it runs through a finished
+    segment, the pause behind it and the decoded part of the next one; while the turn is open it stops at the end of
+    the last segment.  Wire sample u is final iff no tap of it lies at or past the frontier (`resample_ready_open`), or
+    the turn is closed and wholly decoded; under a limiter u + `lookahead` must be final in that sense
+    (`limiter_ready`).  `wire_due()` is the range that has become final since the last `wired()`; `segments_for` the
+    segments its input window touches (with the limiter's halo of `lookahead + hold` outputs in front and `lookahead`
+    behind).  The ranges are monotone and tile [0, total at the wire rate); they do not depend on what is appended
+    later.  `cut_at(cut, keep)` is a revoke: nothing at or past wire sample `cut` is handed out, and the segments
+    behind the first `keep` are dropped (the frontier never passes where they began)."""
+
+    def __init__(self, model_sr, rate, max_samples, res_type="kaiser_best", lookahead=0, hold=0):
+        self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
+        self.lookahead, self.hold = int(lookahead), int(hold)
+        if not 0 <= self.lookahead <= Limiter.MAX_LOOKAHEAD or not 0 <= self.hold <= Limiter.MAX_HOLD:
+            raise ValueError("limiter lookahead must be in [0, %d] and hold in [0, %d] output samples"
+                             % (Limiter.MAX_LOOKAHEAD, Limiter.MAX_HOLD))
+        self.max_samples = int(max_samples)
+        if self.max_samples < 1:
+            raise ValueError("max_samples must be >= 1")
+        self.L, self.M, self.K, self.left = resample_geometry(model_sr, rate, res_type)   # refuses the rate pair here
+        # model-rate samples that stand in for the total while the turn is open: int(capacity * ratio) >= max_samples,
+        # and no timeline that fits max_samples reaches it
+        self.capacity = int(math.ceil(self.max_samples * (float(self.model_sr) / self.rate))) + 1
+        self.starts, self.lengths, self.avail = [], [], []
+        self.closed = False
+        self.out_done = 0             # wire samples [0, out_done) are final and handed out
+        self.cut = None               # the length a revoke left
+        self._fence = None            # where the first dropped segment began
+
+    @property
+    def end(self):
+        """The end of the last segment: the timeline's total once closed."""
+        return self.starts[-1] + self.lengths[-1] if self.starts else 0
+
+    @property
+    def total(self):
+        return self.end if self.closed else None
+
+    def out_total(self, n=None):
+        """Wire samples of a timeline of n model-rate samples (default: this one's, as it stands)."""
+        n = self.end if n is None else int(n)
+        return resample_ready(self.model_sr, self.rate, n, n, self.res_type)
+
+    def check_append(self, n, pause=0):
+        """-> the start of a segment of n samples appended `pause` behind the last; ValueError when refused."""
+        n, pause = int(n), int(pause)
+        if self.closed:
+            raise ValueError("append after close()")
+        if n < 1 or pause < 0:
+            raise ValueError("append: a segment has n >= 1 samples and a pause >= 0")
+        if not self.starts and pause:
+            raise ValueError("append: the first segment starts the turn (pause %d must be 0)" % pause)
+        p = self.end + pause
+        if self.out_total(p + n) > self.max_samples:
+            raise ValueError("append: %d + %d + %d model-rate samples are %d wire samples, beyond the turn's capacity of "
+                             "%d (max_samples)" % (self.end, pause, n, self.out_total(p + n), self.max_samples))
+        return p
+
+    def append(self, n, pause=0):
+        p = self.check_append(n, pause)
+        self.starts.append(p)
+        self.lengths.append(int(n))
+        self.avail.append(0)
+        return len(self.starts) - 1
+
+    def decoded(self, s, avail):
+        self.avail[s] = max(self.avail[s], min(int(avail), self.lengths[s]))
+
+    def close(self):
+        self.closed = True
+
+    @property
+    def complete(self):
+        """Closed, and every segment wholly decoded."""
+        return self.closed and self._fence is None and self.avail == self.lengths
+
+    def frontier(self):
+        f = self.end
+        for p, n, a in zip(self.starts, self.lengths, self.avail):
+            if a < n:
+                f = p + a
+                break
+        return f if self._fence is None else min(f, self._fence)
+
+    def in_total(self):
+        """`in_total` of the wire step: the total, or the capacity that stands in for it while the turn is open."""
+        return self.end if self.closed else self.capacity
+
+    def ready(self):
+        f = self.frontier()
+        if self.closed:
+            r = limiter_ready(self.model_sr, self.rate, f, self.end, self.lookahead, self.res_type)
+        else:
+            r = min(limiter_ready(self.model_sr, self.rate, f, None, self.lookahead, self.res_type), self.max_samples)
+        return r if self.cut is None else min(r, self.cut)
+
+    @property
+    def done(self):
+        """Every final sample is handed out: the turn is closed and either complete or wired up to a revoke's cut."""
+        if not self.closed:
+            return False
+        if self.cut is not None:
+            return self.out_done >= self.cut
+        return self.complete and self.out_done >= self.out_total()
+
+    def wire_due(self):
+        """-> None, or (out_first, out_count): the wire samples that have become final since the last `wired()`."""
+        b = self.ready()
+        return (self.out_done, b - self.out_done) if b > self.out_done else None
+
+    def wired(self, out_done):
+        self.out_done = int(out_done)
+
+    def window(self, out_first, out_count):
+        """[lo, hi): the timeline samples the taps of outputs [out_first, out_first + out_count) touch, the limiter's
+        halo included."""
+        a = max(int(out_first) - self.lookahead - self.hold, 0)
+        b = int(out_first) + int(out_count) + self.lookahead
+        if self.K == 0:
+            return a, b
+        return (a * self.M) // self.L - self.left - 1, ((b - 1) * self.M) // self.L - self.left + self.K
+
+    def segments_for(self, out_first, out_count):
+        """-> (s0, s1): segments [s0, s1) intersect the window of the range (s0 == s1: none does)."""
+        if int(out_count) <= 0:
+            return 0, 0
+        lo, hi = self.window(out_first, out_count)
+        hit = [s for s, (p, n) in enumerate(zip(self.starts, self.lengths)) if p < hi and p + n > lo]
+        return (hit[0], hit[-1] + 1) if hit else (0, 0)
+
+    def revoke_events(self, avails):
+        """The turn's readiness after every chunk of every segment, in timeline order, were it closed now: what
+        `revoke_plan` takes as `ready`.  avails[s] lists the model-rate samples of segment s that exist after each of
+        its chunks (ascending; the last is the whole segment).  -> [(s, i, ready), ...]; after a segment's last chunk
+        the frontier stands at the next segment's start (the end of the turn behind the last one)."""
+        end, out = self.end, []
+        for s, each in enumerate(avails):
+            for i, a in enumerate(each):
+                if i + 1 < len(each):
+                    f = self.starts[s] + min(int(a), self.lengths[s])
+                else:
+                    f = self.starts[s + 1] if s + 1 < len(self.starts) else end
+                out.append((s, i, limiter_ready(self.model_sr, self.rate, f, end, self.lookahead, self.res_type)))
+        return out
+
+    def cut_at(self, cut, keep):
+        self.closed = True
+        self.cut = int(cut)
+        if keep < len(self.starts):
+            self._fence = self.starts[keep]
+
+
+def _frames_decoded(st):
+    """z-frames of a `DecodeStream` decoded so far."""
+    return sum(st.schedule[st._decoded - 1]) if st._decoded else 0
+
+
+def _segment_length(st):
+    """Valid model-rate samples of a single-utterance stream, on the host: what `PcmStream` takes as its valid input."""
+    n = st.o.shape[-1]
+    return n if st.y_lengths is None else min(256 * st.z.shape[2], n)
+
+
+class Turn:
+    """Several utterances as ONE gapless wire stream (`PcmPool.add_turn`): the phrases of a dialogue turn,
+    appended while earlier ones play, resampled, limited and framed as one continuous piece of audio.
+
+    The segments are ordinary single-utterance `DecodeStream`s in the pool's `StreamPool`, untouched: each `st.o` is
+    bitwise its stand-alone decode.  The turn's input is their timeline (`TurnPlan`, `assemble_turn`), read in place by
+    `mbv_resample_turns`; `PcmPool.step()` wires every turn with something due in ONE such call and returns
+    `(turn, first, piece)` entries.  The concatenated pieces are bitwise `service_pcm16` of `assemble_turn` of the
+    finished waveforms with the turn's `peak`, `limiter` and `encoding` (and `fade`, once revoked), however the turn
+    was appended to, ticked or pooled.
+      pcm            int16 (uint8 under G.711) [1, max_samples]; unwritten samples hold silence
+      valid_samples  int64 [1] device, written when the turn is closed and its last piece is wired
+      peak           fp32 [1] device, the running peak of the resampled samples handed out so far
+      marks          one entry per segment: the wire sample at which each of its tokens starts (the segment's offset and
+                     the limiter's lag included), or None for a segment without marks
+      finished       every final sample has been handed out
+    The ramp of `ramp_ms` (5 ms by default: a convention like the fade's, not a measurement) scales both ends of every
+    segment, so a joint never depends on what is appended later."""
+
+    def __init__(self, pool, max_samples, peak=None, limiter=None, loudness=None, ramp_ms=5.0):
+        self._pool, self._net = pool, pool._net
+        net = self._net
+        self.model_sr, self.rate, self.res_type, self.encoding = pool.model_sr, pool.rate, pool.res_type, pool.encoding
+        self.limiter, self._lim = limiter, _limit_arg(limiter, self.rate)
+        loud = _loudness_arg(loudness, peak, "PcmPool.add_turn", stream=True)
+        if loud is not None and loud.target is None:
+            raise ValueError("PcmPool.add_turn: a turn keeps no running loudness; loudness= takes Loudness(measured=...) "
+                             "for the static gain only")
+        if not float(ramp_ms) >= 0.0:
+            raise ValueError("PcmPool.add_turn: ramp_ms must be >= 0")
+        self.ramp_ms, self.ramp = float(ramp_ms), int(round(float(ramp_ms) * 1e-3 * self.model_sr))
+        self._plan = TurnPlan(self.model_sr, self.rate, max_samples, self.res_type,
+                              lookahead=self._lim[1] if self._lim else 0, hold=self._lim[2] if self._lim else 0)
+        self._h = net._ensure_handle()
+        dev = net._device()
+        with torch.cuda.device(dev):
+            if _law_code(self.encoding):              # silence in G.711 is not the zero byte
+                self.pcm = torch.full((1, self._plan.max_samples), G711_ZERO[self.encoding], device=dev, dtype=torch.uint8)
+            else:
+                self.pcm = torch.zeros(1, self._plan.max_samples, device=dev, dtype=torch.int16)
+            self.valid_samples = torch.zeros(1, device=dev, dtype=torch.int64)
+            self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
+            self._peak_in = _peak_arg(peak, 1, dev, shape="1")
+            if loud is not None:
+                self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
+        self.segments = []            # the `DecodeStream`s, in timeline order
+        self.marks = []
+        self._fade = None
+        self._revoked = None
+        self._valid_set = False
+
+    # ---- where it stands
+    @property
+    def closed(self):
+        return self._plan.closed
+
+    @property
+    def finished(self):
+        return self._plan.done
+
+    @property
+    def revoked(self):
+        return self._revoked is not None
+
+    def _pause(self, pause_ms):
+        if not float(pause_ms) >= 0.0:
+            raise ValueError("append: pause_ms must be >= 0")
+        return int(round(float(pause_ms) * 1e-3 * self.model_sr))
+
+    def _check_segment(self, st):
+        from .stream import DecodeStream, LiveStream
+        pool = self._pool
+        if isinstance(st, LiveStream):
+            raise ValueError("Turn.append: a LiveStream is not a segment of a turn (its length is not known)")
+        if not isinstance(st, DecodeStream):
+            raise ValueError("Turn.append takes a DecodeStream (net.infer_stream / StreamPool.admit)")
+        if st._net is not self._net or st._h is not self._h or self._net._handle is not self._h:
+            raise ValueError("Turn.append: the stream belongs to another model or handle")
+        if st.z.shape[0] != 1:
+            raise ValueError("Turn.append takes a stream of ONE utterance (this one has %d rows)" % st.z.shape[0])
+        if pool.follower(st) is not None:
+            raise ValueError("Turn.append: the stream is a plain member of the pool (PcmPool.add): it has its own wire stream")
+        if any(st is m for t in pool.turns for m in t.segments) or any(st is m for m in self.segments):
+            raise ValueError("Turn.append: the stream is a segment of a turn already")
+
+    def append(self, st, pause_ms=0.0):
+        """Appends the single-utterance `DecodeStream` `st` (a member of the pool's `StreamPool`; it joins it otherwise)
+        `pause_ms` of silence behind the last segment; -> its index.  The first segment starts the turn (p_0 = 0): it
+        takes no pause.  ValueError, with nothing changed: a `LiveStream`, a plain member of this pool, a segment of a
+        turn, a stream of another model or handle, a turn that would pass `max_samples`, a closed turn, a non-zero
+        `pause_ms` on the first segment (silence in front of a turn is the caller's to send, not part of it)."""
+        self._check_segment(st)
+        n = _segment_length(st)
+        self._plan.check_append(n, self._pause(pause_ms))
+        if not st._drained():
+            self._pool.pool.add(st)                   # (refuses another device; a member stays one)
+        s = self._plan.append(n, self._pause(pause_ms))
+        self.segments.append(st)
+        lag = self._lim[1] if self._lim else 0
+        marks = getattr(st, "marks", None)
+        self.marks.append(None if marks is None else mark_samples(
+            [self._plan.starts[s] + st.spf * int(f) for f in marks], 1, self.model_sr, self.rate, lag))
+        return s
+
+    def admit(self, requests, pauses_ms=None):
+        """`StreamPool.admit(requests)` followed by `append` in order (`pauses_ms`: None, or one per request); -> the
+        streams.  All or nothing: when a request is refused, the turn would pass `max_samples` or the first segment of
+        the turn is given a non-zero pause (as `append` refuses it), no stream stays in the pool and the turn is
+        unchanged."""
+        reqs = list(requests)
+        pauses = [0.0] * len(reqs) if pauses_ms is None else list(pauses_ms)
+        if len(pauses) != len(reqs):
+            raise ValueError("admit: one pause per request expected (%d), got %d" % (len(reqs), len(pauses)))
+        if self.closed:
+            raise ValueError("append after close()")
+        steps = [self._pause(p) for p in pauses]
+        sts = self._pool.pool.admit(reqs)
+        try:
+            trial = TurnPlan(self.model_sr, self.rate, self._plan.max_samples, self.res_type)
+            trial.starts, trial.lengths = list(self._plan.starts), list(self._plan.lengths)
+            for st, p in zip(sts, steps):
+                self._check_segment(st)
+                trial.starts.append(trial.check_append(_segment_length(st), p))
+                trial.lengths.append(_segment_length(st))
+        except ValueError:
+            for st in sts:
+                if any(st is m for m in self._pool.pool.streams):
+                    self._pool.pool.remove(st)
+            raise
+        for st, p in zip(sts, pauses):
+            self.append(st, p)
+        return sts
+
+    def close(self):
+        """No segment follows: the timeline's total is the end of the last one, and the turn finishes with the piece
+        that flushes the filter's lag."""
+        self._plan.close()
+        self._settle()
+
+    # ---- what the pool shares (PcmPool.step)
+    def _wire_chunk(self, k):
+        """Fills the `_capi.MbvTurnChunk` `k` with the wire step due now; -> [(a, b)], or None."""
+        plan = self._plan
+        for s, st in enumerate(self.segments):
+            plan.decoded(s, st.spf * _frames_decoded(st))
+        due = plan.wire_due()
+        if due is None:
+            return None
+        if self._net._handle is not self._h:
+            raise RuntimeError("the model's handle was re-created (device move) since this turn started")
+        a, count = due
+        c = k.chunk
+        c.wave, c.in_total, c.valid_samples, c.in_avail = None, plan.in_total(), None, plan.frontier()
+        c.out_first, c.out_count = a, count
+        c.peak = self._peak_in.data_ptr() if self._peak_in is not None else None
+        c.pcm, c.pcm_capacity = self.pcm.data_ptr(), self.pcm.shape[1]
+        c.running_peak, c.out_samples = self.peak.data_ptr(), None
+        s0, s1 = plan.segments_for(a, count)
+        segs = (_capi.MbvTurnSeg * max(s1 - s0, 1))()
+        for sg, s in zip(segs, range(s0, s1)):
+            sg.wave, sg.start, sg.length = self.segments[s].o.data_ptr(), plan.starts[s], plan.lengths[s]
+            sg.ramp = turn_ramp(self.ramp, plan.lengths[s])
+        k.segs, k.n_segs = segs, s1 - s0
+        return [(a, a + count)]
+
+    def _chunk_wired(self, pieces):
+        self._plan.wired(pieces[-1][1])
+        self._settle()
+
+    def _settle(self):
+        """Once the last piece is out: `valid_samples` (a device fill of a host integer), and the turn leaves the pool."""
+        plan = self._plan
+        if not plan.done or self._valid_set:
+            return
+        self._valid_set = True
+        with torch.cuda.device(self.pcm.device):
+            self.valid_samples.fill_(plan.out_total() if plan.cut is None else plan.cut)
+        self._pool.turns = [t for t in self._pool.turns if t is not self]
+        for st in self.segments:
+            if any(st is m for m in self._pool.pool.streams):
+                self._pool.pool.remove(st)
+
+    # ---- barge-in
+    def _started(self, first):
+        if any(m is None for m in self.marks):
+            return None
+        return sum(1 for ms in self.marks for m in ms[:-1] if m < first)
+
+    def revoke(self, fade_ms=5.0, at="now"):
+        """Takes the turn back (barge-in, DESIGN §7.16 over a turn): what has been handed out stays, the rest fades to
+        silence over N = round(fade_ms * rate / 1000) samples from F (`at="now"`: the samples handed out so far; an int:
+        that wire sample) and the turn, closed by this, ends at min(its length, F + N) (`valid_samples`).  The segment
+        the cut falls in decodes up to the first chunk that makes F + N outputs final (`revoke_plan` over the turn's
+        readiness), the segments behind it leave the `StreamPool` undecoded.  The bytes are bitwise
+        `service_pcm16(assemble_turn(...), fade=(F, N))`.  -> a `Revoked`; `tokens_started` counts over all segments'
+        marks (None when a segment has none).  Revoking a finished or revoked turn changes nothing."""
+        if self._revoked is not None:
+            return self._revoked
+        if not float(fade_ms) >= 0.0:
+            raise ValueError("revoke: fade_ms must be >= 0")
+        plan = self._plan
+        total_in = plan.end
+        total, E = plan.out_total(total_in), plan.out_done
+        if self.finished:
+            return Revoked(total, 0, total, self._started(total))
+        N = int(round(float(fade_ms) * 1e-3 * self.rate))
+        if at == "now":
+            F = E
+        elif isinstance(at, (int, np.integer)) and not isinstance(at, bool):
+            F = int(at)
+        else:
+            raise ValueError("revoke: at must be 'now' or a wire sample index, got %r" % (at,))
+        events = plan.revoke_events([[st.spf * (first + count) for first, count in st.schedule]
+                                     for st in self.segments]) or [(0, 0, 0)]
+        cut, last, _ = revoke_plan([r for _, _, r in events], total, E, F, N)   # (refuses F < E before anything changes)
+        s_cut, i_cut, _ = events[last]
+        for s, st in enumerate(self.segments):
+            if s == s_cut:
+                st._truncate(max(i_cut + 1, st._decoded))
+            elif s > s_cut and any(st is m for m in self._pool.pool.streams):
+                self._pool.pool.remove(st)
+        keep = s_cut + 1 if self.segments else 0
+        whole = last == len(events) - 1                       # the cut needs the whole turn: nothing is dropped
+        plan.cut_at(cut, len(self.segments) if whole else keep)
+        if not whole:
+            self.segments = self.segments[:keep]              # (`marks` keeps every segment's: the report counts over all)
+        if F < total:
+            self._fade = (F, N)
+        self._revoked = Revoked(F, N, cut, self._started(F))
+        self._settle()
+        return self._revoked
+
+
 class PcmPool:
     """The wire output of many `DecodeStream`s of one model: `step()` steps the wrapped `stream.StreamPool` (one
     `mbv_decode_chunks` call) and then turns what has become final on ALL pooled streams into int16 in ONE
@@ -1179,7 +1668,9 @@ class PcmPool:
     `revoke(st)` takes a member back: its fade rides in the tick's launch and it leaves when the fade is out.
     Members added with `loudness=` keep their running `.loudness`: ONE `mbv_loudness_chunks` launch per tick measures
     the segments completed on all of them; a tick in which none completed one, and a pool without such members,
-    launches nothing for it."""
+    launches nothing for it.
+    `add_turn(max_samples, ...)` opens a `Turn`: several utterances as one gapless wire stream, wired by `step()` in
+    ONE `mbv_resample_turns` call per tick for all turns of the pool."""
 
     def __init__(self, net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):
         _filter_code(res_type)
@@ -1190,12 +1681,13 @@ class PcmPool:
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         self.followers = []
         self.lives = []                           # the `LiveWire`s added with add_live
+        self.turns = []                           # the `Turn`s added with add_turn
         self._packed = None                       # device, the call's pieces back to back (host=True)
         self._host = self._host_np = None         # its pinned host copy, and that as a NumPy array
         self._event = None
 
     def __len__(self):
-        return len(self.followers) + len(self.lives)
+        return len(self.followers) + len(self.lives) + len(self.turns)
 
     def follower(self, st):
         for f in self.followers:
@@ -1205,6 +1697,8 @@ class PcmPool:
 
     def add(self, st, peak=None, limiter=None, loudness=None):
         _refuse_live(st)
+        if any(st is m for t in self.turns for m in t.segments):
+            raise ValueError("PcmPool.add: the stream is a segment of a turn of this pool: the turn is its wire stream")
         _limit_arg(limiter, self.rate)            # refuses bad parameters before the stream joins the pool
         _loudness_arg(loudness, peak, "PcmPool.add", stream=True)
         self.pool.add(st)                         # (refuses B > 1, another model, another device)
@@ -1278,6 +1772,18 @@ class PcmPool:
             self.lives.append(lw)
         return lw
 
+    def add_turn(self, max_samples, peak=None, limiter=None, loudness=None, ramp_ms=5.0):
+        """Opens a `Turn`: several utterances as one gapless wire stream at the pool's rates, filter and
+        encoding; -> the turn.  `max_samples` is its capacity in WIRE samples (only that int16 row is reserved; no
+        model-rate memory is).  `peak`, `limiter` and `loudness` as `add` takes them, for the whole turn; `loudness`
+        takes `Loudness(measured=...)` for the static gain only (a turn keeps no running `.loudness`).  `ramp_ms`: the
+        de-click ramp at both ends of every segment (5 ms: a convention, not a measurement; 0: none).  `step()` then
+        wires the turn along with the other members, ONE `mbv_resample_turns` call per tick for all turns, and
+        `step(streams=[turn])` names it."""
+        t = Turn(self, max_samples, peak=peak, limiter=limiter, loudness=loudness, ramp_ms=ramp_ms)
+        self.turns.append(t)
+        return t
+
     def _feed_lives(self, lives):
         """The input ranges due on all live members in one `mbv_resample_ranges` launch (one per raw rate among them)."""
         by_sr = {}
@@ -1299,13 +1805,20 @@ class PcmPool:
         decoded chunk.  `piece` is the 1-D view `follower.pcm[0, a:b]` on the device, ordered on the current stream;
         with host=True it is a NumPy int16 (uint8 in a G.711 pool) view of ONE pinned buffer that one copy and one event wait filled, valid
         until the next `step(host=True)`.  Live members first resample what has arrived in ONE `mbv_resample_ranges`
-        launch; `streams` may name them by their `LiveWire`."""
+        launch; `streams` may name them by their `LiveWire`.  A `Turn` (`add_turn`) with something due gives one
+        `(turn, first, piece)` entry; all turns of a tick share ONE `mbv_resample_turns` call, their pieces lie behind
+        the members' in the pinned buffer, and `streams` may name a turn (its segments are then stepped)."""
         net = self._net
         if streams is None:
-            members, lives = list(self.followers), list(self.lives)
+            members, lives, turns = list(self.followers), list(self.lives), list(self.turns)
         else:
-            members, lives = [], []
+            members, lives, turns = [], [], []
             for st in streams:
+                if isinstance(st, Turn):
+                    if not any(st is m for m in self.turns):
+                        raise ValueError("step(streams=...) names a turn that is not in the pool")
+                    turns.append(st)
+                    continue
                 if isinstance(st, LiveWire):
                     if not any(st is m for m in self.lives):
                         raise ValueError("step(streams=...) names a live wire that is not in the pool")
@@ -1319,7 +1832,8 @@ class PcmPool:
             self._feed_lives(lives)
         named = None
         if streams is not None:
-            named = [st for st in [f._st for f in members] + [lw.live for lw in lives] if not st._drained()]
+            named = [st for st in [f._st for f in members] + [lw.live for lw in lives]
+                     + [sg for t in turns for sg in t.segments] if not st._drained()]
         if named is None or named:
             self.pool.step(named)
         rows = []                                 # (stream, member, its table row, (final, [(a, b), ...])) per row
@@ -1328,13 +1842,24 @@ class PcmPool:
             due = w._wire_chunk(k)
             if due is not None:
                 rows.append((st, w, k, due))
+        trows = []                                # (turn, its table row, [(a, b)]) per turn with something due
+        for t in turns:
+            k = _capi.MbvTurnChunk()
+            due = t._wire_chunk(k)
+            if due is not None:
+                trows.append((t, k, due))
         out = []
-        if rows:
+        if rows or trows:
             arr = (_capi.MbvPcmChunk * len(rows))(*[k for _, _, k, _ in rows])
+            tarr = (_capi.MbvTurnChunk * len(trows))(*[k for _, k, _ in trows])
+            tlimits = [t._lim for t, _, _ in trows]
             dev = net._device()
             packed = None
             if host:
                 total, offs = pcm_chunks_plan(self.model_sr, self.rate, arr, self.res_type)
+                first_turn = total
+                t_total, toffs = turn_plan(self.model_sr, self.rate, tarr, self.res_type, tlimits) if trows else (0, [])
+                total += t_total                  # the turns' pieces lie behind the members' in the one buffer
                 if self._packed is None or self._packed.shape[0] < total:
                     cap = max(2 * total, 1 << 16)
                     self._packed = torch.empty(cap, device=dev, dtype=self._dtype)
@@ -1342,9 +1867,14 @@ class PcmPool:
                     self._host_np = self._host.numpy()
                     self._event = torch.cuda.Event()
                 packed = self._packed
-            net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
-                                      limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
-                                      fades=[w._fade for _, w, _, _ in rows])
+            if rows:
+                net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
+                                          limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
+                                          fades=[w._fade for _, w, _, _ in rows])
+            if trows:                             # every turn of the tick in ONE call
+                net.resample_turns(tarr, self.model_sr, self.rate, packed=packed[first_turn:] if host else None,
+                                   res_type=self.res_type, limits=tlimits, encoding=self.encoding,
+                                   fades=[t._fade for t, _, _ in trows])
             # the measuring members of the tick: the segments their frontier completed, in ONE launch
             measuring = []
             for _, w, k, _ in rows:
@@ -1358,6 +1888,8 @@ class PcmPool:
                     w._lseg = k1
             for _, w, _, due in rows:
                 w._chunk_wired(*due)
+            for t, _, pieces in trows:
+                t._chunk_wired(pieces)
             if host:
                 if total:
                     with torch.cuda.device(dev):
@@ -1367,9 +1899,13 @@ class PcmPool:
                 for (st, _, _, (_, pieces)), o in zip(rows, offs):
                     first = pieces[0][0]
                     out += [(st, a, self._host_np[o + a - first:o + b - first]) for a, b in pieces]
+                for (t, _, pieces), o in zip(trows, toffs):
+                    out += [(t, a, self._host_np[first_turn + o:first_turn + o + b - a]) for a, b in pieces]
             else:
                 for st, w, _, (_, pieces) in rows:
                     out += [(st, a, w.pcm[0, a:b]) for a, b in pieces]
+                for t, _, pieces in trows:
+                    out += [(t, a, t.pcm[0, a:b]) for a, b in pieces]
         self.followers = [f for f in self.followers if f._wired < len(f._st.schedule)]
         self.lives = [lw for lw in self.lives if not lw._plan.wire_done]
         return out

@@ -1155,7 +1155,11 @@ int mbv_conv_plan(const mbv_conv_desc *d, int32_t out[8]);
  *   mbv_op_sdp_spline       Flip + inverse rational-quadratic spline + mask in place on z [B, 2, T]; h [B, 29, T]
  *   mbv_op_sdp_logw         logw [B, T] = (z[:, 1] - m[0]) * exp(-logs[0]) * mask
  *   mbv_op_sdp_noise        z [n] = noise * scale, or zeros when noise is NULL
- *   mbv_op_chan_add         x [B, C, T] += v [B, C] */
+ *   mbv_op_chan_add         x [B, C, T] += v [B, C]
+ *   mbv_op_istft_single     the single-band waveform tail by itself: x_post [B, 18, frames] (log-magnitude | phase
+ *                           pre-activations; prescaled != 0: rows already times log2(e) | 1 / (2 pi), as the packed
+ *                           conv_post leaves them) -> o [B, 4 (frames - 1)], spec / phase [B, 9, frames] or NULL;
+ *                           frames >= 2; exact or hardware transcendentals as the handle's "istft_exact" option says */
 int mbv_op_embed(mbv_model *m, const int64_t *ids, const int64_t *lengths, const float *emb, float *x, int32_t *lens32,
                  int32_t *bad, int B, int T, int H, int n_vocab, void *stream);
 int mbv_op_layernorm(mbv_model *m, const float *a, const float *r, const float *gamma, const float *beta, float *y,
@@ -1186,6 +1190,8 @@ int mbv_op_sdp_logw(mbv_model *m, const float *z, const float *mean, const float
                     float *logw, int B, int T, void *stream);
 int mbv_op_sdp_noise(mbv_model *m, const float *noise, float scale, float *z, int64_t n, void *stream);
 int mbv_op_chan_add(mbv_model *m, float *x, const float *v, int B, int C, int T, void *stream);
+int mbv_op_istft_single(mbv_model *m, const float *x_post, int B, int frames, int prescaled, float *o, float *spec,
+                        float *phase, void *stream);
 /* the two kernels of mbv_align by themselves (align.hip).
  *   neg_cent: z_p [B, I, T_t], m_p / logs_p [B, I, T_s] (dense), t_y32 / t_x32 int32 [B] -> value [B, T_t, T_s]
  *             (cells outside [t_y, t_x) are not written; lengths are clamped to the tensors)

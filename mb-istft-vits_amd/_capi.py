@@ -27,7 +27,7 @@ SYMBOLS = [
     "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
     "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
     "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
-    "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add",
+    "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add", "mbv_op_istft_single",
     "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
     "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
     "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
@@ -313,6 +313,7 @@ def lib():
     L.mbv_op_sdp_logw.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.mbv_op_sdp_noise.argtypes = [vp, vp, f32, vp, C.c_int64, vp]
     L.mbv_op_chan_add.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    L.mbv_op_istft_single.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.mbv_align.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, C.POINTER(MbvAlignOutputs), vp, vp]
     L.mbv_set_durations.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]

@@ -4547,8 +4547,8 @@ int64_t mbv_read_stage(mbv_model* m, const char* name, float* dst, int64_t capac
 int mbv_op_rel_attention(mbv_model* m, const float* qkv, const float* emb_k, const float* emb_v, const int64_t* lengths,
                          float* o, int B, int H, int n_heads, int T, void* stream) {
   if (!m) return 1;
-  if (!qkv || !emb_k || !emb_v || !lengths || !o || B <= 0 || T <= 0 || n_heads <= 0 || H % n_heads || (H / n_heads) % 2 || H / n_heads > 96)
-    return m->fail("mbv_op_rel_attention: bad arguments (head dimension must be even and <= 96)");
+  if (!qkv || !emb_k || !emb_v || !lengths || !o || B <= 0 || T <= 0 || n_heads <= 0 || H % n_heads || (H / n_heads) % 2 || H / n_heads > 128)
+    return m->fail("mbv_op_rel_attention: bad arguments (head dimension must be even and <= 128, as in mbv_create)");
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
   int* lens32 = nullptr;
@@ -4739,6 +4739,20 @@ int mbv_op_chan_add(mbv_model* m, float* x, const float* v, int B, int C, int T,
   OP_REFUSE(B <= 0 || C <= 0 || T <= 0 || B > kGridYZ || C > kGridYZ, "B, C in [1, 65535] and T > 0 required");
   OP_BEGIN();
   launch_chan_add(x, v, B, C, T, s);
+  OP_END();
+}
+
+int mbv_op_istft_single(mbv_model* m, const float* x_post, int B, int frames, int prescaled, float* o, float* spec,
+                        float* phase, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!x_post || !o, "NULL argument");
+  OP_REFUSE(B <= 0 || frames < 2, "B > 0 and frames >= 2 required");
+  OP_REFUSE((int64_t)B * 18 * frames * 4 >= (1LL << 31), "x_post must stay below 2 GiB");
+  OP_BEGIN();
+  IstftSbArgs a{};
+  a.x_post = x_post; a.o = o; a.spec = spec; a.phase = phase;
+  a.B = B; a.F = frames; a.exact_math = m->exact_math; a.prescaled = prescaled != 0;
+  launch_istft_single(a, s);
   OP_END();
 }
 

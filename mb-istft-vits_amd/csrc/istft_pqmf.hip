@@ -52,10 +52,10 @@ __device__ constexpr float HANN16[16] = {
     0.5f, 0.30865828381745514f, 0.14644660940672624f, 0.03806023374435663f};
 // squared window, for per-lane (runtime-indexed) envelope sums at the signal edges
 __device__ const float WSQ16[16] = {
-    0.0f, 0.0014485813926750633f, 0.021446609406726238f, 0.095269936190567076f,
-    0.25f, 0.47795336526437190f, 0.72855339059327373f, 0.92533011387037270f,
-    1.0f, 0.92533011387037270f, 0.72855339059327373f, 0.47795336526437190f,
-    0.25f, 0.095269936190567076f, 0.021446609406726238f, 0.0014485813926750633f};
+    0.0f, 0.0014485813926750633f, 0.021446609406726238f, 0.095269936169136614f,
+    0.25f, 0.47795336853422657f, 0.72855339059327373f, 0.92532811390396186f,
+    1.0f, 0.92532811390396186f, 0.72855339059327373f, 0.47795336853422657f,
+    0.25f, 0.095269936169136614f, 0.021446609406726238f, 0.0014485813926750633f};
 
 // Fixed PQMF bank (pqmf.py:15-75: taps 62, cutoff 0.15, Kaiser beta 9), factorised:
 //   4 h_k[j] = PQMF_G[j] * PQMF_C[k][j mod 8],  PQMF_C[k][q] = cos((2k+1)(pi/8)(q - 30.5) - (-1)^k pi/4),

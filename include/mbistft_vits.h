@@ -829,6 +829,57 @@ typedef struct mbv_mark_row { int64_t *marks; int32_t count; int32_t reserved; }
 int mbv_token_marks(mbv_model *m, int64_t *marks, int64_t marks_stride, void *stream);
 int mbv_token_marks_rows(mbv_model *m, int slot, const mbv_mark_row *rows_host, int n, void *stream);
 
+/* ---- per-token prosody: rate, pauses and fit-to-length on the predicted durations ------------------------------
+ * After an encode, replace the durations the length regulator will use by
+ *     w_t = ceilf(expf(logw_t) * fl32(s_t * f)) + extra_t        for t < x_lengths[b]
+ * from the logw the encode left (the duration predictor's or the SDP's): the arithmetic of the encode's own
+ * durations with a scale s_t PER TOKEN (rate), extra_t further frames of the token's own prior (a pause of known
+ * length on a blank or "sp" token), and one factor f per row that makes the row fit a frame count.  What follows
+ * (mbv_token_marks, mbv_synthesize, their _rows forms) proceeds unchanged: a token's span includes its extras.
+ *
+ *   scale   DEVICE fp32, finite and >= 0; 0 drops the token.  NULL: s_t = the length_scale given to the encode.  With
+ *           a table that length_scale must have been 1.
+ *   extra   DEVICE int32, >= 0, or NULL.
+ *   fit     frames >= 1 and 0 < lo <= hi < inf: f = the LARGEST fp32 in [lo, hi] with D(f) <= frames, where
+ *           D(f) = sum over t < x_lengths[b] of w_t.  D is non-decreasing in f and positive floats order like their
+ *           bit patterns, so a bisection on the bit pattern finds f exactly, in at most 32 evaluations of D.  If even
+ *           D(lo) > frames: f = lo and status = 1 (the row did not fit; not an error).  If D(hi) <= frames: f = hi.
+ *           Nothing is padded.  During the search a token counts min(frames, 2^20) and the sums are 64-bit.
+ *           frames == 0 in a HOST fit entry: this row is not fitted (f = 1, status 0; s_t is used as it is).
+ * The range rules of mbv_encode hold for a token's total (2^20 frames) and a row's (2^30); a negative, infinite or NaN
+ * scale, or a negative extra, below x_lengths[b] flags the row the same way: y_lengths = -1.  The encode's own flags
+ * are kept.  One launch, no synchronisation, no part in mbv_encoder_runs; mbv_shape_runs counts these launches.
+ * Refused before any launch: bounds not 0 < lo <= hi < inf, frames < 0 (or < 1 where a row asks for a fit), a scale
+ * table after an encode whose length_scale was not 1, and a call with nothing to do.
+ *
+ * mbv_shape_durations: after mbv_encode; scale / extra [B, T] or NULL, fit_host HOST [B] or NULL, fit_out DEVICE [B]
+ * or NULL (8 bytes a row, so that it can stand next to y_lengths in one read-back), y_lengths_out DEVICE int64 [B].
+ * Afterwards mbv_read_stage knows "fit_scale" [B] and "fit_status" [B] (0.0 / 1.0).
+ *
+ * mbv_shape_durations_rows: after mbv_encode_rows on `slot`, one table row per encoded row (n = the run's rows), in
+ * ONE launch for the rows that carry a control; the others keep their durations.  scale / extra are the row's own
+ * [t_text] tensors; y_lengths_out is the run's array as given to mbv_encode_rows.  rows_host is HOST memory.
+ *
+ * mbv_op_shape_durations: the kernel by itself on a caller's logw [B, T] and lens32 [B] (tests), like
+ * mbv_op_durations; `scalar` is s_t without a table.  Synchronises the stream. */
+typedef struct mbv_fit { int64_t frames; float lo, hi; } mbv_fit;
+typedef struct mbv_fit_result { float scale; int32_t status; } mbv_fit_result;
+typedef struct mbv_shape_row {
+  const float *scale;            /* DEVICE [t_text] or NULL */
+  const int32_t *extra;          /* DEVICE [t_text] or NULL */
+  mbv_fit fit;                   /* frames == 0: no fit */
+  mbv_fit_result *fit_out;       /* DEVICE, or NULL */
+} mbv_shape_row;
+int mbv_shape_durations(mbv_model *m, const float *scale, const int32_t *extra, const mbv_fit *fit_host, int B, int T,
+                        mbv_fit_result *fit_out, int64_t *y_lengths_out, void *stream);
+int mbv_shape_durations_rows(mbv_model *m, int slot, const mbv_shape_row *rows_host, int n, int64_t *y_lengths_out,
+                             void *stream);
+int mbv_op_shape_durations(mbv_model *m, const float *logw, const int32_t *lens, const float *scale,
+                           const int32_t *extra, float scalar, const mbv_fit *fit_host, float *w_ceil, int32_t *cum,
+                           int32_t *ylen32, int64_t *ylen64, const int32_t *bad, mbv_fit_result *fit_out, int B, int T,
+                           void *stream);
+int64_t mbv_shape_runs(mbv_model *m);
+
 /* ---- loudness: ITU-R BS.1770 integrated loudness of a mono waveform, on the device ------------------------------
  * K-weighting (two cascaded biquads, zero state at sample 0), segments of H = (rate + 5) / 10 samples (100 ms; a half
  * rounds up), blocks of four segments (400 ms, 75 % overlap), the absolute gate at -70 LKFS and the relative gate 10 LU
@@ -1046,7 +1097,8 @@ int mbv_convert_ranges(mbv_model *m, const mbv_convert_range *rows_host, int n, 
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"
  * [B,1,T], "x_post" [B,72,F], "dec_conv_pre", "dec_up_0", "dec_res_0",
  * "dec_up_1", "dec_res_1"; after mbv_convert_rows / mbv_convert_ranges "convert_ypad" [B, cin_pad, T], the posterior encoder's
- * channel-padded input as the spectrogram kernel wrote it (cin_pad = spec_channels rounded up to 32).  Returns the element count, or < 0 on error;
+ * channel-padded input as the spectrogram kernel wrote it (cin_pad = spec_channels rounded up to 32); after
+ * mbv_shape_durations "fit_scale" and "fit_status" [B].  Returns the element count, or < 0 on error;
  * dst == NULL only queries the count. */
 int64_t mbv_read_stage(mbv_model *m, const char *name, float *dst, int64_t capacity,
                        void *stream);

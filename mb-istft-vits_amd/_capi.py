@@ -44,6 +44,7 @@ SYMBOLS = [
     "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
     "mbv_loudness_runs",
     "mbv_turn_plan", "mbv_resample_turns",
+    "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
 ]
 
 
@@ -119,6 +120,22 @@ TURN_MAX_SEGS = 4096            # MBV_TURN_MAX_SEGS
 class MbvMarkRow(C.Structure):
     """mbv_mark_row of include/mbistft_vits.h (mbv_token_marks_rows); marks None = this row has none."""
     _fields_ = [("marks", C.c_void_p), ("count", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MbvFit(C.Structure):
+    """mbv_fit of include/mbistft_vits.h (the prosody entries); frames 0 = this row is not fitted."""
+    _fields_ = [("frames", C.c_int64), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class MbvShapeRow(C.Structure):
+    """mbv_shape_row of include/mbistft_vits.h (mbv_shape_durations_rows); all None / 0 = this row keeps its durations."""
+    _fields_ = [("scale", C.c_void_p), ("extra", C.c_void_p), ("fit", MbvFit), ("fit_out", C.c_void_p)]
+
+
+def fit_result(word):
+    """One int64 of a read-back that holds an `mbv_fit_result` -> (scale, status)."""
+    import struct
+    return struct.unpack("<fi", struct.pack("<q", int(word)))
 
 
 class MbvLoudnessChunk(C.Structure):
@@ -321,8 +338,8 @@ def lib():
     # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six and the
-    # turns' two may be absent there, and calling one then raises AttributeError.
+    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
+    # turns' two and prosody's four may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -341,7 +358,8 @@ def lib():
                 "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
                 "mbv_token_marks", "mbv_token_marks_rows",
                 "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
-                "mbv_loudness_runs", "mbv_turn_plan", "mbv_resample_turns") if os.environ.get("MBV_LIB") else ()
+                "mbv_loudness_runs", "mbv_turn_plan", "mbv_resample_turns",
+                "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -440,6 +458,13 @@ def lib():
         L.mbv_turn_plan.restype = C.c_int64
         L.mbv_resample_turns.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit), C.POINTER(MbvPcmFade), i32,
                                          i32, i32, i32, i32, vp, C.c_int64, vp]
+    if hasattr(L, "mbv_shape_durations") or not optional:
+        L.mbv_shape_durations.argtypes = [vp, vp, vp, C.POINTER(MbvFit), i32, i32, vp, vp, vp]
+        L.mbv_shape_durations_rows.argtypes = [vp, i32, C.POINTER(MbvShapeRow), i32, vp, vp]
+        L.mbv_op_shape_durations.argtypes = [vp, vp, vp, vp, vp, f32, C.POINTER(MbvFit), vp, vp, vp, vp, vp, vp, i32, i32,
+                                             vp]
+        L.mbv_shape_runs.argtypes = [vp]
+        L.mbv_shape_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -54,6 +54,9 @@ struct EncState {
   float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
   int *lens32 = nullptr, *cum = nullptr, *ylen32 = nullptr;
   int* bad32 = nullptr;         // per-utterance flags (invalid id / length / sid)
+  float* fit = nullptr;         // [2, B]: the factor and the status mbv_shape_durations left (stages fit_scale / fit_status)
+  std::vector<float> scales;    // the length_scale the encode took: one value, or one per row (mbv_encode_rows)
+  std::vector<int> t_text;      // mbv_encode_rows: every row's own text length (its tensors end there)
 };
 
 // one launch of the decoder, as integers (decoder_table)
@@ -149,6 +152,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   char* noise_tab = nullptr; size_t noise_tab_bytes = 0;   // mbv_randn_blocks' table: its own buffer, so that a fill
                                                            // between an encode and its synthesize disturbs no scratch
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
+  int64_t shape_runs = 0;          // launches of the prosody kernel (mbv_shape_runs)
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
@@ -2252,6 +2256,7 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
         m->bad32 = b.take<int>(B);
         m->gvec = b.take<float>((size_t)B * (gin ? gin : 1));
         dpc = b.take<float>((size_t)B * H);
+        m->fit = b.take<float>((size_t)2 * B);
         if (rows_host) rows = b.take<AdmitEncRow>(B);
         if (c.use_sdp) {
           cond = b.take<float>(BT * H);
@@ -2272,6 +2277,10 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
       return AdmitEncRow{k.length_scale, k.noise_scale_w, k.noise_w, k.durations, k.durations_dtype, k.t_text};
     });
   m->stages.clear();
+  m->scales.assign(rows_host ? (size_t)B : 1, length_scale);
+  m->t_text.assign(rows_host ? (size_t)B : 0, 0);
+  if (rows_host)
+    for (int i = 0; i < B; ++i) { m->scales[i] = rows_host[i].length_scale; m->t_text[i] = rows_host[i].t_text; }
 
   ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
   m->ev = m->evr[m->ticket % mbv_model::kEvRing];
@@ -3148,6 +3157,97 @@ int mbv_token_marks_rows(mbv_model* m, int slot, const mbv_mark_row* rows_host, 
   HIPCHK(m, hipGetLastError());
   return 0;
 }
+
+namespace {
+// what a fit entry must be; null: fine (frames == 0: the row is not fitted)
+const char* fit_error(const mbv_fit& f) {
+  if (f.frames < 0) return "fit: frames must be >= 1 (0: no fit)";
+  if (f.frames > 0 && !(f.lo > 0.f && f.lo <= f.hi && f.hi < INFINITY)) return "fit: the bounds must be 0 < lo <= hi < inf";
+  return nullptr;
+}
+// the fit table of the batched forms (only frames / lo / hi are read), into scrB; *out = null when no row is fitted
+int upload_fit(mbv_model* m, const mbv_fit* fit_host, int B, const ShapeRow** out, hipStream_t s) {
+  *out = nullptr;
+  bool any = false;
+  for (int b = 0; fit_host && b < B; ++b) any = any || fit_host[b].frames > 0;
+  if (!any) return 0;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, (size_t)B * sizeof(ShapeRow))) return 1;
+  ShapeRow* t = reinterpret_cast<ShapeRow*>(m->scrB);
+  upload_rows<kShapeChunk>(B, t, s, [&](size_t b) {
+    ShapeRow r{};
+    r.frames = fit_host[b].frames; r.lo = fit_host[b].lo; r.hi = fit_host[b].hi;
+    return r;
+  });
+  *out = t;
+  return 0;
+}
+}  // namespace
+
+int mbv_shape_durations(mbv_model* m, const float* scale, const int32_t* extra, const mbv_fit* fit_host, int B, int T,
+                        mbv_fit_result* fit_out, int64_t* y_lengths_out, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_shape_durations";
+  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
+  if (!y_lengths_out) return m->fail("%s: NULL argument", who);
+  if (B != m->B || T != m->T) return m->fail("%s: the tables must be [%d, %d] as the encoded batch, got [%d, %d]", who, m->B, m->T, B, T);
+  if (m->scales.size() != 1) return m->fail("%s: the last encode was mbv_encode_rows (use mbv_shape_durations_rows)", who);
+  bool any_fit = false;
+  for (int b = 0; fit_host && b < B; ++b) {
+    if (const char* why = fit_error(fit_host[b])) return m->fail("%s: row %d: %s", who, b, why);
+    any_fit = any_fit || fit_host[b].frames > 0;
+  }
+  if (!scale && !extra && !any_fit) return m->fail("%s: nothing to do (no scale table, no extra frames, no fit)", who);
+  if (scale && m->scales[0] != 1.f) return m->fail("%s: a scale table needs an encode with length_scale 1 (it was %g)", who, m->scales[0]);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  const ShapeRow* fit = nullptr;
+  if (upload_fit(m, fit_host, B, &fit, s)) return 1;
+  launch_shape_durations(m->logw, m->lens32, scale, extra, m->scales[0], fit, m->w_ceil, m->cum, m->ylen32, y_lengths_out,
+                         m->bad32, m->fit, reinterpret_cast<FitOut*>(fit_out), B, T, s);
+  ++m->shape_runs;
+  HIPCHK(m, hipGetLastError());
+  m->stages["fit_scale"] = {m->fit, (int64_t)B};
+  m->stages["fit_status"] = {m->fit + B, (int64_t)B};
+  return 0;
+}
+
+int mbv_shape_durations_rows(mbv_model* m, int slot, const mbv_shape_row* rows_host, int n, int64_t* y_lengths_out,
+                             void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_shape_durations_rows";
+  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
+    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
+  const mbv_model::EncSlot& sl = m->slots[slot];
+  const int B = sl.enc.B, T = sl.enc.T;
+  if (!rows_host || !y_lengths_out || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
+  if ((int)sl.enc.scales.size() != B) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot);
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i) {
+    const mbv_shape_row& k = rows_host[i];
+    if (const char* why = fit_error(k.fit)) return m->fail("%s: row %d: %s", who, i, why);
+    if (k.scale && sl.enc.scales[i] != 1.f)
+      return m->fail("%s: row %d: a scale table needs a row encoded with length_scale 1 (it was %g)", who, i, sl.enc.scales[i]);
+    if (k.scale || k.extra || k.fit.frames > 0) live.push_back(i);
+  }
+  if (live.empty()) return m->fail("%s: nothing to do (no row has a scale table, extra frames or a fit)", who);
+  DEVICE_GUARD(m);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(ShapeRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  ShapeRow* rows = reinterpret_cast<ShapeRow*>(m->scrB);
+  // (t_text: the row's tensors end there; the kernel also stops at the row's x_length)
+  upload_rows<kShapeChunk>(live.size(), rows, s, [&](size_t j) {
+    const mbv_shape_row& k = rows_host[live[j]];
+    return ShapeRow{k.scale, k.extra, reinterpret_cast<FitOut*>(k.fit_out), k.fit.frames, k.fit.lo, k.fit.hi,
+                    sl.enc.scales[live[j]], live[j], sl.enc.t_text[live[j]], 0};
+  });
+  launch_shape_durations_rows(sl.enc.logw, sl.enc.lens32, rows, (int)live.size(), sl.enc.w_ceil, sl.enc.cum, sl.enc.ylen32,
+                              y_lengths_out, sl.enc.bad32, T, s);
+  ++m->shape_runs;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_shape_runs(mbv_model* m) { return m ? m->shape_runs : -1; }
 
 int mbv_istft_finalize(mbv_model* m, const float* spec, const float* phase, int B, int frames,
                        float* o, float* o_mb, void* stream) {
@@ -4611,6 +4711,29 @@ int mbv_op_durations(mbv_model* m, const float* h, const float* w, const float* 
   OP_REFUSE(!(length_scale > 0.f) || !(length_scale < INFINITY), "length_scale must be positive and finite");
   OP_BEGIN();
   launch_durations(h, w, bias, lens, length_scale, logw, w_ceil, cum, ylen32, ylen64, bad, B, C, T, s);
+  OP_END();
+}
+
+int mbv_op_shape_durations(mbv_model* m, const float* logw, const int32_t* lens, const float* scale, const int32_t* extra,
+                           float scalar, const mbv_fit* fit_host, float* w_ceil, int32_t* cum, int32_t* ylen32,
+                           int64_t* ylen64, const int32_t* bad, mbv_fit_result* fit_out, int B, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!logw || !lens || !w_ceil || !cum || !ylen32, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0, "B and T must be > 0");
+  OP_REFUSE(!(scalar >= 0.f) || !(scalar < INFINITY), "scalar must be finite and >= 0");
+  OP_REFUSE(scale && scalar != 1.f, "a scale table needs scalar 1");
+  bool any_fit = false;
+  for (int b = 0; fit_host && b < B; ++b) {
+    if (const char* why = fit_error(fit_host[b])) return m->fail("%s: row %d: %s", __func__, b, why);
+    any_fit = any_fit || fit_host[b].frames > 0;
+  }
+  OP_REFUSE(!scale && !extra && !any_fit, "nothing to do (no scale table, no extra frames, no fit)");
+  OP_BEGIN();
+  const ShapeRow* fit = nullptr;
+  if (upload_fit(m, fit_host, B, &fit, s)) return 1;
+  launch_shape_durations(logw, lens, scale, extra, scalar, fit, w_ceil, cum, ylen32, ylen64, bad, nullptr,
+                         reinterpret_cast<FitOut*>(fit_out), B, T, s);
+  ++m->shape_runs;
   OP_END();
 }
 

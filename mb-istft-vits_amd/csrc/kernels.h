@@ -224,6 +224,26 @@ void launch_durations(const float* h, const float* w, const float* b, const int*
                       int64_t* ylen64, const int* bad, int B, int C, int T, hipStream_t s);
 // (w == nullptr: h is logw itself, [B, T] — the SDP path)
 // a token of >= 2^20 frames (or inf / NaN) or an utterance of > 2^30: ylen32 = 1, ylen64 = -1 (ops.hip)
+// per-token prosody (ops.hip shape_durations_kernel): w_t = ceilf(expf(logw_t) * fl32(s_t * f)) + extra_t from the logw
+// a durations launch left; replaces w_ceil (fp32 totals), cum, ylen32 and ylen64 (the range rules and the -1 marker
+// above; a negative / infinite / NaN scale or a negative extra below the row's length flags it too).
+// A table row (in the arena, upload_rows).  launch_shape_durations reads only frames / lo / hi of row b from it (null
+// table: no row is fitted); launch_shape_durations_rows works on the rows the table names, one block each.
+struct FitOut { float scale; int32_t status; };          // mbv_fit_result
+struct ShapeRow {
+  const float* scale;          // this row's scale per token [t_text], or null: `scalar` for every token
+  const int* extra;            // extra frames per token [t_text], or null
+  FitOut* fit_out;             // where the row's factor and status go, or null
+  int64_t frames;              // fit: the frame count to stay within; 0: no fit (f = 1 is not applied at all)
+  float lo, hi, scalar;
+  int32_t row, t_text, pad_;
+};
+constexpr int kShapeChunk = 64;    // rows per upload_rows launch: 3.5 KiB of kernel arguments
+void launch_shape_durations(const float* logw, const int* lens, const float* scale, const int* extra, float scalar,
+                            const ShapeRow* fit, float* w_ceil, int* cum, int* ylen32, int64_t* ylen64, const int* bad,
+                            float* fit_stage, FitOut* fit_out, int B, int T, hipStream_t s);
+void launch_shape_durations_rows(const float* logw, const int* lens, const ShapeRow* rows, int n, float* w_ceil,
+                                 int* cum, int* ylen32, int64_t* ylen64, const int* bad, int T, hipStream_t s);
 // token marks: dst[b stride + j] = j ? cum[b, j - 1] : 0 for j < count (<= T + 1); with a table (in the arena,
 // upload_rows) row b writes rows[b].count entries to rows[b].dst instead, none where that is null.  One launch.
 struct MarkRow {

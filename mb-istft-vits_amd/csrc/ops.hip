@@ -1,5 +1,6 @@
 // Small memory-bound pieces of the path: embedding, channel LayerNorm,
-// durations (proj + exp/ceil/cumsum), length regulation, speaker conditioning.
+// durations (proj + exp/ceil/cumsum), per-token prosody (scale / extra frames / fit-to-length on those durations),
+// length regulation, speaker conditioning.
 #include "kernels.h"
 
 namespace mbv {
@@ -227,6 +228,169 @@ void launch_durations_rows(const float* h, const float* w, const float* b, const
                            int C, int T, hipStream_t s) {
   hipLaunchKernelGGL(durations_kernel<true>, dim3(B), dim3(256), 0, s, h, w, b, lens, 0.f, rows, logw, w_ceil, cum,
                      ylen32, ylen64, bad, C, T);
+}
+
+// ---------------------------------------------------------------------------
+// Per-token prosody (mbv_shape_durations / mbv_shape_durations_rows / mbv_op_shape_durations): the durations of
+// durations_kernel again, from the logw it left, with a scale PER TOKEN, extra frames per token and, for rows that
+// ask for it, one global factor f that makes the row fit a frame count:
+//   w_t = ceilf(expf(logw_t) * fl32(s_t * f)) + extra_t         (two separate fp32 multiplications, then the ceil)
+//   D(f) = sum over t < len of w_t;  f = the largest fp32 in [lo, hi] with D(f) <= frames
+// D is non-decreasing in f (every step is monotone in fp32) and positive floats order like their bit patterns, so
+// the search is a bisection on the bit pattern: D(hi) first, then at most 31 halvings of [bits(lo) - 1, bits(hi)],
+// where bits(lo) - 1 stands for "not even lo fits" (status 1, f = lo).  During the search a token counts
+// min(frames, 2^20) and the sums are 64-bit; the final pass applies the range rules of durations_kernel to the
+// token's total (a negative, infinite or NaN scale and a negative extra flag the row as well) and writes w_ceil
+// (fp32 totals, extras included), cum (chunked scan with carry), ylen32 and ylen64.
+// One block per row.  expf(logw_t) and s_t of the first kShapeReg * 256 tokens stay in registers across the
+// evaluations; a longer text recomputes the rest from memory.
+// ROWS: block i works on row rows[i].row of the run with that row's own [t_text] tensors; rows without controls are
+// not in the table.  Else block b is row b, scale / extra are [B, T], and `rows` (or null: no row fits) holds the
+// fit parameters of row b.
+// ---------------------------------------------------------------------------
+constexpr int kShapeReg = 8;
+
+__device__ __forceinline__ long long shape_block_sum(long long v, long long* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();                                     // (red is free again: everyone read the last result)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+__device__ __forceinline__ long long shape_count(float e, float s, float f, int extra) {
+  const float wc = ceilf(e * (s * f));
+  long long d = wc < kMaxTokenFrames ? (wc > 0.f ? (long long)wc : 0) : (long long)kMaxTokenFrames;   // (NaN: 2^20)
+  return d + (extra > 0 ? extra : 0);
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(256) void shape_durations_kernel(const float* __restrict__ logw, const int* __restrict__ lens,
+                                                              const float* scale, const int* extra, float scalar,
+                                                              const ShapeRow* __restrict__ rows, float* w_ceil, int* cum,
+                                                              int* ylen32, int64_t* ylen64, const int* bad,
+                                                              float* fit_stage, FitOut* fit_out, int T) {
+  __shared__ int scan[256];
+  __shared__ long long red[4];
+  __shared__ int carry_s, over_s;
+  const int tid = threadIdx.x;
+  int b = blockIdx.x;
+  int len;
+  long long frames = 0;
+  float lo = 1.f, hi = 1.f;
+  if (ROWS) {
+    const ShapeRow r = rows[blockIdx.x];
+    b = r.row;
+    len = lens[b] < r.t_text ? lens[b] : r.t_text;      // never read past the row's own tensors
+    scale = r.scale; extra = r.extra; scalar = r.scalar;
+    frames = r.frames; lo = r.lo; hi = r.hi;
+    fit_out = r.fit_out;
+  } else {
+    len = lens[b];
+    if (scale) scale += (int64_t)b * T;
+    if (extra) extra += (int64_t)b * T;
+    if (rows) { frames = rows[b].frames; lo = rows[b].lo; hi = rows[b].hi; }
+    if (fit_out) fit_out += b;
+  }
+  const float* lw = logw + (int64_t)b * T;
+  float e_r[kShapeReg], s_r[kShapeReg];
+  int x_r[kShapeReg];
+#pragma unroll
+  for (int k = 0; k < kShapeReg; ++k) {
+    const int t = k * 256 + tid;
+    e_r[k] = 0.f; s_r[k] = 0.f; x_r[k] = 0;
+    if (t < len) {
+      e_r[k] = expf(lw[t]);
+      s_r[k] = scale ? scale[t] : scalar;
+      x_r[k] = extra ? extra[t] : 0;
+    }
+  }
+  float f = 1.f;
+  int status = 0;
+  if (frames > 0) {
+    auto D = [&](float ff) {
+      long long v = 0;
+#pragma unroll
+      for (int k = 0; k < kShapeReg; ++k)
+        if (k * 256 + tid < len) v += shape_count(e_r[k], s_r[k], ff, x_r[k]);
+      for (int t = kShapeReg * 256 + tid; t < len; t += 256)
+        v += shape_count(expf(lw[t]), scale ? scale[t] : scalar, ff, extra ? extra[t] : 0);
+      return shape_block_sum(v, red);
+    };
+    f = hi;
+    if (D(hi) > frames) {
+      unsigned a = __float_as_uint(lo) - 1u, z = __float_as_uint(hi);      // D(a) fits (a < bits(lo): by decree), D(z) does not
+      while (z - a > 1u) {
+        const unsigned mid = a + (z - a) / 2u;
+        if (D(__uint_as_float(mid)) <= frames) a = mid; else z = mid;     // (uniform over the block)
+      }
+      if (a < __float_as_uint(lo)) { f = lo; status = 1; }
+      else f = __uint_as_float(a);
+    }
+  }
+  if (tid == 0) { carry_s = 0; over_s = 0; }
+  __syncthreads();
+  for (int t0 = 0; t0 < T; t0 += 256) {
+    const int t = t0 + tid;
+    int d = 0;
+    if (t < T) {
+      float wt = 0.f;
+      if (t < len) {
+        float e = 0.f, s = 0.f;
+        int x = 0;
+        bool reg = false;
+#pragma unroll
+        for (int k = 0; k < kShapeReg; ++k)
+          if (t0 == k * 256) { e = e_r[k]; s = s_r[k]; x = x_r[k]; reg = true; }
+        if (!reg) { e = expf(lw[t]); s = scale ? scale[t] : scalar; x = extra ? extra[t] : 0; }
+        const float sf = frames > 0 ? s * f : s;
+        const float wc = ceilf(e * sf);
+        wt = wc + (float)x;
+        // the scale itself must be a finite number >= 0, the extra >= 0, and the token's total in range
+        if (s >= 0.f && s < INFINITY && x >= 0 && wc < kMaxTokenFrames && wt < kMaxTokenFrames) d = (int)wc + x;
+        else over_s = 1;
+      }
+      w_ceil[(int64_t)b * T + t] = wt;
+    }
+    scan[tid] = d;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {          // Hillis-Steele inclusive scan
+      int v = tid >= off ? scan[tid - off] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    const int carry = carry_s;
+    if (t < T) cum[(int64_t)b * T + t] = carry + scan[tid];
+    __syncthreads();
+    if (tid == 255) {
+      int c = carry + scan[255];
+      if (c > kMaxTotalFrames) { over_s = 1; c = kMaxTotalFrames; }
+      carry_s = c;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int total = (carry_s < 1 || over_s) ? 1 : carry_s;
+    ylen32[b] = total;
+    if (ylen64) ylen64[b] = ((bad && bad[b]) || over_s) ? -1 : total;
+    if (fit_stage) { fit_stage[b] = f; fit_stage[gridDim.x + b] = (float)status; }
+    if (fit_out) { fit_out->scale = f; fit_out->status = status; }
+  }
+}
+
+void launch_shape_durations(const float* logw, const int* lens, const float* scale, const int* extra, float scalar,
+                            const ShapeRow* fit, float* w_ceil, int* cum, int* ylen32, int64_t* ylen64, const int* bad,
+                            float* fit_stage, FitOut* fit_out, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(shape_durations_kernel<false>, dim3(B), dim3(256), 0, s, logw, lens, scale, extra, scalar, fit,
+                     w_ceil, cum, ylen32, ylen64, bad, fit_stage, fit_out, T);
+}
+
+void launch_shape_durations_rows(const float* logw, const int* lens, const ShapeRow* rows, int n, float* w_ceil,
+                                 int* cum, int* ylen32, int64_t* ylen64, const int* bad, int T, hipStream_t s) {
+  hipLaunchKernelGGL(shape_durations_kernel<true>, dim3(n), dim3(256), 0, s, logw, lens, nullptr, nullptr, 1.f, rows,
+                     w_ceil, cum, ylen32, ylen64, bad, nullptr, nullptr, T);
 }
 
 // Token marks (mbv_token_marks / mbv_token_marks_rows): the EXCLUSIVE prefix sums of the durations the length regulator

@@ -202,6 +202,8 @@ def sharded_infer(net, x, x_lengths, sid=None, noise_scale=1, length_scale=1, ma
         raise ValueError("batch %d smaller than world size %d" % (B, world))
     if overlap not in (None, "next", "halves"):
         raise ValueError("overlap must be None, 'next' or 'halves'")
+    if torch.is_tensor(length_scale) and length_scale.numel() > 1:    # same test on every rank
+        raise ValueError("sharded_infer keeps the scalar length_scale (per-token prosody is `infer`'s, DESIGN 7.19)")
     sizes = [shard_bounds(B, world, r)[1] - shard_bounds(B, world, r)[0] for r in range(world)]
     lo, hi = shard_bounds(B, world, rank)
     extra = {}

@@ -74,6 +74,85 @@ def _durations_code(durations):
     return durations.to(torch.int64), 1
 
 
+FIT_BOUNDS = (0.5, 2.0)      # default `fit_bounds=`: a convention (half to double rate), not a measurement
+
+
+def frames_of_ms(ms, model_sr, samples_per_frame):
+    """Whole z-frames nearest to `ms` milliseconds at the model's rate (one frame = samples_per_frame samples of
+    model_sr Hz), a half rounding up: (2 ms model_sr + 1000 spf) // (2000 spf).  Pure integers, like the other
+    planners: what `extra_frames=` takes for a pause of known length.  ValueError for anything else."""
+    for name, v in (("ms", ms), ("model_sr", model_sr), ("samples_per_frame", samples_per_frame)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise TypeError("frames_of_ms: %s must be an integer, got %s" % (name, type(v).__name__))
+    ms, model_sr, spf = int(ms), int(model_sr), int(samples_per_frame)
+    if ms < 0 or model_sr < 1 or spf < 1:
+        raise ValueError("frames_of_ms: need ms >= 0, model_sr >= 1 and samples_per_frame >= 1")
+    return (2 * ms * model_sr + 1000 * spf) // (2000 * spf)
+
+
+def _prosody_args(who, length_scale, extra_frames, fit_frames, fit_bounds, durations, B, T, row=False):
+    """The three prosody controls of an entry, checked on the host -> (scalar, scale, extra, fit):
+      scalar  the float the encode takes (1.0 with a scale table)
+      scale   None, or the per-token table as fp32 [B, T]
+      extra   None, or the extra frames as int32 [B, T] (another integer dtype is clamped to [-1, 2^20] first: a
+              negative entry stays negative and one past the range stays past it, so the kernel's flags still see both)
+      fit     None, or [(frames, lo, hi)] * B
+    row: the entry takes one utterance (`Request`): tables are [T] (or [1, T] / [1, 1, T]).  Values on the device are
+    not looked at here (no synchronisation); the kernel flags them."""
+    shapes = ((T,), (1, T), (1, 1, T)) if row else ((B, T), (B, 1, T))
+    names = "[T_text]" if row else "[B, T_text] or [B, 1, T_text]"
+    scale = None
+    if torch.is_tensor(length_scale) and length_scale.dim() >= (1 if row else 2):
+        if not length_scale.dtype.is_floating_point:
+            raise TypeError("%s: a per-token length_scale must be a floating tensor, got %s" % (who, length_scale.dtype))
+        if tuple(length_scale.shape) not in shapes:
+            raise ValueError("%s: a per-token length_scale must be %s = %s, got %s"
+                             % (who, names, shapes[0], tuple(length_scale.shape)))
+        scale = length_scale.reshape(B, T).to(torch.float32).contiguous()
+        scalar = 1.0
+    else:
+        scalar = float(length_scale)
+    extra = None
+    if extra_frames is not None:
+        if not torch.is_tensor(extra_frames):
+            raise ValueError("%s: extra_frames must be an integer tensor %s" % (who, names))
+        if extra_frames.dtype.is_floating_point or extra_frames.dtype.is_complex or extra_frames.dtype == torch.bool:
+            raise TypeError("%s: extra_frames must hold integers, got %s" % (who, extra_frames.dtype))
+        if tuple(extra_frames.shape) not in shapes:
+            raise ValueError("%s: extra_frames must be %s = %s, got %s" % (who, names, shapes[0], tuple(extra_frames.shape)))
+        extra = extra_frames.reshape(B, T)
+        if extra.dtype != torch.int32:
+            extra = extra.clamp(-1, 1 << 20).to(torch.int32)
+        extra = extra.contiguous()
+    fit = None
+    if fit_frames is not None:
+        if torch.is_tensor(fit_frames):
+            if fit_frames.is_cuda:
+                raise ValueError("%s: fit_frames are host integers (an int, or B of them)" % who)
+            fit_frames = fit_frames.reshape(-1).tolist() if fit_frames.dim() else fit_frames.item()
+        elif isinstance(fit_frames, np.ndarray):
+            fit_frames = fit_frames.reshape(-1).tolist() if fit_frames.ndim else fit_frames.item()
+        frames = list(fit_frames) if isinstance(fit_frames, (list, tuple)) else [fit_frames] * B
+        if len(frames) != B:
+            raise ValueError("%s: %d fit_frames for %d rows" % (who, len(frames), B))
+        for v in frames:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s: fit_frames must be integers, got %s" % (who, type(v).__name__))
+            if not 1 <= int(v) < 1 << 62:
+                raise ValueError("%s: fit_frames must be >= 1, got %d" % (who, int(v)))
+        try:
+            lo, hi = (float(np.float32(v)) for v in fit_bounds)
+        except (TypeError, ValueError):
+            raise ValueError("%s: fit_bounds must be (lo, hi)" % who)
+        if not (0.0 < lo <= hi < math.inf):
+            raise ValueError("%s: fit_bounds must be 0 < lo <= hi < inf (in fp32), got %r" % (who, (fit_bounds,)))
+        fit = [(int(v), lo, hi) for v in frames]
+    if durations is not None and (scale is not None or extra is not None or fit is not None):
+        raise ValueError("%s: durations= are used as given: a per-token length_scale, extra_frames= and fit_frames= "
+                         "shape the PREDICTED durations and exclude it" % who)
+    return scalar, scale, extra, fit
+
+
 def _seed_value(v, what="seed"):
     """One seed of the device generator -> int in [0, 2^64).  TypeError for anything that is not an
     integer (bool and floats included), ValueError outside the range."""
@@ -118,6 +197,9 @@ class Request:
       chunk_frames, max_chunk_frames                          as `dec_stream`
       durations          frames per token, [T_text] (or [1, T_text] / [1, 1, T_text]), as `infer(durations=)`:
                          needs length_scale == 1
+      length_scale       may also be a floating tensor [T_text]: one scale per token, as `infer` takes it
+      extra_frames, fit_frames, fit_bounds      the other prosody controls of `infer`: an integer tensor
+                         [T_text], one int, (lo, hi); none of the three goes with durations
       seed               None = the noise comes from torch's generators, as `infer_stream` draws it; an int in
                          [0, 2^64): the request's noise is a function of the seed alone, at row 0
       marks              True: the stream gets `marks`, the z-frame at which every token starts, as
@@ -125,10 +207,11 @@ class Request:
     Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
-                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks")
+                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks", "scale", "extra", "fit")
 
     def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                 chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False):
+                 chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
+                 fit_frames=None, fit_bounds=FIT_BOUNDS):
         self.seed = None if seed is None else _seed_value(seed, "Request: seed")
         self.marks = bool(marks)
         if not torch.is_tensor(x):
@@ -149,7 +232,13 @@ class Request:
                 raise TypeError("Request: sid must be an integer")
             sid = int(sid)
         self.sid = sid
-        self.noise_scale, self.length_scale = float(noise_scale), float(length_scale)
+        # scale / extra: the tables as [T_text] fp32 / int32 (or None); fit: (frames, lo, hi) or None
+        self.length_scale, scale, extra, fit = _prosody_args("Request", length_scale, extra_frames, fit_frames,
+                                                             fit_bounds, durations, 1, self.x.numel(), row=True)
+        self.scale = None if scale is None else scale.reshape(-1)
+        self.extra = None if extra is None else extra.reshape(-1)
+        self.fit = None if fit is None else fit[0]
+        self.noise_scale = float(noise_scale)
         self.noise_scale_w = float(noise_scale_w)
         for name in ("noise_scale", "length_scale", "noise_scale_w"):
             if not math.isfinite(getattr(self, name)):
@@ -630,7 +719,8 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
-             prior_rows=None, trim=False, ragged=False, durations=None, seed=None, marks_out=None):
+             prior_rows=None, trim=False, ragged=False, durations=None, seed=None, marks_out=None, extra_frames=None,
+             fit_frames=None, fit_bounds=FIT_BOUNDS):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -648,7 +738,10 @@ class SynthesizerTrn(nn.Module):
                        draw are one `mbv_randn_blocks` launch each and no generator is touched.  A sharded caller
                        passes the `RowSeeds` of its own rows (row = the global row index)
           marks_out    a list: receives one host list per row, the token marks of `infer_stream(marks=True)` (one
-                       `mbv_token_marks` launch; they ride in the read-back of T'max, with the rows' x_lengths)"""
+                       `mbv_token_marks` launch; they ride in the read-back of T'max, with the rows' x_lengths)
+          length_scale, extra_frames, fit_frames, fit_bounds    the prosody controls (see `infer`): with any of them one
+                       `mbv_shape_durations` launch follows the encode, where `mbv_set_durations` would stand; the
+                       fit's factors and statuses ride in the same read-back and are left in `self.last_fit`"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
@@ -656,6 +749,10 @@ class SynthesizerTrn(nn.Module):
         seeds = _row_seeds(seed, B)
         if seeds is not None and noise_w is not None:
             raise ValueError("seed= and an explicit noise_w= exclude each other")
+        length_scale, scale, extra, fit = _prosody_args("infer", length_scale, extra_frames, fit_frames, fit_bounds,
+                                                        durations, B, T)
+        shaped = scale is not None or extra is not None or fit is not None
+        self.last_fit = None
         if durations is not None:
             durations, dur_dtype = self._check_durations(durations, B, T, length_scale)
         I = self.cfg.inter_channels
@@ -685,6 +782,15 @@ class SynthesizerTrn(nn.Module):
                          y_lengths, stream=stream)
             if durations is not None:
                 self._launch(h, "mbv_set_durations", durations, dur_dtype, B, T, y_lengths, stream=stream)
+            fit_dev = None
+            if shaped:
+                scale = None if scale is None else scale.to(dev)
+                extra = None if extra is None else extra.to(dev)
+                fit_host = None
+                if fit is not None:             # one mbv_fit_result (8 bytes) a row: it rides with the int64 lengths
+                    fit_host = (_capi.MbvFit * B)(*fit)
+                    fit_dev = torch.empty(B, dtype=torch.int64, device=dev)
+                self._launch(h, "mbv_shape_durations", scale, extra, fit_host, B, T, fit_dev, y_lengths, stream=stream)
             lo, hi = torch.aminmax(y_lengths)
             stat = torch.stack((hi, -lo))           # [T'max, > 0 iff an utterance was flagged -1]
             if stat_reduce is not None:
@@ -692,20 +798,25 @@ class SynthesizerTrn(nn.Module):
             if marks_out is not None:               # [B, T + 1] exclusive prefix sums, in the same read-back
                 marks_dev = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
                 self._launch(h, "mbv_token_marks", marks_dev, T + 1, stream=stream)
-                host = torch.cat((stat, y_lengths, x_lengths.to(torch.int64), marks_dev.reshape(-1))).tolist()
+                host = torch.cat((stat, y_lengths, x_lengths.to(torch.int64), marks_dev.reshape(-1))
+                                 + (() if fit_dev is None else (fit_dev,))).tolist()
                 Tp, flag, y_host = int(host[0]), int(host[1]), host[2:2 + B]
                 for b in range(B):
                     n = max(0, min(int(host[2 + B + b]), T))
                     marks_out.append([int(v) for v in host[2 + 2 * B + b * (T + 1):2 + 2 * B + b * (T + 1) + n + 1]])
-            elif ragged:                            # the B lengths ride in the same read-back
-                host = torch.cat((stat, y_lengths)).tolist()
-                Tp, flag, y_host = int(host[0]), int(host[1]), host[2:]
+            elif ragged or fit_dev is not None:     # the B lengths ride in the same read-back
+                host = torch.cat((stat, y_lengths) + (() if fit_dev is None else (fit_dev,))).tolist()
+                Tp, flag, y_host = int(host[0]), int(host[1]), host[2:2 + B]
             else:
                 Tp, flag = (int(v) for v in stat.tolist())      # the one host sync (commons.py:123)
+            if fit_dev is not None:
+                res = [_capi.fit_result(v) for v in host[len(host) - B:]]
+                self.last_fit = ([r[0] for r in res], [r[1] for r in res])
             if flag > 0:                            # flagged by the kernels, no extra sync
                 raise IndexError("index out of range in self (token id, x_lengths or sid outside the "
                                  "model's tables, or a duration outside the supported range: 2^20 frames a token, "
-                                 "2^30 an utterance%s)" % ("" if durations is None else "; given durations must be non-negative integers"))
+                                 "2^30 an utterance%s%s)" % ("" if durations is None else "; given durations must be non-negative integers",
+                                                             "; a per-token scale must be finite and >= 0, extra frames >= 0" if shaped else ""))
             if frames_hook is not None:
                 Tp = int(frames_hook(Tp))
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729)
@@ -797,8 +908,27 @@ class SynthesizerTrn(nn.Module):
         return o, o_mb, spec, phase
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-              max_len=None, outputs=None, trim=False, ragged=False, durations=None, seed=None):
+              max_len=None, outputs=None, trim=False, ragged=False, durations=None, seed=None, extra_frames=None,
+              fit_frames=None, fit_bounds=FIT_BOUNDS):
         """-> (o, o_mb, spec, phase, attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:737)
+
+        Per-token prosody (a float `length_scale` and nothing else launches what it always did).  With
+        any of the three, ONE `mbv_shape_durations` launch follows the encode and replaces the predicted durations by
+        w_t = ceil(exp(logw_t) * fl32(s_t * f)) + extra_t for the tokens below x_lengths:
+          `length_scale`  may be a floating tensor [B, T_text] or [B, 1, T_text] (the reference's own broadcast,
+                          models.py:717): s_t per token, finite and >= 0; 0 drops the token.  A tensor filled with s
+                          is bitwise the float s.
+          `extra_frames`  an integer tensor of that shape, >= 0: further frames of the token's own prior -- on a blank
+                          or "sp" token a pause of known length (`frames_of_ms`).  Token marks include them.
+          `fit_frames`    an int, or B ints on the host: each row gets the LARGEST fp32 factor f in `fit_bounds` whose
+                          total D(f) stays within that many frames (found exactly, on the device).  A row that does not
+                          fit even at the lower bound takes it and is reported with status 1 -- not an error; one that
+                          fits at the upper bound takes that.  Nothing is padded: the remainder is the caller's, e.g. as
+                          a turn pause.  `fit_bounds` = (lo, hi), default (0.5, 2.0): a convention for "still sounds
+                          like speech", not a measurement.  Afterwards `net.last_fit` = ([f_b], [status_b]).
+        Without a tensor, `extra_frames` and `fit_frames` use the float `length_scale` as s_t.  None of the three goes
+        with `durations=` (ValueError).  A negative, infinite or NaN scale, or a negative extra, below x_lengths[b]
+        raises IndexError after the call's one read-back, like an invalid token id.
 
         `seed` (extension, default None = the noise comes from torch's two generators, launch for launch as before):
         reproducible noise.  An int s gives row b the sub-stream (s, row=b); a length-B sequence or
@@ -832,22 +962,28 @@ class SynthesizerTrn(nn.Module):
         are read back in the call's one host synchronisation."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
                       noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, durations=durations,
-                      seed=seed)
+                      seed=seed, extra_frames=extra_frames, fit_frames=fit_frames, fit_bounds=fit_bounds)
         return r[:8]
 
     def infer_z_only(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
-                     max_len=None, durations=None, seed=None):
-        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788); `durations`, `seed` as in `infer`"""
+                     max_len=None, durations=None, seed=None, extra_frames=None, fit_frames=None,
+                     fit_bounds=FIT_BOUNDS):
+        """-> (attn, y_mask, (z, z_p, m_p, logs_p), timings)  (models.py:742-788); `durations`, `seed` and the prosody
+        controls (a tensor `length_scale`, `extra_frames`, `fit_frames`, `fit_bounds`) as in `infer`"""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
-                      noise_scale_w=noise_scale_w, durations=durations, seed=seed)
+                      noise_scale_w=noise_scale_w, durations=durations, seed=seed, extra_frames=extra_frames,
+                      fit_frames=fit_frames, fit_bounds=fit_bounds)
         return r[4], r[5], r[6], r[7]
 
     def infer_with_lengths(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1,
-                           max_len=None, noise_scale_w=1., outputs=None, trim=False, ragged=False, seed=None):
+                           max_len=None, noise_scale_w=1., outputs=None, trim=False, ragged=False, seed=None,
+                           extra_frames=None, fit_frames=None, fit_bounds=FIT_BOUNDS):
         """`infer` plus the per-utterance frame counts y_lengths [B] (int64) — what a batched
-        caller needs to trim the padded waveforms (valid samples = 256 * y_lengths).  `seed` as in `infer`."""
+        caller needs to trim the padded waveforms (valid samples = 256 * y_lengths).  `seed` and the prosody controls
+        as in `infer`."""
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, max_len, decode=True,
-                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, seed=seed)
+                      noise_scale_w=noise_scale_w, outputs=outputs, trim=trim, ragged=ragged, seed=seed,
+                      extra_frames=extra_frames, fit_frames=fit_frames, fit_bounds=fit_bounds)
         return r[:8], r[8]
 
     def _z_g(self, z, g, checked=True):
@@ -1001,7 +1137,8 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
-                     chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False):
+                     chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
+                     fit_frames=None, fit_bounds=FIT_BOUNDS):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
         flows exactly as `infer` does (same random draws; `durations` and `seed` as in `infer`), then returns `dec_stream` of
         z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
@@ -1011,11 +1148,15 @@ class SynthesizerTrn(nn.Module):
                  length regulator used (predicted or given), the last entry their sum, all clipped to the frames the
                  stream keeps (`max_len`).  One `mbv_token_marks` launch; the integers ride in the read-back the call
                  already makes, so there is no second host synchronisation.  False (default): `st.marks` is None and
-                 nothing is added."""
+                 nothing is added.
+          a tensor `length_scale`, `extra_frames`, `fit_frames`, `fit_bounds`    the prosody controls of `infer`.  With
+                 `fit_frames` the stream gets `st.fit_scale` and `st.fit_status`, one value per row (the value itself
+                 for a single utterance); they too ride in the call's one read-back.  Else both are None."""
         marks_out = [] if marks else None
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
                       noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed,
-                      marks_out=marks_out)
+                      marks_out=marks_out, extra_frames=extra_frames, fit_frames=fit_frames, fit_bounds=fit_bounds)
+        fitted = self.last_fit
         y_mask, z, y_lengths = r[5], r[6][0], r[8]
         Tp = z.shape[2]
         Td = Tp if max_len is None else max(0, min(Tp, int(max_len)))
@@ -1030,6 +1171,8 @@ class SynthesizerTrn(nn.Module):
         if marks:
             rows = [[min(v, Td) for v in row] for row in marks_out]
             st.marks = rows[0] if len(rows) == 1 else rows
+        if fitted is not None:
+            st.fit_scale, st.fit_status = (v[0] if len(v) == 1 else v for v in fitted)
         return st
 
     # ------------------------------------------------------------------ pooled admission
@@ -1105,6 +1248,12 @@ class SynthesizerTrn(nn.Module):
         the number of front-half launch chains it cost."""
         return int(_capi.lib().mbv_encoder_runs(self._ensure_handle()))
 
+    def shape_runs(self):
+        """Launches of the prosody kernel made on this model's handle so far (`mbv_shape_runs`): one per call with a
+        per-token `length_scale`, `extra_frames=` or `fit_frames=`, one per admission run that holds such a request,
+        none otherwise."""
+        return int(_capi.lib().mbv_shape_runs(self._ensure_handle()))
+
     @torch.no_grad()
     def infer_streams(self, requests):
         """Pooled admission: one single-utterance `DecodeStream` per `Request`, in order — what `StreamPool.add` takes —
@@ -1170,6 +1319,17 @@ class SynthesizerTrn(nn.Module):
             for i in marked:
                 mark_at[i] = o
                 o += t_text[i] + 1
+            # ... | one mbv_fit_result (8 bytes) per request with fit_frames
+            shaped = [r.scale is not None or r.extra is not None or r.fit is not None for r in reqs]
+            fit_at = {}
+            for i in range(N):
+                if reqs[i].fit is not None:
+                    fit_at[i] = o
+                    o += 1
+            scale_p, kept = self._pack_host([r.scale for r in reqs], dev)
+            keep += kept
+            extra_p, kept = self._pack_host([r.extra for r in reqs], dev)
+            keep += kept
             y_buf = torch.empty(o, dtype=torch.int64, device=dev)
             y_all = y_buf[:N]
             # ids (zero-padded to the run's longest text), lengths and sids of every run: ONE host tensor, one copy
@@ -1196,6 +1356,16 @@ class SynthesizerTrn(nn.Module):
                     row.durations, row.durations_dtype, row.t_text = dur[i], r.durations_dtype or 0, t_text[i]
                 self._launch(h, "mbv_encode_rows", k, C.c_void_p(ids), C.c_void_p(lens), sid, B, T, rows,
                              C.c_void_p(y_all.data_ptr() + 8 * first[k]), stream=hip_stream)
+                if any(shaped[i] for i in m):      # the run's shaped rows: one table-reading launch, in front of the marks
+                    srows = (_capi.MbvShapeRow * B)()
+                    for row, i in zip(srows, m):
+                        if shaped[i]:
+                            row.scale, row.extra = scale_p[i], extra_p[i]
+                            if i in fit_at:
+                                row.fit = _capi.MbvFit(*reqs[i].fit)
+                                row.fit_out = y_buf.data_ptr() + 8 * fit_at[i]
+                    self._launch(h, "mbv_shape_durations_rows", k, srows, B,
+                                 C.c_void_p(y_all.data_ptr() + 8 * first[k]), stream=hip_stream)
                 if any(i in mark_at for i in m):   # the run's marks: one table-reading launch
                     mrows = (_capi.MbvMarkRow * B)()
                     for row, i in zip(mrows, m):
@@ -1207,7 +1377,8 @@ class SynthesizerTrn(nn.Module):
             if bad:
                 raise IndexError("request%s %s: index out of range in self (token id or sid outside the model's tables, or "
                                  "a duration outside the supported range: 2^20 frames a token, 2^30 an utterance; given "
-                                 "durations must be non-negative integers)"
+                                 "durations must be non-negative integers; a per-token scale must be finite and >= 0, "
+                                 "extra frames >= 0)"
                                  % ("s" if len(bad) > 1 else "", ", ".join(str(i) for i in bad)))
             Tp = [int(y_host[pos[i]]) for i in range(N)]
             Td = [Tp[i] if r.max_len is None else min(Tp[i], r.max_len) for i, r in enumerate(reqs)]
@@ -1240,6 +1411,8 @@ class SynthesizerTrn(nn.Module):
             sts = self._streams_of(reqs, z, g, y_all, pos)
             for i in marked:
                 sts[i].marks = [min(int(v), Td[i]) for v in y_host[mark_at[i]:mark_at[i] + t_text[i] + 1]]
+            for i, at in fit_at.items():
+                sts[i].fit_scale, sts[i].fit_status = _capi.fit_result(y_host[at])
             return sts
 
     # ------------------------------------------------------------------ pooled voice conversion

@@ -441,6 +441,7 @@ class DecodeStream:
         self.o = torch.empty(B, 1, self.spf * Tp, device=z.device, dtype=torch.float32)
         self.y_lengths = None
         self.marks = None             # token marks in z-frames (`infer_stream(marks=True)`); a converted stream has none
+        self.fit_scale = self.fit_status = None     # the factor and status of `fit_frames=`, else None
         self._next = 0                # the chunk next() hands out
         self._decoded = 0             # the first chunk not decoded yet (>= _next; ahead of it only through a pool)
 

@@ -880,6 +880,74 @@ int mbv_op_shape_durations(mbv_model *m, const float *logw, const int32_t *lens,
                            void *stream);
 int64_t mbv_shape_runs(mbv_model *m);
 
+/* ---- per-token volume: a gain envelope from the tokens into the wire kernels (no reference counterpart) ---------
+ * `gain` holds one linear factor per token (fp32, 0 <= g <= 16 by convention, checked by the Python layer).  Two
+ * steps, both on the device:
+ *
+ * 1. FRAME GAINS.  For a row with y kept frames inside a stream of `frames` frames, G is fp32 [frames + 1]:
+ *      G[t] = gain[j(t)]   for t < y,   j(t) = the first token whose inclusive duration sum exceeds t: the token the
+ *                          length regulator gave frame t (after mbv_set_durations / mbv_shape_durations); tokens of
+ *                          zero frames are skipped by that rule
+ *      G[t] = G[y - 1]     for y <= t <= frames
+ *      G[t] = 1.0f         everywhere for a flagged row, for y = 0, and for a frame no token holds
+ *    A copy, so bitwise.  One launch, no synchronisation, no part in mbv_encoder_runs; mbv_gain_runs counts them.
+ *    mbv_frame_gain: after mbv_encode (and set / shape durations); gain DEVICE [B, T], out DEVICE [B, out_stride],
+ *      out_stride >= frames + 1; y = min(the row's frame count, frames).
+ *    mbv_frame_gain_rows: after mbv_encode_rows on `slot`, one table row per encoded row (n = the run's rows), in ONE
+ *      launch for the rows that carry a gain (gain DEVICE [t_text], out DEVICE [frames + 1]); a row without one is all
+ *      NULL / 0.  A call in which no row carries one launches nothing.  rows_host is HOST memory.
+ *    mbv_op_frame_gain: the kernel by itself on a caller's cum [B, T] (int32, the inclusive scan) and y_lengths [B]
+ *      (int64, negative = flagged), for tests.  Synchronises the stream.
+ *
+ * 2. THE ENVELOPE.  A pure function of the model-rate sample index j of the row (no state, no halo), with
+ *    hop = samples per frame, f = j / hop, r = j - f hop:
+ *      e(j) = G[f] + ((float)r * inv_hop) * (G[f + 1] - G[f]),       inv_hop = 1.0f / (float)hop
+ *    every operation rounded to fp32 on its own (no fma), and the wire kernels read fl32(wave[j] * e(j)) where they
+ *    read wave[j] today: in front of the FIR, the running peak, the static gain, the limiter, the fade and the clip.
+ *    So the limiter sees the shaped signal and still guarantees its ceiling, the running peak is the shaped signal's,
+ *    and the G.711 byte is the byte of the emitted int16.  A token's gain is reached at the start of its first frame;
+ *    the move to the next token's gain takes that token's last frame.  Continuous, so free of clicks by construction.
+ *    G all 1.0f gives e = 1.0f exactly and the bits of the unshaped entry.
+ *
+ * mbv_pcm_envelope: gain DEVICE [frames + 1]; gain NULL = no envelope on this row (frames, hop, inv_hop then 0): the
+ * row executes no multiply and is bitwise its row in the unshaped entry.
+ *
+ * The three *_shaped entries are supersets of the existing ones: each takes a law (0: int16, MBV_G711_ULAW /
+ * MBV_G711_ALAW: bytes), an optional limiter, an optional fade and the envelope.
+ *   mbv_resample_pcm16_range_shaped: mbv_resample_g711_range_faded with law 0 allowed; `envelope` (or NULL) is the
+ *     envelope of row 0, row b reads gain + b * env_stride (env_stride >= frames + 1 when B > 1).
+ *   mbv_resample_pcm16_chunks_shaped: mbv_resample_g711_chunks_faded with law 0 allowed; envelopes_host HOST [n] beside
+ *     chunks_host (or NULL).
+ *   mbv_resample_turns_shaped: mbv_resample_turns; seg_envelopes_host HOST, one per SEGMENT of the call in call order
+ *     (turn 0's segments, then turn 1's, ..), or NULL.  A segment's envelope runs over its own sample index and is
+ *     applied before its de-click ramp: the timeline of the shaped waves.
+ * The launches are those of the unshaped call (mbv_wire_runs): a launch in which a row is shaped reads an envelope
+ * table beside its row table, a launch without one is the unshaped launch.  Refused before anything is launched, the
+ * handle stays usable: whatever the unshaped entry refuses; hop < 1; frames < 1; an inv_hop that is not bitwise
+ * 1.0f / (float)hop; frames * hop below the row's in_total (in_stride; a segment's length); a NULL gain with non-zero
+ * sibling fields; an env_stride below frames + 1 with B > 1, or non-zero without a gain. */
+typedef struct mbv_gain_row { const float *gain; float *out; int32_t frames; int32_t reserved; } mbv_gain_row;
+int mbv_frame_gain(mbv_model *m, const float *gain, float *out, int64_t out_stride, int frames, void *stream);
+int mbv_frame_gain_rows(mbv_model *m, int slot, const mbv_gain_row *rows_host, int n, void *stream);
+int mbv_op_frame_gain(mbv_model *m, const int32_t *cum, const int64_t *y_lengths, const float *gain, float *out,
+                      int64_t out_stride, int frames, int B, int T, void *stream);
+int64_t mbv_gain_runs(mbv_model *m);
+typedef struct mbv_pcm_envelope { const float *gain; int64_t frames; int32_t hop; float inv_hop; } mbv_pcm_envelope;
+int mbv_resample_pcm16_range_shaped(mbv_model *m, const float *wave, const int64_t *valid_samples, int B,
+                                    int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                    int64_t out_first, int64_t out_count, const float *peak, void *out,
+                                    int64_t out_stride, float *running_peak, int64_t *out_samples,
+                                    const mbv_pcm_limit *limit, int law, const mbv_pcm_fade *fade,
+                                    const mbv_pcm_envelope *envelope, int64_t env_stride, void *stream);
+int mbv_resample_pcm16_chunks_shaped(mbv_model *m, const mbv_pcm_chunk *chunks_host, const mbv_pcm_limit *limits_host,
+                                     const mbv_pcm_fade *fades_host, const mbv_pcm_envelope *envelopes_host, int n,
+                                     int orig_sr, int target_sr, int filter, int law, void *packed,
+                                     int64_t packed_capacity, void *stream);
+int mbv_resample_turns_shaped(mbv_model *m, const mbv_turn_chunk *turns_host, const mbv_pcm_limit *limits_host,
+                              const mbv_pcm_fade *fades_host, const mbv_pcm_envelope *seg_envelopes_host, int n,
+                              int orig_sr, int target_sr, int filter, int law, void *packed, int64_t packed_capacity,
+                              void *stream);
+
 /* ---- loudness: ITU-R BS.1770 integrated loudness of a mono waveform, on the device ------------------------------
  * K-weighting (two cascaded biquads, zero state at sample 0), segments of H = (rate + 5) / 10 samples (100 ms; a half
  * rounds up), blocks of four segments (400 ms, 75 % overlap), the absolute gate at -70 LKFS and the relative gate 10 LU

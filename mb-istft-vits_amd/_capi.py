@@ -45,6 +45,8 @@ SYMBOLS = [
     "mbv_loudness_runs",
     "mbv_turn_plan", "mbv_resample_turns",
     "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
+    "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
+    "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped", "mbv_resample_turns_shaped",
 ]
 
 
@@ -130,6 +132,16 @@ class MbvFit(C.Structure):
 class MbvShapeRow(C.Structure):
     """mbv_shape_row of include/mbistft_vits.h (mbv_shape_durations_rows); all None / 0 = this row keeps its durations."""
     _fields_ = [("scale", C.c_void_p), ("extra", C.c_void_p), ("fit", MbvFit), ("fit_out", C.c_void_p)]
+
+
+class MbvGainRow(C.Structure):
+    """mbv_gain_row of include/mbistft_vits.h (mbv_frame_gain_rows); all None / 0 = this row carries no gain."""
+    _fields_ = [("gain", C.c_void_p), ("out", C.c_void_p), ("frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MbvPcmEnvelope(C.Structure):
+    """mbv_pcm_envelope of include/mbistft_vits.h (the shaped wire entries); gain None (all zero) = no envelope."""
+    _fields_ = [("gain", C.c_void_p), ("frames", C.c_int64), ("hop", C.c_int32), ("inv_hop", C.c_float)]
 
 
 def fit_result(word):
@@ -339,7 +351,7 @@ def lib():
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
     # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
-    # turns' two and prosody's four may be absent there, and calling one then raises AttributeError.
+    # turns' two, prosody's four and volume's seven may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -359,7 +371,10 @@ def lib():
                 "mbv_token_marks", "mbv_token_marks_rows",
                 "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
                 "mbv_loudness_runs", "mbv_turn_plan", "mbv_resample_turns",
-                "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
+                "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
+                "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped",
+                "mbv_resample_turns_shaped") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -465,6 +480,21 @@ def lib():
                                              vp]
         L.mbv_shape_runs.argtypes = [vp]
         L.mbv_shape_runs.restype = C.c_int64
+    if hasattr(L, "mbv_frame_gain") or not optional:
+        envp = C.POINTER(MbvPcmEnvelope)
+        L.mbv_frame_gain.argtypes = [vp, vp, vp, C.c_int64, i32, vp]
+        L.mbv_frame_gain_rows.argtypes = [vp, i32, C.POINTER(MbvGainRow), i32, vp]
+        L.mbv_op_frame_gain.argtypes = [vp, vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp]
+        L.mbv_gain_runs.argtypes = [vp]
+        L.mbv_gain_runs.restype = C.c_int64
+        L.mbv_resample_pcm16_range_shaped.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
+                                                      C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32,
+                                                      C.POINTER(MbvPcmFade), envp, C.c_int64, vp]
+        L.mbv_resample_pcm16_chunks_shaped.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit),
+                                                       C.POINTER(MbvPcmFade), envp, i32, i32, i32, i32, i32, vp,
+                                                       C.c_int64, vp]
+        L.mbv_resample_turns_shaped.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit),
+                                                C.POINTER(MbvPcmFade), envp, i32, i32, i32, i32, i32, vp, C.c_int64, vp]
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

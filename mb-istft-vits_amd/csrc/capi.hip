@@ -153,6 +153,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
                                                            // between an encode and its synthesize disturbs no scratch
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
   int64_t shape_runs = 0;          // launches of the prosody kernel (mbv_shape_runs)
+  int64_t gain_runs = 0;           // launches of the frame-gain kernel (mbv_gain_runs)
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
@@ -3249,6 +3250,60 @@ int mbv_shape_durations_rows(mbv_model* m, int slot, const mbv_shape_row* rows_h
 
 int64_t mbv_shape_runs(mbv_model* m) { return m ? m->shape_runs : -1; }
 
+int mbv_frame_gain(mbv_model* m, const float* gain, float* out, int64_t out_stride, int frames, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_frame_gain";
+  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
+  if (!gain || !out) return m->fail("%s: NULL argument", who);
+  if (frames < 1 || frames > (1 << 30)) return m->fail("%s: frames must be in [1, 2^30], got %d", who, frames);
+  if (out_stride < (int64_t)frames + 1) return m->fail("%s: out must be [%d, out_stride >= frames + 1 = %d]", who, m->B, frames + 1);
+  if (m->B > 65535) return m->fail("%s: more than 65535 rows", who);
+  DEVICE_GUARD(m);
+  launch_frame_gain(m->cum, m->ylen32, nullptr, gain, out, out_stride, frames, m->B, m->T, (hipStream_t)stream);
+  ++m->gain_runs;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_frame_gain_rows(mbv_model* m, int slot, const mbv_gain_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_frame_gain_rows";
+  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
+    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
+  const mbv_model::EncSlot& sl = m->slots[slot];
+  const int B = sl.enc.B, T = sl.enc.T;
+  if (!rows_host || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
+  if ((int)sl.enc.t_text.size() != B) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot);
+  std::vector<int> live;
+  int max_frames = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_gain_row& k = rows_host[i];
+    if (!k.gain) {
+      if (k.out || k.frames) return m->fail("%s: row %d: out / frames given without a gain", who, i);
+      continue;
+    }
+    if (!k.out) return m->fail("%s: row %d: out missing", who, i);
+    if (k.frames < 1 || k.frames > (1 << 30)) return m->fail("%s: row %d: frames must be in [1, 2^30], got %d", who, i, k.frames);
+    live.push_back(i);
+    max_frames = std::max(max_frames, (int)k.frames);
+  }
+  if (live.empty()) return 0;                              // nothing to write (a run holds at most 65535 rows: the grid's y)
+  DEVICE_GUARD(m);
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(GainRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  GainRow* rows = reinterpret_cast<GainRow*>(m->scrB);
+  upload_rows<kAdmitChunk>(live.size(), rows, s, [&](size_t j) {
+    const mbv_gain_row& k = rows_host[live[j]];
+    return GainRow{k.gain, k.out, live[j], sl.enc.t_text[live[j]], k.frames, 0};
+  });
+  launch_frame_gain_rows(sl.enc.cum, sl.enc.ylen32, rows, (int)live.size(), max_frames, T, s);
+  ++m->gain_runs;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_gain_runs(mbv_model* m) { return m ? m->gain_runs : -1; }
+
 int mbv_istft_finalize(mbv_model* m, const float* spec, const float* phase, int B, int frames,
                        float* o, float* o_mb, void* stream) {
   if (!m) return 1;
@@ -3454,6 +3509,20 @@ const char* fade_refusal(const mbv_pcm_fade& f) {
 
 PcmFade fade_of(const mbv_pcm_fade* f) { return f && f->count >= 0 ? PcmFade{f->first, f->count, f->inv, 0} : kNoFade; }
 
+// the envelope of a *_shaped entry over a row (or segment) of `in_total` model-rate samples (gain NULL: none), or why
+// it is refused
+const char* envelope_refusal(const mbv_pcm_envelope& e, int64_t in_total) {
+  if (!e.gain) return e.frames || e.hop || e.inv_hop != 0.f ? "envelope without a gain table must be all zero" : nullptr;
+  if (e.hop < 1) return "envelope hop must be >= 1";
+  if (e.frames < 1) return "envelope frames must be >= 1";
+  const float want = 1.0f / (float)e.hop;
+  if (memcmp(&e.inv_hop, &want, sizeof want) != 0) return "envelope inv_hop is not 1.0f / (float)hop";
+  if ((double)e.frames * (double)e.hop < (double)in_total) return "envelope covers frames * hop samples, fewer than the row holds";
+  return nullptr;
+}
+
+PcmEnv env_of(const mbv_pcm_envelope* e) { return e && e->gain ? PcmEnv{e->gain, e->frames, e->hop, e->inv_hop} : kNoEnv; }
+
 // the codec of a G.711 entry, or why it is refused
 const char* law_refusal(int law) {
   return law == MBV_G711_ULAW || law == MBV_G711_ALAW ? nullptr : "unknown law (MBV_G711_ULAW 1, MBV_G711_ALAW 2)";
@@ -3465,11 +3534,17 @@ const char* law_refusal(int law) {
 int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t* valid_samples, int B, int64_t in_stride,
                 int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t out_first, int64_t out_count,
                 const float* peak, void* pcm, int64_t pcm_stride, float* running_peak, int64_t* out_samples,
-                const mbv_pcm_limit* lim, int law, void* stream, const mbv_pcm_fade* fade = nullptr) {
+                const mbv_pcm_limit* lim, int law, void* stream, const mbv_pcm_fade* fade = nullptr,
+                const mbv_pcm_envelope* env = nullptr, int64_t env_stride = 0) {
   if (!m) return 1;
   if (fade)
     if (const char* why = fade_refusal(*fade)) return m->fail("%s: %s", who, why);
   if (!wave || !pcm || B <= 0 || in_stride <= 0 || pcm_stride <= 0) return m->fail("%s: bad arguments", who);
+  if (env) {
+    if (const char* why = envelope_refusal(*env, in_stride)) return m->fail("%s: %s", who, why);
+    if (!env->gain ? env_stride != 0 : (B > 1 && env_stride < env->frames + 1))
+      return m->fail("%s: env_stride must be >= frames + 1 for B > 1 (0 without a gain table)", who);
+  }
   if (B > 65535) return m->fail("%s: more than 65535 rows", who);
   if (in_avail < 0 || out_first < 0 || out_count < 0)
     return m->fail("%s: in_avail, out_first and out_count must be >= 0", who);
@@ -3492,11 +3567,11 @@ int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t*
     launch_resample_pcm16_range_limited(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count,
                                         peak, pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples,
                                         LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, law, fade_of(fade),
-                                        (hipStream_t)stream);
+                                        env_of(env), env_stride, (hipStream_t)stream);
   else
     launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
                                 pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, law,
-                                fade_of(fade), (hipStream_t)stream);
+                                fade_of(fade), env_of(env), env_stride, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3563,6 +3638,20 @@ int mbv_resample_g711_range_faded(mbv_model* m, const float* wave, const int64_t
   return pcm16_range(m, "mbv_resample_g711_range_faded", wave, valid_samples, B, in_stride, orig_sr, target_sr, filter,
                      in_avail, out_first, out_count, peak, out, out_stride, running_peak, out_samples, limit, law, stream,
                      fade);
+}
+
+int mbv_resample_pcm16_range_shaped(mbv_model* m, const float* wave, const int64_t* valid_samples, int B,
+                                    int64_t in_stride, int orig_sr, int target_sr, int filter, int64_t in_avail,
+                                    int64_t out_first, int64_t out_count, const float* peak, void* out,
+                                    int64_t out_stride, float* running_peak, int64_t* out_samples,
+                                    const mbv_pcm_limit* limit, int law, const mbv_pcm_fade* fade,
+                                    const mbv_pcm_envelope* envelope, int64_t env_stride, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_resample_pcm16_range_shaped";
+  if (law != kLawNone)
+    if (const char* why = law_refusal(law)) return m->fail("%s: %s (0: int16), got %d", who, why, law);
+  return pcm16_range(m, who, wave, valid_samples, B, in_stride, orig_sr, target_sr, filter, in_avail, out_first, out_count,
+                     peak, out, out_stride, running_peak, out_samples, limit, law, stream, fade, envelope, env_stride);
 }
 
 int64_t mbv_limiter_ready(int orig_sr, int target_sr, int filter, int64_t in_avail, int64_t in_total, int lookahead) {
@@ -3661,7 +3750,8 @@ namespace {
 template <typename At, typename Side>
 int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mbv_pcm_limit* limits,
                 const mbv_pcm_fade* fades, int n, const RatePair& rp, const std::vector<int64_t>& off, int64_t total,
-                int law, void* packed, int64_t packed_capacity, void* stream, const Side& side) {
+                int law, void* packed, int64_t packed_capacity, void* stream, const Side& side,
+                const mbv_pcm_envelope* envs = nullptr) {
   if (packed && packed_capacity < total)
     return m->fail("%s: packed_capacity %lld is below the %lld samples of the call", who, (long long)packed_capacity, (long long)total);
   const uintptr_t sample_bytes = law == kLawNone ? sizeof(int16_t) : 1;
@@ -3688,14 +3778,22 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
         if (fades[i].count >= 0) return true;
     return false;
   };
-  // the scratch: the head, then per kind its rows, its side rows and (with a fading row) its fades
+  auto shaped = [&](const std::vector<int>& kind) {       // (a kind with a shaped row gets an envelope table)
+    if (envs)
+      for (int i : kind)
+        if (envs[i].gain) return true;
+    return false;
+  };
+  // the scratch: the head, then per kind its rows, its side rows, (with a fading row) its fades and (with a shaped
+  // row) its envelopes
   size_t end = 0;
   auto take = [&](size_t bytes) { const size_t a = end; end = align_up(end + bytes, 256); return a; };
   const size_t head_at = take(side.head_bytes);
-  struct Kind { size_t rows, side, fades; bool fade; };
+  struct Kind { size_t rows, side, fades; bool fade; size_t envs; bool env; };
   auto kind_of = [&](const std::vector<int>& k, size_t row_bytes) {
-    Kind t{take(k.size() * row_bytes), take(k.size() * side.row_bytes), 0, fading(k)};
+    Kind t{take(k.size() * row_bytes), take(k.size() * side.row_bytes), 0, fading(k), 0, shaped(k)};
     if (t.fade) t.fades = take(k.size() * sizeof(PcmFade));
+    if (t.env) t.envs = take(k.size() * sizeof(PcmEnv));
     return t;
   };
   const Kind ku = kind_of(live, sizeof(PcmPoolRow)), kl = kind_of(live_lim, sizeof(PcmLimRow));
@@ -3711,6 +3809,12 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
     upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return fade_of(&fades[kind[i]]); });
     return t;
   };
+  auto env_table = [&](const std::vector<int>& kind, const Kind& k) -> const PcmEnv* {
+    if (!k.env) return nullptr;
+    PcmEnv* t = reinterpret_cast<PcmEnv*>(m->scrB + k.envs);
+    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return env_of(&envs[kind[i]]); });
+    return t;
+  };
   auto row_of = [&](int i) {
     const mbv_pcm_chunk& k = at(i);
     return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
@@ -3722,10 +3826,11 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
     PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB + ku.rows);
     upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
     const PcmFade* ft = beside(live, ku);
+    const PcmEnv* et = env_table(live, ku);
     grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      side.launch(rows + f, m->scrB + ku.side + f * side.row_bytes, head, ft ? ft + f : nullptr, nn, max_count, rp,
-                  packed, law, s);
+      side.launch(rows + f, m->scrB + ku.side + f * side.row_bytes, head, ft ? ft + f : nullptr, et ? et + f : nullptr,
+                  nn, max_count, rp, packed, law, s);
       return 0;
     });
   }
@@ -3736,10 +3841,11 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
       return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
     });
     const PcmFade* ft = beside(live_lim, kl);
+    const PcmEnv* et = env_table(live_lim, kl);
     grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      side.launch_limited(rows + f, m->scrB + kl.side + f * side.row_bytes, head, ft ? ft + f : nullptr, nn, max_count,
-                          rp, lds_floats, packed, law, s);
+      side.launch_limited(rows + f, m->scrB + kl.side + f * side.row_bytes, head, ft ? ft + f : nullptr,
+                          et ? et + f : nullptr, nn, max_count, rp, lds_floats, packed, law, s);
       return 0;
     });
   }
@@ -3752,13 +3858,14 @@ struct ChunkSide {
   size_t head_bytes = 0, row_bytes = 0;
   void head(char*, hipStream_t) const {}
   void rows(const std::vector<int>&, char*, hipStream_t) const {}
-  void launch(const PcmPoolRow* rows, const char*, const char*, const PcmFade* ft, int n, int64_t max_count,
-              const RatePair& rp, void* packed, int law, hipStream_t s) const {
-    launch_resample_pcm16_pool(rows, ft, n, max_count, rp.bank, rp.g, packed, law, s);
+  void launch(const PcmPoolRow* rows, const char*, const char*, const PcmFade* ft, const PcmEnv* et, int n,
+              int64_t max_count, const RatePair& rp, void* packed, int law, hipStream_t s) const {
+    launch_resample_pcm16_pool(rows, ft, et, n, max_count, rp.bank, rp.g, packed, law, s);
   }
-  void launch_limited(const PcmLimRow* rows, const char*, const char*, const PcmFade* ft, int n, int64_t max_count,
-                      const RatePair& rp, int64_t lds_floats, void* packed, int law, hipStream_t s) const {
-    launch_resample_pcm16_pool_limited(rows, ft, n, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
+  void launch_limited(const PcmLimRow* rows, const char*, const char*, const PcmFade* ft, const PcmEnv* et, int n,
+                      int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law,
+                      hipStream_t s) const {
+    launch_resample_pcm16_pool_limited(rows, ft, et, n, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
   }
 };
 
@@ -3767,9 +3874,12 @@ struct ChunkSide {
 // count < 0) = no row fades
 int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits, int n,
                  int orig_sr, int target_sr, int filter, void* packed, int64_t packed_capacity, int law, void* stream,
-                 const mbv_pcm_fade* fades = nullptr) {
+                 const mbv_pcm_fade* fades = nullptr, const mbv_pcm_envelope* envs = nullptr) {
   if (!m) return 1;
   if (n < 0 || (n > 0 && !chunks_host)) return m->fail("%s: bad arguments", who);
+  if (envs)
+    for (int i = 0; i < n; ++i)
+      if (const char* why = envelope_refusal(envs[i], chunks_host[i].in_total)) return m->fail("%s: chunk %d: %s", who, i, why);
   if (fades)
     for (int i = 0; i < n; ++i)
       if (const char* why = fade_refusal(fades[i])) return m->fail("%s: chunk %d: %s", who, i, why);
@@ -3783,7 +3893,7 @@ int pcm16_chunks(mbv_model* m, const char* who, const mbv_pcm_chunk* chunks_host
   const int64_t total = pcm_chunks_check(who, chunks_host, n, rp, off.data(), &err, limits);
   if (total < 0) return m->fail("%s", err.c_str());
   return pooled_wire(m, who, "chunk", [&](int i) -> const mbv_pcm_chunk& { return chunks_host[i]; }, limits, fades, n, rp,
-                     off, total, law, packed, packed_capacity, stream, ChunkSide{});
+                     off, total, law, packed, packed_capacity, stream, ChunkSide{}, envs);
 }
 }  // namespace
 
@@ -3825,6 +3935,18 @@ int mbv_resample_g711_chunks_faded(mbv_model* m, const mbv_pcm_chunk* chunks_hos
   if (const char* why = law_refusal(law)) return m->fail("mbv_resample_g711_chunks_faded: %s, got %d", why, law);
   return pcm16_chunks(m, "mbv_resample_g711_chunks_faded", chunks_host, limits_host, n, orig_sr, target_sr, filter,
                       packed, packed_capacity, law, stream, fades_host);
+}
+
+int mbv_resample_pcm16_chunks_shaped(mbv_model* m, const mbv_pcm_chunk* chunks_host, const mbv_pcm_limit* limits_host,
+                                     const mbv_pcm_fade* fades_host, const mbv_pcm_envelope* envelopes_host, int n,
+                                     int orig_sr, int target_sr, int filter, int law, void* packed,
+                                     int64_t packed_capacity, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_resample_pcm16_chunks_shaped";
+  if (law != kLawNone)
+    if (const char* why = law_refusal(law)) return m->fail("%s: %s (0: int16), got %d", who, why, law);
+  return pcm16_chunks(m, who, chunks_host, limits_host, n, orig_sr, target_sr, filter, packed, packed_capacity, law,
+                      stream, fades_host, envelopes_host);
 }
 
 }  // extern "C"
@@ -3883,30 +4005,38 @@ struct TurnSide {
   const std::vector<int>& seg_first;
   const mbv_turn_chunk* turns;
   size_t head_bytes, row_bytes = sizeof(TurnSlice);
+  const std::vector<PcmEnv>* seg_envs = nullptr;           // one per segment, behind the segment table; null: none shaped
+  const PcmEnv* envs_in(const char* head) const {
+    return seg_envs ? reinterpret_cast<const PcmEnv*>(head + align_up(segs.size() * sizeof(TurnSeg), 256)) : nullptr;
+  }
   void head(char* dst, hipStream_t s) const {
     upload_rows<kTurnSegChunk>(segs.size(), reinterpret_cast<TurnSeg*>(dst), s, [&](size_t i) { return segs[i]; });
+    if (seg_envs)
+      upload_rows<kTurnSegChunk>(seg_envs->size(), const_cast<PcmEnv*>(envs_in(dst)), s,
+                                 [&](size_t i) { return (*seg_envs)[i]; });
   }
   void rows(const std::vector<int>& kind, char* dst, hipStream_t s) const {
     upload_rows<kPcmPoolChunk>(kind.size(), reinterpret_cast<TurnSlice*>(dst), s,
                                [&](size_t i) { return TurnSlice{seg_first[kind[i]], turns[kind[i]].n_segs}; });
   }
-  void launch(const PcmPoolRow* rows, const char* slices, const char* head, const PcmFade* ft, int n, int64_t max_count,
-              const RatePair& rp, void* packed, int law, hipStream_t s) const {
+  void launch(const PcmPoolRow* rows, const char* slices, const char* head, const PcmFade* ft, const PcmEnv*, int n,
+              int64_t max_count, const RatePair& rp, void* packed, int law, hipStream_t s) const {
     launch_resample_pcm16_turns(rows, reinterpret_cast<const TurnSlice*>(slices), reinterpret_cast<const TurnSeg*>(head),
-                                ft, n, max_count, rp.bank, rp.g, packed, law, s);
+                                envs_in(head), ft, n, max_count, rp.bank, rp.g, packed, law, s);
   }
-  void launch_limited(const PcmLimRow* rows, const char* slices, const char* head, const PcmFade* ft, int n,
-                      int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law, hipStream_t s) const {
+  void launch_limited(const PcmLimRow* rows, const char* slices, const char* head, const PcmFade* ft, const PcmEnv*,
+                      int n, int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law,
+                      hipStream_t s) const {
     launch_resample_pcm16_turns_limited(rows, reinterpret_cast<const TurnSlice*>(slices),
-                                        reinterpret_cast<const TurnSeg*>(head), ft, n, max_count, rp.bank, rp.g,
-                                        lds_floats, packed, law, s);
+                                        reinterpret_cast<const TurnSeg*>(head), envs_in(head), ft, n, max_count, rp.bank,
+                                        rp.g, lds_floats, packed, law, s);
   }
 };
 
 // mbv_resample_turns: the chunk entries' body (pooled_wire) for rows whose input is a timeline
 int pcm16_turns(mbv_model* m, const char* who, const mbv_turn_chunk* turns, const mbv_pcm_limit* limits,
                 const mbv_pcm_fade* fades, int n, int orig_sr, int target_sr, int filter, int law, void* packed,
-                int64_t packed_capacity, void* stream) {
+                int64_t packed_capacity, void* stream, const mbv_pcm_envelope* seg_envs_host = nullptr) {
   if (!m) return 1;
   if (n < 0 || (n > 0 && !turns)) return m->fail("%s: bad arguments", who);
   if (law != kLawNone)
@@ -3927,17 +4057,29 @@ int pcm16_turns(mbv_model* m, const char* who, const mbv_turn_chunk* turns, cons
   if (total < 0) return m->fail("%s", err.c_str());
   std::vector<int> seg_first(n > 0 ? n : 1);
   std::vector<TurnSeg> segs;
+  std::vector<PcmEnv> seg_envs;                            // the call's envelopes, one per segment in call order
+  bool any_env = false;
   for (int i = 0; i < n; ++i) {
     seg_first[i] = (int)segs.size();
     for (int k = 0; k < turns[i].n_segs; ++k) {
       const mbv_turn_seg& sg = turns[i].segs[k];
       if (!sg.wave) return m->fail("%s: turn %d: segment %d: wave missing", who, i, k);
+      if (seg_envs_host) {
+        const mbv_pcm_envelope& e = seg_envs_host[segs.size()];
+        if (const char* why = envelope_refusal(e, sg.length)) return m->fail("%s: turn %d: segment %d: %s", who, i, k, why);
+        seg_envs.push_back(env_of(&e));
+        any_env = any_env || e.gain;
+      }
       segs.push_back(TurnSeg{sg.wave, sg.start, sg.length, sg.ramp, fade_inv(sg.ramp)});
     }
   }
+  TurnSide side{segs, seg_first, turns, segs.size() * sizeof(TurnSeg)};
+  if (any_env) {
+    side.seg_envs = &seg_envs;
+    side.head_bytes = align_up(side.head_bytes, 256) + seg_envs.size() * sizeof(PcmEnv);
+  }
   return pooled_wire(m, who, "turn", [&](int i) -> const mbv_pcm_chunk& { return turns[i].chunk; }, limits, fades, n, rp,
-                     off, total, law, packed, packed_capacity, stream,
-                     TurnSide{segs, seg_first, turns, segs.size() * sizeof(TurnSeg)});
+                     off, total, law, packed, packed_capacity, stream, side);
 }
 }  // namespace
 
@@ -3960,6 +4102,14 @@ int mbv_resample_turns(mbv_model* m, const mbv_turn_chunk* turns_host, const mbv
                        void* packed, int64_t packed_capacity, void* stream) {
   return pcm16_turns(m, "mbv_resample_turns", turns_host, limits_host, fades_host, n, orig_sr, target_sr, filter, law,
                      packed, packed_capacity, stream);
+}
+
+int mbv_resample_turns_shaped(mbv_model* m, const mbv_turn_chunk* turns_host, const mbv_pcm_limit* limits_host,
+                              const mbv_pcm_fade* fades_host, const mbv_pcm_envelope* seg_envelopes_host, int n,
+                              int orig_sr, int target_sr, int filter, int law, void* packed, int64_t packed_capacity,
+                              void* stream) {
+  return pcm16_turns(m, "mbv_resample_turns_shaped", turns_host, limits_host, fades_host, n, orig_sr, target_sr, filter,
+                     law, packed, packed_capacity, stream, seg_envelopes_host);
 }
 
 int mbv_g711_encode(mbv_model* m, const int16_t* pcm, int64_t n, int law, uint8_t* out, void* stream) {
@@ -4734,6 +4884,20 @@ int mbv_op_shape_durations(mbv_model* m, const float* logw, const int32_t* lens,
   launch_shape_durations(logw, lens, scale, extra, scalar, fit, w_ceil, cum, ylen32, ylen64, bad, nullptr,
                          reinterpret_cast<FitOut*>(fit_out), B, T, s);
   ++m->shape_runs;
+  OP_END();
+}
+
+int mbv_op_frame_gain(mbv_model* m, const int32_t* cum, const int64_t* y_lengths, const float* gain, float* out,
+                      int64_t out_stride, int frames, int B, int T, void* stream) {
+  if (!m) return 1;
+  OP_REFUSE(!cum || !y_lengths || !gain || !out, "NULL argument");
+  OP_REFUSE(B <= 0 || T <= 0, "B and T must be > 0");
+  OP_REFUSE(B > kGridYZ, "B <= 65535 required");
+  OP_REFUSE(frames < 1 || frames > (1 << 30), "frames must be in [1, 2^30]");
+  OP_REFUSE(out_stride < (int64_t)frames + 1, "out_stride must be >= frames + 1");
+  OP_BEGIN();
+  launch_frame_gain(cum, nullptr, y_lengths, gain, out, out_stride, frames, B, T, s);
+  ++m->gain_runs;
   OP_END();
 }
 

@@ -252,6 +252,22 @@ struct MarkRow {
 };
 void launch_token_marks(const int* cum, int B, int T, int64_t* dst, int64_t stride, int count, const MarkRow* rows,
                         hipStream_t s);
+// Frame gains (mbv_frame_gain / mbv_frame_gain_rows / mbv_op_frame_gain): the per-token gain spread over
+// the z-frames by the rule of expand_kernel, as the table a PcmEnv reads.  With y = min(y_len, frames) (y_len from
+// ylen64 when given, where a negative value flags the row, else from ylen32):
+//   out[t] = gain[j(t)] for t < y, j(t) = the first token with cum[j] > t;   out[t] = out[y - 1] for y <= t <= frames
+// and 1.0f everywhere for a flagged row, for y = 0, and where no token holds the frame.  A copy: bitwise.  Row b of the
+// grid reads gain + b T and writes frames + 1 entries to out + b out_stride; with a table (in the arena, upload_rows)
+// block row i works on row rows[i].row of the run with that row's own gain [t_text], out and frames.  One launch.
+struct GainRow {
+  const float* gain;
+  float* out;
+  int32_t row, t_text, frames, pad_;
+};
+void launch_frame_gain(const int* cum, const int* ylen32, const int64_t* ylen64, const float* gain, float* out,
+                       int64_t out_stride, int frames, int B, int T, hipStream_t s);
+void launch_frame_gain_rows(const int* cum, const int* ylen32, const GainRow* rows, int n, int max_frames, int T,
+                            hipStream_t s);
 
 // ---------------------------------------------------------------- StochasticDurationPredictor (sdp.hip)
 // DDSConv halves (modules.py:98-111), C <= 256
@@ -439,10 +455,28 @@ struct PcmFade {
   int32_t pad_;
 };
 constexpr PcmFade kNoFade{0, -1, 0.f, 0};
+// Gain envelope of the wire step (the *_shaped entries): per-token volume.  `gain` is the frame-gain
+// table G of the row, fp32 [frames + 1] (launch_frame_gain); model-rate sample j of the row, j < frames * hop, is
+// multiplied WHERE THE WIRE TILE READS ITS SOURCE by
+//   e(j) = G[f] + w * (G[f + 1] - G[f]),   f = j / hop,   w = (float)(j - f * hop) * inv_hop,   inv_hop = 1.0f / (float)hop
+// every operation rounded to fp32 on its own (contraction switched off: no fma), and the staged sample is
+// fl32(x[j] * e(j)).  A pure function of j: no state, no halo.  Everything behind the read (FIR, running peak,
+// static gain, limiter, fade, clip, G.711) sees the shaped signal.  gain null: no envelope, no multiply, and the row is
+// bitwise the unshaped row.  One value (with a row stride) for a ranged launch, a table beside the row table (null =
+// no row is shaped) for a pooled one, a table beside the segment table for turns.  A launch without an envelope runs
+// the instantiations that know none.
+struct PcmEnv {
+  const float* gain;           // G [frames + 1], or null
+  int64_t frames;
+  int32_t hop;                 // model-rate samples per frame
+  float inv_hop;
+};
+constexpr PcmEnv kNoEnv{nullptr, 0, 0, 0.f};
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, const PcmFade& fade, hipStream_t s);
+                                 int64_t* out_samples, int law, const PcmFade& fade, const PcmEnv& env,
+                                 int64_t env_stride, hipStream_t s);
 // Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
 // what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
 // the arena (upload_rows).
@@ -463,9 +497,10 @@ constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of ker
 // row alone (one tile function); also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
 // out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
 // in_total), pcm_cap) of every row.
-// fades: null, or fades[i] beside rows[i].
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, int n, int64_t max_count,
-                                const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s);
+// fades: null, or fades[i] beside rows[i].  envs: null, or envs[i] beside rows[i].
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
+                                int64_t max_count, const float* bank, const ResampleGeom& g, void* packed, int law,
+                                hipStream_t s);
 // Look-ahead limiter of the wire step (mbv_resample_pcm16_range_limited / mbv_resample_pcm16_chunks_limited, DESIGN
 // §7.14).  With v the sample the unlimited kernels clip (static peak gain included; zero outside the row's computed
 // outputs), all in fp32:
@@ -507,10 +542,10 @@ void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, i
                                          int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
                                          int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
                                          unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         const PcmFade& fade, hipStream_t s);
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, int n, int64_t max_count,
-                                        const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
-                                        int law, hipStream_t s);
+                                         const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s);
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
+                                        int64_t max_count, const float* bank, const ResampleGeom& g,
+                                        int64_t lds_floats, void* packed, int law, hipStream_t s);
 // Turns on the wire (mbv_resample_turns): the input of a row is not one wave row but a TIMELINE of
 // segments, each the waveform of one utterance, with silence between them; it is never materialised.  Timeline index j
 // holds x[j - start] g(j - start) of the segment with start <= j < start + n, and 0.f anywhere else.  g is the
@@ -529,14 +564,15 @@ struct TurnSeg {
 };
 struct TurnSlice { int32_t first, count; };
 constexpr int kTurnMaxSegs = 4096;   // segments of one call (MBV_TURN_MAX_SEGS)
-// launch_resample_pcm16_pool / _pool_limited over turn rows: slices[i] beside rows[i]
+// launch_resample_pcm16_pool / _pool_limited over turn rows: slices[i] beside rows[i]; seg_envs: null, or
+// seg_envs[k] beside segs[k], the envelope of that segment in its own sample index (applied before the de-click ramp)
 void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                 const PcmFade* fades, int n, int64_t max_count, const float* bank,
-                                 const ResampleGeom& g, void* packed, int law, hipStream_t s);
+                                 const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
+                                 const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s);
 void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                         const PcmFade* fades, int n, int64_t max_count, const float* bank,
-                                         const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
-                                         hipStream_t s);
+                                         const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
+                                         const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
+                                         int law, hipStream_t s);
 // the stand-alone codec: n samples, law kLawUlaw or kLawAlaw (checked by the caller)
 void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s);
 void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s);

@@ -413,6 +413,55 @@ void launch_token_marks(const int* cum, int B, int T, int64_t* dst, int64_t stri
                      rows);
 }
 
+// Frame gains (mbv_frame_gain / mbv_frame_gain_rows / mbv_op_frame_gain, kernels.h): out[t] = gain[j(t)], j(t) the
+// token expand_kernel gives frame t (the same search over the same scan), held behind the row's kept frames; all 1.0f
+// for a flagged or empty row.  One thread per entry of [0, frames]; only loads and one store, so a copy.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void frame_gain_kernel(const int* __restrict__ cum, const int* __restrict__ ylen32,
+                                                         const int64_t* __restrict__ ylen64, const float* gain,
+                                                         float* out, int64_t out_stride, int frames,
+                                                         const GainRow* __restrict__ rows, int T) {
+  int b = blockIdx.y;
+  int n_tok = T;
+  if (ROWS) {
+    const GainRow r = rows[blockIdx.y];
+    b = r.row;
+    gain = r.gain; out = r.out; frames = r.frames;
+    n_tok = r.t_text < T ? r.t_text : T;                  // never read past the row's own gain tensor
+  } else {
+    gain += (int64_t)b * T;
+    out += (int64_t)b * out_stride;
+  }
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t > frames) return;
+  int64_t y = ylen64 ? ylen64[b] : (int64_t)ylen32[b];
+  if (y > frames) y = frames;
+  float g = 1.f;
+  if (y > 0 && n_tok > 0) {
+    const int tt = t < y ? t : (int)y - 1;
+    const int* cb = cum + (int64_t)b * T;
+    int lo = 0, hi = n_tok - 1;                           // first j with cum[j] > tt
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cb[mid] > tt) hi = mid; else lo = mid + 1;
+    }
+    if (cb[lo] > tt) g = gain[lo];                        // else: all-zero durations, no token holds the frame
+  }
+  out[t] = g;
+}
+
+void launch_frame_gain(const int* cum, const int* ylen32, const int64_t* ylen64, const float* gain, float* out,
+                       int64_t out_stride, int frames, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(frame_gain_kernel<false>, dim3((unsigned)(frames / 256 + 1), B), dim3(256), 0, s, cum, ylen32,
+                     ylen64, gain, out, out_stride, frames, nullptr, T);
+}
+
+void launch_frame_gain_rows(const int* cum, const int* ylen32, const GainRow* rows, int n, int max_frames, int T,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(frame_gain_kernel<true>, dim3((unsigned)(max_frames / 256 + 1), n), dim3(256), 0, s, cum, ylen32,
+                     nullptr, nullptr, nullptr, 0, 0, rows, T);
+}
+
 // ---------------------------------------------------------------------------
 // Length regulation (models.py:720-729, commons.py:128-143).  The reference
 // builds a one-hot path [B,1,T',T] and matmuls; it is a gather: frame t' takes

@@ -214,13 +214,49 @@ __device__ __forceinline__ void resample_stage(float* xs, const uint8_t* __restr
 // The segmented source of a turn row (kernels.h).  The scan over the row's few segments has a uniform
 // trip count and reads the table through uniform addresses; per element it only selects an address and a ramp, and
 // the ONE load behind it is predicated exactly as the plain row's is (below the frontier, inside a segment).
-struct TurnSrc { const TurnSeg* __restrict__ segs; int n; };
+// `envs` (ENV = true only): envs[s] beside segs[s], the gain envelope of that segment (gain null: none)
+struct TurnSrc { const TurnSeg* __restrict__ segs; int n; const PcmEnv* __restrict__ envs; };
 
-// timeline index j: zero in a pause, beyond the timeline and at or past `limit` (nothing there is loaded)
+// The gain envelope (kernels.h) at model-rate sample j >= 0 of its row: G[f] + w (G[f + 1] - G[f]) with
+// f = j / hop and w = (float)(j - f hop) * inv_hop, every operation rounded to fp32 on its own (no fma: the NumPy
+// restatement computes the same bits).  j < frames * hop (checked on the host), so f + 1 <= frames: inside the table.
+// The toolchain's __fmul_rn / __fadd_rn are inline functions over the plain operators, compiled contractable: hipcc
+// fuses them into an fma like any others.  The pragma is what keeps the product and the sum apart; it covers the
+// operators written in this function (also after inlining), not those inside a function it calls
+__device__ __forceinline__ float env_at(const PcmEnv& e, int64_t j) {
+#pragma clang fp contract(off)
+  int64_t f;
+  int r;
+  if (j < 0x80000000LL) {                                 // the common case: one 32-bit division
+    const unsigned q = (unsigned)j / (unsigned)e.hop;
+    f = q;
+    r = (int)((unsigned)j - q * (unsigned)e.hop);
+  } else {
+    f = j / e.hop;
+    r = (int)(j - f * e.hop);
+  }
+  const float g0 = e.gain[f], g1 = e.gain[f + 1];
+  const float w = (float)r * e.inv_hop;
+  const float d = g1 - g0;
+  const float wd = w * d;
+  return g0 + wd;
+}
+
+// the sample a shaped row stages: rounded once, before anything else reads it; a row without an envelope keeps v
+__device__ __forceinline__ float env_mul(float v, const PcmEnv& e, int64_t j) {
+#pragma clang fp contract(off)
+  return e.gain ? v * env_at(e, j) : v;
+}
+
+// timeline index j: zero in a pause, beyond the timeline and at or past `limit` (nothing there is loaded).  ENV: the
+// envelope of the segment first, its de-click ramp after it (the order of a timeline assembled from shaped waves)
+template <bool ENV>
 __device__ __forceinline__ float turn_sample(const TurnSrc& src, int64_t j, int64_t limit) {
   const float* p = nullptr;
   float g = 1.f;
   bool ramped = false;
+  int es = 0;
+  int64_t li = 0;
   for (int s = 0; s < src.n; ++s) {
     const TurnSeg sg = src.segs[s];
     const int64_t i = j - sg.start;
@@ -231,17 +267,34 @@ __device__ __forceinline__ float turn_sample(const TurnSrc& src, int64_t j, int6
     p = in ? sg.x + i : p;
     g = in ? gs : g;
     ramped = in ? (rise || fall >= 0) : ramped;
+    if constexpr (ENV) {
+      es = in ? s : es;
+      li = in ? i : li;
+    }
   }
   if (!p || j >= limit) return 0.f;
-  const float v = *p;
+  float v = *p;
+  if constexpr (ENV) v = env_mul(v, src.envs[es], li);
   return ramped ? v * g : v;
 }
 
 // the window of the plain row's resample_stage, from the timeline
+template <bool ENV>
 __device__ __forceinline__ void resample_stage(float* xs, const TurnSrc& src, int64_t j0, int64_t t_last,
                                                int L, int M, int K, int left, int64_t limit) {
   const int W = (int)((t_last * M) / L - left + K - j0);
-  for (int i = threadIdx.x; i < W; i += kResampleTile) xs[i] = turn_sample(src, j0 + i, limit);
+  for (int i = threadIdx.x; i < W; i += kResampleTile) xs[i] = turn_sample<ENV>(src, j0 + i, limit);
+}
+
+// the window of the plain row's resample_stage, shaped (a row of the launch without an envelope: the sample itself)
+__device__ __forceinline__ void resample_stage_env(float* xs, const float* __restrict__ xb, const PcmEnv& env,
+                                                   int64_t j0, int64_t t_last, int L, int M, int K, int left,
+                                                   int64_t limit) {
+  const int W = (int)((t_last * M) / L - left + K - j0);
+  for (int i = threadIdx.x; i < W; i += kResampleTile) {
+    const int64_t j = j0 + i;
+    xs[i] = (j >= 0 && j < limit) ? env_mul(xb[j], env, j) : 0.f;
+  }
 }
 
 // output t from the staged window
@@ -380,6 +433,11 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - TURN = true: the row's input is the timeline of `src` (r.x is null): the staging, and the direct
 //     read of FIR = false, go through turn_sample; in_total / in_avail count timeline samples.  TURN = false never
 //     reads `src`: those instantiations are the kernels of before
+//   - ENV = true: a row may carry a gain envelope `env` (a turn row: one per segment, src.envs).  The
+//     sample is multiplied where the source is read: the staging, the direct read of FIR = false, the limited tile's
+//     window and turn_sample; FIR, peak, static gain, limiter, fade and clip see the shaped signal.  A row of such a
+//     launch without one (gain null) executes no multiply.  ENV = false never reads `env`: those instantiations are the
+//     kernels of before, and a launch in which no row is shaped uses them
 // ---------------------------------------------------------------------------------------------------
 // what a wire launch stores for the int16 q
 template <int LAW>
@@ -400,18 +458,20 @@ __device__ __forceinline__ float fade_gain(const PcmFade& f, int64_t t) {
   return k < f.count ? (float)(f.count - k) * f.inv : 0.f;
 }
 
-template <bool FIR, int LAW, bool FADE, bool TURN>
+template <bool FIR, int LAW, bool FADE, bool TURN, bool ENV>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
                                                        const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio, const TurnSrc& src);
+                                                       double ratio, const TurnSrc& src, const PcmEnv& env);
 
-template <bool FIR, bool LIM, int LAW, bool FADE, bool TURN = false>
+template <bool FIR, bool LIM, int LAW, bool FADE, bool TURN = false, bool ENV = false>
 __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
                                                     int L, int M, int K, int left, double ratio,
                                                     short* __restrict__ packed, const LimiterParams& lim,
-                                                    const PcmFade& fade, const TurnSrc& src = TurnSrc{nullptr, 0}) {
+                                                    const PcmFade& fade,
+                                                    const TurnSrc& src = TurnSrc{nullptr, 0, nullptr},
+                                                    const PcmEnv& env = PcmEnv{nullptr, 0, 0, 0.f}) {
   using Sample = WireSample<LAW>;
   using W = typename Sample::type;
   W* pcm = reinterpret_cast<W*>(r.pcm);
@@ -436,8 +496,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   }
   const int64_t limit = n < r.in_avail ? n : r.in_avail;
   if constexpr (LIM) {
-    resample_pcm16_limited<FIR, LAW, FADE, TURN>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left, ratio,
-                                                 src);
+    resample_pcm16_limited<FIR, LAW, FADE, TURN, ENV>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left,
+                                                      ratio, src, env);
     return;
   }
   const float* xb = r.x;
@@ -447,7 +507,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
     if (t_last > n_out - 1) t_last = n_out - 1;
     if (t_last > r.out_end - 1) t_last = r.out_end - 1;
     j0 = resample_window_first(t0, L, M, left);
-    if constexpr (TURN) resample_stage(xs, src, j0, t_last, L, M, K, left, limit);
+    if constexpr (TURN) resample_stage<ENV>(xs, src, j0, t_last, L, M, K, left, limit);
+    else if constexpr (ENV) resample_stage_env(xs, xb, env, j0, t_last, L, M, K, left, limit);
     else resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
     __syncthreads();
   }
@@ -455,7 +516,8 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
   const bool live = t < r.out_end && t < n_out;
   if (live) {
     if constexpr (FIR) v = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
-    else if constexpr (TURN) v = turn_sample(src, t, limit);
+    else if constexpr (TURN) v = turn_sample<ENV>(src, t, limit);
+    else if constexpr (ENV) v = t < limit ? env_mul(xb[t], env, t) : 0.f;
     else v = t < limit ? xb[t] : 0.f;
   }
   if (r.running) {
@@ -495,12 +557,12 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
 //      A fade scales y, not v: the limiter sees the unfaded signal, and |y| only shrinks (the ramp is below 1)
 // LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
 // over the workgroup; no thread leaves before the last barrier.
-template <bool FIR, int LAW, bool FADE, bool TURN>
+template <bool FIR, int LAW, bool FADE, bool TURN, bool ENV>
 __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
                                                        const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
                                                        typename WireSample<LAW>::type* pk,
                                                        const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio, const TurnSrc& src) {
+                                                       double ratio, const TurnSrc& src, const PcmEnv& env) {
   const int La = lim.lookahead, H = lim.hold;
   const float c = lim.ceiling;
   int64_t t_end = t0 + kResampleTile;
@@ -520,7 +582,8 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     int64_t k_hi = lo + S - 1;
     if (k_hi > n_out - 1) k_hi = n_out - 1;
     j0 = resample_window_first(k_lo, L, M, left);
-    if constexpr (TURN) resample_stage(lds, src, j0, k_hi, L, M, K, left, limit);
+    if constexpr (TURN) resample_stage<ENV>(lds, src, j0, k_hi, L, M, K, left, limit);
+    else if constexpr (ENV) resample_stage_env(lds, xb, env, j0, k_hi, L, M, K, left, limit);
     else resample_stage(lds, xb, j0, k_hi, L, M, K, left, limit);
     __syncthreads();
   }
@@ -532,7 +595,8 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     float v = 0.f;
     if (k >= 0 && k < n_out) {
       if constexpr (FIR) v = resample_output(lds, j0, k, bank, L, M, K, left, ratio);
-      else if constexpr (TURN) v = turn_sample(src, k, limit);
+      else if constexpr (TURN) v = turn_sample<ENV>(src, k, limit);
+      else if constexpr (ENV) v = k < limit ? env_mul(xb[k], env, k) : 0.f;
       else v = k < limit ? xb[k] : 0.f;
       if (k >= t0 && k < t_end) top = fmaxf(top, fabsf(v));
       if (p > 0.01f) v = (v / p) * 0.9f;
@@ -579,21 +643,28 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
 }
 
 // Ranged kernel (mbv_resample_pcm16_range, mbv_resample_g711_range): row blockIdx.y of [B] tensors, one range for all
-// rows; pcm_stride counts stored samples (int16, or bytes with a codec).  FADE = false never reads `fade`
-template <bool FIR, bool LIM, int LAW, bool FADE>
+// rows; pcm_stride counts stored samples (int16, or bytes with a codec).  FADE = false never reads `fade`, ENV = false
+// never reads `env` / `env_stride` (row b's table starts at env.gain + b env_stride)
+template <bool FIR, bool LIM, int LAW, bool FADE, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
                             int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
                             double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
                             typename WireSample<LAW>::type* __restrict__ pcm, int64_t pcm_stride,
                             unsigned* __restrict__ running, int64_t* __restrict__ out_samples, LimiterParams lim,
-                            PcmFade fade) {
+                            PcmFade fade, PcmEnv env, int64_t env_stride) {
   extern __shared__ float xs[];
   const int b = blockIdx.y;
   const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
                      peak ? peak + b : nullptr, reinterpret_cast<short*>(pcm + (int64_t)b * pcm_stride), pcm_stride,
                      running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
-  resample_pcm16_tile<FIR, LIM, LAW, FADE>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade);
+  if constexpr (ENV) {
+    env.gain += (int64_t)b * env_stride;
+    resample_pcm16_tile<FIR, LIM, LAW, FADE, false, true>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade,
+                                                          TurnSrc{nullptr, 0, nullptr}, env);
+  } else {
+    resample_pcm16_tile<FIR, LIM, LAW, FADE>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade);
+  }
 }
 
 namespace {
@@ -605,31 +676,41 @@ void with_law(int law, F f) {
   else f(std::integral_constant<int, kLawNone>{});
 }
 
+// f(ENV as a std::bool_constant): the shaped instantiation only for a launch in which a row carries an envelope
+template <typename F>
+void with_env(bool shaped, F f) {
+  if (shaped) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 template <bool LIM>
 void launch_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail, const float* bank,
                   const ResampleGeom& g, int64_t out_first, int64_t out_count, const float* peak, void* pcm,
                   int64_t pcm_stride, unsigned* running, int64_t* out_samples, const LimiterParams& lim, size_t lds,
-                  int law, const PcmFade& fade, hipStream_t s) {
+                  int law, const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s) {
   int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
   const dim3 grid((unsigned)bx, B), block(kResampleTile);
-  auto launch = [&](auto lc, auto fc) {
+  auto launch = [&](auto lc, auto fc, auto ec) {
     constexpr int LAW = decltype(lc)::value;
     constexpr bool FADE = decltype(fc)::value;
+    constexpr bool ENV = decltype(ec)::value;
     auto* out = static_cast<typename WireSample<LAW>::type*>(pcm);
     if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW, FADE>), grid, block, lds, s, x, valid, in_stride,
-                         in_avail, bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count, peak, out,
-                         pcm_stride, running, out_samples, lim, fade);
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW, FADE, ENV>), grid, block, lds, s, x, valid,
+                         in_stride, in_avail, bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count,
+                         peak, out, pcm_stride, running, out_samples, lim, fade, env, env_stride);
     } else {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW, FADE>), grid, block, lds, s, x, valid,
+      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW, FADE, ENV>), grid, block, lds, s, x, valid,
                          in_stride, in_avail, bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, out,
-                         pcm_stride, running, out_samples, lim, fade);
+                         pcm_stride, running, out_samples, lim, fade, env, env_stride);
     }
   };
   with_law(law, [&](auto lc) {
-    if (fade.count >= 0) launch(lc, std::true_type{});
-    else launch(lc, std::false_type{});
+    with_env(env.gain != nullptr, [&](auto ec) {
+      if (fade.count >= 0) launch(lc, std::true_type{}, ec);
+      else launch(lc, std::false_type{}, ec);
+    });
   });
 }
 }  // namespace
@@ -638,153 +719,178 @@ void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, i
                                          int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
                                          int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
                                          unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         const PcmFade& fade, hipStream_t s) {
+                                         const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s) {
   const size_t lds = (size_t)limiter_lds_floats(g, bank != nullptr, lim) * sizeof(float);
   launch_range<true>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                     out_samples, lim, lds, law, fade, s);
+                     out_samples, lim, lds, law, fade, env, env_stride, s);
 }
 
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, const PcmFade& fade, hipStream_t s) {
+                                 int64_t* out_samples, int law, const PcmFade& fade, const PcmEnv& env,
+                                 int64_t env_stride, hipStream_t s) {
   const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
   launch_range<false>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                      out_samples, LimiterParams{}, lds, law, fade, s);
+                      out_samples, LimiterParams{}, lds, law, fade, env, env_stride, s);
 }
 
 // Pooled ranged kernel (mbv_resample_pcm16_chunks, mbv_resample_g711_chunks): row blockIdx.y of a table, each with its
-// own range; the grid holds the tiles of the longest one
-template <bool FIR, int LAW>
+// own range; the grid holds the tiles of the longest one.  ENV: envs[i] beside rows[i] (never read otherwise)
+template <bool FIR, int LAW, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const PcmFade* __restrict__ fades,
                            const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                           short* __restrict__ packed) {
+                           short* __restrict__ packed, const PcmEnv* __restrict__ envs) {
   extern __shared__ float xs[];
   const PcmPoolRow r = rows[blockIdx.y];
   const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, false, LAW, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade);
+  if constexpr (ENV)
+    resample_pcm16_tile<FIR, false, LAW, true, false, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{},
+                                                            fade, TurnSrc{nullptr, 0, nullptr}, envs[blockIdx.y]);
+  else
+    resample_pcm16_tile<FIR, false, LAW, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade);
 }
 
 // the same table through the limited tile, each row with its own limiter
-template <bool FIR, int LAW>
+template <bool FIR, int LAW, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const PcmFade* __restrict__ fades,
                                    const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                                   short* __restrict__ packed) {
+                                   short* __restrict__ packed, const PcmEnv* __restrict__ envs) {
   extern __shared__ float xs[];
   const PcmLimRow r = rows[blockIdx.y];
   const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, true, LAW, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade);
+  if constexpr (ENV)
+    resample_pcm16_tile<FIR, true, LAW, true, false, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
+                                                           TurnSrc{nullptr, 0, nullptr}, envs[blockIdx.y]);
+  else
+    resample_pcm16_tile<FIR, true, LAW, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade);
 }
 
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, int n, int64_t max_count,
-                                        const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
-                                        int law, hipStream_t s) {
+void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
+                                        int64_t max_count, const float* bank, const ResampleGeom& g,
+                                        int64_t lds_floats, void* packed, int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
   const size_t lds = (size_t)lds_floats * sizeof(float);
   short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
   with_law(law, [&](auto lc) {
-    constexpr int LAW = decltype(lc)::value;
-    if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW>), grid, block, lds, s, rows, fades, bank, g.L,
-                         g.M, g.K, g.left, g.ratio, pk);
-    } else {
-      hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW>), grid, block, lds, s, rows, fades, bank, 1, 1,
-                         0, 0, 1.0, pk);
-    }
+    with_env(envs != nullptr, [&](auto ec) {
+      constexpr int LAW = decltype(lc)::value;
+      constexpr bool ENV = decltype(ec)::value;
+      if (bank) {
+        hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW, ENV>), grid, block, lds, s, rows, fades, bank,
+                           g.L, g.M, g.K, g.left, g.ratio, pk, envs);
+      } else {
+        hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW, ENV>), grid, block, lds, s, rows, fades,
+                           bank, 1, 1, 0, 0, 1.0, pk, envs);
+      }
+    });
   });
 }
 
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, int n, int64_t max_count,
-                                const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s) {
+void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
+                                int64_t max_count, const float* bank, const ResampleGeom& g, void* packed, int law,
+                                hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
   const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
   short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
   with_law(law, [&](auto lc) {
-    constexpr int LAW = decltype(lc)::value;
-    if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW>), grid, block, lds, s, rows, fades, bank, g.L, g.M,
-                         g.K, g.left, g.ratio, pk);
-    } else {
-      hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW>), grid, block, lds, s, rows, fades, bank, 1, 1, 0, 0,
-                         1.0, pk);
-    }
+    with_env(envs != nullptr, [&](auto ec) {
+      constexpr int LAW = decltype(lc)::value;
+      constexpr bool ENV = decltype(ec)::value;
+      if (bank) {
+        hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW, ENV>), grid, block, lds, s, rows, fades, bank, g.L,
+                           g.M, g.K, g.left, g.ratio, pk, envs);
+      } else {
+        hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW, ENV>), grid, block, lds, s, rows, fades, bank, 1, 1,
+                           0, 0, 1.0, pk, envs);
+      }
+    });
   });
 }
 
 // The pooled kernels over turn rows (mbv_resample_turns): the same tile, its input the row's slice of the call's
-// segment table
-template <bool FIR, int LAW>
+// segment table.  ENV: seg_envs[k] beside segs[k] (never read otherwise)
+template <bool FIR, int LAW, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_turn_kernel(const PcmPoolRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
                            const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
                            const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                           short* __restrict__ packed) {
+                           short* __restrict__ packed, const PcmEnv* __restrict__ seg_envs) {
   extern __shared__ float xs[];
   const PcmPoolRow r = rows[blockIdx.y];
   const TurnSlice sl = slices[blockIdx.y];
   const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, false, LAW, true, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade,
-                                                   TurnSrc{segs + sl.first, sl.count});
+  resample_pcm16_tile<FIR, false, LAW, true, true, ENV>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{},
+                                                        fade,
+                                                        TurnSrc{segs + sl.first, sl.count,
+                                                                ENV ? seg_envs + sl.first : nullptr});
 }
 
-template <bool FIR, int LAW>
+template <bool FIR, int LAW, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_turn_limited_kernel(const PcmLimRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
                                    const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
                                    const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                                   short* __restrict__ packed) {
+                                   short* __restrict__ packed, const PcmEnv* __restrict__ seg_envs) {
   extern __shared__ float xs[];
   const PcmLimRow r = rows[blockIdx.y];
   const TurnSlice sl = slices[blockIdx.y];
   const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, true, LAW, true, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
-                                                  TurnSrc{segs + sl.first, sl.count});
+  resample_pcm16_tile<FIR, true, LAW, true, true, ENV>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
+                                                       TurnSrc{segs + sl.first, sl.count,
+                                                               ENV ? seg_envs + sl.first : nullptr});
 }
 
 void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                         const PcmFade* fades, int n, int64_t max_count, const float* bank,
-                                         const ResampleGeom& g, int64_t lds_floats, void* packed, int law,
-                                         hipStream_t s) {
+                                         const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
+                                         const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
+                                         int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
   const size_t lds = (size_t)lds_floats * sizeof(float);
   short* pk = static_cast<short*>(packed);
   with_law(law, [&](auto lc) {
-    constexpr int LAW = decltype(lc)::value;
-    if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<true, LAW>), grid, block, lds, s, rows, slices, segs,
-                         fades, bank, g.L, g.M, g.K, g.left, g.ratio, pk);
-    } else {
-      hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<false, LAW>), grid, block, lds, s, rows, slices, segs,
-                         fades, bank, 1, 1, 0, 0, 1.0, pk);
-    }
+    with_env(seg_envs != nullptr, [&](auto ec) {
+      constexpr int LAW = decltype(lc)::value;
+      constexpr bool ENV = decltype(ec)::value;
+      if (bank) {
+        hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<true, LAW, ENV>), grid, block, lds, s, rows, slices,
+                           segs, fades, bank, g.L, g.M, g.K, g.left, g.ratio, pk, seg_envs);
+      } else {
+        hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<false, LAW, ENV>), grid, block, lds, s, rows, slices,
+                           segs, fades, bank, 1, 1, 0, 0, 1.0, pk, seg_envs);
+      }
+    });
   });
 }
 
 void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                 const PcmFade* fades, int n, int64_t max_count, const float* bank,
-                                 const ResampleGeom& g, void* packed, int law, hipStream_t s) {
+                                 const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
+                                 const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s) {
   int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
   const dim3 grid((unsigned)bx, n), block(kResampleTile);
   const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
   short* pk = static_cast<short*>(packed);
   with_law(law, [&](auto lc) {
-    constexpr int LAW = decltype(lc)::value;
-    if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_turn_kernel<true, LAW>), grid, block, lds, s, rows, slices, segs, fades, bank,
-                         g.L, g.M, g.K, g.left, g.ratio, pk);
-    } else {
-      hipLaunchKernelGGL((resample_pcm16_turn_kernel<false, LAW>), grid, block, lds, s, rows, slices, segs, fades, bank,
-                         1, 1, 0, 0, 1.0, pk);
-    }
+    with_env(seg_envs != nullptr, [&](auto ec) {
+      constexpr int LAW = decltype(lc)::value;
+      constexpr bool ENV = decltype(ec)::value;
+      if (bank) {
+        hipLaunchKernelGGL((resample_pcm16_turn_kernel<true, LAW, ENV>), grid, block, lds, s, rows, slices, segs, fades,
+                           bank, g.L, g.M, g.K, g.left, g.ratio, pk, seg_envs);
+      } else {
+        hipLaunchKernelGGL((resample_pcm16_turn_kernel<false, LAW, ENV>), grid, block, lds, s, rows, slices, segs,
+                           fades, bank, 1, 1, 0, 0, 1.0, pk, seg_envs);
+      }
+    });
   });
 }
 

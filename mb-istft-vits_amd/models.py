@@ -153,6 +153,113 @@ def _prosody_args(who, length_scale, extra_frames, fit_frames, fit_bounds, durat
     return scalar, scale, extra, fit
 
 
+GAIN_MAX = 16.0              # largest per-token gain (about +24 dB): a convention, not a measurement
+
+
+def gain_of_db(db):
+    """A level change in dB -> the linear factor `gain=` takes: 10 ** (db / 20) in Python floats, then rounded to fp32;
+    -inf gives 0 (silence).  NaN and +inf are a ValueError."""
+    db = float(db)
+    if db == -math.inf:
+        return 0.0
+    if not math.isfinite(db):
+        raise ValueError("gain_of_db: need a finite level in dB (or -inf for silence), got %r" % db)
+    return float(np.float32(10.0 ** (db / 20.0)))
+
+
+def _gain_arg(who, gain, B, T, row=False):
+    """`gain=` of an entry, checked on the host -> None, or the per-token linear gains as a CPU fp32 tensor [B, T]: a
+    host sequence or CPU tensor (the mark-up is parsed on the host) of T_text values per row, finite, in [0, GAIN_MAX].
+    A device tensor is refused."""
+    if gain is None:
+        return None
+    shapes = ((T,), (1, T), (1, 1, T)) if row else ((B, T), (B, 1, T))
+    names = "[T_text]" if row else "[B, T_text]"
+    if torch.is_tensor(gain):
+        if gain.is_cuda:
+            raise TypeError("%s: gain must be a host sequence or a CPU tensor (it is checked on the host), got a "
+                            "device tensor" % who)
+        if gain.dtype.is_complex or gain.dtype == torch.bool:
+            raise TypeError("%s: gain must hold real numbers, got %s" % (who, gain.dtype))
+        g = gain.detach().to(torch.float64)
+    else:
+        if isinstance(gain, (str, bytes)):
+            raise TypeError("%s: gain must be a sequence of numbers %s" % (who, names))
+        try:
+            arr = np.asarray(gain)
+        except Exception:
+            raise TypeError("%s: gain must be a sequence of numbers %s" % (who, names))
+        if arr.dtype == np.bool_ or arr.dtype.kind not in "iuf":
+            raise TypeError("%s: gain must hold real numbers, got %s" % (who, arr.dtype))
+        g = torch.from_numpy(arr.astype(np.float64))
+    if tuple(g.shape) not in shapes:
+        raise ValueError("%s: gain must be %s = %s, got %s" % (who, names, shapes[0], tuple(g.shape)))
+    g = g.reshape(B, T)
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("%s: gain must be finite" % who)
+    if bool((g < 0).any()) or bool((g > GAIN_MAX).any()):
+        raise ValueError("%s: gain must be in [0, GAIN_MAX = %g] (linear factors; gain_of_db converts)" % (who, GAIN_MAX))
+    return g.to(torch.float32).contiguous()
+
+
+class Envelope:
+    """The gain envelope of a wire call (`wire.Envelope`): the frame gains of `net.frame_gain` /
+    `st.frame_gain` and the model's samples per frame.
+      gain               fp32 device tensor [F + 1] (one row) or [B, F + 1] with unit stride along a row: G of the
+                         row(s); model-rate sample j is scaled by G[f] + (j - f hop) / hop * (G[f + 1] - G[f]), f = j // hop
+      samples_per_frame  hop >= 1
+    A wire call refuses an envelope whose (F * hop) is below the samples of its row."""
+
+    __slots__ = ("gain", "hop", "frames", "rows")
+
+    def __init__(self, gain, samples_per_frame):
+        if isinstance(samples_per_frame, (bool, np.bool_)) or not isinstance(samples_per_frame, (int, np.integer)):
+            raise TypeError("Envelope: samples_per_frame must be an integer, got %s" % type(samples_per_frame).__name__)
+        if int(samples_per_frame) < 1 or int(samples_per_frame) >= 1 << 31:
+            raise ValueError("Envelope: samples_per_frame must be in [1, 2^31), got %d" % int(samples_per_frame))
+        if not torch.is_tensor(gain):
+            raise TypeError("Envelope: gain must be an fp32 device tensor [F + 1] or [B, F + 1] (net.frame_gain, "
+                            "st.frame_gain), got %s" % type(gain).__name__)
+        if gain.dtype != torch.float32:
+            raise TypeError("Envelope: gain must be float32, got %s" % gain.dtype)
+        if not gain.is_cuda:
+            raise TypeError("Envelope: gain must live on the device (the wire kernels read it in place)")
+        if gain.dim() not in (1, 2) or gain.shape[-1] < 2 or gain.stride(-1) != 1:
+            raise ValueError("Envelope: gain must be [F + 1] or [B, F + 1] with F >= 1 and unit stride, got %s"
+                             % (tuple(gain.shape),))
+        self.gain, self.hop = gain, int(samples_per_frame)
+        self.frames = gain.shape[-1] - 1
+        self.rows = 1 if gain.dim() == 1 else gain.shape[0]
+
+    def __repr__(self):
+        return "Envelope(%d row%s, %d frames of %d samples)" % (self.rows, "" if self.rows == 1 else "s", self.frames, self.hop)
+
+    def check(self, who, rows, samples, device=None):
+        """ValueError unless the envelope has `rows` rows, covers `samples` model-rate samples and (when given) lives
+        on `device`."""
+        if self.rows != rows:
+            raise ValueError("%s: the envelope has %d row(s), the call %d" % (who, self.rows, rows))
+        if self.frames * self.hop < int(samples):
+            raise ValueError("%s: the envelope covers %d frames x %d = %d samples, the row holds %d"
+                             % (who, self.frames, self.hop, self.frames * self.hop, int(samples)))
+        if device is not None and self.gain.device != device:
+            raise ValueError("%s: the envelope's gain is on %s, the model on %s" % (who, self.gain.device, device))
+
+    @property
+    def stride(self):
+        return self.gain.stride(0) if self.gain.dim() == 2 and self.rows > 1 else 0
+
+    def c(self):
+        """-> the `_capi.MbvPcmEnvelope` of row 0 (inv_hop = fp32 1 / fp32 hop, as the entries check it)."""
+        return _capi.MbvPcmEnvelope(self.gain.data_ptr(), self.frames, self.hop,
+                                    float(np.float32(1.0) / np.float32(self.hop)))
+
+
+def _envelope_c(envelope):
+    """None -> the all-zero table row of a row without an envelope."""
+    return _capi.MbvPcmEnvelope(None, 0, 0, 0.0) if envelope is None else envelope.c()
+
+
 def _seed_value(v, what="seed"):
     """One seed of the device generator -> int in [0, 2^64).  TypeError for anything that is not an
     integer (bool and floats included), ValueError outside the range."""
@@ -204,14 +311,16 @@ class Request:
                          [0, 2^64): the request's noise is a function of the seed alone, at row 0
       marks              True: the stream gets `marks`, the z-frame at which every token starts, as
                          `infer_stream(marks=True)` gives them
+      gain               per-token volume, as `infer_stream(gain=)`: T_text linear factors in [0, GAIN_MAX] on the host
+                         (`gain_of_db` converts); the stream gets `frame_gain` and the wire path shapes it
     Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
-                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks", "scale", "extra", "fit")
+                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks", "scale", "extra", "fit", "gain")
 
     def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
                  chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
-                 fit_frames=None, fit_bounds=FIT_BOUNDS):
+                 fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None):
         self.seed = None if seed is None else _seed_value(seed, "Request: seed")
         self.marks = bool(marks)
         if not torch.is_tensor(x):
@@ -238,6 +347,8 @@ class Request:
         self.scale = None if scale is None else scale.reshape(-1)
         self.extra = None if extra is None else extra.reshape(-1)
         self.fit = None if fit is None else fit[0]
+        gain = _gain_arg("Request", gain, 1, self.x.numel(), row=True)
+        self.gain = None if gain is None else gain.reshape(-1)
         self.noise_scale = float(noise_scale)
         self.noise_scale_w = float(noise_scale_w)
         for name in ("noise_scale", "length_scale", "noise_scale_w"):
@@ -720,7 +831,7 @@ class SynthesizerTrn(nn.Module):
     def _run(self, x, x_lengths, sid, noise_scale, length_scale, max_len, decode,
              frames_hook=None, noise_scale_w=1., noise_w=None, outputs=None, stat_reduce=None,
              prior_rows=None, trim=False, ragged=False, durations=None, seed=None, marks_out=None, extra_frames=None,
-             fit_frames=None, fit_bounds=FIT_BOUNDS):
+             fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None, gain_out=None, gain_max_len=None):
         """One encode + synthesize pair.
           outputs      None = every tensor of the reference's 8-tuple; or a collection of names from
                        _OUTPUT_NAMES: only those are materialised (the others come back as None and
@@ -741,7 +852,10 @@ class SynthesizerTrn(nn.Module):
                        `mbv_token_marks` launch; they ride in the read-back of T'max, with the rows' x_lengths)
           length_scale, extra_frames, fit_frames, fit_bounds    the prosody controls (see `infer`): with any of them one
                        `mbv_shape_durations` launch follows the encode, where `mbv_set_durations` would stand; the
-                       fit's factors and statuses ride in the same read-back and are left in `self.last_fit`"""
+                       fit's factors and statuses ride in the same read-back and are left in `self.last_fit`
+          gain, gain_out, gain_max_len    per-token volume (see `infer_stream`): gain_out, a list, receives the frame
+                       gains [B, F + 1], F = T'max clipped to gain_max_len, from one `mbv_frame_gain` launch behind
+                       the read-back (which tells F), in front of the synthesize; no synchronisation of its own"""
         h = self._ensure_handle()
         L = _capi.lib()
         x, x_lengths, sid = self._check_inputs(x, x_lengths, sid)
@@ -752,6 +866,7 @@ class SynthesizerTrn(nn.Module):
         length_scale, scale, extra, fit = _prosody_args("infer", length_scale, extra_frames, fit_frames, fit_bounds,
                                                         durations, B, T)
         shaped = scale is not None or extra is not None or fit is not None
+        gain = _gain_arg("infer", gain, B, T)
         self.last_fit = None
         if durations is not None:
             durations, dur_dtype = self._check_durations(durations, B, T, length_scale)
@@ -819,6 +934,14 @@ class SynthesizerTrn(nn.Module):
                                                              "; a per-token scale must be finite and >= 0, extra frames >= 0" if shaped else ""))
             if frames_hook is not None:
                 Tp = int(frames_hook(Tp))
+            if gain is not None:                    # the scan of the encode is still in place: spread it over the frames
+                Fg = Tp if gain_max_len is None else max(0, min(Tp, int(gain_max_len)))
+                if Fg <= 0:
+                    raise ValueError("max_len leaves no frames to decode")
+                frame_gain = torch.empty(B, Fg + 1, device=dev, dtype=torch.float32)
+                gain_dev = gain.to(dev)
+                self._launch(h, "mbv_frame_gain", gain_dev, frame_gain, Fg + 1, Fg, stream=stream)
+                gain_out.append(frame_gain)
             # the reference draws randn_like(m_p) even at noise_scale == 0 (models.py:729)
             if seeds is not None:
                 # a function of (seed, row, channel, frame): no generator, no dependence on the batch or its padding;
@@ -1138,7 +1261,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
                      chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
-                     fit_frames=None, fit_bounds=FIT_BOUNDS):
+                     fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
         flows exactly as `infer` does (same random draws; `durations` and `seed` as in `infer`), then returns `dec_stream` of
         z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
@@ -1151,11 +1274,20 @@ class SynthesizerTrn(nn.Module):
                  nothing is added.
           a tensor `length_scale`, `extra_frames`, `fit_frames`, `fit_bounds`    the prosody controls of `infer`.  With
                  `fit_frames` the stream gets `st.fit_scale` and `st.fit_status`, one value per row (the value itself
-                 for a single utterance); they too ride in the call's one read-back.  Else both are None."""
+                 for a single utterance); they too ride in the call's one read-back.  Else both are None.
+          gain   per-token volume: a host sequence or CPU tensor [B, T_text] of linear factors, finite,
+                 in [0, GAIN_MAX] (`gain_of_db` converts; checked here, a device tensor is refused).  The stream gets
+                 `st.frame_gain`, fp32 [B, F + 1] on the device, F the frames the stream keeps: the gain of the token
+                 that holds each frame, held behind a row's end (one `mbv_frame_gain` launch, no synchronisation).  The
+                 decode is untouched: `st.o` is bitwise the stream without `gain=`.  The wire path (`stream_pcm16`,
+                 `PcmPool.add`, `Turn.append`) picks `st.frame_gain` up and shapes the samples in front of its filter
+                 and limiter.  None (default): `st.frame_gain` is None and nothing is launched."""
         marks_out = [] if marks else None
+        gain_out = []
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
                       noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed,
-                      marks_out=marks_out, extra_frames=extra_frames, fit_frames=fit_frames, fit_bounds=fit_bounds)
+                      marks_out=marks_out, extra_frames=extra_frames, fit_frames=fit_frames, fit_bounds=fit_bounds,
+                      gain=gain, gain_out=gain_out, gain_max_len=max_len)
         fitted = self.last_fit
         y_mask, z, y_lengths = r[5], r[6][0], r[8]
         Tp = z.shape[2]
@@ -1173,6 +1305,8 @@ class SynthesizerTrn(nn.Module):
             st.marks = rows[0] if len(rows) == 1 else rows
         if fitted is not None:
             st.fit_scale, st.fit_status = (v[0] if len(v) == 1 else v for v in fitted)
+        if gain_out:
+            st.frame_gain = gain_out[0]
         return st
 
     # ------------------------------------------------------------------ pooled admission
@@ -1254,6 +1388,50 @@ class SynthesizerTrn(nn.Module):
         none otherwise."""
         return int(_capi.lib().mbv_shape_runs(self._ensure_handle()))
 
+    def gain_runs(self):
+        """Launches of the frame-gain kernel made on this model's handle so far (`mbv_gain_runs`): one per call with
+        `gain=`, one per admission run that holds such a request, none otherwise."""
+        return int(_capi.lib().mbv_gain_runs(self._ensure_handle()))
+
+    @torch.no_grad()
+    def frame_gain(self, gain, durations, y_lengths=None):
+        """Per-token gains -> the frame gains a `wire.Envelope` takes, for users of the batch `infer` (DESIGN §7.20;
+        `mbv_op_frame_gain`, the kernel `infer_stream(gain=)` runs).
+          gain       host sequence / CPU tensor [B, T_text], as `infer_stream(gain=)`
+          durations  what the length regulator used: `infer(...)[4]`, the path attn [B, 1, T', T_text] (summed over the
+                     frames here), or frames per token [B, T_text] / [B, 1, T_text] (integers in any dtype)
+          y_lengths  None = every row keeps the sum of its durations; else int64 [B] kept frames (after max_len)
+        -> fp32 [B, F + 1] on the device, F = T' of attn, else the largest kept length (one host read)."""
+        h = self._ensure_handle()
+        dev = self._device()
+        if not torch.is_tensor(durations):
+            raise TypeError("frame_gain: durations must be a tensor (infer(...)[4], or frames per token)")
+        F = None
+        if durations.dim() == 4:
+            if durations.shape[1] != 1:
+                raise ValueError("frame_gain: attn must be [B, 1, T', T_text]")
+            F = durations.shape[2]
+            durations = durations.sum(2)
+        if durations.dim() == 3 and durations.shape[1] == 1:
+            durations = durations[:, 0]
+        if durations.dim() != 2:
+            raise ValueError("frame_gain: durations must be [B, T_text], [B, 1, T_text] or attn [B, 1, T', T_text]")
+        B, T = durations.shape
+        gain = _gain_arg("frame_gain", gain, B, T)
+        with torch.cuda.device(dev):
+            cum = torch.cumsum(durations.to(dev).round().to(torch.int64), 1)
+            if y_lengths is None:
+                y = cum[:, -1].contiguous()
+            else:
+                y = _valid_samples(y_lengths, B, dev, "y_lengths")
+            if F is None:
+                F = int(y.max())
+            if F < 1:
+                raise ValueError("frame_gain: no frames")
+            out = torch.empty(B, F + 1, device=dev, dtype=torch.float32)
+            self._launch(h, "mbv_op_frame_gain", cum.to(torch.int32).contiguous(), y, gain.to(dev), out, F + 1, F, B, T)
+        return out
+
     @torch.no_grad()
     def infer_streams(self, requests):
         """Pooled admission: one single-utterance `DecodeStream` per `Request`, in order — what `StreamPool.add` takes —
@@ -1326,7 +1504,9 @@ class SynthesizerTrn(nn.Module):
                 if reqs[i].fit is not None:
                     fit_at[i] = o
                     o += 1
-            scale_p, kept = self._pack_host([r.scale for r in reqs], dev)
+            # (the gains ride in the copy of the scale tables: one concatenated fp32 host tensor)
+            f32_p, kept = self._pack_host([r.scale for r in reqs] + [r.gain for r in reqs], dev)
+            scale_p, gain_p = f32_p[:N], f32_p[N:]
             keep += kept
             extra_p, kept = self._pack_host([r.extra for r in reqs], dev)
             keep += kept
@@ -1396,8 +1576,16 @@ class SynthesizerTrn(nn.Module):
                                                 _capi.NOISE_PRIOR, noise, hip_stream))
             z = [torch.empty(1, I, Td[i], device=dev, dtype=torch.float32) for i in range(N)]
             g = [None] * N
+            frame_gain = {i: torch.empty(1, Td[i] + 1, device=dev, dtype=torch.float32)
+                          for i in range(N) if reqs[i].gain is not None}
             for k, m in enumerate(members):
                 B = len(m)
+                if any(i in frame_gain for i in m):    # the run's gains over its frames: one table-reading launch
+                    grows = (_capi.MbvGainRow * B)()
+                    for row, i in zip(grows, m):
+                        if i in frame_gain:
+                            row.gain, row.out, row.frames = gain_p[i], frame_gain[i].data_ptr(), Td[i]
+                    self._launch(h, "mbv_frame_gain_rows", k, grows, B, stream=hip_stream)
                 rows = (_capi.MbvRow * B)()
                 for row, i in zip(rows, m):
                     row.noise, row.noise_stride, row.noise_scale = noise[i], Tp[i], reqs[i].noise_scale
@@ -1413,6 +1601,8 @@ class SynthesizerTrn(nn.Module):
                 sts[i].marks = [min(int(v), Td[i]) for v in y_host[mark_at[i]:mark_at[i] + t_text[i] + 1]]
             for i, at in fit_at.items():
                 sts[i].fit_scale, sts[i].fit_status = _capi.fit_result(y_host[at])
+            for i, t in frame_gain.items():
+                sts[i].frame_gain = t
             return sts
 
     # ------------------------------------------------------------------ pooled voice conversion
@@ -1713,7 +1903,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def resample_pcm16_range(self, wave, orig_sr, target_sr, in_avail, out_first, out_count, pcm, valid_samples=None,
                              peak=None, running_peak=None, out_samples=None, res_type="kaiser_best", limiter=None,
-                             encoding="pcm16", fade=None):
+                             encoding="pcm16", fade=None, envelope=None):
         """One step of the streamed wire output (`mbv_resample_pcm16_range`; `wire.stream_pcm16` drives it for a
         decode stream): int16 samples [out_first, out_first + out_count) of every row of `pcm` [B, n'] from the
         first `in_avail` samples of `wave` (fp32 [B, 1, n] or [B, n], contiguous, on the device; nothing at or
@@ -1733,6 +1923,9 @@ class SynthesizerTrn(nn.Module):
           fade           None, or (first, count) in output samples: the fade-out of DESIGN §7.16 on every row, through
                          `mbv_resample_pcm16_range_faded` / `mbv_resample_g711_range_faded`; a `_capi.MbvPcmFade` is
                          passed as it is (the entry checks it)
+          envelope       None, or a `wire.Envelope` with B rows: per-token volume, multiplied into the
+                         samples where the kernel reads them, in front of everything else
+                         (`mbv_resample_pcm16_range_shaped`); the bytes are those of the call on `wave * e`
         Writes into the caller's tensors only; no host synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
         law = _law_code(encoding)
@@ -1758,6 +1951,16 @@ class SynthesizerTrn(nn.Module):
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
         args = (wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail), int(out_first),
                 int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
+        if envelope is not None:
+            if not isinstance(envelope, Envelope):
+                raise TypeError("resample_pcm16_range: envelope must be a wire.Envelope, got %s" % type(envelope).__name__)
+            envelope.check("resample_pcm16_range", B, n, dev)
+            if fade is not None and not isinstance(fade, _capi.MbvPcmFade):
+                fade = _capi.pcm_fade(*fade)
+            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
+            self._call("mbv_resample_pcm16_range_shaped", *args, lim, law, C.byref(fade) if fade is not None else None,
+                       C.byref(envelope.c()), envelope.stride)
+            return
         if fade is not None:
             if not isinstance(fade, _capi.MbvPcmFade):
                 fade = _capi.pcm_fade(*fade)
@@ -1776,7 +1979,7 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
-                              encoding="pcm16", fades=None):
+                              encoding="pcm16", fades=None, envelopes=None):
         """The ranged wire step of many streams in ONE launch (`mbv_resample_pcm16_chunks`; `wire.pcm_pool` drives
         it): `chunks` is a ctypes array (or a list) of `_capi.MbvPcmChunk`, each the arguments of
         `resample_pcm16_range` for one row of its own stream, as device addresses.  Every stored value is bitwise
@@ -1787,8 +1990,10 @@ class SynthesizerTrn(nn.Module):
         `packed` are uint8 and receive G.711 bytes (`mbv_resample_g711_chunks`; `pcm_capacity` counts bytes).  `fades`:
         None, or one entry per chunk, each None, a (first, count) or a `_capi.MbvPcmFade`: the fade-out of DESIGN §7.16
         on those chunks (`mbv_resample_pcm16_chunks_faded` / `mbv_resample_g711_chunks_faded`), in the launches the call
-        makes without it; all None is the call without `fades`.  No host synchronisation (beyond the first call for a
-        rate pair)."""
+        makes without it; all None is the call without `fades`.  `envelopes`: None, or one entry per chunk, each None or
+        a one-row `wire.Envelope`: per-token volume on those chunks (`mbv_resample_pcm16_chunks_shaped`),
+        in the launches the call makes without it; all None is the call without `envelopes`.  No host synchronisation
+        (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
         law = _law_code(encoding)
         wire_dtype = torch.uint8 if law else torch.int16
@@ -1803,6 +2008,24 @@ class SynthesizerTrn(nn.Module):
             cap = packed.shape[0]
         unlimited = limits is None or all(l is None for l in limits)
         unfaded = fades is None or all(f is None for f in fades)
+        if envelopes is not None and any(e is not None for e in envelopes):
+            n = len(chunks)
+            for name, t in (("limit", limits), ("fade", fades), ("envelope", envelopes)):
+                if t is not None and len(t) != n:
+                    raise ValueError("resample_pcm16_chunks: one %s per chunk expected (%d), got %d" % (name, n, len(t)))
+            for i, e in enumerate(envelopes):
+                if e is not None:
+                    if not isinstance(e, Envelope):
+                        raise TypeError("resample_pcm16_chunks: envelopes hold wire.Envelope values or None")
+                    e.check("resample_pcm16_chunks: chunk %d" % i, 1, chunks[i].in_total, dev)
+            lim = None if unlimited else (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+            fd = None if unfaded else (_capi.MbvPcmFade * n)(*[
+                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
+                else _capi.pcm_fade(*f) for f in fades])
+            ev = (_capi.MbvPcmEnvelope * n)(*[_envelope_c(e) for e in envelopes])
+            self._call("mbv_resample_pcm16_chunks_shaped", chunks, lim, fd, ev, n, int(orig_sr), int(target_sr), filt,
+                       law, packed, cap)
+            return
         if unlimited and unfaded and not law:
             self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
             return
@@ -1835,14 +2058,16 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def resample_turns(self, turns, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
-                       encoding="pcm16", fades=None):
+                       encoding="pcm16", fades=None, envelopes=None):
         """`resample_pcm16_chunks` for rows whose input is a TIMELINE of utterances (`mbv_resample_turns`, DESIGN §7.18;
         `wire.PcmPool` drives it for its `wire.Turn`s): `turns` is a ctypes array (or a list) of `_capi.MbvTurnChunk`,
         each a chunk with `wave` None, `in_total` / `in_avail` the timeline's total and frontier, and `segs` a ctypes
         array of the `_capi.MbvTurnSeg` its input window touches.  Every stored value is bitwise what
         `resample_pcm16_range` stores for the timeline written out as one row (`wire.assemble_turn`).  `packed`,
         `limits`, `encoding` and `fades` as `resample_pcm16_chunks` takes them; one launch for the unlimited turns and
-        one for the limited ones.  No host synchronisation (beyond the first call for a rate pair)."""
+        one for the limited ones.  `envelopes`: None, or one list per turn with one entry per SEGMENT the turn passes,
+        each None or a one-row `wire.Envelope` over that segment's own samples, applied before its de-click ramp
+        (`mbv_resample_turns_shaped`).  No host synchronisation (beyond the first call for a rate pair)."""
         filt = _filter_code(res_type)
         law = _law_code(encoding)
         wire_dtype = torch.uint8 if law else torch.int16
@@ -1867,6 +2092,25 @@ class SynthesizerTrn(nn.Module):
             fd = (_capi.MbvPcmFade * n)(*[
                 f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
                 else _capi.pcm_fade(*f) for f in fades])
+        if envelopes is not None and any(e is not None for per in envelopes for e in (per or ())):
+            if len(envelopes) != n:
+                raise ValueError("resample_turns: one envelope list per turn expected (%d), got %d" % (n, len(envelopes)))
+            flat = []
+            for i, per in enumerate(envelopes):
+                per = list(per or [None] * turns[i].n_segs)
+                if len(per) != turns[i].n_segs:
+                    raise ValueError("resample_turns: turn %d: one envelope per segment expected (%d), got %d"
+                                     % (i, turns[i].n_segs, len(per)))
+                for k, e in enumerate(per):
+                    if e is not None:
+                        if not isinstance(e, Envelope):
+                            raise TypeError("resample_turns: envelopes hold wire.Envelope values or None")
+                        e.check("resample_turns: turn %d: segment %d" % (i, k), 1, turns[i].segs[k].length, dev)
+                    flat.append(_envelope_c(e))
+            ev = (_capi.MbvPcmEnvelope * max(len(flat), 1))(*flat)
+            self._call("mbv_resample_turns_shaped", turns, lim, fd, ev, n, int(orig_sr), int(target_sr), filt, law,
+                       packed, cap)
+            return
         self._call("mbv_resample_turns", turns, lim, fd, n, int(orig_sr), int(target_sr), filt, law, packed, cap)
 
     @torch.no_grad()

@@ -442,6 +442,7 @@ class DecodeStream:
         self.y_lengths = None
         self.marks = None             # token marks in z-frames (`infer_stream(marks=True)`); a converted stream has none
         self.fit_scale = self.fit_status = None     # the factor and status of `fit_frames=`, else None
+        self.frame_gain = None        # fp32 [B, F + 1] frame gains of `infer_stream(gain=)`, else None
         self._next = 0                # the chunk next() hands out
         self._decoded = 0             # the first chunk not decoded yet (>= _next; ahead of it only through a pool)
 

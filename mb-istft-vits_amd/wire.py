@@ -56,6 +56,12 @@ segments are ordinary single-utterance decode streams of the pool; the wire kern
 (`mbv_resample_turns`: silence in the pauses, a de-click ramp at both ends of every segment), so one resampler, one
 limiter and one framing run over the joints.  `TurnPlan` is its integer planning, `assemble_turn` the timeline written
 out as one row: the turn's bytes are bitwise `service_pcm16` of that row, `revoke` with `fade=` included.
+
+Volume (DESIGN §7.20): a stream made with `gain=` carries `frame_gain`, the per-token gains spread over its z-frames;
+`Envelope(gain, samples_per_frame)` hands them to the wire kernels, which multiply a continuous envelope into the
+model-rate samples where they read them, in front of the filter, the peak, the limiter and the clip.  `stream_pcm16`,
+`PcmPool.add` / `admit` and `Turn.append` / `admit` pick it up by themselves; `envelope=` names one explicitly.  The
+bytes are those of `service_pcm16` on the waveform times that envelope; rows without one are bitwise what they were.
 """
 import base64
 import ctypes as C
@@ -67,6 +73,7 @@ import torch
 from . import _capi
 # (RESAMPLE_TYPES and ENCODINGS stay names of this module)
 from .models import ENCODINGS, RESAMPLE_TYPES, _filter_code, _g711_law, _law_code      # noqa: F401
+from .models import Envelope, GAIN_MAX, gain_of_db                                      # noqa: F401
 
 G711_ZERO = {"ulaw": 0xFF, "alaw": 0xD5}      # the code of the int16 zero: what the wire kernels store as padding
 # `wave_dtype` of a live wire's raw buffer (MBV_WAVE_*), by its dtype or, for uint8, its `in_encoding`
@@ -328,6 +335,24 @@ def _fade_arg(fade):
     return first, count
 
 
+def _envelope_arg(envelope, st, who):
+    """`envelope=` of a wire stream over the decode stream `st` -> None or an `Envelope`: the one given, else the one of
+    `st.frame_gain` (a stream made with `gain=`), else none."""
+    if envelope is None:
+        g = getattr(st, "frame_gain", None)
+        return None if g is None else Envelope(g, st.spf)
+    if not isinstance(envelope, Envelope):
+        raise TypeError("%s: envelope must be a wire.Envelope, got %s" % (who, type(envelope).__name__))
+    return envelope
+
+
+def _refuse_envelope(envelope, who):
+    """The live wires carry no per-token volume: a converted recording has no tokens."""
+    if envelope is not None:
+        raise ValueError("%s: envelope= is not offered on a live wire or a converted recording (no tokens to take a "
+                         "volume from); shape the finished waveform with service_pcm16(envelope=)" % who)
+
+
 def mark_samples(marks, samples_per_frame, model_sr, rate, lookahead=0):
     """Token marks in z-frames (`infer_stream(marks=True)`) -> wire sample indices, in pure integers: a mark at frame f
     maps to ceil(f * samples_per_frame * rate / model_sr) + lookahead, the first wire sample at or after the token's
@@ -374,7 +399,7 @@ class Revoked:
 
 
 def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding="pcm16",
-                     fade=None):
+                     fade=None, envelope=None):
     """`service_pcm16` through the ranged wire kernel over the whole row, which is where the limiter and the G.711
     epilogue live: one launch with a given peak (or none), two with auto_normalize (the first measures the peak the
     second divides by)."""
@@ -396,9 +421,10 @@ def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type
         if peak_in is None and auto_normalize:
             peak_in = torch.zeros(B, device=dev, dtype=torch.float32)
             net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in,
-                                     running_peak=peak_in, res_type=res_type, encoding=encoding)
+                                     running_peak=peak_in, res_type=res_type, encoding=encoding, envelope=envelope)
     net.resample_pcm16_range(wave, model_sr, rate, n, 0, stride, pcm, valid_samples=valid_in, peak=peak_in,
-                             out_samples=valid, res_type=res_type, limiter=lim, encoding=encoding, fade=fade)
+                             out_samples=valid, res_type=res_type, limiter=lim, encoding=encoding, fade=fade,
+                             envelope=envelope)
     if fade is not None:
         with torch.cuda.device(dev):
             valid.clamp_(max=fade[0] + fade[1])
@@ -406,7 +432,7 @@ def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type
 
 
 def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_type="kaiser_best", limiter=None,
-                  peak=None, encoding="pcm16", fade=None, loudness=None):
+                  peak=None, encoding="pcm16", fade=None, loudness=None, envelope=None):
     """tts_vits.py:196-217 for a batch as one GPU chain: resample every utterance from `model_sr` to
     `rate` (skipped when they are equal, as there), then peak-normalise / clip / int16 it.
       o          fp32 [B, 1, n] waveforms of `net.infer` (device)
@@ -431,9 +457,16 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
                wires with the static gain that takes it to the target: the bytes are those of
                `service_pcm16(..., peak=loudness.peak(L))` on the limited path.  `auto_normalize` is ignored then (not
                refused: it is the default), `peak=` beside it is a ValueError.  Combines with `limiter`, `encoding`
-               and `fade`; without a limiter a positive gain can reach the hard clip"""
+               and `fade`; without a limiter a positive gain can reach the hard clip
+      envelope an `Envelope` with B rows (`net.frame_gain`, or `Envelope(st.frame_gain, spf)`): per-token volume
+               (DESIGN §7.20).  Every model-rate sample is scaled where the ranged kernel reads it, so the bytes are
+               those of `service_pcm16(o * e)` with the same arguments: the `auto_normalize` peak is the shaped
+               signal's, and the limiter holds its ceiling on it.  A `loudness` measurement stays on the UNSHAPED
+               waveform: the static gain sets the normal level and the volume modulates around it"""
     law = _law_code(encoding)
     fade = _fade_arg(fade)
+    if envelope is not None and not isinstance(envelope, Envelope):
+        raise TypeError("service_pcm16: envelope must be a wire.Envelope, got %s" % type(envelope).__name__)
     loud = _loudness_arg(loudness, peak, "service_pcm16", stream=False)
     if loud is not None:
         _limit_arg(limiter, rate)                               # refuses bad parameters before the measuring launch
@@ -446,13 +479,14 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
             L = loud.measured_rows(o.shape[0], dev)
         with torch.cuda.device(dev):
             peak = loud.peak(L)
-        return _service_limited(net, o, y_lengths, model_sr, rate, False, res_type, limiter, peak, encoding, fade=fade)
-    if fade is not None:
+        return _service_limited(net, o, y_lengths, model_sr, rate, False, res_type, limiter, peak, encoding, fade=fade,
+                                envelope=envelope)
+    if fade is not None or envelope is not None:
         if limiter is None and peak is not None:
             raise ValueError("service_pcm16: peak= is the static gain of the limited path; without limiter= the "
                              "utterance's own peak is used (auto_normalize)")
         return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding,
-                                fade=fade)
+                                fade=fade, envelope=envelope)
     if limiter is not None:
         return _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding)
     if peak is not None:
@@ -466,7 +500,7 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
                   auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None, encoding="pcm16",
-                  in_encoding=None, fade=None, loudness=None):
+                  in_encoding=None, fade=None, loudness=None, envelope=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -482,6 +516,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     anything is launched when win_size > n_fft or the model has no speakers.  The one host synchronisation is
     the status check `voice_conversion` already has (besides the first-call table uploads of `resample` and
     `spectrogram`)."""
+    _refuse_envelope(envelope, "convert_pcm16")
     _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
     _law_code(encoding)
     _fade_arg(fade)
@@ -580,7 +615,7 @@ def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
     w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
                                 valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
                                 out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim,
-                                encoding=w.encoding, fade=w._fade)
+                                encoding=w.encoding, fade=w._fade, envelope=getattr(w, "_env", None))
 
 
 def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
@@ -624,9 +659,13 @@ class PcmStream:
     `revoked` say where it stands."""
 
     def __init__(self, net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16",
-                 loudness=None):
+                 loudness=None, envelope=None):
         _refuse_live(st)
         loud = _loudness_arg(loudness, peak, "stream_pcm16", stream=True)
+        # per-token volume (DESIGN §7.20): given, or the stream's own frame gains; None: the row is not shaped
+        self._env = _envelope_arg(envelope, st, "stream_pcm16")
+        if self._env is not None:
+            self._env.check("stream_pcm16", st.o.shape[0], st.o.shape[-1], st.o.device)
         self.encoding, dtype = encoding, _wire_dtype(encoding)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
@@ -785,7 +824,7 @@ class PcmStream:
 
 
 def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", limiter=None, encoding="pcm16",
-                 loudness=None):
+                 loudness=None, envelope=None):
     """The streamed `service_pcm16`: wraps a `stream.DecodeStream` (`net.dec_stream` / `net.infer_stream`, not yet
     iterated) in a `PcmStream`.
       peak  None: no normalisation (auto_normalize=False, exact).  A float or an fp32 [B] tensor: every sample is
@@ -803,11 +842,16 @@ def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", lim
       loudness  None, or a `Loudness`: the static gain comes from its `measured` LUFS (required with a
             target, as `peak` is an input here; `peak=` beside it is a ValueError) and the stream keeps `.loudness`,
             the running integrated loudness of what it has decoded, e.g. the `measured` of the speaker's next
-            utterance.  `Loudness(target=None)` measures only: the bytes are those without `loudness=`."""
+            utterance.  `Loudness(target=None)` measures only: the bytes are those without `loudness=`.
+      envelope  None, or an `Envelope`: per-token volume.  None on a stream made with `gain=` takes
+            `Envelope(st.frame_gain, st.spf)` by itself.  The samples are scaled where the wire kernel reads them, in
+            front of the filter, the peak, the limiter and the clip: the bytes are those of
+            `service_pcm16(st.o, envelope=...)`, and of `service_pcm16(st.o * e)`.  The running `.loudness` stays that
+            of the unshaped waveform."""
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
     return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter, encoding=encoding,
-                     loudness=loudness)
+                     loudness=loudness, envelope=envelope)
 
 
 def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
@@ -991,8 +1035,10 @@ class LiveWire:
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                  chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                 encoding="pcm16", in_encoding=None, loudness=None):
+                 encoding="pcm16", in_encoding=None, loudness=None, envelope=None):
         from .stream import LiveStream
+        _refuse_envelope(envelope, "convert_live_pcm16")
+        self._env = None                          # (what the pooled wire step reads on every member)
         _filter_code(res_type)
         loud = _loudness_arg(loudness, peak, "convert_live_pcm16", stream=True)
         self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
@@ -1154,7 +1200,7 @@ class LiveWire:
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                        chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                       encoding="pcm16", in_encoding=None, loudness=None):
+                       encoding="pcm16", in_encoding=None, loudness=None, envelope=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32; G.711 bytes with `dtype=torch.uint8,
     in_encoding="ulaw" | "alaw"`, which needs `in_sr != model_sr`) while the recording arrives, int16 out at `rate`
     (G.711 bytes with `encoding="ulaw" | "alaw"`); -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
@@ -1163,7 +1209,9 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
     earlier utterance to take a peak from, and the limiter is the level control.  For a recording of more than 256 frames, `pcm` and `valid_samples` end bitwise as
     `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
     (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead.  `loudness` as
-    `stream_pcm16` takes it: `measured` is required with a target, and the wire keeps `.loudness`."""
+    `stream_pcm16` takes it: `measured` is required with a target, and the wire keeps `.loudness`.  `envelope` is refused
+    (ValueError): a converted recording has no tokens to take a volume from."""
+    _refuse_envelope(envelope, "convert_live_pcm16")
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
                     max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter,
@@ -1466,6 +1514,7 @@ class Turn:
             if loud is not None:
                 self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
         self.segments = []            # the `DecodeStream`s, in timeline order
+        self.envelopes = []           # per segment: its `Envelope` (per-token volume) or None
         self.marks = []
         self._fade = None
         self._revoked = None
@@ -1505,19 +1554,25 @@ class Turn:
         if any(st is m for t in pool.turns for m in t.segments) or any(st is m for m in self.segments):
             raise ValueError("Turn.append: the stream is a segment of a turn already")
 
-    def append(self, st, pause_ms=0.0):
+    def append(self, st, pause_ms=0.0, envelope=None):
         """Appends the single-utterance `DecodeStream` `st` (a member of the pool's `StreamPool`; it joins it otherwise)
-        `pause_ms` of silence behind the last segment; -> its index.  The first segment starts the turn (p_0 = 0): it
+        `pause_ms` of silence behind the last segment; -> its index.  `envelope`: None, or a one-row `Envelope` over the
+        segment's own samples (None on a stream made with `gain=` takes its `frame_gain`): per-token volume, applied
+        before the segment's de-click ramp.  The first segment starts the turn (p_0 = 0): it
         takes no pause.  ValueError, with nothing changed: a `LiveStream`, a plain member of this pool, a segment of a
         turn, a stream of another model or handle, a turn that would pass `max_samples`, a closed turn, a non-zero
         `pause_ms` on the first segment (silence in front of a turn is the caller's to send, not part of it)."""
         self._check_segment(st)
         n = _segment_length(st)
+        env = _envelope_arg(envelope, st, "Turn.append")
+        if env is not None:
+            env.check("Turn.append", 1, n, st.o.device)
         self._plan.check_append(n, self._pause(pause_ms))
         if not st._drained():
             self._pool.pool.add(st)                   # (refuses another device; a member stays one)
         s = self._plan.append(n, self._pause(pause_ms))
         self.segments.append(st)
+        self.envelopes.append(env)
         lag = self._lim[1] if self._lim else 0
         marks = getattr(st, "marks", None)
         self.marks.append(None if marks is None else mark_samples(
@@ -1583,6 +1638,7 @@ class Turn:
             sg.wave, sg.start, sg.length = self.segments[s].o.data_ptr(), plan.starts[s], plan.lengths[s]
             sg.ramp = turn_ramp(self.ramp, plan.lengths[s])
         k.segs, k.n_segs = segs, s1 - s0
+        self._seg_envs = self.envelopes[s0:s1]    # beside `segs`, for the pool's call
         return [(a, a + count)]
 
     def _chunk_wired(self, pieces):
@@ -1646,6 +1702,7 @@ class Turn:
         plan.cut_at(cut, len(self.segments) if whole else keep)
         if not whole:
             self.segments = self.segments[:keep]              # (`marks` keeps every segment's: the report counts over all)
+            self.envelopes = self.envelopes[:keep]
         if F < total:
             self._fade = (F, N)
         self._revoked = Revoked(F, N, cut, self._started(F))
@@ -1695,7 +1752,9 @@ class PcmPool:
                 return f
         return None
 
-    def add(self, st, peak=None, limiter=None, loudness=None):
+    def add(self, st, peak=None, limiter=None, loudness=None, envelope=None):
+        """-> the stream's `PcmStream` follower.  `envelope`: per-token volume as `stream_pcm16` takes it; a stream made
+        with `gain=` brings its own."""
         _refuse_live(st)
         if any(st is m for t in self.turns for m in t.segments):
             raise ValueError("PcmPool.add: the stream is a segment of a turn of this pool: the turn is its wire stream")
@@ -1705,7 +1764,7 @@ class PcmPool:
         f = self.follower(st)
         if f is None:
             f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter,
-                          encoding=self.encoding, loudness=loudness)
+                          encoding=self.encoding, loudness=loudness, envelope=envelope)
             self.followers.append(f)
         return f
 
@@ -1749,11 +1808,12 @@ class PcmPool:
                 self.pool.remove(f._st)
         return report
 
-    def add_live(self, lw, limiter=None, loudness=None):
+    def add_live(self, lw, limiter=None, loudness=None, envelope=None):
         """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
         feeds, steps and wires it along with the others; -> `lw`.  The wire keeps the limiter it was opened with;
         `limiter`, when given, must be that one (the lag is part of the pieces it has planned); `loudness` likewise
         (its state is the wire's)."""
+        _refuse_envelope(envelope, "add_live")
         if not isinstance(lw, LiveWire):
             raise TypeError("add_live takes a wire.LiveWire (wire.convert_live_pcm16)")
         if limiter is not None and limiter != lw.limiter:
@@ -1870,11 +1930,13 @@ class PcmPool:
             if rows:
                 net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
                                           limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
-                                          fades=[w._fade for _, w, _, _ in rows])
+                                          fades=[w._fade for _, w, _, _ in rows],
+                                          envelopes=[w._env for _, w, _, _ in rows])
             if trows:                             # every turn of the tick in ONE call
                 net.resample_turns(tarr, self.model_sr, self.rate, packed=packed[first_turn:] if host else None,
                                    res_type=self.res_type, limits=tlimits, encoding=self.encoding,
-                                   fades=[t._fade for t, _, _ in trows])
+                                   fades=[t._fade for t, _, _ in trows],
+                                   envelopes=[t._seg_envs for t, _, _ in trows])
             # the measuring members of the tick: the segments their frontier completed, in ONE launch
             measuring = []
             for _, w, k, _ in rows:

@@ -3563,15 +3563,10 @@ int pcm16_range(mbv_model* m, const char* who, const float* wave, const int64_t*
                    (long long)(out_first + out_count), (long long)in_avail, (long long)in_stride, (long long)ready);
   if (out_count == 0 && !out_samples) return 0;           // nothing to write
   ++m->wire_runs;
-  if (lim)
-    launch_resample_pcm16_range_limited(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count,
-                                        peak, pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples,
-                                        LimiterParams{lim->ceiling, lim->lookahead, lim->hold}, law, fade_of(fade),
-                                        env_of(env), env_stride, (hipStream_t)stream);
-  else
-    launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
-                                pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples, law,
-                                fade_of(fade), env_of(env), env_stride, (hipStream_t)stream);
+  const LimiterParams lp = lim ? LimiterParams{lim->ceiling, lim->lookahead, lim->hold} : LimiterParams{};
+  launch_resample_pcm16_range(wave, valid_samples, B, in_stride, in_avail, rp.bank, rp.g, out_first, out_count, peak,
+                              pcm, pcm_stride, reinterpret_cast<unsigned*>(running_peak), out_samples,
+                              lim ? &lp : nullptr, law, fade_of(fade), env_of(env), env_stride, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3742,11 +3737,11 @@ int64_t mbv_pcm_chunks_plan(int orig_sr, int target_sr, int filter, const mbv_pc
 namespace {
 // The body the pooled wire entries share (mbv_resample_pcm16_chunks and its forms, mbv_resample_turns), behind their own
 // checks: `at(i)` is row i's mbv_pcm_chunk, `noun` what the messages call a row, `off` / `total` what the plan returned.
-// The rows without a limiter go through the unlimited kernel and the limited ones through theirs: one row table and
-// one launch per kind, and a kind with a fading row gets a fade table beside its rows, read by the same launch.  `side`
-// is what an entry has beside its rows: nothing (ChunkSide), or a turn's tables (TurnSide): `head_bytes` in front of
-// everything, written by head(); `row_bytes` per row beside each kind's rows, written by rows(kind, ..); and the two
-// launches, which get the row table, the side rows, the head and the fade table (or null) of their slice.
+// The rows without a limiter go through the unlimited instantiation and the limited ones through theirs: one row table
+// and one launch per kind, and a kind with a fading row gets a fade table beside its rows, read by the same launch.
+// `side` is what an entry has beside its rows: nothing (ChunkSide), or a turn's tables (TurnSide): `head_bytes` in front
+// of everything, written by head(); `row_bytes` per row beside each kind's rows, written by rows(kind, ..); and
+// turn_fields(launch, side rows, head), which names them in the launch of a slice.
 template <typename At, typename Side>
 int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mbv_pcm_limit* limits,
                 const mbv_pcm_fade* fades, int n, const RatePair& rp, const std::vector<int64_t>& off, int64_t total,
@@ -3759,93 +3754,64 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
                                     [&](int i) { return sample_bytes * (uintptr_t)at(i).out_count; });
   if (clash.first >= 0)
     return m->fail("%s: %ss %d and %d write overlapping ranges of one pcm", who, noun, clash.first, clash.second);
-  // rows with something to write (an empty range still carries out_samples), by kind
-  std::vector<int> live, live_lim;
+  // rows with something to write (an empty range still carries out_samples), by kind: [0] unlimited, [1] limited
+  std::vector<int> live[2];
   int64_t lds_floats = 0;
   for (int i = 0; i < n; ++i) {
     if (!(at(i).out_count > 0 || at(i).out_samples)) continue;
-    if (limits && limits[i].ceiling != 0.f) {
-      live_lim.push_back(i);
+    const bool limited = limits && limits[i].ceiling != 0.f;
+    if (limited)
       lds_floats = std::max(lds_floats, limiter_lds_floats(rp.g, rp.fir, LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold}));
-    } else {
-      live.push_back(i);
-    }
+    live[limited].push_back(i);
   }
-  if (live.empty() && live_lim.empty()) return 0;
-  auto fading = [&](const std::vector<int>& kind) {
-    if (fades)
-      for (int i : kind)
-        if (fades[i].count >= 0) return true;
-    return false;
-  };
-  auto shaped = [&](const std::vector<int>& kind) {       // (a kind with a shaped row gets an envelope table)
-    if (envs)
-      for (int i : kind)
-        if (envs[i].gain) return true;
-    return false;
-  };
+  if (live[0].empty() && live[1].empty()) return 0;
   // the scratch: the head, then per kind its rows, its side rows, (with a fading row) its fades and (with a shaped
   // row) its envelopes
   size_t end = 0;
   auto take = [&](size_t bytes) { const size_t a = end; end = align_up(end + bytes, 256); return a; };
   const size_t head_at = take(side.head_bytes);
-  struct Kind { size_t rows, side, fades; bool fade; size_t envs; bool env; };
-  auto kind_of = [&](const std::vector<int>& k, size_t row_bytes) {
-    Kind t{take(k.size() * row_bytes), take(k.size() * side.row_bytes), 0, fading(k), 0, shaped(k)};
-    if (t.fade) t.fades = take(k.size() * sizeof(PcmFade));
-    if (t.env) t.envs = take(k.size() * sizeof(PcmEnv));
-    return t;
-  };
-  const Kind ku = kind_of(live, sizeof(PcmPoolRow)), kl = kind_of(live_lim, sizeof(PcmLimRow));
+  struct Kind { size_t rows, side, fades, envs; bool fade, env; } kinds[2];
+  for (int k = 0; k < 2; ++k) {
+    const std::vector<int>& kind = live[k];
+    Kind& t = kinds[k];
+    t = Kind{take(kind.size() * sizeof(PcmPoolRow)), take(kind.size() * side.row_bytes), 0, 0, false, false};
+    for (int i : kind) {
+      t.fade = t.fade || (fades && fades[i].count >= 0);
+      t.env = t.env || (envs && envs[i].gain);
+    }
+    if (t.fade) t.fades = take(kind.size() * sizeof(PcmFade));
+    if (t.env) t.envs = take(kind.size() * sizeof(PcmEnv));
+  }
   if (ensure(m, &m->scrB, &m->scrB_bytes, end)) return 1;
   hipStream_t s = (hipStream_t)stream;
   const char* head = m->scrB + head_at;
   side.head(m->scrB + head_at, s);
-  // the side rows and the fade table of a kind, in the order of its row table; the fades null for a kind without one
-  auto beside = [&](const std::vector<int>& kind, const Kind& k) -> const PcmFade* {
-    side.rows(kind, m->scrB + k.side, s);
-    if (!k.fade) return nullptr;
-    PcmFade* t = reinterpret_cast<PcmFade*>(m->scrB + k.fades);
-    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return fade_of(&fades[kind[i]]); });
-    return t;
-  };
-  auto env_table = [&](const std::vector<int>& kind, const Kind& k) -> const PcmEnv* {
-    if (!k.env) return nullptr;
-    PcmEnv* t = reinterpret_cast<PcmEnv*>(m->scrB + k.envs);
-    upload_rows<kPcmPoolChunk>(kind.size(), t, s, [&](size_t i) { return env_of(&envs[kind[i]]); });
-    return t;
-  };
-  auto row_of = [&](int i) {
-    const mbv_pcm_chunk& k = at(i);
-    return PcmPoolRow{k.wave, k.in_total, k.valid_samples, k.in_avail, k.out_first, k.out_first + k.out_count, k.peak,
-                      reinterpret_cast<short*>(k.pcm), k.pcm_capacity, reinterpret_cast<unsigned*>(k.running_peak),
-                      k.out_samples, packed ? off[i] : (int64_t)-1};
-  };
-  auto count_of = [&](int i) { return at(i).out_count; };
-  if (!live.empty()) {
-    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB + ku.rows);
-    upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) { return row_of(live[i]); });
-    const PcmFade* ft = beside(live, ku);
-    const PcmEnv* et = env_table(live, ku);
-    grid_y_slices(live, count_of, [&](size_t f, int nn, int64_t max_count) {
-      ++m->wire_runs;
-      side.launch(rows + f, m->scrB + ku.side + f * side.row_bytes, head, ft ? ft + f : nullptr, et ? et + f : nullptr,
-                  nn, max_count, rp, packed, law, s);
-      return 0;
+  // per kind: its row table, its side rows, its fade and envelope tables in the order of the row table (null for a
+  // kind without one), and one launch per 65535 rows
+  for (int k = 0; k < 2; ++k) {
+    const std::vector<int>& kind = live[k];
+    if (kind.empty()) continue;
+    const Kind& t = kinds[k];
+    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB + t.rows);
+    upload_rows<kPcmPoolChunk>(kind.size(), rows, s, [&](size_t j) {
+      const int i = kind[j];
+      const mbv_pcm_chunk& c = at(i);
+      return PcmPoolRow{c.wave, c.in_total, c.valid_samples, c.in_avail, c.out_first, c.out_first + c.out_count, c.peak,
+                        reinterpret_cast<short*>(c.pcm), c.pcm_capacity, reinterpret_cast<unsigned*>(c.running_peak),
+                        c.out_samples, packed ? off[i] : (int64_t)-1,
+                        k ? LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold} : LimiterParams{}, 0};
     });
-  }
-  if (!live_lim.empty()) {
-    PcmLimRow* rows = reinterpret_cast<PcmLimRow*>(m->scrB + kl.rows);
-    upload_rows<kPcmPoolChunk>(live_lim.size(), rows, s, [&](size_t i) {
-      const mbv_pcm_limit& l = limits[live_lim[i]];
-      return PcmLimRow{row_of(live_lim[i]), LimiterParams{l.ceiling, l.lookahead, l.hold}, 0};
-    });
-    const PcmFade* ft = beside(live_lim, kl);
-    const PcmEnv* et = env_table(live_lim, kl);
-    grid_y_slices(live_lim, count_of, [&](size_t f, int nn, int64_t max_count) {
+    side.rows(kind, m->scrB + t.side, s);
+    PcmFade* ft = t.fade ? reinterpret_cast<PcmFade*>(m->scrB + t.fades) : nullptr;
+    if (ft) upload_rows<kPcmPoolChunk>(kind.size(), ft, s, [&](size_t j) { return fade_of(&fades[kind[j]]); });
+    PcmEnv* et = t.env ? reinterpret_cast<PcmEnv*>(m->scrB + t.envs) : nullptr;
+    if (et) upload_rows<kPcmPoolChunk>(kind.size(), et, s, [&](size_t j) { return env_of(&envs[kind[j]]); });
+    grid_y_slices(kind, [&](int i) { return at(i).out_count; }, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
-      side.launch_limited(rows + f, m->scrB + kl.side + f * side.row_bytes, head, ft ? ft + f : nullptr,
-                          et ? et + f : nullptr, nn, max_count, rp, lds_floats, packed, law, s);
+      PcmPoolLaunch a{rows + f, k == 1, nullptr, nullptr, et ? et + f : nullptr, ft ? ft + f : nullptr, nn, max_count,
+                      lds_floats, packed, law};
+      side.turn_fields(&a, m->scrB + t.side + f * side.row_bytes, head);
+      launch_resample_pcm16_pool(a, rp.bank, rp.g, s);
       return 0;
     });
   }
@@ -3858,15 +3824,7 @@ struct ChunkSide {
   size_t head_bytes = 0, row_bytes = 0;
   void head(char*, hipStream_t) const {}
   void rows(const std::vector<int>&, char*, hipStream_t) const {}
-  void launch(const PcmPoolRow* rows, const char*, const char*, const PcmFade* ft, const PcmEnv* et, int n,
-              int64_t max_count, const RatePair& rp, void* packed, int law, hipStream_t s) const {
-    launch_resample_pcm16_pool(rows, ft, et, n, max_count, rp.bank, rp.g, packed, law, s);
-  }
-  void launch_limited(const PcmLimRow* rows, const char*, const char*, const PcmFade* ft, const PcmEnv* et, int n,
-                      int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law,
-                      hipStream_t s) const {
-    launch_resample_pcm16_pool_limited(rows, ft, et, n, max_count, rp.bank, rp.g, lds_floats, packed, law, s);
-  }
+  void turn_fields(PcmPoolLaunch*, const char*, const char*) const {}
 };
 
 // mbv_resample_pcm16_chunks, its limited form and mbv_resample_g711_chunks: one body, limits null = no row limited,
@@ -4019,17 +3977,11 @@ struct TurnSide {
     upload_rows<kPcmPoolChunk>(kind.size(), reinterpret_cast<TurnSlice*>(dst), s,
                                [&](size_t i) { return TurnSlice{seg_first[kind[i]], turns[kind[i]].n_segs}; });
   }
-  void launch(const PcmPoolRow* rows, const char* slices, const char* head, const PcmFade* ft, const PcmEnv*, int n,
-              int64_t max_count, const RatePair& rp, void* packed, int law, hipStream_t s) const {
-    launch_resample_pcm16_turns(rows, reinterpret_cast<const TurnSlice*>(slices), reinterpret_cast<const TurnSeg*>(head),
-                                envs_in(head), ft, n, max_count, rp.bank, rp.g, packed, law, s);
-  }
-  void launch_limited(const PcmLimRow* rows, const char* slices, const char* head, const PcmFade* ft, const PcmEnv*,
-                      int n, int64_t max_count, const RatePair& rp, int64_t lds_floats, void* packed, int law,
-                      hipStream_t s) const {
-    launch_resample_pcm16_turns_limited(rows, reinterpret_cast<const TurnSlice*>(slices),
-                                        reinterpret_cast<const TurnSeg*>(head), envs_in(head), ft, n, max_count, rp.bank,
-                                        rp.g, lds_floats, packed, law, s);
+  // the launch of a slice of turn rows reads their slices, the segment table and the segments' envelopes
+  void turn_fields(PcmPoolLaunch* a, const char* slices, const char* head) const {
+    a->slices = reinterpret_cast<const TurnSlice*>(slices);
+    a->segs = reinterpret_cast<const TurnSeg*>(head);
+    a->envs = envs_in(head);
   }
 };
 

@@ -438,16 +438,17 @@ void launch_resample(const float* x, const int64_t* valid, int B, int64_t in_str
 // streamed wire path: how many outputs of a row of in_total samples are final once its inputs [0, in_avail) exist
 // (no tap of theirs, padded zeros included, at or past in_avail); ceil(in_total ratio) once in_avail >= in_total
 int64_t resample_ready(const ResampleGeom& g, int64_t in_avail, int64_t in_total);
+// launch_resample_pcm16_range (below, behind the structs it takes):
 // outputs [out_first, out_first + out_count) of every row from x[.., 0 : in_avail) -> int16 (pcm16_kernel's
 // epilogue with the given peaks, null = no normalisation) and the running peak; bank null = equal rates (no FIR).
 // The caller guarantees out_first + out_count <= min(resample_ready(g, in_avail, in_stride), pcm_stride).
-// law (g711.h; the same for the three launchers below): kLawNone stores the int16 (pcm is short*), kLawUlaw / kLawAlaw
+// law (g711.h; the same for both launchers below): kLawNone stores the int16 (pcm is short*), kLawUlaw / kLawAlaw
 // its G.711 byte at the same index (pcm, pcm_stride, pcm_cap, packed and packed_off then address bytes); DESIGN §7.15.
 // Fade-out of the wire step (the *_faded entries): with k = t - first, the fp32 value of output t that
 // the clip and the quantisation take is first multiplied by
 //   1 for k < 0,   (float)(count - k) * inv for 0 <= k < count,   0 for k >= count;      inv = 1.0f / (float)(count + 1)
 // (after the limiter's gain where there is one).  A pure function of t: no state, no halo.  count < 0: no fade, and
-// the value is not touched.  The four launchers take it: one for all rows of a ranged launch, a table beside the row
+// the value is not touched.  Both launchers take it: one for all rows of a ranged launch, a table beside the row
 // table (null = no row fades) for a pooled one.
 struct PcmFade {
   int64_t first, count;
@@ -472,35 +473,6 @@ struct PcmEnv {
   float inv_hop;
 };
 constexpr PcmEnv kNoEnv{nullptr, 0, 0, 0.f};
-void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
-                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
-                                 const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, const PcmFade& fade, const PcmEnv& env,
-                                 int64_t env_stride, hipStream_t s);
-// Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
-// what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
-// the arena (upload_rows).
-struct PcmPoolRow {
-  const float* x;              // the stream's wave row
-  int64_t in_total;
-  const int64_t* valid;        // one int64, or null = in_total
-  int64_t in_avail, out_first, out_end;
-  const float* peak;           // one float, or null = no normalisation
-  short* pcm;                  // the stream's own full-length row (bytes under a G.711 launch)
-  int64_t pcm_cap;             // in stored samples
-  unsigned* running;           // one value, or null
-  int64_t* out_samples;        // one value, or null
-  int64_t packed_off;          // where out_first goes in the call's packed buffer, or -1
-};
-constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 3 KiB of kernel arguments
-// outputs [out_first, out_end) of every table row (n <= 65535), each what launch_resample_pcm16_range stores for that
-// row alone (one tile function); also packed[packed_off + t - out_first] when packed is given.  max_count >= out_end -
-// out_first of every row; bank null = equal rates.  The caller guarantees out_end <= min(resample_ready(g, in_avail,
-// in_total), pcm_cap) of every row.
-// fades: null, or fades[i] beside rows[i].  envs: null, or envs[i] beside rows[i].
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
-                                int64_t max_count, const float* bank, const ResampleGeom& g, void* packed, int law,
-                                hipStream_t s);
 // Look-ahead limiter of the wire step (mbv_resample_pcm16_range_limited / mbv_resample_pcm16_chunks_limited, DESIGN
 // §7.14).  With v the sample the unlimited kernels clip (static peak gain included; zero outside the row's computed
 // outputs), all in fp32:
@@ -530,22 +502,31 @@ inline int64_t limiter_ready(int64_t ready, int64_t all, bool complete, int look
   if (complete) return all;
   return ready > lookahead ? ready - lookahead : 0;
 }
-struct PcmLimRow {
-  PcmPoolRow row;
-  LimiterParams lim;
+// lim: null, or the limiter of every row: the launch then goes through the limited tile, and the caller guarantees
+// out_first + out_count <= min(limiter_ready(..), pcm_stride) and limiter_lds_floats(g, bank, *lim) <= kResampleMaxLdsFloats
+void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
+                                 const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
+                                 const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
+                                 int64_t* out_samples, const LimiterParams* lim, int law, const PcmFade& fade,
+                                 const PcmEnv& env, int64_t env_stride, hipStream_t s);
+// Pooled wire output (mbv_resample_pcm16_chunks): the ranged step of MANY rows in one launch.  A table row holds
+// what launch_resample_pcm16_range takes as scalars and [B] vectors, for ONE row of one stream; the table lives in
+// the arena (upload_rows).
+struct PcmPoolRow {
+  const float* x;              // the stream's wave row
+  int64_t in_total;
+  const int64_t* valid;        // one int64, or null = in_total
+  int64_t in_avail, out_first, out_end;
+  const float* peak;           // one float, or null = no normalisation
+  short* pcm;                  // the stream's own full-length row (bytes under a G.711 launch)
+  int64_t pcm_cap;             // in stored samples
+  unsigned* running;           // one value, or null
+  int64_t* out_samples;        // one value, or null
+  int64_t packed_off;          // where out_first goes in the call's packed buffer, or -1
+  LimiterParams lim;           // the row's limiter: read by a limited launch only
   int32_t pad_;
 };
-// launch_resample_pcm16_range / launch_resample_pcm16_pool through the limited tile; lds_floats >=
-// limiter_lds_floats of every row, at most kResampleMaxLdsFloats (checked by the caller).  The caller guarantees
-// out_end <= min(limiter_ready(..), pcm_cap) of every row.
-void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
-                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
-                                         int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
-                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s);
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
-                                        int64_t max_count, const float* bank, const ResampleGeom& g,
-                                        int64_t lds_floats, void* packed, int law, hipStream_t s);
+constexpr int kPcmPoolChunk = 32;   // rows per upload_rows launch: 32 x 112 bytes = 3.5 KiB of kernel arguments
 // Turns on the wire (mbv_resample_turns): the input of a row is not one wave row but a TIMELINE of
 // segments, each the waveform of one utterance, with silence between them; it is never materialised.  Timeline index j
 // holds x[j - start] g(j - start) of the segment with start <= j < start + n, and 0.f anywhere else.  g is the
@@ -553,7 +534,7 @@ void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fa
 //   i < ramp:       (float)(i + 1) * inv              i >= n - ramp:   (float)(ramp - (i - (n - ramp))) * inv
 // (the fade's own ramp, mirrored for the rise; inv = 1.0f / (float)(ramp + 1), as mbv_pcm_fade_make computes it) and
 // no multiply anywhere else; ramp <= n / 2, so the two never overlap.  A table row of the pooled kernels
-// (PcmPoolRow / PcmLimRow with x = null) reads segs[first .. first + count) of the call's segment table: the segments
+// (a PcmPoolRow with x = null) reads segs[first .. first + count) of the call's segment table: the segments
 // that intersect its input window, ascending.  Everything behind the staging is the code of the plain rows, so a turn
 // row is bitwise the plain row of the assembled timeline.
 struct TurnSeg {
@@ -564,15 +545,26 @@ struct TurnSeg {
 };
 struct TurnSlice { int32_t first, count; };
 constexpr int kTurnMaxSegs = 4096;   // segments of one call (MBV_TURN_MAX_SEGS)
-// launch_resample_pcm16_pool / _pool_limited over turn rows: slices[i] beside rows[i]; seg_envs: null, or
-// seg_envs[k] beside segs[k], the envelope of that segment in its own sample index (applied before the de-click ramp)
-void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                 const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
-                                 const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s);
-void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                         const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
-                                         const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
-                                         int law, hipStream_t s);
+// One pooled launch: outputs [out_first, out_end) of every table row (n <= 65535), each what launch_resample_pcm16_range
+// stores for that row alone (one tile function); also packed[packed_off + t - out_first] when packed is given.  The
+// caller guarantees out_end <= min(resample_ready(g, in_avail, in_total), pcm_cap) of every row, and under `limited`
+// out_end <= min(limiter_ready(..), pcm_cap).
+struct PcmPoolLaunch {
+  const PcmPoolRow* rows;
+  bool limited;                // every row through the limited tile, each with its own `lim`
+  const TurnSlice* slices;     // null: chunk rows.  Else turn rows: slices[i] beside rows[i], into
+  const TurnSeg* segs;         //   the call's segment table
+  const PcmEnv* envs;          // null, or envs[i] beside rows[i]; for turn rows envs[k] beside segs[k], the envelope of
+                               //   that segment in its own sample index (applied before the de-click ramp)
+  const PcmFade* fades;        // null, or fades[i] beside rows[i]
+  int n;
+  int64_t max_count;           // >= out_end - out_first of every row
+  int64_t lds_floats;          // limited: >= limiter_lds_floats of every row, <= kResampleMaxLdsFloats; else not read
+  void* packed;
+  int law;
+};
+// bank null = equal rates
+void launch_resample_pcm16_pool(const PcmPoolLaunch& a, const float* bank, const ResampleGeom& g, hipStream_t s);
 // the stand-alone codec: n samples, law kLawUlaw or kLawAlaw (checked by the caller)
 void launch_g711_encode(const short* pcm, int64_t n, int law, uint8_t* out, hipStream_t s);
 void launch_g711_decode(const uint8_t* in, int64_t n, int law, short* pcm, hipStream_t s);

@@ -278,24 +278,31 @@ __device__ __forceinline__ float turn_sample(const TurnSrc& src, int64_t j, int6
   return ramped ? v * g : v;
 }
 
-// the window of the plain row's resample_stage, from the timeline
-template <bool ENV>
-__device__ __forceinline__ void resample_stage(float* xs, const TurnSrc& src, int64_t j0, int64_t t_last,
-                                               int L, int M, int K, int left, int64_t limit) {
-  const int W = (int)((t_last * M) / L - left + K - j0);
-  for (int i = threadIdx.x; i < W; i += kResampleTile) xs[i] = turn_sample<ENV>(src, j0 + i, limit);
-}
-
-// the window of the plain row's resample_stage, shaped (a row of the launch without an envelope: the sample itself)
-__device__ __forceinline__ void resample_stage_env(float* xs, const float* __restrict__ xb, const PcmEnv& env,
-                                                   int64_t j0, int64_t t_last, int L, int M, int K, int left,
-                                                   int64_t limit) {
-  const int W = (int)((t_last * M) / L - left + K - j0);
-  for (int i = threadIdx.x; i < W; i += kResampleTile) {
-    const int64_t j = j0 + i;
-    xs[i] = (j >= 0 && j < limit) ? env_mul(xb[j], env, j) : 0.f;
+// What a row of a wire launch reads from, and the ONE place where it is read: the plain row `xb` (TURN = false), shaped
+// by `env` under ENV, or the timeline `src` of a turn.  Nothing at or past `limit` (and nothing in front of 0) is
+// loaded: a zero stands there.  The members a <TURN, ENV> does not name above are never set and never read.
+template <bool TURN, bool ENV>
+struct WireSource {
+  const float* __restrict__ xb;
+  PcmEnv env;
+  TurnSrc src;
+  // the sample at index j of the row (of the timeline): what FIR = false hands on as it is
+  __device__ __forceinline__ float at(int64_t j, int64_t limit) const {
+    if constexpr (TURN) {
+      return turn_sample<ENV>(src, j, limit);
+    } else {
+      if (j < 0 || j >= limit) return 0.f;
+      if constexpr (ENV) return env_mul(xb[j], env, j);
+      else return xb[j];
+    }
   }
-}
+  // the window of the fp32 resample_stage above, from this source
+  __device__ __forceinline__ void stage(float* xs, int64_t j0, int64_t t_last, const ResampleGeom& g,
+                                        int64_t limit) const {
+    const int W = (int)((t_last * g.M) / g.L - g.left + g.K - j0);
+    for (int i = threadIdx.x; i < W; i += kResampleTile) xs[i] = at(j0 + i, limit);
+  }
+};
 
 // output t from the staged window
 __device__ __forceinline__ float resample_output(const float* xs, int64_t j0, int64_t t, const float* __restrict__ bank,
@@ -423,19 +430,20 @@ void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_cou
 //   - each int16 goes to the row's own pcm[t] and, with a packed buffer, to packed[packed_off + t - out_first]
 //   - LIM = true: the look-ahead limiter between the static gain and the clip (resample_pcm16_limited below); the
 //     caller has checked out_end + lookahead <= resample_ready(in_avail) unless the row is complete.  LIM = false
-//     never reads `lim`
+//     never reads the row's `lim`
 //   - LAW = kLawUlaw / kLawAlaw: the G.711 byte of that int16 is stored where the int16 would be, so
 //     pcm, pcm_cap, packed and packed_off then count bytes; everything before the store is the same code.  Uniform
 //     over a launch, like FIR and LIM
 //   - fade (kernels.h): the value the clip takes is first scaled by the ramp of its own index t; a row
 //     without one (count < 0) skips the multiply, so its bits are those of a launch that knows no fade.  FADE = false
 //     (a ranged launch without a fade) compiles the test away: that instantiation is the kernel of before
-//   - TURN = true: the row's input is the timeline of `src` (r.x is null): the staging, and the direct
-//     read of FIR = false, go through turn_sample; in_total / in_avail count timeline samples.  TURN = false never
-//     reads `src`: those instantiations are the kernels of before
+//   - the input is read through a WireSource (above) and nowhere else: its stage() for the FIR, its at() for FIR = false
+//   - TURN = true: the row's input is the timeline of `src` (r.x is null), read through turn_sample;
+//     in_total / in_avail count timeline samples.  TURN = false never reads `src`: those instantiations are the kernels
+//     of before
 //   - ENV = true: a row may carry a gain envelope `env` (a turn row: one per segment, src.envs).  The
-//     sample is multiplied where the source is read: the staging, the direct read of FIR = false, the limited tile's
-//     window and turn_sample; FIR, peak, static gain, limiter, fade and clip see the shaped signal.  A row of such a
+//     sample is multiplied where the source is read (WireSource::at, turn_sample); FIR, peak, static gain, limiter,
+//     fade and clip see the shaped signal.  A row of such a
 //     launch without one (gain null) executes no multiply.  ENV = false never reads `env`: those instantiations are the
 //     kernels of before, and a launch in which no row is shaped uses them
 // ---------------------------------------------------------------------------------------------------
@@ -458,91 +466,34 @@ __device__ __forceinline__ float fade_gain(const PcmFade& f, int64_t t) {
   return k < f.count ? (float)(f.count - k) * f.inv : 0.f;
 }
 
-template <bool FIR, int LAW, bool FADE, bool TURN, bool ENV>
-__device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
-                                                       const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
-                                                       typename WireSample<LAW>::type* pk,
-                                                       const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio, const TurnSrc& src, const PcmEnv& env);
-
-template <bool FIR, bool LIM, int LAW, bool FADE, bool TURN = false, bool ENV = false>
-__device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const float* __restrict__ bank,
-                                                    int L, int M, int K, int left, double ratio,
-                                                    short* __restrict__ packed, const LimiterParams& lim,
-                                                    const PcmFade& fade,
-                                                    const TurnSrc& src = TurnSrc{nullptr, 0, nullptr},
-                                                    const PcmEnv& env = PcmEnv{nullptr, 0, 0, 0.f}) {
-  using Sample = WireSample<LAW>;
-  using W = typename Sample::type;
-  W* pcm = reinterpret_cast<W*>(r.pcm);
-  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
-  if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
-  const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
-  int64_t n_out = FIR ? (int64_t)((double)n * ratio) : n;
-  if (n_out > r.pcm_cap) n_out = r.pcm_cap;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && r.out_samples) {
-    int64_t keep = FIR ? (int64_t)ceil((double)n * ratio) : n;
-    r.out_samples[0] = keep > r.pcm_cap ? r.pcm_cap : keep;
-  }
-  const int64_t t = t0 + threadIdx.x;
-  if (t0 >= r.out_end) return;                            // the empty range (only out_samples to write)
-  W* pk = (packed && r.packed_off >= 0) ? reinterpret_cast<W*>(packed) + (r.packed_off - r.out_first) : nullptr;
-  if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
-    if (t < r.out_end) {
-      pcm[t] = Sample::of(0);
-      if (pk) pk[t] = Sample::of(0);
-    }
-    return;
-  }
-  const int64_t limit = n < r.in_avail ? n : r.in_avail;
-  if constexpr (LIM) {
-    resample_pcm16_limited<FIR, LAW, FADE, TURN, ENV>(xs, r, lim, fade, t0, n_out, limit, pk, bank, L, M, K, left,
-                                                      ratio, src, env);
-    return;
-  }
-  const float* xb = r.x;
-  int64_t j0 = 0;
-  if (FIR) {
-    int64_t t_last = t0 + kResampleTile - 1;
-    if (t_last > n_out - 1) t_last = n_out - 1;
-    if (t_last > r.out_end - 1) t_last = r.out_end - 1;
-    j0 = resample_window_first(t0, L, M, left);
-    if constexpr (TURN) resample_stage<ENV>(xs, src, j0, t_last, L, M, K, left, limit);
-    else if constexpr (ENV) resample_stage_env(xs, xb, env, j0, t_last, L, M, K, left, limit);
-    else resample_stage(xs, xb, j0, t_last, L, M, K, left, limit);
-    __syncthreads();
-  }
-  float v = 0.f;
-  const bool live = t < r.out_end && t < n_out;
+// The epilogue of both tiles for output t < out_end: a live value (one the row computed) is scaled by the ramp of its
+// own index, clipped and scaled to int16; then truncation, the codec, and the store to the row's pcm and to the packed
+// buffer (pk null: none).  live = false with v = 0 stores the zero of [n_out, out_end).  FADE = false never reads `fade`
+template <int LAW, bool FADE>
+__device__ __forceinline__ void wire_store(float v, bool live, int64_t t, const PcmFade& fade,
+                                           typename WireSample<LAW>::type* pcm, typename WireSample<LAW>::type* pk) {
   if (live) {
-    if constexpr (FIR) v = resample_output(xs, j0, t, bank, L, M, K, left, ratio);
-    else if constexpr (TURN) v = turn_sample<ENV>(src, t, limit);
-    else if constexpr (ENV) v = t < limit ? env_mul(xb[t], env, t) : 0.f;
-    else v = t < limit ? xb[t] : 0.f;
-  }
-  if (r.running) {
-    float m = fabsf(v);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    // m >= 0: bit order == value order.  The peak only grows, so a wave that reads a value at least its own has
-    // nothing to add: most waves skip the atomic (hundreds of them on one address serialise in L2)
-    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(r.running, __ATOMIC_RELAXED))
-      atomicMax(r.running, __float_as_uint(m));
-  }
-  if (t >= r.out_end) return;
-  if (live) {
-    if (r.peak) {
-      const float p = r.peak[0];
-      if (p > 0.01f) v = (v / p) * 0.9f;
-    }
     if constexpr (FADE)
       if (fade.count >= 0) v *= fade_gain(fade, t);
     v = fminf(fmaxf(v, -1.f), 1.f);
     v = v * 32767.f;
   }
-  const W q = Sample::of((short)(int)v);
+  const typename WireSample<LAW>::type q = WireSample<LAW>::of((short)(int)v);
   pcm[t] = q;
   if (pk) pk[t] = q;
+}
+
+// running = max(running, m) with m >= 0 each thread's |v| (0 where it has none): one atomic per wave at the most.
+// Every thread of the workgroup calls it (the shuffle is over whole waves)
+__device__ __forceinline__ void wire_peak(unsigned* running, float m) {
+  if (running) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    // m >= 0: bit order == value order.  The peak only grows, so a wave that reads a value at least its own has
+    // nothing to add: most waves skip the atomic (hundreds of them on one address serialise in L2)
+    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __atomic_load_n(running, __ATOMIC_RELAXED))
+      atomicMax(running, __float_as_uint(m));
+  }
 }
 
 // The limited tile of outputs [t0, t_end), t_end = min(t0 + 256, out_end, n_out) > t0:
@@ -558,13 +509,13 @@ __device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow&
 // LDS: [input window of the row's span][v][a][b], limiter_lds_floats (kernels.h).  All loops and barriers are uniform
 // over the workgroup; no thread leaves before the last barrier.
 template <bool FIR, int LAW, bool FADE, bool TURN, bool ENV>
-__device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const LimiterParams& lim,
+__device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPoolRow& r, const WireSource<TURN, ENV>& in,
                                                        const PcmFade& fade, int64_t t0, int64_t n_out, int64_t limit,
+                                                       typename WireSample<LAW>::type* pcm,
                                                        typename WireSample<LAW>::type* pk,
-                                                       const float* __restrict__ bank, int L, int M, int K, int left,
-                                                       double ratio, const TurnSrc& src, const PcmEnv& env) {
-  const int La = lim.lookahead, H = lim.hold;
-  const float c = lim.ceiling;
+                                                       const float* __restrict__ bank, const ResampleGeom& g) {
+  const int La = r.lim.lookahead, H = r.lim.hold;
+  const float c = r.lim.ceiling;
   int64_t t_end = t0 + kResampleTile;
   if (t_end > r.out_end) t_end = r.out_end;
   if (t_end > n_out) t_end = n_out;
@@ -572,19 +523,16 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
   const int S = cnt + 2 * La + H;                        // v values held
   const int64_t lo = t0 - La - H;                        // output index of vs[0]
   const int span = kResampleTile + 2 * La + H;           // limiter_span: the layout does not depend on the tile
-  float* vs = lds + (FIR ? (int64_t)(span - 1) * M / L + 2 + K : 0);
+  float* vs = lds + (FIR ? (int64_t)(span - 1) * g.M / g.L + 2 + g.K : 0);
   float* a = vs + span;
   float* b = a + span;
-  const float* xb = r.x;
   int64_t j0 = 0;
   if (FIR) {
     const int64_t k_lo = lo > 0 ? lo : 0;
     int64_t k_hi = lo + S - 1;
     if (k_hi > n_out - 1) k_hi = n_out - 1;
-    j0 = resample_window_first(k_lo, L, M, left);
-    if constexpr (TURN) resample_stage<ENV>(lds, src, j0, k_hi, L, M, K, left, limit);
-    else if constexpr (ENV) resample_stage_env(lds, xb, env, j0, k_hi, L, M, K, left, limit);
-    else resample_stage(lds, xb, j0, k_hi, L, M, K, left, limit);
+    j0 = resample_window_first(k_lo, g.L, g.M, g.left);
+    in.stage(lds, j0, k_hi, g, limit);
     __syncthreads();
   }
   float p = 0.f;
@@ -594,10 +542,8 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     const int64_t k = lo + i;
     float v = 0.f;
     if (k >= 0 && k < n_out) {
-      if constexpr (FIR) v = resample_output(lds, j0, k, bank, L, M, K, left, ratio);
-      else if constexpr (TURN) v = turn_sample<ENV>(src, k, limit);
-      else if constexpr (ENV) v = k < limit ? env_mul(xb[k], env, k) : 0.f;
-      else v = k < limit ? xb[k] : 0.f;
+      if constexpr (FIR) v = resample_output(lds, j0, k, bank, g.L, g.M, g.K, g.left, g.ratio);
+      else v = in.at(k, limit);
       if (k >= t0 && k < t_end) top = fmaxf(top, fabsf(v));
       if (p > 0.01f) v = (v / p) * 0.9f;
     }
@@ -606,12 +552,7 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
     a[i] = m > c ? c / m : 1.f;
   }
   __syncthreads();
-  if (r.running) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) top = fmaxf(top, __shfl_xor(top, off));
-    if ((threadIdx.x & 63) == 0 && __float_as_uint(top) > __atomic_load_n(r.running, __ATOMIC_RELAXED))
-      atomicMax(r.running, __float_as_uint(top));
-  }
+  wire_peak(r.running, top);
   const int Wn = H + La + 1;
   int w = 1;
   while (2 * w <= Wn) {
@@ -629,27 +570,72 @@ __device__ __forceinline__ void resample_pcm16_limited(float* lds, const PcmPool
   if (t < t_end) {
     float sum = b[threadIdx.x];
     for (int i = 1; i <= La; ++i) sum += b[threadIdx.x + i];
-    const float g = sum / (float)(La + 1);
-    y = vs[threadIdx.x + La + H] * g;
-    if constexpr (FADE)
-      if (fade.count >= 0) y *= fade_gain(fade, t);
-    y = fminf(fmaxf(y, -1.f), 1.f);
-    y = y * 32767.f;
+    const float gn = sum / (float)(La + 1);
+    y = vs[threadIdx.x + La + H] * gn;
   }
-  using Sample = WireSample<LAW>;
-  const typename Sample::type q = Sample::of((short)(int)y);
-  reinterpret_cast<typename Sample::type*>(r.pcm)[t] = q;
-  if (pk) pk[t] = q;
+  wire_store<LAW, FADE>(y, t < t_end, t, fade, pcm, pk);
 }
 
-// Ranged kernel (mbv_resample_pcm16_range, mbv_resample_g711_range): row blockIdx.y of [B] tensors, one range for all
-// rows; pcm_stride counts stored samples (int16, or bytes with a codec).  FADE = false never reads `fade`, ENV = false
-// never reads `env` / `env_stride` (row b's table starts at env.gain + b env_stride)
+template <bool FIR, bool LIM, int LAW, bool FADE, bool TURN, bool ENV>
+__device__ __forceinline__ void resample_pcm16_tile(float* xs, const PcmPoolRow& r, const WireSource<TURN, ENV>& in,
+                                                    const PcmFade& fade, const float* __restrict__ bank,
+                                                    const ResampleGeom& g, short* __restrict__ packed) {
+  using W = typename WireSample<LAW>::type;
+  W* pcm = reinterpret_cast<W*>(r.pcm);
+  const int64_t t0 = r.out_first + (int64_t)blockIdx.x * kResampleTile;
+  if (blockIdx.x != 0 && t0 >= r.out_end) return;         // uniform over the workgroup: a shorter range than the grid's
+  const int64_t n = resample_row_valid(r.valid, 0, r.in_total);
+  int64_t n_out = FIR ? (int64_t)((double)n * g.ratio) : n;
+  if (n_out > r.pcm_cap) n_out = r.pcm_cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && r.out_samples) {
+    int64_t keep = FIR ? (int64_t)ceil((double)n * g.ratio) : n;
+    r.out_samples[0] = keep > r.pcm_cap ? r.pcm_cap : keep;
+  }
+  const int64_t t = t0 + threadIdx.x;
+  if (t0 >= r.out_end) return;                            // the empty range (only out_samples to write)
+  W* pk = (packed && r.packed_off >= 0) ? reinterpret_cast<W*>(packed) + (r.packed_off - r.out_first) : nullptr;
+  if (t0 >= n_out) {                                      // uniform over the workgroup: zeros past the row's end
+    if (t < r.out_end) wire_store<LAW, false>(0.f, false, t, fade, pcm, pk);
+    return;
+  }
+  const int64_t limit = n < r.in_avail ? n : r.in_avail;
+  if constexpr (LIM) {
+    resample_pcm16_limited<FIR, LAW, FADE>(xs, r, in, fade, t0, n_out, limit, pcm, pk, bank, g);
+    return;
+  }
+  int64_t j0 = 0;
+  if (FIR) {
+    int64_t t_last = t0 + kResampleTile - 1;
+    if (t_last > n_out - 1) t_last = n_out - 1;
+    if (t_last > r.out_end - 1) t_last = r.out_end - 1;
+    j0 = resample_window_first(t0, g.L, g.M, g.left);
+    in.stage(xs, j0, t_last, g, limit);
+    __syncthreads();
+  }
+  float v = 0.f;
+  const bool live = t < r.out_end && t < n_out;
+  if (live) {
+    if constexpr (FIR) v = resample_output(xs, j0, t, bank, g.L, g.M, g.K, g.left, g.ratio);
+    else v = in.at(t, limit);
+  }
+  wire_peak(r.running, fabsf(v));
+  if (t >= r.out_end) return;
+  if (live && r.peak) {
+    const float p = r.peak[0];
+    if (p > 0.01f) v = (v / p) * 0.9f;
+  }
+  wire_store<LAW, FADE>(v, live, t, fade, pcm, pk);
+}
+
+// Ranged kernel (mbv_resample_pcm16_range and its forms): row blockIdx.y of [B] tensors, one range for all rows; the
+// row is built in registers from the arguments.  pcm_stride counts stored samples (int16, or bytes with a codec).
+// LIM = false never reads `lim`, FADE = false never reads `fade`, ENV = false never reads `env` / `env_stride` (row b's
+// table starts at env.gain + b env_stride)
 template <bool FIR, bool LIM, int LAW, bool FADE, bool ENV>
 __global__ void __launch_bounds__(kResampleTile)
 resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restrict__ valid, int64_t in_stride,
-                            int64_t in_avail, const float* __restrict__ bank, int L, int M, int K, int left,
-                            double ratio, int64_t out_first, int64_t out_end, const float* __restrict__ peak,
+                            int64_t in_avail, const float* __restrict__ bank, ResampleGeom g, int64_t out_first,
+                            int64_t out_end, const float* __restrict__ peak,
                             typename WireSample<LAW>::type* __restrict__ pcm, int64_t pcm_stride,
                             unsigned* __restrict__ running, int64_t* __restrict__ out_samples, LimiterParams lim,
                             PcmFade fade, PcmEnv env, int64_t env_stride) {
@@ -657,17 +643,48 @@ resample_pcm16_range_kernel(const float* __restrict__ x, const int64_t* __restri
   const int b = blockIdx.y;
   const PcmPoolRow r{x + (int64_t)b * in_stride, in_stride, valid ? valid + b : nullptr, in_avail, out_first, out_end,
                      peak ? peak + b : nullptr, reinterpret_cast<short*>(pcm + (int64_t)b * pcm_stride), pcm_stride,
-                     running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1};
+                     running ? running + b : nullptr, out_samples ? out_samples + b : nullptr, -1, lim, 0};
+  WireSource<false, ENV> in{};
+  in.xb = r.x;
   if constexpr (ENV) {
-    env.gain += (int64_t)b * env_stride;
-    resample_pcm16_tile<FIR, LIM, LAW, FADE, false, true>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade,
-                                                          TurnSrc{nullptr, 0, nullptr}, env);
-  } else {
-    resample_pcm16_tile<FIR, LIM, LAW, FADE>(xs, r, bank, L, M, K, left, ratio, nullptr, lim, fade);
+    in.env = env;
+    in.env.gain += (int64_t)b * env_stride;
   }
+  resample_pcm16_tile<FIR, LIM, LAW, FADE>(xs, r, in, fade, bank, g, nullptr);
+}
+
+// Pooled kernel (mbv_resample_pcm16_chunks, mbv_resample_turns and their forms): row blockIdx.y of a table, each with
+// its own range (and, LIM, its own limiter); the grid holds the tiles of the longest one.  fades: null, or fades[i]
+// beside rows[i].  TURN = false: envs[i] beside rows[i] (ENV; never read otherwise), `slices` / `segs` never read.
+// TURN = true: the row's input is segs[first .. first + count) of slices[i], and envs[k] lies beside segs[k]
+template <bool FIR, bool LIM, int LAW, bool TURN, bool ENV>
+__global__ void __launch_bounds__(kResampleTile)
+resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
+                           const TurnSeg* __restrict__ segs, const PcmEnv* __restrict__ envs,
+                           const PcmFade* __restrict__ fades, const float* __restrict__ bank, ResampleGeom g,
+                           short* __restrict__ packed) {
+  extern __shared__ float xs[];
+  const PcmPoolRow r = rows[blockIdx.y];
+  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
+  WireSource<TURN, ENV> in{};
+  if constexpr (TURN) {
+    const TurnSlice sl = slices[blockIdx.y];
+    in.src = TurnSrc{segs + sl.first, sl.count, ENV ? envs + sl.first : nullptr};
+  } else {
+    in.xb = r.x;
+    if constexpr (ENV) in.env = envs[blockIdx.y];
+  }
+  resample_pcm16_tile<FIR, LIM, LAW, true>(xs, r, in, fade, bank, g, packed);
 }
 
 namespace {
+// f(c) with c a std::bool_constant of `on`
+template <typename F>
+void with_flag(bool on, F f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 // f(LAW as a std::integral_constant) for the codec of a launch (the caller has refused every other value)
 template <typename F>
 void with_law(int law, F f) {
@@ -676,222 +693,55 @@ void with_law(int law, F f) {
   else f(std::integral_constant<int, kLawNone>{});
 }
 
-// f(ENV as a std::bool_constant): the shaped instantiation only for a launch in which a row carries an envelope
+// What the two wire launchers share.  f(FIR, LIM, LAW, X, ENV as constants, grid, lds bytes, geometry) for a launch of
+// `rows` rows whose longest range has max_count outputs; X is FADE for the ranged kernel and TURN for the pooled one.
+// FIR = bank given, else equal rates with the geometry of the sample itself.  LDS: lim_floats (limiter_lds_floats) for
+// a limited launch, else the staged window of the FIR.  The shaped instantiation runs only where an envelope is given
 template <typename F>
-void with_env(bool shaped, F f) {
-  if (shaped) f(std::true_type{});
-  else f(std::false_type{});
-}
-
-template <bool LIM>
-void launch_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail, const float* bank,
-                  const ResampleGeom& g, int64_t out_first, int64_t out_count, const float* peak, void* pcm,
-                  int64_t pcm_stride, unsigned* running, int64_t* out_samples, const LimiterParams& lim, size_t lds,
-                  int law, const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s) {
-  int64_t bx = (out_count + kResampleTile - 1) / kResampleTile;
+void wire_launch(const float* bank, const ResampleGeom& g, bool limited, int64_t lim_floats, int law, bool x,
+                 bool shaped, int64_t max_count, int rows, F f) {
+  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
   if (bx < 1) bx = 1;                                     // an empty range still writes out_samples
-  const dim3 grid((unsigned)bx, B), block(kResampleTile);
-  auto launch = [&](auto lc, auto fc, auto ec) {
-    constexpr int LAW = decltype(lc)::value;
-    constexpr bool FADE = decltype(fc)::value;
-    constexpr bool ENV = decltype(ec)::value;
-    auto* out = static_cast<typename WireSample<LAW>::type*>(pcm);
-    if (bank) {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<true, LIM, LAW, FADE, ENV>), grid, block, lds, s, x, valid,
-                         in_stride, in_avail, bank, g.L, g.M, g.K, g.left, g.ratio, out_first, out_first + out_count,
-                         peak, out, pcm_stride, running, out_samples, lim, fade, env, env_stride);
-    } else {
-      hipLaunchKernelGGL((resample_pcm16_range_kernel<false, LIM, LAW, FADE, ENV>), grid, block, lds, s, x, valid,
-                         in_stride, in_avail, bank, 1, 1, 0, 0, 1.0, out_first, out_first + out_count, peak, out,
-                         pcm_stride, running, out_samples, lim, fade, env, env_stride);
-    }
-  };
-  with_law(law, [&](auto lc) {
-    with_env(env.gain != nullptr, [&](auto ec) {
-      if (fade.count >= 0) launch(lc, std::true_type{}, ec);
-      else launch(lc, std::false_type{}, ec);
+  const dim3 grid((unsigned)bx, rows);
+  const size_t lds = (size_t)(limited ? lim_floats : bank ? resample_lds_floats(g) : 0) * sizeof(float);
+  const ResampleGeom gk = bank ? g : ResampleGeom{1, 1, 0, 0, 1.0};
+  with_flag(bank != nullptr, [&](auto fir) {
+    with_flag(limited, [&](auto lim) {
+      with_law(law, [&](auto lc) {
+        with_flag(x, [&](auto xc) { with_flag(shaped, [&](auto ec) { f(fir, lim, lc, xc, ec, grid, lds, gk); }); });
+      });
     });
   });
 }
 }  // namespace
 
-void launch_resample_pcm16_range_limited(const float* x, const int64_t* valid, int B, int64_t in_stride,
-                                         int64_t in_avail, const float* bank, const ResampleGeom& g, int64_t out_first,
-                                         int64_t out_count, const float* peak, void* pcm, int64_t pcm_stride,
-                                         unsigned* running, int64_t* out_samples, const LimiterParams& lim, int law,
-                                         const PcmFade& fade, const PcmEnv& env, int64_t env_stride, hipStream_t s) {
-  const size_t lds = (size_t)limiter_lds_floats(g, bank != nullptr, lim) * sizeof(float);
-  launch_range<true>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                     out_samples, lim, lds, law, fade, env, env_stride, s);
-}
-
 void launch_resample_pcm16_range(const float* x, const int64_t* valid, int B, int64_t in_stride, int64_t in_avail,
                                  const float* bank, const ResampleGeom& g, int64_t out_first, int64_t out_count,
                                  const float* peak, void* pcm, int64_t pcm_stride, unsigned* running,
-                                 int64_t* out_samples, int law, const PcmFade& fade, const PcmEnv& env,
-                                 int64_t env_stride, hipStream_t s) {
-  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
-  launch_range<false>(x, valid, B, in_stride, in_avail, bank, g, out_first, out_count, peak, pcm, pcm_stride, running,
-                      out_samples, LimiterParams{}, lds, law, fade, env, env_stride, s);
+                                 int64_t* out_samples, const LimiterParams* lim, int law, const PcmFade& fade,
+                                 const PcmEnv& env, int64_t env_stride, hipStream_t s) {
+  const LimiterParams lp = lim ? *lim : LimiterParams{};
+  wire_launch(bank, g, lim != nullptr, lim ? limiter_lds_floats(g, bank != nullptr, lp) : 0, law, fade.count >= 0,
+              env.gain != nullptr, out_count, B,
+              [&](auto fir, auto lc_lim, auto lc, auto fc, auto ec, dim3 grid, size_t lds, const ResampleGeom& gk) {
+                constexpr int LAW = decltype(lc)::value;
+                hipLaunchKernelGGL((resample_pcm16_range_kernel<decltype(fir)::value, decltype(lc_lim)::value, LAW,
+                                                                decltype(fc)::value, decltype(ec)::value>),
+                                   grid, dim3(kResampleTile), lds, s, x, valid, in_stride, in_avail, bank, gk, out_first,
+                                   out_first + out_count, peak, static_cast<typename WireSample<LAW>::type*>(pcm),
+                                   pcm_stride, running, out_samples, lp, fade, env, env_stride);
+              });
 }
 
-// Pooled ranged kernel (mbv_resample_pcm16_chunks, mbv_resample_g711_chunks): row blockIdx.y of a table, each with its
-// own range; the grid holds the tiles of the longest one.  ENV: envs[i] beside rows[i] (never read otherwise)
-template <bool FIR, int LAW, bool ENV>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_pool_kernel(const PcmPoolRow* __restrict__ rows, const PcmFade* __restrict__ fades,
-                           const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                           short* __restrict__ packed, const PcmEnv* __restrict__ envs) {
-  extern __shared__ float xs[];
-  const PcmPoolRow r = rows[blockIdx.y];
-  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  if constexpr (ENV)
-    resample_pcm16_tile<FIR, false, LAW, true, false, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{},
-                                                            fade, TurnSrc{nullptr, 0, nullptr}, envs[blockIdx.y]);
-  else
-    resample_pcm16_tile<FIR, false, LAW, true>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{}, fade);
-}
-
-// the same table through the limited tile, each row with its own limiter
-template <bool FIR, int LAW, bool ENV>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_pool_limited_kernel(const PcmLimRow* __restrict__ rows, const PcmFade* __restrict__ fades,
-                                   const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                                   short* __restrict__ packed, const PcmEnv* __restrict__ envs) {
-  extern __shared__ float xs[];
-  const PcmLimRow r = rows[blockIdx.y];
-  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  if constexpr (ENV)
-    resample_pcm16_tile<FIR, true, LAW, true, false, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
-                                                           TurnSrc{nullptr, 0, nullptr}, envs[blockIdx.y]);
-  else
-    resample_pcm16_tile<FIR, true, LAW, true>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade);
-}
-
-void launch_resample_pcm16_pool_limited(const PcmLimRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
-                                        int64_t max_count, const float* bank, const ResampleGeom& g,
-                                        int64_t lds_floats, void* packed, int law, hipStream_t s) {
-  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
-  const dim3 grid((unsigned)bx, n), block(kResampleTile);
-  const size_t lds = (size_t)lds_floats * sizeof(float);
-  short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
-  with_law(law, [&](auto lc) {
-    with_env(envs != nullptr, [&](auto ec) {
-      constexpr int LAW = decltype(lc)::value;
-      constexpr bool ENV = decltype(ec)::value;
-      if (bank) {
-        hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<true, LAW, ENV>), grid, block, lds, s, rows, fades, bank,
-                           g.L, g.M, g.K, g.left, g.ratio, pk, envs);
-      } else {
-        hipLaunchKernelGGL((resample_pcm16_pool_limited_kernel<false, LAW, ENV>), grid, block, lds, s, rows, fades,
-                           bank, 1, 1, 0, 0, 1.0, pk, envs);
-      }
-    });
-  });
-}
-
-void launch_resample_pcm16_pool(const PcmPoolRow* rows, const PcmFade* fades, const PcmEnv* envs, int n,
-                                int64_t max_count, const float* bank, const ResampleGeom& g, void* packed, int law,
-                                hipStream_t s) {
-  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
-  const dim3 grid((unsigned)bx, n), block(kResampleTile);
-  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
-  short* pk = static_cast<short*>(packed);                // the tile reads it as the codec's sample type
-  with_law(law, [&](auto lc) {
-    with_env(envs != nullptr, [&](auto ec) {
-      constexpr int LAW = decltype(lc)::value;
-      constexpr bool ENV = decltype(ec)::value;
-      if (bank) {
-        hipLaunchKernelGGL((resample_pcm16_pool_kernel<true, LAW, ENV>), grid, block, lds, s, rows, fades, bank, g.L,
-                           g.M, g.K, g.left, g.ratio, pk, envs);
-      } else {
-        hipLaunchKernelGGL((resample_pcm16_pool_kernel<false, LAW, ENV>), grid, block, lds, s, rows, fades, bank, 1, 1,
-                           0, 0, 1.0, pk, envs);
-      }
-    });
-  });
-}
-
-// The pooled kernels over turn rows (mbv_resample_turns): the same tile, its input the row's slice of the call's
-// segment table.  ENV: seg_envs[k] beside segs[k] (never read otherwise)
-template <bool FIR, int LAW, bool ENV>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_turn_kernel(const PcmPoolRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
-                           const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
-                           const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                           short* __restrict__ packed, const PcmEnv* __restrict__ seg_envs) {
-  extern __shared__ float xs[];
-  const PcmPoolRow r = rows[blockIdx.y];
-  const TurnSlice sl = slices[blockIdx.y];
-  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, false, LAW, true, true, ENV>(xs, r, bank, L, M, K, left, ratio, packed, LimiterParams{},
-                                                        fade,
-                                                        TurnSrc{segs + sl.first, sl.count,
-                                                                ENV ? seg_envs + sl.first : nullptr});
-}
-
-template <bool FIR, int LAW, bool ENV>
-__global__ void __launch_bounds__(kResampleTile)
-resample_pcm16_turn_limited_kernel(const PcmLimRow* __restrict__ rows, const TurnSlice* __restrict__ slices,
-                                   const TurnSeg* __restrict__ segs, const PcmFade* __restrict__ fades,
-                                   const float* __restrict__ bank, int L, int M, int K, int left, double ratio,
-                                   short* __restrict__ packed, const PcmEnv* __restrict__ seg_envs) {
-  extern __shared__ float xs[];
-  const PcmLimRow r = rows[blockIdx.y];
-  const TurnSlice sl = slices[blockIdx.y];
-  const PcmFade fade = fades ? fades[blockIdx.y] : PcmFade{0, -1, 0.f, 0};
-  resample_pcm16_tile<FIR, true, LAW, true, true, ENV>(xs, r.row, bank, L, M, K, left, ratio, packed, r.lim, fade,
-                                                       TurnSrc{segs + sl.first, sl.count,
-                                                               ENV ? seg_envs + sl.first : nullptr});
-}
-
-void launch_resample_pcm16_turns_limited(const PcmLimRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                         const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
-                                         const float* bank, const ResampleGeom& g, int64_t lds_floats, void* packed,
-                                         int law, hipStream_t s) {
-  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
-  const dim3 grid((unsigned)bx, n), block(kResampleTile);
-  const size_t lds = (size_t)lds_floats * sizeof(float);
-  short* pk = static_cast<short*>(packed);
-  with_law(law, [&](auto lc) {
-    with_env(seg_envs != nullptr, [&](auto ec) {
-      constexpr int LAW = decltype(lc)::value;
-      constexpr bool ENV = decltype(ec)::value;
-      if (bank) {
-        hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<true, LAW, ENV>), grid, block, lds, s, rows, slices,
-                           segs, fades, bank, g.L, g.M, g.K, g.left, g.ratio, pk, seg_envs);
-      } else {
-        hipLaunchKernelGGL((resample_pcm16_turn_limited_kernel<false, LAW, ENV>), grid, block, lds, s, rows, slices,
-                           segs, fades, bank, 1, 1, 0, 0, 1.0, pk, seg_envs);
-      }
-    });
-  });
-}
-
-void launch_resample_pcm16_turns(const PcmPoolRow* rows, const TurnSlice* slices, const TurnSeg* segs,
-                                 const PcmEnv* seg_envs, const PcmFade* fades, int n, int64_t max_count,
-                                 const float* bank, const ResampleGeom& g, void* packed, int law, hipStream_t s) {
-  int64_t bx = (max_count + kResampleTile - 1) / kResampleTile;
-  if (bx < 1) bx = 1;                                     // empty ranges still write out_samples
-  const dim3 grid((unsigned)bx, n), block(kResampleTile);
-  const size_t lds = bank ? (size_t)resample_lds_floats(g) * sizeof(float) : 0;
-  short* pk = static_cast<short*>(packed);
-  with_law(law, [&](auto lc) {
-    with_env(seg_envs != nullptr, [&](auto ec) {
-      constexpr int LAW = decltype(lc)::value;
-      constexpr bool ENV = decltype(ec)::value;
-      if (bank) {
-        hipLaunchKernelGGL((resample_pcm16_turn_kernel<true, LAW, ENV>), grid, block, lds, s, rows, slices, segs, fades,
-                           bank, g.L, g.M, g.K, g.left, g.ratio, pk, seg_envs);
-      } else {
-        hipLaunchKernelGGL((resample_pcm16_turn_kernel<false, LAW, ENV>), grid, block, lds, s, rows, slices, segs,
-                           fades, bank, 1, 1, 0, 0, 1.0, pk, seg_envs);
-      }
-    });
-  });
+void launch_resample_pcm16_pool(const PcmPoolLaunch& a, const float* bank, const ResampleGeom& g, hipStream_t s) {
+  wire_launch(bank, g, a.limited, a.lds_floats, a.law, a.slices != nullptr, a.envs != nullptr, a.max_count, a.n,
+              [&](auto fir, auto lim, auto lc, auto tc, auto ec, dim3 grid, size_t lds, const ResampleGeom& gk) {
+                hipLaunchKernelGGL((resample_pcm16_pool_kernel<decltype(fir)::value, decltype(lim)::value,
+                                                               decltype(lc)::value, decltype(tc)::value,
+                                                               decltype(ec)::value>),
+                                   grid, dim3(kResampleTile), lds, s, a.rows, a.slices, a.segs, a.envs, a.fades, bank, gk,
+                                   static_cast<short*>(a.packed));   // the tile reads it as the codec's sample type
+              });
 }
 
 // Stand-alone codec (mbv_g711_encode / mbv_g711_decode): one sample per thread

@@ -260,6 +260,60 @@ def _envelope_c(envelope):
     return _capi.MbvPcmEnvelope(None, 0, 0, 0.0) if envelope is None else envelope.c()
 
 
+def _limits_c(who, noun, limits, n):
+    """`limits` (None, or one entry per `noun`, each None or (ceiling, lookahead, hold)) -> the `MbvPcmLimit` array of a
+    wire entry (ceiling 0: that row has no limiter), or None when no row is limited."""
+    if limits is None or all(l is None for l in limits):
+        return None
+    if len(limits) != n:
+        raise ValueError("%s: one limit per %s expected (%d), got %d" % (who, noun, n, len(limits)))
+    return (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
+
+
+def _fades_c(who, noun, fades, n):
+    """`fades` (None, or one entry per `noun`, each None, a (first, count) or a `_capi.MbvPcmFade`, which is passed as it
+    is) -> the `MbvPcmFade` array of a wire entry (count -1: that row does not fade), or None when no row fades."""
+    if fades is None or all(f is None for f in fades):
+        return None
+    if len(fades) != n:
+        raise ValueError("%s: one fade per %s expected (%d), got %d" % (who, noun, n, len(fades)))
+    return (_capi.MbvPcmFade * n)(*[f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
+                                   else _capi.pcm_fade(*f) for f in fades])
+
+
+def _packed_capacity(who, packed, law, dev):
+    """The capacity of the `packed` buffer of a pooled wire entry (None: 0), a 1-D tensor of the codec's sample type."""
+    if packed is None:
+        return 0
+    wire_dtype = torch.uint8 if law else torch.int16
+    if packed.device != dev or packed.dtype != wire_dtype or packed.dim() != 1 or packed.stride(0) != 1:
+        raise ValueError("%s: packed must be a 1-D %s tensor on %s with unit stride"
+                         % (who, str(wire_dtype).replace("torch.", ""), dev))
+    return packed.shape[0]
+
+
+def _range_entry(lim, law, fade, envelope):
+    """Which entry `resample_pcm16_range` calls -> (name, its arguments behind the ones every form takes)."""
+    if envelope is not None:
+        return "mbv_resample_pcm16_range_shaped", (lim, law, fade, C.byref(envelope.c()), envelope.stride)
+    if fade is not None:
+        return ("mbv_resample_g711_range_faded", (lim, law, fade)) if law else ("mbv_resample_pcm16_range_faded", (lim, fade))
+    if law:
+        return "mbv_resample_g711_range", (lim, law)
+    return ("mbv_resample_pcm16_range", ()) if lim is None else ("mbv_resample_pcm16_range_limited", (lim,))
+
+
+def _chunks_entry(lim, law, fade, env):
+    """Which entry `resample_pcm16_chunks` calls -> (name, the tables it takes, whether it takes `law`)."""
+    if env is not None:
+        return "mbv_resample_pcm16_chunks_shaped", (lim, fade, env), True
+    if fade is not None:
+        return ("mbv_resample_g711_chunks_faded" if law else "mbv_resample_pcm16_chunks_faded"), (lim, fade), bool(law)
+    if law:
+        return "mbv_resample_g711_chunks", (lim,), True
+    return ("mbv_resample_pcm16_chunks", (), False) if lim is None else ("mbv_resample_pcm16_chunks_limited", (lim,), False)
+
+
 def _seed_value(v, what="seed"):
     """One seed of the device generator -> int in [0, 2^64).  TypeError for anything that is not an
     integer (bool and floats included), ValueError outside the range."""
@@ -1951,31 +2005,15 @@ class SynthesizerTrn(nn.Module):
                              % (int(out_first), int(out_first) + int(out_count), pcm.shape[1]))
         args = (wave, valid_samples, B, n, int(orig_sr), int(target_sr), filt, int(in_avail), int(out_first),
                 int(out_count), peak, pcm, pcm.stride(0), running_peak, out_samples)
+        who = "resample_pcm16_range"
         if envelope is not None:
             if not isinstance(envelope, Envelope):
-                raise TypeError("resample_pcm16_range: envelope must be a wire.Envelope, got %s" % type(envelope).__name__)
-            envelope.check("resample_pcm16_range", B, n, dev)
-            if fade is not None and not isinstance(fade, _capi.MbvPcmFade):
-                fade = _capi.pcm_fade(*fade)
-            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
-            self._call("mbv_resample_pcm16_range_shaped", *args, lim, law, C.byref(fade) if fade is not None else None,
-                       C.byref(envelope.c()), envelope.stride)
-            return
-        if fade is not None:
-            if not isinstance(fade, _capi.MbvPcmFade):
-                fade = _capi.pcm_fade(*fade)
-            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
-            if law:
-                self._call("mbv_resample_g711_range_faded", *args, lim, law, C.byref(fade))
-            else:
-                self._call("mbv_resample_pcm16_range_faded", *args, lim, C.byref(fade))
-        elif law:
-            lim = C.byref(_capi.MbvPcmLimit(*limiter)) if limiter is not None else None
-            self._call("mbv_resample_g711_range", *args, lim, law)
-        elif limiter is None:
-            self._call("mbv_resample_pcm16_range", *args)
-        else:
-            self._call("mbv_resample_pcm16_range_limited", *args, C.byref(_capi.MbvPcmLimit(*limiter)))
+                raise TypeError("%s: envelope must be a wire.Envelope, got %s" % (who, type(envelope).__name__))
+            envelope.check(who, B, n, dev)
+        fd = _fades_c(who, "call", [fade], 1)                # one fade and one limiter for every row of the call
+        lim = _limits_c(who, "call", [limiter], 1)
+        name, extra = _range_entry(lim, law, fd, envelope)
+        self._call(name, *args, *extra)
 
     @torch.no_grad()
     def resample_pcm16_chunks(self, chunks, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
@@ -1994,67 +2032,29 @@ class SynthesizerTrn(nn.Module):
         a one-row `wire.Envelope`: per-token volume on those chunks (`mbv_resample_pcm16_chunks_shaped`),
         in the launches the call makes without it; all None is the call without `envelopes`.  No host synchronisation
         (beyond the first call for a rate pair)."""
+        who = "resample_pcm16_chunks"
         filt = _filter_code(res_type)
         law = _law_code(encoding)
-        wire_dtype = torch.uint8 if law else torch.int16
         if not isinstance(chunks, C.Array):
             chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
+        n = len(chunks)
         dev = self._device()
-        cap = 0
-        if packed is not None:
-            if packed.device != dev or packed.dtype != wire_dtype or packed.dim() != 1 or packed.stride(0) != 1:
-                raise ValueError("resample_pcm16_chunks: packed must be a 1-D %s tensor on %s with unit stride"
-                                 % (str(wire_dtype).replace("torch.", ""), dev))
-            cap = packed.shape[0]
-        unlimited = limits is None or all(l is None for l in limits)
-        unfaded = fades is None or all(f is None for f in fades)
+        cap = _packed_capacity(who, packed, law, dev)
+        ev = None
         if envelopes is not None and any(e is not None for e in envelopes):
-            n = len(chunks)
             for name, t in (("limit", limits), ("fade", fades), ("envelope", envelopes)):
                 if t is not None and len(t) != n:
-                    raise ValueError("resample_pcm16_chunks: one %s per chunk expected (%d), got %d" % (name, n, len(t)))
+                    raise ValueError("%s: one %s per chunk expected (%d), got %d" % (who, name, n, len(t)))
             for i, e in enumerate(envelopes):
                 if e is not None:
                     if not isinstance(e, Envelope):
-                        raise TypeError("resample_pcm16_chunks: envelopes hold wire.Envelope values or None")
-                    e.check("resample_pcm16_chunks: chunk %d" % i, 1, chunks[i].in_total, dev)
-            lim = None if unlimited else (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
-            fd = None if unfaded else (_capi.MbvPcmFade * n)(*[
-                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
-                else _capi.pcm_fade(*f) for f in fades])
+                        raise TypeError("%s: envelopes hold wire.Envelope values or None" % who)
+                    e.check("%s: chunk %d" % (who, i), 1, chunks[i].in_total, dev)
             ev = (_capi.MbvPcmEnvelope * n)(*[_envelope_c(e) for e in envelopes])
-            self._call("mbv_resample_pcm16_chunks_shaped", chunks, lim, fd, ev, n, int(orig_sr), int(target_sr), filt,
-                       law, packed, cap)
-            return
-        if unlimited and unfaded and not law:
-            self._call("mbv_resample_pcm16_chunks", chunks, len(chunks), int(orig_sr), int(target_sr), filt, packed, cap)
-            return
-        lim = None
-        if not unlimited:
-            if len(limits) != len(chunks):
-                raise ValueError("resample_pcm16_chunks: one limit per chunk expected (%d), got %d"
-                                 % (len(chunks), len(limits)))
-            lim = (_capi.MbvPcmLimit * len(chunks))(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
-        if not unfaded:
-            if len(fades) != len(chunks):
-                raise ValueError("resample_pcm16_chunks: one fade per chunk expected (%d), got %d"
-                                 % (len(chunks), len(fades)))
-            fd = (_capi.MbvPcmFade * len(chunks))(*[
-                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
-                else _capi.pcm_fade(*f) for f in fades])
-            if law:
-                self._call("mbv_resample_g711_chunks_faded", chunks, lim, fd, len(chunks), int(orig_sr),
-                           int(target_sr), filt, law, packed, cap)
-            else:
-                self._call("mbv_resample_pcm16_chunks_faded", chunks, lim, fd, len(chunks), int(orig_sr),
-                           int(target_sr), filt, packed, cap)
-            return
-        if law:
-            self._call("mbv_resample_g711_chunks", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt, law,
-                       packed, cap)
-            return
-        self._call("mbv_resample_pcm16_chunks_limited", chunks, lim, len(chunks), int(orig_sr), int(target_sr), filt,
-                   packed, cap)
+        lim = _limits_c(who, "chunk", limits, n)
+        fd = _fades_c(who, "chunk", fades, n)
+        name, tables, takes_law = _chunks_entry(lim, law, fd, ev)
+        self._call(name, chunks, *tables, n, int(orig_sr), int(target_sr), filt, *((law,) if takes_law else ()), packed, cap)
 
     @torch.no_grad()
     def resample_turns(self, turns, orig_sr, target_sr, packed=None, res_type="kaiser_best", limits=None,
@@ -2068,50 +2068,34 @@ class SynthesizerTrn(nn.Module):
         one for the limited ones.  `envelopes`: None, or one list per turn with one entry per SEGMENT the turn passes,
         each None or a one-row `wire.Envelope` over that segment's own samples, applied before its de-click ramp
         (`mbv_resample_turns_shaped`).  No host synchronisation (beyond the first call for a rate pair)."""
+        who = "resample_turns"
         filt = _filter_code(res_type)
         law = _law_code(encoding)
-        wire_dtype = torch.uint8 if law else torch.int16
         if not isinstance(turns, C.Array):
             turns = (_capi.MbvTurnChunk * len(turns))(*turns)
         n = len(turns)
         dev = self._device()
-        cap = 0
-        if packed is not None:
-            if packed.device != dev or packed.dtype != wire_dtype or packed.dim() != 1 or packed.stride(0) != 1:
-                raise ValueError("resample_turns: packed must be a 1-D %s tensor on %s with unit stride"
-                                 % (str(wire_dtype).replace("torch.", ""), dev))
-            cap = packed.shape[0]
-        lim = fd = None
-        if limits is not None and any(l is not None for l in limits):
-            if len(limits) != n:
-                raise ValueError("resample_turns: one limit per turn expected (%d), got %d" % (n, len(limits)))
-            lim = (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
-        if fades is not None and any(f is not None for f in fades):
-            if len(fades) != n:
-                raise ValueError("resample_turns: one fade per turn expected (%d), got %d" % (n, len(fades)))
-            fd = (_capi.MbvPcmFade * n)(*[
-                f if isinstance(f, _capi.MbvPcmFade) else _capi.MbvPcmFade(*_capi.NO_FADE) if f is None
-                else _capi.pcm_fade(*f) for f in fades])
+        cap = _packed_capacity(who, packed, law, dev)
+        lim = _limits_c(who, "turn", limits, n)
+        fd = _fades_c(who, "turn", fades, n)
+        name, tables = "mbv_resample_turns", (lim, fd)
         if envelopes is not None and any(e is not None for per in envelopes for e in (per or ())):
             if len(envelopes) != n:
-                raise ValueError("resample_turns: one envelope list per turn expected (%d), got %d" % (n, len(envelopes)))
+                raise ValueError("%s: one envelope list per turn expected (%d), got %d" % (who, n, len(envelopes)))
             flat = []
             for i, per in enumerate(envelopes):
                 per = list(per or [None] * turns[i].n_segs)
                 if len(per) != turns[i].n_segs:
-                    raise ValueError("resample_turns: turn %d: one envelope per segment expected (%d), got %d"
-                                     % (i, turns[i].n_segs, len(per)))
+                    raise ValueError("%s: turn %d: one envelope per segment expected (%d), got %d"
+                                     % (who, i, turns[i].n_segs, len(per)))
                 for k, e in enumerate(per):
                     if e is not None:
                         if not isinstance(e, Envelope):
-                            raise TypeError("resample_turns: envelopes hold wire.Envelope values or None")
-                        e.check("resample_turns: turn %d: segment %d" % (i, k), 1, turns[i].segs[k].length, dev)
+                            raise TypeError("%s: envelopes hold wire.Envelope values or None" % who)
+                        e.check("%s: turn %d: segment %d" % (who, i, k), 1, turns[i].segs[k].length, dev)
                     flat.append(_envelope_c(e))
-            ev = (_capi.MbvPcmEnvelope * max(len(flat), 1))(*flat)
-            self._call("mbv_resample_turns_shaped", turns, lim, fd, ev, n, int(orig_sr), int(target_sr), filt, law,
-                       packed, cap)
-            return
-        self._call("mbv_resample_turns", turns, lim, fd, n, int(orig_sr), int(target_sr), filt, law, packed, cap)
+            name, tables = "mbv_resample_turns_shaped", (lim, fd, (_capi.MbvPcmEnvelope * max(len(flat), 1))(*flat))
+        self._call(name, turns, *tables, n, int(orig_sr), int(target_sr), filt, law, packed, cap)
 
     @torch.no_grad()
     def resample_ranges(self, rows, orig_sr, target_sr, res_type="kaiser_best"):

@@ -139,8 +139,9 @@ def test_pooled_rows_are_their_ranged_calls_at_the_launches_of_the_unfaded_call(
             xb, vb = x[b, 0].contiguous(), valid[b:b + 1].clone()
             pcm = torch.full((width,), sentinel, device="cuda", dtype=dtype)
             ns = torch.full((1,), -1, device="cuda", dtype=torch.int64)
-            state.append((xb, vb, pcm, ns))
-            chunks.append(_chunk(xb, vb, n, first, count, pcm, torch.zeros(1, device="cuda"), ns, peak))
+            running = torch.zeros(1, device="cuda")       # kept in `state`: the launch writes it after this loop
+            state.append((xb, vb, pcm, ns, running))
+            chunks.append(_chunk(xb, vb, n, first, count, pcm, running, ns, peak))
         packed = torch.full((6 * count + 8,), sentinel, device="cuda", dtype=dtype)
         runs = wire.wire_runs(net)
         net.resample_pcm16_chunks(chunks, orig, target, packed=packed, limits=limits, encoding=law,

@@ -948,6 +948,63 @@ int mbv_resample_turns_shaped(mbv_model *m, const mbv_turn_chunk *turns_host, co
                               int orig_sr, int target_sr, int filter, int law, void *packed, int64_t packed_capacity,
                               void *stream);
 
+/* ---- per-token pitch: a time-warp kernel between the decoder and the wire (no reference counterpart) ------------
+ * Varispeed: a token that is synthesised p times longer (per-token length_scale) and played p times faster keeps its
+ * length and sounds p higher.  Formants move with the pitch; nothing here measures quality.  MBV_PITCH_MIN / _MAX are
+ * refusal bounds and a convention.
+ *
+ * One row has `frames` frames of `hop` model-rate samples, n = frames * hop, and
+ *   rate  fp32 [frames]      the playback rate R[f] of frame f, MBV_PITCH_MIN <= R[f] <= MBV_PITCH_MAX
+ *   U     fp64 [frames + 1]  U[0] = 0, U[f + 1] = U[f] + (double)hop / (double)R[f], added in ascending order
+ *   n_out = (int64)floor(U[frames])
+ * Output t in [0, n_out) lies in the largest frame f with U[f] <= (double)t, at the model time
+ *   tau = (double)(f * hop) + ((double)t - U[f]) * (double)R[f]          every operation rounded to fp64 on its own
+ * and is resampy's interpolator evaluated at time tau with ratio 1 / R[f]: scale = R[f] > 1 ? 1.0 / R[f] : 1.0, index
+ * step (int)(scale * 512), the window (MBV_RESAMPLE_KAISER_BEST / _FAST, one fp64 table per filter, fp32 on the device)
+ * times scale, both tap loops bounded by [0, n).  The sample at model index j is wave[j], or with an envelope
+ * fl32(wave[j] * e(j)) as the shaped wire entries read it; nothing at or past min(n, in_avail) and nothing below 0 is
+ * loaded: a zero stands there.  fp32 weights and accumulation.  A pure function of t: a row does not depend on how
+ * it is cut into ranges or on the rows that share its launch.
+ *
+ * mbv_warp_plan (host only): U_out_host [frames + 1] and *n_out from rate_host.  Refuses (mbv_last_error(NULL)) hop or
+ *   frames < 1 and a rate that is not finite or lies outside the bounds, naming the frame.
+ * mbv_warp_ready (host only): how many outputs are final once the model samples [0, in_avail) exist; -1 when refused.
+ *   n_out for in_avail >= n.  Else HW = ceil(num_zeros * max(1, max_f R[f])) + 2 (num_zeros 64 / 16), a = in_avail - HW,
+ *   0 for a <= 0, and with g = a / hop:  max(0, floor(U[g] + (double)(a - g * hop) / (double)R[g]) - 1).
+ * mbv_warp_ranges: outputs [out_first, out_first + out_count) of n rows, each into its own fp32 row, in ONE launch;
+ *   rows_host is HOST memory.  wave, U, rate (and the envelope's gain) are DEVICE; U_host / rate_host are the HOST copies
+ *   of the same tables, from which the entry recomputes the row's readiness.  envelope.gain NULL = none (sibling fields 0).
+ *   No synchronisation; mbv_warp_runs counts the launches.  Refused before anything is launched, the handle stays usable
+ *   and the message names the row: n < 1; a NULL pointer; frames or hop < 1, samples != frames * hop; negative in_avail,
+ *   out_first or out_count; outputs beyond mbv_warp_ready of the row or beyond out_capacity; an unknown res_type; a rate
+ *   outside the bounds; an envelope the shaped entries would refuse or whose frames * hop is below samples; two rows
+ *   that write one sample. */
+#define MBV_PITCH_MIN 0.5f
+#define MBV_PITCH_MAX 2.0f
+typedef struct mbv_warp_row {
+  const float *wave;
+  int64_t samples;
+  int64_t in_avail;
+  const double *U;
+  const float *rate;
+  const double *U_host;
+  const float *rate_host;
+  int32_t frames;
+  int32_t hop;
+  mbv_pcm_envelope envelope;
+  int64_t out_first;
+  int64_t out_count;
+  float *out;
+  int64_t out_capacity;
+  int32_t res_type;
+  int32_t reserved;
+} mbv_warp_row;
+int mbv_warp_plan(int hop, int64_t frames, const float *rate_host, double *U_out_host, int64_t *n_out);
+int64_t mbv_warp_ready(int hop, int64_t frames, const float *rate_host, const double *U_host, int res_type,
+                       int64_t in_avail);
+int mbv_warp_ranges(mbv_model *m, const mbv_warp_row *rows_host, int n, void *stream);
+int64_t mbv_warp_runs(mbv_model *m);
+
 /* ---- loudness: ITU-R BS.1770 integrated loudness of a mono waveform, on the device ------------------------------
  * K-weighting (two cascaded biquads, zero state at sample 0), segments of H = (rate + 5) / 10 samples (100 ms; a half
  * rounds up), blocks of four segments (400 ms, 75 % overlap), the absolute gate at -70 LKFS and the relative gate 10 LU

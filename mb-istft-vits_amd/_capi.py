@@ -47,6 +47,7 @@ SYMBOLS = [
     "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
     "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
     "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped", "mbv_resample_turns_shaped",
+    "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
 ]
 
 
@@ -142,6 +143,18 @@ class MbvGainRow(C.Structure):
 class MbvPcmEnvelope(C.Structure):
     """mbv_pcm_envelope of include/mbistft_vits.h (the shaped wire entries); gain None (all zero) = no envelope."""
     _fields_ = [("gain", C.c_void_p), ("frames", C.c_int64), ("hop", C.c_int32), ("inv_hop", C.c_float)]
+
+
+class MbvWarpRow(C.Structure):
+    """mbv_warp_row of include/mbistft_vits.h (mbv_warp_ranges): U / rate on the device, U_host / rate_host their host
+    copies."""
+    _fields_ = [("wave", C.c_void_p), ("samples", C.c_int64), ("in_avail", C.c_int64), ("U", C.c_void_p),
+                ("rate", C.c_void_p), ("U_host", C.c_void_p), ("rate_host", C.c_void_p), ("frames", C.c_int32),
+                ("hop", C.c_int32), ("envelope", MbvPcmEnvelope), ("out_first", C.c_int64), ("out_count", C.c_int64),
+                ("out", C.c_void_p), ("out_capacity", C.c_int64), ("res_type", C.c_int32), ("reserved", C.c_int32)]
+
+
+PITCH_MIN, PITCH_MAX = 0.5, 2.0     # MBV_PITCH_MIN / MBV_PITCH_MAX
 
 
 def fit_result(word):
@@ -351,7 +364,7 @@ def lib():
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
     # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
-    # turns' two, prosody's four and volume's seven may be absent there, and calling one then raises AttributeError.
+    # turns' two, prosody's four, volume's seven and pitch's four may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -374,7 +387,8 @@ def lib():
                 "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
                 "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
                 "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped",
-                "mbv_resample_turns_shaped") if os.environ.get("MBV_LIB") else ()
+                "mbv_resample_turns_shaped",
+                "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -495,6 +509,13 @@ def lib():
                                                        C.c_int64, vp]
         L.mbv_resample_turns_shaped.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit),
                                                 C.POINTER(MbvPcmFade), envp, i32, i32, i32, i32, i32, vp, C.c_int64, vp]
+    if hasattr(L, "mbv_warp_ranges") or not optional:
+        L.mbv_warp_plan.argtypes = [i32, C.c_int64, vp, vp, i64p]
+        L.mbv_warp_ready.argtypes = [i32, C.c_int64, vp, vp, i32, C.c_int64]
+        L.mbv_warp_ready.restype = C.c_int64
+        L.mbv_warp_ranges.argtypes = [vp, C.POINTER(MbvWarpRow), i32, vp]
+        L.mbv_warp_runs.argtypes = [vp]
+        L.mbv_warp_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -6,8 +6,8 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 OBJS=""
 PIDS=""
-for f in conv1d conv1d_narrow wn_fused ops sdp attention istft_pqmf resample spectrogram align rng loudness capi; do
-  if [ ! -f $f.o ] || [ $f.hip -nt $f.o ] || [ kernels.h -nt $f.o ] || [ philox.h -nt $f.o ] || [ g711.h -nt $f.o ] || [ istft_tail.inc -nt $f.o ] || [ ../../include/mbistft_vits.h -nt $f.o ]; then
+for f in conv1d conv1d_narrow wn_fused ops sdp attention istft_pqmf resample warp spectrogram align rng loudness capi; do
+  if [ ! -f $f.o ] || [ $f.hip -nt $f.o ] || [ kernels.h -nt $f.o ] || [ philox.h -nt $f.o ] || [ g711.h -nt $f.o ] || [ pcm_env.h -nt $f.o ] || [ istft_tail.inc -nt $f.o ] || [ ../../include/mbistft_vits.h -nt $f.o ]; then
     rm -f $f.o                     # a failed compile must not leave a stale object to link
     $HIPCC $FLAGS -c $f.hip -o $f.o &
     PIDS="$PIDS $!"

@@ -145,6 +145,8 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t decoder_runs = 0;        // run_decoder calls since mbv_create (mbv_decoder_runs)
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
+  int64_t warp_runs = 0;           // launches of the time-warp kernel (mbv_warp_runs)
+  float* warp_win[2] = {nullptr, nullptr};   // filter -> fp32 window and its differences on the device (mbv_warp_ranges)
   int64_t noise_runs = 0;          // mbv_randn_blocks launches (mbv_noise_runs)
   int64_t loudness_runs = 0;       // launches of the loudness kernel (mbv_loudness_runs)
   std::map<int, LoudnessParams> loudness_params;    // rate -> K-weighting tables (built once a rate, host only)
@@ -2039,6 +2041,8 @@ void mbv_destroy(mbv_model* m) {
   if (m->user_tab) (void)hipFree(m->user_tab);
   if (m->peak_buf) (void)hipFree(m->peak_buf);
   for (auto& kv : m->resample_banks) (void)hipFree(kv.second.d);
+  for (float* w : m->warp_win)
+    if (w) (void)hipFree(w);
   for (auto& kv : m->spec_tables) { (void)hipFree(kv.second.tw); (void)hipFree(kv.second.win); }
   if (m->ev_ok) { for (auto& set : m->evr) for (auto& e : set) if (e) (void)hipEventDestroy(e); for (auto& e : m->evk) (void)hipEventDestroy(e); }
   if (m->aux_ok) {
@@ -4164,6 +4168,135 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
 }
 
 int64_t mbv_input_runs(mbv_model* m) { return m ? m->input_runs : -1; }
+
+namespace {
+constexpr int kWarpZeros[2] = {64, 16};   // num_zeros of kaiser_best / kaiser_fast
+
+int warp_fail(mbv_model* m, const std::string& why) { (m ? m->err : g_create_error) = why; return 1; }
+
+// the device window of a filter: [nwin] fp32 values, then their [nwin] forward differences (fp64, rounded once)
+int warp_window(mbv_model* m, const char* who, int filter, const float** out) {
+  if (!m->warp_win[filter]) {
+    std::vector<double> win;
+    resample_window(filter, &win, nullptr, nullptr);
+    const size_t nwin = win.size();
+    std::vector<float> tab(2 * nwin, 0.f);
+    for (size_t i = 0; i < nwin; ++i) tab[i] = (float)win[i];
+    for (size_t i = 0; i + 1 < nwin; ++i) tab[nwin + i] = (float)(win[i + 1] - win[i]);
+    float* d = nullptr;
+    HIPCHK(m, hipMalloc((void**)&d, tab.size() * sizeof(float)));
+    if (hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      return m->fail("%s: uploading the filter window failed", who);
+    }
+    m->warp_win[filter] = d;
+  }
+  *out = m->warp_win[filter];
+  return 0;
+}
+}  // namespace
+
+int mbv_warp_plan(int hop, int64_t frames, const float* rate_host, double* U_out_host, int64_t* n_out) {
+  const char* who = "mbv_warp_plan";
+  if (hop < 1 || frames < 1 || !rate_host || !U_out_host || !n_out)
+    return warp_fail(nullptr, std::string(who) + ": hop and frames must be >= 1 and no pointer NULL");
+  const int64_t bad = warp_plan(hop, frames, rate_host, U_out_host, n_out);
+  if (bad >= 0)
+    return warp_fail(nullptr, std::string(who) + ": frame " + std::to_string(bad) + ": rate " +
+                                  std::to_string(rate_host[bad]) + " is not a finite value in [0.5, 2]");
+  return 0;
+}
+
+int64_t mbv_warp_ready(int hop, int64_t frames, const float* rate_host, const double* U_host, int res_type,
+                       int64_t in_avail) {
+  const char* who = "mbv_warp_ready";
+  if (hop < 1 || frames < 1 || !rate_host || !U_host) {
+    warp_fail(nullptr, std::string(who) + ": hop and frames must be >= 1 and no pointer NULL");
+    return -1;
+  }
+  if (res_type != MBV_RESAMPLE_KAISER_BEST && res_type != MBV_RESAMPLE_KAISER_FAST) {
+    warp_fail(nullptr, std::string(who) + ": unknown res_type " + std::to_string(res_type) +
+                           " (0 = kaiser_best, 1 = kaiser_fast)");
+    return -1;
+  }
+  if (in_avail < 0) in_avail = 0;
+  return warp_ready(hop, frames, rate_host, U_host, kWarpZeros[res_type], in_avail);
+}
+
+int mbv_warp_ranges(mbv_model* m, const mbv_warp_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_warp_ranges";
+  if (n < 1 || !rows_host) return m->fail("%s: n must be >= 1 and rows_host given", who);
+  DEVICE_GUARD(m);
+  std::vector<int> live, hw(n);
+  for (int i = 0; i < n; ++i) {
+    const mbv_warp_row& k = rows_host[i];
+    if (!k.wave || !k.U || !k.rate || !k.U_host || !k.rate_host || !k.out)
+      return m->fail("%s: row %d: wave, U, rate, U_host, rate_host or out missing", who, i);
+    if (k.res_type != MBV_RESAMPLE_KAISER_BEST && k.res_type != MBV_RESAMPLE_KAISER_FAST)
+      return m->fail("%s: row %d: unknown res_type %d (0 = kaiser_best, 1 = kaiser_fast)", who, i, (int)k.res_type);
+    if (k.frames < 1 || k.hop < 1 || k.samples != (int64_t)k.frames * k.hop)
+      return m->fail("%s: row %d: frames and hop must be >= 1 and samples (%lld) = frames * hop", who, i,
+                     (long long)k.samples);
+    if (k.in_avail < 0 || k.out_first < 0 || k.out_count < 0 || k.out_capacity < 0)
+      return m->fail("%s: row %d: in_avail, out_first, out_count and out_capacity must be >= 0", who, i);
+    if (k.out_first > k.out_capacity || k.out_count > k.out_capacity - k.out_first)
+      return m->fail("%s: row %d: outputs [%lld, %lld) lie outside the row of out_capacity %lld", who, i,
+                     (long long)k.out_first, (long long)(k.out_first + k.out_count), (long long)k.out_capacity);
+    for (int f = 0; f < k.frames; ++f)
+      if (!(k.rate_host[f] >= kPitchMin && k.rate_host[f] <= kPitchMax))
+        return m->fail("%s: row %d: frame %d: rate %g is not a finite value in [0.5, 2]", who, i, f,
+                       (double)k.rate_host[f]);
+    const mbv_pcm_envelope& e = k.envelope;
+    if (!e.gain) {
+      if (e.frames || e.hop || e.inv_hop != 0.f)
+        return m->fail("%s: row %d: an envelope without a gain table has frames, hop and inv_hop 0", who, i);
+    } else {
+      const float inv = e.hop >= 1 ? 1.0f / (float)e.hop : 0.f;
+      if (e.hop < 1 || e.frames < 1 || memcmp(&inv, &e.inv_hop, sizeof inv) != 0)
+        return m->fail("%s: row %d: an envelope has hop >= 1, frames >= 1 and inv_hop = 1.0f / (float)hop", who, i);
+      if (e.frames * (int64_t)e.hop < k.samples)
+        return m->fail("%s: row %d: the envelope's %lld frames of %d samples do not cover the row's %lld samples", who,
+                       i, (long long)e.frames, (int)e.hop, (long long)k.samples);
+    }
+    const int zeros = kWarpZeros[k.res_type];
+    const int64_t ready = warp_ready(k.hop, k.frames, k.rate_host, k.U_host, zeros, k.in_avail);
+    if (k.out_first + k.out_count > ready)
+      return m->fail("%s: row %d: outputs up to %lld asked for, but %lld of %lld model samples make only %lld final",
+                     who, i, (long long)(k.out_first + k.out_count), (long long)k.in_avail, (long long)k.samples,
+                     (long long)ready);
+    hw[i] = warp_half_width(zeros, k.frames, k.rate_host);
+    if (k.out_count > 0) live.push_back(i);
+  }
+  if (live.empty()) return 0;
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(rows_host[i].out + rows_host[i].out_first); },
+                                    [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].out_count; });
+  if (clash.first >= 0)
+    return m->fail("%s: rows %d and %d write overlapping ranges of one out", who, clash.first, clash.second);
+  const float* win[2] = {nullptr, nullptr};
+  for (int i : live) {
+    const int ft = rows_host[i].res_type;
+    if (!win[ft] && warp_window(m, who, ft, &win[ft])) return 1;
+  }
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(WarpRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  WarpRow* rows = reinterpret_cast<WarpRow*>(m->scrB);
+  upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_warp_row& k = rows_host[live[i]];
+    return WarpRow{k.wave, k.samples, k.in_avail, k.U, k.rate, k.frames, k.hop, env_of(&k.envelope), k.out_first,
+                   k.out_first + k.out_count, k.out, win[k.res_type], kWarpZeros[k.res_type], hw[live[i]]};
+  });
+  if (grid_y_slices(live, [&](int i) { return rows_host[i].out_count; }, [&](size_t f, int nn, int64_t max_count) {
+        if ((max_count + kWarpTile - 1) / kWarpTile > 0x7fffffff) return m->fail("%s: a range too long for one grid", who);
+        ++m->warp_runs;
+        launch_warp_ranges(rows + f, nn, max_count, s);
+        return 0;
+      })) return 1;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_warp_runs(mbv_model* m) { return m ? m->warp_runs : -1; }
 
 namespace {
 // what mbv_randn_blocks and mbv_randn_host refuse about one block's range and purpose, or null

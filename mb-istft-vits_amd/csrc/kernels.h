@@ -590,6 +590,47 @@ int64_t resample_ready_open(const ResampleGeom& g, int64_t in_avail);
 void launch_resample_ranges(const ResampleRangeRow* rows, int n, int64_t max_count, const float* bank,
                             const ResampleGeom& g, hipStream_t s);
 
+// the fp64 half window of a filter (0 = kaiser_best, 1 = kaiser_fast; checked by the caller), [nb * num_zeros + 1]:
+// kaiser(2n + 1, beta)[n:] * rolloff * sinc(rolloff * linspace(0, num_zeros, n + 1)), unscaled.  resample_bank builds
+// its phases from it, the time-warp kernel reads it as it is
+void resample_window(int filter, std::vector<double>* win, int* num_zeros, int* nb);
+
+// ---------------------------------------------------------------- time warp (warp.hip)
+// Per-token pitch by varispeed: a resampler whose ratio changes with the output sample.  One row has F frames of hop
+// model-rate samples (n = F hop), a playback rate R[f] in [kPitchMin, kPitchMax] per frame, and the output position of
+// every frame start, U[0] = 0, U[f + 1] = U[f] + (double)hop / (double)R[f] in ascending order; n_out = floor(U[F]).
+// Output t lies in the frame f with U[f] <= t < U[f + 1], at model time
+//   tau = (double)(f hop) + ((double)t - U[f]) (double)R[f]        every operation rounded to fp64 on its own
+// and is resampy's interpolator evaluated there with ratio 1 / R[f]: scale = R[f] > 1 ? 1 / R[f] : 1, index step
+// int(scale nb), the window times scale, taps outside [0, min(n, in_avail)) zero.  A pure function of t: no state.
+constexpr float kPitchMin = 0.5f, kPitchMax = 2.0f;
+constexpr int kWarpTile = 256;                 // outputs per workgroup (one per thread)
+// floats of the staged window: 255 outputs at kPitchMax apart and the half width of kaiser_best there on both sides
+constexpr int kWarpWindow = 776;
+// first frame whose rate is not finite or lies outside the bounds, or -1; then U [F + 1] and *n_out are written
+int64_t warp_plan(int hop, int64_t F, const float* R, double* U, int64_t* n_out);
+// taps at either side of floor(tau) that an output can reach, with slack: ceil(num_zeros max(1, max R)) + 2
+int warp_half_width(int num_zeros, int64_t F, const float* R);
+// outputs no tap of which lies at or past in_avail (the count of DESIGN §7.22); floor(U[F]) once in_avail >= F hop
+int64_t warp_ready(int hop, int64_t F, const float* R, const double* U, int num_zeros, int64_t in_avail);
+// A table row (in the arena, upload_rows): one stream.  `win` is the fp32 window of the row's filter, [nwin] values
+// followed by their [nwin] forward differences (the last one zero), nwin = 512 num_zeros + 1
+struct WarpRow {
+  const float* x;              // the decoded model-rate row
+  int64_t n, in_avail;         // F hop; nothing at or past min(n, in_avail) is loaded
+  const double* U;             // [F + 1]
+  const float* R;              // [F]
+  int32_t F, hop;
+  PcmEnv env;                  // or kNoEnv: the sample at j is env_mul(x[j], env, j)
+  int64_t out_first, out_end;
+  float* out;                  // the warped row
+  const float* win;
+  int32_t num_zeros, hw;       // hw = warp_half_width of the row
+};
+// outputs [out_first, out_end) of every table row (n <= 65535) in one launch; max_count >= out_end - out_first of every
+// row.  The caller guarantees out_end <= warp_ready of the row and the row's capacity.
+void launch_warp_ranges(const WarpRow* rows, int n, int64_t max_count, hipStream_t s);
+
 // ---------------------------------------------------------------- linear spectrogram (spectrogram.hip)
 // |STFT| of spectrogram_torch(center=False) per row as if alone: (n_fft - hop) / 2 zeros each side, periodic
 // Hann of length win centred in n_fft, [B, n_fft / 2 + 1, F] with frames past a row's length zero.

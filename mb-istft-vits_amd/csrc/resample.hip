@@ -16,6 +16,7 @@
 // its filter tables are rebuilt from the documented specs here.
 #include "kernels.h"
 #include "g711.h"
+#include "pcm_env.h"
 
 #include <cmath>
 #include <cstdio>
@@ -63,6 +64,23 @@ int resample_reduce(int orig_sr, int target_sr, int* L, int* M) {
   return 0;
 }
 
+void resample_window(int filter, std::vector<double>* win, int* num_zeros, int* nb) {
+  const FilterSpec& f = kSpecs[filter];
+  const int n = (1 << f.precision) * f.num_zeros;
+  const int nwin = n + 1;
+  win->resize(nwin);
+  const double alpha = (double)n;            // (2n + 1 - 1) / 2
+  const double i0b = bessel_i0(f.beta);
+  for (int i = 0; i < nwin; ++i) {
+    const double u = (double)i / alpha;      // (j - alpha) / alpha for j = n + i
+    const double kw = bessel_i0(f.beta * std::sqrt(1.0 - u * u)) / i0b;
+    const double x = (double)i * ((double)f.num_zeros / (double)n);
+    (*win)[i] = kw * (f.rolloff * sinc(f.rolloff * x));
+  }
+  if (num_zeros) *num_zeros = f.num_zeros;
+  if (nb) *nb = 1 << f.precision;
+}
+
 const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<float>* bank, ResampleGeom* geom) {
   if (orig_sr <= 0 || target_sr <= 0) return "sample rates must be positive";
   if (filter != 0 && filter != 1) return "unknown resampling filter (0 = kaiser_best, 1 = kaiser_fast)";
@@ -82,16 +100,8 @@ const char* resample_bank(int orig_sr, int target_sr, int filter, std::vector<fl
   // (bank == null: mbv_resample_ready, once per streamed chunk) needs only the wing counts, not the table
   std::vector<double> win, delta;
   if (bank) {
-    win.resize(nwin);
+    resample_window(filter, &win, nullptr, nullptr);
     delta.resize(nwin);
-    const double alpha = (double)n;            // (2n + 1 - 1) / 2
-    const double i0b = bessel_i0(f.beta);
-    for (int i = 0; i < nwin; ++i) {
-      const double u = (double)i / alpha;      // (j - alpha) / alpha for j = n + i
-      const double kw = bessel_i0(f.beta * std::sqrt(1.0 - u * u)) / i0b;
-      const double x = (double)i * ((double)f.num_zeros / (double)n);
-      win[i] = kw * (f.rolloff * sinc(f.rolloff * x));
-    }
     if (ratio < 1.0)
       for (auto& w : win) w *= ratio;
     for (int i = 0; i + 1 < nwin; ++i) delta[i] = win[i + 1] - win[i];
@@ -216,37 +226,6 @@ __device__ __forceinline__ void resample_stage(float* xs, const uint8_t* __restr
 // the ONE load behind it is predicated exactly as the plain row's is (below the frontier, inside a segment).
 // `envs` (ENV = true only): envs[s] beside segs[s], the gain envelope of that segment (gain null: none)
 struct TurnSrc { const TurnSeg* __restrict__ segs; int n; const PcmEnv* __restrict__ envs; };
-
-// The gain envelope (kernels.h) at model-rate sample j >= 0 of its row: G[f] + w (G[f + 1] - G[f]) with
-// f = j / hop and w = (float)(j - f hop) * inv_hop, every operation rounded to fp32 on its own (no fma: the NumPy
-// restatement computes the same bits).  j < frames * hop (checked on the host), so f + 1 <= frames: inside the table.
-// The toolchain's __fmul_rn / __fadd_rn are inline functions over the plain operators, compiled contractable: hipcc
-// fuses them into an fma like any others.  The pragma is what keeps the product and the sum apart; it covers the
-// operators written in this function (also after inlining), not those inside a function it calls
-__device__ __forceinline__ float env_at(const PcmEnv& e, int64_t j) {
-#pragma clang fp contract(off)
-  int64_t f;
-  int r;
-  if (j < 0x80000000LL) {                                 // the common case: one 32-bit division
-    const unsigned q = (unsigned)j / (unsigned)e.hop;
-    f = q;
-    r = (int)((unsigned)j - q * (unsigned)e.hop);
-  } else {
-    f = j / e.hop;
-    r = (int)(j - f * e.hop);
-  }
-  const float g0 = e.gain[f], g1 = e.gain[f + 1];
-  const float w = (float)r * e.inv_hop;
-  const float d = g1 - g0;
-  const float wd = w * d;
-  return g0 + wd;
-}
-
-// the sample a shaped row stages: rounded once, before anything else reads it; a row without an envelope keeps v
-__device__ __forceinline__ float env_mul(float v, const PcmEnv& e, int64_t j) {
-#pragma clang fp contract(off)
-  return e.gain ? v * env_at(e, j) : v;
-}
 
 // timeline index j: zero in a pause, beyond the timeline and at or past `limit` (nothing there is loaded).  ENV: the
 // envelope of the segment first, its de-click ramp after it (the order of a timeline assembled from shaped waves)

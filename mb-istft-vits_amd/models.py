@@ -202,6 +202,78 @@ def _gain_arg(who, gain, B, T, row=False):
     return g.to(torch.float32).contiguous()
 
 
+PITCH_MIN, PITCH_MAX = _capi.PITCH_MIN, _capi.PITCH_MAX      # +-12 semitones: refusal bounds and a convention
+PITCH_GLIDE_FRAMES = 2       # default `pitch_glide_frames=`: a convention, not a measurement
+
+
+def pitch_of_semitones(st):
+    """A pitch change in semitones -> the factor `pitch=` takes: 2 ** (st / 12)."""
+    st = float(st)
+    if not math.isfinite(st):
+        raise ValueError("pitch_of_semitones: need a finite number of semitones, got %r" % st)
+    return 2.0 ** (st / 12.0)
+
+
+def _pitch_arg(who, pitch, B, T, row=False):
+    """`pitch=` of an entry, checked on the host -> None, or the per-token pitch factors as a CPU fp32 tensor [B, T]: a
+    host sequence or CPU tensor of T_text values per row, finite, in [PITCH_MIN, PITCH_MAX] after rounding to fp32.  A
+    device tensor is refused."""
+    if pitch is None:
+        return None
+    shapes = ((T,), (1, T), (1, 1, T)) if row else ((B, T), (B, 1, T))
+    names = "[T_text]" if row else "[B, T_text]"
+    if torch.is_tensor(pitch):
+        if pitch.is_cuda:
+            raise TypeError("%s: pitch must be a host sequence or a CPU tensor (the warp is planned on the host), got a "
+                            "device tensor" % who)
+        if pitch.dtype.is_complex or pitch.dtype == torch.bool:
+            raise TypeError("%s: pitch must hold real numbers, got %s" % (who, pitch.dtype))
+        p = pitch.detach().to(torch.float64)
+    else:
+        if isinstance(pitch, (str, bytes)):
+            raise TypeError("%s: pitch must be a sequence of numbers %s" % (who, names))
+        try:
+            arr = np.asarray(pitch)
+        except Exception:
+            raise TypeError("%s: pitch must be a sequence of numbers %s" % (who, names))
+        if arr.dtype == np.bool_ or arr.dtype.kind not in "iuf":
+            raise TypeError("%s: pitch must hold real numbers, got %s" % (who, arr.dtype))
+        p = torch.from_numpy(arr.astype(np.float64))
+    if tuple(p.shape) not in shapes:
+        raise ValueError("%s: pitch must be %s = %s, got %s" % (who, names, shapes[0], tuple(p.shape)))
+    p = p.reshape(B, T)
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError("%s: pitch must be finite" % who)
+    p = p.to(torch.float32).contiguous()
+    if bool((p < PITCH_MIN).any()) or bool((p > PITCH_MAX).any()):
+        raise ValueError("%s: pitch must be in [PITCH_MIN = %g, PITCH_MAX = %g] (factors; pitch_of_semitones converts)"
+                         % (who, PITCH_MIN, PITCH_MAX))
+    return p
+
+
+def _pitch_scale(who, pitch, length_scale, durations, compensate):
+    """The `length_scale` an entry with `pitch=` encodes with: refused beside `durations=`; with `compensate` the
+    per-token table fl32(length_scale) * pitch, formed in fp32 on the host (on the device of a tensor `length_scale`),
+    so that every token keeps its length; else `length_scale` as it is (plain varispeed)."""
+    if durations is not None:
+        raise ValueError("%s: pitch= does not go with durations=: they are used as given, so no token can be "
+                         "lengthened to be played faster; scale the durations by the pitch yourself and warp the "
+                         "result with net.warp(wave, net.warp_map(pitch, durations))" % who)
+    if not compensate:
+        return length_scale
+    if torch.is_tensor(length_scale):
+        if not length_scale.dtype.is_floating_point:
+            raise TypeError("%s: a per-token length_scale must be a floating tensor, got %s" % (who, length_scale.dtype))
+        base = length_scale.to(torch.float32)
+        if base.numel() != 1:
+            if base.numel() != pitch.numel():
+                raise ValueError("%s: a per-token length_scale must hold one value per token (%d), got %s"
+                                 % (who, pitch.numel(), tuple(base.shape)))
+            base = base.reshape(pitch.shape)
+        return base * pitch.to(base.device)
+    return torch.tensor(float(length_scale), dtype=torch.float32) * pitch
+
+
 class Envelope:
     """The gain envelope of a wire call (`wire.Envelope`): the frame gains of `net.frame_gain` /
     `st.frame_gain` and the model's samples per frame.
@@ -367,14 +439,19 @@ class Request:
                          `infer_stream(marks=True)` gives them
       gain               per-token volume, as `infer_stream(gain=)`: T_text linear factors in [0, GAIN_MAX] on the host
                          (`gain_of_db` converts); the stream gets `frame_gain` and the wire path shapes it
+      pitch, pitch_compensate, pitch_glide_frames      per-token pitch, as `infer_stream(pitch=)`: T_text factors in
+                         [PITCH_MIN, PITCH_MAX] on the host (`pitch_of_semitones` converts); the stream gets `warp` and
+                         the wire path warps it.  Not with durations
     Everything that can be checked without the model is checked here (ValueError / TypeError)."""
 
     __slots__ = ("x", "sid", "noise_scale", "length_scale", "noise_scale_w", "max_len", "chunk_frames",
-                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks", "scale", "extra", "fit", "gain")
+                 "max_chunk_frames", "durations", "durations_dtype", "seed", "marks", "scale", "extra", "fit", "gain",
+                 "pitch", "pitch_glide_frames")
 
     def __init__(self, x, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
                  chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
-                 fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None):
+                 fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None, pitch=None, pitch_compensate=True,
+                 pitch_glide_frames=PITCH_GLIDE_FRAMES):
         self.seed = None if seed is None else _seed_value(seed, "Request: seed")
         self.marks = bool(marks)
         if not torch.is_tensor(x):
@@ -386,6 +463,14 @@ class Request:
         if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
             raise TypeError("Request: x must hold integer token ids, got %s" % x.dtype)
         self.x = x.to(torch.int64)
+        # per-token pitch: the factors as [T_text] fp32 on the host, or None; the stream gets `warp`
+        pitch = _pitch_arg("Request", pitch, 1, self.x.numel(), row=True)
+        self.pitch = None if pitch is None else pitch.reshape(-1)
+        self.pitch_glide_frames = int(pitch_glide_frames)
+        if self.pitch_glide_frames < 0:
+            raise ValueError("Request: pitch_glide_frames must be >= 0")
+        if pitch is not None:
+            length_scale = _pitch_scale("Request", self.pitch, length_scale, durations, pitch_compensate)
         if sid is not None:
             if torch.is_tensor(sid):
                 if sid.numel() != 1:
@@ -1315,7 +1400,8 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None,
                      chunk_frames=32, max_chunk_frames=256, durations=None, seed=None, marks=False, extra_frames=None,
-                     fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None):
+                     fit_frames=None, fit_bounds=FIT_BOUNDS, gain=None, pitch=None, pitch_compensate=True,
+                     pitch_glide_frames=PITCH_GLIDE_FRAMES):
         """`infer(...)[0]` chunk by chunk.  Runs the text encoder, the duration predictor, the prior noise draw and the
         flows exactly as `infer` does (same random draws; `durations` and `seed` as in `infer`), then returns `dec_stream` of
         z * y_mask (truncated to max_len) with `y_lengths` set on the stream.  The concatenation is bitwise
@@ -1335,8 +1421,30 @@ class SynthesizerTrn(nn.Module):
                  that holds each frame, held behind a row's end (one `mbv_frame_gain` launch, no synchronisation).  The
                  decode is untouched: `st.o` is bitwise the stream without `gain=`.  The wire path (`stream_pcm16`,
                  `PcmPool.add`, `Turn.append`) picks `st.frame_gain` up and shapes the samples in front of its filter
-                 and limiter.  None (default): `st.frame_gain` is None and nothing is launched."""
-        marks_out = [] if marks else None
+                 and limiter.  None (default): `st.frame_gain` is None and nothing is launched.
+          pitch  per-token pitch by varispeed, one utterance only (B = 1): a host sequence or CPU tensor
+                 [1, T_text] of factors in [PITCH_MIN, PITCH_MAX] (`pitch_of_semitones` converts).  The model has no F0
+                 input: token t is played p_t times faster by a time-warp kernel behind the decoder, so it sounds p_t
+                 higher and its formants move with the pitch.  `pitch_compensate=True` (default) multiplies the
+                 per-token `length_scale` by p_t (fp32, on the host; the tensor route of the prosody controls), so every
+                 token keeps its length; False is plain varispeed.  Refused beside `durations=`.  The stream gets
+                 `st.warp`, a `stream.WarpMap`: the rate of every kept frame (the pitch of the token that holds it, then
+                 the mean over `pitch_glide_frames` frames either side; 0 = steps), the warped frame positions and the
+                 warped length.  It needs the token marks, which ride in the read-back the call makes anyway (`st.marks`
+                 is set too): no extra synchronisation, no extra encoder run.  The decode is untouched: `st.o` is bitwise
+                 the stream made with the same effective `length_scale` and no pitch.  The wire path (`stream_pcm16`,
+                 `PcmPool.add`, `Turn.append`) warps in front of its filter; `net.warp(o, st.warp)` is the one-shot
+                 form.  None (default): `st.warp` is None and nothing is launched."""
+        if pitch is not None:
+            B, T = x.shape[0], x.shape[1]
+            if B != 1:
+                raise ValueError("infer_stream: pitch= takes ONE utterance (B = 1), got B = %d: the warped rows of a "
+                                 "batch have different lengths; use infer_streams / PcmPool.admit" % B)
+            pitch = _pitch_arg("infer_stream", pitch, B, T)
+            if int(pitch_glide_frames) < 0:
+                raise ValueError("infer_stream: pitch_glide_frames must be >= 0")
+            length_scale = _pitch_scale("infer_stream", pitch, length_scale, durations, pitch_compensate)
+        marks_out = [] if marks or pitch is not None else None
         gain_out = []
         r = self._run(x, x_lengths, sid, noise_scale, length_scale, None, decode=False,
                       noise_scale_w=noise_scale_w, outputs=("z", "y_mask"), durations=durations, seed=seed,
@@ -1354,9 +1462,12 @@ class SynthesizerTrn(nn.Module):
             g = self._speaker_embedding(sid.to(self._device()))
         st = self.dec_stream(zd, g, chunk_frames, max_chunk_frames)
         st.y_lengths = y_lengths
-        if marks:
+        if marks_out is not None:
             rows = [[min(v, Td) for v in row] for row in marks_out]
             st.marks = rows[0] if len(rows) == 1 else rows
+        if pitch is not None:
+            st.warp = stream.WarpMap(stream.frame_rates(pitch[0].tolist(), st.marks, Td, pitch_glide_frames), st.spf,
+                                     zd.device)
         if fitted is not None:
             st.fit_scale, st.fit_status = (v[0] if len(v) == 1 else v for v in fitted)
         if gain_out:
@@ -1546,7 +1657,7 @@ class SynthesizerTrn(nn.Module):
             dur, kept = self._pack_host([r.durations for r in reqs], dev)       # (None where none are given)
             keep += kept
             # [the N lengths | the marks of the requests that want them, t_text + 1 each]: one buffer, one read-back
-            marked = [i for i in range(N) if reqs[i].marks]
+            marked = [i for i in range(N) if reqs[i].marks or reqs[i].pitch is not None]
             mark_at, o = {}, N
             for i in marked:
                 mark_at[i] = o
@@ -1657,6 +1768,10 @@ class SynthesizerTrn(nn.Module):
                 sts[i].fit_scale, sts[i].fit_status = _capi.fit_result(y_host[at])
             for i, t in frame_gain.items():
                 sts[i].frame_gain = t
+            for i, r in enumerate(reqs):
+                if r.pitch is not None:            # the warp of a pitched request, planned on the host from its marks
+                    sts[i].warp = stream.WarpMap(stream.frame_rates(r.pitch.tolist(), sts[i].marks, Td[i],
+                                                                    r.pitch_glide_frames), sts[i].spf, dev)
             return sts
 
     # ------------------------------------------------------------------ pooled voice conversion
@@ -2109,6 +2224,69 @@ class SynthesizerTrn(nn.Module):
         if not isinstance(rows, C.Array):
             rows = (_capi.MbvResampleRange * len(rows))(*rows)
         self._call("mbv_resample_ranges", rows, len(rows), int(orig_sr), int(target_sr), filt)
+
+    # ------------------------------------------------------------------ per-token pitch
+    def warp_runs(self):
+        """Launches of the time-warp kernel made on this model's handle so far (`mbv_warp_runs`)."""
+        return int(_capi.lib().mbv_warp_runs(self._ensure_handle()))
+
+    def warp_map(self, pitch, durations, glide_frames=PITCH_GLIDE_FRAMES):
+        """The `stream.WarpMap` of ONE utterance for users of the batch `infer`: `pitch` as `infer_stream(pitch=)` takes
+        it ([T_text] factors on the host), `durations` the frames per token the utterance was made with ([T_text], or
+        [1, 1, T_text] as `infer(...)[4]` returns them: a read-back when they live on the device).  The tables are
+        uploaded to the model's device."""
+        d = [int(round(float(v))) for v in (durations.reshape(-1).tolist() if torch.is_tensor(durations) else durations)]
+        if min(d, default=0) < 0 or sum(d) < 1:
+            raise ValueError("warp_map: durations must be non-negative frames per token with at least one frame")
+        p = _pitch_arg("warp_map", pitch, 1, len(d), row=True)
+        marks = [0]
+        for v in d:
+            marks.append(marks[-1] + v)
+        return stream.WarpMap(stream.frame_rates(p.reshape(-1).tolist(), marks, marks[-1], glide_frames),
+                              self.cfg.samples_per_frame, self._device())
+
+    @torch.no_grad()
+    def warp_ranges(self, rows):
+        """`mbv_warp_ranges`: `rows` is a ctypes array (or a list) of `_capi.MbvWarpRow`, one per stream; ONE launch for
+        all of them, no host synchronisation (beyond the first call for a filter)."""
+        if not isinstance(rows, C.Array):
+            rows = (_capi.MbvWarpRow * len(rows))(*rows)
+        self._call("mbv_warp_ranges", rows, len(rows))
+
+    @staticmethod
+    def warp_row(wave, warp_map, in_avail, out_first, out_count, out, envelope=None, res_type="kaiser_best"):
+        """The `_capi.MbvWarpRow` of one stream: outputs [out_first, out_first + out_count) of the warped row `out`
+        ([.., n_out] fp32) from the first `in_avail` samples of `wave` (the decoded row, [.., F * hop])."""
+        m = warp_map
+        if m.rate_dev is None or m.rate_dev.device != wave.device:
+            raise ValueError("warp: the WarpMap's tables are not on the wave's device (%s)" % (wave.device,))
+        return _capi.MbvWarpRow(wave.data_ptr(), m.samples, int(in_avail), m.U_dev.data_ptr(), m.rate_dev.data_ptr(),
+                                m.U.ctypes.data, m.rate.ctypes.data, m.frames, m.hop, _envelope_c(envelope),
+                                int(out_first), int(out_count), out.data_ptr(), out.shape[-1], _filter_code(res_type), 0)
+
+    @torch.no_grad()
+    def warp(self, wave, warp_map, envelope=None, res_type="kaiser_best"):
+        """The closed one-shot time warp: `wave` (fp32, one utterance: [n], [1, n] or [1, 1, n] with n >= F * hop of the
+        map; the first F * hop samples are read) -> fp32 [1, n_out], played at the map's rates (`mbv_warp_ranges` with
+        one closed row).  `envelope`: the samples are shaped where they are read, bitwise `warp(wave * e, map)`."""
+        if not isinstance(warp_map, stream.WarpMap):
+            raise TypeError("warp: warp_map must be a stream.WarpMap (st.warp, net.warp_map)")
+        if not torch.is_tensor(wave) or wave.dtype != torch.float32:
+            raise TypeError("warp: wave must be an fp32 tensor")
+        if wave.numel() != wave.shape[-1]:
+            raise ValueError("warp: ONE utterance ([n], [1, n] or [1, 1, n]), got %s" % (tuple(wave.shape),))
+        if wave.shape[-1] < warp_map.samples:
+            raise ValueError("warp: the map covers %d frames x %d = %d samples, the wave holds %d"
+                             % (warp_map.frames, warp_map.hop, warp_map.samples, wave.shape[-1]))
+        if envelope is not None:
+            if not isinstance(envelope, Envelope):
+                raise TypeError("warp: envelope must be a wire.Envelope, got %s" % type(envelope).__name__)
+            envelope.check("warp", 1, warp_map.samples, self._device())
+        x = wave.to(self._device()).reshape(-1).contiguous()
+        out = torch.empty(1, max(warp_map.n_out, 1), device=x.device, dtype=torch.float32)[:, :warp_map.n_out]
+        if warp_map.n_out:
+            self.warp_ranges([self.warp_row(x, warp_map, warp_map.samples, 0, warp_map.n_out, out, envelope, res_type)])
+        return out
 
     @torch.no_grad()
     def g711_encode(self, pcm, law):

@@ -20,7 +20,9 @@ frames from spectrogram windows as soon as the samples they depend on exist (`Li
 decodes every chunk whose z-window is final; a `StreamPool` serves live streams next to finished ones.
 """
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -41,6 +43,82 @@ def chunk_schedule(t_frames, chunk_frames=32, max_chunk_frames=256):
         first += n
         c = min(2 * c, cap)
     return out
+
+
+RES_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}   # MBV_RESAMPLE_KAISER_*: the filters of the warp and the wire
+
+
+def frame_rates(pitch, marks, frames, glide_frames=2):
+    """The rate table of a pitched utterance, fp32 [frames] on the host: frame f takes the pitch of the
+    token that holds it (`marks`: the frame at which every token starts, the last entry the end; 1.0 for a frame no
+    token holds), then the glide: the float64 mean over [f - g, f + g] within [0, frames), added in ascending order and
+    rounded to fp32.  glide_frames = 0 keeps the steps."""
+    g = int(glide_frames)
+    if g < 0:
+        raise ValueError("pitch_glide_frames must be >= 0, got %d" % g)
+    step = np.ones(int(frames), np.float32)
+    for j, p in enumerate(pitch):
+        step[min(int(marks[j]), frames):min(int(marks[j + 1]), frames)] = np.float32(p)
+    if g == 0:
+        return step
+    vals = [float(v) for v in step]
+    out = np.empty_like(step)
+    for f in range(len(vals)):
+        lo, hi = max(0, f - g), min(len(vals), f + g + 1)
+        acc = 0.0
+        for k in range(lo, hi):
+            acc += vals[k]
+        out[f] = np.float32(acc / float(hi - lo))
+    return out
+
+
+class WarpMap:
+    """The time warp of one pitched utterance: `rate` fp32 [F], the playback rate of every kept z-frame,
+    `U` float64 [F + 1], the warped position of every frame start (`mbv_warp_plan`: U[f + 1] = U[f] + hop / rate[f]),
+    and `n_out` = floor(U[F]), the warped length.  Both tables live on the host (`rate`, `U`: NumPy) and, once `device`
+    is given, on the device (`rate_dev`, `U_dev`: uploaded once).  The C side is the authority for every number here."""
+
+    __slots__ = ("rate", "U", "n_out", "hop", "frames", "rate_dev", "U_dev")
+
+    def __init__(self, rate, hop, device=None):
+        rate = np.ascontiguousarray(rate, np.float32).reshape(-1)
+        hop = int(hop)
+        U = np.empty(len(rate) + 1, np.float64)
+        n_out = C.c_int64()
+        L = _capi.lib()
+        if L.mbv_warp_plan(hop, len(rate), rate.ctypes.data, U.ctypes.data, C.byref(n_out)):
+            raise ValueError((L.mbv_last_error(None) or b"mbv_warp_plan failed").decode())
+        self.rate, self.U, self.n_out, self.hop, self.frames = rate, U, int(n_out.value), hop, len(rate)
+        self.rate_dev = self.U_dev = None
+        if device is not None:
+            self.rate_dev = torch.from_numpy(rate).to(device)
+            self.U_dev = torch.from_numpy(U).to(device)
+
+    def __repr__(self):
+        return "WarpMap(%d frames of %d samples -> %d samples)" % (self.frames, self.hop, self.n_out)
+
+    @property
+    def samples(self):
+        return self.frames * self.hop
+
+    def ready(self, in_avail, res_type="kaiser_best"):
+        """Warped samples that are final once the model samples [0, in_avail) exist (`mbv_warp_ready`)."""
+        n = _capi.lib().mbv_warp_ready(self.hop, self.frames, self.rate.ctypes.data, self.U.ctypes.data,
+                                       _res_code(res_type), int(in_avail))
+        if n < 0:
+            raise ValueError((_capi.lib().mbv_last_error(None) or b"mbv_warp_ready failed").decode())
+        return int(n)
+
+    def samples_of_frames(self, frames):
+        """ceil(U[f]) of every z-frame index (clipped to the map's frames): the first warped sample at or behind the
+        frame's first model sample, as integers."""
+        return [int(math.ceil(self.U[min(max(int(f), 0), self.frames)])) for f in frames]
+
+
+def _res_code(res_type):
+    if res_type not in RES_TYPES:
+        raise ValueError("res_type must be 'kaiser_best' or 'kaiser_fast', got %r" % (res_type,))
+    return RES_TYPES[res_type]
 
 
 def decoder_context(config_struct):
@@ -443,6 +521,7 @@ class DecodeStream:
         self.marks = None             # token marks in z-frames (`infer_stream(marks=True)`); a converted stream has none
         self.fit_scale = self.fit_status = None     # the factor and status of `fit_frames=`, else None
         self.frame_gain = None        # fp32 [B, F + 1] frame gains of `infer_stream(gain=)`, else None
+        self.warp = None              # the `WarpMap` of `infer_stream(pitch=)`, else None
         self._next = 0                # the chunk next() hands out
         self._decoded = 0             # the first chunk not decoded yet (>= _next; ahead of it only through a pool)
 

@@ -62,6 +62,14 @@ Volume: a stream made with `gain=` carries `frame_gain`, the per
 model-rate samples where they read them, in front of the filter, the peak, the limiter and the clip.  `stream_pcm16`,
 `PcmPool.add` / `admit` and `Turn.append` / `admit` pick it up by themselves; `envelope=` names one explicitly.  The
 bytes are those of `service_pcm16` on the waveform times that envelope; rows without one are bitwise what they were.
+
+Pitch: a stream made with `pitch=` carries `warp`, a `stream.WarpMap`: the playback rate of every z-frame.
+`stream_pcm16`, `PcmPool.add` / `admit` and `Turn.append` / `admit` then read the WARPED row, which they own and fill
+behind the decoder with the time-warp kernel (`mbv_warp_ranges`: one launch per step of a stream, ONE per tick of a
+pool for all its pitched members and segments), and everything behind it is the wire step that exists.  The bytes are
+those of `service_pcm16(net.warp(st.o, st.warp))`; a stream without `pitch=` launches nothing and is bitwise what it was.
+A gain envelope of such a stream goes to the warp, where the samples are read.  `.loudness` stays that of the decoded,
+unwarped waveform.  Varispeed: formants move with the pitch.
 """
 import base64
 import ctypes as C
@@ -74,6 +82,8 @@ from . import _capi
 # (RESAMPLE_TYPES and ENCODINGS stay names of this module)
 from .models import ENCODINGS, RESAMPLE_TYPES, _filter_code, _g711_law, _law_code      # noqa: F401
 from .models import Envelope, GAIN_MAX, gain_of_db                                      # noqa: F401
+from .models import PITCH_MAX, PITCH_MIN, pitch_of_semitones                            # noqa: F401
+from .stream import WarpMap                                                             # noqa: F401
 
 G711_ZERO = {"ulaw": 0xFF, "alaw": 0xD5}      # the code of the int16 zero: what the wire kernels store as padding
 # `wave_dtype` of a live wire's raw buffer (MBV_WAVE_*), by its dtype or, for uint8, its `in_encoding`
@@ -353,14 +363,62 @@ def _refuse_envelope(envelope, who):
                          "volume from); shape the finished waveform with service_pcm16(envelope=)" % who)
 
 
-def mark_samples(marks, samples_per_frame, model_sr, rate, lookahead=0):
+def _refuse_pitch(pitch, who):
+    """The live wires carry no per-token pitch: a converted recording has no tokens."""
+    if pitch is not None:
+        raise ValueError("%s: pitch= is not offered on a live wire or a converted recording (no tokens to take a "
+                         "pitch from); warp the finished waveform with net.warp(wave, net.warp_map(...))" % who)
+
+
+def mark_samples(marks, samples_per_frame, model_sr, rate, lookahead=0, warp=None):
     """Token marks in z-frames (`infer_stream(marks=True)`) -> wire sample indices, in pure integers: a mark at frame f
     maps to ceil(f * samples_per_frame * rate / model_sr) + lookahead, the first wire sample at or after the token's
-    first model sample, moved by the limiter's lag (a limited stream is the unlimited one `lookahead` samples later)."""
+    first model sample, moved by the limiter's lag (a limited stream is the unlimited one `lookahead` samples later).
+    `warp` (a `stream.WarpMap`): a pitched stream; the frames go through `warp.samples_of_frames` first,
+    and the same integer mapping is applied to those model-rate samples of the warped row."""
     spf, model_sr, rate, lookahead = int(samples_per_frame), int(model_sr), int(rate), int(lookahead)
     if spf < 1 or model_sr < 1 or rate < 1 or lookahead < 0:
         raise ValueError("mark_samples: samples_per_frame and the rates must be positive, lookahead >= 0")
-    return [-((-int(f) * spf * rate) // model_sr) + lookahead for f in marks]
+    at = [int(f) * spf for f in marks] if warp is None else warp.samples_of_frames(marks)
+    return [-((-s * rate) // model_sr) + lookahead for s in at]
+
+
+class _Warped:
+    """The warped row of one pitched `DecodeStream`, owned by the wire stream or turn that reads it:
+    `row` fp32 [1, n_out], filled range by range behind the decoder by `mbv_warp_ranges`.  A gain envelope is handed to
+    the warp, where the samples are read, and not to the wire step behind it."""
+
+    def __init__(self, net, st, env, res_type):
+        self.net, self.st, self.map, self.env, self.res_type = net, st, st.warp, env, res_type
+        if st.z.shape[0] != 1:
+            raise ValueError("a pitched stream holds ONE utterance (this one has %d rows)" % st.z.shape[0])
+        if self.map.samples != st.o.shape[-1] or self.map.rate_dev is None or self.map.rate_dev.device != st.o.device:
+            raise ValueError("the stream's warp does not cover its waveform (%d frames x %d against %d samples)"
+                             % (self.map.frames, self.map.hop, st.o.shape[-1]))
+        self.n = self.map.n_out
+        with torch.cuda.device(st.o.device):
+            self.row = torch.empty(1, max(self.n, 1), device=st.o.device, dtype=torch.float32)[:, :self.n]
+        self.done = 0                             # warped samples written so far
+
+    def frontier(self, model_avail):
+        """warped samples that are final once `model_avail` decoded samples exist"""
+        return self.map.ready(model_avail, self.res_type)
+
+    def due(self, model_avail):
+        """-> (the `_capi.MbvWarpRow` of the range that `model_avail` decoded samples make final, its end), or None"""
+        end = self.frontier(model_avail)
+        if end <= self.done:
+            return None
+        return self.net.warp_row(self.st.o, self.map, model_avail, self.done, end - self.done, self.row, self.env,
+                                 self.res_type), end
+
+
+def _warp_launch(net, due):
+    """ONE `mbv_warp_ranges` launch for [(a `_Warped`, (row, end))]; nothing for an empty list."""
+    if due:
+        net.warp_ranges([row for _, (row, _) in due])
+        for w, (_, end) in due:
+            w.done = end
 
 
 def revoke_plan(ready, total, emitted, first, count):
@@ -500,7 +558,7 @@ def service_pcm16(net, o, y_lengths, model_sr, rate, auto_normalize=True, res_ty
 
 def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size,
                   auto_normalize=True, res_type="kaiser_best", seed=None, limiter=None, encoding="pcm16",
-                  in_encoding=None, fade=None, loudness=None, envelope=None):
+                  in_encoding=None, fade=None, loudness=None, envelope=None, pitch=None):
     """Voice conversion from audio to audio as one GPU chain:
       1. `wave` int16 or fp32 [B, n] / [B, 1, n] at `in_sr` (int16 is scaled by 1 / 32768, data_utils.py:75),
          `valid_samples` int64 [B] samples per utterance or None = whole rows;
@@ -517,6 +575,7 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
     the status check `voice_conversion` already has (besides the first-call table uploads of `resample` and
     `spectrogram`)."""
     _refuse_envelope(envelope, "convert_pcm16")
+    _refuse_pitch(pitch, "convert_pcm16")
     _limit_arg(limiter, rate)                                   # refuses bad parameters before anything is launched
     _law_code(encoding)
     _fade_arg(fade)
@@ -654,6 +713,9 @@ class PcmStream:
     A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
     such a piece out without launching anything, and launches alone otherwise — the same bytes either way.
 
+    A pitched stream (`st.warp`) is read through `_src_row`, `_src_len` and `_src_frontier`: the warped row
+    this stream owns, its length and its frontier, in place of `st.o`; `loudness` stays measured on the decoded row.
+
     `marks` (a stream made with `marks=True`; else None) lists the wire sample at which every token starts
     (`mark_samples`, the limiter's lag included).  `revoke()` takes the stream back with a fade-out; `finished` and
     `revoked` say where it stands."""
@@ -666,26 +728,31 @@ class PcmStream:
         self._env = _envelope_arg(envelope, st, "stream_pcm16")
         if self._env is not None:
             self._env.check("stream_pcm16", st.o.shape[0], st.o.shape[-1], st.o.device)
+        # per-token pitch: the wire reads the warped row this stream owns; the envelope goes to the warp
+        self._warp = None
+        if getattr(st, "warp", None) is not None:
+            self._warp = _Warped(net, st, self._env, res_type)
+            self._env = None
         self.encoding, dtype = encoding, _wire_dtype(encoding)
         self._net, self._st, self._h = net, st, st._h
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
         self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
         lag = self._lim[1] if self._lim else 0
         o = st.o
-        B, n = o.shape[0], o.shape[-1]
+        B, n = o.shape[0], self._src_len()
         dev = o.device
         # final outputs after each decoded chunk (pure integers of the schedule: nothing to ask the device)
-        self._ready = [limiter_ready(model_sr, rate, st.spf * (first + count), n, lag, res_type)
-                       for first, count in st.schedule]
+        self._front = [self._src_frontier(i) for i in range(len(st.schedule))]
+        self._ready = [limiter_ready(model_sr, rate, a, n, lag, res_type) for a in self._front]
         self.out_stride = resample_ready(model_sr, rate, n, n, res_type)
         self.pcm = torch.empty(B, self.out_stride, device=dev, dtype=dtype)
         self.valid_samples = torch.zeros(B, device=dev, dtype=torch.int64)
         self.peak = torch.zeros(B, device=dev, dtype=torch.float32)
         self._valid_in = None                     # valid input samples, as service_pcm16 counts them
-        if st.y_lengths is not None:
+        if st.y_lengths is not None and self._warp is None:      # (a warped row is valid over its whole length)
             self._valid_in = (st.y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
         self._peak_in = _peak_arg(peak, B, dev)
-        _loudness_open(self, loud, B, n, dev)     # .loudness: the running integrated loudness, or None
+        _loudness_open(self, loud, B, o.shape[-1], dev)     # .loudness: the running integrated loudness, or None
         if loud is not None and loud.target is not None:
             with torch.cuda.device(dev):
                 self._peak_in = loud.peak(loud.measured_rows(B, dev)).contiguous()
@@ -698,8 +765,35 @@ class PcmStream:
         self.marks = None
         marks = getattr(st, "marks", None)
         if marks is not None:
-            each = [mark_samples(m, st.spf, model_sr, rate, lag) for m in (marks if B > 1 else [marks])]
+            each = [mark_samples(m, st.spf, model_sr, rate, lag, warp=getattr(st, "warp", None))
+                    for m in (marks if B > 1 else [marks])]
             self.marks = each if B > 1 else each[0]
+
+    # ---- the input of the wire step: the decoded row, or the warped row of a pitched stream
+    def _src_row(self):
+        return self._st.o[:, 0] if self._warp is None else self._warp.row
+
+    def _src_len(self):
+        return self._st.o.shape[-1] if self._warp is None else self._warp.n
+
+    def _src_frontier(self, i):
+        """input samples of the wire step that exist once chunk i is decoded"""
+        first, count = self._st.schedule[i]
+        a = self._st.spf * (first + count)
+        return a if self._warp is None else self._warp.frontier(a)
+
+    def _warp_due(self, i):
+        """the warp range that chunk i made final: (the `_Warped`, (row, end)), or None"""
+        if self._warp is None:
+            return None
+        first, count = self._st.schedule[i]
+        due = self._warp.due(self._st.spf * (first + count))
+        return None if due is None else (self._warp, due)
+
+    def _measured(self, i):
+        """what the loudness of step i is measured on: the DECODED row and frontier, warped or not"""
+        first, count = self._st.schedule[i]
+        return self._st.o[:, 0], self._st.spf * (first + count)
 
     def __len__(self):
         return len(self._st)
@@ -716,8 +810,8 @@ class PcmStream:
     def _total(self):
         """The stream's length in wire samples, on the host: what `valid_samples` holds for a single utterance, whose
         `y_lengths` covers at least the frames the stream keeps."""
-        n = self._st.o.shape[-1]
-        v = n if self._st.y_lengths is None else min(256 * self._st.z.shape[2], n)
+        n = self._src_len()
+        v = n if self._st.y_lengths is None or self._warp is not None else min(256 * self._st.z.shape[2], n)
         return resample_ready(self.model_sr, self.rate, v, v, self.res_type)
 
     def _clamp_valid(self):
@@ -790,16 +884,17 @@ class PcmStream:
             return a, self.pcm[:, a:b]
         a, b = self._done, self._ready[i]
         step = self._step_through(i)
+        due = self._warp_due(i)
+        _warp_launch(net, [due] if due else [])    # the newly ready warped range, in front of the wire step
         _wire_alone(self, *step)
-        _loudness_alone(self, step[0], step[1])
+        _loudness_alone(self, *self._measured(i))
         self._done, self._wired = b, i + 1
         self._clamp_valid()
         return a, self.pcm[:, a:b]
 
     def _step_through(self, i):
         """The wire step that takes in the decoded chunks up to chunk i."""
-        first, count = self._st.schedule[i]
-        return self._st.o[:, 0], self._st.spf * (first + count), self._done, self._ready[i] - self._done, self._wired == 0
+        return self._src_row(), self._front[i], self._done, self._ready[i] - self._done, self._wired == 0
 
     # ---- what a pool shares (PcmPool.step), as `LiveWire` has it
     def _wire_chunk(self, k):
@@ -815,6 +910,12 @@ class PcmStream:
     def _chunk_wired(self, final, pieces):
         self._done, self._wired = pieces[-1][1], self._st._decoded
         self._clamp_valid()
+
+    def _warp_dues(self):
+        """The warp ranges the pool's tick owes this member (at most one), in front of its wire row."""
+        i = self._st._decoded - 1
+        due = self._warp_due(i) if i >= self._wired else None
+        return [due] if due else []
 
     def run(self):
         """Every remaining chunk; -> (pcm, valid_samples)."""
@@ -847,7 +948,12 @@ def stream_pcm16(net, st, model_sr, rate, peak=None, res_type="kaiser_best", lim
             `Envelope(st.frame_gain, st.spf)` by itself.  The samples are scaled where the wire kernel reads them, in
             front of the filter, the peak, the limiter and the clip: the bytes are those of
             `service_pcm16(st.o, envelope=...)`, and of `service_pcm16(st.o * e)`.  The running `.loudness` stays that
-            of the unshaped waveform."""
+            of the unshaped waveform.
+    A stream made with `pitch=` (`st.warp`; one utterance) is wired from its WARPED row, which the wire
+    stream owns and fills behind the decoder, one `mbv_warp_ranges` launch in front of each wire step: `pcm`,
+    `valid_samples`, `marks` and `revoke` count warped samples, and the bytes are those of
+    `service_pcm16(net.warp(st.o, st.warp), ...)`.  Its envelope, if any, is read by the warp.  The running `.loudness`
+    stays that of the decoded, unwarped waveform."""
     if st._next:
         raise ValueError("stream_pcm16: the decode stream has already been advanced")
     return PcmStream(net, st, model_sr, rate, peak=peak, res_type=res_type, limiter=limiter, encoding=encoding,
@@ -1035,9 +1141,10 @@ class LiveWire:
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                  chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                 encoding="pcm16", in_encoding=None, loudness=None, envelope=None):
+                 encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None):
         from .stream import LiveStream
         _refuse_envelope(envelope, "convert_live_pcm16")
+        _refuse_pitch(pitch, "convert_live_pcm16")
         self._env = None                          # (what the pooled wire step reads on every member)
         _filter_code(res_type)
         loud = _loudness_arg(loudness, peak, "convert_live_pcm16", stream=True)
@@ -1200,7 +1307,7 @@ class LiveWire:
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                        chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                       encoding="pcm16", in_encoding=None, loudness=None, envelope=None):
+                       encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32; G.711 bytes with `dtype=torch.uint8,
     in_encoding="ulaw" | "alaw"`, which needs `in_sr != model_sr`) while the recording arrives, int16 out at `rate`
     (G.711 bytes with `encoding="ulaw" | "alaw"`); -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
@@ -1210,8 +1317,9 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
     `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
     (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead.  `loudness` as
     `stream_pcm16` takes it: `measured` is required with a target, and the wire keeps `.loudness`.  `envelope` is refused
-    (ValueError): a converted recording has no tokens to take a volume from."""
+    (ValueError): a converted recording has no tokens to take a volume from; `pitch` likewise (§7.22)."""
     _refuse_envelope(envelope, "convert_live_pcm16")
+    _refuse_pitch(pitch, "convert_live_pcm16")
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
                     max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter,
@@ -1463,7 +1571,10 @@ def _frames_decoded(st):
 
 
 def _segment_length(st):
-    """Valid model-rate samples of a single-utterance stream, on the host: what `PcmStream` takes as its valid input."""
+    """Valid model-rate samples of a single-utterance stream, on the host: what `PcmStream` takes as its valid input
+    (the warped length of a pitched stream)."""
+    if getattr(st, "warp", None) is not None:
+        return st.warp.n_out
     n = st.o.shape[-1]
     return n if st.y_lengths is None else min(256 * st.z.shape[2], n)
 
@@ -1515,6 +1626,7 @@ class Turn:
                 self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
         self.segments = []            # the `DecodeStream`s, in timeline order
         self.envelopes = []           # per segment: its `Envelope` (per-token volume) or None
+        self.warped = []              # per segment: the `_Warped` row of a pitched stream or None
         self.marks = []
         self._fade = None
         self._revoked = None
@@ -1566,17 +1678,23 @@ class Turn:
         n = _segment_length(st)
         env = _envelope_arg(envelope, st, "Turn.append")
         if env is not None:
-            env.check("Turn.append", 1, n, st.o.device)
+            env.check("Turn.append", 1, st.o.shape[-1] if getattr(st, "warp", None) is not None else n, st.o.device)
         self._plan.check_append(n, self._pause(pause_ms))
         if not st._drained():
             self._pool.pool.add(st)                   # (refuses another device; a member stays one)
+        # a pitched segment is its warped row, which the turn owns, with the warped length and frontier; its envelope
+        # is handed to the warp, where the samples are read
+        wp = _Warped(self._net, st, env, self.res_type) if getattr(st, "warp", None) is not None else None
         s = self._plan.append(n, self._pause(pause_ms))
         self.segments.append(st)
-        self.envelopes.append(env)
+        self.envelopes.append(env if wp is None else None)
+        self.warped.append(wp)
         lag = self._lim[1] if self._lim else 0
         marks = getattr(st, "marks", None)
+        at = None if marks is None else ([st.spf * int(f) for f in marks] if wp is None
+                                         else wp.map.samples_of_frames(marks))
         self.marks.append(None if marks is None else mark_samples(
-            [self._plan.starts[s] + st.spf * int(f) for f in marks], 1, self.model_sr, self.rate, lag))
+            [self._plan.starts[s] + a for a in at], 1, self.model_sr, self.rate, lag))
         return s
 
     def admit(self, requests, pauses_ms=None):
@@ -1619,7 +1737,7 @@ class Turn:
         """Fills the `_capi.MbvTurnChunk` `k` with the wire step due now; -> [(a, b)], or None."""
         plan = self._plan
         for s, st in enumerate(self.segments):
-            plan.decoded(s, st.spf * _frames_decoded(st))
+            plan.decoded(s, self._seg_frontier(s, st.spf * _frames_decoded(st)))
         due = plan.wire_due()
         if due is None:
             return None
@@ -1635,7 +1753,8 @@ class Turn:
         s0, s1 = plan.segments_for(a, count)
         segs = (_capi.MbvTurnSeg * max(s1 - s0, 1))()
         for sg, s in zip(segs, range(s0, s1)):
-            sg.wave, sg.start, sg.length = self.segments[s].o.data_ptr(), plan.starts[s], plan.lengths[s]
+            wave = self.segments[s].o if self.warped[s] is None else self.warped[s].row
+            sg.wave, sg.start, sg.length = wave.data_ptr(), plan.starts[s], plan.lengths[s]
             sg.ramp = turn_ramp(self.ramp, plan.lengths[s])
         k.segs, k.n_segs = segs, s1 - s0
         self._seg_envs = self.envelopes[s0:s1]    # beside `segs`, for the pool's call
@@ -1644,6 +1763,19 @@ class Turn:
     def _chunk_wired(self, pieces):
         self._plan.wired(pieces[-1][1])
         self._settle()
+
+    def _seg_frontier(self, s, model_avail):
+        """samples of segment s that exist once `model_avail` of its decoded samples do"""
+        return model_avail if self.warped[s] is None else self.warped[s].frontier(model_avail)
+
+    def _warp_dues(self):
+        """The warp ranges the pool's tick owes the turn's pitched segments, in front of its wire row."""
+        dues = []
+        for st, wp in zip(self.segments, self.warped):
+            due = wp.due(st.spf * _frames_decoded(st)) if wp is not None else None
+            if due:
+                dues.append((wp, due))
+        return dues
 
     def _settle(self):
         """Once the last piece is out: `valid_samples` (a device fill of a host integer), and the turn leaves the pool."""
@@ -1688,8 +1820,8 @@ class Turn:
             F = int(at)
         else:
             raise ValueError("revoke: at must be 'now' or a wire sample index, got %r" % (at,))
-        events = plan.revoke_events([[st.spf * (first + count) for first, count in st.schedule]
-                                     for st in self.segments]) or [(0, 0, 0)]
+        events = plan.revoke_events([[self._seg_frontier(s, st.spf * (first + count)) for first, count in st.schedule]
+                                     for s, st in enumerate(self.segments)]) or [(0, 0, 0)]
         cut, last, _ = revoke_plan([r for _, _, r in events], total, E, F, N)   # (refuses F < E before anything changes)
         s_cut, i_cut, _ = events[last]
         for s, st in enumerate(self.segments):
@@ -1703,6 +1835,7 @@ class Turn:
         if not whole:
             self.segments = self.segments[:keep]              # (`marks` keeps every segment's: the report counts over all)
             self.envelopes = self.envelopes[:keep]
+            self.warped = self.warped[:keep]
         if F < total:
             self._fade = (F, N)
         self._revoked = Revoked(F, N, cut, self._started(F))
@@ -1808,12 +1941,13 @@ class PcmPool:
                 self.pool.remove(f._st)
         return report
 
-    def add_live(self, lw, limiter=None, loudness=None, envelope=None):
+    def add_live(self, lw, limiter=None, loudness=None, envelope=None, pitch=None):
         """Adds a `LiveWire` (`convert_live_pcm16`): its `LiveStream` joins the wrapped `StreamPool`, and `step()` then
         feeds, steps and wires it along with the others; -> `lw`.  The wire keeps the limiter it was opened with;
         `limiter`, when given, must be that one (the lag is part of the pieces it has planned); `loudness` likewise
         (its state is the wire's)."""
         _refuse_envelope(envelope, "add_live")
+        _refuse_pitch(pitch, "add_live")
         if not isinstance(lw, LiveWire):
             raise TypeError("add_live takes a wire.LiveWire (wire.convert_live_pcm16)")
         if limiter is not None and limiter != lw.limiter:
@@ -1896,6 +2030,8 @@ class PcmPool:
                      + [sg for t in turns for sg in t.segments] if not st._drained()]
         if named is None or named:
             self.pool.step(named)
+        # the pitched followers and turn segments of the tick: ONE mbv_warp_ranges launch in front of the wire launches
+        _warp_launch(net, [d for w in members + turns for d in w._warp_dues()])
         rows = []                                 # (stream, member, its table row, (final, [(a, b), ...])) per row
         for w, st in [(f, f._st) for f in members] + [(lw, lw) for lw in lives]:
             k = _capi.MbvPcmChunk()
@@ -1941,7 +2077,11 @@ class PcmPool:
             measuring = []
             for _, w, k, _ in rows:
                 lk = _capi.MbvLoudnessChunk()
-                k1 = _loudness_row(w, lk, k.wave, k.in_total, k.in_avail) if w.loudness is not None else None
+                src = (k.wave, k.in_total, k.in_avail)
+                if getattr(w, "_warp", None) is not None:     # a pitched member is measured on its decoded row
+                    o, avail = w._measured(w._st._decoded - 1)
+                    src = (o.data_ptr(), o.shape[-1], avail)
+                k1 = _loudness_row(w, lk, *src) if w.loudness is not None else None
                 if k1 is not None:
                     measuring.append((w, lk, k1))
             if measuring:

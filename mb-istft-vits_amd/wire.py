@@ -72,6 +72,7 @@ A gain envelope of such a stream goes to the warp, where the samples are read.  
 unwarped waveform.  Varispeed: formants move with the pitch.
 """
 import base64
+import collections
 import ctypes as C
 import math
 
@@ -296,45 +297,6 @@ def loudness_plan(avail, hop):
     return out
 
 
-# The measuring half of a wire step of `w`, a `PcmStream` or a `LiveWire` opened with `loudness=` (both then hold
-# loudness, fp32 [B], the running integrated loudness; _lstate, fp64 [B, 4]; _lenergy, fp64 [B, capacity // H]; _lseg,
-# the segments measured so far; _valid_in): the segments that the first `in_avail` samples completed.  Alone it is one
-# `mbv_loudness_range` launch, in a pool one row of the tick's `mbv_loudness_chunks` table.
-def _loudness_open(w, loud, B, capacity, dev):
-    w._loud, w.loudness = loud, None
-    if loud is None:
-        return
-    w._lhop, segs = _capi.loudness_segments(w.model_sr, capacity)
-    with torch.cuda.device(dev):
-        w.loudness = torch.full((B,), -math.inf, device=dev, dtype=torch.float32)
-        w._lstate = torch.zeros(B, 4, device=dev, dtype=torch.float64)
-        w._lenergy = torch.zeros(B, max(segs, 1), device=dev, dtype=torch.float64)
-    w._lseg = 0
-
-
-def _loudness_alone(w, wave, in_avail):
-    if w.loudness is None:
-        return
-    k1 = _segments_due(w._lseg, in_avail, w._lhop)
-    if k1 > w._lseg:
-        w._net.loudness_range(wave, w.model_sr, in_avail, w._lseg, k1 - w._lseg, w._lstate, w._lenergy, w.loudness,
-                              valid_samples=w._valid_in)
-        w._lseg = k1
-
-
-def _loudness_row(w, k, wave_ptr, in_total, in_avail):
-    """Fills the `_capi.MbvLoudnessChunk` `k` with the segments due now; -> the new segment count, or None."""
-    k1 = _segments_due(w._lseg, in_avail, w._lhop)
-    if k1 <= w._lseg:
-        return None
-    k.wave, k.in_total, k.in_avail = wave_ptr, in_total, in_avail
-    k.valid_samples = w._valid_in.data_ptr() if w._valid_in is not None else None
-    k.seg_first, k.seg_count = w._lseg, k1 - w._lseg
-    k.state, k.energies, k.energy_capacity = w._lstate.data_ptr(), w._lenergy.data_ptr(), w._lenergy.shape[1]
-    k.loudness = w.loudness.data_ptr()
-    return k1
-
-
 def _fade_arg(fade):
     """`fade=` of a one-shot wire entry -> None or (first, count), both >= 0."""
     if fade is None:
@@ -349,8 +311,7 @@ def _envelope_arg(envelope, st, who):
     """`envelope=` of a wire stream over the decode stream `st` -> None or an `Envelope`: the one given, else the one of
     `st.frame_gain` (a stream made with `gain=`), else none."""
     if envelope is None:
-        g = getattr(st, "frame_gain", None)
-        return None if g is None else Envelope(g, st.spf)
+        return None if st.frame_gain is None else Envelope(st.frame_gain, st.spf)
     if not isinstance(envelope, Envelope):
         raise TypeError("%s: envelope must be a wire.Envelope, got %s" % (who, type(envelope).__name__))
     return envelope
@@ -454,6 +415,30 @@ class Revoked:
     def __repr__(self):
         return "Revoked(first=%d, count=%d, valid_samples=%d, tokens_started=%r)" % (
             self.first, self.count, self.valid_samples, self.tokens_started)
+
+
+def _revoke_args(fade_ms, at, rate, emitted, total, marks=None, tokens=True, finished=False):
+    """`fade_ms` and `at` of a revoke in pure integers -> (F, N): the fade starts at wire sample F, `at="now"`: `emitted`, an
+    int: that sample, `at="token"`: the first of `marks` >= `emitted` (`total` when none is; None: a stream without marks;
+    `tokens=False`: a turn, which offers no 'token'), and lasts N = round(fade_ms * rate / 1000) samples.  `finished`:
+    nothing is left to fade, only `fade_ms` is checked, and the answer is None."""
+    if not float(fade_ms) >= 0.0:
+        raise ValueError("revoke: fade_ms must be >= 0")
+    if finished:
+        return None
+    N = int(round(float(fade_ms) * 1e-3 * rate))
+    if at == "now":
+        F = emitted
+    elif at == "token" and tokens:
+        if marks is None:
+            raise ValueError("revoke(at='token'): the stream has no token marks (infer_stream(marks=True); a "
+                             "converted recording has no tokens)")
+        F = next((m for m in marks if m >= emitted), total)
+    elif isinstance(at, (int, np.integer)) and not isinstance(at, bool):
+        F = int(at)
+    else:
+        raise ValueError("revoke: at must be 'now'%s or a wire sample index, got %r" % (", 'token'" if tokens else "", at))
+    return F, N
 
 
 def _service_limited(net, o, y_lengths, model_sr, rate, auto_normalize, res_type, limiter, peak, encoding="pcm16",
@@ -603,29 +588,29 @@ def convert_pcm16(net, wave, valid_samples, sid_src, sid_tgt, in_sr, model_sr, r
                          limiter=limiter, encoding=encoding, fade=fade, loudness=loudness)
 
 
+def _ready_call(name, *args):
+    """A host-only entry of the library that answers with a count, or with a negative value and its reason in
+    `mbv_last_error`: -> the count, or `_capi.MbvError`."""
+    L = _capi.lib()
+    r = getattr(L, name)(*args)
+    if r < 0:
+        msg = L.mbv_last_error(None)
+        raise _capi.MbvError(msg.decode() if msg else name + " failed")
+    return int(r)
+
+
 def resample_ready(orig_sr, target_sr, in_avail, in_total, res_type="kaiser_best"):
     """How many resampled samples of a row of `in_total` input samples are final once its first `in_avail`
     exist (`mbv_resample_ready`, host only: no GPU needed); ceil(in_total * target / orig) once all do."""
-    filt = _filter_code(res_type)
-    L = _capi.lib()
-    r = L.mbv_resample_ready(int(orig_sr), int(target_sr), filt, int(in_avail), int(in_total))
-    if r < 0:
-        msg = L.mbv_last_error(None)
-        raise _capi.MbvError(msg.decode() if msg else "mbv_resample_ready failed")
-    return int(r)
+    return _ready_call("mbv_resample_ready", int(orig_sr), int(target_sr), _filter_code(res_type), int(in_avail),
+                       int(in_total))
 
 
 def resample_ready_open(orig_sr, target_sr, in_avail, res_type="kaiser_best"):
     """How many resampled samples of a row that is still OPEN are final once its first `in_avail` samples exist
     (`mbv_resample_ready_open`, host only: no GPU needed): those no tap of which lies at or past `in_avail`.  The
     count does not depend on the length the row will have."""
-    filt = _filter_code(res_type)
-    L = _capi.lib()
-    r = L.mbv_resample_ready_open(int(orig_sr), int(target_sr), filt, int(in_avail))
-    if r < 0:
-        msg = L.mbv_last_error(None)
-        raise _capi.MbvError(msg.decode() if msg else "mbv_resample_ready_open failed")
-    return int(r)
+    return _ready_call("mbv_resample_ready_open", int(orig_sr), int(target_sr), _filter_code(res_type), int(in_avail))
 
 
 def limiter_ready(orig_sr, target_sr, in_avail, in_total, lookahead, res_type="kaiser_best"):
@@ -664,30 +649,150 @@ def _peak_arg(peak, B, dev, shape="B"):
     return peak
 
 
-# The ranged wire step of `w`, a `PcmStream` or a `LiveWire` (both hold pcm, valid_samples, peak, _valid_in, _peak_in,
-# encoding, _lim, the resolved limiter or None, and _fade, the (first, count) of a revoke or None): from the first
-# `in_avail` samples of `wave` [B, n] to the int16 samples [out_first, out_first + out_count); `lengths`: this step also
-# writes `valid_samples`.  Alone it is one `mbv_resample_pcm16_range` launch (`..._range_limited` with a limiter,
-# `..._range_faded` once revoked), in a pool one row of the `mbv_resample_pcm16_chunks` table (`PcmPool.step` passes
-# the rows' `_lim` and `_fade` along).
-def _wire_alone(w, wave, in_avail, out_first, out_count, lengths):
-    w._net.resample_pcm16_range(wave, w.model_sr, w.rate, in_avail, out_first, out_count, w.pcm,
-                                valid_samples=w._valid_in, peak=w._peak_in, running_peak=w.peak,
-                                out_samples=w.valid_samples if lengths else None, res_type=w.res_type, limiter=w._lim,
-                                encoding=w.encoding, fade=w._fade, envelope=getattr(w, "_env", None))
+def _per_request(who, noun, value, n):
+    """`value`, one for all `n` requests or a list / tuple of one per request -> the list of n."""
+    each = list(value) if isinstance(value, (list, tuple)) else [value] * n
+    if len(each) != n:
+        raise ValueError("%s: one %s per request expected (%d), got %d" % (who, noun, n, len(each)))
+    return each
 
 
-def _wire_row(w, k, wave, in_avail, out_first, out_count, lengths):
-    k.wave, k.in_total = wave.data_ptr(), wave.shape[1]
-    k.valid_samples = w._valid_in.data_ptr() if w._valid_in is not None else None
-    k.in_avail, k.out_first, k.out_count = in_avail, out_first, out_count
-    k.peak = w._peak_in.data_ptr() if w._peak_in is not None else None
-    k.pcm, k.pcm_capacity = w.pcm.data_ptr(), w.pcm.shape[1]
-    k.running_peak = w.peak.data_ptr()
-    k.out_samples = w.valid_samples.data_ptr() if lengths else None
+def _decoded_samples(st, i=None):
+    """Model-rate samples of a `DecodeStream` that exist once its chunk i is decoded (None: as far as it is decoded)."""
+    if i is None:
+        i = st._decoded - 1
+    return st.spf * sum(st.schedule[i]) if i >= 0 else 0
 
 
-class PcmStream:
+_KINDS = ("stream", "live wire", "turn")     # the kinds of wire stream, in the order `PcmPool.step` reports them
+# What `_wire_chunk` answers with: k, the filled `_capi.MbvPcmChunk` (`MbvTurnChunk` of a turn); pieces, the [(a, b)] it makes
+# final; final, whether it is the member's last step (None: a turn learns that from its plan); lim and fade, the member's
+# `_lim` and `_fade`; env, the row's `Envelope` or None (a turn: one per segment of the row).
+_Due = collections.namedtuple("_Due", "k pieces final lim fade env")
+
+
+class _WireOut:
+    """The output state of a wire stream and its membership of a `PcmPool`; `PcmStream`, `LiveWire` and `Turn` derive from
+    it, and the state is opened here and nowhere else: pcm, valid_samples, peak (what the kernels write), _peak_in (from
+    `peak=` or a `Loudness` with a target), _valid_in, limiter and _lim, _fade, _env, _warp, and with a measuring
+    `Loudness` loudness, _lstate fp64 [B, 4], _lenergy fp64 [B, capacity // H] and _lseg, the segments measured so far.
+
+    A wire step turns the first `in_avail` samples of `wave` [B, n] into the int16 samples [out_first, out_first +
+    out_count); `lengths`: it also writes `valid_samples`.  Alone it is one `mbv_resample_pcm16_range` launch, in a pool
+    one row of the tick's table; so its measuring half, over the segments those samples completed (`mbv_loudness_range`).
+
+    The member protocol that `PcmPool.step` drives: _KIND, one of `_KINDS`; _TURNS, the row goes to
+    `net.resample_turns` and not to `net.resample_pcm16_chunks`; _name, what `step` reports the pieces under and
+    `streams=` names the member by; _decode_streams(), what `StreamPool.step` steps for it; _warp_dues(); _wire_chunk(),
+    None or the `_Due` of the step due now; _measure_row(k), the `_capi.MbvLoudnessChunk` due beside the wire row k, or
+    None; _chunk_wired(pieces, final), the step is issued; _wired_out, nothing more to wire: the member leaves the pool.
+
+    `_check_handle` (needs `_h`) and `_revoke_begin` / `_revoke_end` (need `finished`, `_started`) serve a `PcmStream` and a
+    `Turn` only: a `LiveWire` checks its `LiveStream`'s handle and is not revoked."""
+
+    _KIND, _TURNS = None, False
+    _name = property(lambda self: self)           # (a follower goes by its decode stream)
+    _valid_in = _env = _warp = None               # what a wire step also reads; the class that has one sets it
+
+    def __init__(self, net, dev, B, width, *, model_sr, rate, res_type, encoding, peak, limiter, loud, capacity, silent):
+        """`loud`: the resolved `Loudness` or None, and `capacity`, the model-rate samples its measurement covers (0 or
+        None: it gives a gain at most).  `silent`: the ONE row of a live wire or a turn, a capacity that starts as silence
+        (and whose `peak=` refusal says "[1]"); else the B rows of a finished schedule, left unwritten."""
+        self._net, self.model_sr, self.rate, self.res_type = net, int(model_sr), int(rate), res_type
+        self.encoding, dtype = encoding, _wire_dtype(encoding)
+        self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
+        self._loud, self.loudness = loud, None
+        with torch.cuda.device(dev):
+            if not silent:
+                self.pcm = torch.empty(B, width, device=dev, dtype=dtype)
+            elif _law_code(encoding):             # silence in G.711 is not the zero byte
+                self.pcm = torch.full((B, width), G711_ZERO[encoding], device=dev, dtype=dtype)
+            else:
+                self.pcm = torch.zeros(B, width, device=dev, dtype=dtype)
+            self.valid_samples = torch.zeros(B, device=dev, dtype=torch.int64)
+            self.peak = torch.zeros(B, device=dev, dtype=torch.float32)
+            self._peak_in = _peak_arg(peak, B, dev, shape="1" if silent else "B")
+            if loud is not None and loud.target is not None:
+                self._peak_in = loud.peak(loud.measured_rows(B, dev)).contiguous()
+            if loud is not None and capacity:
+                self._lhop, segs = _capi.loudness_segments(self.model_sr, capacity)
+                self.loudness = torch.full((B,), -math.inf, device=dev, dtype=torch.float32)
+                self._lstate = torch.zeros(B, 4, device=dev, dtype=torch.float64)
+                self._lenergy = torch.zeros(B, max(segs, 1), device=dev, dtype=torch.float64)
+                self._lseg = 0
+        self._fade = None                         # (first, count) once revoked with a fade inside the stream
+        self._revoked = None                      # the `Revoked` report of the revoke that stands
+
+    def _check_handle(self, who):
+        if self._net._handle is not self._h:
+            raise RuntimeError("the model's handle was re-created (device move) since %s started" % who)
+
+    # ---- the wire step and its measuring half, alone and as a row of a pool's tick
+    def _wire_alone(self, wave, in_avail, out_first, out_count, lengths):
+        self._net.resample_pcm16_range(wave, self.model_sr, self.rate, in_avail, out_first, out_count, self.pcm,
+                                       valid_samples=self._valid_in, peak=self._peak_in, running_peak=self.peak,
+                                       out_samples=self.valid_samples if lengths else None, res_type=self.res_type,
+                                       limiter=self._lim, encoding=self.encoding, fade=self._fade, envelope=self._env)
+
+    def _wire_row(self, wave, in_avail, out_first, out_count, lengths):
+        k = _capi.MbvPcmChunk()
+        k.wave, k.in_total = wave.data_ptr(), wave.shape[1]
+        k.valid_samples = self._valid_in.data_ptr() if self._valid_in is not None else None
+        k.in_avail, k.out_first, k.out_count = in_avail, out_first, out_count
+        k.peak = self._peak_in.data_ptr() if self._peak_in is not None else None
+        k.pcm, k.pcm_capacity = self.pcm.data_ptr(), self.pcm.shape[1]
+        k.running_peak = self.peak.data_ptr()
+        k.out_samples = self.valid_samples.data_ptr() if lengths else None
+        return k
+
+    def _loudness_alone(self, wave, in_avail):
+        if self.loudness is None:
+            return
+        k1 = _segments_due(self._lseg, in_avail, self._lhop)
+        if k1 > self._lseg:
+            self._net.loudness_range(wave, self.model_sr, in_avail, self._lseg, k1 - self._lseg, self._lstate,
+                                     self._lenergy, self.loudness, valid_samples=self._valid_in)
+            self._lseg = k1
+
+    def _loudness_row(self, wave_ptr, in_total, in_avail):
+        """-> the `_capi.MbvLoudnessChunk` of the segments due now (`_lseg` moves once it is launched), or None."""
+        k1 = _segments_due(self._lseg, in_avail, self._lhop)
+        if k1 <= self._lseg:
+            return None
+        k = _capi.MbvLoudnessChunk()
+        k.wave, k.in_total, k.in_avail = wave_ptr, in_total, in_avail
+        k.valid_samples = self._valid_in.data_ptr() if self._valid_in is not None else None
+        k.seg_first, k.seg_count = self._lseg, k1 - self._lseg
+        k.state, k.energies, k.energy_capacity = self._lstate.data_ptr(), self._lenergy.data_ptr(), self._lenergy.shape[1]
+        k.loudness = self.loudness.data_ptr()
+        return k
+
+    def _due(self, k, pieces, final, env):
+        return _Due(k, pieces, final, self._lim, self._fade, env)
+
+    def _measure_row(self, k):
+        return None if self.loudness is None else self._loudness_row(k.wave, k.in_total, k.in_avail)
+
+    def _warp_dues(self):
+        return []
+
+    # ---- barge-in: the halves of `revoke` that a stream and a turn share
+    def _revoke_begin(self, fade_ms, at, emitted, total, marks=None, tokens=True):
+        """-> (the report that stands, None) for a revoked or finished stream; else (None, (F, N)) of `_revoke_args`."""
+        if self._revoked is not None:
+            return self._revoked, None
+        fade = _revoke_args(fade_ms, at, self.rate, emitted, total, marks, tokens, self.finished)
+        return (Revoked(total, 0, total, self._started(total)) if fade is None else None), fade
+
+    def _revoke_end(self, first, count, cut, total):
+        """The fade (inside the stream only) and the `Revoked` report that now stands."""
+        if first < total:
+            self._fade = (first, count)
+        self._revoked = Revoked(first, count, cut, self._started(first))
+        return self._revoked
+
+
+class PcmStream(_WireOut):
     """Iterator over (first_out_sample, pcm[:, a:b]) of one streamed decode: after every chunk of the wrapped
     `stream.DecodeStream` one `mbv_resample_pcm16_range` launch turns the resampled samples that chunk made final
     into int16, on the caller's current stream, and the view is ordered on that stream like every other output.
@@ -713,7 +818,7 @@ class PcmStream:
     A `PcmPool` may wire chunks ahead of the iterator (`_wired` > the decode stream's `_next`): `next()` then hands
     such a piece out without launching anything, and launches alone otherwise — the same bytes either way.
 
-    A pitched stream (`st.warp`) is read through `_src_row`, `_src_len` and `_src_frontier`: the warped row
+    A pitched stream (`st.warp`) is read through `_src_row`, `_src_n` and `_src_frontier`: the warped row
     this stream owns, its length and its frontier, in place of `st.o`; `loudness` stays measured on the decoded row.
 
     `marks` (a stream made with `marks=True`; else None) lists the wire sample at which every token starts
@@ -725,75 +830,55 @@ class PcmStream:
         _refuse_live(st)
         loud = _loudness_arg(loudness, peak, "stream_pcm16", stream=True)
         # per-token volume: given, or the stream's own frame gains; None: the row is not shaped
-        self._env = _envelope_arg(envelope, st, "stream_pcm16")
-        if self._env is not None:
-            self._env.check("stream_pcm16", st.o.shape[0], st.o.shape[-1], st.o.device)
+        env = _envelope_arg(envelope, st, "stream_pcm16")
+        if env is not None:
+            env.check("stream_pcm16", st.o.shape[0], st.o.shape[-1], st.o.device)
         # per-token pitch: the wire reads the warped row this stream owns; the envelope goes to the warp
-        self._warp = None
-        if getattr(st, "warp", None) is not None:
-            self._warp = _Warped(net, st, self._env, res_type)
-            self._env = None
-        self.encoding, dtype = encoding, _wire_dtype(encoding)
-        self._net, self._st, self._h = net, st, st._h
-        self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
-        self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
-        lag = self._lim[1] if self._lim else 0
+        warp = None if st.warp is None else _Warped(net, st, env, res_type)
+        self._st, self._h, self._env, self._warp = st, st._h, (env if warp is None else None), warp
+        _wire_dtype(encoding)                     # (refused here, in the order of before: encoding, limiter, rate pair)
+        lim = _limit_arg(limiter, rate)
+        lag = lim[1] if lim else 0
         o = st.o
-        B, n = o.shape[0], self._src_len()
-        dev = o.device
+        B, n, dev = o.shape[0], (o.shape[-1] if warp is None else warp.n), o.device
+        self._src_n = n
         # final outputs after each decoded chunk (pure integers of the schedule: nothing to ask the device)
         self._front = [self._src_frontier(i) for i in range(len(st.schedule))]
         self._ready = [limiter_ready(model_sr, rate, a, n, lag, res_type) for a in self._front]
         self.out_stride = resample_ready(model_sr, rate, n, n, res_type)
-        self.pcm = torch.empty(B, self.out_stride, device=dev, dtype=dtype)
-        self.valid_samples = torch.zeros(B, device=dev, dtype=torch.int64)
-        self.peak = torch.zeros(B, device=dev, dtype=torch.float32)
-        self._valid_in = None                     # valid input samples, as service_pcm16 counts them
-        if st.y_lengths is not None and self._warp is None:      # (a warped row is valid over its whole length)
+        super().__init__(net, dev, B, self.out_stride, model_sr=model_sr, rate=rate, res_type=res_type, encoding=encoding,
+                         peak=peak, limiter=limiter, loud=loud, capacity=o.shape[-1], silent=False)
+        # valid input samples, as service_pcm16 counts them (a warped row is valid over its whole length)
+        if st.y_lengths is not None and warp is None:
             self._valid_in = (st.y_lengths.to(device=dev, dtype=torch.int64) * 256).clamp(0, n).contiguous()
-        self._peak_in = _peak_arg(peak, B, dev)
-        _loudness_open(self, loud, B, o.shape[-1], dev)     # .loudness: the running integrated loudness, or None
-        if loud is not None and loud.target is not None:
-            with torch.cuda.device(dev):
-                self._peak_in = loud.peak(loud.measured_rows(B, dev)).contiguous()
         self._done = 0                            # outputs emitted so far
         self._wired = 0                           # the first chunk whose final outputs are not emitted yet
-        self._fade = None                         # (first, count) once revoked with a fade inside the stream
-        self._revoked = None                      # the `Revoked` report of the revoke that stands
         self._cut = None                          # the length a revoke left: valid_samples is clamped to it
         # token marks in wire samples (None: the stream carries none, e.g. a converted recording)
         self.marks = None
-        marks = getattr(st, "marks", None)
-        if marks is not None:
-            each = [mark_samples(m, st.spf, model_sr, rate, lag, warp=getattr(st, "warp", None))
-                    for m in (marks if B > 1 else [marks])]
+        if st.marks is not None:
+            each = [mark_samples(m, st.spf, model_sr, rate, lag, warp=st.warp) for m in (st.marks if B > 1 else [st.marks])]
             self.marks = each if B > 1 else each[0]
 
     # ---- the input of the wire step: the decoded row, or the warped row of a pitched stream
     def _src_row(self):
         return self._st.o[:, 0] if self._warp is None else self._warp.row
 
-    def _src_len(self):
-        return self._st.o.shape[-1] if self._warp is None else self._warp.n
-
     def _src_frontier(self, i):
         """input samples of the wire step that exist once chunk i is decoded"""
-        first, count = self._st.schedule[i]
-        a = self._st.spf * (first + count)
+        a = _decoded_samples(self._st, i)
         return a if self._warp is None else self._warp.frontier(a)
 
-    def _warp_due(self, i):
-        """the warp range that chunk i made final: (the `_Warped`, (row, end)), or None"""
-        if self._warp is None:
-            return None
-        first, count = self._st.schedule[i]
-        due = self._warp.due(self._st.spf * (first + count))
-        return None if due is None else (self._warp, due)
+    def _warp_dues(self, i=None):
+        """[(the `_Warped`, (row, end))] of the warp range that chunk i made final (None: the last decoded, in a pool's
+        tick), in front of its wire step; at most one"""
+        i = self._st._decoded - 1 if i is None else i
+        due = self._warp.due(_decoded_samples(self._st, i)) if self._warp is not None and i >= self._wired else None
+        return [(self._warp, due)] if due else []
 
     def _measured(self, i):
         """what the loudness of step i is measured on: the DECODED row and frontier, warped or not"""
-        first, count = self._st.schedule[i]
-        return self._st.o[:, 0], self._st.spf * (first + count)
+        return self._st.o[:, 0], _decoded_samples(self._st, i)
 
     def __len__(self):
         return len(self._st)
@@ -810,7 +895,7 @@ class PcmStream:
     def _total(self):
         """The stream's length in wire samples, on the host: what `valid_samples` holds for a single utterance, whose
         `y_lengths` covers at least the frames the stream keeps."""
-        n = self._src_len()
+        n = self._src_n
         v = n if self._st.y_lengths is None or self._warp is not None else min(256 * self._st.z.shape[2], n)
         return resample_ready(self.model_sr, self.rate, v, v, self.res_type)
 
@@ -834,38 +919,20 @@ class PcmStream:
         length.  -> a `Revoked` report.  Revoking a finished or already revoked stream changes nothing and returns
         the report of what stands.  The 5 ms default is a convention, like the limiter's, not a measurement.  Single
         utterances only (B = 1), as a pool takes them."""
-        if self._revoked is not None:
-            return self._revoked
-        if self.pcm.shape[0] != 1:
+        if self._revoked is None and self.pcm.shape[0] != 1:
             raise ValueError("revoke: a stream of ONE utterance is taken back (this one has %d rows)" % self.pcm.shape[0])
-        if not float(fade_ms) >= 0.0:
-            raise ValueError("revoke: fade_ms must be >= 0")
         total, E = self._total(), self._done
-        if self.finished:
-            return Revoked(total, 0, total, self._started(total))
-        N = int(round(float(fade_ms) * 1e-3 * self.rate))
-        if at == "now":
-            F = E
-        elif at == "token":
-            if self.marks is None:
-                raise ValueError("revoke(at='token'): the stream has no token marks (infer_stream(marks=True); a "
-                                 "converted recording has no tokens)")
-            F = next((m for m in self.marks if m >= E), total)
-        elif isinstance(at, (int, np.integer)) and not isinstance(at, bool):
-            F = int(at)
-        else:
-            raise ValueError("revoke: at must be 'now', 'token' or a wire sample index, got %r" % (at,))
-        cut, last, ready = revoke_plan(self._ready, total, E, F, N)      # (refuses F < E before anything changes)
+        report, fade = self._revoke_begin(fade_ms, at, E, total, self.marks)
+        if fade is None:
+            return report
+        cut, last, ready = revoke_plan(self._ready, total, E, *fade)     # (refuses F < E before anything changes)
         st = self._st
         keep = max(last + 1, st._decoded, self._wired)
         st._truncate(keep)
         self._ready = ready + [cut] * (keep - len(ready))
-        if F < total:
-            self._fade = (F, N)
         self._cut = cut
         self._clamp_valid()
-        self._revoked = Revoked(F, N, cut, self._started(F))
-        return self._revoked
+        return self._revoke_end(*fade, cut, total)
 
     def _started(self, first):
         return None if self.marks is None else sum(1 for m in self.marks[:-1] if m < first)
@@ -877,17 +944,15 @@ class PcmStream:
         st, net = self._st, self._net
         i = st._next
         next(st)                                  # decodes chunk i (StopIteration ends this stream too)
-        if net._handle is not self._h:
-            raise RuntimeError("the model's handle was re-created (device move) since this stream started")
+        self._check_handle("this stream")
         if i < self._wired:                       # a pool wired it already, on the stream current at its step
             a, b = (self._ready[i - 1] if i else 0), self._ready[i]
             return a, self.pcm[:, a:b]
         a, b = self._done, self._ready[i]
         step = self._step_through(i)
-        due = self._warp_due(i)
-        _warp_launch(net, [due] if due else [])    # the newly ready warped range, in front of the wire step
-        _wire_alone(self, *step)
-        _loudness_alone(self, *self._measured(i))
+        _warp_launch(net, self._warp_dues(i))      # the newly ready warped range, in front of the wire step
+        self._wire_alone(*step)
+        self._loudness_alone(*self._measured(i))
         self._done, self._wired = b, i + 1
         self._clamp_valid()
         return a, self.pcm[:, a:b]
@@ -896,26 +961,31 @@ class PcmStream:
         """The wire step that takes in the decoded chunks up to chunk i."""
         return self._src_row(), self._front[i], self._done, self._ready[i] - self._done, self._wired == 0
 
-    # ---- what a pool shares (PcmPool.step), as `LiveWire` has it
-    def _wire_chunk(self, k):
-        """Fills the `_capi.MbvPcmChunk` `k` with the wire step due now; -> (final, pieces), or None."""
+    # ---- the member of a pool (the protocol of `_WireOut`)
+    _KIND = "stream"
+    _wired_out = finished
+    _name = property(lambda self: self._st)
+
+    def _decode_streams(self):
+        return [self._st]
+
+    def _wire_chunk(self):
         i = self._st._decoded - 1
         if i < self._wired:
             return None
-        if self._net._handle is not self._h:
-            raise RuntimeError("the model's handle was re-created (device move) since a pooled stream started")
-        _wire_row(self, k, *self._step_through(i))
-        return i + 1 == len(self._st.schedule), [(self._done, self._ready[i])]
+        self._check_handle("a pooled stream")
+        return self._due(self._wire_row(*self._step_through(i)), [(self._done, self._ready[i])],
+                         i + 1 == len(self._st.schedule), self._env)
 
-    def _chunk_wired(self, final, pieces):
+    def _measure_row(self, k):
+        if self.loudness is None:
+            return None
+        o, avail = self._measured(self._st._decoded - 1)          # (a pitched member: its decoded row, not `k`'s)
+        return self._loudness_row(o.data_ptr(), o.shape[-1], avail)
+
+    def _chunk_wired(self, pieces, final):
         self._done, self._wired = pieces[-1][1], self._st._decoded
         self._clamp_valid()
-
-    def _warp_dues(self):
-        """The warp ranges the pool's tick owes this member (at most one), in front of its wire row."""
-        i = self._st._decoded - 1
-        due = self._warp_due(i) if i >= self._wired else None
-        return [due] if due else []
 
     def run(self):
         """Every remaining chunk; -> (pcm, valid_samples)."""
@@ -969,12 +1039,8 @@ def pcm_chunks_plan(orig_sr, target_sr, chunks, res_type="kaiser_best"):
         chunks = (_capi.MbvPcmChunk * len(chunks))(*chunks)
     n = len(chunks)
     first = (C.c_int64 * max(n, 1))()
-    L = _capi.lib()
-    total = L.mbv_pcm_chunks_plan(int(orig_sr), int(target_sr), filt, chunks, n, first)
-    if total < 0:
-        msg = L.mbv_last_error(None)
-        raise _capi.MbvError(msg.decode() if msg else "mbv_pcm_chunks_plan failed")
-    return int(total), list(first)[:n]
+    total = _ready_call("mbv_pcm_chunks_plan", int(orig_sr), int(target_sr), filt, chunks, n, first)
+    return total, list(first)[:n]
 
 
 def wire_runs(net):
@@ -1115,7 +1181,7 @@ class LiveWirePlan:
             self.wire_done, self.valid = True, int(out_done)
 
 
-class LiveWire:
+class LiveWire(_WireOut):
     """One live voice conversion from raw samples to int16 (`convert_live_pcm16`): the live form of
     `convert_pcm16`.
 
@@ -1145,55 +1211,45 @@ class LiveWire:
         from .stream import LiveStream
         _refuse_envelope(envelope, "convert_live_pcm16")
         _refuse_pitch(pitch, "convert_live_pcm16")
-        self._env = None                          # (what the pooled wire step reads on every member)
         _filter_code(res_type)
         loud = _loudness_arg(loudness, peak, "convert_live_pcm16", stream=True)
-        self.limiter, self._lim = limiter, _limit_arg(limiter, rate)
-        self.encoding, out_law = encoding, _law_code(encoding)
+        lim = _limit_arg(limiter, rate)           # (refused here, before the `LiveStream` reserves anything)
+        _law_code(encoding)
         self.in_encoding = _in_law(in_encoding, in_sr, model_sr, "convert_live_pcm16")
         if (dtype == torch.uint8) != (self.in_encoding is not None):
             raise TypeError("convert_live_pcm16: dtype=torch.uint8 and in_encoding='ulaw' | 'alaw' go together "
                             "(got dtype %s, in_encoding=%r)" % (dtype, in_encoding))
         if dtype not in (torch.float32, torch.int16, torch.uint8):
             raise TypeError("convert_live_pcm16: dtype must be int16 or float32, got %s" % dtype)
-        self.in_sr, self.model_sr, self.rate, self.res_type = int(in_sr), int(model_sr), int(rate), res_type
-        if min(self.in_sr, self.model_sr, self.rate) <= 0:
+        self.in_sr, model_sr, rate = int(in_sr), int(model_sr), int(rate)
+        if min(self.in_sr, model_sr, rate) <= 0:
             raise ValueError("sample rates must be positive")
         self.max_samples, self.dtype = int(max_samples), dtype
         if self.max_samples < 1:
             raise ValueError("convert_live_pcm16: max_samples must be >= 1")
-        resamples = self.in_sr != self.model_sr
+        resamples = self.in_sr != model_sr
         if resamples:
-            resample_ready_open(self.in_sr, self.model_sr, 0, res_type)      # refuses the rate pair before any buffer
-        if self.rate != self.model_sr:
-            resample_ready(self.model_sr, self.rate, 0, 1, res_type)
-        cap = int(math.ceil(self.max_samples * (float(self.model_sr) / self.in_sr))) if resamples else self.max_samples
+            resample_ready_open(self.in_sr, model_sr, 0, res_type)           # refuses the rate pair before any buffer
+        if rate != model_sr:
+            resample_ready(model_sr, rate, 0, 1, res_type)
+        cap = int(math.ceil(self.max_samples * (float(model_sr) / self.in_sr))) if resamples else self.max_samples
         self.live = LiveStream(net, sid_src, sid_tgt, model_sr, hop_size, win_size, cap,
                                dtype=torch.float32 if resamples else dtype, noise_scale=noise_scale, noise=noise,
                                chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames,
                                convert_frames=convert_frames, seed=seed)
         live = self.live
-        self._net = net
-        self._plan = LiveWirePlan(self.in_sr, self.model_sr, self.rate, live.plan, live.spf, self.max_samples, res_type,
-                                  lookahead=self._lim[1] if self._lim else 0)
+        self._plan = LiveWirePlan(self.in_sr, model_sr, rate, live.plan, live.spf, self.max_samples, res_type,
+                                  lookahead=lim[1] if lim else 0)
         assert self._plan.o_capacity == live.o.shape[-1] and self._plan.capacity == live.max_samples
         dev = live.z.device
+        super().__init__(net, dev, 1, self._plan.pcm_capacity, model_sr=model_sr, rate=rate, res_type=res_type,
+                         encoding=encoding, peak=peak, limiter=limiter, loud=loud, capacity=self._plan.o_capacity,
+                         silent=True)
         with torch.cuda.device(dev):
             # raw samples beyond the frontier are never read, so the buffer is not cleared
             self.raw = torch.empty(self.max_samples, device=dev, dtype=dtype) if resamples else None
-            if out_law:                           # silence in G.711 is not the zero byte
-                self.pcm = torch.full((1, self._plan.pcm_capacity), G711_ZERO[encoding], device=dev, dtype=torch.uint8)
-            else:
-                self.pcm = torch.zeros(1, self._plan.pcm_capacity, device=dev, dtype=torch.int16)
-            self.valid_samples = torch.zeros(1, device=dev, dtype=torch.int64)
-            self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
             # valid input samples of the wire step: the capacity of o while the total is unknown
             self._valid_in = torch.full((1,), self._plan.o_capacity, device=dev, dtype=torch.int64)
-            self._peak_in = _peak_arg(peak, 1, dev, shape="1")
-            if loud is not None and loud.target is not None:
-                self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
-        _loudness_open(self, loud, 1, self._plan.o_capacity, dev)     # .loudness, as on a `PcmStream`
-        self._fade = None             # (a live wire is not revoked: the caller stops pushing and drops it)
         self._pieces = []             # (a, b) of every piece wired so far, in order
         self._handed = 0              # the piece poll() hands out next
 
@@ -1261,7 +1317,7 @@ class LiveWire:
         self.live.fed(n, last=self._plan.fed(n))
 
     def _wire_due(self):
-        """-> None, or ((the arguments of the wire step due now), final, pieces) from `LiveWirePlan.wire_due` of the
+        """-> None, or ((the arguments of the wire step due now), pieces, final) from `LiveWirePlan.wire_due` of the
         chunks decoded so far; with the last chunk the valid input samples become 256 T, as `service_pcm16` counts them
         (a device fill)."""
         w = self._plan.wire_due(self.live.chunks)
@@ -1272,26 +1328,15 @@ class LiveWire:
         if final:
             with torch.cuda.device(self.pcm.device):
                 self._valid_in.fill_(min(256 * self.live.frames, in_total))
-        return (self.live.o[:, 0, :in_total], in_avail, out_first, out_count, final), final, pieces
-
-    def _wire_chunk(self, k):
-        """Fills the `_capi.MbvPcmChunk` `k` with the wire step due now; -> (final, pieces), or None."""
-        w = self._wire_due()
-        if w is None:
-            return None
-        _wire_row(self, k, *w[0])
-        return w[1:]
-
-    def _chunk_wired(self, final, pieces):
-        self._pieces.extend(pieces)
-        self._plan.wired(len(self.live.chunks), pieces[-1][1], final)
+        return (self.live.o[:, 0, :in_total], in_avail, out_first, out_count, final), pieces, final
 
     def _wire(self):
         w = self._wire_due()
         if w is not None:
-            _wire_alone(self, *w[0])
-            _loudness_alone(self, w[0][0], w[0][1])
-            self._chunk_wired(*w[1:])
+            step, pieces, final = w
+            self._wire_alone(*step)
+            self._loudness_alone(step[0], step[1])
+            self._chunk_wired(pieces, final)
 
     def poll(self):
         """-> [(first_out_sample, int16 view of pcm[0, a:b]), ...]: every piece not handed out yet, one per decoded
@@ -1302,6 +1347,22 @@ class LiveWire:
         out = [(a, self.pcm[0, a:b]) for a, b in self._pieces[self._handed:]]
         self._handed = len(self._pieces)
         return out
+
+    # ---- the member of a pool (the protocol of `_WireOut`; `_feed_row` and `_fed` are the live members' own)
+    _KIND = "live wire"
+
+    _wired_out = property(lambda self: self._plan.wire_done)
+
+    def _decode_streams(self):
+        return [self.live]
+
+    def _wire_chunk(self):
+        w = self._wire_due()
+        return None if w is None else self._due(self._wire_row(*w[0]), w[1], w[2], self._env)
+
+    def _chunk_wired(self, pieces, final):
+        self._pieces.extend(pieces)
+        self._plan.wired(len(self.live.chunks), pieces[-1][1], final)
 
 
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
@@ -1400,12 +1461,8 @@ def turn_plan(orig_sr, target_sr, turns, res_type="kaiser_best", limits=None):
     if limits is not None and any(l is not None for l in limits):
         lim = (_capi.MbvPcmLimit * n)(*[_capi.MbvPcmLimit(*(l or (0.0, 0, 0))) for l in limits])
     first = (C.c_int64 * max(n, 1))()
-    L = _capi.lib()
-    total = L.mbv_turn_plan(int(orig_sr), int(target_sr), filt, turns, lim, n, first)
-    if total < 0:
-        msg = L.mbv_last_error(None)
-        raise _capi.MbvError(msg.decode() if msg else "mbv_turn_plan failed")
-    return int(total), list(first)[:n]
+    total = _ready_call("mbv_turn_plan", int(orig_sr), int(target_sr), filt, turns, lim, n, first)
+    return total, list(first)[:n]
 
 
 class TurnPlan:
@@ -1565,21 +1622,16 @@ class TurnPlan:
             self._fence = self.starts[keep]
 
 
-def _frames_decoded(st):
-    """z-frames of a `DecodeStream` decoded so far."""
-    return sum(st.schedule[st._decoded - 1]) if st._decoded else 0
-
-
 def _segment_length(st):
     """Valid model-rate samples of a single-utterance stream, on the host: what `PcmStream` takes as its valid input
     (the warped length of a pitched stream)."""
-    if getattr(st, "warp", None) is not None:
+    if st.warp is not None:
         return st.warp.n_out
     n = st.o.shape[-1]
     return n if st.y_lengths is None else min(256 * st.z.shape[2], n)
 
 
-class Turn:
+class Turn(_WireOut):
     """Several utterances as ONE gapless wire stream (`PcmPool.add_turn`): the phrases of a dialogue turn,
     appended while earlier ones play, resampled, limited and framed as one continuous piece of audio.
 
@@ -1599,37 +1651,25 @@ class Turn:
     segment, so a joint never depends on what is appended later."""
 
     def __init__(self, pool, max_samples, peak=None, limiter=None, loudness=None, ramp_ms=5.0):
-        self._pool, self._net = pool, pool._net
-        net = self._net
-        self.model_sr, self.rate, self.res_type, self.encoding = pool.model_sr, pool.rate, pool.res_type, pool.encoding
-        self.limiter, self._lim = limiter, _limit_arg(limiter, self.rate)
+        self._pool, net = pool, pool._net
+        lim = _limit_arg(limiter, pool.rate)
         loud = _loudness_arg(loudness, peak, "PcmPool.add_turn", stream=True)
         if loud is not None and loud.target is None:
             raise ValueError("PcmPool.add_turn: a turn keeps no running loudness; loudness= takes Loudness(measured=...) "
                              "for the static gain only")
         if not float(ramp_ms) >= 0.0:
             raise ValueError("PcmPool.add_turn: ramp_ms must be >= 0")
-        self.ramp_ms, self.ramp = float(ramp_ms), int(round(float(ramp_ms) * 1e-3 * self.model_sr))
-        self._plan = TurnPlan(self.model_sr, self.rate, max_samples, self.res_type,
-                              lookahead=self._lim[1] if self._lim else 0, hold=self._lim[2] if self._lim else 0)
+        self.ramp_ms, self.ramp = float(ramp_ms), int(round(float(ramp_ms) * 1e-3 * pool.model_sr))
+        self._plan = TurnPlan(pool.model_sr, pool.rate, max_samples, pool.res_type,
+                              lookahead=lim[1] if lim else 0, hold=lim[2] if lim else 0)
         self._h = net._ensure_handle()
-        dev = net._device()
-        with torch.cuda.device(dev):
-            if _law_code(self.encoding):              # silence in G.711 is not the zero byte
-                self.pcm = torch.full((1, self._plan.max_samples), G711_ZERO[self.encoding], device=dev, dtype=torch.uint8)
-            else:
-                self.pcm = torch.zeros(1, self._plan.max_samples, device=dev, dtype=torch.int16)
-            self.valid_samples = torch.zeros(1, device=dev, dtype=torch.int64)
-            self.peak = torch.zeros(1, device=dev, dtype=torch.float32)
-            self._peak_in = _peak_arg(peak, 1, dev, shape="1")
-            if loud is not None:
-                self._peak_in = loud.peak(loud.measured_rows(1, dev)).contiguous()
+        super().__init__(net, net._device(), 1, self._plan.max_samples, model_sr=pool.model_sr, rate=pool.rate,
+                         res_type=pool.res_type, encoding=pool.encoding, peak=peak, limiter=limiter, loud=loud,
+                         capacity=None, silent=True)
         self.segments = []            # the `DecodeStream`s, in timeline order
         self.envelopes = []           # per segment: its `Envelope` (per-token volume, DESIGN §7.20) or None
         self.warped = []              # per segment: the `_Warped` row of a pitched stream (DESIGN §7.22) or None
         self.marks = []
-        self._fade = None
-        self._revoked = None
         self._valid_set = False
 
     # ---- where it stands
@@ -1678,19 +1718,19 @@ class Turn:
         n = _segment_length(st)
         env = _envelope_arg(envelope, st, "Turn.append")
         if env is not None:
-            env.check("Turn.append", 1, st.o.shape[-1] if getattr(st, "warp", None) is not None else n, st.o.device)
+            env.check("Turn.append", 1, st.o.shape[-1] if st.warp is not None else n, st.o.device)
         self._plan.check_append(n, self._pause(pause_ms))
         if not st._drained():
             self._pool.pool.add(st)                   # (refuses another device; a member stays one)
         # a pitched segment is its warped row, which the turn owns, with the warped length and frontier; its envelope
         # is handed to the warp, where the samples are read
-        wp = _Warped(self._net, st, env, self.res_type) if getattr(st, "warp", None) is not None else None
+        wp = _Warped(self._net, st, env, self.res_type) if st.warp is not None else None
         s = self._plan.append(n, self._pause(pause_ms))
         self.segments.append(st)
         self.envelopes.append(env if wp is None else None)
         self.warped.append(wp)
         lag = self._lim[1] if self._lim else 0
-        marks = getattr(st, "marks", None)
+        marks = st.marks
         at = None if marks is None else ([st.spf * int(f) for f in marks] if wp is None
                                          else wp.map.samples_of_frames(marks))
         self.marks.append(None if marks is None else mark_samples(
@@ -1731,19 +1771,25 @@ class Turn:
         that flushes the filter's lag."""
         self._plan.close()
         self._settle()
+        self._pool._drop_finished()               # (a turn that this finished leaves at once, as before)
 
-    # ---- what the pool shares (PcmPool.step)
-    def _wire_chunk(self, k):
-        """Fills the `_capi.MbvTurnChunk` `k` with the wire step due now; -> [(a, b)], or None."""
+    # ---- the member of a pool (the protocol of `_WireOut`)
+    _KIND, _TURNS = "turn", True
+    _wired_out = finished
+
+    def _decode_streams(self):
+        return self.segments
+
+    def _wire_chunk(self):
         plan = self._plan
         for s, st in enumerate(self.segments):
-            plan.decoded(s, self._seg_frontier(s, st.spf * _frames_decoded(st)))
+            plan.decoded(s, self._seg_frontier(s, _decoded_samples(st)))
         due = plan.wire_due()
         if due is None:
             return None
-        if self._net._handle is not self._h:
-            raise RuntimeError("the model's handle was re-created (device move) since this turn started")
+        self._check_handle("this turn")
         a, count = due
+        k = _capi.MbvTurnChunk()
         c = k.chunk
         c.wave, c.in_total, c.valid_samples, c.in_avail = None, plan.in_total(), None, plan.frontier()
         c.out_first, c.out_count = a, count
@@ -1757,10 +1803,9 @@ class Turn:
             sg.wave, sg.start, sg.length = wave.data_ptr(), plan.starts[s], plan.lengths[s]
             sg.ramp = turn_ramp(self.ramp, plan.lengths[s])
         k.segs, k.n_segs = segs, s1 - s0
-        self._seg_envs = self.envelopes[s0:s1]    # beside `segs`, for the pool's call
-        return [(a, a + count)]
+        return self._due(k, [(a, a + count)], None, self.envelopes[s0:s1])
 
-    def _chunk_wired(self, pieces):
+    def _chunk_wired(self, pieces, final):
         self._plan.wired(pieces[-1][1])
         self._settle()
 
@@ -1769,23 +1814,22 @@ class Turn:
         return model_avail if self.warped[s] is None else self.warped[s].frontier(model_avail)
 
     def _warp_dues(self):
-        """The warp ranges the pool's tick owes the turn's pitched segments, in front of its wire row."""
         dues = []
         for st, wp in zip(self.segments, self.warped):
-            due = wp.due(st.spf * _frames_decoded(st)) if wp is not None else None
+            due = wp.due(_decoded_samples(st)) if wp is not None else None
             if due:
                 dues.append((wp, due))
         return dues
 
     def _settle(self):
-        """Once the last piece is out: `valid_samples` (a device fill of a host integer), and the turn leaves the pool."""
+        """Once the last piece is out: `valid_samples` (a device fill of a host integer), the segments still in the
+        `StreamPool` leave it.  (Leaving the `PcmPool` is the pool's: `step`, or `close` / `revoke` asking it.)"""
         plan = self._plan
         if not plan.done or self._valid_set:
             return
         self._valid_set = True
         with torch.cuda.device(self.pcm.device):
             self.valid_samples.fill_(plan.out_total() if plan.cut is None else plan.cut)
-        self._pool.turns = [t for t in self._pool.turns if t is not self]
         for st in self.segments:
             if any(st is m for m in self._pool.pool.streams):
                 self._pool.pool.remove(st)
@@ -1804,25 +1848,14 @@ class Turn:
         readiness), the segments behind it leave the `StreamPool` undecoded.  The bytes are bitwise
         `service_pcm16(assemble_turn(...), fade=(F, N))`.  -> a `Revoked`; `tokens_started` counts over all segments'
         marks (None when a segment has none).  Revoking a finished or revoked turn changes nothing."""
-        if self._revoked is not None:
-            return self._revoked
-        if not float(fade_ms) >= 0.0:
-            raise ValueError("revoke: fade_ms must be >= 0")
         plan = self._plan
-        total_in = plan.end
-        total, E = plan.out_total(total_in), plan.out_done
-        if self.finished:
-            return Revoked(total, 0, total, self._started(total))
-        N = int(round(float(fade_ms) * 1e-3 * self.rate))
-        if at == "now":
-            F = E
-        elif isinstance(at, (int, np.integer)) and not isinstance(at, bool):
-            F = int(at)
-        else:
-            raise ValueError("revoke: at must be 'now' or a wire sample index, got %r" % (at,))
-        events = plan.revoke_events([[self._seg_frontier(s, st.spf * (first + count)) for first, count in st.schedule]
+        total, E = plan.out_total(), plan.out_done
+        report, fade = self._revoke_begin(fade_ms, at, E, total, tokens=False)
+        if fade is None:
+            return report
+        events = plan.revoke_events([[self._seg_frontier(s, _decoded_samples(st, i)) for i in range(len(st.schedule))]
                                      for s, st in enumerate(self.segments)]) or [(0, 0, 0)]
-        cut, last, _ = revoke_plan([r for _, _, r in events], total, E, F, N)   # (refuses F < E before anything changes)
+        cut, last, _ = revoke_plan([r for _, _, r in events], total, E, *fade)  # (refuses F < E before anything changes)
         s_cut, i_cut, _ = events[last]
         for s, st in enumerate(self.segments):
             if s == s_cut:
@@ -1836,11 +1869,10 @@ class Turn:
             self.segments = self.segments[:keep]              # (`marks` keeps every segment's: the report counts over all)
             self.envelopes = self.envelopes[:keep]
             self.warped = self.warped[:keep]
-        if F < total:
-            self._fade = (F, N)
-        self._revoked = Revoked(F, N, cut, self._started(F))
+        report = self._revoke_end(*fade, cut, total)
         self._settle()
-        return self._revoked
+        self._pool._drop_finished()
+        return report
 
 
 class PcmPool:
@@ -1869,21 +1901,25 @@ class PcmPool:
             raise ValueError("the stream pool belongs to another model")
         self._net, self.pool = net, pool
         self.model_sr, self.rate, self.res_type = int(model_sr), int(rate), res_type
-        self.followers = []
-        self.lives = []                           # the `LiveWire`s added with add_live
-        self.turns = []                           # the `Turn`s added with add_turn
+        self._members = []                        # every `PcmStream`, `LiveWire` and `Turn` of the pool, in the order added
         self._packed = None                       # device, the call's pieces back to back (host=True)
         self._host = self._host_np = None         # its pinned host copy, and that as a NumPy array
         self._event = None
 
     def __len__(self):
-        return len(self.followers) + len(self.lives) + len(self.turns)
+        return len(self._members)
+
+    # views: the followers of `add`, the `LiveWire`s of `add_live`, the `Turn`s of `add_turn`, each in the order added
+    followers = property(lambda self: [m for m in self._members if m._KIND == "stream"])
+    lives = property(lambda self: [m for m in self._members if m._KIND == "live wire"])
+    turns = property(lambda self: [m for m in self._members if m._KIND == "turn"])
+
+    def _drop_finished(self):
+        """The one leave rule: a member with nothing more to wire leaves the pool."""
+        self._members = [m for m in self._members if not m._wired_out]
 
     def follower(self, st):
-        for f in self.followers:
-            if f._st is st:
-                return f
-        return None
+        return next((f for f in self.followers if f._st is st), None)
 
     def add(self, st, peak=None, limiter=None, loudness=None, envelope=None):
         """-> the stream's `PcmStream` follower.  `envelope`: per-token volume as `stream_pcm16` takes it; a stream made
@@ -1898,7 +1934,7 @@ class PcmPool:
         if f is None:
             f = PcmStream(self._net, st, self.model_sr, self.rate, peak=peak, res_type=self.res_type, limiter=limiter,
                           encoding=self.encoding, loudness=loudness, envelope=envelope)
-            self.followers.append(f)
+            self._members.append(f)
         return f
 
     def admit(self, requests, peak=None, limiter=None, loudness=None):
@@ -1906,17 +1942,11 @@ class PcmPool:
         request, as `add` takes it; `limiter` and `loudness` likewise); -> the followers, in order.  `requests` is all `models.Request` or all
         `models.ConvertRequest` (audio), as `StreamPool.admit` takes them.  All or nothing, like `StreamPool.admit`."""
         reqs = list(requests)
-        peaks = list(peak) if isinstance(peak, (list, tuple)) else [peak] * len(reqs)
-        if len(peaks) != len(reqs):
-            raise ValueError("admit: one peak per request expected (%d), got %d" % (len(reqs), len(peaks)))
-        limiters = list(limiter) if isinstance(limiter, (list, tuple)) else [limiter] * len(reqs)
-        if len(limiters) != len(reqs):
-            raise ValueError("admit: one limiter per request expected (%d), got %d" % (len(reqs), len(limiters)))
+        peaks = _per_request("admit", "peak", peak, len(reqs))
+        limiters = _per_request("admit", "limiter", limiter, len(reqs))
         for lim in limiters:
             _limit_arg(lim, self.rate)
-        louds = list(loudness) if isinstance(loudness, (list, tuple)) else [loudness] * len(reqs)
-        if len(louds) != len(reqs):
-            raise ValueError("admit: one loudness per request expected (%d), got %d" % (len(reqs), len(louds)))
+        louds = _per_request("admit", "loudness", loudness, len(reqs))
         for p, loud in zip(peaks, louds):
             _loudness_arg(loud, p, "PcmPool.admit", stream=True)
         return [self.add(st, peak=p, limiter=lim, loudness=loud)
@@ -1935,10 +1965,9 @@ class PcmPool:
         if f is None or not any(f is m for m in self.followers):
             raise ValueError("PcmPool.revoke names a stream that is not in the pool")
         report = f.revoke(fade_ms=fade_ms, at=at)
-        if f.finished:
-            self.followers = [m for m in self.followers if m is not f]
-            if any(f._st is m for m in self.pool.streams):
-                self.pool.remove(f._st)
+        if f.finished and any(f._st is m for m in self.pool.streams):
+            self.pool.remove(f._st)
+        self._drop_finished()
         return report
 
     def add_live(self, lw, limiter=None, loudness=None, envelope=None, pitch=None):
@@ -1962,8 +1991,8 @@ class PcmPool:
         if lw.encoding != self.encoding:
             raise ValueError("the live wire was opened with encoding %r, the pool with %r" % (lw.encoding, self.encoding))
         self.pool.add(lw.live)                    # (refuses another model, another device)
-        if not any(lw is m for m in self.lives):
-            self.lives.append(lw)
+        if not any(lw is m for m in self._members):
+            self._members.append(lw)
         return lw
 
     def add_turn(self, max_samples, peak=None, limiter=None, loudness=None, ramp_ms=5.0):
@@ -1975,7 +2004,7 @@ class PcmPool:
         wires the turn along with the other members, ONE `mbv_resample_turns` call per tick for all turns, and
         `step(streams=[turn])` names it."""
         t = Turn(self, max_samples, peak=peak, limiter=limiter, loudness=loudness, ramp_ms=ramp_ms)
-        self.turns.append(t)
+        self._members.append(t)
         return t
 
     def _feed_lives(self, lives):
@@ -2003,59 +2032,33 @@ class PcmPool:
         `(turn, first, piece)` entry; all turns of a tick share ONE `mbv_resample_turns` call, their pieces lie behind
         the members' in the pinned buffer, and `streams` may name a turn (its segments are then stepped)."""
         net = self._net
-        if streams is None:
-            members, lives, turns = list(self.followers), list(self.lives), list(self.turns)
-        else:
-            members, lives, turns = [], [], []
-            for st in streams:
-                if isinstance(st, Turn):
-                    if not any(st is m for m in self.turns):
-                        raise ValueError("step(streams=...) names a turn that is not in the pool")
-                    turns.append(st)
-                    continue
-                if isinstance(st, LiveWire):
-                    if not any(st is m for m in self.lives):
-                        raise ValueError("step(streams=...) names a live wire that is not in the pool")
-                    lives.append(st)
-                    continue
-                f = self.follower(st)
-                if f is None:
-                    raise ValueError("step(streams=...) names a stream that is not in the pool")
-                members.append(f)
-        if lives:
-            self._feed_lives(lives)
+        members = list(self._members) if streams is None else [self._named(st) for st in streams]
+        members = [m for kind in _KINDS for m in members if m._KIND == kind]      # the order of `out`
+        self._feed_lives([m for m in members if m._KIND == "live wire"])
         named = None
         if streams is not None:
-            named = [st for st in [f._st for f in members] + [lw.live for lw in lives]
-                     + [sg for t in turns for sg in t.segments] if not st._drained()]
+            named = [st for m in members for st in m._decode_streams() if not st._drained()]
         if named is None or named:
             self.pool.step(named)
         # the pitched followers and turn segments of the tick: ONE mbv_warp_ranges launch in front of the wire launches
-        _warp_launch(net, [d for w in members + turns for d in w._warp_dues()])
-        rows = []                                 # (stream, member, its table row, (final, [(a, b), ...])) per row
-        for w, st in [(f, f._st) for f in members] + [(lw, lw) for lw in lives]:
-            k = _capi.MbvPcmChunk()
-            due = w._wire_chunk(k)
-            if due is not None:
-                rows.append((st, w, k, due))
-        trows = []                                # (turn, its table row, [(a, b)]) per turn with something due
-        for t in turns:
-            k = _capi.MbvTurnChunk()
-            due = t._wire_chunk(k)
-            if due is not None:
-                trows.append((t, k, due))
+        _warp_launch(net, [d for m in members for d in m._warp_dues()])
+        # (member, the `_Due` of its wire step) per member with one
+        rows = [(m, due) for m in members if (due := m._wire_chunk()) is not None]
         out = []
-        if rows or trows:
-            arr = (_capi.MbvPcmChunk * len(rows))(*[k for _, _, k, _ in rows])
-            tarr = (_capi.MbvTurnChunk * len(trows))(*[k for _, k, _ in trows])
-            tlimits = [t._lim for t, _, _ in trows]
+        if rows:
+            chunk_rows = [due for m, due in rows if not m._TURNS]         # the two tables; in `rows` the turns' come last
+            turn_rows = [due for m, due in rows if m._TURNS]
+            arr = (_capi.MbvPcmChunk * len(chunk_rows))(*[d.k for d in chunk_rows])
+            tarr = (_capi.MbvTurnChunk * len(turn_rows))(*[d.k for d in turn_rows])
+            tlimits = [d.lim for d in turn_rows]
             dev = net._device()
-            packed = None
+            packed, offs = None, [None] * len(rows)
             if host:
                 total, offs = pcm_chunks_plan(self.model_sr, self.rate, arr, self.res_type)
                 first_turn = total
-                t_total, toffs = turn_plan(self.model_sr, self.rate, tarr, self.res_type, tlimits) if trows else (0, [])
+                t_total, toffs = turn_plan(self.model_sr, self.rate, tarr, self.res_type, tlimits) if turn_rows else (0, [])
                 total += t_total                  # the turns' pieces lie behind the members' in the one buffer
+                offs = offs + [first_turn + o for o in toffs]
                 if self._packed is None or self._packed.shape[0] < total:
                     cap = max(2 * total, 1 << 16)
                     self._packed = torch.empty(cap, device=dev, dtype=self._dtype)
@@ -2063,54 +2066,41 @@ class PcmPool:
                     self._host_np = self._host.numpy()
                     self._event = torch.cuda.Event()
                 packed = self._packed
-            if rows:
+            if chunk_rows:                        # every chunk row of the tick in ONE call (two launches when some are limited)
                 net.resample_pcm16_chunks(arr, self.model_sr, self.rate, packed=packed, res_type=self.res_type,
-                                          limits=[w._lim for _, w, _, _ in rows], encoding=self.encoding,
-                                          fades=[w._fade for _, w, _, _ in rows],
-                                          envelopes=[w._env for _, w, _, _ in rows])
-            if trows:                             # every turn of the tick in ONE call
+                                          limits=[d.lim for d in chunk_rows], encoding=self.encoding,
+                                          fades=[d.fade for d in chunk_rows], envelopes=[d.env for d in chunk_rows])
+            if turn_rows:                         # every turn of the tick in ONE call
                 net.resample_turns(tarr, self.model_sr, self.rate, packed=packed[first_turn:] if host else None,
                                    res_type=self.res_type, limits=tlimits, encoding=self.encoding,
-                                   fades=[t._fade for t, _, _ in trows],
-                                   envelopes=[t._seg_envs for t, _, _ in trows])
+                                   fades=[d.fade for d in turn_rows], envelopes=[d.env for d in turn_rows])
             # the measuring members of the tick: the segments their frontier completed, in ONE launch
-            measuring = []
-            for _, w, k, _ in rows:
-                lk = _capi.MbvLoudnessChunk()
-                src = (k.wave, k.in_total, k.in_avail)
-                if getattr(w, "_warp", None) is not None:     # a pitched member is measured on its decoded row
-                    o, avail = w._measured(w._st._decoded - 1)
-                    src = (o.data_ptr(), o.shape[-1], avail)
-                k1 = _loudness_row(w, lk, *src) if w.loudness is not None else None
-                if k1 is not None:
-                    measuring.append((w, lk, k1))
+            measuring = [(m, lk) for m, due in rows if (lk := m._measure_row(due.k)) is not None]
             if measuring:
-                net.loudness_chunks([lk for _, lk, _ in measuring], self.model_sr)
-                for w, _, k1 in measuring:
-                    w._lseg = k1
-            for _, w, _, due in rows:
-                w._chunk_wired(*due)
-            for t, _, pieces in trows:
-                t._chunk_wired(pieces)
-            if host:
-                if total:
-                    with torch.cuda.device(dev):
-                        self._host[:total].copy_(packed[:total], non_blocking=True)
-                        self._event.record(torch.cuda.current_stream(dev))
-                        self._event.synchronize()
-                for (st, _, _, (_, pieces)), o in zip(rows, offs):
-                    first = pieces[0][0]
-                    out += [(st, a, self._host_np[o + a - first:o + b - first]) for a, b in pieces]
-                for (t, _, pieces), o in zip(trows, toffs):
-                    out += [(t, a, self._host_np[first_turn + o:first_turn + o + b - a]) for a, b in pieces]
-            else:
-                for st, w, _, (_, pieces) in rows:
-                    out += [(st, a, w.pcm[0, a:b]) for a, b in pieces]
-                for t, _, pieces in trows:
-                    out += [(t, a, t.pcm[0, a:b]) for a, b in pieces]
-        self.followers = [f for f in self.followers if f._wired < len(f._st.schedule)]
-        self.lives = [lw for lw in self.lives if not lw._plan.wire_done]
+                net.loudness_chunks([lk for _, lk in measuring], self.model_sr)
+                for m, lk in measuring:
+                    m._lseg = lk.seg_first + lk.seg_count
+            for m, due in rows:
+                m._chunk_wired(due.pieces, due.final)
+            if host and total:
+                with torch.cuda.device(dev):
+                    self._host[:total].copy_(packed[:total], non_blocking=True)
+                    self._event.record(torch.cuda.current_stream(dev))
+                    self._event.synchronize()
+            for (m, due), o in zip(rows, offs):   # a piece lies in the member's row, or in the pinned buffer from `o` on
+                first = due.pieces[0][0]
+                out += [(m._name, a, self._host_np[o + a - first:o + b - first] if host else m.pcm[0, a:b])
+                        for a, b in due.pieces]
+        self._drop_finished()
         return out
+
+    def _named(self, st):
+        """The member that `step(streams=)` names by `st`: a decode stream, a `LiveWire` or a `Turn` of this pool."""
+        for m in self._members:
+            if m._name is st:
+                return m
+        raise ValueError("step(streams=...) names a %s that is not in the pool"
+                         % (st._KIND if isinstance(st, _WireOut) else "stream"))
 
 
 def pcm_pool(net, pool, model_sr, rate, res_type="kaiser_best", encoding="pcm16"):

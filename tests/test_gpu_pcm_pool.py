@@ -10,6 +10,7 @@ import torch
 
 from mb_istft_vits_amd import _capi, synth, wire
 
+import test_gpu_live_wire as LW
 from gpu_util import make_net, ptr
 
 pytestmark = pytest.mark.gpu
@@ -512,3 +513,134 @@ def test_error_paths_launch_nothing_and_the_handle_serves_on():
     assert torch.equal(pa, refa) and torch.equal(pb, refb)
     assert torch.equal(packed[:2 * r], torch.cat([refa[0, 10:r], refb[0, :r], refa[0, :10]]))
     assert bool((packed[2 * r:] == SENTINEL).all())
+
+
+# ------------------------------------------------------------------------------------------------ every kind of member
+MIXED_SR, MIXED_RATE, MIXED_IN_SR = 22050, 24000, 48000
+MIXED_LIMITER = wire.Limiter(0.9, lookahead_ms=2.0, hold_ms=4.0)
+MIXED_PITCH = [1.0, 1.26, 1.26, 0.8, 0.8, 1.5, 1.0, 1.12, 0.9, 1.0, 2.0, 0.5, 1.0, 1.0]
+MIXED_GAIN = [1.0, 0.5, 0.5, 2.0, 2.0, 1.0, 0.0, 1.0, 3.0, 1.0, 1.0, 0.25, 1.0, 1.0]
+MIXED_PAUSE_MS = 80.0
+MIXED_KINDS = ("limited", "pitched", "measured", "live", "turn")
+
+
+def _mixed_text(net, T, seed, **kw):
+    x = torch.randint(1, 59, (T,), generator=torch.Generator().manual_seed(seed)).view(1, -1).cuda()
+    return net.infer_stream(x, torch.tensor([T]).cuda(), torch.tensor([seed % 4]).cuda(), noise_scale=0.5, length_scale=3.0,
+                            seed=[seed], chunk_frames=8, max_chunk_frames=16, **kw)
+
+
+def _mixed_streams(net):
+    """the decode streams of (a), (b), (c) and of the two segments of (e), from the same seeds every time"""
+    return dict(limited=_mixed_text(net, 12, 801), pitched=_mixed_text(net, 14, 802, pitch=[MIXED_PITCH], gain=[MIXED_GAIN]),
+                measured=_mixed_text(net, 9, 803),
+                turn=[_mixed_text(net, 8, 804), _mixed_text(net, 10, 805, gain=[MIXED_GAIN[:10]])])
+
+
+def _mixed_live(net, raw, noise):
+    """(d): a live wire that has its whole recording, closed"""
+    lw = LW._open(net, MIXED_IN_SR, MIXED_RATE, raw.dtype, noise)
+    lw.push(raw)
+    lw.close()
+    return lw
+
+
+def _mixed_turn(pp, segments):
+    turn = pp.add_turn(1 << 17)
+    turn.append(segments[0])
+    turn.append(segments[1], pause_ms=MIXED_PAUSE_MS)
+    turn.close()
+    return turn
+
+
+def _state(w):
+    valid, loudness = int(w.valid_samples[0]), getattr(w, "loudness", None)     # (a turn keeps no running loudness)
+    return dict(pcm=w.pcm[:, :valid].clone(), valid=w.valid_samples.clone(), peak=w.peak.clone(),
+                loudness=None if loudness is None else loudness.clone())
+
+
+def _mixed_alone(net, raw, noise):
+    """every member driven alone -> {kind: (its concatenated pieces, its final state)}"""
+    sts, want = _mixed_streams(net), {}
+    for kind, kw in (("limited", dict(limiter=MIXED_LIMITER)), ("pitched", {}),
+                     ("measured", dict(loudness=wire.Loudness(target=None)))):
+        f = wire.stream_pcm16(net, sts[kind], MIXED_SR, MIXED_RATE, **kw)
+        pieces = [v[0].clone() for _, v in f]
+        assert len(pieces) >= 3, (kind, len(pieces))                          # several ticks each
+        want[kind] = (torch.cat(pieces), _state(f))
+    lw, pieces = _mixed_live(net, raw, noise), []
+    while not lw.finished:
+        pieces += [v.clone() for _, v in lw.poll()]
+    want["live"] = (torch.cat(pieces), _state(lw))
+    pp = wire.pcm_pool(net, net.stream_pool(), MIXED_SR, MIXED_RATE)
+    turn, pieces = _mixed_turn(pp, sts["turn"]), []
+    while not turn.finished:
+        pieces += [p.clone() for _, _, p in pp.step()]
+    assert len(pp) == 0 and len(pp.pool) == 0
+    want["turn"] = (torch.cat(pieces), _state(turn))
+    return want
+
+
+def _mixed_pooled(net, raw, noise, host):
+    """all five in ONE pool, driven to the end -> ({kind: ([(first, piece)], final state)}, the launches of the first
+    tick in which all five had something due)"""
+    sts = _mixed_streams(net)
+    sp = net.stream_pool()
+    pp = wire.pcm_pool(net, sp, MIXED_SR, MIXED_RATE)
+    turn = _mixed_turn(pp, sts["turn"])                                       # (the turn first: `out` is ordered by kind)
+    lw = pp.add_live(_mixed_live(net, raw, noise))
+    members = dict(measured=pp.add(sts["measured"], loudness=wire.Loudness(target=None)),
+                   pitched=pp.add(sts["pitched"]), limited=pp.add(sts["limited"], limiter=MIXED_LIMITER), live=lw, turn=turn)
+    assert len(pp) == 5 and pp.followers == [members[k] for k in ("measured", "pitched", "limited")]
+    assert pp.lives == [lw] and pp.turns == [turn] and members["pitched"]._warp is not None
+    kind_of = {id(sts[k]): k for k in ("limited", "pitched", "measured")}
+    kind_of.update({id(lw): "live", id(turn): "turn"})
+    pieces, full_tick, ticks = {k: [] for k in MIXED_KINDS}, None, 0
+    while len(pp):
+        before = wire.wire_runs(net), net.warp_runs(), net.loudness_runs()
+        out = pp.step(host=host)
+        after = wire.wire_runs(net), net.warp_runs(), net.loudness_runs()
+        kinds = [kind_of[id(who)] for who, _, _ in out]
+        order = [k for k in ("measured", "pitched", "limited", "live", "turn") if k in kinds]
+        assert [k for i, k in enumerate(kinds) if k not in kinds[:i]] == order, kinds     # followers, live wires, turns
+        if full_tick is None and set(kinds) == set(MIXED_KINDS):
+            full_tick = tuple(b - a for a, b in zip(before, after))
+        for who, a, piece in out:
+            pieces[kind_of[id(who)]].append((a, torch.from_numpy(piece.copy()).cuda() if host else piece.clone()))
+        ticks += 1
+        assert ticks < 100
+    assert len(pp) == 0 and len(sp) == 0 and pp.step() == []
+    return {k: (pieces[k], _state(members[k])) for k in MIXED_KINDS}, full_tick
+
+
+@pytest.mark.timeout(600)
+def test_every_kind_of_member_in_one_pool_is_bitwise_the_member_alone():
+    """A limited follower, a pitched and shaped one, a measuring one, a live wire and a turn of two segments in ONE
+    `PcmPool`: every member's pieces, `pcm`, `valid_samples`, `peak` and `.loudness` are bitwise those of the member
+    driven alone, on the device and through the pinned host buffer, and a tick that serves all five makes three wire
+    launches (unlimited rows, limited rows, turn rows), one warp launch and at most one loudness launch."""
+    net = _net("uudb_ms_istft_vits_ms")
+    raw = LW._audio(LW._raw_len(257, 1, MIXED_IN_SR), 61, MIXED_IN_SR, True).cuda()
+    noise = LW._noise(net, 161, MIXED_IN_SR)
+    alone = _mixed_alone(net, raw, noise)
+    assert alone["measured"][1]["loudness"] is not None and bool(torch.isfinite(alone["measured"][1]["loudness"]).all())
+    runs = {}
+    for host in (False, True):
+        got, full_tick = _mixed_pooled(net, raw, noise, host)
+        print("host=%s: pieces per member %s, launches of the full tick (wire, warp, loudness) %s"
+              % (host, {k: len(got[k][0]) for k in MIXED_KINDS}, full_tick))
+        assert full_tick is not None and full_tick[0] == 3 and full_tick[1] == 1 and full_tick[2] <= 1, full_tick
+        for kind in MIXED_KINDS:
+            (want_pieces, want), (pieces, state) = alone[kind], got[kind]
+            assert [a for a, _ in pieces] == [sum(len(p) for _, p in pieces[:i]) for i in range(len(pieces))], kind
+            assert torch.equal(torch.cat([p for _, p in pieces]), want_pieces), (kind, host)
+            assert int(want["valid"][0]) > 0 and torch.equal(state["valid"], want["valid"]), (kind, host)
+            assert torch.equal(state["pcm"], want["pcm"]), (kind, host)
+            assert torch.equal(state["peak"].view(torch.int32), want["peak"].view(torch.int32)), (kind, host)
+            assert (state["loudness"] is None) == (want["loudness"] is None), kind
+            if want["loudness"] is not None:
+                assert torch.equal(state["loudness"].view(torch.int32), want["loudness"].view(torch.int32)), (kind, host)
+        runs[host] = got
+    for kind in MIXED_KINDS:                                                  # the host pieces are the device pieces
+        dev, hst = runs[False][kind][0], runs[True][kind][0]
+        assert len(dev) == len(hst) and all(a == b and torch.equal(p, q) for (a, p), (b, q) in zip(dev, hst)), kind

@@ -333,6 +333,47 @@ int64_t mbv_encoder_runs(mbv_model *m);
  * out fp32 [B, gin] */
 int mbv_speaker_embedding(mbv_model *m, const int64_t *sid, int B, float *out, void *stream);
 
+/* ---- blended voices: virtual speakers behind the embedding table (no reference counterpart) -------------------------
+ * A voice is defined once into slot j and is from then on the speaker id n_speakers + j wherever a speaker id is taken
+ * (host ints and device int64 tensors alike, mixed with plain ids at will); an id >= n_speakers whose slot is not
+ * defined is refused or flagged exactly like any other id outside the table.  The model consumes a speaker only as its
+ * row g [gin]; a voice's row is
+ *   a blend   acc = weights[0] * emb_g[ids[0]][c], then acc = fmaf(weights[k], emb_g[ids[k]][c], acc) for
+ *             k = 1 .. count - 1 in that order, all fp32: this order is part of the contract, so a one-hot blend is
+ *             bitwise the table row; ids name real speakers only (0 <= id < n_speakers, no blends of blends); or
+ *   a vector  the gin floats at `vector` (DEVICE), copied in stream order: a row made elsewhere.
+ * Rows live in a buffer of the model outside the weight arena: mbv_export_arena / mbv_import_arena do not carry them.
+ * After mbv_finalize_weights or mbv_import_arena every blend is recomputed from the new table in one launch; a vector
+ * voice stays as given.  MBV_SPEAKER_SLOTS and MBV_BLEND_MAX are conventions of this build, not properties of the
+ * model: a slot costs one row of gin floats, a term one id and one weight.
+ *
+ * mbv_speakers_define   n definitions (HOST array) in ONE blend launch.  Checked on the host, and refused before
+ *                       anything is launched, the message naming the definition: n outside [1, MBV_SPEAKER_SLOTS], a
+ *                       slot outside [0, MBV_SPEAKER_SLOTS) or named twice, count outside [1, MBV_BLEND_MAX] (with
+ *                       vector == NULL), an id outside [0, n_speakers), a weight that is not finite; a model without a
+ *                       speaker table.  A defined slot may be defined again: the new row replaces the old one in
+ *                       stream order.  No synchronisation after the first call (which allocates the buffers).
+ * mbv_speaker_release   the slot is undefined again (host at once, device in stream order); refuses a slot outside the
+ *                       range or not defined.
+ * mbv_speaker_slots     MBV_SPEAKER_SLOTS of the library.
+ * mbv_speaker_defined   1: sid >= n_speakers names a defined voice; 0: it does not (real speakers included); -1: m NULL.
+ * mbv_speaker_runs      blend launches since mbv_create (one per mbv_speakers_define, one per weight refresh with a
+ *                       blend defined); -1: m NULL. */
+#define MBV_SPEAKER_SLOTS 256
+#define MBV_BLEND_MAX 16
+typedef struct mbv_speaker_def {
+  int32_t slot;
+  int32_t count;                 /* terms of the blend; ignored with `vector` */
+  int32_t ids[MBV_BLEND_MAX];
+  float weights[MBV_BLEND_MAX];
+  const float *vector;           /* DEVICE [gin] or NULL */
+} mbv_speaker_def;
+int mbv_speakers_define(mbv_model *m, const mbv_speaker_def *defs, int n, void *stream);
+int mbv_speaker_release(mbv_model *m, int slot, void *stream);
+int mbv_speaker_slots(void);
+int mbv_speaker_defined(mbv_model *m, int64_t sid);
+int64_t mbv_speaker_runs(mbv_model *m);
+
 /* ---- run-time options (no reference counterpart) ------------------------------
  *   "splitk"       1: split the input-channel loop of conv launches that leave most of the chip
  *                  idle over several workgroups (single-utterance latency: ljs_mb batch 1

@@ -48,6 +48,7 @@ SYMBOLS = [
     "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
     "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped", "mbv_resample_turns_shaped",
     "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
+    "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined", "mbv_speaker_runs",
 ]
 
 
@@ -155,6 +156,15 @@ class MbvWarpRow(C.Structure):
 
 
 PITCH_MIN, PITCH_MAX = 0.5, 2.0     # MBV_PITCH_MIN / MBV_PITCH_MAX
+
+
+SPEAKER_SLOTS, BLEND_MAX = 256, 16  # MBV_SPEAKER_SLOTS / MBV_BLEND_MAX
+
+
+class MbvSpeakerDef(C.Structure):
+    """mbv_speaker_def of include/mbistft_vits.h (mbv_speakers_define); vector None = a blend of `count` terms."""
+    _fields_ = [("slot", C.c_int32), ("count", C.c_int32), ("ids", C.c_int32 * BLEND_MAX),
+                ("weights", C.c_float * BLEND_MAX), ("vector", C.c_void_p)]
 
 
 def fit_result(word):
@@ -364,7 +374,7 @@ def lib():
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
     # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
-    # turns' two, prosody's four, volume's seven and pitch's four may be absent there, and calling one then raises AttributeError.
+    # turns' two, prosody's four, volume's seven, pitch's four and the voices' five may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -388,7 +398,9 @@ def lib():
                 "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
                 "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped",
                 "mbv_resample_turns_shaped",
-                "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
+                "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined",
+                "mbv_speaker_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -516,6 +528,13 @@ def lib():
         L.mbv_warp_ranges.argtypes = [vp, C.POINTER(MbvWarpRow), i32, vp]
         L.mbv_warp_runs.argtypes = [vp]
         L.mbv_warp_runs.restype = C.c_int64
+    if hasattr(L, "mbv_speakers_define") or not optional:
+        L.mbv_speakers_define.argtypes = [vp, C.POINTER(MbvSpeakerDef), i32, vp]
+        L.mbv_speaker_release.argtypes = [vp, i32, vp]
+        L.mbv_speaker_slots.argtypes = []
+        L.mbv_speaker_defined.argtypes = [vp, C.c_int64]
+        L.mbv_speaker_runs.argtypes = [vp]
+        L.mbv_speaker_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

@@ -28,6 +28,8 @@ constexpr int kFlowK = 5;
 constexpr int kNFlows = 4;
 constexpr float kLrelu = 0.1f;    // modules.py:17
 
+static_assert(kVoiceSlots == MBV_SPEAKER_SLOTS && kBlendMax == MBV_BLEND_MAX, "the header states the kernels' conventions");
+
 thread_local std::string g_create_error;
 
 struct HostTensor {
@@ -147,6 +149,21 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
   int64_t warp_runs = 0;           // launches of the time-warp kernel (mbv_warp_runs)
   float* warp_win[2] = {nullptr, nullptr};   // filter -> fp32 window and its differences on the device (mbv_warp_ranges)
+  // blended voices (mbv_speakers_define): the rows, the defined words and the definition table on the device, all
+  // allocated by the first definition and outside the weight arena; `voices` is every slot's host copy
+  struct Voice { bool defined = false, vector = false; VoiceDef def{}; };
+  std::vector<Voice> voices;       // empty until the first definition, then kVoiceSlots entries
+  float* voice_rows = nullptr;     // [kVoiceSlots][gin]
+  int* voice_defined = nullptr;    // [kVoiceSlots]
+  VoiceDef* voice_defs = nullptr;  // [kVoiceSlots], the table of the launch in flight
+  int64_t speaker_runs = 0;        // launches of the blend kernel (mbv_speaker_runs)
+  // the second table of every emb_g gather: empty until a voice was defined
+  VoiceTable voice_table() const { return VoiceTable{voice_rows, voice_defined, voice_rows ? kVoiceSlots : 0}; }
+  // a speaker id a host-side check accepts: a row of emb_g or a defined voice
+  bool speaker_ok(long long sid) const {
+    const long long ns = cfg.n_speakers;
+    return sid >= 0 && (sid < ns || (sid - ns < (long long)voices.size() && voices[(size_t)(sid - ns)].defined));
+  }
   int64_t noise_runs = 0;          // mbv_randn_blocks launches (mbv_noise_runs)
   int64_t loudness_runs = 0;       // launches of the loudness kernel (mbv_loudness_runs)
   std::map<int, LoudnessParams> loudness_params;    // rate -> K-weighting tables (built once a rate, host only)
@@ -215,6 +232,39 @@ int ensure_split_arena(mbv_model* m, hipStream_t stream) {
   HIPCHK(m, hipStreamSynchronize(stream));
   m->split_valid = true;
   return 0;
+}
+
+// Blended voices: the validated definitions go up as a table and ONE launch writes their rows (ops.hip
+// speaker_blend_kernel).  The buffers exist from the first definition on.
+int blend_voices(mbv_model* m, const std::vector<VoiceDef>& defs, hipStream_t s) {
+  if (defs.empty()) return 0;
+  const int gin = m->cfg.gin_channels;
+  if (!m->voice_rows) {
+    float* rows = nullptr; int* defined = nullptr; VoiceDef* tab = nullptr;
+    if (hipMalloc((void**)&rows, (size_t)kVoiceSlots * gin * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&defined, kVoiceSlots * sizeof(int)) != hipSuccess ||
+        hipMalloc((void**)&tab, kVoiceSlots * sizeof(VoiceDef)) != hipSuccess ||
+        hipMemsetAsync(rows, 0, (size_t)kVoiceSlots * gin * sizeof(float), s) != hipSuccess ||
+        hipMemsetAsync(defined, 0, kVoiceSlots * sizeof(int), s) != hipSuccess) {
+      if (rows) (void)hipFree(rows);
+      if (defined) (void)hipFree(defined);
+      if (tab) (void)hipFree(tab);
+      return m->fail("hipMalloc of the voice table failed");
+    }
+    m->voice_rows = rows; m->voice_defined = defined; m->voice_defs = tab;
+  }
+  upload_rows<kVoiceChunk>(defs.size(), m->voice_defs, s, [&](size_t i) { return defs[i]; });
+  launch_speaker_blend(m->voice_defs, (int)defs.size(), m->W(m->emb_g.off), m->voice_rows, m->voice_defined, gin, s);
+  ++m->speaker_runs;
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+// after a weight refresh: every blend again from the new table, in one launch (vector voices stay as given)
+int reblend_voices(mbv_model* m, hipStream_t s) {
+  std::vector<VoiceDef> defs;
+  for (const auto& v : m->voices)
+    if (v.defined && !v.vector) defs.push_back(v.def);
+  return blend_voices(m, defs, s);
 }
 
 // Every entry point runs on the model's device and hands the caller's current device back on
@@ -954,7 +1004,7 @@ int do_finalize(mbv_model* m, hipStream_t stream) {
   m->finalized = true;
   m->split_valid = false;
   if (m->conv_bf16 == 3 && ensure_split_arena(m, stream)) return 1;
-  return 0;
+  return reblend_voices(m, stream);
 }
 
 // ------------------------------------------------------------------ scratch
@@ -2036,6 +2086,9 @@ void mbv_destroy(mbv_model* m) {
   if (m->scrA) (void)hipFree(m->scrA);
   if (m->scrB) (void)hipFree(m->scrB);
   if (m->noise_tab) (void)hipFree(m->noise_tab);
+  if (m->voice_rows) (void)hipFree(m->voice_rows);
+  if (m->voice_defined) (void)hipFree(m->voice_defined);
+  if (m->voice_defs) (void)hipFree(m->voice_defs);
   for (auto& sl : m->slots)
     if (sl.scr) (void)hipFree(sl.scr);
   if (m->user_tab) (void)hipFree(m->user_tab);
@@ -2128,10 +2181,75 @@ int mbv_speaker_embedding(mbv_model* m, const int64_t* sid, int B, float* out, v
   if (!m->emb_g.present) return m->fail("model has no speaker embedding (n_speakers <= 1)");
   DEVICE_GUARD(m);
   launch_gather_rows(m->W(m->emb_g.off), sid, out, B, m->cfg.gin_channels, m->cfg.n_speakers, nullptr,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, m->voice_table());
   HIPCHK(m, hipGetLastError());
   return 0;
 }
+
+int mbv_speakers_define(mbv_model* m, const mbv_speaker_def* defs, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_speakers_define";
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!m->emb_g.present) return m->fail("model has no speaker embedding (n_speakers <= 1)");
+  if (!defs || n < 1 || n > kVoiceSlots) return m->fail("%s: needs 1 .. %d definitions, got %d", who, kVoiceSlots, n);
+  const int ns = m->cfg.n_speakers;
+  std::vector<VoiceDef> rows((size_t)n);
+  std::vector<char> seen(kVoiceSlots, 0);
+  for (int i = 0; i < n; ++i) {
+    const mbv_speaker_def& k = defs[i];
+    if (k.slot < 0 || k.slot >= kVoiceSlots)
+      return m->fail("%s: definition %d: slot %d outside [0, %d)", who, i, k.slot, kVoiceSlots);
+    if (seen[k.slot]) return m->fail("%s: definition %d: slot %d is named twice", who, i, k.slot);
+    seen[k.slot] = 1;
+    VoiceDef& r = rows[i];
+    r = VoiceDef{};
+    r.slot = k.slot;
+    r.vector = k.vector;
+    if (k.vector) continue;
+    if (k.count < 1 || k.count > kBlendMax)
+      return m->fail("%s: definition %d: %d terms outside [1, %d]", who, i, k.count, kBlendMax);
+    r.count = k.count;
+    for (int j = 0; j < k.count; ++j) {
+      if (k.ids[j] < 0 || k.ids[j] >= ns)
+        return m->fail("%s: definition %d: term %d: speaker id %d outside [0, %d) (a blend names real speakers only)",
+                       who, i, j, k.ids[j], ns);
+      if (!std::isfinite(k.weights[j])) return m->fail("%s: definition %d: term %d: the weight is not finite", who, i, j);
+      r.ids[j] = k.ids[j];
+      r.weights[j] = k.weights[j];
+    }
+  }
+  DEVICE_GUARD(m);
+  if (blend_voices(m, rows, (hipStream_t)stream)) return 1;
+  if (m->voices.empty()) m->voices.resize(kVoiceSlots);
+  for (const VoiceDef& r : rows) {
+    mbv_model::Voice& v = m->voices[r.slot];
+    v.defined = true;
+    v.vector = r.vector != nullptr;
+    v.def = r;
+    v.def.vector = nullptr;             // the row was copied: the caller's buffer is not kept
+  }
+  return 0;
+}
+
+int mbv_speaker_release(mbv_model* m, int slot, void* stream) {
+  if (!m) return 1;
+  if (slot < 0 || slot >= kVoiceSlots) return m->fail("mbv_speaker_release: slot %d outside [0, %d)", slot, kVoiceSlots);
+  if ((size_t)slot >= m->voices.size() || !m->voices[slot].defined)
+    return m->fail("mbv_speaker_release: slot %d is not defined", slot);
+  DEVICE_GUARD(m);
+  HIPCHK(m, hipMemsetAsync(m->voice_defined + slot, 0, sizeof(int), (hipStream_t)stream));
+  m->voices[slot] = mbv_model::Voice{};
+  return 0;
+}
+
+int mbv_speaker_slots(void) { return kVoiceSlots; }
+
+int mbv_speaker_defined(mbv_model* m, int64_t sid) {
+  if (!m) return -1;
+  return sid >= m->cfg.n_speakers && m->speaker_ok(sid) ? 1 : 0;
+}
+
+int64_t mbv_speaker_runs(mbv_model* m) { return m ? m->speaker_runs : -1; }
 
 namespace {
 // DDSConv (modules.py:98-111) on x [B, C, T] in place; t1, t2: scratch of the same size
@@ -2302,7 +2420,7 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   m->has_g = c.n_speakers > 0;
   const float* cadd = nullptr;
   if (m->has_g) {
-    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad, s);
+    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad, s, m->voice_table());
     if (m->dp_cw.present) {
       launch_cond_gemv(m->gvec, nullptr, nullptr, m->W(m->dp_cw.off), m->W(m->dp_cb.off), dpc, B, gin, H, s);
       cadd = dpc;
@@ -3020,8 +3138,8 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   m->stages.clear();
 
   launch_lens_to_i32(y_lengths, lens, B, T, bad, s);
-  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, bad, s);
-  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, bad, s);
+  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, bad, s, m->voice_table());
+  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, bad, s, m->voice_table());
   if (status) HIPCHK(m, hipMemcpyAsync(status, bad, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (run_enc_q(m, y, lens, g_src, noise, 1.f, pb, zbuf, B, T, s)) return 1;
   // forward flow with the source speaker (models.py:795), then reverse with the target (:796)
@@ -3089,7 +3207,7 @@ int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const fl
   run_text_encoder(m, ids, lengths, te, bad_x, B, T, s);
   const float* g = nullptr;
   if (c.n_speakers > 0) {
-    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad_x, s);
+    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad_x, s, m->voice_table());
     g = m->gvec;
   }
   launch_lens_to_i32(y_lengths, ylens, B, Tp, bad_y, s);
@@ -4629,8 +4747,8 @@ int convert_row_refusal(mbv_model* m, const char* who, int i, int wave_dtype, in
   const int ns = m->cfg.n_speakers;
   if (wave_dtype != MBV_WAVE_F32 && wave_dtype != MBV_WAVE_PCM16)
     return m->fail("%s: row %d: unknown wave_dtype %d", who, i, wave_dtype);
-  if (sid_src < 0 || sid_src >= ns || sid_tgt < 0 || sid_tgt >= ns)
-    return m->fail("%s: row %d: speaker id outside [0, %d)", who, i, ns);
+  if (!m->speaker_ok(sid_src) || !m->speaker_ok(sid_tgt))
+    return m->fail("%s: row %d: speaker id outside [0, %d) and no defined voice", who, i, ns);
   if (!(noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
   return 0;
 }
@@ -4677,8 +4795,8 @@ int run_posterior_rows(mbv_model* m, const char* who, const std::vector<ConvertR
   upload_rows<kAdmitChunk>(B, crows, s, [&](size_t i) { return crows_h[i]; }, ConvertRowCols{lens, sid_src, sid_tgt});
   upload_rows<kAdmitChunk>(B, srows, s, [&](size_t i) { return srows_h[i]; });
   ++m->converter_runs;
-  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s);
-  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s);
+  launch_gather_rows(m->W(m->emb_g.off), sid_src, g_src, B, gin, c.n_speakers, nullptr, s, m->voice_table());
+  launch_gather_rows(m->W(m->emb_g.off), sid_tgt, g_tgt, B, gin, c.n_speakers, nullptr, s, m->voice_table());
   launch_spectrogram_rows(crows, B, n_fft, hop, tab->tw, tab->win, pb.ypad, m->encq.cin_pad, T, s);
   if (run_enc_q(m, nullptr, lens, g_src, nullptr, 1.f, pb, z, B, T, s, srows, route_T)) return 1;
   if (int rc = run_flows(m, false, z, g_src, pb, lens, B, T, s, route_T)) return rc;

@@ -336,8 +336,32 @@ void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* r
 // out[b][co] = bias[co] + sum_ci W[co][ci] * g[b][ci]   (g = table[sid[b]] if sid)
 void launch_cond_gemv(const float* g, const float* table, const int64_t* sid, const float* W,
                       const float* bias, float* out, int B, int Cin, int Cout, hipStream_t s);
+// Blended speakers ("voices"): a second table behind the embedding table.  Voice slot j is speaker id n_rows + j once
+// defined[j] is set; both sizes are conventions, not limits of the kernels (a slot costs one row of C floats, a
+// term one id and one weight in the definition).
+constexpr int kVoiceSlots = 256;   // MBV_SPEAKER_SLOTS
+constexpr int kBlendMax = 16;      // MBV_BLEND_MAX
+struct VoiceTable {                // all zero: no second table
+  const float* rows = nullptr;     // [slots][C]
+  const int* defined = nullptr;    // [slots], written in stream order
+  int slots = 0;
+};
+// A table row (upload_rows): one definition.  vector != null: that ready row [C] (count, ids, weights unused).
+struct VoiceDef {
+  int slot, count;
+  int ids[kBlendMax];
+  float weights[kBlendMax];
+  const float* vector;
+};
+constexpr int kVoiceChunk = 24;    // rows per upload_rows launch: 24 x 144 bytes = 3.4 KiB of kernel arguments
+// out[b] = table[sid[b]] for 0 <= sid[b] < n_rows, voices.rows[sid[b] - n_rows] for a defined voice; anything else
+// sets bad[b] (where given) and reads row 0
 void launch_gather_rows(const float* table, const int64_t* sid, float* out, int B, int C,
-                        int n_rows, int* bad, hipStream_t s);
+                        int n_rows, int* bad, hipStream_t s, VoiceTable voices = VoiceTable{});
+// rows[defs[v].slot] = the blend (fp32, ascending k: w_0 e_0, then fmaf) or the ready row of definition v < n, and
+// defined[defs[v].slot] = 1: ONE launch, grid (channel tiles, n).  defs is a device table (upload_rows).
+void launch_speaker_blend(const VoiceDef* defs, int n, const float* table, float* rows, int* defined, int C,
+                          hipStream_t s);
 
 // ---------------------------------------------------------------- fused iSTFT + PQMF
 struct IstftArgs {

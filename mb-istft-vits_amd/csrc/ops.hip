@@ -587,23 +587,57 @@ void launch_cond_gemv(const float* g, const float* table, const int64_t* sid, co
   hipLaunchKernelGGL(cond_gemv_kernel, grid, dim3(128), 0, s, g, table, sid, W, bias, out, Cin, Cout);
 }
 
+// Row r < n_rows is table[r]; row n_rows + j of a defined voice slot j < voices.slots is voices.rows[j] (the blended
+// speakers, below); every other id is flagged in `bad` and reads row 0.
 __global__ void gather_rows_kernel(const float* table, const int64_t* sid, float* out, int C,
-                                   int n_rows, int* bad) {
+                                   int n_rows, int* bad, const VoiceTable voices) {
   const int b = blockIdx.y;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  long long r = sid[b];
-  if (r < 0 || r >= n_rows) {
-    if (bad && c == 0) bad[b] = 1;
-    r = 0;
+  const long long r = sid[b];
+  const float* src = table;
+  if (r >= 0 && r < n_rows) {
+    src = table + r * C;
+  } else if (r >= n_rows && r - n_rows < voices.slots && voices.defined[r - n_rows]) {
+    src = voices.rows + (r - n_rows) * C;
+  } else if (bad && c == 0) {
+    bad[b] = 1;
   }
-  out[(int64_t)b * C + c] = table[r * C + c];
+  out[(int64_t)b * C + c] = src[c];
 }
 
 void launch_gather_rows(const float* table, const int64_t* sid, float* out, int B, int C,
-                        int n_rows, int* bad, hipStream_t s) {
+                        int n_rows, int* bad, hipStream_t s, VoiceTable voices) {
   dim3 grid((C + 127) / 128, B);
-  hipLaunchKernelGGL(gather_rows_kernel, grid, dim3(128), 0, s, table, sid, out, C, n_rows, bad);
+  hipLaunchKernelGGL(gather_rows_kernel, grid, dim3(128), 0, s, table, sid, out, C, n_rows, bad, voices);
+}
+
+// ---------------------------------------------------------------------------
+// Blended speakers: block (x, v) writes channels [128 x, 128 x + 128) of voice defs[v] to rows[defs[v].slot] and
+// marks the slot defined.  A ready row is copied; a blend is the fp32 chain acc = w_0 e_0[c], then
+// acc = fmaf(w_k, e_k[c], acc) for k = 1 .. count - 1 in ascending k, e_k = table[ids[k]]: a one-hot blend is
+// bitwise its table row.  The host has checked slot, count and ids (capi.hip); two definitions never share a slot.
+// ---------------------------------------------------------------------------
+__global__ void speaker_blend_kernel(const VoiceDef* __restrict__ defs, const float* __restrict__ table,
+                                     float* __restrict__ rows, int* __restrict__ defined, int C) {
+  const VoiceDef& d = defs[blockIdx.y];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float acc;
+  if (d.vector) {
+    acc = d.vector[c];
+  } else {
+    acc = d.weights[0] * table[(int64_t)d.ids[0] * C + c];
+    for (int k = 1; k < d.count; ++k) acc = fmaf(d.weights[k], table[(int64_t)d.ids[k] * C + c], acc);
+  }
+  rows[(int64_t)d.slot * C + c] = acc;
+  if (c == 0) defined[d.slot] = 1;
+}
+
+void launch_speaker_blend(const VoiceDef* defs, int n, const float* table, float* rows, int* defined, int C,
+                          hipStream_t s) {
+  dim3 grid((C + 127) / 128, n);
+  hipLaunchKernelGGL(speaker_blend_kernel, grid, dim3(128), 0, s, defs, table, rows, defined, C);
 }
 
 __global__ void unscale_xpost_kernel(const float* src, float* dst, int rows, int F, int64_t n) {

@@ -420,12 +420,127 @@ def _row_seeds(seed, B, what="seed"):
     return RowSeeds((s, b) for b in range(B))
 
 
+SPEAKER_SLOTS, BLEND_MAX = _capi.SPEAKER_SLOTS, _capi.BLEND_MAX     # conventions of the library, DESIGN 7.24
+
+
+def blend_weights(weights, normalize=True):
+    """The fp32 weights a blended voice is defined with (`net.speaker`), as a list of Python floats that are exactly
+    representable in fp32.  `normalize`: every weight divided by their float64 sum, then rounded to fp32 (needs a sum
+    > 0); else the weights as given, rounded to fp32 (extrapolation such as [1.5, -0.5]).  ValueError: no weight, more
+    than BLEND_MAX, a weight that is not finite (before or after rounding), a sum <= 0 under `normalize`."""
+    if torch.is_tensor(weights):
+        weights = weights.detach().reshape(-1).tolist()
+    w = np.asarray(list(weights), dtype=np.float64).reshape(-1)
+    if not 1 <= w.size <= BLEND_MAX:
+        raise ValueError("a blend takes 1 .. %d weights, got %d" % (BLEND_MAX, w.size))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("blend weights must be finite, got %s" % (w.tolist(),))
+    if normalize:
+        total = float(np.sum(w))
+        if not total > 0:
+            raise ValueError("normalize=True needs weights with a sum > 0 (got %r); normalize=False sends them as given"
+                             % total)
+        w = w / total
+    with np.errstate(over="ignore"):
+        w32 = w.astype(np.float32)
+    if not np.all(np.isfinite(w32)):
+        raise ValueError("a blend weight is beyond fp32")
+    return [float(v) for v in w32]
+
+
+class SpeakerSlots:
+    """The voice slots of one model, on the host: `take()` hands out the lowest free slot, `free(slot)` returns one."""
+
+    def __init__(self, n=SPEAKER_SLOTS):
+        self.n = int(n)
+        self._used = set()
+
+    def take(self):
+        for j in range(self.n):
+            if j not in self._used:
+                self._used.add(j)
+                return j
+        raise ValueError("all %d voice slots are taken: release() a voice first" % self.n)
+
+    def free(self, slot):
+        if slot not in self._used:
+            raise ValueError("voice slot %r is not taken" % (slot,))
+        self._used.remove(slot)
+
+    def __contains__(self, slot):
+        return slot in self._used
+
+    def __len__(self):
+        return len(self._used)
+
+
+class Speaker:
+    """A voice of `net.speaker` / `net.speakers`: a virtual speaker behind the embedding table.
+
+      sid       the int that names it wherever a speaker id goes, n_speakers + its slot; put it into sid tensors
+      ids, weights    the definition: real speaker ids and the fp32 weights actually sent (None for a vector voice)
+      row()     its row [gin] on the device, through `mbv_speaker_embedding`
+      release() frees the slot; refused (ValueError) while an open `LiveStream` converts with it
+    The object itself goes wherever a host speaker id goes (`Request.sid`, `ConvertRequest`, `convert_stream`,
+    `convert_live`, the wire converts) and, standing for a one-element tensor, wherever a sid tensor goes; a released
+    one raises ValueError there."""
+
+    def __init__(self, net, slot, ids, weights, vector):
+        self._net = weakref.ref(net)
+        self.slot = slot
+        self._sid = net.n_speakers + slot
+        self.ids = None if ids is None else tuple(ids)
+        self.weights = None if weights is None else tuple(weights)
+        self._vector = vector                 # the row of a vector voice: what a re-created handle is given again
+        self.released = False
+
+    @property
+    def sid(self):
+        if self.released:
+            raise ValueError("%r was released: its slot may name another voice by now" % (self,))
+        return self._sid
+
+    def __index__(self):
+        return self.sid
+
+    __int__ = __index__
+
+    def _owner(self):
+        net = self._net()
+        if net is None:
+            raise ValueError("the model of %r is gone" % (self,))
+        return net
+
+    def row(self):
+        net = self._owner()
+        return net._speaker_embedding(torch.tensor([self.sid], dtype=torch.int64))[0]
+
+    def release(self):
+        if not self.released:
+            self._owner()._release_speaker(self)
+
+    def __repr__(self):
+        what = "vector" if self.ids is None else "ids=%s, weights=%s" % (list(self.ids), list(self.weights))
+        return "Speaker(sid=%d, %s%s)" % (self._sid, what, ", released" if self.released else "")
+
+
+def _host_sid(sid):
+    """A host speaker id as the entries take it: a `Speaker` gives its int (ValueError once released), anything else
+    passes."""
+    return sid.sid if isinstance(sid, Speaker) else sid
+
+
+def _sid_tensor(sid):
+    """A sid tensor as the entries take it: a `Speaker` stands for the one-element tensor of its id."""
+    return torch.tensor([sid.sid], dtype=torch.int64) if isinstance(sid, Speaker) else sid
+
+
 class Request:
     """One utterance of a pooled admission (`SynthesizerTrn.infer_streams`, `StreamPool.admit`, `PcmPool.admit`): the
     arguments one `infer_stream` call takes, for one text.
 
       x                  1-D token ids (tensor on either device, or a sequence of ints); at least one
-      sid                speaker id (an int; required by a multi-speaker model), or None
+      sid                speaker id (an int, or a `Speaker`; required by a multi-speaker model), or None
       noise_scale, length_scale, noise_scale_w, max_len       as `infer`
       chunk_frames, max_chunk_frames                          as `dec_stream`
       durations          frames per token, [T_text] (or [1, T_text] / [1, 1, T_text]), as `infer(durations=)`:
@@ -471,6 +586,7 @@ class Request:
             raise ValueError("Request: pitch_glide_frames must be >= 0")
         if pitch is not None:
             length_scale = _pitch_scale("Request", self.pitch, length_scale, durations, pitch_compensate)
+        sid = _host_sid(sid)
         if sid is not None:
             if torch.is_tensor(sid):
                 if sid.numel() != 1:
@@ -526,7 +642,7 @@ class ConvertRequest:
 
       wave               1-D int16 (scaled by 1 / 32768, as data_utils.py:75 does) or fp32 samples at `in_sr`, on either
                          device; at least one
-      sid_src, sid_tgt   speaker ids (ints)
+      sid_src, sid_tgt   speaker ids (ints, or `Speaker`s)
       model_sr, hop_size, win_size      the model's data config (sampling_rate, hop_length, win_length)
       in_sr              the rate of `wave`; None = model_sr
       noise_scale        scale of the posterior draw (1 = `voice_conversion`), >= 0
@@ -554,7 +670,7 @@ class ConvertRequest:
             raise ValueError("ConvertRequest: empty wave")
         self.wave = wave.contiguous()
         sids = []
-        for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
+        for name, sid in (("sid_src", _host_sid(sid_src)), ("sid_tgt", _host_sid(sid_tgt))):
             if torch.is_tensor(sid):
                 if sid.numel() != 1:
                     raise ValueError("ConvertRequest: %s must be one speaker id" % name)
@@ -728,6 +844,10 @@ class SynthesizerTrn(nn.Module):
         self._handle_device = None
         self._synced_sig = None
         self._ticket = 0
+        # blended voices: the slots, the live `Speaker` of each, and who holds which
+        self._voice_slots = SpeakerSlots()
+        self._voices = {}
+        self._voice_holders = {}
 
     # ------------------------------------------------------------------ params
     def _build_parameter_tree(self):
@@ -780,10 +900,22 @@ class SynthesizerTrn(nn.Module):
             if rc:
                 raise _capi.MbvError("mbv_create failed: %s" % L.mbv_last_error(None).decode())
             self._handle, self._handle_device = h, idx
+            fresh = True
+        else:
+            fresh = False
         sig = self._weights_signature()
         if sig != self._synced_sig:
             self._upload_weights()
             self._synced_sig = sig
+        if fresh and self._voices:
+            # a handle re-created on another device starts without voices: the catalogue is defined again (a
+            # vector voice from the row it was given, moved along)
+            voices = [self._voices[k] for k in sorted(self._voices)]
+            for v in voices:
+                if v._vector is not None:
+                    v._vector = v._vector.to(dev)
+            with torch.cuda.device(dev):
+                self._define_voices(self._handle, voices)
         return self._handle
 
     def _config_struct(self, device_index=0):
@@ -933,7 +1065,7 @@ class SynthesizerTrn(nn.Module):
         if self.n_speakers > 0:
             if sid is None:
                 raise ValueError("sid is required for a multi-speaker model (models.py:704-705)")
-            sid = sid.to(device=dev, dtype=torch.int64).contiguous()
+            sid = _sid_tensor(sid).to(device=dev, dtype=torch.int64).contiguous()
             if sid.shape != (x.shape[0],):
                 raise ValueError("sid must be [B]")
         else:
@@ -1459,7 +1591,7 @@ class SynthesizerTrn(nn.Module):
         zd = (z * y_mask)[:, :, :Td].contiguous()
         g = None
         if self.n_speakers > 0:
-            g = self._speaker_embedding(sid.to(self._device()))
+            g = self._speaker_embedding(_sid_tensor(sid).to(self._device()))
         st = self.dec_stream(zd, g, chunk_frames, max_chunk_frames)
         st.y_lengths = y_lengths
         if marks_out is not None:
@@ -1867,9 +1999,131 @@ class SynthesizerTrn(nn.Module):
 
     def _check_speakers(self, sid_src, sid_tgt, prefix=""):
         for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
-            if not 0 <= sid < self.n_speakers:
+            if not (0 <= sid < self.n_speakers or self._voice_defined(sid)):
                 raise IndexError("%sindex out of range in self (%s %d outside [0, %d))"
                                  % (prefix, name, sid, self.n_speakers))
+
+    # ------------------------------------------------------------------ blended voices
+    def _voice_defined(self, sid):
+        """`mbv_speaker_defined`: sid >= n_speakers names a defined voice of this model's handle."""
+        if sid < self.n_speakers or (self._handle is None and not self._voices):
+            return False
+        return _capi.lib().mbv_speaker_defined(self._ensure_handle(), int(sid)) == 1
+
+    def _voice_spec(self, i, spec):
+        """One definition, checked on the host -> (ids, weights, vector): ids / weights lists, or the device row."""
+        unknown = set(spec) - {"ids", "weights", "vector", "normalize"} if isinstance(spec, dict) else {type(spec).__name__}
+        if unknown:
+            raise ValueError("voice %d: a definition is a dict of the arguments of `speaker` (ids, weights, vector, "
+                             "normalize), got %s" % (i, sorted(unknown)))
+        ids, weights, vector = spec.get("ids"), spec.get("weights"), spec.get("vector")
+        normalize = spec.get("normalize", True)
+        gin = self.cfg.gin_channels
+        if vector is not None:
+            if ids is not None or weights is not None:
+                raise ValueError("voice %d: vector= excludes ids= and weights=" % i)
+            vector = torch.as_tensor(vector).detach()
+            if vector.dim() != 1 or vector.numel() != gin:
+                raise ValueError("voice %d: vector must hold gin_channels = %d floats, got shape %s"
+                                 % (i, gin, tuple(vector.shape)))
+            vector = vector.to(device=self._device(), dtype=torch.float32).contiguous().clone()
+            if not bool(torch.isfinite(vector).all()):
+                raise ValueError("voice %d: vector must be finite" % i)
+            return None, None, vector
+        if ids is None:
+            raise ValueError("voice %d: needs ids= (real speaker ids) or vector=" % i)
+        ids = _ints(ids)
+        if weights is None:
+            weights = [1.0] * len(ids)             # the mean of a group under normalize=True
+        try:
+            weights = blend_weights(weights, normalize)
+        except ValueError as e:
+            raise ValueError("voice %d: %s" % (i, e))
+        if len(ids) != len(weights):
+            raise ValueError("voice %d: %d ids for %d weights" % (i, len(ids), len(weights)))
+        for v in ids:
+            if not 0 <= v < self.n_speakers:
+                raise ValueError("voice %d: speaker id %d outside [0, %d): a blend names real speakers only (no blends "
+                                 "of blends)" % (i, v, self.n_speakers))
+        return ids, weights, None
+
+    def _define_voices(self, h, voices):
+        """ONE `mbv_speakers_define` call for `voices` (Speaker objects) inside a device scope the caller holds."""
+        arr = (_capi.MbvSpeakerDef * len(voices))()
+        for k, v in zip(arr, voices):
+            k.slot = v.slot
+            if v._vector is not None:
+                k.vector = v._vector.data_ptr()
+            else:
+                k.count = len(v.ids)
+                for j, (sid, w) in enumerate(zip(v.ids, v.weights)):
+                    k.ids[j], k.weights[j] = sid, w
+        self._launch(h, "mbv_speakers_define", arr, len(voices))
+
+    @torch.no_grad()
+    def speakers(self, specs):
+        """Define several voices in ONE blend launch -> [Speaker].  A spec is a dict with the arguments of `speaker`
+        (ids, weights, vector, normalize).  All or nothing: every spec is checked on the host
+        first (ValueError naming it) and nothing is launched or taken when one is refused."""
+        specs = list(specs)
+        if not (self.n_speakers > 1 and self.cfg.gin_channels > 0):
+            raise ValueError("voices need a speaker table: this model has n_speakers = %d" % self.n_speakers)
+        if not specs:
+            return []
+        h = self._ensure_handle()
+        parsed = [self._voice_spec(i, s) for i, s in enumerate(specs)]
+        taken = []
+        try:
+            for ids, weights, vector in parsed:
+                taken.append(Speaker(self, self._voice_slots.take(), ids, weights, vector))
+            with torch.cuda.device(self._device()):
+                self._define_voices(h, taken)
+        except Exception:
+            for v in taken:
+                self._voice_slots.free(v.slot)
+            raise
+        for v in taken:
+            self._voices[v.slot] = v
+        return taken
+
+    def speaker(self, ids=None, weights=None, vector=None, normalize=True):
+        """A voice that is not in the table -> `Speaker`; its `.sid` = n_speakers + slot is valid wherever a speaker id
+        is, in host ints and in device tensors, mixed with plain ids at will.
+
+          ids, weights   real speaker ids (at most BLEND_MAX) and their weights (default: equal).  The row is the fp32
+                         chain w_0 e_0, then fmaf(w_k, e_k, acc) in the order given: a one-hot blend is bitwise the
+                         table row
+          normalize      True: the weights are divided by their float64 sum, then rounded to fp32 (needs a sum > 0);
+                         False: sent as given, which allows extrapolation such as [1.5, -0.5]
+          vector         instead of ids: a ready row of gin_channels floats (an embedding tuned outside the checkpoint);
+                         copied, and kept as given when the weights are refreshed, whereas a blend follows the table
+        One blend launch (`speaker_runs`).  ValueError for anything refused; nothing is defined then."""
+        return self.speakers([dict(ids=ids, weights=weights, vector=vector, normalize=normalize)])[0]
+
+    def _hold_voices(self, holder, *sids):
+        """`holder` (weakly kept) passes these ids on every tick: the voices among them cannot be released until it
+        has `finished`."""
+        for sid in sids:
+            if sid >= self.n_speakers:
+                self._voice_holders.setdefault(sid - self.n_speakers, weakref.WeakSet()).add(holder)
+
+    def _release_speaker(self, v):
+        if self._voices.get(v.slot) is not v:
+            raise ValueError("%r is not a voice of this model" % (v,))
+        for holder in list(self._voice_holders.get(v.slot, ())):
+            if not holder.finished:
+                raise ValueError("%r is held by %r, which passes its id on every tick: finish or drop the stream first"
+                                 % (v, holder))
+        self._call("mbv_speaker_release", v.slot)
+        self._voice_holders.pop(v.slot, None)
+        del self._voices[v.slot]
+        self._voice_slots.free(v.slot)
+        v.released = True
+
+    def speaker_runs(self):
+        """Launches of the blend kernel on this model's handle so far (`mbv_speaker_runs`): one per `speaker` /
+        `speakers` call, one per weight refresh while a blend is defined."""
+        return int(_capi.lib().mbv_speaker_runs(self._ensure_handle()))
 
     def _handle_not_bf16(self, who, instead, why=" (the flows' route follows the launch size there)"):
         """`_ensure_handle()` for the entries that are not built for the "conv_bf16" mode: ValueError there."""
@@ -2432,10 +2686,13 @@ class SynthesizerTrn(nn.Module):
     def _speaker_embedding(self, sid):
         h = self._ensure_handle()
         dev = self._device()
-        sid = sid.to(device=dev, dtype=torch.int64).contiguous()
+        sid = _sid_tensor(sid).to(device=dev, dtype=torch.int64).contiguous()
         flat = sid.reshape(-1)
         if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= self.n_speakers):
-            raise IndexError("index out of range in self")       # nn.Embedding's message
+            # beyond the table: every such id must name a defined voice (`mbv_speaker_defined`)
+            L = _capi.lib()
+            if any(v < 0 or (v >= self.n_speakers and L.mbv_speaker_defined(h, v) != 1) for v in set(flat.tolist())):
+                raise IndexError("index out of range in self")       # nn.Embedding's message
         out = torch.empty(flat.numel(), self.cfg.gin_channels, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             self._launch(h, "mbv_speaker_embedding", flat, flat.numel(), out)
@@ -2573,8 +2830,8 @@ class SynthesizerTrn(nn.Module):
         B, _, T = y.shape
         seeds = _row_seeds(seed, B)
         y_lengths = y_lengths.to(device=dev, dtype=torch.int64).contiguous()
-        sid_src = sid_src.to(device=dev, dtype=torch.int64).contiguous()
-        sid_tgt = sid_tgt.to(device=dev, dtype=torch.int64).contiguous()
+        sid_src = _sid_tensor(sid_src).to(device=dev, dtype=torch.int64).contiguous()
+        sid_tgt = _sid_tensor(sid_tgt).to(device=dev, dtype=torch.int64).contiguous()
         I = cfg.inter_channels
         f32 = dict(device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):

@@ -294,8 +294,9 @@ class LiveStream:
                              % (int(in_sr), self.model_sr))
         if dtype not in (torch.float32, torch.int16):
             raise TypeError("convert_live: dtype must be int16 or float32, got %s" % dtype)
+        from .models import _host_sid
         sids = []
-        for name, sid in (("sid_src", sid_src), ("sid_tgt", sid_tgt)):
+        for name, sid in (("sid_src", _host_sid(sid_src)), ("sid_tgt", _host_sid(sid_tgt))):
             if torch.is_tensor(sid):
                 if sid.numel() != 1:
                     raise ValueError("convert_live: %s must be one speaker id" % name)
@@ -344,6 +345,12 @@ class LiveStream:
         self._chunks = []             # (first, count) of every chunk decoded so far, in order
         self._next = 0                # the chunk poll() hands out next
         self._decoded = 0             # == len(_chunks)
+        # the ids go to the converter on every tick: a voice among them stays defined until the stream has finished
+        net._hold_voices(self, self.sid_src, self.sid_tgt)
+
+    def __repr__(self):
+        return "LiveStream(sid %d -> %d, %d of %d samples%s)" % (self.sid_src, self.sid_tgt, self._plan.arrived,
+                                                                 self.max_samples, ", closed" if self._plan.closed else "")
 
     # ---- the recording
     @property

@@ -259,6 +259,9 @@ int64_t mbv_decoder_runs(mbv_model *m);
  * there: every output and stage tensor is bitwise what it is with the option off.  Inert for B = 1, without
  * y_lengths (mbv_decode), with "splitk", "trim", "conv_bf16", the ranged / ragged / pooled decodes and per-row
  * speaker conditioning in the decoder (gin_channels > 0 with g given).
+ * A stage whose rows are at most 8 column tiles long takes the packed route instead (MBV_ROUTE_TAIL_PACK): every
+ * row keeps its columns below rate * len_b + reach rounded up to 32, the rows' kept columns are laid end to end and
+ * share the tiles, and the copy kernel writes the rest.  The same bits again.
  *
  * mbv_tail_plan (host only, like mbv_conv_plan): one row of 6 ints per launch of the decoder, in launch order:
  * kind (0 conv_pre, 1 ups[stage], 2 / 3 first / second conv of step q of ResBlock j, 4 conv_post, 5 the waveform
@@ -266,13 +269,22 @@ int64_t mbv_decoder_runs(mbv_model *m);
  * z-frame of a row of len frames can influence; for a launch that writes the running ResBlock sum, the maximum over
  * the ResBlocks summed so far).  Row b's tail starts at column rate * len_b + reach.  At most `capacity` rows are
  * written; returns the number of launches, -1 on a bad argument.
- * mbv_tail_dropped: column tiles the tail maps left out on this handle since mbv_create (synchronises the device). */
+ * mbv_tail_dropped: column tiles the tail maps left out on this handle since mbv_create (synchronises the device);
+ * for a packed launch, the column tiles of the full grid that were not launched. */
 int mbv_tail_plan(const mbv_config *cfg, int32_t *out, int capacity);
 /* mbv_decode on z * sequence_mask(lengths): the decoder run mbv_synthesize makes, on a z of the caller's.
  * lengths: DEVICE int32 [B], frames per row; z at and past a row's length is read as zero. */
 int mbv_decode_masked(mbv_model *m, const float *z, const float *g, const int32_t *lengths, int B, int t_frames,
                       const mbv_outputs *outs, void *stream);
 int64_t mbv_tail_dropped(mbv_model *m);
+/* The block table of a packed tail_once launch (MBV_ROUTE_TAIL_PACK), host only, no GPU: what the device builds for
+ * lens (HOST [B], clamped to [0, T]), S_b = lens[b] * num + reach, a launch of T columns with halo (K - 1) * dil,
+ * pad_right of it on the right, tiles of bn columns.  out: [0] column tiles, [1] donor, [2] 32-column blocks in use,
+ * [3] 0, [4 .. 4 + B) the kept columns S_b' of every row, then from the next multiple of 4 one {row, first column,
+ * read limit, 1 = output / 0 = gap or empty} per block.  Returns the ints written (out NULL: the ints needed),
+ * -1 on a bad argument or a capacity too small. */
+int mbv_tail_pack_table(const int64_t *lens, int B, int num, int reach, int T, int halo, int pad_right, int bn,
+                        int32_t *out, int64_t capacity);
 
 /* ---- pooled admission: the front half (text encoder, duration predictor, length regulation, flows) of many
  * requests in one padded run (no reference counterpart: the reference service runs one request at a time,
@@ -1328,7 +1340,10 @@ typedef struct mbv_conv_desc {
   const float *ln_beta;           /* LN: DEVICE [Cout] */
   const int32_t *ln_out_lens;     /* LN: DEVICE [B] or NULL, the mask behind the LayerNorm */
   int32_t tail_once;              /* 1 (with trim_lens; conv with STORE / RESID / RESID_ACC): the launch of "tail_once" — the row with the
-                                   * smallest trim_lens keeps every tile, the tiles the others drop are copied from it (trim_add = reach) */
+                                   * smallest trim_lens keeps every tile, the tiles the others drop are copied from it (trim_add = reach).
+                                   * 2: the same on the packed route (MBV_ROUTE_TAIL_PACK) where the planner grants it: every other
+                                   * row keeps its columns below trim_lens[b] * trim_num + trim_add rounded up to 32, the rows' kept
+                                   * columns laid end to end share the tiles, and the rest is copied from the donor */
 } mbv_conv_desc;
 /* plan[8] = route, tile rows, tile columns, threads, input-channel chunk, nb_big, vs_tv, split-K factor
  * (tile fields 0 on the narrow kernel; see conv1d_plan in csrc/kernels.h) */
@@ -1340,6 +1355,7 @@ typedef struct mbv_conv_desc {
 #define MBV_ROUTE_BIG 6
 #define MBV_ROUTE_SPLIT_BATCH 7
 #define MBV_ROUTE_VS 8
+#define MBV_ROUTE_TAIL_PACK 9   /* 128 x 384 tiles over the packed column axis of a tail_once = 2 launch */
 /* plan_out may be NULL. */
 int mbv_op_conv(mbv_model *m, const mbv_conv_desc *d, const float *x, const float *w_host, const float *bias_host,
                 float *y, int32_t *plan_out, void *stream);

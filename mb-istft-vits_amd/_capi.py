@@ -30,7 +30,7 @@ SYMBOLS = [
     "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add", "mbv_op_istft_single",
     "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
     "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
-    "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
+    "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked", "mbv_tail_pack_table",
     "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
     "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
     "mbv_convert_ranges_plan", "mbv_convert_ranges",
@@ -270,7 +270,8 @@ class MbvConvDesc(C.Structure):
 # MBV_CONV_KIND_* / MBV_CONV_EPI_* / MBV_ROUTE_* of include/mbistft_vits.h
 CONV_KIND_CONV, CONV_KIND_CONVT4, CONV_KIND_CONVT8 = 0, 4, 8
 CONV_EPI_STORE, CONV_EPI_RESID, CONV_EPI_RESID_ACC, CONV_EPI_LN = 0, 1, 2, 7
-ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS"}
+ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6: "BIG", 7: "SPLIT_BATCH", 8: "VS",
+          9: "TAIL_PACK"}
 PLAN_FIELDS = ("route", "bm", "bn", "threads", "ck", "nb_big", "vs_tv", "S")
 
 
@@ -400,7 +401,7 @@ def lib():
                 "mbv_resample_turns_shaped",
                 "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
                 "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined",
-                "mbv_speaker_runs") if os.environ.get("MBV_LIB") else ()
+                "mbv_speaker_runs", "mbv_tail_pack_table") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -429,6 +430,8 @@ def lib():
         L.mbv_tail_dropped.argtypes = [vp]
         L.mbv_tail_dropped.restype = C.c_int64
         L.mbv_decode_masked.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
+    if hasattr(L, "mbv_tail_pack_table") or not optional:
+        L.mbv_tail_pack_table.argtypes = [i64p, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.c_int64]
     if hasattr(L, "mbv_convert_rows") or not optional:
         L.mbv_convert_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.mbv_convert_rows.argtypes = [vp, C.POINTER(MbvConvertRow), i32, i32, i32, i32, vp, vp]

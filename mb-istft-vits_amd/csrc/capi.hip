@@ -1083,6 +1083,13 @@ ConvArgs conv_args(const mbv_model* m, const PConv& p, const float* x, int64_t x
 // dropped tile saves no time and the map and fill launches would only add launch gaps (B = 8: + 0.1 ms).
 int tail_mode(const mbv_model* m) { return (!m->trim && !m->splitk && m->conv_bf16 != 3) ? m->tail_once : 0; }
 bool tail_stage(int mode, int B, long conv_tiles) { return B > 1 && (mode == 2 || (mode == 1 && conv_tiles > 256)); }
+// ... on the packed route: the stages whose rows are at most kTailPackMaxTiles column tiles long.  A row
+// loses half a tile on average to whole-tile dropping, whatever its length, and a packed row pays its gap and the
+// table lookup (1.3 - 2 % per tile, profiles/tail_pack_gate.jsonl): at 6 tiles a row (the headline batch's stage 0)
+// the maps leave out 1.3 % of the tiles and packing 8 %; at 24 tiles a row (its stage 1) 7.6 % against 9.0 %,
+// which the lookup eats.  Between the two nothing was measured: the threshold sits near the lower end.
+constexpr int kTailPackMaxTiles = 8;
+bool tail_pack_stage(int Lo, int bn) { return (Lo + bn - 1) / bn <= kTailPackMaxTiles; }
 
 // The three ResBlocks of a decoder stage on three streams?  Only when one of their convs (ch channels, Lo
 // frames) is at most 192 tiles of 128 x 384, i.e. cannot fill the chip by itself.
@@ -1310,7 +1317,7 @@ struct DecBufs {
   struct TrimMap { int num, add, T, bn; int* map; bool built; };
   TrimMap trim_maps[12]; int n_trim;   // one per geometry: at most two tile widths for each of four (num, add)
   int trim_of[48];                 // per table entry (1 + 2 (1 + 18) + 2 at most): its trim map, -1 none
-  struct TailMap { int kind, j, q, bn; const int* map; };
+  struct TailMap { int kind, j, q, bn; const int* map; int pack_blocks; };   // pack_blocks > 0: a packed job's block table
   // per stage: u, t1 / r of each ResBlock (its own when the three run concurrently), xs, cond vectors, tail maps
   struct Stage { float *u, *t1s[3], *rs[3], *xs, *cb[3]; bool conc; int n_tail; TailMap tail_maps[kTailMapJobs]; TailMapJobs jobs; } st[2];
   int Bc;                          // rows per conv_post + tail sub-batch; 0: one utterance's x_post reaches 2 GiB
@@ -1348,8 +1355,19 @@ void carve_decoder(const mbv_model* m, const DecCall& k, Bump& sc, DecBufs* out)
         const ConvArgs a = planned(e);
         const int bn = conv1d_trim_bn(a);
         if (!bn || conv1d_plan(a, false).route != conv1d_plan(a, true).route) continue;
+        // Few column tiles per row (tail_pack_stage): whole tiles rarely fit behind S_b, so the rows' kept columns
+        // are packed into shared tiles instead (CONV_TAIL_PACK) where the planner grants that route.  A rule on the
+        // launch shape alone: the lengths are on the device.
+        ConvArgs ap = a;
+        ap.tail_pack = 1;
+        if (tail_pack_stage(Lo, bn) && conv1d_plan(ap, true).route == CONV_TAIL_PACK) {
+          const int halo = (a.K - 1) * a.dil, gap = tail_pack_gap(halo);
+          st.jobs.job[st.n_tail] = {e.rate, tail_plan[n_e].reach, Lo, bn, nullptr, gap, halo - a.pad_left};
+          st.tail_maps[st.n_tail++] = {e.kind, e.j, e.q, bn, nullptr, tail_pack_blocks(B, Lo, gap, bn)};
+          continue;
+        }
         st.jobs.job[st.n_tail] = {e.rate, tail_plan[n_e].reach, Lo, bn, nullptr};
-        st.tail_maps[st.n_tail++] = {e.kind, e.j, e.q, bn, nullptr};
+        st.tail_maps[st.n_tail++] = {e.kind, e.j, e.q, bn, nullptr, 0};
       }
     // The three ResBlocks of a stage read the same input and only meet in the running sum xs.  When one of their convs
     // cannot fill the chip (decoder_stage_concurrent) they run on three streams — own temporaries each, the three xs
@@ -1390,7 +1408,9 @@ void carve_decoder(const mbv_model* m, const DecCall& k, Bump& sc, DecBufs* out)
   }
   for (auto& st : d.st)
     for (int i = 0; i < st.n_tail; ++i)
-      st.tail_maps[i].map = st.jobs.job[i].out = sc.take<int>(launch_tail_map_ints(B, st.jobs.job[i].T, st.jobs.job[i].BN));
+      st.tail_maps[i].map = st.jobs.job[i].out = sc.take<int>(
+          st.jobs.job[i].pack_gap ? tail_pack_ints(B, st.jobs.job[i].T, st.jobs.job[i].pack_gap, st.jobs.job[i].BN)
+                                  : launch_tail_map_ints(B, st.jobs.job[i].T, st.jobs.job[i].BN));
   d.xpost = sc.take<float>((size_t)d.Bc * (utt_bytes / 4));
   if (k.own_o) d.otmp = sc.take<float>((size_t)B * table.back().rate * Td);
 }
@@ -1467,6 +1487,11 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
       if (t.kind != e.kind || t.j != e.j || t.q != e.q) continue;
       // (the map was planned before the fork from the launch's shape alone: the launch itself must agree)
       if (conv1d_trim_bn(a) != t.bn) { tail_drift = true; return nullptr; }
+      if (t.pack_blocks) {
+        a.tail_pack = 1; a.pack_tbl = t.map; a.pack_blocks = t.pack_blocks;
+        if (conv1d_plan(a, true, rt_num * e.num).route != CONV_TAIL_PACK) { tail_drift = true; return nullptr; }
+        return &t;
+      }
       a.trim_map = t.map; a.trim_bn = t.bn;
       return &t;
     }
@@ -1546,7 +1571,7 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
         with_trim(a, e);
         const DecBufs::TailMap* tm = with_tail(a, e);
         launch_conv1d(a, s, rt_num * e.num);
-        if (tm) launch_tail_fill(a.y, a.y_bstride, B, a.M, a.T, tm->bn, tm->map, s);
+        if (tm) launch_tail_fill(a.y, a.y_bstride, B, a.M, a.T, tm->bn, tm->map, s, tm->pack_blocks > 0);
         if (conc && e.epi == EPI_RESID_ACC) HIPCHK(m, hipEventRecord(m->ev_rb[j], s));
         if (!first) state = r;
       }
@@ -5321,7 +5346,8 @@ int mbv_op_conv1d(mbv_model* m, const float* x, const float* w_host, const float
 namespace {
 static_assert(MBV_ROUTE_NARROW_M == CONV_NARROW_M && MBV_ROUTE_NARROW_LAUNCH == CONV_NARROW_LAUNCH &&
               MBV_ROUTE_M64 == CONV_M64 && MBV_ROUTE_HALF == CONV_HALF && MBV_ROUTE_SMALL == CONV_SMALL &&
-              MBV_ROUTE_BIG == CONV_BIG && MBV_ROUTE_SPLIT_BATCH == CONV_SPLIT_BATCH && MBV_ROUTE_VS == CONV_VS,
+              MBV_ROUTE_BIG == CONV_BIG && MBV_ROUTE_SPLIT_BATCH == CONV_SPLIT_BATCH && MBV_ROUTE_VS == CONV_VS &&
+              MBV_ROUTE_TAIL_PACK == CONV_TAIL_PACK,
               "route numbers of the C-ABI and the launcher");
 static_assert(MBV_CONV_EPI_LN == EPI_LN, "epilogue numbers of the C-ABI and the launcher");
 
@@ -5347,6 +5373,7 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   if (d.epi != MBV_CONV_EPI_RESID_ACC && d.accum_in) return "accum_in belongs to RESID_ACC";
   if (d.legacy_convt) return "legacy_convt must be 0 (the stand-alone ConvTranspose kernel was removed)";
   if (d.trim_lens && d.splitk) return "a trimmed launch takes no split-K";
+  if (d.tail_once < 0 || d.tail_once > 2) return "tail_once must be 0, 1 or 2";
   if (d.tail_once && (!d.trim_lens || convt || ln)) return "tail_once needs trim_lens and a conv with a STORE / RESID / RESID_ACC epilogue";
   const int U = d.kind;
   if (convt) {
@@ -5377,6 +5404,7 @@ const char* conv_desc_args(const mbv_conv_desc& d, ConvArgs* out) {
   a.B = d.B;
   a.splitk = d.splitk != 0;
   a.prec = d.prec;
+  a.tail_pack = d.tail_once == 2;        // (the planner grants the packed route where the kernel is built for it)
   if ((a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) && (unsigned long long)a.M * a.T * 4ull >= (1ull << 32))
     return "one utterance's output exceeds 4 GiB";
   if (ln) {
@@ -5485,12 +5513,23 @@ int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const floa
     mem.p.push_back(map);
     if (d->tail_once) {
       if (d->B > 65535) return m->fail("mbv_op_conv: tail_once takes at most 65535 rows");
+      const bool packed = p.route == CONV_TAIL_PACK;
+      const int halo = (a.K - 1) * a.dil, gap = tail_pack_gap(halo);
       void* tmap = nullptr;
-      HIPCHK(m, hipMalloc(&tmap, launch_tail_map_ints(d->B, a.T, p.bn) * sizeof(int)));
+      HIPCHK(m, hipMalloc(&tmap, (packed ? tail_pack_ints(d->B, a.T, gap, p.bn) : launch_tail_map_ints(d->B, a.T, p.bn)) * sizeof(int)));
       mem.p.push_back(tmap);
       TailMapJobs jobs{};
-      jobs.job[0] = {d->trim_num, d->trim_add, a.T, p.bn, (int*)tmap};
+      jobs.job[0] = {d->trim_num, d->trim_add, a.T, p.bn, (int*)tmap, packed ? gap : 0, packed ? halo - a.pad_left : 0};
       launch_tail_maps((const int*)dl, d->B, jobs, 1, m->tail_cnt, s);
+      if (packed) {
+        a.pack_tbl = (const int*)tmap; a.pack_blocks = tail_pack_blocks(d->B, a.T, gap, p.bn);
+        launch_conv1d(a, s);
+        launch_tail_fill(a.y, a.y_bstride, a.B, a.M, a.T, p.bn, a.pack_tbl, s, true);
+        HIPCHK(m, hipGetLastError());
+        HIPCHK(m, hipStreamSynchronize(s));
+        if (plan_out) plan_ints(p, plan_out);
+        return 0;
+      }
       map = tmap;
     } else {
       launch_trim_map((const int*)dl, d->B, d->trim_num, d->trim_add, a.T, p.bn, (int*)map, s);
@@ -5503,6 +5542,28 @@ int mbv_op_conv(mbv_model* m, const mbv_conv_desc* d, const float* x, const floa
   HIPCHK(m, hipStreamSynchronize(s));
   if (plan_out) plan_ints(p, plan_out);
   return 0;
+}
+
+int mbv_tail_pack_table(const int64_t* lens, int B, int num, int reach, int T, int halo, int pad_right, int bn,
+                        int32_t* out, int64_t capacity) {
+  if (!lens || B <= 0 || T <= 0 || halo < 0 || pad_right < 0 || pad_right > halo || bn < 32 || bn % 32) return -1;
+  const int gap = tail_pack_gap(halo);
+  const int64_t n = (int64_t)tail_pack_ints(B, T, gap, bn);
+  if (!out) return n > 0x7fffffff ? -1 : (int)n;
+  if (capacity < n || n > 0x7fffffff) return -1;
+  auto len_of = [&](int b) { return lens[b] < 0 ? 0 : (lens[b] > T ? (int64_t)T : lens[b]); };   // (mbv_op_conv's clamp)
+  int donor = 0;
+  for (int b = 1; b < B; ++b) if (len_of(b) < len_of(donor)) donor = b;
+  int run = 0;
+  for (int b = 0; b < B; ++b) {
+    const int sp = tail_pack_sp(len_of(b), num, reach, T, b == donor);
+    out[kTailPackHdr + b] = sp;
+    tail_pack_row(out, B, b, run, sp, gap, pad_right);
+    run += tail_pack_row_blocks(sp, gap);
+  }
+  for (int i = kTailPackHdr + B; i < tail_pack_entries_at(B); ++i) out[i] = 0;
+  tail_pack_finish(out, B, T, gap, bn, donor, run);
+  return (int)n;
 }
 
 }  // extern "C"

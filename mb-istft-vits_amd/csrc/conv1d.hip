@@ -222,6 +222,65 @@ __device__ __forceinline__ void conv_acc_init(f32x16 (&acc)[WM][WN], const ConvA
     }
 }
 
+// The same start values on the packed column axis (CONV_TAIL_PACK; STORE / RESID / RESID_ACC, every row real): a
+// wave's 32-column MFMA tile lies in one block of the table, so (row, first column) is wave-uniform per patch column.
+// One buffer view of the WHOLE tensor (< 2 GiB: conv1d_plan) and one 32-bit lane offset per patch column, out of
+// range — reading 0, touching nothing — for gap and empty blocks and for columns at and past T.
+template <int WM, int WN, int EPI>
+__device__ __forceinline__ void conv_acc_init_packed(f32x16 (&acc)[WM][WN], const ConvArgs& a, const int4* pack_ent,
+                                                     int wrow0, int t0, int wn, int hl, int l31) {
+  if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_ACC) {
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.res), 0, (unsigned)((unsigned long long)a.B * a.res_bstride * 4ull), 0x00020000);
+    unsigned vo[WN], va[WN];
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+      const int4 e = pack_ent[(t0 >> 5) + wn * WN + j];
+      const int t = e.y + l31;
+      const bool ok = e.w && t < a.T;
+      const unsigned in_row = (unsigned)((wrow0 + 4 * hl) * a.T + t);
+      vo[j] = ok ? ((unsigned)e.x * (unsigned)a.res_bstride + in_row) * 4u : 0x7fffffffu;
+      va[j] = ok ? ((unsigned)e.x * (unsigned)a.y_bstride + in_row) * 4u : 0x7fffffffu;
+    }
+    const unsigned rowT = (unsigned)a.T * 4u;
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const unsigned so = (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rowT;
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+          acc[i][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (int)vo[j], (int)so, 0));
+      }
+    if (EPI == EPI_RESID_ACC && a.accum_in) {
+      const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(a.accum_in), 0, (unsigned)((unsigned long long)a.B * a.y_bstride * 4ull), 0x00020000);
+#pragma unroll
+      for (int i = 0; i < WM; ++i) {
+        float tmp[16][WN];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const unsigned so = (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rowT;
+#pragma unroll
+          for (int j = 0; j < WN; ++j)
+            tmp[r][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, (int)va[j], (int)so, 0));
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+          for (int j = 0; j < WN; ++j) acc[i][j][r] += tmp[r][j];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  }
+}
+
 // NWN = waves along time.  NWN == 2: 256 threads, single LDS buffer, 2 barriers per chunk,
 // two workgroups per CU (short sequences / small launches).  NWN == 4: 512 threads = one
 // workgroup per CU with 2 waves per SIMD, the weight slab shared by twice as many columns,
@@ -268,6 +327,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
   const int buf_f4 = G * 2 * XL + a.K * G * 2 * BM + 2 * BM;
   f32x4* const lds4 = reinterpret_cast<f32x4*>(lds);
   const int tin_eff = a.reflect1 ? a.Tin + 1 : a.Tin;  // length of the (virtually padded) input
+  // VS == 2 (CONV_TAIL_PACK): the block table of the packed column axis, one int4 per 32 columns (kernels.h)
+  const int4* const pack_ent = VS == 2 ? reinterpret_cast<const int4*>(a.pack_tbl + tail_pack_entries_at(a.B)) : nullptr;
 
   // ---- async-stage bookkeeping ------------------------------------------------
   constexpr int HALO_MAX = CK == 8 ? 72 : (CK == 16 ? 24 : 0);
@@ -304,6 +365,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
 #define MBV_SETUP_TILE(TILE)                                                                 \
   {                                                                                          \
     const int tile_ = (TILE);                                                                \
+    if constexpr (VS == 2) {          /* packed axis: (column tile, row tile), row 0's addressing */ \
+      lb = 0; lm0 = (tile_ % tiles_y) * BM; lt0 = (tile_ / tiles_y) * BN;                    \
+    } else                                                                                   \
     if (a.trim_map) {                 /* compact list: (column tile of the map, row tile) */    \
       const int ux_ = tile_ / tiles_y;                                                       \
       lb = a.trim_map[a.B + 1 + ux_]; lm0 = (tile_ % tiles_y) * BM; lt0 = (ux_ - a.trim_map[lb]) * BN; \
@@ -319,8 +383,16 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
       int off = -1;                                                                          \
       if (P < 2 * G) {                                                                       \
         int gi = lt0 - a.pad_left + col;                                                     \
-        if constexpr (VS) {     /* virtual column -> (utterance, frame); the gaps read as padding */ \
-          if (gi >= 0) {                                                                     \
+        if constexpr (VS == 2) { /* packed column -> (row, column) through its block's entry */ \
+          if (gi >= 0 && (gi >> 5) < a.pack_blocks) {                                        \
+            const int4 e_ = pack_ent[gi >> 5];                                               \
+            const int cq_ = e_.y + (gi & 31);                                                \
+            if (cq_ < e_.z && cq_ < a.Tin)                                                   \
+              off = e_.x * (int)a.x_bstride + ((P >> 1) * 8 + (P & 1)) * a.x_rstride + cq_;  \
+          }                                                                                  \
+        } else                                                                               \
+        if constexpr (VS == 1) { /* virtual column -> (utterance, frame); the gaps read as padding */ \
+          if (gi >= 0) {                                                                  \
             const int bq_ = gi / a.vs_tv, tq_ = gi - bq_ * a.vs_tv;                          \
             if (bq_ < a.B && tq_ < a.Tin && (!a.in_lens || tq_ < a.in_lens[bq_]))            \
               off = bq_ * (int)a.x_bstride + ((P >> 1) * 8 + (P & 1)) * a.x_rstride + tq_;   \
@@ -438,6 +510,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
   // start values and runs the epilogue.  S == 1: a unit is a tile.
   const int S = NWN == 2 ? ksplit : 1;             // the 512-thread shape is only picked for launches that fill the chip
   if (a.trim_map) total_tiles = a.trim_map[a.B] * tiles_y;    // trimmed decode: the tile count lives on the device
+  if constexpr (VS == 2) total_tiles = a.pack_tbl[0] * tiles_y;   // (and so does the packed axis's)
   const int total_units = total_tiles * S;
   __shared__ int s_ticket;
   int s_unit = blockIdx.x;
@@ -475,6 +548,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     const int tile = unit / S, sp = unit % S;
     const int c_lo = sp * nck / S, c_hi = (sp + 1) * nck / S;
     int b, m0, t0;
+    if constexpr (VS == 2) {
+      b = 0; m0 = (tile % tiles_y) * BM; t0 = (tile / tiles_y) * BN;
+    } else
     if (a.trim_map) {
       const int ux = tile / tiles_y;
       b = a.trim_map[a.B + 1 + ux]; m0 = (tile % tiles_y) * BM; t0 = (ux - a.trim_map[b]) * BN;
@@ -487,6 +563,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     nact = nact < 0 ? 0 : (nact > WM ? WM : nact);
     int nj = ((VS ? a.B * a.vs_tv : a.T) - (t0 + wn * 32 * WN) + 31) / 32;  // ... and 32-column tiles inside the sequence
     nj = nj < 0 ? 0 : (nj > WN ? WN : nj);
+    if constexpr (VS == 2) nj = WN;      // (gap and empty blocks are staged as zeros and never stored)
 
     // Accumulators start from everything the epilogue would otherwise have to READ after the MFMA
     // loop (residual, running ResBlock sum, the tensor a flow layer updates in place).  gfx9 counts
@@ -517,9 +594,12 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
     // conv_acc_init and in the epilogue (no per-element exec masking, loads issued back to back)
     const bool full = !VS && wrow0 + 32 * WM <= a.M && t0 + wn * 32 * WN + 32 * WN <= a.T;
     const int64_t lane_off = (int64_t)(wrow0 + 4 * hl) * a.T + t0 + wn * 32 * WN + l31;   // element (k = 0, j = 0)
+    if constexpr (VS == 2) {
+      conv_acc_init_packed<WM, WN, EPI>(acc, a, pack_ent, wrow0, t0, wn, hl, l31);
+    } else
     if (S == 1) {
       conv_acc_init<WM, WN, EPI>(acc, a, b, wrow0, t0, wn, hl, l31, full, lane_off);
-    } else {                                         // split-K: partial sums start from zero
+    } else {                                        // split-K: partial sums start from zero
 #pragma unroll
       for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -849,6 +929,53 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void conv1d_mfma_kernel(const Co
           }
         }
       }
+    } else if constexpr (VS == 2) {
+      // Packed axis (STORE / RESID / RESID_ACC, every row real, no out_lens: conv1d_plan).  Each patch column has its
+      // own (row, first column), read again from its block's entry — nothing of it lived through the step loop.  A
+      // patch whose three blocks are whole output takes the unguarded stores; gap and empty blocks store nothing.
+      int64_t po[WN];
+      bool pok[WN];
+      int whole = 1;
+#pragma unroll
+      for (int j = 0; j < WN; ++j) {
+        const int4 e = pack_ent[(t0 >> 5) + wn * WN + j];
+        pok[j] = e.w && e.y + l31 < T;
+        whole &= (e.w && e.y + 32 <= T) ? 1 : 0;
+        po[j] = (int64_t)e.x * a.y_bstride + (int64_t)(wrow0 + 4 * hl) * T + e.y + l31;
+      }
+      if (__builtin_amdgcn_readfirstlane(whole)) {     // (the entries are the same in every lane)
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int k0 = i * 32 + (r & 3) + 8 * (r >> 2);
+            const float bias = __shfl(rowc, k0 + 4 * hl);
+            float* q = a.y + (int64_t)k0 * T;
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+              float v = acc[i][j][r] + bias;
+              if constexpr (EPI == EPI_STORE) { if (a.relu) v = fmaxf(v, 0.f); }
+              if constexpr (EPI == EPI_RESID_ACC) v *= a.out_scale;
+              q[po[j]] = v;
+            }
+          }
+      } else {
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int k0 = i * 32 + (r & 3) + 8 * (r >> 2);
+            const float bias = __shfl(rowc, k0 + 4 * hl);              // every lane takes part
+            float* q = a.y + (int64_t)k0 * T;
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+              float v = acc[i][j][r] + bias;
+              if constexpr (EPI == EPI_STORE) { if (a.relu) v = fmaxf(v, 0.f); }
+              if constexpr (EPI == EPI_RESID_ACC) v *= a.out_scale;
+              if (pok[j]) q[po[j]] = v;
+            }
+          }
+      }
     } else if ((EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_RESID_ACC) && full && !a.out_lens) {
       float* py = a.y + (int64_t)b * a.y_bstride + lane_off;
 #pragma unroll
@@ -985,7 +1112,9 @@ static void launch_epi(const ConvArgs& a, hipStream_t s) {
   const size_t lds_bytes = buf_f4 * 16 * (NWN == 4 ? 2 : 1);
   // VS: column tiles run through the batch laid end to end (utterance b at virtual column b * vs_tv); the kernel's
   // tile decode then yields utterance 0 for every tile and the addressing above does the rest
-  const int tiles_x = VS ? (int)(((long)a.B * a.vs_tv + BN - 1) / BN) : (a.T + BN - 1) / BN, tiles_y = (a.M + BM - 1) / BM;
+  // VS == 2: over the packed axis of a tail_once launch; the table's capacity bounds the tile count, which lives on the device
+  const int tiles_x = VS == 2 ? a.pack_blocks / (BN / 32) - 1 : VS ? (int)(((long)a.B * a.vs_tv + BN - 1) / BN) : (a.T + BN - 1) / BN;
+  const int tiles_y = (a.M + BM - 1) / BM;
   const long total = VS ? (long)tiles_x * tiles_y : (long)tiles_x * tiles_y * a.B;
   // persistent tiles: at most the workgroups that are resident at once (1 per CU for the
   // 512-thread shape, 2 for the 256-thread one: both are register-limited to 2 waves / SIMD)
@@ -1081,6 +1210,7 @@ constexpr int kNarrowMinUnits = 16;     // split-K mode: fewer 32-column units t
 ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
   ConvPlan p{};
   p.S = 1;
+  if (a.tail_pack) trimmed = true;       // (a packed launch is a trimmed one: no route that takes every tile)
   // conv1d_narrow.hip (32-column units, rows split over waves, weights from L2) takes over where the
   // 128-column tiles below fit badly:
   //   (a) every sequence of <= 256 frames (the text encoder, the duration predictor): T = 200 fills
@@ -1168,6 +1298,18 @@ ConvPlan conv1d_plan(const ConvArgs& a, bool trimmed, int route_T) {
     return p;
   }
   if (wide_m) {
+    // tail_once, packed: the big shape over the packed column axis, where the kernel is built for it —
+    // exact fp32, the ResBlock epilogues, every row of a wave real, nothing per row but x / y / res themselves, and
+    // tensors the 32-bit offsets of the table route reach
+    const int64_t lim32 = (1ll << 31) - 64ll * a.x_rstride;
+    if (big && a.tail_pack && a.K > 1 && ck <= 16 && a.prec != 3 && !a.splitk && a.M % 128 == 0 &&
+        (a.epi == EPI_STORE || a.epi == EPI_RESID || a.epi == EPI_RESID_ACC) &&
+        !a.in_lens && !a.out_lens && !a.chan_add && !a.res_chan_add && !a.reflect1 && a.B <= 65535 &&
+        (int64_t)a.B * a.x_bstride < lim32 && (int64_t)a.B * a.y_bstride * 4 < (1ll << 31) &&
+        (int64_t)a.B * a.res_bstride * 4 < (1ll << 31)) {
+      shape(CONV_TAIL_PACK, 128, 384, 512, ck);
+      return p;                            // (S = 1: NWN = 4)
+    }
     if (big) shape(CONV_BIG, 128, 384, 512, ck);
     else shape(CONV_SMALL, 128, 128, 256, ck);
   } else {
@@ -1205,6 +1347,23 @@ void launch_conv1d(const ConvArgs& a, hipStream_t s, int route_T) {
   if (a.epi == EPI_LN && !conv1d_narrow_supported(a)) { fprintf(stderr, "mbv: EPI_LN outside the narrow kernel's range\n"); abort(); }
   const ConvPlan p = conv1d_plan(a, a.trim_map != nullptr, route_T);
   switch (p.route) {
+    case CONV_TAIL_PACK:
+      if (!a.pack_tbl || a.trim_map || a.pack_blocks < 2 * (384 / 32)) {
+        fprintf(stderr, "mbv: conv1d: the packed tail route needs its block table (and takes no tile map)\n");
+        abort();
+      }
+      if (p.ck == 16) {
+        switch (a.epi) {
+          case EPI_STORE: launch_epi<2, 3, 16, 4, EPI_STORE, 0, 2, 2>(a, s); return;
+          case EPI_RESID: launch_epi<2, 3, 16, 4, EPI_RESID, 0, 2, 2>(a, s); return;
+          default: launch_epi<2, 3, 16, 4, EPI_RESID_ACC, 0, 2, 2>(a, s); return;
+        }
+      }
+      switch (a.epi) {
+        case EPI_STORE: launch_epi<2, 3, 8, 4, EPI_STORE, 0, 2, 2>(a, s); return;
+        case EPI_RESID: launch_epi<2, 3, 8, 4, EPI_RESID, 0, 2, 2>(a, s); return;
+        default: launch_epi<2, 3, 8, 4, EPI_RESID_ACC, 0, 2, 2>(a, s); return;
+      }
     case CONV_NARROW_M: launch_conv1d_narrow(a, false, s); return;
     case CONV_NARROW_LAUNCH: launch_conv1d_narrow(a, true, s); return;
     case CONV_VS: {

@@ -104,6 +104,12 @@ struct ConvArgs {
   // r03 virtual-sequence tiling (launch_conv1d, EPI_CONVT): > 0 = column tiles run through the batch laid end to end,
   // utterance b at virtual column b * vs_tv (vs_tv = T + halo); set by the launcher only
   int vs_tv;
+  // "tail_once", packed route (CONV_TAIL_PACK): tail_pack = 1 asks the planner for it (set by the decoder's
+  // tail path and mbv_op_conv only); pack_tbl (device, launch_tail_maps with a packed job) is the block table the
+  // kernel tiles over, pack_blocks the entries it holds (tail_pack_blocks)
+  int tail_pack;
+  const int* pack_tbl;
+  int pack_blocks;
   // split-K scratch (small launches): partial accumulators + one self-resetting ticket per tile
   // (conv1d_plan decides from the sizes alone: ws_floats / n_counters are 0 whenever ws / counters are null)
   float* ws;
@@ -130,6 +136,7 @@ enum ConvRoute : int {
   CONV_BIG = 6,             // 128 x 384 tiles, 512 threads
   CONV_SPLIT_BATCH = 7,     // the first nb_big utterances on 128 x 384 tiles, the rest on 128 x 128
   CONV_VS = 8,              // 128 x 384 tiles over the virtual sequence of the batch (stride-4 EPI_CONVT)
+  CONV_TAIL_PACK = 9,       // 128 x 384 tiles over the packed column axis of a tail_once launch (ConvArgs::tail_pack)
 };
 struct ConvPlan {
   int route;
@@ -742,14 +749,57 @@ void launch_trim_map(const int* lens, int B, int num, int add, int T, int BN, in
 // column below S_b = min(T, lens[b] * num + reach), a prefix, and the tiles wholly inside [S_b, T) are dropped.  One
 // launch builds up to kTailMapJobs maps (one workgroup each).  out: launch_tail_map_ints ints = the trim map, then
 // the donor's index; *dropped (device, may be null) += the column tiles dropped by each map.
+//
+// Packed job (pack_gap > 0; the CONV_TAIL_PACK route): instead of dropping whole BN-column tiles, every
+// row contributes its columns [0, S_b') to ONE packed column axis — S_b' = S_b rounded up to 32 and clamped to T,
+// the donor [0, T) — each region followed by a gap of pack_gap = the launch's halo rounded up to 32 columns, and
+// the conv kernel cuts its BN-column tiles over that axis.  Every 32-column block of the axis has one owner and is
+// wholly output or wholly gap.  out (tail_pack_ints ints): [0] column tiles, [1] donor, [2] blocks in use, [3] 0,
+// [4 .. 4 + B) S_b', then from tail_pack_entries_at(B) one int4 per block {row, first column, read limit, 1 =
+// output}.  A gap block continues its row's column numbering: the columns below the read limit S_b' + pad_right
+// are the row's right halo (real memory), everything from there on reads as zero — the next row's left padding.
+// Blocks behind the last gap are empty (read limit 0); the table holds a tile's worth of them behind the last tile.
 constexpr int kTailMapJobs = 24;
-struct TailMapJob { int num, reach, T, BN; int* out; };
+struct TailMapJob { int num, reach, T, BN; int* out; int pack_gap, pad_right; };
 struct TailMapJobs { TailMapJob job[kTailMapJobs]; };
+constexpr int kTailPackHdr = 4;
+__host__ __device__ inline int tail_pack_gap(int halo) { return (halo + 31) & ~31; }
+__host__ __device__ inline int tail_pack_entries_at(int B) { return (kTailPackHdr + B + 3) & ~3; }
+__host__ __device__ inline int tail_pack_blocks(int B, int T, int gap, int BN) {       // entries the table holds
+  const long per_tile = BN / 32, n = (long)B * ((T + 31) / 32 + gap / 32);
+  return (int)((n + per_tile - 1) / per_tile * per_tile + per_tile);
+}
+__host__ __device__ inline size_t tail_pack_ints(int B, int T, int gap, int BN) {
+  return (size_t)tail_pack_entries_at(B) + 4 * (size_t)tail_pack_blocks(B, T, gap, BN);
+}
+__host__ __device__ inline int tail_pack_sp(long len, int num, int reach, int T, bool donor) {
+  if (donor) return T;
+  long s = len * num + reach;
+  s = s < 0 ? 0 : (s > T ? T : s);
+  s = (s + 31) & ~31L;
+  return (int)(s > T ? T : s);
+}
+__host__ __device__ inline int tail_pack_row_blocks(int sp, int gap) { return (sp + 31) / 32 + gap / 32; }
+// the entries of row b, whose region starts at block `first`
+__host__ __device__ inline void tail_pack_row(int* out, int B, int b, int first, int sp, int gap, int pad_right) {
+  int* e = out + tail_pack_entries_at(B) + 4 * (long)first;
+  const int n_out = (sp + 31) / 32, n = n_out + gap / 32;
+  for (int k = 0; k < n; ++k, e += 4) { e[0] = b; e[1] = 32 * k; e[2] = sp + pad_right; e[3] = k < n_out; }
+}
+// header and the empty blocks behind the last row's gap, `used` = blocks in use
+__host__ __device__ inline void tail_pack_finish(int* out, int B, int T, int gap, int BN, int donor, int used) {
+  const int per_tile = BN / 32, cap = tail_pack_blocks(B, T, gap, BN);
+  out[0] = (used + per_tile - 1) / per_tile; out[1] = donor; out[2] = used; out[3] = 0;
+  int* e = out + tail_pack_entries_at(B) + 4 * (long)used;
+  for (int k = used; k < cap; ++k, e += 4) { e[0] = 0; e[1] = 0; e[2] = 0; e[3] = 0; }
+}
 size_t launch_tail_map_ints(int B, int T, int BN);
 void launch_tail_maps(const int* lens, int B, const TailMapJobs& jobs, int n, unsigned long long* dropped, hipStream_t s);
 // y[b, m, c] = y[donor, m, c] for every column c of a tile that `map` (launch_tail_maps, tiles of BN columns) dropped
 // from row b; y [B, M, T] with batch stride y_bstride.  16-byte accesses when T, y_bstride and y allow them.
-void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s);
+// packed: `map` is a packed job's table, and row b gets the donor's columns [S_b', T)
+void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s,
+                      bool packed = false);
 // row-exact ragged decode: n rows of a class, given by value from the host (rows / lens hold up to kRaggedChunk
 // entries per launch) -> out[0 .. 4 stride): the source row of every class row, then its length at the three
 // rates of the decoder (len, us len, us^2 len), entry first + i

@@ -832,6 +832,32 @@ __global__ void tail_map_kernel(const int* __restrict__ lens, int B, const TailM
   const int donor = part_b[0];
   __syncthreads();
   const int full = (T + BN - 1) / BN;
+  if (jb.pack_gap > 0) {                // packed job (kernels.h): the block table instead of the tile map
+    const int gap = jb.pack_gap;
+    auto sp_of = [&](int b) { return tail_pack_sp(lens[b], num, reach, T, b == donor); };
+    int s = 0;
+    for (int i = 0; i < per; ++i) { const int b = tid * per + i; if (b < B) s += tail_pack_row_blocks(sp_of(b), gap); }
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) { int run = 0; for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; } }
+    __syncthreads();
+    int run = part[tid];
+    for (int i = 0; i < per; ++i) {
+      const int b = tid * per + i;
+      if (b < B) {
+        const int sp = sp_of(b);
+        out[kTailPackHdr + b] = sp;
+        tail_pack_row(out, B, b, run, sp, gap, jb.pad_right);
+        run += tail_pack_row_blocks(sp, gap);
+        if (b == B - 1) {
+          tail_pack_finish(out, B, T, gap, BN, donor, run);
+          const long left_out = (long)B * full - out[0];         // (the gaps can cost more than short tails save)
+          if (dropped && left_out > 0) atomicAdd(dropped, (unsigned long long)left_out);
+        }
+      }
+    }
+    return;
+  }
   auto tiles_of = [&](int b) {
     if (b == donor) return full;
     long lim = (long)lens[b] * num + reach;
@@ -868,12 +894,13 @@ void launch_tail_maps(const int* lens, int B, const TailMapJobs& jobs, int n, un
 
 // one workgroup per (row m, utterance b): the columns behind the tiles row b kept, from the donor's row m
 template <bool VEC>
-__global__ void tail_fill_kernel(float* __restrict__ y, int64_t y_bstride, int B, int T, int BN, const int* __restrict__ map) {
+__global__ void tail_fill_kernel(float* __restrict__ y, int64_t y_bstride, int B, int T, int BN, const int* __restrict__ map, int packed) {
   const int m = blockIdx.x, b = blockIdx.y;
   const int full = (T + BN - 1) / BN;
-  const int donor = map[B + 1 + (long)B * full];
+  // (packed table: the columns from S_b' on — a multiple of 32, or T)
+  const int donor = packed ? map[1] : map[B + 1 + (long)B * full];
   if (b == donor) return;
-  const long c0 = (long)(map[b + 1] - map[b]) * BN;
+  const long c0 = packed ? (long)map[kTailPackHdr + b] : (long)(map[b + 1] - map[b]) * BN;
   if (c0 >= T) return;
   const float* src = y + (int64_t)donor * y_bstride + (int64_t)m * T;
   float* dst = y + (int64_t)b * y_bstride + (int64_t)m * T;
@@ -884,10 +911,10 @@ __global__ void tail_fill_kernel(float* __restrict__ y, int64_t y_bstride, int B
     for (long c = c0 + threadIdx.x; c < T; c += blockDim.x) dst[c] = src[c];
   }
 }
-void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s) {
+void launch_tail_fill(float* y, int64_t y_bstride, int B, int M, int T, int BN, const int* map, hipStream_t s, bool packed) {
   const bool vec = T % 4 == 0 && y_bstride % 4 == 0 && BN % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-  if (vec) hipLaunchKernelGGL(tail_fill_kernel<true>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map);
-  else hipLaunchKernelGGL(tail_fill_kernel<false>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map);
+  if (vec) hipLaunchKernelGGL(tail_fill_kernel<true>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map, (int)packed);
+  else hipLaunchKernelGGL(tail_fill_kernel<false>, dim3(M, B), dim3(256), 0, s, y, y_bstride, B, T, BN, map, (int)packed);
 }
 
 // row-exact ragged decode: the rows of a class and their lengths at the decoder's three rates, from host values

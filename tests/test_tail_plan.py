@@ -1,6 +1,10 @@
 """"tail_once", host side (no GPU): the reach table of `mbv_tail_plan` against the decoder's receptive field, and the
 tail map's arithmetic (csrc/ops.hip tail_map_kernel, restated here) against the rule it must keep: a tile that holds
-a column below S_b = rate * len_b + reach is never dropped."""
+a column below S_b = rate * len_b + reach is never dropped.
+
+What this file does not establish: that the reach numbers themselves are right.  `mbv_decoder_context` is the same
+index rules walked backwards, and the launches between the first and the last are only checked to be non-decreasing.
+test_tail_reach_oracle.py measures every tap's reach, and that of every launch inside a ResBlock, on the oracle."""
 import pytest
 import torch
 

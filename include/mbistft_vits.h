@@ -1270,6 +1270,45 @@ int mbv_convert_window(const mbv_config *cfg, int first, int count, int64_t fina
 int mbv_convert_ranges_plan(const mbv_config *cfg, int n, const int32_t *window_frames, int32_t *run_of_range);
 int mbv_convert_ranges(mbv_model *m, const mbv_convert_range *rows_host, int n, int hop, int win, void *stream);
 
+/* ---- live voice conversion with a bounded look-ahead (opt-in) ------
+ * The reach R of mbv_converter_context is what the layers CAN see, and a live call cannot wait that long.  A window
+ * that ends `ahead` frames behind its range, 0 <= ahead <= R, is well defined: the row of the padded run ends there,
+ * every layer is masked there, and the kept frames are what the model gives for a recording whose spectrogram ends
+ * there.  It is an approximation of the full-context z_hat; how close is a property of the weights, not of this code.
+ *
+ * mbv_convert_window_ahead (host only): mbv_convert_window with the window's end at first + count + ahead, clipped to
+ * final_frames.  1 on bad arguments (those of mbv_convert_window, ahead outside [0, R]).
+ * mbv_convert_ranges_ahead: mbv_convert_ranges with one look-ahead per row, ahead_host [n] HOST memory; ahead_host ==
+ * NULL is mbv_convert_ranges (every row at R).  Several rows may name disjoint ranges of one recording (the blocks of
+ * a fixed grid that came due together).  Refused before any launch, naming the row: an ahead outside [0, R], first +
+ * count + ahead beyond mbv_spectrogram_ready while open, two rows whose ranges overlap in one z, and everything
+ * mbv_convert_ranges refuses.  Counted by mbv_converter_runs.
+ *
+ * Seams.  With a short look-ahead of the decoder, the end of chunk k and the start of chunk k + 1 are two
+ * approximations of one signal.  A stream that wants them to meet decodes chunk k a little past its end (the
+ * overhang), keeps the first `seam` overhang samples p, and cross-fades the first `seam` samples q of chunk k + 1:
+ *   q[i] <- p[i] w_p(i) + q[i] w_q(i),  w_p = (float)(seam - i) inv,  w_q = (float)(i + 1) inv,  inv = 1.0f / (float)(seam + 1)
+ * every product and the sum rounded to fp32 once, in that order (no fused multiply-add).
+ * mbv_seam_rows: ONE launch for n streams.  Per row: the blend of o[head_first + i], i < head_count, with stash[i];
+ * then stash[i] = o[over_first + i], i < over_count.  Rows with both counts 0 are skipped.  rows_host is HOST memory.
+ * Refused before any launch, naming the row: a NULL pointer, seam outside [1, 2^20], a count outside [0, seam], a
+ * range outside [0, o_samples), a head that overlaps its overhang, two rows that share a stash or blend the same
+ * samples.  No synchronisation.  mbv_seam_runs counts the launches since mbv_create. */
+typedef struct mbv_seam_row {
+  float *o;                      /* DEVICE [o_samples], the stream's waveform */
+  int64_t o_samples;
+  int64_t head_first;            /* the decoded chunk's first sample */
+  int64_t over_first;            /* the first sample behind the chunk */
+  float *stash;                  /* DEVICE [seam], the stream's own */
+  int32_t head_count, over_count, seam, reserved;
+} mbv_seam_row;
+int mbv_convert_window_ahead(const mbv_config *cfg, int first, int count, int ahead, int64_t final_frames,
+                             int32_t out[2]);
+int mbv_convert_ranges_ahead(mbv_model *m, const mbv_convert_range *rows_host, const int32_t *ahead_host, int n, int hop,
+                             int win, void *stream);
+int mbv_seam_rows(mbv_model *m, const mbv_seam_row *rows_host, int n, void *stream);
+int64_t mbv_seam_runs(mbv_model *m);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"

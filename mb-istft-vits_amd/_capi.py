@@ -49,6 +49,7 @@ SYMBOLS = [
     "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped", "mbv_resample_turns_shaped",
     "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
     "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined", "mbv_speaker_runs",
+    "mbv_convert_window_ahead", "mbv_convert_ranges_ahead", "mbv_seam_rows", "mbv_seam_runs",
 ]
 
 
@@ -225,6 +226,13 @@ class MbvConvertRange(C.Structure):
                 ("z_stride", C.c_int64)]
 
 
+class MbvSeamRow(C.Structure):
+    """mbv_seam_row of include/mbistft_vits.h (mbv_seam_rows)."""
+    _fields_ = [("o", C.c_void_p), ("o_samples", C.c_int64), ("head_first", C.c_int64), ("over_first", C.c_int64),
+                ("stash", C.c_void_p), ("head_count", C.c_int32), ("over_count", C.c_int32), ("seam", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class MbvResampleRange(C.Structure):
     """mbv_resample_range of include/mbistft_vits.h (mbv_resample_ranges)."""
     _fields_ = [("wave", C.c_void_p), ("wave_dtype", C.c_int32), ("in_avail", C.c_int64), ("in_total", C.c_int64),
@@ -375,7 +383,7 @@ def lib():
     # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
     # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
     # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
-    # turns' two, prosody's four, volume's seven, pitch's four and the voices' five may be absent there, and calling one then raises AttributeError.
+    # turns' two, prosody's four, volume's seven, pitch's four, the voices' five and the bounded look-ahead's four may be absent there, and calling one then raises AttributeError.
     # Everything else, and the in-tree library always, must match the header.
     optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
                 "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
@@ -401,7 +409,8 @@ def lib():
                 "mbv_resample_turns_shaped",
                 "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
                 "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined",
-                "mbv_speaker_runs", "mbv_tail_pack_table") if os.environ.get("MBV_LIB") else ()
+                "mbv_speaker_runs", "mbv_tail_pack_table",
+                "mbv_convert_window_ahead", "mbv_convert_ranges_ahead", "mbv_seam_rows", "mbv_seam_runs") if os.environ.get("MBV_LIB") else ()
     if hasattr(L, "mbv_ragged_classes") or not optional:
         L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
         L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
@@ -538,6 +547,12 @@ def lib():
         L.mbv_speaker_defined.argtypes = [vp, C.c_int64]
         L.mbv_speaker_runs.argtypes = [vp]
         L.mbv_speaker_runs.restype = C.c_int64
+    if hasattr(L, "mbv_convert_ranges_ahead") or not optional:
+        L.mbv_convert_window_ahead.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, C.c_int64, C.POINTER(C.c_int32 * 2)]
+        L.mbv_convert_ranges_ahead.argtypes = [vp, C.POINTER(MbvConvertRange), C.POINTER(C.c_int32), i32, i32, i32, vp]
+        L.mbv_seam_rows.argtypes = [vp, C.POINTER(MbvSeamRow), i32, vp]
+        L.mbv_seam_runs.argtypes = [vp]
+        L.mbv_seam_runs.restype = C.c_int64
     for s in SYMBOLS:
         if s not in optional or hasattr(L, s):
             getattr(L, s)      # AttributeError if the header and the library ever drift

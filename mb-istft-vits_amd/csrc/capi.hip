@@ -148,6 +148,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t wire_runs = 0;           // resample / int16 launches of the ranged and the pooled wire step (mbv_wire_runs)
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
   int64_t warp_runs = 0;           // launches of the time-warp kernel (mbv_warp_runs)
+  int64_t seam_runs = 0;           // launches of the chunk-seam kernel (mbv_seam_runs)
   float* warp_win[2] = {nullptr, nullptr};   // filter -> fp32 window and its differences on the device (mbv_warp_ranges)
   // blended voices (mbv_speakers_define): the rows, the defined words and the definition table on the device, all
   // allocated by the first definition and outside the weight arena; `voices` is every slot's host copy
@@ -4441,6 +4442,53 @@ int mbv_warp_ranges(mbv_model* m, const mbv_warp_row* rows_host, int n, void* st
 
 int64_t mbv_warp_runs(mbv_model* m) { return m ? m->warp_runs : -1; }
 
+// ------------------------------------------------------------------ chunk seams of a bounded look-ahead
+int mbv_seam_rows(mbv_model* m, const mbv_seam_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_seam_rows";
+  if (n < 1 || n > 65535 || !rows_host) return m->fail("%s: bad arguments (1 .. 65535 rows expected)", who);
+  DEVICE_GUARD(m);
+  std::vector<int> live;
+  int max_seam = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_seam_row& k = rows_host[i];
+    if (!k.o || !k.stash) return m->fail("%s: row %d: o or stash missing", who, i);
+    if (k.seam < 1 || k.seam > kSeamMax) return m->fail("%s: row %d: seam %d outside [1, %d] samples", who, i, k.seam, kSeamMax);
+    if (k.head_count < 0 || k.head_count > k.seam || k.over_count < 0 || k.over_count > k.seam)
+      return m->fail("%s: row %d: head_count and over_count lie in [0, seam = %d]", who, i, k.seam);
+    if (k.head_first < 0 || k.over_first < 0 || k.o_samples < 0 || k.head_first + k.head_count > k.o_samples ||
+        k.over_first + k.over_count > k.o_samples)
+      return m->fail("%s: row %d: head [%lld, +%d) or overhang [%lld, +%d) outside the %lld samples of o", who, i,
+                     (long long)k.head_first, k.head_count, (long long)k.over_first, k.over_count, (long long)k.o_samples);
+    if (k.head_count && k.over_count && k.head_first < k.over_first + k.over_count && k.over_first < k.head_first + k.head_count)
+      return m->fail("%s: row %d: the head and the overhang overlap", who, i);
+    if (k.head_count || k.over_count) live.push_back(i);
+    if (k.seam > max_seam) max_seam = k.seam;
+  }
+  // a row owns its stash and the samples it blends: two rows on one of them would race
+  auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)rows_host[i].stash; },
+                              [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].seam; });
+  if (clash.first >= 0) return m->fail("%s: rows %d and %d share a stash", who, clash.first, clash.second);
+  clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(rows_host[i].o + rows_host[i].head_first); },
+                         [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].head_count; });
+  if (clash.first >= 0) return m->fail("%s: rows %d and %d blend overlapping samples of one o", who, clash.first, clash.second);
+  if (live.empty()) return 0;
+  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(SeamRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  SeamRow* rows = reinterpret_cast<SeamRow*>(m->scrB);
+  upload_rows<kSeamChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_seam_row& k = rows_host[live[i]];
+    return SeamRow{k.o + k.head_first, k.o + k.over_first, k.stash, k.head_count, k.over_count, k.seam,
+                   1.0f / (float)(k.seam + 1)};
+  });
+  ++m->seam_runs;
+  launch_seam_rows(rows, (int)live.size(), max_seam, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int64_t mbv_seam_runs(mbv_model* m) { return m ? m->seam_runs : -1; }
+
 namespace {
 // what mbv_randn_blocks and mbv_randn_host refuse about one block's range and purpose, or null
 const char* randn_range_error(int64_t first, int64_t count, uint32_t purpose) {
@@ -4897,12 +4945,14 @@ void converter_context(int* L, int* R) {
 // The spectrogram window from which z_hat frames [first, first + count) are computed when `final` frames are final: the
 // context to either side, clipped to the recording, its start aligned down to a whole 32-frame unit of the fused WN
 // layers (so that a frame sits in its unit where the whole-recording run has it).
-void convert_window(int first, int count, int64_t final_frames, int* wa, int* wb) {
+// ahead < 0: the full reach R.  ahead in [0, R] (a bounded look-ahead): the window ends `ahead` frames
+// behind the range, and the row of the padded run ends there as a recording whose spectrogram ends there would.
+void convert_window(int first, int count, int64_t final_frames, int* wa, int* wb, int ahead = -1) {
   int L, R;
   converter_context(&L, &R);
   const int a = first - L > 0 ? first - L : 0;
   *wa = a & ~31;
-  const int64_t b = (int64_t)first + count + R;
+  const int64_t b = (int64_t)first + count + (ahead < 0 ? R : ahead);
   *wb = (int)(b < final_frames ? b : final_frames);
 }
 }  // namespace
@@ -4928,6 +4978,17 @@ int mbv_convert_window(const mbv_config* cfg, int first, int count, int64_t fina
   return 0;
 }
 
+int mbv_convert_window_ahead(const mbv_config* cfg, int first, int count, int ahead, int64_t final_frames, int32_t out[2]) {
+  int L, R;
+  converter_context(&L, &R);
+  if (ahead < 0 || ahead > R) return 1;
+  if (mbv_convert_window(cfg, first, count, final_frames, out)) return 1;
+  int wa, wb;
+  convert_window(first, count, final_frames, &wa, &wb, ahead);
+  out[0] = wa; out[1] = wb;
+  return 0;
+}
+
 int mbv_convert_ranges_plan(const mbv_config* cfg, int n, const int32_t* window_frames, int32_t* run_of_range) {
   if (!cfg || n <= 0 || !window_frames) return -1;
   for (int i = 0; i < n; ++i)
@@ -4937,8 +4998,13 @@ int mbv_convert_ranges_plan(const mbv_config* cfg, int n, const int32_t* window_
 }
 
 int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, int hop, int win, void* stream) {
+  return mbv_convert_ranges_ahead(m, rows_host, nullptr, n, hop, win, stream);
+}
+
+int mbv_convert_ranges_ahead(mbv_model* m, const mbv_convert_range* rows_host, const int32_t* ahead_host, int n, int hop,
+                             int win, void* stream) {
   if (!m) return 1;
-  const char* who = "mbv_convert_ranges";
+  const char* who = ahead_host ? "mbv_convert_ranges_ahead" : "mbv_convert_ranges";
   if (convert_call_refusal(m, who, "live", !rows_host || n <= 0, hop, win)) return 1;
   const mbv_config& c = m->cfg;
   const int n_fft = 2 * (c.spec_channels - 1), B = n;
@@ -4957,12 +5023,14 @@ int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, 
     if (k.first < 0 || k.count < 1 || (int64_t)k.first + k.count > fin)
       return m->fail("%s: row %d: frames [%d, %d + %d) outside the %lld final spectrogram frames", who, i, k.first, k.first,
                      k.count, (long long)fin);
-    if (!k.closed && (int64_t)k.first + k.count + Rv > fin)
+    const int ah = ahead_host ? ahead_host[i] : Rv;
+    if (ah < 0 || ah > Rv) return m->fail("%s: row %d: ahead %d outside [0, %d]", who, i, ah, Rv);
+    if (!k.closed && (int64_t)k.first + k.count + ah > fin)
       return m->fail("%s: row %d: frames [%d, %d + %d) are not final yet: they need spectrogram frames up to %lld, and "
                      "%lld are final (the recording is open)", who, i, k.first, k.first, k.count,
-                     (long long)k.first + k.count + Rv, (long long)fin);
+                     (long long)k.first + k.count + ah, (long long)fin);
     int wa, wb;
-    convert_window(k.first, k.count, fin, &wa, &wb);
+    convert_window(k.first, k.count, fin, &wa, &wb, ah);
     if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < wb))
       return m->fail("%s: row %d: noise missing, or noise_stride %lld < the window's end %d", who, i, (long long)k.noise_stride, wb);
     if (k.z_stride < (int64_t)k.first + k.count)
@@ -4976,6 +5044,11 @@ int mbv_convert_ranges(mbv_model* m, const mbv_convert_range* rows_host, int n, 
     srows[i] = AdmitSynRow{k.noise ? k.noise + wa : nullptr, k.noise_stride, k.noise_scale, k.count,
                            k.z + k.first, wlen[i], k.first - wa, k.z_stride};
   }
+  // several ranges of one recording may share a run (the grid blocks of a bounded look-ahead), never a frame of its z
+  const auto clash = ranges_overlap(B, [&](int i) { return (uintptr_t)(rows_host[i].z + rows_host[i].first); },
+                                    [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].count; });
+  if (clash.first >= 0)
+    return m->fail("%s: rows %d and %d write overlapping ranges of one z", who, clash.first, clash.second);
   if (mbv_convert_ranges_plan(&c, B, wlen.data(), nullptr) != 1)
     return m->fail("%s: the %d rows (widest window %d frames) belong to more than one run of mbv_convert_ranges_plan", who, B, T);
   // the target speaker vectors stay in scratch; the planner sees a length past the narrow kernel's for every window

@@ -840,6 +840,24 @@ void launch_randn_blocks(const RandnRow* rows, int n, int64_t total, hipStream_t
 // the same values on the host (fp32 logf / sqrtf / sinf / cosf): frames [first, first + count) of channel c
 void randn_host(uint64_t seed, uint32_t purpose, uint32_t row, uint32_t c, int64_t first, int64_t count, float* dst);
 
+// ---------------------------------------------------------------- chunk seams (ops.hip)
+// A table row (in the arena, upload_rows): one stream that decoded a chunk under a bounded look-ahead with a seam of
+// `seam` samples.  The chunk's first `head_count` samples q[i] become p[i] w_p(i) + q[i] w_q(i), p = the stash (what the
+// previous decode gave for the same samples), w_p = (float)(seam - i) inv, w_q = (float)(i + 1) inv, each product and
+// the sum rounded once (no contraction); then the first `over_count` samples behind the chunk go to the stash.  head and
+// over never overlap and no two rows share a stash or a head (checked by mbv_seam_rows).
+struct SeamRow {
+  float* head;                 // the chunk's first sample
+  const float* over;           // the first sample behind the chunk
+  float* stash;                // [seam]
+  int32_t head_count, over_count, seam;
+  float inv;                   // 1.0f / (float)(seam + 1)
+};
+constexpr int kSeamChunk = 64;      // rows per upload_rows launch: 64 x 40 bytes = 2.5 KiB of kernel arguments
+constexpr int kSeamMax = 1 << 20;   // samples of a seam
+// every row of the table in ONE launch: grid (ceil(max_seam / 256), n), 1 <= n <= 65535
+void launch_seam_rows(const SeamRow* rows, int n, int max_seam, hipStream_t s);
+
 // ---------------------------------------------------------------- loudness (loudness.hip)
 // ITU-R BS.1770 integrated loudness of mono fp32 rows, measured in 100 ms segments of H samples.  The K-weighting
 // cascade runs in transposed direct form II, state (s1, s2) of the shelf then (s1, s2) of the high-pass, in fp64:

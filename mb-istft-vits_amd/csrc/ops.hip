@@ -413,6 +413,23 @@ void launch_token_marks(const int* cum, int B, int T, int64_t* dst, int64_t stri
                      rows);
 }
 
+// Chunk seams of a bounded look-ahead (mbv_seam_rows): row = blockIdx.y of the table, sample i of its seam.
+// The blend is written with __fmul_rn / __fadd_rn so that no product is contracted into the sum: a restatement in fp32
+// on the host is bitwise.  Thread i reads stash[i] before it writes it, and a row's head and overhang never overlap.
+__global__ __launch_bounds__(256) void seam_rows_kernel(const SeamRow* __restrict__ rows) {
+  const SeamRow r = rows[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < r.head_count) {
+    const float w_p = __fmul_rn((float)(r.seam - i), r.inv), w_q = __fmul_rn((float)(i + 1), r.inv);
+    r.head[i] = __fadd_rn(__fmul_rn(r.stash[i], w_p), __fmul_rn(r.head[i], w_q));
+  }
+  if (i < r.over_count) r.stash[i] = r.over[i];
+}
+
+void launch_seam_rows(const SeamRow* rows, int n, int max_seam, hipStream_t s) {
+  hipLaunchKernelGGL(seam_rows_kernel, dim3((unsigned)((max_seam + 255) / 256), n), dim3(256), 0, s, rows);
+}
+
 // Frame gains (mbv_frame_gain / mbv_frame_gain_rows / mbv_op_frame_gain, kernels.h): out[t] = gain[j(t)], j(t) the
 // token expand_kernel gives frame t (the same search over the same scan), held behind the row's kept frames; all 1.0f
 // for a flagged or empty row.  One thread per entry of [0, frames]; only loads and one store, so a copy.

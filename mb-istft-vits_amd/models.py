@@ -1925,6 +1925,11 @@ class SynthesizerTrn(nn.Module):
         (`mbv_converter_runs`): the difference across a call is the number of launch chains it cost."""
         return int(_capi.lib().mbv_converter_runs(self._ensure_handle()))
 
+    def seam_runs(self):
+        """Launches of the chunk-seam kernel on this model's handle so far (`mbv_seam_runs`): one per `poll()` /
+        `StreamPool.step()` decode call in which a live stream opened with `Ahead(seam_ms=)` decoded."""
+        return int(_capi.lib().mbv_seam_runs(self._ensure_handle()))
+
     def convert_stream(self, wave, sid_src, sid_tgt, model_sr, hop_size, win_size, in_sr=None, noise_scale=1.0,
                        chunk_frames=32, max_chunk_frames=256, noise=None, seed=None):
         """Voice conversion of one recording up to z_hat, as a `DecodeStream`: resample to `model_sr` if `in_sr`
@@ -1950,7 +1955,7 @@ class SynthesizerTrn(nn.Module):
 
     def convert_live(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
                      noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None,
-                     seed=None):
+                     seed=None, ahead=None):
         """Voice conversion of a recording that is still arriving: a `stream.LiveStream` that takes the samples in
         `push` calls of any size and hands out decoded chunks from `poll` as soon as the audio they depend on exists
         (DESIGN 7.11).  The result does not depend on how the samples were cut into pushes; for a recording of more
@@ -1960,10 +1965,13 @@ class SynthesizerTrn(nn.Module):
         `noise`): then the capacity buffer is filled once, as one `mbv_randn_blocks` block, and since element (c, t)
         does not depend on the buffer's length the stream equals `convert_stream(whole, ..., seed=[s])`.  Buffers are
         sized for `max_samples` once.  The audio must be at the model's rate; `wire.convert_live_pcm16` is the form that
-        takes raw samples at any rate and hands out int16 at the service's rate."""
+        takes raw samples at any rate and hands out int16 at the service's rate.  `ahead` (a
+        `stream.Ahead`, opt-in): conversion on a fixed grid of `convert_frames` with a bounded look-ahead,
+        for a call that is live; an approximation of the full-context stream with an exact definition."""
         return stream.LiveStream(self, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=dtype,
                                  noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
-                                 max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr, seed=seed)
+                                 max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr, seed=seed,
+                                 ahead=ahead)
 
     def convert_streams(self, requests):
         """Pooled voice conversion: one single-utterance `DecodeStream` per `ConvertRequest`, in order — what

@@ -18,6 +18,10 @@ stream yields alone.
 Audio that is still arriving: a `LiveStream` (`net.convert_live`) takes a recording in `push` calls, converts z_hat
 frames from spectrogram windows as soon as the samples they depend on exist (`LivePlan`, `mbv_convert_ranges`) and
 decodes every chunk whose z-window is final; a `StreamPool` serves live streams next to finished ones.
+
+A live call cannot wait for the full reach of the layers: `Ahead(conv, dec)` bounds how far a block of z_hat frames and
+a decoder chunk look to their right, on a fixed grid, so that the result is still a pure function of the recording
+(opt-in, an approximation with an exact definition: DESIGN §7.25).
 """
 import ctypes as C
 import math
@@ -157,7 +161,8 @@ def check_closable(arrived, sr, n_fft, hop_size):
 def _decode_chunks(net, work):
     """One decoder call for `work` = [(stream, first, count), ...], each a chunk its stream is ready for: the streams
     fill the `MbvChunk` table (`_fill_chunk`) and are told what was decoded (`_chunk_decoded`).  A member that names
-    a route length (a recording that is still growing) makes it `mbv_decode_chunks_routed`."""
+    a route length (a recording that is still growing) makes it `mbv_decode_chunks_routed`.  Members with a seam
+    (`Ahead(seam_ms=)`, at most one chunk of each in `work`) then share ONE `mbv_seam_rows` launch."""
     arr = (_capi.MbvChunk * len(work))()
     route = (C.c_int32 * len(work))()
     for i, (st, first, count) in enumerate(work):
@@ -166,18 +171,78 @@ def _decode_chunks(net, work):
         net._call("mbv_decode_chunks_routed", arr, route, len(work))
     else:
         net._call("mbv_decode_chunks", arr, len(work))
+    seams = [w for w in work if getattr(w[0], "seam", 0)]
+    if seams:
+        rows = (_capi.MbvSeamRow * len(seams))()
+        if sum(st._fill_seam(row, first, count) for row, (st, first, count) in zip(rows, seams)):
+            net._call("mbv_seam_rows", rows, len(seams))
     for st, first, count in work:
         st._chunk_decoded(first, count)
 
 
 def _convert_ranges(net, todo, hop_size, win_size):
-    """One `mbv_convert_ranges` run for `todo` = [(live stream, (a, b)), ...], the z_hat range due on each."""
+    """One `mbv_convert_ranges` run for `todo` = [(live stream, (a, b)), ...], a z_hat range due on each; with a member
+    of a bounded look-ahead among them (whose grid blocks may be several rows) it is `mbv_convert_ranges_ahead`, the
+    other members at the full reach."""
     rows = (_capi.MbvConvertRange * len(todo))()
     for row, (st, due) in zip(rows, todo):
         st._fill_range(row, *due)
-    net._call("mbv_convert_ranges", rows, len(todo), hop_size, win_size)
+    if any(st._plan.ahead is not None for st, _ in todo):
+        ahead = (C.c_int32 * len(todo))(*[st._plan.conv_ahead for st, _ in todo])
+        net._call("mbv_convert_ranges_ahead", rows, ahead, len(todo), hop_size, win_size)
+    else:
+        net._call("mbv_convert_ranges", rows, len(todo), hop_size, win_size)
     for st, due in todo:
         st._plan.converted(*due)
+
+
+def _convert_live(net, members):
+    """The z_hat ranges due on every live stream among `members` (the grid blocks of a bounded one are several), in one
+    `mbv_convert_ranges` run per run of the planner."""
+    by_cfg = {}
+    for st in members:
+        for due in st._due_blocks():
+            st._check_handle()
+            by_cfg.setdefault((st.hop_size, st.win_size), []).append((st, due))
+    L = _capi.lib()
+    for (hop, win), todo in by_cfg.items():
+        n = len(todo)
+        wl = (C.c_int32 * n)(*[st._window_frames(*due) for st, due in todo])
+        run_of = (C.c_int32 * n)()
+        n_runs = L.mbv_convert_ranges_plan(C.byref(todo[0][0]._cfg_struct), n, wl, run_of)
+        if n_runs < 1:
+            raise ValueError("mbv_convert_ranges_plan refused the windows (one beyond the fused WN layers?)")
+        for r in range(n_runs):
+            _convert_ranges(net, [t for t, k in zip(todo, run_of) if k == r], hop, win)
+
+
+class Ahead:
+    """A bounded look-ahead of a live stream: a block of z_hat frames is converted from a spectrogram
+    window that ends `conv` frames behind it (0 <= conv <= R_conv of `converter_context`), a chunk is decoded from the
+    z_hat frames up to `dec` behind it (0 <= dec <= R_dec of `decoder_context`).  `seam_ms` > 0 cross-fades the first
+    round(seam_ms * model_sr / 1000) samples of every chunk with what the previous decode gave for them (5 ms is a
+    sensible value: a convention, not a measurement).  `Ahead(R_conv, R_dec)` is bitwise the stream without it."""
+
+    __slots__ = ("conv", "dec", "seam_ms")
+
+    def __init__(self, conv, dec, seam_ms=0.0):
+        for name, v in (("conv", conv), ("dec", dec)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("Ahead: %s must be an integer number of frames, got %r" % (name, v))
+            if v < 0:
+                raise ValueError("Ahead: %s must be >= 0, got %d" % (name, v))
+        if isinstance(seam_ms, bool) or not isinstance(seam_ms, (int, float, np.integer, np.floating)):
+            raise TypeError("Ahead: seam_ms must be a number of milliseconds, got %r" % (seam_ms,))
+        if not math.isfinite(seam_ms) or seam_ms < 0:
+            raise ValueError("Ahead: seam_ms must be finite and >= 0, got %r" % (seam_ms,))
+        self.conv, self.dec, self.seam_ms = int(conv), int(dec), float(seam_ms)
+
+    def __repr__(self):
+        return "Ahead(%d, %d%s)" % (self.conv, self.dec, ", seam_ms=%g" % self.seam_ms if self.seam_ms else "")
+
+    def seam_samples(self, model_sr):
+        """S = round(seam_ms * model_sr / 1000) (0 without a seam)."""
+        return int(round(self.seam_ms * int(model_sr) / 1000.0)) if self.seam_ms else 0
 
 
 class LivePlan:
@@ -188,9 +253,20 @@ class LivePlan:
       conversion            launches when >= `convert_frames` new z_hat frames may be converted, or on close
       chunk (first, count)  decodable iff z_hat frames up to first + count + R_dec are converted, or closed
     Chunks are those of `chunk_schedule(T, chunk_frames, max_chunk_frames)`: only the cut of the last one depends on T,
-    and while the recording is open a decodable chunk lies R_dec frames before the end, so it is never the cut one."""
+    and while the recording is open a decodable chunk lies R_dec frames before the end, so it is never the cut one.
 
-    def __init__(self, n_fft, hop_size, r_conv, r_dec, chunk_frames=32, max_chunk_frames=256, convert_frames=32):
+    With `ahead=Ahead(conv, dec)` conversion runs on a fixed grid instead, cf = `convert_frames`:
+      block k               z_hat frames [k cf, min((k + 1) cf, T)), converted from the spectrogram window that ends at
+                            E_k = min((k + 1) cf + conv, T); due iff E_k frames are final, or closed.  `convert_due()`
+                            returns the list of all blocks due (possibly empty)
+      chunk (first, count)  decoded with t_frames = D = min(first + count + dec, T) (`t_frames`), decodable iff z_hat
+                            frames up to D are converted
+      seam                  S samples (`seam`, needs `model_sr` and `samples_per_frame`): the chunk is decoded
+                            `overhang(first, count)` = min(ceil(S / spf), D - first - count) frames past its end
+    so that what is converted and decoded, and from what, does not depend on the pushes."""
+
+    def __init__(self, n_fft, hop_size, r_conv, r_dec, chunk_frames=32, max_chunk_frames=256, convert_frames=32,
+                 ahead=None, model_sr=None, samples_per_frame=None):
         self.n_fft, self.hop = int(n_fft), int(hop_size)
         self.r_conv, self.r_dec = int(r_conv), int(r_dec)
         c, cap, cf = int(chunk_frames), int(max_chunk_frames), int(convert_frames)
@@ -199,9 +275,25 @@ class LivePlan:
         if cf < 1:
             raise ValueError("convert_frames must be >= 1")
         self.convert_frames = cf
+        self.ahead, self.seam, self._over_frames = ahead, 0, 0
+        if ahead is not None:
+            if not isinstance(ahead, Ahead):
+                raise TypeError("ahead must be a stream.Ahead or None, got %r" % (ahead,))
+            if ahead.conv > self.r_conv or ahead.dec > self.r_dec:
+                raise ValueError("%r looks further than the model can: conv <= %d, dec <= %d" % (ahead, self.r_conv, self.r_dec))
+            if ahead.seam_ms:
+                if model_sr is None or samples_per_frame is None:
+                    raise ValueError("a seam needs model_sr and samples_per_frame")
+                S, spf = ahead.seam_samples(model_sr), int(samples_per_frame)
+                if not 1 <= S <= spf * min(ahead.dec, c):
+                    raise ValueError("a seam of %g ms is %d samples at %d Hz: it must be 1 .. %d, the samples of the dec = %d "
+                                     "frames a chunk looks ahead and of the smallest chunk (%d frames)"
+                                     % (ahead.seam_ms, S, int(model_sr), spf * min(ahead.dec, c), ahead.dec, c))
+                self.seam, self._over_frames = S, -(-S // spf)
         self.arrived, self.closed = 0, False
         self.z_done = 0                        # z_hat frames [0, z_done) are converted
         self._first, self._c, self._cap = 0, c, cap          # the next chunk to release
+        self._c0 = c
 
     def push(self, n):
         if self.closed:
@@ -220,8 +312,38 @@ class LivePlan:
         """T, once closed."""
         return self.spec_final if self.closed else None
 
+    @property
+    def conv_ahead(self):
+        """Frames a converted range looks to its right: `ahead.conv`, else R_conv."""
+        return self.r_conv if self.ahead is None else self.ahead.conv
+
+    @property
+    def dec_ahead(self):
+        return self.r_dec if self.ahead is None else self.ahead.dec
+
+    def due_blocks(self):
+        """[(a, b), ...]: every z_hat range to convert now, in order (one at most without `ahead`)."""
+        if self.ahead is None:
+            due = self.convert_due()
+            return [] if due is None else [due]
+        f, cf, a, out = self.spec_final, self.convert_frames, self.z_done, []
+        while True:
+            if self.closed:
+                if a >= f:
+                    break
+                b = min(a + cf, f)
+            else:
+                b = a + cf
+                if b + self.ahead.conv > f:
+                    break
+            out.append((a, b))
+            a = b
+        return out
+
     def convert_due(self):
-        """The z_hat range [a, b) to convert now, or None."""
+        """The z_hat range [a, b) to convert now, or None.  With `ahead`: the list of the grid blocks due now."""
+        if self.ahead is not None:
+            return self.due_blocks()
         f = self.spec_final
         b = f if self.closed else max(0, f - self.r_conv)
         a = self.z_done
@@ -239,7 +361,13 @@ class LivePlan:
         first, c, out = self._first, self._c, []
         T = self.spec_final if self.closed else None
         while True:
-            if self.closed:
+            if self.ahead is not None:         # z_hat up to the chunk's D (of the uncut chunk while T is not known)
+                if self.closed and first >= T:
+                    break
+                n = min(c, T - first) if self.closed else c
+                if self.z_done < self.t_frames(first, n):
+                    break
+            elif self.closed:
                 if self.z_done < T or first >= T:
                     break
                 n = min(c, T - first)
@@ -250,6 +378,34 @@ class LivePlan:
             out.append((first, n))
             first, c = first + n, min(2 * c, self._cap)
         return out
+
+    def t_frames(self, first, count):
+        """D of chunk (first, count): the z_hat frames [0, D) it is decoded from, min(first + count + dec, T) (T once
+        closed; a chunk decodable before lies wholly inside the recording).  Without `ahead`: what is converted."""
+        if self.ahead is None:
+            return self.z_done
+        D = first + count + self.ahead.dec
+        return min(D, self.spec_final) if self.closed else D
+
+    def overhang(self, first, count):
+        """Frames chunk (first, count) is decoded past its end for the seam (0 without one)."""
+        return min(self._over_frames, self.t_frames(first, count) - first - count) if self.seam else 0
+
+    def lag(self):
+        """(arrived, frames): the sample count at which the first chunk is released when `poll()` follows every push
+        however small, and the steady-state lag: the largest distance, over the chunks of full size, from a chunk's
+        first frame to the number of final spectrogram frames its release waits for.  Pure integers; without `ahead`
+        the same arithmetic at (R_conv, R_dec), which the unbounded stream meets under such pushes."""
+        cf, conv, dec = self.convert_frames, self.conv_ahead, self.dec_ahead
+        need = lambda first, c: -(-(first + c + dec) // cf) * cf + conv     # final frames chunk (first, c) waits for
+        first, c, cap = 0, self._c0, self._cap
+        arrived = (need(0, c) - 1) * self.hop + self.n_fft - (self.n_fft - self.hop) // 2
+        steady, seen = 0, 0
+        while seen < cf:
+            if c == cap:
+                steady, seen = max(steady, need(first, c) - first), seen + 1
+            first, c = first + c, min(2 * c, cap)
+        return arrived, steady
 
     def next_chunk(self):
         """The next chunk (first, count) if it is decodable now, else None."""
@@ -276,11 +432,16 @@ class LiveStream:
     recording.  z, o, g, the noise block and the sample buffer belong to the stream, so `infer`, `voice_conversion`
     or other streams may run between any two calls.  Once `finished`, `y_lengths` is set and `result()` is
     o[:, :, :256 T].  A `StreamPool` converts and decodes for many live streams in shared launches; chunks it decoded
-    ahead are handed out by the next `poll()` without a launch."""
+    ahead are handed out by the next `poll()` without a launch.
+
+    `ahead=Ahead(conv, dec, seam_ms)` (opt-in) bounds the look-ahead for a call that is live: conversion on
+    the fixed grid of `convert_frames`, every chunk decoded with its canonical t_frames, the first `seam` samples of a
+    chunk cross-faded with the previous decode's overhang (`mbv_seam_rows`).  Still a pure function of the recording;
+    an approximation of the stream without `ahead`, which `Ahead(R_conv, R_dec)` is bitwise."""
 
     def __init__(self, net, sid_src, sid_tgt, model_sr, hop_size, win_size, max_samples, dtype=torch.float32,
                  noise_scale=1.0, noise=None, chunk_frames=32, max_chunk_frames=256, convert_frames=32, in_sr=None,
-                 seed=None):
+                 seed=None, ahead=None):
         import math
         if seed is not None:
             from .models import _row_seeds
@@ -318,7 +479,9 @@ class LiveStream:
         h = net._handle_not_bf16("convert_live", "convert with voice_conversion", why="")
         cfg = net._config_struct()
         self._plan = LivePlan(self.n_fft, self.hop_size, converter_context(cfg)[1], decoder_context(cfg)[1],
-                              chunk_frames, max_chunk_frames, convert_frames)
+                              chunk_frames, max_chunk_frames, convert_frames, ahead=ahead, model_sr=self.model_sr,
+                              samples_per_frame=net.cfg.samples_per_frame)
+        self.ahead, self.seam = ahead, self._plan.seam
         self._cfg_struct = cfg
         self.chunk_frames, self.max_chunk_frames = int(chunk_frames), int(max_chunk_frames)
         self._net, self._h = net, h
@@ -341,6 +504,9 @@ class LiveStream:
             self.z = torch.zeros(1, I, F, device=dev, dtype=torch.float32)
             self.o = torch.empty(1, 1, self.spf * F, device=dev, dtype=torch.float32)
             self.g = net.emb_g(torch.tensor([self.sid_tgt], dtype=torch.int64, device=dev))
+            # what the previous decode gave for the head of the next chunk (`Ahead(seam_ms=)`); never handed out
+            self._stash = torch.zeros(self.seam, device=dev, dtype=torch.float32) if self.seam else None
+        self._stashed = 0             # samples of the stash that hold an overhang
         self.y_lengths = None
         self._chunks = []             # (first, count) of every chunk decoded so far, in order
         self._next = 0                # the chunk poll() hands out next
@@ -372,7 +538,8 @@ class LiveStream:
         return self._plan.z_done
 
     def pending(self):
-        """The z_hat range (a, b) the next `poll()` / `StreamPool.step()` converts, or None."""
+        """The z_hat range (a, b) the next `poll()` / `StreamPool.step()` converts, or None; with `ahead`, the list of
+        the grid blocks it converts."""
         return self._plan.convert_due()
 
     @property
@@ -441,8 +608,12 @@ class LiveStream:
             raise RuntimeError("the model's handle was re-created (device move) since this stream started")
 
     def _window_frames(self, a, b):
-        out = (C.c_int32 * 2)()
-        if _capi.lib().mbv_convert_window(C.byref(self._cfg_struct), a, b - a, self._plan.spec_final, C.byref(out)):
+        out, L, p = (C.c_int32 * 2)(), _capi.lib(), self._plan
+        if p.ahead is None:
+            rc = L.mbv_convert_window(C.byref(self._cfg_struct), a, b - a, p.spec_final, C.byref(out))
+        else:
+            rc = L.mbv_convert_window_ahead(C.byref(self._cfg_struct), a, b - a, p.ahead.conv, p.spec_final, C.byref(out))
+        if rc:
             raise _capi.MbvError("mbv_convert_window refused [%d, %d)" % (a, b))
         return int(out[1]) - int(out[0])
 
@@ -455,13 +626,26 @@ class LiveStream:
 
     def _fill_chunk(self, k, first, count):
         """-> the route length: the class a finished recording of more than 256 frames is decoded in."""
-        t = self._plan.z_done
+        t = self._plan.t_frames(first, count)      # (what is converted; with `ahead` the chunk's canonical D)
         k.z, k.z_stride, k.t_frames = self.z.data_ptr(), self.z.stride(1), t
-        k.g, k.first, k.count, k.o = self.g.data_ptr(), first, count, self.o.data_ptr()
+        k.g, k.first, k.o = self.g.data_ptr(), first, self.o.data_ptr()
+        k.count = count + self._plan.overhang(first, count)
         return max(t, 257)
 
-    def _convert_due(self):
-        return self._plan.convert_due()
+    def _fill_seam(self, row, first, count):
+        """The `MbvSeamRow` of chunk (first, count), just decoded with its overhang: its head is blended with the stash,
+        then its overhang is stashed.  -> whether the row does anything."""
+        spf, S = self.spf, self.seam
+        head = min(self._stashed, S, spf * count)
+        over = min(S, spf * self._plan.overhang(first, count))
+        row.o, row.o_samples, row.stash, row.seam = self.o.data_ptr(), self.o.shape[-1], self._stash.data_ptr(), S
+        row.head_first, row.head_count = spf * first, head
+        row.over_first, row.over_count = spf * (first + count), over
+        self._stashed = over
+        return bool(head or over)
+
+    def _due_blocks(self):
+        return self._plan.due_blocks()
 
     def _next_chunk(self):
         return self._plan.next_chunk()
@@ -475,21 +659,26 @@ class LiveStream:
         return self._plan.all_released
 
     def _convert(self):
-        due = self._convert_due()
+        if self._plan.ahead is not None:           # the grid blocks due, as rows of the planner's runs
+            _convert_live(self._net, [self])
+            return
+        due = self._plan.convert_due()
         if due is None:
-            return False
+            return
         self._check_handle()
         _convert_ranges(self._net, [(self, due)], self.hop_size, self.win_size)
-        return True
 
     def poll(self):
         """Convert what the rules allow, decode every chunk that has become decodable (all of them in one
-        `mbv_decode_chunks_routed` call) and hand out every chunk not handed out yet: [(first_sample, view), ...]."""
+        `mbv_decode_chunks_routed` call; under a seam one call and one `mbv_seam_rows` launch per chunk) and hand out
+        every chunk not handed out yet: [(first_sample, view), ...]."""
         self._convert()
         todo = self._plan.decodable()
         if todo:
             self._check_handle()
-            _decode_chunks(self._net, [(self, first, count) for first, count in todo])
+            # under a seam a chunk's overhang lies where the next chunk is decoded, and is stashed in between: a call each
+            for part in ([[c] for c in todo] if self.seam else [todo]):
+                _decode_chunks(self._net, [(self, first, count) for first, count in part])
         out = []
         while self._next < self._decoded:
             first, count = self._chunks[self._next]
@@ -564,8 +753,8 @@ class DecodeStream:
         return self.o
 
     # ---- what a pool shares (StreamPool.step), as `LiveStream` has it
-    def _convert_due(self):
-        return None                   # z is whole
+    def _due_blocks(self):
+        return []                     # z is whole
 
     def _next_chunk(self):
         return self.schedule[self._decoded] if self._decoded < len(self.schedule) else None
@@ -650,23 +839,9 @@ class StreamPool:
         return sts
 
     def _convert_live(self, members):
-        """The pending z_hat windows of every live member in one `mbv_convert_ranges` run per run of the planner."""
-        by_cfg = {}
-        for st in members:
-            due = st._convert_due()
-            if due is not None:
-                st._check_handle()
-                by_cfg.setdefault((st.hop_size, st.win_size), []).append((st, due))
-        net, L = self._net, _capi.lib()
-        for (hop, win), todo in by_cfg.items():
-            n = len(todo)
-            wl = (C.c_int32 * n)(*[st._window_frames(*due) for st, due in todo])
-            run_of = (C.c_int32 * n)()
-            n_runs = L.mbv_convert_ranges_plan(C.byref(todo[0][0]._cfg_struct), n, wl, run_of)
-            if n_runs < 1:
-                raise ValueError("mbv_convert_ranges_plan refused the windows (one beyond the fused WN layers?)")
-            for r in range(n_runs):
-                _convert_ranges(net, [t for t, k in zip(todo, run_of) if k == r], hop, win)
+        """The pending z_hat windows of every live member, bounded or not, in one `mbv_convert_ranges` run per run of
+        the planner."""
+        _convert_live(self._net, members)
 
     def step(self, streams=None):
         """Live members first convert their pending windows together (`_convert_live`); then at most one chunk per

@@ -1207,7 +1207,7 @@ class LiveWire(_WireOut):
     def __init__(self, net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                  dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                  chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                 encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None):
+                 encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None, ahead=None):
         from .stream import LiveStream
         _refuse_envelope(envelope, "convert_live_pcm16")
         _refuse_pitch(pitch, "convert_live_pcm16")
@@ -1236,7 +1236,7 @@ class LiveWire(_WireOut):
         self.live = LiveStream(net, sid_src, sid_tgt, model_sr, hop_size, win_size, cap,
                                dtype=torch.float32 if resamples else dtype, noise_scale=noise_scale, noise=noise,
                                chunk_frames=chunk_frames, max_chunk_frames=max_chunk_frames,
-                               convert_frames=convert_frames, seed=seed)
+                               convert_frames=convert_frames, seed=seed, ahead=ahead)
         live = self.live
         self._plan = LiveWirePlan(self.in_sr, model_sr, rate, live.plan, live.spf, self.max_samples, res_type,
                                   lookahead=lim[1] if lim else 0)
@@ -1368,7 +1368,7 @@ class LiveWire(_WireOut):
 def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples,
                        dtype=torch.int16, peak=None, res_type="kaiser_best", noise_scale=1.0, noise=None,
                        chunk_frames=32, max_chunk_frames=256, convert_frames=32, seed=None, limiter=None,
-                       encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None):
+                       encoding="pcm16", in_encoding=None, loudness=None, envelope=None, pitch=None, ahead=None):
     """The live form of `convert_pcm16`: raw samples in at `in_sr` (int16 or fp32; G.711 bytes with `dtype=torch.uint8,
     in_encoding="ulaw" | "alaw"`, which needs `in_sr != model_sr`) while the recording arrives, int16 out at `rate`
     (G.711 bytes with `encoding="ulaw" | "alaw"`); -> a `LiveWire`.  `max_samples` counts raw samples; `noise`, when given, is the block of the
@@ -1378,13 +1378,16 @@ def convert_live_pcm16(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, w
     `stream_pcm16(net, convert_stream(whole, ..., in_sr=in_sr, noise=...), model_sr, rate, peak=peak).run()`.  `seed`
     (as `convert_live` takes it; excludes `noise`) fills that block from the seeded generator instead.  `loudness` as
     `stream_pcm16` takes it: `measured` is required with a target, and the wire keeps `.loudness`.  `envelope` is refused
-    (ValueError): a converted recording has no tokens to take a volume from; `pitch` likewise (§7.22)."""
+    (ValueError): a converted recording has no tokens to take a volume from; `pitch` likewise (§7.22).
+    `ahead` (a `stream.Ahead`) goes to the `LiveStream`'s plan: a bounded look-ahead of the conversion and
+    the decoder, for a call that is live; it is not the limiter's `lookahead`, which delays the int16 pieces.  Then
+    `pcm` ends bitwise as the wiring of the finished bounded `live.o`."""
     _refuse_envelope(envelope, "convert_live_pcm16")
     _refuse_pitch(pitch, "convert_live_pcm16")
     return LiveWire(net, sid_src, sid_tgt, in_sr, model_sr, rate, hop_size, win_size, max_samples, dtype=dtype,
                     peak=peak, res_type=res_type, noise_scale=noise_scale, noise=noise, chunk_frames=chunk_frames,
                     max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, seed=seed, limiter=limiter,
-                    encoding=encoding, in_encoding=in_encoding, loudness=loudness)
+                    encoding=encoding, in_encoding=in_encoding, loudness=loudness, ahead=ahead)
 
 
 # ---- turns: several utterances as one gapless wire stream (DESIGN §7.18)

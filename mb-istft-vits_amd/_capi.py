@@ -12,47 +12,6 @@ CSRC = os.path.join(_HERE, "csrc")
 # MBV_LIB: another build of the same library (A/B measurements of compile-time switches, scripts/stage_ab.py)
 LIB_PATH = os.environ.get("MBV_LIB") or os.path.join(CSRC, "libmbistft_vits.so")
 
-# every symbol include/mbistft_vits.h declares
-SYMBOLS = [
-    "mbv_abi_version", "mbv_create", "mbv_destroy", "mbv_last_error", "mbv_load_weight",
-    "mbv_finalize_weights", "mbv_missing_weights", "mbv_encode", "mbv_synthesize", "mbv_decode",
-    "mbv_speaker_embedding", "mbv_stage_times_ms", "mbv_istft_pqmf", "mbv_read_stage",
-    "mbv_op_conv1d", "mbv_kernel_times_ms", "mbv_istft_finalize", "mbv_pcm16", "mbv_voice_conversion",
-    "mbv_set_option", "mbv_arena_floats", "mbv_export_arena", "mbv_import_arena", "mbv_ticket", "mbv_stage_times_ms_at", "mbv_op_rel_attention",
-    "mbv_pcm16_samples", "mbv_resample", "mbv_resample_bank", "mbv_op_conv", "mbv_conv_plan",
-    "mbv_spectrogram", "mbv_spectrogram_frames", "mbv_decoder_context", "mbv_decode_range",
-    "mbv_resample_ready", "mbv_resample_pcm16_range",
-    "mbv_ragged_classes", "mbv_decode_ragged", "mbv_synthesize_ragged", "mbv_ragged_plan",
-    "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
-    "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
-    "mbv_op_embed", "mbv_op_layernorm", "mbv_op_durations", "mbv_op_expand", "mbv_op_cond_gemv", "mbv_op_gather_rows",
-    "mbv_op_posterior_sample", "mbv_op_lens", "mbv_op_dds_sep", "mbv_op_dds_res", "mbv_op_sdp_pre", "mbv_op_sdp_spline",
-    "mbv_op_sdp_logw", "mbv_op_sdp_noise", "mbv_op_chan_add", "mbv_op_istft_single",
-    "mbv_align", "mbv_set_durations", "mbv_op_neg_cent", "mbv_op_max_path",
-    "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs", "mbv_get_option",
-    "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked", "mbv_tail_pack_table",
-    "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
-    "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
-    "mbv_convert_ranges_plan", "mbv_convert_ranges",
-    "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
-    "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
-    "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
-    "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range", "mbv_resample_g711_chunks",
-    "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
-    "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
-    "mbv_token_marks", "mbv_token_marks_rows",
-    "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
-    "mbv_loudness_runs",
-    "mbv_turn_plan", "mbv_resample_turns",
-    "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
-    "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
-    "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped", "mbv_resample_turns_shaped",
-    "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
-    "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined", "mbv_speaker_runs",
-    "mbv_convert_window_ahead", "mbv_convert_ranges_ahead", "mbv_seam_rows", "mbv_seam_runs",
-]
-
-
 ABI_VERSION = 3             # MBV_ABI_VERSION of include/mbistft_vits.h
 
 
@@ -251,6 +210,10 @@ G711_LAWS = {"ulaw": 1, "alaw": 2}
 WAVE_F32, WAVE_PCM16, WAVE_ULAW, WAVE_ALAW = 0, 1, 8, 9
 
 
+# MBV_RESAMPLE_* of include/mbistft_vits.h, by librosa.resample's res_type: the filters of the warp and the wire
+RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
+
+
 # MBV_NOISE_* of include/mbistft_vits.h: the `purpose` word of the generator's counter
 NOISE_PRIOR, NOISE_SDP, NOISE_POSTERIOR = 0, 1, 2
 
@@ -283,6 +246,193 @@ ROUTES = {1: "NARROW_M", 2: "NARROW_LAUNCH", 3: "M64", 4: "HALF", 5: "SMALL", 6:
 PLAN_FIELDS = ("route", "bm", "bn", "threads", "ck", "nb_big", "vs_tv", "S")
 
 
+# the header's structs by their C names (mbv_model is opaque; mbv_fit_result has no class: `fit_result` unpacks it)
+STRUCTS = {
+    "mbv_config": MbvConfig, "mbv_outputs": MbvOutputs, "mbv_chunk": MbvChunk, "mbv_enc_row": MbvEncRow,
+    "mbv_row": MbvRow, "mbv_speaker_def": MbvSpeakerDef, "mbv_align_outputs": MbvAlignOutputs,
+    "mbv_pcm_chunk": MbvPcmChunk, "mbv_pcm_limit": MbvPcmLimit, "mbv_resample_range": MbvResampleRange,
+    "mbv_pcm_fade": MbvPcmFade, "mbv_turn_seg": MbvTurnSeg, "mbv_turn_chunk": MbvTurnChunk,
+    "mbv_mark_row": MbvMarkRow, "mbv_fit": MbvFit, "mbv_shape_row": MbvShapeRow, "mbv_gain_row": MbvGainRow,
+    "mbv_pcm_envelope": MbvPcmEnvelope, "mbv_warp_row": MbvWarpRow, "mbv_loudness_chunk": MbvLoudnessChunk,
+    "mbv_randn_block": MbvRandnBlock, "mbv_convert_row": MbvConvertRow, "mbv_convert_range": MbvConvertRange,
+    "mbv_seam_row": MbvSeamRow, "mbv_conv_desc": MbvConvDesc,
+}
+
+
+# Every function include/mbistft_vits.h declares: name -> (restype, argtypes); tests/test_capi_header.py holds each
+# entry to its prototype.  vp stands for every pointer the caller passes as an address (device or host memory, the
+# model handle, the stream); a pointer to a struct or to a fixed array is spelled out.
+P, vp, cstr = C.POINTER, C.c_void_p, C.c_char_p
+i32, i64, u32, u64, f32, f64 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_double
+
+# what every build has to export, a MBV_LIB baseline included
+CORE = {
+    "mbv_abi_version": (i32, []),
+    "mbv_create": (i32, [P(MbvConfig), P(vp)]),
+    "mbv_destroy": (None, [vp]),
+    "mbv_last_error": (cstr, [vp]),
+    "mbv_load_weight": (i32, [vp, cstr, vp, P(i64), i32]),
+    "mbv_finalize_weights": (i32, [vp, vp]),
+    "mbv_missing_weights": (i32, [vp, cstr, C.c_size_t]),
+    "mbv_encode": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, f32, vp, vp]),
+    "mbv_synthesize": (i32, [vp, i32, vp, f32, i32, P(MbvOutputs), vp]),
+    "mbv_decode": (i32, [vp, vp, vp, i32, i32, P(MbvOutputs), vp]),
+    "mbv_speaker_embedding": (i32, [vp, vp, i32, vp, vp]),
+    "mbv_stage_times_ms": (i32, [vp, P(f32 * 5)]),
+    "mbv_istft_pqmf": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "mbv_read_stage": (i64, [vp, cstr, vp, i64, vp]),
+    "mbv_op_conv1d": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "mbv_kernel_times_ms": (i32, [vp, P(f32 * 2)]),
+    "mbv_istft_finalize": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "mbv_pcm16": (i32, [vp, vp, vp, i32, i64, i32, vp, vp]),
+    "mbv_voice_conversion": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, P(MbvOutputs), vp, vp]),
+    "mbv_set_option": (i32, [vp, cstr, i32]),
+    "mbv_arena_floats": (i64, [vp]),
+    "mbv_export_arena": (i32, [vp, vp, i64, vp]),
+    "mbv_import_arena": (i32, [vp, vp, i64, vp]),
+    "mbv_ticket": (i64, [vp]),
+    "mbv_stage_times_ms_at": (i32, [vp, i64, P(f32 * 5)]),
+    "mbv_op_rel_attention": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mbv_pcm16_samples": (i32, [vp, vp, vp, i32, i64, i32, vp, vp]),
+    "mbv_resample": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, vp, i64, vp, vp]),
+    "mbv_resample_bank": (i32, [i32, i32, i32, vp, i64, P(i32), P(i32), P(i32)]),
+    "mbv_op_conv": (i32, [vp, P(MbvConvDesc), vp, vp, vp, vp, vp, vp]),     # plan_out: `int32_t *`, 8 values or NULL
+    "mbv_conv_plan": (i32, [P(MbvConvDesc), P(i32 * 8)]),
+    "mbv_spectrogram": (i32, [vp, vp, i32, vp, i32, i64, i32, i32, i32, vp, i64, vp, vp]),
+    "mbv_spectrogram_frames": (i64, [i64, i32, i32]),
+    "mbv_decoder_context": (i32, [P(MbvConfig), P(i32 * 2)]),
+    "mbv_decode_range": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "mbv_resample_ready": (i64, [i32, i32, i32, i64, i64]),
+    "mbv_resample_pcm16_range": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp, vp]),
+    "mbv_op_embed": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mbv_op_layernorm": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mbv_op_durations": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mbv_op_expand": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mbv_op_cond_gemv": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mbv_op_gather_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "mbv_op_posterior_sample": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mbv_op_lens": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "mbv_op_dds_sep": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "mbv_op_dds_res": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "mbv_op_sdp_pre": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mbv_op_sdp_spline": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, vp]),
+    "mbv_op_sdp_logw": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "mbv_op_sdp_noise": (i32, [vp, vp, f32, vp, i64, vp]),
+    "mbv_op_chan_add": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "mbv_op_istft_single": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "mbv_align": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, P(MbvAlignOutputs), vp, vp]),
+    "mbv_set_durations": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "mbv_op_neg_cent": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mbv_op_max_path": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+}
+# what came after the row-exact ragged decode (the first baseline of the scripts/*_timing.py A/B runs): a MBV_LIB build
+# may lack any of these, and calling one it lacks raises AttributeError.  New entries go here.
+LATER = {
+    "mbv_ragged_classes": (i32, [P(MbvConfig), i32, i32, P(i32), i32]),
+    "mbv_decode_ragged": (i32, [vp, vp, vp, i32, i32, P(i64), vp, vp]),
+    "mbv_synthesize_ragged": (i32, [vp, i32, vp, f32, i32, P(MbvOutputs), P(i64), vp]),
+    "mbv_ragged_plan": (i32, [P(MbvConfig), i32, i32, i32, P(i64), P(i32)]),
+    "mbv_chunks_plan": (i32, [P(MbvConfig), i32, i32, P(i32), P(i32)]),
+    "mbv_decode_chunks": (i32, [vp, P(MbvChunk), i32, vp]),
+    "mbv_decoder_runs": (i64, [vp]),
+    "mbv_pcm_chunks_plan": (i64, [i32, i32, i32, P(MbvPcmChunk), i32, P(i64)]),
+    "mbv_resample_pcm16_chunks": (i32, [vp, P(MbvPcmChunk), i32, i32, i32, i32, vp, i64, vp]),
+    "mbv_wire_runs": (i64, [vp]),
+    "mbv_admit_plan": (i32, [P(MbvConfig), i32, i32, P(i32), P(i32)]),
+    "mbv_encode_rows": (i32, [vp, i32, vp, vp, vp, i32, i32, P(MbvEncRow), vp, vp]),
+    "mbv_synthesize_rows": (i32, [vp, i32, i32, P(MbvRow), i32, vp]),
+    "mbv_encoder_runs": (i64, [vp]),
+    "mbv_get_option": (i32, [vp, cstr]),
+    "mbv_tail_plan": (i32, [P(MbvConfig), P(i32), i32]),
+    "mbv_tail_dropped": (i64, [vp]),
+    "mbv_decode_masked": (i32, [vp, vp, vp, vp, i32, i32, P(MbvOutputs), vp]),
+    "mbv_tail_pack_table": (i32, [P(i64), i32, i32, i32, i32, i32, i32, i32, P(i32), i64]),
+    "mbv_convert_plan": (i32, [P(MbvConfig), i32, i32, P(i32), P(i32)]),
+    "mbv_convert_rows": (i32, [vp, P(MbvConvertRow), i32, i32, i32, i32, vp, vp]),
+    "mbv_converter_runs": (i64, [vp]),
+    "mbv_decode_chunks_routed": (i32, [vp, P(MbvChunk), P(i32), i32, vp]),
+    "mbv_converter_context": (i32, [P(MbvConfig), P(i32 * 2)]),
+    "mbv_spectrogram_ready": (i64, [i64, i32, i32, i32]),
+    "mbv_convert_window": (i32, [P(MbvConfig), i32, i32, i64, P(i32 * 2)]),
+    "mbv_convert_ranges_plan": (i32, [P(MbvConfig), i32, P(i32), P(i32)]),
+    "mbv_convert_ranges": (i32, [vp, P(MbvConvertRange), i32, i32, i32, vp]),
+    "mbv_resample_ready_open": (i64, [i32, i32, i32, i64]),
+    "mbv_resample_ranges": (i32, [vp, P(MbvResampleRange), i32, i32, i32, i32, vp]),
+    "mbv_input_runs": (i64, [vp]),
+    "mbv_randn_blocks": (i32, [vp, P(MbvRandnBlock), i32, vp]),
+    "mbv_randn_host": (i32, [u64, u32, u32, u32, i64, i64, vp]),
+    "mbv_noise_runs": (i64, [vp]),
+    "mbv_limiter_ready": (i64, [i32, i32, i32, i64, i64, i32]),
+    "mbv_resample_pcm16_range_limited": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp,
+                                               P(MbvPcmLimit), vp]),
+    "mbv_resample_pcm16_chunks_limited": (i32, [vp, P(MbvPcmChunk), P(MbvPcmLimit), i32, i32, i32, i32, vp, i64, vp]),
+    "mbv_g711_encode": (i32, [vp, vp, i64, i32, vp, vp]),
+    "mbv_g711_decode": (i32, [vp, vp, i64, i32, vp, vp]),
+    "mbv_resample_g711_range": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp,
+                                      P(MbvPcmLimit), i32, vp]),
+    "mbv_resample_g711_chunks": (i32, [vp, P(MbvPcmChunk), P(MbvPcmLimit), i32, i32, i32, i32, i32, vp, i64, vp]),
+    "mbv_pcm_fade_make": (i32, [i64, i64, P(MbvPcmFade)]),
+    "mbv_resample_pcm16_range_faded": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp,
+                                             P(MbvPcmLimit), P(MbvPcmFade), vp]),
+    "mbv_resample_pcm16_chunks_faded": (i32, [vp, P(MbvPcmChunk), P(MbvPcmLimit), P(MbvPcmFade), i32, i32, i32, i32, vp,
+                                              i64, vp]),
+    "mbv_resample_g711_range_faded": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp,
+                                            P(MbvPcmLimit), i32, P(MbvPcmFade), vp]),
+    "mbv_resample_g711_chunks_faded": (i32, [vp, P(MbvPcmChunk), P(MbvPcmLimit), P(MbvPcmFade), i32, i32, i32, i32, i32,
+                                             vp, i64, vp]),
+    "mbv_token_marks": (i32, [vp, vp, i64, vp]),
+    "mbv_token_marks_rows": (i32, [vp, i32, P(MbvMarkRow), i32, vp]),
+    "mbv_kweighting": (i32, [i32, P(f64), P(f64)]),
+    "mbv_loudness_segments": (i64, [i32, i64, P(i32)]),
+    "mbv_loudness": (i32, [vp, vp, vp, i32, i64, i32, vp, vp, vp]),
+    "mbv_loudness_range": (i32, [vp, vp, vp, i32, i64, i32, i64, i64, i64, vp, vp, i64, vp, vp]),
+    "mbv_loudness_chunks": (i32, [vp, P(MbvLoudnessChunk), i32, i32, vp]),
+    "mbv_loudness_runs": (i64, [vp]),
+    "mbv_turn_plan": (i64, [i32, i32, i32, P(MbvTurnChunk), P(MbvPcmLimit), i32, P(i64)]),
+    "mbv_resample_turns": (i32, [vp, P(MbvTurnChunk), P(MbvPcmLimit), P(MbvPcmFade), i32, i32, i32, i32, i32, vp, i64,
+                                 vp]),
+    "mbv_shape_durations": (i32, [vp, vp, vp, P(MbvFit), i32, i32, vp, vp, vp]),
+    "mbv_shape_durations_rows": (i32, [vp, i32, P(MbvShapeRow), i32, vp, vp]),
+    "mbv_op_shape_durations": (i32, [vp, vp, vp, vp, vp, f32, P(MbvFit), vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "mbv_shape_runs": (i64, [vp]),
+    "mbv_frame_gain": (i32, [vp, vp, vp, i64, i32, vp]),
+    "mbv_frame_gain_rows": (i32, [vp, i32, P(MbvGainRow), i32, vp]),
+    "mbv_op_frame_gain": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "mbv_gain_runs": (i64, [vp]),
+    "mbv_resample_pcm16_range_shaped": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i64, i64, i64, vp, vp, i64, vp, vp,
+                                              P(MbvPcmLimit), i32, P(MbvPcmFade), P(MbvPcmEnvelope), i64, vp]),
+    "mbv_resample_pcm16_chunks_shaped": (i32, [vp, P(MbvPcmChunk), P(MbvPcmLimit), P(MbvPcmFade), P(MbvPcmEnvelope),
+                                               i32, i32, i32, i32, i32, vp, i64, vp]),
+    "mbv_resample_turns_shaped": (i32, [vp, P(MbvTurnChunk), P(MbvPcmLimit), P(MbvPcmFade), P(MbvPcmEnvelope), i32, i32,
+                                        i32, i32, i32, vp, i64, vp]),
+    "mbv_warp_plan": (i32, [i32, i64, vp, vp, P(i64)]),
+    "mbv_warp_ready": (i64, [i32, i64, vp, vp, i32, i64]),
+    "mbv_warp_ranges": (i32, [vp, P(MbvWarpRow), i32, vp]),
+    "mbv_warp_runs": (i64, [vp]),
+    "mbv_speakers_define": (i32, [vp, P(MbvSpeakerDef), i32, vp]),
+    "mbv_speaker_release": (i32, [vp, i32, vp]),
+    "mbv_speaker_slots": (i32, []),
+    "mbv_speaker_defined": (i32, [vp, i64]),
+    "mbv_speaker_runs": (i64, [vp]),
+    "mbv_convert_window_ahead": (i32, [P(MbvConfig), i32, i32, i32, i64, P(i32 * 2)]),
+    "mbv_convert_ranges_ahead": (i32, [vp, P(MbvConvertRange), P(i32), i32, i32, i32, vp]),
+    "mbv_seam_rows": (i32, [vp, P(MbvSeamRow), i32, vp]),
+    "mbv_seam_runs": (i64, [vp]),
+}
+TABLE = {**CORE, **LATER}
+SYMBOLS = list(TABLE)
+
+
+def declare(L, allow_missing):
+    """Give every entry of TABLE that `L` has its restype and argtypes.  A CORE entry must be there; so must a LATER
+    one unless `allow_missing`: an absent one is then left undeclared (AttributeError here, or at the call)."""
+    for name, (restype, argtypes) in TABLE.items():
+        if allow_missing and name in LATER and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+
+
 def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 in-tree (`csrc/build.sh`)."""
     if force:
@@ -311,251 +461,8 @@ def lib():
     # system HIP runtime as a second instance, which then sees no device ("no HIP device visible")
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64p, fp = C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p
-    L.mbv_abi_version.restype = i32
-    L.mbv_create.argtypes = [C.POINTER(MbvConfig), C.POINTER(vp)]
-    L.mbv_destroy.argtypes = [vp]
-    L.mbv_destroy.restype = None
-    L.mbv_last_error.argtypes = [vp]
-    L.mbv_last_error.restype = C.c_char_p
-    L.mbv_load_weight.argtypes = [vp, C.c_char_p, vp, i64p, i32]
-    L.mbv_finalize_weights.argtypes = [vp, vp]
-    L.mbv_missing_weights.argtypes = [vp, C.c_char_p, C.c_size_t]
-    L.mbv_encode.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp, C.c_float, vp, vp]
-    L.mbv_synthesize.argtypes = [vp, i32, vp, C.c_float, i32, C.POINTER(MbvOutputs), vp]
-    L.mbv_decode.argtypes = [vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
-    L.mbv_decoder_context.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32 * 2)]
-    L.mbv_decode_range.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.c_int64, vp]
-    L.mbv_speaker_embedding.argtypes = [vp, vp, i32, vp, vp]
-    L.mbv_stage_times_ms.argtypes = [vp, C.POINTER(C.c_float * 5)]
-    L.mbv_kernel_times_ms.argtypes = [vp, C.POINTER(C.c_float * 2)]
-    L.mbv_istft_pqmf.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
-    L.mbv_istft_finalize.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
-    L.mbv_voice_conversion.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(MbvOutputs), vp, vp]
-    L.mbv_pcm16.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp]
-    L.mbv_pcm16_samples.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp]
-    L.mbv_resample.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
-    L.mbv_resample_bank.argtypes = [i32, i32, i32, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                    C.POINTER(C.c_int32)]
-    L.mbv_resample_ready.argtypes = [i32, i32, i32, C.c_int64, C.c_int64]
-    L.mbv_resample_ready.restype = C.c_int64
-    L.mbv_resample_pcm16_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64,
-                                           vp, vp, C.c_int64, vp, vp, vp]
-    L.mbv_spectrogram.argtypes = [vp, vp, i32, vp, i32, C.c_int64, i32, i32, i32, vp, C.c_int64, vp, vp]
-    L.mbv_spectrogram_frames.argtypes = [C.c_int64, i32, i32]
-    L.mbv_spectrogram_frames.restype = C.c_int64
-    L.mbv_set_option.argtypes = [vp, C.c_char_p, i32]
-    L.mbv_ticket.argtypes = [vp]
-    L.mbv_ticket.restype = C.c_int64
-    L.mbv_stage_times_ms_at.argtypes = [vp, C.c_int64, C.POINTER(C.c_float * 5)]
-    L.mbv_arena_floats.argtypes = [vp]
-    L.mbv_arena_floats.restype = C.c_int64
-    L.mbv_export_arena.argtypes = [vp, vp, C.c_int64, vp]
-    L.mbv_import_arena.argtypes = [vp, vp, C.c_int64, vp]
-    L.mbv_read_stage.argtypes = [vp, C.c_char_p, vp, C.c_int64, vp]
-    L.mbv_read_stage.restype = C.c_int64
-    L.mbv_op_rel_attention.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mbv_op_conv1d.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp]
-    L.mbv_op_conv.argtypes = [vp, C.POINTER(MbvConvDesc), vp, vp, vp, vp, C.POINTER(C.c_int32 * 8), vp]
-    L.mbv_conv_plan.argtypes = [C.POINTER(MbvConvDesc), C.POINTER(C.c_int32 * 8)]
-    f32 = C.c_float
-    L.mbv_op_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mbv_op_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.mbv_op_durations.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.mbv_op_expand.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mbv_op_cond_gemv.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.mbv_op_gather_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.mbv_op_posterior_sample.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.mbv_op_lens.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
-    L.mbv_op_dds_sep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.mbv_op_dds_res.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.mbv_op_sdp_pre.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.mbv_op_sdp_spline.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp]
-    L.mbv_op_sdp_logw.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.mbv_op_sdp_noise.argtypes = [vp, vp, f32, vp, C.c_int64, vp]
-    L.mbv_op_chan_add.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    L.mbv_op_istft_single.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    L.mbv_align.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, f32, C.POINTER(MbvAlignOutputs), vp, vp]
-    L.mbv_set_durations.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.mbv_op_neg_cent.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mbv_op_max_path.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    # MBV_LIB may name the build BEFORE the row-exact ragged decode (the baseline of scripts/ragged_timing.py): only
-    # those four entries, the pooled decode's three, the pooled wire output's three, pooled admission's five, the
-    # three that came with "tail_once", pooled conversion's three, live conversion's six, the live wire's three, the
-    # seeded noise's three, the limiter's three, G.711's four, the fade's five, the marks' two, loudness's six, the
-    # turns' two, prosody's four, volume's seven, pitch's four, the voices' five and the bounded look-ahead's four may be absent there, and calling one then raises AttributeError.
-    # Everything else, and the in-tree library always, must match the header.
-    optional = ("mbv_ragged_classes", "mbv_ragged_plan", "mbv_decode_ragged", "mbv_synthesize_ragged",
-                "mbv_chunks_plan", "mbv_decode_chunks", "mbv_decoder_runs",
-                "mbv_pcm_chunks_plan", "mbv_resample_pcm16_chunks", "mbv_wire_runs",
-                "mbv_admit_plan", "mbv_encode_rows", "mbv_synthesize_rows", "mbv_encoder_runs",
-                "mbv_get_option", "mbv_tail_plan", "mbv_tail_dropped", "mbv_decode_masked",
-                "mbv_convert_plan", "mbv_convert_rows", "mbv_converter_runs",
-                "mbv_decode_chunks_routed", "mbv_converter_context", "mbv_spectrogram_ready", "mbv_convert_window",
-                "mbv_convert_ranges_plan", "mbv_convert_ranges",
-                "mbv_resample_ready_open", "mbv_resample_ranges", "mbv_input_runs",
-                "mbv_randn_blocks", "mbv_randn_host", "mbv_noise_runs",
-                "mbv_limiter_ready", "mbv_resample_pcm16_range_limited", "mbv_resample_pcm16_chunks_limited",
-                "mbv_g711_encode", "mbv_g711_decode", "mbv_resample_g711_range",
-                "mbv_resample_g711_chunks",
-                "mbv_pcm_fade_make", "mbv_resample_pcm16_range_faded", "mbv_resample_pcm16_chunks_faded",
-                "mbv_resample_g711_range_faded", "mbv_resample_g711_chunks_faded",
-                "mbv_token_marks", "mbv_token_marks_rows",
-                "mbv_kweighting", "mbv_loudness_segments", "mbv_loudness", "mbv_loudness_range", "mbv_loudness_chunks",
-                "mbv_loudness_runs", "mbv_turn_plan", "mbv_resample_turns",
-                "mbv_shape_durations", "mbv_shape_durations_rows", "mbv_op_shape_durations", "mbv_shape_runs",
-                "mbv_frame_gain", "mbv_frame_gain_rows", "mbv_op_frame_gain", "mbv_gain_runs",
-                "mbv_resample_pcm16_range_shaped", "mbv_resample_pcm16_chunks_shaped",
-                "mbv_resample_turns_shaped",
-                "mbv_warp_plan", "mbv_warp_ready", "mbv_warp_ranges", "mbv_warp_runs",
-                "mbv_speakers_define", "mbv_speaker_release", "mbv_speaker_slots", "mbv_speaker_defined",
-                "mbv_speaker_runs", "mbv_tail_pack_table",
-                "mbv_convert_window_ahead", "mbv_convert_ranges_ahead", "mbv_seam_rows", "mbv_seam_runs") if os.environ.get("MBV_LIB") else ()
-    if hasattr(L, "mbv_ragged_classes") or not optional:
-        L.mbv_ragged_classes.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), i32]
-        L.mbv_ragged_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, i64p, C.POINTER(C.c_int32)]
-        L.mbv_decode_ragged.argtypes = [vp, vp, vp, i32, i32, i64p, vp, vp]
-        L.mbv_synthesize_ragged.argtypes = [vp, i32, vp, C.c_float, i32, C.POINTER(MbvOutputs), i64p, vp]
-    if hasattr(L, "mbv_decode_chunks") or not optional:
-        L.mbv_chunks_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.mbv_decode_chunks.argtypes = [vp, C.POINTER(MbvChunk), i32, vp]
-        L.mbv_decoder_runs.argtypes = [vp]
-        L.mbv_decoder_runs.restype = C.c_int64
-    if hasattr(L, "mbv_resample_pcm16_chunks") or not optional:
-        L.mbv_pcm_chunks_plan.argtypes = [i32, i32, i32, C.POINTER(MbvPcmChunk), i32, i64p]
-        L.mbv_pcm_chunks_plan.restype = C.c_int64
-        L.mbv_resample_pcm16_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), i32, i32, i32, i32, vp, C.c_int64, vp]
-        L.mbv_wire_runs.argtypes = [vp]
-        L.mbv_wire_runs.restype = C.c_int64
-    if hasattr(L, "mbv_encode_rows") or not optional:
-        L.mbv_admit_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.mbv_encode_rows.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(MbvEncRow), vp, vp]
-        L.mbv_synthesize_rows.argtypes = [vp, i32, i32, C.POINTER(MbvRow), i32, vp]
-        L.mbv_encoder_runs.argtypes = [vp]
-        L.mbv_encoder_runs.restype = C.c_int64
-        L.mbv_get_option.argtypes = [vp, C.c_char_p]
-    if hasattr(L, "mbv_tail_plan") or not optional:
-        L.mbv_tail_plan.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32), i32]
-        L.mbv_tail_dropped.argtypes = [vp]
-        L.mbv_tail_dropped.restype = C.c_int64
-        L.mbv_decode_masked.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(MbvOutputs), vp]
-    if hasattr(L, "mbv_tail_pack_table") or not optional:
-        L.mbv_tail_pack_table.argtypes = [i64p, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.c_int64]
-    if hasattr(L, "mbv_convert_rows") or not optional:
-        L.mbv_convert_plan.argtypes = [C.POINTER(MbvConfig), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.mbv_convert_rows.argtypes = [vp, C.POINTER(MbvConvertRow), i32, i32, i32, i32, vp, vp]
-        L.mbv_converter_runs.argtypes = [vp]
-        L.mbv_converter_runs.restype = C.c_int64
-    if hasattr(L, "mbv_convert_ranges") or not optional:
-        L.mbv_decode_chunks_routed.argtypes = [vp, C.POINTER(MbvChunk), C.POINTER(C.c_int32), i32, vp]
-        L.mbv_converter_context.argtypes = [C.POINTER(MbvConfig), C.POINTER(C.c_int32 * 2)]
-        L.mbv_spectrogram_ready.argtypes = [C.c_int64, i32, i32, i32]
-        L.mbv_spectrogram_ready.restype = C.c_int64
-        L.mbv_convert_window.argtypes = [C.POINTER(MbvConfig), i32, i32, C.c_int64, C.POINTER(C.c_int32 * 2)]
-        L.mbv_convert_ranges_plan.argtypes = [C.POINTER(MbvConfig), i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.mbv_convert_ranges.argtypes = [vp, C.POINTER(MbvConvertRange), i32, i32, i32, vp]
-    if hasattr(L, "mbv_resample_ranges") or not optional:
-        L.mbv_resample_ready_open.argtypes = [i32, i32, i32, C.c_int64]
-        L.mbv_resample_ready_open.restype = C.c_int64
-        L.mbv_resample_ranges.argtypes = [vp, C.POINTER(MbvResampleRange), i32, i32, i32, i32, vp]
-        L.mbv_input_runs.argtypes = [vp]
-        L.mbv_input_runs.restype = C.c_int64
-    if hasattr(L, "mbv_randn_blocks") or not optional:
-        L.mbv_randn_blocks.argtypes = [vp, C.POINTER(MbvRandnBlock), i32, vp]
-        L.mbv_randn_host.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, vp]
-        L.mbv_noise_runs.argtypes = [vp]
-        L.mbv_noise_runs.restype = C.c_int64
-    if hasattr(L, "mbv_limiter_ready") or not optional:
-        L.mbv_limiter_ready.argtypes = [i32, i32, i32, C.c_int64, C.c_int64, i32]
-        L.mbv_limiter_ready.restype = C.c_int64
-        L.mbv_resample_pcm16_range_limited.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
-                                                       C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), vp]
-        L.mbv_resample_pcm16_chunks_limited.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32,
-                                                        i32, i32, vp, C.c_int64, vp]
-    if hasattr(L, "mbv_resample_g711_range") or not optional:
-        L.mbv_g711_encode.argtypes = [vp, vp, C.c_int64, i32, vp, vp]
-        L.mbv_g711_decode.argtypes = [vp, vp, C.c_int64, i32, vp, vp]
-        L.mbv_resample_g711_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64,
-                                              vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32, vp]
-        L.mbv_resample_g711_chunks.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), i32, i32, i32, i32,
-                                               i32, vp, C.c_int64, vp]
-    if hasattr(L, "mbv_pcm_fade_make") or not optional:
-        fadep = C.POINTER(MbvPcmFade)
-        L.mbv_pcm_fade_make.argtypes = [C.c_int64, C.c_int64, fadep]
-        L.mbv_resample_pcm16_range_faded.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
-                                                     C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit),
-                                                     fadep, vp]
-        L.mbv_resample_pcm16_chunks_faded.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), fadep, i32,
-                                                      i32, i32, i32, vp, C.c_int64, vp]
-        L.mbv_resample_g711_range_faded.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
-                                                    C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32,
-                                                    fadep, vp]
-        L.mbv_resample_g711_chunks_faded.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit), fadep, i32,
-                                                     i32, i32, i32, i32, vp, C.c_int64, vp]
-    if hasattr(L, "mbv_token_marks") or not optional:
-        L.mbv_token_marks.argtypes = [vp, vp, C.c_int64, vp]
-        L.mbv_token_marks_rows.argtypes = [vp, i32, C.POINTER(MbvMarkRow), i32, vp]
-    if hasattr(L, "mbv_loudness") or not optional:
-        dp = C.POINTER(C.c_double)
-        L.mbv_kweighting.argtypes = [i32, dp, dp]
-        L.mbv_loudness_segments.argtypes = [i32, C.c_int64, C.POINTER(C.c_int32)]
-        L.mbv_loudness_segments.restype = C.c_int64
-        L.mbv_loudness.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp]
-        L.mbv_loudness_range.argtypes = [vp, vp, vp, i32, C.c_int64, i32, C.c_int64, C.c_int64, C.c_int64, vp, vp,
-                                         C.c_int64, vp, vp]
-        L.mbv_loudness_chunks.argtypes = [vp, C.POINTER(MbvLoudnessChunk), i32, i32, vp]
-        L.mbv_loudness_runs.argtypes = [vp]
-        L.mbv_loudness_runs.restype = C.c_int64
-    if hasattr(L, "mbv_resample_turns") or not optional:
-        L.mbv_turn_plan.argtypes = [i32, i32, i32, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit), i32, i64p]
-        L.mbv_turn_plan.restype = C.c_int64
-        L.mbv_resample_turns.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit), C.POINTER(MbvPcmFade), i32,
-                                         i32, i32, i32, i32, vp, C.c_int64, vp]
-    if hasattr(L, "mbv_shape_durations") or not optional:
-        L.mbv_shape_durations.argtypes = [vp, vp, vp, C.POINTER(MbvFit), i32, i32, vp, vp, vp]
-        L.mbv_shape_durations_rows.argtypes = [vp, i32, C.POINTER(MbvShapeRow), i32, vp, vp]
-        L.mbv_op_shape_durations.argtypes = [vp, vp, vp, vp, vp, f32, C.POINTER(MbvFit), vp, vp, vp, vp, vp, vp, i32, i32,
-                                             vp]
-        L.mbv_shape_runs.argtypes = [vp]
-        L.mbv_shape_runs.restype = C.c_int64
-    if hasattr(L, "mbv_frame_gain") or not optional:
-        envp = C.POINTER(MbvPcmEnvelope)
-        L.mbv_frame_gain.argtypes = [vp, vp, vp, C.c_int64, i32, vp]
-        L.mbv_frame_gain_rows.argtypes = [vp, i32, C.POINTER(MbvGainRow), i32, vp]
-        L.mbv_op_frame_gain.argtypes = [vp, vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp]
-        L.mbv_gain_runs.argtypes = [vp]
-        L.mbv_gain_runs.restype = C.c_int64
-        L.mbv_resample_pcm16_range_shaped.argtypes = [vp, vp, vp, i32, C.c_int64, i32, i32, i32, C.c_int64, C.c_int64,
-                                                      C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(MbvPcmLimit), i32,
-                                                      C.POINTER(MbvPcmFade), envp, C.c_int64, vp]
-        L.mbv_resample_pcm16_chunks_shaped.argtypes = [vp, C.POINTER(MbvPcmChunk), C.POINTER(MbvPcmLimit),
-                                                       C.POINTER(MbvPcmFade), envp, i32, i32, i32, i32, i32, vp,
-                                                       C.c_int64, vp]
-        L.mbv_resample_turns_shaped.argtypes = [vp, C.POINTER(MbvTurnChunk), C.POINTER(MbvPcmLimit),
-                                                C.POINTER(MbvPcmFade), envp, i32, i32, i32, i32, i32, vp, C.c_int64, vp]
-    if hasattr(L, "mbv_warp_ranges") or not optional:
-        L.mbv_warp_plan.argtypes = [i32, C.c_int64, vp, vp, i64p]
-        L.mbv_warp_ready.argtypes = [i32, C.c_int64, vp, vp, i32, C.c_int64]
-        L.mbv_warp_ready.restype = C.c_int64
-        L.mbv_warp_ranges.argtypes = [vp, C.POINTER(MbvWarpRow), i32, vp]
-        L.mbv_warp_runs.argtypes = [vp]
-        L.mbv_warp_runs.restype = C.c_int64
-    if hasattr(L, "mbv_speakers_define") or not optional:
-        L.mbv_speakers_define.argtypes = [vp, C.POINTER(MbvSpeakerDef), i32, vp]
-        L.mbv_speaker_release.argtypes = [vp, i32, vp]
-        L.mbv_speaker_slots.argtypes = []
-        L.mbv_speaker_defined.argtypes = [vp, C.c_int64]
-        L.mbv_speaker_runs.argtypes = [vp]
-        L.mbv_speaker_runs.restype = C.c_int64
-    if hasattr(L, "mbv_convert_ranges_ahead") or not optional:
-        L.mbv_convert_window_ahead.argtypes = [C.POINTER(MbvConfig), i32, i32, i32, C.c_int64, C.POINTER(C.c_int32 * 2)]
-        L.mbv_convert_ranges_ahead.argtypes = [vp, C.POINTER(MbvConvertRange), C.POINTER(C.c_int32), i32, i32, i32, vp]
-        L.mbv_seam_rows.argtypes = [vp, C.POINTER(MbvSeamRow), i32, vp]
-        L.mbv_seam_runs.argtypes = [vp]
-        L.mbv_seam_runs.restype = C.c_int64
-    for s in SYMBOLS:
-        if s not in optional or hasattr(L, s):
-            getattr(L, s)      # AttributeError if the header and the library ever drift
+    # the in-tree library must match the whole header; only a MBV_LIB baseline may lack LATER entries
+    declare(L, allow_missing=bool(os.environ.get("MBV_LIB")))
     if L.mbv_abi_version() != ABI_VERSION:
         raise RuntimeError("libmbistft_vits.so ABI version mismatch")
     _lib = L

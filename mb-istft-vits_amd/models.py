@@ -18,8 +18,7 @@ from torch import nn
 from . import _capi, stream
 from .spec import ModelConfig, config_from_ctor, param_shapes, DEC_MS, DEC_SB
 
-# librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
-RESAMPLE_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}
+RESAMPLE_TYPES = _capi.RESAMPLE_TYPES     # librosa.resample res_type -> MBV_RESAMPLE_* of include/mbistft_vits.h
 
 
 ENCODINGS = ("pcm16", "ulaw", "alaw")     # what the wire step stores: 16-bit linear, or G.711 bytes
@@ -2191,12 +2190,13 @@ class SynthesizerTrn(nn.Module):
                 keep.append(out)
                 for b, i in enumerate(idx):
                     wave_ptr[i] = out.data_ptr() + 4 * b * out.shape[-1]
-            # rows at the model's rate are read as they came (MBV_WAVE_F32 0 / MBV_WAVE_PCM16 1)
+            # rows at the model's rate are read as they came
             same = [r.in_sr == r.model_sr for r in reqs]
             own_ptr, kept = self._pack_host([r.wave if same[i] else None for i, r in enumerate(reqs)], dev)
             keep += kept
             wave_ptr = [own_ptr[i] if same[i] else wave_ptr[i] for i in range(N)]
-            wave_dtype = [int(same[i] and r.wave.dtype == torch.int16) for i, r in enumerate(reqs)]
+            wave_dtype = [_capi.WAVE_PCM16 if same[i] and r.wave.dtype == torch.int16 else _capi.WAVE_F32
+                          for i, r in enumerate(reqs)]
             # the posterior draw, per request, in list order: the values and the generator's progress of N stand-alone
             # randn(1, I, T_i) calls (drawn at noise_scale == 0 too, as convert_stream does)
             if alone and noise is not None:
@@ -2657,9 +2657,9 @@ class SynthesizerTrn(nn.Module):
         if center:
             raise ValueError("spectrogram: center=True is not supported (the reference calls it with center=False)")
         if wave.dtype == torch.int16:
-            dtype = 1                                            # MBV_WAVE_PCM16
+            dtype = _capi.WAVE_PCM16
         elif wave.dtype == torch.float32:
-            dtype = 0                                            # MBV_WAVE_F32
+            dtype = _capi.WAVE_F32
         else:
             raise ValueError("spectrogram: wave must be float32 or int16, got %s" % wave.dtype)
         if wave.dim() == 3 and wave.shape[1] == 1:

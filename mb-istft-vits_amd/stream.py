@@ -49,7 +49,7 @@ def chunk_schedule(t_frames, chunk_frames=32, max_chunk_frames=256):
     return out
 
 
-RES_TYPES = {"kaiser_best": 0, "kaiser_fast": 1}   # MBV_RESAMPLE_KAISER_*: the filters of the warp and the wire
+RES_TYPES = _capi.RESAMPLE_TYPES    # MBV_RESAMPLE_KAISER_*: the filters of the warp and the wire
 
 
 def frame_rates(pitch, marks, frames, glide_frames=2):
@@ -619,7 +619,7 @@ class LiveStream:
 
     def _fill_range(self, row, a, b):
         row.wave, row.arrived, row.closed = self.samples.data_ptr(), self._plan.arrived, int(self._plan.closed)
-        row.wave_dtype = 1 if self.dtype == torch.int16 else 0
+        row.wave_dtype = _capi.WAVE_PCM16 if self.dtype == torch.int16 else _capi.WAVE_F32
         row.sid_src, row.sid_tgt, row.first, row.count = self.sid_src, self.sid_tgt, a, b - a
         row.noise, row.noise_stride, row.noise_scale = self.noise.data_ptr(), self.noise.stride(1), self.noise_scale
         row.z, row.z_stride = self.z.data_ptr(), self.z.stride(1)

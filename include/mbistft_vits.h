@@ -306,8 +306,13 @@ int mbv_tail_pack_table(const int64_t *lens, int B, int num, int reach, int T, i
  *
  * mbv_encode_rows: mbv_encode for the B rows of one run, ids [B, T] zero-padded, lengths[b] = rows[b].t_text.  The
  * state the run leaves for its mbv_synthesize_rows is kept under `slot` (0 .. 63), so that several runs can be
- * encoded, their lengths read back and their noise drawn before any is synthesised; slot 0 is the state a plain
- * mbv_encode leaves, too.  rows_host is HOST memory and travels as kernel arguments (free it on return).  Rows with
+ * encoded, their lengths read back and their noise drawn before any is synthesised.  Slot 0 and the plain mbv_encode
+ * are ONE state in one scratch: either call replaces what the other left, and the `_rows` entries take slot 0 only
+ * while it holds an mbv_encode_rows run.  Whatever lays out a run's scratch ends the run: the next mbv_encode_rows on
+ * its slot, and for slot 0 also mbv_encode and mbv_align; slots 1 .. 63 have a buffer each that no other entry
+ * touches.  A `_rows` entry on an ended run is refused before any launch ("without a preceding mbv_encode_rows on
+ * slot k").  The plain entries act on the run encoded or synthesised last, by either form.
+ * rows_host is HOST memory and travels as kernel arguments (free it on return).  Rows with
  * durations have them set as mbv_set_durations does (same range rules, same -1 marker); the others keep the predicted
  * ones.  y_lengths_out as in mbv_encode: -1 flags a row (token id / sid / duration), read it before synthesising.
  * Refused before any launch: t_text outside [1, T], noise_w missing on a model with the stochastic duration

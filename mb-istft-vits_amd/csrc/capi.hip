@@ -45,12 +45,19 @@ struct PConv {              // packed conv living in the weight arena (offsets i
 };
 struct PVec { size_t off = 0; int n = 0; bool present = false; };
 
-struct StageRef { const float* ptr; int64_t numel; };
-
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// state of an encode: its shape and the tensors it left in its scratch (mbv_model: of the last encode; EncSlot: of a kept run)
-struct EncState {
+// A scratch buffer and the number of times it has been laid out.  Every ensure / lay_out on it bumps `claim`: the caller
+// overwrites the buffer from offset 0 and the buffer may move, so whatever pointed into it (an EncRun, a StageRef) is
+// dead from then on.  That is the one rule for state kept between entries: it remembers the claim it was made under.
+struct Scratch { char* p = nullptr; size_t bytes = 0; uint64_t claim = 0; };
+
+// ... what was carved out of a Scratch (home null: nothing yet) under which claim, and whether it is still there
+struct Carved { Scratch* home = nullptr; uint64_t claim = 0; bool live() const { return home && home->claim == claim; } };
+struct StageRef : Carved { const float* ptr = nullptr; int64_t numel = 0; };
+
+// one encode run: its shape and the tensors it left in its scratch `home`
+struct EncRun : Carved {
   int B = 0, T = 0;
   bool has_g = false;
   float *x_enc = nullptr, *stats = nullptr, *logw = nullptr, *w_ceil = nullptr, *gvec = nullptr;
@@ -59,6 +66,8 @@ struct EncState {
   float* fit = nullptr;         // [2, B]: the factor and the status mbv_shape_durations left (stages fit_scale / fit_status)
   std::vector<float> scales;    // the length_scale the encode took: one value, or one per row (mbv_encode_rows)
   std::vector<int> t_text;      // mbv_encode_rows: every row's own text length (its tensors end there)
+  bool rows = false;            // made by mbv_encode_rows
+  Scratch own;                  // the buffer of a pooled slot >= 1 (slot 0 and the plain encode live in scrA)
 };
 
 // one launch of the decoder, as integers (decoder_table)
@@ -80,7 +89,7 @@ inline int convt_pad_left(int u) { return u == 4 ? 2 : 1; }
 
 }  // namespace
 
-struct mbv_model : EncState {     // the base: the state of the last encode
+struct mbv_model {
   mbv_config cfg{};
   std::string err;
   std::map<std::string, HostTensor> raw;
@@ -126,8 +135,7 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   unsigned* conv_cnt = nullptr; int conv_ncnt = 0;        // one ticket counter per tile (zero between launches)
   int wn_fused = 1;           // MBV_WN_FUSED=0: the two-launch WN layer (gate conv, then res/skip conv)
   int splitk = 0;             // option "splitk": split-K for small conv launches (default: MBV_CONV_SPLITK or 0)
-  char* scrA = nullptr; size_t scrA_bytes = 0;
-  char* scrB = nullptr; size_t scrB_bytes = 0;
+  Scratch scrA, scrB;
   float* user_tab = nullptr;   // polyphase table of the stand-alone mbv_istft_pqmf entry
   unsigned* peak_buf = nullptr; int peak_cap = 0;   // per-utterance peaks of mbv_pcm16
   struct ResampleBank { float* d = nullptr; ResampleGeom g{}; };
@@ -169,20 +177,21 @@ struct mbv_model : EncState {     // the base: the state of the last encode
   int64_t loudness_runs = 0;       // launches of the loudness kernel (mbv_loudness_runs)
   std::map<int, LoudnessParams> loudness_params;    // rate -> K-weighting tables (built once a rate, host only)
   std::map<const void*, int64_t> loudness_next;     // state buffer of a measured row -> its next segment
-  char* noise_tab = nullptr; size_t noise_tab_bytes = 0;   // mbv_randn_blocks' table: its own buffer, so that a fill
-                                                           // between an encode and its synthesize disturbs no scratch
+  Scratch noise_tab;               // mbv_randn_blocks' table: its own buffer, so that a fill between an encode and its
+                                   // synthesize disturbs no scratch
   int64_t encoder_runs = 0;        // run_text_encoder calls since mbv_create (mbv_encoder_runs)
   int64_t shape_runs = 0;          // launches of the prosody kernel (mbv_shape_runs)
   int64_t gain_runs = 0;           // launches of the frame-gain kernel (mbv_gain_runs)
   int64_t converter_runs = 0;      // posterior-encoder runs of mbv_convert_rows since mbv_create (mbv_converter_runs)
   int64_t xpost_chunk_bytes = 0;   // option "xpost_chunk_bytes": sub-batch cap of conv_post + iSTFT (0: 2 GiB - 1)
 
-  bool encoded = false;           // the EncState base holds an encode
   std::map<std::string, StageRef> stages;
-  // pooled admission: the encode state of one padded run, kept until its mbv_synthesize_rows (mbv_encode_rows);
-  // slot 0 lives in scrA like a plain encode, every further slot in a buffer of its own
-  struct EncSlot { char* scr = nullptr; size_t bytes = 0; bool valid = false; EncState enc; };
-  std::vector<EncSlot> slots;
+  void stage(const char* name, const float* ptr, int64_t numel, Scratch& home) { stages[name] = StageRef{{&home, home.claim}, ptr, numel}; }
+  // runs[0] is what mbv_encode and mbv_encode_rows(slot 0) write, in scrA; every further slot of the pooled admission
+  // keeps its run in a buffer of its own.  cur: the run the plain entries act on, the one encoded or synthesised last
+  static constexpr int kSlots = 64;
+  EncRun runs[kSlots];
+  int cur = -1;
 
   static constexpr int kEvRing = 8;
   hipEvent_t evr[kEvRing][7]{};    // stage events of the last kEvRing encode (+ synthesize) calls
@@ -1020,12 +1029,13 @@ struct Bump {
   bool fits() const { return off <= cap; }
 };
 
-int ensure(mbv_model* m, char** buf, size_t* cap, size_t need) {
-  if (*cap >= need) return 0;
-  if (*buf) { HIPCHK(m, hipDeviceSynchronize()); HIPCHK(m, hipFree(*buf)); *buf = nullptr; *cap = 0; }
+int ensure(mbv_model* m, Scratch& sc, size_t need) {
+  ++sc.claim;                            // grown or not, the caller writes from offset 0: what pointed in here is dead
+  if (sc.bytes >= need) return 0;
+  if (sc.p) { HIPCHK(m, hipDeviceSynchronize()); HIPCHK(m, hipFree(sc.p)); sc.p = nullptr; sc.bytes = 0; }
   need = align_up(need + (need >> 3), 1 << 20);
-  HIPCHK(m, hipMalloc((void**)buf, need));
-  *cap = need;
+  HIPCHK(m, hipMalloc((void**)&sc.p, need));
+  sc.bytes = need;
   return 0;
 }
 
@@ -1037,14 +1047,15 @@ int ensure(mbv_model* m, char** buf, size_t* cap, size_t need) {
 // may run up to three times per call and must do nothing but set its outputs; a pass that does not fit hands out
 // pointers past the arena, which nobody may read before lay_out has returned 0.
 template <typename Carve>
-int lay_out(mbv_model* m, const char* who, char** buf, size_t* cap, Carve&& carve) {
-  Bump sc{*buf, *cap};
-  if (*buf) carve(sc);
-  if (*buf && sc.fits()) return 0;
+int lay_out(mbv_model* m, const char* who, Scratch& buf, Carve&& carve) {
+  ++buf.claim;                           // (ensure's rule, for the call that fits: before anything is carved or freed)
+  Bump sc{buf.p, buf.bytes};
+  if (buf.p) carve(sc);
+  if (buf.p && sc.fits()) return 0;
   Bump measure{nullptr, 0};
   carve(measure);
-  if (ensure(m, buf, cap, measure.off)) return 1;
-  sc = Bump{*buf, *cap};
+  if (ensure(m, buf, measure.off)) return 1;
+  sc = Bump{buf.p, buf.bytes};
   carve(sc);
   return sc.fits() ? 0 : m->fail("%s: scratch layout exceeds its buffer", who);
 }
@@ -1507,7 +1518,7 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
     with_trim(a, e);
     launch_conv1d(a, s, rt_num);
   }
-  m->stages["dec_conv_pre"] = {d.x0, (int64_t)B * table[0].M * Td};
+  m->stage("dec_conv_pre", d.x0, (int64_t)B * table[0].M * Td, m->scrB);
   const float* cur = d.x0;
   size_t next = 1;                                   // the table entry of the next launch
   for (int i = 0; i < 2; ++i) {
@@ -1525,7 +1536,7 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
       with_trim(a, up);                             // tiles run over INPUT frames (rate of the stage below)
       launch_conv1d(a, s);
     }
-    m->stages[i == 0 ? "dec_up_0" : "dec_up_1"] = {u, (int64_t)n};
+    m->stage(i == 0 ? "dec_up_0" : "dec_up_1", u, (int64_t)n, m->scrB);
     if (conc) {
       HIPCHK(m, hipEventRecord(m->ev_fork, s_main));
       for (auto& st : m->aux) HIPCHK(m, hipStreamWaitEvent(st, m->ev_fork, 0));
@@ -1584,7 +1595,7 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
       return 1;
     }
     if (conc) HIPCHK(m, hipStreamWaitEvent(s_main, m->ev_rb[2], 0));
-    m->stages[i == 0 ? "dec_res_0" : "dec_res_1"] = {xs, (int64_t)n};
+    m->stage(i == 0 ? "dec_res_0" : "dec_res_1", xs, (int64_t)n, m->scrB);
     cur = xs;
   }
   const DecLaunch &post = table[next], &wave = table[next + 1];
@@ -1638,7 +1649,7 @@ int run_decoder(mbv_model* m, const float* z, const int* zlens, const float* gve
       else launch_istft_pqmf(ia, s);
     }
   }
-  if (Bc == B) m->stages["x_post"] = {xpost, (int64_t)B * prow * Fr};     // (a split run keeps only its last chunk)
+  if (Bc == B) m->stage("x_post", xpost, (int64_t)B * prow * Fr, m->scrB);     // (a split run keeps only its last chunk)
   m->xpost_F = Fr;
   m->xpost_rows = prow;
   HIPCHK(m, hipEventRecord(m->evk[2], s));
@@ -2109,14 +2120,14 @@ void mbv_destroy(mbv_model* m) {
   if (m->conv_ws) (void)hipFree(m->conv_ws);
   if (m->conv_cnt) (void)hipFree(m->conv_cnt);
   if (m->tail_cnt) (void)hipFree(m->tail_cnt);
-  if (m->scrA) (void)hipFree(m->scrA);
-  if (m->scrB) (void)hipFree(m->scrB);
-  if (m->noise_tab) (void)hipFree(m->noise_tab);
+  if (m->scrA.p) (void)hipFree(m->scrA.p);
+  if (m->scrB.p) (void)hipFree(m->scrB.p);
+  if (m->noise_tab.p) (void)hipFree(m->noise_tab.p);
   if (m->voice_rows) (void)hipFree(m->voice_rows);
   if (m->voice_defined) (void)hipFree(m->voice_defined);
   if (m->voice_defs) (void)hipFree(m->voice_defs);
-  for (auto& sl : m->slots)
-    if (sl.scr) (void)hipFree(sl.scr);
+  for (auto& r : m->runs)
+    if (r.own.p) (void)hipFree(r.own.p);
   if (m->user_tab) (void)hipFree(m->user_tab);
   if (m->peak_buf) (void)hipFree(m->peak_buf);
   for (auto& kv : m->resample_banks) (void)hipFree(kv.second.d);
@@ -2279,16 +2290,16 @@ int64_t mbv_speaker_runs(mbv_model* m) { return m ? m->speaker_runs : -1; }
 
 namespace {
 // DDSConv (modules.py:98-111) on x [B, C, T] in place; t1, t2: scratch of the same size
-void run_dds(mbv_model* m, const mbv_model::Dds& d, float* x, float* t1, float* t2, int B, int C, int T,
+void run_dds(mbv_model* m, const EncRun& r, const mbv_model::Dds& d, float* x, float* t1, float* t2, int B, int C, int T,
              hipStream_t s) {
   const int64_t bs = (int64_t)C * T;
   int dil = 1;
   for (int i = 0; i < 3; ++i, dil *= 3) {
-    launch_dds_sep(x, m->lens32, m->W(d.sw[i].off), m->W(d.sb[i].off), m->W(d.g1[i].off),
+    launch_dds_sep(x, r.lens32, m->W(d.sw[i].off), m->W(d.sb[i].off), m->W(d.g1[i].off),
                    m->W(d.b1[i].off), t1, B, C, T, 3, dil, s);
     launch_conv1d(conv_args(m, d.c1[i], t1, bs, T, t2, bs, T, B), s);
     launch_dds_res(t2, x, m->W(d.g2[i].off), m->W(d.b2[i].off), x, B, C, T,
-                   i == 2 ? m->lens32 : nullptr, s);
+                   i == 2 ? r.lens32 : nullptr, s);
   }
 }
 struct ExactScope {
@@ -2297,9 +2308,9 @@ struct ExactScope {
   ~ExactScope() { m->conv_bf16 = saved; }
 };
 // Phase A of mbv_encode: embedding, the attention layers and enc_p.proj (models.py:183-195) -> x [B, H, T] and
-// m->stats = [m_text | logs_text]; shared with mbv_align.  Runs in the caller's ExactScope.
+// r.stats = [m_text | logs_text] of the run it is given; shared with mbv_align.  Runs in the caller's ExactScope.
 struct TextEncBufs { float *x, *x1, *qkv, *att, *y, *ffn; };
-TextEncBufs carve_text(Bump& sc, mbv_model* m, int B, int T) {      // and m->stats [B, 2I, T]
+TextEncBufs carve_text(Bump& sc, const mbv_model* m, EncRun& r, int B, int T) {      // and r.stats [B, 2I, T]
   const size_t BT = (size_t)B * T, H = m->cfg.hidden_channels;
   TextEncBufs e{};
   e.x = sc.take<float>(BT * H);
@@ -2308,26 +2319,26 @@ TextEncBufs carve_text(Bump& sc, mbv_model* m, int B, int T) {      // and m->st
   e.att = sc.take<float>(BT * H);
   e.y = sc.take<float>(BT * H);
   e.ffn = sc.take<float>(BT * m->cfg.filter_channels);
-  m->stats = sc.take<float>(BT * 2 * m->cfg.inter_channels);
+  r.stats = sc.take<float>(BT * 2 * m->cfg.inter_channels);
   return e;
 }
 // (a rule on T alone: rows stay batch-independent; the opt-in low-latency mode may look at the launch
 // size: fused, a conv + LayerNorm is one workgroup per 32 frames walking the whole K loop alone)
 bool text_fuse_ln_at(int splitk, int B, int T) { return T <= 256 && !(splitk && (long)B * ((T + 15) / 16) < 128); }
 bool text_fuse_ln(const mbv_model* m, int B, int T) { return text_fuse_ln_at(m->splitk, B, T); }
-void run_text_encoder(mbv_model* m, const int64_t* ids, const int64_t* lengths, const TextEncBufs& e, int* bad, int B,
+void run_text_encoder(mbv_model* m, const EncRun& r, const int64_t* ids, const int64_t* lengths, const TextEncBufs& e, int* bad, int B,
                       int T, hipStream_t s) {
   const mbv_config& c = m->cfg;
   const int H = c.hidden_channels, I = c.inter_channels, Fc = c.filter_channels;
   float *x = e.x, *x1 = e.x1, *qkv = e.qkv, *att = e.att, *y = e.y, *ffn = e.ffn;
   ++m->encoder_runs;
-  launch_embed(ids, lengths, m->W(m->emb.off), x, m->lens32, bad, B, T, H, c.n_vocab, s);
+  launch_embed(ids, lengths, m->W(m->emb.off), x, r.lens32, bad, B, T, H, c.n_vocab, s);
   const int64_t bsH = (int64_t)H * T;
   const bool fuse_ln = text_fuse_ln(m, B, T);
   for (int i = 0; i < c.n_layers; ++i) {
     const auto& L = m->enc[i];
     launch_conv1d(conv_args(m, L.qkv, x, bsH, T, qkv, 3 * bsH, T, B), s);
-    launch_rel_attention(qkv, m->W(L.ek.off), m->W(L.ev.off), m->lens32, att, B, H, c.n_heads, T, s);
+    launch_rel_attention(qkv, m->W(L.ek.off), m->W(L.ev.off), r.lens32, att, B, H, c.n_heads, T, s);
     // conv_o and the LayerNorm(x + y) behind it (attentions.py:40-41): one launch on the narrow kernel
     // for sequences it covers (a rule on T and H only), else conv + LayerNorm
     {
@@ -2344,35 +2355,36 @@ void run_text_encoder(mbv_model* m, const int64_t* ids, const int64_t* lengths, 
     {
       ConvArgs a = conv_args(m, L.ffn1, x1, bsH, T, ffn, (int64_t)Fc * T, T, B);
       a.pad_left = (c.kernel_size - 1) / 2;            // attentions.py:296-303
-      a.in_lens = m->lens32; a.relu = 1;
+      a.in_lens = r.lens32; a.relu = 1;
       launch_conv1d(a, s);
     }
     const bool last = i == c.n_layers - 1;
     {   // FFN's second conv (output masked, attentions.py:303) and LayerNorm(x1 + y) (+ the final mask, :45-46)
       ConvArgs a = conv_args(m, L.ffn2, ffn, (int64_t)Fc * T, T, x, bsH, T, B);
       a.pad_left = (c.kernel_size - 1) / 2;
-      a.in_lens = m->lens32; a.out_lens = m->lens32;
+      a.in_lens = r.lens32; a.out_lens = r.lens32;
       a.epi = EPI_LN; a.res = x1; a.res_bstride = bsH;
       a.ln_gamma = m->W(L.g2.off); a.ln_beta = m->W(L.b2.off);
-      a.ln_out_lens = last ? m->lens32 : nullptr;
+      a.ln_out_lens = last ? r.lens32 : nullptr;
       if (fuse_ln && conv1d_narrow_supported(a)) {
         launch_conv1d(a, s);
       } else {
         a.epi = EPI_STORE; a.res = nullptr; a.y = y; a.ln_gamma = a.ln_beta = nullptr; a.ln_out_lens = nullptr;
         launch_conv1d(a, s);
-        launch_layernorm(x1, y, m->W(L.g2.off), m->W(L.b2.off), x, B, H, T, 0, last ? m->lens32 : nullptr, s);
+        launch_layernorm(x1, y, m->W(L.g2.off), m->W(L.b2.off), x, B, H, T, 0, last ? r.lens32 : nullptr, s);
       }
     }
   }
   {
-    ConvArgs a = conv_args(m, m->enc_proj, x, bsH, T, m->stats, (int64_t)2 * I * T, T, B);
-    a.out_lens = m->lens32;
+    ConvArgs a = conv_args(m, m->enc_proj, x, bsH, T, r.stats, (int64_t)2 * I * T, T, B);
+    a.out_lens = r.lens32;
     launch_conv1d(a, s);
   }
 }
 // mbv_encode; rows_host != nullptr: mbv_encode_rows — the per-call scalars and the SDP noise come from the table,
-// and rows with given durations have them set in the same call (the launches of mbv_set_durations)
-int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
+// and rows with given durations have them set in the same call (the launches of mbv_set_durations).  `r` is the run it
+// makes: laid out in r's own scratch (which ends the run r held), live and the handle's current one once all is launched
+int encode(mbv_model* m, EncRun& r, const int64_t* ids, const int64_t* lengths, const int64_t* sid, int B,
            int T, float length_scale, const float* noise_w, float noise_scale_w, const mbv_enc_row* rows_host,
            int64_t* y_lengths_out, void* stream) {
   const char* const who = rows_host ? "mbv_encode_rows" : "mbv_encode";
@@ -2393,19 +2405,21 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   float *h1, *h2, *dpc;
   float *cond = nullptr, *hh = nullptr, *t1 = nullptr, *t2 = nullptr, *h29 = nullptr, *zf = nullptr;   // the SDP's
   AdmitEncRow* rows = nullptr;
-  if (lay_out(m, who, &m->scrA, &m->scrA_bytes, [&](Bump& b) {
-        te = carve_text(b, m, B, T);
+  m->cur = -1;
+  r.home = &r == m->runs ? &m->scrA : &r.own;
+  if (lay_out(m, who, *r.home, [&](Bump& b) {
+        te = carve_text(b, m, r, B, T);
         h1 = b.take<float>(BT * kDpFilter);
         h2 = b.take<float>(BT * kDpFilter);
-        m->logw = b.take<float>(BT);
-        m->w_ceil = b.take<float>(BT);
-        m->cum = b.take<int>(BT);
-        m->lens32 = b.take<int>(B);
-        m->ylen32 = b.take<int>(B);
-        m->bad32 = b.take<int>(B);
-        m->gvec = b.take<float>((size_t)B * (gin ? gin : 1));
+        r.logw = b.take<float>(BT);
+        r.w_ceil = b.take<float>(BT);
+        r.cum = b.take<int>(BT);
+        r.lens32 = b.take<int>(B);
+        r.ylen32 = b.take<int>(B);
+        r.bad32 = b.take<int>(B);
+        r.gvec = b.take<float>((size_t)B * (gin ? gin : 1));
         dpc = b.take<float>((size_t)B * H);
-        m->fit = b.take<float>((size_t)2 * B);
+        r.fit = b.take<float>((size_t)2 * B);
         if (rows_host) rows = b.take<AdmitEncRow>(B);
         if (c.use_sdp) {
           cond = b.take<float>(BT * H);
@@ -2415,8 +2429,8 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
           h29 = b.take<float>(BT * 32);
           zf = b.take<float>(BT * 2);
         }
-      })) { m->encoded = false; return 1; }      // (the state of the encode before is gone: its scratch is this one)
-  int* const bad = m->bad32;
+      })) return 1;
+  int* const bad = r.bad32;
   float* const x = te.x;
   bool any_given = false;
   if (rows_host)
@@ -2426,29 +2440,29 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
       return AdmitEncRow{k.length_scale, k.noise_scale_w, k.noise_w, k.durations, k.durations_dtype, k.t_text};
     });
   m->stages.clear();
-  m->scales.assign(rows_host ? (size_t)B : 1, length_scale);
-  m->t_text.assign(rows_host ? (size_t)B : 0, 0);
-  if (rows_host)
-    for (int i = 0; i < B; ++i) { m->scales[i] = rows_host[i].length_scale; m->t_text[i] = rows_host[i].t_text; }
+  r.rows = rows_host != nullptr;
+  r.scales.assign(r.rows ? (size_t)B : 1, length_scale);
+  r.t_text.assign(r.rows ? (size_t)B : 0, 0);
+  for (int i = 0; r.rows && i < B; ++i) { r.scales[i] = rows_host[i].length_scale; r.t_text[i] = rows_host[i].t_text; }
 
   ++m->ticket;                                     // a new call: its own set of stage events (mbv_stage_times_ms_at)
   m->ev = m->evr[m->ticket % mbv_model::kEvRing];
   m->evr_a[m->ticket % mbv_model::kEvRing] = false;
   m->evr_b[m->ticket % mbv_model::kEvRing] = false;
   HIPCHK(m, hipEventRecord(m->ev[0], s));
-  run_text_encoder(m, ids, lengths, te, bad, B, T, s);
+  run_text_encoder(m, r, ids, lengths, te, bad, B, T, s);
   const int64_t bsH = (int64_t)H * T;
   const bool fuse_ln = text_fuse_ln(m, B, T);
-  m->x_enc = x;
+  r.x_enc = x;
   HIPCHK(m, hipEventRecord(m->ev[1], s));
 
   // ---- speaker embedding + duration predictor (models.py:704-713)
-  m->has_g = c.n_speakers > 0;
+  r.has_g = c.n_speakers > 0;
   const float* cadd = nullptr;
-  if (m->has_g) {
-    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad, s, m->voice_table());
+  if (r.has_g) {
+    launch_gather_rows(m->W(m->emb_g.off), sid, r.gvec, B, gin, c.n_speakers, bad, s, m->voice_table());
     if (m->dp_cw.present) {
-      launch_cond_gemv(m->gvec, nullptr, nullptr, m->W(m->dp_cw.off), m->W(m->dp_cb.off), dpc, B, gin, H, s);
+      launch_cond_gemv(r.gvec, nullptr, nullptr, m->W(m->dp_cw.off), m->W(m->dp_cb.off), dpc, B, gin, H, s);
       cadd = dpc;
     }
   }
@@ -2456,10 +2470,10 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
     // models.py:53-60: conditioning trunk; :89-100: z through [Flip, ConvFlow] x 3, Flip, affine
     launch_conv1d(conv_args(m, m->sdp.pre, x, bsH, T, hh, bsH, T, B), s);
     if (cadd) launch_chan_add(hh, cadd, B, H, T, s);
-    run_dds(m, m->sdp.dds, hh, t1, t2, B, H, T, s);
+    run_dds(m, r, m->sdp.dds, hh, t1, t2, B, H, T, s);
     {
       ConvArgs a = conv_args(m, m->sdp.proj, hh, bsH, T, cond, bsH, T, B);
-      a.out_lens = m->lens32;
+      a.out_lens = r.lens32;
       launch_conv1d(a, s);
     }
     if (rows) launch_sdp_noise_rows(rows, zf, B, T, s);
@@ -2467,27 +2481,27 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
     for (int k = 0; k < 3; ++k) {
       const auto& f = m->sdp.flow[k];
       launch_sdp_pre(zf, 1, m->W(f.pre_w.off), m->W(f.pre_b.off), cond, hh, B, H, T, s);   // x0 = z[:, 1] after the Flip
-      run_dds(m, f.dds, hh, t1, t2, B, H, T, s);
+      run_dds(m, r, f.dds, hh, t1, t2, B, H, T, s);
       {
         ConvArgs a = conv_args(m, f.proj, hh, bsH, T, h29, (int64_t)29 * T, T, B);
-        a.out_lens = m->lens32;
+        a.out_lens = r.lens32;
         launch_conv1d(a, s);
       }
-      launch_sdp_spline(h29, zf, m->lens32, B, H, T, m->sdp.edge_const, s);
+      launch_sdp_spline(h29, zf, r.lens32, B, H, T, m->sdp.edge_const, s);
     }
-    launch_sdp_logw(zf, m->W(m->sdp.m.off), m->W(m->sdp.logs.off), m->lens32, h29, B, T, s);
-    if (rows) launch_durations_rows(h29, nullptr, nullptr, m->lens32, rows, m->logw, m->w_ceil, m->cum, m->ylen32,
+    launch_sdp_logw(zf, m->W(m->sdp.m.off), m->W(m->sdp.logs.off), r.lens32, h29, B, T, s);
+    if (rows) launch_durations_rows(h29, nullptr, nullptr, r.lens32, rows, r.logw, r.w_ceil, r.cum, r.ylen32,
                                     y_lengths_out, bad, B, 1, T, s);
-    else launch_durations(h29, nullptr, nullptr, m->lens32, length_scale, m->logw, m->w_ceil, m->cum,
-                          m->ylen32, y_lengths_out, bad, B, 1, T, s);
-    m->stages["sdp_cond"] = {cond, (int64_t)BT * H};
-    m->stages["sdp_z"] = {zf, (int64_t)BT * 2};
+    else launch_durations(h29, nullptr, nullptr, r.lens32, length_scale, r.logw, r.w_ceil, r.cum,
+                          r.ylen32, y_lengths_out, bad, B, 1, T, s);
+    m->stage("sdp_cond", cond, (int64_t)BT * H, *r.home);
+    m->stage("sdp_z", zf, (int64_t)BT * 2, *r.home);
   } else {
   // conv -> relu -> LayerNorm twice (models.py:128-135): each pair one launch where the narrow kernel applies
   const float* dp_out = h2;
   {
     ConvArgs a = conv_args(m, m->dp1, x, bsH, T, h2, (int64_t)kDpFilter * T, T, B);
-    a.in_lens = m->lens32; a.chan_add = cadd;
+    a.in_lens = r.lens32; a.chan_add = cadd;
     a.epi = EPI_LN; a.relu = 1; a.ln_gamma = m->W(m->dp_g1.off); a.ln_beta = m->W(m->dp_b1.off);
     if (fuse_ln && conv1d_narrow_supported(a)) {
       launch_conv1d(a, s);
@@ -2499,7 +2513,7 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
   }
   {
     ConvArgs a = conv_args(m, m->dp2, h2, (int64_t)kDpFilter * T, T, h1, (int64_t)kDpFilter * T, T, B);
-    a.in_lens = m->lens32;
+    a.in_lens = r.lens32;
     a.epi = EPI_LN; a.relu = 1; a.ln_gamma = m->W(m->dp_g2.off); a.ln_beta = m->W(m->dp_b2.off);
     if (fuse_ln && conv1d_narrow_supported(a)) {
       launch_conv1d(a, s);
@@ -2510,20 +2524,20 @@ int encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const int64
       launch_layernorm(h1, nullptr, m->W(m->dp_g2.off), m->W(m->dp_b2.off), h2, B, kDpFilter, T, 1, nullptr, s);
     }
   }
-  if (rows) launch_durations_rows(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), m->lens32, rows, m->logw,
-                                  m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
-  else launch_durations(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), m->lens32, length_scale, m->logw,
-                        m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
+  if (rows) launch_durations_rows(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), r.lens32, rows, r.logw,
+                                  r.w_ceil, r.cum, r.ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
+  else launch_durations(dp_out, m->W(m->dp_pw.off), m->W(m->dp_pb.off), r.lens32, length_scale, r.logw,
+                        r.w_ceil, r.cum, r.ylen32, y_lengths_out, bad, B, kDpFilter, T, s);
   }
-  if (any_given) launch_set_durations_rows(rows, m->lens32, m->w_ceil, m->cum, m->ylen32, y_lengths_out, bad, B, T, s);
+  if (any_given) launch_set_durations_rows(rows, r.lens32, r.w_ceil, r.cum, r.ylen32, y_lengths_out, bad, B, T, s);
   HIPCHK(m, hipEventRecord(m->ev[2], s));
   HIPCHK(m, hipGetLastError());
-  m->B = B; m->T = T; m->encoded = true; m->ev_a = true; m->ev_b = false;
+  r.B = B; r.T = T; r.claim = r.home->claim; m->cur = (int)(&r - m->runs); m->ev_a = true; m->ev_b = false;
   m->evr_a[m->ticket % mbv_model::kEvRing] = true;
-  m->stages["x_enc"] = {x, (int64_t)BT * H};
-  m->stages["stats"] = {m->stats, (int64_t)BT * 2 * I};
-  m->stages["logw"] = {m->logw, (int64_t)BT};
-  m->stages["w_ceil"] = {m->w_ceil, (int64_t)BT};
+  m->stage("x_enc", x, (int64_t)BT * H, *r.home);
+  m->stage("stats", r.stats, (int64_t)BT * 2 * I, *r.home);
+  m->stage("logw", r.logw, (int64_t)BT, *r.home);
+  m->stage("w_ceil", r.w_ceil, (int64_t)BT, *r.home);
   return 0;
 }
 }  // namespace
@@ -2532,12 +2546,30 @@ int mbv_encode(mbv_model* m, const int64_t* ids, const int64_t* lengths, const i
                int T, float length_scale, const float* noise_w, float noise_scale_w,
                int64_t* y_lengths_out, void* stream) {
   if (!m) return 1;
-  return encode(m, ids, lengths, sid, B, T, length_scale, noise_w, noise_scale_w, nullptr, y_lengths_out, stream);
+  return encode(m, m->runs[0], ids, lengths, sid, B, T, length_scale, noise_w, noise_scale_w, nullptr, y_lengths_out, stream);
 }
 
 }  // extern "C"
 
 namespace {
+// The run a plain entry acts on: the one encoded or synthesised last, while nothing has laid out its scratch since
+// (null, with the error set, otherwise).
+EncRun* cur_run(mbv_model* m, const char* who) {
+  if (!m) return nullptr;
+  if (m->cur >= 0 && m->runs[m->cur].live()) return &m->runs[m->cur];
+  m->fail("%s without a preceding mbv_encode", who);
+  return nullptr;
+}
+// ... and the one a _rows entry acts on: slot's, live, made by mbv_encode_rows, of n rows
+EncRun* rows_run(mbv_model* m, const char* who, int slot, const void* rows_host, int n) {
+  if (!m) return nullptr;
+  EncRun* r = slot >= 0 && slot < mbv_model::kSlots ? &m->runs[slot] : nullptr;
+  if (!r || !r->live()) return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot), nullptr;
+  if (!r->rows) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot), nullptr;
+  if (!rows_host || n != r->B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, r->B, n), nullptr;
+  return r;
+}
+
 // what the ragged mode refuses, before anything is launched (null: nothing)
 const char* ragged_mode_error(const mbv_model* m, const mbv_outputs* outs) {
   if (outs && (outs->o_mb || outs->spec || outs->phase)) return "the ragged decode writes the waveform only: o_mb / spec / phase must be NULL";
@@ -2547,54 +2579,51 @@ const char* ragged_mode_error(const mbv_model* m, const mbv_outputs* outs) {
 }
 
 // mbv_synthesize; y_lens_host != nullptr: the decoder in the row-exact ragged mode (mbv_synthesize_ragged)
-int synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
+int synthesize(mbv_model* m, const EncRun& r, int t_frames, const float* noise, float noise_scale, int max_len,
                const mbv_outputs* outs, const int64_t* y_lens_host, void* stream) {
   const char* const who = y_lens_host ? "mbv_synthesize_ragged" : "mbv_synthesize";
-  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
   if (t_frames <= 0) return m->fail("t_frames must be > 0");
   const mbv_config& c = m->cfg;
   std::vector<RaggedRun> runs;
   if (y_lens_host) {
     const char* why = ragged_mode_error(m, outs);
-    if (!why) why = ragged_lens_error(y_lens_host, m->B, t_frames);
+    if (!why) why = ragged_lens_error(y_lens_host, r.B, t_frames);
     if (why) return m->fail("%s: %s", who, why);
   }
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
-  const int B = m->B, T = m->T, Tp = t_frames, I = c.inter_channels;
+  const int B = r.B, T = r.T, Tp = t_frames, I = c.inter_channels;
   const int Td = (max_len > 0 && max_len < Tp) ? max_len : Tp;
   const size_t BTp = (size_t)B * Tp;
   const bool run_dec = outs && (outs->o || outs->o_mb || outs->spec || outs->phase);
   if (y_lens_host && run_dec) ragged_plan(m, B, Td, y_lens_host, &runs);
   float* z;
   FlowBufs fb{};
-  const bool with_g = m->has_g && c.gin_channels;
+  const bool with_g = r.has_g && c.gin_channels;
   DecBufs dec;
   std::vector<RunBufs> run_bufs;
-  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, who, m->scrB, [&](Bump& b) {
         z = outs && outs->z ? outs->z : b.take<float>(BTp * I);
         fb = carve_flow(b, c, B, Tp, kFlowLayers);
         if (run_dec && y_lens_host) carve_runs(m, runs, nullptr, with_g, b, &run_bufs);
         else if (run_dec) carve_decoder(m, DecCall{B, Td, Tp, true, with_g, !outs->o, false, false}, b, &dec);
       })) return 1;
-  for (const char* k : {"dec_conv_pre", "dec_up_0", "dec_up_1", "dec_res_0", "dec_res_1", "x_post"})
-    m->stages.erase(k);
 
   HIPCHK(m, hipEventRecord(m->ev[3], s));
   // m_text / logs_text are the two halves of enc_p.proj's output [B, 2I, T]
-  launch_expand(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32,
+  launch_expand(r.stats, r.stats + (size_t)I * T, (int64_t)2 * I * T, r.cum, r.ylen32,
                 noise_scale != 0.f ? noise : nullptr, noise_scale,
                 outs ? outs->m_p : nullptr, outs ? outs->logs_p : nullptr, outs ? outs->z_p : nullptr, z,
                 outs ? outs->attn : nullptr, outs ? outs->y_mask : nullptr, B, I, T, Tp, s);
   HIPCHK(m, hipEventRecord(m->ev[4], s));
 
   // ---- reverse flows, in place on z (models.py:207-214, modules.py:334-353)
-  if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
+  if (int rc = run_flows(m, true, z, r.has_g ? r.gvec : nullptr, fb, r.ylen32, B, Tp, s)) return rc;
   HIPCHK(m, hipEventRecord(m->ev[5], s));
   if (run_dec && y_lens_host) {
-    if (run_decoder_ragged(m, z, Tp, m->has_g ? m->gvec : nullptr, B, Td, runs, outs->o, (int64_t)m->dec_table.back().rate * Td, s, run_bufs)) return 1;
+    if (run_decoder_ragged(m, z, Tp, r.has_g ? r.gvec : nullptr, B, Td, runs, outs->o, (int64_t)m->dec_table.back().rate * Td, s, run_bufs)) return 1;
   } else if (run_dec) {
-    if (run_decoder(m, z, m->ylen32, m->has_g ? m->gvec : nullptr, outs, s, dec)) return 1;
+    if (run_decoder(m, z, r.ylen32, r.has_g ? r.gvec : nullptr, outs, s, dec)) return 1;
   }
   HIPCHK(m, hipEventRecord(m->ev[6], s));
   HIPCHK(m, hipGetLastError());
@@ -2696,15 +2725,16 @@ extern "C" {
 
 int mbv_synthesize(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
                    const mbv_outputs* outs, void* stream) {
-  if (!m) return 1;
-  return synthesize(m, t_frames, noise, noise_scale, max_len, outs, nullptr, stream);
+  const EncRun* r = cur_run(m, "mbv_synthesize");
+  return r ? synthesize(m, *r, t_frames, noise, noise_scale, max_len, outs, nullptr, stream) : 1;
 }
 
 int mbv_synthesize_ragged(mbv_model* m, int t_frames, const float* noise, float noise_scale, int max_len,
                           const mbv_outputs* outs, const int64_t* y_lengths_host, void* stream) {
   if (!m) return 1;
   if (!y_lengths_host) return m->fail("mbv_synthesize_ragged: y_lengths_host is NULL");
-  return synthesize(m, t_frames, noise, noise_scale, max_len, outs, y_lengths_host, stream);
+  const EncRun* r = cur_run(m, "mbv_synthesize_ragged");
+  return r ? synthesize(m, *r, t_frames, noise, noise_scale, max_len, outs, y_lengths_host, stream) : 1;
 }
 
 int mbv_admit_plan(const mbv_config* cfg, int splitk, int n, const int32_t* t_text, int32_t* run_of_request) {
@@ -2719,7 +2749,7 @@ int mbv_encode_rows(mbv_model* m, int slot, const int64_t* ids, const int64_t* l
   if (!m) return 1;
   const char* who = "mbv_encode_rows";
   if (!rows_host || !y_lengths_out || B <= 0 || T <= 0) return m->fail("%s: bad arguments", who);
-  if (slot < 0 || slot >= 64) return m->fail("%s: slot must be in [0, 64)", who);
+  if (slot < 0 || slot >= mbv_model::kSlots) return m->fail("%s: slot must be in [0, %d)", who, mbv_model::kSlots);
   if (B > 65535) return m->fail("%s: at most 65535 rows a run (mbv_admit_plan cuts there)", who);
   if (m->conv_bf16) return m->fail("%s: pooled admission is not built for the \"conv_bf16\" mode", who);
   for (int i = 0; i < B; ++i) {
@@ -2737,28 +2767,17 @@ int mbv_encode_rows(mbv_model* m, int slot, const int64_t* ids, const int64_t* l
     if (admit_plan(m->cfg, m->splitk, B, tt.data(), nullptr) != 1)
       return m->fail("%s: the rows belong to more than one run of mbv_admit_plan", who);
   }
-  if ((size_t)slot >= m->slots.size()) m->slots.resize(slot + 1);
-  mbv_model::EncSlot& sl = m->slots[slot];
-  sl.valid = false;
-  if (slot > 0) { std::swap(m->scrA, sl.scr); std::swap(m->scrA_bytes, sl.bytes); }
-  const int rc = encode(m, ids, lengths, sid, B, T, 1.f, nullptr, 1.f, rows_host, y_lengths_out, stream);
-  if (slot > 0) { std::swap(m->scrA, sl.scr); std::swap(m->scrA_bytes, sl.bytes); }
-  if (rc) { m->encoded = false; return rc; }
-  sl.valid = true; sl.enc = *m;
-  return 0;
+  return encode(m, m->runs[slot], ids, lengths, sid, B, T, 1.f, nullptr, 1.f, rows_host, y_lengths_out, stream);
 }
 
 int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* rows_host, int n, void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_synthesize_rows";
-  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
-    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
-  const mbv_model::EncSlot& sl = m->slots[slot];
-  if (!rows_host || n != sl.enc.B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, sl.enc.B, n);
+  const EncRun* r = rows_run(m, who, slot, rows_host, n);
+  if (!r) return 1;
   if (t_frames <= 0) return m->fail("t_frames must be > 0");
   if (m->conv_bf16) return m->fail("%s: pooled admission is not built for the \"conv_bf16\" mode", who);
   const mbv_config& c = m->cfg;
-  const int B = sl.enc.B, T = sl.enc.T, Tp = t_frames, I = c.inter_channels;
+  const int B = r->B, T = r->T, Tp = t_frames, I = c.inter_channels;
   int max_keep = 0;
   std::vector<AdmitSynRow> rows_h(n);
   for (int i = 0; i < n; ++i) {
@@ -2781,18 +2800,16 @@ int mbv_synthesize_rows(mbv_model* m, int slot, int t_frames, const mbv_row* row
   float* z;
   FlowBufs fb{};
   AdmitSynRow* rows;
-  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, who, m->scrB, [&](Bump& b) {
         z = b.take<float>(BTp * I);
         fb = carve_flow(b, c, B, Tp, kFlowLayers);
         rows = b.take<AdmitSynRow>(B);
       })) return 1;
-  // the run becomes the handle's "last encode", as if mbv_encode had just made it
-  static_cast<EncState&>(*m) = sl.enc;
-  m->encoded = true;
+  m->cur = slot;                    // the plain entries act on this run from here on, as if mbv_encode had just made it
   upload_rows<kAdmitChunk>(B, rows, s, [&](size_t i) { return rows_h[i]; });
-  launch_expand_rows(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, rows, z, B, I, T, Tp, s);
-  if (int rc = run_flows(m, true, z, m->has_g ? m->gvec : nullptr, fb, m->ylen32, B, Tp, s)) return rc;
-  launch_scatter_z_rows(z, m->ylen32, rows, B, I, Tp, max_keep, s);
+  launch_expand_rows(r->stats, r->stats + (size_t)I * T, (int64_t)2 * I * T, r->cum, r->ylen32, rows, z, B, I, T, Tp, s);
+  if (int rc = run_flows(m, true, z, r->has_g ? r->gvec : nullptr, fb, r->ylen32, B, Tp, s)) return rc;
+  launch_scatter_z_rows(z, r->ylen32, rows, B, I, Tp, max_keep, s);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -2840,7 +2857,7 @@ int mbv_decode_ragged(mbv_model* m, const float* z, const float* g, int B, int t
   ragged_plan(m, B, t_frames, lengths_host, &runs);
   if (!c.gin_channels) g = nullptr;
   std::vector<RunBufs> bufs;
-  if (lay_out(m, "mbv_decode_ragged", &m->scrB, &m->scrB_bytes, [&](Bump& b) { carve_runs(m, runs, nullptr, g != nullptr, b, &bufs); }))
+  if (lay_out(m, "mbv_decode_ragged", m->scrB, [&](Bump& b) { carve_runs(m, runs, nullptr, g != nullptr, b, &bufs); }))
     return 1;
   m->stages.clear();
   if (run_decoder_ragged(m, z, t_frames, g, B, t_frames, runs, o, (int64_t)m->dec_table.back().rate * t_frames, (hipStream_t)stream, bufs))
@@ -2859,7 +2876,7 @@ static int decode_entry(mbv_model* m, const char* who, const float* z, const flo
   DEVICE_GUARD(m);
   if (!c.gin_channels) g = nullptr;
   DecBufs dec;
-  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, who, m->scrB, [&](Bump& b) {
         carve_decoder(m, DecCall{B, t_frames, t_frames, lengths != nullptr, g != nullptr, !outs->o, false, false}, b, &dec);
       })) return 1;
   m->stages.clear();
@@ -2908,7 +2925,7 @@ int mbv_decode_range(mbv_model* m, const float* z, const float* g, int B, int t_
   DEVICE_GUARD(m);
   if (!c.gin_channels) g = nullptr;
   DecBufs dec;
-  if (lay_out(m, "mbv_decode_range", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, "mbv_decode_range", m->scrB, [&](Bump& b) {
         carve_decoder(m, DecCall{B, Tw, t_frames, false, g != nullptr, false, true, false}, b, &dec);
       })) return 1;
   m->stages.clear();
@@ -2972,7 +2989,7 @@ int mbv_decode_chunks_routed(mbv_model* m, const mbv_chunk* chunks_host, const i
   std::vector<int> widths(runs.size());
   for (size_t r = 0; r < runs.size(); ++r) { int mc; pooled_run_extent(chunks_host, runs[r], Lc, Rc, &widths[r], &mc); }
   std::vector<RunBufs> bufs;
-  if (lay_out(m, "mbv_decode_chunks", &m->scrB, &m->scrB_bytes, [&](Bump& b) { carve_runs(m, runs, &widths, with_g != 0, b, &bufs); }))
+  if (lay_out(m, "mbv_decode_chunks", m->scrB, [&](Bump& b) { carve_runs(m, runs, &widths, with_g != 0, b, &bufs); }))
     return 1;
   m->stages.clear();
   if (run_decoder_pooled(m, chunks_host, with_g != 0, runs, Lc, Rc, (hipStream_t)stream, bufs)) return 1;
@@ -3151,7 +3168,7 @@ int mbv_voice_conversion(mbv_model* m, const float* y, const int64_t* y_lengths,
   float *zbuf, *zhat, *g_src, *g_tgt;
   int *lens, *bad;
   DecBufs dec;
-  if (lay_out(m, "mbv_voice_conversion", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, "mbv_voice_conversion", m->scrB, [&](Bump& b) {
         pb = carve_posterior(b, m, B, T);
         zbuf = outs->z ? outs->z : b.take<float>(BT * I);
         zhat = outs->m_p ? outs->m_p : b.take<float>(BT * I);
@@ -3198,30 +3215,31 @@ int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const fl
   const int I = c.inter_channels, gin = c.gin_channels;
   const int T = T_text, Tp = T_spec;
   const size_t BT = (size_t)B * T, BTp = (size_t)B * Tp;
-  // ---- text side, in the scratch of mbv_encode (whose state it therefore ends)
-  m->encoded = false;
+  // ---- text side, in the scratch of mbv_encode: the claim ends the run that lived there, and `r` is this call's alone
+  m->cur = -1;
   m->stages.clear();
+  EncRun r;
   TextEncBufs te{};
   int *w32, *bad_y, *ylens, *mas;
-  if (lay_out(m, "mbv_align", &m->scrA, &m->scrA_bytes, [&](Bump& b) {
-        te = carve_text(b, m, B, T);
-        m->cum = b.take<int>(BT);
+  if (lay_out(m, "mbv_align", m->scrA, [&](Bump& b) {
+        te = carve_text(b, m, r, B, T);
+        r.cum = b.take<int>(BT);
         w32 = b.take<int>(BT);
-        m->lens32 = b.take<int>(B);
-        m->ylen32 = b.take<int>(B);
-        m->bad32 = b.take<int>(B);
+        r.lens32 = b.take<int>(B);
+        r.ylen32 = b.take<int>(B);
+        r.bad32 = b.take<int>(B);
         bad_y = b.take<int>(B);
         ylens = b.take<int>(B);
         mas = b.take<int>(B);
-        m->gvec = b.take<float>((size_t)B * (gin ? gin : 1));
+        r.gvec = b.take<float>((size_t)B * (gin ? gin : 1));
       })) return 1;
-  int* const bad_x = m->bad32;
+  int* const bad_x = r.bad32;
   // ---- posterior side
   const size_t bits_bytes = max_path_scratch_bytes(B, Tp, T);
   PosteriorBufs pb{};
   float *zbuf, *zp, *value;
   void* bits = nullptr;
-  if (lay_out(m, "mbv_align", &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, "mbv_align", m->scrB, [&](Bump& b) {
         pb = carve_posterior(b, m, B, Tp);
         zbuf = outs->z ? outs->z : b.take<float>(BTp * I);
         zp = outs->z_p ? outs->z_p : b.take<float>(BTp * I);
@@ -3230,65 +3248,62 @@ int mbv_align(mbv_model* m, const int64_t* ids, const int64_t* lengths, const fl
       })) return 1;
   int* w_out = outs->w ? outs->w : w32;
 
-  run_text_encoder(m, ids, lengths, te, bad_x, B, T, s);
+  run_text_encoder(m, r, ids, lengths, te, bad_x, B, T, s);
   const float* g = nullptr;
   if (c.n_speakers > 0) {
-    launch_gather_rows(m->W(m->emb_g.off), sid, m->gvec, B, gin, c.n_speakers, bad_x, s, m->voice_table());
-    g = m->gvec;
+    launch_gather_rows(m->W(m->emb_g.off), sid, r.gvec, B, gin, c.n_speakers, bad_x, s, m->voice_table());
+    g = r.gvec;
   }
   launch_lens_to_i32(y_lengths, ylens, B, Tp, bad_y, s);
   if (run_enc_q(m, y, ylens, g, noise_scale != 0.f ? noise : nullptr, noise_scale, pb, zbuf, B, Tp, s)) return 1;
   HIPCHK(m, hipMemcpyAsync(zp, zbuf, BTp * I * 4, hipMemcpyDeviceToDevice, s));
   if (int rc = run_flows(m, false, zp, g, pb, ylens, B, Tp, s)) return rc;
   // ---- neg_cent, the search, the durations (models.py:668-680)
-  launch_neg_cent(zp, m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, ylens, m->lens32, value, B, I, Tp, T, s);
-  launch_max_path(value, ylens, m->lens32, w_out, nullptr, mas, bits, B, Tp, T, s);
+  launch_neg_cent(zp, r.stats, r.stats + (size_t)I * T, (int64_t)2 * I * T, ylens, r.lens32, value, B, I, Tp, T, s);
+  launch_max_path(value, ylens, r.lens32, w_out, nullptr, mas, bits, B, Tp, T, s);
   launch_align_status(bad_x, bad_y, mas, status, nullptr, nullptr, B, T, s);
   // ---- the path as length regulation takes it, and the expanded prior (:690-691)
   if (outs->attn || outs->m_p || outs->logs_p) {
-    launch_set_durations(w_out, 0, m->lens32, nullptr, m->cum, m->ylen32, nullptr, nullptr, B, T, s);
+    launch_set_durations(w_out, 0, r.lens32, nullptr, r.cum, r.ylen32, nullptr, nullptr, B, T, s);
     // (a refused row has w = 0: y_len 1 and no token for its frame; pb.stats is free again and takes the copy `z`)
-    launch_expand(m->stats, m->stats + (size_t)I * T, (int64_t)2 * I * T, m->cum, m->ylen32, nullptr, 0.f, outs->m_p,
+    launch_expand(r.stats, r.stats + (size_t)I * T, (int64_t)2 * I * T, r.cum, r.ylen32, nullptr, 0.f, outs->m_p,
                   outs->logs_p, nullptr, pb.stats, outs->attn, nullptr, B, I, T, Tp, s);
   }
-  if (outs->x_mask) launch_sequence_mask(m->lens32, outs->x_mask, B, T, s);
+  if (outs->x_mask) launch_sequence_mask(r.lens32, outs->x_mask, B, T, s);
   if (outs->y_mask) launch_sequence_mask(ylens, outs->y_mask, B, Tp, s);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 int mbv_set_durations(mbv_model* m, const void* w, int dtype, int B, int T, int64_t* y_lengths_out, void* stream) {
-  if (!m) return 1;
-  if (!m->encoded) return m->fail("mbv_set_durations without a preceding mbv_encode");
+  const EncRun* r = cur_run(m, "mbv_set_durations");
+  if (!r) return 1;
   if (!w || !y_lengths_out) return m->fail("mbv_set_durations: NULL argument");
   if (dtype < 0 || dtype > 2) return m->fail("mbv_set_durations: dtype must be 0 (int32), 1 (int64) or 2 (fp32)");
-  if (B != m->B || T != m->T) return m->fail("mbv_set_durations: w must be [%d, %d] as the encoded batch, got [%d, %d]", m->B, m->T, B, T);
+  if (B != r->B || T != r->T) return m->fail("mbv_set_durations: w must be [%d, %d] as the encoded batch, got [%d, %d]", r->B, r->T, B, T);
   DEVICE_GUARD(m);
-  launch_set_durations(w, dtype, m->lens32, m->w_ceil, m->cum, m->ylen32, y_lengths_out, m->bad32, B, T, (hipStream_t)stream);
+  launch_set_durations(w, dtype, r->lens32, r->w_ceil, r->cum, r->ylen32, y_lengths_out, r->bad32, B, T, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 int mbv_token_marks(mbv_model* m, int64_t* marks, int64_t marks_stride, void* stream) {
-  if (!m) return 1;
-  if (!m->encoded) return m->fail("mbv_token_marks without a preceding mbv_encode");
-  if (!marks || marks_stride < (int64_t)m->T + 1)
-    return m->fail("mbv_token_marks: marks must be [%d, marks_stride >= %d]", m->B, m->T + 1);
-  if (m->B > 65535) return m->fail("mbv_token_marks: more than 65535 rows");
+  const EncRun* r = cur_run(m, "mbv_token_marks");
+  if (!r) return 1;
+  if (!marks || marks_stride < (int64_t)r->T + 1)
+    return m->fail("mbv_token_marks: marks must be [%d, marks_stride >= %d]", r->B, r->T + 1);
+  if (r->B > 65535) return m->fail("mbv_token_marks: more than 65535 rows");
   DEVICE_GUARD(m);
-  launch_token_marks(m->cum, m->B, m->T, marks, marks_stride, m->T + 1, nullptr, (hipStream_t)stream);
+  launch_token_marks(r->cum, r->B, r->T, marks, marks_stride, r->T + 1, nullptr, (hipStream_t)stream);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 int mbv_token_marks_rows(mbv_model* m, int slot, const mbv_mark_row* rows_host, int n, void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_token_marks_rows";
-  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
-    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
-  const mbv_model::EncSlot& sl = m->slots[slot];
-  const int B = sl.enc.B, T = sl.enc.T;
-  if (!rows_host || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
+  const EncRun* r = rows_run(m, who, slot, rows_host, n);
+  if (!r) return 1;
+  const int B = r->B, T = r->T;
   bool any = false;
   for (int i = 0; i < n; ++i) {
     const mbv_mark_row& k = rows_host[i];
@@ -3298,11 +3313,11 @@ int mbv_token_marks_rows(mbv_model* m, int slot, const mbv_mark_row* rows_host, 
   }
   if (!any) return 0;                                      // nothing to write
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, (size_t)n * sizeof(MarkRow))) return 1;
+  if (ensure(m, m->scrB, (size_t)n * sizeof(MarkRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  MarkRow* rows = reinterpret_cast<MarkRow*>(m->scrB);
+  MarkRow* rows = reinterpret_cast<MarkRow*>(m->scrB.p);
   upload_rows<kAdmitChunk>(n, rows, s, [&](size_t i) { return MarkRow{rows_host[i].marks, rows_host[i].marks ? rows_host[i].count : 0, 0}; });
-  launch_token_marks(sl.enc.cum, B, T, nullptr, 0, 0, rows, s);
+  launch_token_marks(r->cum, B, T, nullptr, 0, 0, rows, s);
   HIPCHK(m, hipGetLastError());
   return 0;
 }
@@ -3320,8 +3335,8 @@ int upload_fit(mbv_model* m, const mbv_fit* fit_host, int B, const ShapeRow** ou
   bool any = false;
   for (int b = 0; fit_host && b < B; ++b) any = any || fit_host[b].frames > 0;
   if (!any) return 0;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, (size_t)B * sizeof(ShapeRow))) return 1;
-  ShapeRow* t = reinterpret_cast<ShapeRow*>(m->scrB);
+  if (ensure(m, m->scrB, (size_t)B * sizeof(ShapeRow))) return 1;
+  ShapeRow* t = reinterpret_cast<ShapeRow*>(m->scrB.p);
   upload_rows<kShapeChunk>(B, t, s, [&](size_t b) {
     ShapeRow r{};
     r.frames = fit_host[b].frames; r.lo = fit_host[b].lo; r.hi = fit_host[b].hi;
@@ -3334,63 +3349,59 @@ int upload_fit(mbv_model* m, const mbv_fit* fit_host, int B, const ShapeRow** ou
 
 int mbv_shape_durations(mbv_model* m, const float* scale, const int32_t* extra, const mbv_fit* fit_host, int B, int T,
                         mbv_fit_result* fit_out, int64_t* y_lengths_out, void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_shape_durations";
-  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
+  const EncRun* r = cur_run(m, who);
+  if (!r) return 1;
   if (!y_lengths_out) return m->fail("%s: NULL argument", who);
-  if (B != m->B || T != m->T) return m->fail("%s: the tables must be [%d, %d] as the encoded batch, got [%d, %d]", who, m->B, m->T, B, T);
-  if (m->scales.size() != 1) return m->fail("%s: the last encode was mbv_encode_rows (use mbv_shape_durations_rows)", who);
+  if (B != r->B || T != r->T) return m->fail("%s: the tables must be [%d, %d] as the encoded batch, got [%d, %d]", who, r->B, r->T, B, T);
+  if (r->rows) return m->fail("%s: the last encode was mbv_encode_rows (use mbv_shape_durations_rows)", who);
   bool any_fit = false;
   for (int b = 0; fit_host && b < B; ++b) {
     if (const char* why = fit_error(fit_host[b])) return m->fail("%s: row %d: %s", who, b, why);
     any_fit = any_fit || fit_host[b].frames > 0;
   }
   if (!scale && !extra && !any_fit) return m->fail("%s: nothing to do (no scale table, no extra frames, no fit)", who);
-  if (scale && m->scales[0] != 1.f) return m->fail("%s: a scale table needs an encode with length_scale 1 (it was %g)", who, m->scales[0]);
+  if (scale && r->scales[0] != 1.f) return m->fail("%s: a scale table needs an encode with length_scale 1 (it was %g)", who, r->scales[0]);
   DEVICE_GUARD(m);
   hipStream_t s = (hipStream_t)stream;
   const ShapeRow* fit = nullptr;
   if (upload_fit(m, fit_host, B, &fit, s)) return 1;
-  launch_shape_durations(m->logw, m->lens32, scale, extra, m->scales[0], fit, m->w_ceil, m->cum, m->ylen32, y_lengths_out,
-                         m->bad32, m->fit, reinterpret_cast<FitOut*>(fit_out), B, T, s);
+  launch_shape_durations(r->logw, r->lens32, scale, extra, r->scales[0], fit, r->w_ceil, r->cum, r->ylen32, y_lengths_out,
+                         r->bad32, r->fit, reinterpret_cast<FitOut*>(fit_out), B, T, s);
   ++m->shape_runs;
   HIPCHK(m, hipGetLastError());
-  m->stages["fit_scale"] = {m->fit, (int64_t)B};
-  m->stages["fit_status"] = {m->fit + B, (int64_t)B};
+  m->stage("fit_scale", r->fit, (int64_t)B, *r->home);
+  m->stage("fit_status", r->fit + B, (int64_t)B, *r->home);
   return 0;
 }
 
 int mbv_shape_durations_rows(mbv_model* m, int slot, const mbv_shape_row* rows_host, int n, int64_t* y_lengths_out,
                              void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_shape_durations_rows";
-  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
-    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
-  const mbv_model::EncSlot& sl = m->slots[slot];
-  const int B = sl.enc.B, T = sl.enc.T;
-  if (!rows_host || !y_lengths_out || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
-  if ((int)sl.enc.scales.size() != B) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot);
+  const EncRun* r = rows_run(m, who, slot, y_lengths_out ? rows_host : nullptr, n);
+  if (!r) return 1;
+  const int T = r->T;
   std::vector<int> live;
   for (int i = 0; i < n; ++i) {
     const mbv_shape_row& k = rows_host[i];
     if (const char* why = fit_error(k.fit)) return m->fail("%s: row %d: %s", who, i, why);
-    if (k.scale && sl.enc.scales[i] != 1.f)
-      return m->fail("%s: row %d: a scale table needs a row encoded with length_scale 1 (it was %g)", who, i, sl.enc.scales[i]);
+    if (k.scale && r->scales[i] != 1.f)
+      return m->fail("%s: row %d: a scale table needs a row encoded with length_scale 1 (it was %g)", who, i, r->scales[i]);
     if (k.scale || k.extra || k.fit.frames > 0) live.push_back(i);
   }
   if (live.empty()) return m->fail("%s: nothing to do (no row has a scale table, extra frames or a fit)", who);
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(ShapeRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(ShapeRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  ShapeRow* rows = reinterpret_cast<ShapeRow*>(m->scrB);
+  ShapeRow* rows = reinterpret_cast<ShapeRow*>(m->scrB.p);
   // (t_text: the row's tensors end there; the kernel also stops at the row's x_length)
   upload_rows<kShapeChunk>(live.size(), rows, s, [&](size_t j) {
     const mbv_shape_row& k = rows_host[live[j]];
     return ShapeRow{k.scale, k.extra, reinterpret_cast<FitOut*>(k.fit_out), k.fit.frames, k.fit.lo, k.fit.hi,
-                    sl.enc.scales[live[j]], live[j], sl.enc.t_text[live[j]], 0};
+                    r->scales[live[j]], live[j], r->t_text[live[j]], 0};
   });
-  launch_shape_durations_rows(sl.enc.logw, sl.enc.lens32, rows, (int)live.size(), sl.enc.w_ceil, sl.enc.cum, sl.enc.ylen32,
-                              y_lengths_out, sl.enc.bad32, T, s);
+  launch_shape_durations_rows(r->logw, r->lens32, rows, (int)live.size(), r->w_ceil, r->cum, r->ylen32,
+                              y_lengths_out, r->bad32, T, s);
   ++m->shape_runs;
   HIPCHK(m, hipGetLastError());
   return 0;
@@ -3399,29 +3410,25 @@ int mbv_shape_durations_rows(mbv_model* m, int slot, const mbv_shape_row* rows_h
 int64_t mbv_shape_runs(mbv_model* m) { return m ? m->shape_runs : -1; }
 
 int mbv_frame_gain(mbv_model* m, const float* gain, float* out, int64_t out_stride, int frames, void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_frame_gain";
-  if (!m->encoded) return m->fail("%s without a preceding mbv_encode", who);
+  const EncRun* r = cur_run(m, who);
+  if (!r) return 1;
   if (!gain || !out) return m->fail("%s: NULL argument", who);
   if (frames < 1 || frames > (1 << 30)) return m->fail("%s: frames must be in [1, 2^30], got %d", who, frames);
-  if (out_stride < (int64_t)frames + 1) return m->fail("%s: out must be [%d, out_stride >= frames + 1 = %d]", who, m->B, frames + 1);
-  if (m->B > 65535) return m->fail("%s: more than 65535 rows", who);
+  if (out_stride < (int64_t)frames + 1) return m->fail("%s: out must be [%d, out_stride >= frames + 1 = %d]", who, r->B, frames + 1);
+  if (r->B > 65535) return m->fail("%s: more than 65535 rows", who);
   DEVICE_GUARD(m);
-  launch_frame_gain(m->cum, m->ylen32, nullptr, gain, out, out_stride, frames, m->B, m->T, (hipStream_t)stream);
+  launch_frame_gain(r->cum, r->ylen32, nullptr, gain, out, out_stride, frames, r->B, r->T, (hipStream_t)stream);
   ++m->gain_runs;
   HIPCHK(m, hipGetLastError());
   return 0;
 }
 
 int mbv_frame_gain_rows(mbv_model* m, int slot, const mbv_gain_row* rows_host, int n, void* stream) {
-  if (!m) return 1;
   const char* who = "mbv_frame_gain_rows";
-  if (slot < 0 || (size_t)slot >= m->slots.size() || !m->slots[slot].valid)
-    return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
-  const mbv_model::EncSlot& sl = m->slots[slot];
-  const int B = sl.enc.B, T = sl.enc.T;
-  if (!rows_host || n != B) return m->fail("%s: one row per encoded utterance expected (%d), got %d", who, B, n);
-  if ((int)sl.enc.t_text.size() != B) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot);
+  const EncRun* r = rows_run(m, who, slot, rows_host, n);
+  if (!r) return 1;
+  const int T = r->T;
   std::vector<int> live;
   int max_frames = 0;
   for (int i = 0; i < n; ++i) {
@@ -3437,14 +3444,14 @@ int mbv_frame_gain_rows(mbv_model* m, int slot, const mbv_gain_row* rows_host, i
   }
   if (live.empty()) return 0;                              // nothing to write (a run holds at most 65535 rows: the grid's y)
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(GainRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(GainRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  GainRow* rows = reinterpret_cast<GainRow*>(m->scrB);
+  GainRow* rows = reinterpret_cast<GainRow*>(m->scrB.p);
   upload_rows<kAdmitChunk>(live.size(), rows, s, [&](size_t j) {
     const mbv_gain_row& k = rows_host[live[j]];
-    return GainRow{k.gain, k.out, live[j], sl.enc.t_text[live[j]], k.frames, 0};
+    return GainRow{k.gain, k.out, live[j], r->t_text[live[j]], k.frames, 0};
   });
-  launch_frame_gain_rows(sl.enc.cum, sl.enc.ylen32, rows, (int)live.size(), max_frames, T, s);
+  launch_frame_gain_rows(r->cum, r->ylen32, rows, (int)live.size(), max_frames, T, s);
   ++m->gain_runs;
   HIPCHK(m, hipGetLastError());
   return 0;
@@ -3930,17 +3937,17 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
     if (t.fade) t.fades = take(kind.size() * sizeof(PcmFade));
     if (t.env) t.envs = take(kind.size() * sizeof(PcmEnv));
   }
-  if (ensure(m, &m->scrB, &m->scrB_bytes, end)) return 1;
+  if (ensure(m, m->scrB, end)) return 1;
   hipStream_t s = (hipStream_t)stream;
-  const char* head = m->scrB + head_at;
-  side.head(m->scrB + head_at, s);
+  const char* head = m->scrB.p + head_at;
+  side.head(m->scrB.p + head_at, s);
   // per kind: its row table, its side rows, its fade and envelope tables in the order of the row table (null for a
   // kind without one), and one launch per 65535 rows
   for (int k = 0; k < 2; ++k) {
     const std::vector<int>& kind = live[k];
     if (kind.empty()) continue;
     const Kind& t = kinds[k];
-    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB + t.rows);
+    PcmPoolRow* rows = reinterpret_cast<PcmPoolRow*>(m->scrB.p + t.rows);
     upload_rows<kPcmPoolChunk>(kind.size(), rows, s, [&](size_t j) {
       const int i = kind[j];
       const mbv_pcm_chunk& c = at(i);
@@ -3949,16 +3956,16 @@ int pooled_wire(mbv_model* m, const char* who, const char* noun, At at, const mb
                         c.out_samples, packed ? off[i] : (int64_t)-1,
                         k ? LimiterParams{limits[i].ceiling, limits[i].lookahead, limits[i].hold} : LimiterParams{}, 0};
     });
-    side.rows(kind, m->scrB + t.side, s);
-    PcmFade* ft = t.fade ? reinterpret_cast<PcmFade*>(m->scrB + t.fades) : nullptr;
+    side.rows(kind, m->scrB.p + t.side, s);
+    PcmFade* ft = t.fade ? reinterpret_cast<PcmFade*>(m->scrB.p + t.fades) : nullptr;
     if (ft) upload_rows<kPcmPoolChunk>(kind.size(), ft, s, [&](size_t j) { return fade_of(&fades[kind[j]]); });
-    PcmEnv* et = t.env ? reinterpret_cast<PcmEnv*>(m->scrB + t.envs) : nullptr;
+    PcmEnv* et = t.env ? reinterpret_cast<PcmEnv*>(m->scrB.p + t.envs) : nullptr;
     if (et) upload_rows<kPcmPoolChunk>(kind.size(), et, s, [&](size_t j) { return env_of(&envs[kind[j]]); });
     grid_y_slices(kind, [&](int i) { return at(i).out_count; }, [&](size_t f, int nn, int64_t max_count) {
       ++m->wire_runs;
       PcmPoolLaunch a{rows + f, k == 1, nullptr, nullptr, et ? et + f : nullptr, ft ? ft + f : nullptr, nn, max_count,
                       lds_floats, packed, law};
-      side.turn_fields(&a, m->scrB + t.side + f * side.row_bytes, head);
+      side.turn_fields(&a, m->scrB.p + t.side + f * side.row_bytes, head);
       launch_resample_pcm16_pool(a, rp.bank, rp.g, s);
       return 0;
     });
@@ -4293,9 +4300,9 @@ int mbv_resample_ranges(mbv_model* m, const mbv_resample_range* rows_host, int n
                                     [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].out_count; });
   if (clash.first >= 0)
     return m->fail("%s: rows %d and %d write overlapping ranges of one out", who, clash.first, clash.second);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(ResampleRangeRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(ResampleRangeRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  ResampleRangeRow* rows = reinterpret_cast<ResampleRangeRow*>(m->scrB);
+  ResampleRangeRow* rows = reinterpret_cast<ResampleRangeRow*>(m->scrB.p);
   upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
     const mbv_resample_range& k = rows_host[live[i]];
     return ResampleRangeRow{k.wave, k.wave_dtype, k.in_total >= 0 ? 1 : 0, k.in_avail, k.out_first,
@@ -4422,9 +4429,9 @@ int mbv_warp_ranges(mbv_model* m, const mbv_warp_row* rows_host, int n, void* st
     const int ft = rows_host[i].res_type;
     if (!win[ft] && warp_window(m, who, ft, &win[ft])) return 1;
   }
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(WarpRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(WarpRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  WarpRow* rows = reinterpret_cast<WarpRow*>(m->scrB);
+  WarpRow* rows = reinterpret_cast<WarpRow*>(m->scrB.p);
   upload_rows<kPcmPoolChunk>(live.size(), rows, s, [&](size_t i) {
     const mbv_warp_row& k = rows_host[live[i]];
     return WarpRow{k.wave, k.samples, k.in_avail, k.U, k.rate, k.frames, k.hop, env_of(&k.envelope), k.out_first,
@@ -4473,9 +4480,9 @@ int mbv_seam_rows(mbv_model* m, const mbv_seam_row* rows_host, int n, void* stre
                          [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].head_count; });
   if (clash.first >= 0) return m->fail("%s: rows %d and %d blend overlapping samples of one o", who, clash.first, clash.second);
   if (live.empty()) return 0;
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(SeamRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(SeamRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  SeamRow* rows = reinterpret_cast<SeamRow*>(m->scrB);
+  SeamRow* rows = reinterpret_cast<SeamRow*>(m->scrB.p);
   upload_rows<kSeamChunk>(live.size(), rows, s, [&](size_t i) {
     const mbv_seam_row& k = rows_host[live[i]];
     return SeamRow{k.o + k.head_first, k.o + k.over_first, k.stash, k.head_count, k.over_count, k.seam,
@@ -4520,9 +4527,9 @@ int mbv_randn_blocks(mbv_model* m, const mbv_randn_block* blocks_host, int n, vo
     if ((total + 255) / 256 > 0x7fffffff) return m->fail("%s: more work than one grid holds (block %d)", who, i);
   }
   if (live.empty()) return 0;
-  if (ensure(m, &m->noise_tab, &m->noise_tab_bytes, live.size() * sizeof(RandnRow))) return 1;
+  if (ensure(m, m->noise_tab, live.size() * sizeof(RandnRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  RandnRow* rows = reinterpret_cast<RandnRow*>(m->noise_tab);
+  RandnRow* rows = reinterpret_cast<RandnRow*>(m->noise_tab.p);
   upload_rows<kRandnChunk>(live.size(), rows, s, [&](size_t i) { return live[i]; });
   ++m->noise_runs;
   launch_randn_blocks(rows, (int)live.size(), total, s);
@@ -4599,9 +4606,9 @@ int loudness_chunks(mbv_model* m, const char* who, const mbv_loudness_chunk* chu
     if (chunks[i].seg_count == 0) m->loudness_next[chunks[i].state] = chunks[i].seg_first;
   if (live.empty()) return 0;
   DEVICE_GUARD(m);
-  if (ensure(m, &m->scrB, &m->scrB_bytes, live.size() * sizeof(LoudnessRow))) return 1;
+  if (ensure(m, m->scrB, live.size() * sizeof(LoudnessRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB);
+  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB.p);
   upload_rows<kLoudnessChunk>(live.size(), rows, s, [&](size_t i) {
     const mbv_loudness_chunk& k = chunks[live[i]];
     return LoudnessRow{k.wave, k.valid_samples, k.in_avail, k.seg_first, k.seg_first + k.seg_count, k.state, k.energies,
@@ -4659,11 +4666,11 @@ int mbv_loudness(mbv_model* m, const float* wave, const int64_t* valid_samples, 
   // scratch: the rows' states, their energies where the caller wants none, then the table
   const size_t energy_at = align_up((size_t)B * 4 * sizeof(double), 256);
   const size_t table_at = energy_at + (energies ? 0 : align_up((size_t)B * (size_t)segs * sizeof(double), 256));
-  if (ensure(m, &m->scrB, &m->scrB_bytes, table_at + (size_t)B * sizeof(LoudnessRow))) return 1;
+  if (ensure(m, m->scrB, table_at + (size_t)B * sizeof(LoudnessRow))) return 1;
   hipStream_t s = (hipStream_t)stream;
-  double* state = reinterpret_cast<double*>(m->scrB);
-  double* e = energies ? energies : reinterpret_cast<double*>(m->scrB + energy_at);
-  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB + table_at);
+  double* state = reinterpret_cast<double*>(m->scrB.p);
+  double* e = energies ? energies : reinterpret_cast<double*>(m->scrB.p + energy_at);
+  LoudnessRow* rows = reinterpret_cast<LoudnessRow*>(m->scrB.p + table_at);
   upload_rows<kLoudnessChunk>((size_t)B, rows, s, [&](size_t b) {
     return LoudnessRow{wave + b * in_stride, valid_samples ? valid_samples + b : nullptr, in_stride, 0, segs,
                        state + 4 * b, e + b * segs, loudness + b};
@@ -4852,7 +4859,7 @@ int run_posterior_rows(mbv_model* m, const char* who, const std::vector<ConvertR
   ConvertRow* crows;
   AdmitSynRow* srows;
   int64_t *sid_src, *sid_tgt;
-  if (lay_out(m, who, &m->scrB, &m->scrB_bytes, [&](Bump& b) {
+  if (lay_out(m, who, m->scrB, [&](Bump& b) {
         pb = carve_posterior(b, m, B, T);
         z = b.take<float>(BT * I);
         g_src = b.take<float>((size_t)B * gin);
@@ -4864,7 +4871,7 @@ int run_posterior_rows(mbv_model* m, const char* who, const std::vector<ConvertR
         sid_tgt = b.take<int64_t>(B);
       })) return 1;
   m->stages.clear();
-  m->stages["convert_ypad"] = StageRef{pb.ypad, (int64_t)(BT * m->encq.cin_pad)};
+  m->stage("convert_ypad", pb.ypad, (int64_t)(BT * m->encq.cin_pad), m->scrB);
   upload_rows<kAdmitChunk>(B, crows, s, [&](size_t i) { return crows_h[i]; }, ConvertRowCols{lens, sid_src, sid_tgt});
   upload_rows<kAdmitChunk>(B, srows, s, [&](size_t i) { return srows_h[i]; });
   ++m->converter_runs;
@@ -5068,20 +5075,21 @@ int64_t mbv_read_stage(mbv_model* m, const char* name, float* dst, int64_t capac
   // m_text / logs_text are strided halves of `stats` [B, 2I, T]
   if (n == "m_text" || n == "logs_text") {
     auto it = m->stages.find("stats");
-    if (it == m->stages.end()) { m->fail("stage '%s' not available", name); return -1; }
-    const int I = c.inter_channels;
-    numel = (int64_t)m->B * I * m->T;
+    const EncRun* r = m->cur >= 0 ? &m->runs[m->cur] : nullptr;     // (the stage must be this run's: a later pooled run may be current)
+    if (it == m->stages.end() || !it->second.live() || !r || it->second.ptr != r->stats) { m->fail("stage '%s' not available", name); return -1; }
+    const int I = c.inter_channels, B = r->B, T = r->T;
+    numel = (int64_t)B * I * T;
     if (!dst) return numel;
     if (capacity < numel) { m->fail("capacity too small"); return -1; }
-    const float* base = it->second.ptr + (n == "logs_text" ? (size_t)I * m->T : 0);
-    if (hipMemcpy2DAsync(dst, (size_t)I * m->T * 4, base, (size_t)2 * I * m->T * 4, (size_t)I * m->T * 4,
-                         m->B, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    const float* base = it->second.ptr + (n == "logs_text" ? (size_t)I * T : 0);
+    if (hipMemcpy2DAsync(dst, (size_t)I * T * 4, base, (size_t)2 * I * T * 4, (size_t)I * T * 4,
+                         B, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
       m->fail("hipMemcpy2DAsync failed"); return -1;
     }
     return numel;
   }
   auto it = m->stages.find(n);
-  if (it == m->stages.end()) { m->fail("stage '%s' not available", name); return -1; }
+  if (it == m->stages.end() || !it->second.live()) { m->fail("stage '%s' not available", name); return -1; }
   src = it->second.ptr; numel = it->second.numel;
   if (!dst) return numel;
   if (capacity < numel) { m->fail("capacity too small"); return -1; }
@@ -5363,8 +5371,8 @@ int mbv_op_max_path(mbv_model* m, const float* value, const int32_t* t_y32, cons
   OP_REFUSE(!max_path_supported(T_s), "T_s must be <= 1024");
   OP_BEGIN();
   const size_t bits_bytes = max_path_scratch_bytes(B, T_t, T_s);
-  if (bits_bytes && ensure(m, &m->scrB, &m->scrB_bytes, bits_bytes)) return 1;
-  launch_max_path(value, t_y32, t_x32, w_out, path_out, status, bits_bytes ? m->scrB : nullptr, B, T_t, T_s, s);
+  if (bits_bytes && ensure(m, m->scrB, bits_bytes)) return 1;
+  launch_max_path(value, t_y32, t_x32, w_out, path_out, status, bits_bytes ? m->scrB.p : nullptr, B, T_t, T_s, s);
   OP_END();
 }
 #undef OP_REFUSE

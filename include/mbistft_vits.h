@@ -1314,6 +1314,96 @@ int mbv_convert_ranges_ahead(mbv_model *m, const mbv_convert_range *rows_host, c
 int mbv_seam_rows(mbv_model *m, const mbv_seam_row *rows_host, int n, void *stream);
 int64_t mbv_seam_runs(mbv_model *m);
 
+/* ---- live text: an utterance whose tokens are still arriving ------
+ * The text mirror of live voice conversion (no reference counterpart as code: tts_vits.py receives its text unit by
+ * unit, synthesis_module.py:258-353 decodes one shared latent piece by piece).  The tokens of ONE utterance come in
+ * blocks of bt.  Block k, tokens [k bt, (k + 1) bt), is encoded from the text prefix of E_k = min((k + 1) bt + A, N)
+ * tokens as a stand-alone utterance (one row of an mbv_encode_rows run: the text encoder attends over its whole
+ * input, so every block re-encodes its prefix); the block's columns of that run's text-level m_p / logs_p and of its
+ * durations go into the stream's own token tables (mbv_take_tokens_rows), the block is length-regulated into the
+ * stream's own z_p at the running frame offset (mbv_expand_ranges), and the reverse flows run on windows of that z_p
+ * (mbv_flow_ranges): z frame t depends on z_p frames [t - R, t + R] only, (R, R) = mbv_text_context.  The decoder side
+ * is the one of live conversion (mbv_decode_chunks_routed, mbv_seam_rows).  With A = the whole text, a finished stream
+ * of more than 256 frames is BITWISE mbv_encode + mbv_synthesize of the text with the same noise; a shorter one is
+ * within fp32 rounding of it (the other kernel family sums in another order), as for mbv_convert_ranges.
+ *
+ * mbv_text_context (host only): out = (R, R) in frames, the plain sum of the reaches of the reverse pass's k = 5
+ * layers (n_flows x n_layers x 2 = 32 for every supported model).  1 on a NULL argument.
+ * mbv_flow_window (host only): out = [wa, wb), the z_p window for z frames [first, first + count) of P expanded
+ * frames: [first - R, first + count + R) clipped to [0, P), wa rounded down to a multiple of 32 (the rule of
+ * mbv_convert_window).  1 on bad arguments (first < 0, count < 1, P < first + count).
+ * mbv_flow_ranges_plan (host only): the runs for windows of window_frames[i] frames, in order, as
+ * mbv_convert_ranges_plan cuts them.  Returns the number of runs, -1 on a bad argument.
+ *
+ * mbv_take_tokens_rows: after mbv_encode_rows on `slot`.  Row i copies token columns [a, b) of run row `src`: the
+ * run's text-level m_p | logs_p into stats [2 inter, stride] and (int)w_ceil into dur [stride], both at [a, b); a row
+ * whose y_length (the run row's entry of y_lengths_out, still on the device) is -1 writes -1 durations.  dur_copy (or
+ * NULL) receives the same b - a durations packed, so that one read-back serves a tick.  ONE launch, copies only.
+ * Refused before any launch, the handle still usable: an ended run ("without a preceding mbv_encode_rows on slot
+ * k"), src outside the run, [a, b) empty or outside the row's t_text, a NULL pointer, stride < b.
+ *
+ * mbv_expand_ranges: row i regulates tokens [a, b) of the stream's tables into z_p[:, frame : frame + sum dur): an
+ * in-kernel scan of the block's durations, then per element the chain of operations of the length regulator of
+ * mbv_synthesize (BITWISE mbv_op_expand on the same inputs).  dur_host is HOST memory, the b - a durations as read
+ * back.  ONE launch for all rows.  Refused before any launch, naming the row: a NULL pointer, a negative duration,
+ * frame < 0, frame + sum dur > max_frames, max_frames beyond z_stride or (where noise_scale != 0) noise_stride, noise
+ * missing where noise_scale != 0, stride < b, two rows writing overlapping frames of one z_p.  Rows without frames
+ * are skipped.
+ *
+ * mbv_flow_ranges: ONE padded run: a window gather, the reverse flows by the launcher every other entry uses, planned
+ * as for an utterance of more than 256 frames, and a ranged masked scatter of [first, first + count) into z, in
+ * place.  Nothing behind P is read.  sid is ignored on a model without speakers; a defined voice is valid.  Refused
+ * before any launch, naming the row: a NULL pointer, a range that is not computable yet (first + count + R > P while
+ * not complete, or first + count > P), a stride < first + count (z) or < P (z_p), a speaker id outside the tables,
+ * two rows writing overlapping frames of one z, rows of more than one run of mbv_flow_ranges_plan, a run outside the
+ * fused WN layers, "conv_bf16".
+ *
+ * mbv_text_runs counts the mbv_take_tokens_rows and mbv_expand_ranges launches, mbv_flow_runs the flow runs, since
+ * mbv_create; the encoder passes count in mbv_encoder_runs. */
+typedef struct mbv_take_row {
+  int32_t src;                   /* the row of the run */
+  int32_t a, b;                  /* tokens [a, b) */
+  int32_t reserved;
+  const int64_t *y_length;       /* DEVICE, the run row's entry of mbv_encode_rows' y_lengths_out */
+  float *stats;                  /* DEVICE [2 inter, stride], the stream's m_p | logs_p per token */
+  int32_t *dur;                  /* DEVICE [stride], the stream's frames per token */
+  int64_t stride;
+  int32_t *dur_copy;             /* DEVICE [b - a], a packed second copy of the durations, or NULL */
+} mbv_take_row;
+typedef struct mbv_expand_range {
+  const float *stats;            /* DEVICE [2 inter, stride] */
+  const int32_t *dur;            /* DEVICE [stride] */
+  int64_t stride;
+  const int32_t *dur_host;       /* HOST [b - a], the block's durations as read back */
+  int32_t a, b;                  /* tokens [a, b) */
+  int32_t frame;                 /* F_a, the frame at which token a starts */
+  int32_t max_frames;            /* the stream's capacity in frames */
+  const float *noise;            /* DEVICE [inter, noise_stride], the stream's block (not read at noise_scale 0) */
+  int64_t noise_stride;
+  float noise_scale;
+  int32_t reserved;
+  float *z_p;                    /* DEVICE [inter, z_stride], the stream's own z_p; only the block's frames are written */
+  int64_t z_stride;
+} mbv_expand_range;
+typedef struct mbv_flow_range {
+  const float *z_p;              /* DEVICE [inter, z_p_stride] */
+  int64_t z_p_stride;
+  int32_t P;                     /* frames of z_p that are expanded */
+  int32_t complete;              /* != 0: the text is closed and P is its last frame */
+  int64_t sid;
+  int32_t first, count;          /* z frames [first, first + count) */
+  float *z;                      /* DEVICE [inter, z_stride], the stream's own z; only the range is written */
+  int64_t z_stride;
+} mbv_flow_range;
+int mbv_text_context(const mbv_config *cfg, int32_t out[2]);
+int mbv_flow_window(const mbv_config *cfg, int first, int count, int64_t P, int32_t out[2]);
+int mbv_flow_ranges_plan(const mbv_config *cfg, int n, const int32_t *window_frames, int32_t *run_of_range);
+int mbv_take_tokens_rows(mbv_model *m, int slot, const mbv_take_row *rows_host, int n, void *stream);
+int mbv_expand_ranges(mbv_model *m, const mbv_expand_range *rows_host, int n, void *stream);
+int mbv_flow_ranges(mbv_model *m, const mbv_flow_range *rows_host, int n, void *stream);
+int64_t mbv_text_runs(mbv_model *m);
+int64_t mbv_flow_runs(mbv_model *m);
+
 /* ---- introspection (tests, debugging) ---------------------------------------
  * Copies an internal stage tensor of the last call into `dst` (device).
  * Names: "x_enc" [B,H,T], "m_text", "logs_text" [B,I,T], "logw", "w_ceil"

@@ -192,6 +192,28 @@ class MbvSeamRow(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MbvTakeRow(C.Structure):
+    """mbv_take_row of include/mbistft_vits.h (mbv_take_tokens_rows)."""
+    _fields_ = [("src", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("reserved", C.c_int32),
+                ("y_length", C.c_void_p), ("stats", C.c_void_p), ("dur", C.c_void_p), ("stride", C.c_int64),
+                ("dur_copy", C.c_void_p)]
+
+
+class MbvExpandRange(C.Structure):
+    """mbv_expand_range of include/mbistft_vits.h (mbv_expand_ranges); dur_host is HOST memory."""
+    _fields_ = [("stats", C.c_void_p), ("dur", C.c_void_p), ("stride", C.c_int64), ("dur_host", C.c_void_p),
+                ("a", C.c_int32), ("b", C.c_int32), ("frame", C.c_int32), ("max_frames", C.c_int32),
+                ("noise", C.c_void_p), ("noise_stride", C.c_int64), ("noise_scale", C.c_float),
+                ("reserved", C.c_int32), ("z_p", C.c_void_p), ("z_stride", C.c_int64)]
+
+
+class MbvFlowRange(C.Structure):
+    """mbv_flow_range of include/mbistft_vits.h (mbv_flow_ranges)."""
+    _fields_ = [("z_p", C.c_void_p), ("z_p_stride", C.c_int64), ("P", C.c_int32), ("complete", C.c_int32),
+                ("sid", C.c_int64), ("first", C.c_int32), ("count", C.c_int32), ("z", C.c_void_p),
+                ("z_stride", C.c_int64)]
+
+
 class MbvResampleRange(C.Structure):
     """mbv_resample_range of include/mbistft_vits.h (mbv_resample_ranges)."""
     _fields_ = [("wave", C.c_void_p), ("wave_dtype", C.c_int32), ("in_avail", C.c_int64), ("in_total", C.c_int64),
@@ -255,7 +277,8 @@ STRUCTS = {
     "mbv_mark_row": MbvMarkRow, "mbv_fit": MbvFit, "mbv_shape_row": MbvShapeRow, "mbv_gain_row": MbvGainRow,
     "mbv_pcm_envelope": MbvPcmEnvelope, "mbv_warp_row": MbvWarpRow, "mbv_loudness_chunk": MbvLoudnessChunk,
     "mbv_randn_block": MbvRandnBlock, "mbv_convert_row": MbvConvertRow, "mbv_convert_range": MbvConvertRange,
-    "mbv_seam_row": MbvSeamRow, "mbv_conv_desc": MbvConvDesc,
+    "mbv_seam_row": MbvSeamRow, "mbv_conv_desc": MbvConvDesc, "mbv_take_row": MbvTakeRow,
+    "mbv_expand_range": MbvExpandRange, "mbv_flow_range": MbvFlowRange,
 }
 
 
@@ -418,6 +441,14 @@ LATER = {
     "mbv_convert_ranges_ahead": (i32, [vp, P(MbvConvertRange), P(i32), i32, i32, i32, vp]),
     "mbv_seam_rows": (i32, [vp, P(MbvSeamRow), i32, vp]),
     "mbv_seam_runs": (i64, [vp]),
+    "mbv_text_context": (i32, [P(MbvConfig), P(i32 * 2)]),
+    "mbv_flow_window": (i32, [P(MbvConfig), i32, i32, i64, P(i32 * 2)]),
+    "mbv_flow_ranges_plan": (i32, [P(MbvConfig), i32, P(i32), P(i32)]),
+    "mbv_take_tokens_rows": (i32, [vp, i32, P(MbvTakeRow), i32, vp]),
+    "mbv_expand_ranges": (i32, [vp, P(MbvExpandRange), i32, vp]),
+    "mbv_flow_ranges": (i32, [vp, P(MbvFlowRange), i32, vp]),
+    "mbv_text_runs": (i64, [vp]),
+    "mbv_flow_runs": (i64, [vp]),
 }
 TABLE = {**CORE, **LATER}
 SYMBOLS = list(TABLE)

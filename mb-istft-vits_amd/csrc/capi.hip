@@ -157,6 +157,8 @@ struct mbv_model {
   int64_t input_runs = 0;          // launches of the live-input resampler (mbv_input_runs)
   int64_t warp_runs = 0;           // launches of the time-warp kernel (mbv_warp_runs)
   int64_t seam_runs = 0;           // launches of the chunk-seam kernel (mbv_seam_runs)
+  int64_t text_runs = 0;           // mbv_take_tokens_rows + mbv_expand_ranges launches (mbv_text_runs)
+  int64_t flow_runs = 0;           // flow runs of mbv_flow_ranges (mbv_flow_runs)
   float* warp_win[2] = {nullptr, nullptr};   // filter -> fp32 window and its differences on the device (mbv_warp_ranges)
   // blended voices (mbv_speakers_define): the rows, the defined words and the definition table on the device, all
   // allocated by the first definition and outside the weight arena; `voices` is every slot's host copy
@@ -5061,6 +5063,196 @@ int mbv_convert_ranges_ahead(mbv_model* m, const mbv_convert_range* rows_host, c
   // the target speaker vectors stay in scratch; the planner sees a length past the narrow kernel's for every window
   return run_posterior_rows(m, who, crows, srows, T, max_keep, T > kLiveRouteFrames ? T : kLiveRouteFrames, nullptr, hop,
                             win, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ live text (tokens that are still arriving)
+namespace {
+// z frame t depends on z_p frames [t - R, t + R] only: the reverse pass is kNFlows couplings, each a WN of kFlowLayers
+// k = kFlowK, dilation-1 convs between 1x1 convs (the plain sum, as converter_context takes it).
+int text_context() { return kNFlows * kFlowLayers * ((kFlowK - 1) / 2); }
+
+// The z_p window from which z frames [first, first + count) are computed when P frames are expanded (convert_window's
+// rule: the start on a whole 32-frame unit of the fused WN layers, where the whole-utterance run has the frame).
+void flow_window(int first, int count, int64_t P, int* wa, int* wb) {
+  const int R = text_context();
+  const int a = first - R > 0 ? first - R : 0;
+  *wa = a & ~31;
+  const int64_t b = (int64_t)first + count + R;
+  *wb = (int)(b < P ? b : P);
+}
+}  // namespace
+
+int mbv_text_context(const mbv_config* cfg, int32_t out[2]) {
+  if (!cfg || !out) return 1;
+  out[0] = out[1] = text_context();
+  return 0;
+}
+
+int mbv_flow_window(const mbv_config* cfg, int first, int count, int64_t P, int32_t out[2]) {
+  if (!cfg || !out || first < 0 || count < 1 || P < (int64_t)first + count || P > 0x7fffffff) return 1;
+  int wa, wb;
+  flow_window(first, count, P, &wa, &wb);
+  out[0] = wa; out[1] = wb;
+  return 0;
+}
+
+int mbv_flow_ranges_plan(const mbv_config* cfg, int n, const int32_t* window_frames, int32_t* run_of_range) {
+  return mbv_convert_ranges_plan(cfg, n, window_frames, run_of_range);      // the same single class, the same cuts
+}
+
+int64_t mbv_text_runs(mbv_model* m) { return m ? m->text_runs : -1; }
+int64_t mbv_flow_runs(mbv_model* m) { return m ? m->flow_runs : -1; }
+
+int mbv_take_tokens_rows(mbv_model* m, int slot, const mbv_take_row* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_take_tokens_rows";
+  EncRun* r = slot >= 0 && slot < mbv_model::kSlots ? &m->runs[slot] : nullptr;
+  if (!r || !r->live()) return m->fail("%s without a preceding mbv_encode_rows on slot %d", who, slot);
+  if (!r->rows) return m->fail("%s: slot %d holds no mbv_encode_rows run", who, slot);
+  if (!rows_host || n < 1 || n > 65535) return m->fail("%s: bad arguments (1 .. 65535 rows expected)", who);
+  int max_cols = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_take_row& k = rows_host[i];
+    if (k.src < 0 || k.src >= r->B) return m->fail("%s: row %d: src %d outside the run's %d rows", who, i, k.src, r->B);
+    if (k.a < 0 || k.b <= k.a || k.b > r->t_text[k.src])
+      return m->fail("%s: row %d: tokens [%d, %d) outside the %d tokens of run row %d", who, i, k.a, k.b, r->t_text[k.src], k.src);
+    if (!k.y_length || !k.stats || !k.dur) return m->fail("%s: row %d: y_length, stats or dur missing", who, i);
+    if (k.stride < k.b) return m->fail("%s: row %d: stride %lld < b = %d", who, i, (long long)k.stride, k.b);
+    if (k.b - k.a > max_cols) max_cols = k.b - k.a;
+  }
+  DEVICE_GUARD(m);
+  if (ensure(m, m->scrB, (size_t)n * sizeof(TakeRow))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  TakeRow* rows = reinterpret_cast<TakeRow*>(m->scrB.p);
+  upload_rows<kTextChunk>(n, rows, s, [&](size_t i) {
+    const mbv_take_row& k = rows_host[i];
+    return TakeRow{k.y_length, k.stats, k.dur, k.dur_copy, k.stride, k.src, k.a, k.b, 0};
+  });
+  ++m->text_runs;
+  launch_take_tokens_rows(r->stats, r->w_ceil, rows, n, 2 * m->cfg.inter_channels, r->T, max_cols, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_expand_ranges(mbv_model* m, const mbv_expand_range* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_expand_ranges";
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!rows_host || n < 1 || n > 65535) return m->fail("%s: bad arguments (1 .. 65535 rows expected)", who);
+  std::vector<int> live, frames(n);
+  int most = 0;
+  for (int i = 0; i < n; ++i) {
+    const mbv_expand_range& k = rows_host[i];
+    if (!k.stats || !k.dur || !k.dur_host || !k.z_p) return m->fail("%s: row %d: stats, dur, dur_host or z_p missing", who, i);
+    if (k.a < 0 || k.b <= k.a || k.stride < k.b)
+      return m->fail("%s: row %d: tokens [%d, %d) empty or beyond the tables' stride %lld", who, i, k.a, k.b, (long long)k.stride);
+    if (k.frame < 0 || k.max_frames < 1 || k.z_stride < k.max_frames)
+      return m->fail("%s: row %d: frame %d < 0, or max_frames %d outside [1, z_stride = %lld]", who, i, k.frame, k.max_frames,
+                     (long long)k.z_stride);
+    if (!(k.noise_scale >= 0.f)) return m->fail("%s: row %d: noise_scale must be >= 0", who, i);
+    if (k.noise_scale != 0.f && (!k.noise || k.noise_stride < k.max_frames))
+      return m->fail("%s: row %d: noise missing, or noise_stride %lld < max_frames %d", who, i, (long long)k.noise_stride, k.max_frames);
+    int64_t sum = 0;
+    for (int j = 0; j < k.b - k.a; ++j) {
+      if (k.dur_host[j] < 0) return m->fail("%s: row %d: token %d has a negative duration (%d)", who, i, k.a + j, k.dur_host[j]);
+      sum += k.dur_host[j];
+    }
+    if ((int64_t)k.frame + sum > k.max_frames)
+      return m->fail("%s: row %d: frames [%d, %d + %lld) do not fit max_frames = %d", who, i, k.frame, k.frame, (long long)sum, k.max_frames);
+    frames[i] = (int)sum;
+    if (sum) live.push_back(i);
+    if (frames[i] > most) most = frames[i];
+  }
+  const auto clash = ranges_overlap(n, [&](int i) { return (uintptr_t)(rows_host[i].z_p + rows_host[i].frame); },
+                                    [&](int i) { return sizeof(float) * (uintptr_t)frames[i]; });
+  if (clash.first >= 0) return m->fail("%s: rows %d and %d write overlapping frames of one z_p", who, clash.first, clash.second);
+  if (live.empty()) return 0;
+  DEVICE_GUARD(m);
+  if (ensure(m, m->scrB, live.size() * sizeof(ExpandRange))) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  ExpandRange* rows = reinterpret_cast<ExpandRange*>(m->scrB.p);
+  upload_rows<kTextChunk>(live.size(), rows, s, [&](size_t i) {
+    const mbv_expand_range& k = rows_host[live[i]];
+    return ExpandRange{k.stats, k.dur, k.stride, k.noise, k.noise_stride, k.z_p, k.z_stride, k.noise_scale,
+                       k.a, k.b, k.frame, frames[live[i]], 0};
+  });
+  ++m->text_runs;
+  launch_expand_ranges(rows, (int)live.size(), m->cfg.inter_channels, most, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
+}
+
+int mbv_flow_ranges(mbv_model* m, const mbv_flow_range* rows_host, int n, void* stream) {
+  if (!m) return 1;
+  const char* who = "mbv_flow_ranges";
+  if (!m->finalized) return m->fail("weights not finalized");
+  if (!rows_host || n < 1) return m->fail("%s: bad arguments", who);
+  if (m->conv_bf16) return m->fail("%s: live text is not built for the \"conv_bf16\" mode", who);
+  const mbv_config& c = m->cfg;
+  const bool has_g = c.n_speakers > 0 && m->emb_g.present;
+  const int B = n, I = c.inter_channels, gin = c.gin_channels, R = text_context();
+  std::vector<FlowRow> frows(B);
+  std::vector<AdmitSynRow> srows(B);
+  std::vector<int32_t> wlen(B);
+  int T = 0, max_keep = 0;
+  for (int i = 0; i < B; ++i) {
+    const mbv_flow_range& k = rows_host[i];
+    if (!k.z_p || !k.z) return m->fail("%s: row %d: z_p or z missing", who, i);
+    if (k.first < 0 || k.count < 1 || k.P < 1 || (int64_t)k.first + k.count > k.P)
+      return m->fail("%s: row %d: frames [%d, %d + %d) outside the %d expanded frames", who, i, k.first, k.first, k.count, k.P);
+    if (!k.complete && (int64_t)k.first + k.count + R > k.P)
+      return m->fail("%s: row %d: frames [%d, %d + %d) are not computable yet: they need z_p frames up to %lld, and %d are "
+                     "expanded (the text is open)", who, i, k.first, k.first, k.count, (long long)k.first + k.count + R, k.P);
+    if (k.z_p_stride < k.P) return m->fail("%s: row %d: z_p_stride %lld < P = %d", who, i, (long long)k.z_p_stride, k.P);
+    if (k.z_stride < (int64_t)k.first + k.count)
+      return m->fail("%s: row %d: z_stride %lld < first + count = %d", who, i, (long long)k.z_stride, k.first + k.count);
+    if (has_g && !m->speaker_ok(k.sid))
+      return m->fail("%s: row %d: speaker id outside [0, %d) and no defined voice", who, i, c.n_speakers);
+    int wa, wb;
+    flow_window(k.first, k.count, k.P, &wa, &wb);
+    wlen[i] = wb - wa;
+    if (wlen[i] > T) T = wlen[i];
+    if (k.count > max_keep) max_keep = k.count;
+    frows[i] = FlowRow{k.z_p, k.z_p_stride, has_g ? k.sid : 0, wa, wlen[i]};
+    srows[i] = AdmitSynRow{nullptr, 0, 0.f, k.count, k.z + k.first, wlen[i], k.first - wa, k.z_stride};
+  }
+  const auto clash = ranges_overlap(B, [&](int i) { return (uintptr_t)(rows_host[i].z + rows_host[i].first); },
+                                    [&](int i) { return sizeof(float) * (uintptr_t)rows_host[i].count; });
+  if (clash.first >= 0) return m->fail("%s: rows %d and %d write overlapping ranges of one z", who, clash.first, clash.second);
+  if (mbv_flow_ranges_plan(&c, B, wlen.data(), nullptr) != 1)
+    return m->fail("%s: the %d rows (widest window %d frames) belong to more than one run of mbv_flow_ranges_plan", who, B, T);
+  for (int f = 0; f < kNFlows; ++f)
+    if (!wn_takes_fused(m, m->flow[f].in, m->flow[f].in16, B, T) || !wn_fused_fits(B, I, T))
+      return m->fail("%s: a run of %d x %d frames is outside the fused WN layers (option \"wn_fused\" off, a hidden size they "
+                     "do not cover, or tensors beyond their 32-bit offsets)", who, B, T);
+  DEVICE_GUARD(m);
+  hipStream_t s = (hipStream_t)stream;
+  float *z, *g;
+  FlowBufs fb{};
+  int* lens;
+  int64_t* sid;
+  FlowRow* rows;
+  AdmitSynRow* scat;
+  if (lay_out(m, who, m->scrB, [&](Bump& b) {
+        z = b.take<float>((size_t)B * T * I);
+        fb = carve_flow(b, c, B, T, kFlowLayers);
+        g = b.take<float>((size_t)B * (gin ? gin : 1));
+        lens = b.take<int>(B);
+        sid = b.take<int64_t>(B);
+        rows = b.take<FlowRow>(B);
+        scat = b.take<AdmitSynRow>(B);
+      })) return 1;
+  upload_rows<kAdmitChunk>(B, rows, s, [&](size_t i) { return frows[i]; }, FlowRowCols{lens, sid});
+  upload_rows<kAdmitChunk>(B, scat, s, [&](size_t i) { return srows[i]; });
+  ++m->flow_runs;
+  if (has_g) launch_gather_rows(m->W(m->emb_g.off), sid, g, B, gin, c.n_speakers, nullptr, s, m->voice_table());
+  launch_gather_windows(rows, z, B, I, T, s);
+  // the planner sees a length past the narrow kernel's for every window (kLiveRouteFrames): what a window computes does
+  // not depend on how the utterance was cut, and equals the whole-utterance run of more than 256 frames
+  if (int rc = run_flows(m, true, z, has_g ? g : nullptr, fb, lens, B, T, s, T > kLiveRouteFrames ? T : kLiveRouteFrames)) return rc;
+  launch_scatter_z_rows(z, lens, scat, B, I, T, max_keep, s);
+  HIPCHK(m, hipGetLastError());
+  return 0;
 }
 
 

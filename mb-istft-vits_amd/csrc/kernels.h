@@ -339,6 +339,51 @@ void launch_expand_rows(const float* m_t, const float* logs_t, int64_t src_bstri
 void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* rows, int B, int C, int Tp, int max_keep,
                            hipStream_t s);
 
+// ---------------------------------------------------------------- live text (capi.hip mbv_take_tokens_rows / mbv_expand_ranges /
+// mbv_flow_ranges): an utterance whose tokens are still arriving.  Tables in the arena (upload_rows).
+// Token columns [a, b) of row `src` of an encode run into a stream's own token tables: stats[c, j] = the run's
+// m_text / logs_text (c < 2 C), dur[j] = (int)w_ceil[src, j], or -1 where *y_length < 0 (the run flagged the row);
+// dur_copy (or null) receives dur[a .. b) packed, for the tick's one read-back.  Copies only.  One launch.
+struct TakeRow {
+  const int64_t* y_length;
+  float* stats;                // [2 C, stride]
+  int* dur;                    // [stride]
+  int* dur_copy;               // [b - a] or null
+  int64_t stride;
+  int src, a, b, pad_;
+};
+constexpr int kTextChunk = 48;     // rows per upload_rows launch: 48 x 80 bytes (an ExpandRange) = 3.75 KiB of kernel arguments
+void launch_take_tokens_rows(const float* stats, const float* w_ceil, const TakeRow* rows, int n, int C2, int T,
+                             int max_cols, hipStream_t s);
+// Length regulation of a block of tokens at a running frame offset: with cum the inclusive scan of dur[a .. b) (done in
+// the kernel, 256 tokens a round), frame `frame + t`, t < frames, takes token j = the first with cum[j] > t and
+//   z_p[c, frame + t] = m[c, j] + noise[c, frame + t] * expf(logs[c, j]) * noise_scale      (m alone at scale 0)
+// — expand_kernel's expression on expand_kernel's operands, so the element is bitwise that kernel's.  One launch.
+struct ExpandRange {
+  const float* stats;          // [2 C, stride]: m | logs
+  const int* dur;              // [stride]
+  int64_t stride;
+  const float* noise;          // [C, noise_stride], or null
+  int64_t noise_stride;
+  float* z_p;                  // [C, z_stride]
+  int64_t z_stride;
+  float noise_scale;
+  int a, b, frame, frames, pad_;   // frames: the sum of dur[a .. b) as the host read it; nothing behind it is written
+};
+void launch_expand_ranges(const ExpandRange* rows, int n, int C, int max_frames, hipStream_t s);
+// z[b, c, t] = rows[b].z_p[c, wa + t] for t < frames, 0 behind: the window of a stream's z_p as one row of a padded
+// flow run.  upload_rows' Extra fills the columns the flows read.
+struct FlowRow {
+  const float* z_p;
+  int64_t stride, sid;
+  int wa, frames;
+};
+struct FlowRowCols {
+  int* lens; int64_t* sid;
+  __device__ void operator()(int i, const FlowRow& k) const { lens[i] = k.frames; sid[i] = k.sid; }
+};
+void launch_gather_windows(const FlowRow* rows, float* z, int B, int C, int T, hipStream_t s);
+
 // ---------------------------------------------------------------- speaker conditioning
 // out[b][co] = bias[co] + sum_ci W[co][ci] * g[b][ci]   (g = table[sid[b]] if sid)
 void launch_cond_gemv(const float* g, const float* table, const int64_t* sid, const float* W,

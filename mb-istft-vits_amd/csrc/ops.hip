@@ -583,6 +583,102 @@ void launch_scatter_z_rows(const float* z, const int* ylen, const AdmitSynRow* r
 }
 
 // ---------------------------------------------------------------------------
+// Live text (kernels.h).  Block (x, c, row): 256 token columns of channel row c of the run's stats
+// [B, C2, T] (c < C2), or of its w_ceil (c == C2), into the stream's tables.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void take_tokens_rows_kernel(const float* __restrict__ stats,
+                                                               const float* __restrict__ w_ceil,
+                                                               const TakeRow* __restrict__ rows, int C2, int T) {
+  const TakeRow r = rows[blockIdx.z];
+  const int j = r.a + blockIdx.x * 256 + threadIdx.x;
+  if (j >= r.b) return;
+  const int c = blockIdx.y;
+  if (c < C2) {
+    r.stats[(int64_t)c * r.stride + j] = stats[((int64_t)r.src * C2 + c) * T + j];
+    return;
+  }
+  const int d = *r.y_length < 0 ? -1 : (int)w_ceil[(int64_t)r.src * T + j];
+  r.dur[j] = d;
+  if (r.dur_copy) r.dur_copy[j - r.a] = d;
+}
+
+void launch_take_tokens_rows(const float* stats, const float* w_ceil, const TakeRow* rows, int n, int C2, int T,
+                             int max_cols, hipStream_t s) {
+  hipLaunchKernelGGL(take_tokens_rows_kernel, dim3((unsigned)((max_cols + 255) / 256), C2 + 1, n), dim3(256), 0, s,
+                     stats, w_ceil, rows, C2, T);
+}
+
+// Block (x, row, z): frames [256 x, 256 x + 256) of the row's block, 16 channels.  Every round scans 256 durations
+// (the scan of shape_durations_kernel) and the thread whose frame falls into the round takes its token from it: the
+// first j with cum[j] > t, what expand_kernel's search over the whole scan gives.  All threads of a block stay in the
+// loop (its barriers); the host has made sure that frame + frames lies inside z_p and the noise.
+__global__ __launch_bounds__(256) void expand_ranges_kernel(const ExpandRange* __restrict__ rows, int C) {
+  __shared__ int scan[256];
+  __shared__ int carry_s;
+  const ExpandRange r = rows[blockIdx.y];
+  const int tid = threadIdx.x;
+  if ((int)(blockIdx.x * 256) >= r.frames) return;          // (the whole block: no barrier is left waiting)
+  const int t = blockIdx.x * 256 + tid;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  int j = -1;
+  for (int base = r.a; base < r.b; base += 256) {
+    const int tok = base + tid;
+    int d = tok < r.b ? r.dur[tok] : 0;
+    scan[tid] = d > 0 ? d : 0;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {                // Hillis-Steele inclusive scan
+      const int v = tid >= off ? scan[tid - off] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    const int carry = carry_s;
+    if (j < 0 && t >= carry && t < carry + scan[255]) {
+      int lo = 0, hi = 255;                                  // first k with carry + scan[k] > t
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (carry + scan[mid] > t) hi = mid; else lo = mid + 1;
+      }
+      j = base + lo;
+    }
+    __syncthreads();
+    if (tid == 255) carry_s = carry + scan[255];
+    __syncthreads();
+  }
+  if (j < 0 || t >= r.frames) return;
+  const float noise_scale = r.noise_scale;
+  const float* noise = noise_scale != 0.f ? r.noise : nullptr;
+  const int64_t f = (int64_t)r.frame + t;
+  const int c_lo = blockIdx.z * 16, c_hi = c_lo + 16 < C ? c_lo + 16 : C;
+  for (int c = c_lo; c < c_hi; ++c) {
+    const float m = r.stats[(int64_t)c * r.stride + j];
+    const float lg = r.stats[(int64_t)(C + c) * r.stride + j];
+    float zp = m;
+    if (noise) zp = m + noise[(int64_t)c * r.noise_stride + f] * expf(lg) * noise_scale;
+    r.z_p[(int64_t)c * r.z_stride + f] = zp;
+  }
+}
+
+void launch_expand_ranges(const ExpandRange* rows, int n, int C, int max_frames, hipStream_t s) {
+  hipLaunchKernelGGL(expand_ranges_kernel, dim3((unsigned)((max_frames + 255) / 256), n, (C + 15) / 16), dim3(256), 0, s,
+                     rows, C);
+}
+
+__global__ __launch_bounds__(256) void gather_windows_kernel(const FlowRow* __restrict__ rows, float* __restrict__ z,
+                                                             int C, int T) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  const FlowRow r = rows[b];
+  z[((int64_t)b * C + c) * T + t] = t < r.frames ? r.z_p[(int64_t)c * r.stride + r.wa + t] : 0.f;
+}
+
+void launch_gather_windows(const FlowRow* rows, float* z, int B, int C, int T, hipStream_t s) {
+  hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)((T + 255) / 256), C, B), dim3(256), 0, s, rows, z, C, T);
+}
+
+// ---------------------------------------------------------------------------
 // Speaker conditioning: 1x1 convs on g [B, gin, 1] are GEMVs
 // (models.py:127 dp.cond, modules.py:152 WN cond_layer, modules.py:215 ResBlock cond).
 // ---------------------------------------------------------------------------

@@ -1972,6 +1972,43 @@ class SynthesizerTrn(nn.Module):
                                  max_chunk_frames=max_chunk_frames, convert_frames=convert_frames, in_sr=in_sr, seed=seed,
                                  ahead=ahead)
 
+    def text_context(self):
+        """(R, R) of `mbv_text_context` (host only): z frame t depends on z_p frames [t - R, t + R] only."""
+        return stream.text_context(self._config_struct())
+
+    def text_runs(self):
+        """`mbv_take_tokens_rows` + `mbv_expand_ranges` launches made on this model's handle so far (`mbv_text_runs`)."""
+        return int(_capi.lib().mbv_text_runs(self._ensure_handle()))
+
+    def flow_runs(self):
+        """Flow runs of `mbv_flow_ranges` made on this model's handle so far (`mbv_flow_runs`)."""
+        return int(_capi.lib().mbv_flow_runs(self._ensure_handle()))
+
+    def infer_live(self, sid=None, max_tokens=None, max_frames=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
+                   seed=None, noise=None, noise_w=None, block_tokens=16, ahead=None, chunk_frames=32,
+                   max_chunk_frames=256, flow_frames=32, model_sr=None):
+        """Synthesis of ONE utterance whose tokens are still arriving: a `stream.TextStream` that takes token ids in
+        `push` calls of any size and hands out decoded chunks from `poll` as soon as the model's reach allows (DESIGN
+        7.27), the text mirror of `convert_live`.  Token block k (`block_tokens` tokens) is encoded from the text
+        prefix that ends `ahead.tokens` tokens behind it (`stream.TextAhead`; None = the whole text, every block then
+        waits for `close()`), its columns of that prefix call's text-level statistics and durations are length-regulated
+        into the stream's own z_p, the reverse flows run on windows of it, and the chunks are decoded as a live stream's.
+        The result is a pure function of (ids, sid, scales, seed / noise, block_tokens, ahead, chunk schedule): it does
+        not depend on the pushes, the polls or the pool.  With `TextAhead(tokens=None)` and more than 256 frames the
+        finished stream is bitwise `infer_stream(ids, ..., seed=seed)`; with bounded `tokens` it is an approximation
+        with an exact definition, and nothing is claimed about its quality.
+
+        Buffers are sized once for `max_tokens` and `max_frames` (both required).  The prior noise is one
+        `torch.randn(1, inter, max_frames)` on the device generator, unless `noise` (that shape) or `seed` is given; with
+        the stochastic duration predictor `noise_w` [2, max_tokens] likewise (drawn on the CPU generator as the
+        reference's).  `seed=` excludes `noise=` / `noise_w=`.  `model_sr` is only needed for `TextAhead(seam_ms=)`.
+        Refused here: "conv_bf16", a missing or unknown sid, a `TextAhead` beyond the decoder's reach.  Not part of a
+        text stream: per-token prosody, gain and pitch, `durations=`, `max_len`, the wire layer."""
+        return stream.TextStream(self, sid=sid, max_tokens=max_tokens, max_frames=max_frames, noise_scale=noise_scale,
+                                 length_scale=length_scale, noise_scale_w=noise_scale_w, seed=seed, noise=noise,
+                                 noise_w=noise_w, block_tokens=block_tokens, ahead=ahead, chunk_frames=chunk_frames,
+                                 max_chunk_frames=max_chunk_frames, flow_frames=flow_frames, model_sr=model_sr)
+
     def convert_streams(self, requests):
         """Pooled voice conversion: one single-utterance `DecodeStream` per `ConvertRequest`, in order — what
         `StreamPool.add` takes — from ONE padded posterior run per class of `convert_plan`, with no host read-back:

@@ -22,6 +22,11 @@ decodes every chunk whose z-window is final; a `StreamPool` serves live streams 
 A live call cannot wait for the full reach of the layers: `Ahead(conv, dec)` bounds how far a block of z_hat frames and
 a decoder chunk look to their right, on a fixed grid, so that the result is still a pure function of the recording
 (opt-in, an approximation with an exact definition: DESIGN §7.25).
+
+Text that is still arriving: a `TextStream` (`net.infer_live`) is ONE utterance whose tokens are pushed as a language
+model produces them.  Blocks of tokens are encoded from text prefixes (`TextPlan`, `TextAhead`), length-regulated into
+the stream's own z_p at a running frame offset, the reverse flows run on windows of it, and the decode side is the
+live stream's; the audio is a pure function of the token sequence, whatever the pushes.
 """
 import ctypes as C
 import math
@@ -180,6 +185,25 @@ def _decode_chunks(net, work):
         st._chunk_decoded(first, count)
 
 
+def _decode_and_hand_out(st):
+    """The back half of `LiveStream.poll` and `TextStream.poll`: decode every chunk of `st` that has become decodable,
+    hand out every chunk not handed out yet as [(first_sample, view), ...], and set `y_lengths` once all are released."""
+    todo = st._plan.decodable()
+    if todo:
+        st._check_handle()
+        # under a seam a chunk's overhang lies where the next chunk is decoded, and is stashed in between: a call each
+        for part in ([[c] for c in todo] if st.seam else [todo]):
+            _decode_chunks(st._net, [(st, first, count) for first, count in part])
+    out = []
+    while st._next < st._decoded:
+        first, count = st._chunks[st._next]
+        out.append((st.spf * first, st.o[:, :, st.spf * first:st.spf * (first + count)]))
+        st._next += 1
+    if st._plan.all_released and st.y_lengths is None:
+        st.y_lengths = torch.full((1,), st._plan.total, dtype=torch.int64, device=st.z.device)
+    return out
+
+
 def _convert_ranges(net, todo, hop_size, win_size):
     """One `mbv_convert_ranges` run for `todo` = [(live stream, (a, b)), ...], a z_hat range due on each; with a member
     of a bounded look-ahead among them (whose grid blocks may be several rows) it is `mbv_convert_ranges_ahead`, the
@@ -245,6 +269,81 @@ class Ahead:
         return int(round(self.seam_ms * int(model_sr) / 1000.0)) if self.seam_ms else 0
 
 
+def _seam_frames(seam_samples, dec, chunk_frames, seam_ms, model_sr, samples_per_frame):
+    """The overhang, in frames, of a seam of `seam_samples` (ceil(S / spf)); ValueError unless 1 <= S <= the samples of
+    the `dec` frames a chunk looks ahead and of the smallest chunk."""
+    S, spf = int(seam_samples), int(samples_per_frame)
+    if not 1 <= S <= spf * min(dec, chunk_frames):
+        raise ValueError("a seam of %g ms is %d samples at %d Hz: it must be 1 .. %d, the samples of the dec = %d "
+                         "frames a chunk looks ahead and of the smallest chunk (%d frames)"
+                         % (seam_ms, S, int(model_sr), spf * min(dec, chunk_frames), dec, chunk_frames))
+    return -(-S // spf)
+
+
+class ChunkPlan:
+    """Which chunks of a z that is still growing may be decoded, and from what: the rules `LivePlan` (z_hat converted
+    from a recording) and `TextPlan` (z flowed from a text) share.  z frames [0, `z_done`) exist (`advanced`); T is the
+    utterance's length once it is known, None before.
+
+      dec None   chunk (first, count) is decodable iff z frames up to first + count + r_dec exist, or T is known and all
+                 of [0, T) do; it is decoded from what exists (`t_frames` = z_done)
+      dec = d    it is decoded with t_frames = D = min(first + count + d, T), decodable iff z frames up to D exist, and
+                 `overhang` = min(over_frames, D - first - count) frames past its end for a seam
+    Chunks are those of `chunk_schedule(T, chunk_frames, max_chunk_frames)`: only the cut of the last one depends on T."""
+
+    def __init__(self, r_dec, chunk_frames, max_chunk_frames, dec=None, over_frames=0):
+        c, cap = int(chunk_frames), int(max_chunk_frames)
+        if c < 1 or cap < c:
+            raise ValueError("need 1 <= chunk_frames <= max_chunk_frames (got %d, %d)" % (c, cap))
+        self.r_dec, self.dec, self.over_frames = int(r_dec), dec, int(over_frames)
+        self.z_done = 0
+        self.first, self.c, self.cap, self.c0 = 0, c, cap, c     # the next chunk to release
+
+    def advanced(self, a, b):
+        if a != self.z_done or b <= a:
+            raise ValueError("ranges are converted in order, once")
+        self.z_done = b
+
+    def decodable(self, T):
+        first, c, out = self.first, self.c, []
+        while True:
+            if self.dec is not None:           # z up to the chunk's D (of the uncut chunk while T is not known)
+                if T is not None and first >= T:
+                    break
+                n = min(c, T - first) if T is not None else c
+                if self.z_done < self.t_frames(first, n, T):
+                    break
+            elif T is not None:
+                if self.z_done < T or first >= T:
+                    break
+                n = min(c, T - first)
+            else:
+                if self.z_done < first + c + self.r_dec:
+                    break
+                n = c
+            out.append((first, n))
+            first, c = first + n, min(2 * c, self.cap)
+        return out
+
+    def t_frames(self, first, count, T):
+        if self.dec is None:
+            return self.z_done
+        D = first + count + self.dec
+        return min(D, T) if T is not None else D
+
+    def overhang(self, first, count, T):
+        return min(self.over_frames, self.t_frames(first, count, T) - first - count) if self.over_frames else 0
+
+    def released(self, first, count):
+        if first != self.first:
+            raise ValueError("chunks are released in order")
+        self.first += count
+        self.c = min(2 * self.c, self.cap)
+
+    def all_released(self, T):
+        return T is not None and self.first >= T
+
+
 class LivePlan:
     """What a recording that is still arriving may convert and decode, in pure integers (no tensor, no GPU).
 
@@ -275,7 +374,7 @@ class LivePlan:
         if cf < 1:
             raise ValueError("convert_frames must be >= 1")
         self.convert_frames = cf
-        self.ahead, self.seam, self._over_frames = ahead, 0, 0
+        self.ahead, self.seam, over = ahead, 0, 0
         if ahead is not None:
             if not isinstance(ahead, Ahead):
                 raise TypeError("ahead must be a stream.Ahead or None, got %r" % (ahead,))
@@ -284,16 +383,15 @@ class LivePlan:
             if ahead.seam_ms:
                 if model_sr is None or samples_per_frame is None:
                     raise ValueError("a seam needs model_sr and samples_per_frame")
-                S, spf = ahead.seam_samples(model_sr), int(samples_per_frame)
-                if not 1 <= S <= spf * min(ahead.dec, c):
-                    raise ValueError("a seam of %g ms is %d samples at %d Hz: it must be 1 .. %d, the samples of the dec = %d "
-                                     "frames a chunk looks ahead and of the smallest chunk (%d frames)"
-                                     % (ahead.seam_ms, S, int(model_sr), spf * min(ahead.dec, c), ahead.dec, c))
-                self.seam, self._over_frames = S, -(-S // spf)
+                self.seam = ahead.seam_samples(model_sr)
+                over = _seam_frames(self.seam, ahead.dec, c, ahead.seam_ms, model_sr, samples_per_frame)
         self.arrived, self.closed = 0, False
-        self.z_done = 0                        # z_hat frames [0, z_done) are converted
-        self._first, self._c, self._cap = 0, c, cap          # the next chunk to release
-        self._c0 = c
+        self._chunks = ChunkPlan(r_dec, c, cap, None if ahead is None else ahead.dec, over)
+
+    @property
+    def z_done(self):
+        """z_hat frames [0, z_done) are converted."""
+        return self._chunks.z_done
 
     def push(self, n):
         if self.closed:
@@ -352,44 +450,20 @@ class LivePlan:
         return None
 
     def converted(self, a, b):
-        if a != self.z_done or b <= a:
-            raise ValueError("ranges are converted in order, once")
-        self.z_done = b
+        self._chunks.advanced(a, b)
 
     def decodable(self):
-        """[(first, count), ...]: the chunks not released yet that are decodable now, in order."""
-        first, c, out = self._first, self._c, []
-        T = self.spec_final if self.closed else None
-        while True:
-            if self.ahead is not None:         # z_hat up to the chunk's D (of the uncut chunk while T is not known)
-                if self.closed and first >= T:
-                    break
-                n = min(c, T - first) if self.closed else c
-                if self.z_done < self.t_frames(first, n):
-                    break
-            elif self.closed:
-                if self.z_done < T or first >= T:
-                    break
-                n = min(c, T - first)
-            else:
-                if self.z_done < first + c + self.r_dec:
-                    break
-                n = c
-            out.append((first, n))
-            first, c = first + n, min(2 * c, self._cap)
-        return out
+        """[(first, count), ...]: the chunks not released yet that are decodable now, in order (`ChunkPlan`)."""
+        return self._chunks.decodable(self.total)
 
     def t_frames(self, first, count):
         """D of chunk (first, count): the z_hat frames [0, D) it is decoded from, min(first + count + dec, T) (T once
         closed; a chunk decodable before lies wholly inside the recording).  Without `ahead`: what is converted."""
-        if self.ahead is None:
-            return self.z_done
-        D = first + count + self.ahead.dec
-        return min(D, self.spec_final) if self.closed else D
+        return self._chunks.t_frames(first, count, self.total)
 
     def overhang(self, first, count):
         """Frames chunk (first, count) is decoded past its end for the seam (0 without one)."""
-        return min(self._over_frames, self.t_frames(first, count) - first - count) if self.seam else 0
+        return self._chunks.overhang(first, count, self.total)
 
     def lag(self):
         """(arrived, frames): the sample count at which the first chunk is released when `poll()` follows every push
@@ -398,7 +472,7 @@ class LivePlan:
         the same arithmetic at (R_conv, R_dec), which the unbounded stream meets under such pushes."""
         cf, conv, dec = self.convert_frames, self.conv_ahead, self.dec_ahead
         need = lambda first, c: -(-(first + c + dec) // cf) * cf + conv     # final frames chunk (first, c) waits for
-        first, c, cap = 0, self._c0, self._cap
+        first, c, cap = 0, self._chunks.c0, self._chunks.cap
         arrived = (need(0, c) - 1) * self.hop + self.n_fft - (self.n_fft - self.hop) // 2
         steady, seen = 0, 0
         while seen < cf:
@@ -413,14 +487,11 @@ class LivePlan:
         return d[0] if d else None
 
     def released(self, first, count):
-        if first != self._first:
-            raise ValueError("chunks are released in order")
-        self._first += count
-        self._c = min(2 * self._c, self._cap)
+        self._chunks.released(first, count)
 
     @property
     def all_released(self):
-        return self.closed and self._first >= self.spec_final
+        return self._chunks.all_released(self.total)
 
 
 class LiveStream:
@@ -673,23 +744,548 @@ class LiveStream:
         `mbv_decode_chunks_routed` call; under a seam one call and one `mbv_seam_rows` launch per chunk) and hand out
         every chunk not handed out yet: [(first_sample, view), ...]."""
         self._convert()
-        todo = self._plan.decodable()
-        if todo:
-            self._check_handle()
-            # under a seam a chunk's overhang lies where the next chunk is decoded, and is stashed in between: a call each
-            for part in ([[c] for c in todo] if self.seam else [todo]):
-                _decode_chunks(self._net, [(self, first, count) for first, count in part])
-        out = []
-        while self._next < self._decoded:
-            first, count = self._chunks[self._next]
-            out.append((self.spf * first, self.o[:, :, self.spf * first:self.spf * (first + count)]))
-            self._next += 1
-        if self._plan.all_released and self.y_lengths is None:
-            self.y_lengths = torch.full((1,), self._plan.total, dtype=torch.int64, device=self.z.device)
-        return out
+        return _decode_and_hand_out(self)
 
     def result(self):
         """o[:, :, :256 T] of the finished stream."""
+        if not self.finished:
+            raise RuntimeError("result(): the stream is not finished (close() it and poll() until `finished`)")
+        return self.o[:, :, :self.spf * self._plan.total]
+
+
+def text_context(config_struct):
+    """(R, R) of `mbv_text_context` for an `_capi.MbvConfig` (host only): z frame t depends on z_p frames
+    [t - R, t + R] only."""
+    out = (C.c_int32 * 2)()
+    if _capi.lib().mbv_text_context(C.byref(config_struct), C.byref(out)):
+        raise _capi.MbvError("mbv_text_context failed")
+    return int(out[0]), int(out[1])
+
+
+class TextAhead:
+    """How far a live text looks ahead.  `tokens` = A: token block k is encoded from the text prefix of
+    min((k + 1) block_tokens + A, N) tokens; None = the whole text (every block waits for `close()`).  `dec`: None =
+    the decoder's full reach (the rules of `LivePlan` without `ahead`), an integer 0 <= dec <= R_dec the canonical
+    t_frames of `Ahead(., dec, seam_ms)`; `seam_ms` (needs `dec`) as `Ahead` takes it.  With bounded `tokens` the
+    stream is an approximation with an exact definition: how far a trained text encoder looks ahead is a property of
+    its weights."""
+
+    __slots__ = ("tokens", "dec", "seam_ms")
+
+    def __init__(self, tokens=None, dec=None, seam_ms=0.0):
+        for name, v in (("tokens", tokens), ("dec", dec)):
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("TextAhead: %s must be an integer or None, got %r" % (name, v))
+            if v < 0:
+                raise ValueError("TextAhead: %s must be >= 0, got %d" % (name, v))
+        if isinstance(seam_ms, bool) or not isinstance(seam_ms, (int, float, np.integer, np.floating)):
+            raise TypeError("TextAhead: seam_ms must be a number of milliseconds, got %r" % (seam_ms,))
+        if not math.isfinite(seam_ms) or seam_ms < 0:
+            raise ValueError("TextAhead: seam_ms must be finite and >= 0, got %r" % (seam_ms,))
+        if seam_ms and dec is None:
+            raise ValueError("TextAhead: a seam needs a bounded dec (with the full reach the chunks meet as they are)")
+        self.tokens = None if tokens is None else int(tokens)
+        self.dec = None if dec is None else int(dec)
+        self.seam_ms = float(seam_ms)
+
+    def __repr__(self):
+        return "TextAhead(tokens=%r, dec=%r%s)" % (self.tokens, self.dec,
+                                                   ", seam_ms=%g" % self.seam_ms if self.seam_ms else "")
+
+
+class TextPlan:
+    """What a text that is still arriving may encode, flow and decode, in pure integers (no tensor, no GPU); bt =
+    `block_tokens`, A = `ahead.tokens`, R = `r_flow`, N the tokens once closed.
+
+      token block k         tokens [k bt, min((k + 1) bt, N)), encoded from the prefix of E_k = min((k + 1) bt + A, N)
+                            tokens (A None: E_k = N); due iff E_k tokens have arrived, or closed.  `due_blocks()` ->
+                            [(k, E_k), ...] in order; `encoded(k, frames)` takes the block's durations as read back
+      frames                F_t = the sum of the durations in front of token t (`marks`), P those of the encoded blocks
+      z frames [0, b)       may be flowed with b = P once closed and every block is encoded (`complete`), else
+                            b = max(0, P - R); `flow_due()` -> (a, b) when >= `flow_frames` new frames may be, or at
+                            the end; `flowed(a, b)`
+      chunk (first, count)  `LivePlan`'s rules on the flowed frames: without `ahead.dec` decodable iff z frames up to
+                            first + count + R_dec are flowed (or complete), decoded from what is flowed; with it,
+                            decoded with t_frames = min(first + count + dec, T), overhang and seam as `Ahead` has them
+    so that what is encoded, flowed and decoded, and from what, does not depend on the pushes."""
+
+    def __init__(self, block_tokens, r_flow, r_dec, chunk_frames=32, max_chunk_frames=256, flow_frames=32, ahead=None,
+                 model_sr=None, samples_per_frame=None):
+        bt, ff = int(block_tokens), int(flow_frames)
+        if bt < 1:
+            raise ValueError("block_tokens must be >= 1")
+        if ff < 1:
+            raise ValueError("flow_frames must be >= 1")
+        if int(r_flow) < 0 or int(r_dec) < 0:
+            raise ValueError("r_flow and r_dec must be >= 0")
+        if ahead is None:
+            ahead = TextAhead()
+        if not isinstance(ahead, TextAhead):
+            raise TypeError("ahead must be a stream.TextAhead or None, got %r" % (ahead,))
+        if ahead.dec is not None and ahead.dec > int(r_dec):
+            raise ValueError("%r looks further than the decoder can: dec <= %d" % (ahead, int(r_dec)))
+        self.block_tokens, self.r_flow, self.flow_frames, self.ahead = bt, int(r_flow), ff, ahead
+        self._chunks = ChunkPlan(r_dec, chunk_frames, max_chunk_frames, ahead.dec)
+        self.seam = 0
+        if ahead.seam_ms:
+            if model_sr is None or samples_per_frame is None:
+                raise ValueError("a seam needs model_sr and samples_per_frame")
+            self.seam = int(round(ahead.seam_ms * int(model_sr) / 1000.0))
+            self._chunks.over_frames = _seam_frames(self.seam, ahead.dec, self._chunks.c0, ahead.seam_ms, model_sr,
+                                                    samples_per_frame)
+        self.arrived, self.closed = 0, False
+        self.blocks = 0                        # token blocks [0, blocks) are encoded
+        self.durations = []                    # frames of every encoded token
+        self.marks = [0]                       # F_t of every encoded token, then P
+
+    def push(self, n):
+        if self.closed:
+            raise ValueError("push after close()")
+        if int(n) < 0:
+            raise ValueError("push: a negative count")
+        self.arrived += int(n)
+
+    def close(self):
+        if not self.closed and self.arrived < 1:
+            raise ValueError("close(): the text is empty")
+        self.closed = True
+
+    @property
+    def frames(self):
+        """P: the frames of the encoded blocks."""
+        return self.marks[-1]
+
+    @property
+    def complete(self):
+        """Closed, and every block is encoded: P is the utterance's T."""
+        return self.closed and self.blocks * self.block_tokens >= self.arrived
+
+    @property
+    def total(self):
+        """T, once complete (None before)."""
+        return self.frames if self.complete else None
+
+    @property
+    def z_done(self):
+        """z frames [0, z_done) are flowed."""
+        return self._chunks.z_done
+
+    def due_blocks(self):
+        """[(k, E_k), ...]: every token block to encode now, in order."""
+        bt, A, out, k = self.block_tokens, self.ahead.tokens, [], self.blocks
+        while True:
+            if self.closed:
+                if k * bt >= self.arrived:
+                    break
+                E = self.arrived if A is None else min((k + 1) * bt + A, self.arrived)
+            else:
+                if A is None or (k + 1) * bt + A > self.arrived:
+                    break
+                E = (k + 1) * bt + A
+            out.append((k, E))
+            k += 1
+        return out
+
+    def block_tokens_of(self, k, E):
+        """The token range [a, b) of block k encoded from a prefix of E tokens."""
+        return k * self.block_tokens, min((k + 1) * self.block_tokens, E)
+
+    def encoded(self, k, frames):
+        frames = [int(v) for v in frames]
+        if k != self.blocks:
+            raise ValueError("blocks are encoded in order, once")
+        if not frames or len(frames) > self.block_tokens or min(frames) < 0:
+            raise ValueError("block %d: 1 .. %d durations >= 0 expected" % (k, self.block_tokens))
+        if len(self.durations) + len(frames) > self.arrived:
+            raise ValueError("block %d: more durations than tokens have arrived" % k)
+        for v in frames:
+            self.durations.append(v)
+            self.marks.append(self.marks[-1] + v)
+        self.blocks += 1
+
+    def flow_due(self):
+        """The z range [a, b) to flow now, or None."""
+        P = self.frames
+        b = P if self.complete else max(0, P - self.r_flow)
+        a = self._chunks.z_done
+        if b > a and (self.complete or b - a >= self.flow_frames):
+            return a, b
+        return None
+
+    def flowed(self, a, b):
+        self._chunks.advanced(a, b)
+
+    def decodable(self):
+        """[(first, count), ...]: the chunks not released yet that are decodable now, in order (`ChunkPlan`)."""
+        return self._chunks.decodable(self.total)
+
+    def next_chunk(self):
+        d = self.decodable()
+        return d[0] if d else None
+
+    def t_frames(self, first, count):
+        return self._chunks.t_frames(first, count, self.total)
+
+    def overhang(self, first, count):
+        return self._chunks.overhang(first, count, self.total)
+
+    def released(self, first, count):
+        self._chunks.released(first, count)
+
+    @property
+    def all_released(self):
+        return self._chunks.all_released(self.total)
+
+
+def _text_tick(net, members):
+    """The front half of one tick for the text streams `members`: ONE `mbv_encode_rows` run per class of
+    `mbv_admit_plan` over all due token blocks (one row is one prefix), one `mbv_take_tokens_rows` launch per run, ONE
+    host read-back (the blocks' durations, -1 = the prefix was flagged), one `mbv_expand_ranges` launch, then the flow
+    runs `mbv_flow_ranges_plan` cuts.  Nothing due: nothing is launched.  -> whether a member failed in this tick."""
+    members = [st for st in members if not st.failed]
+    due = [(st, k, E) for st in members for k, E in st._plan.due_blocks()]
+    failed = False
+    L = _capi.lib()
+    if due:
+        for st, _, _ in due:
+            st._check_handle()
+        h, dev, cfg = net._ensure_handle(), net._device(), net.cfg
+        n_runs, run_of = net.admit_plan([E for _, _, E in due], splitk=L.mbv_get_option(h, b"splitk") != 0)
+        if n_runs > 64:
+            raise ValueError("a tick of %d encoder runs: at most 64 (the slots of mbv_encode_rows)" % n_runs)
+        runs = [[i for i in range(len(due)) if run_of[i] == r] for r in range(n_runs)]
+        ranges = [st._plan.block_tokens_of(k, E) for st, k, E in due]
+        with torch.cuda.device(dev), torch.no_grad():
+            hip_stream = net._stream(dev)
+            # ids (zero-padded to the run's longest prefix), lengths and sids of every run: ONE host tensor, one copy
+            parts = []
+            for m in runs:
+                T = max(due[i][2] for i in m)
+                for i in m:
+                    st, _, E = due[i]
+                    parts.append(st._ids[:E] + [0] * (T - E))
+                parts.append([due[i][2] for i in m])
+                if net.n_speakers > 0:
+                    parts.append([due[i][0].sid for i in m])
+            packed = torch.tensor([v for p in parts for v in p], dtype=torch.int64).to(dev)
+            noise_w = [None] * len(due)
+            if cfg.use_sdp:                        # the first E columns of both rows of every stream's own draw
+                flat_w = torch.cat([st.noise_w[:, :E].reshape(-1) for st, _, E in due])
+                o = 0
+                for i, (_, _, E) in enumerate(due):
+                    noise_w[i] = flat_w.data_ptr() + 4 * o
+                    o += 2 * E
+            y_buf = torch.empty(len(due), dtype=torch.int64, device=dev)
+            dur_buf = torch.empty(sum(b - a for a, b in ranges), dtype=torch.int32, device=dev)
+            at, o = [], 0
+            for a, b in ranges:
+                at.append(o)
+                o += b - a
+            o, row0 = 0, 0
+            for r, m in enumerate(runs):
+                B, T = len(m), max(due[i][2] for i in m)
+                ids, lens = packed.data_ptr() + 8 * o, packed.data_ptr() + 8 * (o + B * T)
+                sid = packed[o + B * T + B:o + B * T + 2 * B] if net.n_speakers > 0 else None
+                o += B * T + (2 * B if net.n_speakers > 0 else B)
+                rows = (_capi.MbvEncRow * B)()
+                take = (_capi.MbvTakeRow * B)()
+                for j, i in enumerate(m):
+                    st, k, E = due[i]
+                    rows[j].length_scale, rows[j].noise_scale_w = st.length_scale, st.noise_scale_w
+                    rows[j].noise_w, rows[j].t_text = noise_w[i], E
+                    t = take[j]
+                    t.src, (t.a, t.b) = j, ranges[i]
+                    t.y_length = y_buf.data_ptr() + 8 * (row0 + j)
+                    t.stats, t.dur, t.stride = st.stats.data_ptr(), st.dur.data_ptr(), st.max_tokens
+                    t.dur_copy = dur_buf.data_ptr() + 4 * at[i]
+                net._launch(h, "mbv_encode_rows", r, C.c_void_p(ids), C.c_void_p(lens), sid, B, T, rows,
+                            C.c_void_p(y_buf.data_ptr() + 8 * row0), stream=hip_stream)
+                net._launch(h, "mbv_take_tokens_rows", r, take, B, stream=hip_stream)
+                row0 += B
+            host = dur_buf.tolist()                # the one host sync of the tick
+            expand, keep = [], []
+            for i, (st, k, E) in enumerate(due):
+                if st.failed:                      # an earlier block of this tick failed it
+                    continue
+                (a, b), d = ranges[i], host[at[i]:at[i] + ranges[i][1] - ranges[i][0]]
+                if min(d) < 0:
+                    st._fail(IndexError("infer_live: token block %d (tokens [%d, %d), encoded from %d tokens): index out of "
+                                        "range in self (a token id or the sid outside the model's tables, or a duration "
+                                        "outside the supported range)" % (k, a, b, E)))
+                elif st._plan.frames + sum(d) > st.max_frames:
+                    st._fail(ValueError("infer_live: token block %d (tokens [%d, %d)) ends at frame %d: beyond the stream's "
+                                        "max_frames = %d" % (k, a, b, st._plan.frames + sum(d), st.max_frames)))
+                else:
+                    row = _capi.MbvExpandRange()
+                    d_host = (C.c_int32 * len(d))(*d)
+                    keep.append(d_host)
+                    row.stats, row.dur, row.stride = st.stats.data_ptr(), st.dur.data_ptr(), st.max_tokens
+                    row.dur_host, row.a, row.b = C.addressof(d_host), a, b
+                    row.frame, row.max_frames = st._plan.frames, st.max_frames
+                    row.noise, row.noise_stride, row.noise_scale = st.noise.data_ptr(), st.noise.stride(1), st.noise_scale
+                    row.z_p, row.z_stride = st.z_p.data_ptr(), st.z_p.stride(1)
+                    expand.append(row)
+                    st._plan.encoded(k, d)
+                    if st._plan.complete and st._plan.frames < 1:
+                        st._fail(ValueError("infer_live: the text has no frames (every duration is 0)"))
+                failed = failed or st.failed
+            if expand:
+                net._launch(h, "mbv_expand_ranges", (_capi.MbvExpandRange * len(expand))(*expand), len(expand),
+                            stream=hip_stream)
+    todo = [(st, st._plan.flow_due()) for st in members if not st.failed]
+    todo = [(st, fd) for st, fd in todo if fd is not None]
+    if todo:
+        cfg_struct = todo[0][0]._cfg_struct
+        n = len(todo)
+        wl, out = (C.c_int32 * n)(), (C.c_int32 * 2)()
+        for i, (st, (a, b)) in enumerate(todo):
+            st._check_handle()
+            if L.mbv_flow_window(C.byref(cfg_struct), a, b - a, st._plan.frames, C.byref(out)):
+                raise _capi.MbvError("mbv_flow_window refused [%d, %d)" % (a, b))
+            wl[i] = int(out[1]) - int(out[0])
+        run_of = (C.c_int32 * n)()
+        n_runs = L.mbv_flow_ranges_plan(C.byref(cfg_struct), n, wl, run_of)
+        if n_runs < 1:
+            raise ValueError("mbv_flow_ranges_plan refused the windows (one beyond the fused WN layers?)")
+        for r in range(n_runs):
+            part = [t for t, q in zip(todo, run_of) if q == r]
+            rows = (_capi.MbvFlowRange * len(part))()
+            for row, (st, (a, b)) in zip(rows, part):
+                row.z_p, row.z_p_stride = st.z_p.data_ptr(), st.z_p.stride(1)
+                row.P, row.complete, row.sid = st._plan.frames, int(st._plan.complete), st.sid or 0
+                row.first, row.count, row.z, row.z_stride = a, b - a, st.z.data_ptr(), st.z.stride(1)
+            net._call("mbv_flow_ranges", rows, len(part))
+            for st, (a, b) in part:
+                st._plan.flowed(a, b)
+    return failed
+
+
+class TextStream:
+    """Synthesis of ONE utterance whose tokens are pushed as they arrive (`net.infer_live`): the text
+    mirror of `LiveStream`.
+
+    `push(ids)` appends tokens, `close()` ends the text, `poll()` runs one tick — the due token blocks through the text
+    encoder and the duration predictor as prefixes, their columns into the stream's token tables, length regulation
+    into the stream's own z_p, the reverse flows on the window that became computable, every chunk that became
+    decodable — and returns `[(first_sample, view), ...]`.  The ids, the token tables, the noise, z_p, z, o and g
+    belong to the stream, so other calls may run between any two polls.  The token statistics, the durations, z_p, z
+    and every sample are a function of (ids, sid, scales, seed / noise, block_tokens, `TextAhead`, chunk schedule)
+    only: not of the sizes of the pushes, of when `poll()` runs or of which streams share a `StreamPool`.  With
+    `TextAhead(tokens=None)` a finished stream of more than 256 frames is bitwise `infer_stream` on the whole text with
+    the same seed; bounded `tokens` is an approximation with an exact definition, and no claim about its quality is
+    made.  Not part of a text stream: per-token `length_scale` / `extra_frames` / `fit_frames` / `gain` / `pitch`,
+    `durations=`, `max_len`, a bounded flow look-ahead, and the wire layer (`PcmPool`, `stream_pcm16`)."""
+
+    def __init__(self, net, sid=None, max_tokens=None, max_frames=None, noise_scale=1, length_scale=1, noise_scale_w=1.,
+                 seed=None, noise=None, noise_w=None, block_tokens=16, ahead=None, chunk_frames=32, max_chunk_frames=256,
+                 flow_frames=32, model_sr=None):
+        from .models import _host_sid, _row_seeds
+        if seed is not None:
+            if noise is not None or noise_w is not None:
+                raise ValueError("infer_live: seed= and noise= / noise_w= exclude each other")
+            seed = _row_seeds(seed, 1, "infer_live: seed")[0][0]
+        for name, v in (("max_tokens", max_tokens), ("max_frames", max_frames)):
+            if v is None or isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError("infer_live: %s must be an integer >= 1 (the stream's buffers are allocated once)" % name)
+        self.max_tokens, self.max_frames = int(max_tokens), int(max_frames)
+        scales = []
+        for name, v in (("noise_scale", noise_scale), ("length_scale", length_scale), ("noise_scale_w", noise_scale_w)):
+            if torch.is_tensor(v) or isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("infer_live: %s must be one number (per-token controls are not part of a text stream)" % name)
+            if not math.isfinite(v) or v < 0:
+                raise ValueError("infer_live: %s must be finite and >= 0" % name)
+            scales.append(float(v))
+        self.noise_scale, self.length_scale, self.noise_scale_w = scales
+        sid = _host_sid(sid)
+        if net.n_speakers > 0:
+            if sid is None:
+                raise ValueError("sid is required for a multi-speaker model (models.py:704-705)")
+            if torch.is_tensor(sid):
+                if sid.numel() != 1:
+                    raise ValueError("infer_live: sid must be one speaker id")
+                sid = sid.reshape(()).item()
+            if isinstance(sid, bool) or int(sid) != sid:
+                raise TypeError("infer_live: sid must be an integer")
+            sid = int(sid)
+            if not (0 <= sid < net.n_speakers or net._voice_defined(sid)):
+                raise IndexError("index out of range in self (sid %d outside [0, %d))" % (sid, net.n_speakers))
+        else:
+            sid = None
+        self.sid = sid
+        h = net._handle_not_bf16("infer_live", "synthesise with infer_stream", why="")
+        cfg = net._config_struct()
+        self.spf = net.cfg.samples_per_frame
+        self._plan = TextPlan(block_tokens, text_context(cfg)[1], decoder_context(cfg)[1], chunk_frames, max_chunk_frames,
+                              flow_frames, ahead=ahead, model_sr=model_sr, samples_per_frame=self.spf)
+        self.ahead, self.seam = self._plan.ahead, self._plan.seam
+        self._cfg_struct = cfg
+        self.chunk_frames, self.max_chunk_frames = int(chunk_frames), int(max_chunk_frames)
+        self._net, self._h = net, h
+        dev = net._device()
+        I, F, N = net.cfg.inter_channels, self.max_frames, self.max_tokens
+        with torch.cuda.device(dev), torch.no_grad():
+            if seed is not None:
+                # the capacity buffers, once, as one block each: element (c, t) does not depend on F / N (DESIGN 7.13)
+                self.noise = net.randn(seed, I, F, purpose=_capi.NOISE_PRIOR).unsqueeze(0)
+            elif noise is None:
+                self.noise = torch.randn(1, I, F, device=dev, dtype=torch.float32)
+            else:
+                if not torch.is_tensor(noise) or noise.dtype != torch.float32 or tuple(noise.shape) != (1, I, F):
+                    raise ValueError("infer_live: noise must be a float32 tensor [1, %d, %d] (inter_channels, max_frames)"
+                                     % (I, F))
+                self.noise = noise.to(dev).contiguous()
+            self.noise_w = None
+            if net.cfg.use_sdp:
+                if seed is not None:
+                    self.noise_w = net.randn(seed, 2, N, purpose=_capi.NOISE_SDP)
+                elif noise_w is None:
+                    self.noise_w = torch.randn(2, N).to(dev)       # the CPU generator, as the reference's SDP draw
+                else:
+                    if not torch.is_tensor(noise_w) or noise_w.dtype != torch.float32 or tuple(noise_w.shape) != (2, N):
+                        raise ValueError("infer_live: noise_w must be a float32 tensor [2, %d] (max_tokens)" % N)
+                    self.noise_w = noise_w.to(dev).contiguous()
+            self.stats = torch.zeros(2 * I, N, device=dev, dtype=torch.float32)      # m_p | logs_p of every token
+            self.dur = torch.zeros(N, device=dev, dtype=torch.int32)
+            self.z_p = torch.zeros(1, I, F, device=dev, dtype=torch.float32)
+            self.z = torch.zeros(1, I, F, device=dev, dtype=torch.float32)
+            self.o = torch.empty(1, 1, self.spf * F, device=dev, dtype=torch.float32)
+            self.g = None
+            if sid is not None:
+                self.g = net._speaker_embedding(torch.tensor([sid], dtype=torch.int64, device=dev))
+            self._stash = torch.zeros(self.seam, device=dev, dtype=torch.float32) if self.seam else None
+        self._stashed = 0
+        self._ids = []                # the tokens pushed so far, host ints
+        self.y_lengths = None
+        self._error = None
+        self._chunks, self._next, self._decoded = [], 0, 0
+        if sid is not None:
+            net._hold_voices(self, sid)
+
+    def __repr__(self):
+        return "TextStream(%d of %d tokens%s, %d frames)" % (len(self._ids), self.max_tokens,
+                                                             ", closed" if self._plan.closed else "", self._plan.frames)
+
+    # ---- the text
+    @property
+    def tokens(self):
+        """Tokens pushed so far."""
+        return len(self._ids)
+
+    @property
+    def closed(self):
+        return self._plan.closed
+
+    @property
+    def plan(self):
+        """The stream's `TextPlan` (integers only)."""
+        return self._plan
+
+    @property
+    def durations(self):
+        """Frames of every token of the encoded blocks (host ints)."""
+        return list(self._plan.durations)
+
+    @property
+    def marks(self):
+        """The z-frame at which every encoded token starts, then the frames so far: once finished, what
+        `infer_stream(marks=True)` calls `marks`."""
+        return list(self._plan.marks)
+
+    @property
+    def frames(self):
+        """T, once the text is closed and every block is encoded (None before)."""
+        return self._plan.total
+
+    @property
+    def z_frames(self):
+        """z frames flowed so far: z[:, :, :z_frames] is final."""
+        return self._plan.z_done
+
+    @property
+    def chunks(self):
+        return tuple(self._chunks)
+
+    @property
+    def failed(self):
+        return self._error is not None
+
+    @property
+    def finished(self):
+        return self.failed or (self._plan.all_released and self._next >= self._decoded)
+
+    def push(self, ids):
+        """Appends tokens: ints, a sequence of ints or a 1-D int64 tensor."""
+        if torch.is_tensor(ids):
+            if ids.dtype != torch.int64 or ids.dim() != 1:
+                raise TypeError("push takes ints or a 1-D int64 tensor of token ids")
+            ids = ids.tolist()
+        elif isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+            ids = [int(ids)]
+        else:
+            ids = list(ids)
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in ids):
+                raise TypeError("push takes ints or a 1-D int64 tensor of token ids")
+            ids = [int(v) for v in ids]
+        if self._plan.closed:
+            raise ValueError("push after close()")
+        if len(self._ids) + len(ids) > self.max_tokens:
+            raise ValueError("push: %d + %d tokens exceed the stream's capacity of %d (max_tokens)"
+                             % (len(self._ids), len(ids), self.max_tokens))
+        if any(not -(1 << 63) <= v < 1 << 63 for v in ids):
+            raise ValueError("push: a token id outside int64")
+        self._ids += ids
+        self._plan.push(len(ids))
+
+    def close(self):
+        self._plan.close()
+        if self._plan.complete and self._plan.frames < 1 and not self.failed:
+            self._fail(ValueError("infer_live: the text has no frames (every duration is 0)"))
+
+    # ---- what a pool shares (StreamPool.step); poll() is the stand-alone form of the same steps
+    def _check_handle(self):
+        if self._net._handle is not self._h:
+            raise RuntimeError("the model's handle was re-created (device move) since this stream started")
+
+    def _fail(self, error):
+        self._error = error
+
+    def _due_blocks(self):
+        return []                     # (no audio to convert: the token blocks go through `_text_tick`)
+
+    def _fill_chunk(self, k, first, count):
+        """-> the route length, as a live recording's: the class an utterance of more than 256 frames is decoded in."""
+        t = self._plan.t_frames(first, count)      # (what is flowed; with `ahead.dec` the chunk's canonical D)
+        k.z, k.z_stride, k.t_frames = self.z.data_ptr(), self.z.stride(1), t
+        k.g = self.g.data_ptr() if self.g is not None else None
+        k.first, k.o = first, self.o.data_ptr()
+        k.count = count + self._plan.overhang(first, count)
+        return max(t, 257)
+
+    _fill_seam = LiveStream._fill_seam
+    _chunk_decoded = LiveStream._chunk_decoded
+
+    def _next_chunk(self):
+        return None if self.failed else self._plan.next_chunk()
+
+    def _drained(self):
+        return self.failed or self._plan.all_released
+
+    def poll(self):
+        """One tick for this stream alone (the order of `_text_tick`, then every chunk that became decodable: all of
+        them in one `mbv_decode_chunks_routed` call, under a seam one call and one `mbv_seam_rows` launch per chunk);
+        hands out every chunk not handed out yet: [(first_sample, view), ...].  Raises what failed the stream."""
+        if self._error is None:
+            _text_tick(self._net, [self])
+        if self._error is not None:
+            raise self._error
+        return _decode_and_hand_out(self)
+
+    def result(self):
+        """o[:, :, :spf T] of the finished stream."""
+        if self.failed:
+            raise self._error
         if not self.finished:
             raise RuntimeError("result(): the stream is not finished (close() it and poll() until `finished`)")
         return self.o[:, :, :self.spf * self._plan.total]
@@ -789,7 +1385,12 @@ class StreamPool:
 
     A `LiveStream` is a member like any other: `step()` first converts the pending windows of all live members in one
     `mbv_convert_ranges` run, then decodes at most one decodable chunk of each along with the others' chunks; a live
-    member with nothing decodable yet is skipped and stays, and its next `poll()` hands the pooled chunks out."""
+    member with nothing decodable yet is skipped and stays, and its next `poll()` hands the pooled chunks out.
+
+    A `TextStream` is a member too: `step()` runs the due token blocks of all text members through shared encoder
+    runs, one take launch per run, one read-back, one expand launch and the planned flow runs (`_text_tick`, DESIGN
+    §7.27), then decodes at most one chunk of each along with the others'.  A text member that fails (a flagged token
+    id, a block that does not fit `max_frames`) is dropped, the others are served; its own `poll()` raises."""
 
     def __init__(self, net):
         self._net = net
@@ -799,9 +1400,9 @@ class StreamPool:
         return len(self.streams)
 
     def add(self, st):
-        if not isinstance(st, (DecodeStream, LiveStream)):
-            raise TypeError("StreamPool.add takes a DecodeStream (net.dec_stream / net.infer_stream) or a LiveStream "
-                            "(net.convert_live)")
+        if not isinstance(st, (DecodeStream, LiveStream, TextStream)):
+            raise TypeError("StreamPool.add takes a DecodeStream (net.dec_stream / net.infer_stream), a LiveStream "
+                            "(net.convert_live) or a TextStream (net.infer_live)")
         if st.z.shape[0] != 1:
             raise ValueError("StreamPool takes streams of ONE utterance (this one has %d rows): a pooled chunk is bitwise "
                              "its utterance's stand-alone decode, and a row of a batch is measured against the batch's "
@@ -859,6 +1460,10 @@ class StreamPool:
             return []
         net = self._net
         self._convert_live(members)
+        if _text_tick(net, [st for st in members if isinstance(st, TextStream)]):
+            # a text stream that failed in this tick is dropped; the others are served
+            self.streams = [st for st in self.streams if not st._drained()]
+            members = [st for st in members if not st._drained()]
         work = []                     # (stream, first, count)
         for st in members:
             if net._handle is not st._h:

@@ -2,7 +2,8 @@
 synthetic rows, no model run: parity with the float64 restatement tests/warp_ref.py under the bar the resampler's tests
 use for the same kind of filter on unit-scale input (tests/test_gpu_resample.py: max abs <= 5e-6, RMS <= 1e-6), and the
 BITWISE relations: a row does not depend on how it is cut into ranges, on the rows that share its launch, on what lies
-behind the decoded frontier, and an envelope equals the pre-multiplied waveform."""
+behind the decoded frontier, and an envelope equals the pre-multiplied waveform.
+Parity proper (a per-element bar from the float64 reference, full-width tiles, long rows) is tests/test_gpu_warp_pin.py."""
 import functools
 
 import numpy as np
